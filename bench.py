@@ -8,7 +8,9 @@ One "step" = one pass of the hot path over one batch of synthetic frames already
   identify V118_3 forward + softmax for every crop, probabilities copied to the host
 Prints ONE JSON line on rank 0.
 
-    python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2                         (headline only: set up, warm up, time the steps)
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR      (+ the last timed step's outputs as DIR/<name>.npy)
+    python bench.py --full                                                 (+ detect roofline passes, CPU baseline, secondary runs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -66,10 +68,15 @@ def build_parser():
                     help="weak: --batch frames per GPU per step (default); strong: --batch frames per step in total, split between the GPUs")
     ap.add_argument("--force-all", action="store_true", help="run exactly the stages given on the command line instead of the preset of the named config")
     ap.add_argument("--guard-trip", action="store_true", help="secondary row C4_guard_tripped: conv1 of the random-init network is scaled until a handful of the step's crops leave the fp16-piece range, so that the per-crop range guard re-runs them with the bf16x6 kernels inside every timed step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the detect passes of their own behind the timed steps (detect roofline, stage timers of small batches), "
+                         "the CPU baseline, the secondary runs and the long records; a plain run sets up, warms up, times --steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step handed its caller (detect tables, ID table: header words, probabilities, midlines) to DIR/<name>.npy, float32 / float64, 64 MB at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short secondary runs (C2, C3, C5, host input, fp32, the N > 1 code path at N = 1, training step); their long records go to a '# bench_secondary:' line and gpurun_out/bench_secondary.json, one {value, frac} pair each to `configs` of the final line")
-    ap.add_argument("--secondary-only", default="", help="dev: comma-separated subset of the secondary runs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short secondary runs (C2, C3, C5, host input, fp32, the N > 1 code path at N = 1, training step); their long records go to a '# bench_secondary:' line and bench_secondary.json beside the detail record, one {value, frac} pair each to `configs` of the final line")
+    ap.add_argument("--secondary-only", default="", help="dev: comma-separated subset of the secondary runs (with --full)")
     return ap
 
 
@@ -129,6 +136,80 @@ def apply_presets(args):
     if args.normalize == "posture":
         args.with_posture = True
     return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def _float_fields(a, dtype, skip=("pad",)):
+    """structured table -> [n, scalar fields] in `dtype` (u16 fields are exact in float32, u32 / u64 moments and sums in float64)"""
+    import numpy as np
+    names = [f for f in a.dtype.names if a.dtype[f].shape == () and f not in skip]
+    return np.stack([a[f].astype(dtype) for f in names], axis=1) if len(a) else np.zeros((0, len(names)), dtype)
+
+
+def _ranges(begin, count):
+    """the indices begin[i] .. begin[i] + count[i] - 1, range after range"""
+    import numpy as np
+    count = count.astype(np.int64)
+    ends = np.cumsum(count)
+    return np.repeat(begin.astype(np.int64) - ends + count, count) + np.arange(int(ends[-1]) if len(ends) else 0)
+
+
+def dump_outputs(path, pipe, ln):
+    """--dump-outputs: what the timed path handed its caller in its last step (lane `ln` ran it) as path/<name>.npy, float32 / float64, every
+    value exact, in an order that does not change from run to run: the detect tables in the context's pinned host memory (frames, blobs,
+    runs, pixels); with posture the midlines (rows of blobs without one zeroed) and their scalars; with the network the ID table rank 0
+    received (header words as numbers, probabilities, with posture the normalised midline).  Above DUMP_BYTES in all, every array above its
+    share is cut to a fixed, seeded sample of rows, whose indices go to <name>_rows.npy."""
+    import numpy as np
+    from trex_amd import capi, dist as tdist
+    res, n = ln.res, ln.n
+    pc = int(res.pixel_channels) or 1
+    info = capi._from_addr(res.frames, res.n_frames, capi.INFO_DTYPE)
+    blobs = capi._from_addr(res.blobs, res.total_blobs, capi.BLOB_DTYPE)
+    runs = capi._from_addr(res.runs, res.total_runs, capi.RUN_DTYPE)
+    pixels = capi._from_addr(res.pixels, res.total_pixels * pc, np.dtype(np.uint8)).reshape(-1, pc)
+    # the kernels place the frames in the pooled tables at offsets taken with atomics, an order that changes from run to run: the tables
+    # are written frame by frame, as the caller reads them (trexhip_fetch's per-frame views, frames with an error flag empty), without
+    # the pooled offsets; the blobs' own run / pixel offsets are relative to their frame
+    ok = info["flags"] == 0
+    bidx = _ranges(info["blob_begin"][ok], info["n_blobs"][ok])
+    arrays = {"frames": _float_fields(info, np.float64, skip=("blob_begin", "run_begin", "pix_begin")),
+              "blobs": _float_fields(blobs[bidx], np.float64),
+              "runs": _float_fields(runs[_ranges(info["run_begin"][ok], info["n_runs"][ok])], np.float32),
+              "pixels": pixels[_ranges(info["pix_begin"][ok], info["n_pixels"][ok])].astype(np.float32)}
+    if pipe.with_posture:                               # (one row per pooled blob: reordered like the blobs)
+        minfo = ln.p_minfo[:n].cpu().numpy().view(capi.MIDLINE_INFO_DTYPE)[:, 0][bidx]
+        mid = ln.p_mid[:n].flatten(1).cpu().numpy()[bidx]
+        mid[minfo["status"] != 0] = 0.0                 # (written only for blobs with a midline)
+        arrays["midline"] = mid
+        arrays["midline_info"] = _float_fields(minfo, np.float64)
+    if pipe.with_cnn and ln.table_host is not None:
+        t = ln.table_host.numpy()
+        t = t[t[:, 7] != 0]                             # valid rows (all ranks' when gathered), in pooled order
+        t = t[np.argsort(t[:, 0].view(np.uint32), kind="stable")]      # by global frame index: frame by frame, blob order within a frame
+        hdr = tdist.HDR_EX if pipe.with_posture else tdist.HDR
+        words = t[:, :hdr].view(np.uint32).astype(np.float64)
+        f32 = t[:, :hdr].view(np.float32)
+        fcols = [5, 6] + (list(range(8, 15)) if pipe.with_posture else [])     # centroid; moments, midline len / angle / offset
+        words[:, fcols] = f32[:, fcols]
+        if pipe.with_posture:
+            words[:, 15] = t[:, 15]                     # midline status (-1: none handed in)
+        arrays["id_header"] = words
+        arrays["probs"] = t[:, hdr:hdr + pipe.classes].view(np.float32)
+        if pipe.with_posture:
+            arrays["id_midline"] = t[:, hdr + pipe.classes:].view(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    share = DUMP_BYTES // (2 * len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BYTES and a.nbytes > share:
+            row = a.nbytes // len(a)
+            rows = np.sort(np.random.default_rng(0).choice(len(a), share // (row + 8), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def measure(args, env):
@@ -284,7 +365,11 @@ def measure(args, env):
     dt_own = time.perf_counter() - t0          # this rank's own K steps, before it waits for the others
     barrier()
     dt = time.perf_counter() - t0
-    if not timers_in_region:
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, pipe, lanes[(args.steps - 1) % len(lanes)])
+    # everything below that runs passes of its own (stage timers of small batches, the serial and pipelined detect passes, the CPU
+    # baseline) belongs to --full; a plain run reports what the timed region itself measured
+    if not timers_in_region and args.full:
         for ln in lanes:
             ln.seg.profile_enable(True)
             ln.seg.profile_reset()
@@ -328,7 +413,7 @@ def measure(args, env):
         prof[name] = (ms, cnt)
     # the detect stage overlaps the identity network of the previous batch when two lanes are pipelined, so its in-flight
     # HIP-event durations include time lost to sharing the CUs; its roofline is taken from a short serial pass afterwards
-    if len(lanes) > 1:
+    if len(lanes) > 1 and args.full:
         ln0 = lanes[0]
         ln0.seg.profile_reset()
         for _ in range(5):
@@ -341,7 +426,7 @@ def measure(args, env):
     # ... and as the pipeline runs it: the lanes' contexts issue alternate detect passes on their own streams, so the labelling / gather of one
     # batch (latency chains, one workgroup per frame) run under the pixel pass of the next; wall clock over 2 x 10 passes, nothing else on the GPU
     pipe_detect_s = None
-    if len(lanes) > 1 and not host_in:
+    if len(lanes) > 1 and not host_in and args.full:
         for ln in lanes[:2]:
             ln.detect(frames_ptr)
         torch.cuda.synchronize()
@@ -429,6 +514,8 @@ def measure(args, env):
                 "timing": "HIP events on the kernel stream; 5 serial detect passes after the timed region when lanes are pipelined (in-flight the stage shares the GPU with the identity network)",
                 "limiter": "read-only HBM streaming + VALU: the same kernel with the masks replaced by a trivial compare takes 187-200 us (a plain grid-stride streaming read of the same 1.07 GB: 167 us = 6.4 TB/s, tools/bw_probe.hip; torch's fastest read-only reduction: 183 us); exact masks and run extraction add the rest. A/B on one box (tools/rows_exp.sh): k_rows32 generic 250 us, + compile-time threshold modes 242, background row in registers for 8 frames (k_rows32b) 235, both 220, rows fastest 215. k_ccl_lds / k_gather are latency chains of one workgroup per frame / half a wave per blob",
                 "frac_of_measured_copy_bw": ((rows_traffic or seg_bytes) / rows_s / 6.29e12) if rows_s else None}
+    if len(lanes) > 1 and not args.full:
+        seg_roof["timing"] = "HIP events on the kernel stream inside the timed region, in flight beside the other lane's work (the serial passes run with --full)"
     if host_in:
         bytes_step = float(B * W * H * (4 if bgra_in else 1))
         up = [ln.seg.profile_read(capi.STAGE_UPLOAD_COPY) + ln.seg.profile_read(capi.STAGE_UPLOAD_DMA) for ln in lanes]
@@ -507,8 +594,12 @@ def measure(args, env):
         out["roofline_detect"] = seg_roof
     else:
         out["roofline"] = seg_roof
+    if not (timers_in_region or args.full):
+        # the stage timers were off in the timed region and a plain run times no pass of its own: no stage times, no roofline
+        for k in ("roofline", "roofline_kernels", "roofline_detect", "stage_us"):
+            out.pop(k, None)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the CPU restatement (oracle/: a port, not the TRex binary) on this box's host cores, on a bounded sample of the same workload:
         # all usable cores (one frame per OpenMP thread / torch intra-op threads) and ONE thread; medians over the repetitions
         from oracle import oracle, cnn_oracle
@@ -655,7 +746,7 @@ def secondary(args, env):
         a = copy.copy(base)
         for k, v in over.items():
             setattr(a, k, v)
-        a.steps, a.warmup, a.no_cpu_baseline, a.no_secondary = steps, warmup, True, True
+        a.steps, a.warmup, a.no_cpu_baseline, a.no_secondary, a.full = steps, warmup, True, True, True
         apply_presets(a)
         try:
             r = measure(a, env)
@@ -734,11 +825,12 @@ def compact_line(out, sec):
                                                           "blobs_per_step_rank0", "parallelism", "gather"))}
     o["config"]["input"] = c["input"][:60]
     roof_keys = ("bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us", "launches", "mfma_issue_frac")
-    r = out["roofline"]
-    o["roofline"] = {"kernel": r["kernel"].split(" ")[0], **_pick(r, roof_keys)}
-    if o["roofline"].get("traffic") is not None:      # the counters cannot be read from inside this process: the bytes are the committed PMC passes of this same command
-        o["roofline"]["traffic_source"] = "profiles/rNN_pmc_summary.json (separate --pmc passes of this command; not measured in this run)"
-    o["roofline"]["frac"] = o["roofline"]["achieved"] / o["roofline"]["peak"] if o["roofline"]["peak"] else 0.0    # consistent with the rounded `achieved`
+    r = out.get("roofline") or {}       # (absent from a plain run whose stage timers were off)
+    if r:
+        o["roofline"] = {"kernel": r["kernel"].split(" ")[0], **_pick(r, roof_keys)}
+        if o["roofline"].get("traffic") is not None:      # the counters cannot be read from inside this process: the bytes are the committed PMC passes of this same command
+            o["roofline"]["traffic_source"] = "profiles/rNN_pmc_summary.json (separate --pmc passes of this command; not measured in this run)"
+        o["roofline"]["frac"] = o["roofline"]["achieved"] / o["roofline"]["peak"] if o["roofline"]["peak"] else 0.0    # consistent with the rounded `achieved`
     if "roofline_kernels" in out:
         o["roofline_kernels"] = {k: {"kernel": v["kernel"].split(" ")[0], **_pick(v, ("achieved", "frac", "traffic", "avg_launch_us"))} for k, v in out["roofline_kernels"].items()}
     det_keys = ("achieved", "peak", "frac", "traffic", "avg_launch_us", "frac_algorithmic_bytes", "whole_detect_pass_us", "whole_detect_pass_frac",
@@ -852,7 +944,7 @@ def main():
     env = {"world": world, "rank": rank, "local": local, "use_dist": use_dist, "dev": dev}
     out = measure(args, env)
     sec = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         sec = secondary(args, env)
     if dist.is_initialized():
         sys.stdout.flush()
@@ -868,9 +960,10 @@ def main():
     except Exception:
         pass
     if rank == 0:
-        emit_detail("bench_detail", out)
-        if sec is not None:
-            emit_detail("bench_secondary", sec)
+        if args.full:
+            emit_detail("bench_detail", out)
+            if sec is not None:
+                emit_detail("bench_secondary", sec)
         print(fit_line(compact_line(out, sec)), flush=True)
 
 

@@ -9,10 +9,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(*extra):
-    if "--secondary-only" not in extra:
+def run(*extra, full=True):
+    if full and "--secondary-only" not in extra:
         extra = (*extra, "--no-secondary")          # (the secondary runs use their own, full-size shapes: only the test of them pays for that)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "16", *extra],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "16", *extra, *(["--full"] if full else [])],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.strip()]
@@ -105,7 +105,7 @@ def test_final_line_is_short_and_the_long_records_come_before_it():
 
 def test_full_default_line_fits_the_drivers_tail():
     # the driver's own command shape (all secondary runs, cpu baseline) at a small batch: the final line stays under 4 KB
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--full"],
                          capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     last = out.stdout.strip().splitlines()[-1]
@@ -135,7 +135,7 @@ def test_eight_rank_weak_launch_on_one_gpu_covers_every_frame_once():
     # the driver's N = 8 line (weak scaling: B frames per rank and step) with every rank on GPU 0: the gather moves 7 tables to rank 0 per step,
     # rank 0's merged table holds the step's 8 x B frames exactly once in Tracker::add order, and the N > 1 line is short and complete
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "4", "--same-gpu",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200, cwd=ROOT,
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=1200, cwd=ROOT,
                          env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     if out.returncode != 0 and ("Duplicate GPU" in out.stderr or "No socket interfaces" in out.stderr):
         pytest.skip("RCCL cannot run several ranks on one GPU here")
@@ -150,3 +150,25 @@ def test_eight_rank_weak_launch_on_one_gpu_covers_every_frame_once():
     assert m["frames"] == m["frames_expected"] == 8 * 4 and m["every_frame_once"] and m["tracker_order"] and m["rows"] == 8 * 4 * 100
     assert "roofline" in j and j["roofline"]["bound"] == "mfma"
     assert abs(j["value"] - 8 * 4 * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 1e-4      # whole-job frames / the slowest rank's time
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    # without --full: set up, warm up, time the steps, print the line -- no CPU baseline, no secondary runs, no long records; with
+    # --dump-outputs the last timed step's outputs, identical from run to run with the same arguments
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        j = run("--dump-outputs", str(d), full=False)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in j, k
+        assert j["steps"] == 2 and j["warmup"] == 1 and "cpu_baseline" not in j and "configs" not in j and not run.detail
+        assert abs(j["value"] - 16 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-4
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and {"frames.npy", "blobs.npy", "runs.npy", "pixels.npy", "id_header.npy", "probs.npy"} <= set(names)
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in names) <= 64 << 20
+    for f in names:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    probs = np.load(os.path.join(dirs[0], "probs.npy"))
+    assert len(probs) == j["config"]["blobs_per_step_rank0"] == len(np.load(os.path.join(dirs[0], "blobs.npy")))
+    assert np.allclose(probs.sum(1), 1.0, atol=1e-5)

@@ -3,14 +3,17 @@
     unmodified (oracle/ref.mk -> oracle/_ref/libminilzo.so): lzo1x_decompress must give every input back byte for byte (pv.cpp:316-340 is how
     stock TRex reads a compressed frame);
   * the oracle's decoder restatement (oracle/trex_pv.c) against the reference's encoder lzo1x_1_compress and decoder on the same inputs;
+    both through the streams recorded with the reference's minilzo in tests/golden/lzo1x_streams.npz (tests/golden/make_lzo_fixture.py),
+    and live where that library is built;
   * trexhip_pv_write_frames: the rule of pv.cpp:705-772 (>= 15000 bytes, kept if smaller), flag / sizes / stream layout, index table.
 GPU (-m gpu): device packer -> host data section -> restated reader returns the segmentation of every frame."""
+import os
 import numpy as np
 import pytest
 from oracle import oracle, lzo_ref
 from trex_amd import capi, synth
 
-needs_ref = pytest.mark.skipif(not lzo_ref.available(), reason="oracle/_ref/libminilzo.so not built (needs /root/reference)")
+LZO_FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lzo1x_streams.npz")
 
 
 def corpus():
@@ -31,24 +34,38 @@ def corpus():
     return out
 
 
-@needs_ref
 def test_our_streams_through_the_reference_decoder():
+    # the recorded streams of this encoder went through the reference's lzo1x_decompress byte for byte when they were recorded: the
+    # encoder must still write exactly them (and, where the reference's minilzo is built, they go through its decoder here too)
+    fx = np.load(LZO_FIX)
+    live = lzo_ref.available()
     tot_in = tot_ours = tot_ref = 0
-    for data in corpus():
+    data_all = corpus()
+    assert list(fx["sizes"]) == [len(d) for d in data_all]
+    for i, data in enumerate(data_all):
         c = capi.lzo1x_compress(data)
         assert len(c) <= len(data) + len(data) // 16 + 64 + 3
-        assert bytes(lzo_ref.decompress(c, len(data))) == data, len(data)
-        tot_in += len(data); tot_ours += len(c); tot_ref += len(lzo_ref.compress(data))
+        assert bytes(c) == fx["ours_%d" % i].tobytes(), len(data)
+        if live:
+            assert bytes(lzo_ref.decompress(c, len(data))) == data, len(data)
+        tot_in += len(data); tot_ours += len(c); tot_ref += len(fx["ref_%d" % i])
     print("LZO1X: %d bytes in, ours %d, lzo1x_1_compress %d" % (tot_in, tot_ours, tot_ref))
     assert tot_ours <= 1.15 * tot_ref                    # not byte-identical to minilzo, but in the same class
 
 
-@needs_ref
 def test_the_decoder_restatement_equals_the_reference_decoder():
-    for data in corpus():
-        for c in (lzo_ref.compress(data), capi.lzo1x_compress(data)):
+    # the reference encoder's recorded streams (and, where its minilzo is built, its live output and decoder) through the restated decoder
+    fx = np.load(LZO_FIX)
+    live = lzo_ref.available()
+    for i, data in enumerate(corpus()):
+        ref = fx["ref_%d" % i].tobytes()
+        if live:
+            assert bytes(lzo_ref.compress(data)) == ref, len(data)
+        for c in (ref, capi.lzo1x_compress(data)):
             got = oracle.lzo1x_decompress(c, len(data))
-            assert got is not None and bytes(got) == data and bytes(lzo_ref.decompress(c, len(data))) == data
+            assert got is not None and bytes(got) == data
+            if live:
+                assert bytes(lzo_ref.decompress(c, len(data))) == data
     # malformed streams are refused, not read out of bounds
     c = capi.lzo1x_compress(bytes(range(200)) * 20)
     assert oracle.lzo1x_decompress(c[:-1], 4000) is None and oracle.lzo1x_decompress(c, 100) is None

@@ -1,6 +1,6 @@
 mkdir -p gpurun_out/r02
 O=gpurun_out/r02/sweep.txt; : > $O
-run(){ echo "### $*" >> $O; timeout 300 python bench.py --no-cpu-baseline "$@" 2>/dev/null | grep '^{"metric"' >> $O; }
+run(){ echo "### $*" >> $O; timeout 300 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | grep '^{"metric"' >> $O; }
 run --steps 10 --warmup 3
 run --steps 10 --warmup 3 --normalize posture
 run --steps 10 --warmup 3 --encoding rgb8

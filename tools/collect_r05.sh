@@ -11,7 +11,7 @@ bash $ROOT/tools/pmc_kernel.sh "k_conv12_rs|k_conv12_wpre|k_conv5_wp" "" "SQ_VAL
      "SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_INSTS_SALU SQ_INSTS_SMEM" "FETCH_SIZE" "WRITE_SIZE" > "$OUT/r05_pmc_conv.txt" 2>&1
 bash $ROOT/tools/pmc_kernel.sh "k_rows32|k_ccl_lds|k_gather" "--stages segment" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "FETCH_SIZE" "WRITE_SIZE" > "$OUT/r05_pmc_detect_kernels.txt" 2>&1
 cd $ROOT
-timeout 900 python bench.py 2>/dev/null > "$OUT/r05_bench_stdout.txt"; tail -1 "$OUT/r05_bench_stdout.txt" > "$OUT/r05_bench_c4.json"
+timeout 900 python bench.py --full 2>/dev/null > "$OUT/r05_bench_stdout.txt"; tail -1 "$OUT/r05_bench_stdout.txt" > "$OUT/r05_bench_c4.json"
 cp gpurun_out/bench_detail.json "$OUT/r05_bench_detail.json" 2>/dev/null; cp gpurun_out/bench_secondary.json "$OUT/r05_bench_secondary.json" 2>/dev/null
 timeout 400 bash tools/prof_train.sh r05 > /dev/null 2>&1
 # k_posture & co at C3 (25600 blobs per launch): per-call durations

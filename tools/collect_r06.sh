@@ -17,7 +17,7 @@ done
 python $ROOT/tools/pmc_detect_json.py "$OUT/r06_pmc_detect_configs.txt" > "$OUT/r06_pmc_detect_configs.json"
 cd $ROOT
 bash tools/r06_batch1_timeline.sh 2 > "$OUT/r06_batch1_timeline.txt" 2>&1
-timeout 900 python bench.py 2>/dev/null > "$OUT/r06_bench_stdout.txt"; tail -1 "$OUT/r06_bench_stdout.txt" > "$OUT/r06_bench_c4.json"
+timeout 900 python bench.py --full 2>/dev/null > "$OUT/r06_bench_stdout.txt"; tail -1 "$OUT/r06_bench_stdout.txt" > "$OUT/r06_bench_c4.json"
 cp gpurun_out/bench_detail.json "$OUT/r06_bench_detail.json" 2>/dev/null; cp gpurun_out/bench_secondary.json "$OUT/r06_bench_secondary.json" 2>/dev/null
 timeout 400 bash tools/prof_train.sh r06 > /dev/null 2>&1
 ls -la "$OUT" | tail -30

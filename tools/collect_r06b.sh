@@ -13,7 +13,7 @@ cp "$OUT/r06_pmc_detect_configs.json" $ROOT/profiles/r06_pmc_detect_configs.json
 cd $ROOT
 timeout 1200 bash tools/collect_profiles.sh r06 > "$OUT/r06_collect.log" 2>&1
 cp "$OUT/r06_pmc_summary.json" $ROOT/profiles/r06_pmc_summary.json
-timeout 900 python bench.py 2>/dev/null > "$OUT/r06_bench_stdout.txt"; tail -1 "$OUT/r06_bench_stdout.txt" > "$OUT/r06_bench_c4.json"
+timeout 900 python bench.py --full 2>/dev/null > "$OUT/r06_bench_stdout.txt"; tail -1 "$OUT/r06_bench_stdout.txt" > "$OUT/r06_bench_c4.json"
 cp gpurun_out/bench_detail.json "$OUT/r06_bench_detail.json" 2>/dev/null; cp gpurun_out/bench_secondary.json "$OUT/r06_bench_secondary.json" 2>/dev/null
 bash tools/r06_batch1_timeline.sh 2 > "$OUT/r06_batch1_timeline.txt" 2>&1
 python -c "import __graft_entry__ as e; e.smoke()" > "$OUT/r06_smoke.txt" 2>&1; tail -1 "$OUT/r06_smoke.txt"

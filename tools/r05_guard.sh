@@ -3,7 +3,7 @@
 mkdir -p gpurun_out; O=gpurun_out/r05_guard.txt; : > $O
 for i in 1 2 3; do
   python bench.py --no-cpu-baseline --no-secondary --steps 20 2>&1 | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('plain  ', j['value'], j['ms_per_step'])" | tee -a $O
-  python bench.py --no-cpu-baseline --no-secondary --steps 20 --guard-trip 2>&1 | grep "^# bench_detail" | python -c "
+  python bench.py --full --no-cpu-baseline --no-secondary --steps 20 --guard-trip 2>&1 | grep "^# bench_detail" | python -c "
 import sys,json
 l=sys.stdin.read(); j=json.loads(l.split(':',1)[1]); print('tripped', j['value'], j['ms_per_step'], j.get('range_guard'))" | tee -a $O
 done
