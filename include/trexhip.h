@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 6
+#define TREXHIP_ABI_VERSION 7
 
 enum {
     TREXHIP_OK = 0,
@@ -396,10 +396,16 @@ int trexhip_crops_posture_device(trexhip_ctx* ctx, uint8_t* d_crops, int32_t n_b
 /* ---- identity network (V118_3) -------------------------------------------------------------
  * VINetwork::load_weights (ml/VisualIdentification.cpp) / visual_recognition_torch.py:841-921: takes the
  * flat fp32 blob described in trex_amd/weights.py (state_dict order; tools/convert_weights.py makes it
- * from a TRex <base>_dict.pth).  BatchNorm is folded and the tensors repacked on load. */
+ * from a TRex <base>_dict.pth).  BatchNorm is folded and the tensors repacked on load.  The blob's header carries the network's
+ * individual_image_size W x H: any 8 <= W, H <= 256 (square or not; TREXHIP_E_UNSUPPORTED outside), crops are then [n][H][W][C].
+ * 80 x 80 runs the tuned chain, every other size a generic one (conv1 exact fp32, conv2 / conv3 in the precision mode below, fc1 exact
+ * fp32).  The crop kernels (trexhip_crops*_device) need W * H * C to be a multiple of 16 bytes; other sizes (e.g. 50 x 50 gray) take
+ * crops made on the host through trexhip_identify.  Loading another size on the same context replaces the network. */
 int trexhip_load_weights(trexhip_ctx* ctx, const void* blob, size_t bytes);
 int trexhip_num_classes(trexhip_ctx* ctx);
 int trexhip_network_channels(trexhip_ctx* ctx);   /* channels of the crops the loaded network expects (1 or 3); 0 without weights */
+/* the crop size W x H the loaded network expects; 0 x 0 without weights.  Either pointer may be NULL. */
+int trexhip_network_image_size(trexhip_ctx* ctx, int32_t* width, int32_t* height);
 /* arithmetic of conv1..fc1.  All modes but BF16X3 meet the 1e-4 softmax bar against the fp32 reference network:
  *   TREXHIP_CNN_FP16X3 (default): every fp32 operand as two fp16 pieces (22 mantissa bits), 3 piece products per product on the
  *       fp16 matrix cores, fp32 accumulate; an activation outside the fp16 range raises a device flag and the layer stack is
@@ -409,8 +415,8 @@ int trexhip_network_channels(trexhip_ctx* ctx);   /* channels of the crops the l
 enum { TREXHIP_CNN_FP32 = 0, TREXHIP_CNN_BF16X6 = 1, TREXHIP_CNN_BF16X3 = 2, TREXHIP_CNN_FP16X3 = 3 };
 int trexhip_set_identity_precision(trexhip_ctx* ctx, int32_t mode);
 /* VINetwork::probabilities (ml/VisualIdentification.cpp:440-458) -> predict_numpy
- * (visual_recognition_torch.py:290-352): crops are uint8 NHWC [n][80][80][C] (values 0..255, no
- * scaling), probs is [n][classes] float32 softmax rows.  d_logits may be NULL. */
+ * (visual_recognition_torch.py:290-352): crops are uint8 NHWC [n][H][W][C] of the loaded network (trexhip_network_image_size,
+ * trexhip_network_channels; values 0..255, no scaling), probs is [n][classes] float32 softmax rows.  d_logits may be NULL. */
 int trexhip_identify_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n, float* d_probs, float* d_logits);
 int trexhip_identify(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, float* probs);
 /* What the fp16 range guard of the LAST identify call on this context did (waits for the context's stream): *rerun_crops = crops
@@ -484,7 +490,8 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  * reference: the data loader with its augmentation (:158-188, :1325-1336), epochs, validation, ReduceLROnPlateau (-> set_lr) and
  * early stopping (:1160-1283).
  *   trexhip_trainer_create     weights = the blob of trexhip_load_weights (state_dict order, running statistics included); the
- *                              trainer keeps parameters, gradients and Adam moments in HBM
+ *                              trainer keeps parameters, gradients and Adam moments in HBM.  Training runs at 80 x 80 only: a blob
+ *                              of any other individual_image_size is refused with TREXHIP_E_UNSUPPORTED
  *   trexhip_train_step_device  d_inputs [n][80][80][channels] float32 in [0, 255] (NHWC, what TRexImageDataset yields), d_targets
  *                              [n] class indices.  d_keep_masks: null = the library draws the dropout masks (counter-based hash of
  *                              seed, step, index); else n*16 + n*64 + n*128 + n*100 bytes, 1 = keep: the masks of Dropout2d after

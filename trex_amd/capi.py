@@ -110,7 +110,7 @@ class TrainParams(C.Structure):
 
 
 SYMBOLS = [
-    "trexhip_abi_version", "trexhip_network_channels", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
+    "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
@@ -173,6 +173,7 @@ def lib():
         L.trexhip_load_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.trexhip_num_classes.argtypes = [C.c_void_p]
         L.trexhip_network_channels.argtypes = [C.c_void_p]
+        L.trexhip_network_image_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.trexhip_pack_frames_v6_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.trexhip_lzo1x_bound.argtypes = [C.c_size_t]; L.trexhip_lzo1x_bound.restype = C.c_size_t
         L.trexhip_lzo1x_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -488,9 +489,20 @@ class Segmenter:
     def num_classes(self):
         return lib().trexhip_num_classes(self._h)
 
+    def network_image_size(self):
+        """(width, height) of the crops the loaded network expects; (0, 0) without weights."""
+        w, h = C.c_int32(0), C.c_int32(0)
+        _check(lib().trexhip_network_image_size(self._h, C.byref(w), C.byref(h)))
+        return int(w.value), int(h.value)
+
     def probabilities(self, crops):
-        """crops: uint8 ndarray (n,80,80,C) on the host -> float32 (n,classes) softmax rows."""
+        """crops: uint8 ndarray (n,H,W,C) on the host, the loaded network's size and channels -> float32 (n,classes) softmax rows."""
         crops = np.ascontiguousarray(crops, np.uint8)
+        w, h = self.network_image_size()
+        if w:                                   # (without weights the library reports that itself)
+            want = (h, w, lib().trexhip_network_channels(self._h))
+            if crops.ndim != 4 or tuple(crops.shape[1:]) != want:
+                raise ValueError(f"crops must have shape (n, {want[0]}, {want[1]}, {want[2]}) for the loaded network, got {crops.shape}")
         n = crops.shape[0]
         out = np.empty((n, self.num_classes()), np.float32)
         _check(lib().trexhip_identify(self._h, crops.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))

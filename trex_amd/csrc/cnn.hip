@@ -1657,7 +1657,11 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     std::memcpy(hdr, blob, 32);
     if (hdr[0] != 0x57585254 || hdr[1] != 1) { set_error("trexhip_load_weights: bad magic/version"); return TREXHIP_E_INVALID; }
     const int classes = hdr[2], W = hdr[3], H = hdr[4], CH = hdr[5];
-    if (W != 80 || H != 80) { set_error("trexhip_load_weights: only individual_image_size 80x80 is supported"); return TREXHIP_E_UNSUPPORTED; }
+    if (W < 8 || W > 256 || H < 8 || H > 256) {
+        set_error("trexhip_load_weights: individual_image_size " + std::to_string(W) + "x" + std::to_string(H) + " is outside 8..256 x 8..256");
+        return TREXHIP_E_UNSUPPORTED;
+    }
+    const bool at80 = W == 80 && H == 80;      // the tuned chain of this file; every other size runs the generic one of cnn_any.hip
     if (CH != 1 && CH != 3) { set_error("trexhip_load_weights: channels must be 1 or 3"); return TREXHIP_E_UNSUPPORTED; }
     if (classes < 1 || classes > 1024) { set_error("trexhip_load_weights: classes must be 1..1024"); return TREXHIP_E_INVALID; }
     const size_t flat = 128 * (W / 8) * (H / 8);
@@ -1690,7 +1694,7 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
                     w1[((size_t)c * 25 + tap) * 16 + co] = (float)((double)c1w[((size_t)co * CH + c) * 25 + tap] * s);
         }
         TRY(upload(&net->w1, w1)); TRY(upload(&net->b1, b1));
-        if (CH == 3 && rc == TREXHIP_OK) {   // B fragments of k_conv1_mfma3: [shift s][mfma m][piece hi|lo][lane] x 8 halves
+        if (at80 && CH == 3 && rc == TREXHIP_OK) {   // B fragments of k_conv1_mfma3: [shift s][mfma m][piece hi|lo][lane] x 8 halves
             float mx = 0.f;
             for (float v : w1) mx = std::fmax(mx, std::fabs(v));
             int k = 0;
@@ -1718,7 +1722,7 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
             if (hipMalloc(reinterpret_cast<void**>(&net->w1h), tab.size() * 2) != hipSuccess ||
                 hipMemcpy(net->w1h, tab.data(), tab.size() * 2, hipMemcpyHostToDevice) != hipSuccess) rc = TREXHIP_E_DEVICE;
         }
-        if (CH == 1 && rc == TREXHIP_OK) {   // B fragments of k_conv1_mfma: [shift s][mfma 0: ky 0..3 | 1: ky 4][piece hi|lo][lane] x 8 halves
+        if (at80 && CH == 1 && rc == TREXHIP_OK) {   // B fragments of k_conv1_mfma: [shift s][mfma 0: ky 0..3 | 1: ky 4][piece hi|lo][lane] x 8 halves
             float mx = 0.f;
             for (float v : w1) mx = std::fmax(mx, std::fabs(v));
             int k = 0;
@@ -1751,16 +1755,16 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     TRY(upload(&net->w2, wp)); TRY(upload(&net->b2, bias));
     TRY(upload_split(&net->w2s, wp, 16, 64));
     TRY(upload_split_f16(&net->w2h, &net->inv2h, wp, 16, 64));
-    TRY(upload_wino_f16(&net->w2w, &net->inv2w, wp, 16, 64));
+    if (at80) TRY(upload_wino_f16(&net->w2w, &net->inv2w, wp, 16, 64));
     fold_conv(c3w, c3b, g3, be3, m3, v3, 128, 64, 16, wp, bias);       // 16-channel chunks for the bf16 path
     TRY(upload_split(&net->w3s, wp, 64, 128));
     TRY(upload_split_f16(&net->w3h, &net->inv3h, wp, 64, 128));
-    TRY(upload_wino_f16(&net->w3w, &net->inv3w, wp, 64, 128));
+    if (at80) TRY(upload_wino_f16(&net->w3w, &net->inv3w, wp, 64, 128));
     if (rc == TREXHIP_OK && hipMalloc(reinterpret_cast<void**>(&net->d_ovf), 16 + (2 + FB_MAX) * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
     if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, 16 + (2 + FB_MAX) * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
     fold_conv(c3w, c3b, g3, be3, m3, v3, 128, 64, 32, wp, bias);
     TRY(upload(&net->w3, wp)); TRY(upload(&net->b3, bias));
-    {   // fc1 [100][c*100+h*10+w] -> [(h*10+w)*128 + c][128 (o padded)]
+    {   // fc1 [100][c*P + h*(W/8) + w] (the reference's NCHW flatten, P = (H/8)(W/8)) -> [(h*(W/8) + w)*128 + c][128 (o padded)], act3's NHWC order
         const int P = (W / 8) * (H / 8);
         std::vector<float> wf((size_t)flat * 128, 0.f), bf(128, 0.f);
         for (int o = 0; o < 100; ++o) {
@@ -1770,7 +1774,7 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
                     wf[((size_t)hw * 128 + c) * 128 + o] = f1w[(size_t)o * flat + (size_t)c * P + hw];
         }
         TRY(upload(&net->wf1, wf)); TRY(upload(&net->bf1, bf));
-        if (rc == TREXHIP_OK) {      // the same matrix as two fp16 pieces per weight, MFMA B-operand order
+        if (at80 && rc == TREXHIP_OK) {      // the same matrix as two fp16 pieces per weight, MFMA B-operand order (the generic chain's fc1 is exact fp32)
             float mx = 0.f;
             for (float v : wf) mx = std::fmax(mx, std::fabs(v));
             int k = 0;
@@ -1819,18 +1823,53 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     const size_t N = n;
     TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->d_ovfc), N));
     TH_CHECK_HIP(hipMemsetAsync(net->d_ovfc, 0, N, ctx->stream));      // on the stream its users run on; the plan kernel clears what it reads
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act1), N * 40 * 40 * 16 * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act2), N * 20 * 20 * 64 * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act3), N * 10 * 10 * 128 * 4));
+    const size_t W = net->W, H = net->H;       // (80 x 80: 40 x 40 x 16, 20 x 20 x 64, 10 x 10 x 128)
+    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act1), N * (H / 2) * (W / 2) * 16 * 4));
+    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act2), N * (H / 4) * (W / 4) * 64 * 4));
+    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act3), N * (H / 8) * (W / 8) * 128 * 4));
     TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->fc1), N * 128 * 4 * FC1_KSPLIT));
     TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->probs), N * net->classes * 4));
     TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->logits), N * net->classes * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->v2), N * 40 * V2_ROWB));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->v3), N * 20 * V3_ROWB));
+    if (W == 80 && H == 80) {                  // the Winograd-domain operand images of the 80 x 80 chain
+        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->v2), N * 40 * V2_ROWB));
+        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->v3), N * 20 * V3_ROWB));
+    }
     TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->crops), N * net->W * net->H * net->CH));
     TH_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&net->h_probs), N * net->classes * 4, hipHostMallocDefault));
     net->max_crops = n;
     (void)ctx;
+    return TREXHIP_OK;
+}
+
+// every individual_image_size but 80 x 80: conv1..conv3 of cnn_any.hip in the precision mode (conv1 exact fp32 in all of them), fc1 exact fp32
+// (k_fc1, K = 128 (H/8) (W/8) at run time), k_head.  In FP16X3 mode the range guard of the 80 x 80 chain: k_guard_plan lists the crops the fp16
+// convolutions flagged, and the BF16X6 convolutions, fc1 and the head re-run only those (the whole batch past FB_MAX)
+static int net_forward_any(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
+    Net* net = static_cast<Net*>(ctx->net);
+    hipStream_t s = ctx->stream;
+    const int mode = ctx->cnn_mode;
+    const AnyConvNet a{net->W, net->H, net->CH, net->w1, net->b1, net->w2, net->b2, net->w3, net->b3, net->w2s, net->w3s, net->w2h, net->w3h,
+                       net->inv2h, net->inv3h, net->act1, net->act2, net->act3, net->d_ovf, net->d_ovfc};
+    // fc1 split-K planes (summed in k_head): the largest count up to FC1_KSPLIT that divides the (H/8)(W/8) positions, so that every plane is
+    // whole positions of 128 channels (a multiple of k_fc1's 32-deep chunks); it depends on the size alone, never on n
+    const int P = (net->H / 8) * (net->W / 8), K = 128 * P;
+    int ks = FC1_KSPLIT;
+    while (P % ks) --ks;
+    stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
+    any_convs(s, ctx->n_cus, mode, a, d_crops, n);
+    hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, ks), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, K, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
+                       d_probs, d_logits, n, net->classes, (const uint32_t*)nullptr, ks);
+    if (mode == TREXHIP_CNN_FP16X3) {
+        const uint32_t* g = net->d_ovf + 4;
+        hipLaunchKernelGGL(k_guard_plan, dim3(1), dim3(1024), 0, s, net->d_ovf, net->d_ovfc, n, net->d_ovf + 4);
+        any_convs_rerun(s, ctx->n_cus, a, n, g);
+        hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, ks), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, K, g);
+        hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
+                           d_probs, d_logits, n, net->classes, g, ks);
+    }
+    stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
+    TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
 }
 
@@ -1917,8 +1956,11 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb3, reinterpret_cast<const void*>(&k_conv5_wpre<0, 7>), 256, (WinoGeom<64, 128, 20, 2>::LDS_BYTES));
             fprintf(stderr, "[trexhip] workgroups per CU: k_conv2_wpre2 %d (LDS %d), k_conv5_wpre %d\n", nb2, (int)W2bGeom::LDS_BYTES, nb3);
         }
+        const int rc_any = any_set_attributes();
+        if (rc_any != TREXHIP_OK) return rc_any;
         ctx->attr_cnn = true;
     }
+    if (net->W != 80 || net->H != 80) return net_forward_any(ctx, d_crops, n, d_probs, d_logits);
     stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
     const int S = net->W;
     const size_t lds1 = ((size_t)net->CH * (S + 4) * (S + 4) + (size_t)net->CH * 25 * 16) * 4;
@@ -2285,6 +2327,14 @@ int trexhip_num_classes(trexhip_ctx* ctx) {
 int trexhip_network_channels(trexhip_ctx* ctx) {
     if (!ctx || !ctx->net) return 0;
     return static_cast<Net*>(ctx->net)->CH;
+}
+
+int trexhip_network_image_size(trexhip_ctx* ctx, int32_t* width, int32_t* height) {
+    if (!ctx) { set_error("trexhip_network_image_size: null context"); return TREXHIP_E_INVALID; }
+    const Net* net = static_cast<const Net*>(ctx->net);
+    if (width) *width = net ? net->W : 0;
+    if (height) *height = net ? net->H : 0;
+    return TREXHIP_OK;
 }
 
 }  // extern "C"

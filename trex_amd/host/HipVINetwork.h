@@ -51,10 +51,13 @@ struct HipVINetwork {
             if (!weights_loaded()) throw std::runtime_error("weights not loaded");
             const int C = num_classes();
             std::vector<uint8_t> crops;
-            const size_t per = (size_t)80 * 80 * (size_t)trexhip_network_channels(_ctx);     // what the network was built for
+            int32_t W = 0, H = 0;
+            trexhip_network_image_size(_ctx, &W, &H);                                      // what the network was built for
+            const size_t per = (size_t)W * H * (size_t)trexhip_network_channels(_ctx);
             for (auto& im : images) {
                 if (!im) throw std::runtime_error("null image");
-                if (im->rows != 80 || im->cols != 80) throw std::runtime_error("Invalid image size (expected individual_image_size 80x80)");  // visual_recognition_torch.py:1006-1018
+                if ((int32_t)im->rows != H || (int32_t)im->cols != W)                          // visual_recognition_torch.py:1006-1018
+                    throw std::runtime_error("Invalid image size (expected individual_image_size " + std::to_string(W) + "x" + std::to_string(H) + ")");
                 if (im->size() != per) throw std::runtime_error("Invalid image channels (the network expects " + std::to_string(trexhip_network_channels(_ctx)) + ")");
                 crops.insert(crops.end(), im->data(), im->data() + im->size());
             }
