@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev: kernel-trace durations of named kernels for several builds of the library (trex_amd/variants/*.so) on ONE box, two rounds
 #   gpurun -- 'bash tools/ab_variants.sh "<kernel regex>" "<bench arguments>"'
-PAT=${1:-k_conv5_wpre}
+PAT=${1:-k_conv5_wpair}
 ARGS=${2:---no-pipeline --no-cpu-baseline --no-secondary --steps 6}
 ROOT=$(pwd)
 cp trex_amd/libtrexhip.so /tmp/keep.so

@@ -8,5 +8,4 @@ for rep in 1 2; do
 run "default" "A=1" ""
 run "detect at equal priority" "A=1" "--no-detect-priority"
 run "three lanes" "A=1" "--lanes 3"
-run "k_head_small for every batch" "TREXHIP_HEAD_SMALL_MAX=100000" ""
 done 2>&1 | tee gpurun_out/r06/pipe_variants.txt

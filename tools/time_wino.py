@@ -1,4 +1,4 @@
-"""dev: time conv3 (stage CONV3) of identify_device on 25600 crops for TREXHIP_CONV_GEOM debug variants"""
+"""dev: time conv3 (stage CONV3) of identify_device on 25600 crops; TREXHIP_CONV_GEOM=2048 times the fp32-activation chain (k_conv5_wino)"""
 import os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trex_amd import capi, weights

@@ -179,7 +179,9 @@ int trexhip_create(const trexhip_params* p, trexhip_ctx** out) {
     // stop a kernel half-way or skip work (profiling aids) exist only in a -DTREXHIP_DEV_KNOBS build.
     if (const char* e = std::getenv("TREXHIP_ROWS_ORDER")) ctx->tune_rows_order = std::atoi(e) & (1 | 4 | 8 | 1024 | 2048);
     if (const char* e = std::getenv("TREXHIP_ROWS_K")) ctx->tune_rows_k = std::atoi(e);
-    if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e);
+    // TREXHIP_CONV_GEOM: any of bits 0-11 selects the fp32-activation chain of the identity network; bit 28 keeps conv1 and conv2 apart,
+    // bit 29 forces the role-split conv1+conv2 kernel, bit 30 the two-workgroups-per-CU one.  The other bits mean nothing.
+    if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e) & (0xfff | (7 << 28));
 #ifdef TREXHIP_DEV_KNOBS
     if (const char* e = std::getenv("TREXHIP_ROWS_ORDER")) ctx->tune_rows_order = std::atoi(e);
     if (const char* e = std::getenv("TREXHIP_CCL_STOP")) ctx->tune_ccl_stop = std::atoi(e);

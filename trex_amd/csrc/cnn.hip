@@ -7,8 +7,8 @@
 //   x = float(u8)  ->  [conv5x5 same -> BN -> ReLU -> maxpool2] x3 -> flatten(NCHW) -> fc1(12800->100)
 //   -> LayerNorm(100) -> ReLU -> fc2(100->classes) -> softmax.
 //
-// Default chain (1-channel crops, fp16 two-piece split): k_conv12_wpre (cnn_fused12.h: conv1 inside conv2) -> V3 -> k_conv5_wpre (cnn_wpre.h)
-// -> k_fc1_split -> k_head.  The kernels of this file are the exact-fp32 / bf16 precision modes, the fallbacks and the head:
+// Default chain (1-channel crops, fp16 two-piece split): k_conv12_rs (cnn_fused12rs.h) or k_conv12_wpre (cnn_fused12.h): conv1 inside conv2 -> V3
+// -> k_conv5_wpair (cnn_conv3p.h) -> k_fc1_split -> k_head.  The kernels of this file are the exact-fp32 / bf16 precision modes, the fallbacks and the head:
 // Kernels (DESIGN.md "Identity network"):
 //   k_conv1     C_in=1: VALU, one block per crop, u8 crop staged in LDS, fused BN+ReLU+pool
 //   k_conv5<>   conv2/conv3 as 25 shifted GEMMs on v_mfma_f32_32x32x2_f32 (exact fp32):
@@ -344,10 +344,6 @@ __device__ __forceinline__ void split2h(float x, uint32_t& p1, uint32_t& p2, boo
     p2 = __builtin_bit_cast(uint16_t, h2);
 }
 
-template <int KIND> struct SplitK;      // KIND 0 = bf16 (3 pieces), 1 = fp16 (2 pieces)
-template <> struct SplitK<0> { static constexpr int NP = 3; using frag = bf16x8; };
-template <> struct SplitK<1> { static constexpr int NP = 2; using frag = f16x8; };
-
 __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
@@ -367,21 +363,20 @@ struct ConvGeomB {
     static constexpr int BPC = S / ROWS;
 };
 
-// KIND 0: NTERMS 6 (a3b1 a2b2 a1b3 a2b1 a1b2 a1b1) or 3 (last three);  KIND 1: NTERMS 3 (a2b1 a1b2 a1b1)
-template <int CI, int CO, int S, int ROWS, int KIND, int NTERMS, int CIC = 16>
+// the bf16 split: three pieces per operand; NTERMS 6 (a3b1 a2b2 a1b3 a2b1 a1b2 a1b1) or 3 (the last three)
+static constexpr int SPLIT_NP = 3;
+template <int CI, int CO, int S, int ROWS, int NTERMS, int CIC = 16>
 __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ in /*[N][S][S][CI]*/,
                                                      const uint4* __restrict__ wp /*[CI/16][25][NP][2][CO] x 16 B*/,
-                                                     const float* __restrict__ bias, float* __restrict__ out,
-                                                     const float out_scale, uint32_t* __restrict__ overflow,
+                                                     const float* __restrict__ bias, float* __restrict__ out, const float out_scale,
                                                      const uint32_t* __restrict__ guard, const int n_blocks) {
     if (guard && guard[1] == 0u) return;          // re-run pass (guard = the plan of k_guard_plan): only when the fp16 pass flagged an overflow
-    using K = SplitK<KIND>;
-    using frag = typename K::frag;
-    using G = ConvGeomB<CI, CO, S, ROWS, K::NP, CIC>;
+    using frag = bf16x8;
+    using G = ConvGeomB<CI, CO, S, ROWS, SPLIT_NP, CIC>;
     constexpr int Q4 = CIC / 4, KO = CIC / 8;                          // float4 per pixel per chunk, k-octets per chunk
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
     uint8_t* patch = ldsb;                       // NP pieces
-    uint8_t* Bs = ldsb + K::NP * G::PATCH;       // 2 buffers
+    uint8_t* Bs = ldsb + SPLIT_NP * G::PATCH;    // 2 buffers
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int n = wave % G::NT, mg = wave / G::NT;
@@ -414,7 +409,6 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
     const float* inc = in + (size_t)crop * S * S * CI;
     constexpr int BV = G::BT / 16;                                      // uint4 per weight tile
     constexpr int BPT = (BV + 511) / 512;
-    bool ovf = false;
     for (int cc = 0; cc < CI / CIC; ++cc) {
         __syncthreads();
         for (int idx = tid; idx < G::PH * G::PW * Q4; idx += 512) {     // Q4 float4 per pixel
@@ -425,17 +419,12 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
             if (iy >= 0 && iy < S && ix >= 0 && ix < S)
                 v = *reinterpret_cast<const float4*>(inc + ((size_t)iy * S + ix) * CI + cc * CIC + q * 4);
             uint32_t a1[4], a2[4], a3[4];
-            if (KIND == 0) {
-                split3(v.x, a1[0], a2[0], a3[0]); split3(v.y, a1[1], a2[1], a3[1]);
-                split3(v.z, a1[2], a2[2], a3[2]); split3(v.w, a1[3], a2[3], a3[3]);
-            } else {
-                split2h(v.x, a1[0], a2[0], ovf); split2h(v.y, a1[1], a2[1], ovf);
-                split2h(v.z, a1[2], a2[2], ovf); split2h(v.w, a1[3], a2[3], ovf);
-            }
+            split3(v.x, a1[0], a2[0], a3[0]); split3(v.y, a1[1], a2[1], a3[1]);
+            split3(v.z, a1[2], a2[2], a3[2]); split3(v.w, a1[3], a2[3], a3[3]);
             uint8_t* d = patch + px * G::PSTRIDE + q * 8;
             *reinterpret_cast<uint2*>(d) = make_uint2(a1[0] | (a1[1] << 16), a1[2] | (a1[3] << 16));
             *reinterpret_cast<uint2*>(d + G::PATCH) = make_uint2(a2[0] | (a2[1] << 16), a2[2] | (a2[3] << 16));
-            if (KIND == 0) *reinterpret_cast<uint2*>(d + 2 * G::PATCH) = make_uint2(a3[0] | (a3[1] << 16), a3[2] | (a3[3] << 16));
+            *reinterpret_cast<uint2*>(d + 2 * G::PATCH) = make_uint2(a3[0] | (a3[1] << 16), a3[2] | (a3[3] << 16));
         }
         const uint4* wsrc = wp + (size_t)cc * 25 * BV;
         for (int i = tid; i < BV; i += 512) reinterpret_cast<uint4*>(Bs)[i] = wsrc[i];
@@ -456,12 +445,11 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
                 const uint8_t* bsrc = Bs + buf * G::BT + ((2 * ks + h) * CO + n * 32 + j) * 16;
                 const frag b1 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc));
                 const frag b2 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + KO * CO * 16));
-                frag b3 = b1;
-                if (K::NP == 3) b3 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + 2 * KO * CO * 16));
+                const frag b3 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + 2 * KO * CO * 16));
 #pragma unroll
                 for (int m = 0; m < G::TPW; ++m) {
                     const frag p1 = LDA(m, 0), p2 = LDA(m, 1);
-                    if (KIND == 0 && NTERMS == 6) {
+                    if (NTERMS == 6) {
                         const frag p3 = LDA(m, 2);
                         MF(p3, b1, m); MF(p2, b2, m); MF(p1, b3, m);
                     }
@@ -477,7 +465,6 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
             __syncthreads();
         }
     }
-    if (KIND == 1 && __any(ovf) && lane == 0) atomicOr(overflow, 3u);      // (bit 1: raised by a kernel that cannot name the crop -- k_guard_plan re-runs every crop)
     const int co = n * 32 + j;
     const float bz = bias[co];
     float* oc = out + (size_t)crop * WR * WR * CO;
@@ -491,7 +478,7 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
             if (wi >= G::NPIX / 4) continue;
             const float v = fmaxf(fmaxf(acc[m][4 * g], acc[m][4 * g + 1]), fmaxf(acc[m][4 * g + 2], acc[m][4 * g + 3]));
             const int wy = row0 / 2 + wi / WR, wx = wi % WR;
-            oc[((size_t)wy * WR + wx) * CO + co] = fmaxf(v * out_scale + bz, 0.f);     // out_scale undoes the weight scaling (fp16 pieces)
+            oc[((size_t)wy * WR + wx) * CO + co] = fmaxf(v * out_scale + bz, 0.f);     // (out_scale: 1 for the unscaled bf16 weights)
         }
     }
     }
@@ -531,26 +518,19 @@ struct ConvGeomS {
     static constexpr int NITEMS = (NQ + NTHR - 1) / NTHR;
 };
 
-template <int CI, int CO, int S, int ROWS, int WAVES, bool PERSIST = false>
+template <int CI, int CO, int S, int ROWS, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void k_conv5_stream(const float* __restrict__ in /*[N][S][S][CI]*/,
                                                              const uint4* __restrict__ wp /*[CI/16][25][2][2][CO] x 16 B*/,
                                                              const float* __restrict__ bias, float* __restrict__ out,
-                                                             const float out_scale, uint32_t* __restrict__ overflow, const int n_units,
-                                                             uint32_t* __restrict__ unit_ctr /*persistent: zeroed counter handing out units*/) {
+                                                             const float out_scale, uint32_t* __restrict__ overflow, const int n_units) {
     using G = ConvGeomS<CI, CO, S, ROWS, WAVES>;
     static_assert(G::NCH == 1 || G::NITEMS <= 5, "staging slices do not fit between the taps");
-    static_assert(G::NCH == 1 || G::NCH % 2 == 0, "buffer parity must survive the unit loop");
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int n = wave % G::NT, mg = wave / G::NT;
-    // a unit = ROWS output rows of one crop.  gridDim.x == n_units: one unit per workgroup; fewer workgroups: each walks the
-    // units with a grid stride and (multi-chunk layers) stages the next unit's first chunk under the current unit's last one.
-    // Persistent multi-chunk layers take their further units from a counter (first come, first served) instead of a fixed stride:
-    // a workgroup that gets its CU late -- the detect stream or a collective was running there -- just takes fewer units.
-    constexpr bool DYNAMIC = PERSIST && G::NCH > 1;
-    __shared__ int s_next_unit;
-    int unit = blockIdx.x;
+    // a unit = ROWS output rows of one crop, one unit per workgroup
+    const int unit = blockIdx.x;
     if (unit >= n_units) return;
     constexpr int WR = S / 2;
 
@@ -603,94 +583,66 @@ __global__ __launch_bounds__(WAVES * 64) void k_conv5_stream(const float* __rest
     bq[1][0] = wl[G::BV]; bq[1][1] = wl[G::BV + 2 * CO];
     const int co = n * 32 + j;
     const float bz = bias[co];
-    int crop = unit / G::BPC, row0 = (unit % G::BPC) * ROWS;
+    const int crop = unit / G::BPC, row0 = (unit % G::BPC) * ROWS;
     const float* inc = in + (size_t)crop * S * S * CI;
-    bool staged = false;                               // the current unit's first chunk is already in LDS
-    for (;;) {
-        if (!staged) {
-            if (G::NCH == 1 && unit != (int)blockIdx.x) __syncthreads();     // single buffer: the previous unit must be done with it
-            for (int it = 0; it < G::NITEMS; ++it) {
-                float4 v;
-                STG_LOAD(v, it, inc, row0, 0);
-                STG_STORE(v, it, ldsb);
+    for (int it = 0; it < G::NITEMS; ++it) {
+        float4 v;
+        STG_LOAD(v, it, inc, row0, 0);
+        STG_STORE(v, it, ldsb);
+    }
+    __syncthreads();
+    f32x16 acc[G::TPW];
+#pragma unroll
+    for (int m = 0; m < G::TPW; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+    for (int cc = 0; cc < G::NCH; ++cc) {
+        const uint8_t* pbase = ldsb + (G::NBUF > 1 ? (cc & 1) * 2 * G::PATCH : 0);
+        uint8_t* nbase = ldsb + (G::NBUF > 1 ? ((cc + 1) & 1) * 2 * G::PATCH : 0);
+        const bool more_c = cc + 1 < G::NCH;                             // the next chunk's weights are needed and its patch is staged under this one
+        const uint4* wc = wl + (size_t)cc * 25 * G::BV;
+        const uint4* wn = wl + (size_t)(cc + 1) * 25 * G::BV;
+        float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int tap = 0; tap < 25; ++tap) {
+            if (tap + 2 < 25) {                // weights two taps ahead (runs into the following chunk's first taps)
+                bq[(tap + 2) % 5][0] = wc[(size_t)(tap + 2) * G::BV];
+                bq[(tap + 2) % 5][1] = wc[(size_t)(tap + 2) * G::BV + 2 * CO];
+            } else if (more_c) {
+                bq[(tap + 2) % 5][0] = wn[(size_t)(tap + 2 - 25) * G::BV];
+                bq[(tap + 2) % 5][1] = wn[(size_t)(tap + 2 - 25) * G::BV + 2 * CO];
             }
-            __syncthreads();
-        }
-        f32x16 acc[G::TPW];
-#pragma unroll
-        for (int m = 0; m < G::TPW; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-        int next_unit = unit + (int)gridDim.x;
-        bool have_next = PERSIST && next_unit < n_units;             // !PERSIST: gridDim.x == n_units, one unit per workgroup
-        int crop_n = next_unit / G::BPC, row0_n = (next_unit % G::BPC) * ROWS;
-        const float* inc_n = in + (size_t)crop_n * S * S * CI;
-        if (DYNAMIC && tid == 0) s_next_unit = (int)atomicAdd(unit_ctr, 1u) + (int)gridDim.x;   // read by everyone after the first chunk's barrier
-        for (int cc = 0; cc < G::NCH; ++cc) {
-            if (DYNAMIC && cc == G::NCH - 1) {                       // the last chunk stages the next unit: now its number is needed
-                next_unit = s_next_unit;
-                have_next = next_unit < n_units;
-                crop_n = next_unit / G::BPC; row0_n = (next_unit % G::BPC) * ROWS;
-                inc_n = in + (size_t)crop_n * S * S * CI;
+            if (more_c) {
+                if (tap % 5 == 0 && tap / 5 < G::NITEMS) STG_LOAD(sv, tap / 5, inc, row0, cc + 1);
+                if (tap % 5 == 3 && tap / 5 < G::NITEMS) STG_STORE(sv, tap / 5, nbase);
             }
-            const uint8_t* pbase = ldsb + (G::NBUF > 1 ? (cc & 1) * 2 * G::PATCH : 0);
-            uint8_t* nbase = ldsb + (G::NBUF > 1 ? ((cc + 1) & 1) * 2 * G::PATCH : 0);
-            const bool more_c = cc + 1 < G::NCH;
-            const bool more_w = more_c || have_next;                         // weights of a following chunk are needed
-            const bool more_s = G::NCH > 1 && more_w;                        // ... and its patch can be staged under this chunk
-            const float* sinc = more_c ? inc : inc_n;
-            const int srow0 = more_c ? row0 : row0_n, scc = more_c ? cc + 1 : 0;
-            const uint4* wc = wl + (size_t)cc * 25 * G::BV;
-            const uint4* wn = wl + (size_t)scc * 25 * G::BV;
-            float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+            const uint8_t* asrc = pbase + ((tap / 5) * G::RP + (tap % 5) * G::PSTRIDE);
+            const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tap % 5][0]);
+            const f16x8 b2 = __builtin_bit_cast(f16x8, bq[tap % 5][1]);
 #pragma unroll
-            for (int tap = 0; tap < 25; ++tap) {
-                if (tap + 2 < 25) {                // weights two taps ahead (runs into the following chunk's first taps)
-                    bq[(tap + 2) % 5][0] = wc[(size_t)(tap + 2) * G::BV];
-                    bq[(tap + 2) % 5][1] = wc[(size_t)(tap + 2) * G::BV + 2 * CO];
-                } else if (more_w) {
-                    bq[(tap + 2) % 5][0] = wn[(size_t)(tap + 2 - 25) * G::BV];
-                    bq[(tap + 2) % 5][1] = wn[(size_t)(tap + 2 - 25) * G::BV + 2 * CO];
-                }
-                if (more_s) {
-                    if (tap % 5 == 0 && tap / 5 < G::NITEMS) STG_LOAD(sv, tap / 5, sinc, srow0, scc);
-                    if (tap % 5 == 3 && tap / 5 < G::NITEMS) STG_STORE(sv, tap / 5, nbase);
-                }
-                const uint8_t* asrc = pbase + ((tap / 5) * G::RP + (tap % 5) * G::PSTRIDE);
-                const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tap % 5][0]);
-                const f16x8 b2 = __builtin_bit_cast(f16x8, bq[tap % 5][1]);
-#pragma unroll
-                for (int m = 0; m < G::TPW; ++m) {
-                    if (m == G::TPW - 1 && !last_tile) continue;       // wave-uniform: this M-group has one tile less
-                    const f16x8 p1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(asrc + aoff[m]));
-                    const f16x8 p2 = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(asrc + aoff[m] + G::PATCH));
-                    acc[m] = mfma16(p2, b1, acc[m]);
-                    acc[m] = mfma16(p1, b2, acc[m]);
-                    acc[m] = mfma16(p1, b1, acc[m]);
-                }
-            }
-            if (G::NCH > 1) __syncthreads();
-        }
-        float* oc = out + (size_t)crop * WR * WR * CO;
-#pragma unroll
-        for (int m = 0; m < G::TPW; ++m) {
-            const int mt = mg + G::WM * m;
-            if (mt >= G::MT) continue;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int wi = mt * 8 + 2 * g + h;
-                if (wi >= G::NPIX / 4) continue;
-                const float v = fmaxf(fmaxf(acc[m][4 * g], acc[m][4 * g + 1]), fmaxf(acc[m][4 * g + 2], acc[m][4 * g + 3]));
-                const int wy = row0 / 2 + wi / WR, wx = wi % WR;
-                oc[((size_t)wy * WR + wx) * CO + co] = fmaxf(v * out_scale + bz, 0.f);
+            for (int m = 0; m < G::TPW; ++m) {
+                if (m == G::TPW - 1 && !last_tile) continue;       // wave-uniform: this M-group has one tile less
+                const f16x8 p1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(asrc + aoff[m]));
+                const f16x8 p2 = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(asrc + aoff[m] + G::PATCH));
+                acc[m] = mfma16(p2, b1, acc[m]);
+                acc[m] = mfma16(p1, b2, acc[m]);
+                acc[m] = mfma16(p1, b1, acc[m]);
             }
         }
-        if (!PERSIST || !have_next) break;
-        unit = next_unit; crop = crop_n; row0 = row0_n; inc = inc_n;
-        staged = G::NCH > 1;                           // multi-chunk layers staged it under the last chunk
-        if (G::NCH == 1) {                             // single chunk: weights of taps 0,1 again
-            bq[0][0] = wl[0]; bq[0][1] = wl[2 * CO];
-            bq[1][0] = wl[G::BV]; bq[1][1] = wl[G::BV + 2 * CO];
+        if (G::NCH > 1) __syncthreads();
+    }
+    float* oc = out + (size_t)crop * WR * WR * CO;
+#pragma unroll
+    for (int m = 0; m < G::TPW; ++m) {
+        const int mt = mg + G::WM * m;
+        if (mt >= G::MT) continue;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int wi = mt * 8 + 2 * g + h;
+            if (wi >= G::NPIX / 4) continue;
+            const float v = fmaxf(fmaxf(acc[m][4 * g], acc[m][4 * g + 1]), fmaxf(acc[m][4 * g + 2], acc[m][4 * g + 3]));
+            const int wy = row0 / 2 + wi / WR, wx = wi % WR;
+            oc[((size_t)wy * WR + wx) * CO + co] = fmaxf(v * out_scale + bz, 0.f);
         }
     }
 #undef STG_LOAD
@@ -811,7 +763,7 @@ __device__ __forceinline__ void split2h_pair(const float a, const float b, uint3
     p2 = __builtin_bit_cast(uint32_t, h2);
 }
 
-template <int CI, int CO, int S, int TPW, int DBG = 0>
+template <int CI, int CO, int S, int TPW>
 __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1)) void k_conv5_wino(const float* __restrict__ in /*[N][S][S][CI]*/,
                                                                                const uint4* __restrict__ wp /*[CI/16][5][8][2][2][CO] x 16 B*/,
                                                                                const float* __restrict__ bias, float* __restrict__ out,
@@ -852,7 +804,7 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
         const int r_ = idx_ - s_ * (G::TPR * 4);                                                                                \
         const int cq_ = r_ & 3, tx_ = r_ >> 2;                                                                                  \
         s_ = s_ < (nrows_) ? s_ : (nrows_) - 1;                                                                                 \
-        srs = make_rsrc(in + ((size_t)((DBG & 16) ? 0 : (qmin_)) * S) * CI, (uint32_t)(G::NR * S * CI * 4));                    \
+        srs = make_rsrc(in + ((size_t)(qmin_) * S) * CI, (uint32_t)(G::NR * S * CI * 4));                                      \
         const int soff_ = s_ * (S * CI * 4) + (cc_) * 64 + cq_ * 16;                                                            \
         sdstb[item_] = (s_ + 1) * G::RP + tx_ * 32 + cq_ * 8;                                                                   \
         sflagb[item_] = (tx_ == 0 ? 1 : 0) | (tx_ == G::TPR - 1 ? 2 : 0);                                                       \
@@ -987,7 +939,7 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
 #pragma clang loop unroll(full)
             for (int t = 0; t < 40; ++t) {
                 const int cur = t & 1, nxt = cur ^ 1;
-                if (!(DBG & 8) && t + 1 < 40) {                                    // A fragments of the next tap
+                if (t + 1 < 40) {                                    // A fragments of the next tap
                     const uint8_t* an = pbase + ((t + 1) % 8) * G::PS;
 #pragma unroll
                     for (int m = 0; m < TPW; ++m) {
@@ -995,17 +947,14 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
                         af[nxt][m][1] = *reinterpret_cast<const uint4*>(an + aoff[m][(t + 1) / 8] + G::PLANE);
                     }
                 }
-                if (!(DBG & 4)) {                                    // B fragments BD taps ahead
-                    const int wt = t + BD < 40 ? wc + (t + BD) * G::BV * 16 : wn + (t + BD - 40) * G::BV * 16;
-                    bq[(t + BD) % 8][0] = buf_load16(wrs, boff, wt);
-                    bq[(t + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
-                }
-                if (!(DBG & 1)) {                                    // item 0: load at tap 0, slots 6..17; item 1: load at tap 20, slots 26..37
-                    if (t == 0) WS_L(0, scc, sqmin, snrows);
-                    if (t == 20) WS_L(1, scc, sqmin, snrows);
-                    if (t >= 6 && t < 18) WS_STEP(t - 6, 0, nbase);
-                    if (t >= 26 && t < 38) WS_STEP(t - 26, 1, nbase);
-                }
+                const int wt = t + BD < 40 ? wc + (t + BD) * G::BV * 16 : wn + (t + BD - 40) * G::BV * 16;      // B fragments BD taps ahead
+                bq[(t + BD) % 8][0] = buf_load16(wrs, boff, wt);
+                bq[(t + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
+                // staging: item 0 loads at tap 0, slots 6..17; item 1 loads at tap 20, slots 26..37
+                if (t == 0) WS_L(0, scc, sqmin, snrows);
+                if (t == 20) WS_L(1, scc, sqmin, snrows);
+                if (t >= 6 && t < 18) WS_STEP(t - 6, 0, nbase);
+                if (t >= 26 && t < 38) WS_STEP(t - 26, 1, nbase);
                 const int p = t % 8;
                 const f16x8 b1 = __builtin_bit_cast(f16x8, bq[t % 8][0]);
                 const f16x8 b2 = __builtin_bit_cast(f16x8, bq[t % 8][1]);
@@ -1035,7 +984,7 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
         // epilogue: Y = A^T M per tile (16-wide, one M-tile at a time: the four outputs of all 16 accumulator rows of a lane), then the
         // max over the 2x2 pool window (rows y, y+1 = registers r, r+1; outputs 0,1 / 2,3), bias, ReLU
 #pragma unroll
-        for (int m = 0; m < ((DBG & 2) ? 0 : TPW); ++m) {
+        for (int m = 0; m < TPW; ++m) {
             f32x16 y0, y1, y2, y3;
             {
                 const f32x16 e1 = acc[m][1] + acc[m][2], o1 = acc[m][1] - acc[m][2];
@@ -1068,12 +1017,6 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (DBG & 2) {
-#pragma unroll
-            for (int m = 0; m < TPW; ++m)
-#pragma unroll
-                for (int p = 0; p < 8; ++p) asm volatile("" :: "a"(acc[m][p]));
-        }
         if (!have_next) break;
         pass = next_pass; qmin = qmin_n; nrows = nrows_n;
     }
@@ -1087,13 +1030,10 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
 }
 
 #include "cnn_wpre.h"
-#ifndef TREXHIP_V3_OLD
 #include "cnn_conv3p.h"
-#endif
 #include "cnn_fused12.h"
 #include "cnn_fused12rs.h"
 
-static constexpr int W3P_BD = 5;         // k_conv5_wpair: weight fragments 5 taps ahead
 static constexpr int FC1_KSPLIT = 10;     // 12800 = 10 x 1280: 500 workgroups at 6400 crops (5: 129 us, 10: 92 us, 20: 102 us + slower head); partial planes summed in k_head
 // ------------------------------------------------------------------------------------------------
 // fc1: out[N][128] = act[N][K] * W[K][128] + b     (K = 12800, 100 real outputs)
@@ -1873,89 +1813,43 @@ static int net_forward_any(trexhip_ctx* ctx, const uint8_t* d_crops, int n, floa
     return TREXHIP_OK;
 }
 
+template <class K>
+static hipError_t set_lds(K* kernel, const int bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// k_conv5_split over n crops.  A guarded re-run (guard = the plan of k_guard_plan) goes out on a small grid that strides over its crops
+template <int CI, int CO, int S, int ROWS, int NTERMS>
+static void launch_split(trexhip_ctx* ctx, const int n, const float* in, const uint4* w, const float* b, float* out, const uint32_t* guard) {
+    using G = ConvGeomB<CI, CO, S, ROWS, SPLIT_NP>;
+    const int blocks = n * G::BPC;
+    hipLaunchKernelGGL((k_conv5_split<CI, CO, S, ROWS, NTERMS>), dim3(guard ? std::min(blocks, 4 * ctx->n_cus) : blocks), dim3(512), G::LDS_BYTES,
+                       ctx->stream, in, w, b, out, 1.0f, guard, blocks);
+}
+
 static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
     Net* net = static_cast<Net*>(ctx->net);
     hipStream_t s = ctx->stream;
     using G2 = ConvGeom<16, 64, 40, 20, 16>;
     using G3 = ConvGeom<64, 128, 20, 20, 32>;
+    using B2 = ConvGeomB<16, 64, 40, 10, SPLIT_NP>;
+    using B3 = ConvGeomB<64, 128, 20, 20, SPLIT_NP>;
+    using GS = ConvGeomS<16, 64, 40, 8, 4>;
+    using GW = WinoGeom<64, 128, 20, 2>;
     if (!ctx->attr_cnn) {
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5<16, 64, 40, 20, 16>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, G2::LDS_BYTES));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5<64, 128, 20, 20, 32>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, G3::LDS_BYTES));
-#define SET_ATTR(CI_, CO_, S_, ROWS_, KIND_, NT_) SET_ATTRC(CI_, CO_, S_, ROWS_, KIND_, NT_, 16)
-#define SET_ATTRC(CI_, CO_, S_, ROWS_, KIND_, NT_, CIC_)                                                                                 \
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_split<CI_, CO_, S_, ROWS_, KIND_, NT_, CIC_>),                \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (ConvGeomB<CI_, CO_, S_, ROWS_, SplitK<KIND_>::NP, CIC_>::LDS_BYTES)))
-        SET_ATTR(16, 64, 40, 10, 0, 6); SET_ATTR(16, 64, 40, 10, 0, 3); SET_ATTR(16, 64, 40, 10, 1, 3);
-        SET_ATTR(64, 128, 20, 20, 0, 6); SET_ATTR(64, 128, 20, 20, 0, 3); SET_ATTR(64, 128, 20, 20, 1, 3);
-        SET_ATTR(16, 64, 40, 20, 1, 3); SET_ATTR(64, 128, 20, 10, 1, 3); SET_ATTR(64, 128, 20, 4, 0, 6);
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_stream<16, 64, 40, 10, 4>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (ConvGeomS<16, 64, 40, 10, 4>::LDS_BYTES)));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_stream<16, 64, 40, 8, 4>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (ConvGeomS<16, 64, 40, 8, 4>::LDS_BYTES)));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_stream<64, 128, 20, 20, 8, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (ConvGeomS<64, 128, 20, 20, 8>::LDS_BYTES)));
-#define W3A(D_) W3AB(D_, 7)
-#define W3AB(D_, B_) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_wpre<D_, B_>), hipFuncAttributeMaxDynamicSharedMemorySize, (WinoGeom<64, 128, 20, 2>::LDS_BYTES)))
-#define W2BA(D_) W2BAS(D_, 5)
-#define W2BAS(D_, S_) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv2_wpre2<D_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, W2bGeom::LDS_BYTES))
-#ifdef TREXHIP_V3_OLD
-        W3A(0);
-#endif
-        W2BA(0);
-#ifndef TREXHIP_V3_OLD
-#define W3PA(D_, B_) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_wpair<D_, B_>), hipFuncAttributeMaxDynamicSharedMemorySize, (WinoGeom<64, 128, 20, 2>::LDS_BYTES + 1024)))
-        W3PA(0, W3P_BD);
-#ifdef TREXHIP_DEV_KNOBS
-        W3PA(1, W3P_BD); W3PA(4, W3P_BD); W3PA(5, W3P_BD); W3PA(8, W3P_BD); W3PA(13, W3P_BD); W3PA(0, 3); W3PA(0, 5); W3PA(0, 7); TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_wpair<0, 5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (WinoGeom<64, 128, 20, 2>::LDS_BYTES + 1024))); TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_wpair<0, 3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (WinoGeom<64, 128, 20, 2>::LDS_BYTES + 1024)));
-#endif
-#undef W3PA
-#endif
-#define F12A(D_) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_wpre<D_>), hipFuncAttributeMaxDynamicSharedMemorySize, W12Geom::LDS_BYTES))
-        F12A(0);
-#define F12R(D_) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_rs<D_>), hipFuncAttributeMaxDynamicSharedMemorySize, W12RGeom::LDS_BYTES))
-        F12R(0);
-#ifdef TREXHIP_DEV_KNOBS
-        F12R(1); F12R(2); F12R(4); F12R(6); F12R(8); F12R(16); F12R(32); F12R(40); F12R(64); F12R(128);
-#define F12RV(...) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_rs<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, W12RGeom::LDS_BYTES))
-        F12RV(0, 3, 20, 0x202, 0, 0, 0); F12RV(128, 3, 20, 0x202, 0, 0, 0);      // ORD 0: kernel-row-major taps, the whole output transform behind them
-#undef F12RV
-#endif
-#undef F12R
-#ifdef TREXHIP_DEV_KNOBS
-        F12A(1); F12A(2); F12A(4); F12A(8); F12A(16); F12A(24); F12A(32); F12A(40); F12A(56); F12A(64); F12A(128);
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_wpre<128, 0x03>), hipFuncAttributeMaxDynamicSharedMemorySize, W12Geom::LDS_BYTES));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_wpre<0, 0x03>), hipFuncAttributeMaxDynamicSharedMemorySize, W12Geom::LDS_BYTES));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_wpre<0, 0x10>), hipFuncAttributeMaxDynamicSharedMemorySize, W12Geom::LDS_BYTES));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_wpre<0, 0x00>), hipFuncAttributeMaxDynamicSharedMemorySize, W12Geom::LDS_BYTES));
-        TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_wpre<0, 0x31>), hipFuncAttributeMaxDynamicSharedMemorySize, W12Geom::LDS_BYTES));
-#endif
-#undef F12A
-#ifdef TREXHIP_DEV_KNOBS
-        W2BA(1); W2BA(2); W2BA(3); W2BA(7); W2BA(15);
-#ifdef TREXHIP_V3_OLD
-        W3A(1); W3A(2); W3A(3); W3A(7); W3A(15); W3A(16); W3AB(0, 3); W3AB(0, 5); W3A(64); W3A(128); TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_wpre<0, 7, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (WinoGeom<64, 128, 20, 2>::LDS_BYTES)));
-#endif
-#endif
-#undef W3A
-#undef W3AB
-#undef W2BA
-#undef W2BAS
-#define WA(D_) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_wino<64, 128, 20, 2, D_>), hipFuncAttributeMaxDynamicSharedMemorySize, (WinoGeom<64, 128, 20, 2>::LDS_BYTES)))
-        WA(0);
-#ifdef TREXHIP_DEV_KNOBS
-        WA(1); WA(2); WA(3); WA(4); WA(7); WA(8); WA(15); WA(12); WA(16);
-#endif
-#undef WA
-#undef SET_ATTR
-#undef SET_ATTRC
-        if (std::getenv("TREXHIP_DEBUG_OCC")) {      // dev: resident workgroups per CU of the persistent convolutions
-            int nb2 = 0, nb3 = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, reinterpret_cast<const void*>(&k_conv2_wpre2<0, 5>), 256, W2bGeom::LDS_BYTES);
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb3, reinterpret_cast<const void*>(&k_conv5_wpre<0, 7>), 256, (WinoGeom<64, 128, 20, 2>::LDS_BYTES));
-            fprintf(stderr, "[trexhip] workgroups per CU: k_conv2_wpre2 %d (LDS %d), k_conv5_wpre %d\n", nb2, (int)W2bGeom::LDS_BYTES, nb3);
-        }
+        TH_CHECK_HIP(set_lds(&k_conv5<16, 64, 40, 20, 16>, G2::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5<64, 128, 20, 20, 32>, G3::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_split<16, 64, 40, 10, 6>, B2::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_split<16, 64, 40, 10, 3>, B2::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_split<64, 128, 20, 20, 6>, B3::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_split<64, 128, 20, 20, 3>, B3::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_split<64, 128, 20, 4, 6>, ConvGeomB<64, 128, 20, 4, SPLIT_NP>::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_stream<16, 64, 40, 8, 4>, GS::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_wino<64, 128, 20, 2>, GW::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv12_rs, W12RGeom::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv12_wpre, W12Geom::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv2_wpre2, W2bGeom::LDS_BYTES));
+        TH_CHECK_HIP(set_lds(&k_conv5_wpair, GW::LDS_BYTES + 1024));
         const int rc_any = any_set_attributes();
         if (rc_any != TREXHIP_OK) return rc_any;
         ctx->attr_cnn = true;
@@ -1967,199 +1861,95 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
     const int mode = ctx->cnn_mode;
     // the matrix-core conv1 kernels read the crops with 16-byte loads: unaligned crop buffers take the VALU kernel (and the fp32-activation chain)
     const bool aligned = (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0;
-    // default chain (cnn_wpre.h): the Winograd-domain fp16 operand images V2 / V3 are written by the producing layer.  Any of the older
-    // geometry bits of TREXHIP_CONV_GEOM (bit 11 = nothing else) selects the fp32-activation chain of rounds 1-2 instead.
+    // default chain (cnn_wpre.h): the Winograd-domain fp16 operand images V2 / V3 are written by the producing layer.  Any of bits 0-11 of
+    // TREXHIP_CONV_GEOM selects the fp32-activation chain of rounds 1-2 instead.
     const bool pre = mode == TREXHIP_CNN_FP16X3 && aligned && (ctx->tune_conv_geom & 0xfff) == 0;
     // (d_ovf: [0] fp16 range flag, [1] / [2] pass counters of the persistent conv3 / conv2.  They start at zero: the guard's plan kernel -- the last
     // reader of all three -- hands them back zeroed; net_forward clears them itself behind a pass that was not queued to its end)
     // one input channel: conv1 runs INSIDE conv2 (cnn_fused12.h: the V2 image stays in LDS); TREXHIP_CONV_GEOM bit 28 keeps the two kernels
     const bool fused12 = pre && net->CH == 1 && !(ctx->tune_conv_geom & (1 << 28));
-    if (fused12) { }
-    else if (pre) {
+    if (pre && !fused12) {
         if (net->CH == 1) hipLaunchKernelGGL((k_conv1_wpre<1>), dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->v2, net->inv1h, net->d_ovf);
         else              hipLaunchKernelGGL((k_conv1_wpre<3>), dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->v2, net->inv1h, net->d_ovf);
     }
-    else if (net->CH == 1 && !(ctx->tune_conv_geom & 16) && aligned) hipLaunchKernelGGL(k_conv1_mfma, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, (const uint32_t*)nullptr);
-    else if (net->CH == 1) hipLaunchKernelGGL((k_conv1<1>), dim3(n), dim3(256), lds1, s, d_crops, net->w1, net->b1, net->act1, S);
-    else if (net->CH == 3 && !(ctx->tune_conv_geom & 16) && aligned) hipLaunchKernelGGL(k_conv1_mfma3, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, (const uint32_t*)nullptr);
-    else              hipLaunchKernelGGL((k_conv1<3>), dim3(n), dim3(256), lds1, s, d_crops, net->w1, net->b1, net->act1, S);
-#define LAUNCH_SPLIT2 LAUNCH_SPLIT
+    else if (!pre && aligned) {
+        if (net->CH == 1) hipLaunchKernelGGL(k_conv1_mfma, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, (const uint32_t*)nullptr);
+        else              hipLaunchKernelGGL(k_conv1_mfma3, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, (const uint32_t*)nullptr);
+    }
+    else if (!pre) {
+        if (net->CH == 1) hipLaunchKernelGGL((k_conv1<1>), dim3(n), dim3(256), lds1, s, d_crops, net->w1, net->b1, net->act1, S);
+        else              hipLaunchKernelGGL((k_conv1<3>), dim3(n), dim3(256), lds1, s, d_crops, net->w1, net->b1, net->act1, S);
+    }
     stage_begin(ctx, TREXHIP_STAGE_CONV2);
-#define LAUNCH_SPLIT(CI_, CO_, S_, ROWS_, KIND_, NT_, in_, w_, b_, out_, sc_, guard_) LAUNCH_SPLITC(CI_, CO_, S_, ROWS_, KIND_, NT_, 16, in_, w_, b_, out_, sc_, guard_)
-#define LAUNCH_SPLITC(CI_, CO_, S_, ROWS_, KIND_, NT_, CIC_, in_, w_, b_, out_, sc_, guard_)                                                    \
-    hipLaunchKernelGGL((k_conv5_split<CI_, CO_, S_, ROWS_, KIND_, NT_, CIC_>),                                                                      \
-                       dim3((guard_) ? std::min(n * (ConvGeomB<CI_, CO_, S_, ROWS_, SplitK<KIND_>::NP, CIC_>::BPC), 4 * ctx->n_cus)                  \
-                                     : n * (ConvGeomB<CI_, CO_, S_, ROWS_, SplitK<KIND_>::NP, CIC_>::BPC)),                                          \
-                       dim3(512), (ConvGeomB<CI_, CO_, S_, ROWS_, SplitK<KIND_>::NP, CIC_>::LDS_BYTES), s, in_, w_, b_, out_, sc_, net->d_ovf, guard_, \
-                       n * (ConvGeomB<CI_, CO_, S_, ROWS_, SplitK<KIND_>::NP, CIC_>::BPC))
     // the role-split form (cnn_fused12rs.h): one workgroup of 8 waves per CU, consumer waves (tap loop, output transform) beside producer waves (V3
     // transform of the previous pass, V2 rows of the next), the first 15 taps' weight fragments resident in LDS.  Bit-identical to the
     // two-workgroups-per-CU kernel below and 6 % faster at 25600 crops (3.81 against 4.05 ms on one box); batches that do not give every CU a few
     // passes keep the older kernel (1000 crops: 0.207 against 0.196 ms).  TREXHIP_CONV_GEOM bit 29 forces the role-split kernel, bit 30 the older one
     const bool role_split = fused12 && !(ctx->tune_conv_geom & (1 << 30)) && ((ctx->tune_conv_geom & (1 << 29)) || n >= 3200);
+    const int n_pass2 = (n * 20 + W2bGeom::RPP - 1) / W2bGeom::RPP;
     if (role_split) {
-        const int n_pass = (n * 20 + W2bGeom::RPP - 1) / W2bGeom::RPP;
         const int wgs = ctx->n_cus;
-        static const int pk_env = std::getenv("TREXHIP_F12_PK") ? std::atoi(std::getenv("TREXHIP_F12_PK")) : 0;
-        const int pk = pk_env > 0 ? pk_env : std::max(1, std::min(32, n_pass / (wgs * 4)));
-        const int want = (n_pass + pk - 1) / pk;
-#define F12RK(D_) hipLaunchKernelGGL((k_conv12_rs<D_>), dim3(want < wgs ? want : wgs), dim3(512), W12RGeom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, \
-                           net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc)
-#ifdef TREXHIP_DEV_KNOBS
-        static const int f12r_dbg = std::getenv("TREXHIP_F12_DBG") ? std::atoi(std::getenv("TREXHIP_F12_DBG")) : 0;
-        switch (f12r_dbg) { case 1: F12RK(1); break; case 2: F12RK(2); break; case 4: F12RK(4); break; case 6: F12RK(6); break; case 8: F12RK(8); break; case 16: F12RK(16); break; case 32: F12RK(32); break; case 40: F12RK(40); break; case 64: F12RK(64); break;
-            case 128: hipLaunchKernelGGL((k_conv12_rs<128>), dim3(want < wgs ? want : wgs), dim3(512), W12RGeom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc, reinterpret_cast<unsigned long long*>(ctx->d_cnt_px)); break;
-#define F12RKV(...) hipLaunchKernelGGL((k_conv12_rs<__VA_ARGS__>), dim3(want < wgs ? want : wgs), dim3(512), W12RGeom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc)
-            case 230: F12RKV(0, 3, 20, 0x202, 0, 0, 0); break;
-            case 231: hipLaunchKernelGGL((k_conv12_rs<128, 3, 20, 0x202, 0, 0, 0>), dim3(want < wgs ? want : wgs), dim3(512), W12RGeom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc, reinterpret_cast<unsigned long long*>(ctx->d_cnt_px)); break;
-#undef F12RKV
-            default: F12RK(0); }
-#else
-        F12RK(0);
-#endif
-#undef F12RK
+        const int pk = std::max(1, std::min(32, n_pass2 / (wgs * 4)));
+        const int want = (n_pass2 + pk - 1) / pk;
+        hipLaunchKernelGGL(k_conv12_rs, dim3(std::min(want, wgs)), dim3(512), W12RGeom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h,
+                           net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc);
     }
     else if (fused12) {
-        const int n_pass = (n * 20 + W2bGeom::RPP - 1) / W2bGeom::RPP;
-#ifdef TREXHIP_DEV_KNOBS
-        static const int wgs_env = std::getenv("TREXHIP_F12_WGS") ? std::atoi(std::getenv("TREXHIP_F12_WGS")) : 2;      // dev: workgroups per CU
-        const int wgs = wgs_env * ctx->n_cus;
-#else
         const int wgs = 2 * ctx->n_cus;
-#endif
         // passes per ticket: long tickets save the 4 extra rows of a ticket's first pass, short ones keep every workgroup busy when the batch is small
-        static const int pk_env = std::getenv("TREXHIP_F12_PK") ? std::atoi(std::getenv("TREXHIP_F12_PK")) : 0;
-        const int pk = pk_env > 0 ? pk_env : std::max(1, std::min(16, n_pass / (wgs * 4)));
+        const int pk = std::max(1, std::min(16, n_pass2 / (wgs * 4)));
         // (a tail of short tickets was measured and dropped: the dynamic tickets already finish together, and every ticket's first pass produces 10 rows instead of 6)
-        const int want = (n_pass + pk - 1) / pk;
-#define F12K(D_) hipLaunchKernelGGL((k_conv12_wpre<D_>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, \
-                           net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc)
-#ifdef TREXHIP_DEV_KNOBS   // ablations: TREXHIP_F12_DBG = 1 no crop loads, 2 no conv1 MFMAs, 4 no P2 transform, 8 no production, 16 no epilogue, 32 no tap loop
-        static const int f12_dbg = std::getenv("TREXHIP_F12_DBG") ? std::atoi(std::getenv("TREXHIP_F12_DBG")) : 0;
-        switch (f12_dbg) { case 1: F12K(1); break; case 2: F12K(2); break; case 4: F12K(4); break; case 8: F12K(8); break; case 16: F12K(16); break; case 24: F12K(24); break; case 32: F12K(32); break; case 40: F12K(40); break; case 56: F12K(56); break; case 64: F12K(64); break;
-            case 128: hipLaunchKernelGGL((k_conv12_wpre<128>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc, reinterpret_cast<unsigned long long*>(ctx->d_cnt_px)); break;   // phase stamps -> trexhip_debug_read (tools/f12_stamps.py)
-            case 129: hipLaunchKernelGGL((k_conv12_wpre<128, 0x03>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc, reinterpret_cast<unsigned long long*>(ctx->d_cnt_px)); break;   // the same with the priorities of rounds 3-4
-            case 100: hipLaunchKernelGGL((k_conv12_wpre<0, 0x03>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc); break;
-            case 101: hipLaunchKernelGGL((k_conv12_wpre<0, 0x10>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc); break;
-            case 102: hipLaunchKernelGGL((k_conv12_wpre<0, 0x00>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc); break;
-            case 103: hipLaunchKernelGGL((k_conv12_wpre<0, 0x31>), dim3(want < wgs ? want : wgs), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc); break;
-            default: F12K(0); }
-#else
-        F12K(0);
-#endif
-#undef F12K
+        const int want = (n_pass2 + pk - 1) / pk;
+        hipLaunchKernelGGL(k_conv12_wpre, dim3(std::min(want, wgs)), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h,
+                           net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc);
     }
-    else if (pre) {
-        // two workgroups per CU, one M-tile per wave, operand planes fetched by LDS-DMA during the epilogue
-        const int n_pass = (n * 20 + W2bGeom::RPP - 1) / W2bGeom::RPP;
-#define W2K(D_) W2KS(D_, 5)
-        const int wgs = 2 * ctx->n_cus;
-#define W2KS(D_, S_) hipLaunchKernelGGL((k_conv2_wpre2<D_, S_>), dim3(n_pass < wgs ? n_pass : wgs), dim3(256), W2bGeom::LDS_BYTES, s, \
-                           net->v2, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2)
-#ifdef TREXHIP_DEV_KNOBS   // ablations: TREXHIP_CONV_GEOM bits 16..21 = 1 no staging, 2 no epilogue, 4 no weight loads, 8 no A reads, 32 no V3 transform
-        switch ((ctx->tune_conv_geom >> 16) & 63) { case 1: W2K(1); break; case 2: W2K(2); break; case 3: W2K(3); break; case 7: W2K(7); break; case 15: W2K(15); break; default: W2K(0); }
-#else
-        W2K(0);
-#endif
-#undef W2K
-#undef W2KS
-    }
+    else if (pre)       // two workgroups per CU, one M-tile per wave, operand planes fetched by LDS-DMA during the epilogue
+        hipLaunchKernelGGL(k_conv2_wpre2, dim3(std::min(n_pass2, 2 * ctx->n_cus)), dim3(256), W2bGeom::LDS_BYTES, s,
+                           net->v2, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2);
     else if (mode == TREXHIP_CNN_FP32)
         hipLaunchKernelGGL((k_conv5<16, 64, 40, 20, 16>), dim3(n * G2::BPC), dim3(512), G2::LDS_BYTES, s, net->act1, net->w2, net->b2, net->act2);
-    else if (mode == TREXHIP_CNN_BF16X6) LAUNCH_SPLIT(16, 64, 40, 10, 0, 6, net->act1, net->w2s, net->b2, net->act2, 1.0f, (const uint32_t*)nullptr);
-    else if (mode == TREXHIP_CNN_BF16X3) LAUNCH_SPLIT(16, 64, 40, 10, 0, 3, net->act1, net->w2s, net->b2, net->act2, 1.0f, (const uint32_t*)nullptr);
-    else if (!(ctx->tune_conv_geom & (4 | 64)))   // 8 output rows per workgroup: 320 pixels = exactly 10 M-tiles, 3 workgroups per CU (1.15 ms; 10 rows: 1.31 ms)
-        hipLaunchKernelGGL((k_conv5_stream<16, 64, 40, 8, 4>), dim3(n * (ConvGeomS<16, 64, 40, 8, 4>::BPC)), dim3(256),
-                           (ConvGeomS<16, 64, 40, 8, 4>::LDS_BYTES), s, net->act1, net->w2h, net->b2, net->act2, net->inv2h, net->d_ovf, n * (ConvGeomS<16, 64, 40, 8, 4>::BPC), (uint32_t*)nullptr);
-    else if (!(ctx->tune_conv_geom & 4))
-        hipLaunchKernelGGL((k_conv5_stream<16, 64, 40, 10, 4>), dim3(n * (ConvGeomS<16, 64, 40, 10, 4>::BPC)), dim3(256),
-                           (ConvGeomS<16, 64, 40, 10, 4>::LDS_BYTES), s, net->act1, net->w2h, net->b2, net->act2, net->inv2h, net->d_ovf, n * (ConvGeomS<16, 64, 40, 10, 4>::BPC), (uint32_t*)nullptr);
-    else if (ctx->tune_conv_geom & 1)    LAUNCH_SPLIT(16, 64, 40, 20, 1, 3, net->act1, net->w2h, net->b2, net->act2, net->inv2h, (const uint32_t*)nullptr);
-    else                                 LAUNCH_SPLIT(16, 64, 40, 10, 1, 3, net->act1, net->w2h, net->b2, net->act2, net->inv2h, (const uint32_t*)nullptr);
+    else if (mode == TREXHIP_CNN_BF16X6) launch_split<16, 64, 40, 10, 6>(ctx, n, net->act1, net->w2s, net->b2, net->act2, nullptr);
+    else if (mode == TREXHIP_CNN_BF16X3) launch_split<16, 64, 40, 10, 3>(ctx, n, net->act1, net->w2s, net->b2, net->act2, nullptr);
+    else                // 8 output rows per workgroup: 320 pixels = exactly 10 M-tiles, 3 workgroups per CU (1.15 ms; 10 rows: 1.31 ms)
+        hipLaunchKernelGGL((k_conv5_stream<16, 64, 40, 8, 4>), dim3(n * GS::BPC), dim3(256), GS::LDS_BYTES, s,
+                           net->act1, net->w2h, net->b2, net->act2, net->inv2h, net->d_ovf, n * GS::BPC);
     stage_end(ctx, TREXHIP_STAGE_CONV2);
     stage_begin(ctx, TREXHIP_STAGE_CONV3);
+    const int n_pass3 = (n * GW::TPC + GW::MB - 1) / GW::MB;
     if (pre) {
-        using GW = WinoGeom<64, 128, 20, 2>;
-        const int n_pass = (n * GW::TPC + GW::MB - 1) / GW::MB;
-#define W3K(D_) W3KB(D_, 7)
         // tickets of 4 consecutive passes (their halo rows are L2 hits) for the first 7/8 of the passes, single passes behind them; a batch that
         // gives a workgroup fewer than 4 tickets goes out pass by pass altogether (100 crops = 157 passes: 157 workgroups at once instead of 40
         // that walk 4 passes each: 93 -> 35 us)
-        const int n_big3 = n_pass >= 16 * ctx->n_cus ? (int)((long long)n_pass * 7 / 8) / 4 : 0, want3 = n_big3 + (n_pass - n_big3 * 4);
-#define W3KB(D_, B_) hipLaunchKernelGGL((k_conv5_wpre<D_, B_>), dim3(want3 < ctx->n_cus ? want3 : ctx->n_cus), dim3(256), GW::LDS_BYTES, s, \
-                           net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, n_big3)
-#ifndef TREXHIP_V3_OLD
-#define W3P(D_, B_) hipLaunchKernelGGL((k_conv5_wpair<D_, B_>), dim3(want3 < ctx->n_cus ? want3 : ctx->n_cus), dim3(256), GW::LDS_BYTES + 1024 /* slack for the last DMA instruction */, s, \
-                           net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, n_big3)
-#ifdef TREXHIP_DEV_KNOBS
-        switch ((ctx->tune_conv_geom >> 24) & 15) { case 1: W3P(1, W3P_BD); break; case 2: W3P(4, W3P_BD); break; case 3: W3P(5, W3P_BD); break; case 7: W3P(8, W3P_BD); break; case 15: W3P(13, W3P_BD); break;
-                                                    case 9: W3P(0, 3); break; case 10: W3P(0, 5); break; case 11: W3P(0, 7); break; case 12: hipLaunchKernelGGL((k_conv5_wpair<0, 5, 2>), dim3(want3 < ctx->n_cus ? want3 : ctx->n_cus), dim3(256), GW::LDS_BYTES + 1024, s, net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, n_big3); break; case 13: hipLaunchKernelGGL((k_conv5_wpair<0, 3, 2>), dim3(want3 < ctx->n_cus ? want3 : ctx->n_cus), dim3(256), GW::LDS_BYTES + 1024, s, net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, n_big3); break; default: W3P(0, W3P_BD); }
-#else
-        W3P(0, W3P_BD);
-#endif
-#undef W3P
-#else
-#ifdef TREXHIP_DEV_KNOBS
-        switch ((ctx->tune_conv_geom >> 24) & 15) { case 1: W3K(1); break; case 2: W3K(2); break; case 3: W3K(3); break; case 7: W3K(7); break; case 15: W3K(15); break; case 8: W3K(16); break; case 9: W3KB(0, 3); break; case 10: W3KB(0, 5); break; case 12: W3K(64); break; case 13: W3K(128); break; case 11: hipLaunchKernelGGL((k_conv5_wpre<0, 7, 1>), dim3(n_pass < ctx->n_cus ? n_pass : ctx->n_cus), dim3(256), GW::LDS_BYTES, s, net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, 0); break; default: W3K(0); }
-#else
-        W3K(0);
-#endif
-#endif
-#undef W3K
-#undef W3KB
+        const int n_big3 = n_pass3 >= 16 * ctx->n_cus ? (int)((long long)n_pass3 * 7 / 8) / 4 : 0, want3 = n_big3 + (n_pass3 - n_big3 * 4);
+        hipLaunchKernelGGL(k_conv5_wpair, dim3(std::min(want3, ctx->n_cus)), dim3(256), GW::LDS_BYTES + 1024 /* slack for the last DMA instruction */, s,
+                           net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, n_big3);
     }
     else if (mode == TREXHIP_CNN_FP32)
         hipLaunchKernelGGL((k_conv5<64, 128, 20, 20, 32>), dim3(n * G3::BPC), dim3(512), G3::LDS_BYTES, s, net->act2, net->w3, net->b3, net->act3);
-    else if (mode == TREXHIP_CNN_BF16X6) LAUNCH_SPLIT(64, 128, 20, 20, 0, 6, net->act2, net->w3s, net->b3, net->act3, 1.0f, (const uint32_t*)nullptr);
-    else if (mode == TREXHIP_CNN_BF16X3) LAUNCH_SPLIT(64, 128, 20, 20, 0, 3, net->act2, net->w3s, net->b3, net->act3, 1.0f, (const uint32_t*)nullptr);
-    else if (!(ctx->tune_conv_geom & 256)) {
-        // Winograd F(4,5) along x: 0.4x the matrix work of the direct form (TREXHIP_CONV_GEOM bit 8: the direct kernels below)
-        using GW = WinoGeom<64, 128, 20, 2>;
-        const int n_pass = (n * GW::TPC + GW::MB - 1) / GW::MB;
-#define WL(D_) hipLaunchKernelGGL((k_conv5_wino<64, 128, 20, 2, D_>), dim3(n_pass < ctx->n_cus ? n_pass : ctx->n_cus), dim3(GW::NTHR), GW::LDS_BYTES, s, net->act2, net->w3w, net->b3, net->act3, net->inv3w, net->d_ovf, n, net->d_ovf + 1)
-#ifdef TREXHIP_DEV_KNOBS   // ablations (tools/time_wino.py): 1 no staging, 2 no epilogue, 4 no weight loads, 8 no A reads, 16 staging loads from one hot row
-        switch ((ctx->tune_conv_geom >> 12) & 15) { case 1: WL(1); break; case 2: WL(2); break; case 3: WL(3); break; case 4: WL(4); break; case 7: WL(7); break; case 8: WL(8); break; case 15: WL(15); break; case 12: WL(12); break; case 6: WL(16); break; default: WL(0); }
-#else
-        WL(0);
-#endif
-#undef WL
-    }
-    else if (!(ctx->tune_conv_geom & 8))
-        // one workgroup per CU (110 KB LDS, 256 VGPRs): persistent workgroups walk the crops and stage the next crop's first
-        // chunk under the current crop's last one (TREXHIP_CONV_GEOM bit 7: one workgroup per crop instead)
-        hipLaunchKernelGGL((k_conv5_stream<64, 128, 20, 20, 8, true>), dim3((ctx->tune_conv_geom & 128) || n < ctx->n_cus ? n : ctx->n_cus), dim3(512),
-                           (ConvGeomS<64, 128, 20, 20, 8>::LDS_BYTES), s, net->act2, net->w3h, net->b3, net->act3, net->inv3h, net->d_ovf, n, net->d_ovf + 1);
-    else if (ctx->tune_conv_geom & 2)    LAUNCH_SPLIT(64, 128, 20, 10, 1, 3, net->act2, net->w3h, net->b3, net->act3, net->inv3h, (const uint32_t*)nullptr);
-    else                                 LAUNCH_SPLIT(64, 128, 20, 20, 1, 3, net->act2, net->w3h, net->b3, net->act3, net->inv3h, (const uint32_t*)nullptr);   // 32-channel chunks (CIC=32) measured slower: 3.7 vs 3.0 ms
+    else if (mode == TREXHIP_CNN_BF16X6) launch_split<64, 128, 20, 20, 6>(ctx, n, net->act2, net->w3s, net->b3, net->act3, nullptr);
+    else if (mode == TREXHIP_CNN_BF16X3) launch_split<64, 128, 20, 20, 3>(ctx, n, net->act2, net->w3s, net->b3, net->act3, nullptr);
+    else                // Winograd F(4,5) along x: 0.4x the matrix work of the direct form
+        hipLaunchKernelGGL((k_conv5_wino<64, 128, 20, 2>), dim3(std::min(n_pass3, ctx->n_cus)), dim3(GW::NTHR), GW::LDS_BYTES, s,
+                           net->act2, net->w3w, net->b3, net->act3, net->inv3w, net->d_ovf, n, net->d_ovf + 1);
     stage_end(ctx, TREXHIP_STAGE_CONV3);
-    // split-K planes of fc1 (summed in k_head): 10 keeps every CU busy at a few thousand crops; TREXHIP_FC1_KSPLIT overrides (dev)
-    static const int ks_env = std::getenv("TREXHIP_FC1_KSPLIT") ? std::atoi(std::getenv("TREXHIP_FC1_KSPLIT")) : 0;
+    // split-K planes of fc1 (summed in k_head): FC1_KSPLIT keeps every CU busy at a few thousand crops
     // (25600 crops: 10 planes 344 + 72 us for fc1 + head, 5 planes 319 + 66, 4: 365, 8: 381, 2: 347)
     // (the number of planes must not depend on n -- 5 planes above 12800 crops gave the same crop bit-different probabilities in batches
     // of 12799 and 12800; 10 always costs 31 us of a 9 ms step)
-    const int ks1 = (ks_env > 0 && ks_env <= FC1_KSPLIT && 400 % ks_env == 0) ? ks_env : FC1_KSPLIT;
-    const bool split1 = mode == TREXHIP_CNN_FP16X3 && !(ctx->tune_conv_geom & 32);
-    if (split1)
-        if (n <= 1024)     // small batches: 32 crops per workgroup (same sums in the same order: a crop's row does not depend on the kernel its batch got)
-            hipLaunchKernelGGL(k_fc1_split<1>, dim3((n + 31) / 32, ks1), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
-        else {
-            static const int fc1_mt = std::getenv("TREXHIP_FC1_MT") ? std::atoi(std::getenv("TREXHIP_FC1_MT")) : 4;      // (dev: crops per workgroup / 32; the same sums in the same order)
-            if (fc1_mt == 2) hipLaunchKernelGGL(k_fc1_split<2>, dim3((n + 63) / 64, ks1), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
-            else if (fc1_mt == 1) hipLaunchKernelGGL(k_fc1_split<1>, dim3((n + 31) / 32, ks1), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
-            else
-            hipLaunchKernelGGL(k_fc1_split<4>, dim3((n + 127) / 128, ks1), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
-        }
-    else
+    if (mode != TREXHIP_CNN_FP16X3)
         hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, 12800, (const uint32_t*)nullptr);
-    static const int head_small_max = std::getenv("TREXHIP_HEAD_SMALL_MAX") ? std::atoi(std::getenv("TREXHIP_HEAD_SMALL_MAX")) : 1024;      // (dev: where k_head takes over)
-    const bool small_head = n <= head_small_max;
+    else if (n <= 1024)     // small batches: 32 crops per workgroup (same sums in the same order: a crop's row does not depend on the kernel its batch got)
+        hipLaunchKernelGGL(k_fc1_split<1>, dim3((n + 31) / 32, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
+    else
+        hipLaunchKernelGGL(k_fc1_split<4>, dim3((n + 127) / 128, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
+    const bool small_head = n <= 1024;
     if (small_head)     // one crop per wave, nothing but latency to save (k_head_small); same bits.  Its first workgroup also makes the range guard's plan
         hipLaunchKernelGGL(k_head_small, dim3((n + 3) / 4), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                           d_probs, d_logits, n, net->classes, split1 ? ks1 : FC1_KSPLIT,
+                           d_probs, d_logits, n, net->classes, FC1_KSPLIT,
                            mode == TREXHIP_CNN_FP16X3 ? net->d_ovf : (uint32_t*)nullptr, net->d_ovfc, mode == TREXHIP_CNN_FP16X3 ? net->d_ovf + 4 : (uint32_t*)nullptr);
     else
-    hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                       d_probs, d_logits, n, net->classes, (const uint32_t*)nullptr, split1 ? ks1 : FC1_KSPLIT);
+        hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
+                           d_probs, d_logits, n, net->classes, (const uint32_t*)nullptr, FC1_KSPLIT);
     if (mode == TREXHIP_CNN_FP16X3) {
         // guarded re-run with the bf16 split: every workgroup returns at once unless an activation left the fp16 range; k_guard_plan lists the
         // flagged crops (or orders the whole batch when the flag came from a kernel that does not know the crop) and the re-run follows its plan
@@ -2169,18 +1959,15 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
             if (net->CH == 1) hipLaunchKernelGGL(k_conv1_mfma, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, g);
             else              hipLaunchKernelGGL(k_conv1_mfma3, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, g);
         }
-        LAUNCH_SPLIT2(16, 64, 40, 10, 0, 6, net->act1, net->w2s, net->b2, net->act2, 1.0f, g);
+        launch_split<16, 64, 40, 10, 6>(ctx, n, net->act1, net->w2s, net->b2, net->act2, g);
         // (conv3 in bands of 4 rows, five workgroups per crop: a re-run is a handful of crops, and one workgroup walking a whole crop's 2 GFLOP
         // alone took 0.4 ms of the 0.5 ms a tripped guard cost)
-        LAUNCH_SPLIT2(64, 128, 20, 4, 0, 6, net->act2, net->w3s, net->b3, net->act3, 1.0f, g);
+        launch_split<64, 128, 20, 4, 6>(ctx, n, net->act2, net->w3s, net->b3, net->act3, g);
         hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, 12800, g);
         hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
                            d_probs, d_logits, n, net->classes, g, FC1_KSPLIT);
     }
     stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
-#undef LAUNCH_SPLIT
-#undef LAUNCH_SPLITC
-#undef LAUNCH_SPLIT2
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
 }

@@ -1,11 +1,12 @@
 // cnn_conv3p.h -- conv3 of the identity network's default chain, walked PAIR BY PAIR (round 5).  Included by cnn.hip after cnn_wpre.h.
 //
 // Network: visual_identification_network_torch.py:184-258 (V118_3, eval mode): conv3 = 5x5 'same', 64 -> 128 channels on the 20x20 map, then
-// ReLU and the 2x2 max-pool.  Arithmetic as in k_conv5_wpre (cnn_wpre.h): F(4,5) Winograd along x -- 8 position products per kernel row give 4
-// neighbouring outputs --, direct along y, both operands as two fp16 pieces, three piece products per term, fp32 accumulation; per position the
-// order of the sums is the same (16-channel chunk, then kernel row), so the position sums are bit-identical to k_conv5_wpre's.
+// ReLU and the 2x2 max-pool.  Arithmetic: F(4,5) Winograd along x -- 8 position products per kernel row give 4 neighbouring outputs --, direct
+// along y, both operands as two fp16 pieces, three piece products per term, fp32 accumulation; per position the sums run over the 16-channel
+// chunks, then the kernel rows (the order of k_conv5_wino and of the chunk-major kernel of rounds 3-4, k_conv5_wpre, whose position sums are
+// bit-identical to these).
 //
-// What is different is the ORDER OF THE POSITIONS.  k_conv5_wpre walks a pass chunk by chunk with all 8 positions of a chunk inside one tap
+// What is different from k_conv5_wpre is the ORDER OF THE POSITIONS.  It walked a pass chunk by chunk with all 8 positions of a chunk inside one tap
 // group: every position is final only at the very end of the pass, 16 accumulator tuples (all 256 accumulator registers) are live throughout,
 // and the output transform A^T, the pool and the stores -- ~1000 vector instructions per pass -- wait behind the last tap with nothing to run
 // beside them (one wave per SIMD): 19 % of a pass.  Here a pass is 4 UNITS of 40 taps, one per position pair in the order (1,2) (3,4) (5,6) (0,7),
@@ -18,21 +19,23 @@
 // behind the last tap; the next pass's A offsets are computed under the last unit as well.
 // (y0 takes position 0 last instead of first: the only change in the order of a sum against k_conv5_wpre; probabilities differ by <= 6e-7.)
 //
-// Measured (25600 crops, A/B against k_conv5_wpre on the same boxes, tools/r05_conv3.sh): 4.42 -> 4.21, 4.57 -> 4.38 ms; matrix pipe 0.64 ->
+// Measured (25600 crops, A/B against k_conv5_wpre on the same boxes): 4.42 -> 4.21, 4.57 -> 4.38 ms; matrix pipe 0.64 ->
 // 0.69 busy (profiles/r05_pmc_conv_pair.txt) at a clock that FALLS as the pipe fills (1.56 -> 1.50 GHz: the kernel is power-limited; with its
 // operand loads switched off the same 960 MFMAs per pass run at 2.6 GHz).  A first version with the same tap order was SLOWER than
 // k_conv5_wpre (4.50 against 4.39): 47 instructions per tap instead of 28 -- spilled scalars, hoisted address arithmetic, lane masks around the
 // DMA -- and a wave issues one instruction per ~4.5 cycles, so a tap of 6 MFMAs (192 cycles) has room for ~40.  Weight fragments 3 / 5 / 7 taps
 // ahead: 4.52 / 4.39 / 4.39; A fragments 2 taps ahead: no change.
 
-template <int DBG = 0, int BD = 7, int AD = 1, int PK = 4, int DT0 = 2>      // DBG (dev builds): 1 no staging, 2 no folding / tail, 4 no weight loads, 8 no A reads; BD: taps of lead of the weight fragments; PK: passes per ticket
 __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__ v3, const uint4* __restrict__ wp /*[4][5][8][2][2][128] x 16 B*/,
                                                      const float* __restrict__ bias, float* __restrict__ out, const float out_scale,
                                                      const int n_crops, uint32_t* __restrict__ pass_ctr,
                                                      const int n_big /* tickets of PK passes; the passes behind them go out one by one */) {
     constexpr int CI = 64, CO = 128, S = 20, TPW = 2;
+    constexpr int BD = 5;         // taps of lead of the weight fragments (measured above)
+    constexpr int AD = 1;         // taps of lead of the A fragments
+    constexpr int PK = 4;         // passes per ticket: their halo rows are L2 hits
+    constexpr int DT0 = 2;        // the tap at which the DMA of the next unit starts
     using G = WinoGeom<CI, CO, S, TPW>;
-    static_assert(V3_PAIR, "k_conv5_wpair reads the pair-major V3");
     static_assert(G::NTHR == 256 && G::RP0 == 1280 && G::NCH * 2 * G::RP0 == V3_ROWB && G::NT == 4 && G::WM == 1, "geometry");
     static_assert(BD >= 1 && BD <= 7, "weight ring of 8 taps");
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
@@ -87,12 +90,10 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     const int ooff = (4 * h * CO + co) * 4;
     int qmin, nrows;
     wino_pass_rows<G, S>(pass, total_tiles, qmin, nrows);
-    if (!(DBG & 1)) {
-        const __amdgpu_buffer_rsrc_t srs0 = stage_rsrc(0, qmin, nrows);
+    const __amdgpu_buffer_rsrc_t srs0 = stage_rsrc(0, qmin, nrows);
 #pragma unroll
-        for (int k = 0; k < NDW; ++k) P3_DMA(k, srs0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    for (int k = 0; k < NDW; ++k) P3_DMA(k, srs0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // tap tt of unit g: chunk tt / 10, kernel row (tt % 10) / 2, position PAIRS[g][tt & 1]; its weights [chunk][ky][position] x BV x 16 bytes
     auto w_off = [](const int g, const int tt) {
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
 #pragma clang loop unroll(full)
             for (int tt = 0; tt < 40; ++tt) {
                 const int cur = tt % (AD + 1), nxt = (tt + AD) % (AD + 1);
-                if (!(DBG & 8) && tt + AD < 40) {
+                if (tt + AD < 40) {
                     const uint8_t* an = pbase + (((tt + AD) / 10) * 2 + ((tt + AD) & 1)) * G::PS;
 #pragma unroll
                     for (int m = 0; m < TPW; ++m) {
@@ -215,12 +216,10 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                         af[nxt][m][1] = *reinterpret_cast<const uint4*>(an + aoff[m][((tt + AD) % 10) / 2] + G::PLANE);
                     }
                 }
-                if (!(DBG & 4)) {
-                    const int wt = tt + BD < 40 ? w_off(g, tt + BD) : w_off(sg, tt + BD - 40);
-                    bq[(tt + BD) % 8][0] = buf_load16(wrs, boff, wt);
-                    bq[(tt + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
-                }
-                if (!(DBG & 1) && tt >= DT0 && tt < DT0 + NDW) P3_DMA(tt - DT0, srs, (g & 1) ^ 1);
+                const int wt = tt + BD < 40 ? w_off(g, tt + BD) : w_off(sg, tt + BD - 40);
+                bq[(tt + BD) % 8][0] = buf_load16(wrs, boff, wt);
+                bq[(tt + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
+                if (tt >= DT0 && tt < DT0 + NDW) P3_DMA(tt - DT0, srs, (g & 1) ^ 1);
                 const int hp = tt & 1;
                 const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tt % 8][0]);
                 const f16x8 b2 = __builtin_bit_cast(f16x8, bq[tt % 8][1]);
@@ -233,20 +232,18 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                 for (int m = 0; m < TPW; ++m) acc[g & 1][m][hp] = mfma16(a1[m], b2, acc[g & 1][m][hp]);
 #pragma unroll
                 for (int m = 0; m < TPW; ++m) acc[g & 1][m][hp] = mfma16(a1[m], b1, acc[g & 1][m][hp]);
-                if (!(DBG & 2)) {
-                    if (g == 0) {
-                        // the previous pass's tail (its positions 0 and 7 are in bank 1, which this pass first writes in unit 1)
-                        if (tt >= 2 && tt < 34 && !(tt & 1)) tail(ors_prev, (tt - 2) / 16, ((tt - 2) / 2) % 8);
-                    } else if (tt >= 2 && tt < 34) {
-                        fold(g - 1, (tt - 2) / 16, (tt - 2) % 16);
-                    }
-                    // the next pass's A offsets, in place: kernel row ky was last read for tap 31 + 2 ky of this unit, one tap ahead
-                    if (last_u && have_next && (tt == 28 || tt == 30)) a_base(next_pass, qmin_n, (tt - 28) / 2, an_in[(tt - 28) / 2], an_z[(tt - 28) / 2], an_y[(tt - 28) / 2]);
-                    if (last_u && have_next && (tt == 39 || (tt >= 32 && tt < 39 && !(tt & 1)))) {
-                        const int ky = tt == 39 ? 4 : (tt - 32) / 2;
+                if (g == 0) {
+                    // the previous pass's tail (its positions 0 and 7 are in bank 1, which this pass first writes in unit 1)
+                    if (tt >= 2 && tt < 34 && !(tt & 1)) tail(ors_prev, (tt - 2) / 16, ((tt - 2) / 2) % 8);
+                } else if (tt >= 2 && tt < 34) {
+                    fold(g - 1, (tt - 2) / 16, (tt - 2) % 16);
+                }
+                // the next pass's A offsets, in place: kernel row ky was last read for tap 31 + 2 ky of this unit, one tap ahead
+                if (last_u && have_next && (tt == 28 || tt == 30)) a_base(next_pass, qmin_n, (tt - 28) / 2, an_in[(tt - 28) / 2], an_z[(tt - 28) / 2], an_y[(tt - 28) / 2]);
+                if (last_u && have_next && (tt == 39 || (tt >= 32 && tt < 39 && !(tt & 1)))) {
+                    const int ky = tt == 39 ? 4 : (tt - 32) / 2;
 #pragma unroll
-                        for (int m = 0; m < TPW; ++m) aoff[m][ky] = a_offset(an_in[m], an_z[m], an_y[m], ky);
-                    }
+                    for (int m = 0; m < TPW; ++m) aoff[m][ky] = a_offset(an_in[m], an_z[m], an_y[m], ky);
                 }
                 __builtin_amdgcn_sched_group_barrier(0x100, 2 * TPW, 0);
                 __builtin_amdgcn_sched_group_barrier(0x020, 10, 0);
@@ -259,18 +256,16 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             }
             // this wave's part of the next unit has landed: loads return in order, so everything older than the 2 x BD weight fragments in
             // flight is complete -- the DMA instructions were issued before them (stores in between only make the wait stricter)
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"((DBG & 4) ? 0 : 2 * BD) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * BD) : "memory");
             __syncthreads();
         }
         ors_prev = ors;
         if (!have_next) break;
         pass = next_pass; qmin = qmin_n; nrows = nrows_n;
     }
-    if (!(DBG & 2)) {          // the last pass's tail has no next pass to run under
-        // (fold of unit 2 ran under unit 3; unit 3's pair is positions 0 and 7, taken by the tail itself)
+    // the last pass's tail has no next pass to run under (fold of unit 2 ran under unit 3; unit 3's pair is positions 0 and 7, taken by the tail itself)
 #pragma unroll
-        for (int b = 0; b < 16; ++b) tail(ors_prev, b / 8, b % 8);
-    }
+    for (int b = 0; b < 16; ++b) tail(ors_prev, b / 8, b % 8);
 #undef P3_DMA
 #undef P3_PIN
 }

@@ -26,17 +26,18 @@ struct W12Geom {
     static_assert(2 * (LDS_BYTES + 64) <= 160 * 1024, "two workgroups per CU");
 };
 
-template <int DBG = 0, int PRIO = 0x30, int STAGGER = 5, int AD = 1, int BD = 3>      // PRIO: s_setprio of (the vector phases, the tap loop) as hex digits      // DBG (dev builds): 1 no crop loads, 2 no conv1 MFMAs, 4 no P2 transform, 8 no production at all, 16 no epilogue, 32 no tap loop, 64 half the weight fragments (the second piece = a copy of the first: wrong results, same matrix work), 128 phase stamps
 __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restrict__ crops /*[N][80][80]*/, const uint4* __restrict__ w1tab /*[16][64]*/,
                                                         const float* __restrict__ bias1, const float inv_scale1,
                                                         const uint4* __restrict__ wp /*[5][8][2][2][64] x 16 B*/, const float* __restrict__ bias,
                                                         uint8_t* __restrict__ v3, const float out_scale, uint32_t* __restrict__ overflow,
                                                         const int n_crops, uint32_t* __restrict__ pass_ctr, const int PK /* consecutive passes per ticket: the first one produces 10 rows, the others 6 */,
-                                                        uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */,
-                                                        unsigned long long* __restrict__ dbg_stamps = nullptr /* DBG & 128: cycles per phase of workgroups 0 and gridDim.x / 2 */) {
+                                                        uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */) {
     using G = W2bGeom;
     using F = W12Geom;
     constexpr int CO = 64, S = 40;
+    // PRIO: s_setprio of (the vector phases, the tap loop) as hex digits (why: at the tap loop); STAGGER: x 1024 cycles (at the loop head);
+    // AD / BD: taps of lead of the A / weight fragments (as k_conv2_wpre2)
+    constexpr int PRIO = 0x30, STAGGER = 5, AD = 1, BD = 3;
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
     __shared__ int s_next_pass;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -64,10 +65,6 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
             ovf = false;
         }
     };
-    // DBG & 128 (dev builds): thread 0 of two workgroups sums the cycles between the phase boundaries of its passes (tools/f12_stamps.py)
-    unsigned long long st_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
-    bool st_on = false;                                                  // switched on behind the prologue
-#define F12_STAMP(i_) do { if ((DBG & 128) && st_on) { const unsigned long long t_ = __builtin_readcyclecounter(); st_sum[i_] += t_ - st_last; st_last = t_; } } while (0)
 #define W2B_ROWS(pass_, qmin_, nrows_)                                                                                           \
     do {                                                                                                                         \
         const int gp0_ = (pass_) * G::RPP;                                                                                       \
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
     auto prefetch = [&](const int lo, const int hi) {
         const int nr = hi - lo < F::CHUNK ? hi - lo : F::CHUNK;
         const int it = wave * 64 + lane;
-        if (wave < 3 && it < nr * 30 && !(DBG & (1 | 8))) {
+        if (wave < 3 && it < nr * 30) {
             W12_ITEM(it, lo)
             const int iyc = iy < 0 ? 0 : (iy > 79 ? 79 : iy);
             wpre_dma16(crops_u, (uint32_t)((crop * 80 + iyc) * 80 + u * 16), raw_lds + (uint32_t)(wave * 1024));
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
             for (int it = tid; it < nr * 30; it += 256) {
                 W12_ITEM(it, c0)
                 uint4 px = make_uint4(0, 0, 0, 0);
-                if (!(DBG & 1) && iy >= 0 && iy < 80) {
+                if (iy >= 0 && iy < 80) {
                     if (from_raw) px = *reinterpret_cast<const uint4*>(ldsb + F::RAW_OFF + it * 16);
                     else px = *reinterpret_cast<const uint4*>(crops + ((size_t)crop * 80 + iy) * 80 + u * 16);
                 }
@@ -161,7 +158,6 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         f32x4 c = {0.f, 0.f, 0.f, 0.f};
-                        if (DBG & 2) { acc[s] = c; continue; }
                         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 1]), c, 0, 0, 0);   // low pieces first
                         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 3]), c, 0, 0, 0);
                         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 0]), c, 0, 0, 0);
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
     auto p2 = [&](const int c0, const int nr) {
         {
             // P2: (V2 row v, conv2 tile tx, channel quad): 8 pooled pixels x 4 channels -> B^T d -> pieces -> the planes
-            if (!(DBG & 4) && tid < nr * 40) {
+            if (tid < nr * 40) {
                 const int v = tid / 40, rem = tid - v * 40, tx = rem >> 2, quad = rem & 3;
                 const int q = c0 + v;
                 const int slot = q % G::NR + 1, rot = w2b_rot(slot);
@@ -229,21 +225,15 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
     };
     // rows [lo, hi) chunk by chunk; the first chunk's p0 has already run when first_done.  Ends with a barrier: the rows are complete
     auto produce = [&](const int lo, const int hi, const bool first_done, uint4 (&bf0)[4]) {
-        for (int c0 = (DBG & 8) ? hi : lo; c0 < hi; c0 += F::CHUNK) {
+        for (int c0 = lo; c0 < hi; c0 += F::CHUNK) {
             const int nr = hi - c0 < F::CHUNK ? hi - c0 : F::CHUNK;
             if (!(first_done && c0 == lo)) p0(c0, nr, false, bf0);
-            F12_STAMP(5);
             __syncthreads();
-            F12_STAMP(6);
             p1(nr, bf0);
             flag_crops(c0 < total_rows ? c0 : total_rows - 1, c0 + nr - 1 < total_rows ? c0 + nr - 1 : total_rows - 1, S);
-            F12_STAMP(7);
             __syncthreads();
-            F12_STAMP(8);
             p2(c0, nr);
-            F12_STAMP(9);
             __syncthreads();
-            F12_STAMP(10);
         }
     };
 
@@ -264,15 +254,14 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
 #define W2_POS(tau_) (((tau_) / 20) == 0 ? ((tau_) % 4 == 3 ? 7 : (tau_) % 4) : 3 + (tau_) % 4)
 #define W2_BOFF(tau_) (((((tau_) % 20) / 4) * 8 + W2_POS(tau_)) * G::BV * 16)
     // the two workgroups of a CU start together and would keep step: the second half of the grid starts half a pass late
-    if (STAGGER > 0 && blockIdx.x >= gridDim.x / 2) {
+    if (blockIdx.x >= gridDim.x / 2) {
 #pragma unroll 1
         for (int i = 0; i < STAGGER; ++i) __builtin_amdgcn_s_sleep(16);
     }
-    if ((DBG & 128) && dbg_stamps && tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2)) { st_on = true; st_last = __builtin_readcyclecounter(); }
     for (;;) {
         uint4 bq[8][2];
 #pragma unroll
-        for (int t = 0; t < BD; ++t) { bq[t][0] = buf_load16(wrs, boff, W2_BOFF(t)); bq[t][1] = (DBG & 64) ? bq[t][0] : buf_load16(wrs, boff, W2_BOFF(t) + 2 * CO * 16); }
+        for (int t = 0; t < BD; ++t) { bq[t][0] = buf_load16(wrs, boff, W2_BOFF(t)); bq[t][1] = buf_load16(wrs, boff, W2_BOFF(t) + 2 * CO * 16); }
         int aoff[5][4];
         {
             int s = mg * 32 + j;
@@ -310,13 +299,13 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
 #pragma unroll
         for (int t = 0; t < AD; ++t) W2B_AREAD(af[t], t);
 #pragma clang loop unroll(full)
-        for (int tau = 0; tau < ((DBG & 32) ? 0 : 40); ++tau) {
+        for (int tau = 0; tau < 40; ++tau) {
             const int tl = tau % 20;
             if (tau + AD < 40) W2B_AREAD(af[(tau + AD) % (AD + 1)], tau + AD);
             if (tau + BD < 40) {
                 const int wt = W2_BOFF(tau + BD);
                 bq[(tau + BD) % 8][0] = buf_load16(wrs, boff, wt);
-                bq[(tau + BD) % 8][1] = (DBG & 64) ? bq[(tau + BD) % 8][0] : buf_load16(wrs, boff, wt + 2 * CO * 16);
+                bq[(tau + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
             }
             const int p = W2_POS(tau);
             const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tau % 8][0]), b2 = __builtin_bit_cast(f16x8, bq[tau % 8][1]);
@@ -335,9 +324,7 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
         }
 #undef W2B_AREAD
         __builtin_amdgcn_s_setprio((PRIO >> 4) & 0xf);
-        F12_STAMP(0);
         __syncthreads();                                                  // every wave is done with the operand planes
-        F12_STAMP(1);
         const bool draw = pass % PK == PK - 1;                            // the last pass of a ticket moves on to the next ticket
         const int next_pass = draw ? s_next_pass : pass + 1;
         const bool have_next = next_pass < n_pass;
@@ -351,46 +338,41 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
             lo_new = (next_pass == pass + 1 && res_hi > qmin_n) ? res_hi : qmin_n;
             prefetch(lo_new, qmin_n + nrows_n);
         }
-        if (DBG & 32) { _Pragma("unroll") for (int p = 0; p < 8; ++p) acc[p] = zero16; }
         // epilogue 1: Y = A^T M, pool, bias, ReLU -> the pass's 3 x 20 x 64 activations as fp32 in LDS
-        if (!(DBG & 16)) {
-            f32x16 y0, y1, y2, y3;
-            {
-                const f32x16 e1 = acc[1] + acc[2], o1 = acc[1] - acc[2];
-                y0 = acc[0] + e1; y1 = o1; y2 = e1; y3 = o1 + acc[7];
-            }
-            {
-                const f32x16 e2 = acc[3] + acc[4], o2 = acc[3] - acc[4];
-                y0 += e2; y1 += 2.f * o2; y2 += 4.f * e2; y3 += 8.f * o2;
-            }
-            {
-                const f32x16 e3 = acc[5] + acc[6], o3 = acc[5] - acc[6];
-                y0 += e3; y1 += 0.5f * o3; y2 += 0.25f * e3; y3 += 0.125f * o3;
-            }
+        f32x16 y0, y1, y2, y3;
+        {
+            const f32x16 e1 = acc[1] + acc[2], o1 = acc[1] - acc[2];
+            y0 = acc[0] + e1; y1 = o1; y2 = e1; y3 = o1 + acc[7];
+        }
+        {
+            const f32x16 e2 = acc[3] + acc[4], o2 = acc[3] - acc[4];
+            y0 += e2; y1 += 2.f * o2; y2 += 4.f * e2; y3 += 8.f * o2;
+        }
+        {
+            const f32x16 e3 = acc[5] + acc[6], o3 = acc[5] - acc[6];
+            y0 += e3; y1 += 0.5f * o3; y2 += 0.25f * e3; y3 += 0.125f * o3;
+        }
 #pragma unroll
-            for (int rr = 0; rr < 8; ++rr) {
-                const int r = 2 * rr;
-                const int s = mg * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // even: rows y, y+1 of one tile column
-                const float v0 = fmaxf(fmaxf(y0[r], y1[r]), fmaxf(y0[r + 1], y1[r + 1]));
-                const float v1 = fmaxf(fmaxf(y2[r], y3[r]), fmaxf(y2[r + 1], y3[r + 1]));
-                if (s < G::RPP * G::TPP) {
-                    const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
-                    const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
-                    ovf |= !(a0 < 4368.0f) | !(a1 < 4368.0f);
-                    float* o = pbuf + (rp * 20 + 2 * tx) * 64 + co;
-                    o[0] = a0;
-                    o[64] = a1;
-                }
+        for (int rr = 0; rr < 8; ++rr) {
+            const int r = 2 * rr;
+            const int s = mg * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // even: rows y, y+1 of one tile column
+            const float v0 = fmaxf(fmaxf(y0[r], y1[r]), fmaxf(y0[r + 1], y1[r + 1]));
+            const float v1 = fmaxf(fmaxf(y2[r], y3[r]), fmaxf(y2[r + 1], y3[r + 1]));
+            if (s < G::RPP * G::TPP) {
+                const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
+                const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
+                ovf |= !(a0 < 4368.0f) | !(a1 < 4368.0f);
+                float* o = pbuf + (rp * 20 + 2 * tx) * 64 + co;
+                o[0] = a0;
+                o[64] = a1;
             }
         }
         { const int g0 = pass * G::RPP, g1 = g0 + G::RPP - 1; flag_crops(g0, g1 < total_pairs ? g1 : total_pairs - 1, S / 2); }
-        F12_STAMP(2);
         __syncthreads();                                                  // the activations are in pbuf
-        F12_STAMP(3);
         uint4 bf0[4];
         const int hi_new = qmin_n + nrows_n;
         // epilogue 2: (pooled row, conv3 tile, channel quad) items -> V3
-        if (!(DBG & 16) && tid < 240) {
+        if (tid < 240) {
             const int rp = tid / 80, rem = tid - rp * 80, tx = rem >> 4, quad = rem & 15;
             const int gp = pass * G::RPP + rp;                            // = q3: pooled row of the batch
             if (gp < total_pairs) {
@@ -417,13 +399,12 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
                 }
             }
         }
-        F12_STAMP(4);
         if (!have_next) break;
         // the first chunk of the next pass's rows starts here: every lane converts the crop-row unit its OWN LDS-DMA fetched (item = thread
         // index in prefetch and in p0 alike), so no barrier stands between the fetch and the conversion -- only the wave's own counter: the 16
         // V3 stores of epilogue 2 were issued behind the DMA and may stay in flight
         asm volatile("s_waitcnt vmcnt(16)" : "+v"(ticket) :: "memory");
-        if (!(DBG & 8)) p0(lo_new, hi_new - lo_new < F::CHUNK ? hi_new - lo_new : F::CHUNK, true, bf0);
+        p0(lo_new, hi_new - lo_new < F::CHUNK ? hi_new - lo_new : F::CHUNK, true, bf0);
         produce(lo_new, hi_new, true, bf0);                               // (starts with the barrier behind epilogue 2 / p0, ends with one: the planes are complete)
         res_hi = qmin_n + nrows_n;
         if (draw) {
@@ -431,10 +412,7 @@ __global__ __launch_bounds__(256, 2) void k_conv12_wpre(const uint8_t* __restric
             if (tid == 0) s_next_pass = ((int)ticket + (int)gridDim.x) * PK;       // read behind a later pass's first barrier
         }
         pass = next_pass; qmin = qmin_n; nrows = nrows_n;
-        if ((DBG & 128) && st_on) st_sum[11] += 1;
     }
-    if ((DBG & 128) && st_on) { _Pragma("unroll") for (int i = 0; i < 12; ++i) dbg_stamps[(blockIdx.x ? 12 : 0) + i] = st_sum[i]; }
-#undef F12_STAMP
 #undef W2B_ROWS
 #undef W12_ITEM
 #undef W2_POS

@@ -31,19 +31,18 @@ __device__ __forceinline__ float rs_max3(const float a, const float b, const flo
 __device__ __forceinline__ float rs_max3z(const float a, const float b) { float r; asm("v_max3_f32 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b)); return r; }      // max(a, b, 0)
 __device__ __forceinline__ float rs_max(const float a, const float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
-// Order of the 20 taps of a stage (ORD 1, round 5): position PAIR major -- i = tap % 20: pair i / 10, kernel row (i % 10) / 2, position of the pair
+// Order of the 20 taps of a stage (round 5): position PAIR major -- i = tap % 20: pair i / 10, kernel row (i % 10) / 2, position of the pair
 // i % 2 -- with stage 1 = positions (1,2) then (0,7), stage 2 = (3,4) then (5,6): the pairs the output transform A^T combines are final 10 taps
 // before their stage ends, and their part of A^T runs under the taps that follow (the tap loop of stage 2 is bound by the matrix pipe, the
 // output transform behind it by the vector issue of two waves).  Per accumulator the order of the sums is unchanged (kernel row 0..4).
-// ORD 0: kernel row major (i / 4, i % 4), the order of k_conv12_wpre and k_conv2_wpre2.  pg = the position's place in its stored group
-// (group 0 holds positions 0,1,2,7; group 1 holds 3,4,5,6).
-__host__ __device__ constexpr int rs_ky(const int ord, const int tau) { return ord ? ((tau % 20) % 10) / 2 : (tau % 20) / 4; }
-__host__ __device__ constexpr int rs_pg(const int ord, const int tau) {
+// Measured against the kernel-row-major order of k_conv12_wpre and k_conv2_wpre2: 3.63 against 3.69 ms (profiles/r05_f12_pair_order.txt).
+// pg = the position's place in its stored group (group 0 holds positions 0,1,2,7; group 1 holds 3,4,5,6).
+__host__ __device__ constexpr int rs_ky(const int tau) { return ((tau % 20) % 10) / 2; }
+__host__ __device__ constexpr int rs_pg(const int tau) {
     const int i = tau % 20;
-    if (!ord) return i % 4;
     return tau / 20 == 0 ? (i / 10 == 0 ? 1 + i % 2 : (i % 2 ? 3 : 0)) : 2 * (i / 10) + i % 2;
 }
-__host__ __device__ constexpr int rs_pos(const int ord, const int tau) { return tau / 20 == 0 ? (rs_pg(ord, tau) == 3 ? 7 : rs_pg(ord, tau)) : 3 + rs_pg(ord, tau); }
+__host__ __device__ constexpr int rs_pos(const int tau) { return tau / 20 == 0 ? (rs_pg(tau) == 3 ? 7 : rs_pg(tau)) : 3 + rs_pg(tau); }
 
 struct W12RGeom {
     using G = W2bGeom;
@@ -64,19 +63,25 @@ struct W12RGeom {
     static constexpr int LDS_BYTES = WRES_OFF + NRES * WTAP;
     static_assert(LDS_BYTES <= 160 * 1024 && CTL_OFF % 16 == 0 && NRES >= 8 && NRES <= 40, "one workgroup per CU");
     // the FIRST taps of a pass are the resident ones: they run beside the producers' V3 stores and crop loads (stage 1), the later taps beside
-    // conv1, which touches no vector memory (stage 2) -- spread evenly over the loop the same 15 taps bought 10 % of stage 1, not 40
-    static constexpr bool resident(const int tau, const int pat = 0) { return pat == 0 ? tau < NRES : (pat == 1 ? (tau < 10 || (tau >= 20 && tau < 25)) : (tau < 7 || (tau >= 20 && tau < 28))); }
-    static constexpr int res_slot(const int tau, const int pat = 0) { return pat == 0 ? tau : (pat == 1 ? (tau < 10 ? tau : tau - 10) : (tau < 7 ? tau : tau - 13)); }
+    // conv1, which touches no vector memory (stage 2) -- spread evenly over the loop the same 15 taps bought 10 % of stage 1, not 40.  Tap tau < NRES
+    // lives in slot tau
+    static constexpr bool resident(const int tau) { return tau < NRES; }
 };
 
-template <int DBG = 0, int BD = 3, int TSPLIT = 20, int PRIO = 0x201, int PAIR = 0, int RESPAT = 0, int ORD = 1>      // PRIO 0x201: since the taps run in pair order the producers' V2 transform is the longer half of stage 3 and outranks the output transform (0x202, equal priorities: 3.65 ms, 0x201 / 0x200 / 0x301 / 0x311: 3.58-3.60); PAIR: two taps at a time, consecutive MFMAs on different accumulators; TSPLIT: taps in front of the first barrier of a round; PRIO: s_setprio of (producer, tap loop, output transform) as hex digits
+// Tuning (round 5, profiles/r05_rs_ablation.txt):
+//   RS_BD 3       weight fragments 3 taps ahead (2 / 5 taps: 3.99 / 4.01 against 3.90-3.98 ms)
+//   RS_TSPLIT 20  taps in front of the first barrier of a round (16 / 24: 3.94 / 4.03)
+//   RS_PRIO 0x201 s_setprio of (producer, tap loop, output transform) as hex digits: since the taps run in pair order the producers' V2 transform
+//                 is the longer half of stage 3 and outranks the output transform (0x202, equal priorities: 3.65 ms, 0x201 / 0x200 / 0x301 / 0x311:
+//                 3.58-3.60)
+// Measured and not kept: two taps at a time with their products interleaved, consecutive MFMAs on different accumulators (4.09 / 3.81-3.83 against 3.69)
+static constexpr int RS_BD = 3, RS_TSPLIT = 20, RS_PRIO = 0x201;
 __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ crops /*[N][80][80]*/, const uint4* __restrict__ w1tab /*[16][64]*/,
                                                    const float* __restrict__ bias1, const float inv_scale1,
                                                    const uint4* __restrict__ wp /*[5][8][2][2][64] x 16 B*/, const float* __restrict__ bias,
                                                    uint8_t* __restrict__ v3, const float out_scale, uint32_t* __restrict__ overflow,
                                                    const int n_crops, uint32_t* __restrict__ pass_ctr, const int PK /* consecutive passes per ticket */,
-                                                   uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */,
-                                                   unsigned long long* __restrict__ dbg_stamps = nullptr /* DBG & 128 (dev): cycles per stage of waves 0 and 4 of workgroup 0 */) {
+                                                   uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */) {
     using G = W2bGeom;
     using F = W12RGeom;
     constexpr int CO = 64, S = 40;
@@ -102,11 +107,10 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
     float* pbp = reinterpret_cast<float*>(ldsb + F::PBP_OFF);
     for (int i = tid; i < F::IMG_BYTES / 16; i += 512) reinterpret_cast<uint4*>(img)[i] = make_uint4(0, 0, 0, 0);   // the x padding stays zero
     for (int i = tid; i < (F::PBE_BYTES + F::PBP_BYTES) / 16; i += 512) reinterpret_cast<uint4*>(ldsb + F::PBE_OFF)[i] = make_uint4(0, 0, 0, 0);      // the halo pixels stay zero
-    // resident weight fragments: tap tau -> slot res_slot(tau); a slot holds the tap's [piece][k-octet h][co] x 16 B exactly as the weight image does
+    // resident weight fragments: tap tau -> slot tau; a slot holds the tap's [piece][k-octet h][co] x 16 B exactly as the weight image does
     for (int i = tid; i < 40 * (F::WTAP / 16); i += 512) {
         const int tau = i / (F::WTAP / 16), u = i - tau * (F::WTAP / 16);
-        const int slot = F::res_slot(tau, RESPAT);
-        if (F::resident(tau, RESPAT)) reinterpret_cast<uint4*>(ldsb + F::WRES_OFF + slot * F::WTAP)[u] = wp[(size_t)(rs_ky(ORD, tau) * 8 + rs_pos(ORD, tau)) * G::BV + u];
+        if (F::resident(tau)) reinterpret_cast<uint4*>(ldsb + F::WRES_OFF + tau * F::WTAP)[u] = wp[(size_t)(rs_ky(tau) * 8 + rs_pos(tau)) * G::BV + u];
     }
     if (tid == 0) *s_next = ((int)atomicAdd(pass_ctr, 1u) + (int)gridDim.x) * PK;
     float ovfm = 0.f;                                                    // the largest activation seen (all are >= 0 behind their ReLU): the fp16 range guard
@@ -117,10 +121,6 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             ovfm = 0.f;
         }
     };
-    // DBG & 128 (dev builds): lane 0 of waves 0 (consumer) and 4 (producer) of workgroup 0 sum the cycles between the stage boundaries
-    unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
-    const bool st_on = (DBG & 128) && dbg_stamps && blockIdx.x == 0 && (tid == 0 || tid == 256);
-#define RS_STAMP(i_) do { if ((DBG & 128) && st_on) { const unsigned long long t_ = __builtin_readcyclecounter(); st_sum[i_] += t_ - st_last; st_last = t_; } } while (0)
     // every wave: LDS writes done, then the workgroup barrier.  Both roles execute the SAME number of these per round.
 #define RS_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define RS_ROWS(pass_, qmin_, nrows_)                                                                                            \
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         // ------------------------------------------------------------------------------------------------------------------------
         // PRODUCER: V3 transform of the previous pass, V2 rows of the next one
         // ------------------------------------------------------------------------------------------------------------------------
-        __builtin_amdgcn_s_setprio((PRIO >> 8) & 3);
+        __builtin_amdgcn_s_setprio((RS_PRIO >> 8) & 3);
         // the crop-row unit (16 pixels) item `it` of a chunk that starts at V2 row c0 stands for: item = (V2 row v, crop row k of its six, unit u)
 #define RS_ITEM(it_, c0_)                                                                                                        \
                 const int vk = (it_) / 5, u = (it_) - vk * 5;                                                                    \
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             px = make_uint4(0, 0, 0, 0);
             if (rt < nr * 30) {
                 RS_ITEM(rt, c0)
-                if (!(DBG & 1) && iy >= 0 && iy < 80) px = *reinterpret_cast<const uint4*>(crops + ((size_t)crop * 80 + iy) * 80 + u * 16);
+                if (iy >= 0 && iy < 80) px = *reinterpret_cast<const uint4*>(crops + ((size_t)crop * 80 + iy) * 80 + u * 16);
             }
         };
         auto p0_store = [&](const int nr, const uint4 px) {
@@ -225,16 +225,14 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                 for (int u = 0; u < NT1; ++u)
 #pragma unroll
                     for (int s = 0; s < 4; ++s) acc[u][s] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (!(DBG & 2)) {
-                    // per chain the order of k_conv1_wpre: low pieces first (fragments 1, 3), then the high ones (0, 2)
+                // per chain the order of k_conv1_wpre: low pieces first (fragments 1, 3), then the high ones (0, 2)
 #pragma unroll
-                    for (int m = 0; m < 4; ++m)
+                for (int m = 0; m < 4; ++m)
 #pragma unroll
-                        for (int u = 0; u < NT1; ++u)
+                    for (int u = 0; u < NT1; ++u)
 #pragma unroll
-                            for (int s = 0; s < 4; ++s)
-                                acc[u][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16((m & 1) ? a2[u] : a1[u], __builtin_bit_cast(f16x8_c1, bf[s * 4 + (m == 0 ? 1 : m == 1 ? 3 : m == 2 ? 0 : 2)]), acc[u][s], 0, 0, 0);
-                }
+                        for (int s = 0; s < 4; ++s)
+                            acc[u][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16((m & 1) ? a2[u] : a1[u], __builtin_bit_cast(f16x8_c1, bf[s * 4 + (m == 0 ? 1 : m == 1 ? 3 : m == 2 ? 0 : 2)]), acc[u][s], 0, 0, 0);
                 // lane (co = r, q4): accumulator rows 4 q4 .. 4 q4 + 3 = windows 2 q4, 2 q4 + 1 x the two image rows: pooled pixels 2 (window) and
                 // 2 (window) + 1 of the V2 row, channel co.  pbufP [slot of the pooled pixel][16 channels]; slot = the pixel index with its two low
                 // bit pairs swapped (the four q4 groups of a store fill 256 contiguous bytes, P2's lanes read contiguously as well)
@@ -265,7 +263,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         };
         // P2: (V2 row v, conv2 tile tx, channel quad): 8 pooled pixels x 4 channels -> B^T d -> pieces -> the ring slots (q % NR + 1) of the planes
         auto p2 = [&](const int c0, const int nr) {
-            if (!(DBG & 4) && rt < nr * 40) {
+            if (rt < nr * 40) {
                 const int v = rt / 40, rem = rt - v * 40, tx = rem >> 2, quad = rem & 3;
                 const int q = c0 + v;
                 const int slot = q % G::NR + 1, rot = w2b_rot(slot);
@@ -296,7 +294,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         };
         // E2: the V3 transform of pass `ep`: (pooled row, conv3 tile, channel quad) items of pbufE -> B^T d -> pieces -> V3
         auto e2 = [&](const int ep) {
-            if (!(DBG & 16) && rt < 240) {
+            if (rt < 240) {
                 const int rp = rt / 80, rem = rt - rp * 80, tx = rem >> 4, quad = rem & 15;
                 const int gp = ep * G::RPP + rp;                            // = q3: pooled row of the batch
                 if (gp < total_pairs) {
@@ -336,7 +334,6 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         }
         int res_hi = qmin + nrows;
         int prev = -1;
-        if ((DBG & 128) && st_on) st_last = __builtin_readcyclecounter();
         for (;;) {
             int next_pass, lo, hi;
             bool have_next;
@@ -344,34 +341,29 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             // S1 (beside taps 0-19): the crop rows of the first chunk are requested, the V3 transform of the previous pass runs under their flight
             const int nr0 = hi - lo < F::CHUNK ? hi - lo : F::CHUNK;
             uint4 px;
-            if (!(DBG & 8)) p0_load(lo, nr0, px);
+            p0_load(lo, nr0, px);
             if (prev >= 0) e2(prev);
-            if (!(DBG & 8)) p0_store(nr0, px);
-            RS_STAMP(0);
+            p0_store(nr0, px);
             RS_BAR();
-            RS_STAMP(1);
             // S2 (beside taps 20-39): conv1
-            if (!(DBG & 8)) { p1(nr0); if (nr0 > 0) flag_crops(lo, lo + nr0 - 1 < total_rows ? lo + nr0 - 1 : total_rows - 1, S); }
-            RS_STAMP(2);
+            p1(nr0);
+            if (nr0 > 0) flag_crops(lo, lo + nr0 - 1 < total_rows ? lo + nr0 - 1 : total_rows - 1, S);
             RS_BAR();
-            RS_STAMP(3);
             // S3 (beside the output transform; nobody reads the ring): the rows go to their slots
-            if (!(DBG & 8)) p2(lo, nr0);
-            RS_STAMP(4);
+            p2(lo, nr0);
             RS_BAR();
-            RS_STAMP(5);
             // a ticket's first pass needs 10 rows: the second chunk in three more stages (the consumers wait)
             for (int c0 = lo + F::CHUNK; c0 < hi; c0 += F::CHUNK) {
                 const int nr = hi - c0 < F::CHUNK ? hi - c0 : F::CHUNK;
-                if (!(DBG & 8)) { p0_load(c0, nr, px); p0_store(nr, px); }
+                p0_load(c0, nr, px);
+                p0_store(nr, px);
                 RS_BAR();
-                if (!(DBG & 8)) { p1(nr); flag_crops(c0, c0 + nr - 1 < total_rows ? c0 + nr - 1 : total_rows - 1, S); }
+                p1(nr);
+                flag_crops(c0, c0 + nr - 1 < total_rows ? c0 + nr - 1 : total_rows - 1, S);
                 RS_BAR();
-                if (!(DBG & 8)) p2(c0, nr);
+                p2(c0, nr);
                 RS_BAR();
             }
-            RS_STAMP(6);
-            if ((DBG & 128) && st_on) st_sum[7] += 1;
             prev = pass;
             if (!have_next) break;
             res_hi = hi;
@@ -392,23 +384,23 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         const float bz = bias[co];
         for (int c0 = qmin; c0 < qmin + nrows; c0 += F::CHUNK) { RS_BAR(); RS_BAR(); RS_BAR(); }      // the producers' prologue
         int res_hi = qmin + nrows;
-#define W2_POS(tau_) rs_pos(ORD, tau_)
-#define W2_BOFF(tau_) ((rs_ky(ORD, tau_) * 8 + W2_POS(tau_)) * G::BV * 16)
-        // the weight fragments of taps 0 .. BD - 1 are the same for every pass: the last taps of a pass fetch them for the next one
+#define W2_POS(tau_) rs_pos(tau_)
+#define W2_BOFF(tau_) ((rs_ky(tau_) * 8 + W2_POS(tau_)) * G::BV * 16)
+        // the weight fragments of taps 0 .. RS_BD - 1 are the same for every pass: the last taps of a pass fetch them for the next one
         uint4 bq[8][2];
         const uint8_t* wres = ldsb + F::WRES_OFF + boff;
 #define RS_WFETCH(dst_, tau_)                                                                                                    \
         do {                                                                                                                     \
-            if (F::resident(tau_, RESPAT)) {                                                                                     \
-                dst_[0] = *reinterpret_cast<const uint4*>(wres + F::res_slot(tau_, RESPAT) * F::WTAP);                           \
-                dst_[1] = *reinterpret_cast<const uint4*>(wres + F::res_slot(tau_, RESPAT) * F::WTAP + 2 * CO * 16);             \
+            if (F::resident(tau_)) {                                                                                             \
+                dst_[0] = *reinterpret_cast<const uint4*>(wres + (tau_) * F::WTAP);                                              \
+                dst_[1] = *reinterpret_cast<const uint4*>(wres + (tau_) * F::WTAP + 2 * CO * 16);                                \
             } else {                                                                                                             \
                 dst_[0] = buf_load16(wrs, boff, W2_BOFF(tau_));                                                                  \
-                dst_[1] = (DBG & 64) ? dst_[0] : buf_load16(wrs, boff, W2_BOFF(tau_) + 2 * CO * 16);                             \
+                dst_[1] = buf_load16(wrs, boff, W2_BOFF(tau_) + 2 * CO * 16);                                                    \
             }                                                                                                                    \
         } while (0)
 #pragma unroll
-        for (int t = 0; t < BD; ++t) RS_WFETCH(bq[t], t);
+        for (int t = 0; t < RS_BD; ++t) RS_WFETCH(bq[t], t);
         // A-operand byte offsets of this lane's tile for pass `ps_`: per kernel row the row slot (out-of-crop rows -> the zero row), per position of a
         // group the rotated unit.  Computed for the NEXT pass behind the output transform, off the path to the first tap
         // A-operand byte offsets of this lane's tile: per kernel row the row slot of the pass (out-of-crop rows -> the zero row) and its rotation --
@@ -437,9 +429,8 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                 srow[ky] = slot_ * G::ROWL; srot[ky] = w2b_rot(slot_);                                                           \
             }                                                                                                                    \
         } while (0)
-#define RS_AUNIT(tau_) do { if ((tau_) < 20) aoff[rs_ky(ORD, tau_)][rs_pg(ORD, tau_)] = srow[rs_ky(ORD, tau_)] + (wh[rs_pg(ORD, tau_)] | (((wl[rs_pg(ORD, tau_)] + srot[rs_ky(ORD, tau_)]) & 15) << 4)); } while (0)
+#define RS_AUNIT(tau_) do { if ((tau_) < 20) aoff[rs_ky(tau_)][rs_pg(tau_)] = srow[rs_ky(tau_)] + (wh[rs_pg(tau_)] | (((wl[rs_pg(tau_)] + srot[rs_ky(tau_)]) & 15) << 4)); } while (0)
         RS_AOFF(pass);
-        if ((DBG & 128) && st_on) st_last = __builtin_readcyclecounter();
         for (;;) {
             int next_pass, lo, hi;
             bool have_next;
@@ -450,9 +441,9 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             if (draw && tid == 0) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(ticket) : "v"(pass_ctr), "v"(1u) : "memory");
             f32x16 acc[8];
             const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            __builtin_amdgcn_s_setprio((PRIO >> 4) & 3);
-            uint4 af[PAIR ? 4 : 2][2];
-            // ORD 1: the part of A^T whose positions are final, two accumulator rows per tap, in place (an empty volatile asm keeps each result at
+            __builtin_amdgcn_s_setprio((RS_PRIO >> 4) & 3);
+            uint4 af[2][2];
+            // the part of A^T whose positions are final, two accumulator rows per tap, in place (an empty volatile asm keeps each result at
             // its tap; the operations and their order are the output transform's: results stay bit-identical).  After it acc[0] = y0, acc[2] = y1,
             // acc[1] = y2, acc[7] = y3 up to the pair (5,6), which stage 3 adds.
             auto rs_fold = [&](const int tau) {
@@ -483,7 +474,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             };
 #define RS_AREAD(dst_, tau_)                                                                                                     \
             do {                                                                                                                 \
-                const uint8_t* an_ = ldsb + ((tau_) / 20) * G::BUF + aoff[rs_ky(ORD, tau_)][rs_pg(ORD, tau_)];                   \
+                const uint8_t* an_ = ldsb + ((tau_) / 20) * G::BUF + aoff[rs_ky(tau_)][rs_pg(tau_)];                             \
                 dst_[0] = *reinterpret_cast<const uint4*>(an_);                                                                  \
                 dst_[1] = *reinterpret_cast<const uint4*>(an_ + G::PLANE);                                                       \
             } while (0)
@@ -491,133 +482,66 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             do {                                                                                                                 \
                 const int tl = (tau) % 20;                                                                                       \
                 if ((tau) + 1 < 40) { RS_AUNIT((tau) + 1); RS_AREAD(af[((tau) + 1) % 2], (tau) + 1); }                           \
-                RS_WFETCH(bq[((tau) + BD) % 8], ((tau) + BD) % 40);                                                              \
+                RS_WFETCH(bq[((tau) + RS_BD) % 8], ((tau) + RS_BD) % 40);                                                        \
                 const int p = W2_POS(tau);                                                                                       \
                 const f16x8 b1 = __builtin_bit_cast(f16x8, bq[(tau) % 8][0]), b2 = __builtin_bit_cast(f16x8, bq[(tau) % 8][1]); \
                 const f16x8 a1 = __builtin_bit_cast(f16x8, af[(tau) % 2][0]), a2 = __builtin_bit_cast(f16x8, af[(tau) % 2][1]); \
-                acc[p] = mfma16(a2, b1, rs_ky(ORD, tau) == 0 ? zero16 : acc[p]);      /* kernel row 0 starts the accumulator */   \
+                acc[p] = mfma16(a2, b1, rs_ky(tau) == 0 ? zero16 : acc[p]);      /* kernel row 0 starts the accumulator */        \
                 acc[p] = mfma16(a1, b2, acc[p]);                                                                                 \
                 acc[p] = mfma16(a1, b1, acc[p]);                                                                                 \
-                if constexpr (ORD == 1) { if (!(DBG & 16)) rs_fold(tau); }                                                        \
+                rs_fold(tau);                                                                                                    \
                 __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                               \
                 __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                                                               \
                 _Pragma("unroll") for (int g = 0; g < 3; ++g) {                                                                  \
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                           \
-                    __builtin_amdgcn_sched_group_barrier(0x006, ORD ? 6 : 4, 0);                                                 \
-                }                                                                                                                \
-                __builtin_amdgcn_sched_barrier(0);                                                                               \
-            } while (0)
-            // two taps (tau, tau + 1: two positions of one kernel row) at a time, their three products interleaved: consecutive MFMAs go to different
-            // accumulators.  A wave whose next MFMA waits for its own accumulator holds the SIMD's issue port (profiles/r05_ubench_simd.txt: beside
-            // dependent MFMAs a vector wave of equal priority got 1 % of the port, beside independent ones 84 %) -- and here the producer wave outranks
-            // the tap loop, so every port conflict lands on a dependent chain of the consumer
-#define RS_TAP2(tau)                                                                                                             \
-            do {                                                                                                                 \
-                const int tl = (tau) % 20;                                                                                       \
-                if ((tau) + 2 < 40) {                                                                                            \
-                    RS_AUNIT((tau) + 2); RS_AREAD(af[((tau) + 2) % 4], (tau) + 2);                                               \
-                    RS_AUNIT((tau) + 3); RS_AREAD(af[((tau) + 3) % 4], (tau) + 3);                                               \
-                }                                                                                                                \
-                RS_WFETCH(bq[((tau) + BD) % 8], ((tau) + BD) % 40);                                                              \
-                RS_WFETCH(bq[((tau) + BD + 1) % 8], ((tau) + BD + 1) % 40);                                                      \
-                const int p = W2_POS(tau), q = W2_POS((tau) + 1);                                                                \
-                const f16x8 b1 = __builtin_bit_cast(f16x8, bq[(tau) % 8][0]), b2 = __builtin_bit_cast(f16x8, bq[(tau) % 8][1]); \
-                const f16x8 c1 = __builtin_bit_cast(f16x8, bq[((tau) + 1) % 8][0]), c2 = __builtin_bit_cast(f16x8, bq[((tau) + 1) % 8][1]); \
-                const f16x8 a1 = __builtin_bit_cast(f16x8, af[(tau) % 4][0]), a2 = __builtin_bit_cast(f16x8, af[(tau) % 4][1]); \
-                const f16x8 d1 = __builtin_bit_cast(f16x8, af[((tau) + 1) % 4][0]), d2 = __builtin_bit_cast(f16x8, af[((tau) + 1) % 4][1]); \
-                acc[p] = mfma16(a2, b1, rs_ky(ORD, tau) == 0 ? zero16 : acc[p]);                                                 \
-                acc[q] = mfma16(d2, c1, rs_ky(ORD, (tau) + 1) == 0 ? zero16 : acc[q]);                                           \
-                acc[p] = mfma16(a1, b2, acc[p]);                                                                                 \
-                acc[q] = mfma16(d1, c2, acc[q]);                                                                                 \
-                acc[p] = mfma16(a1, b1, acc[p]);                                                                                 \
-                acc[q] = mfma16(d1, c1, acc[q]);                                                                                 \
-                __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);        /* the A fragments of the next pair (+ resident weight fragments) */ \
-                __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);        /* weight fragments from L2 */                          \
-                _Pragma("unroll") for (int g = 0; g < 6; ++g) {                                                                  \
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                           \
-                    __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);                                                           \
+                    __builtin_amdgcn_sched_group_barrier(0x006, 6, 0);                                                           \
                 }                                                                                                                \
                 __builtin_amdgcn_sched_barrier(0);                                                                               \
             } while (0)
             RS_AUNIT(0);
             RS_AREAD(af[0], 0);
-            if constexpr (PAIR) { RS_AUNIT(1); RS_AREAD(af[1], 1); }
-            if constexpr (PAIR) {
-                static_assert(!PAIR || (TSPLIT % 2 == 0 && BD % 2 == 0 && BD <= 4), "pairs of taps");
 #pragma clang loop unroll(full)
-                for (int tau = 0; tau < ((DBG & 32) ? 0 : TSPLIT); tau += 2) RS_TAP2(tau);
-            } else {
-#pragma clang loop unroll(full)
-            for (int tau = 0; tau < ((DBG & 32) ? 0 : TSPLIT); ++tau) RS_TAP(tau);
-            }
-            RS_STAMP(0);
+            for (int tau = 0; tau < RS_TSPLIT; ++tau) RS_TAP(tau);
             RS_BAR();                                                     // S1 | S2
-            RS_STAMP(1);
-            if constexpr (PAIR) {
 #pragma clang loop unroll(full)
-                for (int tau = TSPLIT; tau < ((DBG & 32) ? 0 : 40); tau += 2) RS_TAP2(tau);
-            } else {
-#pragma clang loop unroll(full)
-            for (int tau = TSPLIT; tau < ((DBG & 32) ? 0 : 40); ++tau) RS_TAP(tau);
-            }
-            if (DBG & 32) { _Pragma("unroll") for (int p = 0; p < 8; ++p) acc[p] = zero16; }
+            for (int tau = RS_TSPLIT; tau < 40; ++tau) RS_TAP(tau);
             if (draw) {
                 asm volatile("s_waitcnt vmcnt(0)" : "+v"(ticket) :: "memory");
                 if (tid == 0) *s_next = ((int)ticket + (int)gridDim.x) * PK;       // read at the start of a later round
             }
-            RS_STAMP(2);
             RS_BAR();                                                     // S2 | S3: the producers have read pbufE (in S1), it may be written
-            RS_STAMP(3);
-            __builtin_amdgcn_s_setprio(PRIO & 3);
+            __builtin_amdgcn_s_setprio(RS_PRIO & 3);
             // output transform: Y = A^T M, pool, bias, ReLU -> the pass's 3 x 20 x 64 activations as fp32 in pbufE
-            if (!(DBG & 16)) {
-                f32x16 y0, y1, y2, y3;
-                if constexpr (ORD == 1) { y0 = acc[0]; y1 = acc[2]; y2 = acc[1]; y3 = acc[7]; }
-                else {
-                    {
-                        const f32x16 e1 = acc[1] + acc[2], o1 = acc[1] - acc[2];
-                        y0 = acc[0] + e1; y1 = o1; y2 = e1; y3 = o1 + acc[7];
-                    }
-                    {
-                        const f32x16 e2 = acc[3] + acc[4], o2 = acc[3] - acc[4];
-                        y0 += e2; y1 += 2.f * o2; y2 += 4.f * e2; y3 += 8.f * o2;
-                    }
-                }
-                {
-                    const f32x16 e3 = acc[5] + acc[6], o3 = acc[5] - acc[6];
-                    y0 += e3; y1 += 0.5f * o3; y2 += 0.25f * e3; y3 += 0.125f * o3;
-                }
+            f32x16 y0 = acc[0], y1 = acc[2], y2 = acc[1], y3 = acc[7];      // positions 0-4 were folded in by rs_fold under the taps
+            {
+                const f32x16 e3 = acc[5] + acc[6], o3 = acc[5] - acc[6];
+                y0 += e3; y1 += 0.5f * o3; y2 += 0.25f * e3; y3 += 0.125f * o3;
+            }
 #pragma unroll
-                for (int rr = 0; rr < 8; ++rr) {
-                    const int r = 2 * rr;
-                    const int s = mg * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // even: rows y, y+1 of one tile column
-                    const float v0 = rs_max(rs_max3(y0[r], y1[r], y0[r + 1]), y1[r + 1]);
-                    const float v1 = rs_max(rs_max3(y2[r], y3[r], y2[r + 1]), y3[r + 1]);
-                    if (s < G::RPP * G::TPP) {
-                        const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
-                        const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
-                        ovfm = rs_max3(ovfm, a0, a1);
-                        float* o = pbe + (rp * F::PEP + 2 + 2 * tx) * 64 + co;
-                        o[0] = a0;
-                        o[64] = a1;
-                    }
+            for (int rr = 0; rr < 8; ++rr) {
+                const int r = 2 * rr;
+                const int s = mg * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // even: rows y, y+1 of one tile column
+                const float v0 = rs_max(rs_max3(y0[r], y1[r], y0[r + 1]), y1[r + 1]);
+                const float v1 = rs_max(rs_max3(y2[r], y3[r], y2[r + 1]), y3[r + 1]);
+                if (s < G::RPP * G::TPP) {
+                    const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
+                    const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
+                    ovfm = rs_max3(ovfm, a0, a1);
+                    float* o = pbe + (rp * F::PEP + 2 + 2 * tx) * 64 + co;
+                    o[0] = a0;
+                    o[64] = a1;
                 }
             }
             { const int g0 = pass * G::RPP, g1 = g0 + G::RPP - 1; flag_crops(g0, g1 < total_pairs ? g1 : total_pairs - 1, S / 2); }
             if (have_next) RS_AOFF(next_pass);
-            RS_STAMP(4);
             RS_BAR();                                                     // S3 | the next round
-            RS_STAMP(5);
             for (int c0 = lo + F::CHUNK; c0 < hi; c0 += F::CHUNK) { RS_BAR(); RS_BAR(); RS_BAR(); }    // the second chunk of a ticket's first pass
-            RS_STAMP(6);
-            if ((DBG & 128) && st_on) st_sum[7] += 1;
             if (!have_next) break;
             res_hi = hi;
             tleft = tleft == 1 ? PK : tleft - 1;
             pass = next_pass;
         }
 #undef RS_TAP
-#undef RS_TAP2
 #undef RS_WFETCH
 #undef RS_AOFF
 #undef RS_AUNIT
@@ -625,8 +549,6 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
 #undef W2_POS
 #undef W2_BOFF
     }
-    if ((DBG & 128) && st_on) { _Pragma("unroll") for (int i = 0; i < 8; ++i) dbg_stamps[(tid ? 8 : 0) + i] = st_sum[i]; }
-#undef RS_STAMP
 #undef RS_NEXT
 #undef RS_ROWS
 #undef RS_BAR

@@ -5,7 +5,7 @@
 // (F(4,5) Winograd along x, direct along y, fp16 two-piece split of both operands, three piece products, fp32 accumulate):
 //   k_conv1_wpre  u8 crop -> conv1 (matrix cores) -> bias, ReLU, pool -> B^T d along x -> fp16 pieces -> V2
 //   k_conv2_wpre2 V2 -> conv2 (40 position GEMMs) -> A^T, bias, ReLU, pool -> B^T d -> fp16 pieces -> V3
-//   k_conv5_wpre  V3 -> conv3 -> A^T, bias, ReLU, pool -> act3 (fp32, NHWC) -> fc1 -> head
+//   k_conv5_wpair V3 -> conv3 -> A^T, bias, ReLU, pool -> act3 (fp32, NHWC) -> fc1 -> head   (cnn_conv3p.h)
 // (since round 4 the first two run as ONE kernel for 1-channel crops -- cnn_fused12.h: k_conv12_wpre produces V2's rows straight into conv2's LDS row
 // ring; k_conv1_wpre + k_conv2_wpre2 below serve 3-channel crops and TREXHIP_CONV_GEOM bit 28)
 // so the consumers' staging is a plain 16-byte copy HBM -> VGPR -> LDS (no transform, no split, no 4-byte LDS scatter inside the
@@ -18,19 +18,12 @@
 static constexpr int V2_ROWB = 5120, V3_ROWB = 10240;
 // V3 since round 5 (k_conv5_wpair, cnn_conv3p.h): a row's 10240 bytes are [position pair 4][piece 2][chunk 4][position of the pair 2][tx 5][16 ci],
 // pairs in the order (1,2) (3,4) (5,6) (0,7) -- conv3 walks a pass pair by pair (all 64 input channels of two positions = one 1280-byte plane
-// per row and piece), so that the pairs the output transform combines are final one after the other.  -DTREXHIP_V3_OLD: [chunk][piece][position 8]
-// [tx][16 ci] for k_conv5_wpre.  The producers' stores of position p, chunk c, piece pc, tile tx: v3_off(p, pc) + c * V3_CHUNKB + tx * 32.
-#ifdef TREXHIP_V3_OLD
-static constexpr bool V3_PAIR = false;
-static constexpr int V3_CHUNKB = 2560;
-__host__ __device__ constexpr int v3_off(const int p, const int piece) { return piece * 1280 + p * 160; }
-#else
-static constexpr bool V3_PAIR = true;
+// per row and piece), so that the pairs the output transform combines are final one after the other.  (Rounds 3-4 stored [chunk][piece][position 8]
+// [tx][16 ci].)  The producers' stores of position p, chunk c, piece pc, tile tx: v3_off(p, pc) + c * V3_CHUNKB + tx * 32.
 static constexpr int V3_CHUNKB = 320;
 __host__ __device__ constexpr int v3_pair_of(const int p) { return p == 0 || p == 7 ? 3 : (p - 1) / 2; }
 __host__ __device__ constexpr int v3_half_of(const int p) { return p == 0 ? 0 : p == 7 ? 1 : (p - 1) % 2; }
 __host__ __device__ constexpr int v3_off(const int p, const int piece) { return v3_pair_of(p) * 2560 + piece * 1280 + v3_half_of(p) * 160; }
-#endif
 
 // one LDS-DMA instruction: 64 lanes x 16 bytes from the lanes' global addresses (wave-uniform 64-bit base in SGPRs + a 32-bit lane offset: one
 // address register instead of two) to LDS [lds_addr, lds_addr + 1024).  Raw, so that the compiler's wait-count pass does not know of it: it
@@ -227,12 +220,13 @@ struct W2bGeom {
 };
 __device__ __forceinline__ int w2b_rot(const int slot) { return (slot & 1) + ((slot & 6) << 1); }
 
-template <int DBG = 0, int STAGGER = 5, int AD = 1, int BD = 3>      // DBG (dev builds): 1 no staging, 2 no epilogue, 4 no weight loads, 8 no A reads, 32 no V3 transform; STAGGER: x 1024 cycles; AD / BD: taps of lead of the A / weight fragments
 __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restrict__ v2, const uint4* __restrict__ wp /*[5][8][2][2][64] x 16 B*/,
                                                         const float* __restrict__ bias, uint8_t* __restrict__ v3, const float out_scale,
                                                         uint32_t* __restrict__ overflow, const int n_crops, uint32_t* __restrict__ pass_ctr) {
     using G = W2bGeom;
     constexpr int CO = 64, S = 40;
+    constexpr int STAGGER = 5;                                           // x 1024 cycles (at the loop head)
+    constexpr int AD = 1, BD = 3;                                        // taps of lead of the A / weight fragments (measured at the tap loop)
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
     __shared__ int s_next_pass;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -287,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
     const float bz = bias[co];
     int qmin, nrows;
     W2B_ROWS(pass, qmin, nrows);
-    if (!(DBG & 1)) W2B_DMA(qmin, qmin + nrows);
+    W2B_DMA(qmin, qmin + nrows);
     int res_hi = qmin + nrows;                                           // rows [this pass's qmin, res_hi) are resident
     if (tid == 0) s_next_pass = ((int)atomicAdd(pass_ctr, 1u) + (int)gridDim.x) * PK;
     __syncthreads();
@@ -299,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
     bool ovf = false;
     // the two workgroups of a CU start together and would keep step -- both in their tap loops, then both in their epilogues -- with
     // nothing to overlap: the second half of the grid starts half a pass late
-    if (STAGGER > 0 && blockIdx.x >= gridDim.x / 2) {
+    if (blockIdx.x >= gridDim.x / 2) {
 #pragma unroll 1
         for (int i = 0; i < STAGGER; ++i) __builtin_amdgcn_s_sleep(16);
     }
@@ -330,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         // the tap loop outranks the other workgroup's epilogue on the shared issue port: MFMA and VALU instructions are arbitrated by
         // priority, then age, and an older wave in its (VALU-dense) epilogue would leave a younger wave's MFMAs only the leftover slots
-        if (!(DBG & 64)) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         // operand fetches are issued AD taps (A fragments, LDS) and BD taps (weight fragments, L2) ahead.  Measured: (1, 3), (2, 4), (2, 6) and
         // (3, 7) all take 3.83-3.95 ms per 25600 crops -- the waves' waits (SQ_WAIT_ANY 52 %) are the pass's barriers and its DMA, not these
         uint4 af[AD + 1][2];                                              // ring over taps: [tap % (AD + 1)][piece]
@@ -345,12 +339,10 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
 #pragma clang loop unroll(full)
         for (int tau = 0; tau < 40; ++tau) {
             const int tl = tau % 20;
-            if (!(DBG & 8) && tau + AD < 40) W2B_AREAD(af[(tau + AD) % (AD + 1)], tau + AD);
-            if (!(DBG & 4)) {
-                const int wt = W2_BOFF((tau + BD) % 40);
-                bq[(tau + BD) % 8][0] = buf_load16(wrs, boff, wt);
-                bq[(tau + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
-            }
+            if (tau + AD < 40) W2B_AREAD(af[(tau + AD) % (AD + 1)], tau + AD);
+            const int wt = W2_BOFF((tau + BD) % 40);
+            bq[(tau + BD) % 8][0] = buf_load16(wrs, boff, wt);
+            bq[(tau + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
             const int p = W2_POS(tau);
             const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tau % 8][0]), b2 = __builtin_bit_cast(f16x8, bq[tau % 8][1]);
             const f16x8 a1 = __builtin_bit_cast(f16x8, af[tau % (AD + 1)][0]), a2 = __builtin_bit_cast(f16x8, af[tau % (AD + 1)][1]);
@@ -359,19 +351,17 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
             acc[p] = mfma16(a1, b1, acc[p]);
             // nothing moves across a tap: left alone, the scheduler sinks every operand fetch down to its use (to save registers) and the
             // wave then waits out the full LDS / L2 latency in front of each MFMA
-            if (!(DBG & 512)) {
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);       // the A fragments of tap + AD ...
-                __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);       // ... and the weight fragments of tap + BD go first,
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);       // the A fragments of tap + AD ...
+            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);       // ... and the weight fragments of tap + BD go first,
 #pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // then the three MFMAs with the address arithmetic in between
-                    __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+            for (int g = 0; g < 3; ++g) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // then the three MFMAs with the address arithmetic in between
+                __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
 #undef W2B_AREAD
-        if (!(DBG & 64)) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __syncthreads();                                                  // every wave is done with the operand planes
         const bool draw = pass % PK == PK - 1;                            // the last pass of a ticket moves on to the next ticket
         const int next_pass = draw ? s_next_pass : pass + 1;              // (written at the end of an earlier epilogue, or in the prologue)
@@ -384,56 +374,45 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
         if (have_next) {
             W2B_ROWS(next_pass, qmin_n, nrows_n);
             // the next pass of the same ticket: rows below res_hi are already there (its qmin is not below this pass's)
-            const int lo_new = (next_pass == pass + 1 && res_hi > qmin_n && !(DBG & 256)) ? res_hi : qmin_n;
-            if (!(DBG & 1)) W2B_DMA(lo_new, qmin_n + nrows_n);
+            const int lo_new = (next_pass == pass + 1 && res_hi > qmin_n) ? res_hi : qmin_n;
+            W2B_DMA(lo_new, qmin_n + nrows_n);
             res_hi = qmin_n + nrows_n;
-        }
-        if (DBG & 2) {
-#pragma unroll
-            for (int p = 0; p < 8; ++p) asm volatile("" :: "a"(acc[p]));
         }
         // epilogue 1: Y = A^T M, pool, bias, ReLU -> the pass's 3 x 20 x 64 activations as fp32 in LDS
         float* pbuf = reinterpret_cast<float*>(ldsb + G::PBUF_OFF);
-        if (!(DBG & 2)) {
-            f32x16 y0, y1, y2, y3;
-            {
-                const f32x16 e1 = acc[1] + acc[2], o1 = acc[1] - acc[2];
-                y0 = acc[0] + e1; y1 = o1; y2 = e1; y3 = o1 + acc[7];
-            }
-            {
-                const f32x16 e2 = acc[3] + acc[4], o2 = acc[3] - acc[4];
-                y0 += e2; y1 += 2.f * o2; y2 += 4.f * e2; y3 += 8.f * o2;
-            }
-            {
-                const f32x16 e3 = acc[5] + acc[6], o3 = acc[5] - acc[6];
-                y0 += e3; y1 += 0.5f * o3; y2 += 0.25f * e3; y3 += 0.125f * o3;
-            }
+        f32x16 y0, y1, y2, y3;
+        {
+            const f32x16 e1 = acc[1] + acc[2], o1 = acc[1] - acc[2];
+            y0 = acc[0] + e1; y1 = o1; y2 = e1; y3 = o1 + acc[7];
+        }
+        {
+            const f32x16 e2 = acc[3] + acc[4], o2 = acc[3] - acc[4];
+            y0 += e2; y1 += 2.f * o2; y2 += 4.f * e2; y3 += 8.f * o2;
+        }
+        {
+            const f32x16 e3 = acc[5] + acc[6], o3 = acc[5] - acc[6];
+            y0 += e3; y1 += 0.5f * o3; y2 += 0.25f * e3; y3 += 0.125f * o3;
+        }
 #pragma unroll
-            for (int rr = 0; rr < 8; ++rr) {
-                const int r = 2 * rr;
-                const int s = mg * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // even: rows y, y+1 of one tile column
-                const float v0 = fmaxf(fmaxf(y0[r], y1[r]), fmaxf(y0[r + 1], y1[r + 1]));
-                const float v1 = fmaxf(fmaxf(y2[r], y3[r]), fmaxf(y2[r + 1], y3[r + 1]));
-                if (s < G::RPP * G::TPP) {
-                    const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
-                    const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
-                    ovf |= !(a0 < 4368.0f) | !(a1 < 4368.0f);
-                    float* o = pbuf + (rp * 20 + 2 * tx) * 64 + co;
-                    o[0] = a0;
-                    o[64] = a1;
-                }
+        for (int rr = 0; rr < 8; ++rr) {
+            const int r = 2 * rr;
+            const int s = mg * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // even: rows y, y+1 of one tile column
+            const float v0 = fmaxf(fmaxf(y0[r], y1[r]), fmaxf(y0[r + 1], y1[r + 1]));
+            const float v1 = fmaxf(fmaxf(y2[r], y3[r]), fmaxf(y2[r + 1], y3[r + 1]));
+            if (s < G::RPP * G::TPP) {
+                const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
+                const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
+                ovf |= !(a0 < 4368.0f) | !(a1 < 4368.0f);
+                float* o = pbuf + (rp * 20 + 2 * tx) * 64 + co;
+                o[0] = a0;
+                o[64] = a1;
             }
         }
-        if (DBG & 128) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        } else {
-            // raw barrier: the activations in LDS are what the second half needs; the DMA keeps flying until the end of the epilogue
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
+        // raw barrier: the activations in LDS are what the second half needs; the DMA keeps flying until the end of the epilogue
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
         // epilogue 2: (pooled row, conv3 tile, channel quad) items -> V3
-        if (!(DBG & (2 | 32)) && tid < 240) {
+        if (tid < 240) {
             const int rp = tid / 80, rem = tid - rp * 80, tx = rem >> 4, quad = rem & 15;
             const int gp = pass * G::RPP + rp;                            // = q3: pooled row of the batch
             if (gp < total_pairs) {
@@ -481,285 +460,4 @@ __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restric
 #undef W2_POS
 #undef W2_BOFF
     if (__any(ovf) && lane == 0) atomicOr(overflow, 3u);      // bit 1: this kernel does not know the crop (k_guard_plan: every crop)
-}
-
-// ------------------------------------------------------------------------------------------------
-// conv3 (64 -> 128 channels, 20x20) on V3: k_conv5_wino<64,128,20,2>'s tap loop and epilogue, with the staging of a 16-channel chunk
-// reduced to 13 x (16-byte load, 16-byte LDS store) per thread in two batches (7 loads at tap 0, 6 at tap 19; the stores follow one
-// per tap 12 / 11 taps later).  LDS layout unchanged: [buffer][piece][row slot][position][tx][16 ci], a (row, piece) is 1280
-// contiguous bytes both in V3 and in LDS.
-// ------------------------------------------------------------------------------------------------
-template <int DBG = 0, int BD = 7, int PK = 4, int STG = 1, int DT0 = 2>      // PK: consecutive passes per workgroup and ticket (their halo rows are then L2 hits); STG: 1 = staging by LDS-DMA from tap DT0 on, 0 = through registers
-__global__ __launch_bounds__(256) void k_conv5_wpre(const uint8_t* __restrict__ v3, const uint4* __restrict__ wp /*[4][5][8][2][2][128] x 16 B*/,
-                                                    const float* __restrict__ bias, float* __restrict__ out, const float out_scale,
-                                                    const int n_crops, uint32_t* __restrict__ pass_ctr,
-                                                    const int n_big /* tickets of PK passes; the passes behind them go out one by one, so that the workgroups finish together */) {
-    constexpr int CI = 64, CO = 128, S = 20, TPW = 2;
-    using G = WinoGeom<CI, CO, S, TPW>;
-    static_assert(G::NTHR == 256 && G::RP0 == 1280 && G::NCH * 2 * G::RP0 == V3_ROWB, "geometry");
-    constexpr int NU = G::NR * 2 * 80, NIT = (NU + 255) / 256;          // 16-byte units per chunk, per thread
-    static_assert(NIT == 13, "one batch of 13 units");
-    extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
-    __shared__ int s_next_pass;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;
-    const int n = wave % G::NT, mg = wave / G::NT;
-    const int total_tiles = n_crops * G::TPC;
-    const int n_pass = (total_tiles + G::MB - 1) / G::MB;
-    const int big_end = n_big * PK;
-    auto ticket_first = [&](const int t) { return t < n_big ? t * PK : big_end + (t - n_big); };
-    int pass = ticket_first((int)blockIdx.x);
-    if (pass >= n_pass) return;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)ldsb;
-    // Staging of a chunk by LDS-DMA (no registers, no LDS store instructions -- a 16-byte ds_write costs the whole CU ~30 cycles): the NR padded
-    // rows of a piece plane are one linear LDS range of NR * RP bytes = NI instructions of 1 KB; lane l of instruction ii covers byte
-    // ii * 1024 + 16 l of it = (row, unit) by one division -- units in a row's pad fetch the row's last unit, lanes past the range stay off --
-    // and supplies the offset of its own unit.  Wave w issues the instructions w, w + 4, ...: at most NDW per wave and chunk, one per tap.
-    constexpr int NI = (G::NR * G::RP + 1023) / 1024, NDW = (2 * NI + 3) / 4;
-#define W3_BASE(cc_, qmin_) wave_uniform64(reinterpret_cast<unsigned long long>(v3) + (unsigned long long)(qmin_) * V3_ROWB + (unsigned)((cc_) * 2560))
-#define W3_DMA(k_, sbase_, nrows_, buf_)                                                                                         \
-    do {                                                                                                                         \
-        const int i_ = wave + 4 * (k_);                                                                                          \
-        if (i_ < 2 * NI) {                                                                                                       \
-            const int pc_ = i_ >= NI ? 1 : 0, ii_ = i_ - pc_ * NI;                                                               \
-            const int o_ = ii_ * 1024 + lane * 16;                                                                               \
-            if (o_ < G::NR * G::RP) {                                                                                            \
-                int row_ = o_ / G::RP, w_ = o_ - row_ * G::RP;                                                                   \
-                w_ = w_ < G::RP0 ? w_ : G::RP0 - 16;                                                                             \
-                row_ = row_ < (nrows_) ? row_ : (nrows_) - 1;                                                                    \
-                wpre_dma16(sbase_, (uint32_t)(row_ * V3_ROWB + pc_ * 1280 + w_),                                                 \
-                           lds0 + (uint32_t)((buf_) * G::BUF + pc_ * G::PLANE + G::RP + ii_ * 1024));                            \
-            }                                                                                                                    \
-        }                                                                                                                        \
-    } while (0)
-    for (int i = tid; i < 4 * (G::RP / 16); i += G::NTHR) {
-        const int pl = i / (G::RP / 16), o = i - pl * (G::RP / 16);
-        *reinterpret_cast<uint4*>(ldsb + pl * G::PLANE + o * 16) = make_uint4(0, 0, 0, 0);
-    }
-    uint4 sreg[13] = {};
-    __amdgpu_buffer_rsrc_t srs = make_rsrc(v3, 0);
-    // (the LDS address of a unit is recomputed at its store: a register held across the 40 taps is one the weight ring cannot have, and a spilled
-    // one comes back through a scratch load that drains the whole VMEM queue)
-#define W3_UNIT(k_, nrows_)                                                                                                      \
-        int u_ = tid + (k_) * 256;                                                                                               \
-        asm volatile("" : "+v"(u_));             /* not loop-invariant for the compiler: no hoisting, nothing to keep or spill */ \
-        const int rp_ = u_ / 80, w_ = u_ - rp_ * 80;                                                                             \
-        int row_ = rp_ >> 1;                                                                                                     \
-        const int pc_ = rp_ & 1;                                                                                                 \
-        row_ = row_ < (nrows_) ? row_ : (nrows_) - 1;
-#define W3_L(k_, j_, cc_, qmin_, nrows_)                                                                                         \
-    do {                                                                                                                         \
-        W3_UNIT(k_, nrows_)                                                                                                      \
-        srs = make_rsrc(v3 + (size_t)((DBG & 16) ? 0 : (qmin_)) * V3_ROWB, (uint32_t)(G::NR * V3_ROWB));                         \
-        sreg[j_] = buf_load16(srs, row_ * V3_ROWB + pc_ * 1280 + w_ * 16, (cc_) * 2560);                                         \
-    } while (0)
-#define W3_S(k_, j_, nrows_, base_)                                                                                              \
-    do {                                                                                                                         \
-        W3_UNIT(k_, nrows_)                                                                                                      \
-        *reinterpret_cast<uint4*>((base_) + (row_ + 1) * G::RP + pc_ * G::PLANE + w_ * 16) = sreg[j_];                           \
-    } while (0)
-
-    const __amdgpu_buffer_rsrc_t wrs = make_rsrc(wp, (uint32_t)(G::NCH * 40 * G::BV * 16));
-    const int boff = (h * CO + n * 32 + j) * 16;
-    const int co = n * 32 + j;
-    const float bz = bias[co];
-    int qmin, nrows;
-    wino_pass_rows<G, S>(pass, total_tiles, qmin, nrows);
-    if (!(DBG & 1)) {
-        if constexpr (STG) {
-#pragma unroll
-            for (int k = 0; k < NDW; ++k) W3_DMA(k, W3_BASE(0, qmin), nrows, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-#pragma unroll
-            for (int k = 0; k < 13; ++k) W3_L(k, k, 0, qmin, nrows);
-#pragma unroll
-            for (int k = 0; k < 13; ++k) W3_S(k, k, nrows, ldsb);
-        }
-    }
-    __syncthreads();
-    uint4 bq[8][2];
-#pragma unroll
-    for (int t = 0; t < BD; ++t) {
-        bq[t][0] = buf_load16(wrs, boff, t * G::BV * 16);
-        bq[t][1] = buf_load16(wrs, boff, t * G::BV * 16 + 2 * CO * 16);
-    }
-    int bufsel = 0;
-    for (;;) {
-        int aoff[TPW][5];
-        const int T0 = pass * G::MB + mg * TPW * 32;
-#pragma unroll
-        for (int m = 0; m < TPW; ++m) {
-            int T = T0 + m * 32 + j;
-            if (T > total_tiles - 1) T = total_tiles - 1;
-            const int gp = T / G::TPP, r2 = T - gp * G::TPP;
-            const int tx = r2 >> 1, qo = 2 * gp + (r2 & 1), y = qo % S;
-#pragma unroll
-            for (int ky = 0; ky < 5; ++ky) {
-                const int iy = y + ky - 2;
-                aoff[m][ky] = ((iy >= 0 && iy < S) ? (qo + ky - 2 - qmin + 1) * G::RP : 0) + tx * 32 + h * 16;
-            }
-        }
-        // (not zeroed: the first product of every accumulator -- taps 0..7 of the pass's first chunk -- takes the constant 0 as its C operand;
-        // 256 v_accvgpr_write per pass and wave otherwise)
-        f32x16 acc[TPW][8];
-        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        // The output transform A^T (4 outputs from the 8 positions) in three position groups; y3 takes position 7 last (it is the last to arrive:
-        // position p is final after tap 32 + p of the last chunk).  Tile 0's first two groups are WRITTEN under taps 34-39 of the last chunk.
-        // What the compiler makes of that: the arithmetic itself sinks back into the guarded store blocks behind the loop, but tile 0's 128
-        // accumulator reads stay under the last taps, and with one wave per SIMD everything behind the last tap is exposed: 4.52 -> 4.32 ms.
-        // (Pinning the arithmetic under the taps as well -- an empty asm on the partial sums -- needs 48-64 more live registers: spills, 7 ms.)
-        f32x16 ya0, ya1, ya2, ya3;
-        auto ep1 = [&](const int m, const int ra, const int rb, f32x16& y0, f32x16& y1, f32x16& y2, f32x16& y3) {
-#pragma unroll
-            for (int r = ra; r < rb; ++r) {
-                const float e1 = acc[m][1][r] + acc[m][2][r], o1 = acc[m][1][r] - acc[m][2][r];
-                y0[r] = acc[m][0][r] + e1; y1[r] = o1; y2[r] = e1; y3[r] = o1;
-            }
-        };
-        auto ep2 = [&](const int m, const int ra, const int rb, f32x16& y0, f32x16& y1, f32x16& y2, f32x16& y3) {
-#pragma unroll
-            for (int r = ra; r < rb; ++r) {
-                const float e2 = acc[m][3][r] + acc[m][4][r], o2 = acc[m][3][r] - acc[m][4][r];
-                y0[r] += e2; y1[r] += 2.f * o2; y2[r] += 4.f * e2; y3[r] += 8.f * o2;
-            }
-        };
-        auto ep3 = [&](const int m, f32x16& y0, f32x16& y1, f32x16& y2, f32x16& y3) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e3 = acc[m][5][r] + acc[m][6][r], o3 = acc[m][5][r] - acc[m][6][r];
-                y0[r] += e3; y1[r] += 0.5f * o3; y2[r] += 0.25f * e3; y3[r] += 0.125f * o3;
-                y3[r] += acc[m][7][r];
-            }
-        };
-        int next_pass = pass + 1;
-        const bool draw = pass >= big_end || pass % PK == PK - 1;          // the last pass of a ticket draws the next one
-        if (draw && tid == 0) s_next_pass = ticket_first((int)atomicAdd(pass_ctr, 1u) + (int)gridDim.x);   // read by everyone after the first chunk's barrier
-        bool have_next = false;
-        int qmin_n = qmin, nrows_n = nrows;
-#pragma clang loop unroll(full)
-        for (int cc = 0; cc < G::NCH; ++cc) {
-            const bool last_c = cc == G::NCH - 1;
-            if (last_c) {
-                if (draw) next_pass = s_next_pass;
-                have_next = next_pass < n_pass;
-                if (have_next) wino_pass_rows<G, S>(next_pass, total_tiles, qmin_n, nrows_n);
-            }
-            const uint8_t* pbase = ldsb + bufsel * G::BUF;
-            uint8_t* nbase = ldsb + (bufsel ^ 1) * G::BUF;
-            // staged under this chunk: the next chunk of this pass, or the first chunk of the next pass (without one: this pass's first
-            // chunk once more, into the buffer nobody reads again)
-            const int scc = last_c ? 0 : cc + 1;
-            const int sqmin = last_c ? qmin_n : qmin, snrows = last_c ? nrows_n : nrows;
-            const int wc = cc * 40 * G::BV * 16, wn = scc * 40 * G::BV * 16;
-            const unsigned long long sbase = STG ? W3_BASE(scc, sqmin) : 0ull;
-            uint4 af[2][TPW][2];
-#pragma unroll
-            for (int m = 0; m < TPW; ++m) {
-                af[0][m][0] = *reinterpret_cast<const uint4*>(pbase + aoff[m][0]);
-                af[0][m][1] = *reinterpret_cast<const uint4*>(pbase + aoff[m][0] + G::PLANE);
-            }
-#pragma clang loop unroll(full)
-            for (int t = 0; t < 40; ++t) {
-                const int cur = t & 1, nxt = cur ^ 1;
-                if (!(DBG & 8) && t + 1 < 40) {
-                    const uint8_t* an = pbase + ((t + 1) % 8) * G::PS;
-#pragma unroll
-                    for (int m = 0; m < TPW; ++m) {
-                        af[nxt][m][0] = *reinterpret_cast<const uint4*>(an + aoff[m][(t + 1) / 8]);
-                        af[nxt][m][1] = *reinterpret_cast<const uint4*>(an + aoff[m][(t + 1) / 8] + G::PLANE);
-                    }
-                }
-                if (!(DBG & 4)) {
-                    const int wt = t + BD < 40 ? wc + (t + BD) * G::BV * 16 : wn + (t + BD - 40) * G::BV * 16;
-                    bq[(t + BD) % 8][0] = buf_load16(wrs, boff, wt);
-                    bq[(t + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
-                }
-                if (!(DBG & 1)) {
-                    if constexpr (STG) {
-                        if (t >= DT0 && t < DT0 + NDW) W3_DMA(t - DT0, sbase, snrows, bufsel ^ 1);
-                    } else {
-                        // ONE batch of loads per chunk: every batch of HBM misses holds back the weight fragments queued behind it once
-                        if (t == 0 && !(DBG & 128)) { _Pragma("unroll") for (int k = 0; k < 13; ++k) W3_L(k, k, scc, sqmin, snrows); }
-                        if (t >= 16 && t < 29 && !(DBG & 64)) W3_S(t - 16, t - 16, snrows, nbase);
-                    }
-                }
-                const int p = t % 8;
-                const f16x8 b1 = __builtin_bit_cast(f16x8, bq[t % 8][0]);
-                const f16x8 b2 = __builtin_bit_cast(f16x8, bq[t % 8][1]);
-                f16x8 a1[TPW], a2[TPW];
-#pragma unroll
-                for (int m = 0; m < TPW; ++m) { a1[m] = __builtin_bit_cast(f16x8, af[cur][m][0]); a2[m] = __builtin_bit_cast(f16x8, af[cur][m][1]); }
-#pragma unroll
-                for (int m = 0; m < TPW; ++m) acc[m][p] = mfma16(a2[m], b1, (cc == 0 && t < 8) ? zero16 : acc[m][p]);
-#pragma unroll
-                for (int m = 0; m < TPW; ++m) acc[m][p] = mfma16(a1[m], b2, acc[m][p]);
-#pragma unroll
-                for (int m = 0; m < TPW; ++m) acc[m][p] = mfma16(a1[m], b1, acc[m][p]);
-                if (cc == G::NCH - 1 && !(DBG & 2)) {
-                    if (t == 34) ep1(0, 0, 5, ya0, ya1, ya2, ya3);
-                    if (t == 35) ep1(0, 5, 11, ya0, ya1, ya2, ya3);
-                    if (t == 36) ep1(0, 11, 16, ya0, ya1, ya2, ya3);
-                    if (t == 37) ep2(0, 0, 5, ya0, ya1, ya2, ya3);
-                    if (t == 38) ep2(0, 5, 11, ya0, ya1, ya2, ya3);
-                    if (t == 39) ep2(0, 11, 16, ya0, ya1, ya2, ya3);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * TPW, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 10, 0);
-#pragma unroll
-                for (int g = 0; g < 3 * TPW; ++g) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x206, 8, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // this wave's part of the next chunk has landed: loads return in order, so everything older than the 2 x BD weight fragments in flight
-            // (the next chunk's first taps) is complete -- the DMA instructions were issued before them.  (vmcnt(0) would drain those fragments too:
-            // one L2 round trip per chunk)
-            if constexpr (STG) { if constexpr (BD == 7 && !(DBG & 256)) asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-            __syncthreads();
-            bufsel ^= 1;
-        }
-#pragma unroll
-        for (int m = 0; m < ((DBG & 2) ? 0 : TPW); ++m) {
-            f32x16 y0, y1, y2, y3;
-            if (m == 0) { y0 = ya0; y1 = ya1; y2 = ya2; y3 = ya3; }
-            else {
-                ep1(m, 0, 16, y0, y1, y2, y3);
-                __builtin_amdgcn_sched_barrier(0);
-                ep2(m, 0, 16, y0, y1, y2, y3);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            ep3(m, y0, y1, y2, y3);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) {
-                const int r = 2 * rr;
-                const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int T = T0 + m * 32 + i;
-                const float v0 = fmaxf(fmaxf(y0[r], y1[r]), fmaxf(y0[r + 1], y1[r + 1]));
-                const float v1 = fmaxf(fmaxf(y2[r], y3[r]), fmaxf(y2[r + 1], y3[r + 1]));
-                if (T < total_tiles) {
-                    const int gp = T / G::TPP, tx = (T - gp * G::TPP) >> 1;
-                    float* o = out + ((size_t)gp * (S / 2) + 2 * tx) * CO + co;
-                    __builtin_nontemporal_store(fmaxf(v0 * out_scale + bz, 0.f), o);
-                    __builtin_nontemporal_store(fmaxf(v1 * out_scale + bz, 0.f), o + CO);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (DBG & 2) {
-#pragma unroll
-            for (int m = 0; m < TPW; ++m)
-#pragma unroll
-                for (int p = 0; p < 8; ++p) asm volatile("" :: "a"(acc[m][p]));
-        }
-        if (!have_next) break;
-        pass = next_pass; qmin = qmin_n; nrows = nrows_n;
-    }
-#undef W3_L
-#undef W3_UNIT
-#undef W3_S
-#undef W3_DMA
-#undef W3_BASE
 }

@@ -154,7 +154,7 @@ struct trexhip_ctx {
     int tune_rows_blocks = 8192;
     int tune_rows_k = 0;                // frames per wave of k_rows32b (TREXHIP_ROWS_K; 0 = default 8)
     bool tune_rows_blocks_set = false;  // TREXHIP_ROWS_BLOCKS given: no automatic grid for the wide pixel pass
-    int tune_conv_geom = 0;             // dev only: alternative conv tilings (TREXHIP_CONV_GEOM)
+    int tune_conv_geom = 0;             // dev only: which identity-network chain runs (TREXHIP_CONV_GEOM, bits 0-11 and 28-30)
     // hipFuncSetAttribute is per device: one process may drive several devices through several contexts
     bool attr_cnn = false, attr_ccl = false, attr_split = false;
     bool ctr_dirty = false;             // a detect pass was queued but not to its end: the per-frame overflow counters may be non-zero (launch_segment zeroes them first)
