@@ -312,21 +312,6 @@ def test_range_guard_is_per_crop(geom, monkeypatch):
     seg.close()
 
 
-def _stage_maxima(st, crops):
-    """largest activation behind each conv + BN + ReLU + pool stage per crop (float64 on the host): what the range guards of the default chain look at"""
-    import torch.nn.functional as F
-    t = {k: torch.from_numpy(np.ascontiguousarray(v, np.float64)) for k, v in st.items()}
-    out = []
-    with torch.no_grad():
-        x = torch.from_numpy(np.ascontiguousarray(crops)).to(torch.float64).permute(0, 3, 1, 2)
-        for i in (1, 2, 3):
-            x = F.conv2d(x, t[f"conv{i}.weight"], t[f"conv{i}.bias"], padding=2)
-            x = F.batch_norm(x, t[f"bn{i}.running_mean"], t[f"bn{i}.running_var"], t[f"bn{i}.weight"], t[f"bn{i}.bias"], training=False, eps=1e-5)
-            x = F.max_pool2d(F.relu(x), 2)
-            out.append(x.reshape(x.shape[0], -1).max(1).values.numpy())
-    return out
-
-
 def test_unattributed_range_flag_reruns_every_crop(monkeypatch):
     """in the two-kernel chain (TREXHIP_CONV_GEOM bit 28; also the 3-channel network's chain) conv1 / conv2 raise the fp16 range flag
     WITHOUT naming the crop, while fc1 names it.  Crop A leaves the range in conv1, crop B only in front of fc1: a plan that listed just B would
@@ -340,11 +325,11 @@ def test_unattributed_range_flag_reruns_every_crop(monkeypatch):
     crops[B, 10:70, 10:70, 0] = rng.integers(0, 12, (60, 60))              # B: brighter, still inside conv1's and conv2's range
     quiet = np.ones(n, bool); quiet[[A, B]] = False
     crops[A, :, :, 0] = rng.integers(0, 256, (80, 80))                     # A: far outside conv1's range
-    m1 = _stage_maxima(st, crops)[0]
+    m1 = cnn_oracle.stage_maxima(st, crops)[0]
     m = 3500.0 / m1[B]                                                      # conv1: B peaks at 3500 (< 4368), A far above
     st["conv1.weight"] *= m; st["conv1.bias"] *= m; st["bn1.running_mean"] *= m
     st["bn2.running_var"] = st["bn2.running_var"] * m * m
-    s1, s2, s3 = _stage_maxima(st, crops)
+    s1, s2, s3 = cnn_oracle.stage_maxima(st, crops)
     assert s1[A] > 3 * 4368 and s1[B] < 4368 and s1[quiet].max() < 4368, (s1[A], s1[B], s1[quiet].max())
     assert s2[B] < 4368 and s2[quiet].max() < 4368, (s2[B], s2[quiet].max())
     # act3 (fc1's input) scaled so that B alone passes what two fp16 pieces hold; fc1 takes the scale back out

@@ -50,3 +50,24 @@ def test_rejects_other_networks_and_bad_shapes():
     del ck["state_dict"]["model.bn4.bias"]
     with pytest.raises(KeyError):
         cw.convert(ck)
+
+
+def test_arbitrary_bit_patterns_survive_blob_and_converter():
+    """what a TRAINED network holds -- any float32 whatsoever: denormals, huge and tiny magnitudes, negative zero -- goes through pack_blob,
+    unpack_blob and the converter bit for bit (the values above are uniform(+-1/sqrt(fan_in)): one exponent range).  The device-trained state
+    itself takes the same trip in tests/test_cnn_trained_gpu.py."""
+    rng = np.random.default_rng(3)
+    st = {}
+    for name, shp in weights.shapes(16):
+        bits = rng.integers(0, 1 << 32, int(np.prod(shp)), dtype=np.uint64).astype(np.uint32)
+        bits[(bits & 0x7f800000) == 0x7f800000] &= 0x807fffff            # no inf / NaN: NaN payloads need not survive a torch tensor
+        st[name] = bits.view(np.float32).reshape(shp)
+    st["fc2.bias"][:3] = [-0.0, np.float32(1e-45), np.float32(-3e38)]
+    blob = weights.pack_blob(st, 16)
+    back, classes, channels = weights.unpack_blob(blob)
+    assert (classes, channels) == (16, 1)
+    for k in st:
+        assert back[k].tobytes() == st[k].tobytes(), k
+    assert weights.pack_blob(back, 16) == blob
+    blob2, c, w, h, ch = cw.convert({"model." + k: torch.from_numpy(v.copy()) for k, v in st.items()})
+    assert (c, w, h, ch) == (16, 80, 80, 1) and blob2 == blob
