@@ -7,5 +7,5 @@ F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-un
 /opt/rocm/bin/hipcc $F -c segment.hip -o /tmp/segment_dev.o &
 /opt/rocm/bin/hipcc $F -c capi.hip -o /tmp/capi_dev.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libtrexhip_dev.so /tmp/capi_dev.o /tmp/segment_dev.o cnn.o crops.o morph.o posture.o midline.o split.o upload.o comm.o pack.o train.o hostcvt.o pvfile.o -lpthread -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libtrexhip_dev.so /tmp/capi_dev.o /tmp/segment_dev.o cnn.o cnn_any.o cnn_weights.o crops.o morph.o posture.o midline.o split.o upload.o comm.o pack.o train.o hostcvt.o pvfile.o -lpthread -ldl
 ls -la ../libtrexhip_dev.so

@@ -19,7 +19,8 @@
 //   k_fc1       [crops x 12800] x [12800 x 128] MFMA GEMM, LDS tiles
 //   k_head      LayerNorm + ReLU + fc2 + softmax, four crops per wave
 #include "internal.h"
-#include "conv_f32.h"
+#include "cnn_split.h"
+#include "cnn_weights.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -109,7 +110,6 @@ __global__ __launch_bounds__(256, 2) void k_conv1(const uint8_t* __restrict__ cr
 // (lane: column co, rows 4g..4g+3 = two windows x two image rows) makes the 2x2 max-pool a max over registers of one lane.
 // ------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8_c1 __attribute__((ext_vector_type(8)));
 
 // ------------------------------------------------------------------------------------------------
 // fp16 range guard, per crop (round 5).  The default chain raises overflow[0] when an activation leaves the range its fp16 pieces can hold and,
@@ -120,7 +120,6 @@ typedef _Float16 f16x8_c1 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------
 static constexpr int FB_MAX = 1024;           // more flagged crops than this: every crop is re-run
 __device__ __forceinline__ int fb_count(const uint32_t* __restrict__ plan, const int n) { return (plan && plan[1] == 1u) ? (int)plan[0] : n; }
-__device__ __forceinline__ int fb_crop(const uint32_t* __restrict__ plan, const int i) { return (plan && plan[1] == 1u) ? (int)plan[2 + i] : i; }
 // (called by every thread of ONE workgroup of NT threads; `cnt` is that workgroup's shared counter.)  The last reader of the range flag and of the
 // persistent convolutions' pass counters hands all three back zeroed for the next forward pass: no memset in front of a pass (round 6)
 template <int NT>
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(256) void k_conv1_mfma(const uint8_t* __restrict__ 
     constexpr int S = 80, PH = 84, PITCH = 88;              // halves per padded row (176 B: rows land on distinct bank groups)
     __shared__ __attribute__((aligned(16))) _Float16 img[PH * PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int crop = fb_crop(guard, (int)blockIdx.x);
+    const int crop = plan_crop(guard, (int)blockIdx.x);
     const uint8_t* src = crops + (size_t)crop * S * S;
     // zero the padded image, then 16 pixels per thread: one 16-byte load of the crop row, 16 halves into LDS
     for (int i = tid; i < PH * PITCH * 2 / 16; i += 256) reinterpret_cast<uint4*>(img)[i] = make_uint4(0, 0, 0, 0);
@@ -197,15 +196,15 @@ __global__ __launch_bounds__(256) void k_conv1_mfma(const uint8_t* __restrict__ 
         uint4 a1u, a2u;
         { const uint2 lo = *reinterpret_cast<const uint2*>(p1), hi = *reinterpret_cast<const uint2*>(p1 + 4); a1u = make_uint4(lo.x, lo.y, hi.x, hi.y); }
         { const uint2 lo = *reinterpret_cast<const uint2*>(p2), hi = *reinterpret_cast<const uint2*>(p2 + 4); a2u = make_uint4(lo.x, lo.y, hi.x, hi.y); }
-        const f16x8_c1 a1 = __builtin_bit_cast(f16x8_c1, a1u), a2 = __builtin_bit_cast(f16x8_c1, a2u);
+        const f16x8 a1 = __builtin_bit_cast(f16x8, a1u), a2 = __builtin_bit_cast(f16x8, a2u);
         f32x4 acc[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             f32x4 c = {0.f, 0.f, 0.f, 0.f};
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 1]), c, 0, 0, 0);   // low pieces first
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 3]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 0]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 2]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8, bf[s * 4 + 1]), c, 0, 0, 0);   // low pieces first
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8, bf[s * 4 + 3]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8, bf[s * 4 + 0]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8, bf[s * 4 + 2]), c, 0, 0, 0);
             acc[s] = c;
         }
         // lane (co, q) holds 4 consecutive pooled pixels of channel co; through LDS to one float4 (4 channels of one pixel) per lane
@@ -239,7 +238,7 @@ __global__ __launch_bounds__(256) void k_conv1_mfma3(const uint8_t* __restrict__
     __shared__ __attribute__((aligned(16))) _Float16 img[3 * PLANE];
     __shared__ __attribute__((aligned(16))) float tr[4][64 * 17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int crop = fb_crop(guard, (int)blockIdx.x);
+    const int crop = plan_crop(guard, (int)blockIdx.x);
     const uint32_t* src = reinterpret_cast<const uint32_t*>(crops + (size_t)crop * S * S * 3);
     for (int i = tid; i < 3 * PLANE * 2 / 16; i += 256) reinterpret_cast<uint4*>(img)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
@@ -270,22 +269,22 @@ __global__ __launch_bounds__(256) void k_conv1_mfma3(const uint8_t* __restrict__
         const int wdx = tile * 8 + (r >> 1);
         const int yp = wdx / 20, x4 = (wdx - yp * 20) * 4;
         const int row = 2 * yp + (r & 1);
-        f16x8_c1 a[4];
+        f16x8 a[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             // m < 3: channel m, kernel row q; m == 3: kernel row 4 of channel q (the fourth k-octet meets zero weights)
             const _Float16* pp = m < 3 ? img + m * PLANE + (row + q) * PITCH + x4 : img + (q < 3 ? q : 0) * PLANE + (row + 4) * PITCH + x4;
             const uint2 lo = *reinterpret_cast<const uint2*>(pp), hi = *reinterpret_cast<const uint2*>(pp + 4);
-            a[m] = __builtin_bit_cast(f16x8_c1, make_uint4(lo.x, lo.y, hi.x, hi.y));
+            a[m] = __builtin_bit_cast(f16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
         }
         f32x4 acc[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             f32x4 c = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8_c1, bf[(s * 4 + m) * 2 + 1]), c, 0, 0, 0);   // low pieces first
+            for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8, bf[(s * 4 + m) * 2 + 1]), c, 0, 0, 0);   // low pieces first
 #pragma unroll
-            for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8_c1, bf[(s * 4 + m) * 2 + 0]), c, 0, 0, 0);
+            for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8, bf[(s * 4 + m) * 2 + 0]), c, 0, 0, 0);
             acc[s] = c;
         }
         float* tw = tr[wave];
@@ -307,46 +306,9 @@ __global__ __launch_bounds__(256) void k_conv1_mfma3(const uint8_t* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
-// the same convolution on the bf16 matrix cores with fp32-equivalent accuracy: every fp32 operand is split
-// into three bf16 pieces x = x1 + x2 + x3 (x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2); 24
-// mantissa bits in total) and a product a*w is formed from the six piece products whose order is >= 2^-16
-// (a1w1, a1w2, a2w1, a1w3, a2w2, a3w1; NTERMS = 3 keeps only the first three).  bf16 x bf16 products are
-// exact in fp32 and the MFMA accumulates in fp32, so what is dropped is ~3 * 2^-24 relative per product --
-// the size of fp32 rounding itself.  v_mfma_f32_32x32x16_bf16 runs at 16x the rate of the fp32 MFMA, so six
-// of them per product are 2.7x faster than v_mfma_f32_32x32x2_f32.
-// Layouts: activations are split while the patch is staged (three patches [pixel][16 ci] bf16, 48-byte pixel
-// stride); weights are pre-split on the host as [ci-chunk][tap][piece][k/8][co][8].
+// the same convolution on the bf16 matrix cores with fp32-equivalent accuracy (the operand splits: cnn_split.h).  Activations are split while the
+// patch is staged (three patches [pixel][16 ci] bf16, 48-byte pixel stride); weights are pre-split on the host (cnn_weights.h: pack_bf16x3).
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint32_t bf16_rne(float x) {
-    uint32_t u = __float_as_uint(x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ void split3(float x, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-    p1 = bf16_rne(x);
-    const float r1 = x - __uint_as_float(p1 << 16);
-    p2 = bf16_rne(r1);
-    const float r2 = r1 - __uint_as_float(p2 << 16);
-    p3 = bf16_rne(r2);
-}
-// fp16 variant: two pieces x = h1 + h2 carry 22 mantissa bits (plus an absolute floor of 3e-8 from fp16 subnormals),
-// so the three products h1g1, h1g2, h2g1 are already fp32-class.  fp16 cannot hold |x| >= 65520: such a value raises
-// the overflow flag and the host reruns the layer stack with the bf16 split (never a silent wrong answer).
-__device__ __forceinline__ void split2h(float x, uint32_t& p1, uint32_t& p2, bool& ovf) {
-    const _Float16 h1 = (_Float16)x;
-    ovf |= !(fabsf(x) < 65520.0f);
-    const float r1 = x - (float)h1;
-    const _Float16 h2 = (_Float16)r1;
-    p1 = __builtin_bit_cast(uint16_t, h1);
-    p2 = __builtin_bit_cast(uint16_t, h2);
-}
-
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
 template <int CI, int CO, int S, int ROWS, int NP, int CICP = 16>
 struct ConvGeomB {
     static constexpr int CIC = CICP;                                  // input channels per staged chunk (16 or 32)
@@ -385,7 +347,7 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
     const int n_blocks_eff = (guard && guard[1] == 1u) ? (int)guard[0] * G::BPC : n_blocks;      // list mode: the flagged crops only
     for (int blk = blockIdx.x; blk < n_blocks_eff; blk += gridDim.x) {
     if (blk != (int)blockIdx.x) __syncthreads();                      // the previous block's readers are done with the LDS buffers
-    const int crop = fb_crop(guard, blk / G::BPC), row0 = (blk % G::BPC) * ROWS;
+    const int crop = plan_crop(guard, blk / G::BPC), row0 = (blk % G::BPC) * ROWS;
     constexpr int WR = S / 2;
 
     int aoff[G::TPW];
@@ -1058,7 +1020,7 @@ __global__ __launch_bounds__(256) void k_fc1(const float* __restrict__ act, cons
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     float4 na, nb0, nb1, nb2, nb3;
     const bool arow = m0 + ar < n_eff;
-    const float* asrc = act + (size_t)(arow ? fb_crop(guard, m0 + ar) : 0) * K + kbeg + aq * 4;
+    const float* asrc = act + (size_t)(arow ? plan_crop(guard, m0 + ar) : 0) * K + kbeg + aq * 4;
     const float4* wsrc = reinterpret_cast<const float4*>(w) + (size_t)kbeg * 32 + tid;
 #define FC1_FETCH(k0)                                                                                  \
     do {                                                                                               \
@@ -1094,7 +1056,7 @@ __global__ __launch_bounds__(256) void k_fc1(const float* __restrict__ act, cons
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m0 + i < n_eff) out[(size_t)fb_crop(guard, m0 + i) * 128 + co] = acc[r] + bz;
+        if (m0 + i < n_eff) out[(size_t)plan_crop(guard, m0 + i) * 128 + co] = acc[r] + bz;
     }
 }
 
@@ -1234,7 +1196,7 @@ __global__ __launch_bounds__(256) void k_head(const float* __restrict__ fc1 /*[N
     const int nq = n_items - crop0 < Q ? n_items - crop0 : Q;            // crops of this wave (wave-uniform)
     int cidx[Q];
 #pragma unroll
-    for (int q = 0; q < Q; ++q) cidx[q] = fb_crop(guard, crop0 + (q < nq ? q : 0));
+    for (int q = 0; q < Q; ++q) cidx[q] = plan_crop(guard, crop0 + (q < nq ? q : 0));
     const float g0 = ln_g[lane], be0 = ln_b[lane];
     const float g1 = lane + 64 < 100 ? ln_g[lane + 64] : 0.f, be1 = lane + 64 < 100 ? ln_b[lane + 64] : 0.f;
     // the fc1 partial planes of the split-K launch: every load of the wave's crops goes out first (the planes lie n * 512 bytes apart: a chain of
@@ -1416,7 +1378,8 @@ struct Net {
     float *act1 = nullptr, *act2 = nullptr, *act3 = nullptr, *fc1 = nullptr, *probs = nullptr, *logits = nullptr;
     uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
     uint8_t* crops = nullptr;
-    float* h_probs = nullptr;
+    float* h_probs = nullptr;                  // pinned
+    std::vector<void*> weights, batch;         // every device allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
     // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one
     // identify call is captured into a hipGraph per (buffers, n, precision) and replayed
     // A chain is only captured once the same (buffers, n, precision) key has come THREE times: in tracking the blob count changes from
@@ -1444,307 +1407,85 @@ static void drop_graphs(Net* n) {
     n->graphs.clear();
 }
 
+// every device buffer is allocated through here and freed through the list it was put on
+template <class T>
+static int dev_alloc(std::vector<void*>& list, T** p, size_t bytes) {
+    void* q = nullptr;
+    TH_CHECK_HIP(hipMalloc(&q, bytes));
+    list.push_back(q);
+    *p = static_cast<T*>(q);
+    return TREXHIP_OK;
+}
+static void dev_free(std::vector<void*>& list) {
+    for (void* q : list) (void)hipFree(q);
+    list.clear();
+}
+
 static void free_net(Net* n) {
     if (!n) return;
     drop_graphs(n);
-    float* d[] = {n->w1, n->b1, n->w2, n->b2, n->w3, n->b3, n->wf1, n->bf1, n->lng, n->lnb, n->wf2t, n->bf2,
-                  n->act1, n->act2, n->act3, n->fc1, n->probs, n->logits};
-    for (float* p : d) if (p) (void)hipFree(p);
-    if (n->w2s) (void)hipFree(n->w2s);
-    if (n->w3s) (void)hipFree(n->w3s);
-    if (n->w2h) (void)hipFree(n->w2h);
-    if (n->w3h) (void)hipFree(n->w3h);
-    if (n->w2w) (void)hipFree(n->w2w);
-    if (n->w3w) (void)hipFree(n->w3w);
-    if (n->w1h) (void)hipFree(n->w1h);
-    if (n->wf1h) (void)hipFree(n->wf1h);
-    if (n->d_ovf) (void)hipFree(n->d_ovf);
-    if (n->d_ovfc) (void)hipFree(n->d_ovfc);
-    if (n->v2) (void)hipFree(n->v2);
-    if (n->v3) (void)hipFree(n->v3);
-    if (n->crops) (void)hipFree(n->crops);
+    dev_free(n->weights);
+    dev_free(n->batch);
     if (n->h_probs) (void)hipHostFree(n->h_probs);
     delete n;
 }
 
-static int upload(float** dst, const std::vector<float>& v) {
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(float)));
-    TH_CHECK_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+template <class T>
+static int upload(Net* net, T** dst, const void* data, size_t bytes) {
+    const int rc = dev_alloc(net->weights, dst, bytes);
+    if (rc != TREXHIP_OK) return rc;
+    TH_CHECK_HIP(hipMemcpy(*dst, data, bytes, hipMemcpyHostToDevice));
     return TREXHIP_OK;
 }
+template <class T, class V>
+static int upload(Net* net, T** dst, const std::vector<V>& v) { return upload(net, dst, v.data(), v.size() * sizeof(V)); }
+template <class T>
+static int upload(Net* net, T** dst, float* inv, const ScaledImage& im) { *inv = im.inv; return upload(net, dst, im.v); }
 
-// conv weight [CO][CI][5][5] + BN(eval) -> packed [CI/CIC][25][CIC][CO] (scaled) + bias[CO]
-static void fold_conv(const float* w, const float* b, const float* g, const float* beta, const float* mean, const float* var,
-                      int CO, int CI, int CIC, std::vector<float>& wp, std::vector<float>& bias) {
-    wp.assign((size_t)CO * CI * 25, 0.f);
-    bias.assign(CO, 0.f);
-    for (int co = 0; co < CO; ++co) {
-        const double s = (double)g[co] / std::sqrt((double)var[co] + 1e-5);     // BatchNorm2d eps
-        bias[co] = (float)(((double)b[co] - (double)mean[co]) * s + (double)beta[co]);
-        for (int ci = 0; ci < CI; ++ci)
-            for (int tap = 0; tap < 25; ++tap) {
-                const int cc = ci / CIC, k = ci % CIC;
-                wp[(((size_t)cc * 25 + tap) * CIC + k) * CO + co] = (float)((double)w[((size_t)co * CI + ci) * 25 + tap] * s);
-            }
-    }
-}
-
-static uint16_t h_bf16_rne(float x) {
-    uint32_t u; std::memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static float h_bf16_to_f(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; std::memcpy(&f, &u, 4); return f; }
-
-// packed fp32 conv weights [cc][25][CIC][CO] (CIC = 16 here) -> three bf16 pieces laid out [cc][tap][piece][k/8][co][8]
-static int upload_split(uint4** dst, const std::vector<float>& wp, int CI, int CO, int CIC = 16) {
-    const int ncc = CI / CIC, KO = CIC / 8;
-    std::vector<uint16_t> o((size_t)ncc * 25 * 3 * KO * CO * 8);
-    for (int cc = 0; cc < ncc; ++cc)
-        for (int tap = 0; tap < 25; ++tap)
-            for (int k = 0; k < CIC; ++k)
-                for (int co = 0; co < CO; ++co) {
-                    const float x = wp[(((size_t)cc * 25 + tap) * CIC + k) * CO + co];
-                    const uint16_t p1 = h_bf16_rne(x);
-                    const float r1 = x - h_bf16_to_f(p1);
-                    const uint16_t p2 = h_bf16_rne(r1);
-                    const float r2 = r1 - h_bf16_to_f(p2);
-                    const uint16_t p3 = h_bf16_rne(r2);
-                    const uint16_t pc[3] = {p1, p2, p3};
-                    for (int s = 0; s < 3; ++s)
-                        o[(((((size_t)cc * 25 + tap) * 3 + s) * KO + k / 8) * CO + co) * 8 + (k & 7)] = pc[s];
-                }
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(dst), o.size() * 2));
-    TH_CHECK_HIP(hipMemcpy(*dst, o.data(), o.size() * 2, hipMemcpyHostToDevice));
-    return TREXHIP_OK;
-}
-
-// the same for the fp16 split: two pieces of w * 2^k, k chosen so that max|w| * 2^k is in [8192, 16384)
-static int upload_split_f16(uint4** dst, float* inv_scale, const std::vector<float>& wp, int CI, int CO, int CIC = 16) {
-    float mx = 0.f;
-    for (float v : wp) mx = std::fmax(mx, std::fabs(v));
-    int k = 0;
-    if (mx > 0.f) { k = (int)std::floor(std::log2(16384.0 / (double)mx)); if (k > 24) k = 24; if (k < -24) k = -24; }
-    const float sc = std::ldexp(1.0f, k);
-    *inv_scale = std::ldexp(1.0f, -k);
-    const int ncc = CI / CIC, KO = CIC / 8;
-    std::vector<uint16_t> o((size_t)ncc * 25 * 2 * KO * CO * 8);
-    for (int cc = 0; cc < ncc; ++cc)
-        for (int tap = 0; tap < 25; ++tap)
-            for (int kk = 0; kk < CIC; ++kk)
-                for (int co = 0; co < CO; ++co) {
-                    const float x = wp[(((size_t)cc * 25 + tap) * CIC + kk) * CO + co] * sc;
-                    const _Float16 h1 = (_Float16)x;
-                    const _Float16 h2 = (_Float16)(x - (float)h1);
-                    uint16_t pc[2];
-                    std::memcpy(&pc[0], &h1, 2); std::memcpy(&pc[1], &h2, 2);
-                    for (int s = 0; s < 2; ++s)
-                        o[(((((size_t)cc * 25 + tap) * 2 + s) * KO + kk / 8) * CO + co) * 8 + (kk & 7)] = pc[s];
-                }
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(dst), o.size() * 2));
-    TH_CHECK_HIP(hipMemcpy(*dst, o.data(), o.size() * 2, hipMemcpyHostToDevice));
-    return TREXHIP_OK;
-}
-
-// Winograd-domain weights of k_conv5_wino: Wt[ky][p] = sum_kx G[p][kx] w[ky][kx] (double), scaled by a power of two so that
-// max|Wt| is in [8192, 16384), two fp16 pieces, laid out [cc][ky][p][piece][k-octet][co] x 8 halves
-static int upload_wino_f16(uint4** dst, float* inv_scale, const std::vector<float>& wp /*[cc][25][16][CO]*/, int CI, int CO) {
-    static const double Gm[8][5] = {{-1, 0, 0, 0, 0},
-                                    {-2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9},
-                                    {-2.0 / 9, 2.0 / 9, -2.0 / 9, 2.0 / 9, -2.0 / 9},
-                                    {1.0 / 90, 1.0 / 45, 2.0 / 45, 4.0 / 45, 8.0 / 45},
-                                    {1.0 / 90, -1.0 / 45, 2.0 / 45, -4.0 / 45, 8.0 / 45},
-                                    {32.0 / 45, 16.0 / 45, 8.0 / 45, 4.0 / 45, 2.0 / 45},
-                                    {32.0 / 45, -16.0 / 45, 8.0 / 45, -4.0 / 45, 2.0 / 45},
-                                    {0, 0, 0, 0, 1}};
-    const int ncc = CI / 16;
-    std::vector<double> wt((size_t)ncc * 40 * 16 * CO);
-    double mx = 0.0;
-    for (int cc = 0; cc < ncc; ++cc)
-        for (int ky = 0; ky < 5; ++ky)
-            for (int p = 0; p < 8; ++p)
-                for (int kk = 0; kk < 16; ++kk)
-                    for (int co = 0; co < CO; ++co) {
-                        double a = 0.0;
-                        for (int kx = 0; kx < 5; ++kx) a += Gm[p][kx] * (double)wp[(((size_t)cc * 25 + ky * 5 + kx) * 16 + kk) * CO + co];
-                        wt[(((size_t)cc * 40 + ky * 8 + p) * 16 + kk) * CO + co] = a;
-                        mx = std::fmax(mx, std::fabs(a));
-                    }
-    int k = 0;
-    if (mx > 0.0) { k = (int)std::floor(std::log2(16384.0 / mx)); if (k > 24) k = 24; if (k < -24) k = -24; }
-    *inv_scale = std::ldexp(1.0f, -k);
-    std::vector<uint16_t> o((size_t)ncc * 40 * 2 * 2 * CO * 8);
-    for (int cc = 0; cc < ncc; ++cc)
-        for (int t = 0; t < 40; ++t)
-            for (int kk = 0; kk < 16; ++kk)
-                for (int co = 0; co < CO; ++co) {
-                    const float x = (float)std::ldexp(wt[(((size_t)cc * 40 + t) * 16 + kk) * CO + co], k);
-                    const _Float16 h1 = (_Float16)x;
-                    const _Float16 h2 = (_Float16)(x - (float)h1);
-                    uint16_t pc[2];
-                    std::memcpy(&pc[0], &h1, 2); std::memcpy(&pc[1], &h2, 2);
-                    for (int sidx = 0; sidx < 2; ++sidx)
-                        o[(((((size_t)cc * 40 + t) * 2 + sidx) * 2 + kk / 8) * CO + co) * 8 + (kk & 7)] = pc[sidx];
-                }
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(dst), o.size() * 2));
-    TH_CHECK_HIP(hipMemcpy(*dst, o.data(), o.size() * 2, hipMemcpyHostToDevice));
-    return TREXHIP_OK;
-}
-
+#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)      // a chain of allocations stops at its first failure
+// parse -> pack (cnn_weights.hip) -> upload
 int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
-    if (bytes < 32) { set_error("trexhip_load_weights: blob too small"); return TREXHIP_E_INVALID; }
-    int32_t hdr[8];
-    std::memcpy(hdr, blob, 32);
-    if (hdr[0] != 0x57585254 || hdr[1] != 1) { set_error("trexhip_load_weights: bad magic/version"); return TREXHIP_E_INVALID; }
-    const int classes = hdr[2], W = hdr[3], H = hdr[4], CH = hdr[5];
-    if (W < 8 || W > 256 || H < 8 || H > 256) {
-        set_error("trexhip_load_weights: individual_image_size " + std::to_string(W) + "x" + std::to_string(H) + " is outside 8..256 x 8..256");
-        return TREXHIP_E_UNSUPPORTED;
-    }
+    WeightBlob wb;
+    const int prc = parse_weight_blob(blob, bytes, "trexhip_load_weights", &wb, [](int W, int H) -> int {
+        if (W < 8 || W > 256 || H < 8 || H > 256) {
+            set_error("trexhip_load_weights: individual_image_size " + std::to_string(W) + "x" + std::to_string(H) + " is outside 8..256 x 8..256");
+            return TREXHIP_E_UNSUPPORTED;
+        }
+        return TREXHIP_OK;
+    });
+    if (prc != TREXHIP_OK) return prc;
+    const int classes = wb.classes, W = wb.W, H = wb.H, CH = wb.CH;
     const bool at80 = W == 80 && H == 80;      // the tuned chain of this file; every other size runs the generic one of cnn_any.hip
-    if (CH != 1 && CH != 3) { set_error("trexhip_load_weights: channels must be 1 or 3"); return TREXHIP_E_UNSUPPORTED; }
-    if (classes < 1 || classes > 1024) { set_error("trexhip_load_weights: classes must be 1..1024"); return TREXHIP_E_INVALID; }
-    const size_t flat = 128 * (W / 8) * (H / 8);
-    const size_t need = (size_t)16 * CH * 25 + 16 * 5 + (size_t)64 * 16 * 25 + 64 * 5 + (size_t)128 * 64 * 25 + 128 * 5 +
-                        100 * flat + 100 * 3 + (size_t)classes * 100 + classes;
-    if (bytes != 32 + need * 4) { set_error("trexhip_load_weights: blob size does not match its header"); return TREXHIP_E_INVALID; }
-    const float* p = reinterpret_cast<const float*>(static_cast<const char*>(blob) + 32);
-    auto take = [&](size_t count) { const float* q = p; p += count; return q; };
-    const float *c1w = take((size_t)16 * CH * 25), *c1b = take(16), *g1 = take(16), *be1 = take(16), *m1 = take(16), *v1 = take(16);
-    const float *c2w = take((size_t)64 * 16 * 25), *c2b = take(64), *g2 = take(64), *be2 = take(64), *m2 = take(64), *v2 = take(64);
-    const float *c3w = take((size_t)128 * 64 * 25), *c3b = take(128), *g3 = take(128), *be3 = take(128), *m3 = take(128), *v3 = take(128);
-    const float *f1w = take(100 * flat), *f1b = take(100), *lg = take(100), *lb = take(100);
-    const float *f2w = take((size_t)classes * 100), *f2b = take(classes);
 
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     free_net(static_cast<Net*>(ctx->net));
     ctx->net = nullptr;
     Net* net = new Net();
     net->classes = classes; net->W = W; net->H = H; net->CH = CH;
-    std::vector<float> wp, bias;
     int rc = TREXHIP_OK;
-#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
-    {   // conv1: [16][CH][25] -> [CH][25][16]
-        std::vector<float> w1((size_t)CH * 25 * 16), b1(16);
-        for (int co = 0; co < 16; ++co) {
-            const double s = (double)g1[co] / std::sqrt((double)v1[co] + 1e-5);
-            b1[co] = (float)(((double)c1b[co] - (double)m1[co]) * s + (double)be1[co]);
-            for (int c = 0; c < CH; ++c)
-                for (int tap = 0; tap < 25; ++tap)
-                    w1[((size_t)c * 25 + tap) * 16 + co] = (float)((double)c1w[((size_t)co * CH + c) * 25 + tap] * s);
-        }
-        TRY(upload(&net->w1, w1)); TRY(upload(&net->b1, b1));
-        if (at80 && CH == 3 && rc == TREXHIP_OK) {   // B fragments of k_conv1_mfma3: [shift s][mfma m][piece hi|lo][lane] x 8 halves
-            float mx = 0.f;
-            for (float v : w1) mx = std::fmax(mx, std::fabs(v));
-            int k = 0;
-            if (mx > 0.f) { k = (int)std::floor(std::log2(16384.0 / (double)mx)); if (k > 24) k = 24; if (k < -24) k = -24; }
-            const float sc = std::ldexp(1.0f, k);
-            net->inv1h = std::ldexp(1.0f, -k);
-            std::vector<uint16_t> tab((size_t)32 * 64 * 8, 0);
-            for (int s = 0; s < 4; ++s)
-                for (int m = 0; m < 4; ++m)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int co = lane & 15, q = lane >> 4;
-                        const int ch = m < 3 ? m : q, ky = m < 3 ? q : 4;
-                        for (int slot = 0; slot < 8; ++slot) {
-                            const int kx = slot - s;
-                            float x = 0.f;
-                            if (ch < 3 && kx >= 0 && kx < 5) x = w1[((size_t)ch * 25 + ky * 5 + kx) * 16 + co] * sc;
-                            const _Float16 h1 = (_Float16)x;
-                            const _Float16 h2 = (_Float16)(x - (float)h1);
-                            uint16_t pc[2];
-                            std::memcpy(&pc[0], &h1, 2); std::memcpy(&pc[1], &h2, 2);
-                            for (int piece = 0; piece < 2; ++piece)
-                                tab[((size_t)((s * 4 + m) * 2 + piece) * 64 + lane) * 8 + slot] = pc[piece];
-                        }
-                    }
-            if (hipMalloc(reinterpret_cast<void**>(&net->w1h), tab.size() * 2) != hipSuccess ||
-                hipMemcpy(net->w1h, tab.data(), tab.size() * 2, hipMemcpyHostToDevice) != hipSuccess) rc = TREXHIP_E_DEVICE;
-        }
-        if (at80 && CH == 1 && rc == TREXHIP_OK) {   // B fragments of k_conv1_mfma: [shift s][mfma 0: ky 0..3 | 1: ky 4][piece hi|lo][lane] x 8 halves
-            float mx = 0.f;
-            for (float v : w1) mx = std::fmax(mx, std::fabs(v));
-            int k = 0;
-            if (mx > 0.f) { k = (int)std::floor(std::log2(16384.0 / (double)mx)); if (k > 24) k = 24; if (k < -24) k = -24; }
-            const float sc = std::ldexp(1.0f, k);
-            net->inv1h = std::ldexp(1.0f, -k);
-            std::vector<uint16_t> tab((size_t)16 * 64 * 8, 0);
-            for (int s = 0; s < 4; ++s)
-                for (int mf = 0; mf < 2; ++mf)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int co = lane & 15, q = lane >> 4;
-                        const int ky = mf == 0 ? q : (q == 0 ? 4 : -1);
-                        for (int slot = 0; slot < 8; ++slot) {
-                            const int kx = slot - s;
-                            float x = 0.f;
-                            if (ky >= 0 && kx >= 0 && kx < 5) x = w1[(size_t)(ky * 5 + kx) * 16 + co] * sc;
-                            const _Float16 h1 = (_Float16)x;
-                            const _Float16 h2 = (_Float16)(x - (float)h1);
-                            uint16_t pc[2];
-                            std::memcpy(&pc[0], &h1, 2); std::memcpy(&pc[1], &h2, 2);
-                            for (int piece = 0; piece < 2; ++piece)
-                                tab[((size_t)((s * 2 + mf) * 2 + piece) * 64 + lane) * 8 + slot] = pc[piece];
-                        }
-                    }
-            if (hipMalloc(reinterpret_cast<void**>(&net->w1h), tab.size() * 2) != hipSuccess ||
-                hipMemcpy(net->w1h, tab.data(), tab.size() * 2, hipMemcpyHostToDevice) != hipSuccess) rc = TREXHIP_E_DEVICE;
-        }
-    }
-    fold_conv(c2w, c2b, g2, be2, m2, v2, 64, 16, 16, wp, bias);
-    TRY(upload(&net->w2, wp)); TRY(upload(&net->b2, bias));
-    TRY(upload_split(&net->w2s, wp, 16, 64));
-    TRY(upload_split_f16(&net->w2h, &net->inv2h, wp, 16, 64));
-    if (at80) TRY(upload_wino_f16(&net->w2w, &net->inv2w, wp, 16, 64));
-    fold_conv(c3w, c3b, g3, be3, m3, v3, 128, 64, 16, wp, bias);       // 16-channel chunks for the bf16 path
-    TRY(upload_split(&net->w3s, wp, 64, 128));
-    TRY(upload_split_f16(&net->w3h, &net->inv3h, wp, 64, 128));
-    if (at80) TRY(upload_wino_f16(&net->w3w, &net->inv3w, wp, 64, 128));
-    if (rc == TREXHIP_OK && hipMalloc(reinterpret_cast<void**>(&net->d_ovf), 16 + (2 + FB_MAX) * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
+    const Folded c1 = fold_conv1(&wb.t[T_C1W], CH);
+    TRY(upload(net, &net->w1, c1.w)); TRY(upload(net, &net->b1, c1.b));
+    if (at80) TRY(upload(net, &net->w1h, &net->inv1h, pack_conv1_frags(c1.w, CH)));
+    const Folded c2 = fold_conv(&wb.t[T_C2W], 64, 16, 16);
+    TRY(upload(net, &net->w2, c2.w)); TRY(upload(net, &net->b2, c2.b));
+    TRY(upload(net, &net->w2s, pack_bf16x3(c2.w, 16, 64)));
+    TRY(upload(net, &net->w2h, &net->inv2h, pack_f16x2(c2.w, 16, 64)));
+    if (at80) TRY(upload(net, &net->w2w, &net->inv2w, pack_wino_f16(c2.w, 16, 64)));
+    const Folded c3 = fold_conv(&wb.t[T_C3W], 128, 64, 16);           // 16-channel chunks for the matrix-core paths, 32 for exact fp32
+    TRY(upload(net, &net->w3s, pack_bf16x3(c3.w, 64, 128)));
+    TRY(upload(net, &net->w3h, &net->inv3h, pack_f16x2(c3.w, 64, 128)));
+    if (at80) TRY(upload(net, &net->w3w, &net->inv3w, pack_wino_f16(c3.w, 64, 128)));
+    TRY(dev_alloc(net->weights, &net->d_ovf, 16 + (2 + FB_MAX) * 4));
     if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, 16 + (2 + FB_MAX) * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
-    fold_conv(c3w, c3b, g3, be3, m3, v3, 128, 64, 32, wp, bias);
-    TRY(upload(&net->w3, wp)); TRY(upload(&net->b3, bias));
-    {   // fc1 [100][c*P + h*(W/8) + w] (the reference's NCHW flatten, P = (H/8)(W/8)) -> [(h*(W/8) + w)*128 + c][128 (o padded)], act3's NHWC order
-        const int P = (W / 8) * (H / 8);
-        std::vector<float> wf((size_t)flat * 128, 0.f), bf(128, 0.f);
-        for (int o = 0; o < 100; ++o) {
-            bf[o] = f1b[o];
-            for (int c = 0; c < 128; ++c)
-                for (int hw = 0; hw < P; ++hw)
-                    wf[((size_t)hw * 128 + c) * 128 + o] = f1w[(size_t)o * flat + (size_t)c * P + hw];
-        }
-        TRY(upload(&net->wf1, wf)); TRY(upload(&net->bf1, bf));
-        if (at80 && rc == TREXHIP_OK) {      // the same matrix as two fp16 pieces per weight, MFMA B-operand order (the generic chain's fc1 is exact fp32)
-            float mx = 0.f;
-            for (float v : wf) mx = std::fmax(mx, std::fabs(v));
-            int k = 0;
-            if (mx > 0.f) { k = (int)std::floor(std::log2(16384.0 / (double)mx)); if (k > 24) k = 24; if (k < -24) k = -24; }
-            const float sc = std::ldexp(1.0f, k);
-            net->invf1h = std::ldexp(1.0f, -k);
-            std::vector<uint16_t> o((size_t)flat * 128 * 2);
-            for (size_t kk = 0; kk < flat; ++kk)
-                for (int co = 0; co < 128; ++co) {
-                    const float x = wf[kk * 128 + co] * sc;
-                    const _Float16 h1 = (_Float16)x;
-                    const _Float16 h2 = (_Float16)(x - (float)h1);
-                    uint16_t pc[2];
-                    std::memcpy(&pc[0], &h1, 2); std::memcpy(&pc[1], &h2, 2);
-                    for (int s = 0; s < 2; ++s) o[(((kk / 8) * 2 + s) * 128 + co) * 8 + (kk & 7)] = pc[s];
-                }
-            if (hipMalloc(reinterpret_cast<void**>(&net->wf1h), o.size() * 2) != hipSuccess ||
-                hipMemcpy(net->wf1h, o.data(), o.size() * 2, hipMemcpyHostToDevice) != hipSuccess) rc = TREXHIP_E_DEVICE;
-        }
-    }
-    TRY(upload(&net->lng, std::vector<float>(lg, lg + 100)));
-    TRY(upload(&net->lnb, std::vector<float>(lb, lb + 100)));
-    {
-        std::vector<float> w2t((size_t)100 * classes);
-        for (int c = 0; c < classes; ++c)
-            for (int k = 0; k < 100; ++k) w2t[(size_t)k * classes + c] = f2w[(size_t)c * 100 + k];
-        TRY(upload(&net->wf2t, w2t));
-        TRY(upload(&net->bf2, std::vector<float>(f2b, f2b + classes)));
-    }
-#undef TRY
+    const Folded c3x = fold_conv(&wb.t[T_C3W], 128, 64, 32);
+    TRY(upload(net, &net->w3, c3x.w)); TRY(upload(net, &net->b3, c3x.b));
+    const Folded f1 = pack_fc1(wb.t[T_F1W], wb.t[T_F1B], W, H);
+    TRY(upload(net, &net->wf1, f1.w)); TRY(upload(net, &net->bf1, f1.b));
+    if (at80) TRY(upload(net, &net->wf1h, &net->invf1h, pack_fc1_f16(f1.w)));          // (the generic chain's fc1 is exact fp32)
+    TRY(upload(net, &net->lng, wb.t[T_LNG], 100 * sizeof(float)));
+    TRY(upload(net, &net->lnb, wb.t[T_LNB], 100 * sizeof(float)));
+    TRY(upload(net, &net->wf2t, pack_fc2(wb.t[T_F2W], classes)));
+    TRY(upload(net, &net->bf2, wb.t[T_F2B], classes * sizeof(float)));
     if (rc != TREXHIP_OK) { free_net(net); return rc; }
     ctx->net = net;
     return TREXHIP_OK;
@@ -1753,33 +1494,31 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
 static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     if (n <= net->max_crops) return TREXHIP_OK;
     drop_graphs(net);                                      // the captured chains point into the buffers that are replaced here
-    float** bufs[] = {&net->act1, &net->act2, &net->act3, &net->fc1, &net->probs, &net->logits};
-    for (float** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
-    if (net->v2) { (void)hipFree(net->v2); net->v2 = nullptr; }
-    if (net->v3) { (void)hipFree(net->v3); net->v3 = nullptr; }
-    if (net->crops) { (void)hipFree(net->crops); net->crops = nullptr; }
+    dev_free(net->batch);
     if (net->h_probs) { (void)hipHostFree(net->h_probs); net->h_probs = nullptr; }
-    if (net->d_ovfc) { (void)hipFree(net->d_ovfc); net->d_ovfc = nullptr; }
+    net->max_crops = 0;
+    std::vector<void*>& B = net->batch;
     const size_t N = n;
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->d_ovfc), N));
-    TH_CHECK_HIP(hipMemsetAsync(net->d_ovfc, 0, N, ctx->stream));      // on the stream its users run on (ADVICE r5); the plan kernel clears what it reads
     const size_t W = net->W, H = net->H;       // (80 x 80: 40 x 40 x 16, 20 x 20 x 64, 10 x 10 x 128)
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act1), N * (H / 2) * (W / 2) * 16 * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act2), N * (H / 4) * (W / 4) * 64 * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->act3), N * (H / 8) * (W / 8) * 128 * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->fc1), N * 128 * 4 * FC1_KSPLIT));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->probs), N * net->classes * 4));
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->logits), N * net->classes * 4));
+    int rc = dev_alloc(B, &net->d_ovfc, N);
+    TRY(dev_alloc(B, &net->act1, N * (H / 2) * (W / 2) * 16 * 4));
+    TRY(dev_alloc(B, &net->act2, N * (H / 4) * (W / 4) * 64 * 4));
+    TRY(dev_alloc(B, &net->act3, N * (H / 8) * (W / 8) * 128 * 4));
+    TRY(dev_alloc(B, &net->fc1, N * 128 * 4 * FC1_KSPLIT));
+    TRY(dev_alloc(B, &net->probs, N * net->classes * 4));
+    TRY(dev_alloc(B, &net->logits, N * net->classes * 4));
     if (W == 80 && H == 80) {                  // the Winograd-domain operand images of the 80 x 80 chain
-        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->v2), N * 40 * V2_ROWB));
-        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->v3), N * 20 * V3_ROWB));
+        TRY(dev_alloc(B, &net->v2, N * 40 * V2_ROWB));
+        TRY(dev_alloc(B, &net->v3, N * 20 * V3_ROWB));
     }
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->crops), N * net->W * net->H * net->CH));
+    TRY(dev_alloc(B, &net->crops, N * net->W * net->H * net->CH));
+    if (rc != TREXHIP_OK) return rc;
+    TH_CHECK_HIP(hipMemsetAsync(net->d_ovfc, 0, N, ctx->stream));      // on the stream its users run on (ADVICE r5); the plan kernel clears what it reads
     TH_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&net->h_probs), N * net->classes * 4, hipHostMallocDefault));
     net->max_crops = n;
-    (void)ctx;
     return TREXHIP_OK;
 }
+#undef TRY
 
 // every individual_image_size but 80 x 80: conv1..conv3 of cnn_any.hip in the precision mode (conv1 exact fp32 in all of them), fc1 exact fp32
 // (k_fc1, K = 128 (H/8) (W/8) at run time), k_head.  In FP16X3 mode the range guard of the 80 x 80 chain: k_guard_plan lists the crops the fp16

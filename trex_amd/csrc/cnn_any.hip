@@ -14,41 +14,11 @@
 //   The fp16 kernels flag the crop of an activation outside the fp16 range (crop_flags + overflow bit 0); k_guard_plan (cnn.hip)
 //   lists those crops and the bf16x6 instances, launched with that plan as their guard, re-run only them.
 #include "internal.h"
-#include "conv_f32.h"
+#include "cnn_split.h"
 #include <algorithm>
 
 namespace trexhip {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// the operand splits of cnn.hip (bf16_rne / split3 / split2h), bit for bit
-__device__ __forceinline__ uint32_t bf16_rne(float x) {
-    uint32_t u = __float_as_uint(x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ void split3(float x, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-    p1 = bf16_rne(x);
-    const float r1 = x - __uint_as_float(p1 << 16);
-    p2 = bf16_rne(r1);
-    const float r2 = r1 - __uint_as_float(p2 << 16);
-    p3 = bf16_rne(r2);
-}
-__device__ __forceinline__ void split2h(float x, uint32_t& p1, uint32_t& p2, bool& ovf) {
-    const _Float16 h1 = (_Float16)x;
-    ovf |= !(fabsf(x) < 65520.0f);
-    const float r1 = x - (float)h1;
-    const _Float16 h2 = (_Float16)r1;
-    p1 = __builtin_bit_cast(uint16_t, h1);
-    p2 = __builtin_bit_cast(uint16_t, h2);
-}
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-// the re-run plan of k_guard_plan: plan[1] == 1 -> item i is crop plan[2 + i]
-__device__ __forceinline__ int plan_crop(const uint32_t* __restrict__ plan, const int i) { return (plan && plan[1] == 1u) ? (int)plan[2 + i] : i; }
 
 // ------------------------------------------------------------------------------------------------
 // conv1: CH -> 16, 5x5 'same' + folded BN + ReLU + floor 2x2 max-pool, exact fp32

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             // the pooling -- the vector part of the stage then runs beside the consumers' taps instead of between two bursts of matrix work
             constexpr int NT1 = 4;
             for (int t0 = rw; t0 < n_tiles; t0 += 4 * NT1) {
-                f16x8_c1 a1[NT1], a2[NT1];
+                f16x8 a1[NT1], a2[NT1];
 #pragma unroll
                 for (int u = 0; u < NT1; ++u) {
                     const int tile = t0 + 4 * u < n_tiles ? t0 + 4 * u : t0;
@@ -217,8 +217,8 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                     const _Float16* p2a = img + (row + 4) * F::IMG_PITCH + x4;
                     const uint2 l1 = *reinterpret_cast<const uint2*>(p1a), h1 = *reinterpret_cast<const uint2*>(p1a + 4);
                     const uint2 l2 = *reinterpret_cast<const uint2*>(p2a), h2 = *reinterpret_cast<const uint2*>(p2a + 4);
-                    a1[u] = __builtin_bit_cast(f16x8_c1, make_uint4(l1.x, l1.y, h1.x, h1.y));
-                    a2[u] = __builtin_bit_cast(f16x8_c1, make_uint4(l2.x, l2.y, h2.x, h2.y));
+                    a1[u] = __builtin_bit_cast(f16x8, make_uint4(l1.x, l1.y, h1.x, h1.y));
+                    a2[u] = __builtin_bit_cast(f16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
                 }
                 f32x4 acc[NT1][4];
 #pragma unroll
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                     for (int u = 0; u < NT1; ++u)
 #pragma unroll
                         for (int s = 0; s < 4; ++s)
-                            acc[u][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16((m & 1) ? a2[u] : a1[u], __builtin_bit_cast(f16x8_c1, bf[s * 4 + (m == 0 ? 1 : m == 1 ? 3 : m == 2 ? 0 : 2)]), acc[u][s], 0, 0, 0);
+                            acc[u][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16((m & 1) ? a2[u] : a1[u], __builtin_bit_cast(f16x8, bf[s * 4 + (m == 0 ? 1 : m == 1 ? 3 : m == 2 ? 0 : 2)]), acc[u][s], 0, 0, 0);
                 // lane (co = r, q4): accumulator rows 4 q4 .. 4 q4 + 3 = windows 2 q4, 2 q4 + 1 x the two image rows: pooled pixels 2 (window) and
                 // 2 (window) + 1 of the V2 row, channel co.  pbufP [slot of the pooled pixel][16 channels]; slot = the pixel index with its two low
                 // bit pairs swapped (the four q4 groups of a store fill 256 contiguous bytes, P2's lanes read contiguously as well)

@@ -1,0 +1,62 @@
+// cnn_weights.h -- the identity network's weight blob and the operand images the kernels read: host code only, no device call.
+// cnn.hip (trexhip_load_weights) and train.hip (the trainer's import / export) parse the blob here; cnn.hip uploads what the
+// packers return.  Every packer is a pure function of host floats, so its bytes are pinned by a CPU test (tests/test_cnn_weights.py).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string>
+#include <vector>
+
+namespace trexhip {
+
+void set_error(const std::string& msg);        // capi.hip
+
+// The blob (trex_amd/weights.py): 8 x int32 header {magic 'TRXW', version 1, classes, W, H, CH, 0, 0}, then these float32 tensors
+// in PyTorch's state_dict order and shapes.  The six tensors of a convolution layer are consecutive: weight, bias, BN gamma, beta,
+// running mean, running variance
+enum { T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3,
+       T_F1W, T_F1B, T_LNG, T_LNB, T_F2W, T_F2B, T_COUNT };
+
+size_t weight_tensor_count(int t, int classes, int CH, int W, int H);    // elements of tensor t
+size_t weight_blob_bytes(int classes, int CH, int W, int H);             // header + all tensors
+void write_weight_blob_header(void* blob, int classes, int W, int H, int CH);
+
+struct WeightBlob { int classes, W, H, CH; const float* t[T_COUNT]; };   // the tensors point into the caller's blob
+// Checks the header and the size; `who` prefixes the error texts.  `size_check`, when given, judges the individual_image_size between
+// the magic and the channel check (each caller supports its own range) and returns TREXHIP_OK or the code it has set an error for.
+int parse_weight_blob(const void* blob, size_t bytes, const char* who, WeightBlob* view, int (*size_check)(int W, int H) = nullptr);
+
+// The fp16 operand images: w * 2^k in two pieces h1 = fp16(x), h2 = fp16(x - h1), k = floor(log2(16384 / max|w|)) clamped to +-24,
+// so that max|w| * 2^k is in [8192, 16384).  The kernel multiplies its result by 2^-k
+float pow2_scale(double max_abs, float* inv);                            // returns 2^k, *inv = 2^-k
+void split_f16x2(float x, uint16_t out[2]);
+
+struct Folded { std::vector<float> w, b; };                              // weights in a kernel's layout + their bias
+struct ScaledImage { std::vector<uint16_t> v; float inv = 1.f; };        // fp16 pieces of w * 2^k, and 2^-k
+
+// conv weight [CO][CI][5][5] + BN(eval) of `layer` (its six tensors) -> packed [CI/CIC][25][CIC][CO] (scaled) + bias[CO]
+Folded fold_conv(const float* const* layer, int CO, int CI, int CIC);
+// conv1: [16][CH][25] -> [CH][25][16] + bias[16] (chunks of one channel)
+inline Folded fold_conv1(const float* const* layer, int CH) { return fold_conv(layer, 16, CH, 1); }
+// packed fp32 conv weights [cc][25][CIC][CO] -> three bf16 pieces (x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2), round to
+// nearest even) laid out [cc][tap][piece][k/8][co][8]
+std::vector<uint16_t> pack_bf16x3(const std::vector<float>& wp, int CI, int CO, int CIC = 16);
+// the same for the fp16 split: two pieces, [cc][tap][piece][k/8][co][8]
+ScaledImage pack_f16x2(const std::vector<float>& wp, int CI, int CO, int CIC = 16);
+// Winograd-domain weights of k_conv5_wino: Wt[ky][p] = sum_kx G[p][kx] w[ky][kx] (double), scaled by a power of two so that
+// max|Wt| is in [8192, 16384), two fp16 pieces, laid out [cc][ky][p][piece][k-octet][co] x 8 halves
+ScaledImage pack_wino_f16(const std::vector<float>& wp /*[cc][25][16][CO]*/, int CI, int CO);
+// B fragments of the matrix-core conv1 (k_conv1_mfma: CH 1, k_conv1_mfma3: CH 3) from the folded [CH][25][16]:
+// [shift s 0..3][mfma m 0..CH][piece hi|lo][lane] x 8 halves.  Lane = (q = lane / 16, co = lane % 16); slot j of its 8 halves is tap
+// kx = j - s of one kernel row (zero outside 0..4).  MFMA m < CH holds channel m, rows ky = q; the last one holds row ky = 4 of channel q
+// (zero for q >= CH)
+ScaledImage pack_conv1_frags(const std::vector<float>& w1, int CH);
+// fc1 [100][c*P + h*(W/8) + w] (the reference's NCHW flatten, P = (H/8)(W/8)) -> [(h*(W/8) + w)*128 + c][128 (o padded)], act3's NHWC
+// order; bias padded to 128
+Folded pack_fc1(const float* w, const float* b, int W, int H);
+// the same matrix [K][128] as two fp16 pieces per weight, MFMA B-operand order [K/8][piece][128] x 8 halves
+ScaledImage pack_fc1_f16(const std::vector<float>& wf);
+// fc2 [classes][100] -> [100][classes]
+std::vector<float> pack_fc2(const float* w, int classes);
+
+}  // namespace trexhip

@@ -128,31 +128,31 @@ __global__ __launch_bounds__(256) void k_conv1_wpre(const uint8_t* __restrict__ 
                 uint4 a1u, a2u;
                 { const uint2 l2 = *reinterpret_cast<const uint2*>(p1), h2 = *reinterpret_cast<const uint2*>(p1 + 4); a1u = make_uint4(l2.x, l2.y, h2.x, h2.y); }
                 { const uint2 l2 = *reinterpret_cast<const uint2*>(p2), h2 = *reinterpret_cast<const uint2*>(p2 + 4); a2u = make_uint4(l2.x, l2.y, h2.x, h2.y); }
-                const f16x8_c1 a1 = __builtin_bit_cast(f16x8_c1, a1u), a2 = __builtin_bit_cast(f16x8_c1, a2u);
+                const f16x8 a1 = __builtin_bit_cast(f16x8, a1u), a2 = __builtin_bit_cast(f16x8, a2u);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     f32x4 c = {0.f, 0.f, 0.f, 0.f};
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 1]), c, 0, 0, 0);   // low pieces first
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 3]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 0]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8_c1, bf[s * 4 + 2]), c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8, bf[s * 4 + 1]), c, 0, 0, 0);   // low pieces first
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8, bf[s * 4 + 3]), c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, __builtin_bit_cast(f16x8, bf[s * 4 + 0]), c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, __builtin_bit_cast(f16x8, bf[s * 4 + 2]), c, 0, 0, 0);
                     acc[s] = c;
                 }
             } else {
-                f16x8_c1 a[4];
+                f16x8 a[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     const _Float16* pp = m < 3 ? img + m * PLANE + (row + q) * PITCH + x4 : img + (q < 3 ? q : 0) * PLANE + (row + 4) * PITCH + x4;
                     const uint2 l2 = *reinterpret_cast<const uint2*>(pp), h2 = *reinterpret_cast<const uint2*>(pp + 4);
-                    a[m] = __builtin_bit_cast(f16x8_c1, make_uint4(l2.x, l2.y, h2.x, h2.y));
+                    a[m] = __builtin_bit_cast(f16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
                 }
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     f32x4 c = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8_c1, bf[(s * 4 + m) * 2 + 1]), c, 0, 0, 0);
+                    for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8, bf[(s * 4 + m) * 2 + 1]), c, 0, 0, 0);
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8_c1, bf[(s * 4 + m) * 2 + 0]), c, 0, 0, 0);
+                    for (int m = 0; m < 4; ++m) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], __builtin_bit_cast(f16x8, bf[(s * 4 + m) * 2 + 0]), c, 0, 0, 0);
                     acc[s] = c;
                 }
             }

@@ -20,6 +20,7 @@
 // Every reduction has a fixed order: two runs of a step give identical bits.
 #include "internal.h"
 #include "conv_f32.h"
+#include "cnn_weights.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -28,9 +29,6 @@
 #include <vector>
 
 namespace trexhip {
-
-enum { T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3,
-       T_F1W, T_F1B, T_LNG, T_LNB, T_F2W, T_F2B, T_COUNT };
 
 static constexpr float EPS_BN = 1e-5f, EPS_LN = 1e-5f;
 
@@ -1359,22 +1357,6 @@ using WH2 = WgradHGeom<16, 64, 40, 16, 10>;
 static constexpr int SHARES3H = 64, SHARES2H = 256;
 static constexpr int SHARES3 = 12, SHARES2 = 51;     // 20 x 12 = 240 and 5 x 51 = 255 workgroups: one round on 256 CUs
 
-static size_t tensor_count(int t, int classes, int CH) {
-    switch (t) {
-        case T_C1W: return (size_t)16 * CH * 25;
-        case T_C1B: case T_G1: case T_BE1: case T_RM1: case T_RV1: return 16;
-        case T_C2W: return (size_t)64 * 16 * 25;
-        case T_C2B: case T_G2: case T_BE2: case T_RM2: case T_RV2: return 64;
-        case T_C3W: return (size_t)128 * 64 * 25;
-        case T_C3B: case T_G3: case T_BE3: case T_RM3: case T_RV3: return 128;
-        case T_F1W: return (size_t)100 * 12800;
-        case T_F1B: case T_LNG: case T_LNB: return 100;
-        case T_F2W: return (size_t)classes * 100;
-        case T_F2B: return classes;
-    }
-    return 0;
-}
-
 // index inside the tensor in the kernels' layout of element `i` of the torch layout
 static size_t to_internal(int t, size_t i, int CH) {
     switch (t) {
@@ -1662,23 +1644,19 @@ extern "C" {
 using namespace trexhip;
 
 size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) {
-    size_t n = 0;
-    for (int k = 0; k < T_COUNT; ++k) n += tensor_count(k, classes, channels);
-    return 32 + 4 * n;
+    return weight_blob_bytes(classes, channels, 80, 80);
 }
 
 int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, trexhip_trainer** out) {
     if (!ctx || !blob || !p || !out) { set_error("trexhip_trainer_create: null argument"); return TREXHIP_E_INVALID; }
     *out = nullptr;
-    if (bytes < 32) { set_error("trexhip_trainer_create: blob too small"); return TREXHIP_E_INVALID; }
-    int32_t hdr[8];
-    std::memcpy(hdr, blob, 32);
-    if (hdr[0] != 0x57585254 || hdr[1] != 1) { set_error("trexhip_trainer_create: bad magic/version"); return TREXHIP_E_INVALID; }
-    const int classes = hdr[2], CH = hdr[5];
-    if (hdr[3] != 80 || hdr[4] != 80) { set_error("trexhip_trainer_create: only individual_image_size 80x80 is supported"); return TREXHIP_E_UNSUPPORTED; }
-    if (CH != 1 && CH != 3) { set_error("trexhip_trainer_create: channels must be 1 or 3"); return TREXHIP_E_UNSUPPORTED; }
-    if (classes < 1 || classes > 1024) { set_error("trexhip_trainer_create: classes must be 1..1024"); return TREXHIP_E_INVALID; }
-    if (bytes != trexhip_weight_blob_bytes(classes, CH)) { set_error("trexhip_trainer_create: blob size does not match its header"); return TREXHIP_E_INVALID; }
+    WeightBlob wb;
+    const int prc = parse_weight_blob(blob, bytes, "trexhip_trainer_create", &wb, [](int W, int H) -> int {
+        if (W != 80 || H != 80) { set_error("trexhip_trainer_create: only individual_image_size 80x80 is supported"); return TREXHIP_E_UNSUPPORTED; }
+        return TREXHIP_OK;
+    });
+    if (prc != TREXHIP_OK) return prc;
+    const int classes = wb.classes, CH = wb.CH;
     if (p->max_batch < 1 || p->max_batch > 4096) { set_error("trexhip_trainer_create: max_batch must be 1..4096"); return TREXHIP_E_INVALID; }
     if (p->precision != 0 && p->precision != 1) { set_error("trexhip_trainer_create: precision must be 0 (fp16 two-piece split convolutions) or 1 (exact fp32 MFMA)"); return TREXHIP_E_INVALID; }
     if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f) || !(p->eps > 0.f) ||
@@ -1691,7 +1669,7 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     t->ctx = ctx; t->classes = classes; t->CH = CH; t->max_n = p->max_batch; t->p = *p;
     size_t at = 0;
     for (int k = 0; k < T_COUNT; ++k) {
-        t->off[k] = at; t->cnt[k] = tensor_count(k, classes, CH);
+        t->off[k] = at; t->cnt[k] = weight_tensor_count(k, classes, CH, 80, 80);
         at += (t->cnt[k] + 63) / 64 * 64;
     }
     t->off[T_COUNT] = at; t->total = at;
@@ -1722,11 +1700,8 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
         if (rc == TREXHIP_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("trexhip_trainer_create: no event"); rc = TREXHIP_E_DEVICE; }
     if (rc != TREXHIP_OK) { trainer_free(t); return rc; }
     std::vector<float> host(at, 0.f);
-    const float* src = reinterpret_cast<const float*>(static_cast<const char*>(blob) + 32);
-    for (int k = 0; k < T_COUNT; ++k) {
-        for (size_t i = 0; i < t->cnt[k]; ++i) host[t->off[k] + to_internal(k, i, CH)] = src[i];
-        src += t->cnt[k];
-    }
+    for (int k = 0; k < T_COUNT; ++k)
+        for (size_t i = 0; i < t->cnt[k]; ++i) host[t->off[k] + to_internal(k, i, CH)] = wb.t[k][i];
     bool ok = hipMemcpy(t->P, host.data(), at * 4, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemset(t->bad_target, 0, 8) == hipSuccess;
     ok = ok && hipMemset(t->G, 0, at * 4) == hipSuccess && hipMemset(t->M, 0, at * 4) == hipSuccess && hipMemset(t->V, 0, at * 4) == hipSuccess;
@@ -1813,8 +1788,7 @@ int trexhip_trainer_export(trexhip_trainer* h, void* blob, size_t capacity, size
     const size_t need = trexhip_weight_blob_bytes(t->classes, t->CH);
     if (bytes) *bytes = need;
     if (capacity < need) { set_error("trexhip_trainer_export: buffer too small (trexhip_weight_blob_bytes)"); return TREXHIP_E_CAPACITY; }
-    const int32_t hdr[8] = {0x57585254, 1, t->classes, 80, 80, t->CH, 0, 0};
-    std::memcpy(blob, hdr, 32);
+    write_weight_blob_header(blob, t->classes, 80, 80, t->CH);
     float* dst = reinterpret_cast<float*>(static_cast<char*>(blob) + 32);
     for (int k = 0; k < T_COUNT; ++k) {
         const int rc = trexhip_trainer_read(h, k, 0, dst, t->cnt[k]);
