@@ -373,7 +373,13 @@ int trexhip_midline_movement_device(trexhip_ctx* ctx, const trexhip_midline_para
  * batch ([n][out_h][out_w][3] for the rgb8 pixel encoding, colour codes warped with nearest neighbour for r3g3b2; the difference modes of rgb8 are per-channel
  * differences against the colour background of trexhip_set_background_color, r3g3b2 crops hold raw codes only).  normalization: individual_image_normalization none or
  * moments (posture / legacy: next function).  difference: 0 = grey
- * values, 1 = |bg - p|, 2 = max(bg - p, 0)  (track_background_subtraction, FilterCache.cpp:171-175). */
+ * values, 1 = |bg - p|, 2 = max(bg - p, 0)  (track_background_subtraction, FilterCache.cpp:171-175).
+ * Sizes: any out_w, out_h > 0, square or not.  trexhip_crops_device (none AND moments) needs out_w * out_h * channels to be a multiple of
+ * 16 bytes (the un-normalised gather clears its crop with 16-byte stores; the crop buffer 16-byte aligned): TREXHIP_E_INVALID otherwise
+ * (TREXHIP_E_UNSUPPORTED for rgb8).  trexhip_crops_transformed_device and trexhip_crops_posture_device write single bytes and take any size,
+ * e.g. 50 x 50.  Output rows / columns beyond 256 compute their fixed-point terms per pixel instead of from a table: same result.
+ * Blobs: no limit on size.  The warp keeps a blob's lines in LDS up to 2048 lines and 1024 rows and paints bounding boxes of up to
+ * 16384 bytes (pixels x channels) into LDS; larger blobs read their lines from global memory (a bisection per tap: slow, bit-identical). */
 enum { TREXHIP_NORMALIZE_NONE = 0, TREXHIP_NORMALIZE_MOMENTS = 1, TREXHIP_NORMALIZE_POSTURE = 2 };
 int trexhip_crops_device(trexhip_ctx* ctx, uint8_t* d_crops, int32_t n_blobs, int32_t out_w, int32_t out_h,
                          int32_t normalization, int32_t difference);
@@ -399,8 +405,8 @@ int trexhip_crops_posture_device(trexhip_ctx* ctx, uint8_t* d_crops, int32_t n_b
  * from a TRex <base>_dict.pth).  BatchNorm is folded and the tensors repacked on load.  The blob's header carries the network's
  * individual_image_size W x H: any 8 <= W, H <= 256 (square or not; TREXHIP_E_UNSUPPORTED outside), crops are then [n][H][W][C].
  * 80 x 80 runs the tuned chain, every other size a generic one (conv1 exact fp32, conv2 / conv3 in the precision mode below, fc1 exact
- * fp32).  The crop kernels (trexhip_crops*_device) need W * H * C to be a multiple of 16 bytes; other sizes (e.g. 50 x 50 gray) take
- * crops made on the host through trexhip_identify.  Loading another size on the same context replaces the network. */
+ * fp32).  trexhip_crops_device needs W * H * C to be a multiple of 16 bytes (the posture / transformed crop calls do not, see "crops");
+ * other sizes (e.g. 50 x 50 gray, un-normalised) take crops made on the host through trexhip_identify.  Loading another size on the same context replaces the network. */
 int trexhip_load_weights(trexhip_ctx* ctx, const void* blob, size_t bytes);
 int trexhip_num_classes(trexhip_ctx* ctx);
 int trexhip_network_channels(trexhip_ctx* ctx);   /* channels of the crops the loaded network expects (1 or 3); 0 without weights */

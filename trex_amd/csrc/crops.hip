@@ -1,4 +1,4 @@
-// crops.hip -- blob -> 80x80 identity-network input ("individual_image_size"), gathered on the device.
+// crops.hip -- blob -> identity-network input ("individual_image_size", 80x80 by default), gathered on the device.
 //
 // Replaces constraints::diff_image with individual_image_normalization = none
 //   Application/src/tracker/tracking/FilterCache.cpp:265-294 -> calculate_diff_image :157-235
@@ -527,6 +527,7 @@ extern "C" int trexhip_get_background(trexhip_ctx* ctx, uint8_t* gray, int32_t s
 namespace trexhip {
 
 static constexpr int W_NR = 2048;      // lines of one blob held in LDS
+static constexpr int W_ROWS = 1024;    // rows of one blob whose first line is tabulated in LDS
 static constexpr int W_OUT = 256;      // output rows / columns with tabulated fixed-point terms
 static constexpr int W_IMG = 16384;    // bounding boxes up to this many pixels are painted into LDS
 
@@ -538,7 +539,7 @@ __global__ __launch_bounds__(256) void k_crops_warp(const SegCfg c, const uint8_
                                                     int och /*1 grey or r3g3b2 code, 3 rgb8 (channels warped independently)*/, int enc,
                                                     const uint8_t* __restrict__ bgc, int bgc_ch) {
     __shared__ uint32_t s_runs[W_NR];
-    __shared__ int s_row[1024 + 2];
+    __shared__ int s_row[W_ROWS + 2];
     const uint32_t bi = blockIdx.x;
     uint8_t* out = crops + (size_t)bi * OW * OH * och;
     const uint32_t f = blob_frame[bi];
@@ -546,17 +547,37 @@ __global__ __launch_bounds__(256) void k_crops_warp(const SegCfg c, const uint8_
     trexhip_frame_info fi = {};
     if (ok) { fi = info[f]; ok = fi.flags == 0; }
     trexhip_blob B = {};
-    if (ok) { B = blobs[bi]; ok = B.n_runs <= (uint32_t)W_NR && (B.y1 - B.y0 + 1) <= 1024; }
+    if (ok) B = blobs[bi];
     if (!ok) { for (int i = threadIdx.x; i < OW * OH * och; i += 256) out[i] = 0; return; }
     const trexhip_run* rr = runs + fi.run_begin + B.run_begin;
     const int y0 = B.y0, rows = B.y1 - B.y0 + 1;
-    for (int i = threadIdx.x; i < (int)B.n_runs; i += 256) {
-        const trexhip_run q = rr[i];
-        s_runs[i] = (uint32_t)q.x0 | ((uint32_t)q.x1 << 16);
-        if (i == 0 || rr[i - 1].y != q.y) s_row[q.y - y0] = i;
+    // a blob beyond the two tables (rare: a merged clump, a reflection along a wall) keeps its lines in global memory and finds a
+    // row's first line by bisection on y; same result, no table
+    const bool big = B.n_runs > (uint32_t)W_NR || rows > W_ROWS;
+    if (!big) {
+        for (int i = threadIdx.x; i < (int)B.n_runs; i += 256) {
+            const trexhip_run q = rr[i];
+            s_runs[i] = (uint32_t)q.x0 | ((uint32_t)q.x1 << 16);
+            if (i == 0 || rr[i - 1].y != q.y) s_row[q.y - y0] = i;
+        }
+        if (threadIdx.x == 0) s_row[rows] = (int)B.n_runs;
+        __syncthreads();
     }
-    if (threadIdx.x == 0) s_row[rows] = (int)B.n_runs;
-    __syncthreads();
+    auto line = [&](int r) -> uint32_t {
+        if (big) { const trexhip_run q = rr[r]; return (uint32_t)q.x0 | ((uint32_t)q.x1 << 16); }
+        return s_runs[r];
+    };
+    // first line of bounding-box row yy (0..rows; rows -> n_runs): the lines of a blob are sorted by y and every row has one
+    auto row_begin = [&](int yy) -> int {
+        if (!big) return s_row[yy];
+        int lo = 0, hi = (int)B.n_runs;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)rr[mid].y < yy + y0) lo = mid + 1; else hi = mid; }
+        return lo;
+    };
+    auto member = [&](int yy, int ax) -> bool {
+        for (int r = row_begin(yy), re = row_begin(yy + 1); r < re; ++r) { const uint32_t q = line(r); if (ax >= (int)(q & 0xffffu) && ax <= (int)(q >> 16)) return true; }
+        return false;
+    };
     const double* M = minv + (size_t)bi * 6;
     const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5];
     const int sw = B.x1 - B.x0 + 1, sh = rows, plane = sw * sh;
@@ -585,7 +606,7 @@ __global__ __launch_bounds__(256) void k_crops_warp(const SegCfg c, const uint8_
         for (int i = threadIdx.x; i < (plane * och + 3) / 4; i += 256) reinterpret_cast<uint32_t*>(s_img)[i] = 0u;
         __syncthreads();
         for (int r = threadIdx.x >> 4; r < (int)B.n_runs; r += 16) {      // 16 lanes per line: its pixel loads are independent
-            const uint32_t q = s_runs[r];
+            const uint32_t q = line(r);
             const int xa = (int)(q & 0xffffu), xb = (int)(q >> 16), yy = (int)rr[r].y;
             for (int ax = xa + (int)(threadIdx.x & 15); ax <= xb; ax += 16)
                 for (int ch = 0; ch < och; ++ch) s_img[ch * plane + (yy - y0) * sw + (ax - B.x0)] = (uint8_t)source(yy, ax, ch);
@@ -617,7 +638,7 @@ __global__ __launch_bounds__(256) void k_crops_warp(const SegCfg c, const uint8_
                 if (staged) p = s_img[ny * sw + nx];
                 else {
                     const int ax = nx + B.x0;
-                    for (int r = s_row[ny]; r < s_row[ny + 1]; ++r) { const uint32_t q = s_runs[r]; if (ax >= (int)(q & 0xffffu) && ax <= (int)(q >> 16)) { p = source(ny + y0, ax, 0); break; } }
+                    if (member(ny, ax)) p = source(ny + y0, ax, 0);
                 }
             }
             out[i] = (uint8_t)p;
@@ -631,12 +652,7 @@ __global__ __launch_bounds__(256) void k_crops_warp(const SegCfg c, const uint8_
         for (int k = 0; k < 4; ++k) {
             const int xx = sx + (k & 1), yy = sy + (k >> 1);
             in[k] = xx >= 0 && xx < sw && yy >= 0 && yy < sh;
-            if (in[k] && !staged) {
-                const int ax = xx + B.x0;
-                bool member = false;
-                for (int r = s_row[yy]; r < s_row[yy + 1]; ++r) { const uint32_t q = s_runs[r]; if (ax >= (int)(q & 0xffffu) && ax <= (int)(q >> 16)) { member = true; break; } }
-                in[k] = member;
-            }
+            if (in[k] && !staged) in[k] = member(yy, xx + B.x0);
         }
         const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
         for (int ch = 0; ch < och; ++ch) {
