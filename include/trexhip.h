@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 7
+#define TREXHIP_ABI_VERSION 8
 
 enum {
     TREXHIP_OK = 0,
@@ -493,8 +493,9 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  * (forward in training mode, nn.CrossEntropyLoss, backward, torch.optim.Adam(lr).step -- criterion / optimizer :1420-1421), for
  * V118_3 (visual_identification_network_torch.py:184-258) in fp32: the reference's arithmetic on every device but 'cuda', where it
  * additionally wraps the step in autocast + GradScaler (:1066-1072).  What stays on the host side of the boundary, as in the
- * reference: the data loader with its augmentation (:158-188, :1325-1336), epochs, validation, ReduceLROnPlateau (-> set_lr) and
- * early stopping (:1160-1283).
+ * reference: epochs, validation, ReduceLROnPlateau (-> set_lr) and early stopping (:1160-1283).  The data loader with its
+ * augmentation (:158-188, :1325-1336) may stay there too (trexhip_train_step takes what it yields), or run on the device:
+ * trexhip_augment_device below writes the batch trexhip_train_step_device takes, from crops that never left HBM.
  *   trexhip_trainer_create     weights = the blob of trexhip_load_weights (state_dict order, running statistics included); the
  *                              trainer keeps parameters, gradients and Adam moments in HBM.  Training runs at 80 x 80 only: a blob
  *                              of any other individual_image_size is refused with TREXHIP_E_UNSUPPORTED
@@ -540,6 +541,46 @@ int trexhip_train_step(trexhip_trainer* trainer, const float* inputs, const int3
                        int32_t* correct);
 int trexhip_trainer_read(trexhip_trainer* trainer, int32_t tensor, int32_t kind, float* out, size_t count);
 int trexhip_trainer_export(trexhip_trainer* trainer, void* blob, size_t capacity, size_t* bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * The training loader on the device.  Replaces TRexImageDataset.__getitem__ + DataLoader(num_workers=0)
+ * (visual_recognition_torch.py:158-194, :1325-1337, :1391-1402): a resident pool of uint8 crops (what the crop calls write) and an
+ * index list become the float32 [n][H][W][C] batch in [0, 255] that trexhip_train_step_device takes, augmented as the reference's
+ * transform does it: torchvision RandomAffine(degrees=5, translate=(move_range, move_range)) -- nearest neighbour, fill 0, about the
+ * image centre, angle clockwise -- then ColorJitter(brightness, contrast, saturation = 0.85..1.15, hue = +-0.05) on x = byte / 255
+ * in a random order of its four operations, every operation ending in clamp(0, 1); output clamp(x, 0, 1) * 255 (:186).
+ *   d_pool            [pool_size][H][W][C] uint8;  d_out [n][H][W][C] float32;  sample i of the batch = pool entry indices[i]
+ *   indices           HOST array of n entries, NULL = 0 .. n-1; checked before anything is launched: an entry outside
+ *                     0 .. pool_size-1 returns TREXHIP_E_INVALID and nothing runs
+ *   ap                NULL = the validation loader (transform=None): d_out = float(pool byte) exactly, no draws
+ *   d_draws           device, [n] trexhip_augment_draw.  draws_given != 0: sample i uses d_draws[i] (how the parity tests inject what the
+ *                     reference drew, like d_keep_masks).  draws_given == 0: the kernel draws per sample from a counter-based hash of
+ *                     (ap->seed, counter, i, field) -- angle ~ U(-degrees, degrees), tx = round_half_even(U(-translate_x W, translate_x W)),
+ *                     ty likewise, the four factors uniform in their ranges, a uniformly random order (RandomAffine.get_params,
+ *                     ColorJitter.get_params) -- and writes what it drew to d_draws when that is not NULL.  Hand a new `counter` per call.
+ *   d_pool_targets / d_targets_out   optional, both or neither: d_targets_out[i] = d_pool_targets[indices[i]]
+ * Sizes: 8 <= width, height <= 256, channels 1 or 3 (TREXHIP_E_UNSUPPORTED otherwise), n >= 1.  Saturation and hue are the identity for
+ * one channel; the contrast mean is the mean of the image as it stands at that point (of its gray value for three channels).
+ * One kernel launch on the context's stream, no synchronisation; a sample's output depends on nothing but its pool entry and its draw. */
+typedef struct {
+    float degrees;                       /* 5: angle ~ U(-degrees, degrees)                                  */
+    float translate_x, translate_y;      /* move_range = min(0.05, 2 / min(W, H))   (:1301)                  */
+    float brightness_lo, brightness_hi;  /* 0.85, 1.15                                                       */
+    float contrast_lo, contrast_hi;      /* 0.85, 1.15                                                       */
+    float saturation_lo, saturation_hi;  /* 0.85, 1.15                                                       */
+    float hue_lo, hue_hi;                /* -0.05, 0.05                                                      */
+    uint64_t seed;
+} trexhip_augment_params;
+typedef struct {                         /* one sample's draw, 32 bytes                                      */
+    float angle; int32_t tx, ty;         /* degrees; whole pixels                                            */
+    float brightness, contrast, saturation, hue;
+    int32_t order;                       /* application order of 0 brightness, 1 contrast, 2 saturation, 3 hue: 2 bits each, first
+                                            operation in the lowest bits (identity order = 0xE4)                */
+} trexhip_augment_draw;
+void trexhip_default_augment_params(trexhip_augment_params* p, int32_t width, int32_t height);
+int trexhip_augment_device(trexhip_ctx* ctx, const trexhip_augment_params* ap, const uint8_t* d_pool, const int32_t* d_pool_targets,
+                           int32_t pool_size, const int32_t* indices, int32_t n, int32_t width, int32_t height, int32_t channels,
+                           trexhip_augment_draw* d_draws, int32_t draws_given, uint64_t counter, float* d_out, int32_t* d_targets_out);
 
 #ifdef __cplusplus
 }

@@ -109,6 +109,19 @@ class TrainParams(C.Structure):
                 ("bn_momentum", C.c_float), ("dropout", C.c_float), ("precision", C.c_int32), ("seed", C.c_uint64)]
 
 
+class AugmentParams(C.Structure):
+    _fields_ = [("degrees", C.c_float), ("translate_x", C.c_float), ("translate_y", C.c_float), ("brightness_lo", C.c_float), ("brightness_hi", C.c_float),
+                ("contrast_lo", C.c_float), ("contrast_hi", C.c_float), ("saturation_lo", C.c_float), ("saturation_hi", C.c_float),
+                ("hue_lo", C.c_float), ("hue_hi", C.c_float), ("seed", C.c_uint64)]
+
+
+# trexhip_augment_draw: one sample's augmentation; order = 2 bits per position, first operation lowest (0 brightness, 1 contrast, 2 saturation, 3 hue)
+AUGMENT_DRAW_DTYPE = np.dtype([("angle", "<f4"), ("tx", "<i4"), ("ty", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"),
+                               ("hue", "<f4"), ("order", "<i4")])
+assert AUGMENT_DRAW_DTYPE.itemsize == 32
+AUGMENT_IDENTITY_ORDER = 0xE4
+
+
 SYMBOLS = [
     "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
@@ -116,6 +129,7 @@ SYMBOLS = [
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
     "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats",
     "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
+    "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
 ]
 
@@ -205,6 +219,14 @@ def lib():
         L.trexhip_train_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_trainer_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]
         L.trexhip_trainer_export.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.trexhip_default_augment_params.argtypes = [C.POINTER(AugmentParams), C.c_int32, C.c_int32]
+        L.trexhip_default_augment_params.restype = None
+        L.trexhip_augment_device.argtypes = [C.c_void_p, C.POINTER(AugmentParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.trexhip_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.trexhip_device_free.argtypes = [C.c_void_p, C.c_void_p]
+        L.trexhip_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.trexhip_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         _LIB = L
     return _LIB
 
@@ -226,6 +248,18 @@ def default_params(width, height, **kw):
         p.n_ranges = len(ranges)
         for i, (a, b) in enumerate(ranges):
             p.ranges[2 * i], p.ranges[2 * i + 1] = a, b
+    return p
+
+
+def default_augment_params(width, height, **kw):
+    """The reference's training transform for width x height crops (visual_recognition_torch.py:1301, :1325-1331): RandomAffine(5, move_range) +
+    ColorJitter(0.85..1.15 x 3, hue +-0.05); keywords override single fields (seed among them)."""
+    p = AugmentParams()
+    lib().trexhip_default_augment_params(C.byref(p), width, height)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
     return p
 
 
@@ -518,6 +552,38 @@ class Segmenter:
         _check(lib().trexhip_identify_device(self._h, C.c_void_p(d_crops_ptr), n, C.c_void_p(d_probs_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
 
+    # ---- the training loader on the device ----
+    def device_alloc(self, nbytes):
+        """-> device address of nbytes of HBM on the context's device (trexhip_device_alloc)"""
+        out = C.c_void_p()
+        _check(lib().trexhip_device_alloc(self._h, nbytes, C.byref(out)))
+        return int(out.value)
+
+    def device_free(self, d_ptr):
+        _check(lib().trexhip_device_free(self._h, C.c_void_p(d_ptr or 0)))
+
+    def copy_to_device(self, d_ptr, array):
+        a = np.ascontiguousarray(array)
+        _check(lib().trexhip_copy_to_device(self._h, C.c_void_p(d_ptr), a.ctypes.data_as(C.c_void_p), a.nbytes))
+
+    def copy_to_host(self, d_ptr, shape, dtype):
+        out = np.empty(shape, dtype)
+        _check(lib().trexhip_copy_to_host(self._h, out.ctypes.data_as(C.c_void_p), C.c_void_p(d_ptr), out.nbytes))
+        return out
+
+    def augment_device(self, d_pool_ptr, pool_size, n, width, height, channels, d_out_ptr, ap=None, indices=None, d_pool_targets_ptr=0,
+                       d_targets_out_ptr=0, d_draws_ptr=0, draws_given=False, counter=0):
+        """uint8 pool [pool_size][H][W][C] + indices (host, None = 0..n-1) -> float32 batch [n][H][W][C] at d_out_ptr, augmented like the reference's
+        training transform (ap: AugmentParams; None = the validation loader, float(byte)); one kernel launch, no synchronisation; see include/trexhip.h."""
+        idx = None
+        if indices is not None:
+            idx = np.ascontiguousarray(indices, np.int32)
+            if idx.shape != (n,):
+                raise ValueError(f"indices must hold n = {n} entries, got shape {idx.shape}")
+        _check(lib().trexhip_augment_device(self._h, C.byref(ap) if ap is not None else None, C.c_void_p(d_pool_ptr), C.c_void_p(d_pool_targets_ptr or 0), pool_size,
+                                            idx.ctypes.data_as(C.c_void_p) if idx is not None else None, n, width, height, channels,
+                                            C.c_void_p(d_draws_ptr or 0), 1 if draws_given else 0, counter, C.c_void_p(d_out_ptr), C.c_void_p(d_targets_out_ptr or 0)))
+
     def rethreshold_per_blob(self, d_thresholds_ptr, method=0, size_ranges=(), threshold=0):
         """SplitBlob::apply_threshold building block: one threshold per detect blob (int32 device array, pooled order; <0 skips)."""
         rng = np.ascontiguousarray(np.array(size_ranges, np.float64).reshape(-1))
@@ -594,6 +660,12 @@ class Trainer:
         x, y = self._check_batch(inputs, targets)
         loss, correct = C.c_float(), C.c_int32()
         _check(lib().trexhip_train_eval(self._h, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.shape[0], C.byref(loss), C.byref(correct)))
+        return loss.value, correct.value
+
+    def evaluate_device(self, d_inputs_ptr, d_targets_ptr, n):
+        """the same from device memory (trexhip_train_eval_device; synchronises) -> (mean cross entropy, correct count)"""
+        loss, correct = C.c_float(), C.c_int32()
+        _check(lib().trexhip_train_eval_device(self._h, C.c_void_p(d_inputs_ptr), C.c_void_p(d_targets_ptr), n, C.byref(loss), C.byref(correct)))
         return loss.value, correct.value
 
     def set_lr(self, lr):

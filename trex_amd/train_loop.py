@@ -8,6 +8,10 @@ len(), e.g. the reference's own DataLoader over TRexImageDataset with its augmen
 (ValidationCallback, :355-560: per-class accuracy, uniqueness, early stopping), used through the same three members train() uses:
 on_batch_end(batch, logs), on_epoch_end(epoch, logs), stop_training.  No torch in here: batches may be numpy arrays or anything
 np.asarray() accepts (torch CPU tensors included).
+
+Or the loader runs on the device: ResidentLoader keeps the uint8 crops in HBM and makes every batch there (trexhip_augment_device: the
+reference's RandomAffine + ColorJitter, or the plain conversion of the validation loader), and train_resident() is the same epoch loop
+over the device pointers it yields, so an epoch never leaves the device.
 """
 import numpy as np
 
@@ -60,26 +64,27 @@ class ReduceLROnPlateau:
         return [self.lr]
 
 
-def train(trainer, train_loader, val_loader, callback, scheduler, settings, abort=lambda: False, log=None):
-    """The loop of train(model, train_loader, val_loader, criterion, optimizer, callback, scheduler, settings, device) with model +
-    criterion + optimizer = `trainer` (capi.Trainer).  settings["epochs"] epochs; per batch one optimizer step and
-    callback.on_batch_end(batch, {'loss', 'acc'}); per epoch the validation pass in eval mode (when val_loader is not empty), scheduler.step(val_loss)
-    -> trainer.set_lr, callback.on_epoch_end(epoch, logs); stops when callback.stop_training or abort() is set.  Returns the history."""
+def _host_batch(inputs, targets, check_shape):
+    x = np.ascontiguousarray(np.asarray(inputs), np.float32)
+    y = np.asarray(targets)
+    if check_shape and (x.ndim != 4 or y.ndim != 1 or x.shape[0] != y.shape[0]):
+        raise ValueError(f"Expected inputs (N,H,W,C) and targets (N,), got {x.shape} and {y.shape}")          # train() asserts the same, :1104-1112
+    if y.dtype.kind not in "iu":
+        raise ValueError(f"targets must be integer class indices, got {y.dtype}")     # train() asserts integer labels, :1109-1110
+    return x, y.astype(np.int32), x.shape[0]
+
+
+def _epochs(trainer, train_loader, val_loader, callback, scheduler, settings, abort, log, step, evaluate):
+    """The epoch loop both entry points share.  step(batch) / evaluate(batch) -> (loss, correct, n) for whatever the loaders yield."""
     history = []
     best_val_acc = 0.0
     for epoch in range(int(settings["epochs"])):
         running_loss = 0.0
         running_acc = 0.0
         n_batches = 0
-        for batch, (inputs, targets) in enumerate(train_loader):
-            x = np.ascontiguousarray(np.asarray(inputs), np.float32)
-            y = np.asarray(targets)
-            if x.ndim != 4 or y.ndim != 1 or x.shape[0] != y.shape[0]:
-                raise ValueError(f"Expected inputs (N,H,W,C) and targets (N,), got {x.shape} and {y.shape}")          # train() asserts the same, :1104-1112
-            if np.asarray(y).dtype.kind not in "iu":
-                raise ValueError(f"targets must be integer class indices, got {np.asarray(y).dtype}")     # train() asserts integer labels, :1109-1110
-            loss, correct = trainer.step(x, y.astype(np.int32))
-            acc = correct / float(x.shape[0])
+        for batch, item in enumerate(train_loader):
+            loss, correct, n = step(item)
+            acc = correct / float(n)
             running_loss += loss
             running_acc += acc
             n_batches += 1
@@ -88,15 +93,11 @@ def train(trainer, train_loader, val_loader, callback, scheduler, settings, abor
         acc = running_acc / max(n_batches, 1)
         if len(val_loader) > 0:
             val_loss, correct, total, nb = 0.0, 0, 0, 0
-            for inputs, targets in val_loader:
-                x = np.ascontiguousarray(np.asarray(inputs), np.float32)
-                y = np.asarray(targets)
-                if y.dtype.kind not in "iu":
-                    raise ValueError(f"targets must be integer class indices, got {y.dtype}")
-                l, c = trainer.evaluate(x, y.astype(np.int32))
+            for item in val_loader:
+                l, c, n = evaluate(item)
                 val_loss += l
                 correct += c
-                total += x.shape[0]
+                total += n
                 nb += 1
             val_loss /= nb
             val_acc = correct / float(total)
@@ -118,3 +119,108 @@ def train(trainer, train_loader, val_loader, callback, scheduler, settings, abor
         if abort():
             break
     return history
+
+
+def train(trainer, train_loader, val_loader, callback, scheduler, settings, abort=lambda: False, log=None):
+    """The loop of train(model, train_loader, val_loader, criterion, optimizer, callback, scheduler, settings, device) with model +
+    criterion + optimizer = `trainer` (capi.Trainer).  settings["epochs"] epochs; per batch one optimizer step and
+    callback.on_batch_end(batch, {'loss', 'acc'}); per epoch the validation pass in eval mode (when val_loader is not empty), scheduler.step(val_loss)
+    -> trainer.set_lr, callback.on_epoch_end(epoch, logs); stops when callback.stop_training or abort() is set.  Returns the history."""
+    def step(item):
+        x, y, n = _host_batch(item[0], item[1], True)
+        return (*trainer.step(x, y), n)
+
+    def evaluate(item):
+        x, y, n = _host_batch(item[0], item[1], False)
+        return (*trainer.evaluate(x, y), n)
+
+    return _epochs(trainer, train_loader, val_loader, callback, scheduler, settings, abort, log, step, evaluate)
+
+
+def train_resident(trainer, train_loader, val_loader, callback, scheduler, settings, abort=lambda: False, log=None):
+    """train() over loaders that yield device memory -- (d_inputs_ptr, d_targets_ptr, n), e.g. ResidentLoader --: one
+    Trainer.step_device per batch, Trainer.evaluate_device per validation batch; everything else as in train()."""
+    def step(item):
+        return (*trainer.step_device(item[0], item[1], item[2]), item[2])
+
+    def evaluate(item):
+        return (*trainer.evaluate_device(item[0], item[1], item[2]), item[2])
+
+    return _epochs(trainer, train_loader, val_loader, callback, scheduler, settings, abort, log, step, evaluate)
+
+
+class ResidentLoader:
+    """TRexImageDataset + DataLoader (visual_recognition_torch.py:158-194, :1391-1410) with the samples in HBM.
+
+    crops_uint8: uint8 array (N, H, W, C), uploaded once -- or a device address of such a pool, e.g. what the crop calls wrote, with
+    count=N and image_shape=(H, W, C).  targets: integer array (N,), or a device address of N int32 when crops_uint8 is one.
+    Iterating yields (d_inputs_ptr, d_targets_ptr, n) per batch: float32 [n][H][W][C] in [0, 255] and int32 [n], made by ONE
+    trexhip_augment_device call each, in the loader's own two buffers (the next batch overwrites them; calls on the context are
+    ordered, so a step that was handed a batch has read it before the next is written).  Every epoch draws a new seeded permutation
+    when shuffle is set and new augmentations (the call's counter runs on); drop_last=False: the last batch may be smaller.
+    augment=True applies `params` (default: capi.default_augment_params(W, H), the reference's transform); augment=False,
+    shuffle=False is the validation loader.  `seg` is the capi.Segmenter whose stream the trainer uses."""
+
+    def __init__(self, seg, crops_uint8, targets, batch_size, augment=True, shuffle=True, seed=0, count=None, image_shape=None, params=None):
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        self.seg, self.batch_size, self.shuffle, self.seed = seg, int(batch_size), bool(shuffle), int(seed)
+        self._owned = []
+        if isinstance(crops_uint8, (int, np.integer)):
+            if count is None or image_shape is None or not isinstance(targets, (int, np.integer)):
+                raise ValueError("a device pool needs count, image_shape=(H, W, C) and a device address of its int32 targets")
+            self.count, (self.height, self.width, self.channels) = int(count), (int(v) for v in image_shape)
+            self.d_pool, self.d_pool_targets = int(crops_uint8), int(targets)
+        else:
+            x = np.asarray(crops_uint8)
+            y = np.asarray(targets)
+            if x.dtype != np.uint8 or x.ndim != 4:
+                raise ValueError(f"crops must be uint8 (N, H, W, C), got {x.dtype} {x.shape}")
+            if y.dtype.kind not in "iu" or y.shape != (x.shape[0],):
+                raise ValueError(f"targets must be integer class indices of shape ({x.shape[0]},), got {y.dtype} {y.shape}")
+            self.count, self.height, self.width, self.channels = (int(v) for v in x.shape)
+            self.d_pool = self._alloc(max(x.nbytes, 1))
+            self.d_pool_targets = self._alloc(4 * max(self.count, 1))
+            if self.count:
+                seg.copy_to_device(self.d_pool, x)
+                seg.copy_to_device(self.d_pool_targets, y.astype(np.int32))
+        self.params = None
+        if augment:
+            if params is None:
+                from . import capi
+                params = capi.default_augment_params(self.width, self.height)
+            params.seed = self.seed
+            self.params = params
+        self.d_inputs = self._alloc(4 * self.batch_size * self.height * self.width * self.channels)
+        self.d_targets = self._alloc(4 * self.batch_size)
+        self.epoch = 0
+        self.calls = 0
+
+    def _alloc(self, nbytes):
+        p = self.seg.device_alloc(nbytes)
+        self._owned.append(p)
+        return p
+
+    def __len__(self):
+        return (self.count + self.batch_size - 1) // self.batch_size
+
+    def order(self, epoch):
+        """pool indices of `epoch` in the order they are served"""
+        if not self.shuffle:
+            return np.arange(self.count, dtype=np.int32)
+        return np.random.default_rng([self.seed, epoch]).permutation(self.count).astype(np.int32)
+
+    def __iter__(self):
+        order = self.order(self.epoch)
+        self.epoch += 1
+        for b in range(len(self)):
+            idx = order[b * self.batch_size:(b + 1) * self.batch_size]
+            self.seg.augment_device(self.d_pool, self.count, len(idx), self.width, self.height, self.channels, self.d_inputs, ap=self.params, indices=idx,
+                                    d_pool_targets_ptr=self.d_pool_targets, d_targets_out_ptr=self.d_targets, counter=self.calls)
+            self.calls += 1
+            yield self.d_inputs, self.d_targets, len(idx)
+
+    def close(self):
+        for p in self._owned:
+            self.seg.device_free(p)
+        self._owned = []
