@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 8
+#define TREXHIP_ABI_VERSION 9
 
 enum {
     TREXHIP_OK = 0,
@@ -539,6 +539,14 @@ int trexhip_train_eval(trexhip_trainer* trainer, const float* inputs, const int3
 /* the same step from host memory (what the reference's DataLoader yields); targets are range-checked like train() does (:1112) */
 int trexhip_train_step(trexhip_trainer* trainer, const float* inputs, const int32_t* targets, int32_t n, const uint8_t* keep_masks, float* loss,
                        int32_t* correct);
+/* Softmax rows of any number of crops from the weights as they stand in the trainer: what ValidationCallback.plot_comparison_raw
+ * (visual_recognition_torch.py:406-451) and estimate_uniqueness() -> Accumulation::calculate_uniqueness (ui/Accumulation.cpp:767-879) get from
+ * predict_numpy at the end of every epoch, without exporting the weights to the inference context.  d_crops uint8 [n][80][80][channels]
+ * (what the crop calls and the resident pool hold), d_probs float32 [n][classes]: model.eval(), running statistics, nothing dropped, in the
+ * trainer's `precision`.  Any n >= 1: the call walks the crops in chunks of at most max_batch through the trainer's own buffers (a row does
+ * not depend on its chunk).  Ordered on the context's stream, NO host synchronisation; parameters, moments, running statistics and the step
+ * counter stay as they are */
+int trexhip_train_predict_device(trexhip_trainer* trainer, const uint8_t* d_crops, int32_t n, float* d_probs);
 int trexhip_trainer_read(trexhip_trainer* trainer, int32_t tensor, int32_t kind, float* out, size_t count);
 int trexhip_trainer_export(trexhip_trainer* trainer, void* blob, size_t capacity, size_t* bytes);
 
@@ -581,6 +589,46 @@ void trexhip_default_augment_params(trexhip_augment_params* p, int32_t width, in
 int trexhip_augment_device(trexhip_ctx* ctx, const trexhip_augment_params* ap, const uint8_t* d_pool, const int32_t* d_pool_targets,
                            int32_t pool_size, const int32_t* indices, int32_t n, int32_t width, int32_t height, int32_t channels,
                            trexhip_augment_draw* d_draws, int32_t draws_given, uint64_t counter, float* d_out, int32_t* d_targets_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Validation metrics of identity training on probabilities that are in HBM (trexhip_train_predict_device's rows, or
+ * trexhip_identify_device's for the shipped network): the two reductions ValidationCallback.evaluate
+ * (visual_recognition_torch.py:493-543) steers acceptance and early stopping by.  One launch plus a finalise; the call synchronises,
+ * because it returns host values.
+ *   confusion matrix   confusion[target][argmax] += 1 over all n rows (needs d_targets).  Its diagonal over its row sums is column 3 of
+ *                      plot_comparison_raw (:449, (y.argmax(axis=1) == i).sum() / len(y)).  argmax is np.argmax: the first index of the
+ *                      maximum, the first NaN if the row holds one -- also for a row that has no identity in the sense below (an all-zero
+ *                      row counts in column 0, as plot_comparison_raw would count it)
+ *   uniqueness         Accumulation::calculate_uniqueness (ui/Accumulation.cpp:767-879) over n_frames ranges of rows, line by line:
+ *       identity of a row (:804-814): max_p = 0, ids ascending, take id iff p > max_p: the first index wins a tie; a row with no entry
+ *           > 0 (all zero, all negative, NaN) has no identity and adds nothing to its frame
+ *       per frame: unique_percent_raw = distinct / float(length) in float32, 0 for an empty range (:822-824, :840); accum_p = float32 sum
+ *           over the frame's distinct identities of the largest max_p each got, summed in ASCENDING IDENTITY ORDER (the reference
+ *           iterates a hash_map, :827: its order is unspecified; this one is fixed so that results repeat);
+ *           unique_percent = float(logistic(accum_p / float(distinct)) * raw) when distinct > 0, logistic(x) = 1 / (1 + exp(-x * M_PI)) * NORMAL
+ *           in double, NORMAL = 1 + expf(-float(M_PI)) (:834-849); the frame is good iff distinct == length, so an empty one is (:852-858)
+ *       across frames, in frame order: the double sums of both per-frame values (:841, :850), and per identity the float32 sum of its
+ *           largest max_p over the frames it appeared in, divided by their number, 0 if it never appeared (:830-831, :865-870)
+ *   frame_ranges       HOST [n_frames][2] = {start, end} rows; may overlap and leave gaps.  Checked before anything is launched:
+ *                      0 <= start <= end <= n, n_frames >= 1; 1 <= classes <= 1024; else TREXHIP_E_INVALID and nothing runs
+ *   d_targets          device [n]; a target outside 0..classes-1 is flagged by the device: TREXHIP_E_INVALID, no output is written
+ * Every output pointer is HOST memory and optional; without d_targets no confusion matrix is made, without frame_ranges no uniqueness.
+ * Two calls on the same input give the same bytes: every floating-point sum has a fixed order, the confusion counts are integers. */
+typedef struct {
+    uint32_t good_frames, bad_frames;   /* Accumulation.cpp:852-858 */
+    float    good_ratio;                /* float(good) / float(good + bad)          (:878, first element)  */
+    float    mean_unique;               /* percentages / n_frames                    (:878, third element)  */
+    float    mean_unique_raw;           /* rpercentages / n_frames                   (:875)                 */
+} trexhip_uniqueness_result;
+int trexhip_validation_metrics_device(trexhip_ctx* ctx, const float* d_probs, int32_t n, int32_t classes,
+                                      const int32_t* d_targets,            /* [n] or NULL: no confusion matrix       */
+                                      const int32_t* frame_ranges,         /* HOST [n_frames][2] = {start, end}, or NULL */
+                                      int32_t n_frames,
+                                      uint32_t* confusion,                 /* HOST [classes][classes], row = target, or NULL */
+                                      trexhip_uniqueness_result* result,   /* HOST, or NULL                          */
+                                      float* unique_percent,               /* HOST [n_frames] (:849), or NULL        */
+                                      float* unique_percent_raw,           /* HOST [n_frames] (:840), or NULL        */
+                                      float* uniqueness_per_class);        /* HOST [classes]  (:865-870), or NULL    */
 
 #ifdef __cplusplus
 }

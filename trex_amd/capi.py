@@ -122,6 +122,24 @@ assert AUGMENT_DRAW_DTYPE.itemsize == 32
 AUGMENT_IDENTITY_ORDER = 0xE4
 
 
+class UniquenessResult(C.Structure):
+    _fields_ = [("good_frames", C.c_uint32), ("bad_frames", C.c_uint32), ("good_ratio", C.c_float), ("mean_unique", C.c_float), ("mean_unique_raw", C.c_float)]
+
+
+class ValidationMetrics:
+    """What Segmenter.validation_metrics returns.  With targets: confusion (uint32 [classes][classes], row = target, column = np.argmax) and
+    per_class_accuracy (float64 [classes]: diagonal / row sum, plot_comparison_raw's column 3; a class without samples is left out of the
+    division and stays 0, as the reference's `continue` leaves it, visual_recognition_torch.py:409-416 -- never NaN).  With frame ranges: good_frames, bad_frames, good_ratio,
+    mean_unique, mean_unique_raw, unique_percent / unique_percent_raw (float32 [n_frames]) and uniqueness_per_class (float32 [classes]) of
+    Accumulation::calculate_uniqueness.  What was not asked for is None."""
+    __slots__ = ("confusion", "per_class_accuracy", "good_frames", "bad_frames", "good_ratio", "mean_unique", "mean_unique_raw",
+                 "unique_percent", "unique_percent_raw", "uniqueness_per_class")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
 SYMBOLS = [
     "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
@@ -130,6 +148,7 @@ SYMBOLS = [
     "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats",
     "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
+    "trexhip_train_predict_device", "trexhip_validation_metrics_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
 ]
 
@@ -223,6 +242,9 @@ def lib():
         L.trexhip_default_augment_params.restype = None
         L.trexhip_augment_device.argtypes = [C.c_void_p, C.POINTER(AugmentParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.trexhip_train_predict_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.trexhip_validation_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                        C.POINTER(UniquenessResult), C.c_void_p, C.c_void_p, C.c_void_p]
         L.trexhip_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.trexhip_device_free.argtypes = [C.c_void_p, C.c_void_p]
         L.trexhip_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -584,6 +606,33 @@ class Segmenter:
                                             idx.ctypes.data_as(C.c_void_p) if idx is not None else None, n, width, height, channels,
                                             C.c_void_p(d_draws_ptr or 0), 1 if draws_given else 0, counter, C.c_void_p(d_out_ptr), C.c_void_p(d_targets_out_ptr or 0)))
 
+    def validation_metrics(self, d_probs_ptr, n, classes, d_targets_ptr=0, frame_ranges=None):
+        """Confusion matrix / per-class accuracy (with d_targets_ptr: int32 [n] on the device) and the uniqueness of
+        Accumulation::calculate_uniqueness (with frame_ranges: host integers [n_frames][2] = (start, end) rows) of float32 probabilities
+        [n][classes] in HBM, reduced on the device (trexhip_validation_metrics_device; synchronises) -> ValidationMetrics."""
+        out = ValidationMetrics()
+        conf = np.zeros((classes, classes), np.uint32) if d_targets_ptr else None
+        fr = None
+        res = UniquenessResult()
+        up = upr = upc = None
+        if frame_ranges is not None:
+            fr = np.ascontiguousarray(frame_ranges, np.int32).reshape(-1, 2)
+            up, upr, upc = np.zeros(len(fr), np.float32), np.zeros(len(fr), np.float32), np.zeros(classes, np.float32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        _check(lib().trexhip_validation_metrics_device(self._h, C.c_void_p(d_probs_ptr or 0), n, classes, C.c_void_p(d_targets_ptr or 0), ptr(fr),
+                                                       len(fr) if fr is not None else 0, ptr(conf), C.byref(res) if fr is not None else None,
+                                                       ptr(up), ptr(upr), ptr(upc)))
+        if conf is not None:
+            rows = conf.sum(axis=1, dtype=np.int64)
+            out.confusion = conf
+            out.per_class_accuracy = np.zeros(classes, np.float64)
+            np.divide(np.diagonal(conf), rows, out=out.per_class_accuracy, where=rows > 0)
+        if fr is not None:
+            out.good_frames, out.bad_frames = int(res.good_frames), int(res.bad_frames)
+            out.good_ratio, out.mean_unique, out.mean_unique_raw = float(res.good_ratio), float(res.mean_unique), float(res.mean_unique_raw)
+            out.unique_percent, out.unique_percent_raw, out.uniqueness_per_class = up, upr, upc
+        return out
+
     def rethreshold_per_blob(self, d_thresholds_ptr, method=0, size_ranges=(), threshold=0):
         """SplitBlob::apply_threshold building block: one threshold per detect blob (int32 device array, pooled order; <0 skips)."""
         rng = np.ascontiguousarray(np.array(size_ranges, np.float64).reshape(-1))
@@ -667,6 +716,11 @@ class Trainer:
         loss, correct = C.c_float(), C.c_int32()
         _check(lib().trexhip_train_eval_device(self._h, C.c_void_p(d_inputs_ptr), C.c_void_p(d_targets_ptr), n, C.byref(loss), C.byref(correct)))
         return loss.value, correct.value
+
+    def predict_device(self, d_crops_ptr, n, d_probs_ptr):
+        """uint8 crops [n][80][80][C] in HBM -> float32 softmax rows [n][classes] at d_probs_ptr from the weights as they stand (eval mode; any
+        n, chunked by max_batch inside; no synchronisation; the trainer is unchanged): trexhip_train_predict_device"""
+        _check(lib().trexhip_train_predict_device(self._h, C.c_void_p(d_crops_ptr), n, C.c_void_p(d_probs_ptr)))
 
     def set_lr(self, lr):
         _check(lib().trexhip_trainer_set_lr(self._h, lr))

@@ -504,6 +504,47 @@ __global__ __launch_bounds__(128) void k_t_head(const float* __restrict__ hpart,
     if (act) dh[(size_t)s * 100 + tid] = rstd * (dxh - m1 - xh * m2);
 }
 
+// the head of a prediction (trexhip_train_predict_device): k_t_head's forward half with nothing dropped -- fc1 bias + LayerNorm + ReLU + fc2, the
+// same expressions in the same order -- and the softmax row expf(l - lse), as k_t_head forms p.  No targets, none of the backward buffers
+__global__ __launch_bounds__(128) void k_t_head_eval(const float* __restrict__ hpart, int n, const float* __restrict__ b1, const float* __restrict__ lng,
+                                                     const float* __restrict__ lnb, const float* __restrict__ w2 /*[C][100]*/, const float* __restrict__ b2,
+                                                     int classes, float* __restrict__ probs /*[n][C]*/) {
+    __shared__ float red[128];
+    __shared__ float s_d[100];
+    __shared__ float s_dl[1024];
+    const int tid = threadIdx.x, s = blockIdx.x;
+    const bool act = tid < 100;
+    float h = 0.f;
+    if (act) {
+        h = b1[tid];
+        for (int hw = 0; hw < 100; ++hw) h += hpart[((size_t)hw * n + s) * 100 + tid];
+    }
+    const float mean = block_sum128(act ? h : 0.f, red) * 0.01f;
+    const float dv = act ? h - mean : 0.f;
+    const float var = block_sum128(dv * dv, red) * 0.01f;
+    const float rstd = 1.0f / sqrtf(var + EPS_LN);
+    if (act) {
+        const float xh = dv * rstd;
+        const float y = xh * lng[tid] + lnb[tid];
+        s_d[tid] = fmaxf(y, 0.f);
+    }
+    __syncthreads();
+    float lmax = -INFINITY;
+    for (int c = tid; c < classes; c += 128) {
+        float acc = b2[c];
+        const float* wr = w2 + (size_t)c * 100;
+        for (int j = 0; j < 100; ++j) acc += s_d[j] * wr[j];
+        s_dl[c] = acc;
+        if (acc > lmax) lmax = acc;
+    }
+    const float gmax = block_max128(lmax, red);
+    float se = 0.f;
+    for (int c = tid; c < classes; c += 128) se += expf(s_dl[c] - gmax);
+    const float sum = block_sum128(se, red);
+    const float lse = gmax + logf(sum);
+    for (int c = tid; c < classes; c += 128) probs[(size_t)s * classes + c] = expf(s_dl[c] - lse);
+}
+
 // parameter gradients of the head: fc2 weight / bias, LayerNorm gamma / beta, fc1 bias; one thread per element, samples in order
 __global__ __launch_bounds__(256) void k_t_head_grads(const float* __restrict__ dl, const float* __restrict__ hd, const float* __restrict__ dy,
                                                       const float* __restrict__ xhat, const float* __restrict__ dh, int n, int classes,
@@ -1461,9 +1502,10 @@ static int check_targets(Trainer* t) {
 }
 
 // forward pass up to the per-sample loss / arg-max (and, as a by-product of k_t_head, the gradient at the fc1 output).  train = batch
-// statistics + dropout masks `keep`; eval = running statistics, nothing dropped (model.eval(), visual_recognition_torch.py:1171-1185)
+// statistics + dropout masks `keep`; eval = running statistics, nothing dropped (model.eval(), visual_recognition_torch.py:1171-1185).
+// probs (eval only): the head writes the softmax rows there and nothing else (k_t_head_eval)
 static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, float scale, bool train,
-                            hipStream_t side = nullptr) {
+                            hipStream_t side = nullptr, float* probs = nullptr) {
     const uint8_t *k1 = keep, *k2 = keep + (size_t)n * 16, *k3 = keep + (size_t)n * 80, *k4 = keep + (size_t)n * 208;
     float* P = t->P;
     const size_t* o = t->off;
@@ -1495,6 +1537,10 @@ static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int
     else hipLaunchKernelGGL((k_conv5<64, 128, 20, 10, 32, CONV_EPI_RAW, 128>), dim3(n * G3F::BPC), dim3(512), G3F::LDS_BYTES, s, t->a2, P + o[T_C3W], P + o[T_C3B], t->z3);
     block(std::integral_constant<int, 128>{}, 2, t->z3, t->a3, 20, T_G3, T_BE3, T_RM3, T_RV3, k3, h2 ? n * H3F::BPC : 0);
     hipLaunchKernelGGL(k_t_fc1, dim3(100, (n + 63) / 64), dim3(256), 0, s, t->a3, P + o[T_F1W], t->hpart, n);
+    if (probs) {
+        hipLaunchKernelGGL(k_t_head_eval, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], P + o[T_F2W], P + o[T_F2B], t->classes, probs);
+        return;
+    }
     hipLaunchKernelGGL(k_t_head, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], k4, scale, P + o[T_F2W], P + o[T_F2B], targets,
                        t->classes, t->xhat, t->hd, t->dl, t->dy, t->dh, t->loss, t->correct, t->bad_target);
 }
@@ -1534,6 +1580,25 @@ static int trainer_eval(Trainer* t, const float* x, const int32_t* targets, int 
     if (h_loss) *h_loss = two[0];
     if (h_correct) *h_correct = (int32_t)two[1];
     return check_targets(t);
+}
+
+// softmax rows of any number of uint8 crops from the weights as they stand (predict_numpy in model.eval(), visual_recognition_torch.py:406-451):
+// chunks of at most max_batch through the trainer's own buffers -- bytes -> float32 in x_stage (k_augment's plain path), the eval forward,
+// k_t_head_eval -- all on the context's stream, no synchronisation.  Parameters, moments, running statistics and the step count stay as they are
+static int trainer_predict(Trainer* t, const uint8_t* d_crops, int n, float* d_probs) {
+    trexhip_ctx* ctx = t->ctx;
+    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    hipStream_t s = ctx->stream;
+    { const int rc = trainer_attrs(t); if (rc) return rc; }
+    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)std::min(n, t->max_n) * 308, s));       // nothing dropped
+    for (int at = 0; at < n; at += t->max_n) {
+        const int m = std::min(t->max_n, n - at);
+        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * 6400 * t->CH, nullptr, m, nullptr, m, 80, 80, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
+        if (rc != TREXHIP_OK) return rc;
+        trainer_forward(t, s, t->x_stage, nullptr, m, t->keep, 1.0f, false, nullptr, d_probs + (size_t)at * t->classes);
+    }
+    TH_CHECK_HIP(hipGetLastError());
+    return TREXHIP_OK;
 }
 
 static int trainer_step(Trainer* t, const float* x, const int32_t* targets, int n, const uint8_t* d_keep, float* h_loss, int32_t* h_correct) {
@@ -1753,6 +1818,12 @@ int trexhip_train_eval_device(trexhip_trainer* h, const float* d_inputs, const i
     if (!h || !d_inputs || !d_targets) { set_error("trexhip_train_eval_device: null argument"); return TREXHIP_E_INVALID; }
     if (n < 1 || n > h->t->max_n) { set_error("trexhip_train_eval_device: n must be 1..max_batch"); return TREXHIP_E_INVALID; }
     return trainer_eval(h->t, d_inputs, d_targets, n, loss, correct);
+}
+
+int trexhip_train_predict_device(trexhip_trainer* h, const uint8_t* d_crops, int32_t n, float* d_probs) {
+    if (!h || !d_crops || !d_probs) { set_error("trexhip_train_predict_device: null argument"); return TREXHIP_E_INVALID; }
+    if (n < 1) { set_error("trexhip_train_predict_device: n must be at least 1"); return TREXHIP_E_INVALID; }
+    return trainer_predict(h->t, d_crops, n, d_probs);
 }
 
 int trexhip_train_eval(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, float* loss, int32_t* correct) {

@@ -35,6 +35,7 @@ struct HipVINetwork {
 
     // VINetwork::load_weights: flat blob made by tools/convert_weights.py / trex_amd/weights.py
     void load_weights(const void* blob, size_t bytes) { check(trexhip_load_weights(_ctx, blob, bytes)); }
+    trexhip_ctx* context() const { return _ctx; }          // for the adapters that work on this network's device buffers (HipUniqueness.h)
     bool weights_loaded() const { return trexhip_num_classes(_ctx) > 0; }
     int num_classes() const { return trexhip_num_classes(_ctx); }
 

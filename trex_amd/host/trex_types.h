@@ -3,6 +3,7 @@
 // define TREXHIP_WITH_TREX and the adapter headers include TRex's real headers instead
 // (INTEGRATION.md).  Member names and semantics follow the reference:
 //   cmn::Image             commons misc/Image.h [not in tree]: rows, cols, dims, data()
+//   Frame_t, Range<T>      commons misc/frame_t.h, misc/ranges.h [not in tree]: what Accumulation::calculate_uniqueness takes
 //   HorizontalLine{y,x0,x1} Application/Tests/test_pixels.cpp:994-995 (ctor order), pv.cpp:505-509
 //   blob::Pair             Application/src/ProcessedVideo/pv.cpp:491-529, Tests/test_matching.cpp:1577
 //   pv::Frame              Application/src/ProcessedVideo/pv.h:114-192 (add_object, set_encoding, n, mask(), pixels())
@@ -25,6 +26,7 @@ namespace cmn {
 
 struct Image {
     using Ptr = std::unique_ptr<Image>;
+    using SPtr = std::shared_ptr<Image>;
     uint32_t rows = 0, cols = 0, dims = 0;
     std::vector<uint8_t> storage;
     static Ptr Make(uint32_t rows, uint32_t cols, uint32_t dims) {
@@ -37,6 +39,25 @@ struct Image {
     const uint8_t* data() const { return storage.data(); }
     size_t size() const { return storage.size(); }
     void set_to(uint8_t v) { std::fill(storage.begin(), storage.end(), v); }
+};
+
+// Frame_t (commons misc/frame_t.h [not in tree]: get(), ordered) and Range<T>{start, end} (misc/ranges.h: length() = end - start), as
+// Accumulation::calculate_uniqueness uses them (Application/src/tracker/ui/Accumulation.cpp:767, :799-824)
+struct Frame_t {
+    int32_t value = -1;
+    Frame_t() = default;
+    explicit Frame_t(int32_t v) : value(v) {}
+    int32_t get() const { return value; }
+    bool valid() const { return value >= 0; }
+    bool operator<(const Frame_t& o) const { return value < o.value; }
+    bool operator==(const Frame_t& o) const { return value == o.value; }
+};
+template <typename T>
+struct Range {
+    T start{}, end{};
+    Range() = default;
+    Range(T s, T e) : start(s), end(e) {}
+    T length() const { return end - start; }
 };
 
 struct HorizontalLine {

@@ -12,6 +12,11 @@ np.asarray() accepts (torch CPU tensors included).
 Or the loader runs on the device: ResidentLoader keeps the uint8 crops in HBM and makes every batch there (trexhip_augment_device: the
 reference's RandomAffine + ColorJitter, or the plain conversion of the validation loader), and train_resident() is the same epoch loop
 over the device pointers it yields, so an epoch never leaves the device.
+
+The measurements of the callback can stay there too: ResidentValidation keeps the validation crops and the crops of the uniqueness
+estimate in HBM, predicts them with the weights as they stand in the trainer (trexhip_train_predict_device) and reduces the rows on the
+device (trexhip_validation_metrics_device) to what ValidationCallback.evaluate records per epoch (:510-543): the accuracy of each class
+and estimate_uniqueness().  The stop rules (:545-650) read TRex globals that this library does not own: they stay with the caller.
 """
 import numpy as np
 
@@ -219,6 +224,124 @@ class ResidentLoader:
                                     d_pool_targets_ptr=self.d_pool_targets, d_targets_out_ptr=self.d_targets, counter=self.calls)
             self.calls += 1
             yield self.d_inputs, self.d_targets, len(idx)
+
+    def close(self):
+        for p in self._owned:
+            self.seg.device_free(p)
+        self._owned = []
+
+
+class _PerClassHistory(dict):
+    """ValidationCallback.per_class_accuracy, {class: [accuracy of every epoch]} (:522-525); calling it measures the accuracies now."""
+
+    def __init__(self, measure):
+        super().__init__()
+        self._measure = measure
+
+    def __call__(self):
+        return self._measure()
+
+
+class ResidentValidation:
+    """What ValidationCallback.evaluate measures at the end of an epoch (visual_recognition_torch.py:493-543), with the samples in HBM and
+    the weights where they are, in the trainer: no export, no second copy of the network, one device-to-host copy of the results.
+
+    val_crops_uint8 (N, 80, 80, C) uint8 + val_targets (N,): the validation images (X_test / Y_test); unique_crops_uint8 (M, 80, 80, C) +
+    frame_ranges (F, 2) = (start, end) rows of it per frame, in frame order: what Accumulation hands calculate_uniqueness (_disc_images,
+    _disc_frame_map, ui/Accumulation.cpp:900-901).  Arrays are uploaded once; like ResidentLoader, device addresses are taken as they
+    are with count= (validation pool, targets then a device address of int32) and unique_count=.  Either part may be missing.
+      per_class_accuracy()      -> float64 [classes], plot_comparison_raw's column 3 (:406-451)
+      estimate_uniqueness()     -> float, the third element of calculate_uniqueness's tuple, as step_calculate_uniqueness returns it
+      on_epoch_end(epoch, logs) appends to per_class_accuracy[i], mean_values, worst_values and uniquenesses as :522-543 does, then
+                                forwards to `callback` (the caller's ValidationCallback with its stop rules), if there is one
+      on_batch_end, stop_training  delegate to `callback`
+    so it can be train_resident()'s callback itself, or its two measurements can be plugged into the caller's own."""
+
+    def __init__(self, trainer, seg, val_crops_uint8, val_targets, unique_crops_uint8=None, frame_ranges=None, count=None, unique_count=None, callback=None):
+        self.trainer, self.seg, self.callback = trainer, seg, callback
+        self.classes, self.channels = trainer.classes, trainer.channels
+        self._owned = []
+        self.d_val, self.n_val = self._pool(val_crops_uint8, count)
+        self.d_val_targets = 0
+        if self.n_val:
+            if isinstance(val_targets, (int, np.integer)):
+                self.d_val_targets = int(val_targets)
+            else:
+                y = np.asarray(val_targets)
+                if y.dtype.kind not in "iu" or y.shape != (self.n_val,):
+                    raise ValueError(f"val_targets must be integer class indices of shape ({self.n_val},), got {y.dtype} {y.shape}")
+                self.d_val_targets = self._alloc(4 * self.n_val)
+                seg.copy_to_device(self.d_val_targets, y.astype(np.int32))
+        self.d_unique, self.n_unique = self._pool(unique_crops_uint8, unique_count)
+        self.frame_ranges = None
+        if self.n_unique:
+            if frame_ranges is None:
+                raise ValueError("the crops of the uniqueness estimate need frame_ranges")
+            self.frame_ranges = np.ascontiguousarray(frame_ranges, np.int32).reshape(-1, 2)
+        self.d_probs = self._alloc(4 * self.classes * max(self.n_val, self.n_unique, 1))
+        self.per_class_accuracy = _PerClassHistory(self._measure_per_class_accuracy)
+        self.mean_values, self.worst_values, self.uniquenesses = [], [], []
+        self.last_validation = self.last_uniqueness = None          # the ValidationMetrics of the last measurement of each kind
+        self._stop = False
+
+    def _alloc(self, nbytes):
+        p = self.seg.device_alloc(nbytes)
+        self._owned.append(p)
+        return p
+
+    def _pool(self, crops, count):
+        if crops is None:
+            return 0, 0
+        if isinstance(crops, (int, np.integer)):
+            if count is None:
+                raise ValueError("a device pool needs its count")
+            return int(crops), int(count)
+        x = np.asarray(crops)
+        if x.dtype != np.uint8 or x.ndim != 4 or tuple(x.shape[1:]) != (80, 80, self.channels):
+            raise ValueError(f"crops must be uint8 (N, 80, 80, {self.channels}), got {x.dtype} {x.shape}")
+        if x.shape[0] == 0:
+            return 0, 0
+        d = self._alloc(x.nbytes)
+        self.seg.copy_to_device(d, x)
+        return d, int(x.shape[0])
+
+    def _measure_per_class_accuracy(self):
+        if not self.n_val:
+            raise ValueError("no validation crops")
+        self.trainer.predict_device(self.d_val, self.n_val, self.d_probs)
+        self.last_validation = self.seg.validation_metrics(self.d_probs, self.n_val, self.classes, d_targets_ptr=self.d_val_targets)
+        return self.last_validation.per_class_accuracy
+
+    def estimate_uniqueness(self):
+        if not self.n_unique:
+            raise ValueError("no crops for the uniqueness estimate")
+        self.trainer.predict_device(self.d_unique, self.n_unique, self.d_probs)
+        self.last_uniqueness = self.seg.validation_metrics(self.d_probs, self.n_unique, self.classes, frame_ranges=self.frame_ranges)
+        return self.last_uniqueness.mean_unique
+
+    def on_batch_end(self, batch, logs):
+        if self.callback is not None:
+            self.callback.on_batch_end(batch, logs)
+
+    def on_epoch_end(self, epoch, logs):
+        if self.n_val:
+            acc = self.per_class_accuracy()
+            for i in range(len(acc)):
+                self.per_class_accuracy.setdefault(i, []).append(acc[i])
+            self.mean_values.append(np.mean(acc))
+            self.worst_values.append(np.min(acc))
+        if self.n_unique:
+            self.uniquenesses.append(self.estimate_uniqueness())
+        if self.callback is not None:
+            self.callback.on_epoch_end(epoch, logs)
+
+    @property
+    def stop_training(self):
+        return self._stop or bool(getattr(self.callback, "stop_training", False))
+
+    @stop_training.setter
+    def stop_training(self, value):
+        self._stop = bool(value)
 
     def close(self):
         for p in self._owned:
