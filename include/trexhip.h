@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 9
+#define TREXHIP_ABI_VERSION 10
 
 enum {
     TREXHIP_OK = 0,
@@ -629,6 +629,32 @@ int trexhip_validation_metrics_device(trexhip_ctx* ctx, const float* d_probs, in
                                       float* unique_percent,               /* HOST [n_frames] (:849), or NULL        */
                                       float* unique_percent_raw,           /* HOST [n_frames] (:840), or NULL        */
                                       float* uniqueness_per_class);        /* HOST [classes]  (:865-870), or NULL    */
+
+/* ------------------------------------------------------------------------------------------------
+ * Average probabilities per individual on rows that are in HBM: VINetwork::paverages (ml/VisualIdentification.h:145-180), which
+ * Accumulation::check_additional_range (ui/Accumulation.cpp:455-641) asks for once per candidate range, and the arg-max scan it runs
+ * over every averaged row (:526-541).  Only n_ids x classes floats leave the device instead of n x classes.
+ *   sum        values[k][c] = float32 sum of d_probs[i][c] over the rows i with d_ids[i] == k in ASCENDING ROW ORDER -- the order of the
+ *              reference's loop (std::transform(..., std::plus<>{}), :159-175) -- then ONE correctly rounded division by float(samples[k])
+ *              (:177-178).  The chain of one (id, class) is never split or re-associated: the result equals the host loop bit for bit.
+ *   samples    samples[k] = the number of rows of k as a float (`float samples; ++samples`, :171); n <= 2^24 keeps it exact
+ *   arg-max    max_p = 0, take index i iff v > max_p (:533-536): the first index wins a tie, a NaN is never taken, a row with nothing
+ *              above 0 gives max_index -1 and max_p 0.  Taken on the device: who wants only the decision copies 8 * n_ids bytes
+ *   d_ids      device [n], dense keys 0..n_ids-1 (the position of the individual's id in the ordered std::map of the reference).  A key
+ *              without rows gets samples 0, all-zero values (no division), max_index -1, max_p 0; the reference's map has no entry then.
+ *              A key outside 0..n_ids-1 is flagged by the device: TREXHIP_E_INVALID, no output is written
+ * Checked before anything is launched (TREXHIP_E_INVALID, nothing runs): 1 <= n <= 2^24, 1 <= classes <= 1024, 1 <= n_ids <= 65536,
+ * d_probs and d_ids not NULL.  d_probs needs no alignment beyond a float's.  Every output pointer is HOST memory and optional.
+ * Ordered on the context's stream; the call synchronises, because it returns host values, with one device-to-host copy.  No
+ * floating-point atomics: two calls on the same input give the same bytes.  The rows of an id are found by one wave per (id, segment of
+ * rows) reading the segment's ids: the work of that stage grows with n_ids x n -- it is made for ids that are individuals. */
+int trexhip_class_averages_device(trexhip_ctx* ctx, const float* d_probs, int32_t n, int32_t classes,
+                                  const int32_t* d_ids,                    /* device [n], dense keys 0..n_ids-1      */
+                                  int32_t n_ids,
+                                  float* samples,                          /* HOST [n_ids], or NULL                  */
+                                  float* averages,                         /* HOST [n_ids][classes], or NULL         */
+                                  int32_t* max_index,                      /* HOST [n_ids], or NULL                  */
+                                  float* max_p);                           /* HOST [n_ids], or NULL                  */
 
 #ifdef __cplusplus
 }

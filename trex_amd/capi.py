@@ -140,6 +140,16 @@ class ValidationMetrics:
             setattr(self, k, None)
 
 
+class ClassAverages:
+    """What Segmenter.class_averages returns, per dense key 0..n_ids-1: samples (float32 [n_ids], the row count as VINetwork::paverages counts
+    it), values (float32 [n_ids][classes], the averaged rows; all zero for a key without rows), and the arg-max scan of
+    Accumulation::check_additional_range over every averaged row: max_index (int32 [n_ids], -1 = nothing above 0) and max_p (float32 [n_ids])."""
+    __slots__ = ("samples", "values", "max_index", "max_p")
+
+    def __init__(self, samples, values, max_index, max_p):
+        self.samples, self.values, self.max_index, self.max_p = samples, values, max_index, max_p
+
+
 SYMBOLS = [
     "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
@@ -148,7 +158,7 @@ SYMBOLS = [
     "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats",
     "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
-    "trexhip_train_predict_device", "trexhip_validation_metrics_device",
+    "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
 ]
 
@@ -245,6 +255,7 @@ def lib():
         L.trexhip_train_predict_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.trexhip_validation_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                         C.POINTER(UniquenessResult), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.trexhip_class_averages_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.trexhip_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.trexhip_device_free.argtypes = [C.c_void_p, C.c_void_p]
         L.trexhip_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -632,6 +643,17 @@ class Segmenter:
             out.good_ratio, out.mean_unique, out.mean_unique_raw = float(res.good_ratio), float(res.mean_unique), float(res.mean_unique_raw)
             out.unique_percent, out.unique_percent_raw, out.uniqueness_per_class = up, upr, upc
         return out
+
+    def class_averages(self, d_probs_ptr, n, classes, d_ids_ptr, n_ids):
+        """VINetwork::paverages of float32 probabilities [n][classes] in HBM with one dense key 0..n_ids-1 per row (int32 [n] on the device):
+        per key the float32 sum of its rows in row order over their number, bit for bit what the host loop gives, and the arg-max of every
+        averaged row (trexhip_class_averages_device; synchronises) -> ClassAverages."""
+        samples, values = np.zeros(max(n_ids, 0), np.float32), np.zeros((max(n_ids, 0), max(classes, 0)), np.float32)
+        max_index, max_p = np.zeros(max(n_ids, 0), np.int32), np.zeros(max(n_ids, 0), np.float32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(lib().trexhip_class_averages_device(self._h, C.c_void_p(d_probs_ptr or 0), n, classes, C.c_void_p(d_ids_ptr or 0), n_ids,
+                                                   ptr(samples), ptr(values), ptr(max_index), ptr(max_p)))
+        return ClassAverages(samples, values, max_index, max_p)
 
     def rethreshold_per_blob(self, d_thresholds_ptr, method=0, size_ranges=(), threshold=0):
         """SplitBlob::apply_threshold building block: one threshold per detect blob (int32 device array, pooled order; <0 skips)."""

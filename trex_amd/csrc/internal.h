@@ -142,6 +142,8 @@ struct trexhip_ctx {
     int aug_idx_cap = 0;
     uint8_t* d_val = nullptr;           // scratch and results of trexhip_validation_metrics_device (validate.hip), grown on demand
     size_t val_cap = 0;
+    uint8_t* d_avg = nullptr;           // scratch and results of trexhip_class_averages_device (averages.hip), grown on demand
+    size_t avg_cap = 0;
     void* d_auto = nullptr;             // scratch of trexhip_posture_auto_device (thresholds, selections, first outlines)
     size_t auto_cap = 0;
     uint32_t* d_bits[2] = {nullptr, nullptr};   // 1 bit/pixel masks for the optional morphology [B][H][ceil(W/32)]

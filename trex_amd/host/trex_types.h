@@ -4,6 +4,7 @@
 // (INTEGRATION.md).  Member names and semantics follow the reference:
 //   cmn::Image             commons misc/Image.h [not in tree]: rows, cols, dims, data()
 //   Frame_t, Range<T>      commons misc/frame_t.h, misc/ranges.h [not in tree]: what Accumulation::calculate_uniqueness takes
+//   track::Idx_t           Application/src/tracker/core/idx_t.h:5-52 (what Accumulation::check_additional_range keys its maps by)
 //   HorizontalLine{y,x0,x1} Application/Tests/test_pixels.cpp:994-995 (ctor order), pv.cpp:505-509
 //   blob::Pair             Application/src/ProcessedVideo/pv.cpp:491-529, Tests/test_matching.cpp:1577
 //   pv::Frame              Application/src/ProcessedVideo/pv.h:114-192 (add_object, set_encoding, n, mask(), pixels())
@@ -224,6 +225,17 @@ inline PipelineManager<TileImage>& pipeline_manager(ObjectDetectionType::Class t
 }  // namespace track::detect
 
 namespace track {
+struct Idx_t {                                           // core/idx_t.h:5-52: default = invalid, explicit from an integer, ordered by its number
+    uint32_t _identity = UINT32_MAX;
+    constexpr Idx_t() = default;
+    explicit constexpr Idx_t(uint32_t id) : _identity(id) {}
+    constexpr uint32_t get() const { return _identity; }
+    constexpr bool valid() const { return _identity != UINT32_MAX; }
+    constexpr bool operator<(const Idx_t& o) const { return _identity < o._identity; }
+    constexpr bool operator==(const Idx_t& o) const { return _identity == o._identity; }
+    constexpr bool operator!=(const Idx_t& o) const { return _identity != o._identity; }
+    constexpr Idx_t operator+(const Idx_t& o) const { return Idx_t(get() + o.get()); }
+};
 struct MidlineSegment {                                  // tracking/Outline.h:241-250
     cmn::Float2_t height = 0, l_length = 0;
     cmn::Vec2 pos;

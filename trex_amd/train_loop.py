@@ -17,6 +17,10 @@ The measurements of the callback can stay there too: ResidentValidation keeps th
 estimate in HBM, predicts them with the weights as they stand in the trainer (trexhip_train_predict_device) and reduces the rows on the
 device (trexhip_validation_metrics_device) to what ValidationCallback.evaluate records per epoch (:510-543): the accuracy of each class
 and estimate_uniqueness().  The stop rules (:545-650) read TRex globals that this library does not own: they stay with the caller.
+
+ResidentAverages does the same for the question accumulation asks per candidate range (Accumulation::check_additional_range ->
+VINetwork::paverages, ml/VisualIdentification.h:145-180): the mean probability row of every individual over its crops, predicted and
+averaged in HBM (trexhip_class_averages_device).  The decision made from it is C++ in the reference and here (host/HipAccumulation.h).
 """
 import numpy as np
 
@@ -342,6 +346,67 @@ class ResidentValidation:
     @stop_training.setter
     def stop_training(self, value):
         self._stop = bool(value)
+
+    def close(self):
+        for p in self._owned:
+            self.seg.device_free(p)
+        self._owned = []
+
+
+class ResidentAverages:
+    """VINetwork::paverages (ml/VisualIdentification.h:145-180) with the crops of a candidate range and their ids in HBM: one prediction, one
+    reduction on the device, one device-to-host copy of individuals x classes floats.
+
+    predict(d_crops, n, d_probs): trainer.predict_device (the weights as they stand in the trainer) or seg.identify_device (the loaded
+    network); classes: the width of its rows (None: the trainer's, or the loaded network's).  crops_uint8 (N, H, W, C) uint8 + ids (N,) integers, any values: they are mapped to dense keys
+    in ascending order, as the reference's std::map orders them, and uploaded once.  Like ResidentValidation, device addresses are taken as
+    they are with count=: crops_uint8 a device address, ids a device address of int32 dense keys 0..n_ids-1, id_values the n_ids ids the
+    keys stand for.
+      averages() -> {id: (samples float32, values float32 [classes])} in id order; an id without rows is absent, as in the reference.
+                    Bit for bit what the host loop gives on the same rows.  The ClassAverages of the call (with max_index / max_p of
+                    check_additional_range's scan, by dense key) stays in last."""
+
+    def __init__(self, predict, seg, crops_uint8, ids, classes=None, count=None, id_values=None):
+        if classes is None:                                  # the trainer knows its classes, the segmenter those of the loaded network
+            owner = getattr(predict, "__self__", None)
+            classes = owner.classes if hasattr(owner, "classes") else seg.num_classes()
+        self.predict, self.seg, self.classes = predict, seg, int(classes)
+        self._owned = []
+        self.last = None
+        if isinstance(crops_uint8, (int, np.integer)):
+            if count is None or id_values is None or not isinstance(ids, (int, np.integer)):
+                raise ValueError("a device pool needs its count, a device address of dense int32 keys and id_values")
+            self.d_crops, self.n, self.d_keys = int(crops_uint8), int(count), int(ids)
+            self.id_values = [int(v) for v in id_values]
+        else:
+            x = np.asarray(crops_uint8)
+            y = np.asarray(ids)
+            if x.dtype != np.uint8 or x.ndim != 4:
+                raise ValueError(f"crops must be uint8 (N, H, W, C), got {x.dtype} {x.shape}")
+            if y.dtype.kind not in "iu" or y.shape != (x.shape[0],):
+                raise ValueError(f"ids must be integers of shape ({x.shape[0]},), got {y.dtype} {y.shape}")
+            values, keys = np.unique(y, return_inverse=True)
+            self.id_values = [int(v) for v in values]
+            self.n = int(x.shape[0])
+            self.d_crops = self.d_keys = 0
+            if self.n:
+                self.d_crops = self._alloc(x.nbytes)
+                seg.copy_to_device(self.d_crops, x)
+                self.d_keys = self._alloc(4 * self.n)
+                seg.copy_to_device(self.d_keys, keys.astype(np.int32))
+        self.d_probs = self._alloc(4 * self.classes * max(self.n, 1))
+
+    def _alloc(self, nbytes):
+        p = self.seg.device_alloc(nbytes)
+        self._owned.append(p)
+        return p
+
+    def averages(self):
+        if not self.n:
+            return {}
+        self.predict(self.d_crops, self.n, self.d_probs)
+        self.last = self.seg.class_averages(self.d_probs, self.n, self.classes, self.d_keys, len(self.id_values))
+        return {v: (self.last.samples[k], self.last.values[k]) for k, v in enumerate(self.id_values) if self.last.samples[k] > 0}
 
     def close(self):
         for p in self._owned:
