@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 10
+#define TREXHIP_ABI_VERSION 11
 
 enum {
     TREXHIP_OK = 0,
@@ -36,6 +36,7 @@ enum {
 /* per-frame status bits in trexhip_frame_info.flags */
 #define TREXHIP_FRAME_OVERFLOW_RUNS   1u
 #define TREXHIP_FRAME_OVERFLOW_OUTPUT 2u
+#define TREXHIP_FRAME_MALFORMED       4u   /* trexhip_load_frames_v6_device: the frame's stored body breaks the V_6 layout; it holds no blobs */
 
 /* Settings the hot path reads (names = TRex setting names). */
 typedef struct trexhip_params {
@@ -221,6 +222,24 @@ int trexhip_synchronize(trexhip_ctx* ctx);
  * Compression and the index table: trexhip_pv_write_frames below (host side); the file header (pv.cpp:842-990) is not produced. */
 int trexhip_pack_frames_v6_device(trexhip_ctx* ctx, const uint64_t* timestamps, uint8_t* d_out, size_t capacity, uint64_t* d_offsets);
 
+/* The inverse: pv::Frame::read_from (ProcessedVideo/pv.cpp:296-420, version V_6: u64 timestamp :347-351, LegacyShortHorizontalLine
+ * masks :377-388, pixels :399-403) for a batch of stored frames, on the device.  Tracking runs on frames read back from the file
+ * (Tracker::prefilter, posture, FilterCache, SplitBlob, the identity network): behind this call and trexhip_fetch the context holds the
+ * tables it would hold behind trexhip_segment_device and trexhip_fetch on the frames the file was converted from, and every track-stage
+ * call (re-threshold, split search, posture, midline, crops, id table) runs on them unchanged.
+ *   d_bodies / d_offsets   what trexhip_pack_frames_v6_device writes (or trexhip_pv_read_frames returns, uploaded): uncompressed bodies
+ *                          back to back, each starting with its flag byte 0; d_offsets [n_frames + 1].  1 <= n_frames <= max_batch
+ *   d_timestamps           device [n_frames] or NULL: receives every frame's timestamp
+ * Frames are pooled in frame order, blobs keep file order, every field of trexhip_blob is what the detect stage computes for the same
+ * blob.  The grey values the track stage reads come from a frame image owned by the context into which the call paints every blob's
+ * stored pixels; they are final (the segmenter stored 255 - p under image_invert), so the batch is not inverted again downstream.
+ * A frame beyond max_blobs / max_runs / max_pixels gets the overflow flags of a segmented frame; a frame whose bytes break the layout
+ * (the rules: trex_amd/csrc/pv_read.h; no read passes d_offsets[f + 1] whatever the bytes say) gets TREXHIP_FRAME_MALFORMED, keeps no
+ * blob, and trexhip_fetch returns TREXHIP_E_INVALID ("malformed") for the batch; the other frames are unaffected either way.
+ * Gray pixel arrays, width <= 32768, max_blobs <= 65535 (TREXHIP_E_UNSUPPORTED otherwise, as the packer).  Only enqueues work on the
+ * context's stream: no host synchronisation. */
+int trexhip_load_frames_v6_device(trexhip_ctx* ctx, const uint8_t* d_bodies, const uint64_t* d_offsets, int32_t n_frames, uint64_t* d_timestamps);
+
 /* ---- .pv data section: per-frame LZO1X compression + index table (host side, no GPU needed) -------
  * trexhip_pv_write_frames = the tail of pv::Frame::serialize (pv.cpp:705-772: a pack of >= 15000 bytes -- every pack when
  * always_compress, which is what the rgb8 encoding does -- goes through LZO1X-1 and is kept compressed if 8 + compressed < uncompressed)
@@ -238,6 +257,18 @@ size_t trexhip_lzo1x_bound(size_t n);            /* pv.cpp:712 OUT_LEN: n + n / 
 int trexhip_lzo1x_compress(const uint8_t* in, size_t n, uint8_t* out, size_t capacity, size_t* out_len);
 int trexhip_pv_write_frames(const uint8_t* bodies, const uint64_t* offsets, int32_t n_frames, int32_t always_compress, uint64_t file_offset,
                             uint8_t* out, size_t capacity, uint64_t* index_table, size_t* out_bytes);
+/* Reading it back.  trexhip_lzo1x_decompress = lzo1x_decompress as pv::Frame::read_from calls it (pv.cpp:326-333; decoder
+ * ProcessedVideo/lzo/minilzo.c): this library's own decoder, which checks both buffers on every copy -- a truncated or overlong stream,
+ * or an output beyond `capacity`, is TREXHIP_E_INVALID, never an access outside either buffer.
+ * trexhip_pv_read_frames = the head of pv::Frame::read_from (pv.cpp:313-340) for n_frames frames of a data section: frame f starts at
+ * data[index_table[f] - file_offset]; flag 0: the pack is copied (its extent is the chain of its blob sizes, bounded by `bytes`);
+ * flag 1: u32 compressed size, u32 uncompressed size, the stream is decompressed and given a leading flag byte 0.  bodies / offsets
+ * [n_frames + 1] are then what trexhip_load_frames_v6_device takes.  Everything is bounded by `bytes` and `capacity`
+ * (TREXHIP_E_INVALID beyond either; *out_bytes = bytes written).  bodies == NULL asks for the sizes only: offsets and *out_bytes are
+ * filled, nothing is decompressed. */
+int trexhip_lzo1x_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t capacity, size_t* out_len);
+int trexhip_pv_read_frames(const uint8_t* data, size_t bytes, uint64_t file_offset, const uint64_t* index_table, int32_t n_frames,
+                           uint8_t* bodies, size_t capacity, uint64_t* offsets, size_t* out_bytes);
 
 /* ---- track-stage re-threshold -----------------------------------------------------------------
  * Tracker::prefilter's arithmetic (tracking/Tracker.cpp:765-849): for every kept blob of the last segmented

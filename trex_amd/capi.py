@@ -90,6 +90,7 @@ class BatchResult(C.Structure):
 
 
 ENC_GRAY, ENC_R3G3B2, ENC_RGB8 = 0, 1, 2        # pixel_encoding, order of cmn::meta_encoding_t
+FRAME_OVERFLOW_RUNS, FRAME_OVERFLOW_OUTPUT, FRAME_MALFORMED = 1, 2, 4       # trexhip_frame_info.flags
 
 
 class DeviceView(C.Structure):
@@ -101,6 +102,7 @@ class TrexHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libtrexhip error {code}: {msg}")
         self.code = code
+        self.frames = None            # Segmenter.fetch on a loaded batch with a malformed frame: the per-frame results all the same
 
 
 # every symbol include/trexhip.h declares (tests check the library exports all of them)
@@ -160,6 +162,7 @@ SYMBOLS = [
     "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
+    "trexhip_load_frames_v6_device", "trexhip_lzo1x_decompress", "trexhip_pv_read_frames",
 ]
 
 
@@ -221,6 +224,9 @@ def lib():
         L.trexhip_lzo1x_bound.argtypes = [C.c_size_t]; L.trexhip_lzo1x_bound.restype = C.c_size_t
         L.trexhip_lzo1x_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.trexhip_pv_write_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+        L.trexhip_load_frames_v6_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.trexhip_lzo1x_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.trexhip_pv_read_frames.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
         L.trexhip_comm_unique_id.argtypes = [C.c_void_p]
         L.trexhip_comm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.trexhip_comm_destroy.argtypes = [C.c_void_p]
@@ -442,7 +448,8 @@ class Segmenter:
     def fetch(self, copy=True, rethreshold=False):
         r = BatchResult()
         rc = (lib().trexhip_fetch_rethreshold if rethreshold else lib().trexhip_fetch)(self._h, C.byref(r))
-        if rc != 0 and rc != -3:
+        malformed = rc == -1 and r.n_frames > 0 and bool((_from_addr(r.frames, r.n_frames, INFO_DTYPE)["flags"] & FRAME_MALFORMED).any())
+        if rc != 0 and rc != -3 and not malformed:
             _check(rc)
         info = _from_addr(r.frames, r.n_frames, INFO_DTYPE)
         blobs = _from_addr(r.blobs, r.total_blobs, BLOB_DTYPE)
@@ -461,6 +468,10 @@ class Segmenter:
             if copy:
                 b, ru, px = b.copy(), ru.copy(), px.copy()
             out.append(FrameResult(fi.copy(), b, ru, px))
+        if malformed:                                        # a stored frame broke the V_6 layout: raised, with the other frames' tables attached
+            e = TrexHipError(rc, lib().trexhip_last_error().decode())
+            e.frames = out
+            raise e
         if rc == -3:
             self.last_capacity_error = lib().trexhip_last_error().decode()
         return out
@@ -488,6 +499,11 @@ class Segmenter:
         """pv::Frame::serialize bodies (file version V_6 layout) of the last fetched batch; see include/trexhip.h."""
         ts = np.ascontiguousarray(timestamps, np.uint64) if timestamps is not None else None
         _check(lib().trexhip_pack_frames_v6_device(self._h, ts.ctypes.data if ts is not None else None, C.c_void_p(d_out_ptr), capacity, C.c_void_p(d_offsets_ptr)))
+
+    def load_frames_v6_device(self, d_bodies_ptr, d_offsets_ptr, n, d_timestamps_ptr=0):
+        """pv::Frame::read_from for n stored V_6 frame bodies in HBM (what pack_frames_v6_device wrote): afterwards fetch() and every
+        track-stage call work as behind segment_device; d_timestamps_ptr: device uint64 [n] or 0; see include/trexhip.h."""
+        _check(lib().trexhip_load_frames_v6_device(self._h, C.c_void_p(d_bodies_ptr or 0), C.c_void_p(d_offsets_ptr or 0), n, C.c_void_p(d_timestamps_ptr or 0)))
 
     def crops_device(self, d_crops_ptr, n_blobs, out_w=80, out_h=80, normalization=0, difference=0):
         """constraints::diff_image for every blob of the last batch -> uint8 [n_blobs][out_h][out_w] at d_crops_ptr."""
@@ -825,3 +841,28 @@ def pv_write_frames(bodies, offsets, always_compress=False, file_offset=0):
     _check(lib().trexhip_pv_write_frames(b.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.c_void_p), n, 1 if always_compress else 0, file_offset,
                                          out.ctypes.data_as(C.c_void_p), len(out), idx.ctypes.data_as(C.c_void_p), C.byref(used)))
     return out[:used.value].copy(), idx
+
+
+def lzo1x_decompress(data, out_len):
+    """this library's bounds-checked LZO1X decoder (host code): the stream -> out_len bytes; raises on a truncated / overlong stream or when the
+    output does not fit out_len; see include/trexhip.h"""
+    src = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
+    out = np.empty(max(1, out_len), np.uint8)
+    n = C.c_size_t()
+    _check(lib().trexhip_lzo1x_decompress(src.ctypes.data_as(C.c_void_p), len(src), out.ctypes.data_as(C.c_void_p), out_len, C.byref(n)))
+    return out[:n.value].copy()
+
+
+def pv_read_frames(data, index_table, file_offset=0):
+    """inverse of pv_write_frames: .pv data section + index table -> (bodies, offsets [n + 1] u64), every body uncompressed with its flag byte 0:
+    what Segmenter.load_frames_v6_device takes once uploaded; see include/trexhip.h"""
+    d = np.ascontiguousarray(data, np.uint8)
+    idx = np.ascontiguousarray(index_table, np.uint64)
+    n = len(idx)
+    off = np.zeros(n + 1, np.uint64)
+    used = C.c_size_t()
+    args = (d.ctypes.data_as(C.c_void_p), len(d), file_offset, idx.ctypes.data_as(C.c_void_p), n)
+    _check(lib().trexhip_pv_read_frames(*args, None, 0, off.ctypes.data_as(C.c_void_p), C.byref(used)))      # sizes first
+    out = np.empty(max(1, used.value), np.uint8)
+    _check(lib().trexhip_pv_read_frames(*args, out.ctypes.data_as(C.c_void_p), used.value, off.ctypes.data_as(C.c_void_p), C.byref(used)))
+    return out[:used.value].copy(), off

@@ -145,6 +145,7 @@ struct trexhip_ctx {
     uint8_t* d_avg = nullptr;           // scratch and results of trexhip_class_averages_device (averages.hip), grown on demand
     size_t avg_cap = 0;
     void* d_auto = nullptr;             // scratch of trexhip_posture_auto_device (thresholds, selections, first outlines)
+    void* d_load = nullptr;             // blob index and frame counts of trexhip_load_frames_v6_device (unpack.hip), allocated on its first call
     size_t auto_cap = 0;
     uint32_t* d_bits[2] = {nullptr, nullptr};   // 1 bit/pixel masks for the optional morphology [B][H][ceil(W/32)]
     uint8_t* d_color = nullptr;         // BGR/BGRA frames of the colour-input API

@@ -5,7 +5,8 @@
 //                                   encoding -- go through lzo1x_1_compress and are kept compressed when that is smaller)
 //   pv::File::add_individual        pv.cpp:1488-1496  (u8 compression_flag, then the pack; the frame's file offset goes to the index table)
 //   pv::Header::update              pv.cpp:1181-1192  (the index table: one u64 file offset per frame)
-// and is read back by pv::Frame::read_from (pv.cpp:313-340: u8 flag, u32 compressed size, u32 uncompressed size, lzo1x_decompress).
+// and is read back by pv::Frame::read_from (pv.cpp:313-340: u8 flag, u32 compressed size, u32 uncompressed size, lzo1x_decompress), whose
+// part up to the uncompressed pack is trexhip_pv_read_frames below, with this library's own bounds-checked LZO1X decoder.
 //
 // The compressor below is this library's own: a greedy hash-chain-free LZ77 matcher writing the LZO1X bit stream (literal runs, M2 / M3 / M4
 // matches, end marker) that lzo1x_decompress accepts.  It does not reproduce minilzo's lzo1x_1_compress byte for byte and does not have to:
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 #include "../../include/trexhip.h"
+#include "pv_read.h"
 
 namespace trexhip { void set_error(const std::string& msg); }
 
@@ -107,6 +109,91 @@ size_t lzo1x_compress(const uint8_t* in, size_t n, uint8_t* out) {
     return (size_t)(op - out);
 }
 
+// LZO1X stream -> bytes.  Every copy is checked against both buffers first; false: the stream is cut short, goes on behind its end marker,
+// points in front of the output, or the output does not fit.  Instructions by their first byte t (S = low two bits of the byte in front
+// of the distance's high part: 0..3 literals follow the match):
+//   t < 16    after a match without trailing literals: a run of t + 3 literals (t = 0: 18 + 255 per zero byte + the next byte);
+//             right after such a run: a 3-byte match at distance (t >> 2) + (next << 2) + 2049;
+//             after 1..3 trailing literals: a 2-byte match at distance (t >> 2) + (next << 2) + 1
+//   16..31    M4: length (t & 7) + 2 (0: 9 + ...), distance 16384 + ((t & 8) << 11) + (u16 >> 2); distance 16384 ends the stream
+//   32..63    M3: length (t & 31) + 2 (0: 33 + ...), distance (u16 >> 2) + 1
+//   64..255   M2: length (t >> 5) + 1, distance ((t >> 2) & 7) + (next << 3) + 1
+// A first byte above 17 opens the stream with t - 17 literals.
+bool lzo1x_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t capacity, size_t* out_len) {
+    size_t ip = 0, op = 0;
+    enum { AFTER_MATCH = 0, AFTER_RUN = 4 };                       // 1..3: that many literals trailed the last match
+    int state = AFTER_MATCH;
+    auto literals = [&](size_t t) -> bool {
+        if (n - ip < t || capacity - op < t) return false;
+        memcpy(out + op, in + ip, t);
+        ip += t; op += t;
+        return true;
+    };
+    // a length that did not fit its instruction byte: 255 per zero byte, then the byte that ends it
+    auto long_length = [&](size_t base, size_t* len) -> bool {
+        size_t t = 0;
+        for (;;) {
+            if (ip >= n) return false;
+            const uint8_t b = in[ip++];
+            if (b) { *len = t + base + b; return true; }
+            t += 255;
+            if (t > ((size_t)1 << 40)) return false;
+        }
+    };
+    if (n == 0) return false;
+    if (in[0] > 17) {
+        const size_t t = (size_t)in[ip++] - 17;
+        if (!literals(t)) return false;
+        state = t < 4 ? (int)t : AFTER_RUN;
+    }
+    for (;;) {
+        if (ip >= n) return false;
+        const uint32_t t = in[ip++];
+        size_t len, dist;
+        uint32_t trail;
+        if (t < 16) {
+            if (state == AFTER_MATCH) {
+                size_t run = t + 3;
+                if (t == 0 && !long_length(18, &run)) return false;
+                if (!literals(run)) return false;
+                state = AFTER_RUN;
+                continue;
+            }
+            if (ip >= n) return false;
+            dist = (t >> 2) + ((size_t)in[ip++] << 2) + (state == AFTER_RUN ? 2049 : 1);
+            len = state == AFTER_RUN ? 3 : 2;
+            trail = t & 3;
+        } else if (t >= 64) {
+            if (ip >= n) return false;
+            len = (t >> 5) + 1;
+            dist = ((t >> 2) & 7) + ((size_t)in[ip++] << 3) + 1;
+            trail = t & 3;
+        } else {
+            const bool m3 = t >= 32;
+            len = (t & (m3 ? 31u : 7u)) + 2;
+            if (len == 2 && !long_length(m3 ? 33 : 9, &len)) return false;
+            if (n - ip < 2) return false;
+            const uint32_t d = (uint32_t)in[ip] | ((uint32_t)in[ip + 1] << 8);
+            ip += 2;
+            trail = d & 3;
+            if (m3) dist = (d >> 2) + 1;
+            else {
+                dist = 16384 + ((size_t)(t & 8) << 11) + (d >> 2);
+                if (dist == 16384) {                               // end marker: nothing may follow it
+                    if (ip != n) return false;
+                    *out_len = op;
+                    return true;
+                }
+            }
+        }
+        if (dist > op || capacity - op < len) return false;
+        for (size_t k = 0; k < len; ++k) out[op + k] = out[op - dist + k];      // byte by byte: an overlapping match repeats itself
+        op += len;
+        if (!literals(trail)) return false;
+        state = (int)trail;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -152,6 +239,54 @@ int trexhip_pv_write_frames(const uint8_t* bodies, const uint64_t* offsets, int3
             o += total;
         }
     }
+    *out_bytes = o;
+    return TREXHIP_OK;
+}
+
+int trexhip_lzo1x_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t capacity, size_t* out_len) {
+    if (!in || (!out && capacity) || !out_len) { trexhip::set_error("trexhip_lzo1x_decompress: null argument"); return TREXHIP_E_INVALID; }
+    if (!lzo1x_decompress(in, n, out, capacity, out_len)) {
+        trexhip::set_error("trexhip_lzo1x_decompress: the stream is truncated, overlong or malformed, or the output buffer is too small");
+        return TREXHIP_E_INVALID;
+    }
+    return TREXHIP_OK;
+}
+
+int trexhip_pv_read_frames(const uint8_t* data, size_t bytes, uint64_t file_offset, const uint64_t* index_table, int32_t n_frames,
+                           uint8_t* bodies, size_t capacity, uint64_t* offsets, size_t* out_bytes) {
+    if (!data || !index_table || !offsets || !out_bytes || n_frames < 0) { trexhip::set_error("trexhip_pv_read_frames: bad argument"); return TREXHIP_E_INVALID; }
+    size_t o = 0;
+    for (int32_t f = 0; f < n_frames; ++f) {
+        offsets[f] = o;
+        if (index_table[f] < file_offset || index_table[f] - file_offset >= bytes) { trexhip::set_error("trexhip_pv_read_frames: an index entry points outside the data"); return TREXHIP_E_INVALID; }
+        const size_t at = (size_t)(index_table[f] - file_offset);
+        const uint8_t* p = data + at;
+        const size_t avail = bytes - at;
+        if (p[0] == 0) {                                                     // pv.cpp:313-316: the pack follows as it is
+            uint64_t len = 0;
+            if (!trexhip::pvr::frame_extent(p, avail, &len)) { trexhip::set_error("trexhip_pv_read_frames: an uncompressed frame leaves the data"); return TREXHIP_E_INVALID; }
+            if (bodies) {
+                if (capacity - o < len) { trexhip::set_error("trexhip_pv_read_frames: output buffer too small"); return TREXHIP_E_INVALID; }
+                memcpy(bodies + o, p, (size_t)len);
+            }
+            o += (size_t)len;
+        } else if (p[0] == 1) {                                              // pv.cpp:317-340
+            if (avail < 9) { trexhip::set_error("trexhip_pv_read_frames: a compressed frame's sizes leave the data"); return TREXHIP_E_INVALID; }
+            uint32_t csize, usize;
+            memcpy(&csize, p + 1, 4); memcpy(&usize, p + 5, 4);
+            if (avail - 9 < csize) { trexhip::set_error("trexhip_pv_read_frames: a compressed frame leaves the data"); return TREXHIP_E_INVALID; }
+            if (bodies) {
+                if (capacity - o < (size_t)usize + 1) { trexhip::set_error("trexhip_pv_read_frames: output buffer too small"); return TREXHIP_E_INVALID; }
+                bodies[o] = 0;                                               // the loader's bodies all start with flag 0
+                size_t got = 0;
+                if (!lzo1x_decompress(p + 9, csize, bodies + o + 1, usize, &got) || got != usize) {
+                    trexhip::set_error("trexhip_pv_read_frames: a compressed frame does not decompress to the size it states"); return TREXHIP_E_INVALID;
+                }
+            }
+            o += (size_t)usize + 1;
+        } else { trexhip::set_error("trexhip_pv_read_frames: a frame starts with a compression_flag other than 0 or 1"); return TREXHIP_E_INVALID; }
+    }
+    offsets[n_frames] = o;
     *out_bytes = o;
     return TREXHIP_OK;
 }
