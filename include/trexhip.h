@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 11
+#define TREXHIP_ABI_VERSION 12
 
 enum {
     TREXHIP_OK = 0,
@@ -285,6 +285,77 @@ int trexhip_rethreshold_device(trexhip_ctx* ctx, int32_t threshold, int32_t meth
 int trexhip_rethreshold_per_blob_device(trexhip_ctx* ctx, int32_t threshold, const int32_t* d_blob_thresholds, int32_t method,
                                         const double* size_ranges, int32_t n_ranges);
 int trexhip_fetch_rethreshold(trexhip_ctx* ctx, trexhip_batch_result* out);
+
+/* ---- Tracker::prefilter's blob policy ---------------------------------------------------------------------
+ * The decisions of Tracker::prefilter (tracking/Tracker.cpp:742-914) for every frame of the last fetched batch (segmented or loaded), on
+ * the device: the call runs the re-threshold of trexhip_rethreshold_device at track_threshold (the same code path; the context's second
+ * table set holds its result afterwards and trexhip_fetch_rethreshold / posture table 1 read it as usual) and then walks the reference's
+ * loop (:806-914) per detect blob:
+ *   1. check_blob(own, false): rect_overlaps_shapes(bounds, track_include) and track_ignore_bdx (:786-801);
+ *   2. the gate of :828-831 -- no track_size_filter or close_to_minimum_of_one(recount, 0.5), and track_threshold > 0 -- decides whether
+ *      the blob's sub-blobs stand for it;
+ *   3. each sub-blob through check_precise_not_ignored on its centre: track_ignore, track_include, bdx of itself or its parent (:742-763);
+ *   4. the un-thresholded blob instead when the gate was closed or nothing survived the threshold (:853-858), through the same check;
+ *   5. per surviving entry in_range_of_one(recount) -> the second-threshold test (:865-874) -> committed; else OutsideRange below
+ *      max_range().start; else big.
+ * cm_per_pixel is the context's live value.  Ordered on the context's stream, no host synchronisation.
+ * Entries, with cap = max_batch * max_blobs: e = f * max_blobs + k is sub-blob k of frame f of the second table set (pooled index
+ * frames[f].blob_begin + k of trexhip_fetch_rethreshold), e = cap + f * max_blobs + k is detect blob k of frame f (pooled index
+ * frames[f].blob_begin + k of trexhip_fetch) standing un-thresholded or filtered by step 1.  Entries are numbered by frame and not by
+ * pooled index because both table sets pool their frames in the order the frames finish, which differs from call to call: numbered this
+ * way d_decision, d_order and d_counts (and d_second_count) of two calls on the same frames are the same bytes, whether the batch was
+ * segmented or loaded.
+ *   d_decision   [2 * cap] bytes, one per entry: TREXHIP_DECISION_COMMITTED, TREXHIP_DECISION_BIG, TREXHIP_DECISION_FILTERED + reason,
+ *                or TREXHIP_DECISION_NONE (not an entry: beyond the tables, a sub-blob whose parent stands for itself or was filtered,
+ *                a detect blob whose sub-blobs stand for it)
+ *   d_order      [n_frames][2 * max_blobs] int32: per frame the committed entries, then the big entries, each in the order the reference's
+ *                loop appends them (detect blob order, table order of the sub-blobs inside one detect blob); -1 behind them
+ *   d_counts     [n_frames][4] int32: committed, big, filtered out, and 1 when the frame decided nothing
+ *   d_presumed_nr[total detect blobs] int32, by POOLED index of the detect table: 2 for the detect blob a big entry belongs to
+ *                (split_expectation(2, false), PrefilterBlobs.cpp:223), else 0: what trexhip_split_search_device takes
+ * A frame flagged overflow or malformed (in either table set) keeps its flags, decides nothing (d_counts[f][3] = 1, its decision bytes
+ * stay TREXHIP_DECISION_NONE) and leaves the other frames alone.
+ * Refused: more than 8 size ranges, more than 64 shapes or 4096 points in a list (TREXHIP_E_UNSUPPORTED); thresholds outside 0..255, a
+ * batch that was not fetched (TREXHIP_E_INVALID); a frame whose detect blobs together with the shape tables exceed the 160 KB of LDS of
+ * one workgroup -- about 9000 blobs in a frame with full shape tables, 13000 without -- (TREXHIP_E_CAPACITY).
+ * Not on this path: tags, instance segmentations, categories, classes and prediction confidence (Tracker.cpp:776-784, :876-904) belong
+ * to the YOLO / categorisation backends; there is no field for them.
+ * UNPINNED (the reference calls into the un-vendored commons; each is implemented from its documented meaning):
+ *   pnpoly                   W. R. Franklin's crossing test in float, edges (j, i) with j = i - 1 cyclic
+ *   Bounds::contains         x <= px < x + width and y <= py < y + height
+ *   Bounds::overlaps         open intersection: a.x < b.x + b.width, b.x < a.x + a.width, and the same in y
+ *   Bounds::insert_point     x, y = minimum, width, height = maximum; PrefilterBlobs.cpp:364 starts the polygon's box at
+ *                            (0, 0, FLT_MAX, FLT_MAX), so as written it reaches from min(0, points) to FLT_MAX: kept as written
+ *   Blob::bounds / center    pos = (x0, y0), size = (x1 - x0 + 1, y1 - y0 + 1), center = pos + size * 0.5
+ *   recount                  surviving pixels * cm^2 in float (as trexhip_rethreshold_device); force_set_recount(threshold) at :771 =
+ *                            all pixels of the blob * cm^2 without a pixel pass
+ *   Range<float>::contains   [start, end), as Range<double> in the size filters
+ *   pv::FilterReason         its numbering is not in the tree: TREXHIP_FILTER_* below is this library's own */
+enum { TREXHIP_FILTER_OUTSIDE_INCLUDE = 0, TREXHIP_FILTER_INSIDE_IGNORE = 1, TREXHIP_FILTER_BDX_IGNORED = 2, TREXHIP_FILTER_OUTSIDE_RANGE = 3,
+       TREXHIP_FILTER_SECOND_THRESHOLD = 4 };
+enum { TREXHIP_DECISION_COMMITTED = 0, TREXHIP_DECISION_BIG = 1, TREXHIP_DECISION_FILTERED = 16, TREXHIP_DECISION_NONE = 255 };
+typedef struct trexhip_prefilter_params {
+    int32_t track_threshold;            /* core/default_config.cpp:937; 0 = nothing is thresholded (:830)                          */
+    int32_t method;                     /* difference, as trexhip_rethreshold_device: 0 |bg - p|, 1 max(bg - p, 0), 2 p            */
+    int32_t track_threshold_2;          /* :939; 0 = off                                                                          */
+    int32_t n_ranges;                   /* track_size_filter, at most 8 ranges                                                    */
+    float   threshold_ratio_range[2];   /* :938 (0.5, 1.0)                                                                        */
+    double  size_ranges[16];            /* [start, end) pairs in cm^2                                                             */
+} trexhip_prefilter_params;
+/* track_include / track_ignore: device float2 points of all shapes back to back and device offsets [n_shapes + 1] into them; a shape of
+ * 2 points is a rectangle (corner, opposite corner), of more than 2 a polygon, of fewer nothing (PrefilterBlobs.cpp:328-385).
+ * track_ignore_bdx: per frame of the batch a sorted list of pv::bid words, d_ignore_bdx_offsets [n_frames + 1]; NULL = none.
+ * d_second_count: optional OUTPUT, device [2 * cap] int32 indexed like d_decision: the pixels at track_threshold_2 of every entry that
+ * reached the size test in range, -1 elsewhere (and everywhere with track_threshold_2 == 0). */
+typedef struct trexhip_prefilter_tables {
+    const float*    d_include_points;  const int32_t* d_include_offsets;  int32_t n_include_shapes, n_include_points;
+    const float*    d_ignore_points;   const int32_t* d_ignore_offsets;   int32_t n_ignore_shapes, n_ignore_points;
+    const uint32_t* d_ignore_bdx;      const int32_t* d_ignore_bdx_offsets;  int32_t n_ignore_bdx, reserved_;
+    int32_t*        d_second_count;
+} trexhip_prefilter_tables;
+void trexhip_default_prefilter_params(trexhip_prefilter_params* p);
+int trexhip_prefilter_device(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const trexhip_prefilter_tables* tables /* NULL = none */,
+                             uint8_t* d_decision, int32_t* d_order, int32_t* d_counts, int32_t* d_presumed_nr);
 
 /* ---- splitting merged blobs: SplitBlob's threshold search -----------------------------------------------
  * SplitBlob::split (tracking/SplitBlob.cpp:419-800) for blob_split_algorithm threshold / threshold_approximate: for every detect blob

@@ -72,6 +72,22 @@ class SplitParams(C.Structure):
                 ("size_ranges", C.c_double * 16)]
 
 
+class PrefilterParams(C.Structure):
+    _fields_ = [("track_threshold", C.c_int32), ("method", C.c_int32), ("track_threshold_2", C.c_int32), ("n_ranges", C.c_int32),
+                ("threshold_ratio_range", C.c_float * 2), ("size_ranges", C.c_double * 16)]
+
+
+class PrefilterTables(C.Structure):
+    _fields_ = [("d_include_points", C.c_void_p), ("d_include_offsets", C.c_void_p), ("n_include_shapes", C.c_int32), ("n_include_points", C.c_int32),
+                ("d_ignore_points", C.c_void_p), ("d_ignore_offsets", C.c_void_p), ("n_ignore_shapes", C.c_int32), ("n_ignore_points", C.c_int32),
+                ("d_ignore_bdx", C.c_void_p), ("d_ignore_bdx_offsets", C.c_void_p), ("n_ignore_bdx", C.c_int32), ("reserved_", C.c_int32),
+                ("d_second_count", C.c_void_p)]
+
+
+# trexhip_prefilter_device: d_decision values and the library's numbering of pv::FilterReason
+DECISION_COMMITTED, DECISION_BIG, DECISION_FILTERED, DECISION_NONE = 0, 1, 16, 255
+FILTER_OUTSIDE_INCLUDE, FILTER_INSIDE_IGNORE, FILTER_BDX_IGNORED, FILTER_OUTSIDE_RANGE, FILTER_SECOND_THRESHOLD = 0, 1, 2, 3, 4
+
 SPLIT_INFO_DTYPE = np.dtype([("threshold", "<i4"), ("effective_threshold", "<i4"), ("status", "<i4"), ("initial_action", "<i4"), ("n_result", "<i4"),
                              ("n_evaluated", "<i4"), ("min_pixel", "<i4"), ("max_pixel", "<i4"), ("first_size", "<f4"), ("reserved_", "<f4"),
                              ("min_size_bound", "<f8")])
@@ -163,6 +179,7 @@ SYMBOLS = [
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
     "trexhip_load_frames_v6_device", "trexhip_lzo1x_decompress", "trexhip_pv_read_frames",
+    "trexhip_default_prefilter_params", "trexhip_prefilter_device",
 ]
 
 
@@ -266,6 +283,9 @@ def lib():
         L.trexhip_device_free.argtypes = [C.c_void_p, C.c_void_p]
         L.trexhip_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.trexhip_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.trexhip_default_prefilter_params.argtypes = [C.POINTER(PrefilterParams)]
+        L.trexhip_default_prefilter_params.restype = None
+        L.trexhip_prefilter_device.argtypes = [C.c_void_p, C.POINTER(PrefilterParams), C.POINTER(PrefilterTables), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -866,3 +886,122 @@ def pv_read_frames(data, index_table, file_offset=0):
     out = np.empty(max(1, used.value), np.uint8)
     _check(lib().trexhip_pv_read_frames(*args, out.ctypes.data_as(C.c_void_p), used.value, off.ctypes.data_as(C.c_void_p), C.byref(used)))
     return out[:used.value].copy(), off
+
+
+class PrefilterResult:
+    """Host copies of what trexhip_prefilter_device wrote: decision (uint8 [2 * cap]), order (int32 [n_frames][2 * max_blobs]), counts (int32
+    [n_frames][4]), presumed_nr (int32 [total detect blobs]) and, when asked for, second_count (int32 [2 * cap]); cap = max_batch * max_blobs.  Entry f * max_blobs + k is sub-blob k of frame f,
+    entry cap + f * max_blobs + k its detect blob k; presumed_nr alone is in pooled order of the detect table."""
+    __slots__ = ("decision", "order", "counts", "presumed_nr", "second_count", "cap")
+
+    def __init__(self, decision, order, counts, presumed_nr, second_count, cap):
+        self.decision, self.order, self.counts, self.presumed_nr, self.second_count, self.cap = decision, order, counts, presumed_nr, second_count, cap
+
+
+class Prefilter:
+    """Tracker::prefilter's blob policy on the last fetched batch of a Segmenter (trexhip_prefilter_device).  Packs track_include /
+    track_ignore (lists of shapes, a shape = list of (x, y) points: 2 = rectangle, more = polygon) and track_ignore_bdx (per frame of the
+    batch an iterable of pv::bid words, or None) into the device tables, owns the output buffers (device memory of the context) and keeps
+    them until close().  d_presumed_nr is what Segmenter.split_search_device takes."""
+
+    def __init__(self, seg, n_frames, total_blobs):
+        self.seg, self.n_frames, self.total_blobs = seg, int(n_frames), int(total_blobs)
+        self.cap = int(seg.params.max_batch) * int(seg.params.max_blobs)
+        self.per_frame = 2 * int(seg.params.max_blobs)
+        self._bufs = []
+        self.d_decision = self._alloc(2 * self.cap)
+        self.d_order = self._alloc(4 * self.n_frames * self.per_frame)
+        self.d_counts = self._alloc(16 * self.n_frames)
+        self.d_presumed_nr = self._alloc(4 * max(self.total_blobs, 1))
+        self.d_second_count = None
+        self._tables = []                                      # device tables of the last run(): freed by the next run() and by close()
+        self._want_second = False
+
+    def _alloc(self, nbytes):
+        p = C.c_void_p()
+        _check(lib().trexhip_device_alloc(self.seg._h, max(int(nbytes), 4), C.byref(p)))
+        self._bufs.append(p)
+        return p.value
+
+    def _free_tables(self):
+        if self._tables:
+            self.seg.synchronize()                             # the last run may still read them
+        for p in self._tables:
+            lib().trexhip_device_free(self.seg._h, p)
+            self._bufs.remove(p)
+        self._tables = []
+
+    def _upload(self, arr):
+        arr = np.ascontiguousarray(arr)
+        d = self._alloc(arr.nbytes)
+        self._tables.append(self._bufs[-1])
+        if arr.nbytes:
+            _check(lib().trexhip_copy_to_device(self.seg._h, C.c_void_p(d), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
+        return d
+
+    @staticmethod
+    def pack_shapes(shapes):
+        """-> (float32 [n_points][2], int32 [n_shapes + 1])"""
+        pts = [np.asarray(s, np.float32).reshape(-1, 2) for s in shapes]
+        off = np.zeros(len(pts) + 1, np.int32)
+        if pts:
+            off[1:] = np.cumsum([len(q) for q in pts])
+        flat = np.concatenate(pts) if pts else np.zeros((0, 2), np.float32)
+        return np.ascontiguousarray(flat, np.float32), off
+
+    @staticmethod
+    def pack_bdx(per_frame, n_frames):
+        """-> (uint32 sorted per frame, int32 [n_frames + 1])"""
+        lists = [np.unique(np.asarray(list(per_frame[f]) if per_frame[f] is not None else [], np.uint32)) for f in range(n_frames)]
+        off = np.zeros(n_frames + 1, np.int32)
+        off[1:] = np.cumsum([len(q) for q in lists])
+        return (np.concatenate(lists) if lists else np.zeros(0, np.uint32)).astype(np.uint32), off
+
+    def run(self, track_threshold, method=0, size_ranges=(), track_threshold_2=0, threshold_ratio_range=(0.5, 1.0), include=(), ignore=(),
+            ignore_bdx=None, second_count=False):
+        """Enqueue the call; fetch() reads the results."""
+        pp = PrefilterParams()
+        lib().trexhip_default_prefilter_params(C.byref(pp))
+        pp.track_threshold, pp.method, pp.track_threshold_2 = int(track_threshold), int(method), int(track_threshold_2)
+        pp.threshold_ratio_range[0], pp.threshold_ratio_range[1] = threshold_ratio_range
+        pp.n_ranges = len(size_ranges)
+        for i, (a, b) in enumerate(list(size_ranges)[:8]):
+            pp.size_ranges[2 * i], pp.size_ranges[2 * i + 1] = a, b
+        self._free_tables()
+        tb = PrefilterTables()
+        ipts, ioff = self.pack_shapes(include)
+        gpts, goff = self.pack_shapes(ignore)
+        tb.n_include_shapes, tb.n_include_points = len(ioff) - 1, len(ipts)
+        tb.n_ignore_shapes, tb.n_ignore_points = len(goff) - 1, len(gpts)
+        if len(ioff) > 1:
+            tb.d_include_points, tb.d_include_offsets = self._upload(ipts), self._upload(ioff)
+        if len(goff) > 1:
+            tb.d_ignore_points, tb.d_ignore_offsets = self._upload(gpts), self._upload(goff)
+        if ignore_bdx is not None:
+            words, boff = self.pack_bdx(ignore_bdx, self.n_frames)
+            tb.d_ignore_bdx, tb.d_ignore_bdx_offsets, tb.n_ignore_bdx = self._upload(words), self._upload(boff), len(words)
+        if second_count:
+            if self.d_second_count is None:
+                self.d_second_count = self._alloc(8 * self.cap)
+            tb.d_second_count = self.d_second_count
+        self._want_second = bool(second_count)
+        _check(lib().trexhip_prefilter_device(self.seg._h, C.byref(pp), C.byref(tb), C.c_void_p(self.d_decision), C.c_void_p(self.d_order),
+                                              C.c_void_p(self.d_counts), C.c_void_p(self.d_presumed_nr)))
+
+    def _download(self, d, count, dtype):
+        out = np.empty(count, dtype)
+        if out.nbytes:
+            _check(lib().trexhip_copy_to_host(self.seg._h, out.ctypes.data_as(C.c_void_p), C.c_void_p(d), out.nbytes))
+        return out
+
+    def fetch(self):
+        return PrefilterResult(self._download(self.d_decision, 2 * self.cap, np.uint8),
+                               self._download(self.d_order, self.n_frames * self.per_frame, np.int32).reshape(self.n_frames, self.per_frame),
+                               self._download(self.d_counts, 4 * self.n_frames, np.int32).reshape(self.n_frames, 4),
+                               self._download(self.d_presumed_nr, self.total_blobs, np.int32),
+                               self._download(self.d_second_count, 2 * self.cap, np.int32) if self._want_second else None, self.cap)
+
+    def close(self):
+        for p in self._bufs:
+            lib().trexhip_device_free(self.seg._h, p)
+        self._bufs, self._tables = [], []

@@ -244,7 +244,7 @@ void trexhip_destroy(trexhip_ctx* ctx) {
     pass2_free(ctx);
     void* dev[] = {ctx->d_bg, ctx->d_staging, ctx->d_ctr, ctx->d_band_fail, ctx->d_row_cnt, ctx->d_row_off, ctx->d_row_base, ctx->d_tmp_runs,
                    ctx->d_raster, ctx->d_parent, ctx->d_root_ord, ctx->d_cnt_runs, ctx->d_cnt_px, ctx->d_cur_run,
-                   ctx->d_pix_begin, ctx->d_blob_map, ctx->d_info, ctx->d_blobs, ctx->d_blob_frame, ctx->d_runs, ctx->d_pixels, ctx->d_color, ctx->d_bits[0], ctx->d_bits[1], ctx->d_warp, ctx->d_bg_color, ctx->d_len, ctx->d_auto, ctx->d_aug_idx, ctx->d_val, ctx->d_avg, ctx->d_load};
+                   ctx->d_pix_begin, ctx->d_blob_map, ctx->d_info, ctx->d_blobs, ctx->d_blob_frame, ctx->d_runs, ctx->d_pixels, ctx->d_color, ctx->d_bits[0], ctx->d_bits[1], ctx->d_warp, ctx->d_bg_color, ctx->d_len, ctx->d_auto, ctx->d_aug_idx, ctx->d_val, ctx->d_avg, ctx->d_load, ctx->d_pre};
     for (void* p : dev) if (p) hipFree(p);
     upload_free(ctx);
     void* host[] = {ctx->h_info, ctx->h_totals, ctx->h_blobs, ctx->h_runs, ctx->h_pixels, ctx->h_staging, ctx->h_color, ctx->h_ccl_hint};
@@ -528,13 +528,7 @@ int trexhip_rethreshold_device(trexhip_ctx* ctx, int32_t threshold, int32_t meth
 
 int trexhip_rethreshold_per_blob_device(trexhip_ctx* ctx, int32_t threshold, const int32_t* d_blob_thresholds, int32_t method,
                                         const double* size_ranges, int32_t n_ranges) {
-    if (!ctx) { set_error("trexhip_rethreshold_device: null ctx"); return TREXHIP_E_INVALID; }
-    if (method < 0 || method > 2) { set_error("trexhip_rethreshold_device: method must be 0 (absolute), 1 (sign) or 2 (none)"); return TREXHIP_E_INVALID; }
-    if (n_ranges < 0 || n_ranges > 8 || (n_ranges && !size_ranges)) { set_error("trexhip_rethreshold_device: bad size ranges"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0) { set_error("trexhip_rethreshold_device: no segmented batch"); return TREXHIP_E_INVALID; }
-    if (!ctx->fetched) { set_error("trexhip_rethreshold_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    int rc = pass2_alloc(ctx);
+    int rc = trexhip::rethreshold_prepare(ctx, "trexhip_rethreshold_device", method, size_ranges, n_ranges);
     if (rc) return rc;
     return launch_rethreshold(ctx, threshold, method, size_ranges, n_ranges, d_blob_thresholds);
 }
@@ -619,3 +613,17 @@ int trexhip_profile_reset(trexhip_ctx* ctx) {
 }
 
 }  // extern "C"
+
+namespace trexhip {
+// what every entry point that runs the re-threshold pass checks before it launches: arguments, a fetched batch, the second table set
+int rethreshold_prepare(trexhip_ctx* ctx, const char* who, int32_t method, const double* size_ranges, int32_t n_ranges) {
+    const std::string w(who);
+    if (!ctx) { set_error(w + ": null ctx"); return TREXHIP_E_INVALID; }
+    if (method < 0 || method > 2) { set_error(w + ": method must be 0 (absolute), 1 (sign) or 2 (none)"); return TREXHIP_E_INVALID; }
+    if (n_ranges < 0 || n_ranges > 8 || (n_ranges && !size_ranges)) { set_error(w + ": bad size ranges"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->last_n == 0) { set_error(w + ": no segmented batch"); return TREXHIP_E_INVALID; }
+    if (!ctx->fetched) { set_error(w + ": call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
+    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    return pass2_alloc(ctx);
+}
+}

@@ -145,6 +145,7 @@ struct trexhip_ctx {
     uint8_t* d_avg = nullptr;           // scratch and results of trexhip_class_averages_device (averages.hip), grown on demand
     size_t avg_cap = 0;
     void* d_auto = nullptr;             // scratch of trexhip_posture_auto_device (thresholds, selections, first outlines)
+    void* d_pre = nullptr;              // second counts and sequence scratch of trexhip_prefilter_device (prefilter.hip), allocated on its first call
     void* d_load = nullptr;             // blob index and frame counts of trexhip_load_frames_v6_device (unpack.hip), allocated on its first call
     size_t auto_cap = 0;
     uint32_t* d_bits[2] = {nullptr, nullptr};   // 1 bit/pixel masks for the optional morphology [B][H][ceil(W/32)]
@@ -163,7 +164,7 @@ struct trexhip_ctx {
     bool tune_rows_blocks_set = false;  // TREXHIP_ROWS_BLOCKS given: no automatic grid for the wide pixel pass
     int tune_conv_geom = 0;             // dev only: which identity-network chain runs (TREXHIP_CONV_GEOM, bits 0-11 and 28-30)
     // hipFuncSetAttribute is per device: one process may drive several devices through several contexts
-    bool attr_cnn = false, attr_ccl = false, attr_split = false;
+    bool attr_cnn = false, attr_ccl = false, attr_split = false, attr_prefilter = false;
     bool ctr_dirty = false;             // a detect pass was queued but not to its end: the per-frame overflow counters may be non-zero (launch_segment zeroes them first)
     int attr_posture_bytes = 0;
     int pix_ch = 1;                     // bytes per output pixel (pixel_encoding)
@@ -207,6 +208,10 @@ void any_convs_rerun(hipStream_t s, int n_cus, const AnyConvNet& a, int n, const
 int launch_pending(trexhip_ctx* ctx);
 int launch_morphology(trexhip_ctx* ctx, const uint8_t* d_frames, int n, const uint32_t** result);
 int launch_rethreshold(trexhip_ctx* ctx, int thr, int method, const double* ranges, int n_ranges, const int32_t* d_blob_thr);
+// the checks shared by every entry point that runs the re-threshold pass (arguments, a fetched batch) + the second table set on first use (capi.hip)
+int rethreshold_prepare(trexhip_ctx* ctx, const char* who, int32_t method, const double* size_ranges, int32_t n_ranges);
+int launch_prefilter(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const trexhip_prefilter_tables* tb, uint8_t* d_decision, int32_t* d_order,
+                     int32_t* d_counts, int32_t* d_presumed_nr);
 int launch_to_gray(trexhip_ctx* ctx, const uint8_t* d_color, uint8_t* d_gray, size_t npix, int channels, int color_channel);
 void upload_free(trexhip_ctx* ctx);
 int upload_frames(trexhip_ctx* ctx, const uint8_t* const* frames, int n, size_t rows, size_t row_bytes, size_t stride, uint8_t* d_dst,
