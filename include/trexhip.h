@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 12
+#define TREXHIP_ABI_VERSION 13
 
 enum {
     TREXHIP_OK = 0,
@@ -757,6 +757,88 @@ int trexhip_class_averages_device(trexhip_ctx* ctx, const float* d_probs, int32_
                                   float* averages,                         /* HOST [n_ids][classes], or NULL         */
                                   int32_t* max_index,                      /* HOST [n_ids], or NULL                  */
                                   float* max_p);                           /* HOST [n_ids], or NULL                  */
+
+/* ------------------------------------------------------------------------------------------------
+ * Every individual's visual field on outlines that are in HBM: track::VisualField::calculate (tracking/VisualField.cpp:361-577) as
+ * Individual::save_visual_field (tracking/Individual.cpp:2887-3010) and output_visual_fields ask for it, for a batch of frames and any
+ * number of observers per frame in one call.  Per observer and eye a two-layer depth buffer of TREXHIP_VF_RESOLUTION bins over
+ * +-RADIANS(130) around the eye's direction; every outline point of every individual of the frame, the observer itself included, enters
+ * it as two lines.  Restated line by line:
+ *   tesselate_outline (:339-359)      previous starts as the last outline point; an edge longer than max_distance gets the points
+ *                                     previous + direction * i * max_distance for int i = 1; i < N - 1, N = L / max_distance + 0.5 in double
+ *   the loop over the active individuals (:526-576)   an entry is used iff posture_row >= 0, its posture info has n_outline > 0 and its
+ *                                     tail index is not -1 (:552); entries are applied in list order, the observer's own like any other;
+ *                                     right_side = T + 1, left_side = n - T from the TARGET's tail index T and the tessellated length n,
+ *                                     then the replacements of :435-436
+ *   add_line (:427-496)               per tessellated point i two records, (previous, pt) then (ptp, pt), previous = points[n - 1] and
+ *                                     ptp = points[(n - 2) % n] to begin with; hd = (1 - |i - T_obs| / ((i > T_obs ? left : right) + 1)) * 255
+ *                                     with the OBSERVER's tail index (the lambda captured the outer midline, :460; the inner one of :531 only
+ *                                     shadows it for the two sides), so hd may leave [0, 255]; per eye line = pt + (pos - eye.pos),
+ *                                     atan2 of both ends, project_angles_1d (:74-94) as written; rp = pt0 + pos if the FIRST projected value
+ *                                     (after the swap) is >= 0, else pt1 + pos; d = squared distance from rp to the eye
+ *   plot_projected_line (:96-150)     the x0 / x1 replacements in the order of :102-103, start = uint(max(0, x0)), end = uint(min(512,
+ *                                     ceil(x1))), bins i <= end && i < 512, the two-layer update with its id tests and the invalidation of
+ *                                     layer 2 behind a self hit; fov = uchar(SQR(1 - min(1, max(0, d / max_d))) * 255); points as float(rp)
+ * Per eye the records are applied in the order (entry, i, pair): layer 2 is not a function of a minimum, the order is the algorithm.
+ * Every operation but the two atan2 gives the bits of tests/visual_field_ref.py and HipVisualField::cast_host; atan2 is the device
+ * library's (the reference's is libm's; neither is correctly rounded), so a result can differ only where a projected value sits within
+ * an ulp of an integer or of a field-of-view end.
+ *   d_outline, d_posture_info   what trexhip_posture_device / trexhip_posture_auto_device wrote (row length max_points); the outline of
+ *                               `virtual_frame` (:538-548): the look-back over max_back_view frames is the caller's, it names the row of
+ *                               whichever frame's outline it found
+ *   d_frame_entries             [n_frames + 1] ascending offsets into d_entries, [0] = 0, [n_frames] <= n_entries
+ *   d_entries                   per frame the individuals in the order of Tracker::active_individuals(frame)
+ *   d_observers                 one VisualField object each; eye positions and angles as VisualField::generate_eyes returns them
+ * Outputs: device memory, [n_observers][2 eyes][TREXHIP_VF_LAYERS][TREXHIP_VF_RESOLUTION] each -- per eye the members _depth,
+ * _visible_ids, _visible_points (float2), _fov, _visible_head_distance in the shape save_visual_field writes -- and d_status
+ * [n_observers]; any of them may be NULL.  Initial values are eye::eye()'s (VisualField.h:37-43): depth FLT_MAX as a double, ids -1,
+ * points 0, fov 0, head distance -1.
+ *   d_status   0 ok;  1 the observer's own entry is not used (no outline, no tail index): nothing but the initial values is written;
+ *              2 an entry of its frame needs more than max_tess_points tessellated points: every observer of that frame gets the initial
+ *                values only -- the frame is flagged, nothing is half-done; the other frames of the call are complete
+ * Refused with TREXHIP_E_INVALID: negative counts, max_tess_points < max_points or max_points < 1, offsets that do not ascend from 0 or
+ * pass n_entries, an observer whose frame is outside 0..n_frames-1 or whose entry lies outside its frame's range (found by the device
+ * before anything is written; for that the call synchronises once at its end).  Otherwise ordered on the context's stream; scratch for
+ * the tessellated outlines (n_entries x max_tess_points x 16 bytes) is kept in the context and grown on demand.
+ * Not in this call: generate_eyes (:203-337: commons' LineSegmentsIntersect, and its history smoothing is tracker state; it is a public
+ * static of the reference, the caller hands over its result), visual_field_shapes (:498-522: commons' poly_convex_hull),
+ * gui_pose_smoothing > 0 (:382-383), and the look-back named above.
+ * UNPINNED (the arithmetic is the un-vendored commons'; each reading is stated here and in DESIGN.md):
+ *   Vec2 arithmetic in tesselate_outline   direction = pt - previous, L = sqrtf(x * x + y * y), direction /= L and
+ *                                          previous + (direction * float(i)) * float(max_distance) are float32 operations, each rounded
+ *                                          on its own; L > max_distance and N are evaluated in double; each point is then widened
+ *   atan2(Vec64)                           atan2(v.y, v.x)
+ *   long_t                                 int32_t
+ *   RADIANS(130)                           130 * (M_PI / 180) in double */
+#define TREXHIP_VF_RESOLUTION 512   /* VisualField::field_resolution */
+#define TREXHIP_VF_LAYERS     2     /* VisualField::layers */
+#define TREXHIP_VF_CHUNK_RECORDS 512   /* records one workgroup computes per step (one per thread); an entry is walked in steps of this many */
+#define TREXHIP_VF_LDS_RECORDS  1024   /* records that wait in LDS before the bins apply them */
+typedef struct trexhip_vf_params {
+    double  max_d;            /* SQR(average.cols) + SQR(average.rows); default: the context's width, height */
+    double  max_distance;     /* tesselate_outline's default argument: 5 */
+    int32_t max_points;       /* row length of d_outline (the posture call's max_points) */
+    int32_t max_tess_points;  /* capacity per entry of the tessellated outline */
+} trexhip_vf_params;
+typedef struct trexhip_vf_entry {    /* one individual of one frame, in the order of Tracker::active_individuals(frame) */
+    int32_t id;               /* Identity::ID() */
+    int32_t posture_row;      /* row of d_outline / d_posture_info (the outline of `virtual_frame`); -1: no outline, skipped */
+    float   pos_x, pos_y;     /* bounds().pos() of that blob */
+    int32_t flags;            /* bit 0: the midline was turned round (_inverted_because_previous): use head_index as the tail */
+    int32_t reserved;
+} trexhip_vf_entry;
+typedef struct trexhip_vf_observer { /* one VisualField object */
+    int32_t frame, entry;     /* index into d_frame_entries; index of its own entry (absolute) */
+    double  eye_x[2], eye_y[2], eye_angle[2];   /* eye::pos, eye::angle as generate_eyes returns them (angle already corrected to (-pi, pi]) */
+} trexhip_vf_observer;
+void trexhip_default_vf_params(trexhip_ctx* ctx, trexhip_vf_params* p);
+int trexhip_visual_field_device(trexhip_ctx* ctx, const trexhip_vf_params* vp,
+        const float* d_outline, const trexhip_posture_info* d_posture_info,
+        const int32_t* d_frame_entries /* [n_frames + 1] prefix offsets */, int32_t n_frames,
+        const trexhip_vf_entry* d_entries, int32_t n_entries,
+        const trexhip_vf_observer* d_observers, int32_t n_observers,
+        double* d_depth, int32_t* d_ids, float* d_points /* float2 */, uint8_t* d_fov, double* d_head_distance,
+        int32_t* d_status /* [n_observers] */);
 
 #ifdef __cplusplus
 }

@@ -88,6 +88,18 @@ class PrefilterTables(C.Structure):
 DECISION_COMMITTED, DECISION_BIG, DECISION_FILTERED, DECISION_NONE = 0, 1, 16, 255
 FILTER_OUTSIDE_INCLUDE, FILTER_INSIDE_IGNORE, FILTER_BDX_IGNORED, FILTER_OUTSIDE_RANGE, FILTER_SECOND_THRESHOLD = 0, 1, 2, 3, 4
 
+class VfParams(C.Structure):
+    _fields_ = [("max_d", C.c_double), ("max_distance", C.c_double), ("max_points", C.c_int32), ("max_tess_points", C.c_int32)]
+
+
+# trexhip_visual_field_device: one individual of one frame, one VisualField object; outputs are [n_observers][2 eyes][VF_LAYERS][VF_RESOLUTION]
+VF_ENTRY_DTYPE = np.dtype([("id", "<i4"), ("posture_row", "<i4"), ("pos_x", "<f4"), ("pos_y", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])
+VF_OBSERVER_DTYPE = np.dtype([("frame", "<i4"), ("entry", "<i4"), ("eye_x", "<f8", (2,)), ("eye_y", "<f8", (2,)), ("eye_angle", "<f8", (2,))])
+assert VF_ENTRY_DTYPE.itemsize == 24 and VF_OBSERVER_DTYPE.itemsize == 56
+VF_RESOLUTION, VF_LAYERS = 512, 2
+VF_CHUNK_RECORDS, VF_LDS_RECORDS = 512, 1024      # TREXHIP_VF_CHUNK_RECORDS / TREXHIP_VF_LDS_RECORDS: records per compute step of a workgroup, records waiting in LDS
+VF_OUTPUTS = ("depth", "ids", "points", "fov", "head_distance", "status")
+
 SPLIT_INFO_DTYPE = np.dtype([("threshold", "<i4"), ("effective_threshold", "<i4"), ("status", "<i4"), ("initial_action", "<i4"), ("n_result", "<i4"),
                              ("n_evaluated", "<i4"), ("min_pixel", "<i4"), ("max_pixel", "<i4"), ("first_size", "<f4"), ("reserved_", "<f4"),
                              ("min_size_bound", "<f8")])
@@ -168,6 +180,18 @@ class ClassAverages:
         self.samples, self.values, self.max_index, self.max_p = samples, values, max_index, max_p
 
 
+class VisualFieldResult:
+    """What Segmenter.visual_field returns: depth (float64), ids (int32), points (float32 [..., 2]), fov (uint8), head_distance (float64), each
+    [n_observers][2 eyes][2 layers][512] -- per eye the members _depth, _visible_ids, _visible_points, _fov, _visible_head_distance of
+    VisualField::eye -- and status (int32 [n_observers]: 0 ok, 1 the observer has no usable posture, 2 an entry of its frame exceeded
+    max_tess_points).  What was not asked for is None."""
+    __slots__ = VF_OUTPUTS
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+
+
 SYMBOLS = [
     "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
@@ -180,6 +204,7 @@ SYMBOLS = [
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
     "trexhip_load_frames_v6_device", "trexhip_lzo1x_decompress", "trexhip_pv_read_frames",
     "trexhip_default_prefilter_params", "trexhip_prefilter_device",
+    "trexhip_default_vf_params", "trexhip_visual_field_device",
 ]
 
 
@@ -286,6 +311,10 @@ def lib():
         L.trexhip_default_prefilter_params.argtypes = [C.POINTER(PrefilterParams)]
         L.trexhip_default_prefilter_params.restype = None
         L.trexhip_prefilter_device.argtypes = [C.c_void_p, C.POINTER(PrefilterParams), C.POINTER(PrefilterTables), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.trexhip_default_vf_params.argtypes = [C.c_void_p, C.POINTER(VfParams)]
+        L.trexhip_default_vf_params.restype = None
+        L.trexhip_visual_field_device.argtypes = [C.c_void_p, C.POINTER(VfParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -690,6 +719,74 @@ class Segmenter:
         _check(lib().trexhip_class_averages_device(self._h, C.c_void_p(d_probs_ptr or 0), n, classes, C.c_void_p(d_ids_ptr or 0), n_ids,
                                                    ptr(samples), ptr(values), ptr(max_index), ptr(max_p)))
         return ClassAverages(samples, values, max_index, max_p)
+
+    def default_vf_params(self, **kw):
+        """trexhip_default_vf_params: max_d from the context's frame size, max_distance 5; keywords override single fields"""
+        vp = VfParams()
+        lib().trexhip_default_vf_params(self._h, C.byref(vp))
+        for k, v in kw.items():
+            if not hasattr(vp, k):
+                raise KeyError(k)
+            setattr(vp, k, v)
+        return vp
+
+    def visual_field(self, outline, posture_info, frame_entries, entries, observers, max_points, max_tess_points=1024, max_d=None, max_distance=5.0,
+                     outputs=VF_OUTPUTS):
+        """track::VisualField for every observer of a batch of frames (trexhip_visual_field_device; see include/trexhip.h).
+        outline / posture_info: device addresses of what the posture call wrote (float2 [rows][max_points], trexhip_posture_info [rows]), or
+        host arrays (float32 [rows][max_points][2], POSTURE_INFO_DTYPE [rows]) that are uploaded first.  frame_entries int32 [n_frames + 1],
+        entries VF_ENTRY_DTYPE, observers VF_OBSERVER_DTYPE: host arrays.  outputs: which of VF_OUTPUTS to compute and copy back.
+        -> VisualFieldResult."""
+        unknown = set(outputs) - set(VF_OUTPUTS)
+        if unknown:
+            raise KeyError(sorted(unknown))
+        fe = np.ascontiguousarray(frame_entries, np.int32).reshape(-1)
+        en = np.ascontiguousarray(entries, VF_ENTRY_DTYPE).reshape(-1)
+        ob = np.ascontiguousarray(observers, VF_OBSERVER_DTYPE).reshape(-1)
+        n_frames, n_entries, n_obs = len(fe) - 1, len(en), len(ob)
+        kw = dict(max_points=max_points, max_tess_points=max_tess_points, max_distance=max_distance)
+        if max_d is not None:
+            kw["max_d"] = max_d
+        vp = self.default_vf_params(**kw)
+        owned = []
+
+        def up(a):
+            d = self.device_alloc(max(a.nbytes, 16))
+            owned.append(d)
+            if a.nbytes:
+                self.copy_to_device(d, a)
+            return d
+
+        try:
+            if isinstance(outline, np.ndarray):
+                o = np.ascontiguousarray(outline, np.float32)
+                if o.ndim != 3 or o.shape[1:] != (max_points, 2):
+                    raise ValueError(f"outline must be [rows][{max_points}][2], got {o.shape}")
+                outline = up(o)
+            if isinstance(posture_info, np.ndarray):
+                posture_info = up(np.ascontiguousarray(posture_info, POSTURE_INFO_DTYPE))
+            d_fe, d_en, d_ob = up(fe), up(en), up(ob)
+            cells = n_obs * 2 * VF_LAYERS * VF_RESOLUTION
+            spec = {"depth": ((n_obs, 2, VF_LAYERS, VF_RESOLUTION), np.float64), "ids": ((n_obs, 2, VF_LAYERS, VF_RESOLUTION), np.int32),
+                    "points": ((n_obs, 2, VF_LAYERS, VF_RESOLUTION, 2), np.float32), "fov": ((n_obs, 2, VF_LAYERS, VF_RESOLUTION), np.uint8),
+                    "head_distance": ((n_obs, 2, VF_LAYERS, VF_RESOLUTION), np.float64), "status": ((n_obs,), np.int32)}
+            dev = {}
+            for k in VF_OUTPUTS:
+                if k in outputs:
+                    shape, dt = spec[k]
+                    dev[k] = self.device_alloc(max(int(np.prod(shape)) * np.dtype(dt).itemsize, 16))
+                    owned.append(dev[k])
+            _check(lib().trexhip_visual_field_device(self._h, C.byref(vp), C.c_void_p(outline or 0), C.c_void_p(posture_info or 0), C.c_void_p(d_fe),
+                                                     n_frames, C.c_void_p(d_en), n_entries, C.c_void_p(d_ob), n_obs,
+                                                     *[C.c_void_p(dev.get(k, 0)) for k in VF_OUTPUTS]))
+            res = VisualFieldResult()
+            for k, d in dev.items():
+                shape, dt = spec[k]
+                setattr(res, k, self.copy_to_host(d, shape, dt) if cells else np.zeros(shape, dt))
+            return res
+        finally:
+            for d in owned:
+                self.device_free(d)
 
     def rethreshold_per_blob(self, d_thresholds_ptr, method=0, size_ranges=(), threshold=0):
         """SplitBlob::apply_threshold building block: one threshold per detect blob (int32 device array, pooled order; <0 skips)."""

@@ -144,6 +144,8 @@ struct trexhip_ctx {
     size_t val_cap = 0;
     uint8_t* d_avg = nullptr;           // scratch and results of trexhip_class_averages_device (averages.hip), grown on demand
     size_t avg_cap = 0;
+    uint8_t* d_vf = nullptr;            // scratch of trexhip_visual_field_device (visual_field.hip): flag, tessellated outlines; grown on demand
+    size_t vf_cap = 0;
     void* d_auto = nullptr;             // scratch of trexhip_posture_auto_device (thresholds, selections, first outlines)
     void* d_pre = nullptr;              // second counts and sequence scratch of trexhip_prefilter_device (prefilter.hip), allocated on its first call
     void* d_load = nullptr;             // blob index and frame counts of trexhip_load_frames_v6_device (unpack.hip), allocated on its first call
