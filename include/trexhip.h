@@ -24,6 +24,9 @@ extern "C" {
 
 #define TREXHIP_ABI_VERSION 13
 
+/* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
+   returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
+   the first release of ABI 13 some entry points returned TREXHIP_E_DEVICE for an exhausted device.) */
 enum {
     TREXHIP_OK = 0,
     TREXHIP_E_INVALID = -1,    /* bad argument / not initialised (e.g. no background yet)   */

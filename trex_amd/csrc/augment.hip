@@ -271,16 +271,9 @@ int trexhip_augment_device(trexhip_ctx* ctx, const trexhip_augment_params* ap, c
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     const int32_t* d_idx = nullptr;
     if (indices) {
-        if (n > ctx->aug_idx_cap) {
-            TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));        // an earlier call may still read the old list
-            if (ctx->d_aug_idx) (void)hipFree(ctx->d_aug_idx);
-            ctx->d_aug_idx = nullptr; ctx->aug_idx_cap = 0;
-            const int cap = n < 1024 ? 1024 : n;
-            TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_aug_idx), (size_t)cap * sizeof(int32_t)));
-            ctx->aug_idx_cap = cap;
-        }
-        TH_CHECK_HIP(hipMemcpyAsync(ctx->d_aug_idx, indices, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));   // pageable source: staged before the call returns
-        d_idx = ctx->d_aug_idx;
+        if (int rc = ctx->aug_idx.reserve(ctx, (size_t)std::max(n, 1024) * sizeof(int32_t), "trexhip_augment_device")) return rc;   // at least 1024 entries: typical batches never grow it
+        TH_CHECK_HIP(hipMemcpyAsync(ctx->aug_idx.p, indices, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));   // pageable source: staged before the call returns
+        d_idx = ctx->aug_idx.as<int32_t>();
     }
     AugCfg c{};
     c.W = width; c.H = height; c.HW = width * height; c.HWC = c.HW * channels;

@@ -174,13 +174,8 @@ int trexhip_class_averages_device(trexhip_ctx* ctx, const float* d_probs, int32_
     const size_t back = averages ? o_offs : samples ? o_avg : o_samples;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     hipStream_t s = ctx->stream;
-    if (total > ctx->avg_cap) {
-        if (ctx->d_avg) { TH_CHECK_HIP(hipStreamSynchronize(s)); (void)hipFree(ctx->d_avg); }
-        ctx->d_avg = nullptr; ctx->avg_cap = 0;
-        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_avg), total));
-        ctx->avg_cap = total;
-    }
-    uint8_t* base = ctx->d_avg;
+    if (int rc = ctx->avg.reserve(ctx, total, "trexhip_class_averages_device")) return rc;
+    uint8_t* base = ctx->avg.as<uint8_t>();
     TH_CHECK_HIP(hipMemsetAsync(base + o_flag, 0, 16, s));
     TH_CHECK_HIP(hipMemsetAsync(base + o_offs, 0, (slots + 1) * 4, s));
     AvgArgs A{};

@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -64,16 +65,49 @@ void stage_free(trexhip_ctx* ctx) {
     }
 }
 
-template <typename T>
-static int dmalloc(T** p, size_t count) {
-    if (count == 0) count = 1;
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
+// one table set (pooled outputs, pinned mirrors, labelling state) from the context's capacities; d_totals is allocated unless the caller has set it
+static int alloc_tables(Mem& m, BlobTables& t, LabelState& l, size_t B, size_t H, size_t R, size_t NB, size_t P, size_t pix_ch, const char* who) {
+    int rc = TREXHIP_OK;
+#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
+    TRY(m.device(&l.d_row_cnt, B * H, who)); TRY(m.device(&l.d_row_base, B * (H + 1), who)); TRY(m.device(&l.d_raster, B * R, who));
+    TRY(m.device(&l.d_parent, B * R, who)); TRY(m.device(&l.d_root_ord, B * R, who)); TRY(m.device(&l.d_cnt_runs, B * R, who));
+    TRY(m.device(&l.d_cnt_px, B * R, who)); TRY(m.device(&l.d_cur_run, B * R, who)); TRY(m.device(&l.d_pix_begin, B * R, who));
+    TRY(m.device(&l.d_blob_map, B * R, who));
+    if (!t.d_totals) TRY(m.device(&t.d_totals, 4, who));
+    TRY(m.device(&t.d_info, B, who)); TRY(m.device(&t.d_blobs, B * NB, who)); TRY(m.device(&t.d_blob_frame, B * NB, who));
+    TRY(m.device(&t.d_runs, B * R, who)); TRY(m.device(&t.d_pixels, B * P * pix_ch, who));
+    TRY(m.pinned(&t.h_info, B, who)); TRY(m.pinned(&t.h_totals, 4, who)); TRY(m.pinned(&t.h_blobs, B * NB, who));
+    TRY(m.pinned(&t.h_runs, B * R, who)); TRY(m.pinned(&t.h_pixels, B * P * pix_ch, who));
+#undef TRY
+    return rc;
+}
+
+// frame table and totals of the set's batch into the pinned mirrors, then wait for them
+static int fetch_info(trexhip_ctx* ctx, BlobTables& t) {
+    TH_CHECK_HIP(hipMemcpyAsync(t.h_info, t.d_info, sizeof(trexhip_frame_info) * t.valid_n, hipMemcpyDeviceToHost, ctx->stream));
+    TH_CHECK_HIP(hipMemcpyAsync(t.h_totals, t.d_totals, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return TREXHIP_OK;
 }
-template <typename T>
-static int hmalloc(T** p, size_t count) {
-    if (count == 0) count = 1;
-    TH_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(p), count * sizeof(T), hipHostMallocDefault));
+
+// the rest of a fetch, once h_info and h_totals are in: clamp the totals to the pools (frames that overflowed the pool reserved nothing valid),
+// copy the filled parts of the three tables unless a kernel has already exported them, wait, and fill the caller's result
+static int fetch_tables(trexhip_ctx* ctx, BlobTables& t, bool copy, trexhip_batch_result* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->n_frames = t.valid_n;
+    out->frames = t.h_info; out->blobs = t.h_blobs; out->runs = t.h_runs; out->pixels = t.h_pixels;
+    out->pixel_channels = (uint32_t)ctx->pix_ch;
+    if (t.valid_n == 0) return TREXHIP_OK;
+    const uint32_t tb = std::min(t.h_totals[0], ctx->cfg.pool_blobs), tr = std::min(t.h_totals[1], ctx->cfg.pool_runs), tp = std::min(t.h_totals[2], ctx->cfg.pool_pixels);
+    if (copy) {
+        hipStream_t s = ctx->stream;
+        if (tb) TH_CHECK_HIP(hipMemcpyAsync(t.h_blobs, t.d_blobs, sizeof(trexhip_blob) * tb, hipMemcpyDeviceToHost, s));
+        if (tr) TH_CHECK_HIP(hipMemcpyAsync(t.h_runs, t.d_runs, sizeof(trexhip_run) * tr, hipMemcpyDeviceToHost, s));
+        if (tp) TH_CHECK_HIP(hipMemcpyAsync(t.h_pixels, t.d_pixels, (size_t)tp * ctx->pix_ch, hipMemcpyDeviceToHost, s));
+        TH_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    out->total_blobs = tb; out->total_runs = tr; out->total_pixels = tp;
+    t.fetched = true;
     return TREXHIP_OK;
 }
 
@@ -102,7 +136,6 @@ static int fill_cfg(trexhip_ctx* ctx) {
 
 using namespace trexhip;
 
-static void pass2_free(trexhip_ctx* ctx);
 extern "C" int trexhip_rethreshold_per_blob_device(trexhip_ctx* ctx, int32_t threshold, const int32_t* d_blob_thresholds, int32_t method,
                                                    const double* size_ranges, int32_t n_ranges);
 
@@ -192,44 +225,28 @@ int trexhip_create(const trexhip_params* p, trexhip_ctx** out) {
     if (const char* e = std::getenv("TREXHIP_CCL_INST")) ctx->tune_ccl_inst = std::atoi(e);      // which k_ccl_lds instance goes first: same results either way
     if (const char* e = std::getenv("TREXHIP_ROWS_BLOCKS")) { ctx->tune_rows_blocks = std::atoi(e) > 0 ? std::atoi(e) : 8192; ctx->tune_rows_blocks_set = true; }
     const size_t B = p->max_batch, H = p->height, W = p->width, R = p->max_runs, NB = p->max_blobs, P = p->max_pixels;
-    int rc = TREXHIP_OK;
-#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete ctx; return TREXHIP_E_DEVICE; }
     ctx->stream = ctx->own_stream;
-    TRY(dmalloc(&ctx->d_bg, H * W + 16));
-    TRY(dmalloc(&ctx->d_ctr, B * TREXHIP_CTR_STRIDE + 4));
+    Mem& m = ctx->mem;
+    const char* who = "trexhip_create";
+    int rc = m.device(&ctx->d_bg, H * W + 16, who);
+#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
+    TRY(m.device(&ctx->d_ctr, B * TREXHIP_CTR_STRIDE + 4, who));
     if (rc == TREXHIP_OK && hipMemset(ctx->d_ctr, 0, sizeof(uint32_t) * (B * TREXHIP_CTR_STRIDE + 4)) != hipSuccess) { set_error("hipMemset of the counters failed"); rc = TREXHIP_E_DEVICE; }   // every pass leaves the counters zero (launch_segment)
-    TRY(dmalloc(&ctx->d_band_fail, B));
+    TRY(m.device(&ctx->d_band_fail, B, who));
     if (rc == TREXHIP_OK && hipMemset(ctx->d_band_fail, 0, sizeof(uint32_t) * B) != hipSuccess) { set_error("hipMemset of the band flags failed"); rc = TREXHIP_E_DEVICE; }
-    TRY(dmalloc(&ctx->d_row_cnt, B * H));
-    TRY(dmalloc(&ctx->d_row_off, B * H));
-    TRY(dmalloc(&ctx->d_row_base, B * (H + 1)));
-    TRY(dmalloc(&ctx->d_tmp_runs, B * (H * TREXHIP_ROW_SLOT + R)));
-    TRY(dmalloc(&ctx->d_raster, B * R));
-    TRY(dmalloc(&ctx->d_parent, B * R));
-    TRY(dmalloc(&ctx->d_root_ord, B * R));
-    TRY(dmalloc(&ctx->d_cnt_runs, B * R));
-    TRY(dmalloc(&ctx->d_cnt_px, B * R));
-    TRY(dmalloc(&ctx->d_cur_run, B * R));
-    TRY(dmalloc(&ctx->d_pix_begin, B * R));
-    TRY(dmalloc(&ctx->d_blob_map, B * R));
-    TRY(dmalloc(&ctx->d_info, B));
-    TRY(dmalloc(&ctx->d_blobs, B * NB));
-    TRY(dmalloc(&ctx->d_blob_frame, B * NB));
-    TRY(dmalloc(&ctx->d_runs, B * R));
-    TRY(dmalloc(&ctx->d_pixels, B * P * ctx->pix_ch));
+    TRY(m.device(&ctx->d_row_off, B * H, who));
+    TRY(m.device(&ctx->d_tmp_runs, B * (H * TREXHIP_ROW_SLOT + R), who));
+    if (rc == TREXHIP_OK) ctx->tables.d_totals = ctx->d_ctr + B * TREXHIP_CTR_STRIDE;   // the pooled totals live behind the per-frame counters
+    TRY(alloc_tables(m, ctx->tables, ctx->label, B, H, R, NB, P, ctx->pix_ch, who));
+    ctx->tables.fetched = true;     // no batch yet: nothing waits to be fetched
     if (p->use_closing || p->dilation_size != 0) {
         const size_t WBw = (W + 31) / 32;
-        TRY(dmalloc(&ctx->d_bits[0], B * H * WBw + 4));
-        TRY(dmalloc(&ctx->d_bits[1], B * H * WBw + 4));
+        TRY(m.device(&ctx->d_bits[0], B * H * WBw + 4, who));
+        TRY(m.device(&ctx->d_bits[1], B * H * WBw + 4, who));
     }
-    TRY(hmalloc(&ctx->h_info, B));
-    TRY(hmalloc(&ctx->h_totals, 4));
-    TRY(hmalloc(&ctx->h_ccl_hint, 2));
+    TRY(m.pinned(&ctx->h_ccl_hint, 2, who));
     if (rc == TREXHIP_OK) ctx->h_ccl_hint[0] = ctx->h_ccl_hint[1] = 0u;
-    TRY(hmalloc(&ctx->h_blobs, B * NB));
-    TRY(hmalloc(&ctx->h_runs, B * R));
-    TRY(hmalloc(&ctx->h_pixels, B * P * ctx->pix_ch));
 #undef TRY
     if (rc != TREXHIP_OK) { trexhip_destroy(ctx); return rc; }
     *out = ctx;
@@ -241,14 +258,9 @@ void trexhip_destroy(trexhip_ctx* ctx) {
     hipSetDevice(ctx->p.device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     net_free(ctx);
-    pass2_free(ctx);
-    void* dev[] = {ctx->d_bg, ctx->d_staging, ctx->d_ctr, ctx->d_band_fail, ctx->d_row_cnt, ctx->d_row_off, ctx->d_row_base, ctx->d_tmp_runs,
-                   ctx->d_raster, ctx->d_parent, ctx->d_root_ord, ctx->d_cnt_runs, ctx->d_cnt_px, ctx->d_cur_run,
-                   ctx->d_pix_begin, ctx->d_blob_map, ctx->d_info, ctx->d_blobs, ctx->d_blob_frame, ctx->d_runs, ctx->d_pixels, ctx->d_color, ctx->d_bits[0], ctx->d_bits[1], ctx->d_warp, ctx->d_bg_color, ctx->d_len, ctx->d_auto, ctx->d_aug_idx, ctx->d_val, ctx->d_avg, ctx->d_load, ctx->d_pre, ctx->d_vf};
-    for (void* p : dev) if (p) hipFree(p);
+    ctx->pass2.mem.free_all();
     upload_free(ctx);
-    void* host[] = {ctx->h_info, ctx->h_totals, ctx->h_blobs, ctx->h_runs, ctx->h_pixels, ctx->h_staging, ctx->h_color, ctx->h_ccl_hint};
-    for (void* p : host) if (p) hipHostFree(p);
+    ctx->mem.free_all();
     stage_free(ctx);
     if (ctx->aux_stream) {
         (void)hipStreamDestroy(ctx->aux_stream);
@@ -361,7 +373,7 @@ int trexhip_segment_device(trexhip_ctx* ctx, const uint8_t* d_frames, int32_t n)
     if (ctx->pix_ch != 1 || ctx->p.pixel_encoding != TREXHIP_ENC_GRAY) { set_error("trexhip_segment_device: a colour pixel_encoding needs colour input (trexhip_segment_color*)"); return TREXHIP_E_INVALID; }
     ctx->d_color_src = nullptr; ctx->color_ch = 0;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    if (n == 0) { ctx->last_n = 0; ctx->fetched = false; return TREXHIP_OK; }
+    if (n == 0) { ctx->tables.valid_n = 0; ctx->tables.fetched = false; return TREXHIP_OK; }
     return launch_segment(ctx, d_frames, n);
 }
 
@@ -372,12 +384,10 @@ int trexhip_segment(trexhip_ctx* ctx, const uint8_t* const* frames, int32_t stri
     ctx->d_color_src = nullptr; ctx->color_ch = 0;
     if (stride < ctx->p.width) { set_error("trexhip_segment: stride < width"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    if (n == 0) { ctx->last_n = 0; ctx->fetched = false; return TREXHIP_OK; }
+    if (n == 0) { ctx->tables.valid_n = 0; ctx->tables.fetched = false; return TREXHIP_OK; }
     const size_t W = ctx->p.width, H = ctx->p.height;
-    if (!ctx->d_staging) {
-        rc = dmalloc(&ctx->d_staging, (size_t)ctx->p.max_batch * W * H + 16);
-        if (rc) return rc;
-    }
+    rc = ensure_staging(ctx, "trexhip_segment");
+    if (rc) return rc;
     for (int i = 0; i < n; ++i)
         if (!frames[i]) { set_error("trexhip_segment: null frame pointer"); return TREXHIP_E_INVALID; }
     // pageable frame -> pinned ring slot (host threads) -> HBM, one async DMA per frame overlapping the next frame's staging (upload.hip)
@@ -422,10 +432,12 @@ __global__ __launch_bounds__(256) void k_export(const trexhip_frame_info* __rest
 }
 static_assert(sizeof(trexhip_frame_info) % 4 == 0 && sizeof(trexhip_blob) % 4 == 0 && sizeof(trexhip_run) % 4 == 0, "k_export copies 4-byte words");
 static constexpr int EXPORT_MAX_FRAMES = 16;
-static int export_small(trexhip_ctx* ctx, int n) {
-    hipLaunchKernelGGL(k_export, dim3(32), dim3(256), 0, ctx->stream, ctx->d_info, ctx->d_ctr + (size_t)ctx->p.max_batch * TREXHIP_CTR_STRIDE, ctx->d_blobs,
-                       ctx->d_runs, ctx->d_pixels, ctx->h_info, ctx->h_totals, ctx->h_blobs, ctx->h_runs, ctx->h_pixels, n,
-                       ctx->cfg.pool_blobs, ctx->cfg.pool_runs, ctx->cfg.pool_pixels, ctx->pix_ch);
+// frame table and totals into the pinned mirrors, and with n <= EXPORT_MAX_FRAMES the filled parts of the three tables along with them
+static int export_or_fetch_info(trexhip_ctx* ctx, bool by_kernel) {
+    BlobTables& t = ctx->tables;
+    if (!by_kernel) return fetch_info(ctx, t);
+    hipLaunchKernelGGL(k_export, dim3(32), dim3(256), 0, ctx->stream, t.d_info, t.d_totals, t.d_blobs, t.d_runs, t.d_pixels, t.h_info, t.h_totals, t.h_blobs,
+                       t.h_runs, t.h_pixels, t.valid_n, ctx->cfg.pool_blobs, ctx->cfg.pool_runs, ctx->cfg.pool_pixels, ctx->pix_ch);
     TH_CHECK_HIP(hipGetLastError());
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return TREXHIP_OK;
@@ -436,90 +448,52 @@ extern "C" {
 int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out) {
     if (!ctx || !out) { set_error("trexhip_fetch: null argument"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    std::memset(out, 0, sizeof(*out));
-    const int n = ctx->last_n;
-    out->n_frames = n;
-    out->frames = ctx->h_info; out->blobs = ctx->h_blobs; out->runs = ctx->h_runs; out->pixels = ctx->h_pixels;
-    out->pixel_channels = (uint32_t)ctx->pix_ch; out->reserved_ = 0;
-    if (n == 0) return TREXHIP_OK;
-    hipStream_t s = ctx->stream;
+    BlobTables& t = ctx->tables;
+    const int n = t.valid_n;
     static const bool export_env = !(std::getenv("TREXHIP_EXPORT") && std::atoi(std::getenv("TREXHIP_EXPORT")) == 0);
     const bool by_kernel = export_env && n <= EXPORT_MAX_FRAMES;      // a few frames: one launch + one synchronize (k_export)
-    if (by_kernel) { int rce = export_small(ctx, n); if (rce) return rce; }
-    else {
-        TH_CHECK_HIP(hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(trexhip_frame_info) * n, hipMemcpyDeviceToHost, s));
-        TH_CHECK_HIP(hipMemcpyAsync(ctx->h_totals, ctx->d_ctr + (size_t)ctx->p.max_batch * TREXHIP_CTR_STRIDE, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s));
-        TH_CHECK_HIP(hipStreamSynchronize(s));
-    }
-    bool pending = false;
-    for (int i = 0; i < n; ++i) pending |= ctx->h_info[i].reserved[0] == 1u;
-    if (pending) {   // frames with more runs than fit in LDS: finish them with the global-memory chain
-        int rc2 = launch_pending(ctx);
-        if (rc2) return rc2;
-        if (by_kernel) { int rce = export_small(ctx, n); if (rce) return rce; }
-        else {
-            TH_CHECK_HIP(hipMemcpyAsync(ctx->h_info, ctx->d_info, sizeof(trexhip_frame_info) * n, hipMemcpyDeviceToHost, s));
-            TH_CHECK_HIP(hipMemcpyAsync(ctx->h_totals, ctx->d_ctr + (size_t)ctx->p.max_batch * TREXHIP_CTR_STRIDE, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s));
-            TH_CHECK_HIP(hipStreamSynchronize(s));
+    if (n) {
+        int rc1 = export_or_fetch_info(ctx, by_kernel);
+        if (rc1) return rc1;
+        bool pending = false;
+        for (int i = 0; i < n; ++i) pending |= t.h_info[i].reserved[0] == 1u;
+        if (pending) {   // frames with more runs than fit in LDS: finish them with the global-memory chain
+            rc1 = launch_pending(ctx);
+            if (rc1 == TREXHIP_OK) rc1 = export_or_fetch_info(ctx, by_kernel);
+            if (rc1) return rc1;
         }
     }
-    // frames that overflowed the pool reserved nothing valid; clamp the copies to the pools
-    const uint32_t tb = ctx->h_totals[0] < ctx->cfg.pool_blobs ? ctx->h_totals[0] : ctx->cfg.pool_blobs;
-    const uint32_t tr = ctx->h_totals[1] < ctx->cfg.pool_runs ? ctx->h_totals[1] : ctx->cfg.pool_runs;
-    const uint32_t tp = ctx->h_totals[2] < ctx->cfg.pool_pixels ? ctx->h_totals[2] : ctx->cfg.pool_pixels;
-    if (!by_kernel) {
-        if (tb) TH_CHECK_HIP(hipMemcpyAsync(ctx->h_blobs, ctx->d_blobs, sizeof(trexhip_blob) * tb, hipMemcpyDeviceToHost, s));
-        if (tr) TH_CHECK_HIP(hipMemcpyAsync(ctx->h_runs, ctx->d_runs, sizeof(trexhip_run) * tr, hipMemcpyDeviceToHost, s));
-        if (tp) TH_CHECK_HIP(hipMemcpyAsync(ctx->h_pixels, ctx->d_pixels, (size_t)tp * ctx->pix_ch, hipMemcpyDeviceToHost, s));
-        TH_CHECK_HIP(hipStreamSynchronize(s));
-    }
-    out->total_blobs = tb; out->total_runs = tr; out->total_pixels = tp;
-    ctx->fetched = true;
-    int rc = TREXHIP_OK;
+    int rc = fetch_tables(ctx, t, !by_kernel, out);
+    if (rc || n == 0) return rc;
     for (int i = 0; i < n; ++i)
-        if (ctx->h_info[i].flags & TREXHIP_FRAME_MALFORMED) {       // a loaded frame (trexhip_load_frames_v6_device) that broke a rule of pv_read.h
+        if (t.h_info[i].flags & TREXHIP_FRAME_MALFORMED) {       // a loaded frame (trexhip_load_frames_v6_device) that broke a rule of pv_read.h
             char buf[160];
-            std::snprintf(buf, sizeof(buf), "frame %d of the batch is malformed: its V_6 body breaks the layout (flags=%u); it holds no blobs", i, ctx->h_info[i].flags);
+            std::snprintf(buf, sizeof(buf), "frame %d of the batch is malformed: its V_6 body breaks the layout (flags=%u); it holds no blobs", i, t.h_info[i].flags);
             set_error(buf);
             return TREXHIP_E_INVALID;
         }
     for (int i = 0; i < n; ++i)
-        if (ctx->h_info[i].flags) {
+        if (t.h_info[i].flags) {
             char buf[160];
             std::snprintf(buf, sizeof(buf), "frame %d of the batch exceeded capacity (flags=%u, raw runs=%u): raise max_runs/max_blobs/max_pixels",
-                          i, ctx->h_info[i].flags, ctx->h_info[i].n_raw_runs);
+                          i, t.h_info[i].flags, t.h_info[i].n_raw_runs);
             set_error(buf);
             rc = TREXHIP_E_CAPACITY;
         }
     return rc;
 }
 
-static int pass2_alloc(trexhip_ctx* ctx) {
+static int pass2_alloc(trexhip_ctx* ctx, const char* who) {
     Pass2& q = ctx->pass2;
     if (q.allocated) return TREXHIP_OK;
-    const size_t B = ctx->p.max_batch, H = ctx->p.height, R = ctx->p.max_runs, NB = ctx->p.max_blobs, P = ctx->p.max_pixels;
-    int rc = TREXHIP_OK;
-#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
-    TRY(dmalloc(&q.d_sub_cnt, B * R)); TRY(dmalloc(&q.d_sub_base, B * R)); TRY(dmalloc(&q.d_row_base, B * (H + 1)));
-    TRY(dmalloc(&q.d_row_cnt, B * H)); TRY(dmalloc(&q.d_run_parent, B * R)); TRY(dmalloc(&q.d_raster, B * R));
-    TRY(dmalloc(&q.d_parent, B * R)); TRY(dmalloc(&q.d_root_ord, B * R)); TRY(dmalloc(&q.d_cnt_runs, B * R));
-    TRY(dmalloc(&q.d_cnt_px, B * R)); TRY(dmalloc(&q.d_cur_run, B * R)); TRY(dmalloc(&q.d_pix_begin, B * R));
-    TRY(dmalloc(&q.d_blob_map, B * R)); TRY(dmalloc(&q.d_totals, 4)); TRY(dmalloc(&q.d_info, B));
-    TRY(dmalloc(&q.d_blobs, B * NB)); TRY(dmalloc(&q.d_blob_frame, B * NB)); TRY(dmalloc(&q.d_runs, B * R)); TRY(dmalloc(&q.d_pixels, B * P * ctx->pix_ch));
-    TRY(hmalloc(&q.h_info, B)); TRY(hmalloc(&q.h_totals, 4)); TRY(hmalloc(&q.h_blobs, B * NB)); TRY(hmalloc(&q.h_runs, B * R)); TRY(hmalloc(&q.h_pixels, B * P * ctx->pix_ch));
-#undef TRY
+    const size_t B = ctx->p.max_batch, R = ctx->p.max_runs;
+    int rc = alloc_tables(q.mem, q.tables, q.label, B, ctx->p.height, R, ctx->p.max_blobs, ctx->p.max_pixels, ctx->pix_ch, who);
+    if (rc == TREXHIP_OK) rc = q.mem.device(&q.d_sub_cnt, B * R, who);
+    if (rc == TREXHIP_OK) rc = q.mem.device(&q.d_sub_base, B * R, who);
+    if (rc == TREXHIP_OK) rc = q.mem.device(&q.d_run_parent, B * R, who);
+    if (rc != TREXHIP_OK) { q.mem.free_all(); q = Pass2(); }
     q.allocated = rc == TREXHIP_OK;
     return rc;
-}
-
-static void pass2_free(trexhip_ctx* ctx) {
-    Pass2& q = ctx->pass2;
-    void* dev[] = {q.d_sub_cnt, q.d_sub_base, q.d_row_base, q.d_row_cnt, q.d_run_parent, q.d_raster, q.d_parent, q.d_root_ord, q.d_cnt_runs,
-                   q.d_cnt_px, q.d_cur_run, q.d_pix_begin, q.d_blob_map, q.d_totals, q.d_info, q.d_blobs, q.d_blob_frame, q.d_runs, q.d_pixels};
-    for (void* p : dev) if (p) hipFree(p);
-    void* host[] = {q.h_info, q.h_totals, q.h_blobs, q.h_runs, q.h_pixels};
-    for (void* p : host) if (p) hipHostFree(p);
-    q = Pass2();
 }
 
 int trexhip_rethreshold_device(trexhip_ctx* ctx, int32_t threshold, int32_t method, const double* size_ranges, int32_t n_ranges) {
@@ -536,42 +510,28 @@ int trexhip_rethreshold_per_blob_device(trexhip_ctx* ctx, int32_t threshold, con
 int trexhip_fetch_rethreshold(trexhip_ctx* ctx, trexhip_batch_result* out) {
     if (!ctx || !out) { set_error("trexhip_fetch_rethreshold: null argument"); return TREXHIP_E_INVALID; }
     Pass2& q = ctx->pass2;
-    if (!q.allocated || q.valid_n == 0) { set_error("trexhip_fetch_rethreshold: no re-thresholded batch"); return TREXHIP_E_INVALID; }
+    if (!q.allocated || q.tables.valid_n == 0) { set_error("trexhip_fetch_rethreshold: no re-thresholded batch"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    std::memset(out, 0, sizeof(*out));
-    const int n = q.valid_n;
-    out->n_frames = n;
-    out->frames = q.h_info; out->blobs = q.h_blobs; out->runs = q.h_runs; out->pixels = q.h_pixels;
-    out->pixel_channels = (uint32_t)ctx->pix_ch; out->reserved_ = 0;
-    hipStream_t s = ctx->stream;
-    TH_CHECK_HIP(hipMemcpyAsync(q.h_info, q.d_info, sizeof(trexhip_frame_info) * n, hipMemcpyDeviceToHost, s));
-    TH_CHECK_HIP(hipMemcpyAsync(q.h_totals, q.d_totals, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s));
-    TH_CHECK_HIP(hipStreamSynchronize(s));
-    const uint32_t tb = q.h_totals[0] < ctx->cfg.pool_blobs ? q.h_totals[0] : ctx->cfg.pool_blobs;
-    const uint32_t tr = q.h_totals[1] < ctx->cfg.pool_runs ? q.h_totals[1] : ctx->cfg.pool_runs;
-    const uint32_t tp = q.h_totals[2] < ctx->cfg.pool_pixels ? q.h_totals[2] : ctx->cfg.pool_pixels;
-    if (tb) TH_CHECK_HIP(hipMemcpyAsync(q.h_blobs, q.d_blobs, sizeof(trexhip_blob) * tb, hipMemcpyDeviceToHost, s));
-    if (tr) TH_CHECK_HIP(hipMemcpyAsync(q.h_runs, q.d_runs, sizeof(trexhip_run) * tr, hipMemcpyDeviceToHost, s));
-    if (tp) TH_CHECK_HIP(hipMemcpyAsync(q.h_pixels, q.d_pixels, (size_t)tp * ctx->pix_ch, hipMemcpyDeviceToHost, s));
-    TH_CHECK_HIP(hipStreamSynchronize(s));
-    q.fetched = true;
-    out->total_blobs = tb; out->total_runs = tr; out->total_pixels = tp;
+    const int n = q.tables.valid_n;
+    int rc = fetch_info(ctx, q.tables);
+    if (rc == TREXHIP_OK) rc = fetch_tables(ctx, q.tables, true, out);
+    if (rc) return rc;
     for (int i = 0; i < n; ++i)
-        if (q.h_info[i].flags) { set_error("a frame exceeded capacity during re-threshold: raise max_runs/max_blobs/max_pixels"); return TREXHIP_E_CAPACITY; }
+        if (q.tables.h_info[i].flags) { set_error("a frame exceeded capacity during re-threshold: raise max_runs/max_blobs/max_pixels"); return TREXHIP_E_CAPACITY; }
     return TREXHIP_OK;
 }
 
 int trexhip_device_view_get(trexhip_ctx* ctx, trexhip_device_view* out) {
     if (!ctx || !out) { set_error("trexhip_device_view_get: null argument"); return TREXHIP_E_INVALID; }
-    out->frames = ctx->d_info; out->blobs = ctx->d_blobs; out->runs = ctx->d_runs; out->pixels = ctx->d_pixels;
-    out->totals = ctx->d_ctr + (size_t)ctx->p.max_batch * TREXHIP_CTR_STRIDE; out->blob_frame = ctx->d_blob_frame;
+    out->frames = ctx->tables.d_info; out->blobs = ctx->tables.d_blobs; out->runs = ctx->tables.d_runs; out->pixels = ctx->tables.d_pixels;
+    out->totals = ctx->tables.d_totals; out->blob_frame = ctx->tables.d_blob_frame;
     return TREXHIP_OK;
 }
 
 int trexhip_debug_read(trexhip_ctx* ctx, unsigned long long* out, int32_t n) {   /* dev only: phase stamps of k_ccl_lds */
     if (!ctx || !out) return TREXHIP_E_INVALID;
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    TH_CHECK_HIP(hipMemcpy(out, ctx->d_cnt_px, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+    TH_CHECK_HIP(hipMemcpy(out, ctx->label.d_cnt_px, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
     return TREXHIP_OK;
 }
 
@@ -621,9 +581,9 @@ int rethreshold_prepare(trexhip_ctx* ctx, const char* who, int32_t method, const
     if (!ctx) { set_error(w + ": null ctx"); return TREXHIP_E_INVALID; }
     if (method < 0 || method > 2) { set_error(w + ": method must be 0 (absolute), 1 (sign) or 2 (none)"); return TREXHIP_E_INVALID; }
     if (n_ranges < 0 || n_ranges > 8 || (n_ranges && !size_ranges)) { set_error(w + ": bad size ranges"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0) { set_error(w + ": no segmented batch"); return TREXHIP_E_INVALID; }
-    if (!ctx->fetched) { set_error(w + ": call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0) { set_error(w + ": no segmented batch"); return TREXHIP_E_INVALID; }
+    if (!ctx->tables.fetched) { set_error(w + ": call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    return pass2_alloc(ctx);
+    return pass2_alloc(ctx, who);
 }
 }

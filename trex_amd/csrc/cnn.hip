@@ -1379,7 +1379,7 @@ struct Net {
     uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
     uint8_t* crops = nullptr;
     float* h_probs = nullptr;                  // pinned
-    std::vector<void*> weights, batch;         // every device allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
+    Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
     // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one
     // identify call is captured into a hipGraph per (buffers, n, precision) and replayed
     // A chain is only captured once the same (buffers, n, precision) key has come THREE times: in tracking the blob count changes from
@@ -1407,32 +1407,17 @@ static void drop_graphs(Net* n) {
     n->graphs.clear();
 }
 
-// every device buffer is allocated through here and freed through the list it was put on
-template <class T>
-static int dev_alloc(std::vector<void*>& list, T** p, size_t bytes) {
-    void* q = nullptr;
-    TH_CHECK_HIP(hipMalloc(&q, bytes));
-    list.push_back(q);
-    *p = static_cast<T*>(q);
-    return TREXHIP_OK;
-}
-static void dev_free(std::vector<void*>& list) {
-    for (void* q : list) (void)hipFree(q);
-    list.clear();
-}
-
 static void free_net(Net* n) {
     if (!n) return;
     drop_graphs(n);
-    dev_free(n->weights);
-    dev_free(n->batch);
-    if (n->h_probs) (void)hipHostFree(n->h_probs);
+    n->weights.free_all();
+    n->batch.free_all();
     delete n;
 }
 
 template <class T>
 static int upload(Net* net, T** dst, const void* data, size_t bytes) {
-    const int rc = dev_alloc(net->weights, dst, bytes);
+    const int rc = net->weights.device_bytes(dst, bytes, "trexhip_load_weights");
     if (rc != TREXHIP_OK) return rc;
     TH_CHECK_HIP(hipMemcpy(*dst, data, bytes, hipMemcpyHostToDevice));
     return TREXHIP_OK;
@@ -1475,7 +1460,7 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     TRY(upload(net, &net->w3s, pack_bf16x3(c3.w, 64, 128)));
     TRY(upload(net, &net->w3h, &net->inv3h, pack_f16x2(c3.w, 64, 128)));
     if (at80) TRY(upload(net, &net->w3w, &net->inv3w, pack_wino_f16(c3.w, 64, 128)));
-    TRY(dev_alloc(net->weights, &net->d_ovf, 16 + (2 + FB_MAX) * 4));
+    TRY(net->weights.device_bytes(&net->d_ovf, 16 + (2 + FB_MAX) * 4, "trexhip_load_weights"));
     if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, 16 + (2 + FB_MAX) * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
     const Folded c3x = fold_conv(&wb.t[T_C3W], 128, 64, 32);
     TRY(upload(net, &net->w3, c3x.w)); TRY(upload(net, &net->b3, c3x.b));
@@ -1494,27 +1479,28 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
 static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     if (n <= net->max_crops) return TREXHIP_OK;
     drop_graphs(net);                                      // the captured chains point into the buffers that are replaced here
-    dev_free(net->batch);
-    if (net->h_probs) { (void)hipHostFree(net->h_probs); net->h_probs = nullptr; }
+    net->batch.free_all();
+    net->h_probs = nullptr;
     net->max_crops = 0;
-    std::vector<void*>& B = net->batch;
+    Mem& B = net->batch;
+    const char* who = "trexhip_identify_device";
     const size_t N = n;
     const size_t W = net->W, H = net->H;       // (80 x 80: 40 x 40 x 16, 20 x 20 x 64, 10 x 10 x 128)
-    int rc = dev_alloc(B, &net->d_ovfc, N);
-    TRY(dev_alloc(B, &net->act1, N * (H / 2) * (W / 2) * 16 * 4));
-    TRY(dev_alloc(B, &net->act2, N * (H / 4) * (W / 4) * 64 * 4));
-    TRY(dev_alloc(B, &net->act3, N * (H / 8) * (W / 8) * 128 * 4));
-    TRY(dev_alloc(B, &net->fc1, N * 128 * 4 * FC1_KSPLIT));
-    TRY(dev_alloc(B, &net->probs, N * net->classes * 4));
-    TRY(dev_alloc(B, &net->logits, N * net->classes * 4));
+    int rc = B.device_bytes(&net->d_ovfc, N, who);
+    TRY(B.device_bytes(&net->act1, N * (H / 2) * (W / 2) * 16 * 4, who));
+    TRY(B.device_bytes(&net->act2, N * (H / 4) * (W / 4) * 64 * 4, who));
+    TRY(B.device_bytes(&net->act3, N * (H / 8) * (W / 8) * 128 * 4, who));
+    TRY(B.device_bytes(&net->fc1, N * 128 * 4 * FC1_KSPLIT, who));
+    TRY(B.device_bytes(&net->probs, N * net->classes * 4, who));
+    TRY(B.device_bytes(&net->logits, N * net->classes * 4, who));
     if (W == 80 && H == 80) {                  // the Winograd-domain operand images of the 80 x 80 chain
-        TRY(dev_alloc(B, &net->v2, N * 40 * V2_ROWB));
-        TRY(dev_alloc(B, &net->v3, N * 20 * V3_ROWB));
+        TRY(B.device_bytes(&net->v2, N * 40 * V2_ROWB, who));
+        TRY(B.device_bytes(&net->v3, N * 20 * V3_ROWB, who));
     }
-    TRY(dev_alloc(B, &net->crops, N * net->W * net->H * net->CH));
+    TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
+    TRY(B.pinned(&net->h_probs, N * net->classes, who));
     if (rc != TREXHIP_OK) return rc;
     TH_CHECK_HIP(hipMemsetAsync(net->d_ovfc, 0, N, ctx->stream));      // on the stream its users run on; the plan kernel clears what it reads
-    TH_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&net->h_probs), N * net->classes * 4, hipHostMallocDefault));
     net->max_crops = n;
     return TREXHIP_OK;
 }

@@ -82,11 +82,11 @@ int launch_crops(trexhip_ctx* ctx, uint8_t* d_crops, int n, int OW, int OH, int 
     if (n <= 0) return TREXHIP_OK;
     SegCfg c = ctx->cfg;
     c.invert = ctx->batch_invert; c.zero_bg = ctx->batch_zero_bg;
-    c.B = ctx->last_n;
+    c.B = ctx->tables.valid_n;
     stage_begin(ctx, TREXHIP_STAGE_CROPS);
-    hipLaunchKernelGGL(k_crops_none, dim3(n), dim3(256), 0, ctx->stream, c, ctx->d_frames, ctx->d_bg, ctx->d_info,
-                       ctx->d_blob_frame, ctx->d_blobs, ctx->d_runs, d_crops, OW, OH, diff_mode, ctx->d_color_src, ctx->color_ch,
-                       ctx->p.pixel_encoding == TREXHIP_ENC_RGB8 ? 3 : 1, ctx->p.pixel_encoding, ctx->d_bg_color, ctx->bg_color_ch);
+    hipLaunchKernelGGL(k_crops_none, dim3(n), dim3(256), 0, ctx->stream, c, ctx->d_frames, ctx->d_bg, ctx->tables.d_info,
+                       ctx->tables.d_blob_frame, ctx->tables.d_blobs, ctx->tables.d_runs, d_crops, OW, OH, diff_mode, ctx->d_color_src, ctx->color_ch,
+                       ctx->p.pixel_encoding == TREXHIP_ENC_RGB8 ? 3 : 1, ctx->p.pixel_encoding, ctx->bg_color.as<uint8_t>(), ctx->bg_color_ch);
     stage_end(ctx, TREXHIP_STAGE_CROPS);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
@@ -98,7 +98,7 @@ int check_colour_difference(trexhip_ctx* ctx, int difference, const char* who) {
     if (ctx->p.pixel_encoding != TREXHIP_ENC_RGB8) {
         set_error(std::string(who) + ": r3g3b2 crops hold the colour codes: background-difference crops are not implemented for them"); return TREXHIP_E_UNSUPPORTED;
     }
-    if (!ctx->d_bg_color) { set_error(std::string(who) + ": background-difference crops of rgb8 pixels need the colour background (trexhip_set_background_color)"); return TREXHIP_E_INVALID; }
+    if (!ctx->bg_color.p) { set_error(std::string(who) + ": background-difference crops of rgb8 pixels need the colour background (trexhip_set_background_color)"); return TREXHIP_E_INVALID; }
     return TREXHIP_OK;
 }
 
@@ -120,8 +120,8 @@ int trexhip_crops_device(trexhip_ctx* ctx, uint8_t* d_crops, int32_t n_blobs, in
     if (out_w <= 0 || out_h <= 0 || (out_w * out_h) % 16 != 0) { set_error("trexhip_crops_device: output size must be a multiple of 16 bytes"); return TREXHIP_E_INVALID; }
     if (difference < 0 || difference > 2) { set_error("trexhip_crops_device: difference must be 0,1,2"); return TREXHIP_E_INVALID; }
     if (n_blobs < 0 || (uint32_t)n_blobs > ctx->cfg.pool_blobs) { set_error("trexhip_crops_device: n_blobs outside the blob pool"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0) { set_error("trexhip_crops_device: no segmented batch"); return TREXHIP_E_INVALID; }
-    if (!ctx->fetched) { set_error("trexhip_crops_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0) { set_error("trexhip_crops_device: no segmented batch"); return TREXHIP_E_INVALID; }
+    if (!ctx->tables.fetched) { set_error("trexhip_crops_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     if (normalization == TREXHIP_NORMALIZE_MOMENTS)      // transform from the blob table's integer moments, built on the device (midline.hip)
         return launch_crops_warp_device(ctx, d_crops, n_blobs, out_w, out_h, difference, nullptr, nullptr, false, 1.0f);
@@ -170,10 +170,10 @@ extern "C" int trexhip_export_id_table_device(trexhip_ctx* ctx, const float* d_p
     if (!ctx || !d_table) { trexhip::set_error("trexhip_export_id_table_device: null argument"); return TREXHIP_E_INVALID; }
     if (n_blobs < 0 || max_rows < n_blobs || classes < 0) { trexhip::set_error("trexhip_export_id_table_device: need 0 <= n_blobs <= max_rows"); return TREXHIP_E_INVALID; }
     if (max_rows == 0) return TREXHIP_OK;
-    if (!ctx->fetched) { trexhip::set_error("trexhip_export_id_table_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->tables.fetched) { trexhip::set_error("trexhip_export_id_table_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    hipLaunchKernelGGL(trexhip::k_id_table, dim3(max_rows), dim3(256), 0, ctx->stream, ctx->d_info, ctx->d_blob_frame, ctx->d_blobs,
-                       d_probs, n_blobs, classes, ctx->last_n, frame_base, static_cast<uint32_t*>(d_table), max_rows);
+    hipLaunchKernelGGL(trexhip::k_id_table, dim3(max_rows), dim3(256), 0, ctx->stream, ctx->tables.d_info, ctx->tables.d_blob_frame, ctx->tables.d_blobs,
+                       d_probs, n_blobs, classes, ctx->tables.valid_n, frame_base, static_cast<uint32_t*>(d_table), max_rows);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
 }
@@ -230,10 +230,10 @@ extern "C" int trexhip_export_id_table_ex_device(trexhip_ctx* ctx, const float* 
     if (n_blobs < 0 || max_rows < n_blobs || classes < 0 || midline_resolution < 0 || midline_resolution > 256) { trexhip::set_error("trexhip_export_id_table_ex_device: need 0 <= n_blobs <= max_rows, 0 <= midline_resolution <= 256"); return TREXHIP_E_INVALID; }
     if ((d_midline == nullptr) != (d_midline_info == nullptr)) { trexhip::set_error("trexhip_export_id_table_ex_device: midline points and infos come together"); return TREXHIP_E_INVALID; }
     if (max_rows == 0) return TREXHIP_OK;
-    if (!ctx->fetched) { trexhip::set_error("trexhip_export_id_table_ex_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->tables.fetched) { trexhip::set_error("trexhip_export_id_table_ex_device: call trexhip_fetch on the segmented batch first"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    hipLaunchKernelGGL(trexhip::k_id_table_ex, dim3(max_rows), dim3(256), 0, ctx->stream, ctx->d_info, ctx->d_blob_frame, ctx->d_blobs, d_probs,
-                       reinterpret_cast<const float4*>(d_midline), d_midline_info, n_blobs, classes, midline_resolution, ctx->last_n, frame_base,
+    hipLaunchKernelGGL(trexhip::k_id_table_ex, dim3(max_rows), dim3(256), 0, ctx->stream, ctx->tables.d_info, ctx->tables.d_blob_frame, ctx->tables.d_blobs, d_probs,
+                       reinterpret_cast<const float4*>(d_midline), d_midline_info, n_blobs, classes, midline_resolution, ctx->tables.valid_n, frame_base,
                        static_cast<uint32_t*>(d_table));
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
@@ -329,10 +329,8 @@ extern "C" int trexhip_segment_color(trexhip_ctx* ctx, const uint8_t* const* fra
     if ((W * H) % 4 != 0) { set_error("trexhip_segment_color: width*height must be a multiple of 4"); return TREXHIP_E_UNSUPPORTED; }
     if ((size_t)stride < W * channels) { set_error("trexhip_segment_color: stride < width*channels"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    if (n == 0) { ctx->last_n = 0; ctx->fetched = false; return TREXHIP_OK; }
-    if (!ctx->d_staging) {
-        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_staging), (size_t)ctx->p.max_batch * W * H + 16));
-    }
+    if (n == 0) { ctx->tables.valid_n = 0; ctx->tables.fetched = false; return TREXHIP_OK; }
+    if (int rc = ensure_staging(ctx, "trexhip_segment_color")) return rc;
     for (int i = 0; i < n; ++i)
         if (!frames[i]) { set_error("trexhip_segment_color: null frame pointer"); return TREXHIP_E_INVALID; }
     const size_t row = W * channels, fpx = W * H;
@@ -344,7 +342,7 @@ extern "C" int trexhip_segment_color(trexhip_ctx* ctx, const uint8_t* const* fra
         ctx->d_color_src = nullptr; ctx->color_ch = 0;
         return launch_segment(ctx, ctx->d_staging, n);
     }
-    if (!ctx->d_color) TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_color), (size_t)ctx->p.max_batch * W * H * 4 + 16));
+    if (!ctx->d_color) { if (int rc = ctx->mem.device(&ctx->d_color, (size_t)ctx->p.max_batch * W * H * 4 + 16, "trexhip_segment_color")) return rc; }
     // frame by frame: pageable tile -> pinned ring slot (host threads) -> HBM (DMA on the copy stream) -> cv::cvtColor on the compute
     // stream as soon as the frame has landed; the next frame's staging and DMA run meanwhile (upload.hip)
     int rc = upload_frames(ctx, frames, n, H, row, (size_t)stride, ctx->d_color, [&](int i0, int cnt) {
@@ -366,10 +364,8 @@ extern "C" int trexhip_segment_color_device(trexhip_ctx* ctx, const uint8_t* d_c
     if ((W * H) % 4 != 0) { set_error("trexhip_segment_color_device: width*height must be a multiple of 4"); return TREXHIP_E_UNSUPPORTED; }
     if (reinterpret_cast<uintptr_t>(d_color_frames) & 3) { set_error("trexhip_segment_color_device: colour frames must be 4-byte aligned"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    if (n == 0) { ctx->last_n = 0; ctx->fetched = false; return TREXHIP_OK; }
-    if (!ctx->d_staging) {
-        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_staging), (size_t)ctx->p.max_batch * W * H + 16));
-    }
+    if (n == 0) { ctx->tables.valid_n = 0; ctx->tables.fetched = false; return TREXHIP_OK; }
+    if (int rc = ensure_staging(ctx, "trexhip_segment_color_device")) return rc;
     int rc = launch_to_gray(ctx, d_color_frames, ctx->d_staging, (size_t)n * W * H, channels, color_channel);
     if (rc) return rc;
     ctx->d_color_src = d_color_frames; ctx->color_ch = channels;
@@ -382,7 +378,7 @@ extern "C" int trexhip_segment_color_device(trexhip_ctx* ctx, const uint8_t* d_c
 static int set_background_color_common(trexhip_ctx* ctx, int32_t channels, int32_t color_channel) {
     using namespace trexhip;
     const size_t W = ctx->p.width, H = ctx->p.height;
-    int rc = launch_to_gray(ctx, ctx->d_bg_color, ctx->d_bg, W * H, channels, color_channel >= channels ? -1 : color_channel);
+    int rc = launch_to_gray(ctx, ctx->bg_color.as<uint8_t>(), ctx->d_bg, W * H, channels, color_channel >= channels ? -1 : color_channel);
     if (rc) return rc;
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     ctx->bg_color_ch = channels;
@@ -395,16 +391,14 @@ static int alloc_background_color(trexhip_ctx* ctx, int32_t channels) {
     if (channels != 3 && channels != 4) { set_error("trexhip_set_background_color: channels must be 3 (BGR) or 4 (BGRA)"); return TREXHIP_E_INVALID; }
     if ((W * H) % 4 != 0) { set_error("trexhip_set_background_color: width*height must be a multiple of 4"); return TREXHIP_E_UNSUPPORTED; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    if (ctx->d_bg_color && ctx->bg_color_ch != channels) { (void)hipFree(ctx->d_bg_color); ctx->d_bg_color = nullptr; ctx->bg_color_ch = 0; }
-    if (!ctx->d_bg_color) TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_bg_color), W * H * (size_t)channels));
-    return TREXHIP_OK;
+    return ctx->bg_color.reserve(ctx, W * H * (size_t)channels, "trexhip_set_background_color");
 }
 extern "C" int trexhip_set_background_color(trexhip_ctx* ctx, const uint8_t* bgr, int32_t stride, int32_t channels, int32_t color_channel) {
     using namespace trexhip;
     if (!ctx || !bgr) { set_error("trexhip_set_background_color: null argument"); return TREXHIP_E_INVALID; }
     if (stride < ctx->p.width * channels) { set_error("trexhip_set_background_color: stride < width * channels"); return TREXHIP_E_INVALID; }
     if (int rc = alloc_background_color(ctx, channels)) return rc;
-    TH_CHECK_HIP(hipMemcpy2DAsync(ctx->d_bg_color, (size_t)ctx->p.width * channels, bgr, stride, (size_t)ctx->p.width * channels, ctx->p.height,
+    TH_CHECK_HIP(hipMemcpy2DAsync(ctx->bg_color.as<uint8_t>(), (size_t)ctx->p.width * channels, bgr, stride, (size_t)ctx->p.width * channels, ctx->p.height,
                                   hipMemcpyHostToDevice, ctx->stream));
     return set_background_color_common(ctx, channels, color_channel);
 }
@@ -412,7 +406,7 @@ extern "C" int trexhip_set_background_color_device(trexhip_ctx* ctx, const uint8
     using namespace trexhip;
     if (!ctx || !d_bgr) { set_error("trexhip_set_background_color_device: null argument"); return TREXHIP_E_INVALID; }
     if (int rc = alloc_background_color(ctx, channels)) return rc;
-    TH_CHECK_HIP(hipMemcpyAsync(ctx->d_bg_color, d_bgr, (size_t)ctx->p.width * ctx->p.height * channels, hipMemcpyDeviceToDevice, ctx->stream));
+    TH_CHECK_HIP(hipMemcpyAsync(ctx->bg_color.as<uint8_t>(), d_bgr, (size_t)ctx->p.width * ctx->p.height * channels, hipMemcpyDeviceToDevice, ctx->stream));
     return set_background_color_common(ctx, channels, color_channel);
 }
 
@@ -667,24 +661,15 @@ __global__ __launch_bounds__(256) void k_crops_warp(const SegCfg c, const uint8_
     }
 }
 
-static int ensure_warp(trexhip_ctx* ctx, int n) {
-    if (ctx->warp_cap >= n) return TREXHIP_OK;
-    if (ctx->d_warp) (void)hipFree(ctx->d_warp);
-    ctx->d_warp = nullptr; ctx->warp_cap = 0;
-    TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_warp), (size_t)n * 6 * sizeof(double)));
-    ctx->warp_cap = n;
-    return TREXHIP_OK;
-}
-
-// the warp itself, from the per-blob inverse maps in ctx->d_warp
+// the warp itself, from the per-blob inverse maps in ctx->warp
 int launch_crops_warp_maps(trexhip_ctx* ctx, uint8_t* d_crops, int n, int OW, int OH, int diff_mode) {
     SegCfg c = ctx->cfg;
     c.invert = ctx->batch_invert; c.zero_bg = ctx->batch_zero_bg;
-    c.B = ctx->last_n;
+    c.B = ctx->tables.valid_n;
     stage_begin(ctx, TREXHIP_STAGE_CROPS);
-    hipLaunchKernelGGL(k_crops_warp, dim3(n), dim3(256), 0, ctx->stream, c, ctx->d_frames, ctx->d_bg, ctx->d_info, ctx->d_blob_frame,
-                       ctx->d_blobs, ctx->d_runs, ctx->d_warp, d_crops, OW, OH, diff_mode, ctx->d_color_src, ctx->color_ch,
-                       ctx->p.pixel_encoding == TREXHIP_ENC_RGB8 ? 3 : 1, ctx->p.pixel_encoding, ctx->d_bg_color, ctx->bg_color_ch);
+    hipLaunchKernelGGL(k_crops_warp, dim3(n), dim3(256), 0, ctx->stream, c, ctx->d_frames, ctx->d_bg, ctx->tables.d_info, ctx->tables.d_blob_frame,
+                       ctx->tables.d_blobs, ctx->tables.d_runs, ctx->warp.as<double>(), d_crops, OW, OH, diff_mode, ctx->d_color_src, ctx->color_ch,
+                       ctx->p.pixel_encoding == TREXHIP_ENC_RGB8 ? 3 : 1, ctx->p.pixel_encoding, ctx->bg_color.as<uint8_t>(), ctx->bg_color_ch);
     stage_end(ctx, TREXHIP_STAGE_CROPS);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
@@ -701,13 +686,11 @@ int launch_crops_warp(trexhip_ctx* ctx, uint8_t* d_crops, int n, int OW, int OH,
         std::memcpy(tr.m, tr6 + (size_t)i * 6, sizeof(tr.m));
         compose_and_invert(tr, lengths ? lengths[i] : 0.f, legacy, OW, OH, scale, &minv[(size_t)i * 6]);
     }
-    if (int rc = ensure_warp(ctx, n)) return rc;
-    TH_CHECK_HIP(hipMemcpyAsync(ctx->d_warp, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = ctx->warp.reserve(ctx, minv.size() * sizeof(double), "trexhip_crops_transformed_device")) return rc;
+    TH_CHECK_HIP(hipMemcpyAsync(ctx->warp.p, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));        // minv lives on this stack frame
     return launch_crops_warp_maps(ctx, d_crops, n, OW, OH, diff_mode);
 }
-
-int warp_reserve(trexhip_ctx* ctx, int n) { return ensure_warp(ctx, n); }
 
 }  // namespace trexhip
 
@@ -717,7 +700,7 @@ extern "C" int trexhip_crops_transformed_device(trexhip_ctx* ctx, uint8_t* d_cro
     using namespace trexhip;
     if (!ctx || !d_crops || !transforms) { set_error("trexhip_crops_transformed_device: null argument"); return TREXHIP_E_INVALID; }
     if (out_w <= 0 || out_h <= 0 || difference < 0 || difference > 2) { set_error("trexhip_crops_transformed_device: bad argument"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0 || !ctx->fetched) { set_error("trexhip_crops_transformed_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0 || !ctx->tables.fetched) { set_error("trexhip_crops_transformed_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
     if (n_blobs < 0 || (uint32_t)n_blobs > ctx->cfg.pool_blobs) { set_error("trexhip_crops_transformed_device: n_blobs outside the blob pool"); return TREXHIP_E_INVALID; }
     if (n_blobs == 0) return TREXHIP_OK;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));

@@ -53,25 +53,64 @@ struct Stage {
 }  // namespace trexhip
 
 namespace trexhip {
-// second CCL pass (track-stage re-threshold): its own run-level state and pooled outputs
-struct Pass2 {
-    bool allocated = false;
-    int valid_n = 0;
-    bool fetched = false;               // the host tables below hold the last re-threshold batch
-    uint32_t *d_sub_cnt = nullptr, *d_sub_base = nullptr, *d_row_base = nullptr, *d_row_cnt = nullptr, *d_run_parent = nullptr;
-    trexhip_run* d_raster = nullptr;
-    uint32_t *d_parent = nullptr, *d_root_ord = nullptr, *d_cnt_runs = nullptr, *d_cnt_px = nullptr, *d_cur_run = nullptr,
-             *d_pix_begin = nullptr, *d_totals = nullptr, *d_blob_frame = nullptr;
-    int32_t* d_blob_map = nullptr;
-    trexhip_frame_info* d_info = nullptr;
-    trexhip_blob* d_blobs = nullptr;
-    trexhip_run* d_runs = nullptr;
-    uint8_t* d_pixels = nullptr;
+// every device and pinned-host allocation of a context, a network or a trainer is handed out here, remembered, and freed in one call (mem.hip).
+// A count of 0 is treated as 1.  A failed allocation is reported the same way everywhere: out of memory is TREXHIP_E_NOMEM with a message that
+// names the entry point (`who`), any other HIP failure TREXHIP_E_DEVICE.
+struct Mem {
+    std::vector<void*> dev, host;
+    int alloc(void** p, size_t bytes, bool pinned, const char* who);
+    template <typename T> int device_bytes(T** p, size_t bytes, const char* who) { return alloc(reinterpret_cast<void**>(p), bytes, false, who); }
+    template <typename T> int device(T** p, size_t count, const char* who) { return device_bytes(p, (count ? count : 1) * sizeof(T), who); }
+    template <typename T> int pinned(T** p, size_t count, const char* who) { return alloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T), true, who); }
+    void release(void* d);      // one device buffer ahead of the rest (Scratch::reserve)
+    void free_all();
+};
+
+// a grow-on-demand device buffer of the context, sized in bytes.  reserve() does nothing while the buffer is large enough; otherwise it waits for
+// the context's stream (an earlier call may still read the old buffer), frees it and allocates `need` bytes from ctx->mem.
+struct Scratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int reserve(trexhip_ctx* ctx, size_t need, const char* who);
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+// the pooled output tables of one CCL pass and their pinned host mirrors
+struct BlobTables {
+    trexhip_frame_info* d_info = nullptr;  // [B]
+    trexhip_blob* d_blobs = nullptr;       // [B*NB] pooled
+    uint32_t* d_blob_frame = nullptr;      // [B*NB]
+    trexhip_run* d_runs = nullptr;         // [B*R] pooled, grouped by blob
+    uint8_t* d_pixels = nullptr;           // [B*P*pix_ch] pooled
+    uint32_t* d_totals = nullptr;          // [4] pooled totals: blobs, runs, pixels (pass 1: the words behind ctx->d_ctr's per-frame counters)
     trexhip_frame_info* h_info = nullptr;
     uint32_t* h_totals = nullptr;
     trexhip_blob* h_blobs = nullptr;
     trexhip_run* h_runs = nullptr;
     uint8_t* h_pixels = nullptr;
+    int valid_n = 0;                       // frames of the batch the device tables hold
+    bool fetched = false;                  // the host mirrors hold that batch
+};
+// the per-run labelling arrays of one CCL pass
+struct LabelState {
+    uint32_t* d_row_cnt = nullptr;      // [B*H]
+    uint32_t* d_row_base = nullptr;     // [B*(H+1)] exclusive scan of row_cnt = raster index
+    trexhip_run* d_raster = nullptr;    // [B*R]   runs in raster order
+    uint32_t* d_parent = nullptr;       // [B*R]   union-find parent -> root label
+    uint32_t* d_root_ord = nullptr;     // [B*R]   ordinal of the raw blob rooted at run r
+    uint32_t* d_cnt_runs = nullptr;     // [B*R]   per raw blob
+    uint32_t* d_cnt_px = nullptr;       // [B*R]
+    uint32_t* d_cur_run = nullptr;      // [B*R]   frame-relative run cursor per raw blob
+    uint32_t* d_pix_begin = nullptr;    // [B*R]   frame-relative pixel begin per raw blob
+    int32_t* d_blob_map = nullptr;      // [B*R]   raw blob ordinal -> kept index or -1
+};
+// second CCL pass (track-stage re-threshold): its own tables and labelling state, allocated on first use
+struct Pass2 {
+    bool allocated = false;
+    Mem mem;
+    BlobTables tables;
+    LabelState label;
+    uint32_t *d_sub_cnt = nullptr, *d_sub_base = nullptr, *d_run_parent = nullptr;   // [B*R]
 };
 }
 
@@ -98,61 +137,33 @@ struct trexhip_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     bool has_bg = false;
-    int last_n = 0;
     int batch_invert = 0, batch_zero_bg = 0;      // image_invert / zero_is_background the LAST segmented batch was taken with: its crops, re-threshold and
                                                   // split search keep them although trexhip_update_params may have changed the live settings since
-    bool fetched = true;
 
     // device memory (layout: DESIGN.md "Data layout in HBM")
+    trexhip::Mem mem;                   // owns every buffer below
+    trexhip::BlobTables tables;         // pass 1: valid_n frames of the last segmented / loaded batch
+    trexhip::LabelState label;
     uint8_t* d_bg = nullptr;
     uint8_t* d_staging = nullptr;       // frames uploaded by the host-pointer API
     const uint8_t* d_frames = nullptr;  // frames of the last segment call
-    uint32_t* d_ctr = nullptr;          // [B*CTR_STRIDE] per-frame overflow counters (128 B apart) + [4] pooled totals
+    uint32_t* d_ctr = nullptr;          // [B*CTR_STRIDE] per-frame overflow counters (128 B apart) + [4] pooled totals (tables.d_totals)
     uint32_t* d_band_fail = nullptr;    // [B] a band of the frame held more lines than k_ccl_band's workgroup takes (k_ccl_lds reads and clears it)
-    uint32_t* d_row_cnt = nullptr;      // [B*H]
     uint32_t* d_row_off = nullptr;      // [B*H]   offset of the row's runs in tmp order
-    uint32_t* d_row_base = nullptr;     // [B*(H+1)] exclusive scan of row_cnt = raster index
     uint32_t* d_tmp_runs = nullptr;     // [B*T]   x0 | x1 << 16; T = H*ROW_SLOT (row slots) + R (overflow area)
-    trexhip_run* d_raster = nullptr;    // [B*R]   runs in raster order
-    uint32_t* d_parent = nullptr;       // [B*R]   union-find parent -> root label
-    uint32_t* d_root_ord = nullptr;     // [B*R]   ordinal of the raw blob rooted at run r
-    uint32_t* d_cnt_runs = nullptr;     // [B*R]   per raw blob
-    uint32_t* d_cnt_px = nullptr;       // [B*R]
-    uint32_t* d_cur_run = nullptr;      // [B*R]   frame-relative run cursor per raw blob
-    uint32_t* d_pix_begin = nullptr;    // [B*R]   frame-relative pixel begin per raw blob
-    int32_t* d_blob_map = nullptr;      // [B*R]   raw blob ordinal -> kept index or -1
-    trexhip_frame_info* d_info = nullptr;  // [B]
-    trexhip_blob* d_blobs = nullptr;       // [B*NB] pooled
-    uint32_t* d_blob_frame = nullptr;      // [B*NB]
-    trexhip_run* d_runs = nullptr;         // [B*R] pooled, grouped by blob
-    uint8_t* d_pixels = nullptr;           // [B*P] pooled
-
-    // pinned host mirrors for trexhip_fetch
-    trexhip_frame_info* h_info = nullptr;
-    uint32_t* h_totals = nullptr;
-    trexhip_blob* h_blobs = nullptr;
-    trexhip_run* h_runs = nullptr;
-    uint8_t* h_pixels = nullptr;
-    uint8_t* h_staging = nullptr;       // pinned upload buffer
-    double* d_warp = nullptr;           // per-blob inverse affine maps of the normalised crops
-    int warp_cap = 0;
-    float* d_len = nullptr;             // per-blob (median) midline lengths handed in by the caller
-    int len_cap = 0;
-    int32_t* d_aug_idx = nullptr;       // index list of the last trexhip_augment_device call (copied in stream order, so one buffer serves every call)
-    int aug_idx_cap = 0;
-    uint8_t* d_val = nullptr;           // scratch and results of trexhip_validation_metrics_device (validate.hip), grown on demand
-    size_t val_cap = 0;
-    uint8_t* d_avg = nullptr;           // scratch and results of trexhip_class_averages_device (averages.hip), grown on demand
-    size_t avg_cap = 0;
-    uint8_t* d_vf = nullptr;            // scratch of trexhip_visual_field_device (visual_field.hip): flag, tessellated outlines; grown on demand
-    size_t vf_cap = 0;
-    void* d_auto = nullptr;             // scratch of trexhip_posture_auto_device (thresholds, selections, first outlines)
-    void* d_pre = nullptr;              // second counts and sequence scratch of trexhip_prefilter_device (prefilter.hip), allocated on its first call
-    void* d_load = nullptr;             // blob index and frame counts of trexhip_load_frames_v6_device (unpack.hip), allocated on its first call
-    size_t auto_cap = 0;
+    // grown on demand
+    trexhip::Scratch warp;              // double[6] per blob: inverse affine maps of the normalised crops
+    trexhip::Scratch len;               // float per blob: (median) midline lengths handed in by the caller (midline.hip); u64 per frame: timestamps (pack.hip)
+    trexhip::Scratch aug_idx;           // int32: index list of the last trexhip_augment_device call (copied in stream order, so one buffer serves every call)
+    trexhip::Scratch val;               // scratch and results of trexhip_validation_metrics_device (validate.hip)
+    trexhip::Scratch avg;               // scratch and results of trexhip_class_averages_device (averages.hip)
+    trexhip::Scratch vf;                // scratch of trexhip_visual_field_device (visual_field.hip): flag, tessellated outlines
+    trexhip::Scratch autos;             // scratch of trexhip_posture_auto_device (thresholds, selections, first outlines)
+    trexhip::Scratch pre;               // second counts and sequence scratch of trexhip_prefilter_device (prefilter.hip), fixed size
+    trexhip::Scratch load;              // blob index and frame counts of trexhip_load_frames_v6_device (unpack.hip), fixed size
+    trexhip::Scratch bg_color;          // colour background ([H][W][bg_color_ch]) for the difference crops of the rgb8 encoding
     uint32_t* d_bits[2] = {nullptr, nullptr};   // 1 bit/pixel masks for the optional morphology [B][H][ceil(W/32)]
     uint8_t* d_color = nullptr;         // BGR/BGRA frames of the colour-input API
-    uint8_t* h_color = nullptr;
 
     void* net = nullptr;                // trexhip::Net (cnn.hip)
     trexhip::Pass2 pass2;
@@ -172,7 +183,6 @@ struct trexhip_ctx {
     int pix_ch = 1;                     // bytes per output pixel (pixel_encoding)
     const uint8_t* d_color_src = nullptr; // colour frames of the last segment_color* call ([n][H][W][color_ch])
     int color_ch = 0;
-    uint8_t* d_bg_color = nullptr;      // colour background ([H][W][bg_color_ch]) for the difference crops of the rgb8 encoding
     int bg_color_ch = 0;
     int n_cus = 256;                    // compute units of the device (persistent kernels size their grids with it)
     int tune_seg_groups = 1;            // >1: pixel pass of frame group g+1 on the caller stream, labelling of g on an auxiliary stream (TREXHIP_SEG_GROUPS); measured SLOWER (cross-stream events cost 30-50 us each: 159 -> 266 us at 2 groups), kept off
@@ -215,6 +225,7 @@ int rethreshold_prepare(trexhip_ctx* ctx, const char* who, int32_t method, const
 int launch_prefilter(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const trexhip_prefilter_tables* tb, uint8_t* d_decision, int32_t* d_order,
                      int32_t* d_counts, int32_t* d_presumed_nr);
 int launch_to_gray(trexhip_ctx* ctx, const uint8_t* d_color, uint8_t* d_gray, size_t npix, int channels, int color_channel);
+int ensure_staging(trexhip_ctx* ctx, const char* who);   // ctx->d_staging, allocated on first use (mem.hip)
 void upload_free(trexhip_ctx* ctx);
 int upload_frames(trexhip_ctx* ctx, const uint8_t* const* frames, int n, size_t rows, size_t row_bytes, size_t stride, uint8_t* d_dst,
                   const std::function<int(int, int)>& after_chunk, int reduce_channels = 0, int color_channel = -1);

@@ -171,7 +171,6 @@ __global__ __launch_bounds__(64) void k_midline(const MidlineCfg C, const trexhi
 }
 
 int launch_crops_warp_maps(trexhip_ctx* ctx, uint8_t* d_crops, int n, int OW, int OH, int diff_mode);
-int warp_reserve(trexhip_ctx* ctx, int n);
 int check_colour_difference(trexhip_ctx* ctx, int difference, const char* who);
 
 // per-blob inverse affine maps of the normalised crops, on the device (no host round trip): one thread per blob.
@@ -203,8 +202,8 @@ __global__ __launch_bounds__(64) void k_warp_maps(const trexhip_midline_info* __
 int launch_crops_warp_device(trexhip_ctx* ctx, uint8_t* d_crops, int n, int OW, int OH, int diff_mode, const trexhip_midline_info* d_minfo,
                              const float* d_lengths, bool legacy, float scale) {
     if (int rc = check_colour_difference(ctx, diff_mode, "normalised crops")) return rc;
-    if (int rc = warp_reserve(ctx, n)) return rc;
-    hipLaunchKernelGGL(k_warp_maps, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d_minfo, d_lengths, ctx->d_blobs, n, legacy ? 1 : 0, OW, OH, scale, ctx->d_warp);
+    if (int rc = ctx->warp.reserve(ctx, (size_t)n * 6 * sizeof(double), "trexhip_crops_posture_device")) return rc;
+    hipLaunchKernelGGL(k_warp_maps, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d_minfo, d_lengths, ctx->tables.d_blobs, n, legacy ? 1 : 0, OW, OH, scale, ctx->warp.as<double>());
     TH_CHECK_HIP(hipGetLastError());
     return launch_crops_warp_maps(ctx, d_crops, n, OW, OH, diff_mode);
 }
@@ -246,7 +245,7 @@ extern "C" int trexhip_crops_posture_device(trexhip_ctx* ctx, uint8_t* d_crops, 
                                             float image_scale, int32_t difference) {
     if (!ctx || !d_crops || !d_midline_info) { set_error("trexhip_crops_posture_device: null argument"); return TREXHIP_E_INVALID; }
     if (out_w <= 0 || out_h <= 0 || difference < 0 || difference > 2) { set_error("trexhip_crops_posture_device: bad argument"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0 || !ctx->fetched) { set_error("trexhip_crops_posture_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0 || !ctx->tables.fetched) { set_error("trexhip_crops_posture_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
     if (n_blobs < 0 || (uint32_t)n_blobs > ctx->cfg.pool_blobs) { set_error("trexhip_crops_posture_device: n_blobs outside the blob pool"); return TREXHIP_E_INVALID; }
     if (n_blobs == 0) return TREXHIP_OK;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
@@ -254,14 +253,9 @@ extern "C" int trexhip_crops_posture_device(trexhip_ctx* ctx, uint8_t* d_crops, 
     // The optional per-blob (median) midline lengths are a host array: they are uploaded into a buffer of the context.
     const float* d_len = nullptr;
     if (midline_lengths) {
-        if (ctx->len_cap < n_blobs) {
-            if (ctx->d_len) (void)hipFree(ctx->d_len);
-            ctx->d_len = nullptr; ctx->len_cap = 0;
-            TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_len), (size_t)n_blobs * sizeof(float)));
-            ctx->len_cap = n_blobs;
-        }
-        TH_CHECK_HIP(hipMemcpyAsync(ctx->d_len, midline_lengths, (size_t)n_blobs * sizeof(float), hipMemcpyHostToDevice, ctx->stream));   // pageable source: staged before the call returns
-        d_len = ctx->d_len;
+        if (int rc = ctx->len.reserve(ctx, (size_t)n_blobs * sizeof(float), "trexhip_crops_posture_device")) return rc;
+        TH_CHECK_HIP(hipMemcpyAsync(ctx->len.p, midline_lengths, (size_t)n_blobs * sizeof(float), hipMemcpyHostToDevice, ctx->stream));   // pageable source: staged before the call returns
+        d_len = ctx->len.as<float>();
     }
     return launch_crops_warp_device(ctx, d_crops, n_blobs, out_w, out_h, difference, d_midline_info, d_len, use_legacy != 0, image_scale);
 }

@@ -109,25 +109,20 @@ using namespace trexhip;
 
 extern "C" int trexhip_pack_frames_v6_device(trexhip_ctx* ctx, const uint64_t* timestamps, uint8_t* d_out, size_t capacity, uint64_t* d_offsets) {
     if (!ctx || !d_out || !d_offsets) { set_error("trexhip_pack_frames_v6_device: null argument"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0 || !ctx->fetched) { set_error("trexhip_pack_frames_v6_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0 || !ctx->tables.fetched) { set_error("trexhip_pack_frames_v6_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
     if (ctx->p.pixel_encoding != TREXHIP_ENC_GRAY) { set_error("trexhip_pack_frames_v6_device: the V_6 layout holds one byte per pixel (gray); colour encodings came with V_12"); return TREXHIP_E_UNSUPPORTED; }
     if (ctx->p.width > 32768) { set_error("trexhip_pack_frames_v6_device: LegacyShortHorizontalLine holds x1 < 32768 (pv.h:36)"); return TREXHIP_E_UNSUPPORTED; }
     if (ctx->p.max_blobs > 65535) { set_error("trexhip_pack_frames_v6_device: a frame holds at most 65535 objects (u16 n, pv.cpp:686)"); return TREXHIP_E_UNSUPPORTED; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    const int n = ctx->last_n;
+    const int n = ctx->tables.valid_n;
     unsigned long long* d_ts = nullptr;
     if (timestamps) {
-        if (ctx->len_cap < 2 * n) {                                 // the context's small scratch buffer (floats): 2 per frame hold a u64
-            if (ctx->d_len) (void)hipFree(ctx->d_len);
-            ctx->d_len = nullptr; ctx->len_cap = 0;
-            TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_len), (size_t)2 * n * sizeof(float)));
-            ctx->len_cap = 2 * n;
-        }
-        d_ts = reinterpret_cast<unsigned long long*>(ctx->d_len);
+        if (int rc = ctx->len.reserve(ctx, (size_t)n * 8, "trexhip_pack_frames_v6_device")) return rc;     // the context's small upload buffer: a u64 per frame
+        d_ts = ctx->len.as<unsigned long long>();
         TH_CHECK_HIP(hipMemcpyAsync(d_ts, timestamps, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     }
-    hipLaunchKernelGGL(k_pack_sizes, dim3(1), dim3(256), 0, ctx->stream, ctx->d_info, ctx->d_blobs, n, reinterpret_cast<unsigned long long*>(d_offsets));
-    hipLaunchKernelGGL(k_pack, dim3(n), dim3(256), 0, ctx->stream, ctx->d_info, ctx->d_blobs, ctx->d_runs, ctx->d_pixels,
+    hipLaunchKernelGGL(k_pack_sizes, dim3(1), dim3(256), 0, ctx->stream, ctx->tables.d_info, ctx->tables.d_blobs, n, reinterpret_cast<unsigned long long*>(d_offsets));
+    hipLaunchKernelGGL(k_pack, dim3(n), dim3(256), 0, ctx->stream, ctx->tables.d_info, ctx->tables.d_blobs, ctx->tables.d_runs, ctx->tables.d_pixels,
                        reinterpret_cast<const unsigned long long*>(d_offsets), d_ts, (unsigned long long)capacity, d_out);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;

@@ -866,21 +866,20 @@ extern "C" int trexhip_posture_device(trexhip_ctx* ctx, int32_t table, const tre
     if (pp->posture_closing_steps != 0) { set_error("trexhip_posture_device: posture_closing_steps > 0 is not implemented (closing inside pixel::threshold_get_biggest_blob, Posture.cpp:335)"); return TREXHIP_E_UNSUPPORTED; }
     if (pp->peak_mode != 0) { set_error("trexhip_posture_device: peak_mode = broad is not implemented (needs periodic::find_peaks' peak ranges / integrals, Outline.cpp:627-661); only pointy"); return TREXHIP_E_UNSUPPORTED; }
     if (pp->posture_direction_smoothing < 0) { set_error("trexhip_posture_device: posture_direction_smoothing must not be negative"); return TREXHIP_E_INVALID; }   // (> 1: the caller hands the movement direction to trexhip_midline_movement_device)
-    if (!ctx->d_frames || ctx->last_n == 0 || !ctx->fetched) { set_error("trexhip_posture_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0 || !ctx->tables.fetched) { set_error("trexhip_posture_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
     if (n_blobs < 0 || (uint32_t)n_blobs > ctx->cfg.pool_blobs) { set_error("trexhip_posture_device: n_blobs outside the blob pool"); return TREXHIP_E_INVALID; }
     if (n_blobs == 0) return TREXHIP_OK;
-    const trexhip_frame_info* info = ctx->d_info; const uint32_t* bf = ctx->d_blob_frame; const trexhip_blob* bl = ctx->d_blobs; const trexhip_run* ru = ctx->d_runs;
     if (table == 1) {
-        if (!ctx->pass2.allocated || ctx->pass2.valid_n == 0) { set_error("trexhip_posture_device: no re-thresholded batch"); return TREXHIP_E_INVALID; }
-        info = ctx->pass2.d_info; bf = ctx->pass2.d_blob_frame; bl = ctx->pass2.d_blobs; ru = ctx->pass2.d_runs;
+        if (!ctx->pass2.allocated || ctx->pass2.tables.valid_n == 0) { set_error("trexhip_posture_device: no re-thresholded batch"); return TREXHIP_E_INVALID; }
     } else if (table != 0) { set_error("trexhip_posture_device: table must be 0 (detect) or 1 (re-threshold)"); return TREXHIP_E_INVALID; }
+    const BlobTables& t = table == 0 ? ctx->tables : ctx->pass2.tables;
+    const trexhip_frame_info* info = t.d_info; const uint32_t* bf = t.d_blob_frame; const trexhip_blob* bl = t.d_blobs; const trexhip_run* ru = t.d_runs;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     // line / row capacity of this launch from the fetched host tables (full capacity when they are not at hand)
     int nr_cap = P_NR, rows_cap = P_ROWS;
     {
-        const trexhip_blob* hb = table == 0 ? ctx->h_blobs : ctx->pass2.h_blobs;
-        const bool fetched = table == 0 ? ctx->fetched : ctx->pass2.fetched;
-        if (hb && fetched) {
+        const trexhip_blob* hb = t.h_blobs;
+        if (hb && t.fetched) {
             uint32_t mr = 1, mrows = 1;
             for (int i = 0; i < n_blobs; ++i) {
                 const trexhip_blob& b = hb[i];
@@ -911,7 +910,7 @@ extern "C" int trexhip_posture_device(trexhip_ctx* ctx, int32_t table, const tre
     if (const char* e = std::getenv("TREXHIP_POSTURE_WALK_GROUP")) P.walk_group = std::atoi(e);
 #endif
     stage_begin(ctx, TREXHIP_STAGE_POSTURE);
-    hipLaunchKernelGGL(k_posture, dim3((n_blobs + wpb - 1) / wpb), dim3(wpb * 64), lds_bytes, ctx->stream, P, info, bf, bl, ru, n_blobs, ctx->last_n,
+    hipLaunchKernelGGL(k_posture, dim3((n_blobs + wpb - 1) / wpb), dim3(wpb * 64), lds_bytes, ctx->stream, P, info, bf, bl, ru, n_blobs, ctx->tables.valid_n,
                        reinterpret_cast<float2*>(d_outline), reinterpret_cast<float4*>(d_segments), d_info, (const int32_t*)nullptr, (const trexhip_blob*)nullptr);
     launch_posture_walk(ctx->stream, pp, P.walk_group, n_blobs, d_outline, d_segments, d_info);
     stage_end(ctx, TREXHIP_STAGE_POSTURE);
@@ -1015,13 +1014,8 @@ extern "C" int trexhip_posture_auto_device(trexhip_ctx* ctx, const trexhip_postu
     const int n = n_blobs, MPt = pp->max_points;
     // scratch of the loop, kept by the context
     const size_t need = (size_t)n * (6 * sizeof(int32_t) + sizeof(unsigned long long) + (size_t)MPt * sizeof(float2)) + 64;
-    if (ctx->auto_cap < need) {
-        if (ctx->d_auto) (void)hipFree(ctx->d_auto);
-        ctx->d_auto = nullptr; ctx->auto_cap = 0;
-        TH_CHECK_HIP(hipMalloc(&ctx->d_auto, need));
-        ctx->auto_cap = need;
-    }
-    uint8_t* base = static_cast<uint8_t*>(ctx->d_auto);
+    if (int rc = ctx->autos.reserve(ctx, need, "trexhip_posture_auto_device")) return rc;
+    uint8_t* base = ctx->autos.as<uint8_t>();
     unsigned long long* best = reinterpret_cast<unsigned long long*>(base); base += (size_t)n * 8;
     float2* first = reinterpret_cast<float2*>(base); base += (size_t)n * MPt * sizeof(float2);
     int32_t* thr = reinterpret_cast<int32_t*>(base); base += (size_t)n * 4;
@@ -1036,10 +1030,10 @@ extern "C" int trexhip_posture_auto_device(trexhip_ctx* ctx, const trexhip_postu
     hipLaunchKernelGGL(k_auto_init, g256, dim3(256), 0, s, n, (int)track_posture_threshold, thr, first_n, first_thr, used, iters, best, d_info);
     // LDS capacities of the posture launches: a thresholded sub-blob has at most its parent's rows, and more lines only where a line splits
     int nr_cap = P_NR, rows_cap = P_ROWS;
-    if (ctx->h_blobs && ctx->fetched) {
+    if (ctx->tables.h_blobs && ctx->tables.fetched) {
         uint32_t mr = 1, mrows = 1;
         for (int i = 0; i < n; ++i) {
-            const trexhip_blob& b = ctx->h_blobs[i];
+            const trexhip_blob& b = ctx->tables.h_blobs[i];
             const uint32_t rws = (uint32_t)(b.y1 - b.y0 + 1);
             if (rws <= (uint32_t)P_ROWS) { mr = std::max(mr, std::min<uint32_t>(b.n_runs * 2u, (uint32_t)P_NR)); mrows = std::max(mrows, rws); }
         }
@@ -1068,18 +1062,18 @@ extern "C" int trexhip_posture_auto_device(trexhip_ctx* ctx, const trexhip_postu
         int rc = trexhip_rethreshold_per_blob_device(ctx, 0, thr, method, nullptr, 0);     // negative entries (finished blobs) are skipped
         if (rc) return rc;
         const Pass2& q = ctx->pass2;
-        hipLaunchKernelGGL(k_auto_pick, dim3((ctx->cfg.pool_blobs + 255u) / 256u), dim3(256), 0, s, q.d_blobs, q.d_totals, ctx->cfg.pool_blobs, n, best);
+        hipLaunchKernelGGL(k_auto_pick, dim3((ctx->cfg.pool_blobs + 255u) / 256u), dim3(256), 0, s, q.tables.d_blobs, q.tables.d_totals, ctx->cfg.pool_blobs, n, best);
         hipLaunchKernelGGL(k_auto_sel, g256, dim3(256), 0, s, n, thr, best, sel);
         uint32_t still[2] = {0, 0};
         for (int attempt = 0; attempt < 2; ++attempt) {               // attempt 1: only if a sub-blob did not fit the estimated LDS capacities
             TH_CHECK_HIP(hipMemsetAsync(active, 0, 8, s));
             stage_begin(ctx, TREXHIP_STAGE_POSTURE);
-            hipLaunchKernelGGL(k_posture, dim3((n + wpb - 1) / wpb), dim3(wpb * 64), lds_bytes, s, P, q.d_info, q.d_blob_frame, q.d_blobs, q.d_runs, n, ctx->last_n,
-                               reinterpret_cast<float2*>(d_outline), reinterpret_cast<float4*>(d_segments), d_info, sel, ctx->d_blobs);
+            hipLaunchKernelGGL(k_posture, dim3((n + wpb - 1) / wpb), dim3(wpb * 64), lds_bytes, s, P, q.tables.d_info, q.tables.d_blob_frame, q.tables.d_blobs, q.tables.d_runs, n, ctx->tables.valid_n,
+                               reinterpret_cast<float2*>(d_outline), reinterpret_cast<float4*>(d_segments), d_info, sel, ctx->tables.d_blobs);
             launch_posture_walk(s, pp, P.walk_group, n, d_outline, d_segments, d_info);
             stage_end(ctx, TREXHIP_STAGE_POSTURE);
-            hipLaunchKernelGGL(k_auto_step, dim3((n + 3) / 4), dim3(256), 0, s, n, (int)track_posture_threshold, MPt, ctx->d_blobs, thr, sel, best, first_n, first_thr,
-                               used, iters, first, reinterpret_cast<float2*>(d_outline), d_info, active, q.d_blobs, P.nr_cap, P.rows_cap);
+            hipLaunchKernelGGL(k_auto_step, dim3((n + 3) / 4), dim3(256), 0, s, n, (int)track_posture_threshold, MPt, ctx->tables.d_blobs, thr, sel, best, first_n, first_thr,
+                               used, iters, first, reinterpret_cast<float2*>(d_outline), d_info, active, q.tables.d_blobs, P.nr_cap, P.rows_cap);
             TH_CHECK_HIP(hipGetLastError());
             TH_CHECK_HIP(hipMemcpyAsync(still, active, 8, hipMemcpyDeviceToHost, s));
             TH_CHECK_HIP(hipStreamSynchronize(s));

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(PRE_THREADS) void k_pre_decide(const PreCfg c, cons
 
 int launch_prefilter(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const trexhip_prefilter_tables* tb, uint8_t* d_decision, int32_t* d_order,
                      int32_t* d_counts, int32_t* d_presumed_nr) {
-    const int n = ctx->last_n;
+    const int n = ctx->tables.valid_n;
     const size_t cap = (size_t)ctx->p.max_batch * ctx->p.max_blobs, per_frame = 2 * (size_t)ctx->p.max_blobs;
     PreCfg c = {};
     c.W = ctx->cfg.W; c.H = ctx->cfg.H; c.B = n; c.invert = ctx->batch_invert; c.method = pp->method; c.thr = pp->track_threshold; c.thr2 = pp->track_threshold_2;
@@ -433,11 +433,11 @@ int launch_prefilter(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const
     // total detect blobs of the fetched batch (every frame's pooled slice, flagged ones included): the whole of d_presumed_nr is zeroed
     uint32_t n1max = 1, total1 = 0;
     for (int f = 0; f < n; ++f) {
-        total1 = std::max(total1, ctx->h_info[f].blob_begin + ctx->h_info[f].n_blobs);
-        if (ctx->h_info[f].flags) continue;
-        n1max = std::max(n1max, ctx->h_info[f].n_blobs);
+        total1 = std::max(total1, ctx->tables.h_info[f].blob_begin + ctx->tables.h_info[f].n_blobs);
+        if (ctx->tables.h_info[f].flags) continue;
+        n1max = std::max(n1max, ctx->tables.h_info[f].n_blobs);
     }
-    total1 = std::min<uint32_t>(std::max(total1, ctx->h_totals[0]), (uint32_t)cap);
+    total1 = std::min<uint32_t>(std::max(total1, ctx->tables.h_totals[0]), (uint32_t)cap);
     c.n1max = n1max;
     const size_t lds = sizeof(float2) * (size_t)(c.n_inc_pts + c.n_ign_pts) + sizeof(int) * (size_t)(c.n_inc + c.n_ign + 2) + 3 * sizeof(uint32_t) * (size_t)n1max;
     if (lds + 4096 > PRE_LDS_LIMIT) {
@@ -449,12 +449,8 @@ int launch_prefilter(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const
         TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pre_decide<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRE_LDS_LIMIT - 4096));
         ctx->attr_prefilter = true;
     }
-    if (!ctx->d_pre) {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(int32_t) * (2 * cap + (size_t)ctx->p.max_batch * per_frame)) != hipSuccess) { set_error("trexhip_prefilter_device: out of device memory"); return TREXHIP_E_NOMEM; }
-        ctx->d_pre = p;
-    }
-    int32_t* d_count2_own = static_cast<int32_t*>(ctx->d_pre);
+    if (int rc = ctx->pre.reserve(ctx, sizeof(int32_t) * (2 * cap + (size_t)ctx->p.max_batch * per_frame), "trexhip_prefilter_device")) return rc;
+    int32_t* d_count2_own = ctx->pre.as<int32_t>();
     int32_t* d_seq = d_count2_own + 2 * cap;
     int32_t* d_count2 = tb && tb->d_second_count ? tb->d_second_count : d_count2_own;
     hipStream_t s = ctx->stream;
@@ -473,15 +469,15 @@ int launch_prefilter(trexhip_ctx* ctx, const trexhip_prefilter_params* pp, const
     const int* go = tb ? tb->d_ignore_offsets : nullptr;
     const uint32_t* bx = tb ? tb->d_ignore_bdx : nullptr;
     const int* bo = bx ? tb->d_ignore_bdx_offsets : nullptr;
-    const uint32_t* tot1 = ctx->d_ctr + (size_t)ctx->p.max_batch * TREXHIP_CTR_STRIDE;
+    const uint32_t* tot1 = ctx->tables.d_totals;
     if (c.thr2 > 0) {
-        hipLaunchKernelGGL(k_pre_decide<1>, dim3(n), dim3(PRE_THREADS), lds, s, c, ctx->d_info, ctx->d_blobs, q.d_info, q.d_blobs, ip, io, gp, go, bx, bo,
+        hipLaunchKernelGGL(k_pre_decide<1>, dim3(n), dim3(PRE_THREADS), lds, s, c, ctx->tables.d_info, ctx->tables.d_blobs, q.tables.d_info, q.tables.d_blobs, ip, io, gp, go, bx, bo,
                            d_count2, d_seq, d_decision, d_order, d_counts, d_presumed_nr);
         const unsigned waves_wanted = (unsigned)std::min<size_t>((size_t)total1 + cap, (size_t)ctx->n_cus * 32);
-        hipLaunchKernelGGL(k_pre_count2, dim3((waves_wanted + 3) / 4), dim3(PRE_THREADS), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->d_info, ctx->d_blob_frame,
-                           ctx->d_blobs, ctx->d_runs, tot1, q.d_info, q.d_blob_frame, q.d_blobs, q.d_runs, q.d_totals, d_count2);
+        hipLaunchKernelGGL(k_pre_count2, dim3((waves_wanted + 3) / 4), dim3(PRE_THREADS), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->tables.d_info, ctx->tables.d_blob_frame,
+                           ctx->tables.d_blobs, ctx->tables.d_runs, tot1, q.tables.d_info, q.tables.d_blob_frame, q.tables.d_blobs, q.tables.d_runs, q.tables.d_totals, d_count2);
     }
-    hipLaunchKernelGGL(k_pre_decide<0>, dim3(n), dim3(PRE_THREADS), lds, s, c, ctx->d_info, ctx->d_blobs, q.d_info, q.d_blobs, ip, io, gp, go, bx, bo,
+    hipLaunchKernelGGL(k_pre_decide<0>, dim3(n), dim3(PRE_THREADS), lds, s, c, ctx->tables.d_info, ctx->tables.d_blobs, q.tables.d_info, q.tables.d_blobs, ip, io, gp, go, bx, bo,
                        d_count2, d_seq, d_decision, d_order, d_counts, d_presumed_nr);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;

@@ -1768,7 +1768,7 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
             if (c.R <= CCL_S_NMAX) inst = 1; else if (c.R <= CCL_M_NMAX && inst > 2) inst = 2;     // max_runs itself bounds the lines of a frame
         }
     }
-    uint32_t* totals = ctx->d_ctr + (size_t)ctx->p.max_batch * CTR_STRIDE;
+    uint32_t* totals = ctx->tables.d_totals;
     // The batch can be cut into groups of frames so that the labelling of one group (latency chains, one workgroup per frame) runs beside the
     // pixel pass of another (HBM-bound, every CU).  TREXHIP_SEG_GROUPS = G, TREXHIP_SEG_SCHEME:
     //   0  pixel passes on the caller's stream, labelling of group g on an auxiliary stream behind an event (rounds 4-5: slower, the L instance needs a whole CU)
@@ -1831,9 +1831,9 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
             const dim3 grid_b(K ? (unsigned)(((size_t)H * (cg.B / K) + 3) / 4) : 1u);
             // (k_rows32b for one and, since round 6, two 2048-pixel chunks: the two-chunk form needed its loads written without conditional 128-bit
             // assignments, on which hipcc 7.2 crashes; TREXHIP_ROWS_ORDER bit 3 keeps k_rows32 for two chunks)
-#define TH_ROWS32(NCH_, MODE_) do { if (K && NCH_ == 1) hipLaunchKernelGGL((k_rows32b<1, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, K, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); \
-                                    else if (K && NCH_ == 2 && !(ctx->tune_rows_order & 8)) hipLaunchKernelGGL((k_rows32b<2, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, K, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); \
-                                    else hipLaunchKernelGGL((k_rows32<NCH_, MODE_>), grid_g, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); } while (0)
+#define TH_ROWS32(NCH_, MODE_) do { if (K && NCH_ == 1) hipLaunchKernelGGL((k_rows32b<1, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, K, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); \
+                                    else if (K && NCH_ == 2 && !(ctx->tune_rows_order & 8)) hipLaunchKernelGGL((k_rows32b<2, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, K, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); \
+                                    else hipLaunchKernelGGL((k_rows32<NCH_, MODE_>), grid_g, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); } while (0)
 #define TH_ROWS32_M(NCH_) do { switch (mode) { case 1: TH_ROWS32(NCH_, 1); break; case 2: TH_ROWS32(NCH_, 2); break; case 5: TH_ROWS32(NCH_, 5); break; \
                                                case 6: TH_ROWS32(NCH_, 6); break; default: TH_ROWS32(NCH_, 0); } } while (0)
             switch (nch32) {
@@ -1845,8 +1845,8 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
 #undef TH_ROWS32_M
 #undef TH_ROWS32
         } else
-        if (aligned) launch_rows<true>(nch, grid_g, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits, (uint32_t)f0);
-        else         launch_rows<false>(nch, grid_g, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits, (uint32_t)f0);
+        if (aligned) launch_rows<true>(nch, grid_g, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits, (uint32_t)f0);
+        else         launch_rows<false>(nch, grid_g, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits, (uint32_t)f0);
         if (g == G - 1) stage_end(ctx, TREXHIP_STAGE_ROWS);
         hipStream_t t = s;
         if (G > 1 && scheme == 0) {
@@ -1872,12 +1872,12 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
         }
         const int band_rows = n_bands > 1 ? (H + n_bands - 1) / n_bands : 0;
         if (n_bands > 1)
-            hipLaunchKernelGGL(k_ccl_band, dim3((f1 - f0) * n_bands), dim3(CCLB_NT), CCLB_LDS_BYTES, t, c, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_row_base, ctx->d_tmp_runs,
-                               ctx->d_raster, ctx->d_parent, ctx->d_band_fail, n_bands, band_rows, f0);
-#define TH_CCL(NT_, NMAX_, SA_, RETRY_) hipLaunchKernelGGL((k_ccl_lds<NT_, NMAX_, SA_>), dim3(f1 - f0), dim3(NT_), (CclLds<NMAX_, SA_>::BYTES), t, c, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_off, ctx->d_row_base, \
-                           ctx->d_tmp_runs, ctx->d_raster, ctx->d_parent, ctx->d_root_ord, ctx->d_cur_run, ctx->d_pix_begin, ctx->d_blob_map,                           \
-                           totals, ctx->d_info, ctx->d_blobs, ctx->d_blob_frame, ctx->d_runs, ctx->tune_ccl_stop, reinterpret_cast<unsigned long long*>(ctx->d_cnt_px), f0, \
-                           fuse_gather ? d_frames : (const uint8_t*)nullptr, ctx->d_pixels, RETRY_, ctx->h_ccl_hint, (NT_) == 1024 && (NMAX_) == CCL_NMAX && !(RETRY_) ? band_rows : 0, ctx->d_band_fail)
+            hipLaunchKernelGGL(k_ccl_band, dim3((f1 - f0) * n_bands), dim3(CCLB_NT), CCLB_LDS_BYTES, t, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base, ctx->d_tmp_runs,
+                               ctx->label.d_raster, ctx->label.d_parent, ctx->d_band_fail, n_bands, band_rows, f0);
+#define TH_CCL(NT_, NMAX_, SA_, RETRY_) hipLaunchKernelGGL((k_ccl_lds<NT_, NMAX_, SA_>), dim3(f1 - f0), dim3(NT_), (CclLds<NMAX_, SA_>::BYTES), t, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base, \
+                           ctx->d_tmp_runs, ctx->label.d_raster, ctx->label.d_parent, ctx->label.d_root_ord, ctx->label.d_cur_run, ctx->label.d_pix_begin, ctx->label.d_blob_map,                           \
+                           totals, ctx->tables.d_info, ctx->tables.d_blobs, ctx->tables.d_blob_frame, ctx->tables.d_runs, ctx->tune_ccl_stop, reinterpret_cast<unsigned long long*>(ctx->label.d_cnt_px), f0, \
+                           fuse_gather ? d_frames : (const uint8_t*)nullptr, ctx->tables.d_pixels, RETRY_, ctx->h_ccl_hint, (NT_) == 1024 && (NMAX_) == CCL_NMAX && !(RETRY_) ? band_rows : 0, ctx->d_band_fail)
         switch (inst) {
             case 1: TH_CCL(256, CCL_S_NMAX, CCL_S_SA, 0); break;
             case 2: TH_CCL(512, CCL_M_NMAX, CCL_M_SA, 0); break;
@@ -1890,8 +1890,8 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
         const unsigned gather_need = (unsigned)(((size_t)(f1 - f0) * ctx->p.max_blobs + 7) / 8);
         const unsigned gather_grid = gather_blocks_env > 0 ? (unsigned)gather_blocks_env : (gather_need < 16u ? 16u : (gather_need > 2048u ? 2048u : gather_need));
         if (!fuse_gather)
-        LAUNCH_GATHER(dim3(G > 1 ? 256 : gather_grid), t, c, 0, d_frames, totals, ctx->d_info, ctx->d_blob_frame,
-                           ctx->d_blobs, ctx->d_runs, ctx->d_pixels, (uint32_t)f0, (uint32_t)f1, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
+        LAUNCH_GATHER(dim3(G > 1 ? 256 : gather_grid), t, c, 0, d_frames, totals, ctx->tables.d_info, ctx->tables.d_blob_frame,
+                           ctx->tables.d_blobs, ctx->tables.d_runs, ctx->tables.d_pixels, (uint32_t)f0, (uint32_t)f1, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
     }
     if (G > 1) {
         TH_CHECK_HIP(hipEventRecord(ctx->ev_grp[8], ctx->aux_stream));
@@ -1901,10 +1901,10 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
     TH_CHECK_HIP(hipGetLastError());
     ctx->ctr_dirty = false;              // every frame's labelling kernel is queued behind its rows kernel
     ctx->d_frames = d_frames;
-    ctx->last_n = n;
-    ctx->fetched = false;
-    ctx->pass2.valid_n = 0;
-    ctx->pass2.fetched = false;
+    ctx->tables.valid_n = n;
+    ctx->tables.fetched = false;
+    ctx->pass2.tables.valid_n = 0;
+    ctx->pass2.tables.fetched = false;
     return TREXHIP_OK;
 }
 
@@ -1912,20 +1912,20 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
 int launch_pending(trexhip_ctx* ctx) {
     SegCfg c = ctx->cfg;
     c.invert = ctx->batch_invert; c.zero_bg = ctx->batch_zero_bg;
-    const int n = ctx->last_n;
+    const int n = ctx->tables.valid_n;
     c.B = n;
     hipStream_t s = ctx->stream;
     const dim3 grid_r((unsigned)((n * c.H + 255) / 256));
-    uint32_t* totals = ctx->d_ctr + (size_t)ctx->p.max_batch * CTR_STRIDE;
-    hipLaunchKernelGGL(k_rowscan, dim3(n), dim3(256), 0, s, c, 1, ctx->d_ctr, ctx->d_row_cnt, ctx->d_row_base, ctx->d_parent, ctx->d_info);
-    hipLaunchKernelGGL(k_link, grid_r, dim3(256), 0, s, c, 1, ctx->d_row_cnt, ctx->d_row_off, ctx->d_row_base,
-                       ctx->d_tmp_runs, ctx->d_raster, ctx->d_parent, ctx->d_info);
-    hipLaunchKernelGGL(k_flatten, grid_r, dim3(256), 0, s, c, 1, ctx->d_row_cnt, ctx->d_row_base, ctx->d_parent, ctx->d_info);
-    hipLaunchKernelGGL(k_blobs, dim3(n), dim3(256), 0, s, c, 1, ctx->d_raster, ctx->d_parent, ctx->d_root_ord,
-                       ctx->d_cnt_runs, ctx->d_cnt_px, ctx->d_cur_run, ctx->d_pix_begin, ctx->d_blob_map, totals, ctx->d_info,
-                       ctx->d_blobs, ctx->d_blob_frame, ctx->d_runs, 0, (const uint32_t*)nullptr);
-    LAUNCH_GATHER(dim3(1024), s, c, 1, ctx->d_frames, totals, ctx->d_info, ctx->d_blob_frame,
-                       ctx->d_blobs, ctx->d_runs, ctx->d_pixels, 0u, (uint32_t)n, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
+    uint32_t* totals = ctx->tables.d_totals;
+    hipLaunchKernelGGL(k_rowscan, dim3(n), dim3(256), 0, s, c, 1, ctx->d_ctr, ctx->label.d_row_cnt, ctx->label.d_row_base, ctx->label.d_parent, ctx->tables.d_info);
+    hipLaunchKernelGGL(k_link, grid_r, dim3(256), 0, s, c, 1, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base,
+                       ctx->d_tmp_runs, ctx->label.d_raster, ctx->label.d_parent, ctx->tables.d_info);
+    hipLaunchKernelGGL(k_flatten, grid_r, dim3(256), 0, s, c, 1, ctx->label.d_row_cnt, ctx->label.d_row_base, ctx->label.d_parent, ctx->tables.d_info);
+    hipLaunchKernelGGL(k_blobs, dim3(n), dim3(256), 0, s, c, 1, ctx->label.d_raster, ctx->label.d_parent, ctx->label.d_root_ord,
+                       ctx->label.d_cnt_runs, ctx->label.d_cnt_px, ctx->label.d_cur_run, ctx->label.d_pix_begin, ctx->label.d_blob_map, totals, ctx->tables.d_info,
+                       ctx->tables.d_blobs, ctx->tables.d_blob_frame, ctx->tables.d_runs, 0, (const uint32_t*)nullptr);
+    LAUNCH_GATHER(dim3(1024), s, c, 1, ctx->d_frames, totals, ctx->tables.d_info, ctx->tables.d_blob_frame,
+                       ctx->tables.d_blobs, ctx->tables.d_runs, ctx->tables.d_pixels, 0u, (uint32_t)n, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
 }
@@ -2058,28 +2058,28 @@ int launch_rethreshold(trexhip_ctx* ctx, int thr, int method, const double* rang
     Pass2& q = ctx->pass2;
     SegCfg c = ctx->cfg;
     c.invert = ctx->batch_invert; c.zero_bg = ctx->batch_zero_bg;
-    const int n = ctx->last_n;
+    const int n = ctx->tables.valid_n;
     c.B = n;
     c.n_ranges = n_ranges;
     for (int i = 0; i < 2 * n_ranges; ++i) c.ranges[i] = ranges[i];
     hipStream_t s = ctx->stream;
     const dim3 grid_r((unsigned)((n * c.H + 255) / 256));
-    TH_CHECK_HIP(hipMemsetAsync(q.d_totals, 0, sizeof(uint32_t) * 4, s));
-    hipLaunchKernelGGL((k_sub<0>), grid_r, dim3(256), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->d_row_base, ctx->d_raster, ctx->d_parent,
-                       ctx->d_root_ord, ctx->d_blob_map, ctx->d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.d_raster, q.d_run_parent);
-    hipLaunchKernelGGL(k_sub_scan, dim3(n), dim3(256), 0, s, c, ctx->d_info, ctx->d_row_base, q.d_sub_cnt, q.d_sub_base, q.d_row_base,
-                       q.d_row_cnt, q.d_parent, q.d_info);
-    hipLaunchKernelGGL((k_sub<1>), grid_r, dim3(256), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->d_row_base, ctx->d_raster, ctx->d_parent,
-                       ctx->d_root_ord, ctx->d_blob_map, ctx->d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.d_raster, q.d_run_parent);
-    hipLaunchKernelGGL(k_link2, grid_r, dim3(256), 0, s, c, q.d_row_base, q.d_raster, q.d_parent, q.d_info);
-    hipLaunchKernelGGL(k_flatten, grid_r, dim3(256), 0, s, c, 0, q.d_row_cnt, q.d_row_base, q.d_parent, q.d_info);
-    hipLaunchKernelGGL(k_blobs, dim3(n), dim3(256), 0, s, c, 0, q.d_raster, q.d_parent, q.d_root_ord, q.d_cnt_runs, q.d_cnt_px, q.d_cur_run,
-                       q.d_pix_begin, q.d_blob_map, q.d_totals, q.d_info, q.d_blobs, q.d_blob_frame, q.d_runs, 1, q.d_run_parent);
-    LAUNCH_GATHER(dim3(1024), s, c, 0, ctx->d_frames, q.d_totals, q.d_info, q.d_blob_frame, q.d_blobs,
-                       q.d_runs, q.d_pixels, 0u, (uint32_t)n, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
+    TH_CHECK_HIP(hipMemsetAsync(q.tables.d_totals, 0, sizeof(uint32_t) * 4, s));
+    hipLaunchKernelGGL((k_sub<0>), grid_r, dim3(256), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->label.d_row_base, ctx->label.d_raster, ctx->label.d_parent,
+                       ctx->label.d_root_ord, ctx->label.d_blob_map, ctx->tables.d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.label.d_raster, q.d_run_parent);
+    hipLaunchKernelGGL(k_sub_scan, dim3(n), dim3(256), 0, s, c, ctx->tables.d_info, ctx->label.d_row_base, q.d_sub_cnt, q.d_sub_base, q.label.d_row_base,
+                       q.label.d_row_cnt, q.label.d_parent, q.tables.d_info);
+    hipLaunchKernelGGL((k_sub<1>), grid_r, dim3(256), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->label.d_row_base, ctx->label.d_raster, ctx->label.d_parent,
+                       ctx->label.d_root_ord, ctx->label.d_blob_map, ctx->tables.d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.label.d_raster, q.d_run_parent);
+    hipLaunchKernelGGL(k_link2, grid_r, dim3(256), 0, s, c, q.label.d_row_base, q.label.d_raster, q.label.d_parent, q.tables.d_info);
+    hipLaunchKernelGGL(k_flatten, grid_r, dim3(256), 0, s, c, 0, q.label.d_row_cnt, q.label.d_row_base, q.label.d_parent, q.tables.d_info);
+    hipLaunchKernelGGL(k_blobs, dim3(n), dim3(256), 0, s, c, 0, q.label.d_raster, q.label.d_parent, q.label.d_root_ord, q.label.d_cnt_runs, q.label.d_cnt_px, q.label.d_cur_run,
+                       q.label.d_pix_begin, q.label.d_blob_map, q.tables.d_totals, q.tables.d_info, q.tables.d_blobs, q.tables.d_blob_frame, q.tables.d_runs, 1, q.d_run_parent);
+    LAUNCH_GATHER(dim3(1024), s, c, 0, ctx->d_frames, q.tables.d_totals, q.tables.d_info, q.tables.d_blob_frame, q.tables.d_blobs,
+                       q.tables.d_runs, q.tables.d_pixels, 0u, (uint32_t)n, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
     TH_CHECK_HIP(hipGetLastError());
-    q.valid_n = n;
-    q.fetched = false;
+    q.tables.valid_n = n;
+    q.tables.fetched = false;
     return TREXHIP_OK;
 }
 

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(64) void k_split_search(const SplitCfg C, const uin
 int launch_split_search(trexhip_ctx* ctx, const trexhip_split_params* sp, int method, const int32_t* d_presumed, int n_blobs, int32_t* d_thr,
                         trexhip_split_info* d_info) {
     SplitCfg C = {};
-    C.W = ctx->cfg.W; C.H = ctx->cfg.H; C.B = ctx->last_n; C.invert = ctx->batch_invert; C.slack = ctx->cfg.slack; C.method = method;
+    C.W = ctx->cfg.W; C.H = ctx->cfg.H; C.B = ctx->tables.valid_n; C.invert = ctx->batch_invert; C.slack = ctx->cfg.slack; C.method = method;
     C.initial_threshold = (sp->calculate_posture ? max(sp->track_threshold, sp->track_posture_threshold) : sp->track_threshold) + 1;   // :512
     C.algorithm = sp->algorithm; C.n_ranges = sp->n_ranges;
     C.sqcm = ctx->cfg.sqcm; C.max_shrink = sp->blob_split_max_shrink; C.global_shrink = sp->blob_split_global_shrink_limit;
@@ -319,13 +319,13 @@ int launch_split_search(trexhip_ctx* ctx, const trexhip_split_params* sp, int me
     }
     hipLaunchKernelGGL((k_split_search<S_PX_SMALL, S_RUNS_SMALL, S_SUB_SMALL, 0, 0>), dim3((unsigned)n_blobs), dim3(64),
                        split_lds_bytes(S_PX_SMALL, S_RUNS_SMALL, S_SUB_SMALL), ctx->stream, C, ctx->d_frames,
-                       ctx->d_bg, ctx->d_info, ctx->d_blob_frame, ctx->d_blobs, ctx->d_runs, d_presumed, n_blobs, d_thr, d_info);
+                       ctx->d_bg, ctx->tables.d_info, ctx->tables.d_blob_frame, ctx->tables.d_blobs, ctx->tables.d_runs, d_presumed, n_blobs, d_thr, d_info);
     hipLaunchKernelGGL((k_split_search<S_PX, S_RUNS, S_SUB, S_PX_SMALL, S_RUNS_SMALL>), dim3((unsigned)n_blobs), dim3(64),
                        split_lds_bytes(S_PX, S_RUNS, S_SUB), ctx->stream, C, ctx->d_frames,
-                       ctx->d_bg, ctx->d_info, ctx->d_blob_frame, ctx->d_blobs, ctx->d_runs, d_presumed, n_blobs, d_thr, d_info);
+                       ctx->d_bg, ctx->tables.d_info, ctx->tables.d_blob_frame, ctx->tables.d_blobs, ctx->tables.d_runs, d_presumed, n_blobs, d_thr, d_info);
     // the third size class (134 KB of LDS: one blob per CU) only when the fetched tables hold a blob of that size
     bool huge = false;
-    for (int i = 0; i < n_blobs && !huge; ++i) huge = ctx->h_blobs[i].n_pixels > (uint32_t)S_PX || ctx->h_blobs[i].n_runs > (uint32_t)S_RUNS;
+    for (int i = 0; i < n_blobs && !huge; ++i) huge = ctx->tables.h_blobs[i].n_pixels > (uint32_t)S_PX || ctx->tables.h_blobs[i].n_runs > (uint32_t)S_RUNS;
     if (huge) {
         const int bytes = split_lds_bytes(S_PX_HUGE, S_RUNS_HUGE, S_SUB_HUGE);
         if (!ctx->attr_split) {
@@ -334,7 +334,7 @@ int launch_split_search(trexhip_ctx* ctx, const trexhip_split_params* sp, int me
             ctx->attr_split = true;
         }
         hipLaunchKernelGGL((k_split_search<S_PX_HUGE, S_RUNS_HUGE, S_SUB_HUGE, S_PX, S_RUNS>), dim3((unsigned)n_blobs), dim3(64), bytes, ctx->stream, C,
-                           ctx->d_frames, ctx->d_bg, ctx->d_info, ctx->d_blob_frame, ctx->d_blobs, ctx->d_runs, d_presumed, n_blobs, d_thr, d_info);
+                           ctx->d_frames, ctx->d_bg, ctx->tables.d_info, ctx->tables.d_blob_frame, ctx->tables.d_blobs, ctx->tables.d_runs, d_presumed, n_blobs, d_thr, d_info);
     }
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
@@ -358,7 +358,7 @@ extern "C" int trexhip_split_search_device(trexhip_ctx* ctx, const trexhip_split
     if (sp->algorithm == 3 || sp->algorithm == 4) { set_error("trexhip_split_search_device: blob_split_algorithm = fill / fill_approximate (cv::watershed, SplitBlob.cpp:419-485) is not implemented by this backend"); return TREXHIP_E_UNSUPPORTED; }
     if (sp->algorithm < 0 || sp->algorithm > 2) { set_error("trexhip_split_search_device: algorithm must be 0 (none), 1 (threshold) or 2 (threshold_approximate)"); return TREXHIP_E_INVALID; }
     if (sp->n_ranges < 0 || sp->n_ranges > 8) { set_error("trexhip_split_search_device: at most 8 size ranges"); return TREXHIP_E_INVALID; }
-    if (!ctx->d_frames || ctx->last_n == 0 || !ctx->fetched) { set_error("trexhip_split_search_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
+    if (!ctx->d_frames || ctx->tables.valid_n == 0 || !ctx->tables.fetched) { set_error("trexhip_split_search_device: segment and fetch a batch first"); return TREXHIP_E_INVALID; }
     if (n_blobs < 0 || (uint32_t)n_blobs > ctx->cfg.pool_blobs) { set_error("trexhip_split_search_device: n_blobs outside the blob pool"); return TREXHIP_E_INVALID; }
     if (n_blobs == 0) return TREXHIP_OK;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));

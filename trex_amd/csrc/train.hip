@@ -1387,7 +1387,7 @@ struct Trainer {
     bool masks_on_side = false;          // this step's keep masks are being drawn on `side` (ev[6])
     double* red_bias = nullptr;          // [3][BWD_BLOCKS][128]: k_t_bn_bwd's column sums, finalized on `side`
     bool attr = false;
-    std::vector<void*> allocs;
+    Mem mem;                             // every device buffer above
 };
 
 static constexpr int RED_BLOCKS = 256, BWD_BLOCKS = 1024;   // grids of the reduction kernels (partials: red[BWD_BLOCKS][2][128])
@@ -1409,19 +1409,10 @@ static size_t to_internal(int t, size_t i, int CH) {
     }
 }
 
-template <class T>
-static int dev_alloc(Trainer* t, T** p, size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) { set_error("trexhip_trainer_create: out of device memory"); return TREXHIP_E_NOMEM; }
-    t->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return TREXHIP_OK;
-}
-
 static void trainer_free(Trainer* t) {
     if (!t) return;
     if (t->side) (void)hipStreamSynchronize(t->side);                     // (a step joins its side stream before Adam; this is for a half-queued one)
-    for (void* q : t->allocs) (void)hipFree(q);
+    t->mem.free_all();
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
     if (t->side) { (void)hipStreamSynchronize(t->side); (void)hipStreamDestroy(t->side); }
     delete t;
@@ -1740,25 +1731,26 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     t->off[T_COUNT] = at; t->total = at;
     const size_t n = (size_t)t->max_n;
     int rc = TREXHIP_OK;
+    const char* who = "trexhip_trainer_create";
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
-    TRY(dev_alloc(t, &t->P, at)); TRY(dev_alloc(t, &t->G, at)); TRY(dev_alloc(t, &t->M, at)); TRY(dev_alloc(t, &t->V, at));
-    TRY(dev_alloc(t, &t->z1, n * 6400 * 16)); TRY(dev_alloc(t, &t->a1, n * 1600 * 16)); TRY(dev_alloc(t, &t->z2, n * 1600 * 64));
-    TRY(dev_alloc(t, &t->a2, n * 400 * 64)); TRY(dev_alloc(t, &t->z3, n * 400 * 128)); TRY(dev_alloc(t, &t->a3, n * 100 * 128));
-    TRY(dev_alloc(t, &t->da3, n * 100 * 128)); TRY(dev_alloc(t, &t->da2, n * 400 * 64)); TRY(dev_alloc(t, &t->da1, n * 1600 * 16));
-    TRY(dev_alloc(t, &t->wb3, (size_t)4 * 25 * 32 * 64)); TRY(dev_alloc(t, &t->wb2, (size_t)2 * 25 * 32 * 32));
-    TRY(dev_alloc(t, &t->wh2f, (size_t)2 * 2 * 25 * 64)); TRY(dev_alloc(t, &t->wh2b, (size_t)2 * 8 * 25 * 32));
-    TRY(dev_alloc(t, &t->wh3f, (size_t)2 * 8 * 25 * 128)); TRY(dev_alloc(t, &t->wh3b, (size_t)2 * 16 * 25 * 64));
-    TRY(dev_alloc(t, &t->wh_scale, 2));
+    TRY(t->mem.device(&t->P, at, who)); TRY(t->mem.device(&t->G, at, who)); TRY(t->mem.device(&t->M, at, who)); TRY(t->mem.device(&t->V, at, who));
+    TRY(t->mem.device(&t->z1, n * 6400 * 16, who)); TRY(t->mem.device(&t->a1, n * 1600 * 16, who)); TRY(t->mem.device(&t->z2, n * 1600 * 64, who));
+    TRY(t->mem.device(&t->a2, n * 400 * 64, who)); TRY(t->mem.device(&t->z3, n * 400 * 128, who)); TRY(t->mem.device(&t->a3, n * 100 * 128, who));
+    TRY(t->mem.device(&t->da3, n * 100 * 128, who)); TRY(t->mem.device(&t->da2, n * 400 * 64, who)); TRY(t->mem.device(&t->da1, n * 1600 * 16, who));
+    TRY(t->mem.device(&t->wb3, (size_t)4 * 25 * 32 * 64, who)); TRY(t->mem.device(&t->wb2, (size_t)2 * 25 * 32 * 32, who));
+    TRY(t->mem.device(&t->wh2f, (size_t)2 * 2 * 25 * 64, who)); TRY(t->mem.device(&t->wh2b, (size_t)2 * 8 * 25 * 32, who));
+    TRY(t->mem.device(&t->wh3f, (size_t)2 * 8 * 25 * 128, who)); TRY(t->mem.device(&t->wh3b, (size_t)2 * 16 * 25 * 64, who));
+    TRY(t->mem.device(&t->wh_scale, 2, who));
     t->part_floats = std::max(std::max(std::max((size_t)SHARES3 * 25 * 64 * 128, (size_t)SHARES2 * 25 * 16 * 64), std::max((size_t)SHARES3H * 25 * 64 * 128, (size_t)SHARES2H * 25 * 16 * 64)),
                               n * 10 * CH * 400);
-    TRY(dev_alloc(t, &t->part, t->part_floats)); TRY(dev_alloc(t, &t->part1, n * 10 * CH * 400)); TRY(dev_alloc(t, &t->red_bias, (size_t)3 * BWD_BLOCKS * 128));
-    TRY(dev_alloc(t, &t->stat, (size_t)3 * 512));
-    TRY(dev_alloc(t, &t->hpart, n * 100 * 100)); TRY(dev_alloc(t, &t->xhat, n * 100)); TRY(dev_alloc(t, &t->hd, n * 100));
-    TRY(dev_alloc(t, &t->dl, n * classes)); TRY(dev_alloc(t, &t->dy, n * 100)); TRY(dev_alloc(t, &t->dh, n * 100));
-    TRY(dev_alloc(t, &t->loss, n)); TRY(dev_alloc(t, &t->correct, n)); TRY(dev_alloc(t, &t->out2, 2)); TRY(dev_alloc(t, &t->bad_target, 2));
-    TRY(dev_alloc(t, &t->red, std::max((size_t)BWD_BLOCKS * 2 * 128, n * 640)));   // conv1 leaves 20 n x 2 x 16 partials, conv2 / conv3 2 n x 2 x C
-    TRY(dev_alloc(t, &t->keep, n * 308));
-    TRY(dev_alloc(t, &t->x_stage, n * 6400 * CH)); TRY(dev_alloc(t, &t->y_stage, n)); TRY(dev_alloc(t, &t->keep_stage, n * 308));
+    TRY(t->mem.device(&t->part, t->part_floats, who)); TRY(t->mem.device(&t->part1, n * 10 * CH * 400, who)); TRY(t->mem.device(&t->red_bias, (size_t)3 * BWD_BLOCKS * 128, who));
+    TRY(t->mem.device(&t->stat, (size_t)3 * 512, who));
+    TRY(t->mem.device(&t->hpart, n * 100 * 100, who)); TRY(t->mem.device(&t->xhat, n * 100, who)); TRY(t->mem.device(&t->hd, n * 100, who));
+    TRY(t->mem.device(&t->dl, n * classes, who)); TRY(t->mem.device(&t->dy, n * 100, who)); TRY(t->mem.device(&t->dh, n * 100, who));
+    TRY(t->mem.device(&t->loss, n, who)); TRY(t->mem.device(&t->correct, n, who)); TRY(t->mem.device(&t->out2, 2, who)); TRY(t->mem.device(&t->bad_target, 2, who));
+    TRY(t->mem.device(&t->red, std::max((size_t)BWD_BLOCKS * 2 * 128, n * 640), who));   // conv1 leaves 20 n x 2 x 16 partials, conv2 / conv3 2 n x 2 x C
+    TRY(t->mem.device(&t->keep, n * 308, who));
+    TRY(t->mem.device(&t->x_stage, n * 6400 * CH, who)); TRY(t->mem.device(&t->y_stage, n, who)); TRY(t->mem.device(&t->keep_stage, n * 308, who));
 #undef TRY
     if (rc == TREXHIP_OK && hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess) { set_error("trexhip_trainer_create: no second stream"); rc = TREXHIP_E_DEVICE; }
     for (hipEvent_t& e : t->ev)

@@ -337,37 +337,37 @@ extern "C" int trexhip_load_frames_v6_device(trexhip_ctx* ctx, const uint8_t* d_
     if (ctx->p.max_blobs > 65535) { set_error("trexhip_load_frames_v6_device: a frame holds at most 65535 objects (u16 n, pv.cpp:686)"); return TREXHIP_E_UNSUPPORTED; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     const size_t B = (size_t)ctx->p.max_batch, W = (size_t)ctx->p.width, H = (size_t)ctx->p.height, NB = (size_t)ctx->p.max_blobs;
-    if (!ctx->d_staging) TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_staging), B * W * H + 16));
-    if (!ctx->d_load) TH_CHECK_HIP(hipMalloc(&ctx->d_load, B * NB * sizeof(LoadBlob) + B * sizeof(LoadFrame)));
-    LoadBlob* index = static_cast<LoadBlob*>(ctx->d_load);
+    if (int rc = ensure_staging(ctx, "trexhip_load_frames_v6_device")) return rc;
+    if (int rc = ctx->load.reserve(ctx, B * NB * sizeof(LoadBlob) + B * sizeof(LoadFrame), "trexhip_load_frames_v6_device")) return rc;
+    LoadBlob* index = ctx->load.as<LoadBlob>();
     LoadFrame* meta = reinterpret_cast<LoadFrame*>(index + B * NB);
     const int n = n_frames;
     const uint32_t w = (uint32_t)W, h = (uint32_t)H, R = (uint32_t)ctx->p.max_runs;
     hipStream_t s = ctx->stream;
     const unsigned long long* offs = reinterpret_cast<const unsigned long long*>(d_offsets);
-    uint32_t* totals = ctx->d_ctr + B * TREXHIP_CTR_STRIDE;
-    TH_CHECK_HIP(hipMemsetAsync(ctx->d_row_cnt, 0, sizeof(uint32_t) * (size_t)n * H, s));
+    uint32_t* totals = ctx->tables.d_totals;
+    TH_CHECK_HIP(hipMemsetAsync(ctx->label.d_row_cnt, 0, sizeof(uint32_t) * (size_t)n * H, s));
     hipLaunchKernelGGL(k_load_index, dim3(n), dim3(64), 0, s, d_bodies, offs, w, h, (uint32_t)NB, R, (uint32_t)ctx->p.max_pixels, index, meta,
                        reinterpret_cast<unsigned long long*>(d_timestamps));
-    hipLaunchKernelGGL(k_load_scan, dim3(1), dim3(256), 0, s, meta, n, ctx->d_info, totals);
+    hipLaunchKernelGGL(k_load_scan, dim3(1), dim3(256), 0, s, meta, n, ctx->tables.d_info, totals);
     // four blobs per workgroup; a frame of a few blobs does not need workgroups that find nothing to do
     const unsigned gx_blobs = (unsigned)((NB + 3) / 4 < 64 ? (NB + 3) / 4 : 64);
-    hipLaunchKernelGGL(k_load_decode, dim3(gx_blobs, n), dim3(256), 0, s, d_bodies, offs, w, h, (uint32_t)NB, R, index, ctx->d_info, ctx->d_blobs,
-                       ctx->d_blob_frame, ctx->d_runs, ctx->d_pixels, ctx->d_staging, ctx->d_row_cnt, ctx->d_root_ord, ctx->d_blob_map);
-    hipLaunchKernelGGL(k_load_rows, dim3(n), dim3(256), 0, s, h, ctx->d_info, ctx->d_row_cnt, ctx->d_row_base);
-    hipLaunchKernelGGL(k_load_scatter, dim3(gx_blobs, n), dim3(256), 0, s, h, R, ctx->d_info, ctx->d_blobs, ctx->d_runs, ctx->d_row_base, ctx->d_row_cnt,
-                       ctx->d_cur_run, ctx->d_pix_begin);
-    hipLaunchKernelGGL(k_load_rank, dim3((R + 255u) / 256u, n), dim3(256), 0, s, h, R, ctx->d_info, ctx->d_row_base, ctx->d_cur_run, ctx->d_pix_begin,
-                       ctx->d_raster, ctx->d_parent);
+    hipLaunchKernelGGL(k_load_decode, dim3(gx_blobs, n), dim3(256), 0, s, d_bodies, offs, w, h, (uint32_t)NB, R, index, ctx->tables.d_info, ctx->tables.d_blobs,
+                       ctx->tables.d_blob_frame, ctx->tables.d_runs, ctx->tables.d_pixels, ctx->d_staging, ctx->label.d_row_cnt, ctx->label.d_root_ord, ctx->label.d_blob_map);
+    hipLaunchKernelGGL(k_load_rows, dim3(n), dim3(256), 0, s, h, ctx->tables.d_info, ctx->label.d_row_cnt, ctx->label.d_row_base);
+    hipLaunchKernelGGL(k_load_scatter, dim3(gx_blobs, n), dim3(256), 0, s, h, R, ctx->tables.d_info, ctx->tables.d_blobs, ctx->tables.d_runs, ctx->label.d_row_base, ctx->label.d_row_cnt,
+                       ctx->label.d_cur_run, ctx->label.d_pix_begin);
+    hipLaunchKernelGGL(k_load_rank, dim3((R + 255u) / 256u, n), dim3(256), 0, s, h, R, ctx->tables.d_info, ctx->label.d_row_base, ctx->label.d_cur_run, ctx->label.d_pix_begin,
+                       ctx->label.d_raster, ctx->label.d_parent);
     TH_CHECK_HIP(hipGetLastError());
     // the context as it stands behind launch_segment
     ctx->d_frames = ctx->d_staging;
     ctx->d_color_src = nullptr; ctx->color_ch = 0;
     ctx->batch_invert = 0;                       // stored pixels are what the tracker sees: the segmenter stored 255 - p under image_invert
     ctx->batch_zero_bg = ctx->cfg.zero_bg;
-    ctx->last_n = n;
-    ctx->fetched = false;
-    ctx->pass2.valid_n = 0;
-    ctx->pass2.fetched = false;
+    ctx->tables.valid_n = n;
+    ctx->tables.fetched = false;
+    ctx->pass2.tables.valid_n = 0;
+    ctx->pass2.tables.fetched = false;
     return TREXHIP_OK;
 }

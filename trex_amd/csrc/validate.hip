@@ -205,13 +205,8 @@ int trexhip_validation_metrics_device(trexhip_ctx* ctx, const float* d_probs, in
                  o_tab = o_good + up16((size_t)nf * 4), total = o_tab + up16(per_class ? (size_t)nf * classes * 4 : 0);
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     hipStream_t s = ctx->stream;
-    if (total > ctx->val_cap) {
-        if (ctx->d_val) { TH_CHECK_HIP(hipStreamSynchronize(s)); (void)hipFree(ctx->d_val); }
-        ctx->d_val = nullptr; ctx->val_cap = 0;
-        TH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_val), total));
-        ctx->val_cap = total;
-    }
-    uint8_t* base = ctx->d_val;
+    if (int rc = ctx->val.reserve(ctx, total, "trexhip_validation_metrics_device")) return rc;
+    uint8_t* base = ctx->val.as<uint8_t>();
     TH_CHECK_HIP(hipMemsetAsync(base, 0, o_conf + (conf ? (size_t)classes * classes * 4 : 0), s));   // flag, outputs and the confusion counts
     if (frames) TH_CHECK_HIP(hipMemcpyAsync(base + o_ranges, frame_ranges, (size_t)nf * 8, hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
     ValArgs A{};

@@ -315,17 +315,8 @@ int trexhip_visual_field_device(trexhip_ctx* ctx, const trexhip_vf_params* vp, c
                  total = o_tess + (size_t)n_entries * (size_t)vp->max_tess_points * sizeof(double2);
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     hipStream_t s = ctx->stream;
-    if (total > ctx->vf_cap) {
-        if (ctx->d_vf) { TH_CHECK_HIP(hipStreamSynchronize(s)); (void)hipFree(ctx->d_vf); }
-        ctx->d_vf = nullptr; ctx->vf_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_vf), total) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error(std::string(who) + "no device memory for n_entries x max_tess_points tessellated points");
-            return TREXHIP_E_NOMEM;
-        }
-        ctx->vf_cap = total;
-    }
-    uint8_t* base = ctx->d_vf;
+    if (int rc = ctx->vf.reserve(ctx, total, "trexhip_visual_field_device")) return rc;     // n_entries x max_tess_points tessellated points
+    uint8_t* base = ctx->vf.as<uint8_t>();
     TH_CHECK_HIP(hipMemsetAsync(base + o_flag, 0, 16, s));
     VfArgs A{};
     A.p = *vp;
