@@ -510,3 +510,61 @@ def test_wide_frames_with_the_background_in_registers(W, kw):
         res = run_gpu(np.stack(frames), bg, **kw)
         for r, fr in zip(res, frames):
             assert_frame_equal(r, fr, bg, **kw)
+
+
+def ladder_frames():
+    """six 128 x 128 frames on a flat background: two light (under 2000 lines), two medium (2001 .. 3840), two heavy (3841 .. 8160); noise of
+    many small blobs beside structured frames whose lines all belong to a few large blobs"""
+    rng = np.random.default_rng(2000)
+    W = H = 128
+    bg = np.full((H, W), 120, np.uint8)
+    def noise(density):
+        f = bg.copy(); f[rng.random((H, W)) < density] = 10
+        return f
+    light = bg.copy()                                                # a few solid blobs, one of them through most rows
+    light[5:120, 10:14] = 10; light[30:40, 40:90] = 10; light[60:100:2, 20:120] = 10; light[110:125, 100:127] = 10
+    medium = bg.copy()                                               # 24 lines in every row, joined by a bar every 16 rows: few blobs of many lines
+    for j in range(24): medium[:, 2 + 5 * j:2 + 5 * j + 1 + j % 4] = 10
+    medium[::16, :] = 10
+    heavy = bg.copy()                                                # lines of two pixels, one apart, shifted row by row: ONE 8-connected blob of ~5.4 k lines
+    ys, xs = np.mgrid[0:H, 0:W]
+    heavy[(xs + ys) % 3 != 0] = 10
+    return bg, [noise(0.05), light], [noise(0.2), medium], [noise(0.5), heavy]
+
+
+def test_instance_ladder_by_the_shipped_policy():
+    """k_ccl_lds by capacity, chosen by launch_segment from the frame count and the two hint words alone: a launch of two frames per CU starts a
+    fresh context on the S instance; frames S cannot hold are finished by the L retry behind it and raise the first hint word, so the next call
+    starts on M; frames M cannot hold raise the second word, and the call after starts on L.  At this frame count the gather is fused into
+    k_ccl_lds, so every instance also gathers.  Every table is the oracle's byte for byte, whatever instance produced it; which instance ran
+    follows from the code and is not observed."""
+    n = 2 * torch.cuda.get_device_properties(0).multi_processor_count
+    bg, light, medium, heavy = ladder_frames()
+    H, W = bg.shape
+    distinct = light + medium + heavy
+    bracket = [(0, 1999)] * 2 + [(2001, 3840)] * 2 + [(3841, 8160)] * 2
+    all_light = [i % 2 for i in range(n)]                            # indices into `distinct`
+    with_medium = list(all_light); with_medium[0] = 2; with_medium[n // 2] = 3; with_medium[n - 1] = 2
+    with_heavy = list(with_medium); with_heavy[1] = 4; with_heavy[n // 2 + 1] = 5; with_heavy[n - 2] = 4
+    seg = capi.Segmenter(capi.default_params(W, H, max_batch=n, max_runs=8000, max_blobs=4096, max_pixels=W * H))
+    seg.set_background(bg)
+    pool = torch.from_numpy(np.stack(distinct)).cuda()
+    tables = []
+    for batch in (all_light, with_medium, with_medium, with_heavy, with_heavy):
+        d = pool[torch.tensor(batch, device="cuda")].contiguous()
+        seg.segment_device(d.data_ptr(), n)
+        res = seg.fetch()
+        sig = [(r.blobs.tobytes(), r.runs.tobytes(), r.pixels.tobytes()) for r in res]
+        first = {}
+        for i, k in enumerate(batch):
+            assert res[i].info["flags"] == 0
+            if k not in first:
+                first[k] = i
+                lo, hi = bracket[k]
+                assert lo <= res[i].info["n_raw_runs"] <= hi, (k, res[i].info["n_raw_runs"])
+                assert_frame_equal(res[i], distinct[k], bg)
+            else:
+                assert sig[i] == sig[first[k]], (i, k)
+        tables.append(sig)
+    seg.close()
+    assert tables[1] == tables[2] and tables[3] == tables[4]

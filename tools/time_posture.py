@@ -1,5 +1,5 @@
-"""Kernel time of k_posture on the bench scene (dev tool; TREXHIP_POSTURE_STOP=N returns after phase N).
-   gpurun -- 'PYTHONPATH=. python tools/time_posture.py [frames]'"""
+"""Time of one whole posture call (k_posture + the walk kernels) on the bench scene (dev tool).
+   PYTHONPATH=. python tools/time_posture.py [frames]"""
 import sys, time
 import numpy as np, torch
 from trex_amd import capi, synth

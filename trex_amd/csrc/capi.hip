@@ -42,8 +42,7 @@ void stage_begin(trexhip_ctx* ctx, int stage) {
         // to measure timing ... avoiding the cost of cache writeback and invalidation, and the performance impact of those actions on the execution of
         // following work", hip_runtime_api.h).  A default event between the pixel pass and the labelling kernel wrote back and invalidated the L2 the
         // labelling kernel was about to read (round 6: the detect pass read 280 us through its own timers and 270 us on the wall clock without them)
-        static const unsigned flags = std::getenv("TREXHIP_TIMER_EVENT_FLAGS") ? (unsigned)std::strtoul(std::getenv("TREXHIP_TIMER_EVENT_FLAGS"), nullptr, 0) : (unsigned)hipEventDisableSystemFence;
-        hipEventCreateWithFlags(&p.a, flags); hipEventCreateWithFlags(&p.b, flags);
+        hipEventCreateWithFlags(&p.a, hipEventDisableSystemFence); hipEventCreateWithFlags(&p.b, hipEventDisableSystemFence);
     }
     hipEventRecord(p.a, ctx->stream);
     s.cur = p;
@@ -208,22 +207,11 @@ int trexhip_create(const trexhip_params* p, trexhip_ctx** out) {
     ctx->pix_ch = p->pixel_encoding == TREXHIP_ENC_RGB8 ? 3 : 1;
     fill_cfg(ctx);
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess && cus > 0) ctx->n_cus = cus; }
-    // tuning knobs of the default build only choose between schedules / tilings that give identical results.  The knobs that
-    // stop a kernel half-way or skip work (profiling aids) exist only in a -DTREXHIP_DEV_KNOBS build.
-    if (const char* e = std::getenv("TREXHIP_ROWS_ORDER")) ctx->tune_rows_order = std::atoi(e) & (1 | 4 | 8 | 1024 | 2048);
-    if (const char* e = std::getenv("TREXHIP_ROWS_K")) ctx->tune_rows_k = std::atoi(e);
+    // the two test hooks (INTEGRATION.md "Environment variables"): each chooses between schedules that give identical results.
     // TREXHIP_CONV_GEOM: any of bits 0-11 selects the fp32-activation chain of the identity network; bit 28 keeps conv1 and conv2 apart,
     // bit 29 forces the role-split conv1+conv2 kernel, bit 30 the two-workgroups-per-CU one.  The other bits mean nothing.
     if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e) & (0xfff | (7 << 28));
-#ifdef TREXHIP_DEV_KNOBS
-    if (const char* e = std::getenv("TREXHIP_ROWS_ORDER")) ctx->tune_rows_order = std::atoi(e);
-    if (const char* e = std::getenv("TREXHIP_CCL_STOP")) ctx->tune_ccl_stop = std::atoi(e);
-#endif
-    if (const char* e = std::getenv("TREXHIP_SEG_GROUPS")) ctx->tune_seg_groups = std::atoi(e);
-    if (const char* e = std::getenv("TREXHIP_SEG_SCHEME")) ctx->tune_seg_scheme = std::atoi(e);
     if (const char* e = std::getenv("TREXHIP_CCL_BANDS")) ctx->tune_ccl_bands = std::atoi(e);     // same tables whatever the bands
-    if (const char* e = std::getenv("TREXHIP_CCL_INST")) ctx->tune_ccl_inst = std::atoi(e);      // which k_ccl_lds instance goes first: same results either way
-    if (const char* e = std::getenv("TREXHIP_ROWS_BLOCKS")) { ctx->tune_rows_blocks = std::atoi(e) > 0 ? std::atoi(e) : 8192; ctx->tune_rows_blocks_set = true; }
     const size_t B = p->max_batch, H = p->height, W = p->width, R = p->max_runs, NB = p->max_blobs, P = p->max_pixels;
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete ctx; return TREXHIP_E_DEVICE; }
     ctx->stream = ctx->own_stream;
@@ -262,10 +250,6 @@ void trexhip_destroy(trexhip_ctx* ctx) {
     upload_free(ctx);
     ctx->mem.free_all();
     stage_free(ctx);
-    if (ctx->aux_stream) {
-        (void)hipStreamDestroy(ctx->aux_stream);
-        for (hipEvent_t e : ctx->ev_grp) if (e) (void)hipEventDestroy(e);
-    }
     if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -450,8 +434,7 @@ int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out) {
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     BlobTables& t = ctx->tables;
     const int n = t.valid_n;
-    static const bool export_env = !(std::getenv("TREXHIP_EXPORT") && std::atoi(std::getenv("TREXHIP_EXPORT")) == 0);
-    const bool by_kernel = export_env && n <= EXPORT_MAX_FRAMES;      // a few frames: one launch + one synchronize (k_export)
+    const bool by_kernel = n <= EXPORT_MAX_FRAMES;      // a few frames: one launch + one synchronize (k_export)
     if (n) {
         int rc1 = export_or_fetch_info(ctx, by_kernel);
         if (rc1) return rc1;
@@ -525,13 +508,6 @@ int trexhip_device_view_get(trexhip_ctx* ctx, trexhip_device_view* out) {
     if (!ctx || !out) { set_error("trexhip_device_view_get: null argument"); return TREXHIP_E_INVALID; }
     out->frames = ctx->tables.d_info; out->blobs = ctx->tables.d_blobs; out->runs = ctx->tables.d_runs; out->pixels = ctx->tables.d_pixels;
     out->totals = ctx->tables.d_totals; out->blob_frame = ctx->tables.d_blob_frame;
-    return TREXHIP_OK;
-}
-
-int trexhip_debug_read(trexhip_ctx* ctx, unsigned long long* out, int32_t n) {   /* dev only: phase stamps of k_ccl_lds */
-    if (!ctx || !out) return TREXHIP_E_INVALID;
-    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    TH_CHECK_HIP(hipMemcpy(out, ctx->label.d_cnt_px, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
     return TREXHIP_OK;
 }
 

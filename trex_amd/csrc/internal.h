@@ -170,11 +170,6 @@ struct trexhip_ctx {
     int cnn_mode = TREXHIP_CNN_FP16X3;  // TREXHIP_CNN_*: fp32-class arithmetic on the fp16 matrix cores, range-guarded
 
     bool profiling = false;
-    // tuning knobs (env TREXHIP_ROWS_ORDER / TREXHIP_ROWS_BLOCKS override the defaults)
-    int tune_rows_order = 0;
-    int tune_rows_blocks = 8192;
-    int tune_rows_k = 0;                // frames per wave of k_rows32b (TREXHIP_ROWS_K; 0 = default 8)
-    bool tune_rows_blocks_set = false;  // TREXHIP_ROWS_BLOCKS given: no automatic grid for the wide pixel pass
     int tune_conv_geom = 0;             // dev only: which identity-network chain runs (TREXHIP_CONV_GEOM, bits 0-11 and 28-30)
     // hipFuncSetAttribute is per device: one process may drive several devices through several contexts
     bool attr_cnn = false, attr_ccl = false, attr_split = false, attr_prefilter = false;
@@ -185,13 +180,7 @@ struct trexhip_ctx {
     int color_ch = 0;
     int bg_color_ch = 0;
     int n_cus = 256;                    // compute units of the device (persistent kernels size their grids with it)
-    int tune_seg_groups = 1;            // >1: pixel pass of frame group g+1 on the caller stream, labelling of g on an auxiliary stream (TREXHIP_SEG_GROUPS); measured SLOWER (cross-stream events cost 30-50 us each: 159 -> 266 us at 2 groups), kept off
-    hipStream_t aux_stream = nullptr;   // labelling + gather of a group while the next group's pixel pass runs
-    hipEvent_t ev_grp[10] = {};
-    int tune_seg_scheme = 0;            // TREXHIP_SEG_SCHEME: how the groups use the two streams (launch_segment)
-    int tune_ccl_stop = 0;              // dev only: stop k_ccl_lds after phase N (TREXHIP_CCL_STOP)
-    int tune_ccl_bands = -1;            // dev only: several workgroups per frame (TREXHIP_CCL_BANDS; -1 = by the frames per launch and the hint word, 0 never, n always n bands)
-    int tune_ccl_inst = 0;              // dev only: the k_ccl_lds instance that goes first (TREXHIP_CCL_INST; 0 = by the hint words)
+    int tune_ccl_bands = -1;            // test hook: several workgroups per frame (TREXHIP_CCL_BANDS; -1 = by the frames per launch and the hint word, 0 never, n always n bands)
     uint32_t* h_ccl_hint = nullptr;     // [2] pinned, written by k_ccl_lds: a frame had more lines than the S / the M instance holds
     uint32_t ccl_calls = 0;
     trexhip::Stage stages[TREXHIP_STAGE_COUNT];

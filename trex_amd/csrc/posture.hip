@@ -25,16 +25,10 @@ static constexpr int P_ROWS = 1022;    // rows per blob
 // blobs fit into a CU's LDS -- the kernel is a chain of LDS / memory latencies and lives on the number of blobs in flight)
 __host__ __device__ constexpr int posture_wave_lds(int np, int nr, int nrows) { return np * 8 * 2 + np * 4 * 2 + nr * 4 + (nrows + 2) * 4; }
 
-#ifdef TREXHIP_DEV_KNOBS
-#define POSTURE_STOP(n) do { if (P.stop == (n)) return; } while (0)
-#else
-#define POSTURE_STOP(n) do { } while (0)
-#endif
 struct PostureCfg {
     float outline_resample; int smooth_samples, smooth_step, approximate;
     float curvature_range_ratio, midline_walk_offset; int max_points;
     int nr_cap, rows_cap;            // <= P_NR, P_ROWS
-    int stop;                        // dev only: return after phase N (TREXHIP_POSTURE_STOP)
     int walk_group;                  // bits 8 / 16: blobs whose two-pointer walk searches at most 8 / 16 candidates leave the walk to k_posture_walk<8> / <16>
 };
 
@@ -264,7 +258,6 @@ __global__ __launch_bounds__(256) void k_posture(const PostureCfg P, const trexh
         } while (!(vx == sx && vy == sy && dx == 1 && dy == 0));
         res.n_traced = status ? 0 : nt;                 // an outline beyond the capacity reports no points at all
     }
-    POSTURE_STOP(1);
     int nt_all = traced ? res.n_traced : __shfl(res.n_traced, 0);
     if (!traced) status = __shfl(status, 0);
     res.n_traced = nt_all;
@@ -315,7 +308,6 @@ __global__ __launch_bounds__(256) void k_posture(const PostureCfg P, const trexh
     __builtin_amdgcn_wave_barrier();
     if (status) { if (lane == 0) { res.status = status; out_info[bi] = res; } return; }
 
-    POSTURE_STOP(2);
     float2* pts = bufB; float2* other = bufA;
     // ---- smooth_outline (Outline.cpp:330-378): triangular weights over +-range*step ----
     if (P.smooth_samples > 0 && n > P.smooth_samples) {
@@ -518,7 +510,6 @@ __global__ __launch_bounds__(256) void k_posture(const PostureCfg P, const trexh
         __builtin_amdgcn_wave_barrier();
         float2* t = pts; pts = other; other = t;
     }
-    POSTURE_STOP(3);
     // ---- curvature, tail = highest peak, head = farthest peak ----
     int r = (int)(P.curvature_range_ratio * (float)n); if (r < 1) r = 1;
     for (int i = lane; i < n; i += 64) {
@@ -571,7 +562,6 @@ __global__ __launch_bounds__(256) void k_posture(const PostureCfg P, const trexh
     res.n_outline = n; res.tail_index = 0;
     res.head_index = head == 0x7fffffff ? -1 : ((head - tail) % n + n) % n;
     if (n <= 1) { if (lane == 0) { res.status = 1; out_info[bi] = res; } return; }
-    POSTURE_STOP(4);
     {
         // the walk keeps 3 .. a few lanes of a wave busy (max_offset candidates per search) and is bound by instruction issue: blobs whose
         // searches fit a small lane group are finished by k_posture_walk, several blobs per wave (n_segments = -1 marks them)
@@ -904,11 +894,7 @@ extern "C" int trexhip_posture_device(trexhip_ctx* ctx, int32_t table, const tre
         ctx->attr_posture_bytes = lds_bytes;
     }
     PostureCfg P{pp->outline_resample, pp->outline_smooth_samples, pp->outline_smooth_step, pp->outline_approximate,
-                 pp->outline_curvature_range_ratio, pp->midline_walk_offset, pp->max_points, nr_cap, rows_cap, 0, posture_walk_groups(pp)};
-#ifdef TREXHIP_DEV_KNOBS
-    if (const char* e = std::getenv("TREXHIP_POSTURE_STOP")) P.stop = std::atoi(e);
-    if (const char* e = std::getenv("TREXHIP_POSTURE_WALK_GROUP")) P.walk_group = std::atoi(e);
-#endif
+                 pp->outline_curvature_range_ratio, pp->midline_walk_offset, pp->max_points, nr_cap, rows_cap, posture_walk_groups(pp)};
     stage_begin(ctx, TREXHIP_STAGE_POSTURE);
     hipLaunchKernelGGL(k_posture, dim3((n_blobs + wpb - 1) / wpb), dim3(wpb * 64), lds_bytes, ctx->stream, P, info, bf, bl, ru, n_blobs, ctx->tables.valid_n,
                        reinterpret_cast<float2*>(d_outline), reinterpret_cast<float4*>(d_segments), d_info, (const int32_t*)nullptr, (const trexhip_blob*)nullptr);
@@ -1041,10 +1027,7 @@ extern "C" int trexhip_posture_auto_device(trexhip_ctx* ctx, const trexhip_postu
         rows_cap = (int)std::min<uint32_t>((mrows + 29u) / 32u * 32u + 30u, (uint32_t)P_ROWS);
     }
     PostureCfg P{pp->outline_resample, pp->outline_smooth_samples, pp->outline_smooth_step, pp->outline_approximate,
-                 pp->outline_curvature_range_ratio, pp->midline_walk_offset, pp->max_points, nr_cap, rows_cap, 0, posture_walk_groups(pp)};
-#ifdef TREXHIP_DEV_KNOBS
-    if (const char* e = std::getenv("TREXHIP_POSTURE_WALK_GROUP")) P.walk_group = std::atoi(e);
-#endif
+                 pp->outline_curvature_range_ratio, pp->midline_walk_offset, pp->max_points, nr_cap, rows_cap, posture_walk_groups(pp)};
     int wpb = 1, lds_bytes = 0;
     auto size_launch = [&]() -> int {
         const int wave_lds = posture_wave_lds(MPt, P.nr_cap, P.rows_cap);

@@ -19,7 +19,6 @@
 //   k_gather    1 wave = 1 kept blob: gather grey values, bounding box, integer moments, bid
 #include "internal.h"
 #include <cstddef>
-#include <cstdlib>
 
 namespace trexhip {
 
@@ -184,20 +183,18 @@ __device__ __forceinline__ uint4 load16(const uint8_t* p, int x, int W) {
 }
 
 // One wave = one image row at a time; waves walk the (frame,row) tasks with a grid stride and
-// prefetch the next row's 16-byte loads before they process the current one.
-//   order 0: frame index fastest (concurrent waves share background rows)
-//   order 1: row index fastest   (each frame is streamed front to back)
+// prefetch the next row's 16-byte loads before they process the current one.  Frame index fastest: concurrent waves share background rows.
 template <int NCH, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_rows(const uint8_t* __restrict__ frames,
-                                              const uint8_t* __restrict__ bg, const SegCfg c, const int order,
+                                              const uint8_t* __restrict__ bg, const SegCfg c,
                                               uint32_t* __restrict__ frame_ctr,
                                               uint32_t* __restrict__ row_cnt,
                                               uint32_t* __restrict__ row_off,
-                                              uint32_t* __restrict__ tmp_runs, const uint32_t* __restrict__ bits, const uint32_t f0) {
+                                              uint32_t* __restrict__ tmp_runs, const uint32_t* __restrict__ bits) {
     const int lane = lane_id();
     // the pooled totals of the pass (blobs, runs, pixels) start at zero: written here, ahead of the labelling kernel in stream order (the
     // per-frame counters are handed back zeroed by k_ccl_lds, so a pass needs no memset)
-    if (f0 == 0u && !(order & (1 << 30)) && blockIdx.x == 0 && threadIdx.x < 4) frame_ctr[(size_t)c.ctr_frames * CTR_STRIDE + threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < 4) frame_ctr[(size_t)c.ctr_frames * CTR_STRIDE + threadIdx.x] = 0u;
     const int W = c.W;
     const int WB = (W + 31) / 32;
     const uint32_t ntask = (uint32_t)c.B * (uint32_t)c.H;
@@ -208,14 +205,11 @@ __global__ __launch_bounds__(256) void k_rows(const uint8_t* __restrict__ frames
     uint4 a[NCH], b[NCH];
     // (frame, row) of a task without a division per row: the wave's first task is divided once, every further one is the previous
     // plus a constant step with one carry (the two udiv sequences were ~40 % of the instructions of a row without foreground)
-    const bool frame_fastest = (order & 1) == 0;
-    const uint32_t modulus = frame_fastest ? (uint32_t)c.B : (uint32_t)c.H;           // c.B = frames of this launch
+    const uint32_t modulus = (uint32_t)c.B;                                         // c.B = frames of this launch
     const uint32_t step_lo = nwave % modulus, step_hi = nwave / modulus;
-    uint32_t cur_lo = task % modulus, cur_hi = task / modulus;                      // lo = fastest index, hi = the other
+    uint32_t cur_lo = task % modulus, cur_hi = task / modulus;                      // lo = frame (the fastest index), hi = row
     auto advance = [&](uint32_t& lo, uint32_t& hi) { lo += step_lo; hi += step_hi; if (lo >= modulus) { lo -= modulus; ++hi; } };
-    auto issue = [&](uint32_t lo, uint32_t hi) {
-        const uint32_t f = f0 + (frame_fastest ? lo : hi);
-        const uint32_t y = frame_fastest ? hi : lo;
+    auto issue = [&](uint32_t f, uint32_t y) {
         const uint8_t* fp = frames + ((size_t)f * c.H + y) * W;
         const uint8_t* bp = bg + (size_t)y * W;
 #pragma unroll
@@ -232,8 +226,7 @@ __global__ __launch_bounds__(256) void k_rows(const uint8_t* __restrict__ frames
     };
     issue(cur_lo, cur_hi);
     for (; task < ntask; task += nwave) {
-        const uint32_t f = f0 + (frame_fastest ? cur_lo : cur_hi);
-        const uint32_t y = frame_fastest ? cur_hi : cur_lo;
+        const uint32_t f = cur_lo, y = cur_hi;
         advance(cur_lo, cur_hi);                             // now the next task's coordinates
         uint32_t m[NCH];
         bool any = false;
@@ -257,19 +250,12 @@ __global__ __launch_bounds__(256) void k_rows(const uint8_t* __restrict__ frames
                         mm &= nz;
                     }
                 } else
-#ifdef TREXHIP_DEV_KNOBS
-                mm = (order & 512) ? ((a[ch].x ^ b[ch].x) == 0x12345u) : mask16(a[ch], b[ch], c);
-#else
                 mm = mask16(a[ch], b[ch], c);
-#endif
                 if (!ALIGNED && x + 16 > W) mm &= (1u << (W - x)) - 1u;
             }
             m[ch] = mm;
             any |= mm != 0;
         }
-#ifdef TREXHIP_DEV_KNOBS
-        if (order & 256) any = false;
-#endif
         // registers a/b are free again: prefetch the next row while this one is finished
         if (task + nwave < ntask) issue(cur_lo, cur_hi);
 
@@ -337,26 +323,19 @@ __global__ __launch_bounds__(256) void k_rows(const uint8_t* __restrict__ frames
 // masks of one row-task: 32 pixels per lane per 2048-pixel chunk
 template <int NCH, int MODE>
 __device__ __forceinline__ bool rows32_masks(const uint4 (&a)[NCH][2], const uint4 (&b)[NCH][2], const SegCfg& c, const int lane, const int W,
-                                             const int order, uint32_t (&m)[NCH]) {
+                                             uint32_t (&m)[NCH]) {
     bool any = false;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
         const int x = ch * 2048 + lane * 32;
         uint32_t mm = 0;
         if (x < W) {
-#ifdef TREXHIP_DEV_KNOBS
-            if (order & 4096) mm = ((a[ch][0].x ^ b[ch][0].x ^ a[ch][1].y ^ b[ch][1].w) == 0x12345u);      // profiling aid: stream only
-            else
-#endif
             if constexpr (MODE == 0) mm = mask16(a[ch][0], b[ch][0], c) | (mask16(a[ch][1], b[ch][1], c) << 16);
             else mm = mask16_fast<MODE>(a[ch][0], b[ch][0], c) | (mask16_fast<MODE>(a[ch][1], b[ch][1], c) << 16);
         }
         m[ch] = mm;
         any |= mm != 0;
     }
-#ifdef TREXHIP_DEV_KNOBS
-    if (order & 8192) any = false;                                                                            // profiling aid: no run extraction
-#endif
     return any;
 }
 
@@ -420,15 +399,15 @@ __device__ __forceinline__ void rows32_emit(const uint32_t (&m)[NCH], const bool
 
 template <int NCH, int MODE = 0>
 __global__ __launch_bounds__(256) void k_rows32(const uint8_t* __restrict__ frames,
-                                                const uint8_t* __restrict__ bg, const SegCfg c, const int order,
+                                                const uint8_t* __restrict__ bg, const SegCfg c,
                                                 uint32_t* __restrict__ frame_ctr,
                                                 uint32_t* __restrict__ row_cnt,
                                                 uint32_t* __restrict__ row_off,
-                                                uint32_t* __restrict__ tmp_runs, const uint32_t f0) {
+                                                uint32_t* __restrict__ tmp_runs) {
     const int lane = lane_id();
     // the pooled totals of the pass (blobs, runs, pixels) start at zero: written here, ahead of the labelling kernel in stream order (the
     // per-frame counters are handed back zeroed by k_ccl_lds, so a pass needs no memset)
-    if (f0 == 0u && !(order & (1 << 30)) && blockIdx.x == 0 && threadIdx.x < 4) frame_ctr[(size_t)c.ctr_frames * CTR_STRIDE + threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < 4) frame_ctr[(size_t)c.ctr_frames * CTR_STRIDE + threadIdx.x] = 0u;
     const int W = c.W;
     const uint32_t ntask = (uint32_t)c.B * (uint32_t)c.H;
     const uint32_t nwave = gridDim.x * 4u;
@@ -436,14 +415,11 @@ __global__ __launch_bounds__(256) void k_rows32(const uint8_t* __restrict__ fram
     if (task >= ntask) return;
 
     uint4 a[NCH][2], b[NCH][2];
-    const bool frame_fastest = (order & 1) == 0;
-    const uint32_t modulus = frame_fastest ? (uint32_t)c.B : (uint32_t)c.H;
+    const uint32_t modulus = (uint32_t)c.B;
     const uint32_t step_lo = nwave % modulus, step_hi = nwave / modulus;
-    uint32_t cur_lo = task % modulus, cur_hi = task / modulus;
+    uint32_t cur_lo = task % modulus, cur_hi = task / modulus;                      // lo = frame (the fastest index), hi = row
     auto advance = [&](uint32_t& lo, uint32_t& hi) { lo += step_lo; hi += step_hi; if (lo >= modulus) { lo -= modulus; ++hi; } };
-    auto issue = [&](uint32_t lo, uint32_t hi) {
-        const uint32_t f = f0 + (frame_fastest ? lo : hi);
-        const uint32_t y = frame_fastest ? hi : lo;
+    auto issue = [&](uint32_t f, uint32_t y) {
         const uint8_t* fp = frames + ((size_t)f * c.H + y) * W;
         const uint8_t* bp = bg + (size_t)y * W;
 #pragma unroll
@@ -459,11 +435,10 @@ __global__ __launch_bounds__(256) void k_rows32(const uint8_t* __restrict__ fram
     };
     issue(cur_lo, cur_hi);
     for (; task < ntask; task += nwave) {
-        const uint32_t f = f0 + (frame_fastest ? cur_lo : cur_hi);
-        const uint32_t y = frame_fastest ? cur_hi : cur_lo;
+        const uint32_t f = cur_lo, y = cur_hi;
         advance(cur_lo, cur_hi);
         uint32_t m[NCH];
-        const bool any = rows32_masks<NCH, MODE>(a, b, c, lane, W, order, m);
+        const bool any = rows32_masks<NCH, MODE>(a, b, c, lane, W, m);
         if (task + nwave < ntask) issue(cur_lo, cur_hi);
         rows32_emit<NCH>(m, any, c, f, y, lane, W, frame_ctr, row_cnt, row_off, tmp_runs);
     }
@@ -471,26 +446,25 @@ __global__ __launch_bounds__(256) void k_rows32(const uint8_t* __restrict__ fram
 
 // The wide pass with the background row held in registers: a wave takes row y of K consecutive frames (K divides the number of
 // frames of the launch), so the 2 KB background row is loaded once per K frame rows instead of once per frame row -- half the load
-// instructions and half the L2 -> CU traffic of the kernel above.  Wave w: row w % H, frames (w / H) * K ...
+// instructions and half the L2 -> CU traffic of the kernel above.  Wave w: row w % H, frames (w / H) * K ...: neighbouring waves read
+// neighbouring rows of the same frames.  Measured against frame groups fastest, alternated on three boxes: 215 against 220 us on two of them,
+// 189 against 215 on the third.
 template <int NCH, int MODE = 0>
 __global__ __launch_bounds__(256) void k_rows32b(const uint8_t* __restrict__ frames,
-                                                 const uint8_t* __restrict__ bg, const SegCfg c, const int order, const int K,
+                                                 const uint8_t* __restrict__ bg, const SegCfg c, const int K,
                                                  uint32_t* __restrict__ frame_ctr,
                                                  uint32_t* __restrict__ row_cnt,
                                                  uint32_t* __restrict__ row_off,
-                                                 uint32_t* __restrict__ tmp_runs, const uint32_t f0) {
+                                                 uint32_t* __restrict__ tmp_runs) {
     const int lane = lane_id();
     // the pooled totals of the pass (blobs, runs, pixels) start at zero: written here, ahead of the labelling kernel in stream order (the
     // per-frame counters are handed back zeroed by k_ccl_lds, so a pass needs no memset)
-    if (f0 == 0u && !(order & (1 << 30)) && blockIdx.x == 0 && threadIdx.x < 4) frame_ctr[(size_t)c.ctr_frames * CTR_STRIDE + threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < 4) frame_ctr[(size_t)c.ctr_frames * CTR_STRIDE + threadIdx.x] = 0u;
     const int W = c.W;
     const uint32_t groups = (uint32_t)c.B / (uint32_t)K;
     const uint32_t wid = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (wid >= groups * (uint32_t)c.H) return;
-    uint32_t y = wid / groups, fb = f0 + (wid - y * groups) * (uint32_t)K;
-    // rows fastest (the default): neighbouring waves read neighbouring rows of the same frames.  Measured against frame groups fastest
-    // (TREXHIP_ROWS_ORDER bit 0) alternated on three boxes: 215 against 220 us on two of them, 189 against 215 on the third
-    if (!(order & 1)) { const uint32_t gq = wid / (uint32_t)c.H; y = wid - gq * (uint32_t)c.H; fb = f0 + gq * (uint32_t)K; }
+    const uint32_t gq = wid / (uint32_t)c.H, y = wid - gq * (uint32_t)c.H, fb = gq * (uint32_t)K;
     uint4 a[NCH][2], b[NCH][2];
     const uint8_t* bp = bg + (size_t)y * W;
     auto issue = [&](uint32_t f) {
@@ -529,7 +503,7 @@ __global__ __launch_bounds__(256) void k_rows32b(const uint8_t* __restrict__ fra
     issue(fb);
     for (int k = 0; k < K; ++k) {
         uint32_t m[NCH];
-        const bool any = rows32_masks<NCH, MODE>(a, b, c, lane, W, order, m);
+        const bool any = rows32_masks<NCH, MODE>(a, b, c, lane, W, m);
         if (k + 1 < K) issue(fb + k + 1);
         rows32_emit<NCH>(m, any, c, fb + k, y, lane, W, frame_ctr, row_cnt, row_off, tmp_runs);
     }
@@ -846,7 +820,7 @@ __global__ __launch_bounds__(256) void k_blobs(const SegCfg c, const int only_pe
 //   s_b  flatten scratch (P4) | ordinal of a root run (P5a) | pixels per raw blob (P5b) | kept index or ~0 (P6, P7) | segment cursor or ~0
 // ---------------------------------------------------------------------------------------------
 // Instantiated BY CAPACITY (round 6): a workgroup that holds 8160 lines needs all 160 KB of a CU and 16 waves whatever the frame carries, so one
-// frame occupies one CU.  The smaller instances leave room for several frames per CU (and for the pixel pass of another group beside them):
+// frame occupies one CU.  The smaller instances leave room for several frames per CU:
 //   L  1024 threads, 8160 lines, 160 KB  (a 4096 x 4096 frame of 256 individuals: ~7.7 k lines)
 //   M   512 threads, 3840 lines,  76 KB  (two per CU; a 2048 x 2048 frame of 100 individuals: ~2.5 k lines)
 //   S   256 threads, 2000 lines,  40 KB  (four per CU; 1280 x 720 with 32 blobs: ~0.7 k lines; TRex's one-frame calls)
@@ -1013,8 +987,7 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
                                                   uint32_t* __restrict__ pix_begin, int32_t* __restrict__ blob_map,
                                                   uint32_t* __restrict__ totals, trexhip_frame_info* __restrict__ info,
                                                   trexhip_blob* __restrict__ blobs, uint32_t* __restrict__ blob_frame,
-                                                  trexhip_run* __restrict__ out_runs, const int dbg_stop,
-                                                  unsigned long long* __restrict__ dbg, const int f0,
+                                                  trexhip_run* __restrict__ out_runs, const int f0,
                                                   const uint8_t* __restrict__ own_frames /* gray frames: the workgroup also gathers its frame's blobs; else null */,
                                                   uint8_t* __restrict__ own_pixels,
                                                   const int retry_only /* 1: only the frames a smaller instance left for this one */,
@@ -1024,13 +997,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
     static_assert(NT % 64 == 0 && NT <= 1024 && (SA & (SA - 1)) == 0 && SA >= NMAX && SA % NT == 0 && NMAX <= CCL_NMAX, "k_ccl_lds: geometry");
     constexpr int NW = NT / 64;                   // waves
     constexpr int NSW = NT >= 1024 ? 2 : 4;       // row sweeps whose count / offset / raster index / first run stay in registers
-#ifdef TREXHIP_DEV_KNOBS
-#define CCL_STAMP(i) do { if (dbg_stop == -1 && blockIdx.x == 0 && threadIdx.x == 0) dbg[i] = __builtin_readcyclecounter(); } while (0)
-#define CCL_STOP(n) do { if (dbg_stop == (n)) return; } while (0)
-#else
-#define CCL_STAMP(i) do { } while (0)
-#define CCL_STOP(n) do { } while (0)
-#endif
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t* s_a = smem;                         // [SA] (see above)
     uint32_t* s_run = s_a + SA;             // x0 | x1 << 16, raster order
@@ -1047,7 +1013,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
     uint32_t* rb = row_base + (size_t)f * (H + 1);
     const size_t fo = (size_t)f * c.R;
 
-    CCL_STAMP(0);
     if (retry_only && info[f].reserved[0] != 3u) return;      // (block-uniform: every thread reads the same word) the frame was finished by a smaller instance
     // the frame's overflow-area counter: thread 0 reads it and hands it back zeroed for the next pass (every path: a frame left pending for the
     // global-memory chain did not overflow, and that chain's own check then reads 0)
@@ -1123,8 +1088,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
     }
     if (tid == 0) { rb[H] = n; if (rb_lds) s_key[H] = n; }
     __syncthreads();
-    CCL_STOP(1);
-    CCL_STAMP(1);
     const int slack = c.slack;
     if (banded) {
         // banded (k_ccl_band): lines and band-local roots come from the run-level tables, only the seams are left to link
@@ -1167,8 +1130,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
         for (uint32_t i = 0; i < k; ++i) { s_run[b + i] = tmp[o + i]; s_y[b + i] = (uint16_t)y; s_par[b + i] = b + i; }
     }
     __syncthreads();
-    CCL_STOP(2);
-    CCL_STAMP(2);
     // P3: link every run with the touching runs of the row above (thread per run, binary search for the first candidate)
     for (uint32_t r = tid; r < n; r += NT) {
         const int y = s_y[r];
@@ -1188,15 +1149,11 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
     }
     }
     __syncthreads();
-    CCL_STOP(3);
-    CCL_STAMP(3);
     // P4: flatten
     for (uint32_t r = tid; r < n; r += NT) { const uint32_t root = lds_find(s_par, r); s_b[r] = root; }
     __syncthreads();
     for (uint32_t r = tid; r < n; r += NT) s_par[r] = s_b[r];
     __syncthreads();
-    CCL_STOP(4);
-    CCL_STAMP(4);
     // P5: blob ordinals (raster order of the root run) -> s_b at the roots; the run-level state of the re-threshold pass (root label, ordinal
     // of a root) goes to global memory here, then every run's label becomes its blob's ordinal and s_a / s_b count runs / pixels per blob
     uint32_t nraw = 0;
@@ -1226,8 +1183,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
         atomicAdd(s_b + o, (q >> 16) - (q & 0xffffu) + 1u);
     }
     __syncthreads();
-    CCL_STOP(5);
-    CCL_STAMP(5);
     // P6: size filter, offsets of the kept blobs.  s_a[o] = runs | first slot of the segment << 16 (both < 8192), s_b[o] = kept index or ~0
     uint32_t kept = 0, kruns = 0, kpx = 0;
     uint32_t* pbg = pix_begin + fo;
@@ -1270,8 +1225,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
         if (tid == 0) { fi.flags |= TREXHIP_FRAME_OVERFLOW_OUTPUT; info[f] = fi; }
         return;
     }
-    CCL_STOP(6);
-    CCL_STAMP(6);
     // P7: blob records, raster-order runs for the re-threshold pass, largest kept blob (decides the grouping strategy, block-uniform)
     uint32_t mx = 0;
     for (uint32_t o = tid; o < nraw; o += NT) {
@@ -1291,8 +1244,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
         trexhip_run q; q.x0 = (uint16_t)(s_run[r] & 0xffffu); q.x1 = (uint16_t)(s_run[r] >> 16); q.y = s_y[r]; q.pad = 0;
         raster[fo + r] = q;
     }
-    CCL_STOP(7);
-    CCL_STAMP(7);
     mx = wmax32(mx);
     __syncthreads();
     if ((tid & 63) == 0) s_misc[40 + (tid >> 6)] = mx;
@@ -1312,7 +1263,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
             s_seg[(s_a[o] >> 16) + slot] = (uint16_t)r;
         }
         __syncthreads();
-        CCL_STAMP(9);
         // (2) an in-register bitonic network per blob -- two blobs per wave (32 lanes each) when both have at most 32 lines, one per wave
         //     up to 64 lines, rank-by-counting through LDS beyond that.  The waves walk the RAW ordinals; a dropped blob counts 0 lines
         const uint32_t lane = tid & 63, wave = tid >> 6;
@@ -1402,7 +1352,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
             outr[i] = q;
         }
     }
-    CCL_STAMP(8);
     if (tid == 0) {
         fi.n_blobs = kept; fi.n_runs = kruns; fi.n_pixels = kpx;
         fi.blob_begin = bb; fi.run_begin = rbeg; fi.pix_begin = pb;
@@ -1421,8 +1370,6 @@ __global__ __launch_bounds__(NT) void k_ccl_lds(const SegCfg c, uint32_t* __rest
         gather_blobs<false, 16>(c, 0, own_frames, info, blob_frame, blobs, out_runs, own_pixels, 0u, 0xffffffffu, nullptr, 0, 0,
                                 bb + (uint32_t)(tid >> 6) * 4u, 4u * NW, bb + kept, f, rbeg, pb);
     }
-#undef CCL_STAMP
-#undef CCL_STOP
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1540,7 +1487,7 @@ __device__ __forceinline__ void gather_blobs(const SegCfg& c, const int only_pen
             const uint2 rn = *reinterpret_cast<const uint2*>(&blobs[bi].run_begin);
             B.run_begin = rn.x; B.n_runs = rn.y; B.pix_begin = blobs[bi].pix_begin;
         }
-        active = active && (own_frame >= 0 || (f < (uint32_t)c.B && f >= f0 && f < f1));   // else: hole left by a frame that overflowed the pool / another group's frame
+        active = active && (own_frame >= 0 || (f < (uint32_t)c.B && f >= f0 && f < f1));   // else: hole left by a frame that overflowed the pool / a frame outside [f0, f1)
         struct { uint32_t run_begin, pix_begin; } fi = {own_run_begin, own_pix_begin};
         if (active && own_frame < 0) {                           // off the critical path unless only_pending
             const uint2 rp = *reinterpret_cast<const uint2*>(&info[f].run_begin);
@@ -1706,24 +1653,26 @@ __global__ __launch_bounds__(256) void k_gather(const SegCfg c, const int only_p
 // ---------------------------------------------------------------------------------------------
 template <bool ALIGNED>
 static void launch_rows(int nch, dim3 grid, hipStream_t s, const uint8_t* frames, const uint8_t* bg,
-                        const SegCfg& c, int order, uint32_t* ctr, uint32_t* row_cnt, uint32_t* row_off, uint32_t* tmp, const uint32_t* bits, uint32_t f0) {
+                        const SegCfg& c, uint32_t* ctr, uint32_t* row_cnt, uint32_t* row_off, uint32_t* tmp, const uint32_t* bits) {
     switch (nch) {
-        case 1: hipLaunchKernelGGL((k_rows<1, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, order, ctr, row_cnt, row_off, tmp, bits, f0); break;
-        case 2: hipLaunchKernelGGL((k_rows<2, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, order, ctr, row_cnt, row_off, tmp, bits, f0); break;
-        case 3: hipLaunchKernelGGL((k_rows<3, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, order, ctr, row_cnt, row_off, tmp, bits, f0); break;
-        case 4: hipLaunchKernelGGL((k_rows<4, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, order, ctr, row_cnt, row_off, tmp, bits, f0); break;
+        case 1: hipLaunchKernelGGL((k_rows<1, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, ctr, row_cnt, row_off, tmp, bits); break;
+        case 2: hipLaunchKernelGGL((k_rows<2, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, ctr, row_cnt, row_off, tmp, bits); break;
+        case 3: hipLaunchKernelGGL((k_rows<3, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, ctr, row_cnt, row_off, tmp, bits); break;
+        case 4: hipLaunchKernelGGL((k_rows<4, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, ctr, row_cnt, row_off, tmp, bits); break;
         case 5: case 6:
-                hipLaunchKernelGGL((k_rows<6, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, order, ctr, row_cnt, row_off, tmp, bits, f0); break;
-        default: hipLaunchKernelGGL((k_rows<8, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, order, ctr, row_cnt, row_off, tmp, bits, f0); break;
+                hipLaunchKernelGGL((k_rows<6, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, ctr, row_cnt, row_off, tmp, bits); break;
+        default: hipLaunchKernelGGL((k_rows<8, ALIGNED>), grid, dim3(256), 0, s, frames, bg, c, ctr, row_cnt, row_off, tmp, bits); break;
     }
 }
 
+// One detect pass on the context's stream: [morphology] -> pixel pass -> [k_ccl_band] -> k_ccl_lds [-> its L instance for the frames the first one
+// could not hold] -> [k_gather].  Every choice below is made from what the call can see (frame size and count, alignment, settings, CUs, the two
+// hint words); none changes a result.
 int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
     SegCfg c = ctx->cfg;
     c.B = n;
     ctx->batch_invert = c.invert; ctx->batch_zero_bg = c.zero_bg;      // the batch's own copy: downstream calls on this batch use it
-    hipStream_t s_main = ctx->stream;
-    hipStream_t s = s_main;
+    hipStream_t s = ctx->stream;
     const int H = c.H, W = c.W;
     const int nch = (W + 1023) / 1024;
     if (nch > 8) { set_error("frame width > 8192 is not supported yet"); return TREXHIP_E_UNSUPPORTED; }
@@ -1732,8 +1681,6 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
     // zeroed at create.  A pass that was left half-queued by an error return below leaves the flag up: the next one starts from clean counters)
     if (ctx->ctr_dirty) TH_CHECK_HIP(hipMemsetAsync(ctx->d_ctr, 0, sizeof(uint32_t) * ((size_t)ctx->p.max_batch * CTR_STRIDE + 4), s));
     ctx->ctr_dirty = true;
-    const unsigned want = (unsigned)(((size_t)H * n + 3) / 4);
-    const dim3 grid_rows(want < (unsigned)ctx->tune_rows_blocks ? want : (unsigned)ctx->tune_rows_blocks);
     const bool aligned = (W % 16 == 0) && ((reinterpret_cast<uintptr_t>(d_frames) & 15) == 0) &&
                          ((reinterpret_cast<uintptr_t>(ctx->d_bg) & 15) == 0);
     const uint32_t* bits = nullptr;
@@ -1757,149 +1704,100 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
     // held the frames of the earlier calls, told by two pinned words the kernels write (a frame had more lines than S / than M holds).  A wrong
     // guess costs time, never results: frames the first instance cannot hold are finished by the L instance queued right behind it.  Every 64th
     // call the words are cleared, so a context whose frames got emptier finds its way back down.
-    // TREXHIP_CCL_INST (dev): 1 S, 2 M, 3 L.  (M with 1024 threads and S with 512 were measured too: profiles/r06_ccl_by_capacity.txt, variants 4 and 5.)
-    int inst = ctx->tune_ccl_inst;
+    // inst: 1 S, 2 M, 3 L.  (M with 1024 threads and S with 512 were measured too: profiles/r06_ccl_by_capacity.txt, variants 4 and 5.)
     if ((++ctx->ccl_calls & 63) == 0) { ctx->h_ccl_hint[0] = 0u; ctx->h_ccl_hint[1] = 0u; }
-    if (inst <= 0) {
-        inst = 3;
-        if (n >= 2 * ctx->n_cus) {
-            const uint32_t over_s = __atomic_load_n(&ctx->h_ccl_hint[0], __ATOMIC_RELAXED), over_m = __atomic_load_n(&ctx->h_ccl_hint[1], __ATOMIC_RELAXED);
-            inst = over_m ? 3 : (over_s ? 2 : 1);
-            if (c.R <= CCL_S_NMAX) inst = 1; else if (c.R <= CCL_M_NMAX && inst > 2) inst = 2;     // max_runs itself bounds the lines of a frame
-        }
+    int inst = 3;
+    if (n >= 2 * ctx->n_cus) {
+        const uint32_t over_s = __atomic_load_n(&ctx->h_ccl_hint[0], __ATOMIC_RELAXED), over_m = __atomic_load_n(&ctx->h_ccl_hint[1], __ATOMIC_RELAXED);
+        inst = over_m ? 3 : (over_s ? 2 : 1);
+        if (c.R <= CCL_S_NMAX) inst = 1; else if (c.R <= CCL_M_NMAX && inst > 2) inst = 2;     // max_runs itself bounds the lines of a frame
     }
     uint32_t* totals = ctx->tables.d_totals;
-    // The batch can be cut into groups of frames so that the labelling of one group (latency chains, one workgroup per frame) runs beside the
-    // pixel pass of another (HBM-bound, every CU).  TREXHIP_SEG_GROUPS = G, TREXHIP_SEG_SCHEME:
-    //   0  pixel passes on the caller's stream, labelling of group g on an auxiliary stream behind an event (rounds 4-5: slower, the L instance needs a whole CU)
-    //   1  group g as a whole (pixel pass, labelling) on stream g % 2; the pixel pass of g waits for the pixel pass of g - 1 (one event per group)
-    //   2  the same without events between the groups: the two streams start together, the auxiliary one at the lowest priority
-    int G = ctx->tune_seg_groups;
-    const int scheme = ctx->tune_seg_scheme;
-    if (G > 8) G = 8;
-    if (G < 1 || n < 2 * G) G = 1;
-    if (G > 1 && !ctx->aux_stream) {
-        int plo = 0, phi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-        TH_CHECK_HIP(hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, scheme == 0 ? phi : (scheme == 2 ? plo : 0)));
-        // (the events order kernels of this device only: no system-scope fence, i.e. no write-back / invalidate of the caches, when one is recorded)
-        static const unsigned ev_flags = std::getenv("TREXHIP_EVENT_FLAGS") ? (unsigned)std::strtoul(std::getenv("TREXHIP_EVENT_FLAGS"), nullptr, 0) : (hipEventDisableTiming | hipEventDisableSystemFence);
-        for (int g = 0; g < 10; ++g) TH_CHECK_HIP(hipEventCreateWithFlags(&ctx->ev_grp[g], ev_flags));
-    }
-    int order_bits = ctx->tune_rows_order;
-    if (G > 1 && scheme >= 1) {
-        // the pooled totals start at zero BEFORE either stream starts (the pixel pass of frame 0 does it otherwise, in stream order ahead of its labelling)
-        TH_CHECK_HIP(hipMemsetAsync(totals, 0, 16, s));
-        order_bits |= 1 << 30;
-        TH_CHECK_HIP(hipEventRecord(ctx->ev_grp[9], s));
-        TH_CHECK_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_grp[9], 0));
-    }
-    const int gs = (n + G - 1) / G;
-    // gray pixel arrays: k_ccl_lds gathers the blobs of the frame it has just labelled (TREXHIP_FUSE_GATHER=0: the separate k_gather launch);
-    // the colour encodings keep k_gather (one wave per blob, colour addressing)
+    // gray pixel arrays: k_ccl_lds gathers the blobs of the frame it has just labelled; the colour encodings keep k_gather (one wave per blob,
+    // colour addressing)
     // ... when the launch gives (nearly) every CU a frame.  With fewer frames the labelling workgroups are the only ones at work and the gather
     // is better spread over the idle CUs by its own launch (round 6, profiles/r06_fuse_gather.txt; us per detect pass, fused / separate:
     // C4 1 frame 47.7 / 39.3, 16 frames 71.0 / 59.7; C5 64 frames 347 / 313, 16 frames 170 / 134; C2 64 frames 44.8 / 45.8; C4 256 frames: fused 5 us ahead)
-    static const int fuse_env = std::getenv("TREXHIP_FUSE_GATHER") ? std::atoi(std::getenv("TREXHIP_FUSE_GATHER")) : -1;
-    const bool fuse_gather = ctx->p.pixel_encoding == TREXHIP_ENC_GRAY && (fuse_env >= 0 ? fuse_env != 0 : 4 * n >= 3 * ctx->n_cus);
+    const bool fuse_gather = ctx->p.pixel_encoding == TREXHIP_ENC_GRAY && 4 * n >= 3 * ctx->n_cus;
+
+    // the pixel pass
     stage_begin(ctx, TREXHIP_STAGE_ROWS);
-    for (int g = 0; g < G; ++g) {
-        const int f0 = g * gs, f1 = (g + 1) * gs < n ? (g + 1) * gs : n;
-        if (f0 >= f1) break;
-        SegCfg cg = c;
-        cg.B = f1 - f0;
-        hipStream_t s = s_main;
-        if (G > 1 && scheme >= 1) {
-            s = (g & 1) ? ctx->aux_stream : s_main;
-            if (scheme == 1 && g > 0) TH_CHECK_HIP(hipStreamWaitEvent(s, ctx->ev_grp[g - 1], 0));      // behind the previous group's pixel pass
-        }
-        const unsigned wantg = (unsigned)(((size_t)H * cg.B + 3) / 4);
-        const int nch32 = (W + 2047) / 2048;
-        const bool wide = aligned && !bits && W % 32 == 0 && nch32 <= 4 && W >= 1024 && !(ctx->tune_rows_order & 1024);   // TREXHIP_ROWS_ORDER bit 10: 16 pixels per lane
-        // rows per wave: the wide kernel is fastest with ~4 rows per wave (measured at 256 frames of 2048^2: 8192 blocks 266 us, 16384: 260,
-        // 32768 = 4 rows per wave: 250, 65536: 268); TREXHIP_ROWS_BLOCKS overrides
-        unsigned cap = (unsigned)ctx->tune_rows_blocks;
-        if (wide && !ctx->tune_rows_blocks_set) { cap = wantg / 4; if (cap < 2048u) cap = 2048u; }
-        const dim3 grid_g(wantg < cap ? wantg : cap);
-        if (wide) {
-            // compile-time modes of the common settings (see exact4_fast); TREXHIP_ROWS_ORDER bit 11 keeps the generic kernel
-            int mode = 0;
-            if (cg.enable_diff && !cg.invert && cg.tmax >= 255 && cg.tmin >= 1 && !(ctx->tune_rows_order & 2048)) mode = (cg.absdiff ? 1 : 2) | (cg.zero_bg ? 4 : 0);
-            // background row in registers for K frames (k_rows32b) when K divides the launch's frames; TREXHIP_ROWS_ORDER bit 2 keeps k_rows32
-            int K = 0;
-            if (!(ctx->tune_rows_order & 4)) { const int want = ctx->tune_rows_k > 0 ? ctx->tune_rows_k : 8; for (int k = want; k >= 2; --k) if (cg.B % k == 0) { K = k; break; } }
-            const dim3 grid_b(K ? (unsigned)(((size_t)H * (cg.B / K) + 3) / 4) : 1u);
-            // (k_rows32b for one and, since round 6, two 2048-pixel chunks: the two-chunk form needed its loads written without conditional 128-bit
-            // assignments, on which hipcc 7.2 crashes; TREXHIP_ROWS_ORDER bit 3 keeps k_rows32 for two chunks)
-#define TH_ROWS32(NCH_, MODE_) do { if (K && NCH_ == 1) hipLaunchKernelGGL((k_rows32b<1, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, K, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); \
-                                    else if (K && NCH_ == 2 && !(ctx->tune_rows_order & 8)) hipLaunchKernelGGL((k_rows32b<2, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, K, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); \
-                                    else hipLaunchKernelGGL((k_rows32<NCH_, MODE_>), grid_g, dim3(256), 0, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, (uint32_t)f0); } while (0)
+    const unsigned want = (unsigned)(((size_t)H * n + 3) / 4);
+    const int nch32 = (W + 2047) / 2048;
+    const bool wide = aligned && !bits && W % 32 == 0 && nch32 <= 4 && W >= 1024;       // 32 pixels per lane (k_rows32 / k_rows32b); else 16 (k_rows)
+    // rows per wave: the wide kernel is fastest with ~4 rows per wave (measured at 256 frames of 2048^2: 8192 blocks 266 us, 16384: 260,
+    // 32768 = 4 rows per wave: 250, 65536: 268)
+    unsigned cap = 8192u;
+    if (wide) { cap = want / 4; if (cap < 2048u) cap = 2048u; }
+    const dim3 grid_rows(want < cap ? want : cap);
+    if (wide) {
+        // compile-time modes of the common settings (see exact4_fast)
+        int mode = 0;
+        if (c.enable_diff && !c.invert && c.tmax >= 255 && c.tmin >= 1) mode = (c.absdiff ? 1 : 2) | (c.zero_bg ? 4 : 0);
+        // background row in registers for K frames (k_rows32b) when a K in 8..2 divides the launch's frames
+        int K = 0;
+        for (int k = 8; k >= 2; --k) if (n % k == 0) { K = k; break; }
+        const dim3 grid_b(K ? (unsigned)(((size_t)H * (n / K) + 3) / 4) : 1u);
+        // (k_rows32b for one and, since round 6, two 2048-pixel chunks: the two-chunk form needed its loads written without conditional 128-bit
+        // assignments, on which hipcc 7.2 crashes)
+#define TH_ROWS32(NCH_, MODE_) do { if (K && NCH_ == 1) hipLaunchKernelGGL((k_rows32b<1, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, c, K, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs); \
+                                    else if (K && NCH_ == 2) hipLaunchKernelGGL((k_rows32b<2, MODE_>), grid_b, dim3(256), 0, s, d_frames, ctx->d_bg, c, K, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs); \
+                                    else hipLaunchKernelGGL((k_rows32<NCH_, MODE_>), grid_rows, dim3(256), 0, s, d_frames, ctx->d_bg, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs); } while (0)
 #define TH_ROWS32_M(NCH_) do { switch (mode) { case 1: TH_ROWS32(NCH_, 1); break; case 2: TH_ROWS32(NCH_, 2); break; case 5: TH_ROWS32(NCH_, 5); break; \
                                                case 6: TH_ROWS32(NCH_, 6); break; default: TH_ROWS32(NCH_, 0); } } while (0)
-            switch (nch32) {
-                case 1: TH_ROWS32_M(1); break;
-                case 2: TH_ROWS32_M(2); break;
-                case 3: TH_ROWS32_M(3); break;
-                default: TH_ROWS32_M(4); break;
-            }
+        switch (nch32) {
+            case 1: TH_ROWS32_M(1); break;
+            case 2: TH_ROWS32_M(2); break;
+            case 3: TH_ROWS32_M(3); break;
+            default: TH_ROWS32_M(4); break;
+        }
 #undef TH_ROWS32_M
 #undef TH_ROWS32
-        } else
-        if (aligned) launch_rows<true>(nch, grid_g, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits, (uint32_t)f0);
-        else         launch_rows<false>(nch, grid_g, s, d_frames, ctx->d_bg, cg, order_bits, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits, (uint32_t)f0);
-        if (g == G - 1) stage_end(ctx, TREXHIP_STAGE_ROWS);
-        hipStream_t t = s;
-        if (G > 1 && scheme == 0) {
-            TH_CHECK_HIP(hipEventRecord(ctx->ev_grp[g], s));
-            TH_CHECK_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_grp[g], 0));
-            t = ctx->aux_stream;
-        } else if (G > 1 && scheme == 1 && g + 1 < G) TH_CHECK_HIP(hipEventRecord(ctx->ev_grp[g], s));
-        // run-level CCL of every frame inside one workgroup's LDS; frames with too many runs are left pending
-        // and finished by the global-memory chain in finish_segment()
-        // several workgroups per frame (k_ccl_band) when the launch leaves CUs idle AND the frames are heavy: bands of at most CCLB_ROWS rows, as many as
-        // there are CUs per frame (at most 8), none of fewer than 64 rows.  The extra launch + the reload cost ~10 us and save phases 2 and 3 of
-        // k_ccl_lds: 29 us for a 4096 x 4096 frame of 6.4 k lines, 10 us for a 2048 x 2048 frame of 2.5 k, 2 us for C2 -- measured (us per pass, one
-        // workgroup per frame / banded): C5 64 frames 325 / 313, 16 frames 133 / 119; C4 one frame 38.9 / 41.9, 64 frames 95 / 100; C2 one frame 23 / 34.
-        // So: only for frames of more lines than the M instance holds (the pinned hint word the kernels of the context's earlier calls wrote).
-        // TREXHIP_CCL_BANDS (dev, read at trexhip_create): 0 never, n >= 2 always n bands.  Same tables either way (tests/test_segment_gpu.py).
-        int n_bands = 1;
-        if (inst == 3) {
-            int want = ctx->tune_ccl_bands >= 0 ? ctx->tune_ccl_bands
-                                                : ((2 * (f1 - f0) <= ctx->n_cus && __atomic_load_n(&ctx->h_ccl_hint[1], __ATOMIC_RELAXED)) ? ctx->n_cus / (f1 - f0) : 0);
-            if (want > 8) want = 8;
-            while (want > 1 && (H + want - 1) / want < 64) --want;
-            if (want >= 2 && (H + want - 1) / want <= CCLB_ROWS) n_bands = want;
-        }
-        const int band_rows = n_bands > 1 ? (H + n_bands - 1) / n_bands : 0;
-        if (n_bands > 1)
-            hipLaunchKernelGGL(k_ccl_band, dim3((f1 - f0) * n_bands), dim3(CCLB_NT), CCLB_LDS_BYTES, t, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base, ctx->d_tmp_runs,
-                               ctx->label.d_raster, ctx->label.d_parent, ctx->d_band_fail, n_bands, band_rows, f0);
-#define TH_CCL(NT_, NMAX_, SA_, RETRY_) hipLaunchKernelGGL((k_ccl_lds<NT_, NMAX_, SA_>), dim3(f1 - f0), dim3(NT_), (CclLds<NMAX_, SA_>::BYTES), t, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base, \
-                           ctx->d_tmp_runs, ctx->label.d_raster, ctx->label.d_parent, ctx->label.d_root_ord, ctx->label.d_cur_run, ctx->label.d_pix_begin, ctx->label.d_blob_map,                           \
-                           totals, ctx->tables.d_info, ctx->tables.d_blobs, ctx->tables.d_blob_frame, ctx->tables.d_runs, ctx->tune_ccl_stop, reinterpret_cast<unsigned long long*>(ctx->label.d_cnt_px), f0, \
-                           fuse_gather ? d_frames : (const uint8_t*)nullptr, ctx->tables.d_pixels, RETRY_, ctx->h_ccl_hint, (NT_) == 1024 && (NMAX_) == CCL_NMAX && !(RETRY_) ? band_rows : 0, ctx->d_band_fail)
-        switch (inst) {
-            case 1: TH_CCL(256, CCL_S_NMAX, CCL_S_SA, 0); break;
-            case 2: TH_CCL(512, CCL_M_NMAX, CCL_M_SA, 0); break;
-            default: TH_CCL(1024, CCL_NMAX, CCL_SORT, 0); break;
-        }
-        if (inst != 3) TH_CCL(1024, CCL_NMAX, CCL_SORT, 1);      // returns at once for every frame the first instance finished
-#undef TH_CCL
-        static const int gather_blocks_env = std::getenv("TREXHIP_GATHER_BLOCKS") ? std::atoi(std::getenv("TREXHIP_GATHER_BLOCKS")) : 0;
-        // (eight blobs per workgroup; a launch of a few frames does not need 2048 workgroups that look at the total and leave)
-        const unsigned gather_need = (unsigned)(((size_t)(f1 - f0) * ctx->p.max_blobs + 7) / 8);
-        const unsigned gather_grid = gather_blocks_env > 0 ? (unsigned)gather_blocks_env : (gather_need < 16u ? 16u : (gather_need > 2048u ? 2048u : gather_need));
-        if (!fuse_gather)
-        LAUNCH_GATHER(dim3(G > 1 ? 256 : gather_grid), t, c, 0, d_frames, totals, ctx->tables.d_info, ctx->tables.d_blob_frame,
-                           ctx->tables.d_blobs, ctx->tables.d_runs, ctx->tables.d_pixels, (uint32_t)f0, (uint32_t)f1, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
+    } else if (aligned) launch_rows<true>(nch, grid_rows, s, d_frames, ctx->d_bg, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits);
+    else                launch_rows<false>(nch, grid_rows, s, d_frames, ctx->d_bg, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->d_tmp_runs, bits);
+    stage_end(ctx, TREXHIP_STAGE_ROWS);
+
+    // run-level CCL of every frame inside one workgroup's LDS; frames with too many runs are left pending
+    // and finished by the global-memory chain (launch_pending)
+    // several workgroups per frame (k_ccl_band) when the launch leaves CUs idle AND the frames are heavy: bands of at most CCLB_ROWS rows, as many as
+    // there are CUs per frame (at most 8), none of fewer than 64 rows.  The extra launch + the reload cost ~10 us and save phases 2 and 3 of
+    // k_ccl_lds: 29 us for a 4096 x 4096 frame of 6.4 k lines, 10 us for a 2048 x 2048 frame of 2.5 k, 2 us for C2 -- measured (us per pass, one
+    // workgroup per frame / banded): C5 64 frames 325 / 313, 16 frames 133 / 119; C4 one frame 38.9 / 41.9, 64 frames 95 / 100; C2 one frame 23 / 34.
+    // So: only for frames of more lines than the M instance holds (the pinned hint word the kernels of the context's earlier calls wrote).
+    // TREXHIP_CCL_BANDS (test hook, read at trexhip_create): 0 never, n >= 2 always n bands.  Same tables either way (tests/test_segment_gpu.py).
+    int n_bands = 1;
+    if (inst == 3) {
+        int bands = ctx->tune_ccl_bands >= 0 ? ctx->tune_ccl_bands
+                                             : ((2 * n <= ctx->n_cus && __atomic_load_n(&ctx->h_ccl_hint[1], __ATOMIC_RELAXED)) ? ctx->n_cus / n : 0);
+        if (bands > 8) bands = 8;
+        while (bands > 1 && (H + bands - 1) / bands < 64) --bands;
+        if (bands >= 2 && (H + bands - 1) / bands <= CCLB_ROWS) n_bands = bands;
     }
-    if (G > 1) {
-        TH_CHECK_HIP(hipEventRecord(ctx->ev_grp[8], ctx->aux_stream));
-        TH_CHECK_HIP(hipStreamWaitEvent(s_main, ctx->ev_grp[8], 0));
+    const int band_rows = n_bands > 1 ? (H + n_bands - 1) / n_bands : 0;
+    if (n_bands > 1)
+        hipLaunchKernelGGL(k_ccl_band, dim3(n * n_bands), dim3(CCLB_NT), CCLB_LDS_BYTES, s, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base, ctx->d_tmp_runs,
+                           ctx->label.d_raster, ctx->label.d_parent, ctx->d_band_fail, n_bands, band_rows, 0);
+#define TH_CCL(NT_, NMAX_, SA_, RETRY_) hipLaunchKernelGGL((k_ccl_lds<NT_, NMAX_, SA_>), dim3(n), dim3(NT_), (CclLds<NMAX_, SA_>::BYTES), s, c, ctx->d_ctr, ctx->label.d_row_cnt, ctx->d_row_off, ctx->label.d_row_base, \
+                       ctx->d_tmp_runs, ctx->label.d_raster, ctx->label.d_parent, ctx->label.d_root_ord, ctx->label.d_cur_run, ctx->label.d_pix_begin, ctx->label.d_blob_map,                           \
+                       totals, ctx->tables.d_info, ctx->tables.d_blobs, ctx->tables.d_blob_frame, ctx->tables.d_runs, 0,                                                                                 \
+                       fuse_gather ? d_frames : (const uint8_t*)nullptr, ctx->tables.d_pixels, RETRY_, ctx->h_ccl_hint, (NT_) == 1024 && (NMAX_) == CCL_NMAX && !(RETRY_) ? band_rows : 0, ctx->d_band_fail)
+    switch (inst) {
+        case 1: TH_CCL(256, CCL_S_NMAX, CCL_S_SA, 0); break;
+        case 2: TH_CCL(512, CCL_M_NMAX, CCL_M_SA, 0); break;
+        default: TH_CCL(1024, CCL_NMAX, CCL_SORT, 0); break;
+    }
+    if (inst != 3) TH_CCL(1024, CCL_NMAX, CCL_SORT, 1);      // returns at once for every frame the first instance finished
+#undef TH_CCL
+    if (!fuse_gather) {
+        // (eight blobs per workgroup; a launch of a few frames does not need 2048 workgroups that look at the total and leave)
+        const unsigned gather_need = (unsigned)(((size_t)n * ctx->p.max_blobs + 7) / 8);
+        const unsigned gather_grid = gather_need < 16u ? 16u : (gather_need > 2048u ? 2048u : gather_need);
+        LAUNCH_GATHER(dim3(gather_grid), s, c, 0, d_frames, totals, ctx->tables.d_info, ctx->tables.d_blob_frame,
+                      ctx->tables.d_blobs, ctx->tables.d_runs, ctx->tables.d_pixels, 0u, (uint32_t)n, ctx->d_color_src, ctx->color_ch, ctx->p.pixel_encoding);
     }
     stage_end(ctx, TREXHIP_STAGE_SEGMENT_ALL);
     TH_CHECK_HIP(hipGetLastError());
-    ctx->ctr_dirty = false;              // every frame's labelling kernel is queued behind its rows kernel
+    ctx->ctr_dirty = false;              // the labelling kernel of every frame is queued behind the rows kernel
     ctx->d_frames = d_frames;
     ctx->tables.valid_n = n;
     ctx->tables.fetched = false;
