@@ -5,6 +5,8 @@ import pytest
 import torch
 from oracle import oracle
 from trex_amd import capi, synth
+import ccl_scenes as cs
+from rethreshold_checks import assert_per_blob_equal, assert_sub_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -89,14 +91,53 @@ def test_per_blob_thresholds():
     dthr = torch.from_numpy(thr).cuda()
     seg.rethreshold_per_blob(dthr.data_ptr(), method=0)
     sub = seg.fetch(rethreshold=True)[0]
-    for k, b in enumerate(det.blobs):
-        mine = sub.blobs[sub.blobs["parent"] == det.info["blob_begin"] + k]
-        if thr[k] < 0:
-            assert len(mine) == 0
-            continue
-        rs = det.runs[b["run_begin"]:b["run_begin"] + b["n_runs"]]
-        px = det.pixels[b["pix_begin"]:b["pix_begin"] + b["n_pixels"]]
-        ob, orr, opx = oracle.threshold_blob(rs, px, bg, 0, int(thr[k]))
-        assert sorted(mine["n_pixels"].tolist()) == sorted(ob["n_pixels"].tolist())
-        assert sorted(mine["bid"].tolist()) == sorted(ob["bid"].tolist())
+    # per detect blob: the sorted pixel counts and bids of its sub-blobs, then every sub-blob matched by bid: its lines, pixels, counts, bounding box and
+    # moments; with size ranges its class too
+    assert_per_blob_equal(det, sub, bg, thr, 0)
+    ranges = [(20, 200), (400, 900)]
+    for method in (0, 1):
+        seg.rethreshold_per_blob(dthr.data_ptr(), method=method, size_ranges=ranges)
+        sub = seg.fetch(rethreshold=True)[0]
+        assert_per_blob_equal(det, sub, bg, thr, method, ranges)
+        assert len(set(sub.blobs["flags"].tolist())) > 1
     seg.close()
+
+
+@pytest.mark.parametrize("case", sorted(cs.SETTINGS_CASES))
+def test_detect_settings_reach_pass_two(case):
+    """what pass 2 takes over from the detect pass's configuration: connectivity (k_link2's c.slack), image_invert (k_sub's c.invert), a detect size
+    filter that drops blobs (blob_map == -1: their lines give no sub-runs), and detect thresholds that change which lines there are"""
+    kw = cs.SETTINGS_CASES[case]
+    bg, scene = cs.settings_scene()
+    H, W = bg.shape
+    fr = (255 - scene) if kw.get("image_invert") else scene
+    key = cs.register(("settings", case), bg, fr)
+    ranges = [(4, 60)]
+    if "size_ranges" in kw:
+        n_all, n_kept = len(oracle.segment(fr, bg, oracle.make_params(W, H))[0]), len(cs.detect_tables(key, **kw)[0])
+        assert 0.3 * n_all < n_kept < 0.7 * n_all, (n_all, n_kept)   # some dropped, some kept
+    seg = capi.Segmenter(capi.default_params(W, H, max_batch=1, max_blobs=32768, **kw))
+    seg.set_background(bg)
+    d = torch.from_numpy(fr[None]).cuda()
+    seg.segment_device(d.data_ptr(), 1)
+    det = seg.fetch()[0]
+    assert len(det.blobs) == len(cs.detect_tables(key, **kw)[0]) > 10
+    for method, thr in ((0, 30), (1, 25), (2, 100)):
+        want = cs.sub_tables(key, method, thr, ranges, **kw)
+        assert len(want[0]) > 10
+        seg.rethreshold(thr, method, ranges)
+        assert_sub_equal(seg.fetch(rethreshold=True)[0], det, want)
+    seg.close()
+
+
+@pytest.mark.parametrize("W", [17, 1001, 1030, 2050, 2080, 4096])
+def test_widths(W):
+    """pass 2 behind every pixel pass: unaligned widths, rows of more than 2048 pixels with textured lines across x = 2047 / 2048 and one that ends
+    with the row, in batches of 8 and 3 frames, so that k_rows32b (several frames per wave) produces the row lists k_sub starts from"""
+    for n in (8, 3):
+        bg, frames = cs.wide_frames(W, n)
+        det, sub = run(np.stack(frames), bg, 40, 0, [(4, 60)])
+        for i, fr in enumerate(frames):
+            want = cs.sub_tables(cs.register(("wide", W, n, i), bg, fr), 0, 40, [(4, 60)])
+            assert len(want[1]) > len(cs.detect_tables(("wide", W, n, i))[1]) > 0          # the threshold cuts lines apart
+            assert_sub_equal(sub[i], det[i], want)

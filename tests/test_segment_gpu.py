@@ -7,6 +7,7 @@ import pytest
 import torch
 from oracle import oracle
 from trex_amd import capi, synth
+from ccl_scenes import band_frames, ladder_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -440,24 +441,7 @@ def test_several_workgroups_per_frame_give_the_same_tables(bands, monkeypatch):
     workgroup per frame), 8- and 4-connectivity -- every table byte for byte the oracle's."""
     monkeypatch.setenv("TREXHIP_CCL_BANDS", str(bands))
     rng = np.random.default_rng(100 + bands)
-    W, H = 1024, 2048
-    bg = np.full((H, W), 120, np.uint8)
-    frames = []
-    f = bg.copy()                                                    # tall columns and diagonals through every seam
-    for x in range(20, 1000, 480):
-        f[int(rng.integers(0, 400)):int(rng.integers(1500, H)), x:x + int(rng.integers(1, 9))] = 10
-    for k in range(0, 400):
-        f[300 + k * 2:300 + k * 2 + 3, 40 + k:40 + k + 2] = 10       # a staircase: 8-connected only through its corners in places
-    frames.append(f)
-    f, _ = synth.random_scene(rng, W, H, density=0.018); frames.append(f)        # ~6000 lines: labelled in LDS, banded
-    f, _ = synth.random_scene(rng, W, H, density=0.05); frames.append(f)         # ~16000 lines: the global-memory chain (the band workgroups leave it alone)
-    f = bg.copy(); f[H // 2 - 3:H // 2 + 3, :] = 10; f[::2, 5:9] = 10; frames.append(f)       # a bar on the middle seam, single-line blobs everywhere
-    f = bg.copy()                                                    # ~5000 lines inside ONE band of rows: the band workgroup cannot hold them
-    for y in range(0, 250):
-        for j in range(20):
-            f[y, 10 + 50 * j:10 + 50 * j + 3 + (y % 7)] = 10
-    frames.append(f)
-    frames.append(bg.copy())                                         # an empty frame
+    bg, frames = band_frames(rng)                                    # 1024 x 2048
     for kw in (dict(), dict(connectivity=4)):
         res = run_gpu(np.stack(frames), bg, max_runs=20000, max_blobs=16384, max_pixels=1 << 21, **kw)
         for r, fr in zip(res, frames):
@@ -510,26 +494,6 @@ def test_wide_frames_with_the_background_in_registers(W, kw):
         res = run_gpu(np.stack(frames), bg, **kw)
         for r, fr in zip(res, frames):
             assert_frame_equal(r, fr, bg, **kw)
-
-
-def ladder_frames():
-    """six 128 x 128 frames on a flat background: two light (under 2000 lines), two medium (2001 .. 3840), two heavy (3841 .. 8160); noise of
-    many small blobs beside structured frames whose lines all belong to a few large blobs"""
-    rng = np.random.default_rng(2000)
-    W = H = 128
-    bg = np.full((H, W), 120, np.uint8)
-    def noise(density):
-        f = bg.copy(); f[rng.random((H, W)) < density] = 10
-        return f
-    light = bg.copy()                                                # a few solid blobs, one of them through most rows
-    light[5:120, 10:14] = 10; light[30:40, 40:90] = 10; light[60:100:2, 20:120] = 10; light[110:125, 100:127] = 10
-    medium = bg.copy()                                               # 24 lines in every row, joined by a bar every 16 rows: few blobs of many lines
-    for j in range(24): medium[:, 2 + 5 * j:2 + 5 * j + 1 + j % 4] = 10
-    medium[::16, :] = 10
-    heavy = bg.copy()                                                # lines of two pixels, one apart, shifted row by row: ONE 8-connected blob of ~5.4 k lines
-    ys, xs = np.mgrid[0:H, 0:W]
-    heavy[(xs + ys) % 3 != 0] = 10
-    return bg, [noise(0.05), light], [noise(0.2), medium], [noise(0.5), heavy]
 
 
 def test_instance_ladder_by_the_shipped_policy():

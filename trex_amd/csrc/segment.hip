@@ -1841,13 +1841,15 @@ __device__ __forceinline__ bool track_pass(int p, int b, int method, int thr) {
     return d >= thr;
 }
 
-// thread per image row: for every run of a KEPT detect blob count (write=0) or emit (write=1) its sub-runs
+// thread per image row: for every run of a KEPT detect blob count (write=0) or emit (write=1) its sub-runs.  A run of L pixels breaks into up to
+// ceil(L / 2) sub-runs, so a frame whose detect lines fit R can have more than R sub-runs: k_sub_scan flags it in info2, and the emitting pass
+// (which runs behind k_sub_scan) leaves such a frame alone -- every frame it does write has its n2 <= R sub-runs inside its own share of raster2
 template <int WRITE>
 __global__ __launch_bounds__(256) void k_sub(const SegCfg c, const uint8_t* __restrict__ frames, const uint8_t* __restrict__ bg,
                                              const uint32_t* __restrict__ row_base, const trexhip_run* __restrict__ raster,
                                              const uint32_t* __restrict__ label, const uint32_t* __restrict__ root_ord,
                                              const int32_t* __restrict__ blob_map, const trexhip_frame_info* __restrict__ info,
-                                             const int method, const int thr_all, const int32_t* __restrict__ blob_thr,
+                                             const trexhip_frame_info* __restrict__ info2, const int method, const int thr_all, const int32_t* __restrict__ blob_thr,
                                              uint32_t* __restrict__ sub_cnt,
                                              const uint32_t* __restrict__ sub_base, trexhip_run* __restrict__ raster2,
                                              uint32_t* __restrict__ run_parent2) {
@@ -1856,6 +1858,7 @@ __global__ __launch_bounds__(256) void k_sub(const SegCfg c, const uint8_t* __re
     const int f = gid / c.H, y = gid - f * c.H;
     const trexhip_frame_info fi = info[f];
     if (fi.flags) return;
+    if (WRITE && info2[f].flags) return;
     const uint32_t* rb = row_base + (size_t)f * (c.H + 1);
     const size_t fo = (size_t)f * c.R;
     const uint8_t* img = frames + ((size_t)f * c.H + y) * c.W;
@@ -1964,11 +1967,11 @@ int launch_rethreshold(trexhip_ctx* ctx, int thr, int method, const double* rang
     const dim3 grid_r((unsigned)((n * c.H + 255) / 256));
     TH_CHECK_HIP(hipMemsetAsync(q.tables.d_totals, 0, sizeof(uint32_t) * 4, s));
     hipLaunchKernelGGL((k_sub<0>), grid_r, dim3(256), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->label.d_row_base, ctx->label.d_raster, ctx->label.d_parent,
-                       ctx->label.d_root_ord, ctx->label.d_blob_map, ctx->tables.d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.label.d_raster, q.d_run_parent);
+                       ctx->label.d_root_ord, ctx->label.d_blob_map, ctx->tables.d_info, q.tables.d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.label.d_raster, q.d_run_parent);
     hipLaunchKernelGGL(k_sub_scan, dim3(n), dim3(256), 0, s, c, ctx->tables.d_info, ctx->label.d_row_base, q.d_sub_cnt, q.d_sub_base, q.label.d_row_base,
                        q.label.d_row_cnt, q.label.d_parent, q.tables.d_info);
     hipLaunchKernelGGL((k_sub<1>), grid_r, dim3(256), 0, s, c, ctx->d_frames, ctx->d_bg, ctx->label.d_row_base, ctx->label.d_raster, ctx->label.d_parent,
-                       ctx->label.d_root_ord, ctx->label.d_blob_map, ctx->tables.d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.label.d_raster, q.d_run_parent);
+                       ctx->label.d_root_ord, ctx->label.d_blob_map, ctx->tables.d_info, q.tables.d_info, method, thr, d_blob_thr, q.d_sub_cnt, q.d_sub_base, q.label.d_raster, q.d_run_parent);
     hipLaunchKernelGGL(k_link2, grid_r, dim3(256), 0, s, c, q.label.d_row_base, q.label.d_raster, q.label.d_parent, q.tables.d_info);
     hipLaunchKernelGGL(k_flatten, grid_r, dim3(256), 0, s, c, 0, q.label.d_row_cnt, q.label.d_row_base, q.label.d_parent, q.tables.d_info);
     hipLaunchKernelGGL(k_blobs, dim3(n), dim3(256), 0, s, c, 0, q.label.d_raster, q.label.d_parent, q.label.d_root_ord, q.label.d_cnt_runs, q.label.d_cnt_px, q.label.d_cur_run,
