@@ -3,6 +3,7 @@
      masks the reference drew injected, and
  (2) the CPU restatement (oracle/cnn_train_oracle.py) at the batch size VINetwork uses.
 fp32 on both sides; the bar is relative to each tensor's largest gradient (sums of 1e4..1e6 terms in another order), stated below."""
+import functools
 import os
 import numpy as np
 import pytest
@@ -315,3 +316,58 @@ def test_step_is_the_same_bits_on_every_kind_of_caller_stream():
         assert loss == results[0][1] and correct == results[0][2], kind
         for k in NAMES:
             assert np.array_equal(p_[k], results[0][3][k]) and np.array_equal(g_[k], results[0][4][k]), (kind, k)
+
+
+RESIZE_STEPS = (67, 1, 33)          # a batch that is no multiple of the 32- and 64-sample tiles, a single sample, and up again
+# Adam's first steps move every element by about lr whatever the size of its gradient, so two fp32 implementations part by 2 lr per step in
+# the elements whose gradient is rounding noise (at lr = 1e-3 convolution weights of size 0.05 differ by 4 % after one step, and the next
+# step's gradients by more than 10 %: measured).  The restatement below carries its own state, so lr keeps the two on one trajectory:
+# 2 lr x 3 steps = 6e-7 on weights of 0.05 is 1.2e-5 relative, a twentieth of GRAD_RTOL
+RESIZE_LR = 1e-7
+
+
+@functools.lru_cache(maxsize=None)
+def resize_reference():
+    """The restatement's three steps (its own Adam state carried along), computed once for both precisions and left unchanged."""
+    classes, ch, seed, lr = 257, 3, 4100, RESIZE_LR
+    state = weights.synthetic_state(classes, seed, channels=ch)
+    adam = tro.new_adam_state(state)
+    rng = np.random.default_rng(seed)
+    steps, st = [], state
+    for s, n in enumerate(RESIZE_STEPS):
+        x, y = weights.synthetic_train_batch(n, seed + 1 + s, classes, ch)
+        masks = {"d1": rng.random((n, 16)) >= 0.05, "d2": rng.random((n, 64)) >= 0.05, "d3": rng.random((n, 128)) >= 0.05, "d4": rng.random((n, 100)) >= 0.05}
+        st, loss, correct, grads = tro.train_step(st, adam, x, y, masks, lr, threads=16)
+        steps.append((x, y, masks, loss, correct, grads, st))
+    return classes, ch, lr, state, steps
+
+
+@pytest.mark.parametrize("precision", [0, 1])
+def test_one_trainer_follows_the_oracle_while_its_batch_size_changes(precision):
+    """One trainer sized for 67 samples takes steps of 67, 1 and 33 samples with injected masks; after each step the loss, the correct count,
+    every gradient and every parameter are held to the restatement.  Everything the step derives from n -- grids, mask plane offsets, the
+    partial counts of the reductions, the shares of the weight gradients -- must follow the batch at hand, not the largest one, and nothing of
+    a larger batch may be left over in a smaller one's sums.  Bars as in the tests above: 5e-5 on the loss, GRAD_RTOL on the gradients, 1e-4 on
+    the parameters (running statistics included: they take a tenth of each batch's statistics)."""
+    classes, ch, lr, state, steps = resize_reference()
+    seg = make_seg()
+    tr = capi.Trainer(seg, weights.pack_blob(state, classes, ch), max_batch=max(RESIZE_STEPS), lr=lr, precision=precision)
+    for s, (x, y, masks, loss_ref, correct_ref, grads, new) in enumerate(steps):
+        loss, correct = step(tr, x, y, masks)
+        g = read_all(tr, classes, ch, 1)
+        p = read_all(tr, classes, ch, 0)
+        print(f"step {s} n {x.shape[0]} precision {precision}: loss {loss:.7f} ref {loss_ref:.7f} correct {correct} ref {correct_ref}")
+        for k in tro.TRAINABLE + tro.BUFFERS:
+            dg = f"|dg| {float(np.abs(g[k] - grads[k]).max()):.3g} of max|g| {float(np.abs(grads[k]).max()):.3g}; " if k in grads else ""
+            print(f"  {k}: {dg}|dp| {float(np.abs(p[k] - new[k]).max()):.3g} of max|p| {float(np.abs(new[k]).max()):.3g}")
+        assert abs(loss - loss_ref) <= 5e-5 * max(1.0, abs(loss_ref)) and correct == correct_ref, (s, loss, loss_ref, correct, correct_ref)
+        for k in tro.TRAINABLE:
+            if k in CONV_BIAS:
+                continue
+            tol = GRAD_RTOL * float(np.abs(grads[k]).max()) + 1e-9
+            assert np.abs(g[k] - grads[k]).max() <= tol, (s, k, float(np.abs(g[k] - grads[k]).max()), tol)
+        for k in tro.TRAINABLE + tro.BUFFERS:
+            assert np.abs(p[k] - new[k]).max() <= 1e-4 * max(1.0, np.abs(new[k]).max()), (s, k, float(np.abs(p[k] - new[k]).max()))
+    assert tr.steps == len(steps)
+    tr.close()
+    seg.close()

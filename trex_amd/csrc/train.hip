@@ -18,6 +18,9 @@
 // flipped + transposed weights); weight gradients = k_t_wgrad (fp32 MFMA, operands straight from L2: one MFMA k-step = two pixels,
 // A = activations at the tap's shift, B = dz); batch-norm statistics and their backward sums in double; everything else VALU.
 // Every reduction has a fixed order: two runs of a step give identical bits.
+// Host side (below the kernels): each of the three blocks is one `Layer` -- shape, tensor ids, buffers, and the kernel instances of the
+// trainer's precision bound to their LDS sizes -- filled once in trexhip_trainer_create; the forward pass, block_backward and trainer_attrs
+// walk that table.
 #include "internal.h"
 #include "conv_f32.h"
 #include "cnn_weights.h"
@@ -1357,6 +1360,78 @@ __global__ __launch_bounds__(256) void k_t_masks(uint8_t* __restrict__ keep, siz
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// The 80x80 network as the host sees it (the kernels carry the same numbers as their own literals)
+static constexpr int IMG = 80, IMG_PIX = IMG * IMG;                  // crop side; every block halves it: 80 -> 40 -> 20 -> 10
+static constexpr int FC1_POS = (IMG / 8) * (IMG / 8), HID = 100;     // fc1: 100 positions x 128 channels -> 100 outputs
+static constexpr int FC1_K = 128 * FC1_POS;                          // = 12800
+// keep masks of one step: four planes back to back, [n][16] [n][64] [n][128] (Dropout2d behind block 1..3) [n][100] (Dropout behind fc1);
+// plane i starts at keep + n * KEEP_OFF[i]
+static constexpr int KEEP_OFF[4] = {0, 16, 16 + 64, 16 + 64 + 128}, KEEP_ROW = 16 + 64 + 128 + HID;
+static_assert(KEEP_ROW == 308 && FC1_K == 12800, "mask row / fc1 of the 80x80 network");
+static constexpr int C1_BPC = IMG / 4, WG1_BPC = IMG / 8;            // workgroups per crop of k_t_conv1 (4 rows each) and k_t_wgrad1 (8 rows)
+static constexpr int RED_BLOCKS = 256, BWD_BLOCKS = 1024;            // grids of the reduction kernels (partials: red[BWD_BLOCKS][2][128])
+
+// What each event of a step orders.  "main" is the context's stream, "side" the trainer's second one
+enum {
+    EV_PARAMS,       // main -> side: the side stream starts behind whatever wrote the parameters last
+    EV_PACKED,       // side -> main: this step's fp16 weight images are packed (conv2 is the first to read them)
+    EV_FORWARD,      // main -> side: the head has run (its gradients, fc1's weight gradient, the loss sum)
+    EV_DZ3,          // main -> side: block i's dz is in z_i (bias finaliser, weight gradient)
+    EV_DZ2,
+    EV_DZ1,
+    EV_SIDE_DONE,    // side -> main: the side stream's last piece of this step -- the join in front of Adam
+    EV_MASKS,        // side -> main: this step's keep masks are drawn
+    EV_COUNT
+};
+
+// A kernel instance that needs hipFuncAttributeMaxDynamicSharedMemorySize, bound to its geometry where it is named (trexhip_trainer_create):
+// trainer_attrs and the launches read the same entry.  A convolution is one of three kernels (exactly one pointer is set)
+struct ConvKernel {
+    decltype(&k_conv5<16, 64, 40, 20, 16, CONV_EPI_RAW, 64>) f32 = nullptr;      // exact fp32 MFMA
+    decltype(&k_conv5_n16<64, 40, 20, 16>) f32_n16 = nullptr;                    // ... 16 output channels on 16x16x4 tiles
+    decltype(&k_t_conv5_h2<16, 64, 40, 20, 16, 64>) h2 = nullptr;                // fp16 two-piece split
+    int lds = 0, bpc = 0;                                                        // dynamic LDS bytes, workgroups per crop
+    int cic = 0, co = 0;                                                         // input-channel chunk and output-channel tile of its weight image
+    const void* fn() const { return f32 ? reinterpret_cast<const void*>(f32) : f32_n16 ? reinterpret_cast<const void*>(f32_n16) : reinterpret_cast<const void*>(h2); }
+};
+template <int CI, int CO, int S, int ROWS, int CIC, int COUT>
+static ConvKernel conv_f32() { using G = ConvGeom<CI, CO, S, ROWS, CIC>; return {&k_conv5<CI, CO, S, ROWS, CIC, CONV_EPI_RAW, COUT>, nullptr, nullptr, G::LDS_BYTES, G::BPC, CIC, CO}; }
+template <int CI, int S, int ROWS, int CIC>
+static ConvKernel conv_f32_n16() { using G = ConvGeom16<CI, S, ROWS, CIC>; return {nullptr, &k_conv5_n16<CI, S, ROWS, CIC>, nullptr, G::LDS_BYTES, G::BPC, CIC, 16}; }
+template <int CI, int CO, int S, int ROWS, int CIC, int COUT>
+static ConvKernel conv_h2() { using G = ConvGeomH<CI, CO, S, ROWS, CIC>; return {nullptr, nullptr, &k_t_conv5_h2<CI, CO, S, ROWS, CIC, COUT>, G::LDS_BYTES, G::BPC, CIC, CO}; }
+// a weight gradient: grid = (block types, shares of the batch's work units), partials part[share][tap][ci][co]
+struct WgradKernel {
+    decltype(&k_t_wgrad<16, 64, 40, 16, 64, 3, 5>) fn = nullptr;                 // (k_t_wgrad_h2 has the same signature)
+    int lds = 0, types = 0, units = 0 /*work units per crop*/, threads = 0, max_shares = 0;
+};
+template <int CI, int CO, int S, int CIS, int COS, int MT, int ROWS>
+static WgradKernel wgrad_f32(int max_shares) { using G = WgradGeom<CI, CO, S, CIS, COS, MT, ROWS>; return {&k_t_wgrad<CI, CO, S, CIS, COS, MT, ROWS>, G::LDS_BYTES, G::TYPES, G::NB, 512, max_shares}; }
+template <int CI, int CO, int S, int CIS, int ROWS>
+static WgradKernel wgrad_h2(int max_shares) { using G = WgradHGeom<CI, CO, S, CIS, ROWS>; return {&k_t_wgrad_h2<CI, CO, S, CIS, ROWS>, G::LDS_BYTES, G::TYPES, G::NB, G::NTHR, max_shares}; }
+
+// One convolution block [conv5x5 -> BatchNorm2d -> ReLU -> MaxPool2 -> Dropout2d], stated once (trexhip_trainer_create fills the three)
+struct Layer {
+    int C, CI, S;                          // output / input channels, input side: z [n][S][S][C], a and da [n][S/2][S/2][C]
+    int w, b, g, be, rm, rv;               // tensor ids: weight, bias, gamma, beta, running mean, running variance
+    int dz_event;                          // recorded when its dz is complete
+    int slot;                              // its statistics: stat + slot * 512 (mean, invstd, sums[2] x 128), red_bias + slot * BWD_BLOCKS * 128
+    int keep_off;                          // its keep masks inside the mask row
+    // the BN kernels at its channel count
+    decltype(&k_t_bn_stats<64>) bn_stats;
+    decltype(&k_t_bn_pool<64>) bn_pool;
+    decltype(&k_t_pool_bwd_stats<64>) pool_bwd_stats;
+    decltype(&k_t_bn_bwd<64>) bn_bwd;
+    float *z = nullptr, *a = nullptr, *da = nullptr;
+    // blocks 2 and 3: the three roles of its convolution at the trainer's precision, and the weight images they read
+    ConvKernel fwd, dgrad;
+    WgradKernel wgrad;
+    int pack_blocks = 0;                   // grid of k_t_pack_h2
+    uint4 *wh_f = nullptr, *wh_b = nullptr;   // precision 0: fp16 two-piece operand images (forward, data gradient) and their scale
+    float* wh_scale = nullptr;
+    float* wb = nullptr;                   // precision 1: flipped + transposed weights of the data gradient
+};
+
 struct Trainer {
     trexhip_ctx* ctx = nullptr;
     int classes = 0, CH = 1, max_n = 0;
@@ -1365,11 +1440,10 @@ struct Trainer {
     size_t off[T_COUNT + 1] = {}, cnt[T_COUNT] = {};
     size_t total = 0;
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
-    float *z1 = nullptr, *a1 = nullptr, *z2 = nullptr, *a2 = nullptr, *z3 = nullptr, *a3 = nullptr, *da3 = nullptr, *da2 = nullptr, *da1 = nullptr;
-    float *wb3 = nullptr, *wb2 = nullptr, *part = nullptr, *stat = nullptr /*3 x (mean, invstd, sums[2]) x 128*/;
-    // precision 0: fp16 two-piece operand images of the conv2 / conv3 weights (forward, data gradient) and their scales
-    uint4 *wh2f = nullptr, *wh2b = nullptr, *wh3f = nullptr, *wh3b = nullptr;
-    float* wh_scale = nullptr;
+    Layer L[3] = {};
+    decltype(&k_t_conv1<1>) conv1 = nullptr;      // block 1's convolution and weight gradient (no MFMA) at the trainer's 1 or 3 input channels
+    decltype(&k_t_wgrad1<1>) wgrad1 = nullptr;
+    float *part = nullptr /*conv2's / conv3's weight-gradient partials*/, *stat = nullptr /*3 x (mean, invstd, sums[2]) x 128*/;
     float *hpart = nullptr, *xhat = nullptr, *hd = nullptr, *dl = nullptr, *dy = nullptr, *dh = nullptr, *loss = nullptr, *out2 = nullptr;
     int32_t* correct = nullptr;
     int32_t* bad_target = nullptr;       // set by k_t_head when a target is outside 0..classes-1; sticky until read
@@ -1378,25 +1452,15 @@ struct Trainer {
     float* x_stage = nullptr;            // host-pointer entry point: inputs, targets and injected masks staged here
     int32_t* y_stage = nullptr;
     uint8_t* keep_stage = nullptr;
-    size_t part_floats = 0;
     float* part1 = nullptr;              // conv1's weight-gradient partials (its kernels run beside the side stream's, which own `part`)
     // the training step forks: weight packing, the head's / fc1's / the convolutions' weight gradients and the loss sum run on `side`, beside the
     // chain that the next kernel waits for (data gradients, BN backward); the step joins again in front of Adam
     hipStream_t side = nullptr;
-    hipEvent_t ev[8] = {};
-    bool masks_on_side = false;          // this step's keep masks are being drawn on `side` (ev[6])
+    hipEvent_t ev[EV_COUNT] = {};
+    bool masks_on_side = false;          // this step's keep masks are being drawn on `side` (EV_MASKS)
     double* red_bias = nullptr;          // [3][BWD_BLOCKS][128]: k_t_bn_bwd's column sums, finalized on `side`
-    bool attr = false;
     Mem mem;                             // every device buffer above
 };
-
-static constexpr int RED_BLOCKS = 256, BWD_BLOCKS = 1024;   // grids of the reduction kernels (partials: red[BWD_BLOCKS][2][128])
-using WG3 = WgradGeom<64, 128, 20, 32, 64, 5, 10>;   // conv3: block type = kernel row x 32-channel half x 64-channel half (20 types), unit = 10 rows of a crop
-using WG2 = WgradGeom<16, 64, 40, 16, 64, 3, 5>;     // conv2: block type = kernel row (5 types), unit = 5 rows of a crop
-using WH3 = WgradHGeom<64, 128, 20, 32, 10>;        // precision 0: conv3 4 block types x 64 shares, conv2 1 x 256
-using WH2 = WgradHGeom<16, 64, 40, 16, 10>;
-static constexpr int SHARES3H = 64, SHARES2H = 256;
-static constexpr int SHARES3 = 12, SHARES2 = 51;     // 20 x 12 = 240 and 5 x 51 = 255 workgroups: one round on 256 CUs
 
 // index inside the tensor in the kernels' layout of element `i` of the torch layout
 static size_t to_internal(int t, size_t i, int CH) {
@@ -1404,7 +1468,7 @@ static size_t to_internal(int t, size_t i, int CH) {
         case T_C1W: { const size_t tap = i % 25, c = (i / 25) % CH, co = i / (25 * (size_t)CH); return (c * 25 + tap) * 16 + co; }
         case T_C2W: { const size_t tap = i % 25, ci = (i / 25) % 16, co = i / 400; return (tap * 16 + ci) * 64 + co; }
         case T_C3W: { const size_t tap = i % 25, ci = (i / 25) % 64, co = i / 1600; return (((ci / 32) * 25 + tap) * 32 + ci % 32) * 128 + co; }
-        case T_F1W: { const size_t k = i % 12800, o = i / 12800, c = k / 100, hw = k % 100; return (hw * 128 + c) * 100 + o; }
+        case T_F1W: { const size_t k = i % FC1_K, o = i / FC1_K, c = k / FC1_POS, hw = k % FC1_POS; return (hw * 128 + c) * HID + o; }
         default: return i;
     }
 }
@@ -1414,66 +1478,93 @@ static void trainer_free(Trainer* t) {
     if (t->side) (void)hipStreamSynchronize(t->side);                     // (a step joins its side stream before Adam; this is for a half-queued one)
     t->mem.free_all();
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    if (t->side) { (void)hipStreamSynchronize(t->side); (void)hipStreamDestroy(t->side); }
+    if (t->side) (void)hipStreamDestroy(t->side);
     delete t;
 }
 
-using G2F = ConvGeom<16, 64, 40, 20, 16>;
-using G3F = ConvGeom<64, 128, 20, 10, 32>;     // 10-row bands: 2 blocks per crop (a training batch is 64..128 crops, the chip has 256 CUs; 4-row bands measured no faster)
-using G3B = ConvGeom<128, 64, 20, 10, 32>;
-using G2B = ConvGeom16<64, 40, 20, 16>;
-using H2F = ConvGeomH<16, 64, 40, 20, 16>;       // precision 0 (fp16 two-piece split): conv2 / conv3 forward, conv3 / conv2 data gradient
-using H3F = ConvGeomH<64, 128, 20, 10, 32>;
-using H3B = ConvGeomH<128, 64, 20, 10, 32>;
-using H2B = ConvGeomH<64, 32, 40, 20, 16>;       // 16 output channels in a 32-wide tile          // conv2's data gradient: 16 output channels on 16x16x4 tiles, two blocks per crop
-
-template <int CH>
-static void launch_layer1(Trainer* t, hipStream_t s, const float* x, int n, bool train) {
-    hipLaunchKernelGGL((k_t_conv1<CH>), dim3(n * 20), dim3(320), 0, s, x, t->P + t->off[T_C1W], t->P + t->off[T_C1B], t->z1, train ? t->red : nullptr);
-}
-template <int CH>
-static void launch_wgrad1(Trainer* t, hipStream_t s, const float* x, int n) {
-    hipLaunchKernelGGL((k_t_wgrad1<CH>), dim3(n * 10), dim3(512), 0, s, x, t->z1, t->part1);
-    const int count = CH * 400;
-    hipLaunchKernelGGL(k_t_reduce, dim3((count + 15) / 16), dim3(256), 0, s, t->part1, n * 10, count, t->G + t->off[T_C1W]);
+// every kernel instance of the table that needs more dynamic LDS than the default limit
+static int trainer_attrs(Trainer* t) {
+    for (const Layer& L : t->L) {
+        for (const ConvKernel* k : {&L.fwd, &L.dgrad})
+            if (k->fn()) TH_CHECK_HIP(hipFuncSetAttribute(k->fn(), hipFuncAttributeMaxDynamicSharedMemorySize, k->lds));
+        if (L.wgrad.fn) TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(L.wgrad.fn), hipFuncAttributeMaxDynamicSharedMemorySize, L.wgrad.lds));
+    }
+    return TREXHIP_OK;
 }
 
-template <int C>
-static void bn_forward(Trainer* t, hipStream_t s, int layer, const float* z, float* a, int n, int S, int tg, int tb, int trm, int trv, const uint8_t* keep,
-                       float scale, int have_partials /*workgroups of the convolution that left their column sums in t->red; 0 = none did*/) {
-    float* mean = t->stat + layer * 512;
+// z -> a.  train: batch statistics (from the `partials` column sums the convolution's workgroups left in t->red, or from a pass of its own
+// over z when there are none) + dropout masks; eval: running statistics (the caller's masks keep everything)
+static void bn_forward(Trainer* t, hipStream_t s, const Layer& L, int n, const uint8_t* keep, float scale, bool train, int partials) {
+    float* P = t->P;
+    const size_t* o = t->off;
+    float* mean = t->stat + L.slot * 512;
     float* invstd = mean + 128;
-    const size_t rows = (size_t)n * S * S;
-    if (!have_partials) hipLaunchKernelGGL((k_t_bn_stats<C>), dim3(RED_BLOCKS), dim3(256), 0, s, z, rows, t->red);
-    hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_STATS>), dim3(C), dim3(256), 0, s, t->red, have_partials ? have_partials : RED_BLOCKS, C,
-                       FinArgs{(double)rows, t->p.bn_momentum, mean, invstd, t->P + t->off[trm], t->P + t->off[trv], t->bad_target});
-    const size_t total = (size_t)n * (S / 2) * (S / 2) * (C / 4);
-    hipLaunchKernelGGL((k_t_bn_pool<C>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, z, mean, invstd, t->P + t->off[tg], t->P + t->off[tb], keep, scale,
-                       a, n, S);
+    if (train) {
+        const size_t rows = (size_t)n * L.S * L.S;
+        if (!partials) hipLaunchKernelGGL(L.bn_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.z, rows, t->red);
+        hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_STATS>), dim3(L.C), dim3(256), 0, s, t->red, partials ? partials : RED_BLOCKS, L.C,
+                           FinArgs{(double)rows, t->p.bn_momentum, mean, invstd, P + o[L.rm], P + o[L.rv], t->bad_target});
+    } else {
+        hipLaunchKernelGGL(k_t_bn_from_running, dim3(1), dim3(128), 0, s, P + o[L.rm], P + o[L.rv], L.C, mean, invstd);
+    }
+    const size_t total = (size_t)n * (L.S / 2) * (L.S / 2) * (L.C / 4);
+    hipLaunchKernelGGL(L.bn_pool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L.z, mean, invstd, P + o[L.g], P + o[L.be], keep + (size_t)n * L.keep_off,
+                       scale, L.a, n, L.S);
 }
 
-// da (pooled gradient) -> dz written over z; gradients of gamma, beta and of the convolution bias
-template <int C>
-static int bn_backward(Trainer* t, hipStream_t s, int layer, const float* da, float* z, int n, int S, int tg, int tb, int tcb, const uint8_t* keep, float scale) {
-    float* mean = t->stat + layer * 512;
+// da (pooled gradient) -> dz written over z; gradients of gamma and beta.  Returns the grid of k_t_bn_bwd, whose column sums bias_finalize adds
+static int bn_backward(Trainer* t, hipStream_t s, const Layer& L, int n, const uint8_t* keep, float scale) {
+    float* P = t->P;
+    const size_t* o = t->off;
+    float* mean = t->stat + L.slot * 512;
     float* invstd = mean + 128;
     float* sums = mean + 256;
-    hipLaunchKernelGGL((k_t_pool_bwd_stats<C>), dim3(RED_BLOCKS), dim3(256), 0, s, da, z, mean, invstd, t->P + t->off[tg], t->P + t->off[tb], keep, scale, n, S,
-                       t->red);
-    hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_BWD>), dim3(C), dim3(256), 0, s, t->red, RED_BLOCKS, C,
-                       FinArgs{0.0, 0.f, sums, t->G + t->off[tg], t->G + t->off[tb], nullptr, nullptr});
-    const size_t total = (size_t)n * (S / 2) * (S / 2) * (C / 4);
-    const float inv_count = (float)(1.0 / ((double)n * S * S));
+    const uint8_t* kp = keep + (size_t)n * L.keep_off;
+    hipLaunchKernelGGL(L.pool_bwd_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.S, t->red);
+    hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_BWD>), dim3(L.C), dim3(256), 0, s, t->red, RED_BLOCKS, L.C,
+                       FinArgs{0.0, 0.f, sums, t->G + o[L.g], t->G + o[L.be], nullptr, nullptr});
+    const size_t total = (size_t)n * (L.S / 2) * (L.S / 2) * (L.C / 4);
+    const float inv_count = (float)(1.0 / ((double)n * L.S * L.S));
     // whole rounds: every workgroup takes the same number of elements, all of them resident at once
     const unsigned nb0 = (unsigned)((total + 255) / 256), per = (nb0 + BWD_BLOCKS - 1) / BWD_BLOCKS, nb = (nb0 + per - 1) / per;
-    hipLaunchKernelGGL((k_t_bn_bwd<C>), dim3(nb), dim3(256), 0, s, da, z, mean, invstd, t->P + t->off[tg], t->P + t->off[tb], keep, scale, sums, inv_count, n, S,
-                       t->red_bias + (size_t)layer * BWD_BLOCKS * 128);
+    hipLaunchKernelGGL(L.bn_bwd, dim3(nb), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, sums, inv_count, n, L.S,
+                       t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128);
     return (int)nb;
 }
 // the convolution bias's gradient from k_t_bn_bwd's column sums (nothing but Adam waits for it: the caller puts it on the side stream)
-static void bias_finalize(Trainer* t, hipStream_t w, int layer, int nb, int C, int tcb) {
-    hipLaunchKernelGGL((k_t_red_finalize<FIN_BIAS>), dim3(C), dim3(256), 0, w, t->red_bias + (size_t)layer * BWD_BLOCKS * 128, nb, C,
-                       FinArgs{0.0, 0.f, t->G + t->off[tcb], nullptr, nullptr, nullptr, nullptr});
+static void bias_finalize(Trainer* t, hipStream_t w, const Layer& L, int nb) {
+    hipLaunchKernelGGL((k_t_red_finalize<FIN_BIAS>), dim3(L.C), dim3(256), 0, w, t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128, nb, L.C,
+                       FinArgs{0.0, 0.f, t->G + t->off[L.b], nullptr, nullptr, nullptr, nullptr});
+}
+
+// The streams of a step: main = the context's, w = the side stream (main itself when the step does not fork), es = main as events name it.
+// Events go through the null stream when the caller's stream is the hipStreamLegacy handle (this runtime faults in a wait on an event
+// recorded on the handle itself; in this library the two name the same stream); the per-thread handle has no such stand-in: the step then
+// stays on the one stream
+struct Streams { hipStream_t s, w, es; bool forked; };
+static void fork(Trainer* t, const Streams& q, int e) {
+    if (q.forked) { (void)hipEventRecord(t->ev[e], q.es); (void)hipStreamWaitEvent(q.w, t->ev[e], 0); }
+}
+
+// One block backwards: dz on the main stream; behind it the side stream takes the bias gradient and the weight gradient with its reduce
+// (nothing but Adam waits for them) while the main stream goes on with the data gradient, which the block below waits for.  Block 1 ends
+// behind the bias: it has no data gradient, and the caller runs its weight gradient
+static void block_backward(Trainer* t, const Streams& q, const Layer& L, int n, const uint8_t* keep, float scale) {
+    const int nb = bn_backward(t, q.s, L, n, keep, scale);
+    fork(t, q, L.dz_event);
+    bias_finalize(t, q.w, L, nb);
+    if (!L.wgrad.fn) return;
+    const Layer& below = t->L[L.slot - 1];
+    const WgradKernel& g = L.wgrad;
+    const int shares = std::min(n * g.units, g.max_shares);
+    hipLaunchKernelGGL(g.fn, dim3(g.types, shares), dim3(g.threads), g.lds, q.w, below.a, L.z, t->part, n);
+    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w]);
+    // the data gradient: the same convolution on flipped + transposed weights
+    const ConvKernel& k = L.dgrad;
+    if (!k.h2) hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * k.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, k.co, k.cic, L.wb);
+    if (k.h2) hipLaunchKernelGGL(k.h2, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wh_b, nullptr, below.da, L.wh_scale, nullptr);
+    else if (k.f32_n16) hipLaunchKernelGGL(k.f32_n16, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wb, below.da);
+    else hipLaunchKernelGGL(k.f32, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wb, nullptr, below.da);
 }
 
 // steps with a target outside 0..classes-1 were refused on the device (k_t_check_targets) and have changed nothing: report them at the next
@@ -1497,61 +1588,45 @@ static int check_targets(Trainer* t) {
 // probs (eval only): the head writes the softmax rows there and nothing else (k_t_head_eval)
 static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, float scale, bool train,
                             hipStream_t side = nullptr, float* probs = nullptr) {
-    const uint8_t *k1 = keep, *k2 = keep + (size_t)n * 16, *k3 = keep + (size_t)n * 80, *k4 = keep + (size_t)n * 208;
     float* P = t->P;
     const size_t* o = t->off;
+    const Layer* L = t->L;
     const bool h2 = t->p.precision == 0;
+    hipStream_t es = s == hipStreamLegacy ? nullptr : s;
     if (h2) {
         // this step's weights as fp16 two-piece operand images (both directions); conv2 is the first to need them
-        hipStream_t ps = side ? side : s;
-        hipLaunchKernelGGL(k_t_pack_h2, dim3(10), dim3(1024), 0, ps, P + o[T_C2W], 16, 64, 16, 16, 16, 32, t->wh2f, t->wh2b, t->wh_scale);
-        hipLaunchKernelGGL(k_t_pack_h2, dim3(50), dim3(1024), 0, ps, P + o[T_C3W], 64, 128, 32, 32, 32, 64, t->wh3f, t->wh3b, t->wh_scale + 1);
-        if (side) (void)hipEventRecord(t->ev[1], side);
+        for (int i = 1; i < 3; ++i)
+            hipLaunchKernelGGL(k_t_pack_h2, dim3(L[i].pack_blocks), dim3(1024), 0, side ? side : s, P + o[L[i].w], L[i].CI, L[i].C, L[i].fwd.cic, L[i].fwd.cic,
+                               L[i].dgrad.cic, L[i].dgrad.co, L[i].wh_f, L[i].wh_b, L[i].wh_scale);
+        if (side) (void)hipEventRecord(t->ev[EV_PACKED], side);
     }
-    auto block = [&](auto tag, int layer, const float* z, float* a, int S, int tg, int tb, int trm, int trv, const uint8_t* kp, int have_partials) {
-        constexpr int C = decltype(tag)::value;
-        if (train) { bn_forward<C>(t, s, layer, z, a, n, S, tg, tb, trm, trv, kp, scale, have_partials); return; }
-        float* mean = t->stat + layer * 512;
-        float* invstd = mean + 128;
-        hipLaunchKernelGGL(k_t_bn_from_running, dim3(1), dim3(128), 0, s, P + o[trm], P + o[trv], C, mean, invstd);
-        const size_t total = (size_t)n * (S / 2) * (S / 2) * (C / 4);
-        hipLaunchKernelGGL((k_t_bn_pool<C>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, z, mean, invstd, P + o[tg], P + o[tb], kp, scale, a, n, S);
-    };
-    if (t->CH == 1) launch_layer1<1>(t, s, x, n, train); else launch_layer1<3>(t, s, x, n, train);
-    if (side && t->masks_on_side) (void)hipStreamWaitEvent(s == hipStreamLegacy ? nullptr : s, t->ev[6], 0);
-    block(std::integral_constant<int, 16>{}, 0, t->z1, t->a1, 80, T_G1, T_BE1, T_RM1, T_RV1, k1, n * 20);
-    if (h2 && side) (void)hipStreamWaitEvent(s == hipStreamLegacy ? nullptr : s, t->ev[1], 0);
-    if (h2) hipLaunchKernelGGL((k_t_conv5_h2<16, 64, 40, 20, 16, 64>), dim3(n * H2F::BPC), dim3(512), H2F::LDS_BYTES, s, t->a1, t->wh2f, P + o[T_C2B], t->z2, t->wh_scale, train ? t->red : nullptr);
-    else hipLaunchKernelGGL((k_conv5<16, 64, 40, 20, 16, CONV_EPI_RAW, 64>), dim3(n * G2F::BPC), dim3(512), G2F::LDS_BYTES, s, t->a1, P + o[T_C2W], P + o[T_C2B], t->z2);
-    block(std::integral_constant<int, 64>{}, 1, t->z2, t->a2, 40, T_G2, T_BE2, T_RM2, T_RV2, k2, h2 ? n * H2F::BPC : 0);
-    if (h2) hipLaunchKernelGGL((k_t_conv5_h2<64, 128, 20, 10, 32, 128>), dim3(n * H3F::BPC), dim3(512), H3F::LDS_BYTES, s, t->a2, t->wh3f, P + o[T_C3B], t->z3, t->wh_scale + 1, train ? t->red : nullptr);
-    else hipLaunchKernelGGL((k_conv5<64, 128, 20, 10, 32, CONV_EPI_RAW, 128>), dim3(n * G3F::BPC), dim3(512), G3F::LDS_BYTES, s, t->a2, P + o[T_C3W], P + o[T_C3B], t->z3);
-    block(std::integral_constant<int, 128>{}, 2, t->z3, t->a3, 20, T_G3, T_BE3, T_RM3, T_RV3, k3, h2 ? n * H3F::BPC : 0);
-    hipLaunchKernelGGL(k_t_fc1, dim3(100, (n + 63) / 64), dim3(256), 0, s, t->a3, P + o[T_F1W], t->hpart, n);
+    hipLaunchKernelGGL(t->conv1, dim3(n * C1_BPC), dim3(320), 0, s, x, P + o[T_C1W], P + o[T_C1B], L[0].z, train ? t->red : nullptr);
+    if (side && t->masks_on_side) (void)hipStreamWaitEvent(es, t->ev[EV_MASKS], 0);
+    bn_forward(t, s, L[0], n, keep, scale, train, n * C1_BPC);
+    if (h2 && side) (void)hipStreamWaitEvent(es, t->ev[EV_PACKED], 0);
+    for (int i = 1; i < 3; ++i) {
+        const ConvKernel& k = L[i].fwd;                              // the fp16 kernel leaves its BN column sums, the fp32 one does not
+        if (k.h2) hipLaunchKernelGGL(k.h2, dim3(n * k.bpc), dim3(512), k.lds, s, L[i - 1].a, L[i].wh_f, P + o[L[i].b], L[i].z, L[i].wh_scale, train ? t->red : nullptr);
+        else hipLaunchKernelGGL(k.f32, dim3(n * k.bpc), dim3(512), k.lds, s, L[i - 1].a, P + o[L[i].w], P + o[L[i].b], L[i].z);
+        bn_forward(t, s, L[i], n, keep, scale, train, k.h2 ? n * k.bpc : 0);
+    }
+    hipLaunchKernelGGL(k_t_fc1, dim3(FC1_POS, (n + 63) / 64), dim3(256), 0, s, L[2].a, P + o[T_F1W], t->hpart, n);
     if (probs) {
         hipLaunchKernelGGL(k_t_head_eval, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], P + o[T_F2W], P + o[T_F2B], t->classes, probs);
         return;
     }
-    hipLaunchKernelGGL(k_t_head, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], k4, scale, P + o[T_F2W], P + o[T_F2B], targets,
-                       t->classes, t->xhat, t->hd, t->dl, t->dy, t->dh, t->loss, t->correct, t->bad_target);
+    hipLaunchKernelGGL(k_t_head, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], keep + (size_t)n * KEEP_OFF[3], scale, P + o[T_F2W],
+                       P + o[T_F2B], targets, t->classes, t->xhat, t->hd, t->dl, t->dy, t->dh, t->loss, t->correct, t->bad_target);
 }
 
-static int trainer_attrs(Trainer* t) {
-    if (t->attr) return TREXHIP_OK;
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5<16, 64, 40, 20, 16, CONV_EPI_RAW, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, G2F::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5<64, 128, 20, 10, 32, CONV_EPI_RAW, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, G3F::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5<128, 64, 20, 10, 32, CONV_EPI_RAW, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, G3B::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv5_n16<64, 40, 20, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, G2B::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_conv5_h2<16, 64, 40, 20, 16, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, H2F::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_conv5_h2<64, 128, 20, 10, 32, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, H3F::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_conv5_h2<128, 64, 20, 10, 32, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, H3B::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_conv5_h2<64, 32, 40, 20, 16, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, H2B::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_wgrad<64, 128, 20, 32, 64, 5, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, WG3::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_wgrad<16, 64, 40, 16, 64, 3, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, WG2::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_wgrad_h2<64, 128, 20, 32, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, WH3::LDS_BYTES));
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_t_wgrad_h2<16, 64, 40, 16, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, WH2::LDS_BYTES));
-    t->attr = true;
-    return TREXHIP_OK;
+// the loss and the correct count of the batch just queued, to the host (synchronises), and what the device refused
+static int fetch_loss(Trainer* t, hipStream_t s, float* h_loss, int32_t* h_correct) {
+    float two[2];
+    TH_CHECK_HIP(hipMemcpyAsync(two, t->out2, sizeof(two), hipMemcpyDeviceToHost, s));
+    TH_CHECK_HIP(hipStreamSynchronize(s));
+    if (h_loss) *h_loss = two[0];
+    if (h_correct) *h_correct = (int32_t)two[1];
+    return check_targets(t);
 }
 
 // model.eval() forward + mean cross entropy + arg-max count of one validation batch (train(), :1171-1190); changes nothing in the trainer
@@ -1559,18 +1634,12 @@ static int trainer_eval(Trainer* t, const float* x, const int32_t* targets, int 
     trexhip_ctx* ctx = t->ctx;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     hipStream_t s = ctx->stream;
-    { const int rc = trainer_attrs(t); if (rc) return rc; }
-    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)n * 308, s));                 // nothing dropped
+    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)n * KEEP_ROW, s));                 // nothing dropped
     hipLaunchKernelGGL(k_t_check_targets, dim3(1), dim3(256), 0, s, targets, n, t->classes, t->bad_target, 1);
     trainer_forward(t, s, x, targets, n, t->keep, 1.0f, false);
     hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, s, t->loss, t->correct, n, t->out2);
     TH_CHECK_HIP(hipGetLastError());
-    float two[2];
-    TH_CHECK_HIP(hipMemcpyAsync(two, t->out2, sizeof(two), hipMemcpyDeviceToHost, s));
-    TH_CHECK_HIP(hipStreamSynchronize(s));
-    if (h_loss) *h_loss = two[0];
-    if (h_correct) *h_correct = (int32_t)two[1];
-    return check_targets(t);
+    return fetch_loss(t, s, h_loss, h_correct);
 }
 
 // softmax rows of any number of uint8 crops from the weights as they stand (predict_numpy in model.eval(), visual_recognition_torch.py:406-451):
@@ -1580,11 +1649,10 @@ static int trainer_predict(Trainer* t, const uint8_t* d_crops, int n, float* d_p
     trexhip_ctx* ctx = t->ctx;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     hipStream_t s = ctx->stream;
-    { const int rc = trainer_attrs(t); if (rc) return rc; }
-    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)std::min(n, t->max_n) * 308, s));       // nothing dropped
+    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)std::min(n, t->max_n) * KEEP_ROW, s));       // nothing dropped
     for (int at = 0; at < n; at += t->max_n) {
         const int m = std::min(t->max_n, n - at);
-        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * 6400 * t->CH, nullptr, m, nullptr, m, 80, 80, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
+        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * IMG_PIX * t->CH, nullptr, m, nullptr, m, IMG, IMG, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
         if (rc != TREXHIP_OK) return rc;
         trainer_forward(t, s, t->x_stage, nullptr, m, t->keep, 1.0f, false, nullptr, d_probs + (size_t)at * t->classes);
     }
@@ -1596,99 +1664,53 @@ static int trainer_step(Trainer* t, const float* x, const int32_t* targets, int 
     trexhip_ctx* ctx = t->ctx;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     hipStream_t s = ctx->stream;
-    { const int rc = trainer_attrs(t); if (rc) return rc; }
     const float scale = 1.0f / (1.0f - t->p.dropout);
     const uint8_t* keep = d_keep;
     float* P = t->P;
     float* G = t->G;
     const size_t* o = t->off;
-    // the weight-gradient side of the step.  Events go through the null stream when the caller's stream is the hipStreamLegacy handle (this
-    // runtime faults in a wait on an event recorded on the handle itself; in this library the two name the same stream); the per-thread
-    // handle has no such stand-in: the step then stays on the one stream
     const bool forked = s != hipStreamPerThread;
-    hipStream_t w = forked ? t->side : s;
-    hipStream_t es = s == hipStreamLegacy ? nullptr : s;
-    auto fork = [&](int e) { if (forked) { (void)hipEventRecord(t->ev[e], es); (void)hipStreamWaitEvent(w, t->ev[e], 0); } };
-    fork(0);                                                                // behind whatever wrote the parameters last
+    const Streams q{s, forked ? t->side : s, s == hipStreamLegacy ? nullptr : s, forked};
+    hipStream_t w = q.w;
+    fork(t, q, EV_PARAMS);
     t->masks_on_side = forked && !keep;
     if (!keep) {
-        const size_t count = (size_t)n * 308;
+        const size_t count = (size_t)n * KEEP_ROW;
         hipLaunchKernelGGL(k_t_masks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, w, t->keep, count, t->p.seed, (uint64_t)t->step, t->p.dropout);
-        if (forked) (void)hipEventRecord(t->ev[6], w);
+        if (forked) (void)hipEventRecord(t->ev[EV_MASKS], w);
         keep = t->keep;
     }
     hipLaunchKernelGGL(k_t_check_targets, dim3(1), dim3(256), 0, s, targets, n, t->classes, t->bad_target, 0);
     trainer_forward(t, s, x, targets, n, keep, scale, true, forked ? w : nullptr);
-    fork(2);
-    const uint8_t *k1 = keep, *k2 = keep + (size_t)n * 16, *k3 = keep + (size_t)n * 80;
+    fork(t, q, EV_FORWARD);
     // ---- backward
     {
-        const int cnt = t->classes * 100 + t->classes + 300;
+        const int cnt = t->classes * HID + t->classes + 3 * HID;
         hipLaunchKernelGGL(k_t_head_grads, dim3((cnt + 255) / 256), dim3(256), 0, w, t->dl, t->hd, t->dy, t->xhat, t->dh, n, t->classes, G + o[T_F2W], G + o[T_F2B],
                            G + o[T_LNG], G + o[T_LNB], G + o[T_F1B]);
     }
-    hipLaunchKernelGGL(k_t_fc1_wgrad, dim3(100), dim3(256), 0, w, t->a3, t->dh, G + o[T_F1W], n);
+    hipLaunchKernelGGL(k_t_fc1_wgrad, dim3(FC1_POS), dim3(256), 0, w, t->L[2].a, t->dh, G + o[T_F1W], n);
     hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, w, t->loss, t->correct, n, t->out2);
-    hipLaunchKernelGGL(k_t_fc1_dgrad, dim3(100, (n + 31) / 32), dim3(256), 0, s, t->dh, P + o[T_F1W], t->da3, n);
-    // block 3
-    const bool h2 = t->p.precision == 0;
-    const int nb3 = bn_backward<128>(t, s, 2, t->da3, t->z3, n, 20, T_G3, T_BE3, T_C3B, k3, scale);
-    fork(3);
-    bias_finalize(t, w, 2, nb3, 128, T_C3B);
-    {
-        const int shares = h2 ? (n * WH3::NB < SHARES3H ? n * WH3::NB : SHARES3H) : (n * WG3::NB < SHARES3 ? n * WG3::NB : SHARES3);
-        if (h2) hipLaunchKernelGGL((k_t_wgrad_h2<64, 128, 20, 32, 10>), dim3(WH3::TYPES, shares), dim3(640), WH3::LDS_BYTES, w, t->a2, t->z3, t->part, n);
-        else hipLaunchKernelGGL((k_t_wgrad<64, 128, 20, 32, 64, 5, 10>), dim3(WG3::TYPES, shares), dim3(512), WG3::LDS_BYTES, w, t->a2, t->z3, t->part, n);
-        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * 64 * 128 + 255) / 256), dim3(256), 0, w, t->part, shares, 64, 128, 32, G + o[T_C3W]);
-        if (h2) hipLaunchKernelGGL((k_t_conv5_h2<128, 64, 20, 10, 32, 64>), dim3(n * H3B::BPC), dim3(512), H3B::LDS_BYTES, s, t->z3, t->wh3b, (const float*)nullptr, t->da2, t->wh_scale + 1, (double*)nullptr);
-        else {
-            hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * 128 * 64 + 255) / 256), dim3(256), 0, s, P + o[T_C3W], 64, 128, 32, 64, 32, t->wb3);
-            hipLaunchKernelGGL((k_conv5<128, 64, 20, 10, 32, CONV_EPI_RAW, 64>), dim3(n * G3B::BPC), dim3(512), G3B::LDS_BYTES, s, t->z3, t->wb3, (const float*)nullptr, t->da2);
-        }
-    }
-    // block 2
-    const int nb2 = bn_backward<64>(t, s, 1, t->da2, t->z2, n, 40, T_G2, T_BE2, T_C2B, k2, scale);
-    fork(4);
-    bias_finalize(t, w, 1, nb2, 64, T_C2B);
-    {
-        const int shares = h2 ? (n * WH2::NB < SHARES2H ? n * WH2::NB : SHARES2H) : (n * WG2::NB < SHARES2 ? n * WG2::NB : SHARES2);
-        if (h2) hipLaunchKernelGGL((k_t_wgrad_h2<16, 64, 40, 16, 10>), dim3(WH2::TYPES, shares), dim3(640), WH2::LDS_BYTES, w, t->a1, t->z2, t->part, n);
-        else hipLaunchKernelGGL((k_t_wgrad<16, 64, 40, 16, 64, 3, 5>), dim3(WG2::TYPES, shares), dim3(512), WG2::LDS_BYTES, w, t->a1, t->z2, t->part, n);
-        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * 16 * 64 + 255) / 256), dim3(256), 0, w, t->part, shares, 16, 64, 16, G + o[T_C2W]);
-        if (h2) hipLaunchKernelGGL((k_t_conv5_h2<64, 32, 40, 20, 16, 16>), dim3(n * H2B::BPC), dim3(512), H2B::LDS_BYTES, s, t->z2, t->wh2b, (const float*)nullptr, t->da1, t->wh_scale, (double*)nullptr);
-        else {
-            hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * 64 * 16 + 255) / 256), dim3(256), 0, s, P + o[T_C2W], 16, 64, 16, 16, 16, t->wb2);
-            hipLaunchKernelGGL((k_conv5_n16<64, 40, 20, 16>), dim3(n * G2B::BPC), dim3(512), G2B::LDS_BYTES, s, t->z2, t->wb2, t->da1);
-        }
-    }
-    // block 1
-    const int nb1 = bn_backward<16>(t, s, 0, t->da1, t->z1, n, 80, T_G1, T_BE1, T_C1B, k1, scale);
-    fork(7);
-    bias_finalize(t, w, 0, nb1, 16, T_C1B);
-    if (forked) (void)hipEventRecord(t->ev[5], w);                          // the side stream's last piece of this step
-    if (t->CH == 1) launch_wgrad1<1>(t, s, x, n); else launch_wgrad1<3>(t, s, x, n);
-    if (forked) (void)hipStreamWaitEvent(es, t->ev[5], 0);                  // join: every gradient is in G
+    hipLaunchKernelGGL(k_t_fc1_dgrad, dim3(FC1_POS, (n + 31) / 32), dim3(256), 0, s, t->dh, P + o[T_F1W], t->L[2].da, n);
+    for (int i = 2; i >= 0; --i) block_backward(t, q, t->L[i], n, keep, scale);
+    if (forked) (void)hipEventRecord(t->ev[EV_SIDE_DONE], w);               // the side stream's last piece of this step
+    hipLaunchKernelGGL(t->wgrad1, dim3(n * WG1_BPC), dim3(512), 0, s, x, t->L[0].z, t->part1);
+    hipLaunchKernelGGL(k_t_reduce, dim3((t->CH * 400 + 15) / 16), dim3(256), 0, s, t->part1, n * WG1_BPC, t->CH * 400, G + o[T_C1W]);
+    if (forked) (void)hipStreamWaitEvent(q.es, t->ev[EV_SIDE_DONE], 0);     // join: every gradient is in G
     // ---- optimizer
     t->step += 1;
     {
         const double b1 = t->p.beta1, b2 = t->p.beta2;
         const double bc1 = 1.0 - std::pow(b1, (double)t->step), bc2 = 1.0 - std::pow(b2, (double)t->step);
         AdamSkip skip;
-        const int bufs[6] = {T_RM1, T_RV1, T_RM2, T_RV2, T_RM3, T_RV3};
-        for (int k = 0; k < 6; ++k) { skip.lo[k] = (uint32_t)o[bufs[k]]; skip.hi[k] = (uint32_t)(o[bufs[k]] + t->cnt[bufs[k]]); }
+        int k = 0;
+        for (const Layer& L : t->L)
+            for (int buf : {L.rm, L.rv}) { skip.lo[k] = (uint32_t)o[buf]; skip.hi[k] = (uint32_t)(o[buf] + t->cnt[buf]); ++k; }
         hipLaunchKernelGGL(k_t_adam, dim3((unsigned)((t->total + 255) / 256)), dim3(256), 0, s, P, G, t->M, t->V, (uint32_t)t->total, skip, (float)(1.0 - b1), (float)b2,
                            (float)(1.0 - b2), (float)((double)t->p.lr / bc1), (float)std::sqrt(bc2), t->p.eps, t->bad_target);
     }
     TH_CHECK_HIP(hipGetLastError());
-    if (h_loss || h_correct) {
-        float two[2];
-        TH_CHECK_HIP(hipMemcpyAsync(two, t->out2, sizeof(two), hipMemcpyDeviceToHost, s));
-        TH_CHECK_HIP(hipStreamSynchronize(s));
-        if (h_loss) *h_loss = two[0];
-        if (h_correct) *h_correct = (int32_t)two[1];
-        return check_targets(t);
-    }
-    return TREXHIP_OK;
+    return h_loss || h_correct ? fetch_loss(t, s, h_loss, h_correct) : TREXHIP_OK;
 }
 
 }  // namespace trexhip
@@ -1700,7 +1722,7 @@ extern "C" {
 using namespace trexhip;
 
 size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) {
-    return weight_blob_bytes(classes, channels, 80, 80);
+    return weight_blob_bytes(classes, channels, IMG, IMG);
 }
 
 int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, trexhip_trainer** out) {
@@ -1708,7 +1730,7 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     *out = nullptr;
     WeightBlob wb;
     const int prc = parse_weight_blob(blob, bytes, "trexhip_trainer_create", &wb, [](int W, int H) -> int {
-        if (W != 80 || H != 80) { set_error("trexhip_trainer_create: only individual_image_size 80x80 is supported"); return TREXHIP_E_UNSUPPORTED; }
+        if (W != IMG || H != IMG) { set_error("trexhip_trainer_create: only individual_image_size 80x80 is supported"); return TREXHIP_E_UNSUPPORTED; }
         return TREXHIP_OK;
     });
     if (prc != TREXHIP_OK) return prc;
@@ -1725,36 +1747,66 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     t->ctx = ctx; t->classes = classes; t->CH = CH; t->max_n = p->max_batch; t->p = *p;
     size_t at = 0;
     for (int k = 0; k < T_COUNT; ++k) {
-        t->off[k] = at; t->cnt[k] = weight_tensor_count(k, classes, CH, 80, 80);
+        t->off[k] = at; t->cnt[k] = weight_tensor_count(k, classes, CH, IMG, IMG);
         at += (t->cnt[k] + 63) / 64 * 64;
     }
     t->off[T_COUNT] = at; t->total = at;
+    // ---- the three blocks and their kernel instances.  The convolutions' precision is chosen here, once per role
+    const bool h2 = p->precision == 0;
+    Layer* L = t->L;
+    // (k_t_bn_stats<16> is never launched: conv1 always leaves its column sums.  It stays instantiated because the compiler lays out the epilogue
+    // of k_t_pool_bwd_stats<16>, which shares block_columns<16, 2> with it, in another order without it)
+    //      C    CI  S        weight bias   gamma beta   running mean / variance  dz event  slot  masks    BN kernels
+    L[0] = {16,  CH, IMG,     T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, KEEP_OFF[0], &k_t_bn_stats<16>, &k_t_bn_pool<16>, &k_t_pool_bwd_stats<16>, &k_t_bn_bwd<16>};
+    L[1] = {64,  16, IMG / 2, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, EV_DZ2, 1, KEEP_OFF[1], &k_t_bn_stats<64>, &k_t_bn_pool<64>, &k_t_pool_bwd_stats<64>, &k_t_bn_bwd<64>};
+    L[2] = {128, 64, IMG / 4, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3, EV_DZ3, 2, KEEP_OFF[2], &k_t_bn_stats<128>, &k_t_bn_pool<128>, &k_t_pool_bwd_stats<128>, &k_t_bn_bwd<128>};
+    t->conv1 = CH == 1 ? &k_t_conv1<1> : &k_t_conv1<3>;
+    t->wgrad1 = CH == 1 ? &k_t_wgrad1<1> : &k_t_wgrad1<3>;
+    // conv3 forward in 10-row bands: 2 blocks per crop (a training batch is 64..128 crops, the chip has 256 CUs; 4-row bands measured no faster).
+    // conv2's data gradient has 16 output channels: 16x16x4 tiles in fp32, 16 of a 32-wide tile's channels real in fp16
+    L[1].fwd = h2 ? conv_h2<16, 64, 40, 20, 16, 64>() : conv_f32<16, 64, 40, 20, 16, 64>();
+    L[2].fwd = h2 ? conv_h2<64, 128, 20, 10, 32, 128>() : conv_f32<64, 128, 20, 10, 32, 128>();
+    L[1].dgrad = h2 ? conv_h2<64, 32, 40, 20, 16, 16>() : conv_f32_n16<64, 40, 20, 16>();
+    L[2].dgrad = h2 ? conv_h2<128, 64, 20, 10, 32, 64>() : conv_f32<128, 64, 20, 10, 32, 64>();
+    // weight gradients.  fp32: conv2 block type = kernel row (5 types), unit = 5 rows of a crop; conv3 block type = kernel row x 32-channel half x
+    // 64-channel half (20 types), unit = 10 rows; 5 x 51 = 255 and 20 x 12 = 240 workgroups: one round on 256 CUs.  fp16: conv2 1 type x 256 shares,
+    // conv3 4 x 64
+    L[1].wgrad = h2 ? wgrad_h2<16, 64, 40, 16, 10>(256) : wgrad_f32<16, 64, 40, 16, 64, 3, 5>(51);
+    L[2].wgrad = h2 ? wgrad_h2<64, 128, 20, 32, 10>(64) : wgrad_f32<64, 128, 20, 32, 64, 5, 10>(12);
+    L[1].pack_blocks = 10; L[2].pack_blocks = 50;
+    // ---- memory
     const size_t n = (size_t)t->max_n;
     int rc = TREXHIP_OK;
     const char* who = "trexhip_trainer_create";
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
     TRY(t->mem.device(&t->P, at, who)); TRY(t->mem.device(&t->G, at, who)); TRY(t->mem.device(&t->M, at, who)); TRY(t->mem.device(&t->V, at, who));
-    TRY(t->mem.device(&t->z1, n * 6400 * 16, who)); TRY(t->mem.device(&t->a1, n * 1600 * 16, who)); TRY(t->mem.device(&t->z2, n * 1600 * 64, who));
-    TRY(t->mem.device(&t->a2, n * 400 * 64, who)); TRY(t->mem.device(&t->z3, n * 400 * 128, who)); TRY(t->mem.device(&t->a3, n * 100 * 128, who));
-    TRY(t->mem.device(&t->da3, n * 100 * 128, who)); TRY(t->mem.device(&t->da2, n * 400 * 64, who)); TRY(t->mem.device(&t->da1, n * 1600 * 16, who));
-    TRY(t->mem.device(&t->wb3, (size_t)4 * 25 * 32 * 64, who)); TRY(t->mem.device(&t->wb2, (size_t)2 * 25 * 32 * 32, who));
-    TRY(t->mem.device(&t->wh2f, (size_t)2 * 2 * 25 * 64, who)); TRY(t->mem.device(&t->wh2b, (size_t)2 * 8 * 25 * 32, who));
-    TRY(t->mem.device(&t->wh3f, (size_t)2 * 8 * 25 * 128, who)); TRY(t->mem.device(&t->wh3b, (size_t)2 * 16 * 25 * 64, who));
-    TRY(t->mem.device(&t->wh_scale, 2, who));
-    t->part_floats = std::max(std::max(std::max((size_t)SHARES3 * 25 * 64 * 128, (size_t)SHARES2 * 25 * 16 * 64), std::max((size_t)SHARES3H * 25 * 64 * 128, (size_t)SHARES2H * 25 * 16 * 64)),
-                              n * 10 * CH * 400);
-    TRY(t->mem.device(&t->part, t->part_floats, who)); TRY(t->mem.device(&t->part1, n * 10 * CH * 400, who)); TRY(t->mem.device(&t->red_bias, (size_t)3 * BWD_BLOCKS * 128, who));
+    size_t part_floats = 0;
+    for (int i = 0; i < 3; ++i) {
+        const size_t act = n * L[i].S * L[i].S * L[i].C;                      // z; pooled: a quarter of it
+        TRY(t->mem.device(&L[i].z, act, who)); TRY(t->mem.device(&L[i].a, act / 4, who)); TRY(t->mem.device(&L[i].da, act / 4, who));
+        part_floats = std::max(part_floats, (size_t)L[i].wgrad.max_shares * 25 * L[i].CI * L[i].C);
+    }
+    if (h2) {                                                                 // the weight images of the trainer's own precision
+        TRY(t->mem.device(&L[1].wh_f, (size_t)2 * 2 * 25 * 64, who)); TRY(t->mem.device(&L[1].wh_b, (size_t)2 * 8 * 25 * 32, who));
+        TRY(t->mem.device(&L[2].wh_f, (size_t)2 * 8 * 25 * 128, who)); TRY(t->mem.device(&L[2].wh_b, (size_t)2 * 16 * 25 * 64, who));
+        TRY(t->mem.device(&L[1].wh_scale, 2, who));
+        L[2].wh_scale = L[1].wh_scale + 1;
+    } else {
+        TRY(t->mem.device(&L[2].wb, (size_t)4 * 25 * 32 * 64, who)); TRY(t->mem.device(&L[1].wb, (size_t)2 * 25 * 32 * 32, who));
+    }
+    TRY(t->mem.device(&t->part, part_floats, who)); TRY(t->mem.device(&t->part1, n * WG1_BPC * CH * 400, who)); TRY(t->mem.device(&t->red_bias, (size_t)3 * BWD_BLOCKS * 128, who));
     TRY(t->mem.device(&t->stat, (size_t)3 * 512, who));
-    TRY(t->mem.device(&t->hpart, n * 100 * 100, who)); TRY(t->mem.device(&t->xhat, n * 100, who)); TRY(t->mem.device(&t->hd, n * 100, who));
-    TRY(t->mem.device(&t->dl, n * classes, who)); TRY(t->mem.device(&t->dy, n * 100, who)); TRY(t->mem.device(&t->dh, n * 100, who));
+    TRY(t->mem.device(&t->hpart, n * FC1_POS * HID, who)); TRY(t->mem.device(&t->xhat, n * HID, who)); TRY(t->mem.device(&t->hd, n * HID, who));
+    TRY(t->mem.device(&t->dl, n * classes, who)); TRY(t->mem.device(&t->dy, n * HID, who)); TRY(t->mem.device(&t->dh, n * HID, who));
     TRY(t->mem.device(&t->loss, n, who)); TRY(t->mem.device(&t->correct, n, who)); TRY(t->mem.device(&t->out2, 2, who)); TRY(t->mem.device(&t->bad_target, 2, who));
     TRY(t->mem.device(&t->red, std::max((size_t)BWD_BLOCKS * 2 * 128, n * 640), who));   // conv1 leaves 20 n x 2 x 16 partials, conv2 / conv3 2 n x 2 x C
-    TRY(t->mem.device(&t->keep, n * 308, who));
-    TRY(t->mem.device(&t->x_stage, n * 6400 * CH, who)); TRY(t->mem.device(&t->y_stage, n, who)); TRY(t->mem.device(&t->keep_stage, n * 308, who));
-#undef TRY
+    TRY(t->mem.device(&t->keep, n * KEEP_ROW, who));
+    TRY(t->mem.device(&t->x_stage, n * IMG_PIX * CH, who)); TRY(t->mem.device(&t->y_stage, n, who)); TRY(t->mem.device(&t->keep_stage, n * KEEP_ROW, who));
     if (rc == TREXHIP_OK && hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess) { set_error("trexhip_trainer_create: no second stream"); rc = TREXHIP_E_DEVICE; }
     for (hipEvent_t& e : t->ev)
         if (rc == TREXHIP_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("trexhip_trainer_create: no event"); rc = TREXHIP_E_DEVICE; }
+    TRY(trainer_attrs(t));
+#undef TRY
     if (rc != TREXHIP_OK) { trainer_free(t); return rc; }
     std::vector<float> host(at, 0.f);
     for (int k = 0; k < T_COUNT; ++k)
@@ -1782,53 +1834,55 @@ int trexhip_trainer_set_lr(trexhip_trainer* h, float lr) {
 
 int64_t trexhip_trainer_steps(trexhip_trainer* h) { return h ? h->t->step : -1; }
 
+// what every batch entry point checks first: the handle, its two pointers, 1 <= n <= max_batch (any_n: no upper bound, the call chunks)
+static int check_batch(const char* who, const trexhip_trainer* h, const void* a, const void* b, int n, bool any_n = false) {
+    if (!h || !a || !b) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
+    if (n < 1 || (!any_n && n > h->t->max_n)) { set_error(std::string(who) + (any_n ? ": n must be at least 1" : ": n must be 1..max_batch")); return TREXHIP_E_INVALID; }
+    return TREXHIP_OK;
+}
+
+// the host-pointer entry points: the same checks, the targets' range before anything is uploaded (visual_recognition_torch.py:1112), then the
+// batch into the staging buffers on the context's stream
+static int stage_batch(const char* who, const trexhip_trainer* h, const float* inputs, const int32_t* targets, int n, const uint8_t* keep_masks) {
+    if (const int rc = check_batch(who, h, inputs, targets, n)) return rc;
+    Trainer* t = h->t;
+    for (int i = 0; i < n; ++i)
+        if (targets[i] < 0 || targets[i] >= t->classes) { set_error(std::string(who) + ": target class out of range"); return TREXHIP_E_INVALID; }
+    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
+    hipStream_t s = t->ctx->stream;
+    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * IMG_PIX * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
+    TH_CHECK_HIP(hipMemcpyAsync(t->y_stage, targets, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (keep_masks) TH_CHECK_HIP(hipMemcpyAsync(t->keep_stage, keep_masks, (size_t)n * KEEP_ROW, hipMemcpyHostToDevice, s));
+    return TREXHIP_OK;
+}
+
 int trexhip_train_step_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks, float* loss,
                               int32_t* correct) {
-    if (!h || !d_inputs || !d_targets) { set_error("trexhip_train_step_device: null argument"); return TREXHIP_E_INVALID; }
-    if (n < 1 || n > h->t->max_n) { set_error("trexhip_train_step_device: n must be 1..max_batch"); return TREXHIP_E_INVALID; }
+    if (const int rc = check_batch("trexhip_train_step_device", h, d_inputs, d_targets, n)) return rc;
     return trainer_step(h->t, d_inputs, d_targets, n, d_keep_masks, loss, correct);
 }
 
 int trexhip_train_step(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, const uint8_t* keep_masks, float* loss, int32_t* correct) {
-    if (!h || !inputs || !targets) { set_error("trexhip_train_step: null argument"); return TREXHIP_E_INVALID; }
+    if (const int rc = stage_batch("trexhip_train_step", h, inputs, targets, n, keep_masks)) return rc;
     Trainer* t = h->t;
-    if (n < 1 || n > t->max_n) { set_error("trexhip_train_step: n must be 1..max_batch"); return TREXHIP_E_INVALID; }
-    for (int i = 0; i < n; ++i)
-        if (targets[i] < 0 || targets[i] >= t->classes) { set_error("trexhip_train_step: target class out of range"); return TREXHIP_E_INVALID; }   // visual_recognition_torch.py:1112
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    hipStream_t s = t->ctx->stream;
-    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * 6400 * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
-    TH_CHECK_HIP(hipMemcpyAsync(t->y_stage, targets, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (keep_masks) TH_CHECK_HIP(hipMemcpyAsync(t->keep_stage, keep_masks, (size_t)n * 308, hipMemcpyHostToDevice, s));
-    const int rc = trainer_step(t, t->x_stage, t->y_stage, n, keep_masks ? t->keep_stage : nullptr, loss, correct);
-    if (rc != TREXHIP_OK) return rc;
-    TH_CHECK_HIP(hipStreamSynchronize(s));        // the caller's buffers may go away
+    if (const int rc = trainer_step(t, t->x_stage, t->y_stage, n, keep_masks ? t->keep_stage : nullptr, loss, correct)) return rc;
+    TH_CHECK_HIP(hipStreamSynchronize(t->ctx->stream));        // the caller's buffers may go away
     return TREXHIP_OK;
 }
 
 int trexhip_train_eval_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, float* loss, int32_t* correct) {
-    if (!h || !d_inputs || !d_targets) { set_error("trexhip_train_eval_device: null argument"); return TREXHIP_E_INVALID; }
-    if (n < 1 || n > h->t->max_n) { set_error("trexhip_train_eval_device: n must be 1..max_batch"); return TREXHIP_E_INVALID; }
+    if (const int rc = check_batch("trexhip_train_eval_device", h, d_inputs, d_targets, n)) return rc;
     return trainer_eval(h->t, d_inputs, d_targets, n, loss, correct);
 }
 
 int trexhip_train_predict_device(trexhip_trainer* h, const uint8_t* d_crops, int32_t n, float* d_probs) {
-    if (!h || !d_crops || !d_probs) { set_error("trexhip_train_predict_device: null argument"); return TREXHIP_E_INVALID; }
-    if (n < 1) { set_error("trexhip_train_predict_device: n must be at least 1"); return TREXHIP_E_INVALID; }
+    if (const int rc = check_batch("trexhip_train_predict_device", h, d_crops, d_probs, n, true)) return rc;
     return trainer_predict(h->t, d_crops, n, d_probs);
 }
 
 int trexhip_train_eval(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, float* loss, int32_t* correct) {
-    if (!h || !inputs || !targets) { set_error("trexhip_train_eval: null argument"); return TREXHIP_E_INVALID; }
-    Trainer* t = h->t;
-    if (n < 1 || n > t->max_n) { set_error("trexhip_train_eval: n must be 1..max_batch"); return TREXHIP_E_INVALID; }
-    for (int i = 0; i < n; ++i)
-        if (targets[i] < 0 || targets[i] >= t->classes) { set_error("trexhip_train_eval: target class out of range"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    hipStream_t s = t->ctx->stream;
-    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * 6400 * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
-    TH_CHECK_HIP(hipMemcpyAsync(t->y_stage, targets, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    return trainer_eval(t, t->x_stage, t->y_stage, n, loss, correct);
+    if (const int rc = stage_batch("trexhip_train_eval", h, inputs, targets, n, nullptr)) return rc;
+    return trainer_eval(h->t, h->t->x_stage, h->t->y_stage, n, loss, correct);
 }
 
 int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float* out, size_t count) {
@@ -1851,7 +1905,7 @@ int trexhip_trainer_export(trexhip_trainer* h, void* blob, size_t capacity, size
     const size_t need = trexhip_weight_blob_bytes(t->classes, t->CH);
     if (bytes) *bytes = need;
     if (capacity < need) { set_error("trexhip_trainer_export: buffer too small (trexhip_weight_blob_bytes)"); return TREXHIP_E_CAPACITY; }
-    write_weight_blob_header(blob, t->classes, 80, 80, t->CH);
+    write_weight_blob_header(blob, t->classes, IMG, IMG, t->CH);
     float* dst = reinterpret_cast<float*>(static_cast<char*>(blob) + 32);
     for (int k = 0; k < T_COUNT; ++k) {
         const int rc = trexhip_trainer_read(h, k, 0, dst, t->cnt[k]);
