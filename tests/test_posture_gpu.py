@@ -79,7 +79,8 @@ def test_synthetic_individuals():
 
 @pytest.mark.parametrize("kw", [dict(outline_resample=0.5), dict(outline_resample=2.0, outline_smooth_samples=0),
                                  dict(outline_approximate=0), dict(outline_approximate=1, midline_walk_offset=0.1),
-                                 dict(outline_resample=0.5, midline_walk_offset=0.45), dict(midline_walk_offset=0.07), dict(outline_resample=0.5, midline_walk_offset=0.06)])
+                                 dict(outline_resample=0.5, midline_walk_offset=0.45), dict(midline_walk_offset=0.07), dict(outline_resample=0.5, midline_walk_offset=0.06),
+                                 dict(outline_resample=0.7), dict(outline_resample=1.3, outline_smooth_samples=0)])     # 2 * distance not whole: the sequential resample
 def test_setting_variants_and_odd_shapes(kw):
     rng = np.random.default_rng(3)
     H, W = 160, 320
@@ -99,6 +100,18 @@ def test_setting_variants_and_odd_shapes(kw):
     # order-1 EFT turns every outline into an exact ellipse whose two tips have EQUAL curvature: the tail is a coin flip
     # decided by float rounding there, so only the closed curve is compared for that variant
     compare(res, outline, segs, info, oracle.posture_params(max_points=512, **kw))     # (the tie rate is printed: discs and order-1 ellipses are mostly ties)
+    # the paths of k_posture this scene is here for are really taken (one frame: info row k is blob k)
+    width = res[0].blobs["x1"].astype(int) - res[0].blobs["x0"].astype(int) + 1
+    assert np.any((width > 64) & (info["n_traced"] > 0))                           # the 100-pixel bar: no one-word-per-row bitmap, the sequential tracer
+    ok = info["status"] == 0
+    cand = np.maximum(3, (np.float32(kw.get("midline_walk_offset", 0.025)) * info["n_outline"][ok].astype(np.float32)).astype(int))   # candidates per search of the walk
+    if kw.get("midline_walk_offset") == 0.45:
+        assert np.any(cand > 64)                                                     # more candidates than lanes: the multi-pass walk
+    print("candidates per search:", sorted(cand.tolist()))
+    if kw.get("midline_walk_offset") == 0.06:
+        assert np.any((cand >= 17) & (cand <= 64))                                   # beyond the lane groups of k_posture_walk: the 64-lane walk inside k_posture
+    if kw.get("midline_walk_offset") == 0.07:
+        assert np.any((cand >= 9) & (cand <= 16))                                    # at resample 1.0 no outline of the scene is long enough for 17: k_posture_walk<16>
 
 
 @pytest.mark.parametrize("walk_offset", [0.02, 0.04, 0.045, 0.08, 0.085, 0.16, 0.165, 0.2])
