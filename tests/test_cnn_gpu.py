@@ -106,6 +106,57 @@ def test_fp16_range_overflow_falls_back_on_the_device():
     seg.close()
 
 
+def _out_of_range_state(channels):
+    """the weights of test_fp16_range_overflow_falls_back_on_the_device: every crop's conv1 output leaves the fp16 range, the oracle's rows stay finite"""
+    st = {k: v.copy() for k, v in weights.synthetic_state(8, 31, channels=channels).items()}
+    st["conv1.weight"] *= 4000.0
+    st["bn1.running_var"] = np.full(16, 1.0, np.float32); st["bn1.running_mean"] = np.zeros(16, np.float32)
+    st["bn2.running_var"] = np.full(64, 1e10, np.float32)
+    return st
+
+
+def test_three_channel_rerun_starts_at_conv1_on_the_plan():
+    """3 channels, FP16X3: the two-kernel chain leaves no fp32 activations, so the guarded re-run starts at the crops (k_conv1_mfma3 on the plan);
+    the 3-channel conv1 cannot name the crop that left the range, so the plan orders the whole batch"""
+    st = _out_of_range_state(3)
+    crops = weights.synthetic_crops(5, 77, channels=3)
+    ref, _ = cnn_oracle.predict(st, crops, threads=4)
+    assert np.all(np.isfinite(ref))
+    seg = capi.Segmenter(capi.default_params(64, 64, max_batch=1))
+    seg.load_weights(weights.pack_blob(st, 8, channels=3))
+    seg.set_identity_precision(capi.CNN_FP16X3)
+    got = seg.probabilities(crops)
+    assert np.all(np.isfinite(got)) and np.abs(got - ref).max() <= 1e-4
+    assert seg.guard_stats() == (0, True)
+    seg.close()
+
+
+def test_unaligned_rerun_starts_at_conv2():
+    """1 channel, FP16X3, crops at an odd device address: the fp32-activation chain, whose guarded re-run keeps conv1's exact act1 and starts at conv2"""
+    st = _out_of_range_state(1)
+    crops = weights.synthetic_crops(5, 77)
+    ref, _ = cnn_oracle.predict(st, crops, threads=4)
+    assert np.all(np.isfinite(ref))
+    seg = make_net(st, 8)
+    raw = torch.zeros(5 * 6400 + 64, dtype=torch.uint8, device="cuda")
+    off = (16 - raw.data_ptr() % 16) % 16
+    pa = torch.empty((5, 8), dtype=torch.float32, device="cuda"); pb = torch.empty_like(pa)
+    raw[off:off + 5 * 6400] = torch.from_numpy(crops.reshape(-1)).cuda()
+    seg.set_identity_precision(capi.CNN_FP32)
+    seg.identify_device(raw.data_ptr() + off, 5, pa.data_ptr())
+    seg.synchronize()
+    raw[off + 3:off + 3 + 5 * 6400] = torch.from_numpy(crops.reshape(-1)).cuda()
+    seg.set_identity_precision(capi.CNN_FP16X3)
+    seg.identify_device(raw.data_ptr() + off + 3, 5, pb.data_ptr())
+    seg.synchronize()
+    rerun, whole = seg.guard_stats()
+    got = pb.cpu().numpy()
+    assert np.all(np.isfinite(got)) and np.abs(got - ref).max() <= 1e-4
+    assert whole or rerun == 5                  # every crop's conv1 peak is far outside the range
+    assert np.abs(got - pa.cpu().numpy()).max() <= 1e-5
+    seg.close()
+
+
 def test_unaligned_crop_buffer_and_both_conv1_kernels_agree():
     # the matrix-core conv1 needs 16-byte aligned crops; an odd device pointer must take the VALU kernel and give the same answer
     z, st = load_fixture(100)

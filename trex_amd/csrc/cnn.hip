@@ -18,7 +18,7 @@
 //               registers of one lane; BN folded into weights/bias; epilogue bias+ReLU+pool
 //   k_fc1       [crops x 12800] x [12800 x 128] MFMA GEMM, LDS tiles
 //   k_head      LayerNorm + ReLU + fc2 + softmax, four crops per wave
-#include "internal.h"
+#include "cnn_net.h"
 #include "cnn_split.h"
 #include "cnn_weights.h"
 #include <algorithm>
@@ -118,7 +118,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // The re-run kernels take the plan as their guard: item i of a launch is crop plan[2 + i] in list mode.  One out-of-range crop in 25600
 // used to cost a second pass over the whole batch (4x the step); now it costs the launches of the re-run chain and its own crop.
 // ------------------------------------------------------------------------------------------------
-static constexpr int FB_MAX = 1024;           // more flagged crops than this: every crop is re-run
 __device__ __forceinline__ int fb_count(const uint32_t* __restrict__ plan, const int n) { return (plan && plan[1] == 1u) ? (int)plan[0] : n; }
 // (called by every thread of ONE workgroup of NT threads; `cnt` is that workgroup's shared counter.)  The last reader of the range flag and of the
 // persistent convolutions' pass counters hands all three back zeroed for the next forward pass: no memset in front of a pass (round 6)
@@ -309,24 +308,6 @@ __global__ __launch_bounds__(256) void k_conv1_mfma3(const uint8_t* __restrict__
 // the same convolution on the bf16 matrix cores with fp32-equivalent accuracy (the operand splits: cnn_split.h).  Activations are split while the
 // patch is staged (three patches [pixel][16 ci] bf16, 48-byte pixel stride); weights are pre-split on the host (cnn_weights.h: pack_bf16x3).
 // ------------------------------------------------------------------------------------------------
-template <int CI, int CO, int S, int ROWS, int NP, int CICP = 16>
-struct ConvGeomB {
-    static constexpr int CIC = CICP;                                  // input channels per staged chunk (16 or 32)
-    static constexpr int PW = S + 4, PH = ROWS + 4;
-    static constexpr int PSTRIDE = CIC * 2 + 16;                      // bytes per pixel (data + 16 pad: odd multiple of 16)
-    static constexpr int PATCH = PH * PW * PSTRIDE;                   // bytes per piece
-    static constexpr int BT = NP * (CIC / 8) * CO * 16;               // bytes per weight tile (NP pieces x CIC/8 k-octets)
-    static constexpr int NPIX = ROWS * S;
-    static constexpr int MT = (NPIX + 31) / 32;
-    static constexpr int NT = CO / 32;
-    static constexpr int WM = 8 / NT;
-    static constexpr int TPW = (MT + WM - 1) / WM;
-    static constexpr int LDS_BYTES = NP * PATCH + 2 * BT;
-    static constexpr int BPC = S / ROWS;
-};
-
-// the bf16 split: three pieces per operand; NTERMS 6 (a3b1 a2b2 a1b3 a2b1 a1b2 a1b1) or 3 (the last three)
-static constexpr int SPLIT_NP = 3;
 template <int CI, int CO, int S, int ROWS, int NTERMS, int CIC = 16>
 __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ in /*[N][S][S][CI]*/,
                                                      const uint4* __restrict__ wp /*[CI/16][25][NP][2][CO] x 16 B*/,
@@ -456,30 +437,6 @@ __global__ __launch_bounds__(512) void k_conv5_split(const float* __restrict__ i
 //   * patch rows are padded so that the row pitch is 8 (mod 16) in 16-byte slots: the 16 lanes of one ds_read_b128 lane
 //     group (MI355X guide, LDS table) then hit 16 distinct slots.
 // ------------------------------------------------------------------------------------------------
-template <int CI, int CO, int S, int ROWS, int WAVES>
-struct ConvGeomS {
-    static constexpr int CIC = 16;
-    static constexpr int PW = S + 4, PH = ROWS + 4;
-    static constexpr int PSTRIDE = 48;                                  // 16 fp16 + 16 B pad per pixel
-    static constexpr int RP0 = PW * PSTRIDE;
-    static constexpr int PADU = ((8 - (RP0 / 16) % 16) + 16) % 16;
-    static constexpr int RP = RP0 + PADU * 16;                          // row pitch, bytes
-    static constexpr int PATCH = PH * RP;                               // bytes per piece
-    static constexpr int NCH = CI / CIC;
-    static constexpr int NBUF = NCH > 1 ? 2 : 1;
-    static constexpr int LDS_BYTES = NBUF * 2 * PATCH;
-    static constexpr int NTHR = WAVES * 64;
-    static constexpr int NPIX = ROWS * S;
-    static constexpr int MT = (NPIX + 31) / 32;
-    static constexpr int NT = CO / 32;
-    static constexpr int WM = WAVES / NT;
-    static constexpr int TPW = (MT + WM - 1) / WM;
-    static constexpr int BPC = S / ROWS;
-    static constexpr int BV = 2 * 2 * CO;                               // uint4 per tap tile: pieces x k-octets x co
-    static constexpr int NQ = PH * PW * 4;                              // float4 per staged chunk
-    static constexpr int NITEMS = (NQ + NTHR - 1) / NTHR;
-};
-
 template <int CI, int CO, int S, int ROWS, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void k_conv5_stream(const float* __restrict__ in /*[N][S][S][CI]*/,
                                                              const uint4* __restrict__ wp /*[CI/16][25][2][2][CO] x 16 B*/,
@@ -652,31 +609,6 @@ __device__ __forceinline__ void wino_at(const float m0, const float m1, const fl
 // LDS: [buffer][piece][row slot][position][tx][16 ci] fp16, slot 0 = zeros; double-buffered over the 16-channel chunks
 // (the next chunk / next pass is transformed and stored in slices between the taps of the current one).
 // ------------------------------------------------------------------------------------------------
-template <int CI, int CO, int S, int TPW>
-struct WinoGeom {
-    static constexpr int CIC = 16, NCH = CI / CIC;
-    static constexpr int TPR = S / 4, TPP = 2 * TPR, TPC = S * TPR;     // tiles per row / row pair / crop
-    static constexpr int NT = CO / 32, WM = NT >= 4 ? 1 : 4 / NT, WAVES = NT * WM, NTHR = WAVES * 64;
-    static constexpr int MB = WM * TPW * 32;                            // tiles per pass
-    static constexpr int MAXPAIRS = (MB + TPP - 2) / TPP + 1;
-    static constexpr int NR = 2 * MAXPAIRS + 4;                         // real input rows a pass can need
-    static constexpr int PS = TPR * 32;                                 // bytes per position of a row: tiles x 16 halves
-    static constexpr int RP0 = 8 * PS;
-    // row pitch: == 5 (mod 8) 16-byte slots when a row pair holds 10 tiles, so that the 16 lanes of a ds_read_b128 lane group
-    // (tiles i, i+1 = rows y, y+1 of one column, then the next column) fall into 16 different slots
-    static constexpr int RP = RP0 + (((5 - (RP0 / 16) % 8) + 8) % 8) * 16;
-    static constexpr int PLANE = (NR + 1) * RP;                         // one piece; slot 0 = the zero row
-    static constexpr int BUF = 2 * PLANE;
-    static constexpr int LDS_BYTES = 2 * BUF;
-    static constexpr int BV = 2 * 2 * CO;                               // uint4 per (ky, position): pieces x k-octets x co
-    static constexpr int IPR = TPR * 8;                                 // staging items per row: tile x channel pair
-    static constexpr int NQ = NR * IPR;
-    static constexpr int NITEMS = (NQ + NTHR - 1) / NTHR;
-    static_assert(S % 4 == 0 && CO % 32 == 0 && CI % 16 == 0, "geometry");
-    static_assert(NITEMS * 8 <= 40, "staging slices do not fit between the 40 taps");
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-};
-
 // rows qmin .. qmin+nrows-1 (batch row numbering q = crop*S + y) that the tiles [T0, T0+MB) of a pass read
 template <class G, int S>
 __device__ __forceinline__ void wino_pass_rows(const int pass, const int total_tiles, int& qmin, int& nrows) {
@@ -996,7 +928,6 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
 #include "cnn_fused12.h"
 #include "cnn_fused12rs.h"
 
-static constexpr int FC1_KSPLIT = 10;     // 12800 = 10 x 1280: 500 workgroups at 6400 crops (5: 129 us, 10: 92 us, 20: 102 us + slower head); partial planes summed in k_head
 // ------------------------------------------------------------------------------------------------
 // fc1: out[N][128] = act[N][K] * W[K][128] + b     (K = 12800, 100 real outputs)
 // ------------------------------------------------------------------------------------------------
@@ -1181,7 +1112,6 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // HEAD_CPW crops per wave: the fc2 weight of (input k, class c) is loaded once and serves the wave's crops (four independent sums per lane
 // instead of one chain of 100 dependent loads + multiply-adds); per crop the operations and their order are those of one wave per crop
-static constexpr int HEAD_CPW = 4;
 __global__ __launch_bounds__(256) void k_head(const float* __restrict__ fc1 /*[N][128]*/, const float* __restrict__ ln_g,
                                               const float* __restrict__ ln_b, const float* __restrict__ w2t /*[100][C]*/,
                                               const float* __restrict__ b2, float* __restrict__ probs /*[N][C]*/,
@@ -1360,39 +1290,6 @@ __global__ __launch_bounds__(256) void k_head_small(const float* __restrict__ fc
 // ------------------------------------------------------------------------------------------------
 // host: weight blob -> folded / repacked device tensors
 // ------------------------------------------------------------------------------------------------
-struct Net {
-    int classes = 0, W = 0, H = 0, CH = 0, max_crops = 0;
-    uint4 *w2s = nullptr, *w3s = nullptr;      // bf16-split conv weights
-    uint4 *w2h = nullptr, *w3h = nullptr;      // fp16-split conv weights (scaled by a power of two)
-    float inv2h = 1.f, inv3h = 1.f;
-    uint4 *w2w = nullptr, *w3w = nullptr;      // Winograd F(4,5)-domain conv weights, fp16 pieces (k_conv5_wino)
-    float inv2w = 1.f, inv3w = 1.f;
-    uint4* wf1h = nullptr;                     // fc1 weights, fp16 pieces in MFMA B layout [K/8][2][128] x 8 halves
-    float invf1h = 1.f;
-    uint4* w1h = nullptr;                      // conv1 B fragments (16 fragments x 64 lanes), fp16 pieces of the folded weights
-    float inv1h = 1.f;
-    uint32_t* d_ovf = nullptr;                 // [0] fp16 range flag, [1] / [2] pass counters of the persistent conv3 / conv2, [4 ..] the re-run plan (k_guard_plan)
-    uint8_t* d_ovfc = nullptr;                 // per-crop range flags [max_crops]
-    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
-    float *wf1 = nullptr, *bf1 = nullptr, *lng = nullptr, *lnb = nullptr, *wf2t = nullptr, *bf2 = nullptr;
-    float *act1 = nullptr, *act2 = nullptr, *act3 = nullptr, *fc1 = nullptr, *probs = nullptr, *logits = nullptr;
-    uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
-    uint8_t* crops = nullptr;
-    float* h_probs = nullptr;                  // pinned
-    Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
-    // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one
-    // identify call is captured into a hipGraph per (buffers, n, precision) and replayed
-    // A chain is only captured once the same (buffers, n, precision) key has come THREE times: in tracking the blob count changes from
-    // batch to batch, and capture + instantiate costs far more than the ~100 us of launch overhead a replay saves.
-    struct GraphEntry { const uint8_t* crops; int n; float* probs; float* logits; int mode, geom; hipStream_t stream; hipGraphExec_t exec; uint64_t used;
-                        hipEvent_t last; int seen; };          // exec == nullptr: a candidate key that is still being counted
-    std::vector<GraphEntry> graphs;
-    bool graphs_ok = true;
-    uint64_t tick = 0;
-    bool ovf_clean = true;                     // d_ovf[0..2] are zero, or will be when the queued work has run (see net_forward)
-    int last_mode = -1;                        // precision mode of the last forward pass (trexhip_identify_guard_stats reads the plan only behind an fp16x3 pass)
-};
-
 // an exec may still be running on its stream (launches are asynchronous): wait for the event recorded behind its last launch first
 static void destroy_graph_entry(Net::GraphEntry& g) {
     if (g.exec) {
@@ -1460,8 +1357,8 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     TRY(upload(net, &net->w3s, pack_bf16x3(c3.w, 64, 128)));
     TRY(upload(net, &net->w3h, &net->inv3h, pack_f16x2(c3.w, 64, 128)));
     if (at80) TRY(upload(net, &net->w3w, &net->inv3w, pack_wino_f16(c3.w, 64, 128)));
-    TRY(net->weights.device_bytes(&net->d_ovf, 16 + (2 + FB_MAX) * 4, "trexhip_load_weights"));
-    if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, 16 + (2 + FB_MAX) * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
+    TRY(net->weights.device_bytes(&net->d_ovf, OVF_WORDS * 4, "trexhip_load_weights"));
+    if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, OVF_WORDS * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
     const Folded c3x = fold_conv(&wb.t[T_C3W], 128, 64, 32);
     TRY(upload(net, &net->w3, c3x.w)); TRY(upload(net, &net->b3, c3x.b));
     const Folded f1 = pack_fc1(wb.t[T_F1W], wb.t[T_F1B], W, H);
@@ -1506,192 +1403,136 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
 }
 #undef TRY
 
-// every individual_image_size but 80 x 80: conv1..conv3 of cnn_any.hip in the precision mode (conv1 exact fp32 in all of them), fc1 exact fp32
-// (k_fc1, K = 128 (H/8) (W/8) at run time), k_head.  In FP16X3 mode the range guard of the 80 x 80 chain: k_guard_plan lists the crops the fp16
-// convolutions flagged, and the BF16X6 convolutions, fc1 and the head re-run only those (the whole batch past FB_MAX)
-static int net_forward_any(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
-    Net* net = static_cast<Net*>(ctx->net);
-    hipStream_t s = ctx->stream;
-    const int mode = ctx->cnn_mode;
-    const AnyConvNet a{net->W, net->H, net->CH, net->w1, net->b1, net->w2, net->b2, net->w3, net->b3, net->w2s, net->w3s, net->w2h, net->w3h,
-                       net->inv2h, net->inv3h, net->act1, net->act2, net->act3, net->d_ovf, net->d_ovfc};
-    // fc1 split-K planes (summed in k_head): the largest count up to FC1_KSPLIT that divides the (H/8)(W/8) positions, so that every plane is
-    // whole positions of 128 channels (a multiple of k_fc1's 32-deep chunks); it depends on the size alone, never on n
-    const int P = (net->H / 8) * (net->W / 8), K = 128 * P;
-    int ks = FC1_KSPLIT;
-    while (P % ks) --ks;
-    stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
-    any_convs(s, ctx->n_cus, mode, a, d_crops, n);
-    hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, ks), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, K, (const uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                       d_probs, d_logits, n, net->classes, (const uint32_t*)nullptr, ks);
-    if (mode == TREXHIP_CNN_FP16X3) {
-        const uint32_t* g = net->d_ovf + 4;
-        hipLaunchKernelGGL(k_guard_plan, dim3(1), dim3(1024), 0, s, net->d_ovf, net->d_ovfc, n, net->d_ovf + 4);
-        any_convs_rerun(s, ctx->n_cus, a, n, g);
-        hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, ks), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, K, g);
-        hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                           d_probs, d_logits, n, net->classes, g, ks);
-    }
-    stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
-    TH_CHECK_HIP(hipGetLastError());
-    return TREXHIP_OK;
-}
+// ------------------------------------------------------------------------------------------------
+// host: one forward pass = make the plan (cnn_plan.h), launch what it says, in order
+// ------------------------------------------------------------------------------------------------
+std::vector<LdsAttr>& lds_attrs() { static std::vector<LdsAttr> v; return v; }
 
-template <class K>
-static hipError_t set_lds(K* kernel, const int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-// k_conv5_split over n crops.  A guarded re-run (guard = the plan of k_guard_plan) goes out on a small grid that strides over its crops
+// every kernel instance of this file's chains, once (the any-size convolutions: cnn_any.hip)
+// (k_conv1's LDS depends on the channels alone at 80 x 80; it never had the attribute and is not listed for it)
+static const ByChannels K_CONV1{Kern(k_conv1<1>, 256, (84 * 84 + 25 * 16) * 4, false), Kern(k_conv1<3>, 256, 3 * (84 * 84 + 25 * 16) * 4, false)};
+static const ByChannels K_CONV1_MFMA{Kern(k_conv1_mfma, 256), Kern(k_conv1_mfma3, 256)};
+static const ByChannels K_CONV1_WPRE{Kern(k_conv1_wpre<1>, 256), Kern(k_conv1_wpre<3>, 256)};
+static const Kern K_CONV12_RS(k_conv12_rs, 512, W12RGeom::LDS_BYTES);
+static const Kern K_CONV12_WPRE(k_conv12_wpre, 256, W12Geom::LDS_BYTES);
+static const Kern K_CONV2_WPRE2(k_conv2_wpre2, 256, W2bGeom::LDS_BYTES);
+static const Kern K_CONV2_STREAM(k_conv5_stream<16, 64, 40, 8, 4>, 256, ConvGeomS<16, 64, 40, 8, 4>::LDS_BYTES);
+using GW3 = WinoGeom<64, 128, 20, 2>;
+static const Kern K_CONV3_WINO(k_conv5_wino<64, 128, 20, 2>, GW3::NTHR, GW3::LDS_BYTES);
+static const Kern K_CONV3_WPAIR(k_conv5_wpair, 256, GW3::LDS_BYTES + 1024 /* slack for the last DMA instruction */);
 template <int CI, int CO, int S, int ROWS, int NTERMS>
-static void launch_split(trexhip_ctx* ctx, const int n, const float* in, const uint4* w, const float* b, float* out, const uint32_t* guard) {
-    using G = ConvGeomB<CI, CO, S, ROWS, SPLIT_NP>;
-    const int blocks = n * G::BPC;
-    hipLaunchKernelGGL((k_conv5_split<CI, CO, S, ROWS, NTERMS>), dim3(guard ? std::min(blocks, 4 * ctx->n_cus) : blocks), dim3(512), G::LDS_BYTES,
-                       ctx->stream, in, w, b, out, 1.0f, guard, blocks);
+static auto split_kern() { return Kern(k_conv5_split<CI, CO, S, ROWS, NTERMS>, 512, ConvGeomB<CI, CO, S, ROWS, SPLIT_NP>::LDS_BYTES); }
+// conv2 / conv3 on fp32 activations in the exact modes; x6_plan is the bf16x6 instance of every chain's guarded re-run
+struct ExactLayer { decltype(Kern(k_conv5<16, 64, 40, 20, 16>, 512)) f32; decltype(split_kern<16, 64, 40, 10, 6>()) x6, x3, x6_plan; };
+static const auto K_CONV2_X6 = split_kern<16, 64, 40, 10, 6>();
+static const ExactLayer K_CONV2{Kern(k_conv5<16, 64, 40, 20, 16>, 512, ConvGeom<16, 64, 40, 20, 16>::LDS_BYTES), K_CONV2_X6, split_kern<16, 64, 40, 10, 3>(), K_CONV2_X6};
+static const ExactLayer K_CONV3{Kern(k_conv5<64, 128, 20, 20, 32>, 512, ConvGeom<64, 128, 20, 20, 32>::LDS_BYTES), split_kern<64, 128, 20, 20, 6>(),
+                                split_kern<64, 128, 20, 20, 3>(), split_kern<64, 128, 20, 4, 6>()};
+static const Kern K_FC1(k_fc1, 256);
+static const Kern K_FC1_SPLIT1(k_fc1_split<1>, 256), K_FC1_SPLIT4(k_fc1_split<4>, 256);
+static const Kern K_HEAD(k_head, 256);
+static const Kern K_HEAD_SMALL(k_head_small, 256);
+static const Kern K_GUARD_PLAN(k_guard_plan, 1024);
+
+struct Pass {            // one forward pass: what every launch below needs
+    const Net& net; const CnnPlan& p; hipStream_t s; int mode;
+    const uint8_t* crops; int n; float *probs, *logits;
+};
+
+// a conv1 of its own, on every crop or (guard = the re-run plan) on the plan's
+static void launch_conv1(const Pass& f, const Conv1 kind, const uint32_t* guard) {
+    const Net& net = f.net;
+    switch (kind) {
+    case Conv1::FUSED: break;
+    case Conv1::WPRE: K_CONV1_WPRE[net.CH](f.s, f.p.conv1_grid, f.crops, net.w1h, net.b1, net.v2, net.inv1h, net.ovf(OVF_RANGE)); break;
+    case Conv1::MFMA: K_CONV1_MFMA[net.CH](f.s, f.p.conv1_grid, f.crops, net.w1h, net.b1, net.act1, net.inv1h, guard); break;
+    case Conv1::VALU: K_CONV1[net.CH](f.s, f.p.conv1_grid, f.crops, net.w1, net.b1, net.act1, net.W); break;
+    case Conv1::ANY: any_conv1(f.s, net, f.p, f.crops); break;
+    }
+}
+
+// conv2 (layer 2) or conv3 on fp32 activations in an exact mode: FP32, BF16X6, BF16X3; with a guard the bf16x6 instance on the re-run plan
+static void launch_exact(const Pass& f, const int layer, const int mode, const uint32_t* guard) {
+    const Net& net = f.net;
+    const bool c2 = layer == 2;
+    const ExactLayer& K = c2 ? K_CONV2 : K_CONV3;
+    const Launch& l = guard ? (c2 ? f.p.r_conv2 : f.p.r_conv3) : (c2 ? f.p.conv2 : f.p.conv3);
+    const float *in = c2 ? net.act1 : net.act2, *b = c2 ? net.b2 : net.b3;
+    float* out = c2 ? net.act2 : net.act3;
+    if (mode == TREXHIP_CNN_FP32) K.f32(f.s, l.grid, in, c2 ? net.w2 : net.w3, b, out);
+    else (guard ? K.x6_plan : mode == TREXHIP_CNN_BF16X6 ? K.x6 : K.x3)(f.s, l.grid, in, c2 ? net.w2s : net.w3s, b, out, 1.0f, guard, l.items);
+}
+
+// fc1 + head: either fc1 variant and either head on the whole batch, or (guard = the re-run plan) k_fc1 and k_head on the plan's crops
+static void launch_tail(const Pass& f, const uint32_t* guard) {
+    const Net& net = f.net;
+    const CnnPlan& p = f.p;
+    if (guard || p.fc1 == Fc1::EXACT)
+        K_FC1(f.s, dim3(guard ? p.r_fc1_grid : p.fc1_grid, p.planes), net.act3, net.wf1, net.bf1, net.fc1, f.n, p.K, guard);
+    else
+        (p.fc1 == Fc1::SPLIT1 ? K_FC1_SPLIT1 : K_FC1_SPLIT4)(f.s, dim3(p.fc1_grid, p.planes), net.act3, net.wf1h, net.bf1, net.fc1, f.n, p.K, net.invf1h,
+                                                            net.ovf(OVF_RANGE), net.d_ovfc);
+    if (guard || p.head == Head::BIG)
+        K_HEAD(f.s, guard ? p.r_head_grid : p.head_grid, net.fc1, net.lng, net.lnb, net.wf2t, net.bf2, f.probs, f.logits, f.n, net.classes, guard, p.planes);
+    else        // its first workgroup also makes the range guard's plan
+        K_HEAD_SMALL(f.s, p.head_grid, net.fc1, net.lng, net.lnb, net.wf2t, net.bf2, f.probs, f.logits, f.n, net.classes, p.planes,
+                     p.head_plans ? net.ovf(OVF_RANGE) : nullptr, net.d_ovfc, p.head_plans ? net.ovf(OVF_PLAN) : nullptr);
+}
+
+// the guarded re-run behind an FP16X3 pass, in bf16x6 on the plan
+static void launch_rerun(const Pass& f) {
+    const uint32_t* g = f.net.ovf(OVF_PLAN);
+    if (!f.p.head_plans) K_GUARD_PLAN(f.s, 1, f.net.ovf(OVF_RANGE), f.net.d_ovfc, f.n, f.net.ovf(OVF_PLAN));
+    if (f.p.rerun_conv1) launch_conv1(f, Conv1::MFMA, g);
+    for (const int layer : {2, 3}) {
+        if (f.p.chain == Chain::ANY_SIZE) any_conv(f.s, f.net, f.p, layer, TREXHIP_CNN_BF16X6, g);
+        else launch_exact(f, layer, TREXHIP_CNN_BF16X6, g);
+    }
+    launch_tail(f, g);
 }
 
 static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
-    Net* net = static_cast<Net*>(ctx->net);
-    hipStream_t s = ctx->stream;
-    using G2 = ConvGeom<16, 64, 40, 20, 16>;
-    using G3 = ConvGeom<64, 128, 20, 20, 32>;
-    using B2 = ConvGeomB<16, 64, 40, 10, SPLIT_NP>;
-    using B3 = ConvGeomB<64, 128, 20, 20, SPLIT_NP>;
-    using GS = ConvGeomS<16, 64, 40, 8, 4>;
-    using GW = WinoGeom<64, 128, 20, 2>;
+    const Net& net = *static_cast<Net*>(ctx->net);
     if (!ctx->attr_cnn) {
-        TH_CHECK_HIP(set_lds(&k_conv5<16, 64, 40, 20, 16>, G2::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5<64, 128, 20, 20, 32>, G3::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_split<16, 64, 40, 10, 6>, B2::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_split<16, 64, 40, 10, 3>, B2::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_split<64, 128, 20, 20, 6>, B3::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_split<64, 128, 20, 20, 3>, B3::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_split<64, 128, 20, 4, 6>, ConvGeomB<64, 128, 20, 4, SPLIT_NP>::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_stream<16, 64, 40, 8, 4>, GS::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_wino<64, 128, 20, 2>, GW::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv12_rs, W12RGeom::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv12_wpre, W12Geom::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv2_wpre2, W2bGeom::LDS_BYTES));
-        TH_CHECK_HIP(set_lds(&k_conv5_wpair, GW::LDS_BYTES + 1024));
-        const int rc_any = any_set_attributes();
-        if (rc_any != TREXHIP_OK) return rc_any;
+        for (const LdsAttr& a : lds_attrs()) TH_CHECK_HIP(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes));
         ctx->attr_cnn = true;
     }
-    if (net->W != 80 || net->H != 80) return net_forward_any(ctx, d_crops, n, d_probs, d_logits);
+    const CnnPlan p = cnn_plan(net.W, net.H, net.CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0, ctx->tune_conv_geom, n, ctx->n_cus);
+    const Pass f{net, p, ctx->stream, ctx->cnn_mode, d_crops, n, d_probs, d_logits};
+    hipStream_t s = f.s;
+    // (the guard words in front of the plan start at zero: the plan's writer -- the last reader of all three -- hands them back zeroed; net_forward
+    // clears them itself behind a pass that was not queued to its end)
     stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
-    const int S = net->W;
-    const size_t lds1 = ((size_t)net->CH * (S + 4) * (S + 4) + (size_t)net->CH * 25 * 16) * 4;
-    const int mode = ctx->cnn_mode;
-    // the matrix-core conv1 kernels read the crops with 16-byte loads: unaligned crop buffers take the VALU kernel (and the fp32-activation chain)
-    const bool aligned = (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0;
-    // default chain (cnn_wpre.h): the Winograd-domain fp16 operand images V2 / V3 are written by the producing layer.  Any of bits 0-11 of
-    // TREXHIP_CONV_GEOM selects the fp32-activation chain of rounds 1-2 instead.
-    const bool pre = mode == TREXHIP_CNN_FP16X3 && aligned && (ctx->tune_conv_geom & 0xfff) == 0;
-    // (d_ovf: [0] fp16 range flag, [1] / [2] pass counters of the persistent conv3 / conv2.  They start at zero: the guard's plan kernel -- the last
-    // reader of all three -- hands them back zeroed; net_forward clears them itself behind a pass that was not queued to its end)
-    // one input channel: conv1 runs INSIDE conv2 (cnn_fused12.h: the V2 image stays in LDS); TREXHIP_CONV_GEOM bit 28 keeps the two kernels
-    const bool fused12 = pre && net->CH == 1 && !(ctx->tune_conv_geom & (1 << 28));
-    if (pre && !fused12) {
-        if (net->CH == 1) hipLaunchKernelGGL((k_conv1_wpre<1>), dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->v2, net->inv1h, net->d_ovf);
-        else              hipLaunchKernelGGL((k_conv1_wpre<3>), dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->v2, net->inv1h, net->d_ovf);
-    }
-    else if (!pre && aligned) {
-        if (net->CH == 1) hipLaunchKernelGGL(k_conv1_mfma, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, (const uint32_t*)nullptr);
-        else              hipLaunchKernelGGL(k_conv1_mfma3, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, (const uint32_t*)nullptr);
-    }
-    else if (!pre) {
-        if (net->CH == 1) hipLaunchKernelGGL((k_conv1<1>), dim3(n), dim3(256), lds1, s, d_crops, net->w1, net->b1, net->act1, S);
-        else              hipLaunchKernelGGL((k_conv1<3>), dim3(n), dim3(256), lds1, s, d_crops, net->w1, net->b1, net->act1, S);
-    }
-    stage_begin(ctx, TREXHIP_STAGE_CONV2);
-    // the role-split form (cnn_fused12rs.h): one workgroup of 8 waves per CU, consumer waves (tap loop, output transform) beside producer waves (V3
-    // transform of the previous pass, V2 rows of the next), the first 15 taps' weight fragments resident in LDS.  Bit-identical to the
-    // two-workgroups-per-CU kernel below and 6 % faster at 25600 crops (3.81 against 4.05 ms on one box); batches that do not give every CU a few
-    // passes keep the older kernel (1000 crops: 0.207 against 0.196 ms).  TREXHIP_CONV_GEOM bit 29 forces the role-split kernel, bit 30 the older one
-    const bool role_split = fused12 && !(ctx->tune_conv_geom & (1 << 30)) && ((ctx->tune_conv_geom & (1 << 29)) || n >= 3200);
-    const int n_pass2 = (n * 20 + W2bGeom::RPP - 1) / W2bGeom::RPP;
-    if (role_split) {
-        const int wgs = ctx->n_cus;
-        const int pk = std::max(1, std::min(32, n_pass2 / (wgs * 4)));
-        const int want = (n_pass2 + pk - 1) / pk;
-        hipLaunchKernelGGL(k_conv12_rs, dim3(std::min(want, wgs)), dim3(512), W12RGeom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h,
-                           net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc);
-    }
-    else if (fused12) {
-        const int wgs = 2 * ctx->n_cus;
-        // passes per ticket: long tickets save the 4 extra rows of a ticket's first pass, short ones keep every workgroup busy when the batch is small
-        const int pk = std::max(1, std::min(16, n_pass2 / (wgs * 4)));
-        // (a tail of short tickets was measured and dropped: the dynamic tickets already finish together, and every ticket's first pass produces 10 rows instead of 6)
-        const int want = (n_pass2 + pk - 1) / pk;
-        hipLaunchKernelGGL(k_conv12_wpre, dim3(std::min(want, wgs)), dim3(256), W12Geom::LDS_BYTES, s, d_crops, net->w1h, net->b1, net->inv1h,
-                           net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2, pk, net->d_ovfc);
-    }
-    else if (pre)       // two workgroups per CU, one M-tile per wave, operand planes fetched by LDS-DMA during the epilogue
-        hipLaunchKernelGGL(k_conv2_wpre2, dim3(std::min(n_pass2, 2 * ctx->n_cus)), dim3(256), W2bGeom::LDS_BYTES, s,
-                           net->v2, net->w2w, net->b2, net->v3, net->inv2w, net->d_ovf, n, net->d_ovf + 2);
-    else if (mode == TREXHIP_CNN_FP32)
-        hipLaunchKernelGGL((k_conv5<16, 64, 40, 20, 16>), dim3(n * G2::BPC), dim3(512), G2::LDS_BYTES, s, net->act1, net->w2, net->b2, net->act2);
-    else if (mode == TREXHIP_CNN_BF16X6) launch_split<16, 64, 40, 10, 6>(ctx, n, net->act1, net->w2s, net->b2, net->act2, nullptr);
-    else if (mode == TREXHIP_CNN_BF16X3) launch_split<16, 64, 40, 10, 3>(ctx, n, net->act1, net->w2s, net->b2, net->act2, nullptr);
-    else                // 8 output rows per workgroup: 320 pixels = exactly 10 M-tiles, 3 workgroups per CU (1.15 ms; 10 rows: 1.31 ms)
-        hipLaunchKernelGGL((k_conv5_stream<16, 64, 40, 8, 4>), dim3(n * GS::BPC), dim3(256), GS::LDS_BYTES, s,
-                           net->act1, net->w2h, net->b2, net->act2, net->inv2h, net->d_ovf, n * GS::BPC);
-    stage_end(ctx, TREXHIP_STAGE_CONV2);
-    stage_begin(ctx, TREXHIP_STAGE_CONV3);
-    const int n_pass3 = (n * GW::TPC + GW::MB - 1) / GW::MB;
-    if (pre) {
-        // tickets of 4 consecutive passes (their halo rows are L2 hits) for the first 7/8 of the passes, single passes behind them; a batch that
-        // gives a workgroup fewer than 4 tickets goes out pass by pass altogether (100 crops = 157 passes: 157 workgroups at once instead of 40
-        // that walk 4 passes each: 93 -> 35 us)
-        const int n_big3 = n_pass3 >= 16 * ctx->n_cus ? (int)((long long)n_pass3 * 7 / 8) / 4 : 0, want3 = n_big3 + (n_pass3 - n_big3 * 4);
-        hipLaunchKernelGGL(k_conv5_wpair, dim3(std::min(want3, ctx->n_cus)), dim3(256), GW::LDS_BYTES + 1024 /* slack for the last DMA instruction */, s,
-                           net->v3, net->w3w, net->b3, net->act3, net->inv3w, n, net->d_ovf + 1, n_big3);
-    }
-    else if (mode == TREXHIP_CNN_FP32)
-        hipLaunchKernelGGL((k_conv5<64, 128, 20, 20, 32>), dim3(n * G3::BPC), dim3(512), G3::LDS_BYTES, s, net->act2, net->w3, net->b3, net->act3);
-    else if (mode == TREXHIP_CNN_BF16X6) launch_split<64, 128, 20, 20, 6>(ctx, n, net->act2, net->w3s, net->b3, net->act3, nullptr);
-    else if (mode == TREXHIP_CNN_BF16X3) launch_split<64, 128, 20, 20, 3>(ctx, n, net->act2, net->w3s, net->b3, net->act3, nullptr);
-    else                // Winograd F(4,5) along x: 0.4x the matrix work of the direct form
-        hipLaunchKernelGGL((k_conv5_wino<64, 128, 20, 2>), dim3(std::min(n_pass3, ctx->n_cus)), dim3(GW::NTHR), GW::LDS_BYTES, s,
-                           net->act2, net->w3w, net->b3, net->act3, net->inv3w, net->d_ovf, n, net->d_ovf + 1);
-    stage_end(ctx, TREXHIP_STAGE_CONV3);
-    // split-K planes of fc1 (summed in k_head): FC1_KSPLIT keeps every CU busy at a few thousand crops
-    // (25600 crops: 10 planes 344 + 72 us for fc1 + head, 5 planes 319 + 66, 4: 365, 8: 381, 2: 347)
-    // (the number of planes must not depend on n -- 5 planes above 12800 crops gave the same crop bit-different probabilities in batches
-    // of 12799 and 12800; 10 always costs 31 us of a 9 ms step)
-    if (mode != TREXHIP_CNN_FP16X3)
-        hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, 12800, (const uint32_t*)nullptr);
-    else if (n <= 1024)     // small batches: 32 crops per workgroup (same sums in the same order: a crop's row does not depend on the kernel its batch got)
-        hipLaunchKernelGGL(k_fc1_split<1>, dim3((n + 31) / 32, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
-    else
-        hipLaunchKernelGGL(k_fc1_split<4>, dim3((n + 127) / 128, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1h, net->bf1, net->fc1, n, 12800, net->invf1h, net->d_ovf, net->d_ovfc);
-    const bool small_head = n <= 1024;
-    if (small_head)     // one crop per wave, nothing but latency to save (k_head_small); same bits.  Its first workgroup also makes the range guard's plan
-        hipLaunchKernelGGL(k_head_small, dim3((n + 3) / 4), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                           d_probs, d_logits, n, net->classes, FC1_KSPLIT,
-                           mode == TREXHIP_CNN_FP16X3 ? net->d_ovf : (uint32_t*)nullptr, net->d_ovfc, mode == TREXHIP_CNN_FP16X3 ? net->d_ovf + 4 : (uint32_t*)nullptr);
-    else
-        hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                           d_probs, d_logits, n, net->classes, (const uint32_t*)nullptr, FC1_KSPLIT);
-    if (mode == TREXHIP_CNN_FP16X3) {
-        // guarded re-run with the bf16 split: every workgroup returns at once unless an activation left the fp16 range; k_guard_plan lists the
-        // flagged crops (or orders the whole batch when the flag came from a kernel that does not know the crop) and the re-run follows its plan
-        if (!small_head) hipLaunchKernelGGL(k_guard_plan, dim3(1), dim3(1024), 0, s, net->d_ovf, net->d_ovfc, n, net->d_ovf + 4);
-        const uint32_t* g = net->d_ovf + 4;
-        if (pre) {      // the default chain has no fp32 activations: the re-run starts at the crops
-            if (net->CH == 1) hipLaunchKernelGGL(k_conv1_mfma, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, g);
-            else              hipLaunchKernelGGL(k_conv1_mfma3, dim3(n), dim3(256), 0, s, d_crops, net->w1h, net->b1, net->act1, net->inv1h, g);
+    launch_conv1(f, p.conv1, nullptr);
+    if (p.chain == Chain::ANY_SIZE) {
+        any_conv(s, net, p, 2, f.mode, nullptr);
+        any_conv(s, net, p, 3, f.mode, nullptr);
+    } else {
+        const bool pre = p.chain == Chain::ROLE_SPLIT || p.chain == Chain::FUSED_2WG || p.chain == Chain::TWO_KERNEL;      // conv2 writes V3
+        stage_begin(ctx, TREXHIP_STAGE_CONV2);
+        switch (p.chain) {
+        case Chain::ROLE_SPLIT: case Chain::FUSED_2WG:
+            (p.chain == Chain::ROLE_SPLIT ? K_CONV12_RS : K_CONV12_WPRE)(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w,
+                                                                        net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2), p.pk2, net.d_ovfc);
+            break;
+        case Chain::TWO_KERNEL:
+            K_CONV2_WPRE2(s, p.conv2.grid, net.v2, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2));
+            break;
+        case Chain::FP32_ACT:
+            K_CONV2_STREAM(s, p.conv2.grid, net.act1, net.w2h, net.b2, net.act2, net.inv2h, net.ovf(OVF_RANGE), p.conv2.items);
+            break;
+        default: launch_exact(f, 2, f.mode, nullptr);
         }
-        launch_split<16, 64, 40, 10, 6>(ctx, n, net->act1, net->w2s, net->b2, net->act2, g);
-        // (conv3 in bands of 4 rows, five workgroups per crop: a re-run is a handful of crops, and one workgroup walking a whole crop's 2 GFLOP
-        // alone took 0.4 ms of the 0.5 ms a tripped guard cost)
-        launch_split<64, 128, 20, 4, 6>(ctx, n, net->act2, net->w3s, net->b3, net->act3, g);
-        hipLaunchKernelGGL(k_fc1, dim3((n + 31) / 32, FC1_KSPLIT), dim3(256), 0, s, net->act3, net->wf1, net->bf1, net->fc1, n, 12800, g);
-        hipLaunchKernelGGL(k_head, dim3((n + 4 * HEAD_CPW - 1) / (4 * HEAD_CPW)), dim3(256), 0, s, net->fc1, net->lng, net->lnb, net->wf2t, net->bf2,
-                           d_probs, d_logits, n, net->classes, g, FC1_KSPLIT);
+        stage_end(ctx, TREXHIP_STAGE_CONV2);
+        stage_begin(ctx, TREXHIP_STAGE_CONV3);
+        if (pre) K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3);
+        else if (p.chain == Chain::FP32_ACT)
+            K_CONV3_WINO(s, p.conv3.grid, net.act2, net.w3w, net.b3, net.act3, net.inv3w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS3));
+        else launch_exact(f, 3, f.mode, nullptr);
+        stage_end(ctx, TREXHIP_STAGE_CONV3);
     }
+    launch_tail(f, nullptr);
+    if (p.rerun) launch_rerun(f);
     stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
@@ -1707,68 +1548,78 @@ int net_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs,
     if (ctx->cnn_mode == TREXHIP_CNN_FP16X3) {
         // the range flag and the pass counters: zero by construction (the plan kernel of the previous pass), cleared here only behind a pass that
         // failed half-way (outside any capture: a replayed chain never holds this memset)
-        if (!net->ovf_clean) TH_CHECK_HIP(hipMemsetAsync(net->d_ovf, 0, 16, ctx->stream));
+        if (!net->ovf_clean) TH_CHECK_HIP(hipMemsetAsync(net->d_ovf, 0, OVF_PLAN * 4, ctx->stream));
         net->ovf_clean = false;
     }
     const int rc = net_forward_inner(ctx, d_crops, n, d_probs, d_logits);
     if (rc == TREXHIP_OK) { net->last_mode = ctx->cnn_mode; if (ctx->cnn_mode == TREXHIP_CNN_FP16X3) net->ovf_clean = true; }
     return rc;
 }
+
+// captures the chain of one call into `cand`; false (and graphs off for the net) when any step of that fails -- nothing was executed then
+static bool capture_chain(trexhip_ctx* ctx, Net* net, Net::GraphEntry* cand, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipEvent_t ev = nullptr;
+    bool ok = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+        const int rc = net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
+        const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
+        ok = rc == TREXHIP_OK && e_end == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess &&
+             hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!ok) {
+        (void)hipGetLastError();
+        if (exec) (void)hipGraphExecDestroy(exec);
+        net->graphs_ok = false;
+        return false;
+    }
+    cand->exec = exec; cand->last = ev;
+    return true;
+}
+
 static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
     Net* net = static_cast<Net*>(ctx->net);
     static const bool enabled = [] { const char* e = std::getenv("TREXHIP_GRAPHS"); return !(e && std::atoi(e) == 0); }();
     // not while profiling (the stage events are host-side bookkeeping), not before the first plain call (function attributes are set there)
     if (!enabled || !net->graphs_ok || n > GRAPH_MAX_CROPS || ctx->profiling || !ctx->attr_cnn) return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
     hipStream_t s = ctx->stream;
-    const int mode = ctx->cnn_mode, geom = ctx->tune_conv_geom;
+    const Net::GraphKey key{d_crops, n, d_probs, d_logits, ctx->cnn_mode, ctx->tune_conv_geom, s};
     ++net->tick;
     Net::GraphEntry* cand = nullptr;
     for (auto& g : net->graphs)
-        if (g.crops == d_crops && g.n == n && g.probs == d_probs && g.logits == d_logits && g.mode == mode && g.geom == geom && g.stream == s) {
-            g.used = net->tick;
-            if (g.exec) {
-                TH_CHECK_HIP(hipGraphLaunch(g.exec, s));
-                TH_CHECK_HIP(hipEventRecord(g.last, s));
-                return TREXHIP_OK;
-            }
-            cand = &g;
-            break;
-        }
-    auto evict_lru = [&]() {
-        size_t lru = 0;
-        for (size_t i = 1; i < net->graphs.size(); ++i) if (net->graphs[i].used < net->graphs[lru].used) lru = i;
-        destroy_graph_entry(net->graphs[lru]);
-        net->graphs.erase(net->graphs.begin() + (long)lru);
-    };
+        if (g.key == key) { cand = &g; break; }
     if (!cand) {                                                  // a new key: count it, run the chain directly
-        if (net->graphs.size() >= GRAPH_CACHE) evict_lru();
-        net->graphs.push_back({d_crops, n, d_probs, d_logits, mode, geom, s, nullptr, net->tick, nullptr, 1});
+        if (net->graphs.size() >= GRAPH_CACHE) {                  // ... in the place of the least recently used one
+            size_t lru = 0;
+            for (size_t i = 1; i < net->graphs.size(); ++i) if (net->graphs[i].used < net->graphs[lru].used) lru = i;
+            destroy_graph_entry(net->graphs[lru]);
+            net->graphs.erase(net->graphs.begin() + (long)lru);
+        }
+        net->graphs.push_back({key, nullptr, net->tick, nullptr, 1});
         return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
     }
-    if (++cand->seen < GRAPH_MIN_SEEN) return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        net->graphs_ok = false;
+    cand->used = net->tick;
+    if (!cand->exec && (++cand->seen < GRAPH_MIN_SEEN || !capture_chain(ctx, net, cand, d_crops, n, d_probs, d_logits)))
         return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
-    }
-    const int rc = net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
-    hipGraph_t graph = nullptr;
-    const hipError_t e_end = hipStreamEndCapture(s, &graph);
-    hipGraphExec_t exec = nullptr;
-    hipEvent_t ev = nullptr;
-    if (rc != TREXHIP_OK || e_end != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        net->graphs_ok = false;                                   // nothing was executed during the capture: run the chain directly, from now on always
-        return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
-    }
-    (void)hipGraphDestroy(graph);
-    cand->exec = exec; cand->last = ev;
-    TH_CHECK_HIP(hipGraphLaunch(exec, s));
-    TH_CHECK_HIP(hipEventRecord(ev, s));
+    TH_CHECK_HIP(hipGraphLaunch(cand->exec, s));
+    TH_CHECK_HIP(hipEventRecord(cand->last, s));
     return TREXHIP_OK;
+}
+
+// the checks and preparations every identify entry point shares; *net stays null when there is nothing to do (n == 0)
+static int identify_prepare(trexhip_ctx* ctx, const bool args, const char* who, const int32_t n, Net** net) {
+    *net = nullptr;
+    if (!args) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
+    Net* loaded = static_cast<Net*>(ctx->net);
+    if (!loaded) { set_error("trexhip_identify: weights not loaded (VINetwork status().weights.loaded())"); return TREXHIP_E_INVALID; }
+    if (n < 0) { set_error("trexhip_identify: n < 0"); return TREXHIP_E_INVALID; }
+    if (n == 0) return TREXHIP_OK;
+    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    const int rc = ensure_act(ctx, loaded, n);
+    if (rc == TREXHIP_OK) *net = loaded;
+    return rc;
 }
 
 }  // namespace trexhip
@@ -1783,26 +1634,16 @@ int trexhip_load_weights(trexhip_ctx* ctx, const void* blob, size_t bytes) {
 }
 
 int trexhip_identify_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n, float* d_probs, float* d_logits) {
-    if (!ctx || !d_crops || !d_probs) { set_error("trexhip_identify_device: null argument"); return TREXHIP_E_INVALID; }
-    Net* net = static_cast<Net*>(ctx->net);
-    if (!net) { set_error("trexhip_identify: weights not loaded (VINetwork status().weights.loaded())"); return TREXHIP_E_INVALID; }
-    if (n < 0) { set_error("trexhip_identify: n < 0"); return TREXHIP_E_INVALID; }
-    if (n == 0) return TREXHIP_OK;
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    int rc = ensure_act(ctx, net, n);
-    if (rc) return rc;
+    Net* net;
+    const int rc = identify_prepare(ctx, ctx && d_crops && d_probs, "trexhip_identify_device", n, &net);
+    if (rc || !net) return rc;
     return net_forward(ctx, d_crops, n, d_probs, d_logits);
 }
 
 int trexhip_identify(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, float* probs) {
-    if (!ctx || !crops || !probs) { set_error("trexhip_identify: null argument"); return TREXHIP_E_INVALID; }
-    Net* net = static_cast<Net*>(ctx->net);
-    if (!net) { set_error("trexhip_identify: weights not loaded (VINetwork status().weights.loaded())"); return TREXHIP_E_INVALID; }
-    if (n < 0) { set_error("trexhip_identify: n < 0"); return TREXHIP_E_INVALID; }
-    if (n == 0) return TREXHIP_OK;
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    int rc = ensure_act(ctx, net, n);
-    if (rc) return rc;
+    Net* net;
+    int rc = identify_prepare(ctx, ctx && crops && probs, "trexhip_identify", n, &net);
+    if (rc || !net) return rc;
     const size_t cb = (size_t)net->W * net->H * net->CH;
     TH_CHECK_HIP(hipMemcpyAsync(net->crops, crops, cb * n, hipMemcpyHostToDevice, ctx->stream));
     rc = net_forward(ctx, net->crops, n, net->probs, nullptr);
@@ -1819,7 +1660,7 @@ int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     // the plan of the LAST forward pass -- none before the first pass or behind a pass in another precision mode (not ctx->cnn_mode, which
     // trexhip_set_identity_precision may have changed since)
-    if (net->last_mode == TREXHIP_CNN_FP16X3) TH_CHECK_HIP(hipMemcpy(plan, net->d_ovf + 4, 8, hipMemcpyDeviceToHost));
+    if (net->last_mode == TREXHIP_CNN_FP16X3) TH_CHECK_HIP(hipMemcpy(plan, net->ovf(OVF_PLAN), 8, hipMemcpyDeviceToHost));
     if (rerun_crops) *rerun_crops = plan[1] == 1u ? plan[0] : 0u;
     if (whole_batch) *whole_batch = plan[1] == 2u ? 1u : 0u;
     return TREXHIP_OK;

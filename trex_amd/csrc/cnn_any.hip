@@ -13,9 +13,8 @@
 //                        (3 piece products, scaled weights): the arithmetic of the 80x80 chain's precision modes.
 //   The fp16 kernels flag the crop of an activation outside the fp16 range (crop_flags + overflow bit 0); k_guard_plan (cnn.hip)
 //   lists those crops and the bf16x6 instances, launched with that plan as their guard, re-run only them.
-#include "internal.h"
+#include "cnn_net.h"
 #include "cnn_split.h"
-#include <algorithm>
 
 namespace trexhip {
 namespace {
@@ -23,7 +22,6 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // conv1: CH -> 16, 5x5 'same' + folded BN + ReLU + floor 2x2 max-pool, exact fp32
 // ------------------------------------------------------------------------------------------------
-constexpr int C1T = 16;                      // pooled outputs per tile side: one per thread
 template <int CH>
 __global__ __launch_bounds__(256) void k_any_conv1(const uint8_t* __restrict__ crops /*[N][H][W][CH]*/, const float* __restrict__ w /*[CH][25][16]*/,
                                                    const float* __restrict__ bias, float* __restrict__ out /*[N][H/2][W/2][16]*/,
@@ -94,7 +92,6 @@ __global__ __launch_bounds__(256) void k_any_conv1(const uint8_t* __restrict__ c
 // ------------------------------------------------------------------------------------------------
 // conv2 / conv3: 5x5 'same' + folded BN + ReLU + floor 2x2 max-pool on the matrix cores, 2-D output tiles
 // ------------------------------------------------------------------------------------------------
-constexpr int AW = 64;                       // pool windows per tile = 8 M-tiles of 32 conv pixels
 constexpr int APMAX = 36 * 12;               // patch pixels of the largest tile shape (4 x 16 or 16 x 4 windows)
 
 template <int KIND> struct AnyK;             // 0 = bf16 (3 pieces), 1 = fp16 (2 pieces), 2 = fp32
@@ -252,78 +249,29 @@ __global__ __launch_bounds__(512) void k_any_conv(const float* __restrict__ in /
     }
 }
 
-// the tile shape (TX windows wide, 64 / TX high) with the fewest tiles over a pooled output of Ho x Wo; 8 x 8 on a tie
-struct AnyTiles { int TX, tx_n, tiles; };
-AnyTiles any_tiles(const int Ho, const int Wo) {
-    AnyTiles best{8, (Wo + 7) / 8, ((Ho + 7) / 8) * ((Wo + 7) / 8)};
-    for (const int tx : {4, 16}) {
-        const int ty = AW / tx, txn = (Wo + tx - 1) / tx, t = ((Ho + ty - 1) / ty) * txn;
-        if (t < best.tiles) best = {tx, txn, t};
-    }
-    return best;
-}
-
+// the four precision instances of a layer, each stated once; the bf16x6 one also runs the guarded re-run
+using AnyKern = decltype(Kern(k_any_conv<16, 64, 2, 1, 16>, 512));
 template <int CI, int CO, int KIND, int NTERMS, int CIC>
-void launch_conv(hipStream_t s, const int n_cus, const float* in, const void* w, const float* bias, float* out, const int Hi, const int Wi,
-                 const float scale, uint32_t* ovf, uint8_t* flags, const uint32_t* guard, const int n) {
-    const AnyTiles tl = any_tiles(Hi / 2, Wi / 2);
-    const int nb = n * tl.tiles;
-    hipLaunchKernelGGL((k_any_conv<CI, CO, KIND, NTERMS, CIC>), dim3(guard ? std::min(nb, 4 * n_cus) : nb), dim3(512),
-                       (AnyGeom<CO, KIND, CIC>::LDS_BYTES), s, in, static_cast<const uint4*>(w), bias, out, Hi, Wi, tl.TX, tl.tx_n, tl.tiles,
-                       scale, ovf, flags, guard, nb);
-}
-
-template <int CI, int CO, int KIND, int NTERMS, int CIC>
-int set_lds() {
-    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_any_conv<CI, CO, KIND, NTERMS, CIC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     AnyGeom<CO, KIND, CIC>::LDS_BYTES));
-    return TREXHIP_OK;
-}
+AnyKern any_kern() { return Kern(k_any_conv<CI, CO, KIND, NTERMS, CIC>, 512, AnyGeom<CO, KIND, CIC>::LDS_BYTES); }
+struct AnyLayer { AnyKern by_mode[4]; };     // indexed by TREXHIP_CNN_*: FP32, BF16X6, BF16X3, FP16X3
+const AnyLayer ANY_CONV[2] = {{{any_kern<16, 64, 2, 1, 16>(), any_kern<16, 64, 0, 6, 16>(), any_kern<16, 64, 0, 3, 16>(), any_kern<16, 64, 1, 3, 16>()}},
+                              {{any_kern<64, 128, 2, 1, 32>(), any_kern<64, 128, 0, 6, 16>(), any_kern<64, 128, 0, 3, 16>(), any_kern<64, 128, 1, 3, 16>()}}};
+const ByChannels ANY_CONV1{Kern(k_any_conv1<1>, 256), Kern(k_any_conv1<3>, 256)};
 
 }  // namespace
 
-int any_set_attributes() {
-    int rc = TREXHIP_OK;
-    if (!rc) rc = set_lds<16, 64, 2, 1, 16>();
-    if (!rc) rc = set_lds<64, 128, 2, 1, 32>();
-    if (!rc) rc = set_lds<16, 64, 0, 6, 16>();
-    if (!rc) rc = set_lds<64, 128, 0, 6, 16>();
-    if (!rc) rc = set_lds<16, 64, 0, 3, 16>();
-    if (!rc) rc = set_lds<64, 128, 0, 3, 16>();
-    if (!rc) rc = set_lds<16, 64, 1, 3, 16>();
-    if (!rc) rc = set_lds<64, 128, 1, 3, 16>();
-    return rc;
+void any_conv1(hipStream_t s, const Net& net, const CnnPlan& p, const uint8_t* d_crops) {
+    ANY_CONV1[net.CH](s, p.conv1_grid, d_crops, net.w1, net.b1, net.act1, net.W, net.H, p.tx1, p.t1);
 }
 
-void any_convs(hipStream_t s, const int n_cus, const int mode, const AnyConvNet& a, const uint8_t* d_crops, const int n) {
-    const int Ho = a.H / 2, Wo = a.W / 2;
-    const int tx1 = (Wo + C1T - 1) / C1T, t1 = ((Ho + C1T - 1) / C1T) * tx1;
-    if (a.CH == 1) hipLaunchKernelGGL((k_any_conv1<1>), dim3(n * t1), dim3(256), 0, s, d_crops, a.w1, a.b1, a.act1, a.W, a.H, tx1, t1);
-    else           hipLaunchKernelGGL((k_any_conv1<3>), dim3(n * t1), dim3(256), 0, s, d_crops, a.w1, a.b1, a.act1, a.W, a.H, tx1, t1);
-    const int H2 = a.H / 2, W2 = a.W / 2, H3 = a.H / 4, W3 = a.W / 4;
-    const uint32_t* ng = nullptr;
-    switch (mode) {
-    case TREXHIP_CNN_FP32:
-        launch_conv<16, 64, 2, 1, 16>(s, n_cus, a.act1, a.w2, a.b2, a.act2, H2, W2, 1.f, a.ovf, a.flags, ng, n);
-        launch_conv<64, 128, 2, 1, 32>(s, n_cus, a.act2, a.w3, a.b3, a.act3, H3, W3, 1.f, a.ovf, a.flags, ng, n);
-        break;
-    case TREXHIP_CNN_BF16X6:
-        launch_conv<16, 64, 0, 6, 16>(s, n_cus, a.act1, a.w2s, a.b2, a.act2, H2, W2, 1.f, a.ovf, a.flags, ng, n);
-        launch_conv<64, 128, 0, 6, 16>(s, n_cus, a.act2, a.w3s, a.b3, a.act3, H3, W3, 1.f, a.ovf, a.flags, ng, n);
-        break;
-    case TREXHIP_CNN_BF16X3:
-        launch_conv<16, 64, 0, 3, 16>(s, n_cus, a.act1, a.w2s, a.b2, a.act2, H2, W2, 1.f, a.ovf, a.flags, ng, n);
-        launch_conv<64, 128, 0, 3, 16>(s, n_cus, a.act2, a.w3s, a.b3, a.act3, H3, W3, 1.f, a.ovf, a.flags, ng, n);
-        break;
-    default:
-        launch_conv<16, 64, 1, 3, 16>(s, n_cus, a.act1, a.w2h, a.b2, a.act2, H2, W2, a.inv2h, a.ovf, a.flags, ng, n);
-        launch_conv<64, 128, 1, 3, 16>(s, n_cus, a.act2, a.w3h, a.b3, a.act3, H3, W3, a.inv3h, a.ovf, a.flags, ng, n);
-    }
-}
-
-void any_convs_rerun(hipStream_t s, const int n_cus, const AnyConvNet& a, const int n, const uint32_t* plan) {
-    launch_conv<16, 64, 0, 6, 16>(s, n_cus, a.act1, a.w2s, a.b2, a.act2, a.H / 2, a.W / 2, 1.f, a.ovf, a.flags, plan, n);
-    launch_conv<64, 128, 0, 6, 16>(s, n_cus, a.act2, a.w3s, a.b3, a.act3, a.H / 4, a.W / 4, 1.f, a.ovf, a.flags, plan, n);
+void any_conv(hipStream_t s, const Net& net, const CnnPlan& p, const int layer, const int mode, const uint32_t* guard) {
+    const bool c2 = layer == 2, h16 = mode == TREXHIP_CNN_FP16X3;
+    const AnyTiles& tl = c2 ? p.t2 : p.t3;
+    const Launch& l = guard ? (c2 ? p.r_conv2 : p.r_conv3) : (c2 ? p.conv2 : p.conv3);
+    const void* w = mode == TREXHIP_CNN_FP32 ? (c2 ? (const void*)net.w2 : net.w3) : h16 ? (c2 ? net.w2h : net.w3h) : (c2 ? net.w2s : net.w3s);
+    ANY_CONV[layer - 2].by_mode[mode](s, l.grid, c2 ? net.act1 : net.act2, w, c2 ? net.b2 : net.b3, c2 ? net.act2 : net.act3, net.H / (c2 ? 2 : 4),
+                                      net.W / (c2 ? 2 : 4), tl.TX, tl.tx_n, tl.tiles, h16 ? (c2 ? net.inv2h : net.inv3h) : 1.f, net.ovf(OVF_RANGE), net.d_ovfc,
+                                      guard, l.items);
 }
 
 }  // namespace trexhip

@@ -1,0 +1,69 @@
+// cnn_net.h -- the identity network's host state and how its kernels are launched, shared by cnn.hip and cnn_any.hip (not part of the ABI)
+#pragma once
+#include "internal.h"
+#include "cnn_plan.h"
+#include <tuple>
+
+namespace trexhip {
+
+struct Net {
+    int classes = 0, W = 0, H = 0, CH = 0, max_crops = 0;
+    uint4 *w2s = nullptr, *w3s = nullptr;      // bf16-split conv weights
+    uint4 *w2h = nullptr, *w3h = nullptr;      // fp16-split conv weights (scaled by a power of two)
+    float inv2h = 1.f, inv3h = 1.f;
+    uint4 *w2w = nullptr, *w3w = nullptr;      // Winograd F(4,5)-domain conv weights, fp16 pieces (k_conv5_wino)
+    float inv2w = 1.f, inv3w = 1.f;
+    uint4* wf1h = nullptr;                     // fc1 weights, fp16 pieces in MFMA B layout [K/8][2][128] x 8 halves
+    float invf1h = 1.f;
+    uint4* w1h = nullptr;                      // conv1 B fragments (16 fragments x 64 lanes), fp16 pieces of the folded weights
+    float inv1h = 1.f;
+    uint32_t* d_ovf = nullptr;                 // the guard words, OVF_WORDS of them (cnn_geom.h: OVF_RANGE, OVF_PASS3, OVF_PASS2, OVF_PLAN)
+    uint8_t* d_ovfc = nullptr;                 // per-crop range flags [max_crops]
+    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;      // folded fp32: conv1 [CH][25][16], conv2 / conv3 chunked
+    float *wf1 = nullptr, *bf1 = nullptr, *lng = nullptr, *lnb = nullptr, *wf2t = nullptr, *bf2 = nullptr;
+    float *act1 = nullptr, *act2 = nullptr, *act3 = nullptr, *fc1 = nullptr, *probs = nullptr, *logits = nullptr;   // act: [n][H/2][W/2][16], [n][H/4][W/4][64], [n][H/8][W/8][128]
+    uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
+    uint8_t* crops = nullptr;
+    float* h_probs = nullptr;                  // pinned
+    Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
+    // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one
+    // identify call is captured into a hipGraph per (buffers, n, precision) and replayed
+    // A chain is only captured once the same (buffers, n, precision) key has come THREE times: in tracking the blob count changes from
+    // batch to batch, and capture + instantiate costs far more than the ~100 us of launch overhead a replay saves.
+    using GraphKey = std::tuple<const uint8_t* /*crops*/, int /*n*/, float* /*probs*/, float* /*logits*/, int /*mode*/, int /*geom*/, hipStream_t>;
+    struct GraphEntry { GraphKey key; hipGraphExec_t exec; uint64_t used; hipEvent_t last; int seen; };      // exec == nullptr: a candidate key that is still being counted
+    std::vector<GraphEntry> graphs;
+    bool graphs_ok = true;
+    uint64_t tick = 0;
+    bool ovf_clean = true;                     // the words in front of OVF_PLAN are zero, or will be when the queued work has run (see net_forward)
+    int last_mode = -1;                        // precision mode of the last forward pass (trexhip_identify_guard_stats reads the plan only behind an fp16x3 pass)
+    uint32_t* ovf(const int word) const { return d_ovf + word; }
+};
+
+// A kernel instance, stated once with its workgroup size and its dynamic LDS bytes.  An instance that needs the dynamic-LDS attribute lists itself
+// when it is constructed (they are file-scope constants); the attribute pass (net_forward_launch) walks that list, and the launch uses the same entry.
+struct LdsAttr { const void* fn; int bytes; };
+std::vector<LdsAttr>& lds_attrs();
+template <class... A>
+struct Kern {
+    void (*fn)(A...);
+    int threads, lds;
+    Kern(void (*f)(A...), const int threads_, const int lds_ = 0, const bool attr = true) : fn(f), threads(threads_), lds(lds_) {
+        if (lds && attr) lds_attrs().push_back({reinterpret_cast<const void*>(f), lds});
+    }
+    template <class... B>
+    void operator()(hipStream_t s, const dim3 grid, B... args) const { hipLaunchKernelGGL(fn, grid, dim3(threads), lds, s, static_cast<A>(args)...); }
+};
+// the instances for 1 and for 3 input channels share a signature
+template <class K> struct ByChannels {
+    K one, three;
+    const K& operator[](const int CH) const { return CH == 1 ? one : three; }
+};
+template <class K> ByChannels(K, K) -> ByChannels<K>;
+
+// the any-size chain's convolutions (cnn_any.hip): conv1 in exact fp32, conv2 (layer 2) / conv3 (layer 3) in the precision mode; with a guard
+// (the re-run plan) on the plan's small grid
+void any_conv1(hipStream_t s, const Net& net, const CnnPlan& p, const uint8_t* d_crops);
+void any_conv(hipStream_t s, const Net& net, const CnnPlan& p, int layer, int mode, const uint32_t* guard);
+
+}  // namespace trexhip

@@ -209,15 +209,6 @@ __global__ __launch_bounds__(256) void k_conv1_wpre(const uint8_t* __restrict__ 
 //     each row's 16-byte units within their 256-byte blocks by rot(slot) = (slot & 1) + 4 ((slot >> 1) & 3): applied to the SOURCE
 //     address of the DMA and to the read address alike.
 // ------------------------------------------------------------------------------------------------
-struct W2bGeom {
-    static constexpr int CO = 64, S = 40, TPP = 20, RPP = 3, NR = 2 * RPP + 4;
-    static constexpr int ROWL = 1280;                                   // one (row, piece, group): 4 positions x 10 tiles x 32 B, in V2 and in LDS
-    static constexpr int PLANE = (NR + 1) * ROWL, BUF = 2 * PLANE;      // slot 0 = the zero row; BUF = the two pieces of one position group
-    static constexpr int PBUF_OFF = 2 * BUF, PBUF = RPP * 20 * 64 * 4;
-    static constexpr int LDS_BYTES = PBUF_OFF + PBUF;
-    static constexpr int BV = 2 * 2 * CO;
-    static_assert(2 * (LDS_BYTES + 64) <= 160 * 1024, "two workgroups per CU");
-};
 __device__ __forceinline__ int w2b_rot(const int slot) { return (slot & 1) + ((slot & 6) << 1); }
 
 __global__ __launch_bounds__(256, 2) void k_conv2_wpre2(const uint8_t* __restrict__ v2, const uint4* __restrict__ wp /*[5][8][2][2][64] x 16 B*/,

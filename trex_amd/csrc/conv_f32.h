@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cnn_geom.h"
 
 namespace trexhip {
 
@@ -14,23 +15,6 @@ enum { CONV_EPI_POOL = 0, CONV_EPI_RAW = 1 };
 // ------------------------------------------------------------------------------------------------
 // conv 5x5 'same' + folded BN + ReLU + maxpool2 as 25 shifted GEMMs on fp32 MFMA
 // ------------------------------------------------------------------------------------------------
-template <int CI, int CO, int S, int ROWS, int CIC>
-struct ConvGeom {
-    static constexpr int PW = S + 4, PH = ROWS + 4;
-    static constexpr int STR = CIC + 1;                               // odd pixel stride: conflict-free b32 reads
-    static constexpr int RP0 = PW * STR;
-    static constexpr int RP = RP0 + ((16 - (RP0 % 32)) + 32) % 32;    // row pitch == 16 (mod 32): rows y, y+1 use disjoint banks
-    static constexpr int PATCH = PH * RP;                             // floats
-    static constexpr int BT = CIC * CO;                               // floats per weight tile
-    static constexpr int NPIX = ROWS * S;
-    static constexpr int MT = (NPIX + 31) / 32;
-    static constexpr int NT = CO / 32;
-    static constexpr int WM = 8 / NT;                                 // wave groups along M
-    static constexpr int TPW = (MT + WM - 1) / WM;                    // M tiles per wave
-    static constexpr int LDS_BYTES = (PATCH + 2 * BT) * 4;
-    static constexpr int BPC = S / ROWS;                              // blocks per crop
-};
-
 template <int CI, int CO, int S, int ROWS, int CIC, int EPI = CONV_EPI_POOL, int COUT = CO>
 __global__ __launch_bounds__(512) void k_conv5(const float* __restrict__ in /*[N][S][S][CI]*/,
                                                const float* __restrict__ wp /*[CI/CIC][25][CIC][CO]*/,

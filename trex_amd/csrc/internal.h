@@ -192,20 +192,6 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n);
 void stage_begin(trexhip_ctx* ctx, int stage);
 void stage_end(trexhip_ctx* ctx, int stage);
 void net_free(trexhip_ctx* ctx);
-// the identity network's convolutions at an individual_image_size other than 80x80 (cnn_any.hip); cnn.hip owns the tensors and runs fc1 + head
-struct AnyConvNet {
-    int W, H, CH;
-    const float *w1, *b1;                      // conv1 folded [CH][25][16]
-    const float *w2, *b2, *w3, *b3;            // folded fp32 [1][25][16][64] and [2][25][32][128]
-    const void *w2s, *w3s, *w2h, *w3h;         // the same as bf16 (three) / fp16 (two, scaled) pieces in 16-channel chunks
-    float inv2h, inv3h;
-    float *act1, *act2, *act3;                 // [n][H/2][W/2][16], [n][H/4][W/4][64], [n][H/8][W/8][128]
-    uint32_t* ovf;                             // fp16 range flag (bit 0)
-    uint8_t* flags;                            // per-crop range flags
-};
-int any_set_attributes();
-void any_convs(hipStream_t s, int n_cus, int mode, const AnyConvNet& a, const uint8_t* d_crops, int n);
-void any_convs_rerun(hipStream_t s, int n_cus, const AnyConvNet& a, int n, const uint32_t* plan);    // bf16x6 conv2 + conv3 of the plan's crops
 int launch_pending(trexhip_ctx* ctx);
 int launch_morphology(trexhip_ctx* ctx, const uint8_t* d_frames, int n, const uint32_t** result);
 int launch_rethreshold(trexhip_ctx* ctx, int thr, int method, const double* ranges, int n_ranges, const int32_t* d_blob_thr);
