@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 13
+#define TREXHIP_ABI_VERSION 14
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -602,9 +602,13 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  * augmentation (:158-188, :1325-1336) may stay there too (trexhip_train_step takes what it yields), or run on the device:
  * trexhip_augment_device below writes the batch trexhip_train_step_device takes, from crops that never left HBM.
  *   trexhip_trainer_create     weights = the blob of trexhip_load_weights (state_dict order, running statistics included); the
- *                              trainer keeps parameters, gradients and Adam moments in HBM.  Training runs at 80 x 80 only: a blob
- *                              of any other individual_image_size is refused with TREXHIP_E_UNSUPPORTED
- *   trexhip_train_step_device  d_inputs [n][80][80][channels] float32 in [0, 255] (NHWC, what TRexImageDataset yields), d_targets
+ *                              trainer keeps parameters, gradients and Adam moments in HBM.  Any individual_image_size that
+ *                              trexhip_load_weights takes trains: 8 <= W, H <= 256, square or not (TREXHIP_E_UNSUPPORTED outside);
+ *                              every call below follows the trainer's size (trexhip_trainer_image_size).  80 x 80 runs the tuned
+ *                              kernels in the `precision` asked for; every other size runs a generic chain in exact fp32 (fp32 MFMA
+ *                              for conv2 / conv3 in all three roles) at BOTH values of `precision` -- the fp16 two-piece split is an
+ *                              80 x 80 matter.  Every reduction has a fixed order at every size: the same inputs give the same bits
+ *   trexhip_train_step_device  d_inputs [n][H][W][channels] float32 in [0, 255] (NHWC, what TRexImageDataset yields), d_targets
  *                              [n] class indices.  d_keep_masks: null = the library draws the dropout masks (counter-based hash of
  *                              seed, step, index); else n*16 + n*64 + n*128 + n*100 bytes, 1 = keep: the masks of Dropout2d after
  *                              block 1, 2, 3 ([n][C]) and of the Dropout after fc1 ([n][100]) -- how the parity tests inject what
@@ -625,16 +629,18 @@ typedef struct {
     float beta1, beta2, eps;    /* torch.optim.Adam defaults 0.9, 0.999, 1e-8                                                */
     float bn_momentum;          /* nn.BatchNorm2d default 0.1                                                                */
     float dropout;              /* 0.05 for all four dropout layers (visual_identification_network_torch.py:189-208)         */
-    int32_t precision;          /* arithmetic of the conv2 / conv3 forward, data-gradient and weight-gradient convolutions: 0 = fp16 two-piece split on the
+    int32_t precision;          /* (80 x 80; other sizes run exact fp32 at both values) arithmetic of the conv2 / conv3 forward, data-gradient and weight-gradient convolutions: 0 = fp16 two-piece split on the
                                    16-bit matrix cores (22-bit operands, fp32 accumulate, per-tensor power-of-two scales: the inference
                                    path's arithmetic), 1 = exact fp32 MFMA.  Everything else is fp32 either way                     */
     uint64_t seed;              /* of the library's own dropout masks                                                        */
 } trexhip_train_params;
-size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels);
+size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels);   /* of an 80 x 80 blob; a trainer exports as many bytes as the blob it was created from */
 int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* params, trexhip_trainer** out);
 void trexhip_trainer_destroy(trexhip_trainer* trainer);
 int trexhip_trainer_set_lr(trexhip_trainer* trainer, float lr);
 int64_t trexhip_trainer_steps(trexhip_trainer* trainer);
+/* the individual_image_size of the blob the trainer was created from: what every batch, crop and exported blob of this trainer has (ABI 14) */
+int trexhip_trainer_image_size(trexhip_trainer* trainer, int32_t* width, int32_t* height);
 int trexhip_train_step_device(trexhip_trainer* trainer, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks,
                               float* loss, int32_t* correct);
 /* model.eval() forward + mean cross entropy + arg-max count of one validation batch (train(), :1171-1190: what ReduceLROnPlateau and the
@@ -646,7 +652,7 @@ int trexhip_train_step(trexhip_trainer* trainer, const float* inputs, const int3
                        int32_t* correct);
 /* Softmax rows of any number of crops from the weights as they stand in the trainer: what ValidationCallback.plot_comparison_raw
  * (visual_recognition_torch.py:406-451) and estimate_uniqueness() -> Accumulation::calculate_uniqueness (ui/Accumulation.cpp:767-879) get from
- * predict_numpy at the end of every epoch, without exporting the weights to the inference context.  d_crops uint8 [n][80][80][channels]
+ * predict_numpy at the end of every epoch, without exporting the weights to the inference context.  d_crops uint8 [n][H][W][channels] at the trainer's size
  * (what the crop calls and the resident pool hold), d_probs float32 [n][classes]: model.eval(), running statistics, nothing dropped, in the
  * trainer's `precision`.  Any n >= 1: the call walks the crops in chunks of at most max_batch through the trainer's own buffers (a row does
  * not depend on its chunk).  Ordered on the context's stream, NO host synchronisation; parameters, moments, running statistics and the step

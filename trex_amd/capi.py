@@ -198,7 +198,7 @@ SYMBOLS = [
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
     "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats",
-    "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
+    "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
@@ -290,6 +290,7 @@ def lib():
         L.trexhip_trainer_set_lr.argtypes = [C.c_void_p, C.c_float]
         L.trexhip_trainer_steps.argtypes = [C.c_void_p]
         L.trexhip_trainer_steps.restype = C.c_int64
+        L.trexhip_trainer_image_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.trexhip_train_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_train_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_train_eval_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -827,6 +828,10 @@ class Trainer:
         _check(lib().trexhip_trainer_create(seg.handle, buf, len(weight_blob), C.byref(p), C.byref(self._h)))
         hdr = np.frombuffer(weight_blob[:32], np.int32)
         self.classes, self.channels = int(hdr[2]), int(hdr[5])
+        w, h = C.c_int32(), C.c_int32()
+        _check(lib().trexhip_trainer_image_size(self._h, C.byref(w), C.byref(h)))
+        self.width, self.height = w.value, h.value        # individual_image_size: every batch and crop of this trainer is [n][height][width][channels]
+        self._blob_bytes = len(weight_blob)
 
     def step_device(self, d_inputs_ptr, d_targets_ptr, n, d_keep_ptr=0, want_loss=True):
         """-> (mean loss, correct count) when want_loss (synchronises), else None"""
@@ -839,8 +844,8 @@ class Trainer:
         """the reference asserts image size, channel count and integer class labels per batch (visual_recognition_torch.py:1109-1110); the ABI
         takes raw pointers, so a wrong shape would be an out-of-bounds read, not an error"""
         x = np.asarray(inputs)
-        if x.ndim != 4 or tuple(x.shape[1:]) != (80, 80, self.channels):
-            raise ValueError(f"inputs must be (n, 80, 80, {self.channels}), got {tuple(x.shape)}")
+        if x.ndim != 4 or tuple(x.shape[1:]) != (self.height, self.width, self.channels):
+            raise ValueError(f"inputs must be (n, {self.height}, {self.width}, {self.channels}), got {tuple(x.shape)}")
         t = np.asarray(targets)
         if t.dtype.kind not in "iu":
             raise ValueError(f"targets must be integer class indices, got dtype {t.dtype}")
@@ -849,7 +854,7 @@ class Trainer:
         return np.ascontiguousarray(x, np.float32), np.ascontiguousarray(t, np.int32)
 
     def step(self, inputs, targets, keep_masks=None):
-        """host arrays: inputs float32 (n,80,80,C) in [0,255], targets int (n,), keep_masks uint8 (n*308,) or None -> (loss, correct)"""
+        """host arrays: inputs float32 (n,height,width,C) in [0,255], targets int (n,), keep_masks uint8 (n*308,) or None -> (loss, correct)"""
         x, y = self._check_batch(inputs, targets)
         k = np.ascontiguousarray(keep_masks, np.uint8) if keep_masks is not None else None
         if k is not None and k.size != x.shape[0] * 308:
@@ -873,7 +878,7 @@ class Trainer:
         return loss.value, correct.value
 
     def predict_device(self, d_crops_ptr, n, d_probs_ptr):
-        """uint8 crops [n][80][80][C] in HBM -> float32 softmax rows [n][classes] at d_probs_ptr from the weights as they stand (eval mode; any
+        """uint8 crops [n][height][width][C] in HBM -> float32 softmax rows [n][classes] at d_probs_ptr from the weights as they stand (eval mode; any
         n, chunked by max_batch inside; no synchronisation; the trainer is unchanged): trexhip_train_predict_device"""
         _check(lib().trexhip_train_predict_device(self._h, C.c_void_p(d_crops_ptr), n, C.c_void_p(d_probs_ptr)))
 
@@ -891,7 +896,7 @@ class Trainer:
         return out.reshape(shape)
 
     def export(self):
-        need = int(lib().trexhip_weight_blob_bytes(self.classes, self.channels))
+        need = self._blob_bytes                            # the blob it was created from: same classes, channels and size
         buf = (C.c_char * need)()
         got = C.c_size_t()
         _check(lib().trexhip_trainer_export(self._h, buf, need, C.byref(got)))

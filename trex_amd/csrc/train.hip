@@ -21,9 +21,14 @@
 // Host side (below the kernels): each of the three blocks is one `Layer` -- shape, tensor ids, buffers, and the kernel instances of the
 // trainer's precision bound to their LDS sizes -- filled once in trexhip_trainer_create; the forward pass, block_backward and trainer_attrs
 // walk that table.
+// The kernels of this file are the 80x80 chain.  A blob of any other individual_image_size (8..256 each way) trains on the chain of
+// train_any.hip (exact fp32, geometry in train_geom.h): the same walk, with `Trainer::any` choosing the launch at every size-dependent
+// kernel; the head, Adam, the masks, the target check, the loss and the reductions are shared.
 #include "internal.h"
 #include "conv_f32.h"
 #include "cnn_weights.h"
+#include "train_dev.h"
+#include "train_any.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -163,26 +168,6 @@ __global__ __launch_bounds__(256) void k_t_red_finalize(const double* __restrict
     }
 }
 
-// a block's column sums: the RL row-lanes of every channel added in fixed order -> partial[block][plane][C]
-template <int C, int NP>
-__device__ __forceinline__ void block_columns(const double (&acc)[NP][4], double* sh /*[256 / (C / 4) * C]*/, double* partial) {
-    constexpr int LC = C / 4, RL = 256 / LC;
-    const int tid = threadIdx.x, cl = tid % LC, rl = tid / LC;
-#pragma unroll
-    for (int pl = 0; pl < NP; ++pl) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sh[rl * C + cl * 4 + k] = acc[pl][k];
-        __syncthreads();
-        if (tid < C) {
-            double t = 0;
-            for (int r = 0; r < RL; ++r) t += sh[r * C + tid];
-            partial[((size_t)blockIdx.x * NP + pl) * C + tid] = t;
-        }
-    }
-    __syncthreads();
-}
-
 // ------------------------------------------------------------------------------------------------
 // batch statistics of z[rows][C]: per-channel sum and sum of squares, double accumulation -> partial[block][2][C] (FIN_BN_STATS)
 // ------------------------------------------------------------------------------------------------
@@ -211,8 +196,6 @@ __global__ void k_t_bn_from_running(const float* __restrict__ run_mean, const fl
 // ------------------------------------------------------------------------------------------------
 // BN (batch statistics) + ReLU + 2x2 max-pool + channel dropout: z [n][S][S][C] -> a [n][S/2][S/2][C]
 // ------------------------------------------------------------------------------------------------
-struct PoolWin { float4 y[4]; };
-
 template <int C>
 __device__ __forceinline__ void load_window(const float* __restrict__ z, int S, int crop, int py, int px, int c4, float4 v[4]) {
     const float* base = z + (((size_t)crop * S + 2 * py) * S + 2 * px) * C + c4 * 4;
@@ -221,9 +204,6 @@ __device__ __forceinline__ void load_window(const float* __restrict__ z, int S, 
     v[2] = *reinterpret_cast<const float4*>(base + (size_t)S * C);
     v[3] = *reinterpret_cast<const float4*>(base + (size_t)S * C + C);
 }
-
-__device__ __forceinline__ float f4get(const float4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
-__device__ __forceinline__ void f4set(float4& v, int k, float x) { if (k == 0) v.x = x; else if (k == 1) v.y = x; else if (k == 2) v.z = x; else v.w = x; }
 
 template <int C>
 __global__ __launch_bounds__(256) void k_t_bn_pool(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -250,22 +230,6 @@ __global__ __launch_bounds__(256) void k_t_bn_pool(const float* __restrict__ z, 
         f4set(out, k, keep[(size_t)crop * C + c] ? m * scale : 0.f);
     }
     *reinterpret_cast<float4*>(a + pos * C + c4 * 4) = out;
-}
-
-// the gradient that reaches the BN output of one pooled element: through dropout, the pool's arg-max (first maximum in scan order,
-// like torch's max_pool2d) and the ReLU gate.  Returns the arg-max position and x-hat there.
-__device__ __forceinline__ float pooled_grad(const float zq[4], float mean, float inv, float alpha, float beta, float da, bool kept, float scale,
-                                             int* arg, float* xhat) {
-    float best = zq[0] * alpha + beta;
-    int bi = 0;
-#pragma unroll
-    for (int q = 1; q < 4; ++q) {
-        const float y = zq[q] * alpha + beta;
-        if (y > best) { best = y; bi = q; }
-    }
-    *arg = bi;
-    *xhat = (zq[bi] - mean) * inv;
-    return (kept && best > 0.f) ? da * scale : 0.f;
 }
 
 // sums of dy and dy * x-hat over (n, y, x) per channel (BN backward), from the pooled gradient: partial[block][2][C] (FIN_BN_BWD)
@@ -422,7 +386,10 @@ __device__ __forceinline__ float block_max128(float v, float* red) {
     return red[0];
 }
 
-// one block per sample: fc1 bias + LayerNorm + ReLU + dropout + fc2 + softmax cross entropy, and the way back down to d(fc1 output)
+// one block per sample: fc1 bias + LayerNorm + ReLU + dropout + fc2 + softmax cross entropy, and the way back down to d(fc1 output).
+// PLANES = fc1's partial planes in hpart, added here in order: 100 at 80x80 (one per position), 1 at every other size (k_tany_fc1_sum has
+// added them)
+template <int PLANES>
 __global__ __launch_bounds__(128) void k_t_head(const float* __restrict__ hpart, int n, const float* __restrict__ b1, const float* __restrict__ lng,
                                                 const float* __restrict__ lnb, const uint8_t* __restrict__ keep /*[n][100]*/, float scale,
                                                 const float* __restrict__ w2 /*[C][100]*/, const float* __restrict__ b2, const int32_t* __restrict__ targets,
@@ -438,7 +405,7 @@ __global__ __launch_bounds__(128) void k_t_head(const float* __restrict__ hpart,
     float h = 0.f;
     if (act) {
         h = b1[tid];
-        for (int hw = 0; hw < 100; ++hw) h += hpart[((size_t)hw * n + s) * 100 + tid];
+        for (int hw = 0; hw < PLANES; ++hw) h += hpart[((size_t)hw * n + s) * 100 + tid];
     }
     const float mean = block_sum128(act ? h : 0.f, red) * 0.01f;
     const float dv = act ? h - mean : 0.f;
@@ -509,6 +476,7 @@ __global__ __launch_bounds__(128) void k_t_head(const float* __restrict__ hpart,
 
 // the head of a prediction (trexhip_train_predict_device): k_t_head's forward half with nothing dropped -- fc1 bias + LayerNorm + ReLU + fc2, the
 // same expressions in the same order -- and the softmax row expf(l - lse), as k_t_head forms p.  No targets, none of the backward buffers
+template <int PLANES>
 __global__ __launch_bounds__(128) void k_t_head_eval(const float* __restrict__ hpart, int n, const float* __restrict__ b1, const float* __restrict__ lng,
                                                      const float* __restrict__ lnb, const float* __restrict__ w2 /*[C][100]*/, const float* __restrict__ b2,
                                                      int classes, float* __restrict__ probs /*[n][C]*/) {
@@ -520,7 +488,7 @@ __global__ __launch_bounds__(128) void k_t_head_eval(const float* __restrict__ h
     float h = 0.f;
     if (act) {
         h = b1[tid];
-        for (int hw = 0; hw < 100; ++hw) h += hpart[((size_t)hw * n + s) * 100 + tid];
+        for (int hw = 0; hw < PLANES; ++hw) h += hpart[((size_t)hw * n + s) * 100 + tid];
     }
     const float mean = block_sum128(act ? h : 0.f, red) * 0.01f;
     const float dv = act ? h - mean : 0.f;
@@ -1430,11 +1398,16 @@ struct Layer {
     uint4 *wh_f = nullptr, *wh_b = nullptr;   // precision 0: fp16 two-piece operand images (forward, data gradient) and their scale
     float* wh_scale = nullptr;
     float* wb = nullptr;                   // precision 1: flipped + transposed weights of the data gradient
+    int ph = 0, pw = 0;                    // the plane of z as the size-following code reads it: S x S at 80x80, the level's (h, w) of TrainAnyGeom elsewhere
 };
 
 struct Trainer {
     trexhip_ctx* ctx = nullptr;
     int classes = 0, CH = 1, max_n = 0;
+    int W = IMG, H = IMG;                // individual_image_size of the blob
+    bool any = false;                    // not 80x80: the chain of train_any.hip on the geometry below (exact fp32 whatever `precision` says)
+    TrainAnyGeom geom{};
+    float* hsum = nullptr;               // any: fc1's partial planes added up (k_tany_fc1_sum), what the head reads as its one plane
     trexhip_train_params p{};
     int64_t step = 0;
     size_t off[T_COUNT + 1] = {}, cnt[T_COUNT] = {};
@@ -1463,12 +1436,12 @@ struct Trainer {
 };
 
 // index inside the tensor in the kernels' layout of element `i` of the torch layout
-static size_t to_internal(int t, size_t i, int CH) {
+static size_t to_internal(int t, size_t i, int CH, size_t P /*fc1 positions, (H/8)(W/8)*/) {
     switch (t) {
         case T_C1W: { const size_t tap = i % 25, c = (i / 25) % CH, co = i / (25 * (size_t)CH); return (c * 25 + tap) * 16 + co; }
         case T_C2W: { const size_t tap = i % 25, ci = (i / 25) % 16, co = i / 400; return (tap * 16 + ci) * 64 + co; }
         case T_C3W: { const size_t tap = i % 25, ci = (i / 25) % 64, co = i / 1600; return (((ci / 32) * 25 + tap) * 32 + ci % 32) * 128 + co; }
-        case T_F1W: { const size_t k = i % FC1_K, o = i / FC1_K, c = k / FC1_POS, hw = k % FC1_POS; return (hw * 128 + c) * HID + o; }
+        case T_F1W: { const size_t K = 128 * P, k = i % K, o = i / K, c = k / P, hw = k % P; return (hw * 128 + c) * HID + o; }
         default: return i;
     }
 }
@@ -1500,13 +1473,14 @@ static void bn_forward(Trainer* t, hipStream_t s, const Layer& L, int n, const u
     float* mean = t->stat + L.slot * 512;
     float* invstd = mean + 128;
     if (train) {
-        const size_t rows = (size_t)n * L.S * L.S;
+        const size_t rows = (size_t)n * L.ph * L.pw;                  // every pixel counts in the statistics, the odd last row / column too
         if (!partials) hipLaunchKernelGGL(L.bn_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.z, rows, t->red);
         hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_STATS>), dim3(L.C), dim3(256), 0, s, t->red, partials ? partials : RED_BLOCKS, L.C,
                            FinArgs{(double)rows, t->p.bn_momentum, mean, invstd, P + o[L.rm], P + o[L.rv], t->bad_target});
     } else {
         hipLaunchKernelGGL(k_t_bn_from_running, dim3(1), dim3(128), 0, s, P + o[L.rm], P + o[L.rv], L.C, mean, invstd);
     }
+    if (t->any) { tany_bn_pool(s, L.C, L.z, mean, invstd, P + o[L.g], P + o[L.be], keep + (size_t)n * L.keep_off, scale, L.a, n, L.ph, L.pw); return; }
     const size_t total = (size_t)n * (L.S / 2) * (L.S / 2) * (L.C / 4);
     hipLaunchKernelGGL(L.bn_pool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L.z, mean, invstd, P + o[L.g], P + o[L.be], keep + (size_t)n * L.keep_off,
                        scale, L.a, n, L.S);
@@ -1520,11 +1494,15 @@ static int bn_backward(Trainer* t, hipStream_t s, const Layer& L, int n, const u
     float* invstd = mean + 128;
     float* sums = mean + 256;
     const uint8_t* kp = keep + (size_t)n * L.keep_off;
-    hipLaunchKernelGGL(L.pool_bwd_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.S, t->red);
+    if (t->any) tany_pool_bwd_stats(s, L.C, RED_BLOCKS, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.ph, L.pw, t->red);
+    else hipLaunchKernelGGL(L.pool_bwd_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.S, t->red);
     hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_BWD>), dim3(L.C), dim3(256), 0, s, t->red, RED_BLOCKS, L.C,
                        FinArgs{0.0, 0.f, sums, t->G + o[L.g], t->G + o[L.be], nullptr, nullptr});
+    const float inv_count = (float)(1.0 / ((double)n * L.ph * L.pw));      // the means run over every pixel of the plane
+    if (t->any)
+        return tany_bn_bwd(s, L.C, BWD_BLOCKS, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, sums, inv_count, n, L.ph, L.pw,
+                           t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128);
     const size_t total = (size_t)n * (L.S / 2) * (L.S / 2) * (L.C / 4);
-    const float inv_count = (float)(1.0 / ((double)n * L.S * L.S));
     // whole rounds: every workgroup takes the same number of elements, all of them resident at once
     const unsigned nb0 = (unsigned)((total + 255) / 256), per = (nb0 + BWD_BLOCKS - 1) / BWD_BLOCKS, nb = (nb0 + per - 1) / per;
     hipLaunchKernelGGL(L.bn_bwd, dim3(nb), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, sums, inv_count, n, L.S,
@@ -1553,8 +1531,16 @@ static void block_backward(Trainer* t, const Streams& q, const Layer& L, int n, 
     const int nb = bn_backward(t, q.s, L, n, keep, scale);
     fork(t, q, L.dz_event);
     bias_finalize(t, q.w, L, nb);
-    if (!L.wgrad.fn) return;
+    if (L.slot == 0) return;
     const Layer& below = t->L[L.slot - 1];
+    if (t->any) {
+        const int shares = t->geom.wg_shares(L.slot, n);
+        tany_wgrad(q.w, t->geom, L.slot, n, below.a, L.z, t->part);
+        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w]);
+        hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * L.dgrad.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, L.dgrad.co, L.dgrad.cic, L.wb);
+        tany_conv_dgrad(q.s, t->geom, L.slot, n, L.z, L.wb, below.da);
+        return;
+    }
     const WgradKernel& g = L.wgrad;
     const int shares = std::min(n * g.units, g.max_shares);
     hipLaunchKernelGGL(g.fn, dim3(g.types, shares), dim3(g.threads), g.lds, q.w, below.a, L.z, t->part, n);
@@ -1591,7 +1577,7 @@ static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int
     float* P = t->P;
     const size_t* o = t->off;
     const Layer* L = t->L;
-    const bool h2 = t->p.precision == 0;
+    const bool h2 = t->p.precision == 0 && !t->any;
     hipStream_t es = s == hipStreamLegacy ? nullptr : s;
     if (h2) {
         // this step's weights as fp16 two-piece operand images (both directions); conv2 is the first to need them
@@ -1600,22 +1586,26 @@ static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int
                                L[i].dgrad.cic, L[i].dgrad.co, L[i].wh_f, L[i].wh_b, L[i].wh_scale);
         if (side) (void)hipEventRecord(t->ev[EV_PACKED], side);
     }
-    hipLaunchKernelGGL(t->conv1, dim3(n * C1_BPC), dim3(320), 0, s, x, P + o[T_C1W], P + o[T_C1B], L[0].z, train ? t->red : nullptr);
+    if (t->any) tany_conv1(s, t->geom, n, x, P + o[T_C1W], P + o[T_C1B], L[0].z);
+    else hipLaunchKernelGGL(t->conv1, dim3(n * C1_BPC), dim3(320), 0, s, x, P + o[T_C1W], P + o[T_C1B], L[0].z, train ? t->red : nullptr);
     if (side && t->masks_on_side) (void)hipStreamWaitEvent(es, t->ev[EV_MASKS], 0);
-    bn_forward(t, s, L[0], n, keep, scale, train, n * C1_BPC);
+    bn_forward(t, s, L[0], n, keep, scale, train, t->any ? 0 : n * C1_BPC);      // (any: no column sums from the convolution, k_t_bn_stats reads z)
     if (h2 && side) (void)hipStreamWaitEvent(es, t->ev[EV_PACKED], 0);
     for (int i = 1; i < 3; ++i) {
         const ConvKernel& k = L[i].fwd;                              // the fp16 kernel leaves its BN column sums, the fp32 one does not
-        if (k.h2) hipLaunchKernelGGL(k.h2, dim3(n * k.bpc), dim3(512), k.lds, s, L[i - 1].a, L[i].wh_f, P + o[L[i].b], L[i].z, L[i].wh_scale, train ? t->red : nullptr);
+        if (t->any) tany_conv_fwd(s, t->geom, i, n, L[i - 1].a, P + o[L[i].w], P + o[L[i].b], L[i].z);
+        else if (k.h2) hipLaunchKernelGGL(k.h2, dim3(n * k.bpc), dim3(512), k.lds, s, L[i - 1].a, L[i].wh_f, P + o[L[i].b], L[i].z, L[i].wh_scale, train ? t->red : nullptr);
         else hipLaunchKernelGGL(k.f32, dim3(n * k.bpc), dim3(512), k.lds, s, L[i - 1].a, P + o[L[i].w], P + o[L[i].b], L[i].z);
         bn_forward(t, s, L[i], n, keep, scale, train, k.h2 ? n * k.bpc : 0);
     }
-    hipLaunchKernelGGL(k_t_fc1, dim3(FC1_POS, (n + 63) / 64), dim3(256), 0, s, L[2].a, P + o[T_F1W], t->hpart, n);
+    if (t->any) tany_fc1(s, t->geom, n, L[2].a, P + o[T_F1W], t->hpart, t->hsum);
+    else hipLaunchKernelGGL(k_t_fc1, dim3(FC1_POS, (n + 63) / 64), dim3(256), 0, s, L[2].a, P + o[T_F1W], t->hpart, n);
+    const float* planes = t->any ? t->hsum : t->hpart;
     if (probs) {
-        hipLaunchKernelGGL(k_t_head_eval, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], P + o[T_F2W], P + o[T_F2B], t->classes, probs);
+        hipLaunchKernelGGL(t->any ? &k_t_head_eval<1> : &k_t_head_eval<FC1_POS>, dim3(n), dim3(128), 0, s, planes, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], P + o[T_F2W], P + o[T_F2B], t->classes, probs);
         return;
     }
-    hipLaunchKernelGGL(k_t_head, dim3(n), dim3(128), 0, s, t->hpart, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], keep + (size_t)n * KEEP_OFF[3], scale, P + o[T_F2W],
+    hipLaunchKernelGGL(t->any ? &k_t_head<1> : &k_t_head<FC1_POS>, dim3(n), dim3(128), 0, s, planes, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], keep + (size_t)n * KEEP_OFF[3], scale, P + o[T_F2W],
                        P + o[T_F2B], targets, t->classes, t->xhat, t->hd, t->dl, t->dy, t->dh, t->loss, t->correct, t->bad_target);
 }
 
@@ -1652,7 +1642,7 @@ static int trainer_predict(Trainer* t, const uint8_t* d_crops, int n, float* d_p
     TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)std::min(n, t->max_n) * KEEP_ROW, s));       // nothing dropped
     for (int at = 0; at < n; at += t->max_n) {
         const int m = std::min(t->max_n, n - at);
-        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * IMG_PIX * t->CH, nullptr, m, nullptr, m, IMG, IMG, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
+        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * t->H * t->W * t->CH, nullptr, m, nullptr, m, t->W, t->H, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
         if (rc != TREXHIP_OK) return rc;
         trainer_forward(t, s, t->x_stage, nullptr, m, t->keep, 1.0f, false, nullptr, d_probs + (size_t)at * t->classes);
     }
@@ -1689,13 +1679,16 @@ static int trainer_step(Trainer* t, const float* x, const int32_t* targets, int 
         hipLaunchKernelGGL(k_t_head_grads, dim3((cnt + 255) / 256), dim3(256), 0, w, t->dl, t->hd, t->dy, t->xhat, t->dh, n, t->classes, G + o[T_F2W], G + o[T_F2B],
                            G + o[T_LNG], G + o[T_LNB], G + o[T_F1B]);
     }
-    hipLaunchKernelGGL(k_t_fc1_wgrad, dim3(FC1_POS), dim3(256), 0, w, t->L[2].a, t->dh, G + o[T_F1W], n);
+    if (t->any) tany_fc1_wgrad(w, t->geom, n, t->L[2].a, t->dh, G + o[T_F1W]);
+    else hipLaunchKernelGGL(k_t_fc1_wgrad, dim3(FC1_POS), dim3(256), 0, w, t->L[2].a, t->dh, G + o[T_F1W], n);
     hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, w, t->loss, t->correct, n, t->out2);
-    hipLaunchKernelGGL(k_t_fc1_dgrad, dim3(FC1_POS, (n + 31) / 32), dim3(256), 0, s, t->dh, P + o[T_F1W], t->L[2].da, n);
+    if (t->any) tany_fc1_dgrad(s, t->geom, n, t->dh, P + o[T_F1W], t->L[2].da);
+    else hipLaunchKernelGGL(k_t_fc1_dgrad, dim3(FC1_POS, (n + 31) / 32), dim3(256), 0, s, t->dh, P + o[T_F1W], t->L[2].da, n);
     for (int i = 2; i >= 0; --i) block_backward(t, q, t->L[i], n, keep, scale);
     if (forked) (void)hipEventRecord(t->ev[EV_SIDE_DONE], w);               // the side stream's last piece of this step
-    hipLaunchKernelGGL(t->wgrad1, dim3(n * WG1_BPC), dim3(512), 0, s, x, t->L[0].z, t->part1);
-    hipLaunchKernelGGL(k_t_reduce, dim3((t->CH * 400 + 15) / 16), dim3(256), 0, s, t->part1, n * WG1_BPC, t->CH * 400, G + o[T_C1W]);
+    if (t->any) tany_wgrad1(s, t->geom, n, x, t->L[0].z, t->part1);
+    else hipLaunchKernelGGL(t->wgrad1, dim3(n * WG1_BPC), dim3(512), 0, s, x, t->L[0].z, t->part1);
+    hipLaunchKernelGGL(k_t_reduce, dim3((t->CH * 400 + 15) / 16), dim3(256), 0, s, t->part1, n * (t->any ? t->geom.wg1_tiles : WG1_BPC), t->CH * 400, G + o[T_C1W]);
     if (forked) (void)hipStreamWaitEvent(q.es, t->ev[EV_SIDE_DONE], 0);     // join: every gradient is in G
     // ---- optimizer
     t->step += 1;
@@ -1730,7 +1723,10 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     *out = nullptr;
     WeightBlob wb;
     const int prc = parse_weight_blob(blob, bytes, "trexhip_trainer_create", &wb, [](int W, int H) -> int {
-        if (W != IMG || H != IMG) { set_error("trexhip_trainer_create: only individual_image_size 80x80 is supported"); return TREXHIP_E_UNSUPPORTED; }
+        if (W < 8 || W > 256 || H < 8 || H > 256) {               // the range of trexhip_load_weights
+            set_error("trexhip_trainer_create: individual_image_size " + std::to_string(W) + "x" + std::to_string(H) + " is outside 8..256 x 8..256");
+            return TREXHIP_E_UNSUPPORTED;
+        }
         return TREXHIP_OK;
     });
     if (prc != TREXHIP_OK) return prc;
@@ -1745,14 +1741,17 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     if (hipSetDevice(ctx->p.device) != hipSuccess) { set_error("trexhip_trainer_create: hipSetDevice failed"); return TREXHIP_E_DEVICE; }
     Trainer* t = new Trainer();
     t->ctx = ctx; t->classes = classes; t->CH = CH; t->max_n = p->max_batch; t->p = *p;
+    t->W = wb.W; t->H = wb.H;
+    t->any = wb.W != IMG || wb.H != IMG;
+    t->geom = train_any_geom(wb.W, wb.H, CH);
     size_t at = 0;
     for (int k = 0; k < T_COUNT; ++k) {
-        t->off[k] = at; t->cnt[k] = weight_tensor_count(k, classes, CH, IMG, IMG);
+        t->off[k] = at; t->cnt[k] = weight_tensor_count(k, classes, CH, t->W, t->H);
         at += (t->cnt[k] + 63) / 64 * 64;
     }
     t->off[T_COUNT] = at; t->total = at;
     // ---- the three blocks and their kernel instances.  The convolutions' precision is chosen here, once per role
-    const bool h2 = p->precision == 0;
+    const bool h2 = p->precision == 0 && !t->any;      // every other size runs the exact-fp32 chain at both precisions
     Layer* L = t->L;
     // (k_t_bn_stats<16> is never launched: conv1 always leaves its column sums.  It stays instantiated because the compiler lays out the epilogue
     // of k_t_pool_bwd_stats<16>, which shares block_columns<16, 2> with it, in another order without it)
@@ -1760,30 +1759,40 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     L[0] = {16,  CH, IMG,     T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, KEEP_OFF[0], &k_t_bn_stats<16>, &k_t_bn_pool<16>, &k_t_pool_bwd_stats<16>, &k_t_bn_bwd<16>};
     L[1] = {64,  16, IMG / 2, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, EV_DZ2, 1, KEEP_OFF[1], &k_t_bn_stats<64>, &k_t_bn_pool<64>, &k_t_pool_bwd_stats<64>, &k_t_bn_bwd<64>};
     L[2] = {128, 64, IMG / 4, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3, EV_DZ3, 2, KEEP_OFF[2], &k_t_bn_stats<128>, &k_t_bn_pool<128>, &k_t_pool_bwd_stats<128>, &k_t_bn_bwd<128>};
-    t->conv1 = CH == 1 ? &k_t_conv1<1> : &k_t_conv1<3>;
-    t->wgrad1 = CH == 1 ? &k_t_wgrad1<1> : &k_t_wgrad1<3>;
-    // conv3 forward in 10-row bands: 2 blocks per crop (a training batch is 64..128 crops, the chip has 256 CUs; 4-row bands measured no faster).
-    // conv2's data gradient has 16 output channels: 16x16x4 tiles in fp32, 16 of a 32-wide tile's channels real in fp16
-    L[1].fwd = h2 ? conv_h2<16, 64, 40, 20, 16, 64>() : conv_f32<16, 64, 40, 20, 16, 64>();
-    L[2].fwd = h2 ? conv_h2<64, 128, 20, 10, 32, 128>() : conv_f32<64, 128, 20, 10, 32, 128>();
-    L[1].dgrad = h2 ? conv_h2<64, 32, 40, 20, 16, 16>() : conv_f32_n16<64, 40, 20, 16>();
-    L[2].dgrad = h2 ? conv_h2<128, 64, 20, 10, 32, 64>() : conv_f32<128, 64, 20, 10, 32, 64>();
-    // weight gradients.  fp32: conv2 block type = kernel row (5 types), unit = 5 rows of a crop; conv3 block type = kernel row x 32-channel half x
-    // 64-channel half (20 types), unit = 10 rows; 5 x 51 = 255 and 20 x 12 = 240 workgroups: one round on 256 CUs.  fp16: conv2 1 type x 256 shares,
-    // conv3 4 x 64
-    L[1].wgrad = h2 ? wgrad_h2<16, 64, 40, 16, 10>(256) : wgrad_f32<16, 64, 40, 16, 64, 3, 5>(51);
-    L[2].wgrad = h2 ? wgrad_h2<64, 128, 20, 32, 10>(64) : wgrad_f32<64, 128, 20, 32, 64, 5, 10>(12);
-    L[1].pack_blocks = 10; L[2].pack_blocks = 50;
+    for (int i = 0; i < 3; ++i) { L[i].ph = t->any ? t->geom.L[i].h : L[i].S; L[i].pw = t->any ? t->geom.L[i].w : L[i].S; }
+    if (t->any) {
+        // the generic chain (train_any.hip): the BN / pool kernels, the convolutions' three roles and fc1 follow t->geom; what the shared kernels
+        // (k_t_wgrad_reduce, k_t_repack_bwd) read of a convolution is its weight image: the parameter layout's chunk, the data gradient's chunk and tile
+        for (int i = 0; i < 3; ++i) L[i].S = 0;
+        L[1].fwd.cic = 16; L[1].dgrad.cic = 16; L[1].dgrad.co = 32;        // conv2's data gradient: 16 real channels in a 32-wide tile
+        L[2].fwd.cic = 32; L[2].dgrad.cic = 32; L[2].dgrad.co = 64;
+    } else {
+        t->conv1 = CH == 1 ? &k_t_conv1<1> : &k_t_conv1<3>;
+        t->wgrad1 = CH == 1 ? &k_t_wgrad1<1> : &k_t_wgrad1<3>;
+        // conv3 forward in 10-row bands: 2 blocks per crop (a training batch is 64..128 crops, the chip has 256 CUs; 4-row bands measured no faster).
+        // conv2's data gradient has 16 output channels: 16x16x4 tiles in fp32, 16 of a 32-wide tile's channels real in fp16
+        L[1].fwd = h2 ? conv_h2<16, 64, 40, 20, 16, 64>() : conv_f32<16, 64, 40, 20, 16, 64>();
+        L[2].fwd = h2 ? conv_h2<64, 128, 20, 10, 32, 128>() : conv_f32<64, 128, 20, 10, 32, 128>();
+        L[1].dgrad = h2 ? conv_h2<64, 32, 40, 20, 16, 16>() : conv_f32_n16<64, 40, 20, 16>();
+        L[2].dgrad = h2 ? conv_h2<128, 64, 20, 10, 32, 64>() : conv_f32<128, 64, 20, 10, 32, 64>();
+        // weight gradients.  fp32: conv2 block type = kernel row (5 types), unit = 5 rows of a crop; conv3 block type = kernel row x 32-channel half x
+        // 64-channel half (20 types), unit = 10 rows; 5 x 51 = 255 and 20 x 12 = 240 workgroups: one round on 256 CUs.  fp16: conv2 1 type x 256 shares,
+        // conv3 4 x 64
+        L[1].wgrad = h2 ? wgrad_h2<16, 64, 40, 16, 10>(256) : wgrad_f32<16, 64, 40, 16, 64, 3, 5>(51);
+        L[2].wgrad = h2 ? wgrad_h2<64, 128, 20, 32, 10>(64) : wgrad_f32<64, 128, 20, 32, 64, 5, 10>(12);
+        L[1].pack_blocks = 10; L[2].pack_blocks = 50;
+    }
     // ---- memory
     const size_t n = (size_t)t->max_n;
     int rc = TREXHIP_OK;
     const char* who = "trexhip_trainer_create";
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
     TRY(t->mem.device(&t->P, at, who)); TRY(t->mem.device(&t->G, at, who)); TRY(t->mem.device(&t->M, at, who)); TRY(t->mem.device(&t->V, at, who));
-    size_t part_floats = 0;
+    size_t part_floats = t->any ? t->geom.part_floats() : 0;
     for (int i = 0; i < 3; ++i) {
-        const size_t act = n * L[i].S * L[i].S * L[i].C;                      // z; pooled: a quarter of it
-        TRY(t->mem.device(&L[i].z, act, who)); TRY(t->mem.device(&L[i].a, act / 4, who)); TRY(t->mem.device(&L[i].da, act / 4, who));
+        const size_t act = n * L[i].ph * L[i].pw * L[i].C;                      // z; pooled: a quarter of it at 80x80, the floored plane elsewhere
+        const size_t pooled = n * (L[i].ph / 2) * (L[i].pw / 2) * L[i].C;
+        TRY(t->mem.device(&L[i].z, act, who)); TRY(t->mem.device(&L[i].a, pooled, who)); TRY(t->mem.device(&L[i].da, pooled, who));
         part_floats = std::max(part_floats, (size_t)L[i].wgrad.max_shares * 25 * L[i].CI * L[i].C);
     }
     if (h2) {                                                                 // the weight images of the trainer's own precision
@@ -1794,23 +1803,24 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     } else {
         TRY(t->mem.device(&L[2].wb, (size_t)4 * 25 * 32 * 64, who)); TRY(t->mem.device(&L[1].wb, (size_t)2 * 25 * 32 * 32, who));
     }
-    TRY(t->mem.device(&t->part, part_floats, who)); TRY(t->mem.device(&t->part1, n * WG1_BPC * CH * 400, who)); TRY(t->mem.device(&t->red_bias, (size_t)3 * BWD_BLOCKS * 128, who));
+    TRY(t->mem.device(&t->part, part_floats, who)); TRY(t->mem.device(&t->part1, t->any ? t->geom.part1_floats(n) : n * WG1_BPC * CH * 400, who)); TRY(t->mem.device(&t->red_bias, (size_t)3 * BWD_BLOCKS * 128, who));
     TRY(t->mem.device(&t->stat, (size_t)3 * 512, who));
-    TRY(t->mem.device(&t->hpart, n * FC1_POS * HID, who)); TRY(t->mem.device(&t->xhat, n * HID, who)); TRY(t->mem.device(&t->hd, n * HID, who));
+    TRY(t->mem.device(&t->hpart, n * t->geom.P * HID, who)); if (t->any) TRY(t->mem.device(&t->hsum, n * HID, who)); TRY(t->mem.device(&t->xhat, n * HID, who)); TRY(t->mem.device(&t->hd, n * HID, who));
     TRY(t->mem.device(&t->dl, n * classes, who)); TRY(t->mem.device(&t->dy, n * HID, who)); TRY(t->mem.device(&t->dh, n * HID, who));
     TRY(t->mem.device(&t->loss, n, who)); TRY(t->mem.device(&t->correct, n, who)); TRY(t->mem.device(&t->out2, 2, who)); TRY(t->mem.device(&t->bad_target, 2, who));
     TRY(t->mem.device(&t->red, std::max((size_t)BWD_BLOCKS * 2 * 128, n * 640), who));   // conv1 leaves 20 n x 2 x 16 partials, conv2 / conv3 2 n x 2 x C
     TRY(t->mem.device(&t->keep, n * KEEP_ROW, who));
-    TRY(t->mem.device(&t->x_stage, n * IMG_PIX * CH, who)); TRY(t->mem.device(&t->y_stage, n, who)); TRY(t->mem.device(&t->keep_stage, n * KEEP_ROW, who));
+    TRY(t->mem.device(&t->x_stage, n * t->H * t->W * CH, who)); TRY(t->mem.device(&t->y_stage, n, who)); TRY(t->mem.device(&t->keep_stage, n * KEEP_ROW, who));
     if (rc == TREXHIP_OK && hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess) { set_error("trexhip_trainer_create: no second stream"); rc = TREXHIP_E_DEVICE; }
     for (hipEvent_t& e : t->ev)
         if (rc == TREXHIP_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("trexhip_trainer_create: no event"); rc = TREXHIP_E_DEVICE; }
     TRY(trainer_attrs(t));
+    if (t->any) TRY(tany_attrs());
 #undef TRY
     if (rc != TREXHIP_OK) { trainer_free(t); return rc; }
     std::vector<float> host(at, 0.f);
     for (int k = 0; k < T_COUNT; ++k)
-        for (size_t i = 0; i < t->cnt[k]; ++i) host[t->off[k] + to_internal(k, i, CH)] = wb.t[k][i];
+        for (size_t i = 0; i < t->cnt[k]; ++i) host[t->off[k] + to_internal(k, i, CH, (size_t)(t->H / 8) * (t->W / 8))] = wb.t[k][i];
     bool ok = hipMemcpy(t->P, host.data(), at * 4, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemset(t->bad_target, 0, 8) == hipSuccess;
     ok = ok && hipMemset(t->G, 0, at * 4) == hipSuccess && hipMemset(t->M, 0, at * 4) == hipSuccess && hipMemset(t->V, 0, at * 4) == hipSuccess;
@@ -1834,6 +1844,12 @@ int trexhip_trainer_set_lr(trexhip_trainer* h, float lr) {
 
 int64_t trexhip_trainer_steps(trexhip_trainer* h) { return h ? h->t->step : -1; }
 
+int trexhip_trainer_image_size(trexhip_trainer* h, int32_t* width, int32_t* height) {
+    if (!h || !width || !height) { set_error("trexhip_trainer_image_size: null argument"); return TREXHIP_E_INVALID; }
+    *width = h->t->W; *height = h->t->H;
+    return TREXHIP_OK;
+}
+
 // what every batch entry point checks first: the handle, its two pointers, 1 <= n <= max_batch (any_n: no upper bound, the call chunks)
 static int check_batch(const char* who, const trexhip_trainer* h, const void* a, const void* b, int n, bool any_n = false) {
     if (!h || !a || !b) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
@@ -1850,7 +1866,7 @@ static int stage_batch(const char* who, const trexhip_trainer* h, const float* i
         if (targets[i] < 0 || targets[i] >= t->classes) { set_error(std::string(who) + ": target class out of range"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
     hipStream_t s = t->ctx->stream;
-    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * IMG_PIX * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
+    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * t->H * t->W * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
     TH_CHECK_HIP(hipMemcpyAsync(t->y_stage, targets, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (keep_masks) TH_CHECK_HIP(hipMemcpyAsync(t->keep_stage, keep_masks, (size_t)n * KEEP_ROW, hipMemcpyHostToDevice, s));
     return TREXHIP_OK;
@@ -1895,17 +1911,17 @@ int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float
     const float* src = kind == 0 ? t->P : kind == 1 ? t->G : kind == 2 ? t->M : t->V;
     std::vector<float> tmp(count);
     TH_CHECK_HIP(hipMemcpy(tmp.data(), src + t->off[tensor], count * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < count; ++i) out[i] = tmp[to_internal(tensor, i, t->CH)];
+    for (size_t i = 0; i < count; ++i) out[i] = tmp[to_internal(tensor, i, t->CH, (size_t)(t->H / 8) * (t->W / 8))];
     return TREXHIP_OK;
 }
 
 int trexhip_trainer_export(trexhip_trainer* h, void* blob, size_t capacity, size_t* bytes) {
     if (!h || !blob) { set_error("trexhip_trainer_export: null argument"); return TREXHIP_E_INVALID; }
     Trainer* t = h->t;
-    const size_t need = trexhip_weight_blob_bytes(t->classes, t->CH);
+    const size_t need = weight_blob_bytes(t->classes, t->CH, t->W, t->H);
     if (bytes) *bytes = need;
-    if (capacity < need) { set_error("trexhip_trainer_export: buffer too small (trexhip_weight_blob_bytes)"); return TREXHIP_E_CAPACITY; }
-    write_weight_blob_header(blob, t->classes, IMG, IMG, t->CH);
+    if (capacity < need) { set_error("trexhip_trainer_export: buffer too small (the bytes of the blob the trainer was created from)"); return TREXHIP_E_CAPACITY; }
+    write_weight_blob_header(blob, t->classes, t->W, t->H, t->CH);
     float* dst = reinterpret_cast<float*>(static_cast<char*>(blob) + 32);
     for (int k = 0; k < T_COUNT; ++k) {
         const int rc = trexhip_trainer_read(h, k, 0, dst, t->cnt[k]);

@@ -120,7 +120,8 @@ struct HipVINetwork {
     // (visual_recognition_torch.py:1100-1158) is what a Trainer step replaces; epochs, validation, the learning-rate schedule and
     // early stopping stay with the caller, as they are host logic in the reference too.
     struct Trainer {
-        // weights: the same blob as load_weights (the reference starts from the network's current state_dict)
+        // weights: the same blob as load_weights (the reference starts from the network's current state_dict), at any individual_image_size it
+        // loads; batches and the blob of weights() have the blob's size (trexhip_trainer_image_size)
         // exact_fp32: conv2 / conv3 forward and data gradients on the fp32 matrix cores instead of the fp16 two-piece split arithmetic
         // (trexhip_train_params::precision; same parity bars, 1.6 instead of 1.2 ms per 128-sample step)
         Trainer(HipVINetwork& net, const void* blob, size_t bytes, int max_batch, float learning_rate = 0.001f, uint64_t seed = 0, bool exact_fp32 = false) : _net(net) {
@@ -130,6 +131,7 @@ struct HipVINetwork {
             check(trexhip_trainer_create(net._ctx, blob, bytes, &p, &_t));
             std::memcpy(&_classes, static_cast<const char*>(blob) + 8, 4);
             std::memcpy(&_channels, static_cast<const char*>(blob) + 20, 4);
+            _bytes = bytes;
         }
         ~Trainer() { trexhip_trainer_destroy(_t); }
         Trainer(const Trainer&) = delete;
@@ -149,7 +151,7 @@ struct HipVINetwork {
         void set_learning_rate(float lr) { check(trexhip_trainer_set_lr(_t, lr)); }          // ReduceLROnPlateau lives with the caller
         int64_t steps() const { return trexhip_trainer_steps(_t); }
         std::vector<uint8_t> weights() const {                                                // what the reference serialises back (state_dict)
-            std::vector<uint8_t> blob(trexhip_weight_blob_bytes(_classes, _channels));
+            std::vector<uint8_t> blob(_bytes);                                                // same classes, channels and size as the blob it started from
             size_t got = 0;
             check(trexhip_trainer_export(_t, blob.data(), blob.size(), &got));
             return blob;
@@ -159,6 +161,7 @@ struct HipVINetwork {
         HipVINetwork& _net;
         trexhip_trainer* _t = nullptr;
         int32_t _classes = 0, _channels = 1;
+        size_t _bytes = 0;
     };
 
 private:

@@ -250,7 +250,8 @@ class ResidentValidation:
     """What ValidationCallback.evaluate measures at the end of an epoch (visual_recognition_torch.py:493-543), with the samples in HBM and
     the weights where they are, in the trainer: no export, no second copy of the network, one device-to-host copy of the results.
 
-    val_crops_uint8 (N, 80, 80, C) uint8 + val_targets (N,): the validation images (X_test / Y_test); unique_crops_uint8 (M, 80, 80, C) +
+    val_crops_uint8 (N, H, W, C) uint8 at the trainer's individual_image_size (trainer.height, trainer.width) + val_targets (N,): the validation
+    images (X_test / Y_test); unique_crops_uint8 (M, H, W, C) +
     frame_ranges (F, 2) = (start, end) rows of it per frame, in frame order: what Accumulation hands calculate_uniqueness (_disc_images,
     _disc_frame_map, ui/Accumulation.cpp:900-901).  Arrays are uploaded once; like ResidentLoader, device addresses are taken as they
     are with count= (validation pool, targets then a device address of int32) and unique_count=.  Either part may be missing.
@@ -264,6 +265,7 @@ class ResidentValidation:
     def __init__(self, trainer, seg, val_crops_uint8, val_targets, unique_crops_uint8=None, frame_ranges=None, count=None, unique_count=None, callback=None):
         self.trainer, self.seg, self.callback = trainer, seg, callback
         self.classes, self.channels = trainer.classes, trainer.channels
+        self.height, self.width = trainer.height, trainer.width
         self._owned = []
         self.d_val, self.n_val = self._pool(val_crops_uint8, count)
         self.d_val_targets = 0
@@ -301,8 +303,8 @@ class ResidentValidation:
                 raise ValueError("a device pool needs its count")
             return int(crops), int(count)
         x = np.asarray(crops)
-        if x.dtype != np.uint8 or x.ndim != 4 or tuple(x.shape[1:]) != (80, 80, self.channels):
-            raise ValueError(f"crops must be uint8 (N, 80, 80, {self.channels}), got {x.dtype} {x.shape}")
+        if x.dtype != np.uint8 or x.ndim != 4 or tuple(x.shape[1:]) != (self.height, self.width, self.channels):
+            raise ValueError(f"crops must be uint8 (N, {self.height}, {self.width}, {self.channels}), got {x.dtype} {x.shape}")
         if x.shape[0] == 0:
             return 0, 0
         d = self._alloc(x.nbytes)
@@ -383,6 +385,9 @@ class ResidentAverages:
             y = np.asarray(ids)
             if x.dtype != np.uint8 or x.ndim != 4:
                 raise ValueError(f"crops must be uint8 (N, H, W, C), got {x.dtype} {x.shape}")
+            owner = getattr(predict, "__self__", None)           # a trainer's predict_device reads crops of the trainer's own size
+            if hasattr(owner, "height") and tuple(x.shape[1:]) != (owner.height, owner.width, owner.channels):
+                raise ValueError(f"crops must be uint8 (N, {owner.height}, {owner.width}, {owner.channels}) for this trainer, got {x.shape}")
             if y.dtype.kind not in "iu" or y.shape != (x.shape[0],):
                 raise ValueError(f"ids must be integers of shape ({x.shape[0]},), got {y.dtype} {y.shape}")
             values, keys = np.unique(y, return_inverse=True)
