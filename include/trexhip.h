@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 14
+#define TREXHIP_ABI_VERSION 15
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -540,6 +540,16 @@ int trexhip_identify(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, float* p
  * trexhip_set_identity_precision was called since; zeros before the first call and behind a call in another precision mode.  No reference
  * counterpart (the reference's torch network has no range limit); either pointer may be NULL. */
 int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32_t* whole_batch);
+/* Identity crops are mostly background rows, and from 3200 one-channel 80 x 80 crops on (FP16X3) the fused conv1 + conv2 kernel computes only
+ * the passes (3 pooled rows of conv2's output) whose band of crop rows holds a non-zero byte; the rows of the other passes are copied from the
+ * image of an all-zero crop, made when the weights are loaded.  The crops' bytes decide, on the device, in every call; the results are the bits
+ * of a run that computes every pass.  A network whose all-zero crop leaves the fp16 range computes every pass.  The environment variable
+ * TREXHIP_CONV_GEOM (a test hook read when the context is created; every value gives identical results) switches this off with bit 27 (value
+ * 134217728); its bits 0-11 select the fp32-activation chain, bit 28 keeps conv1 and conv2 apart, bit 29 forces this kernel at any batch size,
+ * bit 30 the older fused kernel.
+ * What the last such call did (waits for the context's stream): *passes of the batch, *listed of them computed, *bytes_filled of conv2's output
+ * copied instead; zeros before the first such call.  No reference counterpart; any pointer may be NULL.  (ABI 15) */
+int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* listed, uint64_t* bytes_filled);
 
 /* ---- multi-GPU hand-off --------------------------------------------------------------------
  * Fixed-size per-blob identity table of the last batch, written to caller-owned device memory

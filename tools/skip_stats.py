@@ -1,0 +1,30 @@
+"""How much of conv1+conv2 the benchmark's crops need (dev tool, needs the GPU): one step of bench.py's default workload (config C4, 256 frames,
+gray, FP16X3) through the same Pipeline, then the device counters of the last identify call of lane 0 (trexhip_identify_skip_stats): passes of
+the batch, passes the role-split kernel computed, bytes of V3 rows filled from the empty crop's image -- and the crops' own row statistics, on
+the host.  Nothing here is timed.  One JSON line.
+   python tools/skip_stats.py"""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from trex_amd import synth, weights
+from trex_amd.pipeline import Pipeline
+
+W, H, n_ind, _ = synth.CONFIGS["C4"]
+B, classes = 256, 100
+frames, bg = synth.batch_torch("C4", B, torch.device("cuda:0"), t0=0)
+blob = weights.pack_blob(weights.synthetic_state(classes, 4242), classes)
+pipe = Pipeline(W, H, n_ind, B, classes, bg, blob)
+n = pipe.run(1, frames.data_ptr())
+torch.cuda.synchronize()
+lane = pipe.lanes[0]
+passes, listed, filled = lane.seg.skip_stats()
+crops = lane.crops[:passes * 3 // 20]
+rows = (crops != 0).any(dim=2)                       # [n][80]: the row holds a non-zero byte
+print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passes": passes, "passes_listed": listed,
+                  "fraction_listed": round(listed / max(passes, 1), 4), "v3_bytes_filled": filled, "v3_bytes": int(crops.shape[0]) * 20 * 10240,
+                  "mean_nonzero_rows_per_crop": round(float(rows.sum(1).float().mean()), 2),
+                  "empty_crops": int((~rows.any(1)).sum())}))
+pipe.close()

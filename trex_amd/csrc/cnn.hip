@@ -927,6 +927,7 @@ __global__ __launch_bounds__((WinoGeom<CI, CO, S, TPW>::NTHR), (TPW == 1 ? 2 : 1
 #include "cnn_conv3p.h"
 #include "cnn_fused12.h"
 #include "cnn_fused12rs.h"
+#include "cnn_skip_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // fc1: out[N][128] = act[N][K] * W[K][128] + b     (K = 12800, 100 real outputs)
@@ -1325,6 +1326,7 @@ template <class T>
 static int upload(Net* net, T** dst, float* inv, const ScaledImage& im) { *inv = im.inv; return upload(net, dst, im.v); }
 
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)      // a chain of allocations stops at its first failure
+static int make_empty_v3(trexhip_ctx* ctx, Net* net);
 // parse -> pack (cnn_weights.hip) -> upload
 int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     WeightBlob wb;
@@ -1368,6 +1370,7 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     TRY(upload(net, &net->lnb, wb.t[T_LNB], 100 * sizeof(float)));
     TRY(upload(net, &net->wf2t, pack_fc2(wb.t[T_F2W], classes)));
     TRY(upload(net, &net->bf2, wb.t[T_F2B], classes * sizeof(float)));
+    if (at80 && CH == 1) TRY(make_empty_v3(ctx, net));
     if (rc != TREXHIP_OK) { free_net(net); return rc; }
     ctx->net = net;
     return TREXHIP_OK;
@@ -1394,6 +1397,12 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->v2, N * 40 * V2_ROWB, who));
         TRY(B.device_bytes(&net->v3, N * 20 * V3_ROWB, who));
     }
+    if (net->v3e) {                            // the pass list of the role-split kernel
+        const size_t n_pass = (N * SkipGeom::V3_ROWS + SkipGeom::RPP - 1) / SkipGeom::RPP;
+        TRY(B.device_bytes(&net->skip_bands, N * sizeof(int2), who));
+        TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4, who));
+        TRY(B.device_bytes(&net->skip_list, (n_pass + SKIP_PAD) * 4, who));
+    }
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
     TRY(B.pinned(&net->h_probs, N * net->classes, who));
     if (rc != TREXHIP_OK) return rc;
@@ -1415,6 +1424,10 @@ static const ByChannels K_CONV1_MFMA{Kern(k_conv1_mfma, 256), Kern(k_conv1_mfma3
 static const ByChannels K_CONV1_WPRE{Kern(k_conv1_wpre<1>, 256), Kern(k_conv1_wpre<3>, 256)};
 static const Kern K_CONV12_RS(k_conv12_rs, 512, W12RGeom::LDS_BYTES);
 static const Kern K_CONV12_WPRE(k_conv12_wpre, 256, W12Geom::LDS_BYTES);
+static const Kern K_CROP_BANDS(k_crop_bands, 256);
+static const Kern K_PASS_COUNT(k_pass_count, SKIP_LB);
+static const Kern K_PASS_LIST(k_pass_list, SKIP_LB);
+static const Kern K_V3_FILL(k_v3_fill, 256);
 static const Kern K_CONV2_WPRE2(k_conv2_wpre2, 256, W2bGeom::LDS_BYTES);
 static const Kern K_CONV2_STREAM(k_conv5_stream<16, 64, 40, 8, 4>, 256, ConvGeomS<16, 64, 40, 8, 4>::LDS_BYTES);
 using GW3 = WinoGeom<64, 128, 20, 2>;
@@ -1491,6 +1504,26 @@ static void launch_rerun(const Pass& f) {
     launch_tail(f, g);
 }
 
+// The V3 image of an all-zero crop, once per loaded network: k_conv12_rs itself on one zero crop, every pass computed, its own range-flag word.
+// A net whose background activations leave the fp16 range raises that word, and the list kernels then list every pass (they read it on the device).
+static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
+    const char* who = "trexhip_load_weights";
+    uint8_t* zero = nullptr;
+    int rc = net->weights.device_bytes(&net->v3e, (size_t)SkipGeom::V3_ROWS * V3_ROWB, who);
+    if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->d_skip, SK_WORDS * 4, who);
+    if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&zero, SkipGeom::CROP_ROWS * 80, who);
+    if (rc != TREXHIP_OK) return rc;
+    const CnnPlan p = cnn_plan(80, 80, 1, TREXHIP_CNN_FP16X3, true, (1 << 29) | (1 << 27), 1, ctx->n_cus);
+    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV12_RS.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV12_RS.lds));
+    TH_CHECK_HIP(hipMemsetAsync(net->d_skip, 0, SK_WORDS * 4, ctx->stream));
+    TH_CHECK_HIP(hipMemsetAsync(zero, 0, SkipGeom::CROP_ROWS * 80, ctx->stream));
+    K_CONV12_RS(ctx->stream, p.conv2.grid, zero, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3e, net->inv2w, net->d_skip + SK_EMPTY_RANGE, 1,
+                net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr);
+    TH_CHECK_HIP(hipGetLastError());
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return TREXHIP_OK;
+}
+
 static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
     const Net& net = *static_cast<Net*>(ctx->net);
     if (!ctx->attr_cnn) {
@@ -1511,9 +1544,20 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         const bool pre = p.chain == Chain::ROLE_SPLIT || p.chain == Chain::FUSED_2WG || p.chain == Chain::TWO_KERNEL;      // conv2 writes V3
         stage_begin(ctx, TREXHIP_STAGE_CONV2);
         switch (p.chain) {
-        case Chain::ROLE_SPLIT: case Chain::FUSED_2WG:
-            (p.chain == Chain::ROLE_SPLIT ? K_CONV12_RS : K_CONV12_WPRE)(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w,
-                                                                        net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2), p.pk2, net.d_ovfc);
+        case Chain::ROLE_SPLIT:
+            if (p.skip) {      // which passes the crops need, and the rows of the others (cnn_skip_kernels.h); the decisions stay on the device
+                const int lb = ceil_div(p.conv2.items, SKIP_LB);
+                K_CROP_BANDS(s, ceil_div(n, 4), d_crops, n, net.skip_bands);
+                K_PASS_COUNT(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts);
+                K_PASS_LIST(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts, net.skip_list);
+                K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3));
+            }
+            K_CONV12_RS(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
+                        p.pk2, net.d_ovfc, p.skip ? net.skip_list : nullptr, p.skip ? net.d_skip + SK_LEN : nullptr);
+            break;
+        case Chain::FUSED_2WG:
+            K_CONV12_WPRE(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
+                          p.pk2, net.d_ovfc);
             break;
         case Chain::TWO_KERNEL:
             K_CONV2_WPRE2(s, p.conv2.grid, net.v2, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2));
@@ -1663,6 +1707,18 @@ int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32
     if (net->last_mode == TREXHIP_CNN_FP16X3) TH_CHECK_HIP(hipMemcpy(plan, net->ovf(OVF_PLAN), 8, hipMemcpyDeviceToHost));
     if (rerun_crops) *rerun_crops = plan[1] == 1u ? plan[0] : 0u;
     if (whole_batch) *whole_batch = plan[1] == 2u ? 1u : 0u;
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* listed, uint64_t* bytes_filled) {
+    if (!ctx || !ctx->net) { set_error("trexhip_identify_skip_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
+    Net* net = static_cast<Net*>(ctx->net);
+    uint32_t w[SK_WORDS] = {};
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    if (passes) *passes = w[SK_NPASS];
+    if (listed) *listed = w[SK_LEN];
+    if (bytes_filled) *bytes_filled = (uint64_t)w[SK_FILLED] * V3_ROWB;
     return TREXHIP_OK;
 }
 

@@ -21,6 +21,11 @@
 // 64 MFMAs (~3900 cycles wherever it runs): behind the 1770-cycle output transform it is exposed, the round grows from 10.3 k to 11.7 k cycles
 // (3.63 -> 3.68 ms).  Both roles are single instruction streams of ~8300-8500 cycles per round; the stages only decide how they line up.
 //
+// The kernel walks a LIST of passes when it is given one (cnn_skip.h: the passes whose crop rows are all background are left out, their V3 rows
+// are copied from an all-zero crop's image by k_v3_fill): a ticket is PK consecutive list slots, and a listed pass that does not follow its
+// predecessor starts like a ticket's first pass (all 10 rows produced, RS_NEXT).  Both roles read the same list entries, so they still execute
+// the same barriers.  Without a list slot i is pass i.
+//
 // LDS: the four operand planes (ring of NR = 10 row slots + the zero row, as before: P2 writes the ring in the stage where no tap reads it),
 // pbufE (consumer -> producer), pbufP (conv1's pooled activations of a chunk), the padded fp16 crop rows of a chunk: 93 KB.
 
@@ -81,7 +86,9 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                                                    const uint4* __restrict__ wp /*[5][8][2][2][64] x 16 B*/, const float* __restrict__ bias,
                                                    uint8_t* __restrict__ v3, const float out_scale, uint32_t* __restrict__ overflow,
                                                    const int n_crops, uint32_t* __restrict__ pass_ctr, const int PK /* consecutive passes per ticket */,
-                                                   uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */) {
+                                                   uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */,
+                                                   const int* __restrict__ list /* the passes to compute, in order (cnn_skip_kernels.h); null: every pass */,
+                                                   const uint32_t* __restrict__ list_len) {
     using G = W2bGeom;
     using F = W12RGeom;
     constexpr int CO = 64, S = 40;
@@ -91,9 +98,14 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
     const int rt = tid & 255, rw = wave & 3;                             // thread / wave index within the role
     const int total_pairs = n_crops * (S / 2);
     const int total_rows = n_crops * S;
-    const int n_pass = (total_pairs + G::RPP - 1) / G::RPP;
-    int pass = blockIdx.x * PK;
-    if (pass >= n_pass) return;
+    // a ticket is PK consecutive SLOTS; slot i stands for pass list[i], or for pass i without a list.  n_pass counts slots.  A read behind the
+    // last slot (a ticket drawn past the end, the look-ahead) is clamped to the one entry k_pass_list writes behind the list, and is never used
+    const int n_pass = list ? (int)*list_len : (total_pairs + G::RPP - 1) / G::RPP;
+    int slot = blockIdx.x * PK;
+    if (slot >= n_pass) return;
+#define RS_LIST(i_) list[(i_) < n_pass ? (i_) : n_pass]
+    int pass = list ? RS_LIST(slot) : slot;
+    int ahead = list ? RS_LIST(slot + 1) : 0;                             // list[slot + 1], read one round before it is needed
     // the next ticket's first pass: written by thread 0, read by every wave behind a barrier (a plain LDS word: through a volatile pointer into
     // the dynamic array it became a FLAT load with a vmcnt(0) behind it, and everything computed from it vector arithmetic)
     int* s_next = reinterpret_cast<int*>(ldsb + F::CTL_OFF);
@@ -134,11 +146,16 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
     } while (0)
     // the rows the NEXT pass needs that are not in the ring yet: [lo, hi); the next pass itself (the last pass of a ticket moves on to the
     // ticket drawn one round earlier).  Computed identically by every wave.
-#define RS_NEXT(pass_, res_hi_, next_, have_, lo_, hi_)                                                                          \
+#define RS_NEXT(pass_, res_hi_, nslot_, next_, have_, lo_, hi_)                                                                  \
     do {                                                                                                                         \
         const bool draw_ = tleft == 1;                                                                                           \
-        next_ = draw_ ? __builtin_amdgcn_readfirstlane(*s_next) : (pass_) + 1;                                                   \
-        have_ = next_ < n_pass;                                                                                                  \
+        nslot_ = draw_ ? __builtin_amdgcn_readfirstlane(*s_next) : slot + 1;                                                     \
+        have_ = nslot_ < n_pass;                                                                                                 \
+        next_ = nslot_;                                                                                                          \
+        if (list) {                                                                                                              \
+            next_ = draw_ ? RS_LIST(nslot_) : ahead;                                                                             \
+            ahead = RS_LIST(nslot_ + 1);                                                                                         \
+        }                                                                                                                        \
         lo_ = hi_ = 0;                                                                                                           \
         if (have_) {                                                                                                             \
             int qn_, nn_;                                                                                                        \
@@ -157,13 +174,15 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         // ------------------------------------------------------------------------------------------------------------------------
         __builtin_amdgcn_s_setprio((RS_PRIO >> 8) & 3);
         // the crop-row unit (16 pixels) item `it` of a chunk that starts at V2 row c0 stands for: item = (V2 row v, crop row k of its six, unit u)
+        constexpr int CR = G::POOL + G::KH - 1;                           // crop rows under one V2 row
+        static_assert(CR == 6 && F::IMG_ROWS == F::CHUNK * CR, "the chunk's crop rows in LDS");
 #define RS_ITEM(it_, c0_)                                                                                                        \
                 const int vk = (it_) / 5, u = (it_) - vk * 5;                                                                    \
-                const int v = vk / 6, k = vk - v * 6;                                                                            \
+                const int v = vk / CR, k = vk - v * CR;                                                                          \
                 int q = (c0_) + v;                                                                                               \
                 q = q < total_rows ? q : total_rows - 1;                                                                         \
                 const int crop = q / S, y = q - crop * S;                                                                        \
-                const int iy = 2 * y - 2 + k;
+                const int iy = G::POOL * y - G::KH / 2 + k;
         // P0 in two halves: the loads (issued in front of the V3 transform, whose instructions hide their latency), then the conversion
         auto p0_load = [&](const int c0, const int nr, uint4& px) {
             px = make_uint4(0, 0, 0, 0);
@@ -335,9 +354,9 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         int res_hi = qmin + nrows;
         int prev = -1;
         for (;;) {
-            int next_pass, lo, hi;
+            int next_slot, next_pass, lo, hi;
             bool have_next;
-            RS_NEXT(pass, res_hi, next_pass, have_next, lo, hi);
+            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi);
             // S1 (beside taps 0-19): the crop rows of the first chunk are requested, the V3 transform of the previous pass runs under their flight
             const int nr0 = hi - lo < F::CHUNK ? hi - lo : F::CHUNK;
             uint4 px;
@@ -369,6 +388,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             res_hi = hi;
             tleft = tleft == 1 ? PK : tleft - 1;
             pass = next_pass;
+            slot = next_slot;
         }
         e2(prev);                                                         // the last pass's activations (behind its third barrier)
 #undef RS_ITEM
@@ -406,7 +426,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         // A-operand byte offsets of this lane's tile: per kernel row the row slot of the pass (out-of-crop rows -> the zero row) and its rotation --
         // computed for the NEXT pass behind the output transform -- and per position of a group the rotated unit, put together inside taps 0-19,
         // one tap ahead of its first use (taps 20-39 use the same twenty offsets for the second position group)
-        int aoff[5][4], srow[5], srot[5];
+        int aoff[G::KH][4], srow[G::KH], srot[G::KH];
         int wh[4], wl[4];
         {
             int s_ = mg * 32 + j;
@@ -423,18 +443,18 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             int gp_ = (ps_) * G::RPP + rp_;                                                                                      \
             gp_ = gp_ < total_pairs ? gp_ : total_pairs - 1;                                                                     \
             const int qo_ = 2 * gp_ + (r2_ & 1), y_ = qo_ % S;                                                                   \
-            _Pragma("unroll") for (int ky = 0; ky < 5; ++ky) {                                                                   \
-                const int iy_ = y_ + ky - 2;                                                                                     \
-                const int slot_ = (iy_ >= 0 && iy_ < S) ? (qo_ + ky - 2) % G::NR + 1 : 0;                                        \
+            _Pragma("unroll") for (int ky = 0; ky < G::KH; ++ky) {                                                               \
+                const int iy_ = y_ + ky - G::KH / 2;                                                                             \
+                const int slot_ = (iy_ >= 0 && iy_ < S) ? (qo_ + ky - G::KH / 2) % G::NR + 1 : 0;                                \
                 srow[ky] = slot_ * G::ROWL; srot[ky] = w2b_rot(slot_);                                                           \
             }                                                                                                                    \
         } while (0)
 #define RS_AUNIT(tau_) do { if ((tau_) < 20) aoff[rs_ky(tau_)][rs_pg(tau_)] = srow[rs_ky(tau_)] + (wh[rs_pg(tau_)] | (((wl[rs_pg(tau_)] + srot[rs_ky(tau_)]) & 15) << 4)); } while (0)
         RS_AOFF(pass);
         for (;;) {
-            int next_pass, lo, hi;
+            int next_slot, next_pass, lo, hi;
             bool have_next;
-            RS_NEXT(pass, res_hi, next_pass, have_next, lo, hi);
+            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi);
             const bool draw = tleft == 1;
             uint32_t ticket = 0;
             // the ticket after the next one (raw instruction: atomicAdd() waits for the returned value on the spot); stored behind the second barrier
@@ -540,6 +560,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             res_hi = hi;
             tleft = tleft == 1 ? PK : tleft - 1;
             pass = next_pass;
+            slot = next_slot;
         }
 #undef RS_TAP
 #undef RS_WFETCH
@@ -550,6 +571,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
 #undef W2_BOFF
     }
 #undef RS_NEXT
+#undef RS_LIST
 #undef RS_ROWS
 #undef RS_BAR
     if (__any(!(ovfm < 4368.0f)) && lane == 0) atomicOr(overflow, 3u);      // (nothing is left here behind the last flag_crops; if it ever is, it is unattributed: every crop)

@@ -97,6 +97,10 @@ struct WinoGeom {
 // k_conv2_wpre2 (cnn_wpre.h) and the fused conv1+conv2 kernels on top of it: a pass = RPP row pairs of conv2's output
 struct W2bGeom {
     static constexpr int CO = 64, S = 40, TPP = 20, RPP = 3, NR = 2 * RPP + 4;
+    // conv1 and conv2 alike: KH x KH 'same' convolution, then a POOL x POOL max-pool.  The fused kernels' row arithmetic (a V2 row reads
+    // POOL + KH - 1 crop rows from POOL y - KH / 2 on; a tap row ky reads V2 row y + ky - KH / 2) and the row-skipping rule (cnn_skip.h) use these
+    static constexpr int KH = 5, POOL = 2;
+    static_assert(NR == POOL * RPP + KH - 1, "the V2 rows a pass reads");
     static constexpr int ROWL = 1280;                                   // one (row, piece, group): 4 positions x 10 tiles x 32 B, in V2 and in LDS
     static constexpr int PLANE = (NR + 1) * ROWL, BUF = 2 * PLANE;      // slot 0 = the zero row; BUF = the two pieces of one position group
     static constexpr int PBUF_OFF = 2 * BUF, PBUF = RPP * 20 * 64 * 4;

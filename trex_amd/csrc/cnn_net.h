@@ -2,6 +2,7 @@
 #pragma once
 #include "internal.h"
 #include "cnn_plan.h"
+#include "cnn_skip.h"
 #include <tuple>
 
 namespace trexhip {
@@ -24,6 +25,12 @@ struct Net {
     float *act1 = nullptr, *act2 = nullptr, *act3 = nullptr, *fc1 = nullptr, *probs = nullptr, *logits = nullptr;   // act: [n][H/2][W/2][16], [n][H/4][W/4][64], [n][H/8][W/8][128]
     uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
     uint8_t* crops = nullptr;
+    // skipping the passes of k_conv12_rs whose crop rows are all background (cnn_skip.h, cnn_skip_kernels.h)
+    uint8_t* v3e = nullptr;                    // the V3 image of an all-zero crop [20][V3_ROWB], made when the weights are loaded (1 channel, 80 x 80)
+    uint32_t* d_skip = nullptr;                // SK_WORDS words: the empty crop's range flag, the last call's list length and counters
+    int2* skip_bands = nullptr;                // [max_crops] first / last non-zero row
+    uint32_t* skip_counts = nullptr;           // needed passes per SKIP_LB passes
+    int* skip_list = nullptr;                  // the passes to compute, in order, + the SKIP_PAD entry behind them
     float* h_probs = nullptr;                  // pinned
     Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
     // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one

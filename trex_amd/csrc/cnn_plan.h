@@ -9,6 +9,7 @@ namespace trexhip {
 
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
 //   ROLE_SPLIT  k_conv12_rs (conv1 inside conv2, one workgroup per CU)   -> k_conv5_wpair       1 channel, aligned crops, >= 3200 crops
+//               (in front of it, unless bit 27 is set: k_crop_bands, k_pass_count, k_pass_list, k_v3_fill -- passes of background rows are skipped)
 //   FUSED_2WG   k_conv12_wpre (the same, two workgroups per CU)          -> k_conv5_wpair       1 channel, aligned crops, fewer
 //   TWO_KERNEL  k_conv1_wpre -> k_conv2_wpre2                            -> k_conv5_wpair       3 channels, or TREXHIP_CONV_GEOM bit 28
 //   FP32_ACT    conv1 -> act1 -> k_conv5_stream -> act2 -> k_conv5_wino                         unaligned crops, or any of bits 0-11
@@ -42,6 +43,7 @@ struct CnnPlan {
     int r_fc1_grid, r_head_grid;    // k_fc1 (r_fc1_grid, planes) and k_head on the plan
     AnyTiles t2, t3;                // ANY_SIZE: tile shapes of conv2 / conv3
     int tx1, t1;                    //           conv1 tiles per row / per crop
+    bool skip;                      // ROLE_SPLIT: the passes whose crop rows are all background are not computed (cnn_skip.h); off: TREXHIP_CONV_GEOM bit 27
 };
 
 inline int ceil_div(const int a, const int b) { return (a + b - 1) / b; }
@@ -97,6 +99,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
     p.chain = role_split ? Chain::ROLE_SPLIT : fused12 ? Chain::FUSED_2WG : pre ? Chain::TWO_KERNEL : h16 ? Chain::FP32_ACT : Chain::EXACT;
     p.conv1 = fused12 ? Conv1::FUSED : pre ? Conv1::WPRE : aligned ? Conv1::MFMA : Conv1::VALU;
     p.conv1_grid = n;
+    p.skip = role_split && !(geom & (1 << 27));
 
     const int n_pass2 = ceil_div(n * 20, W2bGeom::RPP), n_pass3 = ceil_div(n * GW::TPC, GW::MB);
     if (fused12) {
