@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 15
+#define TREXHIP_ABI_VERSION 16
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -550,6 +550,16 @@ int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32
  * What the last such call did (waits for the context's stream): *passes of the batch, *listed of them computed, *bytes_filled of conv2's output
  * copied instead; zeros before the first such call.  No reference counterpart; any pointer may be NULL.  (ABI 15) */
 int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* listed, uint64_t* bytes_filled);
+
+/* Where those passes are skipped, conv3 (k_conv5_wpair) computes only the row pairs -- two rows of its 20 x 20 map, pooled to one row of its
+ * output -- that read a row of conv2's output with a blob in it, six listed pairs to a pass; the other row pairs are copied from the output of an
+ * all-zero crop, made when the weights are loaded.  The crops' bytes decide, on the device, in every call, also whether the listed form pays at
+ * all (a batch of noise lists every pair: the dense kernel runs then); the results are the bits of the dense kernel.  Bit 26 of TREXHIP_CONV_GEOM
+ * (value 67108864) switches this off.
+ * What the last such call did (waits for the context's stream): *pairs of the batch (10 per crop), *listed of them to be computed, *passes the
+ * listed form walked (0: the dense kernel ran), *bytes_filled of conv3's output copied instead; zeros before the first such call.  No reference
+ * counterpart; any pointer may be NULL.  (ABI 16) */
+int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled);
 
 /* ---- multi-GPU hand-off --------------------------------------------------------------------
  * Fixed-size per-blob identity table of the last batch, written to caller-owned device memory

@@ -1,7 +1,8 @@
 """How much of conv1+conv2 the benchmark's crops need (dev tool, needs the GPU): one step of bench.py's default workload (config C4, 256 frames,
 gray, FP16X3) through the same Pipeline, then the device counters of the last identify call of lane 0 (trexhip_identify_skip_stats): passes of
 the batch, passes the role-split kernel computed, bytes of V3 rows filled from the empty crop's image -- and the crops' own row statistics, on
-the host.  Nothing here is timed.  One JSON line.
+the host -- and the counters of the listed conv3 (trexhip_identify_skip3_stats): row pairs of the batch, row pairs listed, the passes its listed
+form walked (0: the dense kernel ran) against the dense kernel's, bytes of act3 filled from the empty crop's.  Nothing here is timed.  One JSON line.
    python tools/skip_stats.py"""
 import json
 import os
@@ -21,10 +22,14 @@ n = pipe.run(1, frames.data_ptr())
 torch.cuda.synchronize()
 lane = pipe.lanes[0]
 passes, listed, filled = lane.seg.skip_stats()
+pairs3, listed3, passes3, filled3 = lane.seg.skip3_stats()
 crops = lane.crops[:passes * 3 // 20]
 rows = (crops != 0).any(dim=2)                       # [n][80]: the row holds a non-zero byte
 print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passes": passes, "passes_listed": listed,
                   "fraction_listed": round(listed / max(passes, 1), 4), "v3_bytes_filled": filled, "v3_bytes": int(crops.shape[0]) * 20 * 10240,
                   "mean_nonzero_rows_per_crop": round(float(rows.sum(1).float().mean()), 2),
-                  "empty_crops": int((~rows.any(1)).sum())}))
+                  "empty_crops": int((~rows.any(1)).sum()),
+                  "conv3_pairs": pairs3, "conv3_pairs_listed": listed3, "conv3_fraction_listed": round(listed3 / max(pairs3, 1), 4),
+                  "conv3_listed_passes": passes3, "conv3_dense_passes": (pairs3 * 10 + 63) // 64,
+                  "conv3_pass_ratio": round(passes3 / max((pairs3 * 10 + 63) // 64, 1), 4), "act3_bytes_filled": filled3}))
 pipe.close()

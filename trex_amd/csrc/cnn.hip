@@ -1402,6 +1402,10 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->skip_bands, N * sizeof(int2), who));
         TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4, who));
         TRY(B.device_bytes(&net->skip_list, (n_pass + SKIP_PAD) * 4, who));
+        const size_t blocks3 = (N + Skip3Geom::BLOCK - 1) / Skip3Geom::BLOCK;
+        TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint2), who));
+        TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 4, who));
+        TRY(B.device_bytes(&net->skip3_desc, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Geom::DESC * 4, who));
     }
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
     TRY(B.pinned(&net->h_probs, N * net->classes, who));
@@ -1432,7 +1436,11 @@ static const Kern K_CONV2_WPRE2(k_conv2_wpre2, 256, W2bGeom::LDS_BYTES);
 static const Kern K_CONV2_STREAM(k_conv5_stream<16, 64, 40, 8, 4>, 256, ConvGeomS<16, 64, 40, 8, 4>::LDS_BYTES);
 using GW3 = WinoGeom<64, 128, 20, 2>;
 static const Kern K_CONV3_WINO(k_conv5_wino<64, 128, 20, 2>, GW3::NTHR, GW3::LDS_BYTES);
-static const Kern K_CONV3_WPAIR(k_conv5_wpair, 256, GW3::LDS_BYTES + 1024 /* slack for the last DMA instruction */);
+static const Kern K_CONV3_WPAIR(k_conv5_wpair<false>, 256, GW3::LDS_BYTES + 1024 /* slack for the last DMA instruction */);
+static const Kern K_CONV3_WPAIR_LIST(k_conv5_wpair<true>, 256, GW3::LDS_BYTES + 1024);
+static const Kern K_PAIR_COUNT(k_pair_count, SKIP3_TB);
+static const Kern K_PAIR_LIST(k_pair_list, SKIP3_TB);
+static const Kern K_ACT3_FILL(k_act3_fill, 256);
 template <int CI, int CO, int S, int ROWS, int NTERMS>
 static auto split_kern() { return Kern(k_conv5_split<CI, CO, S, ROWS, NTERMS>, 512, ConvGeomB<CI, CO, S, ROWS, SPLIT_NP>::LDS_BYTES); }
 // conv2 / conv3 on fp32 activations in the exact modes; x6_plan is the bf16x6 instance of every chain's guarded re-run
@@ -1506,10 +1514,12 @@ static void launch_rerun(const Pass& f) {
 
 // The V3 image of an all-zero crop, once per loaded network: k_conv12_rs itself on one zero crop, every pass computed, its own range-flag word.
 // A net whose background activations leave the fp16 range raises that word, and the list kernels then list every pass (they read it on the device).
+// Right behind it the act3 of that crop: the dense k_conv5_wpair itself on that image.
 static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     const char* who = "trexhip_load_weights";
     uint8_t* zero = nullptr;
     int rc = net->weights.device_bytes(&net->v3e, (size_t)SkipGeom::V3_ROWS * V3_ROWB, who);
+    if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->act3e, (size_t)Skip3Geom::PAIRS * 10 * 128 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->d_skip, SK_WORDS * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&zero, SkipGeom::CROP_ROWS * 80, who);
     if (rc != TREXHIP_OK) return rc;
@@ -1519,6 +1529,9 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     TH_CHECK_HIP(hipMemsetAsync(zero, 0, SkipGeom::CROP_ROWS * 80, ctx->stream));
     K_CONV12_RS(ctx->stream, p.conv2.grid, zero, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3e, net->inv2w, net->d_skip + SK_EMPTY_RANGE, 1,
                 net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr);
+    TH_CHECK_HIP(hipGetLastError());
+    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV3_WPAIR.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV3_WPAIR.lds));
+    K_CONV3_WPAIR(ctx->stream, p.conv3.grid, net->v3e, net->w3w, net->b3, net->act3e, net->inv3w, 1, net->d_skip + SK3_EMPTY_CTR, p.n_big3, nullptr, nullptr);
     TH_CHECK_HIP(hipGetLastError());
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return TREXHIP_OK;
@@ -1569,7 +1582,15 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         }
         stage_end(ctx, TREXHIP_STAGE_CONV2);
         stage_begin(ctx, TREXHIP_STAGE_CONV3);
-        if (pre) K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3);
+        if (pre) {
+            if (p.skip3) {     // the row pairs to compute, packed into passes, and the others' act3; which form of the kernel runs is the device's word
+                K_PAIR_COUNT(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
+                K_PAIR_LIST(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
+                K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e), reinterpret_cast<uint4*>(net.act3), net.skip3_desc);
+                K_CONV3_WPAIR_LIST(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.d_skip);
+            }
+            K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3, nullptr, p.skip3 ? net.d_skip : nullptr);
+        }
         else if (p.chain == Chain::FP32_ACT)
             K_CONV3_WINO(s, p.conv3.grid, net.act2, net.w3w, net.b3, net.act3, net.inv3w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS3));
         else launch_exact(f, 3, f.mode, nullptr);
@@ -1719,6 +1740,19 @@ int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* li
     if (passes) *passes = w[SK_NPASS];
     if (listed) *listed = w[SK_LEN];
     if (bytes_filled) *bytes_filled = (uint64_t)w[SK_FILLED] * V3_ROWB;
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled) {
+    if (!ctx || !ctx->net) { set_error("trexhip_identify_skip3_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
+    Net* net = static_cast<Net*>(ctx->net);
+    uint32_t w[SK_WORDS] = {};
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    if (pairs) *pairs = w[SK3_PAIRS];
+    if (listed) *listed = w[SK3_LISTED];
+    if (passes) *passes = w[SK3_USE] ? w[SK3_PASSES] : 0u;
+    if (bytes_filled) *bytes_filled = (uint64_t)w[SK3_FILLED] * (10 * 128 * 4);
     return TREXHIP_OK;
 }
 

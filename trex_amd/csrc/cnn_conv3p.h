@@ -26,10 +26,26 @@
 // DMA -- and a wave issues one instruction per ~4.5 cycles, so a tap of 6 MFMAs (192 cycles) has room for ~40.  Weight fragments 3 / 5 / 7 taps
 // ahead: 4.52 / 4.39 / 4.39; A fragments 2 taps ahead: no change.
 
+//
+// The LISTED form (cnn_skip3.h) computes only the row pairs whose V3 rows hold more than the empty crop's image.  A pass is then SIX listed row
+// pairs -- 60 of the 64 tile slots, so that a lane's pair slot and its place in the pair are the same in every pass -- from at most two runs (one
+// crop's consecutive pairs): 2 pA + 4 and 2 pB + 4 V3 rows, at most NR together.  k_pair_list (cnn_skip_kernels.h) has written per pass what the
+// kernel needs (skip3_describe): the staging goes through one buffer resource from run A's first row, a lane whose row slot lies behind run A
+// adds the distance to run B (a compare, a select and an add per DMA instruction), what lies behind run B is out of range and reads zeros as
+// before; y comes from the listed pair's q; the stores go to the listed pair's place in act3, a per-lane select between two of the pass's six
+// pair offsets (tiles i and i + 4 h can lie in different pairs).  Everything else -- the taps, their order, the fold, the tail -- is the dense
+// form's, so a listed pair's outputs are the dense kernel's bits.  Both forms are launched; `words` (SK3_USE) names the one that runs.
+// Measured (profiles/conv3_listed_pairs.txt; the benchmark's 25600 crops: 31381 listed passes against 40000 dense ones): 4511 -> 3573 us under a
+// kernel trace, a listed pass costs 1.01 dense passes; the dense instance keeps its registers (256 + 210, no scratch), the listed one has 256 + 230,
+// no scratch.  (The pass's values are plain scalars on purpose: as members of a struct handed to the lambdas they stayed in scratch memory, 104
+// bytes per lane in BOTH instances.)
+template <bool LISTED>
 __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__ v3, const uint4* __restrict__ wp /*[4][5][8][2][2][128] x 16 B*/,
                                                      const float* __restrict__ bias, float* __restrict__ out, const float out_scale,
                                                      const int n_crops, uint32_t* __restrict__ pass_ctr,
-                                                     const int n_big /* tickets of PK passes; the passes behind them go out one by one */) {
+                                                     const int n_big_dense /* tickets of PK passes; the passes behind them go out one by one */,
+                                                     const int* __restrict__ desc /* LISTED: DESC words per pass */,
+                                                     const uint32_t* __restrict__ words /* Net::d_skip; null: the dense form, unconditionally */) {
     constexpr int CI = 64, CO = 128, S = 20, TPW = 2;
     constexpr int BD = 5;         // taps of lead of the weight fragments (measured above)
     constexpr int AD = 1;         // taps of lead of the A fragments
@@ -42,8 +58,12 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     __shared__ int s_next_pass;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
+    using L = Skip3Geom;
+    static_assert(L::NR == G::NR && L::SLOTS * G::TPP <= G::MB && L::PAIRS * 2 == S, "a listed pass fits the dense pass's rows and tiles");
+    if (words && (words[SK3_USE] != 0) != LISTED) return;
     const int total_tiles = n_crops * G::TPC;
-    const int n_pass = (total_tiles + G::MB - 1) / G::MB;
+    const int n_pass = LISTED ? __builtin_amdgcn_readfirstlane((int)words[SK3_PASSES]) : (total_tiles + G::MB - 1) / G::MB;
+    const int n_big = LISTED ? (n_pass >= 16 * (int)gridDim.x ? (int)((long long)n_pass * 7 / 8) / 4 : 0) : n_big_dense;
     const int big_end = n_big * PK;
     auto ticket_first = [&](const int t) { return t < n_big ? t * PK : big_end + (t - n_big); };
     int pass = ticket_first((int)blockIdx.x);
@@ -68,16 +88,20 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         dvo[k] = (q < G::NR * G::RP && o < RNG) ? (uint32_t)(row * V3_ROWB + pc * 1280 + (w < G::RP0 ? w : G::RP0 - 16)) : 0x80000000u;
     }
     const uint32_t mbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + G::RP + wave * 1024));
+    // (LISTED: nrows_ counts the rows from run A's first to run B's last, the gap included)
     auto stage_rsrc = [&](const int g, const int qmin_, const int nrows_) {
         const unsigned long long base = wave_uniform64(reinterpret_cast<unsigned long long>(v3) + (unsigned long long)qmin_ * V3_ROWB + (unsigned)(g * 2560));
         return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0, __builtin_amdgcn_readfirstlane(nrows_ * V3_ROWB - g * 2560), 0x00020000);
     };
     // (M0 is written and not restored: nothing else in this kernel reads it -- checked in the ISA)
-#define P3_DMA(k_, srs_, buf_)                                                                                                   \
+    // (LISTED: nab_ = the bytes of run A's rows, gapb_ = the bytes between them and run B's; the lanes marked out of range stay so: both are < 2^31)
+#define P3_DMA(k_, srs_, buf_, nab_, gapb_)                                                                                      \
     do {                                                                                                                         \
-        if ((k_) < NDW - 1 || wave + 4 * (NDW - 1) < NI)                                                                         \
+        if ((k_) < NDW - 1 || wave + 4 * (NDW - 1) < NI) {                                                                       \
+            const uint32_t vo_ = LISTED ? dvo[k_] + (dvo[k_] >= (uint32_t)(nab_) ? (uint32_t)(gapb_) : 0u) : dvo[k_];            \
             asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds"                          \
-                         :: "s"(mbase), "n"((buf_) * G::BUF + (k_) * 4096), "v"(dvo[k_]), "s"(srs_) : "memory", "scc");           \
+                         :: "s"(mbase), "n"((buf_) * G::BUF + (k_) * 4096), "v"(vo_), "s"(srs_) : "memory", "scc");               \
+        }                                                                                                                        \
     } while (0)
     for (int i = tid; i < 4 * (G::RP / 16); i += G::NTHR) {          // row slot 0 of the four planes = the zero row
         const int pl = i / (G::RP / 16), o = i - pl * (G::RP / 16);
@@ -88,11 +112,45 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     const int co = wave * 32 + j;
     const float bz = bias[co];
     const int ooff = (4 * h * CO + co) * 4;
-    int qmin, nrows;
-    wino_pass_rows<G, S>(pass, total_tiles, qmin, nrows);
+    // LISTED: the lane's two tiles m * 32 + j: pair slot (the idle tiles 60 .. 63 take the last one's rows; their stores are dropped) and place in the pair
+    int lps[TPW], lr2[TPW];
+#pragma unroll
+    for (int m = 0; m < TPW; ++m) {
+        const int t = m * 32 + j;
+        lps[m] = t / G::TPP < L::SLOTS ? t / G::TPP : L::SLOTS - 1;
+        lr2[m] = t % G::TPP;
+    }
+    // what a pass is: the dense form's rows qmin .. qmin + nrows - 1; LISTED: the descriptor's scalars (rows of run A, gap, the pairs' act3 offsets
+    // relative to the pass's first pair) and the lane's two pair entries
+    // (the descriptor as it is loaded: word lane % DESC and the lane's two pair entries)
+    int raw_w = 0, ent[TPW] = {};
+    auto pass_fetch = [&](const int pass_) {
+        const int* d = desc + (size_t)pass_ * L::DESC;
+        raw_w = d[lane & (L::DESC - 1)];
+#pragma unroll
+        for (int m = 0; m < TPW; ++m) ent[m] = d[S3_SLOT + lps[m]];
+    };
+    auto pass_decode = [&](int& qmin_, int& nrows_, int& na_, int& gap_, int& gp0_, int& span_, uint32_t (&rel_)[L::SLOTS]) {
+        const int w = raw_w;
+        qmin_ = __builtin_amdgcn_readlane(w, S3_ROW0);
+        na_ = __builtin_amdgcn_readlane(w, S3_NA) * V3_ROWB;
+        gap_ = __builtin_amdgcn_readlane(w, S3_GAP) * V3_ROWB;
+        nrows_ = __builtin_amdgcn_readlane(w, S3_ROWS) + __builtin_amdgcn_readlane(w, S3_GAP);
+        gp0_ = __builtin_amdgcn_readlane(w, S3_GP0);
+        span_ = __builtin_amdgcn_readlane(w, S3_SPAN);
+#pragma unroll
+        for (int s2 = 0; s2 < L::SLOTS; ++s2) {
+            const uint32_t rp = (uint32_t)__builtin_amdgcn_readlane(w, S3_SLOT + s2) >> 16;
+            rel_[s2] = rp == (uint32_t)S3_IDLE ? 0x80000000u : rp * (uint32_t)(G::TPP * CO * 4);
+        }
+    };
+    int qmin = 0, nrows = 0, na = 0, gap = 0, gp0 = 0, span = 0;
+    uint32_t rel[L::SLOTS] = {};
+    if (LISTED) { pass_fetch(pass); pass_decode(qmin, nrows, na, gap, gp0, span, rel); }
+    else wino_pass_rows<G, S>(pass, total_tiles, qmin, nrows);
     const __amdgpu_buffer_rsrc_t srs0 = stage_rsrc(0, qmin, nrows);
 #pragma unroll
-    for (int k = 0; k < NDW; ++k) P3_DMA(k, srs0, 0);
+    for (int k = 0; k < NDW; ++k) P3_DMA(k, srs0, 0, na, gap);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // tap tt of unit g: chunk tt / 10, kernel row (tt % 10) / 2, position PAIRS[g][tt & 1]; its weights [chunk][ky][position] x BV x 16 bytes
@@ -109,6 +167,11 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     // A-operand byte offsets of this lane's two tiles, per kernel row: the row slot (out-of-crop rows -> the zero row) + the tile's 32 bytes
     // (per tile: the offset of its own input row and of the zero row, and its y; per kernel row a compare and a select)
     auto a_base = [&](const int pass_, const int qmin_, const int m, int& inr, int& zr, int& yy) {
+        if (LISTED) {             // (the entries fetched last: this pass's in front of the loop, the next one's under the last unit)
+            const int r2 = lr2[m], par = r2 & 1, e = ent[m];
+            yy = 2 * ((e >> 8) & 0xff) + par; zr = (r2 >> 1) * 32 + h * 16; inr = ((e & 0xff) + par) * G::RP + zr;
+            return;
+        }
         int T = pass_ * G::MB + m * 32 + j;
         if (T > total_tiles - 1) T = total_tiles - 1;
         const int gp = T / G::TPP, r2 = T - gp * G::TPP;
@@ -149,6 +212,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     // first use of the value -- the tail, one pass later -- and the registers of three units' accumulators with it)
 #define P3_PIN(x_) asm volatile("" : "+v"(x_))
     __amdgpu_buffer_rsrc_t ors_prev = make_rsrc(out, 0);
+    uint32_t rel_prev[L::SLOTS] = {};                  // LISTED: the act3 offsets of the pairs of the pass whose tail is still to run
     // pool (rows r, r + 1 x outputs 0,1 / 2,3), bias, ReLU, store.  Accumulator rows r, r + 1 (r even) of lane half h are the tiles i, i + 1 = the
     // two rows of a row pair at one tx, and the tile number of the even one IS the pooled output's index: T = 10 gp + 2 tx (TPP = 10 is even, so
     // T & 1 = the row's parity).  No division: the address is the lane's constant offset + a compile-time one, and tiles past the end of the
@@ -159,6 +223,17 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         const float d0 = y[m][3][r] + P3_ACC(acc[1][m][1][r]), d1 = y[m][3][r + 1] + P3_ACC(acc[1][m][1][r + 1]);
         const float v0 = fmaxf(fmaxf(a0, y[m][1][r]), fmaxf(a1, y[m][1][r + 1]));
         const float v1 = fmaxf(fmaxf(y[m][2][r], d0), fmaxf(y[m][2][r + 1], d1));
+        if (LISTED) {
+            // tiles t0 = m * 32 + i (h = 0) and t0 + 4 (h = 1): pair slot and place in the pair are compile-time, the pair's offset is the pass's
+            // (all of it in the lane's offset: that is what the resource's range check looks at)
+            const int t0 = m * 32 + i, t1 = t0 + 4;
+            const uint32_t o0 = rel_prev[t0 / G::TPP] + (uint32_t)((t0 % G::TPP) * CO * 4);
+            const uint32_t o1 = t1 / G::TPP < L::SLOTS ? rel_prev[t1 / G::TPP < L::SLOTS ? t1 / G::TPP : 0] + (uint32_t)((t1 % G::TPP) * CO * 4) : 0x80000000u;
+            const int vo = co * 4 + (int)(h ? o1 : o0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v0 * out_scale + bz, 0.f)), rs, vo, 0, 2 /* nt */);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v1 * out_scale + bz, 0.f)), rs, vo + CO * 4, 0, 2);
+            return;
+        }
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v0 * out_scale + bz, 0.f)), rs, ooff, (m * 32 + i) * CO * 4, 2 /* nt */);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v1 * out_scale + bz, 0.f)), rs, ooff, (m * 32 + i + 1) * CO * 4, 2);
     };
@@ -176,25 +251,32 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     };
     for (;;) {
         const int tleft = total_tiles - pass * G::MB;
-        const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (size_t)(pass * G::MB) * CO, (uint32_t)((tleft < G::MB ? tleft : G::MB) * CO * 4));
+        const __amdgpu_buffer_rsrc_t ors = LISTED ? make_rsrc(out + (size_t)gp0 * (G::TPP * CO), (uint32_t)(span * (G::TPP * CO * 4)))
+                                                  : make_rsrc(out + (size_t)(pass * G::MB) * CO, (uint32_t)((tleft < G::MB ? tleft : G::MB) * CO * 4));
         int next_pass = pass + 1;
         const bool draw = pass >= big_end || pass % PK == PK - 1;          // the last pass of a ticket draws the next one
         if (draw && tid == 0) s_next_pass = ticket_first((int)atomicAdd(pass_ctr, 1u) + (int)gridDim.x);   // read by everyone after the first unit's barrier
         bool have_next = false;
-        int qmin_n = qmin, nrows_n = nrows;
+        int qmin_n = qmin, nrows_n = nrows, na_n = na, gap_n = gap, gp0_n = gp0, span_n = span;
+        uint32_t rel_n[L::SLOTS];
+#pragma unroll
+        for (int s2 = 0; s2 < L::SLOTS; ++s2) rel_n[s2] = rel[s2];
 #pragma clang loop unroll(full)
         for (int g = 0; g < 4; ++g) {
             const bool last_u = g == 3;
-            if (last_u) {
+            if (!LISTED && last_u) {
                 if (draw) next_pass = s_next_pass;
                 have_next = next_pass < n_pass;
                 if (have_next) wino_pass_rows<G, S>(next_pass, total_tiles, qmin_n, nrows_n);
             }
+            // (without a next pass the descriptor fetched is this pass's own: the next = this one once more)
+            if (LISTED && last_u) pass_decode(qmin_n, nrows_n, na_n, gap_n, gp0_n, span_n, rel_n);
             const uint8_t* pbase = ldsb + (g & 1) * G::BUF;
             // staged under this unit: the next unit of this pass, or unit 0 of the next pass (without one: this pass's once more, into the buffer
             // nobody reads again)
             const int sg = last_u ? 0 : g + 1;
             const int sqmin = last_u ? qmin_n : qmin, snrows = last_u ? nrows_n : nrows;
+            const int sna = last_u ? na_n : na, sgap = last_u ? gap_n : gap;
             const __amdgpu_buffer_rsrc_t srs = stage_rsrc(sg, sqmin, snrows);
             // A fragments AD taps ahead (tap tt: position slot (tt / 10) * 2 + (tt & 1), kernel row (tt % 10) / 2)
             uint4 af[AD + 1][TPW][2];
@@ -219,7 +301,14 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                 const int wt = tt + BD < 40 ? w_off(g, tt + BD) : w_off(sg, tt + BD - 40);
                 bq[(tt + BD) % 8][0] = buf_load16(wrs, boff, wt);
                 bq[(tt + BD) % 8][1] = buf_load16(wrs, boff, wt + 2 * CO * 16);
-                if (tt >= DT0 && tt < DT0 + NDW) P3_DMA(tt - DT0, srs, (g & 1) ^ 1);
+                // LISTED: the next pass's descriptor is fetched late in the unit before the last -- the ticket is there behind the first unit's
+                // barrier -- and taken apart at the top of the last one, whose staging needs its scalars
+                if (LISTED && g == 2 && tt == 34) {
+                    if (draw) next_pass = s_next_pass;
+                    have_next = next_pass < n_pass;
+                    pass_fetch(have_next ? next_pass : pass);
+                }
+                if (tt >= DT0 && tt < DT0 + NDW) P3_DMA(tt - DT0, srs, (g & 1) ^ 1, sna, sgap);
                 const int hp = tt & 1;
                 const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tt % 8][0]);
                 const f16x8 b2 = __builtin_bit_cast(f16x8, bq[tt % 8][1]);
@@ -260,8 +349,10 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             __syncthreads();
         }
         ors_prev = ors;
+#pragma unroll
+        for (int s2 = 0; s2 < L::SLOTS; ++s2) { rel_prev[s2] = rel[s2]; rel[s2] = rel_n[s2]; }
         if (!have_next) break;
-        pass = next_pass; qmin = qmin_n; nrows = nrows_n;
+        pass = next_pass; qmin = qmin_n; nrows = nrows_n; na = na_n; gap = gap_n; gp0 = gp0_n; span = span_n;
     }
     // the last pass's tail has no next pass to run under (fold of unit 2 ran under unit 3; unit 3's pair is positions 0 and 7, taken by the tail itself)
 #pragma unroll

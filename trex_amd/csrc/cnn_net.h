@@ -3,6 +3,7 @@
 #include "internal.h"
 #include "cnn_plan.h"
 #include "cnn_skip.h"
+#include "cnn_skip3.h"
 #include <tuple>
 
 namespace trexhip {
@@ -31,6 +32,11 @@ struct Net {
     int2* skip_bands = nullptr;                // [max_crops] first / last non-zero row
     uint32_t* skip_counts = nullptr;           // needed passes per SKIP_LB passes
     int* skip_list = nullptr;                  // the passes to compute, in order, + the SKIP_PAD entry behind them
+    // computing only the row pairs of conv3 whose V3 rows hold more than background (cnn_skip3.h, cnn_skip_kernels.h)
+    float* act3e = nullptr;                    // the act3 of an all-zero crop [10][10][128], made when the weights are loaded, behind v3e
+    uint2* skip3_counts = nullptr;             // listed passes and pairs per workgroup of k_pair_count
+    uint32_t* skip3_tcounts = nullptr;         // listed passes per thread of it (Skip3Geom::BLOCK crops)
+    int* skip3_desc = nullptr;                 // Skip3Geom::DESC words per listed pass
     float* h_probs = nullptr;                  // pinned
     Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
     // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one

@@ -9,7 +9,9 @@ namespace trexhip {
 
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
 //   ROLE_SPLIT  k_conv12_rs (conv1 inside conv2, one workgroup per CU)   -> k_conv5_wpair       1 channel, aligned crops, >= 3200 crops
-//               (in front of it, unless bit 27 is set: k_crop_bands, k_pass_count, k_pass_list, k_v3_fill -- passes of background rows are skipped)
+//               (in front of it, unless bit 27 is set: k_crop_bands, k_pass_count, k_pass_list, k_v3_fill -- passes of background rows are skipped;
+//                then, unless bit 26 is set as well: k_pair_count, k_pair_list, k_act3_fill and BOTH forms of k_conv5_wpair, the dense one and the
+//                one that walks the listed row pairs -- the word k_pair_list writes names the one that runs, the other returns at once)
 //   FUSED_2WG   k_conv12_wpre (the same, two workgroups per CU)          -> k_conv5_wpair       1 channel, aligned crops, fewer
 //   TWO_KERNEL  k_conv1_wpre -> k_conv2_wpre2                            -> k_conv5_wpair       3 channels, or TREXHIP_CONV_GEOM bit 28
 //   FP32_ACT    conv1 -> act1 -> k_conv5_stream -> act2 -> k_conv5_wino                         unaligned crops, or any of bits 0-11
@@ -44,6 +46,9 @@ struct CnnPlan {
     AnyTiles t2, t3;                // ANY_SIZE: tile shapes of conv2 / conv3
     int tx1, t1;                    //           conv1 tiles per row / per crop
     bool skip;                      // ROLE_SPLIT: the passes whose crop rows are all background are not computed (cnn_skip.h); off: TREXHIP_CONV_GEOM bit 27
+    bool skip3;                     // where skip is on: conv3 computes only the row pairs that read a row with a blob in it (cnn_skip3.h); off: bit 26
+    int skip3_grid;                 // workgroups of k_pair_count / k_pair_list
+    Launch act3_fill;               // k_act3_fill: 16 crops (SKIP3_FC) per workgroup
 };
 
 inline int ceil_div(const int a, const int b) { return (a + b - 1) / b; }
@@ -100,6 +105,11 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
     p.conv1 = fused12 ? Conv1::FUSED : pre ? Conv1::WPRE : aligned ? Conv1::MFMA : Conv1::VALU;
     p.conv1_grid = n;
     p.skip = role_split && !(geom & (1 << 27));
+    p.skip3 = p.skip && !(geom & (1 << 26));
+    if (p.skip3) {
+        p.skip3_grid = ceil_div(ceil_div(n, 32 /* Skip3Geom::BLOCK crops per thread */), 256);
+        p.act3_fill = {ceil_div(n, 16), n};
+    }
 
     const int n_pass2 = ceil_div(n * 20, W2bGeom::RPP), n_pass3 = ceil_div(n * GW::TPC, GW::MB);
     if (fused12) {

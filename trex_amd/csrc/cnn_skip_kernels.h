@@ -4,6 +4,11 @@
 //   k_pass_count   needed passes per block of SKIP_LB consecutive passes
 //   k_pass_list    order-preserving compaction of the needed passes into the list k_conv12_rs walks, its length, the entry behind its end
 //   k_v3_fill      the V3 rows of every pass that is NOT listed, copied from the V3 image of an all-zero crop (Net::v3e, made at load)
+// and three more for the listed form of k_conv5_wpair (the rule and the packing: cnn_skip3.h), from the same bands:
+//   k_pair_count   listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK consecutive crops
+//   k_pair_list    the passes in order, each as its two runs, the counters, and the word that names the form of conv3 that runs (SK3_USE)
+//   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place); then a wave per crop: the act3 row pairs
+//                  that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load)
 #pragma once
 
 // the words of Net::d_skip
@@ -13,8 +18,9 @@ enum : int {
     SK_LEN = 2,              // passes listed by the last call
     SK_NPASS = 3,            // passes of the last call's batch
     SK_FILLED = 4,           // V3 rows the last call filled
-    SK_WORDS = 8
+    SK_WORDS = 16            // (8 ..: the words of the listed conv3, SK3_* in cnn_skip3.h)
 };
+static_assert(SK3_LAST < SK_WORDS, "the words of the listed conv3 lie behind these");
 static constexpr int SKIP_LB = 1024;      // passes per block of the count / list kernels (one per thread)
 static constexpr int SKIP_PAD = 1;        // one entry behind the last one: k_conv12_rs clamps every read behind the list's end to it (RS_LIST)
 static constexpr int SKIP_FB = 64;        // passes per block of the fill kernel
@@ -130,4 +136,145 @@ __global__ __launch_bounds__(256) void k_v3_fill(const int2* __restrict__ bands,
         }
     }
     if (tid == 0 && rows) atomicAdd(&words[SK_FILLED], rows);
+}
+
+// ---- the listed form of conv3 ----
+static constexpr int SKIP3_TB = 256;      // threads per workgroup of the count / list kernels: SKIP3_TB * Skip3Geom::BLOCK crops
+
+// the listed pairs of the workgroup's SKIP3_TB * BLOCK crops into LDS, one byte each for the first pair and the count, crop k of thread t at
+// [k][t]: read with coalesced loads here, walked by one thread per BLOCK crops from LDS in a loop that stays small (a walk unrolled over
+// registers is 30 KB of code that every thread runs once, from a cold instruction cache: 35 us for what is 800 threads' work)
+__device__ __forceinline__ void skip3_stage_runs(const int2* __restrict__ bands, const int n, const bool all, uint16_t* s_run) {
+    using G = Skip3Geom;
+    const int c0 = blockIdx.x * SKIP3_TB * G::BLOCK;
+    constexpr int U = 8;              // loads in flight per thread: one after the other they are BLOCK round trips to memory
+    static_assert(G::BLOCK % U == 0, "whole groups of loads");
+    for (int i0 = threadIdx.x; i0 < SKIP3_TB * G::BLOCK; i0 += U * SKIP3_TB) {
+        int2 b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * SKIP3_TB;
+            b[u] = c0 + i < n ? bands[c0 + i] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * SKIP3_TB;
+            const SkipPairs r = all && c0 + i < n ? SkipPairs{0, G::PAIRS - 1} : skip3_pairs({b[u].x, b[u].y});
+            s_run[(i % G::BLOCK) * SKIP3_TB + i / G::BLOCK] = (uint16_t)(r.lo <= r.hi ? r.lo | (r.hi - r.lo + 1) << 8 : 0);
+        }
+    }
+    __syncthreads();
+}
+// the row pairs of the crops of block `blk` (this thread's) packed into passes (numbered from `passes` on); emit(index, pass) takes each; -> pairs listed
+template <class E>
+__device__ __forceinline__ int skip3_walk(const uint16_t* s_run, const int blk, int& passes, E&& emit) {
+    using G = Skip3Geom;
+    Skip3Pass p{};
+    int listed = 0;
+#pragma unroll 1
+    for (int k = 0; k < G::BLOCK; ++k) {
+        const int r = s_run[k * SKIP3_TB + threadIdx.x], len = r >> 8;
+        if (len) {
+            listed += len;
+            skip3_add_run(p, passes, (blk * G::BLOCK + k) * G::PAIRS + (r & 0xff), len, emit);
+        }
+    }
+    skip3_flush(p, passes, emit);
+    return listed;
+}
+
+__global__ __launch_bounds__(SKIP3_TB) void k_pair_count(const int2* __restrict__ bands, const int n, const uint32_t* __restrict__ words,
+                                                         uint2* __restrict__ counts /* per workgroup: passes, pairs */,
+                                                         uint32_t* __restrict__ tcounts /* per thread: passes */) {
+    __shared__ uint32_t s_pass, s_pair;
+    __shared__ uint16_t s_run[SKIP3_TB * Skip3Geom::BLOCK];
+    if (threadIdx.x == 0) { s_pass = 0; s_pair = 0; }
+    skip3_stage_runs(bands, n, words[SK_EMPTY_RANGE] != 0, s_run);
+    const int blk = blockIdx.x * SKIP3_TB + threadIdx.x;
+    if (blk * Skip3Geom::BLOCK < n) {
+        int passes = 0;
+        const int listed = skip3_walk(s_run, blk, passes, [](int, const Skip3Pass&) {});
+        tcounts[blk] = (uint32_t)passes;
+        if (passes) { atomicAdd(&s_pass, (uint32_t)passes); atomicAdd(&s_pair, (uint32_t)listed); }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = make_uint2(s_pass, s_pair);
+}
+
+__global__ __launch_bounds__(SKIP3_TB) void k_pair_list(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
+                                                        const uint2* __restrict__ counts, const uint32_t* __restrict__ tcounts, int* __restrict__ desc) {
+    using G = Skip3Geom;
+    __shared__ uint32_t s_scan[SKIP3_TB];
+    __shared__ uint16_t s_run[SKIP3_TB * G::BLOCK];
+    const int tid = threadIdx.x, blk = blockIdx.x * SKIP3_TB + tid;
+    const bool mine = blk * G::BLOCK < n;
+    skip3_stage_runs(bands, n, words[SK_EMPTY_RANGE] != 0, s_run);
+    // the passes in front of this workgroup (all of them, and the pairs: the last workgroup writes the counters)
+    uint32_t before = 0, pairs = 0;
+    for (int b = 0; b <= (int)blockIdx.x; ++b) { const uint2 c = counts[b]; if (b < (int)blockIdx.x) before += c.x; pairs += c.y; }
+    const int cnt = mine ? (int)tcounts[blk] : 0;
+    s_scan[tid] = (uint32_t)cnt;
+    __syncthreads();
+    for (int d = 1; d < SKIP3_TB; d <<= 1) {          // inclusive scan
+        const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    int at = (int)(before + s_scan[tid]) - cnt;
+    if (mine)         // (the pass as its runs, in the first words of its descriptor: k_act3_fill makes the descriptor of it, a thread per pass)
+        skip3_walk(s_run, blk, at, [&](const int idx, const Skip3Pass& p) {
+            *reinterpret_cast<int4*>(desc + (size_t)idx * G::DESC) = make_int4(p.gp0[0], p.len[0], p.gp0[1], p.runs > 1 ? p.len[1] : 0);
+        });
+    if (blockIdx.x == gridDim.x - 1 && tid == SKIP3_TB - 1) {
+        const uint32_t listed = before + s_scan[tid];
+        const long long dense = ((long long)n * (G::PAIRS * 10) + 63) / 64;      // the dense form's passes: 64 of the crop's 100 tiles each
+        words[SK3_PAIRS] = (uint32_t)(n * G::PAIRS); words[SK3_LISTED] = pairs; words[SK3_PASSES] = listed; words[SK3_FILLED] = 0;
+        words[SK3_USE] = skip3_use_list(listed, dense) ? 1u : 0u;
+    }
+}
+
+// a thread per listed pass: its descriptor; then SKIP3_FC crops per workgroup, a wave after the other: the row pairs outside the listed range
+// <- the empty crop's (a pair is 10 x 128 floats).  Nothing to do when the dense form runs.  (n * 16 threads, fewer than 3 n passes.)  One add to
+// the counter per workgroup: an add per crop is 25600 of them on one word, and they took longer than the copy
+static constexpr int SKIP3_FC = 16;
+__global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
+                                                   const uint4* __restrict__ act3e, uint4* __restrict__ act3, int* __restrict__ desc) {
+    using G = Skip3Geom;
+    constexpr int PQ = 10 * 128 * 4 / 16;             // 16-byte units per pair
+    static_assert(Skip3Geom::BLOCK_PASSES * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass: 256 threads per SKIP3_FC crops");
+    __shared__ uint32_t s_filled;
+    const int lane = threadIdx.x & 63;
+    if (!words[SK3_USE]) return;
+    if (threadIdx.x == 0) s_filled = 0;
+    __syncthreads();
+    const int gid = blockIdx.x * 256 + threadIdx.x;
+    if (gid < (int)words[SK3_PASSES]) {
+        int4* dst = reinterpret_cast<int4*>(desc + (size_t)gid * G::DESC);
+        const int4 r = dst[0];
+        Skip3Pass p{};
+        p.runs = r.w ? 2 : 1; p.n = r.y + r.w;
+        p.gp0[0] = r.x; p.len[0] = r.y; p.gp0[1] = r.z; p.len[1] = r.w;
+        int d[G::DESC];
+        skip3_describe(p, d);
+#pragma unroll
+        for (int k = 0; k < G::DESC / 4; ++k) dst[k] = make_int4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+    }
+    const bool all = words[SK_EMPTY_RANGE] != 0;
+    uint32_t filled = 0;
+    for (int k = 0; k < SKIP3_FC / 4; ++k) {
+        const int crop = blockIdx.x * SKIP3_FC + (threadIdx.x >> 6) * (SKIP3_FC / 4) + k;
+        if (crop >= n) break;
+        const int2 b = bands[crop];
+        const SkipPairs r = all ? SkipPairs{0, G::PAIRS - 1} : skip3_pairs({b.x, b.y});
+        for (int q = 0; q < G::PAIRS; ++q) {
+            if (q >= r.lo && q <= r.hi) continue;
+            ++filled;
+#pragma unroll
+            for (int i = lane; i < PQ; i += 64) act3[((size_t)crop * G::PAIRS + q) * PQ + i] = act3e[q * PQ + i];
+        }
+    }
+    if (lane == 0 && filled) atomicAdd(&s_filled, filled);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_filled) atomicAdd(&words[SK3_FILLED], s_filled);
 }
