@@ -548,14 +548,16 @@ int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32
  * 134217728); its bits 0-11 select the fp32-activation chain, bit 28 keeps conv1 and conv2 apart, bit 29 forces this kernel at any batch size,
  * bit 30 the older fused kernel.
  * What the last such call did (waits for the context's stream): *passes of the batch, *listed of them computed, *bytes_filled of conv2's output
- * copied instead; zeros before the first such call.  No reference counterpart; any pointer may be NULL.  (ABI 15) */
+ * taken from that image instead of computed (copied for the dense conv3; read from the image in place by the listed conv3 below, which copies
+ * nothing -- the count is the same either way); zeros before the first such call.  No reference counterpart; any pointer may be NULL.  (ABI 15) */
 int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* listed, uint64_t* bytes_filled);
 
 /* Where those passes are skipped, conv3 (k_conv5_wpair) computes only the row pairs -- two rows of its 20 x 20 map, pooled to one row of its
  * output -- that read a row of conv2's output with a blob in it, six listed pairs to a pass; the other row pairs are copied from the output of an
  * all-zero crop, made when the weights are loaded.  The crops' bytes decide, on the device, in every call, also whether the listed form pays at
  * all (a batch of noise lists every pair: the dense kernel runs then); the results are the bits of the dense kernel.  Bit 26 of TREXHIP_CONV_GEOM
- * (value 67108864) switches this off.
+ * (value 67108864) switches this off.  The listed form reads the background rows of conv2's output from the all-zero crop's image itself; bit 25
+ * (value 33554432) has them copied into conv2's output first, as for the dense kernel.
  * What the last such call did (waits for the context's stream): *pairs of the batch (10 per crop), *listed of them to be computed, *passes the
  * listed form walked (0: the dense kernel ran), *bytes_filled of conv3's output copied instead; zeros before the first such call.  No reference
  * counterpart; any pointer may be NULL.  (ABI 16) */

@@ -1,7 +1,8 @@
 """How much of conv1+conv2 the benchmark's crops need (dev tool, needs the GPU): one step of bench.py's default workload (config C4, 256 frames,
 gray, FP16X3) through the same Pipeline, then the device counters of the last identify call of lane 0 (trexhip_identify_skip_stats): passes of
-the batch, passes the role-split kernel computed, bytes of V3 rows filled from the empty crop's image -- and the crops' own row statistics, on
-the host -- and the counters of the listed conv3 (trexhip_identify_skip3_stats): row pairs of the batch, row pairs listed, the passes its listed
+the batch, passes the role-split kernel computed, bytes of V3 rows taken from the empty crop's image instead (`v3_bytes_filled`: copied into V3
+where the dense conv3 runs; where the listed conv3 runs, as on these crops, nothing is copied and the kernel reads those rows from the image
+itself -- the count is the same) -- and the crops' own row statistics, on the host -- and the counters of the listed conv3 (trexhip_identify_skip3_stats): row pairs of the batch, row pairs listed, the passes its listed
 form walked (0: the dense kernel ran) against the dense kernel's, bytes of act3 filled from the empty crop's.  Nothing here is timed.  One JSON line.
    python tools/skip_stats.py"""
 import json

@@ -1395,7 +1395,15 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     TRY(B.device_bytes(&net->logits, N * net->classes * 4, who));
     if (W == 80 && H == 80) {                  // the Winograd-domain operand images of the 80 x 80 chain
         TRY(B.device_bytes(&net->v2, N * 40 * V2_ROWB, who));
-        TRY(B.device_bytes(&net->v3, N * 20 * V3_ROWB, who));
+        // (the empty crop's V3 image in front of V3 and behind it, in the same allocation: the listed conv3 reads background rows from the nearer
+        // one through the buffer resource it reads V3 through, cnn_skip3.h)
+        const size_t img = net->v3e ? (size_t)SkipGeom::V3_ROWS * V3_ROWB : 0;
+        TRY(B.device_bytes(&net->v3, N * 20 * V3_ROWB + 2 * img, who));
+        if (rc == TREXHIP_OK && img) {
+            TH_CHECK_HIP(hipMemcpyAsync(net->v3, net->v3e, img, hipMemcpyDeviceToDevice, ctx->stream));
+            TH_CHECK_HIP(hipMemcpyAsync(net->v3 + img + N * 20 * V3_ROWB, net->v3e, img, hipMemcpyDeviceToDevice, ctx->stream));
+            net->v3 += img;
+        }
     }
     if (net->v3e) {                            // the pass list of the role-split kernel
         const size_t n_pass = (N * SkipGeom::V3_ROWS + SkipGeom::RPP - 1) / SkipGeom::RPP;
@@ -1406,6 +1414,7 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint2), who));
         TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 4, who));
         TRY(B.device_bytes(&net->skip3_desc, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Geom::DESC * 4, who));
+        TRY(B.device_bytes(&net->skip3_rows, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Reach::WORDS * 4, who));
     }
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
     TRY(B.pinned(&net->h_probs, N * net->classes, who));
@@ -1531,7 +1540,7 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
                 net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr);
     TH_CHECK_HIP(hipGetLastError());
     TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV3_WPAIR.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV3_WPAIR.lds));
-    K_CONV3_WPAIR(ctx->stream, p.conv3.grid, net->v3e, net->w3w, net->b3, net->act3e, net->inv3w, 1, net->d_skip + SK3_EMPTY_CTR, p.n_big3, nullptr, nullptr);
+    K_CONV3_WPAIR(ctx->stream, p.conv3.grid, net->v3e, net->w3w, net->b3, net->act3e, net->inv3w, 1, net->d_skip + SK3_EMPTY_CTR, p.n_big3, nullptr, nullptr, nullptr);
     TH_CHECK_HIP(hipGetLastError());
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return TREXHIP_OK;
@@ -1546,6 +1555,9 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
     const CnnPlan p = cnn_plan(net.W, net.H, net.CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0, ctx->tune_conv_geom, n, ctx->n_cus);
     const Pass f{net, p, ctx->stream, ctx->cnn_mode, d_crops, n, d_probs, d_logits};
     hipStream_t s = f.s;
+    // the back image lies behind the ALLOCATION's rows, whatever this call's n is
+    const long long alloc_rows = (long long)net.max_crops * SkipGeom::V3_ROWS;
+    const bool direct = p.v3_direct && skip3_direct_fits(alloc_rows);
     // (the guard words in front of the plan start at zero: the plan's writer -- the last reader of all three -- hands them back zeroed; net_forward
     // clears them itself behind a pass that was not queued to its end)
     stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
@@ -1563,7 +1575,12 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
                 K_CROP_BANDS(s, ceil_div(n, 4), d_crops, n, net.skip_bands);
                 K_PASS_COUNT(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts);
                 K_PASS_LIST(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts, net.skip_list);
-                K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3));
+                if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
+                    K_PAIR_COUNT(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
+                    K_PAIR_LIST(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
+                }
+                K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3),
+                          (int)direct);
             }
             K_CONV12_RS(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
                         p.pk2, net.d_ovfc, p.skip ? net.skip_list : nullptr, p.skip ? net.d_skip + SK_LEN : nullptr);
@@ -1583,13 +1600,12 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         stage_end(ctx, TREXHIP_STAGE_CONV2);
         stage_begin(ctx, TREXHIP_STAGE_CONV3);
         if (pre) {
-            if (p.skip3) {     // the row pairs to compute, packed into passes, and the others' act3; which form of the kernel runs is the device's word
-                K_PAIR_COUNT(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
-                K_PAIR_LIST(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
-                K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e), reinterpret_cast<uint4*>(net.act3), net.skip3_desc);
-                K_CONV3_WPAIR_LIST(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.d_skip);
+            if (p.skip3) {     // the listed passes' descriptors and row sources, and the other pairs' act3; which form of the kernel runs is the device's word
+                K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e), reinterpret_cast<uint4*>(net.act3), net.skip3_desc,
+                            net.skip3_rows, alloc_rows, (int)direct);
+                K_CONV3_WPAIR_LIST(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.skip3_rows, net.d_skip);
             }
-            K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3, nullptr, p.skip3 ? net.d_skip : nullptr);
+            K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3, nullptr, nullptr, p.skip3 ? net.d_skip : nullptr);
         }
         else if (p.chain == Chain::FP32_ACT)
             K_CONV3_WINO(s, p.conv3.grid, net.act2, net.w3w, net.b3, net.act3, net.inv3w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS3));

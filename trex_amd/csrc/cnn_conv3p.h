@@ -30,14 +30,21 @@
 // The LISTED form (cnn_skip3.h) computes only the row pairs whose V3 rows hold more than the empty crop's image.  A pass is then SIX listed row
 // pairs -- 60 of the 64 tile slots, so that a lane's pair slot and its place in the pair are the same in every pass -- from at most two runs (one
 // crop's consecutive pairs): 2 pA + 4 and 2 pB + 4 V3 rows, at most NR together.  k_pair_list (cnn_skip_kernels.h) has written per pass what the
-// kernel needs (skip3_describe): the staging goes through one buffer resource from run A's first row, a lane whose row slot lies behind run A
-// adds the distance to run B (a compare, a select and an add per DMA instruction), what lies behind run B is out of range and reads zeros as
-// before; y comes from the listed pair's q; the stores go to the listed pair's place in act3, a per-lane select between two of the pass's six
+// kernel needs (skip3_describe) and k_act3_fill where each of its rows comes from (skip3_row_words): a crop's own rows from V3, its background
+// rows from the empty crop's image, which lies in front of V3 and behind it in V3's allocation -- k_v3_fill copies nothing where this form runs,
+// and what V3 holds outside the own rows is never read.  The staging goes through one buffer resource per pass whose base the table names; the
+// table's entry i, in lane i, is the byte offset of row slot i's source, and a lane fetches its slot's entry and adds its constant (a shift, a
+// ds_bpermute_b32 and an add per DMA instruction, where a compare, a select and an add jumped the gap between the runs before); what lies
+// behind the pass's rows has an offset behind the resource's end and reads zeros as before; y comes from the listed pair's q; the stores go to
+// the listed pair's place in act3, a per-lane select between two of the pass's six
 // pair offsets (tiles i and i + 4 h can lie in different pairs).  Everything else -- the taps, their order, the fold, the tail -- is the dense
 // form's, so a listed pair's outputs are the dense kernel's bits.  Both forms are launched; `words` (SK3_USE) names the one that runs.
 // Measured (profiles/conv3_listed_pairs.txt; the benchmark's 25600 crops: 31381 listed passes against 40000 dense ones): 4511 -> 3573 us under a
-// kernel trace, a listed pass costs 1.01 dense passes; the dense instance keeps its registers (256 + 210, no scratch), the listed one has 256 + 230,
-// no scratch.  (The pass's values are plain scalars on purpose: as members of a struct handed to the lambdas they stayed in scratch memory, 104
+// kernel trace, a listed pass cost 1.01 dense passes.  With the background rows read from the image (profiles/v3_direct_rows.txt, 31393 listed
+// passes): 3669 -> 3542 us under a kernel trace, 116.9 -> 112.8 ns per listed pass (half of what it stages now comes from 200 KB that stay in
+// L2), 1.00 dense passes; with the table entry fetched in the tap that needs it -- its wait in front of that tap's first MFMA -- 3634 us.  The
+// dense instance keeps its registers (256 + 210, no scratch, 2 vector spills), the listed one has 256 + 242, no scratch, no vector spills (256 +
+// 230 and 20 spills before).  (The pass's values are plain scalars on purpose: as members of a struct handed to the lambdas they stayed in scratch memory, 104
 // bytes per lane in BOTH instances.)
 template <bool LISTED>
 __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__ v3, const uint4* __restrict__ wp /*[4][5][8][2][2][128] x 16 B*/,
@@ -45,6 +52,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                                                      const int n_crops, uint32_t* __restrict__ pass_ctr,
                                                      const int n_big_dense /* tickets of PK passes; the passes behind them go out one by one */,
                                                      const int* __restrict__ desc /* LISTED: DESC words per pass */,
+                                                     const uint32_t* __restrict__ rowsrc /* LISTED: Skip3Reach::WORDS per pass, the sources of its rows */,
                                                      const uint32_t* __restrict__ words /* Net::d_skip; null: the dense form, unconditionally */) {
     constexpr int CI = 64, CO = 128, S = 20, TPW = 2;
     constexpr int BD = 5;         // taps of lead of the weight fragments (measured above)
@@ -59,6 +67,8 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
     using L = Skip3Geom;
+    using LR = Skip3Reach;
+    static_assert(LR::ROWB == V3_ROWB && SkipGeom::V3_ROWS == S, "the images in front of V3 and behind it are S rows of V3_ROWB bytes");
     static_assert(L::NR == G::NR && L::SLOTS * G::TPP <= G::MB && L::PAIRS * 2 == S, "a listed pass fits the dense pass's rows and tiles");
     if (words && (words[SK3_USE] != 0) != LISTED) return;
     const int total_tiles = n_crops * G::TPC;
@@ -85,20 +95,29 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         const int o = (wave + 4 * k) * 1024 + lane * 16;
         const int pc = o >= (G::NR + 1) * G::RP ? 1 : 0, q = o - pc * (G::NR + 1) * G::RP;
         const int row = q / G::RP, w = q - row * G::RP;
-        dvo[k] = (q < G::NR * G::RP && o < RNG) ? (uint32_t)(row * V3_ROWB + pc * 1280 + (w < G::RP0 ? w : G::RP0 - 16)) : 0x80000000u;
+        const bool real = q < G::NR * G::RP && o < RNG;
+        const uint32_t inrow = (uint32_t)(pc * 1280 + (w < G::RP0 ? w : G::RP0 - 16));
+        // LISTED: the row slot and the byte in the row; the slot's source is the pass's (its table's entry NR: none)
+        dvo[k] = LISTED ? (real ? (uint32_t)row << LR::ROW_SHIFT | inrow : (uint32_t)G::NR << LR::ROW_SHIFT)
+                        : real ? (uint32_t)(row * V3_ROWB) + inrow : 0x80000000u;
     }
     const uint32_t mbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + G::RP + wave * 1024));
-    // (LISTED: nrows_ counts the rows from run A's first to run B's last, the gap included)
+    // (LISTED: qmin_ is the row of V3's allocation the pass's resource starts at -- the empty crop's image lies in front of V3 and behind it,
+    // cnn_skip3.h --, and the resource has one size: the table's offsets are in range, what it calls none is not)
     auto stage_rsrc = [&](const int g, const int qmin_, const int nrows_) {
-        const unsigned long long base = wave_uniform64(reinterpret_cast<unsigned long long>(v3) + (unsigned long long)qmin_ * V3_ROWB + (unsigned)(g * 2560));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0, __builtin_amdgcn_readfirstlane(nrows_ * V3_ROWB - g * 2560), 0x00020000);
+        const unsigned long long base = wave_uniform64(reinterpret_cast<unsigned long long>(v3) + (unsigned long long)(long long)(qmin_ - (LISTED ? S : 0)) * V3_ROWB + (unsigned)(g * 2560));
+        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0,
+                                                 LISTED ? (int)(LR::NUM_RECORDS - (unsigned)(g * 2560)) : __builtin_amdgcn_readfirstlane(nrows_ * V3_ROWB - g * 2560), 0x00020000);
     };
     // (M0 is written and not restored: nothing else in this kernel reads it -- checked in the ISA)
-    // (LISTED: nab_ = the bytes of run A's rows, gapb_ = the bytes between them and run B's; the lanes marked out of range stay so: both are < 2^31)
-#define P3_DMA(k_, srs_, buf_, nab_, gapb_)                                                                                      \
+    // (LISTED: the pass's table, entry i in lane i: the lane fetches its row slot's entry -- P3_SRC, a shift and a permute, one tap AHEAD of the
+    // instruction that needs it: the permute's answer takes as long as an LDS read, and waiting for it in the tap that issued it holds up that tap's
+    // first MFMA -- and adds its constant)
+#define P3_SRC(k_, tab_) (uint32_t)__builtin_amdgcn_ds_bpermute((int)(dvo[k_] >> (LR::ROW_SHIFT - 2)), (int)(tab_))
+#define P3_DMA(k_, srs_, buf_, src_)                                                                                             \
     do {                                                                                                                         \
         if ((k_) < NDW - 1 || wave + 4 * (NDW - 1) < NI) {                                                                       \
-            const uint32_t vo_ = LISTED ? dvo[k_] + (dvo[k_] >= (uint32_t)(nab_) ? (uint32_t)(gapb_) : 0u) : dvo[k_];            \
+            const uint32_t vo_ = LISTED ? dvo[k_] + (src_) : dvo[k_];                                                            \
             asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds"                          \
                          :: "s"(mbase), "n"((buf_) * G::BUF + (k_) * 4096), "v"(vo_), "s"(srs_) : "memory", "scc");               \
         }                                                                                                                        \
@@ -124,18 +143,17 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     // relative to the pass's first pair) and the lane's two pair entries
     // (the descriptor as it is loaded: word lane % DESC and the lane's two pair entries)
     int raw_w = 0, ent[TPW] = {};
+    uint32_t tab = 0;
     auto pass_fetch = [&](const int pass_) {
         const int* d = desc + (size_t)pass_ * L::DESC;
         raw_w = d[lane & (L::DESC - 1)];
+        tab = rowsrc[(size_t)pass_ * LR::WORDS + (lane & (LR::WORDS - 1))];
 #pragma unroll
         for (int m = 0; m < TPW; ++m) ent[m] = d[S3_SLOT + lps[m]];
     };
-    auto pass_decode = [&](int& qmin_, int& nrows_, int& na_, int& gap_, int& gp0_, int& span_, uint32_t (&rel_)[L::SLOTS]) {
+    auto pass_decode = [&](int& qmin_, int& gp0_, int& span_, uint32_t (&rel_)[L::SLOTS]) {
         const int w = raw_w;
-        qmin_ = __builtin_amdgcn_readlane(w, S3_ROW0);
-        na_ = __builtin_amdgcn_readlane(w, S3_NA) * V3_ROWB;
-        gap_ = __builtin_amdgcn_readlane(w, S3_GAP) * V3_ROWB;
-        nrows_ = __builtin_amdgcn_readlane(w, S3_ROWS) + __builtin_amdgcn_readlane(w, S3_GAP);
+        qmin_ = __builtin_amdgcn_readlane((int)tab, LR::BASE);
         gp0_ = __builtin_amdgcn_readlane(w, S3_GP0);
         span_ = __builtin_amdgcn_readlane(w, S3_SPAN);
 #pragma unroll
@@ -144,13 +162,13 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             rel_[s2] = rp == (uint32_t)S3_IDLE ? 0x80000000u : rp * (uint32_t)(G::TPP * CO * 4);
         }
     };
-    int qmin = 0, nrows = 0, na = 0, gap = 0, gp0 = 0, span = 0;
+    int qmin = 0, nrows = 0, gp0 = 0, span = 0;
     uint32_t rel[L::SLOTS] = {};
-    if (LISTED) { pass_fetch(pass); pass_decode(qmin, nrows, na, gap, gp0, span, rel); }
+    if (LISTED) { pass_fetch(pass); pass_decode(qmin, gp0, span, rel); }
     else wino_pass_rows<G, S>(pass, total_tiles, qmin, nrows);
     const __amdgpu_buffer_rsrc_t srs0 = stage_rsrc(0, qmin, nrows);
 #pragma unroll
-    for (int k = 0; k < NDW; ++k) P3_DMA(k, srs0, 0, na, gap);
+    for (int k = 0; k < NDW; ++k) P3_DMA(k, srs0, 0, P3_SRC(k, tab));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // tap tt of unit g: chunk tt / 10, kernel row (tt % 10) / 2, position PAIRS[g][tt & 1]; its weights [chunk][ky][position] x BV x 16 bytes
@@ -257,7 +275,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         const bool draw = pass >= big_end || pass % PK == PK - 1;          // the last pass of a ticket draws the next one
         if (draw && tid == 0) s_next_pass = ticket_first((int)atomicAdd(pass_ctr, 1u) + (int)gridDim.x);   // read by everyone after the first unit's barrier
         bool have_next = false;
-        int qmin_n = qmin, nrows_n = nrows, na_n = na, gap_n = gap, gp0_n = gp0, span_n = span;
+        int qmin_n = qmin, nrows_n = nrows, gp0_n = gp0, span_n = span;
         uint32_t rel_n[L::SLOTS];
 #pragma unroll
         for (int s2 = 0; s2 < L::SLOTS; ++s2) rel_n[s2] = rel[s2];
@@ -270,14 +288,14 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                 if (have_next) wino_pass_rows<G, S>(next_pass, total_tiles, qmin_n, nrows_n);
             }
             // (without a next pass the descriptor fetched is this pass's own: the next = this one once more)
-            if (LISTED && last_u) pass_decode(qmin_n, nrows_n, na_n, gap_n, gp0_n, span_n, rel_n);
+            if (LISTED && last_u) pass_decode(qmin_n, gp0_n, span_n, rel_n);
             const uint8_t* pbase = ldsb + (g & 1) * G::BUF;
             // staged under this unit: the next unit of this pass, or unit 0 of the next pass (without one: this pass's once more, into the buffer
             // nobody reads again)
             const int sg = last_u ? 0 : g + 1;
             const int sqmin = last_u ? qmin_n : qmin, snrows = last_u ? nrows_n : nrows;
-            const int sna = last_u ? na_n : na, sgap = last_u ? gap_n : gap;
             const __amdgpu_buffer_rsrc_t srs = stage_rsrc(sg, sqmin, snrows);
+            uint32_t src_next = 0;
             // A fragments AD taps ahead (tap tt: position slot (tt / 10) * 2 + (tt & 1), kernel row (tt % 10) / 2)
             uint4 af[AD + 1][TPW][2];
 #pragma unroll
@@ -290,6 +308,10 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
 #pragma clang loop unroll(full)
             for (int tt = 0; tt < 40; ++tt) {
                 const int cur = tt % (AD + 1), nxt = (tt + AD) % (AD + 1);
+                // (LISTED: the source of the next tap's DMA instruction, asked for in front of this tap's MFMAs; under the last unit `tab` is the
+                // next pass's already: fetched under the unit before)
+                const uint32_t src_cur = src_next;
+                if (LISTED && tt + 1 >= DT0 && tt + 1 < DT0 + NDW) src_next = P3_SRC(tt + 1 - DT0, tab);
                 if (tt + AD < 40) {
                     const uint8_t* an = pbase + (((tt + AD) / 10) * 2 + ((tt + AD) & 1)) * G::PS;
 #pragma unroll
@@ -308,7 +330,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                     have_next = next_pass < n_pass;
                     pass_fetch(have_next ? next_pass : pass);
                 }
-                if (tt >= DT0 && tt < DT0 + NDW) P3_DMA(tt - DT0, srs, (g & 1) ^ 1, sna, sgap);
+                if (tt >= DT0 && tt < DT0 + NDW) P3_DMA(tt - DT0, srs, (g & 1) ^ 1, src_cur);
                 const int hp = tt & 1;
                 const f16x8 b1 = __builtin_bit_cast(f16x8, bq[tt % 8][0]);
                 const f16x8 b2 = __builtin_bit_cast(f16x8, bq[tt % 8][1]);
@@ -352,11 +374,12 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
 #pragma unroll
         for (int s2 = 0; s2 < L::SLOTS; ++s2) { rel_prev[s2] = rel[s2]; rel[s2] = rel_n[s2]; }
         if (!have_next) break;
-        pass = next_pass; qmin = qmin_n; nrows = nrows_n; na = na_n; gap = gap_n; gp0 = gp0_n; span = span_n;
+        pass = next_pass; qmin = qmin_n; nrows = nrows_n; gp0 = gp0_n; span = span_n;
     }
     // the last pass's tail has no next pass to run under (fold of unit 2 ran under unit 3; unit 3's pair is positions 0 and 7, taken by the tail itself)
 #pragma unroll
     for (int b = 0; b < 16; ++b) tail(ors_prev, b / 8, b % 8);
 #undef P3_DMA
+#undef P3_SRC
 #undef P3_PIN
 }

@@ -25,6 +25,7 @@ struct Net {
     float *wf1 = nullptr, *bf1 = nullptr, *lng = nullptr, *lnb = nullptr, *wf2t = nullptr, *bf2 = nullptr;
     float *act1 = nullptr, *act2 = nullptr, *act3 = nullptr, *fc1 = nullptr, *probs = nullptr, *logits = nullptr;   // act: [n][H/2][W/2][16], [n][H/4][W/4][64], [n][H/8][W/8][128]
     uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
+                                               // (v3: a copy of v3e lies in front of it and behind its max_crops * 20 rows, where v3e exists)
     uint8_t* crops = nullptr;
     // skipping the passes of k_conv12_rs whose crop rows are all background (cnn_skip.h, cnn_skip_kernels.h)
     uint8_t* v3e = nullptr;                    // the V3 image of an all-zero crop [20][V3_ROWB], made when the weights are loaded (1 channel, 80 x 80)
@@ -37,6 +38,7 @@ struct Net {
     uint2* skip3_counts = nullptr;             // listed passes and pairs per workgroup of k_pair_count
     uint32_t* skip3_tcounts = nullptr;         // listed passes per thread of it (Skip3Geom::BLOCK crops)
     int* skip3_desc = nullptr;                 // Skip3Geom::DESC words per listed pass
+    uint32_t* skip3_rows = nullptr;            // Skip3Reach::WORDS words per listed pass: where the rows it stages come from
     float* h_probs = nullptr;                  // pinned
     Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
     // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one

@@ -4,14 +4,17 @@
 #include <algorithm>
 #include "../../include/trexhip.h"
 #include "cnn_geom.h"
+#include "cnn_skip3.h"
 
 namespace trexhip {
 
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
 //   ROLE_SPLIT  k_conv12_rs (conv1 inside conv2, one workgroup per CU)   -> k_conv5_wpair       1 channel, aligned crops, >= 3200 crops
 //               (in front of it, unless bit 27 is set: k_crop_bands, k_pass_count, k_pass_list, k_v3_fill -- passes of background rows are skipped;
-//                then, unless bit 26 is set as well: k_pair_count, k_pair_list, k_act3_fill and BOTH forms of k_conv5_wpair, the dense one and the
-//                one that walks the listed row pairs -- the word k_pair_list writes names the one that runs, the other returns at once)
+//                unless bit 26 is set as well: k_pair_count and k_pair_list in front of k_v3_fill, k_act3_fill and BOTH forms of k_conv5_wpair, the
+//                dense one and the one that walks the listed row pairs, behind conv2 -- the word k_pair_list writes names the one that runs, the
+//                other returns at once.  The listed form reads the background rows from the empty crop's image itself and k_v3_fill returns at
+//                once where that form runs; bit 25 keeps the copy -- the fill always runs and the listed form reads every row from V3)
 //   FUSED_2WG   k_conv12_wpre (the same, two workgroups per CU)          -> k_conv5_wpair       1 channel, aligned crops, fewer
 //   TWO_KERNEL  k_conv1_wpre -> k_conv2_wpre2                            -> k_conv5_wpair       3 channels, or TREXHIP_CONV_GEOM bit 28
 //   FP32_ACT    conv1 -> act1 -> k_conv5_stream -> act2 -> k_conv5_wino                         unaligned crops, or any of bits 0-11
@@ -49,6 +52,8 @@ struct CnnPlan {
     bool skip3;                     // where skip is on: conv3 computes only the row pairs that read a row with a blob in it (cnn_skip3.h); off: bit 26
     int skip3_grid;                 // workgroups of k_pair_count / k_pair_list
     Launch act3_fill;               // k_act3_fill: 16 crops (SKIP3_FC) per workgroup
+    bool v3_direct;                 // where skip3 is on: the listed conv3 reads background rows from the empty crop's image, k_v3_fill copies only for the
+                                    // dense form; off: bit 25, or a batch whose V3 is longer than both images' reach (skip3_direct_fits)
 };
 
 inline int ceil_div(const int a, const int b) { return (a + b - 1) / b; }
@@ -109,6 +114,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
     if (p.skip3) {
         p.skip3_grid = ceil_div(ceil_div(n, 32 /* Skip3Geom::BLOCK crops per thread */), 256);
         p.act3_fill = {ceil_div(n, 16), n};
+        p.v3_direct = !(geom & (1 << 25)) && skip3_direct_fits((long long)n * SkipGeom::V3_ROWS);
     }
 
     const int n_pass2 = ceil_div(n * 20, W2bGeom::RPP), n_pass3 = ceil_div(n * GW::TPC, GW::MB);

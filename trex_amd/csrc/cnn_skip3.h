@@ -5,7 +5,7 @@
 // conv3 is the same kind of layer as conv1 and conv2 (cnn_skip.h): pooled output row q -- a ROW PAIR of the kernel, conv rows 2q and 2q + 1 --
 // reads the V3 rows skip_layer_lo(q) .. skip_layer_hi(q).  A pair all of whose V3 rows are rows the rule of cnn_skip.h calls empty equals, bit
 // for bit, the same pair of the all-zero crop's act3 (Net::act3e, made once per loaded network): such a V3 row holds the empty image's bits
-// whether k_conv12_rs computed it or k_v3_fill copied it, the rows outside the crop are the zero row either way, and the kernel's arithmetic per
+// whether k_conv12_rs computed it, k_v3_fill copied it or the listed kernel reads it from the image itself (skip3_row_sources), the rows outside the crop are the zero row either way, and the kernel's arithmetic per
 // output element does not depend on the pass, tile or lane it lands in.
 #pragma once
 #include "cnn_skip.h"
@@ -95,6 +95,81 @@ TREXHIP_HD constexpr void skip3_describe(const Skip3Pass& p, int (&d)[Skip3Geom:
     }
 }
 
+// Where the staged rows of a listed pass come from.  Only the rows inside skip_rows(band) of a crop -- its OWN rows -- are read from V3: every
+// other row of the crop holds the empty image's bits by the rule of cnn_skip.h, and the kernel takes it from that image itself (20 rows that stay
+// in every L2) instead of from a copy of it in V3.  Nothing writes the rows of V3 outside the own rows then: they hold what an earlier call, or a
+// neighbour's straddling conv2 pass, left there, and must never be read.
+//   src[i], i < NR: the source of LDS row slot 1 + i (the numbering of S3_SLOT: run A's rows, run B's behind them)
+//     >= 0 and < S3_SRC_IMAGE   V3 row crop * V3_ROWS + y
+//     S3_SRC_IMAGE | y          row y of the empty image
+//     S3_SRC_NONE               behind the pass's rows: reads zeros
+// own_a / own_b: skip_rows of the bands of run A's and run B's crop ({0, V3_ROWS - 1}: every row from V3 -- where k_v3_fill has copied the image)
+enum : int { S3_SRC_NONE = -1, S3_SRC_IMAGE = 1 << 30 };
+TREXHIP_HD constexpr void skip3_row_sources(const Skip3Pass& p, const SkipRows own_a, const SkipRows own_b, int (&src)[Skip3Geom::NR]) {
+    using G = Skip3Geom;
+    const bool two = p.runs > 1;
+    const Skip3Rows a = skip3_run_rows(p.gp0[0], p.len[0]);
+    const Skip3Rows b = two ? skip3_run_rows(p.gp0[1], p.len[1]) : Skip3Rows{a.row0 + a.n, 0};
+    const int ca = p.gp0[0] / G::PAIRS, cb = two ? p.gp0[1] / G::PAIRS : ca;
+    for (int i = 0; i < G::NR; ++i) {      // (no index that is a variable but the unrolled i)
+        const bool in_a = i < a.n, in_b = !in_a && i - a.n < b.n;
+        const int row = in_a ? a.row0 + i : b.row0 + (i - a.n);
+        const int y = row - (in_a ? ca : cb) * SkipGeom::V3_ROWS;
+        const SkipRows own = in_a ? own_a : own_b;
+        src[i] = in_a || in_b ? (y >= own.lo && y <= own.hi ? row : S3_SRC_IMAGE | y) : S3_SRC_NONE;
+    }
+}
+
+// The sources as the kernel reads them: one buffer resource per pass and a 32-bit byte offset per row slot.  A resource reaches 4 GB forward from
+// its base and V3 is 5.2 GB at 25600 crops, so the image lies TWICE in V3's allocation, in front of it and behind it:
+//   rows of the allocation:  0 .. V3_ROWS - 1 the image | V3_ROWS + r: V3 row r | V3_ROWS + total + y: the image again
+// and a pass starts its resource at the front image where its last row is within reach of that, else at its own first row, from where the back
+// image is within reach as long as skip3_direct_fits(total).  A pass that reads no image row starts at its first row (any batch size).
+//   w[i], i < NR   byte offset of slot 1 + i's source from the resource's base, minus i << S3_ROW_SHIFT (the lane adds its packed constant
+//                  row << S3_ROW_SHIFT | byte in the row and has the offset); none: S3_OFF_NONE, at or behind the resource's S3_NUM_RECORDS
+//   w[NR .. 30]    none (the lanes of a staging instruction that cover no row use entry NR)
+//   w[31]          the row of the allocation the resource starts at
+struct Skip3Reach {
+    static constexpr int ROWB = 10240;                                      // bytes of a V3 row (V3_ROWB, cnn_wpre.h)
+    static constexpr int WORDS = 32, BASE = 31, ROW_SHIFT = 18;
+    static constexpr unsigned REACH = 0xF0000000u;                          // every source byte of a pass lies below this offset
+    static constexpr unsigned NUM_RECORDS = 0xF8000000u;                    // of the resource (a unit's 2560-byte step comes off base and size alike)
+    static constexpr unsigned OFF_NONE = 0xFFFF0000u;                       // + a byte in the row: still below 2^32, never below NUM_RECORDS
+    static constexpr long long REACH_ROWS = REACH / ROWB;
+    static constexpr int PASS_ROWS = (Skip3Geom::SPAN + Skip3Geom::SLOTS) * SkipGeom::POOL + 2 * Skip3Geom::HALO;   // first to last row of a pass, at most
+    static_assert(ROWB * 4 <= (1 << ROW_SHIFT) && Skip3Geom::NR < WORDS - 1 && (Skip3Geom::NR << ROW_SHIFT) > 0, "the packed constant");
+    static_assert(NUM_RECORDS - 4 * 2560 >= REACH && OFF_NONE >= NUM_RECORDS, "none is out of range in every unit's resource");
+};
+// can every pass of a batch of `total` V3 rows reach an image?  (a pass out of the front image's reach starts behind row
+// REACH_ROWS - V3_ROWS - PASS_ROWS - 1 and needs the back image's last row within REACH_ROWS of it)
+TREXHIP_HD constexpr bool skip3_direct_fits(const long long total) {
+    using R = Skip3Reach;
+    return total <= 2 * R::REACH_ROWS - 2 * SkipGeom::V3_ROWS - R::PASS_ROWS - 1;
+}
+TREXHIP_HD constexpr void skip3_row_words(const Skip3Pass& p, const SkipRows own_a, const SkipRows own_b, const long long total,
+                                          unsigned (&w)[Skip3Reach::WORDS]) {
+    using G = Skip3Geom;
+    using R = Skip3Reach;
+    constexpr int IMG = SkipGeom::V3_ROWS;
+    int src[G::NR] = {};
+    skip3_row_sources(p, own_a, own_b, src);
+    const bool two = p.runs > 1;
+    const Skip3Rows a = skip3_run_rows(p.gp0[0], p.len[0]);
+    const Skip3Rows b = two ? skip3_run_rows(p.gp0[1], p.len[1]) : Skip3Rows{a.row0 + a.n, 0};
+    const long long last = b.row0 + b.n - 1;                               // the pass's first row is a.row0
+    bool image = false;
+    for (int i = 0; i < G::NR; ++i) image = image || (src[i] != S3_SRC_NONE && (src[i] & S3_SRC_IMAGE));
+    const bool front = image && IMG + last + 1 <= R::REACH_ROWS;
+    const long long base = front ? 0 : IMG + a.row0, back = IMG + total;
+    for (int i = 0; i < R::WORDS; ++i) {
+        const int s = i < G::NR ? src[i < G::NR ? i : 0] : S3_SRC_NONE;
+        const bool none = s == S3_SRC_NONE, img = !none && (s & S3_SRC_IMAGE);
+        const long long row = img ? (front ? 0 : back) + (s & ~S3_SRC_IMAGE) : IMG + s;
+        const unsigned off = none ? R::OFF_NONE : (unsigned)((row - base) * R::ROWB);
+        w[i] = i == R::BASE ? (unsigned)base : off - ((unsigned)i << R::ROW_SHIFT);
+    }
+}
+
 // the words of Net::d_skip that belong to the listed conv3 (the others: cnn_skip_kernels.h)
 enum : int {
     SK3_PAIRS = 8,           // row pairs of the last call's batch
@@ -107,10 +182,12 @@ enum : int {
 };
 
 // listed passes against the dense kernel's: the listed form runs when  listed * FACTOR_NUM < dense * FACTOR_DEN.  The factor is what a listed
-// pass costs in dense passes, measured on the benchmark's crops under a kernel trace (profiles/conv3_listed_pairs.txt): 3583 us for 31378 listed
-// passes against 4523 us for the dense kernel's 40000 = 1.010.  Noise crops (every pair listed: 1.067 times the dense passes) stay dense,
-// the benchmark's crops (0.784) are listed; what the list and fill kernels cost beside that is the same either way
-static constexpr int SKIP3_FACTOR_NUM = 101, SKIP3_FACTOR_DEN = 100;
+// pass costs in dense passes, measured on the benchmark's crops under a kernel trace (profiles/v3_direct_rows.txt): 3542 us for 31393 listed
+// passes = 112.8 ns against 4539 us for the dense kernel's 40000 = 113.5 ns: 0.994, and 1.004 against the parent build's dense kernel on the same
+// box -- 1.00.  (1.010 while the listed form read its background rows from a copy in V3, profiles/conv3_listed_pairs.txt.)  Noise crops (every
+// pair listed: 1.067 times the dense passes) stay dense, the benchmark's crops (0.785) are listed.  What the list kernels cost is the same either
+// way; k_v3_fill's copy, which only the dense form needs now, is left out of the choice: it matters where the two forms are within a few percent
+static constexpr int SKIP3_FACTOR_NUM = 100, SKIP3_FACTOR_DEN = 100;
 TREXHIP_HD constexpr bool skip3_use_list(const long long listed, const long long dense) {
     return listed * SKIP3_FACTOR_NUM < dense * SKIP3_FACTOR_DEN;
 }

@@ -3,11 +3,13 @@
 //   k_crop_bands   first / last non-zero row of every crop (it looks at the bytes, not at how the crop was made)
 //   k_pass_count   needed passes per block of SKIP_LB consecutive passes
 //   k_pass_list    order-preserving compaction of the needed passes into the list k_conv12_rs walks, its length, the entry behind its end
-//   k_v3_fill      the V3 rows of every pass that is NOT listed, copied from the V3 image of an all-zero crop (Net::v3e, made at load)
+//   k_v3_fill      the V3 rows of every pass that is NOT listed, copied from the V3 image of an all-zero crop (Net::v3e, made at load) -- for
+//                  the dense conv3 only: where the listed form runs and takes those rows from the image itself (`direct`), it returns at once
 // and three more for the listed form of k_conv5_wpair (the rule and the packing: cnn_skip3.h), from the same bands:
 //   k_pair_count   listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK consecutive crops
 //   k_pair_list    the passes in order, each as its two runs, the counters, and the word that names the form of conv3 that runs (SK3_USE)
-//   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place); then a wave per crop: the act3 row pairs
+//                  (both run in front of k_v3_fill, which reads that word)
+//   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place) and the sources of its rows; then a wave per crop: the act3 row pairs
 //                  that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load)
 #pragma once
 
@@ -17,7 +19,7 @@ enum : int {
     SK_EMPTY_CTR = 1,        // that run's pass counter
     SK_LEN = 2,              // passes listed by the last call
     SK_NPASS = 3,            // passes of the last call's batch
-    SK_FILLED = 4,           // V3 rows the last call filled
+    SK_FILLED = 4,           // V3 rows the last call took from the empty crop's image instead of computing them (copied by k_v3_fill or read in place)
     SK_WORDS = 16            // (8 ..: the words of the listed conv3, SK3_* in cnn_skip3.h)
 };
 static_assert(SK3_LAST < SK_WORDS, "the words of the listed conv3 lie behind these");
@@ -101,19 +103,25 @@ __global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ 
     if (need) list[off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = p;
     if (blockIdx.x == gridDim.x - 1) {                                   // the last block knows the length
         if (tid < SKIP_PAD) list[total + tid] = n_pass;
-        if (tid == 0) { words[SK_LEN] = total; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = 0; }
+        // the rows of the passes that are not listed (the batch's last pass may be short): counted here, whoever supplies them
+        if (p == n_pass - 1) {
+            const uint32_t listed_rows = total * SkipGeom::RPP - (need ? (uint32_t)(n_pass * SkipGeom::RPP - total_pairs) : 0u);
+            words[SK_LEN] = total; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = (uint32_t)total_pairs - listed_rows;
+        }
     }
 }
 
 // V3 rows of the passes that are not listed <- the empty crop's rows.  A block looks at SKIP_FB consecutive passes
-__global__ __launch_bounds__(256) void k_v3_fill(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
-                                                 const uint4* __restrict__ v3e /*[20][V3_ROWB]*/, uint4* __restrict__ v3) {
+__global__ __launch_bounds__(256) void k_v3_fill(const int2* __restrict__ bands, const int n, const uint32_t* __restrict__ words,
+                                                 const uint4* __restrict__ v3e /*[20][V3_ROWB]*/, uint4* __restrict__ v3,
+                                                 const int direct /* the listed conv3 reads the image itself: nothing to copy where it runs */) {
     using G = SkipGeom;
     static_assert(SKIP_FB == 64, "one ballot");
     __shared__ unsigned long long s_skip;
     constexpr int ROWQ = V3_ROWB / 16;
     const int total_pairs = n * G::V3_ROWS, n_pass = (total_pairs + G::RPP - 1) / G::RPP;
     const int tid = threadIdx.x, p0 = blockIdx.x * SKIP_FB;
+    if (direct && words[SK3_USE]) return;
     if (tid < 64) {
         const int p = p0 + tid;
         const bool skip = p < n_pass && !skip_needed(p, total_pairs, bands, words[SK_EMPTY_RANGE] != 0);
@@ -122,20 +130,17 @@ __global__ __launch_bounds__(256) void k_v3_fill(const int2* __restrict__ bands,
     }
     __syncthreads();
     unsigned long long m = s_skip;
-    uint32_t rows = 0;
     while (m) {
         const int b = __ffsll((long long)m) - 1;
         m &= m - 1;
         const int gp0 = (p0 + b) * G::RPP;
         const int nr = total_pairs - gp0 < G::RPP ? total_pairs - gp0 : G::RPP;
-        rows += (uint32_t)nr;
         for (int i = tid; i < nr * ROWQ; i += 256) {
             const int r = i / ROWQ, q = i - r * ROWQ;
             const int gp = gp0 + r;
             v3[(size_t)gp * ROWQ + q] = v3e[(gp % G::V3_ROWS) * ROWQ + q];
         }
     }
-    if (tid == 0 && rows) atomicAdd(&words[SK_FILLED], rows);
 }
 
 // ---- the listed form of conv3 ----
@@ -239,7 +244,9 @@ __global__ __launch_bounds__(SKIP3_TB) void k_pair_list(const int2* __restrict__
 // the counter per workgroup: an add per crop is 25600 of them on one word, and they took longer than the copy
 static constexpr int SKIP3_FC = 16;
 __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
-                                                   const uint4* __restrict__ act3e, uint4* __restrict__ act3, int* __restrict__ desc) {
+                                                   const uint4* __restrict__ act3e, uint4* __restrict__ act3, int* __restrict__ desc,
+                                                   uint32_t* __restrict__ rows /* Skip3Reach::WORDS per pass */,
+                                                   const long long alloc_rows /* V3 rows in front of the back image */, const int direct) {
     using G = Skip3Geom;
     constexpr int PQ = 10 * 128 * 4 / 16;             // 16-byte units per pair
     static_assert(Skip3Geom::BLOCK_PASSES * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass: 256 threads per SKIP3_FC crops");
@@ -248,6 +255,7 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
     if (!words[SK3_USE]) return;
     if (threadIdx.x == 0) s_filled = 0;
     __syncthreads();
+    const bool all = words[SK_EMPTY_RANGE] != 0;
     const int gid = blockIdx.x * 256 + threadIdx.x;
     if (gid < (int)words[SK3_PASSES]) {
         int4* dst = reinterpret_cast<int4*>(desc + (size_t)gid * G::DESC);
@@ -259,8 +267,16 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
         skip3_describe(p, d);
 #pragma unroll
         for (int k = 0; k < G::DESC / 4; ++k) dst[k] = make_int4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+        // where its rows come from: the own rows of its crops from V3, the others from the image -- or all of them from V3, where the copy is kept
+        const SkipRows every{0, SkipGeom::V3_ROWS - 1};
+        const bool from_v3 = all || !direct;
+        const int2 ba = bands[r.x / G::PAIRS], bb = bands[(r.w ? r.z : r.x) / G::PAIRS];
+        unsigned w[Skip3Reach::WORDS];
+        skip3_row_words(p, from_v3 ? every : skip_rows({ba.x, ba.y}), from_v3 ? every : skip_rows({bb.x, bb.y}), alloc_rows, w);
+        uint4* wd = reinterpret_cast<uint4*>(rows + (size_t)gid * Skip3Reach::WORDS);
+#pragma unroll
+        for (int k = 0; k < Skip3Reach::WORDS / 4; ++k) wd[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
     }
-    const bool all = words[SK_EMPTY_RANGE] != 0;
     uint32_t filled = 0;
     for (int k = 0; k < SKIP3_FC / 4; ++k) {
         const int crop = blockIdx.x * SKIP3_FC + (threadIdx.x >> 6) * (SKIP3_FC / 4) + k;
