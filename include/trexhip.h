@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 16
+#define TREXHIP_ABI_VERSION 17
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -517,6 +517,25 @@ int trexhip_num_classes(trexhip_ctx* ctx);
 int trexhip_network_channels(trexhip_ctx* ctx);   /* channels of the crops the loaded network expects (1 or 3); 0 without weights */
 /* the crop size W x H the loaded network expects; 0 x 0 without weights.  Either pointer may be NULL. */
 int trexhip_network_image_size(trexhip_ctx* ctx, int32_t* width, int32_t* height);
+/* The architecture of the network: TRex's setting visual_identification_version (core/default_config.h:83), a checkpoint's
+ * metadata.model_type.  The blob's header word 6 carries it (0 in every blob written before ABI 17, which keep their meaning):
+ *   TREXHIP_NET_V118_3  visual_identification_network_torch.py:184-258, sizes 8..256 each way -- the chains above, and the only one that trains
+ *   TREXHIP_NET_V100    :328-382   8..256      TREXHIP_NET_V110  :262-324   8..256
+ *   TREXHIP_NET_V119    :106-180   16..256     TREXHIP_NET_V200  :30-102    27..256
+ * The four others run one generic chain (cnn_arch.hip): first layer exact fp32, the further convolutions in the precision mode below with the
+ * same range guard, fc1 exact fp32; a call's crops are walked in chunks of trexhip_identify_chunk_crops (a constant of version and size), and a
+ * crop's row does not depend on its chunk.  A smaller size is TREXHIP_E_UNSUPPORTED, an id outside 0..4 TREXHIP_E_INVALID; a trainer refuses
+ * every version but V118_3 with TREXHIP_E_UNSUPPORTED.  (ABI 17) */
+enum { TREXHIP_NET_V118_3 = 0, TREXHIP_NET_V100 = 1, TREXHIP_NET_V110 = 2, TREXHIP_NET_V119 = 3, TREXHIP_NET_V200 = 4 };
+/* the loaded network's TREXHIP_NET_*; 0 without a context or weights, like trexhip_num_classes (VINetwork's
+ * visual_identification_version, ml/VisualIdentification.cpp) */
+int trexhip_network_version(trexhip_ctx* ctx);
+/* bytes of the blob trexhip_load_weights takes for that version (trex_amd/weights.py shapes(arch=...)); 0 for a version, channel count or
+ * size that no network has.  No reference counterpart (a state_dict knows its own size). */
+size_t trexhip_network_blob_bytes(int32_t version, int32_t classes, int32_t channels, int32_t width, int32_t height);
+/* crops per chunk of an identify call on the loaded network; *crops = 0 for V118_3, where a call is not chunked, and without weights.
+ * No reference counterpart (predict_numpy walks batches of its own choosing, visual_recognition_torch.py:290-352). */
+int trexhip_identify_chunk_crops(trexhip_ctx* ctx, int32_t* crops);
 /* arithmetic of conv1..fc1.  All modes but BF16X3 meet the 1e-4 softmax bar against the fp32 reference network:
  *   TREXHIP_CNN_FP16X3 (default): every fp32 operand as two fp16 pieces (22 mantissa bits), 3 piece products per product on the
  *       fp16 matrix cores, fp32 accumulate; an activation outside the fp16 range raises a device flag and the layer stack is

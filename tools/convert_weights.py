@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Convert a TRex identity-network checkpoint into the flat blob trexhip_load_weights() takes.
 
-The reference writes `<base>_dict.pth` as {'model': None, 'state_dict': <V118_3 state_dict>, 'metadata': {'input_shape': (W, H, C),
-'num_classes', 'model_type', ...}} (visual_recognition_torch.py:102-117 save_model_files); a bare state_dict is accepted too.
+The reference writes `<base>_dict.pth` as {'model': None, 'state_dict': <state_dict>, 'metadata': {'input_shape': (W, H, C),
+'num_classes', 'model_type', ...}} (visual_recognition_torch.py:102-117 save_model_files); a bare state_dict is accepted too (as V118_3).
+metadata.model_type names the architecture -- v118_3, v100, v110, v119 or v200 (visual_identification_network_torch.py:30-382) -- and the
+blob's header carries it; the torchvision backbones are not implemented.
 
     python tools/convert_weights.py model_dict.pth model.trxw
 """
@@ -14,8 +16,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trex_amd import weights  # noqa: E402
 
 
+def model_arch(model_type):
+    """metadata.model_type -> one of trex_amd.weights.ARCH_IDS; ValueError for every other network"""
+    mt = str(model_type).lower()
+    for name in sorted(weights.ARCH_IDS, key=len, reverse=True):
+        if name in mt:
+            return name
+    raise ValueError(f"model_type {model_type!r} is none of {sorted(weights.ARCH_IDS)}: only these networks are implemented "
+                     "(visual_identification_network_torch.py:30-382)")
+
+
 def convert(obj, width=None, height=None, channels=None):
-    """checkpoint object (as torch.load returns it) -> (blob bytes, classes, width, height, channels)"""
+    """checkpoint object (as torch.load returns it) -> (blob bytes, classes, width, height, channels); the blob's header names the
+    architecture of metadata.model_type (weights.blob_arch)"""
     import torch
     meta = {}
     if isinstance(obj, dict) and "state_dict" in obj:
@@ -27,9 +40,7 @@ def convert(obj, width=None, height=None, channels=None):
         sd = obj.state_dict()
     if sd is None:
         raise ValueError("checkpoint holds no state_dict")
-    mt = str(meta.get("model_type", "v118_3")).lower()
-    if "v118_3" not in mt:
-        raise ValueError(f"model_type {meta.get('model_type')!r} is not V118_3: only that network is implemented (visual_identification_network_torch.py:184-258)")
+    arch = model_arch(meta.get("model_type", "v118_3"))
     # PermuteAxesWrapper / Sequential prefixes (visual_identification_network_torch.py:618-644); BatchNorm's step counter is not a weight
     clean = {}
     for k, v in sd.items():
@@ -48,14 +59,21 @@ def convert(obj, width=None, height=None, channels=None):
     if classes != int(clean["fc2.weight"].shape[0]):
         raise ValueError("metadata num_classes does not match fc2.weight")
     st = {}
-    for name, shp in weights.shapes(classes, channels, width, height):
+    want = weights.shapes(classes, channels, width, height, arch)
+    if arch != "v118_3" and sorted(clean) != sorted(n for n, _ in want):       # (V118_3 keeps its KeyError for a missing tensor below)
+        raise ValueError(f"the checkpoint's tensors are not those of {arch}: missing {sorted(set(n for n, _ in want) - set(clean))[:6]}, "
+                         f"unexpected {sorted(set(clean) - set(n for n, _ in want))[:6]}")
+    for other in weights.ARCH_LAYERS:                                          # ... but not when the tensors are exactly another network's
+        if arch == "v118_3" and sorted(clean) == sorted(n for n, _ in weights.shapes(classes, channels, width, height, other)):
+            raise ValueError(f"the checkpoint's tensors are those of {other}, not of {arch}")
+    for name, shp in want:
         if name not in clean:
             raise KeyError(f"checkpoint has no tensor {name!r} (keys: {sorted(clean)[:6]} ...)")
         t = clean[name].detach().to(torch.float32).numpy()
         if tuple(t.shape) != tuple(shp):
-            raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(shp)} expected for {classes} classes, {width}x{height}x{channels}")
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(shp)} expected for {arch}, {classes} classes, {width}x{height}x{channels}")
         st[name] = t
-    return weights.pack_blob(st, classes, channels, width, height), classes, width, height, channels
+    return weights.pack_blob(st, classes, channels, width, height, arch), classes, width, height, channels
 
 
 def main():

@@ -193,7 +193,7 @@ class VisualFieldResult:
 
 
 SYMBOLS = [
-    "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
+    "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_network_version", "trexhip_network_blob_bytes", "trexhip_identify_chunk_crops", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
@@ -262,6 +262,9 @@ def lib():
         L.trexhip_num_classes.argtypes = [C.c_void_p]
         L.trexhip_network_channels.argtypes = [C.c_void_p]
         L.trexhip_network_image_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.trexhip_network_version.argtypes = [C.c_void_p]
+        L.trexhip_network_blob_bytes.argtypes = [C.c_int32] * 5; L.trexhip_network_blob_bytes.restype = C.c_size_t
+        L.trexhip_identify_chunk_crops.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.trexhip_pack_frames_v6_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.trexhip_lzo1x_bound.argtypes = [C.c_size_t]; L.trexhip_lzo1x_bound.restype = C.c_size_t
         L.trexhip_lzo1x_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -629,6 +632,16 @@ class Segmenter:
         w, h = C.c_int32(0), C.c_int32(0)
         _check(lib().trexhip_network_image_size(self._h, C.byref(w), C.byref(h)))
         return int(w.value), int(h.value)
+
+    def network_version(self):
+        """TREXHIP_NET_* of the loaded network (trex_amd.weights.ARCH_IDS: 0 v118_3, 1 v100, 2 v110, 3 v119, 4 v200); 0 without weights."""
+        return int(lib().trexhip_network_version(self._h))
+
+    def identify_chunk_crops(self):
+        """crops per chunk of an identify call on the loaded network; 0 for v118_3 (not chunked) and without weights."""
+        c = C.c_int32(0)
+        _check(lib().trexhip_identify_chunk_crops(self._h, C.byref(c)))
+        return int(c.value)
 
     def probabilities(self, crops):
         """crops: uint8 ndarray (n,H,W,C) on the host, the loaded network's size and channels -> float32 (n,classes) softmax rows."""

@@ -19,6 +19,7 @@
 //   k_fc1       [crops x 12800] x [12800 x 128] MFMA GEMM, LDS tiles
 //   k_head      LayerNorm + ReLU + fc2 + softmax, four crops per wave
 #include "cnn_net.h"
+#include "cnn_arch.h"
 #include "cnn_split.h"
 #include "cnn_weights.h"
 #include <algorithm>
@@ -1305,9 +1306,10 @@ static void drop_graphs(Net* n) {
     n->graphs.clear();
 }
 
-static void free_net(Net* n) {
+void free_net(Net* n) {
     if (!n) return;
     drop_graphs(n);
+    delete n->arch;
     n->weights.free_all();
     n->batch.free_all();
     delete n;
@@ -1329,6 +1331,8 @@ static int upload(Net* net, T** dst, float* inv, const ScaledImage& im) { *inv =
 static int make_empty_v3(trexhip_ctx* ctx, Net* net);
 // parse -> pack (cnn_weights.hip) -> upload
 int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
+    const int arch = blob_arch_id(blob, bytes);
+    if (arch >= TREXHIP_NET_V100 && arch <= TREXHIP_NET_V200) return arch_load(ctx, blob, bytes);      // the other architectures: cnn_arch.hip
     WeightBlob wb;
     const int prc = parse_weight_blob(blob, bytes, "trexhip_load_weights", &wb, [](int W, int H) -> int {
         if (W < 8 || W > 256 || H < 8 || H > 256) {
@@ -1662,6 +1666,7 @@ static bool capture_chain(trexhip_ctx* ctx, Net* net, Net::GraphEntry* cand, con
 
 static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
     Net* net = static_cast<Net*>(ctx->net);
+    if (net->arch) return arch_forward(ctx, d_crops, n, d_probs, d_logits);      // chunked, never captured
     static const bool enabled = [] { const char* e = std::getenv("TREXHIP_GRAPHS"); return !(e && std::atoi(e) == 0); }();
     // not while profiling (the stage events are host-side bookkeeping), not before the first plain call (function attributes are set there)
     if (!enabled || !net->graphs_ok || n > GRAPH_MAX_CROPS || ctx->profiling || !ctx->attr_cnn) return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
@@ -1698,7 +1703,7 @@ static int identify_prepare(trexhip_ctx* ctx, const bool args, const char* who, 
     if (n < 0) { set_error("trexhip_identify: n < 0"); return TREXHIP_E_INVALID; }
     if (n == 0) return TREXHIP_OK;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    const int rc = ensure_act(ctx, loaded, n);
+    const int rc = loaded->arch ? arch_ensure_act(ctx, loaded, n) : ensure_act(ctx, loaded, n);
     if (rc == TREXHIP_OK) *net = loaded;
     return rc;
 }
@@ -1741,6 +1746,13 @@ int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     // the plan of the LAST forward pass -- none before the first pass or behind a pass in another precision mode (not ctx->cnn_mode, which
     // trexhip_set_identity_precision may have changed since)
+    if (net->last_mode == TREXHIP_CNN_FP16X3 && net->arch) {      // the chunks of the call together (k_arch_guard_plan)
+        uint32_t st[2] = {0, 0};
+        TH_CHECK_HIP(hipMemcpy(st, net->ovf(ARCH_STAT_RERUN), 8, hipMemcpyDeviceToHost));
+        if (rerun_crops) *rerun_crops = st[0];
+        if (whole_batch) *whole_batch = st[1] ? 1u : 0u;
+        return TREXHIP_OK;
+    }
     if (net->last_mode == TREXHIP_CNN_FP16X3) TH_CHECK_HIP(hipMemcpy(plan, net->ovf(OVF_PLAN), 8, hipMemcpyDeviceToHost));
     if (rerun_crops) *rerun_crops = plan[1] == 1u ? plan[0] : 0u;
     if (whole_batch) *whole_batch = plan[1] == 2u ? 1u : 0u;
@@ -1781,6 +1793,23 @@ int trexhip_set_identity_precision(trexhip_ctx* ctx, int32_t mode) {
 int trexhip_num_classes(trexhip_ctx* ctx) {
     if (!ctx || !ctx->net) return 0;
     return static_cast<Net*>(ctx->net)->classes;
+}
+
+int trexhip_network_version(trexhip_ctx* ctx) {
+    if (!ctx || !ctx->net) return 0;
+    const Net* net = static_cast<const Net*>(ctx->net);
+    return net->arch ? net->arch->plan.spec->id : TREXHIP_NET_V118_3;
+}
+
+size_t trexhip_network_blob_bytes(int32_t version, int32_t classes, int32_t channels, int32_t width, int32_t height) {
+    return arch_blob_bytes(version, classes, channels, width, height);
+}
+
+int trexhip_identify_chunk_crops(trexhip_ctx* ctx, int32_t* crops) {
+    if (!ctx || !crops) { set_error("trexhip_identify_chunk_crops: null argument"); return TREXHIP_E_INVALID; }
+    const Net* net = static_cast<const Net*>(ctx->net);
+    *crops = net && net->arch ? net->arch->plan.chunk : 0;
+    return TREXHIP_OK;
 }
 
 int trexhip_network_channels(trexhip_ctx* ctx) {

@@ -1,0 +1,630 @@
+// cnn_arch.hip -- the identity networks v100, v110, v119 and v200 (visual_identification_network_torch.py:30-382; the layer table: cnn_arch_plan.h)
+// at any individual_image_size of their range, inference only.  NHWC fp32 activations throughout, every pool floors like nn.MaxPool2d.
+//
+//   k_arch_conv1<CH, T>   first layer, u8 crops -> fp32, T x T taps, 16 output channels per workgroup (grid y = CO / 16), exact fp32 on the VALU:
+//                         the model of k_any_conv1 with the tap size, the optional pool and the epilogue below
+//   k_arch_conv<COB, ..>  every further convolution as T * T shifted GEMMs on the matrix cores, the model of k_any_conv (cnn_any.hip): run-time
+//                         CI, taps 3 or 5, fused floor 2x2 max-pool or none, COB = 32 / 64 / 128 output channels per workgroup with the
+//                         channel block on the grid's y, the three arithmetic kinds, the fp16 range flag per crop and the guarded bf16x6 re-run
+//   k_pool3               floor 3x3 max-pool, streaming, one float4 of channels per lane (v200: a 3x3 window does not fit the window-major tile)
+//   k_gap                 global average pool (v200), summed in raster order
+//   k_arch_fc1            fc1 as an exact fp32 GEMM on the matrix cores, K split over the 4 waves of a workgroup and summed in wave order
+//   k_arch_head           BatchNorm1d or none + ReLU + fc2 + softmax, one wave per crop, the expressions of k_head (cnn.hip)
+//
+// The epilogue of both convolution kernels: relu((max_window(conv) * out_scale + bias[co]) * s[co] + t[co]) -- the affine BEHIND the pool, which
+// v110 needs (its BatchNorm follows the max-pool and its scale may be negative); v119 / v200 fold their BatchNorm into weights and bias
+// (s = 1, t = 0), v100 has none.
+//
+// A call's crops are walked in chunks of ArchPlan::chunk (a constant of version and size); every kernel computes a crop from that crop alone, in
+// an order that does not depend on the chunk or on n, so a crop's row is the same bits wherever it stands.
+#include "cnn_arch.h"
+#include "cnn_split.h"
+#include "cnn_weights.h"
+
+namespace trexhip {
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// first layer: CH -> 16 channels of one block, T x T 'same', optional floor 2x2 max-pool, exact fp32
+// ------------------------------------------------------------------------------------------------
+// One thread per 2 x 2 window of conv pixels, 16 x 16 windows per workgroup.  LDS: (CH * T * T * 16 + CH * PW * PW) * 4 bytes, PW = 32 + T - 1
+// (3 channels, 5 taps: 4800 + 15552 = 20352 B); 64 accumulators per thread
+template <int CH, int T>
+__global__ __launch_bounds__(256) void k_arch_conv1(const uint8_t* __restrict__ crops /*[N][H][W][CH]*/, const float* __restrict__ w /*[CO/16][CH][T*T][16]*/,
+                                                    const float* __restrict__ bias, const float* __restrict__ sv, const float* __restrict__ tv,
+                                                    float* __restrict__ out /*[N][Ho][Wo][CO]*/, const int CO, const int W, const int H, const int pool,
+                                                    const int tx_n, const int tiles) {
+    constexpr int C1 = ARCH_C1T, PW = 2 * C1 + T - 1, PAD = T / 2, T2 = T * T;
+    __shared__ __attribute__((aligned(16))) float wl[CH * T2 * 16];
+    __shared__ float img[CH * PW * PW];
+    const int crop = blockIdx.x / tiles, t = blockIdx.x - crop * tiles;
+    const int ty = t / tx_n, tx = t - ty * tx_n;
+    const int cog = blockIdx.y;
+    const int y0 = 2 * C1 * ty - PAD, x0 = 2 * C1 * tx - PAD;
+    const uint8_t* src = crops + (size_t)crop * H * W * CH;
+    const float* wg = w + (size_t)cog * CH * T2 * 16;
+    for (int i = threadIdx.x; i < CH * T2 * 16; i += 256) wl[i] = wg[i];
+    for (int i = threadIdx.x; i < PW * PW * CH; i += 256) {
+        const int c = i % CH, p = i / CH, py = p / PW, px = p - py * PW;
+        const int iy = y0 + py, ix = x0 + px;
+        img[c * PW * PW + p] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? (float)src[((size_t)iy * W + ix) * CH + c] : 0.f;   // predict_numpy: no scaling
+    }
+    __syncthreads();
+    const int wy = threadIdx.x / C1, wx = threadIdx.x % C1;
+    const int py0 = 2 * (C1 * ty + wy), px0 = 2 * (C1 * tx + wx);       // the window's first conv pixel
+    if (py0 >= H || px0 >= W) return;
+    float acc[4][16];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+        for (int co = 0; co < 16; ++co) acc[s4][co] = 0.f;
+    for (int c = 0; c < CH; ++c) {
+        const float* base = img + c * PW * PW + (2 * wy) * PW + 2 * wx;
+#pragma unroll 1
+        for (int ky = 0; ky < T; ++ky) {
+            float r0[T + 1], r1[T + 1];
+#pragma unroll
+            for (int b6 = 0; b6 < T + 1; ++b6) { r0[b6] = base[ky * PW + b6]; r1[b6] = base[(ky + 1) * PW + b6]; }
+#pragma unroll
+            for (int kx = 0; kx < T; ++kx) {
+                const float4* wt = reinterpret_cast<const float4*>(wl + (c * T2 + ky * T + kx) * 16);
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const float4 wv = wt[q4];
+                    const float ww[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int co = q4 * 4 + q;
+                        acc[0][co] = fmaf(r0[kx], ww[q], acc[0][co]);
+                        acc[1][co] = fmaf(r0[kx + 1], ww[q], acc[1][co]);
+                        acc[2][co] = fmaf(r1[kx], ww[q], acc[2][co]);
+                        acc[3][co] = fmaf(r1[kx + 1], ww[q], acc[3][co]);
+                    }
+                }
+            }
+        }
+    }
+    const int cb = cog * 16;
+    if (pool) {
+        const int Ho = H / 2, Wo = W / 2, oy = py0 >> 1, ox = px0 >> 1;
+        if (oy >= Ho || ox >= Wo) return;                                // the odd last row / column is dropped by the floor
+        float* o = out + (((size_t)crop * Ho + oy) * Wo + ox) * CO + cb;
+#pragma unroll
+        for (int co = 0; co < 16; co += 4) {
+            float4 v;
+            float* vv = &v.x;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float m = fmaxf(fmaxf(acc[0][co + q], acc[1][co + q]), fmaxf(acc[2][co + q], acc[3][co + q]));
+                vv[q] = fmaxf((m + bias[cb + co + q]) * sv[cb + co + q] + tv[cb + co + q], 0.f);
+            }
+            *reinterpret_cast<float4*>(o + co) = v;
+        }
+    } else {
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const int py = py0 + (s4 >> 1), px = px0 + (s4 & 1);
+            if (py >= H || px >= W) continue;
+            float* o = out + (((size_t)crop * H + py) * W + px) * CO + cb;
+#pragma unroll
+            for (int co = 0; co < 16; co += 4) {
+                float4 v;
+                float* vv = &v.x;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) vv[q] = fmaxf((acc[s4][co + q] + bias[cb + co + q]) * sv[cb + co + q] + tv[cb + co + q], 0.f);
+                *reinterpret_cast<float4*>(o + co) = v;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// every further convolution: T x T 'same' on the matrix cores, 2-D tiles of 64 windows of 2 x 2 conv pixels
+// ------------------------------------------------------------------------------------------------
+constexpr int ARCH_APMAX = 36 * 12;          // patch pixels of the largest tile shape at 5 taps (4 x 16 or 16 x 4 windows); 3 taps: 34 * 10
+
+template <int KIND> struct ArchK;            // 0 = bf16 (3 pieces), 1 = fp16 (2 pieces), 2 = fp32
+template <> struct ArchK<0> { static constexpr int NP = 3; using frag = bf16x8; };
+template <> struct ArchK<1> { static constexpr int NP = 2; using frag = f16x8; };
+template <> struct ArchK<2> { static constexpr int NP = 1; using frag = float; };
+
+// per instance: LDS bytes and accumulator registers.  Input channels are staged 16 at a time in every kind.
+//   COB 128: fp32 29376 + 16384 = 45760 B, bf16 62208 + 24576 = 86784 B, fp16 41472 + 16384 = 57856 B; 4 M-tiles per wave = 64 accumulators
+//   COB  64: fp32 37568, bf16 74496, fp16 49664 B; 32 accumulators          COB 32: fp32 33472, bf16 68352, fp16 45568 B; 16 accumulators
+template <int COB, int KIND>
+struct ArchGeom {
+    static constexpr int CIC = 16;
+    static constexpr int NP = ArchK<KIND>::NP;
+    static constexpr int PSTRIDE = KIND == 2 ? (CIC + 1) * 4 : CIC * 2 + 16;      // bytes per patch pixel (fp32: odd float stride; split: odd multiple of 16)
+    static constexpr int PIECE = ARCH_APMAX * PSTRIDE;                             // bytes per piece of the patch
+    static constexpr int BT = KIND == 2 ? CIC * COB * 4 : NP * (CIC / 8) * COB * 16;   // bytes per weight tile (one tap of one chunk of one block)
+    static constexpr int BV = BT / 16;
+    static constexpr int BPT = (BV + 511) / 512;
+    static constexpr int NT = COB / 32, WM = 8 / NT, TPW = 8 / WM;                // 8 waves: NT along N, WM along M, TPW M-tiles each
+    static constexpr int ACC = TPW * 16;
+    static constexpr int LDS_BYTES = NP * PIECE + 2 * BT;
+    static_assert(COB == 32 || COB == 64 || COB == 128, "channel block");
+    static_assert(LDS_BYTES <= 160 * 1024 && ACC <= 128, "LDS / accumulators");
+};
+
+// wp: [CO/COB][CI/16][T*T] weight tiles: KIND 2 [16][COB] fp32; KIND 0 / 1 [NP][2][COB] x 16 B (pack_arch_bf16x3 / pack_arch_f16x2).
+// Grid (items, CO / COB): one workgroup per (crop, tile) and channel block; with a guard (the plan of k_arch_guard_plan) the x grid strides over
+// the tiles of the listed crops.
+template <int COB, int KIND, int NTERMS>
+__global__ __launch_bounds__(512) void k_arch_conv(const float* __restrict__ in /*[N][Hi][Wi][CI]*/, const uint4* __restrict__ wp, const float* __restrict__ bias,
+                                                   const float* __restrict__ sv, const float* __restrict__ tv, float* __restrict__ out /*[N][Ho][Wo][CO]*/,
+                                                   const int CI, const int CO, const int Hi, const int Wi, const int taps, const int pool, const int TX,
+                                                   const int tx_n, const int tiles, const float out_scale, uint32_t* __restrict__ overflow,
+                                                   uint8_t* __restrict__ crop_flags, const uint32_t* __restrict__ guard, const int n_blocks) {
+    if (guard && guard[1] == 0u) return;          // re-run pass: only when the fp16 pass flagged something
+    using G = ArchGeom<COB, KIND>;
+    using frag = typename ArchK<KIND>::frag;
+    constexpr int CIC = G::CIC, Q4 = CIC / 4, KO = CIC / 8;
+    extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
+    uint8_t* patch = ldsb;
+    uint8_t* Bs = ldsb + G::NP * G::PIECE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int n = wave % G::NT, mg = wave / G::NT;
+    const int T2 = taps * taps, pad = taps >> 1;
+    const int TY = AW / TX, PW = 2 * TX + taps - 1, PH = 2 * TY + taps - 1;
+    const int Ho = pool ? Hi / 2 : Hi, Wo = pool ? Wi / 2 : Wi;
+    const int cob = blockIdx.y, ncc = CI / CIC;
+    const uint4* wblk = wp + (size_t)cob * ncc * T2 * G::BV;
+    int aoff[G::TPW];
+#pragma unroll
+    for (int m = 0; m < G::TPW; ++m) {
+        const int p = (mg + G::WM * m) * 32 + j;                        // window-major pixel index of the tile, < 256
+        const int wi = p >> 2, sub = p & 3;
+        const int wy = wi / TX, wx = wi - wy * TX;
+        aoff[m] = ((2 * wy + (sub >> 1)) * PW + (2 * wx + (sub & 1))) * G::PSTRIDE + (KIND == 2 ? h * 4 : h * 16);
+    }
+    const int n_eff = (guard && guard[1] == 1u) ? (int)guard[0] * tiles : n_blocks;
+    for (int blk = blockIdx.x; blk < n_eff; blk += gridDim.x) {
+        if (blk != (int)blockIdx.x) __syncthreads();                    // the previous tile's readers are done with the LDS buffers
+        const int crop = plan_crop(guard, blk / tiles), t = blk % tiles;
+        const int ty = t / tx_n, tx = t - ty * tx_n;
+        const int oy0 = ty * TY, ox0 = tx * TX;                         // first window of the tile
+        const int iy0 = 2 * oy0 - pad, ix0 = 2 * ox0 - pad;             // first input pixel of its patch
+        f32x16 acc[G::TPW];
+#pragma unroll
+        for (int m = 0; m < G::TPW; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+        const float* inc = in + (size_t)crop * Hi * Wi * CI;
+        bool ovf = false;
+        for (int cc = 0; cc < ncc; ++cc) {
+            __syncthreads();
+            for (int idx = tid; idx < PH * PW * Q4; idx += 512) {
+                const int q = idx % Q4, px = idx / Q4;
+                const int py = px / PW, pxx = px - py * PW;
+                const int iy = iy0 + py, ix = ix0 + pxx;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);             // zero padding ('same'), and the rows / columns past a ragged edge
+                if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi)
+                    v = *reinterpret_cast<const float4*>(inc + ((size_t)iy * Wi + ix) * CI + cc * CIC + q * 4);
+                if constexpr (KIND == 2) {
+                    float* d = reinterpret_cast<float*>(patch + px * G::PSTRIDE) + q * 4;
+                    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+                } else {
+                    uint32_t a1[4], a2[4], a3[4];
+                    if constexpr (KIND == 0) {
+                        split3(v.x, a1[0], a2[0], a3[0]); split3(v.y, a1[1], a2[1], a3[1]);
+                        split3(v.z, a1[2], a2[2], a3[2]); split3(v.w, a1[3], a2[3], a3[3]);
+                    } else {
+                        split2h(v.x, a1[0], a2[0], ovf); split2h(v.y, a1[1], a2[1], ovf);
+                        split2h(v.z, a1[2], a2[2], ovf); split2h(v.w, a1[3], a2[3], ovf);
+                    }
+                    uint8_t* d = patch + px * G::PSTRIDE + q * 8;
+                    *reinterpret_cast<uint2*>(d) = make_uint2(a1[0] | (a1[1] << 16), a1[2] | (a1[3] << 16));
+                    *reinterpret_cast<uint2*>(d + G::PIECE) = make_uint2(a2[0] | (a2[1] << 16), a2[2] | (a2[3] << 16));
+                    if constexpr (KIND == 0) *reinterpret_cast<uint2*>(d + 2 * G::PIECE) = make_uint2(a3[0] | (a3[1] << 16), a3[2] | (a3[3] << 16));
+                }
+            }
+            const uint4* wsrc = wblk + (size_t)cc * T2 * G::BV;
+            for (int i = tid; i < G::BV; i += 512) reinterpret_cast<uint4*>(Bs)[i] = wsrc[i];
+            __syncthreads();
+            int ky = 0, kx = 0;
+#pragma unroll 1
+            for (int tap = 0; tap < T2; ++tap) {
+                const int buf = tap & 1;
+                uint4 nb[G::BPT];
+                if (tap < T2 - 1) {
+#pragma unroll
+                    for (int u = 0; u < G::BPT; ++u) { const int i = tid + u * 512; if (i < G::BV) nb[u] = wsrc[(size_t)(tap + 1) * G::BV + i]; }
+                }
+                const uint8_t* asrc = patch + (ky * PW + kx) * G::PSTRIDE;
+                if constexpr (KIND == 2) {
+                    const float* bsrc = reinterpret_cast<const float*>(Bs + buf * G::BT) + h * COB + n * 32 + j;
+#pragma unroll
+                    for (int t2 = 0; t2 < CIC / 2; ++t2) {                // input channel 2 t2 + h of the chunk
+                        const float b = bsrc[2 * t2 * COB];
+#pragma unroll
+                        for (int m = 0; m < G::TPW; ++m) {
+                            const float a = *reinterpret_cast<const float*>(asrc + aoff[m] + 8 * t2);
+                            acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[m], 0, 0, 0);
+                        }
+                    }
+                } else {
+                    const uint8_t* bsrc = Bs + buf * G::BT + (h * COB + n * 32 + j) * 16;
+                    const frag b1 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc));
+                    const frag b2 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + KO * COB * 16));
+                    frag b3 = b1;
+                    if constexpr (G::NP == 3) b3 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + 2 * KO * COB * 16));
+#pragma unroll
+                    for (int m = 0; m < G::TPW; ++m) {
+                        const frag p1 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(asrc + aoff[m]));
+                        const frag p2 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(asrc + aoff[m] + G::PIECE));
+                        if constexpr (KIND == 0 && NTERMS == 6) {        // smallest products first: a3b1 a2b2 a1b3 a2b1 a1b2 a1b1
+                            const frag p3 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(asrc + aoff[m] + 2 * G::PIECE));
+                            acc[m] = mfma16(p3, b1, acc[m]); acc[m] = mfma16(p2, b2, acc[m]); acc[m] = mfma16(p1, b3, acc[m]);
+                        }
+                        acc[m] = mfma16(p2, b1, acc[m]); acc[m] = mfma16(p1, b2, acc[m]); acc[m] = mfma16(p1, b1, acc[m]);
+                    }
+                }
+                if (tap < T2 - 1) {
+#pragma unroll
+                    for (int u = 0; u < G::BPT; ++u) { const int i = tid + u * 512; if (i < G::BV) reinterpret_cast<uint4*>(Bs + (buf ^ 1) * G::BT)[i] = nb[u]; }
+                }
+                if (++kx == taps) { kx = 0; ++ky; }
+                __syncthreads();
+            }
+        }
+        if (KIND == 1 && __any(ovf) && lane == 0) { crop_flags[crop] = 1; atomicOr(overflow, 1u); }     // the crop is known: the plan lists it
+        // epilogue: lane (j, h) holds for g = 0..3 the four pixels of window mt * 8 + 2 g + h, channel cob * COB + n * 32 + j
+        const int co = cob * COB + n * 32 + j;
+        const float bz = bias[co], sc = sv[co], sh = tv[co];
+        float* oc = out + (size_t)crop * Ho * Wo * CO;
+#pragma unroll
+        for (int m = 0; m < G::TPW; ++m) {
+            const int mt = mg + G::WM * m;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int wi = mt * 8 + 2 * g + h;
+                const int wy = wi / TX, wx = wi - wy * TX;
+                if (pool) {
+                    const int oy = oy0 + wy, ox = ox0 + wx;
+                    if (oy >= Ho || ox >= Wo) continue;                 // ragged edge of the layer
+                    const float v = fmaxf(fmaxf(acc[m][4 * g], acc[m][4 * g + 1]), fmaxf(acc[m][4 * g + 2], acc[m][4 * g + 3]));
+                    oc[((size_t)oy * Wo + ox) * CO + co] = fmaxf((v * out_scale + bz) * sc + sh, 0.f);      // out_scale undoes the weight scaling (fp16 pieces)
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int py = 2 * (oy0 + wy) + (q >> 1), px = 2 * (ox0 + wx) + (q & 1);
+                        if (py >= Hi || px >= Wi) continue;
+                        oc[((size_t)py * Wi + px) * CO + co] = fmaxf((acc[m][4 * g + q] * out_scale + bz) * sc + sh, 0.f);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// floor 3x3 max-pool, NHWC, one float4 of channels per lane: reads the layer's output once and writes a ninth of it
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pool3(const float4* __restrict__ in /*[N][Hi][Wi][C4]*/, float4* __restrict__ out /*[N][Hi/3][Wi/3][C4]*/, const int n,
+                                               const int Hi, const int Wi, const int C4, const uint32_t* __restrict__ guard) {
+    if (guard && guard[1] == 0u) return;
+    const int items = (guard && guard[1] == 1u) ? (int)guard[0] : n;
+    const int Ho = Hi / 3, Wo = Wi / 3;
+    const size_t total = (size_t)items * Ho * Wo * C4;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int c = (int)(idx % C4);
+        size_t r = idx / C4;
+        const int ox = (int)(r % Wo); r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int crop = plan_crop(guard, (int)(r / Ho));
+        const float4* src = in + (((size_t)crop * Hi + 3 * oy) * Wi + 3 * ox) * C4 + c;
+        float4 m = src[0];
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const float4 v = src[((size_t)dy * Wi + dx) * C4];
+                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+            }
+        out[(((size_t)crop * Ho + oy) * Wo + ox) * C4 + c] = m;
+    }
+}
+
+// global average pool: the P positions of a channel summed in raster order, then one division
+__global__ __launch_bounds__(256) void k_gap(const float* __restrict__ in /*[N][P][C]*/, float* __restrict__ out /*[N][C]*/, const int n, const int P, const int C) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)n * C) return;
+    const size_t crop = idx / C;
+    const int c = (int)(idx - crop * C);
+    const float* src = in + crop * P * C + c;
+    float s = 0.f;
+    for (int p = 0; p < P; ++p) s += src[(size_t)p * C];
+    out[idx] = s / (float)P;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fc1: out[n][NH] = act[n][K] x w[K][NH] + bias, exact fp32 (v_mfma_f32_32x32x2_f32)
+// ------------------------------------------------------------------------------------------------
+// Grid (ceil(n / 32), NH / 32): 32 crops x 32 outputs per workgroup.  Wave v of the 4 walks the k-octets v, v + 4, ... (K is a multiple of 8);
+// the four partial tiles meet in LDS (4 * 32 * 33 * 4 = 16896 B) and are summed in wave order.  The split is the layer's, never n's.
+__global__ __launch_bounds__(256) void k_arch_fc1(const float* __restrict__ act /*[n][K]*/, const float* __restrict__ w /*[K][NH]*/, const float* __restrict__ bias,
+                                                  float* __restrict__ out /*[n][NH]*/, const int n, const int K, const int NH) {
+    __shared__ float red[4][32][33];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int row0 = blockIdx.x * 32, col0 = blockIdx.y * 32;
+    const int row = row0 + j < n ? row0 + j : n - 1;                    // rows past the batch repeat its last crop and are not written
+    const float* a = act + (size_t)row * K + 4 * h;
+    const float* b = w + (size_t)(4 * h) * NH + col0 + j;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int ko = wave; ko < K / 8; ko += 4) {
+        const float4 av = *reinterpret_cast<const float4*>(a + (size_t)ko * 8);
+        const float* bp = b + (size_t)ko * 8 * NH;
+        const float b0 = bp[0], b1 = bp[NH], b2 = bp[2 * (size_t)NH], b3 = bp[3 * (size_t)NH];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b2, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b3, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[wave][8 * g + 4 * h + q][j] = acc[4 * g + q];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int idx = tid + 256 * r, i = idx >> 5, c = idx & 31;
+        if (row0 + i >= n) continue;
+        out[(size_t)(row0 + i) * NH + col0 + c] = ((red[0][i][c] + red[1][i][c]) + red[2][i][c]) + red[3][i][c] + bias[col0 + c];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// head: (BatchNorm1d as s, t) + ReLU + fc2 + softmax, one wave per crop
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float arch_wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ float arch_wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_arch_head(const float* __restrict__ fc1 /*[n][NH]*/, const float* __restrict__ hs, const float* __restrict__ ht,
+                                                   const float* __restrict__ w2t /*[hidden][C]*/, const float* __restrict__ b2, float* __restrict__ probs /*[n][C]*/,
+                                                   float* __restrict__ logits_out, const int n, const int C, const int NH, const int hidden) {
+    __shared__ float ys[4][1024];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int crop = blockIdx.x * 4 + wave;
+    if (crop >= n) return;
+    const float* x = fc1 + (size_t)crop * NH;
+    for (int k = lane; k < NH; k += 64) ys[wave][k] = fmaxf(x[k] * hs[k] + ht[k], 0.f);
+    __builtin_amdgcn_wave_barrier();      // ys[wave] is private to this wave; LDS ops of one wave stay in order
+    const int nrep = (C + 63) / 64;
+    float mx = -3.4e38f, sum = 0.f;
+    float lg[16];                         // up to 1024 classes
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        lg[r] = -3.4e38f;
+        if (r < nrep) {
+            const int c = r * 64 + lane;
+            if (c < C) {
+                float s = b2[c];
+                for (int k = 0; k < hidden; ++k) s = fmaf(ys[wave][k], w2t[(size_t)k * C + c], s);
+                lg[r] = s;
+                if (logits_out) logits_out[(size_t)crop * C + c] = s;
+            }
+            mx = fmaxf(mx, lg[r]);
+        }
+    }
+    mx = arch_wave_max(mx);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (r < nrep) {
+            const int c = r * 64 + lane;
+            if (c < C) { lg[r] = expf(lg[r] - mx); sum += lg[r]; }
+        }
+    sum = 1.f / arch_wave_sum(sum);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (r < nrep) {
+            const int c = r * 64 + lane;
+            if (c < C) probs[(size_t)crop * C + c] = lg[r] * sum;
+        }
+}
+
+// the plan of a chunk's guarded re-run: the protocol of k_guard_plan (cnn.hip) -- lists the flagged crops, clears their flags and the range word --
+// and adds what it planned to the call's two statistics words
+__global__ __launch_bounds__(1024) void k_arch_guard_plan(uint32_t* __restrict__ overflow, uint8_t* __restrict__ flags, const int n, uint32_t* __restrict__ plan,
+                                                          uint32_t* __restrict__ stats) {
+    __shared__ uint32_t cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    const uint32_t raised = overflow[0];
+    if (raised == 0u) {
+        for (int i = threadIdx.x; i < n; i += 1024) if (flags[i]) flags[i] = 0;
+        if (threadIdx.x == 0) { plan[0] = 0; plan[1] = 0; }
+        return;
+    }
+    for (int i = threadIdx.x; i < n; i += 1024)
+        if (flags[i]) {
+            flags[i] = 0;
+            const uint32_t k = atomicAdd(&cnt, 1u);
+            if (k < (uint32_t)FB_MAX) plan[2 + k] = (uint32_t)i;
+        }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool whole = cnt == 0u || cnt > (uint32_t)FB_MAX;
+        plan[0] = whole ? 0u : cnt; plan[1] = whole ? 2u : 1u;
+        if (whole) stats[1] = 1u; else stats[0] += cnt;
+        overflow[0] = 0u;
+    }
+}
+
+// ---- the instances, each stated once ----
+using ArchKern = decltype(Kern(k_arch_conv<128, 2, 1>, 512));
+template <int COB, int KIND, int NTERMS>
+ArchKern arch_kern() { return Kern(k_arch_conv<COB, KIND, NTERMS>, 512, ArchGeom<COB, KIND>::LDS_BYTES); }
+struct ArchConvSet { ArchKern by_mode[4]; };     // indexed by TREXHIP_CNN_*: FP32, BF16X6, BF16X3, FP16X3
+template <int COB>
+ArchConvSet arch_set() { return {{arch_kern<COB, 2, 1>(), arch_kern<COB, 0, 6>(), arch_kern<COB, 0, 3>(), arch_kern<COB, 1, 3>()}}; }
+const ArchConvSet ARCH_CONV[3] = {arch_set<32>(), arch_set<64>(), arch_set<128>()};      // COB 32, 64, 128
+const ByChannels ARCH_CONV1_T3{Kern(k_arch_conv1<1, 3>, 256), Kern(k_arch_conv1<3, 3>, 256)};
+const ByChannels ARCH_CONV1_T5{Kern(k_arch_conv1<1, 5>, 256), Kern(k_arch_conv1<3, 5>, 256)};
+const Kern K_POOL3(k_pool3, 256);
+const Kern K_GAP(k_gap, 256);
+const Kern K_ARCH_FC1(k_arch_fc1, 256);
+const Kern K_ARCH_HEAD(k_arch_head, 256);
+const Kern K_ARCH_GUARD_PLAN(k_arch_guard_plan, 1024);
+
+inline int cdiv(const size_t a, const size_t b) { return (int)((a + b - 1) / b); }
+
+// one convolution of the chain behind the first on m crops, or (guard) on the plan's
+void launch_conv(hipStream_t s, const Net& net, const ArchNet& a, const int i, const int mode, const int m, const uint32_t* guard, const int n_cus) {
+    const ArchLayerPlan& l = a.plan.L[i];
+    const ArchLayerDev &d = a.L[i], &prev = a.L[i - 1];
+    const bool h16 = mode == TREXHIP_CNN_FP16X3;
+    const void* w = mode == TREXHIP_CNN_FP32 ? (const void*)d.w : h16 ? (const void*)d.wh : (const void*)d.ws;
+    const int items = m * l.tl.tiles;
+    const int gx = guard ? std::min(items, 4 * n_cus) : items;          // a re-run is a handful of crops: a small grid strides over them
+    ARCH_CONV[l.COB == 32 ? 0 : l.COB == 64 ? 1 : 2].by_mode[mode](s, dim3(gx, l.co_blocks), prev.pool ? prev.pool : prev.act, w, d.bias, d.s, d.t, d.act, l.CI, l.CO,
+                                                                 l.Hi, l.Wi, l.taps, l.pool == 2 ? 1 : 0, l.tl.TX, l.tl.tx_n, l.tl.tiles, h16 ? d.invh : 1.f,
+                                                                 net.ovf(OVF_RANGE), net.d_ovfc, guard, items);
+    if (l.pool == 3) {
+        const size_t total = (size_t)m * l.H3 * l.W3 * (l.CO / 4);
+        K_POOL3(s, std::min(cdiv(total, 256), 64 * n_cus), reinterpret_cast<const float4*>(d.act), reinterpret_cast<float4*>(d.pool), m, l.Ho, l.Wo, l.CO / 4, guard);
+    }
+}
+
+}  // namespace
+
+#define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)      // a chain of allocations stops at its first failure
+template <class T, class V>
+static int up(Net* net, T** dst, const std::vector<V>& v) {
+    const int rc = net->weights.device_bytes(dst, v.size() * sizeof(V), "trexhip_load_weights");
+    if (rc != TREXHIP_OK) return rc;
+    TH_CHECK_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
+    return TREXHIP_OK;
+}
+
+int arch_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
+    ArchBlob wb;
+    const int prc = parse_arch_blob(blob, bytes, "trexhip_load_weights", &wb);
+    if (prc != TREXHIP_OK) return prc;
+    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    free_net(static_cast<Net*>(ctx->net));
+    ctx->net = nullptr;
+    Net* net = new Net();
+    net->classes = wb.classes; net->W = wb.W; net->H = wb.H; net->CH = wb.CH;
+    ArchNet* a = net->arch = new ArchNet();
+    a->plan = arch_plan(wb.id, wb.W, wb.H, wb.CH);
+    const ArchSpec& sp = *a->plan.spec;
+    const bool fold = sp.bn2d && !sp.bn_behind_pool;
+    int rc = TREXHIP_OK;
+    for (int i = 0; i < sp.n_conv && rc == TREXHIP_OK; ++i) {
+        const ArchLayerPlan& l = a->plan.L[i];
+        ArchLayerDev& d = a->L[i];
+        const int ci_real = i == 0 ? wb.CH : sp.conv[i - 1].CO;
+        const ArchConvImage im = i == 0 ? pack_arch_conv1(wb.conv[i], sp.conv[i].CO, wb.CH, l.taps, l.CO, fold)
+                                        : pack_arch_conv(wb.conv[i], sp.conv[i].CO, ci_real, l.taps, l.CO, l.CI, l.COB, fold);
+        TRY(up(net, &d.w, im.w)); TRY(up(net, &d.bias, im.bias)); TRY(up(net, &d.s, im.s)); TRY(up(net, &d.t, im.t));
+        if (i > 0) {
+            TRY(up(net, &d.ws, pack_arch_bf16x3(im.w, l.COB)));
+            const ScaledImage h = pack_arch_f16x2(im.w, l.COB);
+            d.invh = h.inv;
+            TRY(up(net, &d.wh, h.v));
+        }
+    }
+    const int P = sp.gap ? 1 : a->plan.Hf * a->plan.Wf;
+    const Folded f1 = pack_arch_fc1(wb.fc1w, wb.fc1b, sp.hidden, a->plan.NH, sp.conv[sp.n_conv - 1].CO, a->plan.Cf, P);
+    TRY(up(net, &a->wf1, f1.w)); TRY(up(net, &a->bf1, f1.b));
+    const Folded bn = pack_arch_bn1d(wb.bn1d, sp.hidden, a->plan.NH);
+    TRY(up(net, &a->hs, bn.w)); TRY(up(net, &a->ht, bn.b));
+    TRY(up(net, &a->wf2t, pack_arch_fc2(wb.fc2w, wb.classes, sp.hidden)));
+    TRY(up(net, &a->bf2, std::vector<float>(wb.fc2b, wb.fc2b + wb.classes)));
+    TRY(net->weights.device_bytes(&net->d_ovf, ARCH_OVF_WORDS * 4, "trexhip_load_weights"));
+    if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, ARCH_OVF_WORDS * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
+    if (rc != TREXHIP_OK) { free_net(net); return rc; }
+    ctx->net = net;
+    return TREXHIP_OK;
+}
+
+int arch_ensure_act(trexhip_ctx* ctx, Net* net, int n) {
+    if (n <= net->max_crops) return TREXHIP_OK;
+    ArchNet& a = *net->arch;
+    // (no captured chains to drop: these chains are not captured)
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));       // an earlier call may still read the buffers that are replaced here
+    net->batch.free_all();
+    net->h_probs = nullptr;
+    net->max_crops = 0;
+    Mem& B = net->batch;
+    const char* who = "trexhip_identify_device";
+    const size_t N = n, M = std::min(n, a.plan.chunk);
+    int rc = B.device_bytes(&net->d_ovfc, M, who);
+    for (int i = 0; i < a.plan.n_conv; ++i) {
+        TRY(B.device_bytes(&a.L[i].act, M * a.plan.L[i].act_floats * 4, who));
+        a.L[i].pool = nullptr;
+        if (a.plan.L[i].pool == 3) TRY(B.device_bytes(&a.L[i].pool, M * a.plan.L[i].pool_floats * 4, who));
+    }
+    a.gap = nullptr;
+    if (a.plan.spec->gap) TRY(B.device_bytes(&a.gap, M * a.plan.Cf * 4, who));
+    TRY(B.device_bytes(&a.fc1, M * a.plan.NH * 4, who));
+    TRY(B.device_bytes(&net->probs, N * net->classes * 4, who));
+    TRY(B.device_bytes(&net->logits, N * net->classes * 4, who));
+    TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
+    TRY(B.pinned(&net->h_probs, N * net->classes, who));
+    if (rc != TREXHIP_OK) return rc;
+    TH_CHECK_HIP(hipMemsetAsync(net->d_ovfc, 0, M, ctx->stream));
+    net->max_crops = n;
+    return TREXHIP_OK;
+}
+#undef TRY
+
+int arch_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
+    const Net& net = *static_cast<Net*>(ctx->net);
+    const ArchNet& a = *net.arch;
+    const ArchPlan& p = a.plan;
+    if (!ctx->attr_cnn) {
+        for (const LdsAttr& at : lds_attrs()) TH_CHECK_HIP(hipFuncSetAttribute(at.fn, hipFuncAttributeMaxDynamicSharedMemorySize, at.bytes));
+        ctx->attr_cnn = true;
+    }
+    hipStream_t s = ctx->stream;
+    const int mode = ctx->cnn_mode;
+    const bool h16 = mode == TREXHIP_CNN_FP16X3;
+    const size_t crop_bytes = (size_t)net.W * net.H * net.CH;
+    stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
+    if (h16) TH_CHECK_HIP(hipMemsetAsync(net.ovf(ARCH_STAT_RERUN), 0, 8, s));
+    const ArchLayerPlan& l0 = p.L[0];
+    const ArchLayerDev& last = a.L[p.n_conv - 1];
+    for (int c0 = 0; c0 < n; c0 += p.chunk) {
+        const int m = std::min(p.chunk, n - c0);
+        (l0.taps == 3 ? ARCH_CONV1_T3 : ARCH_CONV1_T5)[net.CH](s, dim3(m * l0.tl.tiles, l0.co_blocks), d_crops + (size_t)c0 * crop_bytes, a.L[0].w, a.L[0].bias,
+                                                              a.L[0].s, a.L[0].t, a.L[0].act, l0.CO, net.W, net.H, l0.pool == 2 ? 1 : 0, l0.tl.tx_n, l0.tl.tiles);
+        for (int i = 1; i < p.n_conv; ++i) {       // (profiling: conv2 and conv3 have stages of their own, as in the V118_3 chains)
+            const int stage = i == 1 ? TREXHIP_STAGE_CONV2 : i == 2 ? TREXHIP_STAGE_CONV3 : -1;
+            if (stage >= 0) stage_begin(ctx, stage);
+            launch_conv(s, net, a, i, mode, m, nullptr, ctx->n_cus);
+            if (stage >= 0) stage_end(ctx, stage);
+        }
+        if (h16) {     // the guarded re-run of this chunk, in bf16x6 on the plan: every workgroup of it returns at once unless a crop left the fp16 range
+            const uint32_t* g = net.ovf(OVF_PLAN);
+            K_ARCH_GUARD_PLAN(s, 1, net.ovf(OVF_RANGE), net.d_ovfc, m, net.ovf(OVF_PLAN), net.ovf(ARCH_STAT_RERUN));
+            for (int i = 1; i < p.n_conv; ++i) launch_conv(s, net, a, i, TREXHIP_CNN_BF16X6, m, g, ctx->n_cus);
+        }
+        const float* feat = last.pool ? last.pool : last.act;
+        if (p.spec->gap) {
+            K_GAP(s, cdiv((size_t)m * p.Cf, 256), feat, a.gap, m, p.Hf * p.Wf, p.Cf);
+            feat = a.gap;
+        }
+        K_ARCH_FC1(s, dim3(cdiv(m, 32), p.NH / 32), feat, a.wf1, a.bf1, a.fc1, m, p.K, p.NH);
+        K_ARCH_HEAD(s, cdiv(m, 4), a.fc1, a.hs, a.ht, a.wf2t, a.bf2, d_probs + (size_t)c0 * net.classes, d_logits ? d_logits + (size_t)c0 * net.classes : nullptr, m,
+                    net.classes, p.NH, p.spec->hidden);
+    }
+    stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
+    TH_CHECK_HIP(hipGetLastError());
+    return TREXHIP_OK;
+}
+
+}  // namespace trexhip

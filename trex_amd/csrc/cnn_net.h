@@ -8,8 +8,12 @@
 
 namespace trexhip {
 
+struct ArchNet;      // cnn_arch.h
+
 struct Net {
     int classes = 0, W = 0, H = 0, CH = 0, max_crops = 0;
+    ArchNet* arch = nullptr;                   // v100 / v110 / v119 / v200: the network's own state (cnn_arch.hip); of the fields below it uses the guard
+                                               // words, the per-crop flags, crops / probs / logits / h_probs and the two owners.  Null: V118_3
     uint4 *w2s = nullptr, *w3s = nullptr;      // bf16-split conv weights
     uint4 *w2h = nullptr, *w3h = nullptr;      // fp16-split conv weights (scaled by a power of two)
     float inv2h = 1.f, inv3h = 1.f;

@@ -1,6 +1,7 @@
 // cnn_weights.hip -- weight blob -> folded / repacked operand images of the identity network (cnn_weights.h).  Host code only; it is
 // a .hip file for _Float16, whose conversions are the fp16 rounding of the images.
 #include "cnn_weights.h"
+#include "cnn_arch_plan.h"
 #include "../../include/trexhip.h"
 #include <cmath>
 #include <cstring>
@@ -43,6 +44,8 @@ int parse_weight_blob(const void* blob, size_t bytes, const char* who, WeightBlo
     std::memcpy(hdr, blob, 32);
     if (hdr[0] != BLOB_MAGIC || hdr[1] != BLOB_VERSION) { set_error(pre + "bad magic/version"); return TREXHIP_E_INVALID; }
     const int classes = hdr[2], W = hdr[3], H = hdr[4], CH = hdr[5];
+    if (hdr[6] < TREXHIP_NET_V118_3 || hdr[6] > TREXHIP_NET_V200) { set_error(pre + "unknown network version id " + std::to_string(hdr[6]) + " (0..4: v118_3, v100, v110, v119, v200)"); return TREXHIP_E_INVALID; }
+    if (hdr[6] != TREXHIP_NET_V118_3) { set_error(pre + "the blob holds a " + arch_name(hdr[6]) + " network; only v118_3 is implemented here"); return TREXHIP_E_UNSUPPORTED; }
     if (size_check) { const int rc = size_check(W, H); if (rc != TREXHIP_OK) return rc; }
     if (CH != 1 && CH != 3) { set_error(pre + "channels must be 1 or 3"); return TREXHIP_E_UNSUPPORTED; }
     if (classes < 1 || classes > 1024) { set_error(pre + "classes must be 1..1024"); return TREXHIP_E_INVALID; }
@@ -50,6 +53,72 @@ int parse_weight_blob(const void* blob, size_t bytes, const char* who, WeightBlo
     view->classes = classes; view->W = W; view->H = H; view->CH = CH;
     const float* p = reinterpret_cast<const float*>(static_cast<const char*>(blob) + 32);
     for (int k = 0; k < T_COUNT; ++k) { view->t[k] = p; p += weight_tensor_count(k, classes, CH, W, H); }
+    return TREXHIP_OK;
+}
+
+// ---- the blobs of the other architectures ----
+int blob_arch_id(const void* blob, size_t bytes) {
+    if (bytes < 32) return -1;
+    int32_t hdr[8];
+    std::memcpy(hdr, blob, 32);
+    return hdr[0] == BLOB_MAGIC && hdr[1] == BLOB_VERSION ? hdr[6] : -1;
+}
+
+// walks the tensors of (id, classes, CH, W, H) in blob order: f(elements) is called once per tensor and returns where it lies
+template <class F>
+static void arch_walk(const ArchSpec& s, int classes, int CH, int W, int H, ArchBlob* v, F next) {
+    int ci = CH, h = H, w = W;
+    for (int i = 0; i < s.n_conv; ++i) {
+        const ArchConv& c = s.conv[i];
+        const float* p = next((size_t)c.CO * ci * c.taps * c.taps);
+        if (v) v->conv[i][0] = p;
+        p = next(c.CO);
+        if (v) v->conv[i][1] = p;
+        for (int k = 2; k < 6; ++k) { p = s.bn2d ? next(c.CO) : nullptr; if (v) v->conv[i][k] = p; }
+        ci = c.CO;
+        if (c.pool) { h /= c.pool; w /= c.pool; }
+    }
+    const size_t flat = s.gap ? (size_t)ci : (size_t)ci * h * w;
+    const float* p = next((size_t)s.hidden * flat);
+    if (v) v->fc1w = p;
+    p = next(s.hidden);
+    if (v) v->fc1b = p;
+    for (int k = 0; k < 4; ++k) { p = s.bn1d ? next(s.hidden) : nullptr; if (v) v->bn1d[k] = p; }
+    p = next((size_t)classes * s.hidden);
+    if (v) v->fc2w = p;
+    p = next(classes);
+    if (v) v->fc2b = p;
+}
+
+size_t arch_blob_bytes(int id, int classes, int CH, int W, int H) {
+    if (id == TREXHIP_NET_V118_3) return (CH == 1 || CH == 3) && W >= 8 && W <= 256 && H >= 8 && H <= 256 && classes >= 1 && classes <= 1024 ? weight_blob_bytes(classes, CH, W, H) : 0;
+    const ArchSpec* s = arch_spec(id);
+    if (!s || (CH != 1 && CH != 3) || W < s->min_size || W > 256 || H < s->min_size || H > 256 || classes < 1 || classes > 1024) return 0;
+    size_t n = 0;
+    arch_walk(*s, classes, CH, W, H, nullptr, [&](size_t cnt) -> const float* { n += cnt; return nullptr; });
+    return 32 + 4 * n;
+}
+
+int parse_arch_blob(const void* blob, size_t bytes, const char* who, ArchBlob* view) {
+    const std::string pre = std::string(who) + ": ";
+    if (bytes < 32) { set_error(pre + "blob too small"); return TREXHIP_E_INVALID; }
+    int32_t hdr[8];
+    std::memcpy(hdr, blob, 32);
+    if (hdr[0] != BLOB_MAGIC || hdr[1] != BLOB_VERSION) { set_error(pre + "bad magic/version"); return TREXHIP_E_INVALID; }
+    const int classes = hdr[2], W = hdr[3], H = hdr[4], CH = hdr[5], id = hdr[6];
+    const ArchSpec* s = arch_spec(id);
+    if (!s) { set_error(pre + "unknown network version id " + std::to_string(id) + " (0..4: v118_3, v100, v110, v119, v200)"); return TREXHIP_E_INVALID; }
+    if (W < s->min_size || W > 256 || H < s->min_size || H > 256) {
+        set_error(pre + "individual_image_size " + std::to_string(W) + "x" + std::to_string(H) + " is outside " + std::to_string(s->min_size) + "..256 x " +
+                  std::to_string(s->min_size) + "..256, the range of " + s->name + " (minimum " + std::to_string(s->min_size) + ")");
+        return TREXHIP_E_UNSUPPORTED;
+    }
+    if (CH != 1 && CH != 3) { set_error(pre + "channels must be 1 or 3"); return TREXHIP_E_UNSUPPORTED; }
+    if (classes < 1 || classes > 1024) { set_error(pre + "classes must be 1..1024"); return TREXHIP_E_INVALID; }
+    if (bytes != arch_blob_bytes(id, classes, CH, W, H)) { set_error(pre + "blob size does not match its header (" + s->name + ")"); return TREXHIP_E_INVALID; }
+    view->id = id; view->classes = classes; view->W = W; view->H = H; view->CH = CH;
+    const float* p = reinterpret_cast<const float*>(static_cast<const char*>(blob) + 32);
+    arch_walk(*s, classes, CH, W, H, view, [&](size_t cnt) -> const float* { const float* at = p; p += cnt; return at; });
     return TREXHIP_OK;
 }
 
@@ -193,6 +262,90 @@ ScaledImage pack_fc1_f16(const std::vector<float>& wf) {
     const float sc = pow2_scale(max_abs(wf), &im.inv);
     im.v = piece_image<2>((int)(wf.size() / 128 / 8), 1, 8, 128, [&](size_t i, uint16_t* pc) { split_f16x2(wf[i] * sc, pc); });
     return im;
+}
+
+// ---- operand images of the other architectures ----
+// the epilogue's vectors of one layer (see cnn_weights.h); returns the per-channel factor folded into the weights
+static std::vector<double> arch_affine(const float* const* layer, int CO, int CO_pad, bool fold, ArchConvImage* im) {
+    const float *b = layer[1], *g = layer[2], *beta = layer[3], *mean = layer[4], *var = layer[5];
+    im->bias.assign(CO_pad, 0.f); im->s.assign(CO_pad, 0.f); im->t.assign(CO_pad, 0.f);
+    std::vector<double> f(CO, 1.0);
+    for (int co = 0; co < CO; ++co) {
+        const double s = g ? (double)g[co] / std::sqrt((double)var[co] + 1e-5) : 1.0;     // BatchNorm2d eps
+        if (fold) {
+            f[co] = s;
+            im->bias[co] = (float)(((double)b[co] - (double)mean[co]) * s + (double)beta[co]);
+            im->s[co] = 1.f;
+        } else {
+            im->bias[co] = b[co];
+            im->s[co] = (float)s;
+            im->t[co] = g ? (float)((double)beta[co] - (double)mean[co] * s) : 0.f;
+        }
+    }
+    return f;
+}
+
+ArchConvImage pack_arch_conv(const float* const* layer, int CO, int CI, int taps, int CO_pad, int CI_pad, int COB, bool fold) {
+    ArchConvImage im;
+    const std::vector<double> f = arch_affine(layer, CO, CO_pad, fold, &im);
+    const int T2 = taps * taps, ncc = CI_pad / 16;
+    im.w.assign((size_t)CO_pad * CI_pad * T2, 0.f);
+    for (int co = 0; co < CO; ++co)
+        for (int ci = 0; ci < CI; ++ci)
+            for (int tap = 0; tap < T2; ++tap)
+                im.w[(((((size_t)(co / COB)) * ncc + ci / 16) * T2 + tap) * 16 + ci % 16) * COB + co % COB] = (float)((double)layer[0][((size_t)co * CI + ci) * T2 + tap] * f[co]);
+    return im;
+}
+
+ArchConvImage pack_arch_conv1(const float* const* layer, int CO, int CH, int taps, int CO_pad, bool fold) {
+    ArchConvImage im;
+    const std::vector<double> f = arch_affine(layer, CO, CO_pad, fold, &im);
+    const int T2 = taps * taps;
+    im.w.assign((size_t)CO_pad * CH * T2, 0.f);
+    for (int co = 0; co < CO; ++co)
+        for (int c = 0; c < CH; ++c)
+            for (int tap = 0; tap < T2; ++tap)
+                im.w[((((size_t)(co / 16)) * CH + c) * T2 + tap) * 16 + co % 16] = (float)((double)layer[0][((size_t)co * CH + c) * T2 + tap] * f[co]);
+    return im;
+}
+
+std::vector<uint16_t> pack_arch_bf16x3(const std::vector<float>& wp, int COB) {
+    return piece_image<3>((int)(wp.size() / ((size_t)16 * COB)), 1, 16, COB, [&](size_t i, uint16_t* pc) { split_bf16x3(wp[i], pc); });
+}
+
+ScaledImage pack_arch_f16x2(const std::vector<float>& wp, int COB) {
+    ScaledImage im;
+    const float sc = pow2_scale(max_abs(wp), &im.inv);
+    im.v = piece_image<2>((int)(wp.size() / ((size_t)16 * COB)), 1, 16, COB, [&](size_t i, uint16_t* pc) { split_f16x2(wp[i] * sc, pc); });
+    return im;
+}
+
+Folded pack_arch_fc1(const float* w, const float* b, int hidden, int NH, int C, int C_pad, int P) {
+    const size_t flat = (size_t)C * P;
+    Folded f{std::vector<float>((size_t)C_pad * P * NH, 0.f), std::vector<float>(NH, 0.f)};
+    for (int o = 0; o < hidden; ++o) {
+        f.b[o] = b[o];
+        for (int c = 0; c < C; ++c)
+            for (int hw = 0; hw < P; ++hw) f.w[((size_t)hw * C_pad + c) * NH + o] = w[(size_t)o * flat + (size_t)c * P + hw];
+    }
+    return f;
+}
+
+Folded pack_arch_bn1d(const float* const* bn, int hidden, int NH) {
+    Folded f{std::vector<float>(NH, 0.f), std::vector<float>(NH, 0.f)};
+    for (int o = 0; o < hidden; ++o) {
+        const double s = bn && bn[0] ? (double)bn[0][o] / std::sqrt((double)bn[3][o] + 1e-5) : 1.0;     // BatchNorm1d eps
+        f.w[o] = (float)s;
+        f.b[o] = bn && bn[0] ? (float)((double)bn[1][o] - (double)bn[2][o] * s) : 0.f;
+    }
+    return f;
+}
+
+std::vector<float> pack_arch_fc2(const float* w, int classes, int hidden) {
+    std::vector<float> t((size_t)hidden * classes);
+    for (int c = 0; c < classes; ++c)
+        for (int k = 0; k < hidden; ++k) t[(size_t)k * classes + c] = w[(size_t)c * hidden + k];
+    return t;
 }
 
 std::vector<float> pack_fc2(const float* w, int classes) {

@@ -38,6 +38,10 @@ struct HipVINetwork {
     trexhip_ctx* context() const { return _ctx; }          // for the adapters that work on this network's device buffers (HipUniqueness.h)
     bool weights_loaded() const { return trexhip_num_classes(_ctx) > 0; }
     int num_classes() const { return trexhip_num_classes(_ctx); }
+    // visual_identification_version of the loaded network as TREXHIP_NET_* (core/default_config.h:83; a checkpoint's metadata.model_type):
+    // V118_3, v100, v110, v119 or v200.  probabilities() is the same call for all five; the Trainer below takes V118_3 blobs only and throws
+    // the library's TREXHIP_E_UNSUPPORTED text for the others
+    int network_version() const { return trexhip_network_version(_ctx); }
 
     static size_t batch_size_for(size_t n_ids) {        // VisualIdentification.cpp:112-118
         size_t b = n_ids > 64 ? n_ids : 64;

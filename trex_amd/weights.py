@@ -1,8 +1,9 @@
-"""Identity-network (V118_3) weights: deterministic recipe for synthetic weights + the flat blob
+"""Identity-network weights: deterministic recipe for synthetic weights + the flat blob
 format libtrexhip loads (trexhip_load_weights).
 
-Blob = little-endian: 8 x int32 header {magic 'TRXW', version 1, num_classes, width, height, channels, 0, 0}
-followed by float32 tensors in PyTorch state_dict order and shapes of
+Blob = little-endian: 8 x int32 header {magic 'TRXW', version 1, num_classes, width, height, channels, architecture id, 0}
+(architecture id: ARCH_IDS, 0 = V118_3; the other four: shapes(arch=...), ARCH_LAYERS)
+followed by float32 tensors in PyTorch state_dict order and shapes, for V118_3 those of
 visual_identification_network_torch.py:184-211 (V118_3):
   conv1.weight[16,C,5,5] conv1.bias[16] bn1.weight bn1.bias bn1.running_mean bn1.running_var [16 each]
   conv2.weight[64,16,5,5] conv2.bias[64] bn2.* [64]  conv3.weight[128,64,5,5] conv3.bias[128] bn3.* [128]
@@ -31,18 +32,57 @@ TENSORS = [
 ]
 
 
-def shapes(num_classes, channels=1, width=80, height=80):
-    flat = 128 * (width // 8) * (height // 8)
-    return [(n, f(num_classes, channels, flat)) for n, f in TENSORS]
+# The architectures of visual_identification_network_torch.py:30-382 the library runs, by the id the blob's header word 6 carries.
+# Per architecture: the convolutions (output channels, taps), BatchNorm2d or not, the flatten, fc1's width and its BatchNorm1d's name.
+ARCH_IDS = {"v118_3": 0, "v100": 1, "v110": 2, "v119": 3, "v200": 4}
+ARCH_NAMES = {v: k for k, v in ARCH_IDS.items()}
+ARCH_LAYERS = {
+    "v100": dict(convs=[(16, 5), (64, 5), (100, 5)], bn2d=False, flat=lambda w, h: 100 * (w // 8) * (h // 8), hidden=100, bn1d=None, min=8),
+    "v110": dict(convs=[(16, 5), (64, 5), (100, 5)], bn2d=True, flat=lambda w, h: 100 * (w // 8) * (h // 8), hidden=100, bn1d="bn4", min=8),
+    "v119": dict(convs=[(256, 5), (128, 5), (32, 5), (128, 5)], bn2d=True, flat=lambda w, h: 128 * (w // 16) * (h // 16), hidden=1024, bn1d="bn5", min=16),
+    "v200": dict(convs=[(64, 3), (128, 3), (256, 3), (512, 3), (512, 3)], bn2d=True, flat=lambda w, h: 512, hidden=1024, bn1d="bn6", min=27),
+}
+_BN = ("weight", "bias", "running_mean", "running_var")
 
 
-def synthetic_state(num_classes, seed, channels=1, width=80, height=80):
+def arch_name(arch):
+    """'v200', 'V200', 4 -> 'v200'"""
+    if isinstance(arch, (int, np.integer)):
+        return ARCH_NAMES[int(arch)]
+    a = str(arch).lower()
+    if a not in ARCH_IDS:
+        raise ValueError(f"unknown identity network version {arch!r}: one of {sorted(ARCH_IDS)}")
+    return a
+
+
+def shapes(num_classes, channels=1, width=80, height=80, arch="v118_3"):
+    """(name, shape) of every tensor in the architecture's state_dict order, without num_batches_tracked"""
+    arch = arch_name(arch)
+    if arch == "v118_3":
+        flat = 128 * (width // 8) * (height // 8)
+        return [(n, f(num_classes, channels, flat)) for n, f in TENSORS]
+    L = ARCH_LAYERS[arch]
+    out, ci = [], channels
+    for i, (co, k) in enumerate(L["convs"], 1):
+        out += [(f"conv{i}.weight", (co, ci, k, k)), (f"conv{i}.bias", (co,))]
+        if L["bn2d"]:
+            out += [(f"bn{i}.{t}", (co,)) for t in _BN]
+        ci = co
+    hid = L["hidden"]
+    out += [("fc1.weight", (hid, L["flat"](width, height))), ("fc1.bias", (hid,))]
+    if L["bn1d"]:
+        out += [(f"{L['bn1d']}.{t}", (hid,)) for t in _BN]
+    out += [("fc2.weight", (num_classes, hid)), ("fc2.bias", (num_classes,))]
+    return out
+
+
+def synthetic_state(num_classes, seed, channels=1, width=80, height=80, arch="v118_3"):
     """Deterministic random weights (numpy PCG64, reproducible anywhere numpy runs): uniform
     +-1/sqrt(fan_in) like PyTorch's default init, non-trivial BN/LayerNorm affine.  Running
     statistics are placeholders here; calibrated values come from the golden fixture."""
     rng = np.random.default_rng(seed)
     st = {}
-    for name, shp in shapes(num_classes, channels, width, height):
+    for name, shp in shapes(num_classes, channels, width, height, arch):
         if name.endswith("running_mean"):
             st[name] = np.zeros(shp, np.float32)
         elif name.endswith("running_var"):
@@ -78,23 +118,29 @@ def synthetic_crops(n, seed, channels=1, width=80, height=80):
     return out
 
 
-def pack_blob(state, num_classes, channels=1, width=80, height=80):
-    hdr = np.array([MAGIC, 1, num_classes, width, height, channels, 0, 0], np.int32)
+def pack_blob(state, num_classes, channels=1, width=80, height=80, arch="v118_3"):
+    hdr = np.array([MAGIC, 1, num_classes, width, height, channels, ARCH_IDS[arch_name(arch)], 0], np.int32)
     parts = [hdr.tobytes()]
-    for name, shp in shapes(num_classes, channels, width, height):
+    for name, shp in shapes(num_classes, channels, width, height, arch):
         t = np.ascontiguousarray(state[name], np.float32)
         assert t.shape == tuple(shp), (name, t.shape, shp)
         parts.append(t.tobytes())
     return b"".join(parts)
 
 
-def unpack_blob(blob):
-    """Inverse of pack_blob: -> (state dict, num_classes, channels)."""
+def blob_arch(blob):
+    """the architecture name a blob's header word 6 names"""
+    return arch_name(int(np.frombuffer(blob[24:28], np.int32)[0]))
+
+
+def unpack_blob(blob, arch="v118_3"):
+    """Inverse of pack_blob: -> (state dict, num_classes, channels).  `arch` must be the blob's own (blob_arch)."""
     hdr = np.frombuffer(blob[:32], np.int32)
     assert int(hdr[0]) == MAGIC and int(hdr[1]) == 1, "not a TRXW v1 blob"
     classes, width, height, channels = int(hdr[2]), int(hdr[3]), int(hdr[4]), int(hdr[5])
+    assert int(hdr[6]) == ARCH_IDS[arch_name(arch)], f"the blob holds {ARCH_NAMES.get(int(hdr[6]), int(hdr[6]))}, not {arch}"
     st, off = {}, 32
-    for name, shp in shapes(classes, channels, width, height):
+    for name, shp in shapes(classes, channels, width, height, arch):
         cnt = int(np.prod(shp))
         st[name] = np.frombuffer(blob[off:off + 4 * cnt], np.float32).reshape(shp).copy()
         off += 4 * cnt
