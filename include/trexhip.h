@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 17
+#define TREXHIP_ABI_VERSION 18
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -519,13 +519,13 @@ int trexhip_network_channels(trexhip_ctx* ctx);   /* channels of the crops the l
 int trexhip_network_image_size(trexhip_ctx* ctx, int32_t* width, int32_t* height);
 /* The architecture of the network: TRex's setting visual_identification_version (core/default_config.h:83), a checkpoint's
  * metadata.model_type.  The blob's header word 6 carries it (0 in every blob written before ABI 17, which keep their meaning):
- *   TREXHIP_NET_V118_3  visual_identification_network_torch.py:184-258, sizes 8..256 each way -- the chains above, and the only one that trains
+ *   TREXHIP_NET_V118_3  visual_identification_network_torch.py:184-258, sizes 8..256 each way -- the chains above
  *   TREXHIP_NET_V100    :328-382   8..256      TREXHIP_NET_V110  :262-324   8..256
  *   TREXHIP_NET_V119    :106-180   16..256     TREXHIP_NET_V200  :30-102    27..256
  * The four others run one generic chain (cnn_arch.hip): first layer exact fp32, the further convolutions in the precision mode below with the
  * same range guard, fc1 exact fp32; a call's crops are walked in chunks of trexhip_identify_chunk_crops (a constant of version and size), and a
- * crop's row does not depend on its chunk.  A smaller size is TREXHIP_E_UNSUPPORTED, an id outside 0..4 TREXHIP_E_INVALID; a trainer refuses
- * every version but V118_3 with TREXHIP_E_UNSUPPORTED.  (ABI 17) */
+ * crop's row does not depend on its chunk.  A smaller size is TREXHIP_E_UNSUPPORTED, an id outside 0..4 TREXHIP_E_INVALID.  V118_3, v100 and v110
+ * train (trexhip_trainer_create, ABI 18); a trainer refuses v119 and v200 with TREXHIP_E_UNSUPPORTED.  (ABI 17) */
 enum { TREXHIP_NET_V118_3 = 0, TREXHIP_NET_V100 = 1, TREXHIP_NET_V110 = 2, TREXHIP_NET_V119 = 3, TREXHIP_NET_V200 = 4 };
 /* the loaded network's TREXHIP_NET_*; 0 without a context or weights, like trexhip_num_classes (VINetwork's
  * visual_identification_version, ml/VisualIdentification.cpp) */
@@ -662,6 +662,19 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  *   trexhip_trainer_export     the current weights as a blob for trexhip_load_weights (the reference hands its state_dict back)
  *   trexhip_trainer_read       one tensor in torch's layout; tensor = index in state_dict order (0 conv1.weight ... 23 fc2.bias,
  *                              running statistics included), kind 0 parameter, 1 gradient of the last step, 2 / 3 Adam moments
+ * v100 and v110 (ABI 18).  A blob whose header names TREXHIP_NET_V100 or TREXHIP_NET_V110 (:328-382, :262-324) is parsed like
+ * trexhip_load_weights parses it and gives a trainer of that version (trexhip_trainer_version): the same calls, the same resident path
+ * (trexhip_augment_device, trexhip_train_predict_device, the validation and average calls).  Such a trainer runs one generic chain in exact
+ * fp32 at every size, 80 x 80 included, at both values of `precision` (trex_amd/csrc/train_arch.hip), on the context's stream alone.  What differs:
+ *   dropout rates              the architecture's: v100 0.25, 0.25, 0.25, 0.5; v110 0.25 four times.  trexhip_train_params.dropout is V118_3's
+ *                              field; it is range-checked and otherwise not read
+ *   d_keep_masks               n*16 + n*64 + n*100 + n*100 bytes: conv3 has 100 channels
+ *   v110 and n = 1             a training step is TREXHIP_E_INVALID before any launch and leaves the trainer unchanged (the reference's
+ *                              BatchNorm raises "Expected more than 1 value per channel when training"); eval and predict take n = 1
+ *   trexhip_trainer_read       the version's own state_dict order and torch's shapes (trex_amd/weights.py shapes(arch=...)): v100 has 10 tensors,
+ *                              v110 26 (bn4's running statistics included); conv3 and fc1 have 100 channels
+ *   trexhip_trainer_export     header word 6 names the version; the blob loads with trexhip_load_weights
+ * v119 and v200 are refused with TREXHIP_E_UNSUPPORTED and a text that names the version.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct trexhip_trainer trexhip_trainer;
 typedef struct {
@@ -669,7 +682,8 @@ typedef struct {
     float lr;                   /* learning_rate, 0.001 (visual_identification_network.py:151)                                */
     float beta1, beta2, eps;    /* torch.optim.Adam defaults 0.9, 0.999, 1e-8                                                */
     float bn_momentum;          /* nn.BatchNorm2d default 0.1                                                                */
-    float dropout;              /* 0.05 for all four dropout layers (visual_identification_network_torch.py:189-208)         */
+    float dropout;              /* V118_3: 0.05 for all four dropout layers (visual_identification_network_torch.py:189-208).
+                                   v100 / v110 use their architecture's rates and do not read it                              */
     int32_t precision;          /* (80 x 80; other sizes run exact fp32 at both values) arithmetic of the conv2 / conv3 forward, data-gradient and weight-gradient convolutions: 0 = fp16 two-piece split on the
                                    16-bit matrix cores (22-bit operands, fp32 accumulate, per-tensor power-of-two scales: the inference
                                    path's arithmetic), 1 = exact fp32 MFMA.  Everything else is fp32 either way                     */
@@ -682,6 +696,8 @@ int trexhip_trainer_set_lr(trexhip_trainer* trainer, float lr);
 int64_t trexhip_trainer_steps(trexhip_trainer* trainer);
 /* the individual_image_size of the blob the trainer was created from: what every batch, crop and exported blob of this trainer has (ABI 14) */
 int trexhip_trainer_image_size(trexhip_trainer* trainer, int32_t* width, int32_t* height);
+/* the TREXHIP_NET_* of the blob the trainer was created from: V118_3, V100 or V110 (ABI 18) */
+int trexhip_trainer_version(trexhip_trainer* trainer, int32_t* version);
 int trexhip_train_step_device(trexhip_trainer* trainer, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks,
                               float* loss, int32_t* correct);
 /* model.eval() forward + mean cross entropy + arg-max count of one validation batch (train(), :1171-1190: what ReduceLROnPlateau and the

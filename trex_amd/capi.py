@@ -198,7 +198,7 @@ SYMBOLS = [
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
     "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats", "trexhip_identify_skip_stats", "trexhip_identify_skip3_stats",
-    "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
+    "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_trainer_version", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
@@ -296,6 +296,7 @@ def lib():
         L.trexhip_trainer_steps.argtypes = [C.c_void_p]
         L.trexhip_trainer_steps.restype = C.c_int64
         L.trexhip_trainer_image_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.trexhip_trainer_version.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.trexhip_train_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_train_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_train_eval_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -847,7 +848,8 @@ class Segmenter:
 
 
 class Trainer:
-    """Training step of the identity network (include/trexhip.h: trexhip_trainer_*, trexhip_train_step_device)."""
+    """Training step of the identity network (include/trexhip.h: trexhip_trainer_*, trexhip_train_step_device): V118_3, v100 or v110, as the
+    blob's header says.  `dropout` is V118_3's rate: v100 and v110 use their architecture's own and do not read it."""
 
     def __init__(self, seg, weight_blob, max_batch, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, bn_momentum=0.1, dropout=0.05, seed=0, precision=0):
         self._h = C.c_void_p()
@@ -860,6 +862,12 @@ class Trainer:
         _check(lib().trexhip_trainer_image_size(self._h, C.byref(w), C.byref(h)))
         self.width, self.height = w.value, h.value        # individual_image_size: every batch and crop of this trainer is [n][height][width][channels]
         self._blob_bytes = len(weight_blob)
+        v = C.c_int32()
+        _check(lib().trexhip_trainer_version(self._h, C.byref(v)))
+        self.version = v.value                            # TREXHIP_NET_*: 0 V118_3, 1 v100, 2 v110 (trex_amd.weights.ARCH_IDS)
+        # injected keep masks of one sample: Dropout2d behind block 1, 2, 3 and the Dropout behind fc1; conv3 has 128 channels in V118_3, 100 in v100 / v110
+        self.mask_planes = (16, 64, 128, 100) if self.version == 0 else (16, 64, 100, 100)
+        self.mask_row = sum(self.mask_planes)
 
     def step_device(self, d_inputs_ptr, d_targets_ptr, n, d_keep_ptr=0, want_loss=True):
         """-> (mean loss, correct count) when want_loss (synchronises), else None"""
@@ -882,11 +890,12 @@ class Trainer:
         return np.ascontiguousarray(x, np.float32), np.ascontiguousarray(t, np.int32)
 
     def step(self, inputs, targets, keep_masks=None):
-        """host arrays: inputs float32 (n,height,width,C) in [0,255], targets int (n,), keep_masks uint8 (n*308,) or None -> (loss, correct)"""
+        """host arrays: inputs float32 (n,height,width,C) in [0,255], targets int (n,), keep_masks uint8 (n*mask_row,) or None -> (loss, correct);
+        mask_row is 308 for V118_3 and 280 for v100 / v110"""
         x, y = self._check_batch(inputs, targets)
         k = np.ascontiguousarray(keep_masks, np.uint8) if keep_masks is not None else None
-        if k is not None and k.size != x.shape[0] * 308:
-            raise ValueError(f"keep_masks holds {k.size} entries, a batch of {x.shape[0]} needs {x.shape[0]} x 308 (16 + 64 + 128 + 100 per sample)")
+        if k is not None and k.size != x.shape[0] * self.mask_row:
+            raise ValueError(f"keep_masks holds {k.size} entries, a batch of {x.shape[0]} needs {x.shape[0]} x {self.mask_row} ({' + '.join(map(str, self.mask_planes))} per sample)")
         loss, correct = C.c_float(), C.c_int32()
         _check(lib().trexhip_train_step(self._h, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.shape[0],
                                         k.ctypes.data_as(C.c_void_p) if k is not None else None, C.byref(loss), C.byref(correct)))
@@ -918,7 +927,7 @@ class Trainer:
         return int(lib().trexhip_trainer_steps(self._h))
 
     def read(self, tensor, kind, shape):
-        """tensor: index in state_dict order (trex_amd.weights.TENSORS); kind 0 parameter, 1 gradient, 2 / 3 Adam moments; torch layout"""
+        """tensor: index in the version's state_dict order (trex_amd.weights.shapes(arch=version)); kind 0 parameter, 1 gradient, 2 / 3 Adam moments; torch layout"""
         out = np.empty(int(np.prod(shape)), np.float32)
         _check(lib().trexhip_trainer_read(self._h, tensor, kind, out.ctypes.data_as(C.c_void_p), out.size))
         return out.reshape(shape)

@@ -24,11 +24,15 @@
 // The kernels of this file are the 80x80 chain.  A blob of any other individual_image_size (8..256 each way) trains on the chain of
 // train_any.hip (exact fp32, geometry in train_geom.h): the same walk, with `Trainer::any` choosing the launch at every size-dependent
 // kernel; the head, Adam, the masks, the target check, the loss and the reductions are shared.
+// A v100 or v110 blob gives a trainer of train_arch.hip instead (ArchTrainer): the entry points at the end of this file hand every call of such a
+// handle over, and that chain launches this file's size-independent kernels through train_shared.h.
 #include "internal.h"
 #include "conv_f32.h"
 #include "cnn_weights.h"
 #include "train_dev.h"
 #include "train_any.h"
+#include "train_shared.h"
+#include "train_arch.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1337,7 +1341,7 @@ static constexpr int FC1_K = 128 * FC1_POS;                          // = 12800
 static constexpr int KEEP_OFF[4] = {0, 16, 16 + 64, 16 + 64 + 128}, KEEP_ROW = 16 + 64 + 128 + HID;
 static_assert(KEEP_ROW == 308 && FC1_K == 12800, "mask row / fc1 of the 80x80 network");
 static constexpr int C1_BPC = IMG / 4, WG1_BPC = IMG / 8;            // workgroups per crop of k_t_conv1 (4 rows each) and k_t_wgrad1 (8 rows)
-static constexpr int RED_BLOCKS = 256, BWD_BLOCKS = 1024;            // grids of the reduction kernels (partials: red[BWD_BLOCKS][2][128])
+static constexpr int RED_BLOCKS = T_RED_BLOCKS, BWD_BLOCKS = T_BWD_BLOCKS;   // grids of the reduction kernels (partials: red[BWD_BLOCKS][2][128])
 
 // What each event of a step orders.  "main" is the context's stream, "side" the trainer's second one
 enum {
@@ -1693,26 +1697,83 @@ static int trainer_step(Trainer* t, const float* x, const int32_t* targets, int 
     // ---- optimizer
     t->step += 1;
     {
-        const double b1 = t->p.beta1, b2 = t->p.beta2;
-        const double bc1 = 1.0 - std::pow(b1, (double)t->step), bc2 = 1.0 - std::pow(b2, (double)t->step);
-        AdamSkip skip;
+        uint32_t lo[6], hi[6];
         int k = 0;
         for (const Layer& L : t->L)
-            for (int buf : {L.rm, L.rv}) { skip.lo[k] = (uint32_t)o[buf]; skip.hi[k] = (uint32_t)(o[buf] + t->cnt[buf]); ++k; }
-        hipLaunchKernelGGL(k_t_adam, dim3((unsigned)((t->total + 255) / 256)), dim3(256), 0, s, P, G, t->M, t->V, (uint32_t)t->total, skip, (float)(1.0 - b1), (float)b2,
-                           (float)(1.0 - b2), (float)((double)t->p.lr / bc1), (float)std::sqrt(bc2), t->p.eps, t->bad_target);
+            for (int buf : {L.rm, L.rv}) { lo[k] = (uint32_t)o[buf]; hi[k] = (uint32_t)(o[buf] + t->cnt[buf]); ++k; }
+        t_adam(s, P, G, t->M, t->V, t->total, lo, hi, 6, t->p.lr, t->p.beta1, t->p.beta2, t->p.eps, t->step, t->bad_target);
     }
     TH_CHECK_HIP(hipGetLastError());
     return h_loss || h_correct ? fetch_loss(t, s, h_loss, h_correct) : TREXHIP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// train_shared.h: the size-independent kernels as train_arch.hip launches them
+// ------------------------------------------------------------------------------------------------
+void t_bn_stats(hipStream_t s, int C, const float* d, size_t rows, double* partial) {
+    const auto fn = C == 16 ? &k_t_bn_stats<16> : C == 64 ? &k_t_bn_stats<64> : &k_t_bn_stats<128>;
+    hipLaunchKernelGGL(fn, dim3(RED_BLOCKS), dim3(256), 0, s, d, rows, partial);
+}
+void t_fin_bn_stats(hipStream_t s, const double* partial, int nblocks, int C, double count, float momentum, float* mean, float* invstd, float* run_mean,
+                    float* run_var, const int32_t* refused) {
+    hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_STATS>), dim3(C), dim3(256), 0, s, partial, nblocks, C, FinArgs{count, momentum, mean, invstd, run_mean, run_var, refused});
+}
+void t_fin_bn_bwd(hipStream_t s, const double* partial, int nblocks, int C, float* sums, float* d_gamma, float* d_beta) {
+    hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_BWD>), dim3(C), dim3(256), 0, s, partial, nblocks, C, FinArgs{0.0, 0.f, sums, d_gamma, d_beta, nullptr, nullptr});
+}
+void t_fin_bias(hipStream_t s, const double* partial, int nblocks, int C, float* d_bias) {
+    hipLaunchKernelGGL((k_t_red_finalize<FIN_BIAS>), dim3(C), dim3(256), 0, s, partial, nblocks, C, FinArgs{0.0, 0.f, d_bias, nullptr, nullptr, nullptr, nullptr});
+}
+void t_bn_from_running(hipStream_t s, const float* run_mean, const float* run_var, int C, float* mean, float* invstd) {
+    hipLaunchKernelGGL(k_t_bn_from_running, dim3(1), dim3(128), 0, s, run_mean, run_var, C, mean, invstd);
+}
+void t_wgrad_reduce(hipStream_t s, const float* part, int shares, int CI, int CO, int CIC, float* g) {
+    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * CI * CO + 255) / 256), dim3(256), 0, s, part, shares, CI, CO, CIC, g);
+}
+void t_reduce(hipStream_t s, const float* part, int nparts, int count, float* out) {
+    hipLaunchKernelGGL(k_t_reduce, dim3((count + 15) / 16), dim3(256), 0, s, part, nparts, count, out);
+}
+void t_repack_bwd(hipStream_t s, const float* wf, int CI, int CO, int CIC, int COP, int CICB, float* wb) {
+    hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * CO * COP + 255) / 256), dim3(256), 0, s, wf, CI, CO, CIC, COP, CICB, wb);
+}
+void t_adam(hipStream_t s, float* P, const float* G, float* M, float* V, size_t total, const uint32_t* skip_lo, const uint32_t* skip_hi, int nskip, double lr,
+            double beta1, double beta2, float eps, int64_t step, const int32_t* refused) {
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    AdamSkip skip{};
+    for (int k = 0; k < nskip && k < 6; ++k) { skip.lo[k] = skip_lo[k]; skip.hi[k] = skip_hi[k]; }
+    hipLaunchKernelGGL(k_t_adam, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P, G, M, V, (uint32_t)total, skip, (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), eps, refused);
+}
+void t_masks(hipStream_t s, uint8_t* keep, size_t count, uint64_t seed, uint64_t step, float p_drop) {
+    hipLaunchKernelGGL(k_t_masks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, keep, count, seed, step, p_drop);
+}
+void t_check_targets(hipStream_t s, const int32_t* targets, int n, int classes, int32_t* refused, int eval) {
+    hipLaunchKernelGGL(k_t_check_targets, dim3(1), dim3(256), 0, s, targets, n, classes, refused, eval);
+}
+void t_loss(hipStream_t s, const float* loss, const int32_t* correct, int n, float* out2) {
+    hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, s, loss, correct, n, out2);
+}
+
 }  // namespace trexhip
 
-struct trexhip_trainer { trexhip::Trainer* t; };
+// a trainer is one of two: V118_3 (t, this file) or v100 / v110 (a, train_arch.hip); every entry point below looks at `a` first
+struct trexhip_trainer { trexhip::Trainer* t; trexhip::ArchTrainer* a = nullptr; };
 
 extern "C" {
 
 using namespace trexhip;
+
+// what trexhip_trainer_create asks of its parameters, whatever the network
+static int check_train_params(const trexhip_train_params* p) {
+    if (p->max_batch < 1 || p->max_batch > 4096) { set_error("trexhip_trainer_create: max_batch must be 1..4096"); return TREXHIP_E_INVALID; }
+    if (p->precision != 0 && p->precision != 1) { set_error("trexhip_trainer_create: precision must be 0 (fp16 two-piece split convolutions) or 1 (exact fp32 MFMA)"); return TREXHIP_E_INVALID; }
+    if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f) || !(p->eps > 0.f) ||
+        !(p->dropout >= 0.f && p->dropout < 1.f) || !(p->bn_momentum >= 0.f && p->bn_momentum <= 1.f)) {
+        set_error("trexhip_trainer_create: lr > 0, 0 <= beta < 1, eps > 0, 0 <= dropout < 1, 0 <= bn_momentum <= 1 are required");
+        return TREXHIP_E_INVALID;
+    }
+    return TREXHIP_OK;
+}
 
 size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) {
     return weight_blob_bytes(classes, channels, IMG, IMG);
@@ -1721,6 +1782,14 @@ size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) {
 int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, trexhip_trainer** out) {
     if (!ctx || !blob || !p || !out) { set_error("trexhip_trainer_create: null argument"); return TREXHIP_E_INVALID; }
     *out = nullptr;
+    const int arch = blob_arch_id(blob, bytes);
+    if (arch == TREXHIP_NET_V100 || arch == TREXHIP_NET_V110) {       // the parser of trexhip_load_weights, the chain of train_arch.hip
+        if (const int rc = check_train_params(p)) return rc;
+        ArchTrainer* a = nullptr;
+        if (const int rc = arch_trainer_create(ctx, blob, bytes, p, &a)) return rc;
+        *out = new trexhip_trainer{nullptr, a};
+        return TREXHIP_OK;
+    }
     WeightBlob wb;
     const int prc = parse_weight_blob(blob, bytes, "trexhip_trainer_create", &wb, [](int W, int H) -> int {
         if (W < 8 || W > 256 || H < 8 || H > 256) {               // the range of trexhip_load_weights
@@ -1731,13 +1800,7 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     });
     if (prc != TREXHIP_OK) return prc;
     const int classes = wb.classes, CH = wb.CH;
-    if (p->max_batch < 1 || p->max_batch > 4096) { set_error("trexhip_trainer_create: max_batch must be 1..4096"); return TREXHIP_E_INVALID; }
-    if (p->precision != 0 && p->precision != 1) { set_error("trexhip_trainer_create: precision must be 0 (fp16 two-piece split convolutions) or 1 (exact fp32 MFMA)"); return TREXHIP_E_INVALID; }
-    if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f) || !(p->eps > 0.f) ||
-        !(p->dropout >= 0.f && p->dropout < 1.f) || !(p->bn_momentum >= 0.f && p->bn_momentum <= 1.f)) {
-        set_error("trexhip_trainer_create: lr > 0, 0 <= beta < 1, eps > 0, 0 <= dropout < 1, 0 <= bn_momentum <= 1 are required");
-        return TREXHIP_E_INVALID;
-    }
+    if (const int rc = check_train_params(p)) return rc;
     if (hipSetDevice(ctx->p.device) != hipSuccess) { set_error("trexhip_trainer_create: hipSetDevice failed"); return TREXHIP_E_DEVICE; }
     Trainer* t = new Trainer();
     t->ctx = ctx; t->classes = classes; t->CH = CH; t->max_n = p->max_batch; t->p = *p;
@@ -1753,7 +1816,7 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     // ---- the three blocks and their kernel instances.  The convolutions' precision is chosen here, once per role
     const bool h2 = p->precision == 0 && !t->any;      // every other size runs the exact-fp32 chain at both precisions
     Layer* L = t->L;
-    // (k_t_bn_stats<16> is never launched: conv1 always leaves its column sums.  It stays instantiated because the compiler lays out the epilogue
+    // (k_t_bn_stats<16> is never launched by this chain: conv1 always leaves its column sums.  It stays instantiated because the compiler lays out the epilogue
     // of k_t_pool_bwd_stats<16>, which shares block_columns<16, 2> with it, in another order without it)
     //      C    CI  S        weight bias   gamma beta   running mean / variance  dz event  slot  masks    BN kernels
     L[0] = {16,  CH, IMG,     T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, KEEP_OFF[0], &k_t_bn_stats<16>, &k_t_bn_pool<16>, &k_t_pool_bwd_stats<16>, &k_t_bn_bwd<16>};
@@ -1832,28 +1895,41 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
 
 void trexhip_trainer_destroy(trexhip_trainer* h) {
     if (!h) return;
+    if (h->a) arch_trainer_destroy(h->a);
     if (h->t) { (void)hipSetDevice(h->t->ctx->p.device); (void)hipStreamSynchronize(h->t->ctx->stream); trainer_free(h->t); }
     delete h;
 }
 
 int trexhip_trainer_set_lr(trexhip_trainer* h, float lr) {
     if (!h || !(lr > 0.f)) { set_error("trexhip_trainer_set_lr: a trainer and lr > 0 are required"); return TREXHIP_E_INVALID; }
-    h->t->p.lr = lr;
+    if (h->a) arch_trainer_set_lr(h->a, lr);
+    else h->t->p.lr = lr;
     return TREXHIP_OK;
 }
 
-int64_t trexhip_trainer_steps(trexhip_trainer* h) { return h ? h->t->step : -1; }
+int64_t trexhip_trainer_steps(trexhip_trainer* h) { return !h ? -1 : h->a ? arch_trainer_steps(h->a) : h->t->step; }
 
 int trexhip_trainer_image_size(trexhip_trainer* h, int32_t* width, int32_t* height) {
     if (!h || !width || !height) { set_error("trexhip_trainer_image_size: null argument"); return TREXHIP_E_INVALID; }
-    *width = h->t->W; *height = h->t->H;
+    if (h->a) arch_trainer_info(h->a, width, height, nullptr, nullptr);
+    else { *width = h->t->W; *height = h->t->H; }
+    return TREXHIP_OK;
+}
+
+int trexhip_trainer_version(trexhip_trainer* h, int32_t* version) {
+    if (!h || !version) { set_error("trexhip_trainer_version: null argument"); return TREXHIP_E_INVALID; }
+    *version = TREXHIP_NET_V118_3;
+    if (h->a) arch_trainer_info(h->a, nullptr, nullptr, version, nullptr);
     return TREXHIP_OK;
 }
 
 // what every batch entry point checks first: the handle, its two pointers, 1 <= n <= max_batch (any_n: no upper bound, the call chunks)
 static int check_batch(const char* who, const trexhip_trainer* h, const void* a, const void* b, int n, bool any_n = false) {
     if (!h || !a || !b) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
-    if (n < 1 || (!any_n && n > h->t->max_n)) { set_error(std::string(who) + (any_n ? ": n must be at least 1" : ": n must be 1..max_batch")); return TREXHIP_E_INVALID; }
+    int32_t max_n = 0;
+    if (h->a) arch_trainer_info(h->a, nullptr, nullptr, nullptr, &max_n);
+    else max_n = h->t->max_n;
+    if (n < 1 || (!any_n && n > max_n)) { set_error(std::string(who) + (any_n ? ": n must be at least 1" : ": n must be 1..max_batch")); return TREXHIP_E_INVALID; }
     return TREXHIP_OK;
 }
 
@@ -1875,10 +1951,15 @@ static int stage_batch(const char* who, const trexhip_trainer* h, const float* i
 int trexhip_train_step_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks, float* loss,
                               int32_t* correct) {
     if (const int rc = check_batch("trexhip_train_step_device", h, d_inputs, d_targets, n)) return rc;
+    if (h->a) return arch_trainer_step(h->a, false, d_inputs, d_targets, n, d_keep_masks, loss, correct);
     return trainer_step(h->t, d_inputs, d_targets, n, d_keep_masks, loss, correct);
 }
 
 int trexhip_train_step(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, const uint8_t* keep_masks, float* loss, int32_t* correct) {
+    if (h && h->a) {
+        if (const int rc = check_batch("trexhip_train_step", h, inputs, targets, n)) return rc;
+        return arch_trainer_step(h->a, true, inputs, targets, n, keep_masks, loss, correct);
+    }
     if (const int rc = stage_batch("trexhip_train_step", h, inputs, targets, n, keep_masks)) return rc;
     Trainer* t = h->t;
     if (const int rc = trainer_step(t, t->x_stage, t->y_stage, n, keep_masks ? t->keep_stage : nullptr, loss, correct)) return rc;
@@ -1888,20 +1969,27 @@ int trexhip_train_step(trexhip_trainer* h, const float* inputs, const int32_t* t
 
 int trexhip_train_eval_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, float* loss, int32_t* correct) {
     if (const int rc = check_batch("trexhip_train_eval_device", h, d_inputs, d_targets, n)) return rc;
+    if (h->a) return arch_trainer_eval(h->a, false, d_inputs, d_targets, n, loss, correct);
     return trainer_eval(h->t, d_inputs, d_targets, n, loss, correct);
 }
 
 int trexhip_train_predict_device(trexhip_trainer* h, const uint8_t* d_crops, int32_t n, float* d_probs) {
     if (const int rc = check_batch("trexhip_train_predict_device", h, d_crops, d_probs, n, true)) return rc;
+    if (h->a) return arch_trainer_predict(h->a, d_crops, n, d_probs);
     return trainer_predict(h->t, d_crops, n, d_probs);
 }
 
 int trexhip_train_eval(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, float* loss, int32_t* correct) {
+    if (h && h->a) {
+        if (const int rc = check_batch("trexhip_train_eval", h, inputs, targets, n)) return rc;
+        return arch_trainer_eval(h->a, true, inputs, targets, n, loss, correct);
+    }
     if (const int rc = stage_batch("trexhip_train_eval", h, inputs, targets, n, nullptr)) return rc;
     return trainer_eval(h->t, h->t->x_stage, h->t->y_stage, n, loss, correct);
 }
 
 int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float* out, size_t count) {
+    if (h && h->a) return arch_trainer_read(h->a, tensor, kind, out, count);
     if (!h || !out || tensor < 0 || tensor >= T_COUNT || kind < 0 || kind > 3) { set_error("trexhip_trainer_read: bad argument"); return TREXHIP_E_INVALID; }
     Trainer* t = h->t;
     if (count != t->cnt[tensor]) { set_error("trexhip_trainer_read: count does not match the tensor"); return TREXHIP_E_INVALID; }
@@ -1917,6 +2005,7 @@ int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float
 
 int trexhip_trainer_export(trexhip_trainer* h, void* blob, size_t capacity, size_t* bytes) {
     if (!h || !blob) { set_error("trexhip_trainer_export: null argument"); return TREXHIP_E_INVALID; }
+    if (h->a) return arch_trainer_export(h->a, blob, capacity, bytes);
     Trainer* t = h->t;
     const size_t need = weight_blob_bytes(t->classes, t->CH, t->W, t->H);
     if (bytes) *bytes = need;

@@ -125,7 +125,8 @@ struct HipVINetwork {
     // early stopping stay with the caller, as they are host logic in the reference too.
     struct Trainer {
         // weights: the same blob as load_weights (the reference starts from the network's current state_dict), at any individual_image_size it
-        // loads; batches and the blob of weights() have the blob's size (trexhip_trainer_image_size)
+        // loads; batches and the blob of weights() have the blob's size (trexhip_trainer_image_size).  The blob's header names the network:
+        // V118_3, v100 or v110 train (version()); v100 and v110 run exact fp32 whatever exact_fp32 says and use their own dropout rates
         // exact_fp32: conv2 / conv3 forward and data gradients on the fp32 matrix cores instead of the fp16 two-piece split arithmetic
         // (trexhip_train_params::precision; same parity bars, 1.6 instead of 1.2 ms per 128-sample step)
         Trainer(HipVINetwork& net, const void* blob, size_t bytes, int max_batch, float learning_rate = 0.001f, uint64_t seed = 0, bool exact_fp32 = false) : _net(net) {
@@ -154,6 +155,7 @@ struct HipVINetwork {
         }
         void set_learning_rate(float lr) { check(trexhip_trainer_set_lr(_t, lr)); }          // ReduceLROnPlateau lives with the caller
         int64_t steps() const { return trexhip_trainer_steps(_t); }
+        int version() const { int32_t v = 0; check(trexhip_trainer_version(_t, &v)); return v; }   // TREXHIP_NET_V118_3, _V100 or _V110
         std::vector<uint8_t> weights() const {                                                // what the reference serialises back (state_dict)
             std::vector<uint8_t> blob(_bytes);                                                // same classes, channels and size as the blob it started from
             size_t got = 0;
