@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 18
+#define TREXHIP_ABI_VERSION 19
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -905,6 +905,51 @@ int trexhip_visual_field_device(trexhip_ctx* ctx, const trexhip_vf_params* vp,
         const trexhip_vf_observer* d_observers, int32_t n_observers,
         double* d_depth, int32_t* d_ids, float* d_points /* float2 */, uint8_t* d_fov, double* d_head_distance,
         int32_t* d_status /* [n_observers] */);
+
+/* ------------------------------------------------------------------------------------------------
+ * Categorisation (ABI 19): TRex's second network, and the reduction of its labels per tracklet, on crops that are in HBM.
+ *
+ * The network is trex_learn_category.py:18-44 (PyTorchModel) in eval mode: x = crop / 127.5 - 1 (:289, :435; a true fp32 division, then an fp32
+ * subtraction), three times [conv 3x3 padding 1 -> BatchNorm2d -> ReLU -> floor 2x2 max-pool] with 16, 64 and 100 channels -- the zero padding is
+ * applied to the NORMALISED image --, the NCHW flatten, fc1 (100) -> ReLU -> fc2 (categories); label = argmax(softmax(logits)) (:441), the first
+ * maximum.  It takes the same individual_image_size crops as the identity network (CategorizeDatastore.cpp:1185-1245), uint8 NHWC [n][H][W][C].
+ * A context holds it BESIDE the identity network: loading, reloading or calling either one leaves the other and its results untouched, and nothing
+ * is allocated for it before trexhip_categorize_load_weights.  Sizes 8..256 each way (square or not), 1 or 3 channels, 1..1024 categories.
+ * The chain is the generic one of the v100..v200 identity networks (first layer and fc1 exact fp32, conv2 / conv3 in the arithmetic mode of
+ * trexhip_set_identity_precision with its range guard, crops walked in chunks; a crop's row does not depend on n or on where it stands); a
+ * category call adds nothing to trexhip_identify_guard_stats or to the identity stages of the profile.
+ *
+ * trexhip_categorize_load_weights  replaces model.load_state_dict(npz['model_state']) (trex_learn_category.py:232-233).  The blob
+ *     (trex_amd/weights.py pack_category_blob; tools/convert_category_weights.py makes it from a checkpoint): 8 x int32 header {magic 'TRXC', 1,
+ *     categories, width, height, channels, 0, 0}, then the float32 tensors in state_dict order.  A blob with a bad size, magic, version or range is
+ *     refused with the field named in trexhip_last_error(), and the loaded category network stays.  An identity blob ('TRXW') is refused here, and
+ *     trexhip_load_weights refuses a category blob, by the magic.
+ * trexhip_categorize_info          the loaded network's categories, channels and size; zeros without weights.  Any pointer may be NULL.
+ * trexhip_categorize_blob_bytes    bytes of the blob for that network; 0 outside the ranges above.  No reference counterpart.
+ * trexhip_categorize_device        replaces Categorize.predict (trex_learn_category.py:398-443) behind py::set_variable("images", ..) +
+ *     py::run(module, "predict") + receive (ui/Categorize.cpp:730-761): d_labels[n] = the category of each crop; d_probs [n][categories] (the softmax
+ *     rows) and d_logits [n][categories] are optional.  Ordered on the context's stream, does not synchronise.
+ * trexhip_categorize               the same from host crops to host labels (includes the copies, synchronises).
+ * n = 0 is a no-op that returns TREXHIP_OK; a call without category weights is TREXHIP_E_INVALID and says so. */
+int trexhip_categorize_load_weights(trexhip_ctx* ctx, const void* blob, size_t bytes);
+int trexhip_categorize_info(trexhip_ctx* ctx, int32_t* categories, int32_t* channels, int32_t* width, int32_t* height);
+size_t trexhip_categorize_blob_bytes(int32_t categories, int32_t channels, int32_t width, int32_t height);
+int trexhip_categorize_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n, int32_t* d_labels, float* d_probs /* or NULL */, float* d_logits /* or NULL */);
+int trexhip_categorize(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, int32_t* labels);
+/* The labels of a tracklet's rows reduced to the tracklet's label: DataStore::label_averaged (CategorizeDatastore.cpp:513-594, the counting
+ * :555-585) and the shares of a sample (CategorizeInterface.cpp:212-247), for every tracklet in one call.
+ *   d_labels[n], d_tracklet[n]   a row's label and its tracklet, 0 <= tracklet < n_tracklets; rows of a tracklet may stand anywhere
+ *   d_counts[T][categories]      uint32: rows of the tracklet with that label.  A negative label (none) is skipped; a label >= categories is
+ *                                skipped and counted in *skipped (the reference warns and goes on)
+ *   d_rows[T]                    uint32: every row handed in for the tracklet, skipped ones included
+ *   d_label[T]                   the first maximum of the counts (std::max_element), -1 when that maximum is 0
+ *   d_share[T][categories]       optional: counts / float(rows), one correctly rounded fp32 division; 0 for a tracklet without rows
+ *   skipped                      HOST, optional: rows skipped for a label >= categories
+ * Integer adds only: the result does not depend on the order of the rows or on the grid.  A tracklet id outside [0, n_tracklets) is
+ * TREXHIP_E_INVALID and nothing is written: a checked pass runs first.  1 <= n_tracklets <= 2^24, 1 <= categories <= 1024; n = 0 returns
+ * TREXHIP_OK and writes nothing but *skipped = 0.  Needs no category weights.  Ordered on the context's stream; the call synchronises. */
+int trexhip_tracklet_labels_device(trexhip_ctx* ctx, const int32_t* d_labels, const int32_t* d_tracklet, int32_t n, int32_t n_tracklets, int32_t categories,
+                                   uint32_t* d_counts, uint32_t* d_rows, int32_t* d_label, float* d_share /* or NULL */, uint32_t* skipped /* host, or NULL */);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
 
 There is NO CPU fallback: if the HIP library is missing or a call fails, this raises.
 """
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -192,6 +193,9 @@ class VisualFieldResult:
             setattr(self, k, None)
 
 
+TrackletLabels = collections.namedtuple("TrackletLabels", "counts rows label share skipped")
+
+
 SYMBOLS = [
     "trexhip_abi_version", "trexhip_network_channels", "trexhip_network_image_size", "trexhip_network_version", "trexhip_network_blob_bytes", "trexhip_identify_chunk_crops", "trexhip_comm_unique_id", "trexhip_comm_create", "trexhip_comm_destroy", "trexhip_comm_rank", "trexhip_comm_world", "trexhip_comm_gather_device", "trexhip_comm_gather_device_on", "trexhip_comm_count_ranks", "trexhip_last_error", "trexhip_default_params", "trexhip_create", "trexhip_destroy",
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
@@ -205,6 +209,8 @@ SYMBOLS = [
     "trexhip_load_frames_v6_device", "trexhip_lzo1x_decompress", "trexhip_pv_read_frames",
     "trexhip_default_prefilter_params", "trexhip_prefilter_device",
     "trexhip_default_vf_params", "trexhip_visual_field_device",
+    "trexhip_categorize_load_weights", "trexhip_categorize_info", "trexhip_categorize_blob_bytes", "trexhip_categorize_device", "trexhip_categorize",
+    "trexhip_tracklet_labels_device",
 ]
 
 
@@ -322,6 +328,14 @@ def lib():
         L.trexhip_default_vf_params.restype = None
         L.trexhip_visual_field_device.argtypes = [C.c_void_p, C.POINTER(VfParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.trexhip_categorize_load_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.trexhip_categorize_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.trexhip_categorize_blob_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.trexhip_categorize_blob_bytes.restype = C.c_size_t
+        L.trexhip_categorize_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.trexhip_categorize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.trexhip_tracklet_labels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(C.c_uint32)]
         _LIB = L
     return _LIB
 
@@ -749,6 +763,65 @@ class Segmenter:
         _check(lib().trexhip_class_averages_device(self._h, C.c_void_p(d_probs_ptr or 0), n, classes, C.c_void_p(d_ids_ptr or 0), n_ids,
                                                    ptr(samples), ptr(values), ptr(max_index), ptr(max_p)))
         return ClassAverages(samples, values, max_index, max_p)
+
+    # ---- categorisation: the category network beside the identity network, and the tracklet vote ----
+    def load_category_weights(self, blob):
+        """a category blob (weights.pack_category_blob) into the context's second slot; the identity network is not touched"""
+        _check(lib().trexhip_categorize_load_weights(self._h, blob, len(blob)))
+
+    def category_info(self):
+        """(categories, channels, width, height) of the loaded category network; zeros without one"""
+        v = [C.c_int32(0) for _ in range(4)]
+        _check(lib().trexhip_categorize_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def categorize_device(self, d_crops_ptr, n, d_labels_ptr, d_probs_ptr=None, d_logits_ptr=None):
+        """uint8 crops [n][H][W][C] in HBM -> int32 labels [n] (and, where asked, float32 softmax rows / logits [n][categories]); no synchronisation"""
+        _check(lib().trexhip_categorize_device(self._h, C.c_void_p(d_crops_ptr or 0), n, C.c_void_p(d_labels_ptr or 0),
+                                               C.c_void_p(d_probs_ptr) if d_probs_ptr else None, C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
+
+    def categorize(self, crops):
+        """crops: uint8 ndarray (n,H,W,C) on the host, the category network's size and channels -> int32 (n,) labels (host route)"""
+        crops = np.ascontiguousarray(crops, np.uint8)
+        cats, ch, w, h = self.category_info()
+        if cats and (crops.ndim != 4 or tuple(crops.shape[1:]) != (h, w, ch)):      # (without weights the library reports that itself)
+            raise ValueError(f"crops must have shape (n, {h}, {w}, {ch}) for the loaded category network, got {crops.shape}")
+        n = crops.shape[0]
+        out = np.empty(n, np.int32)
+        _check(lib().trexhip_categorize(self._h, crops.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def tracklet_labels_device(self, d_labels_ptr, d_tracklet_ptr, n, n_tracklets, categories, d_counts_ptr, d_rows_ptr, d_label_ptr, d_share_ptr=None):
+        """DataStore::label_averaged for every tracklet on rows in HBM (trexhip_tracklet_labels_device; synchronises) -> rows skipped for a label >= categories"""
+        skipped = C.c_uint32(0)
+        _check(lib().trexhip_tracklet_labels_device(self._h, C.c_void_p(d_labels_ptr or 0), C.c_void_p(d_tracklet_ptr or 0), n, n_tracklets, categories,
+                                                    C.c_void_p(d_counts_ptr or 0), C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_label_ptr or 0),
+                                                    C.c_void_p(d_share_ptr) if d_share_ptr else None, C.byref(skipped)))
+        return int(skipped.value)
+
+    def tracklet_labels(self, labels, tracklet, n_tracklets, categories, share=True):
+        """the same on host arrays (int32 labels and tracklet ids per row): uploads, votes, fetches -> TrackletLabels(counts, rows, label, share, skipped)"""
+        lb, tr = np.ascontiguousarray(labels, np.int32).reshape(-1), np.ascontiguousarray(tracklet, np.int32).reshape(-1)
+        if lb.shape != tr.shape:
+            raise ValueError(f"labels and tracklet must have one entry per row, got {lb.shape} and {tr.shape}")
+        n, T, Cn = len(lb), int(n_tracklets), int(categories)
+        sizes = [max(n, 1) * 4, max(n, 1) * 4, max(T * Cn, 1) * 4, max(T, 1) * 4, max(T, 1) * 4, max(T * Cn, 1) * 4]
+        ptrs = []
+        try:
+            for b in sizes:
+                ptrs.append(self.device_alloc(b))
+            if n:
+                self.copy_to_device(ptrs[0], lb)
+                self.copy_to_device(ptrs[1], tr)
+            skipped = self.tracklet_labels_device(ptrs[0], ptrs[1], n, T, Cn, ptrs[2], ptrs[3], ptrs[4], ptrs[5] if share else None)
+            if n == 0:
+                return TrackletLabels(np.zeros((T, Cn), np.uint32), np.zeros(T, np.uint32), np.full(T, -1, np.int32),
+                                      np.zeros((T, Cn), np.float32) if share else None, 0)
+            return TrackletLabels(self.copy_to_host(ptrs[2], (T, Cn), np.uint32), self.copy_to_host(ptrs[3], (T,), np.uint32),
+                                  self.copy_to_host(ptrs[4], (T,), np.int32), self.copy_to_host(ptrs[5], (T, Cn), np.float32) if share else None, skipped)
+        finally:
+            for d in ptrs:
+                self.device_free(d)
 
     def default_vf_params(self, **kw):
         """trexhip_default_vf_params: max_d from the context's frame size, max_distance 5; keywords override single fields"""

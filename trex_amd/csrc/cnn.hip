@@ -1666,7 +1666,7 @@ static bool capture_chain(trexhip_ctx* ctx, Net* net, Net::GraphEntry* cand, con
 
 static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
     Net* net = static_cast<Net*>(ctx->net);
-    if (net->arch) return arch_forward(ctx, d_crops, n, d_probs, d_logits);      // chunked, never captured
+    if (net->arch) return arch_forward(ctx, *net, d_crops, n, d_probs, d_logits);      // chunked, never captured
     static const bool enabled = [] { const char* e = std::getenv("TREXHIP_GRAPHS"); return !(e && std::atoi(e) == 0); }();
     // not while profiling (the stage events are host-side bookkeeping), not before the first plain call (function attributes are set there)
     if (!enabled || !net->graphs_ok || n > GRAPH_MAX_CROPS || ctx->profiling || !ctx->attr_cnn) return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
@@ -1828,5 +1828,8 @@ int trexhip_network_image_size(trexhip_ctx* ctx, int32_t* width, int32_t* height
 }  // extern "C"
 
 namespace trexhip {
-void net_free(trexhip_ctx* ctx) { free_net(static_cast<Net*>(ctx->net)); ctx->net = nullptr; }
+void net_free(trexhip_ctx* ctx) {
+    free_net(static_cast<Net*>(ctx->net)); ctx->net = nullptr;
+    free_net(static_cast<Net*>(ctx->cat)); ctx->cat = nullptr;
+}
 }

@@ -10,6 +10,10 @@
 //   k_gap                 global average pool (v200), summed in raster order
 //   k_arch_fc1            fc1 as an exact fp32 GEMM on the matrix cores, K split over the 4 waves of a workgroup and summed in wave order
 //   k_arch_head           BatchNorm1d or none + ReLU + fc2 + softmax, one wave per crop, the expressions of k_head (cnn.hip)
+//   k_cat_label           the category network only: label = index of the first maximum of a crop's logits, one wave per crop, behind the head
+//
+// The category network (trex_learn_category.py:18-44; category_spec, cnn_arch_plan.h) runs the same chain from the context's second slot
+// (ctx->cat): its first layer is the NORM instance of k_arch_conv1, which stages x / 127.5 - 1 instead of x, and k_cat_label follows its head.
 //
 // The epilogue of both convolution kernels: relu((max_window(conv) * out_scale + bias[co]) * s[co] + t[co]) -- the affine BEHIND the pool, which
 // v110 needs (its BatchNorm follows the max-pool and its scale may be negative); v119 / v200 fold their BatchNorm into weights and bias
@@ -29,7 +33,12 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // One thread per 2 x 2 window of conv pixels, 16 x 16 windows per workgroup.  LDS: (CH * T * T * 16 + CH * PW * PW) * 4 bytes, PW = 32 + T - 1
 // (3 channels, 5 taps: 4800 + 15552 = 20352 B); 64 accumulators per thread
-template <int CH, int T>
+// NORM (the category network, trex_learn_category.py:289, :435 "torch.tensor(images, float32) / 127.5 - 1"): a pixel inside the crop is staged as
+//     __fsub_rn(__fdiv_rn((float)byte, 127.5f), 1.0f)      -- a true fp32 division, then an fp32 subtraction, each rounded on its own --
+// which is what torch's CPU and what numpy give for all 256 bytes (a multiply by the rounded reciprocal differs at 111 of them, a fused multiply-
+// subtract at 205: tests/test_category_ref.py); a pixel outside it as 0, because the reference pads the NORMALISED image with zeros.  The offset
+// can therefore not live in the bias.  The identity instances (NORM = false) compile to what they were: the mode is a template parameter.
+template <int CH, int T, bool NORM = false>
 __global__ __launch_bounds__(256) void k_arch_conv1(const uint8_t* __restrict__ crops /*[N][H][W][CH]*/, const float* __restrict__ w /*[CO/16][CH][T*T][16]*/,
                                                     const float* __restrict__ bias, const float* __restrict__ sv, const float* __restrict__ tv,
                                                     float* __restrict__ out /*[N][Ho][Wo][CO]*/, const int CO, const int W, const int H, const int pool,
@@ -47,7 +56,10 @@ __global__ __launch_bounds__(256) void k_arch_conv1(const uint8_t* __restrict__ 
     for (int i = threadIdx.x; i < PW * PW * CH; i += 256) {
         const int c = i % CH, p = i / CH, py = p / PW, px = p - py * PW;
         const int iy = y0 + py, ix = x0 + px;
-        img[c * PW * PW + p] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? (float)src[((size_t)iy * W + ix) * CH + c] : 0.f;   // predict_numpy: no scaling
+        const bool inside = iy >= 0 && iy < H && ix >= 0 && ix < W;
+        const size_t at = ((size_t)iy * W + ix) * CH + c;
+        if constexpr (NORM) img[c * PW * PW + p] = inside ? __fsub_rn(__fdiv_rn((float)src[at], 127.5f), 1.0f) : 0.f;      // zero padding of the normalised image
+        else img[c * PW * PW + p] = inside ? (float)src[at] : 0.f;                                                          // predict_numpy: no scaling
     }
     __syncthreads();
     const int wy = threadIdx.x / C1, wx = threadIdx.x % C1;
@@ -435,6 +447,28 @@ __global__ __launch_bounds__(256) void k_arch_head(const float* __restrict__ fc1
         }
 }
 
+// the category network's label (trex_learn_category.py:441, softmax(..).argmax(dim=1)): the index of the FIRST maximum of the crop's logits -- the
+// softmax is monotonic, and its row is the head's.  One wave per crop: a lane keeps the first maximum of its columns lane, lane + 64, ..., the
+// wave keeps the larger value and, between equal ones, the lower index.  Reads 4 C bytes per crop, writes 4.
+__global__ __launch_bounds__(256) void k_cat_label(const float* __restrict__ logits /*[n][C]*/, int32_t* __restrict__ labels, const int n, const int C) {
+    const int lane = threadIdx.x & 63, crop = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (crop >= n) return;
+    const float* x = logits + (size_t)crop * C;
+    float best = -INFINITY;
+    int at = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const float v = x[c];
+        if (at == 0x7fffffff || v > best) { best = v; at = c; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const float ob = __shfl_xor(best, d);
+        const int oa = __shfl_xor(at, d);
+        if (oa != 0x7fffffff && (at == 0x7fffffff || ob > best || (ob == best && oa < at))) { best = ob; at = oa; }
+    }
+    if (lane == 0) labels[crop] = at;
+}
+
 // the plan of a chunk's guarded re-run: the protocol of k_guard_plan (cnn.hip) -- lists the flagged crops, clears their flags and the range word --
 // and adds what it planned to the call's two statistics words
 __global__ __launch_bounds__(1024) void k_arch_guard_plan(uint32_t* __restrict__ overflow, uint8_t* __restrict__ flags, const int n, uint32_t* __restrict__ plan,
@@ -472,6 +506,8 @@ template <int COB>
 ArchConvSet arch_set() { return {{arch_kern<COB, 2, 1>(), arch_kern<COB, 0, 6>(), arch_kern<COB, 0, 3>(), arch_kern<COB, 1, 3>()}}; }
 const ArchConvSet ARCH_CONV[3] = {arch_set<32>(), arch_set<64>(), arch_set<128>()};      // COB 32, 64, 128
 const ByChannels ARCH_CONV1_T3{Kern(k_arch_conv1<1, 3>, 256), Kern(k_arch_conv1<3, 3>, 256)};
+const ByChannels ARCH_CONV1_T3N{Kern(k_arch_conv1<1, 3, true>, 256), Kern(k_arch_conv1<3, 3, true>, 256)};      // the category network's
+const Kern K_CAT_LABEL(k_cat_label, 256);
 const ByChannels ARCH_CONV1_T5{Kern(k_arch_conv1<1, 5>, 256), Kern(k_arch_conv1<3, 5>, 256)};
 const Kern K_POOL3(k_pool3, 256);
 const Kern K_GAP(k_gap, 256);
@@ -502,10 +538,48 @@ void launch_conv(hipStream_t s, const Net& net, const ArchNet& a, const int i, c
 
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)      // a chain of allocations stops at its first failure
 template <class T, class V>
-static int up(Net* net, T** dst, const std::vector<V>& v) {
-    const int rc = net->weights.device_bytes(dst, v.size() * sizeof(V), "trexhip_load_weights");
+static int up(Net* net, T** dst, const std::vector<V>& v, const char* who) {
+    const int rc = net->weights.device_bytes(dst, v.size() * sizeof(V), who);
     if (rc != TREXHIP_OK) return rc;
     TH_CHECK_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
+    return TREXHIP_OK;
+}
+
+// pack -> upload of a parsed blob into a new Net; *out stays null on a failure
+static int arch_build(const ArchBlob& wb, const ArchPlan& plan, const char* who, Net** out) {
+    *out = nullptr;
+    Net* net = new Net();
+    net->classes = wb.classes; net->W = wb.W; net->H = wb.H; net->CH = wb.CH;
+    ArchNet* a = net->arch = new ArchNet();
+    a->plan = plan;
+    const ArchSpec& sp = *a->plan.spec;
+    const bool fold = sp.bn2d && !sp.bn_behind_pool;
+    int rc = TREXHIP_OK;
+    for (int i = 0; i < sp.n_conv && rc == TREXHIP_OK; ++i) {
+        const ArchLayerPlan& l = a->plan.L[i];
+        ArchLayerDev& d = a->L[i];
+        const int ci_real = i == 0 ? wb.CH : sp.conv[i - 1].CO;
+        const ArchConvImage im = i == 0 ? pack_arch_conv1(wb.conv[i], sp.conv[i].CO, wb.CH, l.taps, l.CO, fold)
+                                        : pack_arch_conv(wb.conv[i], sp.conv[i].CO, ci_real, l.taps, l.CO, l.CI, l.COB, fold);
+        TRY(up(net, &d.w, im.w, who)); TRY(up(net, &d.bias, im.bias, who)); TRY(up(net, &d.s, im.s, who)); TRY(up(net, &d.t, im.t, who));
+        if (i > 0) {
+            TRY(up(net, &d.ws, pack_arch_bf16x3(im.w, l.COB), who));
+            const ScaledImage h = pack_arch_f16x2(im.w, l.COB);
+            d.invh = h.inv;
+            TRY(up(net, &d.wh, h.v, who));
+        }
+    }
+    const int P = sp.gap ? 1 : a->plan.Hf * a->plan.Wf;
+    const Folded f1 = pack_arch_fc1(wb.fc1w, wb.fc1b, sp.hidden, a->plan.NH, sp.conv[sp.n_conv - 1].CO, a->plan.Cf, P);
+    TRY(up(net, &a->wf1, f1.w, who)); TRY(up(net, &a->bf1, f1.b, who));
+    const Folded bn = pack_arch_bn1d(wb.bn1d, sp.hidden, a->plan.NH);
+    TRY(up(net, &a->hs, bn.w, who)); TRY(up(net, &a->ht, bn.b, who));
+    TRY(up(net, &a->wf2t, pack_arch_fc2(wb.fc2w, wb.classes, sp.hidden), who));
+    TRY(up(net, &a->bf2, std::vector<float>(wb.fc2b, wb.fc2b + wb.classes), who));
+    TRY(net->weights.device_bytes(&net->d_ovf, ARCH_OVF_WORDS * 4, who));
+    if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, ARCH_OVF_WORDS * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
+    if (rc != TREXHIP_OK) { free_net(net); return rc; }
+    *out = net;
     return TREXHIP_OK;
 }
 
@@ -516,42 +590,30 @@ int arch_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
     free_net(static_cast<Net*>(ctx->net));
     ctx->net = nullptr;
-    Net* net = new Net();
-    net->classes = wb.classes; net->W = wb.W; net->H = wb.H; net->CH = wb.CH;
-    ArchNet* a = net->arch = new ArchNet();
-    a->plan = arch_plan(wb.id, wb.W, wb.H, wb.CH);
-    const ArchSpec& sp = *a->plan.spec;
-    const bool fold = sp.bn2d && !sp.bn_behind_pool;
-    int rc = TREXHIP_OK;
-    for (int i = 0; i < sp.n_conv && rc == TREXHIP_OK; ++i) {
-        const ArchLayerPlan& l = a->plan.L[i];
-        ArchLayerDev& d = a->L[i];
-        const int ci_real = i == 0 ? wb.CH : sp.conv[i - 1].CO;
-        const ArchConvImage im = i == 0 ? pack_arch_conv1(wb.conv[i], sp.conv[i].CO, wb.CH, l.taps, l.CO, fold)
-                                        : pack_arch_conv(wb.conv[i], sp.conv[i].CO, ci_real, l.taps, l.CO, l.CI, l.COB, fold);
-        TRY(up(net, &d.w, im.w)); TRY(up(net, &d.bias, im.bias)); TRY(up(net, &d.s, im.s)); TRY(up(net, &d.t, im.t));
-        if (i > 0) {
-            TRY(up(net, &d.ws, pack_arch_bf16x3(im.w, l.COB)));
-            const ScaledImage h = pack_arch_f16x2(im.w, l.COB);
-            d.invh = h.inv;
-            TRY(up(net, &d.wh, h.v));
-        }
-    }
-    const int P = sp.gap ? 1 : a->plan.Hf * a->plan.Wf;
-    const Folded f1 = pack_arch_fc1(wb.fc1w, wb.fc1b, sp.hidden, a->plan.NH, sp.conv[sp.n_conv - 1].CO, a->plan.Cf, P);
-    TRY(up(net, &a->wf1, f1.w)); TRY(up(net, &a->bf1, f1.b));
-    const Folded bn = pack_arch_bn1d(wb.bn1d, sp.hidden, a->plan.NH);
-    TRY(up(net, &a->hs, bn.w)); TRY(up(net, &a->ht, bn.b));
-    TRY(up(net, &a->wf2t, pack_arch_fc2(wb.fc2w, wb.classes, sp.hidden)));
-    TRY(up(net, &a->bf2, std::vector<float>(wb.fc2b, wb.fc2b + wb.classes)));
-    TRY(net->weights.device_bytes(&net->d_ovf, ARCH_OVF_WORDS * 4, "trexhip_load_weights"));
-    if (rc == TREXHIP_OK && hipMemset(net->d_ovf, 0, ARCH_OVF_WORDS * 4) != hipSuccess) rc = TREXHIP_E_DEVICE;
-    if (rc != TREXHIP_OK) { free_net(net); return rc; }
+    Net* net;
+    const int rc = arch_build(wb, arch_plan(wb.id, wb.W, wb.H, wb.CH), "trexhip_load_weights", &net);
+    if (rc != TREXHIP_OK) return rc;
     ctx->net = net;
     return TREXHIP_OK;
 }
 
-int arch_ensure_act(trexhip_ctx* ctx, Net* net, int n) {
+// the category network: parsed and built BEFORE the loaded one is let go, so a refused blob leaves it in place; the identity slot is not touched
+int category_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
+    const char* who = "trexhip_categorize_load_weights";
+    ArchBlob wb;
+    const int prc = parse_category_blob(blob, bytes, who, &wb);
+    if (prc != TREXHIP_OK) return prc;
+    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    Net* net;
+    const int rc = arch_build(wb, category_plan(wb.W, wb.H, wb.CH), who, &net);
+    if (rc != TREXHIP_OK) return rc;
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));        // an earlier call may still run on the network that is replaced
+    free_net(static_cast<Net*>(ctx->cat));
+    ctx->cat = net;
+    return TREXHIP_OK;
+}
+
+int arch_ensure_act(trexhip_ctx* ctx, Net* net, int n, const char* who) {
     if (n <= net->max_crops) return TREXHIP_OK;
     ArchNet& a = *net->arch;
     // (no captured chains to drop: these chains are not captured)
@@ -560,7 +622,6 @@ int arch_ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     net->h_probs = nullptr;
     net->max_crops = 0;
     Mem& B = net->batch;
-    const char* who = "trexhip_identify_device";
     const size_t N = n, M = std::min(n, a.plan.chunk);
     int rc = B.device_bytes(&net->d_ovfc, M, who);
     for (int i = 0; i < a.plan.n_conv; ++i) {
@@ -575,6 +636,8 @@ int arch_ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     TRY(B.device_bytes(&net->logits, N * net->classes * 4, who));
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
     TRY(B.pinned(&net->h_probs, N * net->classes, who));
+    a.labels = nullptr; a.h_labels = nullptr;
+    if (a.plan.spec->id == ARCH_ID_CATEGORY) { TRY(B.device_bytes(&a.labels, N * 4, who)); TRY(B.pinned(&a.h_labels, N, who)); }
     if (rc != TREXHIP_OK) return rc;
     TH_CHECK_HIP(hipMemsetAsync(net->d_ovfc, 0, M, ctx->stream));
     net->max_crops = n;
@@ -582,9 +645,9 @@ int arch_ensure_act(trexhip_ctx* ctx, Net* net, int n) {
 }
 #undef TRY
 
-int arch_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
-    const Net& net = *static_cast<Net*>(ctx->net);
+int arch_forward(trexhip_ctx* ctx, const Net& net, const uint8_t* d_crops, int n, float* d_probs, float* d_logits, int32_t* d_labels) {
     const ArchNet& a = *net.arch;
+    const bool cat = a.plan.spec->id == ARCH_ID_CATEGORY;      // normalised first layer, a label per crop, no share in the identity stages' times
     const ArchPlan& p = a.plan;
     if (!ctx->attr_cnn) {
         for (const LdsAttr& at : lds_attrs()) TH_CHECK_HIP(hipFuncSetAttribute(at.fn, hipFuncAttributeMaxDynamicSharedMemorySize, at.bytes));
@@ -594,16 +657,16 @@ int arch_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs
     const int mode = ctx->cnn_mode;
     const bool h16 = mode == TREXHIP_CNN_FP16X3;
     const size_t crop_bytes = (size_t)net.W * net.H * net.CH;
-    stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
+    if (!cat) stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
     if (h16) TH_CHECK_HIP(hipMemsetAsync(net.ovf(ARCH_STAT_RERUN), 0, 8, s));
     const ArchLayerPlan& l0 = p.L[0];
     const ArchLayerDev& last = a.L[p.n_conv - 1];
     for (int c0 = 0; c0 < n; c0 += p.chunk) {
         const int m = std::min(p.chunk, n - c0);
-        (l0.taps == 3 ? ARCH_CONV1_T3 : ARCH_CONV1_T5)[net.CH](s, dim3(m * l0.tl.tiles, l0.co_blocks), d_crops + (size_t)c0 * crop_bytes, a.L[0].w, a.L[0].bias,
+        (cat ? ARCH_CONV1_T3N : l0.taps == 3 ? ARCH_CONV1_T3 : ARCH_CONV1_T5)[net.CH](s, dim3(m * l0.tl.tiles, l0.co_blocks), d_crops + (size_t)c0 * crop_bytes, a.L[0].w, a.L[0].bias,
                                                               a.L[0].s, a.L[0].t, a.L[0].act, l0.CO, net.W, net.H, l0.pool == 2 ? 1 : 0, l0.tl.tx_n, l0.tl.tiles);
         for (int i = 1; i < p.n_conv; ++i) {       // (profiling: conv2 and conv3 have stages of their own, as in the V118_3 chains)
-            const int stage = i == 1 ? TREXHIP_STAGE_CONV2 : i == 2 ? TREXHIP_STAGE_CONV3 : -1;
+            const int stage = cat ? -1 : i == 1 ? TREXHIP_STAGE_CONV2 : i == 2 ? TREXHIP_STAGE_CONV3 : -1;
             if (stage >= 0) stage_begin(ctx, stage);
             launch_conv(s, net, a, i, mode, m, nullptr, ctx->n_cus);
             if (stage >= 0) stage_end(ctx, stage);
@@ -621,8 +684,9 @@ int arch_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs
         K_ARCH_FC1(s, dim3(cdiv(m, 32), p.NH / 32), feat, a.wf1, a.bf1, a.fc1, m, p.K, p.NH);
         K_ARCH_HEAD(s, cdiv(m, 4), a.fc1, a.hs, a.ht, a.wf2t, a.bf2, d_probs + (size_t)c0 * net.classes, d_logits ? d_logits + (size_t)c0 * net.classes : nullptr, m,
                     net.classes, p.NH, p.spec->hidden);
+        if (d_labels) K_CAT_LABEL(s, cdiv(m, 4), d_logits + (size_t)c0 * net.classes, d_labels + c0, m, net.classes);       // (the caller hands logits with labels)
     }
-    stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
+    if (!cat) stage_end(ctx, TREXHIP_STAGE_CNN_ALL);
     TH_CHECK_HIP(hipGetLastError());
     return TREXHIP_OK;
 }

@@ -36,6 +36,14 @@ inline const ArchSpec* arch_spec(const int id) {
     };
     return id >= TREXHIP_NET_V100 && id <= TREXHIP_NET_V200 ? &S[id - 1] : nullptr;
 }
+// The category network (trex_learn_category.py:18-44, PyTorchModel): not an identity network -- it has no TREXHIP_NET_* id, its blob has a magic of
+// its own and arch_spec() does not know it.  Three convolutions of 3 taps, each BatchNorm2d -> ReLU -> floor 2x2 max-pool (the BatchNorm in front of
+// the pool: folded into weights and bias), the NCHW flatten, fc1 (100) -> ReLU -> fc2; no BatchNorm1d.  Its first layer reads normalised bytes.
+static constexpr int ARCH_ID_CATEGORY = -1;
+inline const ArchSpec* category_spec() {
+    static const ArchSpec S = {ARCH_ID_CATEGORY, "category", 8, 3, {{16, 3, 2}, {64, 3, 2}, {100, 3, 2}}, true, false, false, 100, false};
+    return &S;
+}
 inline const char* arch_name(const int id) { return id == TREXHIP_NET_V118_3 ? "v118_3" : arch_spec(id) ? arch_spec(id)->name : "?"; }
 
 // channels as the kernels see them: 16, or a multiple of 32 (v100 / v110 conv3: 100 -> 128 with zero weights, s = t = 0 behind them)
@@ -76,9 +84,8 @@ struct ArchPlan {
 
 inline int arch_min_size(const int id) { const ArchSpec* s = arch_spec(id); return s ? s->min_size : 8; }
 
-inline ArchPlan arch_plan(const int id, const int W, const int H, const int CH) {
+inline ArchPlan arch_plan_of(const ArchSpec* s, const int W, const int H, const int CH) {
     ArchPlan p{};
-    const ArchSpec* s = arch_spec(id);
     p.spec = s;
     p.n_conv = s->n_conv;
     int h = H, w = W, ci = CH;
@@ -112,5 +119,7 @@ inline ArchPlan arch_plan(const int id, const int W, const int H, const int CH) 
     p.chunk = fit < 1 ? 1 : fit > (size_t)ARCH_CHUNK_MAX ? ARCH_CHUNK_MAX : (int)fit;
     return p;
 }
+inline ArchPlan arch_plan(const int id, const int W, const int H, const int CH) { return arch_plan_of(arch_spec(id), W, H, CH); }
+inline ArchPlan category_plan(const int W, const int H, const int CH) { return arch_plan_of(category_spec(), W, H, CH); }
 
 }  // namespace trexhip

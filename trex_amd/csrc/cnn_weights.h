@@ -74,6 +74,15 @@ struct ArchBlob {
 };
 int parse_arch_blob(const void* blob, size_t bytes, const char* who, ArchBlob* view);
 
+// ---- the category network (trex_learn_category.py:18-44; the layer table: category_spec, cnn_arch_plan.h) ----
+// Its blob (trex_amd/weights.py pack_category_blob): 8 x int32 header {magic 'TRXC', version 1, categories, W, H, CH, 0, 0}, then the float32 tensors
+// in PyTorchModel's state_dict order: conv1.{weight,bias}, conv2.*, conv3.*, batch_norm1.{weight,bias,running_mean,running_var}, batch_norm2.*,
+// batch_norm3.*, fc1.*, fc2.*.  The magic differs from an identity blob's, so each loader refuses the other's.
+size_t category_blob_bytes(int categories, int CH, int W, int H);       // 0 outside 1..1024 categories, 1 or 3 channels, 8..256 each way
+// view->id = ARCH_ID_CATEGORY, view->classes = categories, bn1d null.  A refusal names the field (size, magic, version, width, height, channels,
+// categories) and `who`
+int parse_category_blob(const void* blob, size_t bytes, const char* who, ArchBlob* view);
+
 // One convolution for k_arch_conv: weight [CO][CI][T][T] -> fp32 [CO_pad/COB][CI_pad/16][T*T][16][COB] (zero where padded), and the epilogue's
 // per-channel vectors relu((max_window(conv) * out_scale + bias) * s + t):  fold = true (v119, v200: BatchNorm in front of the pool) folds the
 // BatchNorm into weights and bias in double, s = 1, t = 0;  fold = false keeps bias = the convolution's and s = gamma / sqrt(var + eps),

@@ -122,6 +122,60 @@ int parse_arch_blob(const void* blob, size_t bytes, const char* who, ArchBlob* v
     return TREXHIP_OK;
 }
 
+// ---- the category network's blob ----
+static constexpr int32_t CAT_MAGIC = 0x43585254;      // 'TRXC'
+template <class F>
+static void category_walk(int categories, int CH, int W, int H, ArchBlob* v, F next) {
+    const ArchSpec& s = *category_spec();
+    int ci = CH;
+    for (int i = 0; i < s.n_conv; ++i) {
+        const ArchConv& c = s.conv[i];
+        const float* p = next((size_t)c.CO * ci * c.taps * c.taps);
+        if (v) v->conv[i][0] = p;
+        p = next(c.CO);
+        if (v) v->conv[i][1] = p;
+        ci = c.CO;
+    }
+    for (int i = 0; i < s.n_conv; ++i)
+        for (int k = 2; k < 6; ++k) { const float* p = next(s.conv[i].CO); if (v) v->conv[i][k] = p; }
+    const float* p = next((size_t)s.hidden * ci * (H / 8) * (W / 8));
+    if (v) v->fc1w = p;
+    p = next(s.hidden);
+    if (v) v->fc1b = p;
+    p = next((size_t)categories * s.hidden);
+    if (v) v->fc2w = p;
+    p = next(categories);
+    if (v) v->fc2b = p;
+}
+
+size_t category_blob_bytes(int categories, int CH, int W, int H) {
+    if ((CH != 1 && CH != 3) || W < 8 || W > 256 || H < 8 || H > 256 || categories < 1 || categories > 1024) return 0;
+    size_t n = 0;
+    category_walk(categories, CH, W, H, nullptr, [&](size_t cnt) -> const float* { n += cnt; return nullptr; });
+    return 32 + 4 * n;
+}
+
+int parse_category_blob(const void* blob, size_t bytes, const char* who, ArchBlob* view) {
+    const std::string pre = std::string(who) + ": ";
+    if (bytes < 32) { set_error(pre + "size: " + std::to_string(bytes) + " bytes are less than the header"); return TREXHIP_E_INVALID; }
+    int32_t hdr[8];
+    std::memcpy(hdr, blob, 32);
+    if (hdr[0] != CAT_MAGIC) { set_error(pre + "magic: not a category blob ('TRXC')" + (hdr[0] == BLOB_MAGIC ? "; this is an identity blob ('TRXW', trexhip_load_weights)" : "")); return TREXHIP_E_INVALID; }
+    if (hdr[1] != 1) { set_error(pre + "version: " + std::to_string(hdr[1]) + ", only 1 is known"); return TREXHIP_E_INVALID; }
+    const int categories = hdr[2], W = hdr[3], H = hdr[4], CH = hdr[5];
+    if (W < 8 || W > 256) { set_error(pre + "width: " + std::to_string(W) + " is outside 8..256"); return TREXHIP_E_UNSUPPORTED; }
+    if (H < 8 || H > 256) { set_error(pre + "height: " + std::to_string(H) + " is outside 8..256"); return TREXHIP_E_UNSUPPORTED; }
+    if (CH != 1 && CH != 3) { set_error(pre + "channels: " + std::to_string(CH) + ", must be 1 or 3"); return TREXHIP_E_UNSUPPORTED; }
+    if (categories < 1 || categories > 1024) { set_error(pre + "categories: " + std::to_string(categories) + " is outside 1..1024"); return TREXHIP_E_INVALID; }
+    const size_t want = category_blob_bytes(categories, CH, W, H);
+    if (bytes != want) { set_error(pre + "size: " + std::to_string(bytes) + " bytes, the header asks for " + std::to_string(want)); return TREXHIP_E_INVALID; }
+    *view = ArchBlob{};
+    view->id = ARCH_ID_CATEGORY; view->classes = categories; view->W = W; view->H = H; view->CH = CH;
+    const float* p = reinterpret_cast<const float*>(static_cast<const char*>(blob) + 32);
+    category_walk(categories, CH, W, H, view, [&](size_t cnt) -> const float* { const float* at = p; p += cnt; return at; });
+    return TREXHIP_OK;
+}
+
 // ---- scale and pieces ----
 float pow2_scale(double max_abs, float* inv) {
     int k = 0;

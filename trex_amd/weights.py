@@ -156,3 +156,75 @@ def synthetic_train_batch(n, seed, classes, channels=1):
     x = np.clip(x * rng.uniform(0.85, 1.15, (n, 1, 1, 1)).astype(np.float32) + rng.uniform(0.0, 3.0, x.shape).astype(np.float32) * (x > 0), 0.0, 255.0)
     y = rng.integers(0, classes, n).astype(np.int32)
     return np.ascontiguousarray(x, np.float32), y
+
+
+# ---- the category network (trex_learn_category.py:18-44, PyTorchModel) ----
+# Its blob: 8 x int32 header {magic 'TRXC', version 1, categories, width, height, channels, 0, 0}, then the float32 tensors in the module's
+# state_dict order (declaration order: the three convolutions, the three BatchNorm2d, fc1, fc2), without num_batches_tracked.  The magic differs
+# from an identity blob's, so trexhip_load_weights refuses it and trexhip_categorize_load_weights refuses an identity blob; ARCH_IDS has no entry
+# for it.  A checkpoint's 'model_state' converts with tools/convert_category_weights.py.
+CATEGORY_MAGIC = 0x43585254  # 'TRXC'
+CATEGORY_CONVS = (16, 64, 100)
+
+
+def category_shapes(categories, channels=1, width=80, height=80):
+    """(name, shape) of every tensor of the category network in its state_dict order"""
+    out, ci = [], channels
+    for i, co in enumerate(CATEGORY_CONVS, 1):
+        out += [(f"conv{i}.weight", (co, ci, 3, 3)), (f"conv{i}.bias", (co,))]
+        ci = co
+    for i, co in enumerate(CATEGORY_CONVS, 1):
+        out += [(f"batch_norm{i}.{t}", (co,)) for t in _BN]
+    out += [("fc1.weight", (100, 100 * (width // 8) * (height // 8))), ("fc1.bias", (100,)), ("fc2.weight", (categories, 100)), ("fc2.bias", (categories,))]
+    return out
+
+
+def synthetic_category_state(categories, seed, channels=1, width=80, height=80):
+    """The recipe of synthetic_state for the category network; every third BatchNorm2d scale is negative (the BatchNorm stands in front of the
+    max-pool: a negative scale makes the pool pick what was the window's minimum)."""
+    rng = np.random.default_rng(seed)
+    st = {}
+    for name, shp in category_shapes(categories, channels, width, height):
+        if name.endswith("running_mean"):
+            st[name] = np.zeros(shp, np.float32)
+        elif name.endswith("running_var"):
+            st[name] = np.ones(shp, np.float32)
+        elif name.startswith("batch_norm") and name.endswith("weight"):
+            g = rng.uniform(0.5, 1.5, shp).astype(np.float32)
+            g[::3] = -g[::3]
+            st[name] = g
+        elif name.startswith("batch_norm") and name.endswith("bias"):
+            st[name] = rng.uniform(-0.3, 0.3, shp).astype(np.float32)
+        else:
+            fan_in = int(np.prod(shp[1:])) if len(shp) > 1 else int(np.prod(st[name.replace("bias", "weight")].shape[1:]))
+            b = 1.0 / np.sqrt(fan_in)
+            st[name] = rng.uniform(-b, b, shp).astype(np.float32)
+    st["fc2.weight"] = (st["fc2.weight"] * 8.0).astype(np.float32)   # peaky softmax: a flat one hides errors
+    return st
+
+
+def pack_category_blob(state, categories, channels=1, width=80, height=80):
+    hdr = np.array([CATEGORY_MAGIC, 1, categories, width, height, channels, 0, 0], np.int32)
+    parts = [hdr.tobytes()]
+    for name, shp in category_shapes(categories, channels, width, height):
+        if name not in state:
+            raise ValueError(f"{name} is missing")
+        t = np.ascontiguousarray(state[name], np.float32)
+        if t.shape != tuple(shp):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, the category network of {categories} categories at {width}x{height}x{channels} has {tuple(shp)}")
+        parts.append(t.tobytes())
+    return b"".join(parts)
+
+
+def unpack_category_blob(blob):
+    """Inverse of pack_category_blob: -> (state dict, categories, channels, width, height)"""
+    hdr = np.frombuffer(blob[:32], np.int32)
+    assert int(hdr[0]) == CATEGORY_MAGIC and int(hdr[1]) == 1, "not a TRXC v1 blob"
+    categories, width, height, channels = int(hdr[2]), int(hdr[3]), int(hdr[4]), int(hdr[5])
+    st, off = {}, 32
+    for name, shp in category_shapes(categories, channels, width, height):
+        cnt = int(np.prod(shp))
+        st[name] = np.frombuffer(blob[off:off + 4 * cnt], np.float32).reshape(shp).copy()
+        off += 4 * cnt
+    assert off == len(blob), "blob size does not match its header"
+    return st, categories, channels, width, height
