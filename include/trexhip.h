@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 19
+#define TREXHIP_ABI_VERSION 20
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -675,7 +675,32 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  *                              v110 26 (bn4's running statistics included); conv3 and fc1 have 100 channels
  *   trexhip_trainer_export     header word 6 names the version; the blob loads with trexhip_load_weights
  * v119 and v200 are refused with TREXHIP_E_UNSUPPORTED and a text that names the version.
+ * The category network (ABI 20).  A 'TRXC' blob -- the blob of trexhip_categorize_load_weights, parsed by the same parser, so refused with the
+ * same codes and field names: 1..1024 categories, 1 or 3 channels, 8..256 each way -- gives a trainer of the category network
+ * (trex_learn_category.py:18-44, PyTorchModel, in train mode; trexhip_trainer_version: TREXHIP_NET_CATEGORY).  A category network has no life
+ * outside training: there are no pretrained weights, Categorize.perform_training (:276-340) trains it on the crops the user labelled.  The
+ * step restates the loop body :314-332 on a non-CUDA device, in fp32; on 'cuda' the reference adds autocast and a GradScaler (:297, :318-331),
+ * whose arithmetic is not restated.  The same calls, the same resident path; one generic chain in exact fp32 at every size and both values of
+ * `precision` (trex_amd/csrc/train_cat.hip), on the context's stream alone, every reduction in a fixed order.  What differs:
+ *   the network                x = byte / 127.5 - 1 (:289, a true fp32 division, then the subtraction), padded with zeros AFTER the normalisation;
+ *                              three blocks of [conv 3x3 padding 1 -> BatchNorm2d (batch statistics over all n h w pixels, the odd last row and
+ *                              column included) -> ReLU -> floor 2x2 max-pool -> element-wise Dropout(0.25)] with 16, 64, 100 channels (:22-36);
+ *                              NCHW flatten; fc1 (100) -> ReLU -> Dropout(0.25) -> fc2 (categories) (:37-43); mean cross entropy; Adam with the
+ *                              reference's defaults (:295: lr 1e-4 -- trexhip_train_params.lr -- and a batch of 32)
+ *   inputs                     float32 [n][H][W][channels] in [0, 255] like every other trainer: the normalisation happens inside the first layer,
+ *                              forward and in conv1's weight gradient.  trexhip_augment_device's plain path, trexhip_train_predict_device on uint8
+ *                              crops and the validation calls work unchanged
+ *   dropout                    0.25 four times; trexhip_train_params.dropout is range-checked and otherwise not read
+ *   d_keep_masks               ELEMENT-wise ("Using Dropout instead of Dropout2d", :35): four planes back to back, 1 = keep, NHWC,
+ *                              [n][h1][w1][16] [n][h2][w2][64] [n][h3][w3][100] [n][100] with (h_i, w_i) the pooled planes by successive floors
+ *                              (h1 = H / 2, h2 = h1 / 2, h3 = h2 / 2); 4-byte aligned.  trexhip_trainer_keep_mask_bytes gives the size
+ *   n = 1                      trains: block 3's convolution plane has at least 2 x 2 pixels at every legal size
+ *   trexhip_trainer_read       the module's state_dict order and torch's shapes (trex_amd/weights.py category_shapes): 22 tensors, running
+ *                              statistics included, without num_batches_tracked
+ *   trexhip_trainer_export     a 'TRXC' blob that trexhip_categorize_load_weights takes; trexhip_load_weights keeps refusing it
+ * What stays with the caller: the validation split, the "500 new samples" rule, the checkpoint file, classification_report.
  * ------------------------------------------------------------------------------------------------ */
+#define TREXHIP_NET_CATEGORY 100      /* trexhip_trainer_version of a category trainer: not an identity network, outside the TREXHIP_NET_* of a blob's header */
 typedef struct trexhip_trainer trexhip_trainer;
 typedef struct {
     int32_t max_batch;          /* largest n of a step (VINetwork: 64..128, ml/VisualIdentification.cpp:112-118)               */
@@ -696,8 +721,11 @@ int trexhip_trainer_set_lr(trexhip_trainer* trainer, float lr);
 int64_t trexhip_trainer_steps(trexhip_trainer* trainer);
 /* the individual_image_size of the blob the trainer was created from: what every batch, crop and exported blob of this trainer has (ABI 14) */
 int trexhip_trainer_image_size(trexhip_trainer* trainer, int32_t* width, int32_t* height);
-/* the TREXHIP_NET_* of the blob the trainer was created from: V118_3, V100 or V110 (ABI 18) */
+/* the TREXHIP_NET_* of the blob the trainer was created from: V118_3, V100 or V110 (ABI 18); TREXHIP_NET_CATEGORY for a 'TRXC' blob (ABI 20) */
 int trexhip_trainer_version(trexhip_trainer* trainer, int32_t* version);
+/* bytes of the d_keep_masks of a step of n samples, for any trainer: V118_3 n * 308, v100 / v110 n * 280, the category network
+ * n * (h1 w1 16 + h2 w2 64 + h3 w3 100 + 100).  The three layouts differ; callers need not restate them.  0 for a null trainer or n < 0 (ABI 20) */
+size_t trexhip_trainer_keep_mask_bytes(trexhip_trainer* trainer, int32_t n);
 int trexhip_train_step_device(trexhip_trainer* trainer, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks,
                               float* loss, int32_t* correct);
 /* model.eval() forward + mean cross entropy + arg-max count of one validation batch (train(), :1171-1190: what ReduceLROnPlateau and the

@@ -7,6 +7,11 @@ BatchNorm2d, fc1 and fc2.  The crop size cannot be read off the tensors alone (f
 channels and categories come from conv1.weight and fc2.weight.
 
     python tools/convert_category_weights.py categories.pth categories.trxc --width 80 --height 80
+
+The way back -- a blob that trexhip_trainer_export wrote, as a checkpoint holding {'model_state': state_dict} that PyTorchModel.load_state_dict
+takes (the blob knows its own size; num_batches_tracked is not a weight and is left to the module's default):
+
+    python tools/convert_category_weights.py --from-blob categories.trxc categories.pth
 """
 import argparse
 import os
@@ -46,14 +51,28 @@ def convert(obj, width, height):
     return weights.pack_category_blob(st, categories, channels, width, height), categories, channels
 
 
+def model_state(blob):
+    """'TRXC' blob -> the module's state_dict as torch tensors, in its declaration order"""
+    import torch
+    st, categories, channels, width, height = weights.unpack_category_blob(blob)
+    return {k: torch.from_numpy(v) for k, v in st.items()}, categories, channels, width, height
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("checkpoint")
     ap.add_argument("output")
     ap.add_argument("--width", type=int, default=80, help="individual_image_size, width")
     ap.add_argument("--height", type=int, default=80, help="individual_image_size, height")
+    ap.add_argument("--from-blob", action="store_true", help="the way back: `checkpoint` is a 'TRXC' blob, `output` the checkpoint to write")
     a = ap.parse_args()
     import torch
+    if a.from_blob:
+        with open(a.checkpoint, "rb") as f:
+            sd, categories, channels, width, height = model_state(f.read())
+        torch.save({"model_state": sd}, a.output)
+        print(f"{a.output}: model_state of {categories} categories, {width}x{height}x{channels}")
+        return
     obj = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     blob, categories, channels = convert(obj, a.width, a.height)
     with open(a.output, "wb") as f:

@@ -202,7 +202,7 @@ SYMBOLS = [
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
     "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats", "trexhip_identify_skip_stats", "trexhip_identify_skip3_stats",
-    "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_trainer_version", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
+    "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_trainer_version", "trexhip_trainer_keep_mask_bytes", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
     "trexhip_lzo1x_bound", "trexhip_lzo1x_compress", "trexhip_pv_write_frames",
@@ -303,6 +303,8 @@ def lib():
         L.trexhip_trainer_steps.restype = C.c_int64
         L.trexhip_trainer_image_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.trexhip_trainer_version.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.trexhip_trainer_keep_mask_bytes.argtypes = [C.c_void_p, C.c_int32]
+        L.trexhip_trainer_keep_mask_bytes.restype = C.c_size_t
         L.trexhip_train_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_train_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.trexhip_train_eval_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -922,7 +924,9 @@ class Segmenter:
 
 class Trainer:
     """Training step of the identity network (include/trexhip.h: trexhip_trainer_*, trexhip_train_step_device): V118_3, v100 or v110, as the
-    blob's header says.  `dropout` is V118_3's rate: v100 and v110 use their architecture's own and do not read it."""
+    blob's header says -- or of the category network, when the blob is a 'TRXC' one (version NET_CATEGORY).  `dropout` is V118_3's rate: the other
+    networks use their architecture's own and do not read it."""
+    NET_CATEGORY = 100                                    # TREXHIP_NET_CATEGORY
 
     def __init__(self, seg, weight_blob, max_batch, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, bn_momentum=0.1, dropout=0.05, seed=0, precision=0):
         self._h = C.c_void_p()
@@ -937,10 +941,20 @@ class Trainer:
         self._blob_bytes = len(weight_blob)
         v = C.c_int32()
         _check(lib().trexhip_trainer_version(self._h, C.byref(v)))
-        self.version = v.value                            # TREXHIP_NET_*: 0 V118_3, 1 v100, 2 v110 (trex_amd.weights.ARCH_IDS)
-        # injected keep masks of one sample: Dropout2d behind block 1, 2, 3 and the Dropout behind fc1; conv3 has 128 channels in V118_3, 100 in v100 / v110
-        self.mask_planes = (16, 64, 128, 100) if self.version == 0 else (16, 64, 100, 100)
-        self.mask_row = sum(self.mask_planes)
+        self.version = v.value                            # TREXHIP_NET_*: 0 V118_3, 1 v100, 2 v110 (trex_amd.weights.ARCH_IDS); NET_CATEGORY
+        # injected keep masks of one sample: Dropout2d behind block 1, 2, 3 and the Dropout behind fc1; conv3 has 128 channels in V118_3, 100 in v100 / v110.
+        # The category network's dropout is element-wise: one byte per pooled element, NHWC, (h_i, w_i) by successive floors
+        if self.version == self.NET_CATEGORY:
+            h1, w1 = self.height // 2, self.width // 2
+            self.mask_planes = (h1 * w1 * 16, (h1 // 2) * (w1 // 2) * 64, (h1 // 4) * (w1 // 4) * 100, 100)
+        else:
+            self.mask_planes = (16, 64, 128, 100) if self.version == 0 else (16, 64, 100, 100)
+        self.mask_row = self.keep_mask_bytes(1)           # the library's own statement of the layout
+        assert self.mask_row == sum(self.mask_planes)
+
+    def keep_mask_bytes(self, n):
+        """bytes of the keep masks of a step of n samples (trexhip_trainer_keep_mask_bytes): the planes lie back to back, each [n][...]"""
+        return int(lib().trexhip_trainer_keep_mask_bytes(self._h, n))
 
     def step_device(self, d_inputs_ptr, d_targets_ptr, n, d_keep_ptr=0, want_loss=True):
         """-> (mean loss, correct count) when want_loss (synchronises), else None"""
@@ -964,7 +978,7 @@ class Trainer:
 
     def step(self, inputs, targets, keep_masks=None):
         """host arrays: inputs float32 (n,height,width,C) in [0,255], targets int (n,), keep_masks uint8 (n*mask_row,) or None -> (loss, correct);
-        mask_row is 308 for V118_3 and 280 for v100 / v110"""
+        mask_row is 308 for V118_3, 280 for v100 / v110 and keep_mask_bytes(1) for the category network (element-wise masks: it follows the size)"""
         x, y = self._check_batch(inputs, targets)
         k = np.ascontiguousarray(keep_masks, np.uint8) if keep_masks is not None else None
         if k is not None and k.size != x.shape[0] * self.mask_row:

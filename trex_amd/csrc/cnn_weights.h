@@ -82,6 +82,8 @@ size_t category_blob_bytes(int categories, int CH, int W, int H);       // 0 out
 // view->id = ARCH_ID_CATEGORY, view->classes = categories, bn1d null.  A refusal names the field (size, magic, version, width, height, channels,
 // categories) and `who`
 int parse_category_blob(const void* blob, size_t bytes, const char* who, ArchBlob* view);
+bool blob_is_category(const void* blob, size_t bytes);                  // its first word is the category magic (whatever else is wrong with it)
+void write_category_blob_header(void* blob, int categories, int W, int H, int CH);
 
 // One convolution for k_arch_conv: weight [CO][CI][T][T] -> fp32 [CO_pad/COB][CI_pad/16][T*T][16][COB] (zero where padded), and the epilogue's
 // per-channel vectors relu((max_window(conv) * out_scale + bias) * s + t):  fold = true (v119, v200: BatchNorm in front of the pool) folds the

@@ -155,6 +155,17 @@ size_t category_blob_bytes(int categories, int CH, int W, int H) {
     return 32 + 4 * n;
 }
 
+bool blob_is_category(const void* blob, size_t bytes) {
+    int32_t magic = 0;
+    if (bytes >= 4) std::memcpy(&magic, blob, 4);
+    return magic == CAT_MAGIC;
+}
+
+void write_category_blob_header(void* blob, int categories, int W, int H, int CH) {
+    const int32_t hdr[8] = {CAT_MAGIC, 1, categories, W, H, CH, 0, 0};
+    std::memcpy(blob, hdr, 32);
+}
+
 int parse_category_blob(const void* blob, size_t bytes, const char* who, ArchBlob* view) {
     const std::string pre = std::string(who) + ": ";
     if (bytes < 32) { set_error(pre + "size: " + std::to_string(bytes) + " bytes are less than the header"); return TREXHIP_E_INVALID; }

@@ -24,8 +24,9 @@
 // The kernels of this file are the 80x80 chain.  A blob of any other individual_image_size (8..256 each way) trains on the chain of
 // train_any.hip (exact fp32, geometry in train_geom.h): the same walk, with `Trainer::any` choosing the launch at every size-dependent
 // kernel; the head, Adam, the masks, the target check, the loss and the reductions are shared.
-// A v100 or v110 blob gives a trainer of train_arch.hip instead (ArchTrainer): the entry points at the end of this file hand every call of such a
-// handle over, and that chain launches this file's size-independent kernels through train_shared.h.
+// A v100 or v110 blob gives a trainer of train_arch.hip instead (ArchTrainer), a category blob ('TRXC') one of train_cat.hip (CatTrainer): the entry
+// points at the end of this file hand every call of such a handle over, and those chains launch this file's size-independent kernels through
+// train_shared.h.
 #include "internal.h"
 #include "conv_f32.h"
 #include "cnn_weights.h"
@@ -33,6 +34,7 @@
 #include "train_any.h"
 #include "train_shared.h"
 #include "train_arch.h"
+#include "train_cat.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1150,11 +1152,12 @@ __global__ __launch_bounds__(640) void k_t_wgrad_h2(const float* __restrict__ a 
 }
 
 // sum of the partials in order -> gradient in the parameter layout [ci / CIC][tap][ci % CIC][co]
-__global__ __launch_bounds__(256) void k_t_wgrad_reduce(const float* __restrict__ part, int nparts, int CI, int CO, int CIC, float* __restrict__ g) {
+// (T = the taps of the convolution: 25, or 9 for the category network)
+__global__ __launch_bounds__(256) void k_t_wgrad_reduce(const float* __restrict__ part, int nparts, int CI, int CO, int CIC, float* __restrict__ g, int T) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int total = 25 * CI * CO;
+    const int total = T * CI * CO;
     if (idx >= total) return;
-    const int co = idx % CO, cic = (idx / CO) % CIC, tap = (idx / (CO * CIC)) % 25, cc = idx / (CO * CIC * 25);
+    const int co = idx % CO, cic = (idx / CO) % CIC, tap = (idx / (CO * CIC)) % T, cc = idx / (CO * CIC * T);
     const size_t src = ((size_t)tap * CI + cc * CIC + cic) * CO + co;
     float acc = 0.f;
     for (int p0 = 0; p0 < nparts; p0 += 8) {                            // eight loads in flight, added in part order
@@ -1254,17 +1257,17 @@ __global__ __launch_bounds__(256) void k_t_reduce(const float* __restrict__ part
 }
 
 // weights of the data-gradient convolutions: input channels = the forward layer's outputs, taps flipped.
-// wb[cc'][t][cic'][co'] = w_fwd(ci = co', co = cc' * CICB + cic', tap = 24 - t); forward layout [ci / CIC][tap][ci % CIC][co]
+// wb[cc'][t][cic'][co'] = w_fwd(ci = co', co = cc' * CICB + cic', tap = T - 1 - t); forward layout [ci / CIC][tap][ci % CIC][co]; T taps (25 or 9)
 __global__ __launch_bounds__(256) void k_t_repack_bwd(const float* __restrict__ wf, int CI, int CO, int CIC, int COP /*padded output channels*/,
-                                                      int CICB /*input-channel chunk of the data-gradient kernel*/, float* __restrict__ wb) {
+                                                      int CICB /*input-channel chunk of the data-gradient kernel*/, float* __restrict__ wb, int T) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int total = 25 * CO * COP;
+    const int total = T * CO * COP;
     if (idx >= total) return;
-    const int cop = idx % COP, cicp = (idx / COP) % CICB, t = (idx / (COP * CICB)) % 25, ccp = idx / (COP * CICB * 25);
+    const int cop = idx % COP, cicp = (idx / COP) % CICB, t = (idx / (COP * CICB)) % T, ccp = idx / (COP * CICB * T);
     float v = 0.f;
     if (cop < CI) {
-        const int ci = cop, co = ccp * CICB + cicp, tap = 24 - t;
-        v = wf[(((size_t)(ci / CIC) * 25 + tap) * CIC + ci % CIC) * CO + co];
+        const int ci = cop, co = ccp * CICB + cicp, tap = T - 1 - t;
+        v = wf[(((size_t)(ci / CIC) * T + tap) * CIC + ci % CIC) * CO + co];
     }
     wb[idx] = v;
 }
@@ -1540,18 +1543,18 @@ static void block_backward(Trainer* t, const Streams& q, const Layer& L, int n, 
     if (t->any) {
         const int shares = t->geom.wg_shares(L.slot, n);
         tany_wgrad(q.w, t->geom, L.slot, n, below.a, L.z, t->part);
-        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w]);
-        hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * L.dgrad.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, L.dgrad.co, L.dgrad.cic, L.wb);
+        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w], 25);
+        hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * L.dgrad.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, L.dgrad.co, L.dgrad.cic, L.wb, 25);
         tany_conv_dgrad(q.s, t->geom, L.slot, n, L.z, L.wb, below.da);
         return;
     }
     const WgradKernel& g = L.wgrad;
     const int shares = std::min(n * g.units, g.max_shares);
     hipLaunchKernelGGL(g.fn, dim3(g.types, shares), dim3(g.threads), g.lds, q.w, below.a, L.z, t->part, n);
-    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w]);
+    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w], 25);
     // the data gradient: the same convolution on flipped + transposed weights
     const ConvKernel& k = L.dgrad;
-    if (!k.h2) hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * k.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, k.co, k.cic, L.wb);
+    if (!k.h2) hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * k.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, k.co, k.cic, L.wb, 25);
     if (k.h2) hipLaunchKernelGGL(k.h2, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wh_b, nullptr, below.da, L.wh_scale, nullptr);
     else if (k.f32_n16) hipLaunchKernelGGL(k.f32_n16, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wb, below.da);
     else hipLaunchKernelGGL(k.f32, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wb, nullptr, below.da);
@@ -1727,14 +1730,14 @@ void t_fin_bias(hipStream_t s, const double* partial, int nblocks, int C, float*
 void t_bn_from_running(hipStream_t s, const float* run_mean, const float* run_var, int C, float* mean, float* invstd) {
     hipLaunchKernelGGL(k_t_bn_from_running, dim3(1), dim3(128), 0, s, run_mean, run_var, C, mean, invstd);
 }
-void t_wgrad_reduce(hipStream_t s, const float* part, int shares, int CI, int CO, int CIC, float* g) {
-    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * CI * CO + 255) / 256), dim3(256), 0, s, part, shares, CI, CO, CIC, g);
+void t_wgrad_reduce(hipStream_t s, const float* part, int shares, int CI, int CO, int CIC, float* g, int taps) {
+    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((taps * taps * CI * CO + 255) / 256), dim3(256), 0, s, part, shares, CI, CO, CIC, g, taps * taps);
 }
 void t_reduce(hipStream_t s, const float* part, int nparts, int count, float* out) {
     hipLaunchKernelGGL(k_t_reduce, dim3((count + 15) / 16), dim3(256), 0, s, part, nparts, count, out);
 }
-void t_repack_bwd(hipStream_t s, const float* wf, int CI, int CO, int CIC, int COP, int CICB, float* wb) {
-    hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * CO * COP + 255) / 256), dim3(256), 0, s, wf, CI, CO, CIC, COP, CICB, wb);
+void t_repack_bwd(hipStream_t s, const float* wf, int CI, int CO, int CIC, int COP, int CICB, float* wb, int taps) {
+    hipLaunchKernelGGL(k_t_repack_bwd, dim3((taps * taps * CO * COP + 255) / 256), dim3(256), 0, s, wf, CI, CO, CIC, COP, CICB, wb, taps * taps);
 }
 void t_adam(hipStream_t s, float* P, const float* G, float* M, float* V, size_t total, const uint32_t* skip_lo, const uint32_t* skip_hi, int nskip, double lr,
             double beta1, double beta2, float eps, int64_t step, const int32_t* refused) {
@@ -1756,8 +1759,9 @@ void t_loss(hipStream_t s, const float* loss, const int32_t* correct, int n, flo
 
 }  // namespace trexhip
 
-// a trainer is one of two: V118_3 (t, this file) or v100 / v110 (a, train_arch.hip); every entry point below looks at `a` first
-struct trexhip_trainer { trexhip::Trainer* t; trexhip::ArchTrainer* a = nullptr; };
+// a trainer is one of three: V118_3 (t, this file), v100 / v110 (a, train_arch.hip) or the category network (c, train_cat.hip); every entry point
+// below looks at `c` and `a` first
+struct trexhip_trainer { trexhip::Trainer* t; trexhip::ArchTrainer* a = nullptr; trexhip::CatTrainer* c = nullptr; };
 
 extern "C" {
 
@@ -1782,6 +1786,13 @@ size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) {
 int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, trexhip_trainer** out) {
     if (!ctx || !blob || !p || !out) { set_error("trexhip_trainer_create: null argument"); return TREXHIP_E_INVALID; }
     *out = nullptr;
+    if (blob_is_category(blob, bytes)) {                              // the parser of trexhip_categorize_load_weights, the chain of train_cat.hip
+        if (const int rc = check_train_params(p)) return rc;
+        CatTrainer* c = nullptr;
+        if (const int rc = cat_trainer_create(ctx, blob, bytes, p, &c)) return rc;
+        *out = new trexhip_trainer{nullptr, nullptr, c};
+        return TREXHIP_OK;
+    }
     const int arch = blob_arch_id(blob, bytes);
     if (arch == TREXHIP_NET_V100 || arch == TREXHIP_NET_V110) {       // the parser of trexhip_load_weights, the chain of train_arch.hip
         if (const int rc = check_train_params(p)) return rc;
@@ -1895,6 +1906,7 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
 
 void trexhip_trainer_destroy(trexhip_trainer* h) {
     if (!h) return;
+    if (h->c) cat_trainer_destroy(h->c);
     if (h->a) arch_trainer_destroy(h->a);
     if (h->t) { (void)hipSetDevice(h->t->ctx->p.device); (void)hipStreamSynchronize(h->t->ctx->stream); trainer_free(h->t); }
     delete h;
@@ -1902,16 +1914,18 @@ void trexhip_trainer_destroy(trexhip_trainer* h) {
 
 int trexhip_trainer_set_lr(trexhip_trainer* h, float lr) {
     if (!h || !(lr > 0.f)) { set_error("trexhip_trainer_set_lr: a trainer and lr > 0 are required"); return TREXHIP_E_INVALID; }
-    if (h->a) arch_trainer_set_lr(h->a, lr);
+    if (h->c) cat_trainer_set_lr(h->c, lr);
+    else if (h->a) arch_trainer_set_lr(h->a, lr);
     else h->t->p.lr = lr;
     return TREXHIP_OK;
 }
 
-int64_t trexhip_trainer_steps(trexhip_trainer* h) { return !h ? -1 : h->a ? arch_trainer_steps(h->a) : h->t->step; }
+int64_t trexhip_trainer_steps(trexhip_trainer* h) { return !h ? -1 : h->c ? cat_trainer_steps(h->c) : h->a ? arch_trainer_steps(h->a) : h->t->step; }
 
 int trexhip_trainer_image_size(trexhip_trainer* h, int32_t* width, int32_t* height) {
     if (!h || !width || !height) { set_error("trexhip_trainer_image_size: null argument"); return TREXHIP_E_INVALID; }
-    if (h->a) arch_trainer_info(h->a, width, height, nullptr, nullptr);
+    if (h->c) cat_trainer_info(h->c, width, height, nullptr);
+    else if (h->a) arch_trainer_info(h->a, width, height, nullptr, nullptr);
     else { *width = h->t->W; *height = h->t->H; }
     return TREXHIP_OK;
 }
@@ -1919,15 +1933,22 @@ int trexhip_trainer_image_size(trexhip_trainer* h, int32_t* width, int32_t* heig
 int trexhip_trainer_version(trexhip_trainer* h, int32_t* version) {
     if (!h || !version) { set_error("trexhip_trainer_version: null argument"); return TREXHIP_E_INVALID; }
     *version = TREXHIP_NET_V118_3;
-    if (h->a) arch_trainer_info(h->a, nullptr, nullptr, version, nullptr);
+    if (h->c) *version = TREXHIP_NET_CATEGORY;
+    else if (h->a) arch_trainer_info(h->a, nullptr, nullptr, version, nullptr);
     return TREXHIP_OK;
+}
+
+size_t trexhip_trainer_keep_mask_bytes(trexhip_trainer* h, int32_t n) {
+    if (!h || n < 0) return 0;
+    return h->c ? cat_trainer_keep_mask_bytes(h->c, n) : h->a ? arch_trainer_keep_mask_bytes(n) : (size_t)n * KEEP_ROW;
 }
 
 // what every batch entry point checks first: the handle, its two pointers, 1 <= n <= max_batch (any_n: no upper bound, the call chunks)
 static int check_batch(const char* who, const trexhip_trainer* h, const void* a, const void* b, int n, bool any_n = false) {
     if (!h || !a || !b) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
     int32_t max_n = 0;
-    if (h->a) arch_trainer_info(h->a, nullptr, nullptr, nullptr, &max_n);
+    if (h->c) cat_trainer_info(h->c, nullptr, nullptr, &max_n);
+    else if (h->a) arch_trainer_info(h->a, nullptr, nullptr, nullptr, &max_n);
     else max_n = h->t->max_n;
     if (n < 1 || (!any_n && n > max_n)) { set_error(std::string(who) + (any_n ? ": n must be at least 1" : ": n must be 1..max_batch")); return TREXHIP_E_INVALID; }
     return TREXHIP_OK;
@@ -1951,14 +1972,15 @@ static int stage_batch(const char* who, const trexhip_trainer* h, const float* i
 int trexhip_train_step_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks, float* loss,
                               int32_t* correct) {
     if (const int rc = check_batch("trexhip_train_step_device", h, d_inputs, d_targets, n)) return rc;
+    if (h->c) return cat_trainer_step(h->c, false, d_inputs, d_targets, n, d_keep_masks, loss, correct);
     if (h->a) return arch_trainer_step(h->a, false, d_inputs, d_targets, n, d_keep_masks, loss, correct);
     return trainer_step(h->t, d_inputs, d_targets, n, d_keep_masks, loss, correct);
 }
 
 int trexhip_train_step(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, const uint8_t* keep_masks, float* loss, int32_t* correct) {
-    if (h && h->a) {
+    if (h && (h->a || h->c)) {
         if (const int rc = check_batch("trexhip_train_step", h, inputs, targets, n)) return rc;
-        return arch_trainer_step(h->a, true, inputs, targets, n, keep_masks, loss, correct);
+        return h->c ? cat_trainer_step(h->c, true, inputs, targets, n, keep_masks, loss, correct) : arch_trainer_step(h->a, true, inputs, targets, n, keep_masks, loss, correct);
     }
     if (const int rc = stage_batch("trexhip_train_step", h, inputs, targets, n, keep_masks)) return rc;
     Trainer* t = h->t;
@@ -1969,26 +1991,29 @@ int trexhip_train_step(trexhip_trainer* h, const float* inputs, const int32_t* t
 
 int trexhip_train_eval_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, float* loss, int32_t* correct) {
     if (const int rc = check_batch("trexhip_train_eval_device", h, d_inputs, d_targets, n)) return rc;
+    if (h->c) return cat_trainer_eval(h->c, false, d_inputs, d_targets, n, loss, correct);
     if (h->a) return arch_trainer_eval(h->a, false, d_inputs, d_targets, n, loss, correct);
     return trainer_eval(h->t, d_inputs, d_targets, n, loss, correct);
 }
 
 int trexhip_train_predict_device(trexhip_trainer* h, const uint8_t* d_crops, int32_t n, float* d_probs) {
     if (const int rc = check_batch("trexhip_train_predict_device", h, d_crops, d_probs, n, true)) return rc;
+    if (h->c) return cat_trainer_predict(h->c, d_crops, n, d_probs);
     if (h->a) return arch_trainer_predict(h->a, d_crops, n, d_probs);
     return trainer_predict(h->t, d_crops, n, d_probs);
 }
 
 int trexhip_train_eval(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, float* loss, int32_t* correct) {
-    if (h && h->a) {
+    if (h && (h->a || h->c)) {
         if (const int rc = check_batch("trexhip_train_eval", h, inputs, targets, n)) return rc;
-        return arch_trainer_eval(h->a, true, inputs, targets, n, loss, correct);
+        return h->c ? cat_trainer_eval(h->c, true, inputs, targets, n, loss, correct) : arch_trainer_eval(h->a, true, inputs, targets, n, loss, correct);
     }
     if (const int rc = stage_batch("trexhip_train_eval", h, inputs, targets, n, nullptr)) return rc;
     return trainer_eval(h->t, h->t->x_stage, h->t->y_stage, n, loss, correct);
 }
 
 int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float* out, size_t count) {
+    if (h && h->c) return cat_trainer_read(h->c, tensor, kind, out, count);
     if (h && h->a) return arch_trainer_read(h->a, tensor, kind, out, count);
     if (!h || !out || tensor < 0 || tensor >= T_COUNT || kind < 0 || kind > 3) { set_error("trexhip_trainer_read: bad argument"); return TREXHIP_E_INVALID; }
     Trainer* t = h->t;
@@ -2005,6 +2030,7 @@ int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float
 
 int trexhip_trainer_export(trexhip_trainer* h, void* blob, size_t capacity, size_t* bytes) {
     if (!h || !blob) { set_error("trexhip_trainer_export: null argument"); return TREXHIP_E_INVALID; }
+    if (h->c) return cat_trainer_export(h->c, blob, capacity, bytes);
     if (h->a) return arch_trainer_export(h->a, blob, capacity, bytes);
     Trainer* t = h->t;
     const size_t need = weight_blob_bytes(t->classes, t->CH, t->W, t->H);

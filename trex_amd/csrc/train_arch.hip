@@ -547,8 +547,7 @@ void trainer_forward(ArchTrainer* t, hipStream_t s, const float* x, const int32_
         hipLaunchKernelGGL(k_tarch_head<true>, dim3(n), dim3(128), 0, s, t->hsum, n, t->param(S_F1B), mean, invstd, t->param(S_G4), t->param(S_BE4), kp, scale[3], t->param(S_F2W),
                            t->param(S_F2B), targets, t->classes, t->xhat, t->hd, t->dl, t->dy, t->loss, t->correct, probs);
     } else {
-        hipLaunchKernelGGL(k_tarch_head<false>, dim3(n), dim3(128), 0, s, t->hsum, n, t->param(S_F1B), nullptr, nullptr, nullptr, nullptr, kp, scale[3], t->param(S_F2W),
-                           t->param(S_F2B), targets, t->classes, nullptr, t->hd, t->dl, t->dh, t->loss, t->correct, probs);
+        tarch_head_plain(s, t->hsum, n, t->param(S_F1B), kp, scale[3], t->param(S_F2W), t->param(S_F2B), targets, t->classes, t->hd, t->dl, t->dh, t->loss, t->correct, probs);
     }
 }
 
@@ -662,6 +661,16 @@ int arch_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const 
     return TREXHIP_OK;
 }
 
+// the BatchNorm-free head as another chain launches it (train_cat.hip): k_tarch_head<false> and k_tarch_head_grads, stated here once
+void tarch_head_plain(hipStream_t s, const float* hsum, int n, const float* b1, const uint8_t* keep, float scale, const float* w2, const float* b2, const int32_t* targets,
+                      int classes, float* hd, float* dl, float* dh, float* loss, int32_t* correct, float* probs) {
+    hipLaunchKernelGGL(k_tarch_head<false>, dim3(n), dim3(128), 0, s, hsum, n, b1, nullptr, nullptr, nullptr, nullptr, keep, scale, w2, b2, targets, classes, nullptr, hd, dl, dh,
+                       loss, correct, probs);
+}
+void tarch_head_grads(hipStream_t s, const float* dl, const float* hd, const float* dh, int n, int classes, float* g_w2, float* g_b2, float* g_b1) {
+    hipLaunchKernelGGL(k_tarch_head_grads, dim3((classes * HID + classes + HID + 255) / 256), dim3(256), 0, s, dl, hd, dh, n, classes, g_w2, g_b2, g_b1);
+}
+
 void arch_trainer_destroy(ArchTrainer* t) {
     if (!t) return;
     (void)hipSetDevice(t->ctx->p.device);
@@ -669,6 +678,7 @@ void arch_trainer_destroy(ArchTrainer* t) {
     trainer_free(t);
 }
 
+size_t arch_trainer_keep_mask_bytes(int n) { return (size_t)n * KEEP_ROW; }
 void arch_trainer_set_lr(ArchTrainer* t, float lr) { t->p.lr = lr; }
 int64_t arch_trainer_steps(const ArchTrainer* t) { return t->step; }
 void arch_trainer_info(const ArchTrainer* t, int32_t* width, int32_t* height, int32_t* version, int32_t* max_batch) {
@@ -707,8 +717,7 @@ int arch_trainer_step(ArchTrainer* t, bool host, const float* x, const int32_t* 
         hipLaunchKernelGGL(k_tarch_bn1d_sums, dim3(1), dim3(128), 0, s, t->dy, t->xhat, n, mean + 256, t->grad(S_G4), t->grad(S_BE4));
         hipLaunchKernelGGL(k_tarch_bn1d_dh, dim3((n * HID + 255) / 256), dim3(256), 0, s, t->dy, t->xhat, mean + 256, t->param(S_G4), mean + 128, n, t->dh);
     }
-    hipLaunchKernelGGL(k_tarch_head_grads, dim3((t->classes * HID + t->classes + HID + 255) / 256), dim3(256), 0, s, t->dl, t->hd, t->dh, n, t->classes, t->grad(S_F2W),
-                       t->grad(S_F2B), t->grad(S_F1B));
+    tarch_head_grads(s, t->dl, t->hd, t->dh, n, t->classes, t->grad(S_F2W), t->grad(S_F2B), t->grad(S_F1B));
     tany_fc1_wgrad(s, t->geom, n, t->L[2].a, t->dh, t->grad(S_F1W));
     t_loss(s, t->loss, t->correct, n, t->out2);
     tany_fc1_dgrad(s, t->geom, n, t->dh, t->param(S_F1W), t->L[2].da);

@@ -24,6 +24,7 @@ struct TrainAnyLayer {
 
 struct TrainAnyGeom {
     int W, H, CH;
+    int taps;                                // the convolutions are taps x taps with a halo of taps / 2: 5 (the identity networks) or 3 (the category network)
     TrainAnyLayer L[3];
     int h3, w3, P;                           // fc1: positions of the last pooled plane, P = (H / 8)(W / 8) by successive floors; the partial planes
                                              // of fc1 are the positions in row-major order (y * w3 + x), summed 0, 1, .. P - 1
@@ -49,16 +50,17 @@ struct TrainAnyGeom {
     size_t a_floats(const int i, const size_t n) const { return n * (L[i].h / 2) * (L[i].w / 2) * L[i].C; }
     size_t hpart_floats(const size_t n) const { return n * P * TA_HID; }
     size_t part_floats() const {
-        const size_t p1 = (size_t)L[1].wg_max_shares * 25 * L[1].CI * L[1].C, p2 = (size_t)L[2].wg_max_shares * 25 * L[2].CI * L[2].C;
+        const size_t t2 = (size_t)taps * taps;
+        const size_t p1 = (size_t)L[1].wg_max_shares * t2 * L[1].CI * L[1].C, p2 = (size_t)L[2].wg_max_shares * t2 * L[2].CI * L[2].C;
         return p1 > p2 ? p1 : p2;
     }
-    size_t part1_floats(const size_t n) const { return n * wg1_tiles * CH * 400; }
+    size_t part1_floats(const size_t n) const { return n * wg1_tiles * CH * taps * taps * 16; }
     size_t fc1_weight_floats() const { return (size_t)P * 128 * TA_HID; }
 };
 
-inline TrainAnyGeom train_any_geom(const int W, const int H, const int CH) {
+inline TrainAnyGeom train_any_geom(const int W, const int H, const int CH, const int taps = 5) {
     TrainAnyGeom g{};
-    g.W = W; g.H = H; g.CH = CH;
+    g.W = W; g.H = H; g.CH = CH; g.taps = taps;
     const int C[3] = {16, 64, 128};
     int h = H, w = W;
     // successive floors: every level halves the one above it and has an odd edge of its own (21 -> 10 -> 5 -> 2, 13 -> 6 -> 3 -> 1)
@@ -69,11 +71,11 @@ inline TrainAnyGeom train_any_geom(const int W, const int H, const int CH) {
         h /= 2; w /= 2;
     }
     g.h3 = h; g.w3 = w; g.P = h * w;
-    // weight gradients: a workgroup type is a kernel row x a 32-wide slice of the input channels (conv2: 16 channels x 2 taps per slice);
-    // the shares keep the grid near two workgroups per CU of the 256
+    // weight gradients: a workgroup type is a kernel row x a 32-wide slice of the input channels (conv2: 16 channels x 2 taps per slice), so
+    // taps and 2 taps types: 5 and 10 at 5 taps, 3 and 6 at 3; the shares keep the 5-tap grid near two workgroups per CU of the 256
     g.L[0].wg_types = 0; g.L[0].wg_max_shares = 0;
-    g.L[1].wg_types = 5; g.L[1].wg_max_shares = 96;
-    g.L[2].wg_types = 10; g.L[2].wg_max_shares = 48;
+    g.L[1].wg_types = taps; g.L[1].wg_max_shares = 96;
+    g.L[2].wg_types = 2 * taps; g.L[2].wg_max_shares = 48;
     g.c1_tx = (W + TA_C1T - 1) / TA_C1T;
     g.c1_tiles = ((H + TA_C1T - 1) / TA_C1T) * g.c1_tx;
     g.wg1_tx = (W + TA_WG1_COLS - 1) / TA_WG1_COLS;

@@ -1,5 +1,6 @@
 // train_shared.h -- the launches of train.hip's size-independent kernels (reductions, the optimizer, the masks, the target check, the loss sum) as
-// another chain calls them: train_arch.hip (v100, v110) runs them unchanged.  Everything is queued on the given stream, nothing synchronises.
+// another chain calls them: train_arch.hip (v100, v110) and train_cat.hip (the category network) run them unchanged.  Everything is queued on the
+// given stream, nothing synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -20,12 +21,12 @@ void t_fin_bn_bwd(hipStream_t s, const double* partial, int nblocks, int C, floa
 void t_fin_bias(hipStream_t s, const double* partial, int nblocks, int C, float* d_bias);
 // k_t_bn_from_running: eval mode's mean and invstd
 void t_bn_from_running(hipStream_t s, const float* run_mean, const float* run_var, int C, float* mean, float* invstd);
-// k_t_wgrad_reduce: part[shares][25][CI][CO] -> g in the parameter layout [CI / CIC][25][CIC][CO]
-void t_wgrad_reduce(hipStream_t s, const float* part, int shares, int CI, int CO, int CIC, float* g);
+// k_t_wgrad_reduce: part[shares][T][CI][CO] -> g in the parameter layout [CI / CIC][T][CIC][CO], T = taps^2
+void t_wgrad_reduce(hipStream_t s, const float* part, int shares, int CI, int CO, int CIC, float* g, int taps = 5);
 // k_t_reduce: out[count] = sum of nparts parts, fixed order
 void t_reduce(hipStream_t s, const float* part, int nparts, int count, float* out);
 // k_t_repack_bwd: the data gradient's flipped + transposed weights
-void t_repack_bwd(hipStream_t s, const float* wf, int CI, int CO, int CIC, int COP, int CICB, float* wb);
+void t_repack_bwd(hipStream_t s, const float* wf, int CI, int CO, int CIC, int COP, int CICB, float* wb, int taps = 5);
 // k_t_adam over [0, total) but the `nskip` (at most 6) ranges [lo, hi) of buffers
 void t_adam(hipStream_t s, float* P, const float* G, float* M, float* V, size_t total, const uint32_t* skip_lo, const uint32_t* skip_hi, int nskip, double lr,
             double beta1, double beta2, float eps, int64_t step, const int32_t* refused);

@@ -11,11 +11,17 @@
 //   sample_rows(size, first_frame, sample_rate, min_samples)
 //                                     which rows of a tracklet are predicted at all (DataStore::temporary, CategorizeDatastore.cpp:1103-1152).
 //                                     Pure host code.
+//   HipCategorize::Trainer(ctx, blob, bytes, max_batch, lr)
+//                                     Categorize.perform_training's model + criterion + optimizer (trex_learn_category.py:276-340) on the device: a
+//                                     trexhip_trainer created from a 'TRXC' blob.  step(inputs, targets) is one pass of the loop body :317-334,
+//                                     evaluate(inputs, targets) one batch of _predict_labels_and_loss (:356-373), export_blob() the weights as they
+//                                     stand, load_into(categorize) hands them to the inference slot of a HipCategorize
 // Define TREXHIP_CATEGORIZE_HOST_ONLY to leave out everything that calls the library (the host twin and sample_rows then need nothing but this file).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -143,6 +149,64 @@ struct HipCategorize {
     static CategorySampleRows sample_rows(size_t size, long first_frame, size_t sample_rate, size_t min_samples) {
         return category_sample_rows(size, first_frame, sample_rate, min_samples);
     }
+
+    struct StepResult { float loss = 0.f; int32_t correct = 0; };
+
+    // inputs: float32 [n][H][W][channels] in [0, 255] on the host (the crops as stored: the normalisation is the network's first layer);
+    // targets: [n] category indices.  The dropout masks are the library's own draw
+    struct Trainer {
+        Trainer(trexhip_ctx* ctx, const void* blob, size_t bytes, int32_t max_batch = 32, float lr = 1e-4f, uint64_t seed = 0) {
+            if (!ctx) throw std::invalid_argument("HipCategorize::Trainer: null context");
+            trexhip_train_params p{};
+            p.max_batch = max_batch; p.lr = lr; p.beta1 = 0.9f; p.beta2 = 0.999f; p.eps = 1e-8f; p.bn_momentum = 0.1f; p.dropout = 0.25f; p.precision = 1; p.seed = seed;
+            check(trexhip_trainer_create(ctx, blob, bytes, &p, &_t));
+            int32_t version = 0;
+            check(trexhip_trainer_version(_t, &version));
+            if (version != TREXHIP_NET_CATEGORY) { trexhip_trainer_destroy(_t); throw std::invalid_argument("HipCategorize::Trainer: not a category blob ('TRXC')"); }
+            _bytes = bytes;
+            int32_t hdr[8];
+            std::memcpy(hdr, blob, sizeof(hdr));                        // (the library has accepted the blob: it holds its header)
+            _channels = hdr[5];
+            check(trexhip_trainer_image_size(_t, &_width, &_height));
+        }
+        ~Trainer() { trexhip_trainer_destroy(_t); }
+        Trainer(const Trainer&) = delete;
+        Trainer& operator=(const Trainer&) = delete;
+
+        StepResult step(const std::vector<float>& inputs, const std::vector<int32_t>& targets) {
+            StepResult r;
+            check_batch(inputs, targets);
+            check(trexhip_train_step(_t, inputs.data(), targets.data(), (int32_t)targets.size(), nullptr, &r.loss, &r.correct));
+            return r;
+        }
+        StepResult evaluate(const std::vector<float>& inputs, const std::vector<int32_t>& targets) {
+            StepResult r;
+            check_batch(inputs, targets);
+            check(trexhip_train_eval(_t, inputs.data(), targets.data(), (int32_t)targets.size(), &r.loss, &r.correct));
+            return r;
+        }
+        int64_t steps() const { return trexhip_trainer_steps(_t); }
+        std::vector<uint8_t> export_blob() {
+            std::vector<uint8_t> blob(_bytes);
+            size_t got = 0;
+            check(trexhip_trainer_export(_t, blob.data(), blob.size(), &got));
+            return blob;
+        }
+        void load_into(HipCategorize& categorize) {
+            const std::vector<uint8_t> blob = export_blob();
+            categorize.load_weights(blob.data(), blob.size());
+        }
+        trexhip_trainer* handle() const { return _t; }
+
+      private:
+        void check_batch(const std::vector<float>& inputs, const std::vector<int32_t>& targets) const {
+            if (targets.empty() || inputs.size() != targets.size() * (size_t)_width * _height * _channels)
+                throw std::invalid_argument("HipCategorize::Trainer: inputs must be [n][H][W][channels] for n targets");
+        }
+        trexhip_trainer* _t = nullptr;
+        size_t _bytes = 0;
+        int32_t _width = 0, _height = 0, _channels = 0;
+    };
 
   private:
     trexhip_ctx* _ctx;

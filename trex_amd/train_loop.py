@@ -168,9 +168,10 @@ class ResidentLoader:
     ordered, so a step that was handed a batch has read it before the next is written).  Every epoch draws a new seeded permutation
     when shuffle is set and new augmentations (the call's counter runs on); drop_last=False: the last batch may be smaller.
     augment=True applies `params` (default: capi.default_augment_params(W, H), the reference's transform); augment=False,
-    shuffle=False is the validation loader.  `seg` is the capi.Segmenter whose stream the trainer uses."""
+    shuffle=False is the validation loader.  `rows` (pool indices, default: all of them) restricts what is served to a subset of the pool -- the
+    training or the validation rows of one resident pool.  `seg` is the capi.Segmenter whose stream the trainer uses."""
 
-    def __init__(self, seg, crops_uint8, targets, batch_size, augment=True, shuffle=True, seed=0, count=None, image_shape=None, params=None):
+    def __init__(self, seg, crops_uint8, targets, batch_size, augment=True, shuffle=True, seed=0, count=None, image_shape=None, params=None, rows=None):
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         self.seg, self.batch_size, self.shuffle, self.seed = seg, int(batch_size), bool(shuffle), int(seed)
@@ -193,6 +194,9 @@ class ResidentLoader:
             if self.count:
                 seg.copy_to_device(self.d_pool, x)
                 seg.copy_to_device(self.d_pool_targets, y.astype(np.int32))
+        self.rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        if self.rows is not None and self.rows.size and (self.rows.min() < 0 or self.rows.max() >= self.count):
+            raise ValueError("rows must be indices into the pool")
         self.params = None
         if augment:
             if params is None:
@@ -211,13 +215,15 @@ class ResidentLoader:
         return p
 
     def __len__(self):
-        return (self.count + self.batch_size - 1) // self.batch_size
+        served = self.count if self.rows is None else len(self.rows)
+        return (served + self.batch_size - 1) // self.batch_size
 
     def order(self, epoch):
         """pool indices of `epoch` in the order they are served"""
+        rows = np.arange(self.count, dtype=np.int32) if self.rows is None else self.rows
         if not self.shuffle:
-            return np.arange(self.count, dtype=np.int32)
-        return np.random.default_rng([self.seed, epoch]).permutation(self.count).astype(np.int32)
+            return rows
+        return rows[np.random.default_rng([self.seed, epoch]).permutation(len(rows))].astype(np.int32)
 
     def __iter__(self):
         order = self.order(self.epoch)
@@ -233,6 +239,68 @@ class ResidentLoader:
         for p in self._owned:
             self.seg.device_free(p)
         self._owned = []
+
+
+def train_category(seg, weight_blob, crops_uint8, targets, validation_indexes, epochs=10, batch_size=32, lr=1e-4, seed=0, keep_masks=None, history=None,
+                   log=None):
+    """Categorize.perform_training (trex_learn_category.py:276-340) without leaving the device: the labelled crops (uint8 (N, H, W, C), targets (N,))
+    are uploaded once as a resident pool; the training rows are the pool without `validation_indexes` (:291-294); `epochs` epochs (10) of batches of
+    `batch_size` (32) over a shuffled index list per epoch (DataLoader(shuffle=True), :312 -- here ResidentLoader's seeded permutation, augment=False:
+    the reference feeds the crops as they are), one Adam step at `lr` (1e-4, :295) per batch and the epoch's mean of the batch losses (:334-336); then the
+    evaluation of update_best_accuracy (:356-391) on the validation rows in eval mode: the mean loss over the samples and the accuracy.  Returns the
+    exported 'TRXC' blob, which trexhip_categorize_load_weights takes.
+
+    weight_blob: the network to start from (a fresh one: weights.pack_category_blob of an initialisation).  keep_masks(epoch, batch, n) -> packed uint8
+    masks of that step or None (the library draws them): how a test injects what a restatement used.  history, when a dict, receives "losses" (per
+    epoch), "val_loss", "val_accuracy" and "steps".  What stays with the caller, as it is GUI and file business in the reference: choosing the
+    validation split (:232-260), the "500 new samples" rule that decides WHEN to train, the checkpoint file with the sample store (:342-351), and
+    classification_report beyond the accuracy."""
+    from . import capi
+    x = np.asarray(crops_uint8)
+    y = np.asarray(targets)
+    val = np.unique(np.asarray(validation_indexes, np.int64))
+    train_rows = np.delete(np.arange(len(x), dtype=np.int64), val)
+    if not len(train_rows):
+        raise ValueError("no training rows are left beside the validation rows")
+    trainer = capi.Trainer(seg, weight_blob, max_batch=batch_size, lr=lr, seed=seed)
+    if trainer.version != capi.Trainer.NET_CATEGORY:
+        trainer.close()
+        raise ValueError("train_category needs a category blob ('TRXC')")
+    train = ResidentLoader(seg, x, y, batch_size, augment=False, shuffle=True, seed=seed, rows=train_rows)
+    # the validation rows out of the same resident pool
+    valid = ResidentLoader(seg, train.d_pool, train.d_pool_targets, batch_size, augment=False, shuffle=False, count=train.count,
+                           image_shape=(train.height, train.width, train.channels), rows=val)
+    d_keep = seg.device_alloc(max(trainer.keep_mask_bytes(batch_size), 1)) if keep_masks is not None else 0
+    try:
+        losses = []
+        for epoch in range(epochs):
+            running = 0.0
+            for b, (d_x, d_y, n) in enumerate(train):
+                k = keep_masks(epoch, b, n) if keep_masks is not None else None
+                if k is not None:
+                    k = np.ascontiguousarray(k, np.uint8)
+                    if k.size != trainer.keep_mask_bytes(n):
+                        raise ValueError(f"keep_masks({epoch}, {b}, {n}) holds {k.size} bytes, the step needs {trainer.keep_mask_bytes(n)}")
+                    seg.copy_to_device(d_keep, k)
+                running += trainer.step_device(d_x, d_y, n, d_keep if k is not None else 0)[0]
+            losses.append(running / len(train))
+            if log:
+                log(f"Epoch {epoch + 1}, Loss: {losses[-1]}")
+        total_loss, total_correct, count = 0.0, 0, 0
+        for d_x, d_y, n in valid:
+            loss, correct = trainer.evaluate_device(d_x, d_y, n)
+            total_loss += loss * n
+            total_correct += correct
+            count += n
+        if history is not None:
+            history.update(losses=losses, val_loss=total_loss / max(count, 1), val_accuracy=total_correct / max(count, 1), steps=trainer.steps)
+        return trainer.export()
+    finally:
+        if d_keep:
+            seg.device_free(d_keep)
+        valid.close()
+        train.close()
+        trainer.close()
 
 
 class _PerClassHistory(dict):
