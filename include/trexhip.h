@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 20
+#define TREXHIP_ABI_VERSION 21
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -581,6 +581,14 @@ int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* li
  * listed form walked (0: the dense kernel ran), *bytes_filled of conv3's output copied instead; zeros before the first such call.  No reference
  * counterpart; any pointer may be NULL.  (ABI 16) */
 int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled);
+
+/* Where conv3 lists row pairs and the batch has more than 1024 crops, fc1 -- ten split-K planes, plane q = row pair q of every crop -- computes
+ * only the (crop, plane) rows whose row pair is listed; the head takes every other plane from the fc1 planes of an all-zero crop, made when the
+ * weights are loaded, and the unlisted row pairs of conv3's output are no longer copied (bytes_filled above still counts them).  The results are
+ * the bits of the dense fc1.  Bit 24 of TREXHIP_CONV_GEOM (value 16777216) switches this off.
+ * What the last identify call did (waits for the context's stream): *rows = crop-plane rows of the batch (10 per crop), *listed of them
+ * computed; both 0 where the call's fc1 was not the listed form.  No reference counterpart; either pointer may be NULL.  (ABI 21) */
+int trexhip_identify_fc1_stats(trexhip_ctx* ctx, uint32_t* rows, uint32_t* listed);
 
 /* ---- multi-GPU hand-off --------------------------------------------------------------------
  * Fixed-size per-blob identity table of the last batch, written to caller-owned device memory

@@ -1004,18 +1004,36 @@ __global__ __launch_bounds__(256) void k_fc1(const float* __restrict__ act, cons
 // call): ten workgroups walking 40 chunks of (load, split, barrier, 24 MFMAs) each took 54 us of a 234 us step -- a chain no prefetch depth shortens
 // (four chunks in flight: 57 us); with 32 crops per workgroup the chain is a quarter as long per chunk and four times as many workgroups run it.
 // Every output is the same sum in the same order whatever MT is.
-template <int MT = 4>
+// LISTED (cnn_skip3.h: skip3_fc1_listed): plane blockIdx.y computes only the crops of its list -- row r of the workgroup's tile is crop
+// list[plane][m0 + r], the loads, the output rows and the crop flags go by that crop; rows behind the list's length load zeros and store
+// nothing, whole 32-crop tiles behind it skip their MFMAs, a workgroup behind it returns at once.  A row's sum and its order are those of
+// the dense form (a row of an MFMA tile depends on no other row); the head takes the planes that are not computed from Net::fc1e.
+template <int MT = 4, bool LISTED = false>
 __global__ __launch_bounds__(256) void k_fc1_split(const float* __restrict__ act, const uint4* __restrict__ wq /*[K/8][2][128]*/,
                                                    const float* __restrict__ bias, float* __restrict__ out, int n, int K,
-                                                   const float out_scale, uint32_t* __restrict__ overflow, uint8_t* __restrict__ crop_flags) {
+                                                   const float out_scale, uint32_t* __restrict__ overflow, uint8_t* __restrict__ crop_flags,
+                                                   const int* __restrict__ list /*[planes][stride]*/, const uint32_t* __restrict__ lens, const int stride) {
     constexpr int RPB = 80;                                     // bytes per staged row (32 halves + 16 pad)
     constexpr int RW = 32 * MT;                                 // crops per workgroup
     __shared__ __attribute__((aligned(16))) uint8_t As[2][2][RW * RPB];
+    __shared__ int s_crop[LISTED ? RW : 1];                     // LISTED: the crop of every row of the tile (-1: behind the list)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int m0 = blockIdx.x * RW;
+    const int len = LISTED ? (int)lens[blockIdx.y] : n;         // rows of this plane
+    if (LISTED && m0 >= len) return;                            // (in front of every barrier)
     const int kspan = K / (int)gridDim.y, kbeg = (int)blockIdx.y * kspan;
     out += (size_t)blockIdx.y * n * 128;
+    int crow[LISTED ? MT : 1];                                  // LISTED: the crop behind each row this thread stages
+    if constexpr (LISTED) {
+        list += (size_t)blockIdx.y * stride;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int row = (tid + 256 * i) >> 3;
+            crow[i] = m0 + row < len ? list[m0 + row] : -1;
+        }
+        if (tid < RW) s_crop[tid] = m0 + tid < len ? list[m0 + tid] : -1;      // read behind the first barrier below
+    }
     f32x16 acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -1029,8 +1047,9 @@ __global__ __launch_bounds__(256) void k_fc1_split(const float* __restrict__ act
     do {                                                                                                                   \
         _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                    \
             const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;                                                    \
-            na[i] = m0 + row < n ? *reinterpret_cast<const float4*>(act + (size_t)(m0 + row) * K + kbeg + (kc) * 32 + q * 4) \
-                                 : make_float4(0.f, 0.f, 0.f, 0.f);                                                        \
+            const int crop_ = LISTED ? crow[LISTED ? i : 0] : m0 + row < n ? m0 + row : -1;                                \
+            na[i] = crop_ >= 0 ? *reinterpret_cast<const float4*>(act + (size_t)crop_ * K + kbeg + (kc) * 32 + q * 4)      \
+                               : make_float4(0.f, 0.f, 0.f, 0.f);                                                          \
         }                                                                                                                  \
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                                 \
             const uint4* w_ = wl + (size_t)((kc) * 4 + 2 * ks + h) * 256;                                                  \
@@ -1062,6 +1081,7 @@ __global__ __launch_bounds__(256) void k_fc1_split(const float* __restrict__ act
             const f16x8 b1 = __builtin_bit_cast(f16x8, cb[ks][0]), b2 = __builtin_bit_cast(f16x8, cb[ks][1]);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
+                if (LISTED && m0 + 32 * m >= len) break;      // (uniform in the workgroup) a whole tile behind the list: nothing to add up
                 const uint8_t* a = As[buf][0] + (32 * m + j) * RPB + (2 * ks + h) * 16;
                 const f16x8 p1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(a));
                 const f16x8 p2 = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(a + RW * RPB));
@@ -1083,8 +1103,11 @@ __global__ __launch_bounds__(256) void k_fc1_split(const float* __restrict__ act
     for (int i = 0; i < MT; ++i) any_ovf |= ovf4[i];
     if (__any(any_ovf)) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
-            if (ovf4[i] && crop_flags && m0 + ((tid + 256 * i) >> 3) < n) crop_flags[m0 + ((tid + 256 * i) >> 3)] = 1;
+        for (int i = 0; i < MT; ++i) {
+            const int row = (tid + 256 * i) >> 3;
+            const int crop = LISTED ? crow[LISTED ? i : 0] : m0 + row < n ? m0 + row : -1;
+            if (ovf4[i] && crop_flags && crop >= 0) crop_flags[crop] = 1;
+        }
         if (lane == 0) atomicOr(overflow, 1u);
     }
     const int co = wave * 32 + j;
@@ -1094,7 +1117,8 @@ __global__ __launch_bounds__(256) void k_fc1_split(const float* __restrict__ act
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int i = 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (m0 + i < n) out[(size_t)(m0 + i) * 128 + co] = acc[m][r] * out_scale + bz;
+            const int crop = LISTED ? s_crop[LISTED ? i : 0] : m0 + i < n ? m0 + i : -1;
+            if (crop >= 0) out[(size_t)crop * 128 + co] = acc[m][r] * out_scale + bz;
         }
 }
 
@@ -1117,7 +1141,11 @@ __device__ __forceinline__ float wave_max(float v) {
 __global__ __launch_bounds__(256) void k_head(const float* __restrict__ fc1 /*[N][128]*/, const float* __restrict__ ln_g,
                                               const float* __restrict__ ln_b, const float* __restrict__ w2t /*[100][C]*/,
                                               const float* __restrict__ b2, float* __restrict__ probs /*[N][C]*/,
-                                              float* __restrict__ logits_out, int n, int C, const uint32_t* __restrict__ guard, int ksplit) {
+                                              float* __restrict__ logits_out, int n, int C, const uint32_t* __restrict__ guard, int ksplit,
+                                              const float* __restrict__ fc1e /*[KSPLIT][128]*/, const int2* __restrict__ bands,
+                                              const uint32_t* __restrict__ words) {
+    // fc1e != nullptr: behind the listed fc1 (never with a guard: the re-run computes every plane of its crops) -- the plane of a pair that
+    // is not listed (skip3_fc1_listed) was not computed: it is the empty crop's, the same bits
     if (guard && guard[1] == 0u) return;                   // guard = the plan of k_guard_plan; list mode: item i is crop plan[2 + i]
     const int n_items = fb_count(guard, n);
     constexpr int Q = HEAD_CPW;
@@ -1134,11 +1162,18 @@ __global__ __launch_bounds__(256) void k_head(const float* __restrict__ fc1 /*[N
     // the fc1 partial planes of the split-K launch: every load of the wave's crops goes out first (the planes lie n * 512 bytes apart: a chain of
     // dependent loads would pay one memory latency per plane), the sums follow in the fixed plane order
     float xa[FC1_KSPLIT][Q], xb[FC1_KSPLIT][Q];
+    const bool all = !fc1e || words[SK_EMPTY_RANGE] != 0;
+    SkipBand band[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int2 b = all ? make_int2(0, 0) : bands[cidx[q]];
+        band[q] = {b.x, b.y};
+    }
 #pragma unroll
     for (int s = 0; s < FC1_KSPLIT; ++s)
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            const float* xs = fc1 + (size_t)s * n * 128 + (size_t)cidx[q] * 128;
+            const float* xs = skip3_fc1_listed(all, band[q], s) ? fc1 + (size_t)s * n * 128 + (size_t)cidx[q] * 128 : fc1e + s * 128;
             xa[s][q] = s < ksplit ? xs[lane] : 0.f;
             xb[s][q] = (s < ksplit && lane + 64 < 100) ? xs[lane + 64] : 0.f;
         }
@@ -1419,6 +1454,7 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 4, who));
         TRY(B.device_bytes(&net->skip3_desc, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Geom::DESC * 4, who));
         TRY(B.device_bytes(&net->skip3_rows, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Reach::WORDS * 4, who));
+        TRY(B.device_bytes(&net->fc1_list, Skip3Geom::PAIRS * N * sizeof(int), who));
     }
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
     TRY(B.pinned(&net->h_probs, N * net->classes, who));
@@ -1463,7 +1499,8 @@ static const ExactLayer K_CONV2{Kern(k_conv5<16, 64, 40, 20, 16>, 512, ConvGeom<
 static const ExactLayer K_CONV3{Kern(k_conv5<64, 128, 20, 20, 32>, 512, ConvGeom<64, 128, 20, 20, 32>::LDS_BYTES), split_kern<64, 128, 20, 20, 6>(),
                                 split_kern<64, 128, 20, 20, 3>(), split_kern<64, 128, 20, 4, 6>()};
 static const Kern K_FC1(k_fc1, 256);
-static const Kern K_FC1_SPLIT1(k_fc1_split<1>, 256), K_FC1_SPLIT4(k_fc1_split<4>, 256);
+static const Kern K_FC1_SPLIT1(k_fc1_split<1>, 256), K_FC1_SPLIT4(k_fc1_split<4>, 256), K_FC1_SPLIT4_LIST(k_fc1_split<4, true>, 256);
+static const Kern K_FC1_LIST(k_fc1_list, FC1L_TB);
 static const Kern K_HEAD(k_head, 256);
 static const Kern K_HEAD_SMALL(k_head_small, 256);
 static const Kern K_GUARD_PLAN(k_guard_plan, 1024);
@@ -1503,11 +1540,17 @@ static void launch_tail(const Pass& f, const uint32_t* guard) {
     const CnnPlan& p = f.p;
     if (guard || p.fc1 == Fc1::EXACT)
         K_FC1(f.s, dim3(guard ? p.r_fc1_grid : p.fc1_grid, p.planes), net.act3, net.wf1, net.bf1, net.fc1, f.n, p.K, guard);
+    else if (p.fc1_listed)      // only the listed (crop, plane) rows; the head takes the others from fc1e
+        K_FC1_SPLIT4_LIST(f.s, dim3(p.fc1_grid, p.planes), net.act3, net.wf1h, net.bf1, net.fc1, f.n, p.K, net.invf1h, net.ovf(OVF_RANGE), net.d_ovfc,
+                          net.fc1_list, net.d_skip + SK3_FC1_LEN, net.max_crops);
     else
         (p.fc1 == Fc1::SPLIT1 ? K_FC1_SPLIT1 : K_FC1_SPLIT4)(f.s, dim3(p.fc1_grid, p.planes), net.act3, net.wf1h, net.bf1, net.fc1, f.n, p.K, net.invf1h,
-                                                            net.ovf(OVF_RANGE), net.d_ovfc);
-    if (guard || p.head == Head::BIG)
-        K_HEAD(f.s, guard ? p.r_head_grid : p.head_grid, net.fc1, net.lng, net.lnb, net.wf2t, net.bf2, f.probs, f.logits, f.n, net.classes, guard, p.planes);
+                                                            net.ovf(OVF_RANGE), net.d_ovfc, nullptr, nullptr, 0);
+    if (guard || p.head == Head::BIG) {
+        const bool listed = !guard && p.fc1_listed;
+        K_HEAD(f.s, guard ? p.r_head_grid : p.head_grid, net.fc1, net.lng, net.lnb, net.wf2t, net.bf2, f.probs, f.logits, f.n, net.classes, guard, p.planes,
+               listed ? net.fc1e : nullptr, listed ? net.skip_bands : nullptr, listed ? net.d_skip : nullptr);
+    }
     else        // its first workgroup also makes the range guard's plan
         K_HEAD_SMALL(f.s, p.head_grid, net.fc1, net.lng, net.lnb, net.wf2t, net.bf2, f.probs, f.logits, f.n, net.classes, p.planes,
                      p.head_plans ? net.ovf(OVF_RANGE) : nullptr, net.d_ovfc, p.head_plans ? net.ovf(OVF_PLAN) : nullptr);
@@ -1533,6 +1576,7 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     uint8_t* zero = nullptr;
     int rc = net->weights.device_bytes(&net->v3e, (size_t)SkipGeom::V3_ROWS * V3_ROWB, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->act3e, (size_t)Skip3Geom::PAIRS * 10 * 128 * 4, who);
+    if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->fc1e, (size_t)FC1_KSPLIT * 128 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->d_skip, SK_WORDS * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&zero, SkipGeom::CROP_ROWS * 80, who);
     if (rc != TREXHIP_OK) return rc;
@@ -1546,7 +1590,19 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV3_WPAIR.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV3_WPAIR.lds));
     K_CONV3_WPAIR(ctx->stream, p.conv3.grid, net->v3e, net->w3w, net->b3, net->act3e, net->inv3w, 1, net->d_skip + SK3_EMPTY_CTR, p.n_big3, nullptr, nullptr, nullptr);
     TH_CHECK_HIP(hipGetLastError());
+    // ... and that crop's fc1 planes: k_fc1_split<4> itself on that act3, one crop, every plane, its own range-flag word.  A background activation
+    // outside the fp16 pieces' range raises the empty crop's flag: every pass and every pair is listed then, nothing is taken from these images
+    const CnnPlan pf = cnn_plan(80, 80, 1, TREXHIP_CNN_FP16X3, true, 0, 1, ctx->n_cus);
+    K_FC1_SPLIT4(ctx->stream, dim3(1, pf.planes), net->act3e, net->wf1h, net->bf1, net->fc1e, 1, pf.K, net->invf1h, net->d_skip + SK3_FC1E_RANGE, nullptr,
+                 nullptr, nullptr, 0);
+    TH_CHECK_HIP(hipGetLastError());
+    uint32_t range = 0;
+    TH_CHECK_HIP(hipMemcpyAsync(&range, net->d_skip + SK3_FC1E_RANGE, 4, hipMemcpyDeviceToHost, ctx->stream));
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (range) {
+        const uint32_t one = 1;
+        TH_CHECK_HIP(hipMemcpy(net->d_skip + SK_EMPTY_RANGE, &one, 4, hipMemcpyHostToDevice));
+    }
     return TREXHIP_OK;
 }
 
@@ -1582,6 +1638,8 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
                 if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
                     K_PAIR_COUNT(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
                     K_PAIR_LIST(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
+                    // the crops each plane of the listed fc1 computes: from the bands alone, so here and not between conv3 and fc1
+                    if (p.fc1_listed) K_FC1_LIST(s, Skip3Geom::PAIRS, net.skip_bands, n, net.d_skip, net.fc1_list, net.max_crops);
                 }
                 K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3),
                           (int)direct);
@@ -1606,7 +1664,7 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         if (pre) {
             if (p.skip3) {     // the listed passes' descriptors and row sources, and the other pairs' act3; which form of the kernel runs is the device's word
                 K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e), reinterpret_cast<uint4*>(net.act3), net.skip3_desc,
-                            net.skip3_rows, alloc_rows, (int)direct);
+                            net.skip3_rows, alloc_rows, (int)direct, (int)!p.fc1_listed);
                 K_CONV3_WPAIR_LIST(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.skip3_rows, net.d_skip);
             }
             K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3, nullptr, nullptr, p.skip3 ? net.d_skip : nullptr);
@@ -1638,6 +1696,9 @@ int net_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs,
     }
     const int rc = net_forward_inner(ctx, d_crops, n, d_probs, d_logits);
     if (rc == TREXHIP_OK) { net->last_mode = ctx->cnn_mode; if (ctx->cnn_mode == TREXHIP_CNN_FP16X3) net->ovf_clean = true; }
+    // (the plan is a pure function of these: the same one the launch, or the capture that is replayed, was made from)
+    net->last_fc1_n = rc == TREXHIP_OK && !net->arch && cnn_plan(net->W, net->H, net->CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0,
+                                                                 ctx->tune_conv_geom, n, ctx->n_cus).fc1_listed ? n : 0;
     return rc;
 }
 
@@ -1781,6 +1842,19 @@ int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* li
     if (listed) *listed = w[SK3_LISTED];
     if (passes) *passes = w[SK3_USE] ? w[SK3_PASSES] : 0u;
     if (bytes_filled) *bytes_filled = (uint64_t)w[SK3_FILLED] * (10 * 128 * 4);
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_fc1_stats(trexhip_ctx* ctx, uint32_t* rows, uint32_t* listed) {
+    if (!ctx || !ctx->net) { set_error("trexhip_identify_fc1_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
+    Net* net = static_cast<Net*>(ctx->net);
+    uint32_t w[SK_WORDS] = {};
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (net->last_fc1_n && net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    uint32_t sum = 0;
+    for (int q = 0; q < Skip3Geom::PAIRS; ++q) sum += w[SK3_FC1_LEN + q];
+    if (rows) *rows = (uint32_t)net->last_fc1_n * Skip3Geom::PAIRS;
+    if (listed) *listed = sum;
     return TREXHIP_OK;
 }
 

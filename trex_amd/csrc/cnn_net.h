@@ -43,6 +43,10 @@ struct Net {
     uint32_t* skip3_tcounts = nullptr;         // listed passes per thread of it (Skip3Geom::BLOCK crops)
     int* skip3_desc = nullptr;                 // Skip3Geom::DESC words per listed pass
     uint32_t* skip3_rows = nullptr;            // Skip3Reach::WORDS words per listed pass: where the rows it stages come from
+    // fc1 computing only the listed (crop, plane) rows (skip3_fc1_listed, cnn_skip3.h)
+    float* fc1e = nullptr;                     // the fc1 planes of an all-zero crop [FC1_KSPLIT][128] (plane 0 with the bias), made behind act3e
+    int* fc1_list = nullptr;                   // [Skip3Geom::PAIRS][max_crops]: per plane the crops it computes, in order (lengths: d_skip + SK3_FC1_LEN)
+    int last_fc1_n = 0;                        // crops of the last forward pass if its fc1 was the listed form, else 0 (trexhip_identify_fc1_stats)
     float* h_probs = nullptr;                  // pinned
     Mem weights, batch;                        // every allocation behind the pointers above: made at load / sized by max_crops (ensure_act)
     // small batches are launch-bound (one frame's 100 crops: 60 us of convolutions in a 160 us chain of ~12 launches): the chain of one

@@ -14,7 +14,10 @@ namespace trexhip {
 //                unless bit 26 is set as well: k_pair_count and k_pair_list in front of k_v3_fill, k_act3_fill and BOTH forms of k_conv5_wpair, the
 //                dense one and the one that walks the listed row pairs, behind conv2 -- the word k_pair_list writes names the one that runs, the
 //                other returns at once.  The listed form reads the background rows from the empty crop's image itself and k_v3_fill returns at
-//                once where that form runs; bit 25 keeps the copy -- the fill always runs and the listed form reads every row from V3)
+//                once where that form runs; bit 25 keeps the copy -- the fill always runs and the listed form reads every row from V3.
+//                Above 1024 crops, unless bit 24 is set: k_fc1_list beside k_pair_list, and fc1 computes only the (crop, split-K plane) rows whose
+//                row pair is listed -- the listed k_fc1_split<4>; k_head takes the other planes from the empty crop's, k_act3_fill copies no pair.
+//                Bit 24 keeps the dense fc1 and the fill's copy: the chain as it was before fc1 was listed, launch for launch)
 //   FUSED_2WG   k_conv12_wpre (the same, two workgroups per CU)          -> k_conv5_wpair       1 channel, aligned crops, fewer
 //   TWO_KERNEL  k_conv1_wpre -> k_conv2_wpre2                            -> k_conv5_wpair       3 channels, or TREXHIP_CONV_GEOM bit 28
 //   FP32_ACT    conv1 -> act1 -> k_conv5_stream -> act2 -> k_conv5_wino                         unaligned crops, or any of bits 0-11
@@ -54,6 +57,8 @@ struct CnnPlan {
     Launch act3_fill;               // k_act3_fill: 16 crops (SKIP3_FC) per workgroup
     bool v3_direct;                 // where skip3 is on: the listed conv3 reads background rows from the empty crop's image, k_v3_fill copies only for the
                                     // dense form; off: bit 25, or a batch whose V3 is longer than both images' reach (skip3_direct_fits)
+    bool fc1_listed;                // where skip3 is on, fc1 is SPLIT4 and the head BIG: k_fc1_list in front of conv1+conv2, the listed k_fc1_split<4>
+                                    // computes only the listed (crop, plane) rows, k_head takes the others from Net::fc1e, k_act3_fill copies nothing; off: bit 24
 };
 
 inline int ceil_div(const int a, const int b) { return (a + b - 1) / b; }
@@ -149,6 +154,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
         if (!small) p.fc1_grid = ceil_div(n, 128);
     }
     if (small) { p.head = Head::SMALL; p.head_grid = ceil_div(n, 4); }
+    p.fc1_listed = p.skip3 && p.fc1 == Fc1::SPLIT4 && p.head == Head::BIG && !(geom & (1 << 24));
     p.head_plans = h16 && small;
     p.rerun_conv1 = pre;
     p.r_conv2 = guarded(n * ConvGeomB<16, 64, 40, 10, SPLIT_NP>::BPC, n_cus);

@@ -178,8 +178,23 @@ enum : int {
     SK3_FILLED = 11,         // act3 row pairs filled from the empty crop's
     SK3_USE = 12,            // non-zero: the listed form of k_conv5_wpair runs, zero: the dense one
     SK3_EMPTY_CTR = 13,      // the pass counter of the run that made the empty crop's act3
-    SK3_LAST = SK3_EMPTY_CTR
+    SK3_FC1E_RANGE = 14,     // the fp16 range flag of the run that made the empty crop's fc1 planes (Net::fc1e): non-zero -> SK_EMPTY_RANGE is raised
+    SK3_FC1_LEN = 16,        // .. + PAIRS - 1: crops listed for plane q of the listed fc1 by the last call that listed (skip3_fc1_listed)
+    SK3_LAST = SK3_FC1_LEN + Skip3Geom::PAIRS - 1
 };
+
+// fc1's split-K plane s is row pair q = s of every crop (FC1_KSPLIT planes of 10 x 128 inputs), and a crop's row of an MFMA tile depends on
+// that crop's activations and the weights alone: the partial sum of a pair that holds the empty crop's bits is, bit for bit, plane q of fc1 run on
+// the empty crop's act3 (Net::fc1e, made once per loaded network).  The ONE rule that says which (crop, plane) the listed fc1 computes and the
+// head reads from memory -- the list kernel and the head call this function: every pair where the empty crop left the fp16 range (`all`: the
+// word SK_EMPTY_RANGE), else the pairs conv3's rule lists.  It does not depend on the form of conv3 that ran: behind the dense one an unlisted
+// pair holds the empty crop's bits just the same.
+static_assert(Skip3Geom::PAIRS == FC1_KSPLIT, "plane s of the split-K fc1 is row pair s");
+TREXHIP_HD constexpr bool skip3_fc1_listed(const bool all, const SkipBand b, const int q) {
+    if (all) return true;
+    const SkipPairs r = skip3_pairs(b);
+    return q >= r.lo && q <= r.hi;
+}
 
 // listed passes against the dense kernel's: the listed form runs when  listed * FACTOR_NUM < dense * FACTOR_DEN.  The factor is what a listed
 // pass costs in dense passes, measured on the benchmark's crops under a kernel trace (profiles/v3_direct_rows.txt): 3542 us for 31393 listed

@@ -10,7 +10,10 @@
 //   k_pair_list    the passes in order, each as its two runs, the counters, and the word that names the form of conv3 that runs (SK3_USE)
 //                  (both run in front of k_v3_fill, which reads that word)
 //   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place) and the sources of its rows; then a wave per crop: the act3 row pairs
-//                  that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load)
+//                  that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load) -- counted only, where the listed fc1
+//                  runs: it never reads them
+// and one for the listed form of k_fc1_split (the rule: skip3_fc1_listed, cnn_skip3.h), beside the two above:
+//   k_fc1_list     a workgroup per split-K plane: the crops whose pair the plane has to compute, in order, and how many they are
 #pragma once
 
 // the words of Net::d_skip
@@ -20,7 +23,7 @@ enum : int {
     SK_LEN = 2,              // passes listed by the last call
     SK_NPASS = 3,            // passes of the last call's batch
     SK_FILLED = 4,           // V3 rows the last call took from the empty crop's image instead of computing them (copied by k_v3_fill or read in place)
-    SK_WORDS = 16            // (8 ..: the words of the listed conv3, SK3_* in cnn_skip3.h)
+    SK_WORDS = 32            // (8 ..: the words of the listed conv3 and the listed fc1, SK3_* in cnn_skip3.h)
 };
 static_assert(SK3_LAST < SK_WORDS, "the words of the listed conv3 lie behind these");
 static constexpr int SKIP_LB = 1024;      // passes per block of the count / list kernels (one per thread)
@@ -239,6 +242,58 @@ __global__ __launch_bounds__(SKIP3_TB) void k_pair_list(const int2* __restrict__
     }
 }
 
+// ---- the listed form of fc1 ----
+// Plane q's list: the crops whose pair q is listed (skip3_fc1_listed), ascending, at list[q * stride ..], and its length in words[SK3_FC1_LEN + q].
+// One workgroup per plane, no atomics, nothing between workgroups: a wave looks at 64 consecutive crops at a time (one ballot = one 64-bit word of
+// the plane's bit map in LDS), a thread per word counts, one scan over the workgroup gives every word its place, and the waves write their words'
+// crops out, coalesced.  FC1L_SEG crops per round; every batch the role-split chain has seen is one round.
+static constexpr int FC1L_TB = 1024, FC1L_SEG = FC1L_TB * 64;
+__global__ __launch_bounds__(FC1L_TB) void k_fc1_list(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
+                                                      int* __restrict__ list /*[PAIRS][stride]*/, const int stride) {
+    constexpr int NW = FC1L_TB / 64, U = 8;
+    __shared__ unsigned long long s_mask[FC1L_TB];
+    __shared__ uint32_t s_off[FC1L_TB], s_wave[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = blockIdx.x;
+    const bool all = words[SK_EMPTY_RANGE] != 0;
+    int* out = list + (size_t)q * stride;
+    uint32_t base = 0;
+    for (int seg0 = 0; seg0 < n; seg0 += FC1L_SEG) {
+        const int left = n - seg0, nw = left >= FC1L_SEG ? FC1L_TB : (left + 63) / 64;      // bit-map words of this round
+        for (int w0 = wave; w0 < nw; w0 += U * NW) {          // U loads in flight per lane
+            int2 b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int crop = seg0 + (w0 + u * NW) * 64 + lane;
+                b[u] = w0 + u * NW < nw && crop < n ? bands[crop] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int crop = seg0 + (w0 + u * NW) * 64 + lane;
+                const unsigned long long m = __ballot(crop < n && skip3_fc1_listed(all, {b[u].x, b[u].y}, q));
+                if (lane == 0 && w0 + u * NW < nw) s_mask[w0 + u * NW] = m;
+            }
+        }
+        __syncthreads();
+        const uint32_t cnt = tid < nw ? (uint32_t)__popcll(s_mask[tid]) : 0u;
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = base, total = base;
+        for (int w = 0; w < NW; ++w) { const uint32_t c = s_wave[w]; if (w < wave) before += c; total += c; }
+        s_off[tid] = before + incl - cnt;
+        __syncthreads();
+        for (int w = wave; w < nw; w += NW) {
+            const unsigned long long m = s_mask[w];
+            if ((m >> lane) & 1ull) out[s_off[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = seg0 + w * 64 + lane;
+        }
+        base = total;
+        __syncthreads();
+    }
+    if (tid == 0) words[SK3_FC1_LEN + q] = base;
+}
+
 // a thread per listed pass: its descriptor; then SKIP3_FC crops per workgroup, a wave after the other: the row pairs outside the listed range
 // <- the empty crop's (a pair is 10 x 128 floats).  Nothing to do when the dense form runs.  (n * 16 threads, fewer than 3 n passes.)  One add to
 // the counter per workgroup: an add per crop is 25600 of them on one word, and they took longer than the copy
@@ -246,7 +301,8 @@ static constexpr int SKIP3_FC = 16;
 __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
                                                    const uint4* __restrict__ act3e, uint4* __restrict__ act3, int* __restrict__ desc,
                                                    uint32_t* __restrict__ rows /* Skip3Reach::WORDS per pass */,
-                                                   const long long alloc_rows /* V3 rows in front of the back image */, const int direct) {
+                                                   const long long alloc_rows /* V3 rows in front of the back image */, const int direct,
+                                                   const int copy /* 0: the listed fc1 runs and reads no unlisted pair -- they are counted, not copied */) {
     using G = Skip3Geom;
     constexpr int PQ = 10 * 128 * 4 / 16;             // 16-byte units per pair
     static_assert(Skip3Geom::BLOCK_PASSES * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass: 256 threads per SKIP3_FC crops");
@@ -286,6 +342,7 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
         for (int q = 0; q < G::PAIRS; ++q) {
             if (q >= r.lo && q <= r.hi) continue;
             ++filled;
+            if (!copy) continue;
 #pragma unroll
             for (int i = lane; i < PQ; i += 64) act3[((size_t)crop * G::PAIRS + q) * PQ + i] = act3e[q * PQ + i];
         }
