@@ -673,7 +673,7 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  * v100 and v110 (ABI 18).  A blob whose header names TREXHIP_NET_V100 or TREXHIP_NET_V110 (:328-382, :262-324) is parsed like
  * trexhip_load_weights parses it and gives a trainer of that version (trexhip_trainer_version): the same calls, the same resident path
  * (trexhip_augment_device, trexhip_train_predict_device, the validation and average calls).  Such a trainer runs one generic chain in exact
- * fp32 at every size, 80 x 80 included, at both values of `precision` (trex_amd/csrc/train_arch.hip), on the context's stream alone.  What differs:
+ * fp32 at every size, 80 x 80 included, at both values of `precision` (ChainTrainer, trex_amd/csrc/train_arch.hip), on the context's stream alone.  What differs:
  *   dropout rates              the architecture's: v100 0.25, 0.25, 0.25, 0.5; v110 0.25 four times.  trexhip_train_params.dropout is V118_3's
  *                              field; it is range-checked and otherwise not read
  *   d_keep_masks               n*16 + n*64 + n*100 + n*100 bytes: conv3 has 100 channels
@@ -689,7 +689,7 @@ int trexhip_profile_reset(trexhip_ctx* ctx);
  * outside training: there are no pretrained weights, Categorize.perform_training (:276-340) trains it on the crops the user labelled.  The
  * step restates the loop body :314-332 on a non-CUDA device, in fp32; on 'cuda' the reference adds autocast and a GradScaler (:297, :318-331),
  * whose arithmetic is not restated.  The same calls, the same resident path; one generic chain in exact fp32 at every size and both values of
- * `precision` (trex_amd/csrc/train_cat.hip), on the context's stream alone, every reduction in a fixed order.  What differs:
+ * `precision` (the same ChainTrainer, trex_amd/csrc/train_arch.hip), on the context's stream alone, every reduction in a fixed order.  What differs:
  *   the network                x = byte / 127.5 - 1 (:289, a true fp32 division, then the subtraction), padded with zeros AFTER the normalisation;
  *                              three blocks of [conv 3x3 padding 1 -> BatchNorm2d (batch statistics over all n h w pixels, the odd last row and
  *                              column included) -> ReLU -> floor 2x2 max-pool -> element-wise Dropout(0.25)] with 16, 64, 100 channels (:22-36);

@@ -1,4 +1,4 @@
-"""The cases of the category network's training step (trex_amd/csrc/train_cat.hip): the smallest shapes at which each path of the 3-tap chain can go
+"""The cases of the category network's training step (ChainTrainer in trex_amd/csrc/train_arch.hip): the smallest shapes at which each path of the 3-tap chain can go
 wrong.  A plain table plus the input recipe, shared by test_category_train_ref.py (the float64 margin of the float32 restatement, on the CPU) and
 test_train_category_gpu.py (the device against float64).
 

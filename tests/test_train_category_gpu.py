@@ -1,4 +1,4 @@
-"""The training step of the category network (trex_amd/csrc/train_cat.hip: train_any.hip's chain at 3 taps with a normalising conv1 pair and
+"""The training step of the category network (ChainTrainer in trex_amd/csrc/train_arch.hip: train_any.hip's chain at 3 taps with a normalising conv1 pair and
 element-wise dropout masks) against the float64 restatement (tests/category_train_ref.py, dtype=torch.float64) with injected masks, at the cases of
 tests/category_train_cases.py -- the smallest shapes at which each path can go wrong; that the float32 restatement stays five times inside every
 bar of float64 at every one of them is shown on the CPU by test_category_train_ref.py, so a miss here is the device's.

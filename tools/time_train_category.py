@@ -1,4 +1,4 @@
-"""Times one training step (trexhip_train_step_device) of the category network -- the 3-tap mode of the generic exact-fp32 chain, train_cat.hip -- at
+"""Times one training step (trexhip_train_step_device) of the category network -- the 3-tap mode of the one-stream exact-fp32 chain, train_arch.hip -- at
 batch 32 (the reference's) and 128, 80x80x1, 4 categories, beside the same step as torch fp32 autograd + torch.optim.Adam on the same GPU
 (trex_learn_category.py:18-44 restated with torch.nn; the torch step normalises its uint8-valued input as :289 does, so both sides start from the
 same [0, 255] batch): device events around windows of steps, the cases alternating, the median of the windows.  Every case is warmed up first.  No

@@ -18,23 +18,22 @@
 // flipped + transposed weights); weight gradients = k_t_wgrad (fp32 MFMA, operands straight from L2: one MFMA k-step = two pixels,
 // A = activations at the tap's shift, B = dz); batch-norm statistics and their backward sums in double; everything else VALU.
 // Every reduction has a fixed order: two runs of a step give identical bits.
-// Host side (below the kernels): each of the three blocks is one `Layer` -- shape, tensor ids, buffers, and the kernel instances of the
-// trainer's precision bound to their LDS sizes -- filled once in trexhip_trainer_create; the forward pass, block_backward and trainer_attrs
-// walk that table.
+// Host side (below the kernels): `Trainer` derives from TrainerCore (train_host.h), which holds what every trainer holds and does -- the tensors
+// (train_tensors.h), P / G / M / V, staging, the refusals, evaluation, prediction, read, export, the Adam call and the walk of a step -- and
+// supplies V118_3's chain: begin_step (the fork, the masks), forward, backward.  Each of the three blocks is one `Layer` -- shape, tensor ids,
+// buffers, and the kernel instances of the trainer's precision bound to their LDS sizes -- filled once in v118_trainer_create; the forward
+// pass, block_backward and trainer_attrs walk that table.
 // The kernels of this file are the 80x80 chain.  A blob of any other individual_image_size (8..256 each way) trains on the chain of
 // train_any.hip (exact fp32, geometry in train_geom.h): the same walk, with `Trainer::any` choosing the launch at every size-dependent
 // kernel; the head, Adam, the masks, the target check, the loss and the reductions are shared.
-// A v100 or v110 blob gives a trainer of train_arch.hip instead (ArchTrainer), a category blob ('TRXC') one of train_cat.hip (CatTrainer): the entry
-// points at the end of this file hand every call of such a handle over, and those chains launch this file's size-independent kernels through
-// train_shared.h.
+// A v100, v110 or category ('TRXC') blob gives a ChainTrainer (train_arch.hip) instead: trexhip_trainer_create (train_host.hip) chooses by the
+// blob, and that chain and the core launch this file's size-independent kernels through the t_* functions declared in train_host.h.
 #include "internal.h"
 #include "conv_f32.h"
 #include "cnn_weights.h"
 #include "train_dev.h"
 #include "train_any.h"
-#include "train_shared.h"
-#include "train_arch.h"
-#include "train_cat.h"
+#include "train_host.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1339,10 +1338,9 @@ __global__ __launch_bounds__(256) void k_t_masks(uint8_t* __restrict__ keep, siz
 static constexpr int IMG = 80, IMG_PIX = IMG * IMG;                  // crop side; every block halves it: 80 -> 40 -> 20 -> 10
 static constexpr int FC1_POS = (IMG / 8) * (IMG / 8), HID = 100;     // fc1: 100 positions x 128 channels -> 100 outputs
 static constexpr int FC1_K = 128 * FC1_POS;                          // = 12800
-// keep masks of one step: four planes back to back, [n][16] [n][64] [n][128] (Dropout2d behind block 1..3) [n][100] (Dropout behind fc1);
-// plane i starts at keep + n * KEEP_OFF[i]
-static constexpr int KEEP_OFF[4] = {0, 16, 16 + 64, 16 + 64 + 128}, KEEP_ROW = 16 + 64 + 128 + HID;
-static_assert(KEEP_ROW == 308 && FC1_K == 12800, "mask row / fc1 of the 80x80 network");
+// (keep masks of one step: four planes back to back, [n][16] [n][64] [n][128] (Dropout2d behind block 1..3) [n][100] (Dropout behind fc1);
+// plane i starts at keep + n * tt.keep_off[i]: train_tensors.h)
+static_assert(FC1_K == 12800 && T_COUNT == S_RM4 + 2, "fc1 of the 80x80 network; the slots of train_tensors.h are the blob's tensor ids");
 static constexpr int C1_BPC = IMG / 4, WG1_BPC = IMG / 8;            // workgroups per crop of k_t_conv1 (4 rows each) and k_t_wgrad1 (8 rows)
 static constexpr int RED_BLOCKS = T_RED_BLOCKS, BWD_BLOCKS = T_BWD_BLOCKS;   // grids of the reduction kernels (partials: red[BWD_BLOCKS][2][128])
 
@@ -1408,59 +1406,42 @@ struct Layer {
     int ph = 0, pw = 0;                    // the plane of z as the size-following code reads it: S x S at 80x80, the level's (h, w) of TrainAnyGeom elsewhere
 };
 
-struct Trainer {
-    trexhip_ctx* ctx = nullptr;
-    int classes = 0, CH = 1, max_n = 0;
-    int W = IMG, H = IMG;                // individual_image_size of the blob
+// The streams of a step: main = the context's, w = the side stream (main itself when the step does not fork), es = main as events name it.
+// Events go through the null stream when the caller's stream is the hipStreamLegacy handle (this runtime faults in a wait on an event
+// recorded on the handle itself; in this library the two name the same stream); the per-thread handle has no such stand-in: the step then
+// stays on the one stream
+struct Streams { hipStream_t s, w, es; bool forked; };
+
+struct Trainer : TrainerCore {
     bool any = false;                    // not 80x80: the chain of train_any.hip on the geometry below (exact fp32 whatever `precision` says)
     TrainAnyGeom geom{};
     float* hsum = nullptr;               // any: fc1's partial planes added up (k_tany_fc1_sum), what the head reads as its one plane
-    trexhip_train_params p{};
-    int64_t step = 0;
-    size_t off[T_COUNT + 1] = {}, cnt[T_COUNT] = {};
-    size_t total = 0;
-    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
     Layer L[3] = {};
     decltype(&k_t_conv1<1>) conv1 = nullptr;      // block 1's convolution and weight gradient (no MFMA) at the trainer's 1 or 3 input channels
     decltype(&k_t_wgrad1<1>) wgrad1 = nullptr;
     float *part = nullptr /*conv2's / conv3's weight-gradient partials*/, *stat = nullptr /*3 x (mean, invstd, sums[2]) x 128*/;
-    float *hpart = nullptr, *xhat = nullptr, *hd = nullptr, *dl = nullptr, *dy = nullptr, *dh = nullptr, *loss = nullptr, *out2 = nullptr;
-    int32_t* correct = nullptr;
-    int32_t* bad_target = nullptr;       // set by k_t_head when a target is outside 0..classes-1; sticky until read
+    float *hpart = nullptr, *xhat = nullptr, *hd = nullptr, *dl = nullptr, *dy = nullptr, *dh = nullptr;
     double* red = nullptr;
-    uint8_t* keep = nullptr;
-    float* x_stage = nullptr;            // host-pointer entry point: inputs, targets and injected masks staged here
-    int32_t* y_stage = nullptr;
-    uint8_t* keep_stage = nullptr;
     float* part1 = nullptr;              // conv1's weight-gradient partials (its kernels run beside the side stream's, which own `part`)
     // the training step forks: weight packing, the head's / fc1's / the convolutions' weight gradients and the loss sum run on `side`, beside the
     // chain that the next kernel waits for (data gradients, BN backward); the step joins again in front of Adam
     hipStream_t side = nullptr;
     hipEvent_t ev[EV_COUNT] = {};
+    Streams q{};                         // the streams of the step being queued (begin_step)
     bool masks_on_side = false;          // this step's keep masks are being drawn on `side` (EV_MASKS)
     double* red_bias = nullptr;          // [3][BWD_BLOCKS][128]: k_t_bn_bwd's column sums, finalized on `side`
-    Mem mem;                             // every device buffer above
-};
 
-// index inside the tensor in the kernels' layout of element `i` of the torch layout
-static size_t to_internal(int t, size_t i, int CH, size_t P /*fc1 positions, (H/8)(W/8)*/) {
-    switch (t) {
-        case T_C1W: { const size_t tap = i % 25, c = (i / 25) % CH, co = i / (25 * (size_t)CH); return (c * 25 + tap) * 16 + co; }
-        case T_C2W: { const size_t tap = i % 25, ci = (i / 25) % 16, co = i / 400; return (tap * 16 + ci) * 64 + co; }
-        case T_C3W: { const size_t tap = i % 25, ci = (i / 25) % 64, co = i / 1600; return (((ci / 32) * 25 + tap) * 32 + ci % 32) * 128 + co; }
-        case T_F1W: { const size_t K = 128 * P, k = i % K, o = i / K, c = k / P, hw = k % P; return (hw * 128 + c) * HID + o; }
-        default: return i;
+    ~Trainer() override {
+        if (side) (void)hipStreamSynchronize(side);                       // (a step joins its side stream before Adam; this is for a half-queued one)
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (side) (void)hipStreamDestroy(side);
     }
-}
-
-static void trainer_free(Trainer* t) {
-    if (!t) return;
-    if (t->side) (void)hipStreamSynchronize(t->side);                     // (a step joins its side stream before Adam; this is for a half-queued one)
-    t->mem.free_all();
-    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    if (t->side) (void)hipStreamDestroy(t->side);
-    delete t;
-}
+    const uint8_t* begin_step(hipStream_t s, int n, const uint8_t* injected) override;
+    void forward(hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, bool train, float* probs) override;
+    void backward(hipStream_t s, const float* x, int n, const uint8_t* keep) override;
+    size_t blob_bytes() const override { return weight_blob_bytes(classes, CH, W, H); }
+    void write_blob_header(void* blob) const override { write_weight_blob_header(blob, classes, W, H, CH); }
+};
 
 // every kernel instance of the table that needs more dynamic LDS than the default limit
 static int trainer_attrs(Trainer* t) {
@@ -1476,7 +1457,7 @@ static int trainer_attrs(Trainer* t) {
 // over z when there are none) + dropout masks; eval: running statistics (the caller's masks keep everything)
 static void bn_forward(Trainer* t, hipStream_t s, const Layer& L, int n, const uint8_t* keep, float scale, bool train, int partials) {
     float* P = t->P;
-    const size_t* o = t->off;
+    const size_t* o = t->tt.off;
     float* mean = t->stat + L.slot * 512;
     float* invstd = mean + 128;
     if (train) {
@@ -1496,7 +1477,7 @@ static void bn_forward(Trainer* t, hipStream_t s, const Layer& L, int n, const u
 // da (pooled gradient) -> dz written over z; gradients of gamma and beta.  Returns the grid of k_t_bn_bwd, whose column sums bias_finalize adds
 static int bn_backward(Trainer* t, hipStream_t s, const Layer& L, int n, const uint8_t* keep, float scale) {
     float* P = t->P;
-    const size_t* o = t->off;
+    const size_t* o = t->tt.off;
     float* mean = t->stat + L.slot * 512;
     float* invstd = mean + 128;
     float* sums = mean + 256;
@@ -1519,14 +1500,9 @@ static int bn_backward(Trainer* t, hipStream_t s, const Layer& L, int n, const u
 // the convolution bias's gradient from k_t_bn_bwd's column sums (nothing but Adam waits for it: the caller puts it on the side stream)
 static void bias_finalize(Trainer* t, hipStream_t w, const Layer& L, int nb) {
     hipLaunchKernelGGL((k_t_red_finalize<FIN_BIAS>), dim3(L.C), dim3(256), 0, w, t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128, nb, L.C,
-                       FinArgs{0.0, 0.f, t->G + t->off[L.b], nullptr, nullptr, nullptr, nullptr});
+                       FinArgs{0.0, 0.f, t->G + t->tt.off[L.b], nullptr, nullptr, nullptr, nullptr});
 }
 
-// The streams of a step: main = the context's, w = the side stream (main itself when the step does not fork), es = main as events name it.
-// Events go through the null stream when the caller's stream is the hipStreamLegacy handle (this runtime faults in a wait on an event
-// recorded on the handle itself; in this library the two name the same stream); the per-thread handle has no such stand-in: the step then
-// stays on the one stream
-struct Streams { hipStream_t s, w, es; bool forked; };
 static void fork(Trainer* t, const Streams& q, int e) {
     if (q.forked) { (void)hipEventRecord(t->ev[e], q.es); (void)hipStreamWaitEvent(q.w, t->ev[e], 0); }
 }
@@ -1543,46 +1519,32 @@ static void block_backward(Trainer* t, const Streams& q, const Layer& L, int n, 
     if (t->any) {
         const int shares = t->geom.wg_shares(L.slot, n);
         tany_wgrad(q.w, t->geom, L.slot, n, below.a, L.z, t->part);
-        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w], 25);
-        hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * L.dgrad.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, L.dgrad.co, L.dgrad.cic, L.wb, 25);
+        hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->tt.off[L.w], 25);
+        hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * L.dgrad.co + 255) / 256), dim3(256), 0, q.s, t->P + t->tt.off[L.w], L.CI, L.C, L.fwd.cic, L.dgrad.co, L.dgrad.cic, L.wb, 25);
         tany_conv_dgrad(q.s, t->geom, L.slot, n, L.z, L.wb, below.da);
         return;
     }
     const WgradKernel& g = L.wgrad;
     const int shares = std::min(n * g.units, g.max_shares);
     hipLaunchKernelGGL(g.fn, dim3(g.types, shares), dim3(g.threads), g.lds, q.w, below.a, L.z, t->part, n);
-    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->off[L.w], 25);
+    hipLaunchKernelGGL(k_t_wgrad_reduce, dim3((25 * L.CI * L.C + 255) / 256), dim3(256), 0, q.w, t->part, shares, L.CI, L.C, L.fwd.cic, t->G + t->tt.off[L.w], 25);
     // the data gradient: the same convolution on flipped + transposed weights
     const ConvKernel& k = L.dgrad;
-    if (!k.h2) hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * k.co + 255) / 256), dim3(256), 0, q.s, t->P + t->off[L.w], L.CI, L.C, L.fwd.cic, k.co, k.cic, L.wb, 25);
+    if (!k.h2) hipLaunchKernelGGL(k_t_repack_bwd, dim3((25 * L.C * k.co + 255) / 256), dim3(256), 0, q.s, t->P + t->tt.off[L.w], L.CI, L.C, L.fwd.cic, k.co, k.cic, L.wb, 25);
     if (k.h2) hipLaunchKernelGGL(k.h2, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wh_b, nullptr, below.da, L.wh_scale, nullptr);
     else if (k.f32_n16) hipLaunchKernelGGL(k.f32_n16, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wb, below.da);
     else hipLaunchKernelGGL(k.f32, dim3(n * k.bpc), dim3(512), k.lds, q.s, L.z, L.wb, nullptr, below.da);
 }
 
-// steps with a target outside 0..classes-1 were refused on the device (k_t_check_targets) and have changed nothing: report them at the next
-// synchronising call, take them back out of the step count (Adam's bias correction, the dropout counter) and go on
-static int check_targets(Trainer* t) {
-    int32_t bad[2] = {0, 0};
-    TH_CHECK_HIP(hipMemcpy(bad, t->bad_target, 8, hipMemcpyDeviceToHost));
-    if (bad[0] || bad[1]) {
-        TH_CHECK_HIP(hipMemset(t->bad_target, 0, 8));
-        if (bad[0]) t->step -= bad[0];
-        set_error(bad[0] ? std::string("training step: a target class index was outside 0..classes-1; that step (and the ") + std::to_string(bad[0] - 1) +
-                               " queued behind it) was refused, parameters, moments and running statistics are unchanged"
-                         : std::string("evaluation batch: a target class index was outside 0..classes-1"));
-        return TREXHIP_E_INVALID;
-    }
-    return TREXHIP_OK;
-}
-
 // forward pass up to the per-sample loss / arg-max (and, as a by-product of k_t_head, the gradient at the fc1 output).  train = batch
 // statistics + dropout masks `keep`; eval = running statistics, nothing dropped (model.eval(), visual_recognition_torch.py:1171-1185).
 // probs (eval only): the head writes the softmax rows there and nothing else (k_t_head_eval)
-static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, float scale, bool train,
-                            hipStream_t side = nullptr, float* probs = nullptr) {
+void Trainer::forward(hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, bool train, float* probs) {
+    Trainer* t = this;
+    const float scale = train ? 1.0f / (1.0f - p.dropout) : 1.0f;
+    hipStream_t side = train && q.forked ? q.w : nullptr;             // a training step packs its weights beside conv1
     float* P = t->P;
-    const size_t* o = t->off;
+    const size_t* o = t->tt.off;
     const Layer* L = t->L;
     const bool h2 = t->p.precision == 0 && !t->any;
     hipStream_t es = s == hipStreamLegacy ? nullptr : s;
@@ -1612,75 +1574,32 @@ static void trainer_forward(Trainer* t, hipStream_t s, const float* x, const int
         hipLaunchKernelGGL(t->any ? &k_t_head_eval<1> : &k_t_head_eval<FC1_POS>, dim3(n), dim3(128), 0, s, planes, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], P + o[T_F2W], P + o[T_F2B], t->classes, probs);
         return;
     }
-    hipLaunchKernelGGL(t->any ? &k_t_head<1> : &k_t_head<FC1_POS>, dim3(n), dim3(128), 0, s, planes, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], keep + (size_t)n * KEEP_OFF[3], scale, P + o[T_F2W],
+    hipLaunchKernelGGL(t->any ? &k_t_head<1> : &k_t_head<FC1_POS>, dim3(n), dim3(128), 0, s, planes, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], keep + (size_t)n * tt.keep_off[3], scale, P + o[T_F2W],
                        P + o[T_F2B], targets, t->classes, t->xhat, t->hd, t->dl, t->dy, t->dh, t->loss, t->correct, t->bad_target);
 }
 
-// the loss and the correct count of the batch just queued, to the host (synchronises), and what the device refused
-static int fetch_loss(Trainer* t, hipStream_t s, float* h_loss, int32_t* h_correct) {
-    float two[2];
-    TH_CHECK_HIP(hipMemcpyAsync(two, t->out2, sizeof(two), hipMemcpyDeviceToHost, s));
-    TH_CHECK_HIP(hipStreamSynchronize(s));
-    if (h_loss) *h_loss = two[0];
-    if (h_correct) *h_correct = (int32_t)two[1];
-    return check_targets(t);
+// a step starts by forking: the side stream waits for whatever wrote the parameters last, then draws the masks beside conv1
+const uint8_t* Trainer::begin_step(hipStream_t s, int n, const uint8_t* injected) {
+    const bool forked = s != hipStreamPerThread;
+    q = Streams{s, forked ? side : s, s == hipStreamLegacy ? nullptr : s, forked};
+    fork(this, q, EV_PARAMS);
+    masks_on_side = forked && !injected;
+    if (injected) return injected;
+    const size_t count = (size_t)n * tt.keep_row;
+    hipLaunchKernelGGL(k_t_masks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, q.w, keep, count, p.seed, (uint64_t)step, p.dropout);
+    if (forked) (void)hipEventRecord(ev[EV_MASKS], q.w);
+    return keep;
 }
 
-// model.eval() forward + mean cross entropy + arg-max count of one validation batch (train(), :1171-1190); changes nothing in the trainer
-static int trainer_eval(Trainer* t, const float* x, const int32_t* targets, int n, float* h_loss, int32_t* h_correct) {
-    trexhip_ctx* ctx = t->ctx;
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    hipStream_t s = ctx->stream;
-    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)n * KEEP_ROW, s));                 // nothing dropped
-    hipLaunchKernelGGL(k_t_check_targets, dim3(1), dim3(256), 0, s, targets, n, t->classes, t->bad_target, 1);
-    trainer_forward(t, s, x, targets, n, t->keep, 1.0f, false);
-    hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, s, t->loss, t->correct, n, t->out2);
-    TH_CHECK_HIP(hipGetLastError());
-    return fetch_loss(t, s, h_loss, h_correct);
-}
-
-// softmax rows of any number of uint8 crops from the weights as they stand (predict_numpy in model.eval(), visual_recognition_torch.py:406-451):
-// chunks of at most max_batch through the trainer's own buffers -- bytes -> float32 in x_stage (k_augment's plain path), the eval forward,
-// k_t_head_eval -- all on the context's stream, no synchronisation.  Parameters, moments, running statistics and the step count stay as they are
-static int trainer_predict(Trainer* t, const uint8_t* d_crops, int n, float* d_probs) {
-    trexhip_ctx* ctx = t->ctx;
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    hipStream_t s = ctx->stream;
-    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)std::min(n, t->max_n) * KEEP_ROW, s));       // nothing dropped
-    for (int at = 0; at < n; at += t->max_n) {
-        const int m = std::min(t->max_n, n - at);
-        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * t->H * t->W * t->CH, nullptr, m, nullptr, m, t->W, t->H, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
-        if (rc != TREXHIP_OK) return rc;
-        trainer_forward(t, s, t->x_stage, nullptr, m, t->keep, 1.0f, false, nullptr, d_probs + (size_t)at * t->classes);
-    }
-    TH_CHECK_HIP(hipGetLastError());
-    return TREXHIP_OK;
-}
-
-static int trainer_step(Trainer* t, const float* x, const int32_t* targets, int n, const uint8_t* d_keep, float* h_loss, int32_t* h_correct) {
-    trexhip_ctx* ctx = t->ctx;
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    hipStream_t s = ctx->stream;
-    const float scale = 1.0f / (1.0f - t->p.dropout);
-    const uint8_t* keep = d_keep;
+void Trainer::backward(hipStream_t s, const float* x, int n, const uint8_t* keep) {
+    Trainer* t = this;
+    const float scale = 1.0f / (1.0f - p.dropout);
     float* P = t->P;
     float* G = t->G;
-    const size_t* o = t->off;
-    const bool forked = s != hipStreamPerThread;
-    const Streams q{s, forked ? t->side : s, s == hipStreamLegacy ? nullptr : s, forked};
+    const size_t* o = tt.off;
+    const bool forked = q.forked;
     hipStream_t w = q.w;
-    fork(t, q, EV_PARAMS);
-    t->masks_on_side = forked && !keep;
-    if (!keep) {
-        const size_t count = (size_t)n * KEEP_ROW;
-        hipLaunchKernelGGL(k_t_masks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, w, t->keep, count, t->p.seed, (uint64_t)t->step, t->p.dropout);
-        if (forked) (void)hipEventRecord(t->ev[EV_MASKS], w);
-        keep = t->keep;
-    }
-    hipLaunchKernelGGL(k_t_check_targets, dim3(1), dim3(256), 0, s, targets, n, t->classes, t->bad_target, 0);
-    trainer_forward(t, s, x, targets, n, keep, scale, true, forked ? w : nullptr);
     fork(t, q, EV_FORWARD);
-    // ---- backward
     {
         const int cnt = t->classes * HID + t->classes + 3 * HID;
         hipLaunchKernelGGL(k_t_head_grads, dim3((cnt + 255) / 256), dim3(256), 0, w, t->dl, t->hd, t->dy, t->xhat, t->dh, n, t->classes, G + o[T_F2W], G + o[T_F2B],
@@ -1697,21 +1616,10 @@ static int trainer_step(Trainer* t, const float* x, const int32_t* targets, int 
     else hipLaunchKernelGGL(t->wgrad1, dim3(n * WG1_BPC), dim3(512), 0, s, x, t->L[0].z, t->part1);
     hipLaunchKernelGGL(k_t_reduce, dim3((t->CH * 400 + 15) / 16), dim3(256), 0, s, t->part1, n * (t->any ? t->geom.wg1_tiles : WG1_BPC), t->CH * 400, G + o[T_C1W]);
     if (forked) (void)hipStreamWaitEvent(q.es, t->ev[EV_SIDE_DONE], 0);     // join: every gradient is in G
-    // ---- optimizer
-    t->step += 1;
-    {
-        uint32_t lo[6], hi[6];
-        int k = 0;
-        for (const Layer& L : t->L)
-            for (int buf : {L.rm, L.rv}) { lo[k] = (uint32_t)o[buf]; hi[k] = (uint32_t)(o[buf] + t->cnt[buf]); ++k; }
-        t_adam(s, P, G, t->M, t->V, t->total, lo, hi, 6, t->p.lr, t->p.beta1, t->p.beta2, t->p.eps, t->step, t->bad_target);
-    }
-    TH_CHECK_HIP(hipGetLastError());
-    return h_loss || h_correct ? fetch_loss(t, s, h_loss, h_correct) : TREXHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// train_shared.h: the size-independent kernels as train_arch.hip launches them
+// train_host.h: the size-independent kernels as the core (train_host.hip) and the one-stream chain (train_arch.hip) launch them
 // ------------------------------------------------------------------------------------------------
 void t_bn_stats(hipStream_t s, int C, const float* d, size_t rows, double* partial) {
     const auto fn = C == 16 ? &k_t_bn_stats<16> : C == 64 ? &k_t_bn_stats<64> : &k_t_bn_stats<128>;
@@ -1757,50 +1665,8 @@ void t_loss(hipStream_t s, const float* loss, const int32_t* correct, int n, flo
     hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, s, loss, correct, n, out2);
 }
 
-}  // namespace trexhip
-
-// a trainer is one of three: V118_3 (t, this file), v100 / v110 (a, train_arch.hip) or the category network (c, train_cat.hip); every entry point
-// below looks at `c` and `a` first
-struct trexhip_trainer { trexhip::Trainer* t; trexhip::ArchTrainer* a = nullptr; trexhip::CatTrainer* c = nullptr; };
-
-extern "C" {
-
-using namespace trexhip;
-
-// what trexhip_trainer_create asks of its parameters, whatever the network
-static int check_train_params(const trexhip_train_params* p) {
-    if (p->max_batch < 1 || p->max_batch > 4096) { set_error("trexhip_trainer_create: max_batch must be 1..4096"); return TREXHIP_E_INVALID; }
-    if (p->precision != 0 && p->precision != 1) { set_error("trexhip_trainer_create: precision must be 0 (fp16 two-piece split convolutions) or 1 (exact fp32 MFMA)"); return TREXHIP_E_INVALID; }
-    if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f) || !(p->eps > 0.f) ||
-        !(p->dropout >= 0.f && p->dropout < 1.f) || !(p->bn_momentum >= 0.f && p->bn_momentum <= 1.f)) {
-        set_error("trexhip_trainer_create: lr > 0, 0 <= beta < 1, eps > 0, 0 <= dropout < 1, 0 <= bn_momentum <= 1 are required");
-        return TREXHIP_E_INVALID;
-    }
-    return TREXHIP_OK;
-}
-
-size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) {
-    return weight_blob_bytes(classes, channels, IMG, IMG);
-}
-
-int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, trexhip_trainer** out) {
-    if (!ctx || !blob || !p || !out) { set_error("trexhip_trainer_create: null argument"); return TREXHIP_E_INVALID; }
-    *out = nullptr;
-    if (blob_is_category(blob, bytes)) {                              // the parser of trexhip_categorize_load_weights, the chain of train_cat.hip
-        if (const int rc = check_train_params(p)) return rc;
-        CatTrainer* c = nullptr;
-        if (const int rc = cat_trainer_create(ctx, blob, bytes, p, &c)) return rc;
-        *out = new trexhip_trainer{nullptr, nullptr, c};
-        return TREXHIP_OK;
-    }
-    const int arch = blob_arch_id(blob, bytes);
-    if (arch == TREXHIP_NET_V100 || arch == TREXHIP_NET_V110) {       // the parser of trexhip_load_weights, the chain of train_arch.hip
-        if (const int rc = check_train_params(p)) return rc;
-        ArchTrainer* a = nullptr;
-        if (const int rc = arch_trainer_create(ctx, blob, bytes, p, &a)) return rc;
-        *out = new trexhip_trainer{nullptr, a};
-        return TREXHIP_OK;
-    }
+// a V118_3 blob (parse_weight_blob refuses every other identity network: none of those trains here)
+int v118_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, TrainerCore** out) {
     WeightBlob wb;
     const int prc = parse_weight_blob(blob, bytes, "trexhip_trainer_create", &wb, [](int W, int H) -> int {
         if (W < 8 || W > 256 || H < 8 || H > 256) {               // the range of trexhip_load_weights
@@ -1814,25 +1680,20 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     if (const int rc = check_train_params(p)) return rc;
     if (hipSetDevice(ctx->p.device) != hipSuccess) { set_error("trexhip_trainer_create: hipSetDevice failed"); return TREXHIP_E_DEVICE; }
     Trainer* t = new Trainer();
-    t->ctx = ctx; t->classes = classes; t->CH = CH; t->max_n = p->max_batch; t->p = *p;
+    t->ctx = ctx; t->version = TREXHIP_NET_V118_3; t->classes = classes; t->CH = CH; t->max_n = p->max_batch; t->p = *p;
     t->W = wb.W; t->H = wb.H;
+    t->tt = train_tensors(TRAIN_V118_3, wb.W, wb.H, CH, classes);
     t->any = wb.W != IMG || wb.H != IMG;
     t->geom = train_any_geom(wb.W, wb.H, CH);
-    size_t at = 0;
-    for (int k = 0; k < T_COUNT; ++k) {
-        t->off[k] = at; t->cnt[k] = weight_tensor_count(k, classes, CH, t->W, t->H);
-        at += (t->cnt[k] + 63) / 64 * 64;
-    }
-    t->off[T_COUNT] = at; t->total = at;
     // ---- the three blocks and their kernel instances.  The convolutions' precision is chosen here, once per role
     const bool h2 = p->precision == 0 && !t->any;      // every other size runs the exact-fp32 chain at both precisions
     Layer* L = t->L;
     // (k_t_bn_stats<16> is never launched by this chain: conv1 always leaves its column sums.  It stays instantiated because the compiler lays out the epilogue
     // of k_t_pool_bwd_stats<16>, which shares block_columns<16, 2> with it, in another order without it)
     //      C    CI  S        weight bias   gamma beta   running mean / variance  dz event  slot  masks    BN kernels
-    L[0] = {16,  CH, IMG,     T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, KEEP_OFF[0], &k_t_bn_stats<16>, &k_t_bn_pool<16>, &k_t_pool_bwd_stats<16>, &k_t_bn_bwd<16>};
-    L[1] = {64,  16, IMG / 2, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, EV_DZ2, 1, KEEP_OFF[1], &k_t_bn_stats<64>, &k_t_bn_pool<64>, &k_t_pool_bwd_stats<64>, &k_t_bn_bwd<64>};
-    L[2] = {128, 64, IMG / 4, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3, EV_DZ3, 2, KEEP_OFF[2], &k_t_bn_stats<128>, &k_t_bn_pool<128>, &k_t_pool_bwd_stats<128>, &k_t_bn_bwd<128>};
+    L[0] = {16,  CH, IMG,     T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, (int)t->tt.keep_off[0], &k_t_bn_stats<16>, &k_t_bn_pool<16>, &k_t_pool_bwd_stats<16>, &k_t_bn_bwd<16>};
+    L[1] = {64,  16, IMG / 2, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, EV_DZ2, 1, (int)t->tt.keep_off[1], &k_t_bn_stats<64>, &k_t_bn_pool<64>, &k_t_pool_bwd_stats<64>, &k_t_bn_bwd<64>};
+    L[2] = {128, 64, IMG / 4, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3, EV_DZ3, 2, (int)t->tt.keep_off[2], &k_t_bn_stats<128>, &k_t_bn_pool<128>, &k_t_pool_bwd_stats<128>, &k_t_bn_bwd<128>};
     for (int i = 0; i < 3; ++i) { L[i].ph = t->any ? t->geom.L[i].h : L[i].S; L[i].pw = t->any ? t->geom.L[i].w : L[i].S; }
     if (t->any) {
         // the generic chain (train_any.hip): the BN / pool kernels, the convolutions' three roles and fc1 follow t->geom; what the shared kernels
@@ -1861,7 +1722,6 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     int rc = TREXHIP_OK;
     const char* who = "trexhip_trainer_create";
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
-    TRY(t->mem.device(&t->P, at, who)); TRY(t->mem.device(&t->G, at, who)); TRY(t->mem.device(&t->M, at, who)); TRY(t->mem.device(&t->V, at, who));
     size_t part_floats = t->any ? t->geom.part_floats() : 0;
     for (int i = 0; i < 3; ++i) {
         const size_t act = n * L[i].ph * L[i].pw * L[i].C;                      // z; pooled: a quarter of it at 80x80, the floored plane elsewhere
@@ -1881,169 +1741,19 @@ int trexhip_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, con
     TRY(t->mem.device(&t->stat, (size_t)3 * 512, who));
     TRY(t->mem.device(&t->hpart, n * t->geom.P * HID, who)); if (t->any) TRY(t->mem.device(&t->hsum, n * HID, who)); TRY(t->mem.device(&t->xhat, n * HID, who)); TRY(t->mem.device(&t->hd, n * HID, who));
     TRY(t->mem.device(&t->dl, n * classes, who)); TRY(t->mem.device(&t->dy, n * HID, who)); TRY(t->mem.device(&t->dh, n * HID, who));
-    TRY(t->mem.device(&t->loss, n, who)); TRY(t->mem.device(&t->correct, n, who)); TRY(t->mem.device(&t->out2, 2, who)); TRY(t->mem.device(&t->bad_target, 2, who));
     TRY(t->mem.device(&t->red, std::max((size_t)BWD_BLOCKS * 2 * 128, n * 640), who));   // conv1 leaves 20 n x 2 x 16 partials, conv2 / conv3 2 n x 2 x C
-    TRY(t->mem.device(&t->keep, n * KEEP_ROW, who));
-    TRY(t->mem.device(&t->x_stage, n * t->H * t->W * CH, who)); TRY(t->mem.device(&t->y_stage, n, who)); TRY(t->mem.device(&t->keep_stage, n * KEEP_ROW, who));
     if (rc == TREXHIP_OK && hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess) { set_error("trexhip_trainer_create: no second stream"); rc = TREXHIP_E_DEVICE; }
     for (hipEvent_t& e : t->ev)
         if (rc == TREXHIP_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("trexhip_trainer_create: no event"); rc = TREXHIP_E_DEVICE; }
     TRY(trainer_attrs(t));
     if (t->any) TRY(tany_attrs());
+    TRY(t->init_state(wb.t, who));
 #undef TRY
-    if (rc != TREXHIP_OK) { trainer_free(t); return rc; }
-    std::vector<float> host(at, 0.f);
-    for (int k = 0; k < T_COUNT; ++k)
-        for (size_t i = 0; i < t->cnt[k]; ++i) host[t->off[k] + to_internal(k, i, CH, (size_t)(t->H / 8) * (t->W / 8))] = wb.t[k][i];
-    bool ok = hipMemcpy(t->P, host.data(), at * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemset(t->bad_target, 0, 8) == hipSuccess;
-    ok = ok && hipMemset(t->G, 0, at * 4) == hipSuccess && hipMemset(t->M, 0, at * 4) == hipSuccess && hipMemset(t->V, 0, at * 4) == hipSuccess;
-    if (!ok) { trainer_free(t); set_error("trexhip_trainer_create: upload failed"); return TREXHIP_E_DEVICE; }
-    trexhip_trainer* h = new trexhip_trainer{t};
-    *out = h;
+    if (rc != TREXHIP_OK) { delete t; return rc; }
+    *out = t;
     return TREXHIP_OK;
 }
 
-void trexhip_trainer_destroy(trexhip_trainer* h) {
-    if (!h) return;
-    if (h->c) cat_trainer_destroy(h->c);
-    if (h->a) arch_trainer_destroy(h->a);
-    if (h->t) { (void)hipSetDevice(h->t->ctx->p.device); (void)hipStreamSynchronize(h->t->ctx->stream); trainer_free(h->t); }
-    delete h;
-}
+}  // namespace trexhip
 
-int trexhip_trainer_set_lr(trexhip_trainer* h, float lr) {
-    if (!h || !(lr > 0.f)) { set_error("trexhip_trainer_set_lr: a trainer and lr > 0 are required"); return TREXHIP_E_INVALID; }
-    if (h->c) cat_trainer_set_lr(h->c, lr);
-    else if (h->a) arch_trainer_set_lr(h->a, lr);
-    else h->t->p.lr = lr;
-    return TREXHIP_OK;
-}
-
-int64_t trexhip_trainer_steps(trexhip_trainer* h) { return !h ? -1 : h->c ? cat_trainer_steps(h->c) : h->a ? arch_trainer_steps(h->a) : h->t->step; }
-
-int trexhip_trainer_image_size(trexhip_trainer* h, int32_t* width, int32_t* height) {
-    if (!h || !width || !height) { set_error("trexhip_trainer_image_size: null argument"); return TREXHIP_E_INVALID; }
-    if (h->c) cat_trainer_info(h->c, width, height, nullptr);
-    else if (h->a) arch_trainer_info(h->a, width, height, nullptr, nullptr);
-    else { *width = h->t->W; *height = h->t->H; }
-    return TREXHIP_OK;
-}
-
-int trexhip_trainer_version(trexhip_trainer* h, int32_t* version) {
-    if (!h || !version) { set_error("trexhip_trainer_version: null argument"); return TREXHIP_E_INVALID; }
-    *version = TREXHIP_NET_V118_3;
-    if (h->c) *version = TREXHIP_NET_CATEGORY;
-    else if (h->a) arch_trainer_info(h->a, nullptr, nullptr, version, nullptr);
-    return TREXHIP_OK;
-}
-
-size_t trexhip_trainer_keep_mask_bytes(trexhip_trainer* h, int32_t n) {
-    if (!h || n < 0) return 0;
-    return h->c ? cat_trainer_keep_mask_bytes(h->c, n) : h->a ? arch_trainer_keep_mask_bytes(n) : (size_t)n * KEEP_ROW;
-}
-
-// what every batch entry point checks first: the handle, its two pointers, 1 <= n <= max_batch (any_n: no upper bound, the call chunks)
-static int check_batch(const char* who, const trexhip_trainer* h, const void* a, const void* b, int n, bool any_n = false) {
-    if (!h || !a || !b) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
-    int32_t max_n = 0;
-    if (h->c) cat_trainer_info(h->c, nullptr, nullptr, &max_n);
-    else if (h->a) arch_trainer_info(h->a, nullptr, nullptr, nullptr, &max_n);
-    else max_n = h->t->max_n;
-    if (n < 1 || (!any_n && n > max_n)) { set_error(std::string(who) + (any_n ? ": n must be at least 1" : ": n must be 1..max_batch")); return TREXHIP_E_INVALID; }
-    return TREXHIP_OK;
-}
-
-// the host-pointer entry points: the same checks, the targets' range before anything is uploaded (visual_recognition_torch.py:1112), then the
-// batch into the staging buffers on the context's stream
-static int stage_batch(const char* who, const trexhip_trainer* h, const float* inputs, const int32_t* targets, int n, const uint8_t* keep_masks) {
-    if (const int rc = check_batch(who, h, inputs, targets, n)) return rc;
-    Trainer* t = h->t;
-    for (int i = 0; i < n; ++i)
-        if (targets[i] < 0 || targets[i] >= t->classes) { set_error(std::string(who) + ": target class out of range"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    hipStream_t s = t->ctx->stream;
-    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * t->H * t->W * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
-    TH_CHECK_HIP(hipMemcpyAsync(t->y_stage, targets, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (keep_masks) TH_CHECK_HIP(hipMemcpyAsync(t->keep_stage, keep_masks, (size_t)n * KEEP_ROW, hipMemcpyHostToDevice, s));
-    return TREXHIP_OK;
-}
-
-int trexhip_train_step_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, const uint8_t* d_keep_masks, float* loss,
-                              int32_t* correct) {
-    if (const int rc = check_batch("trexhip_train_step_device", h, d_inputs, d_targets, n)) return rc;
-    if (h->c) return cat_trainer_step(h->c, false, d_inputs, d_targets, n, d_keep_masks, loss, correct);
-    if (h->a) return arch_trainer_step(h->a, false, d_inputs, d_targets, n, d_keep_masks, loss, correct);
-    return trainer_step(h->t, d_inputs, d_targets, n, d_keep_masks, loss, correct);
-}
-
-int trexhip_train_step(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, const uint8_t* keep_masks, float* loss, int32_t* correct) {
-    if (h && (h->a || h->c)) {
-        if (const int rc = check_batch("trexhip_train_step", h, inputs, targets, n)) return rc;
-        return h->c ? cat_trainer_step(h->c, true, inputs, targets, n, keep_masks, loss, correct) : arch_trainer_step(h->a, true, inputs, targets, n, keep_masks, loss, correct);
-    }
-    if (const int rc = stage_batch("trexhip_train_step", h, inputs, targets, n, keep_masks)) return rc;
-    Trainer* t = h->t;
-    if (const int rc = trainer_step(t, t->x_stage, t->y_stage, n, keep_masks ? t->keep_stage : nullptr, loss, correct)) return rc;
-    TH_CHECK_HIP(hipStreamSynchronize(t->ctx->stream));        // the caller's buffers may go away
-    return TREXHIP_OK;
-}
-
-int trexhip_train_eval_device(trexhip_trainer* h, const float* d_inputs, const int32_t* d_targets, int32_t n, float* loss, int32_t* correct) {
-    if (const int rc = check_batch("trexhip_train_eval_device", h, d_inputs, d_targets, n)) return rc;
-    if (h->c) return cat_trainer_eval(h->c, false, d_inputs, d_targets, n, loss, correct);
-    if (h->a) return arch_trainer_eval(h->a, false, d_inputs, d_targets, n, loss, correct);
-    return trainer_eval(h->t, d_inputs, d_targets, n, loss, correct);
-}
-
-int trexhip_train_predict_device(trexhip_trainer* h, const uint8_t* d_crops, int32_t n, float* d_probs) {
-    if (const int rc = check_batch("trexhip_train_predict_device", h, d_crops, d_probs, n, true)) return rc;
-    if (h->c) return cat_trainer_predict(h->c, d_crops, n, d_probs);
-    if (h->a) return arch_trainer_predict(h->a, d_crops, n, d_probs);
-    return trainer_predict(h->t, d_crops, n, d_probs);
-}
-
-int trexhip_train_eval(trexhip_trainer* h, const float* inputs, const int32_t* targets, int32_t n, float* loss, int32_t* correct) {
-    if (h && (h->a || h->c)) {
-        if (const int rc = check_batch("trexhip_train_eval", h, inputs, targets, n)) return rc;
-        return h->c ? cat_trainer_eval(h->c, true, inputs, targets, n, loss, correct) : arch_trainer_eval(h->a, true, inputs, targets, n, loss, correct);
-    }
-    if (const int rc = stage_batch("trexhip_train_eval", h, inputs, targets, n, nullptr)) return rc;
-    return trainer_eval(h->t, h->t->x_stage, h->t->y_stage, n, loss, correct);
-}
-
-int trexhip_trainer_read(trexhip_trainer* h, int32_t tensor, int32_t kind, float* out, size_t count) {
-    if (h && h->c) return cat_trainer_read(h->c, tensor, kind, out, count);
-    if (h && h->a) return arch_trainer_read(h->a, tensor, kind, out, count);
-    if (!h || !out || tensor < 0 || tensor >= T_COUNT || kind < 0 || kind > 3) { set_error("trexhip_trainer_read: bad argument"); return TREXHIP_E_INVALID; }
-    Trainer* t = h->t;
-    if (count != t->cnt[tensor]) { set_error("trexhip_trainer_read: count does not match the tensor"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    TH_CHECK_HIP(hipStreamSynchronize(t->ctx->stream));
-    { const int rc = check_targets(t); if (rc != TREXHIP_OK) return rc; }
-    const float* src = kind == 0 ? t->P : kind == 1 ? t->G : kind == 2 ? t->M : t->V;
-    std::vector<float> tmp(count);
-    TH_CHECK_HIP(hipMemcpy(tmp.data(), src + t->off[tensor], count * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < count; ++i) out[i] = tmp[to_internal(tensor, i, t->CH, (size_t)(t->H / 8) * (t->W / 8))];
-    return TREXHIP_OK;
-}
-
-int trexhip_trainer_export(trexhip_trainer* h, void* blob, size_t capacity, size_t* bytes) {
-    if (!h || !blob) { set_error("trexhip_trainer_export: null argument"); return TREXHIP_E_INVALID; }
-    if (h->c) return cat_trainer_export(h->c, blob, capacity, bytes);
-    if (h->a) return arch_trainer_export(h->a, blob, capacity, bytes);
-    Trainer* t = h->t;
-    const size_t need = weight_blob_bytes(t->classes, t->CH, t->W, t->H);
-    if (bytes) *bytes = need;
-    if (capacity < need) { set_error("trexhip_trainer_export: buffer too small (the bytes of the blob the trainer was created from)"); return TREXHIP_E_CAPACITY; }
-    write_weight_blob_header(blob, t->classes, t->W, t->H, t->CH);
-    float* dst = reinterpret_cast<float*>(static_cast<char*>(blob) + 32);
-    for (int k = 0; k < T_COUNT; ++k) {
-        const int rc = trexhip_trainer_read(h, k, 0, dst, t->cnt[k]);
-        if (rc != TREXHIP_OK) return rc;
-        dst += t->cnt[k];
-    }
-    return TREXHIP_OK;
-}
-
-}  // extern "C"
+extern "C" size_t trexhip_weight_blob_bytes(int32_t classes, int32_t channels) { return trexhip::weight_blob_bytes(classes, channels, trexhip::IMG, trexhip::IMG); }

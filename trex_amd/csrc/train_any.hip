@@ -2,7 +2,7 @@
 // kernels there, as cnn.hip does beside cnn_any.hip).  W, H = 8..256 at run time, square or not, CH = 1 or 3, NHWC fp32 throughout, exact
 // fp32 arithmetic (both values of trexhip_train_params.precision).  Every pool floors like nn.MaxPool2d(2).
 //
-// The tap count of every convolution kernel is a template parameter: 5 (V118_3, v100, v110) or 3 (the category network, train_cat.hip), whose conv1
+// The tap count of every convolution kernel is a template parameter: 5 (V118_3, v100, v110) or 3 (the category network, train_arch.hip), whose conv1
 // pair also normalises its input and whose block kernels read element-wise dropout masks.
 //
 //   k_tany_conv1       CH -> 16 on the VALU, raw output + bias: one workgroup per (crop, 16 x 16 pixels), patch in LDS

@@ -1,12 +1,21 @@
-// train_arch.hip -- the training step of the identity networks v100 and v110 (visual_identification_network_torch.py:262-382, train mode;
-// the loop body visual_recognition_torch.py:1137-1158) at every size they load: W, H = 8..256, CH = 1 or 3, NHWC fp32, exact fp32 arithmetic at
-// both values of trexhip_train_params.precision.
+// train_arch.hip -- the training step of the networks that run the generic chain on one stream: the identity networks v100 and v110
+// (visual_identification_network_torch.py:262-382, train mode; the loop body visual_recognition_torch.py:1137-1158) and the category network
+// (trex_learn_category.py:18-44, PyTorchModel, in train mode; the loop body :314-332 on a non-CUDA device: fp32 arithmetic.  On `cuda` the reference
+// adds autocast and a GradScaler; that arithmetic is not restated), at every size they load: W, H = 8..256, CH = 1 or 3, NHWC fp32, exact fp32
+// arithmetic at both values of trexhip_train_params.precision.
 //
-//   v100   [conv5x5 'same' -> ReLU -> MaxPool2 -> Dropout2d(0.25)] x3 -> flatten (NCHW) -> fc1 -> ReLU -> Dropout(0.5) -> fc2 -> cross entropy
-//   v110   [conv5x5 'same' -> MaxPool2 -> BatchNorm2d -> ReLU -> Dropout2d(0.25)] x3 -> flatten -> fc1 -> BatchNorm1d -> ReLU -> Dropout(0.25) -> fc2
+//   v100      [conv5x5 'same' -> ReLU -> MaxPool2 -> Dropout2d(0.25)] x3 -> flatten (NCHW) -> fc1 -> ReLU -> Dropout(0.5) -> fc2 -> cross entropy
+//   v110      [conv5x5 'same' -> MaxPool2 -> BatchNorm2d -> ReLU -> Dropout2d(0.25)] x3 -> flatten -> fc1 -> BatchNorm1d -> ReLU -> Dropout(0.25) -> fc2
+//   category  x = byte / 127.5 - 1, zero padded -> [conv3x3 pad 1 -> BatchNorm2d -> ReLU -> MaxPool2 -> Dropout(0.25)] x3 (16, 64, 100 channels)
+//             -> flatten -> fc1 (100) -> ReLU -> Dropout(0.25) -> fc2 (categories); nn.Dropout on [n][C][h/2][w/2]: ELEMENT-wise keep masks
 //
+// One trainer type, ChainTrainer (the host side at the end of this file), runs all three: it derives from TrainerCore (train_host.h) and a network is
+// a row of data plus the functions of its block kind and its head.  The category network adds no kernel: its blocks are train_any.hip's block kernels
+// (tany_bn_pool, tany_pool_bwd_stats, tany_bn_bwd) with `creal`, its convolutions the 3-tap mode of the same chain, its head v100's; BatchNorm's
+// statistics run over all n h w pixels of the convolution's plane, the odd last row and column included, and block 3's plane has at least 2 x 2 pixels
+// at every legal size, so n = 1 trains.
 // The convolutions are V118_3's with conv3 at 100 outputs instead of 128, so the three roles of every convolution, both conv1 kernels and fc1 are
-// train_any.hip's (tany_*), and the reductions, Adam, the masks, the target check and the loss sum train.hip's (train_shared.h).  The 100 channels
+// train_any.hip's (tany_*), and the reductions, Adam, the masks, the target check and the loss sum train.hip's (t_*, train_host.h).  The 100 channels
 // travel padded to 128 in z3, a3, their gradients and the packed images of conv3.weight and fc1.weight; every per-channel tensor of block 3 has
 // 128 slots.  A padded slot holds 0 and stays 0: its weights and bias are 0, so z = 0; the kernels below give a channel >= 100 the activation 0
 // and the gradient 0 whatever its slots hold, so the weight gradients' padded columns and fc1's padded rows are sums of zeros, and Adam's update of
@@ -27,7 +36,7 @@
 #include "cnn_weights.h"
 #include "train_dev.h"
 #include "train_any.h"
-#include "train_shared.h"
+#include "train_host.h"
 #include "train_arch.h"
 #include <algorithm>
 #include <cmath>
@@ -40,12 +49,6 @@ namespace {
 
 constexpr float EPS_BN = 1e-5f;
 constexpr int HID = TA_HID;
-constexpr int CP[3] = {16, 64, 128};                     // channels of a block as the kernels see them
-constexpr int CR[3] = {16, 64, 100};                     // ... and as torch does
-// keep masks of one step: four planes back to back, [n][16] [n][64] [n][100] [n][100]; plane i starts at keep + n * KEEP_OFF[i]
-constexpr int KEEP_OFF[4] = {0, 16, 16 + 64, 16 + 64 + 100}, KEEP_ROW = 16 + 64 + 100 + HID;
-// the architecture's dropout rates (trexhip_train_params.dropout is V118_3's)
-constexpr float P_DROP[2][4] = {{0.25f, 0.25f, 0.25f, 0.5f}, {0.25f, 0.25f, 0.25f, 0.25f}};
 
 // the BatchNorm output of one element, the one expression forward and backward share (the ReLU gate is [y > 0] of this value on both ways)
 __device__ __forceinline__ float bn_y(const float xhat, const float gamma, const float beta) { return xhat * gamma + beta; }
@@ -399,12 +402,9 @@ __global__ __launch_bounds__(256) void k_tarch_head_grads(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side: one trainer for the three networks of the one-stream chain.  A network is data (Net, and its tensors: train_tensors.h) plus the two
+// functions of its block kind and its head, chosen once in chain_trainer_create; the walk below is the same for all of them
 // ------------------------------------------------------------------------------------------------
-// the tensors as the trainer holds them: six slots per block (weight, bias, gamma, beta, running mean, running variance), then the head's
-enum { S_F1W = 18, S_F1B, S_G4, S_BE4, S_RM4, S_RV4, S_F2W, S_F2B, S_COUNT };
-enum { K_W, K_B, K_G, K_BE, K_RM, K_RV };
-
 struct Block {
     int C, CI, creal, h, w;                 // z [n][h][w][C]; pl, arg, a, da [n][h/2][w/2][C]
     int slot;                               // its first tensor slot
@@ -414,50 +414,44 @@ struct Block {
     int cic = 0, dg_co = 0, dg_cic = 0;     // its weight image: the parameter layout's chunk, the data gradient's tile and chunk
 };
 
-}  // namespace
-
-struct ArchTrainer {
-    trexhip_ctx* ctx = nullptr;
-    int version = 0, classes = 0, CH = 1, max_n = 0, W = 0, H = 0;
-    bool bn = false;                        // v110
-    TrainAnyGeom geom{};
-    trexhip_train_params p{};
-    int64_t step = 0;
-    int n_tensors = 0, order[S_COUNT] = {};           // the version's state_dict order -> slots
-    size_t off[S_COUNT + 1] = {}, cnt[S_COUNT] = {}, isz[S_COUNT] = {};      // offset, torch's element count, elements held (padded)
-    size_t total = 0;
-    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
-    Block L[3];
-    float *part = nullptr, *part1 = nullptr, *stat = nullptr /*4 x (mean, invstd, sums[2]) x 128*/;
-    float *hpart = nullptr, *hsum = nullptr, *xhat = nullptr, *hd = nullptr, *dl = nullptr, *dy = nullptr, *dh = nullptr, *loss = nullptr, *out2 = nullptr;
-    int32_t *correct = nullptr, *bad_target = nullptr;
-    double *red = nullptr, *red_bias = nullptr;
-    uint8_t *keep = nullptr, *keep_stage = nullptr;
-    float* x_stage = nullptr;
-    int32_t* y_stage = nullptr;
-    Mem mem;
-    float* param(int slot) const { return P + off[slot]; }
-    float* grad(int slot) const { return G + off[slot]; }
+struct ChainTrainer;
+struct Net {
+    TrainNet tensors;                       // its row of train_tensors.h: taps, slots, state_dict order, mask planes, Adam's buffers
+    float drop[4];                          // the network's own dropout rates (trexhip_train_params.dropout is V118_3's)
+    bool arg, pl, bn_head;                  // a block keeps the pool's arg-max bytes (v100, v110) and the raw pooled plane (v110); BatchNorm1d behind fc1
+    // z -> a of one block.  train: batch statistics + the dropout masks; eval: running statistics, the caller's masks keep everything
+    void (*block_forward)(ChainTrainer*, hipStream_t, const Block&, int n, const uint8_t* kp, float scale, bool train);
+    // da -> dz written over z, the gradients of gamma and beta where it has them; returns the workgroups whose column sums red_bias holds
+    int (*block_backward)(ChainTrainer*, hipStream_t, const Block&, int n, const uint8_t* kp, float scale);
+    void (*head)(ChainTrainer*, hipStream_t, int n, const uint8_t* kp, float scale, const int32_t* targets, bool train, float* probs);
 };
 
-namespace {
+struct ChainTrainer : TrainerCore {
+    const Net* net = nullptr;
+    TrainAnyGeom geom{};
+    Block L[3];
+    float *part = nullptr, *part1 = nullptr, *stat = nullptr /*4 x (mean, invstd, sums[2]) x 128*/;
+    float *hpart = nullptr, *hsum = nullptr, *xhat = nullptr, *hd = nullptr, *dl = nullptr, *dy = nullptr, *dh = nullptr;
+    double *red = nullptr, *red_bias = nullptr;
+    float scale(int i, bool train) const { return train ? 1.0f / (1.0f - net->drop[i]) : 1.f; }
+    const uint8_t* plane(const uint8_t* keep, int n, int i) const { return keep + (size_t)n * tt.keep_off[i]; }
 
-// index inside the slot, in the kernels' layout, of element `i` of torch's tensor
-size_t to_internal(const int slot, const size_t i, const int CH, const size_t P) {
-    switch (slot) {
-        case 0: { const size_t tap = i % 25, c = (i / 25) % CH, co = i / (25 * (size_t)CH); return (c * 25 + tap) * 16 + co; }
-        case 6: { const size_t tap = i % 25, ci = (i / 25) % 16, co = i / 400; return (tap * 16 + ci) * 64 + co; }
-        case 12: { const size_t tap = i % 25, ci = (i / 25) % 64, co = i / 1600; return (((ci / 32) * 25 + tap) * 32 + ci % 32) * 128 + co; }
-        case S_F1W: { const size_t K = 100 * P, k = i % K, o = i / K, c = k / P, hw = k % P; return (hw * 128 + c) * HID + o; }
-        default: return i;
+    int refuse_step(const char* who, int n) override {
+        // BatchNorm over one value per channel: the reference raises "Expected more than 1 value per channel when training"
+        if (!net->bn_head || n >= 2) return TREXHIP_OK;
+        set_error(std::string(who) + ": a v110 training step needs n >= 2 (BatchNorm1d over the batch: more than 1 value per channel)");
+        return TREXHIP_E_INVALID;
     }
-}
-
-void trainer_free(ArchTrainer* t) {
-    if (!t) return;
-    t->mem.free_all();
-    delete t;
-}
+    const uint8_t* begin_step(hipStream_t s, int n, const uint8_t* injected) override;
+    void forward(hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, bool train, float* probs) override;
+    void backward(hipStream_t s, const float* x, int n, const uint8_t* keep) override;
+    size_t blob_bytes() const override { return version == TREXHIP_NET_CATEGORY ? category_blob_bytes(classes, CH, W, H) : arch_blob_bytes(version, classes, CH, W, H); }
+    void write_blob_header(void* blob) const override {
+        if (version == TREXHIP_NET_CATEGORY) { write_category_blob_header(blob, classes, W, H, CH); return; }
+        write_weight_blob_header(blob, classes, W, H, CH);
+        static_cast<int32_t*>(blob)[6] = version;
+    }
+};
 
 template <bool V100>
 void launch_pool(hipStream_t s, const Block& L, const uint8_t* keep, float scale, float* out, int n) {
@@ -467,334 +461,199 @@ void launch_pool(hipStream_t s, const Block& L, const uint8_t* keep, float scale
     hipLaunchKernelGGL(fn, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L.z, keep, L.creal, scale, out, L.arg, n, L.h, L.w);
 }
 
-// z -> a of one block.  train: batch statistics + the dropout masks; eval: running statistics, the caller's masks keep everything
-void block_forward(ArchTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* keep, float scale, bool train) {
-    const int i = L.slot / 6;
-    const uint8_t* kp = keep + (size_t)n * KEEP_OFF[i];
-    if (!t->bn) { launch_pool<true>(s, L, kp, scale, L.a, n); return; }
+// mean and invstd of block i for its BatchNorm over `rows` rows of d: the batch's (and the running statistics move) or the running ones
+void block_stats(ChainTrainer* t, hipStream_t s, const Block& L, const float* d, size_t rows, bool train) {
+    float* mean = t->stat + L.slot / 6 * 512;
+    if (train) {
+        t_bn_stats(s, L.C, d, rows, t->red);
+        t_fin_bn_stats(s, t->red, T_RED_BLOCKS, L.C, (double)rows, t->p.bn_momentum, mean, mean + 128, t->param(L.slot + K_RM), t->param(L.slot + K_RV), t->bad_target);
+    } else {
+        t_bn_from_running(s, t->param(L.slot + K_RM), t->param(L.slot + K_RV), L.C, mean, mean + 128);
+    }
+}
+
+// ---- pool only (v100)
+void pool_forward(ChainTrainer*, hipStream_t s, const Block& L, int n, const uint8_t* kp, float scale, bool) { launch_pool<true>(s, L, kp, scale, L.a, n); }
+
+// the grid of k_tarch_unpool -- whole rounds: every workgroup takes the same number of elements
+size_t unpool_blocks(const Block& L, int n) {
+    const size_t total = (size_t)n * ((L.h + 1) / 2) * ((L.w + 1) / 2) * (L.C / 4);
+    const size_t nb0 = (total + 255) / 256, per = (nb0 + T_BWD_BLOCKS - 1) / T_BWD_BLOCKS;
+    return (nb0 + per - 1) / per;
+}
+
+// ---- pool, then BatchNorm over the pooled rows (v110)
+void pool_bn_forward(ChainTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* kp, float scale, bool train) {
     launch_pool<false>(s, L, nullptr, 1.f, L.pl, n);
-    float* mean = t->stat + i * 512;
-    float* invstd = mean + 128;
+    float* mean = t->stat + L.slot / 6 * 512;
     const int hw = (L.h / 2) * (L.w / 2);
     const size_t rows = (size_t)n * hw;
-    if (train) {
-        t_bn_stats(s, L.C, L.pl, rows, t->red);
-        t_fin_bn_stats(s, t->red, T_RED_BLOCKS, L.C, (double)rows, t->p.bn_momentum, mean, invstd, t->param(L.slot + K_RM), t->param(L.slot + K_RV), t->bad_target);
-    } else {
-        t_bn_from_running(s, t->param(L.slot + K_RM), t->param(L.slot + K_RV), L.C, mean, invstd);
-    }
+    block_stats(t, s, L, L.pl, rows, train);
     const size_t lanes = rows * (L.C / 4);
     const auto fn = L.C == 16 ? &k_tarch_bn_apply<16> : L.C == 64 ? &k_tarch_bn_apply<64> : &k_tarch_bn_apply<128>;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, L.pl, mean, invstd, t->param(L.slot + K_G), t->param(L.slot + K_BE), kp, L.creal, scale,
+    hipLaunchKernelGGL(fn, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, L.pl, mean, mean + 128, t->param(L.slot + K_G), t->param(L.slot + K_BE), kp, L.creal, scale,
                        L.a, rows, hw);
 }
 
-// da -> dz written over z, the gradients of bias (and gamma, beta); then the weight gradient and the data gradient of blocks 2 and 3
-void block_backward(ArchTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* keep, float scale) {
-    const int i = L.slot / 6;
-    const uint8_t* kp = keep + (size_t)n * KEEP_OFF[i];
-    float* mean = t->stat + i * 512;
+int pool_bn_backward(ChainTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* kp, float scale) {
+    float* mean = t->stat + L.slot / 6 * 512;
     float* invstd = mean + 128;
     float* sums = mean + 256;
     const int hw = (L.h / 2) * (L.w / 2);
     const size_t rows = (size_t)n * hw;
-    if (t->bn) {
-        const auto fn = L.C == 16 ? &k_tarch_bn_bwd_stats<16> : L.C == 64 ? &k_tarch_bn_bwd_stats<64> : &k_tarch_bn_bwd_stats<128>;
-        hipLaunchKernelGGL(fn, dim3(T_RED_BLOCKS), dim3(256), 0, s, L.da, L.pl, mean, invstd, t->param(L.slot + K_G), t->param(L.slot + K_BE), kp, L.creal, scale, rows, hw,
-                           t->red);
-        t_fin_bn_bwd(s, t->red, T_RED_BLOCKS, L.C, sums, t->grad(L.slot + K_G), t->grad(L.slot + K_BE));
-    }
+    const float *g = t->param(L.slot + K_G), *be = t->param(L.slot + K_BE);
     {
-        const size_t total = (size_t)n * ((L.h + 1) / 2) * ((L.w + 1) / 2) * (L.C / 4);
-        // whole rounds: every workgroup takes the same number of elements
-        const size_t nb0 = (total + 255) / 256, per = (nb0 + T_BWD_BLOCKS - 1) / T_BWD_BLOCKS, nb = (nb0 + per - 1) / per;
-        const float inv_count = (float)(1.0 / (double)std::max<size_t>(rows, 1));
-        if (t->bn) {
-            const auto fn = L.C == 16 ? &k_tarch_unpool<16, false> : L.C == 64 ? &k_tarch_unpool<64, false> : &k_tarch_unpool<128, false>;
-            hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(256), 0, s, L.da, L.pl, L.arg, L.z, mean, invstd, t->param(L.slot + K_G), t->param(L.slot + K_BE), kp, L.creal, scale,
-                               sums, inv_count, n, L.h, L.w, t->red_bias);
-        } else {
-            const auto fn = L.C == 16 ? &k_tarch_unpool<16, true> : L.C == 64 ? &k_tarch_unpool<64, true> : &k_tarch_unpool<128, true>;
-            hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(256), 0, s, L.da, nullptr, L.arg, L.z, nullptr, nullptr, nullptr, nullptr, kp, L.creal, scale, nullptr, 0.f, n, L.h,
-                               L.w, t->red_bias);
-        }
-        t_fin_bias(s, t->red_bias, (int)nb, L.C, t->grad(L.slot + K_B));
+        const auto fn = L.C == 16 ? &k_tarch_bn_bwd_stats<16> : L.C == 64 ? &k_tarch_bn_bwd_stats<64> : &k_tarch_bn_bwd_stats<128>;
+        hipLaunchKernelGGL(fn, dim3(T_RED_BLOCKS), dim3(256), 0, s, L.da, L.pl, mean, invstd, g, be, kp, L.creal, scale, rows, hw, t->red);
     }
-    if (i == 0) return;
-    const Block& below = t->L[i - 1];
-    tany_wgrad(s, t->geom, i, n, below.a, L.z, t->part);
-    t_wgrad_reduce(s, t->part, t->geom.wg_shares(i, n), L.CI, L.C, L.cic, t->grad(L.slot + K_W));
-    t_repack_bwd(s, t->param(L.slot + K_W), L.CI, L.C, L.cic, L.dg_co, L.dg_cic, L.wb);
-    tany_conv_dgrad(s, t->geom, i, n, L.z, L.wb, below.da);
+    t_fin_bn_bwd(s, t->red, T_RED_BLOCKS, L.C, sums, t->grad(L.slot + K_G), t->grad(L.slot + K_BE));
+    const size_t nb = unpool_blocks(L, n);
+    const float inv_count = (float)(1.0 / (double)std::max<size_t>(rows, 1));
+    const auto fn = L.C == 16 ? &k_tarch_unpool<16, false> : L.C == 64 ? &k_tarch_unpool<64, false> : &k_tarch_unpool<128, false>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(256), 0, s, L.da, L.pl, L.arg, L.z, mean, invstd, g, be, kp, L.creal, scale, sums, inv_count, n, L.h, L.w, t->red_bias);
+    return (int)nb;
 }
 
-// forward pass up to the per-sample loss / arg-max and the gradient at the ReLU's input of the head (k_tarch_head); probs: a prediction
-void trainer_forward(ArchTrainer* t, hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, const float* scale, bool train, float* probs = nullptr) {
-    Block* L = t->L;
-    tany_conv1(s, t->geom, n, x, t->param(K_W), t->param(K_B), L[0].z);
-    block_forward(t, s, L[0], n, keep, scale[0], train);
-    for (int i = 1; i < 3; ++i) {
-        tany_conv_fwd(s, t->geom, i, n, L[i - 1].a, t->param(L[i].slot + K_W), t->param(L[i].slot + K_B), L[i].z);
-        block_forward(t, s, L[i], n, keep, scale[i], train);
-    }
-    tany_fc1(s, t->geom, n, L[2].a, t->param(S_F1W), t->hpart, t->hsum);
+// (v100's way back stands behind v110's so that the kernel instances keep the order the compiler has always emitted them in; the heads likewise)
+int pool_backward(ChainTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* kp, float scale) {
+    const size_t nb = unpool_blocks(L, n);
+    const auto fn = L.C == 16 ? &k_tarch_unpool<16, true> : L.C == 64 ? &k_tarch_unpool<64, true> : &k_tarch_unpool<128, true>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(256), 0, s, L.da, nullptr, L.arg, L.z, nullptr, nullptr, nullptr, nullptr, kp, L.creal, scale, nullptr, 0.f, n, L.h, L.w,
+                       t->red_bias);
+    return (int)nb;
+}
+
+// ---- BatchNorm over all n h w pixels of the convolution's plane, then the pool with element-wise masks (the category network): train_any.hip's
+// block kernels with `creal`
+void bn_pool_forward(ChainTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* kp, float scale, bool train) {
+    float* mean = t->stat + L.slot / 6 * 512;
+    block_stats(t, s, L, L.z, (size_t)n * L.h * L.w, train);
+    tany_bn_pool(s, L.C, L.z, mean, mean + 128, t->param(L.slot + K_G), t->param(L.slot + K_BE), kp, scale, L.a, n, L.h, L.w, L.creal);
+}
+
+int bn_pool_backward(ChainTrainer* t, hipStream_t s, const Block& L, int n, const uint8_t* kp, float scale) {
+    float* mean = t->stat + L.slot / 6 * 512;
+    float* invstd = mean + 128;
+    float* sums = mean + 256;
+    const float *g = t->param(L.slot + K_G), *be = t->param(L.slot + K_BE);
+    tany_pool_bwd_stats(s, L.C, T_RED_BLOCKS, L.da, L.z, mean, invstd, g, be, kp, scale, n, L.h, L.w, t->red, L.creal);
+    t_fin_bn_bwd(s, t->red, T_RED_BLOCKS, L.C, sums, t->grad(L.slot + K_G), t->grad(L.slot + K_BE));
+    const float inv_count = (float)(1.0 / ((double)n * L.h * L.w));      // the means run over every pixel of the plane
+    return tany_bn_bwd(s, L.C, T_BWD_BLOCKS, L.da, L.z, mean, invstd, g, be, kp, scale, sums, inv_count, n, L.h, L.w, t->red_bias, L.creal);
+}
+
+// ---- the heads: hsum -> loss, arg-max and the gradient at the ReLU's input (dh; v110: dy, in front of its BatchNorm1d's way back)
+void head_bn(ChainTrainer* t, hipStream_t s, int n, const uint8_t* kp, float scale, const int32_t* targets, bool train, float* probs) {
     float* mean = t->stat + 3 * 512;
     float* invstd = mean + 128;
-    const uint8_t* kp = keep + (size_t)n * KEEP_OFF[3];
-    if (t->bn) {
-        if (train) hipLaunchKernelGGL(k_tarch_bn1d_stats, dim3(1), dim3(128), 0, s, t->hsum, t->param(S_F1B), n, t->p.bn_momentum, mean, invstd, t->param(S_RM4), t->param(S_RV4), t->bad_target);
-        else t_bn_from_running(s, t->param(S_RM4), t->param(S_RV4), HID, mean, invstd);
-        hipLaunchKernelGGL(k_tarch_head<true>, dim3(n), dim3(128), 0, s, t->hsum, n, t->param(S_F1B), mean, invstd, t->param(S_G4), t->param(S_BE4), kp, scale[3], t->param(S_F2W),
-                           t->param(S_F2B), targets, t->classes, t->xhat, t->hd, t->dl, t->dy, t->loss, t->correct, probs);
-    } else {
-        tarch_head_plain(s, t->hsum, n, t->param(S_F1B), kp, scale[3], t->param(S_F2W), t->param(S_F2B), targets, t->classes, t->hd, t->dl, t->dh, t->loss, t->correct, probs);
+    if (train) hipLaunchKernelGGL(k_tarch_bn1d_stats, dim3(1), dim3(128), 0, s, t->hsum, t->param(S_F1B), n, t->p.bn_momentum, mean, invstd, t->param(S_RM4), t->param(S_RV4), t->bad_target);
+    else t_bn_from_running(s, t->param(S_RM4), t->param(S_RV4), HID, mean, invstd);
+    hipLaunchKernelGGL(k_tarch_head<true>, dim3(n), dim3(128), 0, s, t->hsum, n, t->param(S_F1B), mean, invstd, t->param(S_G4), t->param(S_BE4), kp, scale, t->param(S_F2W),
+                       t->param(S_F2B), targets, t->classes, t->xhat, t->hd, t->dl, t->dy, t->loss, t->correct, probs);
+}
+
+void head_plain(ChainTrainer* t, hipStream_t s, int n, const uint8_t* kp, float scale, const int32_t* targets, bool, float* probs) {
+    hipLaunchKernelGGL(k_tarch_head<false>, dim3(n), dim3(128), 0, s, t->hsum, n, t->param(S_F1B), nullptr, nullptr, nullptr, nullptr, kp, scale, t->param(S_F2W), t->param(S_F2B),
+                       targets, t->classes, nullptr, t->hd, t->dl, t->dh, t->loss, t->correct, probs);
+}
+
+//                    tensors         dropout rates                 arg    pl     BN head  z -> a           da -> dz          head
+const Net NET_V100 = {TRAIN_V100,     {0.25f, 0.25f, 0.25f, 0.5f},  true,  false, false,   pool_forward,    pool_backward,    head_plain};
+const Net NET_V110 = {TRAIN_V110,     {0.25f, 0.25f, 0.25f, 0.25f}, true,  true,  true,    pool_bn_forward, pool_bn_backward, head_bn};
+const Net NET_CAT  = {TRAIN_CATEGORY, {0.25f, 0.25f, 0.25f, 0.25f}, false, false, false,   bn_pool_forward, bn_pool_backward, head_plain};
+
+// the three planes behind the blocks share a rate and are one draw; the head's plane comes from another stream of the same counter hash
+const uint8_t* ChainTrainer::begin_step(hipStream_t s, int n, const uint8_t* injected) {
+    if (injected) return injected;
+    t_masks(s, keep, (size_t)n * tt.keep_off[3], p.seed, (uint64_t)step, net->drop[0]);
+    t_masks(s, keep + (size_t)n * tt.keep_off[3], (size_t)n * HID, p.seed ^ 0xD1B54A32D192ED03ull, (uint64_t)step, net->drop[3]);
+    return keep;
+}
+
+void ChainTrainer::forward(hipStream_t s, const float* x, const int32_t* targets, int n, const uint8_t* keep, bool train, float* probs) {
+    tany_conv1(s, geom, n, x, param(K_W), param(K_B), L[0].z);
+    net->block_forward(this, s, L[0], n, plane(keep, n, 0), scale(0, train), train);
+    for (int i = 1; i < 3; ++i) {
+        tany_conv_fwd(s, geom, i, n, L[i - 1].a, param(L[i].slot + K_W), param(L[i].slot + K_B), L[i].z);
+        net->block_forward(this, s, L[i], n, plane(keep, n, i), scale(i, train), train);
     }
+    tany_fc1(s, geom, n, L[2].a, param(S_F1W), hpart, hsum);
+    net->head(this, s, n, plane(keep, n, 3), scale(3, train), targets, train, probs);
 }
 
-// steps with a target outside 0..classes-1 were refused on the device (k_t_check_targets): train.hip's rule and texts
-int check_targets(ArchTrainer* t) {
-    int32_t bad[2] = {0, 0};
-    TH_CHECK_HIP(hipMemcpy(bad, t->bad_target, 8, hipMemcpyDeviceToHost));
-    if (bad[0] || bad[1]) {
-        TH_CHECK_HIP(hipMemset(t->bad_target, 0, 8));
-        if (bad[0]) t->step -= bad[0];
-        set_error(bad[0] ? std::string("training step: a target class index was outside 0..classes-1; that step (and the ") + std::to_string(bad[0] - 1) +
-                               " queued behind it) was refused, parameters, moments and running statistics are unchanged"
-                         : std::string("evaluation batch: a target class index was outside 0..classes-1"));
-        return TREXHIP_E_INVALID;
+void ChainTrainer::backward(hipStream_t s, const float* x, int n, const uint8_t* keep) {
+    if (net->bn_head) {
+        float* mean = stat + 3 * 512;
+        hipLaunchKernelGGL(k_tarch_bn1d_sums, dim3(1), dim3(128), 0, s, dy, xhat, n, mean + 256, grad(S_G4), grad(S_BE4));
+        hipLaunchKernelGGL(k_tarch_bn1d_dh, dim3((n * HID + 255) / 256), dim3(256), 0, s, dy, xhat, mean + 256, param(S_G4), mean + 128, n, dh);
     }
-    return TREXHIP_OK;
-}
-
-int fetch_loss(ArchTrainer* t, hipStream_t s, float* h_loss, int32_t* h_correct) {
-    float two[2];
-    TH_CHECK_HIP(hipMemcpyAsync(two, t->out2, sizeof(two), hipMemcpyDeviceToHost, s));
-    TH_CHECK_HIP(hipStreamSynchronize(s));
-    if (h_loss) *h_loss = two[0];
-    if (h_correct) *h_correct = (int32_t)two[1];
-    return check_targets(t);
-}
-
-constexpr float ONES[4] = {1.f, 1.f, 1.f, 1.f};
-
-int stage(ArchTrainer* t, const char* who, const float* inputs, const int32_t* targets, int n, const uint8_t* keep_masks) {
-    for (int i = 0; i < n; ++i)
-        if (targets[i] < 0 || targets[i] >= t->classes) { set_error(std::string(who) + ": target class out of range"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    hipStream_t s = t->ctx->stream;
-    TH_CHECK_HIP(hipMemcpyAsync(t->x_stage, inputs, (size_t)n * t->H * t->W * t->CH * sizeof(float), hipMemcpyHostToDevice, s));
-    TH_CHECK_HIP(hipMemcpyAsync(t->y_stage, targets, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (keep_masks) TH_CHECK_HIP(hipMemcpyAsync(t->keep_stage, keep_masks, (size_t)n * KEEP_ROW, hipMemcpyHostToDevice, s));
-    return TREXHIP_OK;
+    hipLaunchKernelGGL(k_tarch_head_grads, dim3((classes * HID + classes + HID + 255) / 256), dim3(256), 0, s, dl, hd, dh, n, classes, grad(S_F2W), grad(S_F2B), grad(S_F1B));
+    tany_fc1_wgrad(s, geom, n, L[2].a, dh, grad(S_F1W));
+    t_loss(s, loss, correct, n, out2);
+    tany_fc1_dgrad(s, geom, n, dh, param(S_F1W), L[2].da);
+    for (int i = 2; i >= 0; --i) {
+        const Block& B = L[i];
+        const int nb = net->block_backward(this, s, B, n, plane(keep, n, i), scale(i, true));
+        t_fin_bias(s, red_bias, nb, B.C, grad(B.slot + K_B));
+        if (i == 0) break;
+        // the weight gradient and the data gradient of blocks 2 and 3
+        tany_wgrad(s, geom, i, n, L[i - 1].a, B.z, part);
+        t_wgrad_reduce(s, part, geom.wg_shares(i, n), B.CI, B.C, B.cic, grad(B.slot + K_W), geom.taps);
+        t_repack_bwd(s, param(B.slot + K_W), B.CI, B.C, B.cic, B.dg_co, B.dg_cic, B.wb, geom.taps);
+        tany_conv_dgrad(s, geom, i, n, B.z, B.wb, L[i - 1].da);
+    }
+    tany_wgrad1(s, geom, n, x, L[0].z, part1);
+    t_reduce(s, part1, n * geom.wg1_tiles, CH * geom.taps * geom.taps * 16, grad(K_W));
 }
 
 }  // namespace
 
-int arch_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, ArchTrainer** out) {
+// blob: a category blob ('TRXC', the parser of trexhip_categorize_load_weights: its codes and field names) or an identity blob whose header names
+// v100 or v110 (the parser of trexhip_load_weights)
+int chain_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const trexhip_train_params* p, TrainerCore** out) {
     const char* who = "trexhip_trainer_create";
+    if (const int rc = check_train_params(p)) return rc;
     ArchBlob ab;
-    if (const int rc = parse_arch_blob(blob, bytes, who, &ab)) return rc;
-    if (ab.id != TREXHIP_NET_V100 && ab.id != TREXHIP_NET_V110) { set_error(std::string(who) + ": this version does not train"); return TREXHIP_E_UNSUPPORTED; }
+    const bool cat = blob_is_category(blob, bytes);
+    if (const int rc = cat ? parse_category_blob(blob, bytes, who, &ab) : parse_arch_blob(blob, bytes, who, &ab)) return rc;
     if (hipSetDevice(ctx->p.device) != hipSuccess) { set_error("trexhip_trainer_create: hipSetDevice failed"); return TREXHIP_E_DEVICE; }
-    ArchTrainer* t = new ArchTrainer();
-    t->ctx = ctx; t->version = ab.id; t->bn = ab.id == TREXHIP_NET_V110; t->classes = ab.classes; t->CH = ab.CH; t->max_n = p->max_batch; t->p = *p;
+    ChainTrainer* t = new ChainTrainer();
+    t->net = cat ? &NET_CAT : ab.id == TREXHIP_NET_V110 ? &NET_V110 : &NET_V100;
+    t->ctx = ctx; t->version = cat ? TREXHIP_NET_CATEGORY : ab.id; t->classes = ab.classes; t->CH = ab.CH; t->max_n = p->max_batch; t->p = *p;
     t->W = ab.W; t->H = ab.H;
-    t->geom = train_any_geom(ab.W, ab.H, ab.CH);
-    const size_t P = t->geom.P;
-    // ---- the tensors: torch's count, the count held (block 3 and fc1 padded to 128 channels), the version's state_dict order
+    t->tt = train_tensors(t->net->tensors, ab.W, ab.H, ab.CH, ab.classes);
+    t->geom = train_any_geom(ab.W, ab.H, ab.CH, t->tt.taps);
     const float* src[S_COUNT] = {};
-    for (int i = 0; i < 3; ++i) {
-        const size_t ci_r = i ? CR[i - 1] : ab.CH, ci_p = i ? CP[i - 1] : ab.CH;
-        t->cnt[6 * i] = (size_t)CR[i] * ci_r * 25; t->isz[6 * i] = (size_t)CP[i] * ci_p * 25;
-        for (int k = 1; k < 6; ++k) { t->cnt[6 * i + k] = CR[i]; t->isz[6 * i + k] = CP[i]; }
+    for (int i = 0; i < 3; ++i)
         for (int k = 0; k < 6; ++k) src[6 * i + k] = ab.conv[i][k];
-    }
-    t->cnt[S_F1W] = (size_t)HID * 100 * P; t->isz[S_F1W] = t->geom.fc1_weight_floats();
-    for (int k = S_F1B; k <= S_RV4; ++k) t->cnt[k] = t->isz[k] = HID;
-    t->cnt[S_F2W] = t->isz[S_F2W] = (size_t)ab.classes * HID; t->cnt[S_F2B] = t->isz[S_F2B] = ab.classes;
     src[S_F1W] = ab.fc1w; src[S_F1B] = ab.fc1b; src[S_F2W] = ab.fc2w; src[S_F2B] = ab.fc2b;
     for (int k = 0; k < 4; ++k) src[S_G4 + k] = ab.bn1d[k];
-    size_t at = 0;
-    for (int k = 0; k < S_COUNT; ++k) {
-        const bool is_bn = (k < 18 && k % 6 >= 2) || (k >= S_G4 && k <= S_RV4);
-        if (is_bn && !t->bn) t->cnt[k] = t->isz[k] = 0;
-        else t->order[t->n_tensors++] = k;
-        t->off[k] = at;
-        at += (t->isz[k] + 63) / 64 * 64;
-    }
-    t->off[S_COUNT] = at; t->total = at;
     Block* L = t->L;
-    for (int i = 0; i < 3; ++i) { L[i].C = CP[i]; L[i].CI = i ? CP[i - 1] : ab.CH; L[i].creal = CR[i]; L[i].h = t->geom.L[i].h; L[i].w = t->geom.L[i].w; L[i].slot = 6 * i; }
+    for (int i = 0; i < 3; ++i) { L[i].C = t->geom.L[i].C; L[i].CI = t->geom.L[i].CI; L[i].creal = i == 2 ? t->tt.c3 : L[i].C; L[i].h = t->geom.L[i].h; L[i].w = t->geom.L[i].w; L[i].slot = 6 * i; }
     L[1].cic = 16; L[1].dg_cic = 16; L[1].dg_co = 32;            // conv2's data gradient: 16 real channels in a 32-wide tile
     L[2].cic = 32; L[2].dg_cic = 32; L[2].dg_co = 64;
     // ---- memory
-    const size_t n = (size_t)t->max_n;
+    const size_t n = (size_t)t->max_n, T2 = (size_t)t->tt.taps * t->tt.taps;
     int rc = TREXHIP_OK;
 #define TRY(x) do { if (rc == TREXHIP_OK) rc = (x); } while (0)
-    TRY(t->mem.device(&t->P, at, who)); TRY(t->mem.device(&t->G, at, who)); TRY(t->mem.device(&t->M, at, who)); TRY(t->mem.device(&t->V, at, who));
     for (int i = 0; i < 3; ++i) {
         const size_t pooled = t->geom.a_floats(i, n);
         TRY(t->mem.device(&L[i].z, t->geom.z_floats(i, n), who)); TRY(t->mem.device(&L[i].a, pooled, who)); TRY(t->mem.device(&L[i].da, pooled, who));
-        TRY(t->mem.device(&L[i].arg, pooled / 4, who));
-        if (t->bn) TRY(t->mem.device(&L[i].pl, pooled, who));
+        if (t->net->arg) TRY(t->mem.device(&L[i].arg, pooled / 4, who));
+        if (t->net->pl) TRY(t->mem.device(&L[i].pl, pooled, who));
     }
-    TRY(t->mem.device(&L[2].wb, (size_t)4 * 25 * 32 * 64, who)); TRY(t->mem.device(&L[1].wb, (size_t)2 * 25 * 32 * 32, who));
+    TRY(t->mem.device(&L[2].wb, 4 * T2 * 32 * 64, who)); TRY(t->mem.device(&L[1].wb, 2 * T2 * 32 * 32, who));
     TRY(t->mem.device(&t->part, t->geom.part_floats(), who)); TRY(t->mem.device(&t->part1, t->geom.part1_floats(n), who));
     TRY(t->mem.device(&t->red_bias, (size_t)T_BWD_BLOCKS * 128, who)); TRY(t->mem.device(&t->red, (size_t)T_BWD_BLOCKS * 2 * 128, who));
     TRY(t->mem.device(&t->stat, (size_t)4 * 512, who));
-    TRY(t->mem.device(&t->hpart, t->geom.hpart_floats(n), who)); TRY(t->mem.device(&t->hsum, n * HID, who)); TRY(t->mem.device(&t->xhat, n * HID, who));
-    TRY(t->mem.device(&t->hd, n * HID, who)); TRY(t->mem.device(&t->dl, n * ab.classes, who)); TRY(t->mem.device(&t->dy, n * HID, who)); TRY(t->mem.device(&t->dh, n * HID, who));
-    TRY(t->mem.device(&t->loss, n, who)); TRY(t->mem.device(&t->correct, n, who)); TRY(t->mem.device(&t->out2, 2, who)); TRY(t->mem.device(&t->bad_target, 2, who));
-    TRY(t->mem.device(&t->keep, n * KEEP_ROW, who)); TRY(t->mem.device(&t->keep_stage, n * KEEP_ROW, who));
-    TRY(t->mem.device(&t->x_stage, t->geom.x_floats(n), who)); TRY(t->mem.device(&t->y_stage, n, who));
+    TRY(t->mem.device(&t->hpart, t->geom.hpart_floats(n), who)); TRY(t->mem.device(&t->hsum, n * HID, who));
+    TRY(t->mem.device(&t->hd, n * HID, who)); TRY(t->mem.device(&t->dl, n * ab.classes, who)); TRY(t->mem.device(&t->dh, n * HID, who));
+    if (t->net->bn_head) { TRY(t->mem.device(&t->xhat, n * HID, who)); TRY(t->mem.device(&t->dy, n * HID, who)); }
     TRY(tany_attrs());
+    TRY(t->init_state(src, who));
 #undef TRY
-    if (rc != TREXHIP_OK) { trainer_free(t); return rc; }
-    std::vector<float> host(at, 0.f);
-    for (int k = 0; k < S_COUNT; ++k)
-        for (size_t i = 0; i < t->cnt[k]; ++i) host[t->off[k] + to_internal(k, i, ab.CH, P)] = src[k][i];
-    bool ok = hipMemcpy(t->P, host.data(), at * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemset(t->bad_target, 0, 8) == hipSuccess;
-    ok = ok && hipMemset(t->G, 0, at * 4) == hipSuccess && hipMemset(t->M, 0, at * 4) == hipSuccess && hipMemset(t->V, 0, at * 4) == hipSuccess;
-    if (!ok) { trainer_free(t); set_error("trexhip_trainer_create: upload failed"); return TREXHIP_E_DEVICE; }
+    if (rc != TREXHIP_OK) { delete t; return rc; }
     *out = t;
-    return TREXHIP_OK;
-}
-
-// the BatchNorm-free head as another chain launches it (train_cat.hip): k_tarch_head<false> and k_tarch_head_grads, stated here once
-void tarch_head_plain(hipStream_t s, const float* hsum, int n, const float* b1, const uint8_t* keep, float scale, const float* w2, const float* b2, const int32_t* targets,
-                      int classes, float* hd, float* dl, float* dh, float* loss, int32_t* correct, float* probs) {
-    hipLaunchKernelGGL(k_tarch_head<false>, dim3(n), dim3(128), 0, s, hsum, n, b1, nullptr, nullptr, nullptr, nullptr, keep, scale, w2, b2, targets, classes, nullptr, hd, dl, dh,
-                       loss, correct, probs);
-}
-void tarch_head_grads(hipStream_t s, const float* dl, const float* hd, const float* dh, int n, int classes, float* g_w2, float* g_b2, float* g_b1) {
-    hipLaunchKernelGGL(k_tarch_head_grads, dim3((classes * HID + classes + HID + 255) / 256), dim3(256), 0, s, dl, hd, dh, n, classes, g_w2, g_b2, g_b1);
-}
-
-void arch_trainer_destroy(ArchTrainer* t) {
-    if (!t) return;
-    (void)hipSetDevice(t->ctx->p.device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    trainer_free(t);
-}
-
-size_t arch_trainer_keep_mask_bytes(int n) { return (size_t)n * KEEP_ROW; }
-void arch_trainer_set_lr(ArchTrainer* t, float lr) { t->p.lr = lr; }
-int64_t arch_trainer_steps(const ArchTrainer* t) { return t->step; }
-void arch_trainer_info(const ArchTrainer* t, int32_t* width, int32_t* height, int32_t* version, int32_t* max_batch) {
-    if (width) *width = t->W;
-    if (height) *height = t->H;
-    if (version) *version = t->version;
-    if (max_batch) *max_batch = t->max_n;
-}
-
-int arch_trainer_step(ArchTrainer* t, bool host, const float* x, const int32_t* targets, int n, const uint8_t* d_keep, float* h_loss, int32_t* h_correct) {
-    const char* who = host ? "trexhip_train_step" : "trexhip_train_step_device";
-    // BatchNorm over one value per channel: the reference raises "Expected more than 1 value per channel when training"
-    if (t->bn && n < 2) { set_error(std::string(who) + ": a v110 training step needs n >= 2 (BatchNorm1d over the batch: more than 1 value per channel)"); return TREXHIP_E_INVALID; }
-    if (host) {
-        if (const int rc = stage(t, who, x, targets, n, d_keep)) return rc;
-        x = t->x_stage; targets = t->y_stage;
-        if (d_keep) d_keep = t->keep_stage;
-    }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    hipStream_t s = t->ctx->stream;
-    const float* rate = P_DROP[t->bn ? 1 : 0];
-    float scale[4];
-    for (int i = 0; i < 4; ++i) scale[i] = 1.0f / (1.0f - rate[i]);
-    const uint8_t* keep = d_keep;
-    if (!keep) {
-        // the first three planes share a rate; the head's plane is drawn from another stream of the same counter hash
-        t_masks(s, t->keep, (size_t)n * KEEP_OFF[3], t->p.seed, (uint64_t)t->step, rate[0]);
-        t_masks(s, t->keep + (size_t)n * KEEP_OFF[3], (size_t)n * HID, t->p.seed ^ 0xD1B54A32D192ED03ull, (uint64_t)t->step, rate[3]);
-        keep = t->keep;
-    }
-    t_check_targets(s, targets, n, t->classes, t->bad_target, 0);
-    trainer_forward(t, s, x, targets, n, keep, scale, true);
-    // ---- backward
-    if (t->bn) {
-        float* mean = t->stat + 3 * 512;
-        hipLaunchKernelGGL(k_tarch_bn1d_sums, dim3(1), dim3(128), 0, s, t->dy, t->xhat, n, mean + 256, t->grad(S_G4), t->grad(S_BE4));
-        hipLaunchKernelGGL(k_tarch_bn1d_dh, dim3((n * HID + 255) / 256), dim3(256), 0, s, t->dy, t->xhat, mean + 256, t->param(S_G4), mean + 128, n, t->dh);
-    }
-    tarch_head_grads(s, t->dl, t->hd, t->dh, n, t->classes, t->grad(S_F2W), t->grad(S_F2B), t->grad(S_F1B));
-    tany_fc1_wgrad(s, t->geom, n, t->L[2].a, t->dh, t->grad(S_F1W));
-    t_loss(s, t->loss, t->correct, n, t->out2);
-    tany_fc1_dgrad(s, t->geom, n, t->dh, t->param(S_F1W), t->L[2].da);
-    for (int i = 2; i >= 0; --i) block_backward(t, s, t->L[i], n, keep, scale[i]);
-    tany_wgrad1(s, t->geom, n, x, t->L[0].z, t->part1);
-    t_reduce(s, t->part1, n * t->geom.wg1_tiles, t->CH * 400, t->grad(K_W));
-    // ---- optimizer
-    t->step += 1;
-    {
-        uint32_t lo[4], hi[4];                                   // running statistics are buffers: mean and variance of a BatchNorm lie side by side
-        int k = 0;
-        if (t->bn)
-            for (int rm : {(int)K_RM, 6 + K_RM, 12 + K_RM, (int)S_RM4}) { lo[k] = (uint32_t)t->off[rm]; hi[k] = (uint32_t)(t->off[rm + 1] + t->isz[rm + 1]); ++k; }
-        t_adam(s, t->P, t->G, t->M, t->V, t->total, lo, hi, k, t->p.lr, t->p.beta1, t->p.beta2, t->p.eps, t->step, t->bad_target);
-    }
-    TH_CHECK_HIP(hipGetLastError());
-    if (h_loss || h_correct) { if (const int rc = fetch_loss(t, s, h_loss, h_correct)) return rc; }
-    if (host) TH_CHECK_HIP(hipStreamSynchronize(s));             // the caller's buffers may go away
-    return TREXHIP_OK;
-}
-
-int arch_trainer_eval(ArchTrainer* t, bool host, const float* x, const int32_t* targets, int n, float* h_loss, int32_t* h_correct) {
-    if (host) {
-        if (const int rc = stage(t, "trexhip_train_eval", x, targets, n, nullptr)) return rc;
-        x = t->x_stage; targets = t->y_stage;
-    }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    hipStream_t s = t->ctx->stream;
-    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)n * KEEP_ROW, s));                 // nothing dropped
-    t_check_targets(s, targets, n, t->classes, t->bad_target, 1);
-    trainer_forward(t, s, x, targets, n, t->keep, ONES, false);
-    t_loss(s, t->loss, t->correct, n, t->out2);
-    TH_CHECK_HIP(hipGetLastError());
-    return fetch_loss(t, s, h_loss, h_correct);
-}
-
-int arch_trainer_predict(ArchTrainer* t, const uint8_t* d_crops, int n, float* d_probs) {
-    trexhip_ctx* ctx = t->ctx;
-    TH_CHECK_HIP(hipSetDevice(ctx->p.device));
-    hipStream_t s = ctx->stream;
-    TH_CHECK_HIP(hipMemsetAsync(t->keep, 1, (size_t)std::min(n, t->max_n) * KEEP_ROW, s));       // nothing dropped
-    for (int at = 0; at < n; at += t->max_n) {
-        const int m = std::min(t->max_n, n - at);
-        const int rc = trexhip_augment_device(ctx, nullptr, d_crops + (size_t)at * t->H * t->W * t->CH, nullptr, m, nullptr, m, t->W, t->H, t->CH, nullptr, 0, 0, t->x_stage, nullptr);
-        if (rc != TREXHIP_OK) return rc;
-        trainer_forward(t, s, t->x_stage, nullptr, m, t->keep, ONES, false, d_probs + (size_t)at * t->classes);
-    }
-    TH_CHECK_HIP(hipGetLastError());
-    return TREXHIP_OK;
-}
-
-int arch_trainer_read(ArchTrainer* t, int32_t tensor, int32_t kind, float* out, size_t count) {
-    if (!out || tensor < 0 || tensor >= t->n_tensors || kind < 0 || kind > 3) { set_error("trexhip_trainer_read: bad argument"); return TREXHIP_E_INVALID; }
-    const int slot = t->order[tensor];
-    if (count != t->cnt[slot]) { set_error("trexhip_trainer_read: count does not match the tensor"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipSetDevice(t->ctx->p.device));
-    TH_CHECK_HIP(hipStreamSynchronize(t->ctx->stream));
-    { const int rc = check_targets(t); if (rc != TREXHIP_OK) return rc; }
-    const float* src = kind == 0 ? t->P : kind == 1 ? t->G : kind == 2 ? t->M : t->V;
-    std::vector<float> tmp(t->isz[slot]);
-    TH_CHECK_HIP(hipMemcpy(tmp.data(), src + t->off[slot], tmp.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < count; ++i) out[i] = tmp[to_internal(slot, i, t->CH, (size_t)t->geom.P)];
-    return TREXHIP_OK;
-}
-
-int arch_trainer_export(ArchTrainer* t, void* blob, size_t capacity, size_t* bytes) {
-    const size_t need = arch_blob_bytes(t->version, t->classes, t->CH, t->W, t->H);
-    if (bytes) *bytes = need;
-    if (capacity < need) { set_error("trexhip_trainer_export: buffer too small (the bytes of the blob the trainer was created from)"); return TREXHIP_E_CAPACITY; }
-    write_weight_blob_header(blob, t->classes, t->W, t->H, t->CH);
-    static_cast<int32_t*>(blob)[6] = t->version;
-    float* dst = reinterpret_cast<float*>(static_cast<char*>(blob) + 32);
-    for (int k = 0; k < t->n_tensors; ++k) {
-        const size_t cnt = t->cnt[t->order[k]];
-        if (const int rc = arch_trainer_read(t, k, 0, dst, cnt)) return rc;
-        dst += cnt;
-    }
     return TREXHIP_OK;
 }
 
