@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 21
+#define TREXHIP_ABI_VERSION 22
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -581,6 +581,16 @@ int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* li
  * listed form walked (0: the dense kernel ran), *bytes_filled of conv3's output copied instead; zeros before the first such call.  No reference
  * counterpart; any pointer may be NULL.  (ABI 16) */
 int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled);
+
+/* Above 3200 one-channel 80x80 crops in TREXHIP_CNN_FP16X3, where the skipping above is on, a crop whose blob fits 8 of the 10 column tiles of
+ * conv2's output takes windowed passes of the fused conv1+conv2 kernel: 8 tiles of up to 4 output row pairs of that crop alone, the rest taken
+ * from images of an all-zero crop made when the weights are loaded; the other crops (and every crop of a network whose background leaves the
+ * fp16 range) take the full-width passes as before.  The crops' bytes decide, on the device, in every call; the results are the bits of the
+ * full-width kernel.  Bit 23 of TREXHIP_CONV_GEOM (value 8388608) switches this off.
+ * What the last such call did (waits for the context's stream): *crops_windowed that took windowed passes, *windowed_passes of them, and the
+ * aligned *full_passes the other crops took; zeros where the windowed form did not run.  trexhip_identify_skip_stats keeps counting by the row
+ * rule alone.  No reference counterpart; any pointer may be NULL.  (ABI 22) */
+int trexhip_identify_skipx_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes);
 
 /* Where conv3 lists row pairs and the batch has more than 1024 crops, fc1 -- ten split-K planes, plane q = row pair q of every crop -- computes
  * only the (crop, plane) rows whose row pair is listed; the head takes every other plane from the fc1 planes of an all-zero crop, made when the

@@ -4,7 +4,9 @@ the batch, passes the role-split kernel computed, bytes of V3 rows taken from th
 where the dense conv3 runs; where the listed conv3 runs, as on these crops, nothing is copied and the kernel reads those rows from the image
 itself -- the count is the same) -- and the crops' own row statistics, on the host -- and the counters of the listed conv3 (trexhip_identify_skip3_stats): row pairs of the batch, row pairs listed, the passes its listed
 form walked (0: the dense kernel ran) against the dense kernel's, bytes of act3 filled from the empty crop's -- and those of the listed fc1
-(trexhip_identify_fc1_stats): crop-plane rows of the batch and the rows it computed.  Nothing here is timed.  One JSON line.
+(trexhip_identify_fc1_stats): crop-plane rows of the batch and the rows it computed -- and those of the windowed conv1+conv2
+(trexhip_identify_skipx_stats): crops that took windowed passes, those passes, the full-width passes the other crops took (the first counters
+keep counting by the row rule alone).  Nothing here is timed.  One JSON line.
    python tools/skip_stats.py"""
 import json
 import os
@@ -26,6 +28,7 @@ lane = pipe.lanes[0]
 passes, listed, filled = lane.seg.skip_stats()
 pairs3, listed3, passes3, filled3 = lane.seg.skip3_stats()
 fc1_rows, fc1_listed = lane.seg.fc1_stats()          # crop-plane rows of the listed fc1 and the rows it computed (0, 0: the dense fc1 ran)
+x_crops, x_passes, x_full = lane.seg.skipx_stats()
 crops = lane.crops[:passes * 3 // 20]
 rows = (crops != 0).any(dim=2)                       # [n][80]: the row holds a non-zero byte
 print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passes": passes, "passes_listed": listed,
@@ -35,5 +38,7 @@ print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passe
                   "conv3_pairs": pairs3, "conv3_pairs_listed": listed3, "conv3_fraction_listed": round(listed3 / max(pairs3, 1), 4),
                   "conv3_listed_passes": passes3, "conv3_dense_passes": (pairs3 * 10 + 63) // 64,
                   "conv3_pass_ratio": round(passes3 / max((pairs3 * 10 + 63) // 64, 1), 4), "act3_bytes_filled": filled3,
-                  "fc1_rows": fc1_rows, "fc1_rows_listed": fc1_listed, "fc1_fraction_listed": round(fc1_listed / max(fc1_rows, 1), 4)}))
+                  "fc1_rows": fc1_rows, "fc1_rows_listed": fc1_listed, "fc1_fraction_listed": round(fc1_listed / max(fc1_rows, 1), 4),
+                  "crops_windowed": x_crops, "windowed_passes": x_passes, "full_width_passes": x_full,
+                  "windowed_passes_per_crop": round(x_passes / max(x_crops, 1), 3)}))
 pipe.close()

@@ -211,7 +211,7 @@ int trexhip_create(const trexhip_params* p, trexhip_ctx** out) {
     // TREXHIP_CONV_GEOM: any of bits 0-11 selects the fp32-activation chain of the identity network; bit 28 keeps conv1 and conv2 apart,
     // bit 29 forces the role-split conv1+conv2 kernel, bit 30 the two-workgroups-per-CU one; bit 27 makes the role-split kernel compute every pass, those of
     // background rows too.  The other bits mean nothing.
-    if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e) & (0xfff | (127 << 24));
+    if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e) & (0xfff | (255 << 23));
     if (const char* e = std::getenv("TREXHIP_CCL_BANDS")) ctx->tune_ccl_bands = std::atoi(e);     // same tables whatever the bands
     const size_t B = p->max_batch, H = p->height, W = p->width, R = p->max_runs, NB = p->max_blobs, P = p->max_pixels;
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete ctx; return TREXHIP_E_DEVICE; }

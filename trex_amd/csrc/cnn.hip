@@ -1449,6 +1449,9 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->skip_bands, N * sizeof(int2), who));
         TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4, who));
         TRY(B.device_bytes(&net->skip_list, (n_pass + SKIP_PAD) * 4, who));
+        TRY(B.device_bytes(&net->skipx_cols, N * sizeof(int2), who));
+        TRY(B.device_bytes(&net->skipx_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4 * 4, who));
+        TRY(B.device_bytes(&net->skipx_list, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         const size_t blocks3 = (N + Skip3Geom::BLOCK - 1) / Skip3Geom::BLOCK;
         TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint2), who));
         TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 4, who));
@@ -1475,7 +1478,11 @@ std::vector<LdsAttr>& lds_attrs() { static std::vector<LdsAttr> v; return v; }
 static const ByChannels K_CONV1{Kern(k_conv1<1>, 256, (84 * 84 + 25 * 16) * 4, false), Kern(k_conv1<3>, 256, 3 * (84 * 84 + 25 * 16) * 4, false)};
 static const ByChannels K_CONV1_MFMA{Kern(k_conv1_mfma, 256), Kern(k_conv1_mfma3, 256)};
 static const ByChannels K_CONV1_WPRE{Kern(k_conv1_wpre<1>, 256), Kern(k_conv1_wpre<3>, 256)};
-static const Kern K_CONV12_RS(k_conv12_rs, 512, W12RGeom::LDS_BYTES);
+static const Kern K_CONV12_RS(k_conv12_rs<W12RGeom>, 512, W12RGeom::LDS_BYTES);
+static const Kern K_CONV12_RSX(k_conv12_rs<W12XGeom>, 512, W12XGeom::LDS_BYTES);
+static const Kern K_PASSX_COUNT(k_passx_count, SKIP_LB);
+static const Kern K_PASSX_LIST(k_passx_list, SKIP_LB);
+static const Kern K_V3_FILLX(k_v3_fillx, 256);
 static const Kern K_CONV12_WPRE(k_conv12_wpre, 256, W12Geom::LDS_BYTES);
 static const Kern K_CROP_BANDS(k_crop_bands, 256);
 static const Kern K_PASS_COUNT(k_pass_count, SKIP_LB);
@@ -1578,6 +1585,7 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->act3e, (size_t)Skip3Geom::PAIRS * 10 * 128 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->fc1e, (size_t)FC1_KSPLIT * 128 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->d_skip, SK_WORDS * 4, who);
+    if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->act2e, (size_t)SkipGeom::V3_ROWS * 20 * 64 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&zero, SkipGeom::CROP_ROWS * 80, who);
     if (rc != TREXHIP_OK) return rc;
     const CnnPlan p = cnn_plan(80, 80, 1, TREXHIP_CNN_FP16X3, true, (1 << 29) | (1 << 27), 1, ctx->n_cus);
@@ -1585,7 +1593,7 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     TH_CHECK_HIP(hipMemsetAsync(net->d_skip, 0, SK_WORDS * 4, ctx->stream));
     TH_CHECK_HIP(hipMemsetAsync(zero, 0, SkipGeom::CROP_ROWS * 80, ctx->stream));
     K_CONV12_RS(ctx->stream, p.conv2.grid, zero, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3e, net->inv2w, net->d_skip + SK_EMPTY_RANGE, 1,
-                net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr);
+                net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr, net->act2e);
     TH_CHECK_HIP(hipGetLastError());
     TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV3_WPAIR.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV3_WPAIR.lds));
     K_CONV3_WPAIR(ctx->stream, p.conv3.grid, net->v3e, net->w3w, net->b3, net->act3e, net->inv3w, 1, net->d_skip + SK3_EMPTY_CTR, p.n_big3, nullptr, nullptr, nullptr);
@@ -1632,20 +1640,33 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         case Chain::ROLE_SPLIT:
             if (p.skip) {      // which passes the crops need, and the rows of the others (cnn_skip_kernels.h); the decisions stay on the device
                 const int lb = ceil_div(p.conv2.items, SKIP_LB);
-                K_CROP_BANDS(s, ceil_div(n, 4), d_crops, n, net.skip_bands);
-                K_PASS_COUNT(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts);
-                K_PASS_LIST(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts, net.skip_list);
+                K_CROP_BANDS(s, ceil_div(n, 4), d_crops, n, net.skip_bands, p.skipx ? net.skipx_cols : nullptr);
+                if (p.skipx) {     // two lists: the windowed passes of the crops that have a window, the full-width passes the others need
+                    K_PASSX_COUNT(s, lb, net.skip_bands, net.skipx_cols, n, net.d_skip, net.skipx_counts);
+                    K_PASSX_LIST(s, lb, net.skip_bands, net.skipx_cols, n, net.d_skip, net.skipx_counts, net.skip_list, net.skipx_list);
+                } else {
+                    K_PASS_COUNT(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts);
+                    K_PASS_LIST(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts, net.skip_list);
+                }
                 if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
                     K_PAIR_COUNT(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
                     K_PAIR_LIST(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
                     // the crops each plane of the listed fc1 computes: from the bands alone, so here and not between conv3 and fc1
                     if (p.fc1_listed) K_FC1_LIST(s, Skip3Geom::PAIRS, net.skip_bands, n, net.d_skip, net.fc1_list, net.max_crops);
                 }
-                K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3),
-                          (int)direct);
+                if (p.skipx)
+                    K_V3_FILLX(s, ceil_div(n * SkipGeom::V3_ROWS, SKIPX_FB), net.skip_bands, net.skipx_cols, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e),
+                               reinterpret_cast<uint4*>(net.v3), (int)direct);
+                else
+                    K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3),
+                              (int)direct);
             }
+            // (an instance whose list is empty returns at once)
+            if (p.skipx)
+                K_CONV12_RSX(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.d_skip + SKX_CTR,
+                             p.pk2, net.d_ovfc, net.skipx_list, net.d_skip + SKX_PASSES, net.act2e);
             K_CONV12_RS(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
-                        p.pk2, net.d_ovfc, p.skip ? net.skip_list : nullptr, p.skip ? net.d_skip + SK_LEN : nullptr);
+                        p.pk2, net.d_ovfc, p.skip ? net.skip_list : nullptr, p.skip ? net.d_skip + (p.skipx ? SKX_FULL : SK_LEN) : nullptr, nullptr);
             break;
         case Chain::FUSED_2WG:
             K_CONV12_WPRE(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
@@ -1829,6 +1850,18 @@ int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* li
     if (passes) *passes = w[SK_NPASS];
     if (listed) *listed = w[SK_LEN];
     if (bytes_filled) *bytes_filled = (uint64_t)w[SK_FILLED] * V3_ROWB;
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_skipx_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes) {
+    if (!ctx || !ctx->net) { set_error("trexhip_identify_skipx_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
+    Net* net = static_cast<Net*>(ctx->net);
+    uint32_t w[SK_WORDS] = {};
+    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    if (crops_windowed) *crops_windowed = w[SKX_CROPS];
+    if (windowed_passes) *windowed_passes = w[SKX_PASSES];
+    if (full_passes) *full_passes = w[SKX_FULL];
     return TREXHIP_OK;
 }
 

@@ -28,6 +28,10 @@
 //
 // LDS: the four operand planes (ring of NR = 10 row slots + the zero row, as before: P2 writes the ring in the stage where no tap reads it),
 // pbufE (consumer -> producer), pbufP (conv1's pooled activations of a chunk), the padded fp16 crop rows of a chunk: 93 KB.
+//
+// The geometry is a template parameter (W12RGeomT): the full-width instance is the kernel described above; the windowed instance (cnn_skipx.h)
+// computes 8 of a row's 10 tiles for up to 4 row pairs of one crop per pass -- 64 of 64 M-slots, a ring of 12 rows x 8 tiles, chunks of 8 rows,
+// 108 KB of LDS and 12 resident taps -- and is told at the kernel.
 
 // max of three / two floats as ONE instruction each (the compiler's fmaxf puts a canonicalising v_max v, v, v in front of operands it does not
 // know to be canonical); exact, so results do not change.  ONLY for operands written by ordinary VALU instructions: an MFMA result read by
@@ -49,9 +53,27 @@ __host__ __device__ constexpr int rs_pg(const int tau) {
 }
 __host__ __device__ constexpr int rs_pos(const int tau) { return tau / 20 == 0 ? (rs_pg(tau) == 3 ? 7 : rs_pg(tau)) : 3 + rs_pg(tau); }
 
-struct W12RGeom {
-    using G = W2bGeom;
-    static constexpr int CHUNK = 6;
+// the windowed instance's V2 geometry (cnn_skipx.h): a pass = RPP = 4 row pairs x WT = 8 tiles of ONE crop, a ring row holds WT tiles
+struct W2xGeom {
+    static constexpr int CO = 64, S = 40, TPP = 2 * SkipXGeom::WT, RPP = SkipXGeom::RPP, NR = SkipXGeom::NR;
+    static constexpr int KH = 5, POOL = 2;
+    static constexpr int ROWL = 4 * SkipXGeom::WT * 32;                 // one (row, piece, group): 4 positions x WT tiles x 32 B
+    static constexpr int PLANE = (NR + 1) * ROWL, BUF = 2 * PLANE;
+    static constexpr int PBUF_OFF = 2 * BUF;
+    static constexpr int BV = 2 * 2 * CO;
+    static_assert(RPP * TPP == 64 && NR == POOL * RPP + KH - 1, "64 M-slots, the V2 rows a pass reads");
+};
+
+// GG: the V2 geometry; CHUNK_: V2 rows the producers make per three stages; TPR_: tiles per ring row; NW1_: conv1 windows (4 outputs = 2 pooled
+// pixels) per V2 row; NT1_: conv1 tiles per producer wave and step; WIN_: the windowed instance
+template <class GG, int CHUNK_, int TPR_, int NW1_, int NT1_, bool WIN_>
+struct W12RGeomT {
+    using G = GG;
+    static constexpr bool WIN = WIN_;
+    static constexpr int CHUNK = CHUNK_, TPR = TPR_, NW1 = NW1_, NT1 = NT1_;
+    static constexpr int SLOTS = G::RPP * G::TPP;                       // M-slots in use
+    static constexpr int E2_ITEMS = G::RPP * 80;                        // (pooled row, conv3 tile, channel quad)
+    static_assert(G::TPP == 2 * TPR && SLOTS <= 64 && CHUNK * 30 <= 256 && CHUNK * 4 * TPR <= 256, "items per stage: one per producer thread");
     static constexpr int IMG_PITCH = 88, IMG_ROWS = CHUNK * 6;
     // pbufE: the pass's 3 x 20 x 64 pooled activations of conv2 (fp32), rows padded by two zero pixels on either side: the V3 transform's 8-pixel
     // windows read their halo as plain loads (no clamps, no selects); pbufP: conv1's pooled activations of a chunk, rows of 40 pixels in a pitch of
@@ -72,6 +94,11 @@ struct W12RGeom {
     // lives in slot tau
     static constexpr bool resident(const int tau) { return tau < NRES; }
 };
+using W12RGeom = W12RGeomT<W2bGeom, 6, 10, 20, 4, false>;
+// the windowed instance: 8 rows x 18 windows = 18 conv1 tiles, three a wave and step, two steps (five in one step spill registers, four leave
+// two waves a second step of their own: 128 MFMAs on the longest wave against 96); the windows of a row start at window
+// clamp(2 t0 - 1, 0, 20 - NW1): V2 columns 4 t0 - 2 .. 4 t0 + 4 WT + 1, clipped to the crop
+using W12XGeom = W12RGeomT<W2xGeom, SkipXGeom::CHUNK, SkipXGeom::WT, 2 * SkipXGeom::WT + 2, 3, true>;
 
 // Tuning (round 5, profiles/r05_rs_ablation.txt):
 //   RS_BD 3       weight fragments 3 taps ahead (2 / 5 taps: 3.99 / 4.01 against 3.90-3.98 ms)
@@ -81,6 +108,17 @@ struct W12RGeom {
 //                 3.58-3.60)
 // Measured and not kept: two taps at a time with their products interleaved, consecutive MFMAs on different accumulators (4.09 / 3.81-3.83 against 3.69)
 static constexpr int RS_BD = 3, RS_TSPLIT = 20, RS_PRIO = 0x201;
+// F = W12RGeom: the full-width instance, passes of 3 row pairs x 10 tiles numbered through the batch.  F = W12XGeom: the windowed instance
+// (cnn_skipx.h): it always walks a list, whose entries name (crop, first V3 row, rows, t0) -- a pass holds one crop, 8 of its 10 tiles from t0
+// on, up to 4 row pairs.  Its P1 runs conv1 over the windows those tiles' V2 input needs (the x halo is real pixels, zero padding only at the
+// crop's edge), its P2 writes 8 tiles per ring row, its consumers' slot s = (row pair s / 16, tile (s % 16) / 2, parity s % 2) writes pooled
+// pixel 2 (t0 + tile) of pbufE; the pooled pixels outside the window are copied from act2e -- the empty crop's, bit for bit -- by the producers
+// in stage 2, loaded in front of conv1 and stored behind it.  E2 stays full width: it writes whole V3 rows.  The taps, their order, the fold and
+// the output transform are the same instructions: per output element the arithmetic does not depend on the slot it lands in.
+// act2e: full width: where not null, the pooled conv2 activations [n_crops * 20][20][64] are written there as well (the run on the empty crop,
+// once per loaded network); windowed: that image of the empty crop, read.
+// A round's barriers: rs_round_stages (cnn_skipx.h), called by both roles on the same new rows.
+template <class F>
 __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ crops /*[N][80][80]*/, const uint4* __restrict__ w1tab /*[16][64]*/,
                                                    const float* __restrict__ bias1, const float inv_scale1,
                                                    const uint4* __restrict__ wp /*[5][8][2][2][64] x 16 B*/, const float* __restrict__ bias,
@@ -88,9 +126,8 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                                                    const int n_crops, uint32_t* __restrict__ pass_ctr, const int PK /* consecutive passes per ticket */,
                                                    uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */,
                                                    const int* __restrict__ list /* the passes to compute, in order (cnn_skip_kernels.h); null: every pass */,
-                                                   const uint32_t* __restrict__ list_len) {
-    using G = W2bGeom;
-    using F = W12RGeom;
+                                                   const uint32_t* __restrict__ list_len, float* __restrict__ act2e) {
+    using G = typename F::G;
     constexpr int CO = 64, S = 40;
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -135,18 +172,28 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
     };
     // every wave: LDS writes done, then the workgroup barrier.  Both roles execute the SAME number of these per round.
 #define RS_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+    // a pass (full width: its number; windowed: its list entry) as the V3 rows gp0 .. gp0 + rows - 1 of the batch and its first tile
+    auto rs_gp0 = [&](const int e) { if constexpr (F::WIN) { const SkipXPass x = skipx_unpack(e); return x.crop * (S / 2) + x.r0; } else return e * G::RPP; };
+    auto rs_nrw = [&](const int e) {
+        if constexpr (F::WIN) return skipx_unpack(e).rows;
+        else { const int left = total_pairs - e * G::RPP; return left < G::RPP ? left : G::RPP; }
+    };
+    // row pair rp of a pass as a V3 row of the batch; behind a short pass's last row: that row again
+    auto rs_row = [&](const int e, const int rp) {
+        if constexpr (F::WIN) { const SkipXPass x = skipx_unpack(e); return x.crop * (S / 2) + x.r0 + (rp < x.rows ? rp : x.rows - 1); }
+        else { const int gp = e * G::RPP + rp; return gp < total_pairs ? gp : total_pairs - 1; }
+    };
+    auto rs_t0 = [&](const int e) { if constexpr (F::WIN) return skipx_unpack(e).t0; else return 0; };
 #define RS_ROWS(pass_, qmin_, nrows_)                                                                                            \
     do {                                                                                                                         \
-        const int gp0_ = (pass_) * G::RPP;                                                                                       \
-        int gpl_ = gp0_ + G::RPP - 1;                                                                                            \
-        gpl_ = gpl_ < total_pairs ? gpl_ : total_pairs - 1;                                                                      \
-        const int y0_ = (2 * gp0_) % S, yl_ = (2 * gpl_) % S + 1;                                                                \
-        qmin_ = 2 * gp0_ - (y0_ >= 2 ? 2 : 0);                                                                                   \
-        nrows_ = 2 * gpl_ + 1 + (yl_ + 2 <= S - 1 ? 2 : 0) - qmin_ + 1;                                                          \
+        const int gp0_ = rs_gp0(pass_);                                                                                          \
+        const SkipXV2 v_ = rs_v2_rows(gp0_, gp0_ + rs_nrw(pass_) - 1);                                                           \
+        qmin_ = v_.qmin;                                                                                                         \
+        nrows_ = v_.nrows;                                                                                                       \
     } while (0)
     // the rows the NEXT pass needs that are not in the ring yet: [lo, hi); the next pass itself (the last pass of a ticket moves on to the
     // ticket drawn one round earlier).  Computed identically by every wave.
-#define RS_NEXT(pass_, res_hi_, nslot_, next_, have_, lo_, hi_)                                                                  \
+#define RS_NEXT(pass_, res_hi_, nslot_, next_, have_, lo_, hi_, extra_)                                                                \
     do {                                                                                                                         \
         const bool draw_ = tleft == 1;                                                                                           \
         nslot_ = draw_ ? __builtin_amdgcn_readfirstlane(*s_next) : slot + 1;                                                     \
@@ -158,11 +205,13 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         }                                                                                                                        \
         lo_ = hi_ = 0;                                                                                                           \
         if (have_) {                                                                                                             \
-            int qn_, nn_;                                                                                                        \
-            RS_ROWS(next_, qn_, nn_);                                                                                            \
-            lo_ = (next_ == (pass_) + 1 && (res_hi_) > qn_) ? (res_hi_) : qn_;                                                   \
-            hi_ = qn_ + nn_;                                                                                                     \
+            const int gn_ = rs_gp0(next_);                                                                                       \
+            const bool follows_ = F::WIN ? gn_ == rs_gp0(pass_) + rs_nrw(pass_) : next_ == (pass_) + 1;                          \
+            const SkipXV2 nw_ = rs_new_rows(follows_, res_hi_, gn_, gn_ + rs_nrw(next_) - 1);                                    \
+            lo_ = nw_.qmin;                                                                                                      \
+            hi_ = lo_ + nw_.nrows;                                                                                               \
         }                                                                                                                        \
+        extra_ = rs_round_chunks(hi_ - lo_, F::CHUNK) - 1;                                                                       \
     } while (0)
     __syncthreads();
 
@@ -217,12 +266,14 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             bf[8 + f] = make_uint4(0u, b.x, b.y, b.z);
             bf[12 + f] = make_uint4(0u, b.x << 16, __builtin_amdgcn_alignbit(b.y, b.x, 16), __builtin_amdgcn_alignbit(b.z, b.y, 16));
         }
-        auto p1 = [&](const int nr) {
+        auto p1 = [&](const int nr, const int tw /* windowed: the pass's first tile */) {
             const int r = lane & 15, q4 = lane >> 4;
-            const int n_win = nr * 20, n_tiles = (n_win + 7) >> 3;
-            // all (up to four) tiles of the wave in one step (t0, t0 + 4, t0 + 8, t0 + 12): every LDS read first, then the sixteen product chains, then
+            constexpr int NW = F::NW1;
+            const int wb = F::WIN ? (2 * tw - 1 < 0 ? 0 : 2 * tw - 1 > 20 - NW ? 20 - NW : 2 * tw - 1) : 0;      // the first window of a row
+            const int n_win = nr * NW, n_tiles = (n_win + 7) >> 3;
+            // all (up to NT1) tiles of the wave in one step (t0, t0 + 4, t0 + 8, t0 + 12): every LDS read first, then the sixteen product chains, then
             // the pooling -- the vector part of the stage then runs beside the consumers' taps instead of between two bursts of matrix work
-            constexpr int NT1 = 4;
+            constexpr int NT1 = F::NT1;
             for (int t0 = rw; t0 < n_tiles; t0 += 4 * NT1) {
                 f16x8 a1[NT1], a2[NT1];
 #pragma unroll
@@ -230,7 +281,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                     const int tile = t0 + 4 * u < n_tiles ? t0 + 4 * u : t0;
                     int wdx = tile * 8 + (r >> 1);
                     wdx = wdx < n_win ? wdx : n_win - 1;
-                    const int v = wdx / 20, x4 = (wdx - v * 20) * 4;
+                    const int v = wdx / NW, x4 = (wb + wdx - v * NW) * 4;
                     const int row = v * 6 + (r & 1);
                     const _Float16* p1a = img + (row + q4) * F::IMG_PITCH + x4;
                     const _Float16* p2a = img + (row + 4) * F::IMG_PITCH + x4;
@@ -271,7 +322,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                         const float v0 = rs_max3z(rs_max3(t0, t1, t2), t3), v1 = rs_max3z(rs_max3(t4, t5, t6), t7);
                         if (tile < n_tiles && w < n_win) {
                             ovfm = rs_max3(ovfm, v0, v1);
-                            const int vr = w / 20, px = vr * F::PPP + 4 + 2 * (w - vr * 20);     // row of the chunk, padded pixel index (even)
+                            const int vr = w / NW, px = vr * F::PPP + 4 + 2 * (wb + w - vr * NW);     // row of the chunk, padded pixel index (even)
                             float* o = pbp + ((px & ~15) | ((px & 3) << 2) | ((px >> 2) & 3)) * 16 + r;
                             o[0] = v0;
                             o[64] = v1;                                          // px + 1: bit 0 of the pixel is bit 2 of the slot
@@ -281,15 +332,15 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             }
         };
         // P2: (V2 row v, conv2 tile tx, channel quad): 8 pooled pixels x 4 channels -> B^T d -> pieces -> the ring slots (q % NR + 1) of the planes
-        auto p2 = [&](const int c0, const int nr) {
-            if (rt < nr * 40) {
-                const int v = rt / 40, rem = rt - v * 40, tx = rem >> 2, quad = rem & 3;
+        auto p2 = [&](const int c0, const int nr, const int tw) {
+            if (rt < nr * (4 * F::TPR)) {
+                const int v = rt / (4 * F::TPR), rem = rt - v * (4 * F::TPR), tx = rem >> 2, quad = rem & 3;
                 const int q = c0 + v;
                 const int slot = q % G::NR + 1, rot = w2b_rot(slot);
                 float4 d[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const int px = v * F::PPP + 4 * tx + 2 + k;                  // x = 4 tx - 2 + k in the padded row: the halo pixels are zeros
+                    const int px = v * F::PPP + 4 * (tw + tx) + 2 + k;           // x = 4 (tile of the row) - 2 + k in the padded row: the halo pixels of the crop's edge are zeros
                     d[k] = *reinterpret_cast<const float4*>(pbp + ((px & ~15) | ((px & 3) << 2) | ((px >> 2) & 3)) * 16 + quad * 4);
                 }
                 float ua[8], ub[8], uc[8], ud[8];
@@ -301,7 +352,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
 #pragma unroll
                 for (int p = 0; p < 8; ++p) {
                     const int pi = p < 3 ? p : (p == 7 ? 3 : p + 1);             // stored order 0,1,2,7 | 3,4,5,6: group = pi >> 2, place pi & 3
-                    const int w = (pi & 3) * 20 + tx * 2 + (quad >> 1);
+                    const int w = (pi & 3) * (2 * F::TPR) + tx * 2 + (quad >> 1);
                     uint8_t* dst = rowb + (pi >> 2) * G::BUF + ((w & ~15) | ((w + rot) & 15)) * 16;
                     uint32_t l0, l1, m0, m1;
                     split2h_pair(ua[p], ub[p], l0, m0);
@@ -313,10 +364,21 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         };
         // E2: the V3 transform of pass `ep`: (pooled row, conv3 tile, channel quad) items of pbufE -> B^T d -> pieces -> V3
         auto e2 = [&](const int ep) {
-            if (rt < 240) {
-                const int rp = rt / 80, rem = rt - rp * 80, tx = rem >> 4, quad = rem & 15;
-                const int gp = ep * G::RPP + rp;                            // = q3: pooled row of the batch
-                if (gp < total_pairs) {
+            const int egp0 = rs_gp0(ep), enrw = rs_nrw(ep);
+            if constexpr (!F::WIN) {
+                if (act2e) {                                               // the run on the empty crop: the pooled activations themselves as well
+                    for (int i = rt; i < G::RPP * 20 * 16; i += 256) {
+                        const int rp = i / 320, rem = i - rp * 320, x = rem >> 4, c4 = rem & 15;
+                        if (rp < enrw)
+                            *reinterpret_cast<float4*>(act2e + ((size_t)(egp0 + rp) * 20 + x) * 64 + c4 * 4) =
+                                *reinterpret_cast<const float4*>(pbe + (rp * F::PEP + 2 + x) * 64 + c4 * 4);
+                    }
+                }
+            }
+            auto e2_item = [&](const int it) {
+                const int rp = it / 80, rem = it - rp * 80, tx = rem >> 4, quad = rem & 15;
+                const int gp = egp0 + rp;                                   // = q3: pooled row of the batch
+                if (rp < enrw) {
                     float4 d[8];
                     const float* src = pbe + (rp * F::PEP + 4 * tx) * 64 + quad * 4;      // x = 4 tx - 2 in the padded row: the halo pixels are zeros
 #pragma unroll
@@ -336,27 +398,52 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                         *reinterpret_cast<uint2*>(dst + v3_off(p, 1)) = make_uint2(m0, m1);
                     }
                 }
+            };
+            // full width: 240 items, one per thread; windowed: 320, the first wave takes a second one
+            static_assert(F::E2_ITEMS <= 256 || (F::WIN && F::E2_ITEMS <= 320), "items of the V3 transform");
+            if (rt < (F::E2_ITEMS < 256 ? F::E2_ITEMS : 256)) e2_item(rt);
+            if constexpr (F::E2_ITEMS > 256) { if (rt < F::E2_ITEMS - 256) e2_item(rt + 256); }
+        };
+        // windowed: the pooled pixels of pass `ps` outside its window (20 - 2 WT = 4 per row) <- the empty crop's: one float4 per producer thread.
+        // pbufE is read in stage 1 (E2) and written by the consumers in stage 3, inside the window only; this runs in stage 2
+        auto bg_load = [&](const int ps, float4& bg) {
+            if constexpr (F::WIN) {
+                const SkipXPass x = skipx_unpack(ps);
+                const int rp = rt >> 6, k = (rt >> 4) & 3, c4 = rt & 15;
+                const int px = k < 2 * x.t0 ? k : k + 2 * F::TPR;
+                bg = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (rp < x.rows) bg = *reinterpret_cast<const float4*>(act2e + ((x.r0 + rp) * 20 + px) * 64 + c4 * 4);
+            }
+        };
+        auto bg_store = [&](const int ps, const float4 bg) {
+            if constexpr (F::WIN) {
+                static_assert(!F::WIN || (G::RPP * (20 - 2 * F::TPR) * 16 == 256), "one item per producer thread");
+                const int t0 = skipx_unpack(ps).t0;
+                const int rp = rt >> 6, k = (rt >> 4) & 3, c4 = rt & 15;
+                const int px = k < 2 * t0 ? k : k + 2 * F::TPR;
+                *reinterpret_cast<float4*>(pbe + (rp * F::PEP + 2 + px) * 64 + c4 * 4) = bg;
             }
         };
         // prologue: every row of the first pass, chunk by chunk (three barriers each; the consumers wait at them)
-        for (int c0 = qmin; c0 < qmin + nrows; c0 += F::CHUNK) {
+        for (int c = 0, c0 = qmin; c < rs_round_chunks(nrows, F::CHUNK); ++c, c0 += F::CHUNK) {
             const int nr = qmin + nrows - c0 < F::CHUNK ? qmin + nrows - c0 : F::CHUNK;
             uint4 px;
             p0_load(c0, nr, px);
             p0_store(nr, px);
             RS_BAR();
-            p1(nr);
+            p1(nr, rs_t0(pass));
             flag_crops(c0, c0 + nr - 1, S);
             RS_BAR();
-            p2(c0, nr);
+            p2(c0, nr, rs_t0(pass));
             RS_BAR();
         }
         int res_hi = qmin + nrows;
         int prev = -1;
         for (;;) {
-            int next_slot, next_pass, lo, hi;
+            int next_slot, next_pass, lo, hi, extra;
             bool have_next;
-            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi);
+            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi, extra);
+            const int tn = have_next ? rs_t0(next_pass) : 0;
             // S1 (beside taps 0-19): the crop rows of the first chunk are requested, the V3 transform of the previous pass runs under their flight
             const int nr0 = hi - lo < F::CHUNK ? hi - lo : F::CHUNK;
             uint4 px;
@@ -364,23 +451,26 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             if (prev >= 0) e2(prev);
             p0_store(nr0, px);
             RS_BAR();
-            // S2 (beside taps 20-39): conv1
-            p1(nr0);
+            // S2 (beside taps 20-39): conv1; windowed: around it the pooled pixels of this pass that lie outside its window
+            float4 bg = make_float4(0.f, 0.f, 0.f, 0.f);
+            bg_load(pass, bg);
+            p1(nr0, tn);
             if (nr0 > 0) flag_crops(lo, lo + nr0 - 1 < total_rows ? lo + nr0 - 1 : total_rows - 1, S);
+            bg_store(pass, bg);
             RS_BAR();
             // S3 (beside the output transform; nobody reads the ring): the rows go to their slots
-            p2(lo, nr0);
+            p2(lo, nr0, tn);
             RS_BAR();
-            // a ticket's first pass needs 10 rows: the second chunk in three more stages (the consumers wait)
-            for (int c0 = lo + F::CHUNK; c0 < hi; c0 += F::CHUNK) {
+            // a ticket's first pass needs more rows than a chunk: the further chunks in three more stages each (the consumers wait)
+            for (int c = 0, c0 = lo + F::CHUNK; c < extra; ++c, c0 += F::CHUNK) {
                 const int nr = hi - c0 < F::CHUNK ? hi - c0 : F::CHUNK;
                 p0_load(c0, nr, px);
                 p0_store(nr, px);
                 RS_BAR();
-                p1(nr);
+                p1(nr, tn);
                 flag_crops(c0, c0 + nr - 1 < total_rows ? c0 + nr - 1 : total_rows - 1, S);
                 RS_BAR();
-                p2(c0, nr);
+                p2(c0, nr, tn);
                 RS_BAR();
             }
             prev = pass;
@@ -402,7 +492,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         const int boff = (h * CO + n * 32 + j) * 16;
         const int co = n * 32 + j;
         const float bz = bias[co];
-        for (int c0 = qmin; c0 < qmin + nrows; c0 += F::CHUNK) { RS_BAR(); RS_BAR(); RS_BAR(); }      // the producers' prologue
+        for (int c = 0; c < rs_round_chunks(nrows, F::CHUNK); ++c) { RS_BAR(); RS_BAR(); RS_BAR(); }      // the producers' prologue
         int res_hi = qmin + nrows;
 #define W2_POS(tau_) rs_pos(tau_)
 #define W2_BOFF(tau_) ((rs_ky(tau_) * 8 + W2_POS(tau_)) * G::BV * 16)
@@ -433,15 +523,14 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             s_ = s_ < G::RPP * G::TPP ? s_ : G::RPP * G::TPP - 1;
             const int r2_ = s_ % G::TPP, tx_ = r2_ >> 1;
 #pragma unroll
-            for (int pg = 0; pg < 4; ++pg) { const int w_ = pg * 20 + tx_ * 2 + h; wh[pg] = (w_ & ~15) * 16; wl[pg] = w_ & 15; }
+            for (int pg = 0; pg < 4; ++pg) { const int w_ = pg * (2 * F::TPR) + tx_ * 2 + h; wh[pg] = (w_ & ~15) * 16; wl[pg] = w_ & 15; }
         }
 #define RS_AOFF(ps_)                                                                                                             \
         do {                                                                                                                     \
             int s_ = mg * 32 + j;                                                                                                \
             s_ = s_ < G::RPP * G::TPP ? s_ : G::RPP * G::TPP - 1;                                                                \
             const int rp_ = s_ / G::TPP, r2_ = s_ - rp_ * G::TPP;                                                                \
-            int gp_ = (ps_) * G::RPP + rp_;                                                                                      \
-            gp_ = gp_ < total_pairs ? gp_ : total_pairs - 1;                                                                     \
+            const int gp_ = rs_row(ps_, rp_);                                                                                    \
             const int qo_ = 2 * gp_ + (r2_ & 1), y_ = qo_ % S;                                                                   \
             _Pragma("unroll") for (int ky = 0; ky < G::KH; ++ky) {                                                               \
                 const int iy_ = y_ + ky - G::KH / 2;                                                                             \
@@ -452,9 +541,9 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
 #define RS_AUNIT(tau_) do { if ((tau_) < 20) aoff[rs_ky(tau_)][rs_pg(tau_)] = srow[rs_ky(tau_)] + (wh[rs_pg(tau_)] | (((wl[rs_pg(tau_)] + srot[rs_ky(tau_)]) & 15) << 4)); } while (0)
         RS_AOFF(pass);
         for (;;) {
-            int next_slot, next_pass, lo, hi;
+            int next_slot, next_pass, lo, hi, extra;
             bool have_next;
-            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi);
+            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi, extra);
             const bool draw = tleft == 1;
             uint32_t ticket = 0;
             // the ticket after the next one (raw instruction: atomicAdd() waits for the returned value on the spot); stored behind the second barrier
@@ -531,6 +620,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             }
             RS_BAR();                                                     // S2 | S3: the producers have read pbufE (in S1), it may be written
             __builtin_amdgcn_s_setprio(RS_PRIO & 3);
+            const int t0c = rs_t0(pass);
             // output transform: Y = A^T M, pool, bias, ReLU -> the pass's 3 x 20 x 64 activations as fp32 in pbufE
             f32x16 y0 = acc[0], y1 = acc[2], y2 = acc[1], y3 = acc[7];      // positions 0-4 were folded in by rs_fold under the taps
             {
@@ -547,15 +637,15 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                     const int rp = s / G::TPP, tx = (s - rp * G::TPP) >> 1;
                     const float a0 = fmaxf(v0 * out_scale + bz, 0.f), a1 = fmaxf(v1 * out_scale + bz, 0.f);
                     ovfm = rs_max3(ovfm, a0, a1);
-                    float* o = pbe + (rp * F::PEP + 2 + 2 * tx) * 64 + co;
+                    float* o = pbe + (rp * F::PEP + 2 + 2 * (t0c + tx)) * 64 + co;
                     o[0] = a0;
                     o[64] = a1;
                 }
             }
-            { const int g0 = pass * G::RPP, g1 = g0 + G::RPP - 1; flag_crops(g0, g1 < total_pairs ? g1 : total_pairs - 1, S / 2); }
+            { const int g0 = rs_gp0(pass); flag_crops(g0, g0 + rs_nrw(pass) - 1, S / 2); }
             if (have_next) RS_AOFF(next_pass);
             RS_BAR();                                                     // S3 | the next round
-            for (int c0 = lo + F::CHUNK; c0 < hi; c0 += F::CHUNK) { RS_BAR(); RS_BAR(); RS_BAR(); }    // the second chunk of a ticket's first pass
+            for (int c = 0; c < extra; ++c) { RS_BAR(); RS_BAR(); RS_BAR(); }    // the further chunks of a ticket's first pass
             if (!have_next) break;
             res_hi = hi;
             tleft = tleft == 1 ? PK : tleft - 1;

@@ -4,6 +4,7 @@
 #include "cnn_plan.h"
 #include "cnn_skip.h"
 #include "cnn_skip3.h"
+#include "cnn_skipx.h"
 #include <tuple>
 
 namespace trexhip {
@@ -37,6 +38,11 @@ struct Net {
     int2* skip_bands = nullptr;                // [max_crops] first / last non-zero row
     uint32_t* skip_counts = nullptr;           // needed passes per SKIP_LB passes
     int* skip_list = nullptr;                  // the passes to compute, in order, + the SKIP_PAD entry behind them
+    // the windowed conv1+conv2 (cnn_skipx.h)
+    float* act2e = nullptr;                    // the pooled conv2 activations of an all-zero crop [20][20][64], made by the run that makes v3e
+    int2* skipx_cols = nullptr;                // [max_crops] first / last non-zero column
+    int* skipx_list = nullptr;                 // the windowed passes (skipx_pack), in order, + the SKIP_PAD entry behind them
+    uint32_t* skipx_counts = nullptr;          // per SKIP_LB passes / crops: full-width passes, aligned needed passes, windowed passes, windowed crops
     // computing only the row pairs of conv3 whose V3 rows hold more than background (cnn_skip3.h, cnn_skip_kernels.h)
     float* act3e = nullptr;                    // the act3 of an all-zero crop [10][10][128], made when the weights are loaded, behind v3e
     uint2* skip3_counts = nullptr;             // listed passes and pairs per workgroup of k_pair_count

@@ -5,6 +5,7 @@
 #include "../../include/trexhip.h"
 #include "cnn_geom.h"
 #include "cnn_skip3.h"
+#include "cnn_skipx.h"
 
 namespace trexhip {
 
@@ -17,7 +18,11 @@ namespace trexhip {
 //                once where that form runs; bit 25 keeps the copy -- the fill always runs and the listed form reads every row from V3.
 //                Above 1024 crops, unless bit 24 is set: k_fc1_list beside k_pair_list, and fc1 computes only the (crop, split-K plane) rows whose
 //                row pair is listed -- the listed k_fc1_split<4>; k_head takes the other planes from the empty crop's, k_act3_fill copies no pair.
-//                Bit 24 keeps the dense fc1 and the fill's copy: the chain as it was before fc1 was listed, launch for launch)
+//                Bit 24 keeps the dense fc1 and the fill's copy: the chain as it was before fc1 was listed, launch for launch.
+//                Unless bit 23 is set: k_crop_bands writes the column bands as well, k_passx_count / k_passx_list stand in for k_pass_count /
+//                k_pass_list and make TWO lists -- the windowed passes (8 tiles x up to 4 row pairs of one crop) of the crops whose blob fits 8
+//                tiles, the aligned full-width passes the other crops need -- k_v3_fillx stands in for k_v3_fill, and k_conv12_rs<W12XGeom> runs on
+//                the first list in front of k_conv12_rs<W12RGeom> on the second.  Bit 23 keeps the chain as it was, launch for launch)
 //   FUSED_2WG   k_conv12_wpre (the same, two workgroups per CU)          -> k_conv5_wpair       1 channel, aligned crops, fewer
 //   TWO_KERNEL  k_conv1_wpre -> k_conv2_wpre2                            -> k_conv5_wpair       3 channels, or TREXHIP_CONV_GEOM bit 28
 //   FP32_ACT    conv1 -> act1 -> k_conv5_stream -> act2 -> k_conv5_wino                         unaligned crops, or any of bits 0-11
@@ -59,6 +64,9 @@ struct CnnPlan {
                                     // dense form; off: bit 25, or a batch whose V3 is longer than both images' reach (skip3_direct_fits)
     bool fc1_listed;                // where skip3 is on, fc1 is SPLIT4 and the head BIG: k_fc1_list in front of conv1+conv2, the listed k_fc1_split<4>
                                     // computes only the listed (crop, plane) rows, k_head takes the others from Net::fc1e, k_act3_fill copies nothing; off: bit 24
+    bool skipx;                     // where skip is on: the crops whose blob fits a window of 8 tiles take the windowed instance of the role-split kernel
+                                    // (cnn_skipx.h), the others the full-width one, each on its own list, grid conv2.grid and tickets of pk2 slots; off: bit 23,
+                                    // or a batch of SKIPX_MAX_CROPS (2^22) crops or more, whose crop index a windowed list entry does not hold
 };
 
 inline int ceil_div(const int a, const int b) { return (a + b - 1) / b; }
@@ -116,6 +124,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
     p.conv1_grid = n;
     p.skip = role_split && !(geom & (1 << 27));
     p.skip3 = p.skip && !(geom & (1 << 26));
+    p.skipx = p.skip && !(geom & (1 << 23)) && n < SKIPX_MAX_CROPS;
     if (p.skip3) {
         p.skip3_grid = ceil_div(ceil_div(n, 32 /* Skip3Geom::BLOCK crops per thread */), 256);
         p.act3_fill = {ceil_div(n, 16), n};

@@ -14,6 +14,15 @@
 //                  runs: it never reads them
 // and one for the listed form of k_fc1_split (the rule: skip3_fc1_listed, cnn_skip3.h), beside the two above:
 //   k_fc1_list     a workgroup per split-K plane: the crops whose pair the plane has to compute, in order, and how many they are
+// and, where the windowed conv1+conv2 runs (the rule in x, the windows and the packing: cnn_skipx.h), in the place of k_pass_count, k_pass_list
+// and k_v3_fill:
+//   k_crop_bands   writes the first / last non-zero COLUMN of every crop as well
+//   k_passx_count  per SKIP_LB passes and crops: full-width passes, passes the row rule lists, windowed passes, windowed crops
+//   k_passx_list   TWO lists in order: the windowed passes of the crops that have a window, the aligned full-width passes the other crops need;
+//                  their lengths, the entries behind their ends, the windowed instance's ticket counter zeroed, and the words of k_pass_list
+//                  with the values k_pass_list gives them
+//   k_v3_fillx     k_v3_fill row by row: a row is computed where its crop has a window and needs it, or where its aligned pass is on the
+//                  full-width list
 #pragma once
 
 // the words of Net::d_skip
@@ -31,7 +40,8 @@ static constexpr int SKIP_PAD = 1;        // one entry behind the last one: k_co
 static constexpr int SKIP_FB = 64;        // passes per block of the fill kernel
 
 // one wave per crop: 400 x 16 bytes, unit i lies in row i / 5
-__global__ __launch_bounds__(256) void k_crop_bands(const uint8_t* __restrict__ crops, const int n, int2* __restrict__ bands) {
+// cols (may be null): the first / last non-zero COLUMN as well (cnn_skipx.h), from the same registers
+__global__ __launch_bounds__(256) void k_crop_bands(const uint8_t* __restrict__ crops, const int n, int2* __restrict__ bands, int2* __restrict__ cols) {
     using G = SkipGeom;
     constexpr int UPR = 80 / 16, UNITS = G::CROP_ROWS * UPR;
     const int lane = threadIdx.x & 63, crop = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -59,6 +69,29 @@ __global__ __launch_bounds__(256) void k_crop_bands(const uint8_t* __restrict__ 
         y1 = b > y1 ? b : y1;
     }
     if (lane == 0) bands[crop] = make_int2(y0, y1);
+    if (cols) {                                                          // wave-uniform
+        int x0 = 80, x1 = -1;
+#pragma unroll
+        for (int k = 0; k < (UNITS + 63) / 64; ++k) {
+            const int c0 = ((lane + 64 * k) % UPR) * 16;
+            const uint32_t w4[4] = {px[k].x, px[k].y, px[k].z, px[k].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (w4[j]) {                                             // byte b of the word is column c0 + 4 j + b
+                    const int a = c0 + 4 * j + ((__ffs((int)w4[j]) - 1) >> 3), b = c0 + 4 * j + ((31 - __clz((int)w4[j])) >> 3);
+                    x0 = a < x0 ? a : x0;
+                    x1 = b > x1 ? b : x1;
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int a = __shfl_xor(x0, d), b = __shfl_xor(x1, d);
+            x0 = a < x0 ? a : x0;
+            x1 = b > x1 ? b : x1;
+        }
+        if (lane == 0) cols[crop] = make_int2(x0, x1);
+    }
 }
 
 struct SkipBandsOf {
@@ -110,6 +143,145 @@ __global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ 
         if (p == n_pass - 1) {
             const uint32_t listed_rows = total * SkipGeom::RPP - (need ? (uint32_t)(n_pass * SkipGeom::RPP - total_pairs) : 0u);
             words[SK_LEN] = total; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = (uint32_t)total_pairs - listed_rows;
+        }
+    }
+}
+
+// ---- the windowed conv1+conv2 (cnn_skipx.h): two lists from one pair of kernels ----
+// the words of Net::d_skip that belong to it
+enum : int {
+    SKX_CROPS = 26,          // crops of the last call that took windowed passes
+    SKX_PASSES = 27,         // windowed passes listed by the last call: the length of the windowed instance's list
+    SKX_FULL = 28,           // full-width passes listed by the last call (for the crops without a window): the length of the full-width instance's list
+    SKX_CTR = 29             // the windowed instance's ticket counter (zeroed by k_passx_list)
+};
+static_assert(SKX_CROPS > SK3_LAST && SKX_CTR < SK_WORDS, "behind the words of the listed conv3 and fc1");
+
+struct SkipXWinOf {
+    const int2* bands; const int2* cols; bool all;
+    // a crop without a blob has a window and no pass
+    __host__ __device__ int operator()(const int crop) const { const int2 c = cols[crop]; return skipx_window({c.x, c.y}, all); }
+};
+// thread i of the grid: pass i of the batch (full width: is it needed by a crop without a window; and by the row rule alone, for the counters)
+// and crop i (its windowed passes).  counts[4 b ..]: full-width passes, aligned needed passes, windowed passes, windowed crops of block b
+struct SkipXItem { bool full, need; int wpasses, t0; SkipRows rows; };
+__device__ __forceinline__ SkipXItem skipx_item(const int i, const int n, const int2* __restrict__ bands, const int2* __restrict__ cols, const bool all) {
+    const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
+    SkipXItem it{false, false, 0, -1, {1, 0}};
+    if (i < n_pass) {
+        it.need = skip_needed(i, total_pairs, bands, all);
+        it.full = all || (it.need && skipx_full_needed(i, total_pairs, SkipBandsOf{bands}, SkipXWinOf{bands, cols, all}));
+    }
+    if (i < n) {
+        it.t0 = SkipXWinOf{bands, cols, all}(i);
+        const int2 b = bands[i];
+        it.rows = skip_rows({b.x, b.y});
+        it.wpasses = it.t0 >= 0 ? skipx_passes(it.rows) : 0;
+    }
+    return it;
+}
+__global__ __launch_bounds__(SKIP_LB) void k_passx_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
+                                                         const uint32_t* __restrict__ words, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const SkipXItem it = skipx_item(blockIdx.x * SKIP_LB + threadIdx.x, n, bands, cols, words[SK_EMPTY_RANGE] != 0);
+    uint32_t v[4] = {it.full ? 1u : 0u, it.need ? 1u : 0u, (uint32_t)it.wpasses, it.wpasses ? 1u : 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
+        if ((threadIdx.x & 63) == 0 && v[k]) atomicAdd(&s_cnt[k], v[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) counts[blockIdx.x * 4 + threadIdx.x] = s_cnt[threadIdx.x];
+}
+__global__ __launch_bounds__(SKIP_LB) void k_passx_list(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
+                                                        uint32_t* __restrict__ words, const uint32_t* __restrict__ counts, int* __restrict__ list,
+                                                        int* __restrict__ wlist) {
+    __shared__ uint32_t s_base[4], s_wave[2][SKIP_LB / 64];
+    const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = blockIdx.x * SKIP_LB + tid;
+    if (tid < 4) s_base[tid] = 0;
+    __syncthreads();
+    // what the blocks in front of this one counted
+    uint32_t part[4] = {0, 0, 0, 0};
+    for (int b = tid; b < (int)blockIdx.x; b += SKIP_LB) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part[k] += counts[b * 4 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) part[k] += __shfl_xor(part[k], d);
+        if (lane == 0 && part[k]) atomicAdd(&s_base[k], part[k]);
+    }
+    const SkipXItem it = skipx_item(i, n, bands, cols, words[SK_EMPTY_RANGE] != 0);
+    // inclusive scans over the workgroup: inside the wave by shuffles, the waves' totals through LDS
+    uint32_t sc[2] = {it.full ? 1u : 0u, (uint32_t)it.wpasses};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(sc[k], d); if (lane >= d) sc[k] += v; }
+        if (lane == 63) s_wave[k][wave] = sc[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        uint32_t before = 0;
+        for (int w = 0; w < wave; ++w) before += s_wave[k][w];
+        sc[k] += before;
+    }
+    if (it.full) list[s_base[0] + sc[0] - 1] = i;
+    if (it.wpasses) {
+        const uint32_t at = s_base[2] + sc[1] - (uint32_t)it.wpasses;
+        for (int k = 0; k < it.wpasses; ++k) wlist[at + k] = skipx_pack(skipx_pass(i, it.rows, it.t0, k));
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == SKIP_LB - 1) {               // the last block knows the lengths
+        const uint32_t full = s_base[0] + sc[0], wp = s_base[2] + sc[1];
+        uint32_t need = s_base[1], wc = s_base[3];
+        for (int k = 0; k < 2; ++k) { const uint32_t c = counts[blockIdx.x * 4 + 1 + 2 * k]; if (k) wc += c; else need += c; }
+        for (int k = 0; k < SKIP_PAD; ++k) { list[full + k] = n_pass; wlist[wp + k] = 0; }
+        // SK_LEN, SK_NPASS, SK_FILLED keep their meaning: the aligned passes the row rule lists and the rows outside them
+        const bool last_need = skip_needed(n_pass - 1, total_pairs, bands, words[SK_EMPTY_RANGE] != 0);
+        const uint32_t listed_rows = need * SkipGeom::RPP - (last_need ? (uint32_t)(n_pass * SkipGeom::RPP - total_pairs) : 0u);
+        words[SK_LEN] = need; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = (uint32_t)total_pairs - listed_rows;
+        words[SKX_CROPS] = wc; words[SKX_PASSES] = wp; words[SKX_FULL] = full; words[SKX_CTR] = 0;
+    }
+}
+// with both lists: V3 row r of crop c is computed where c has a window and needs the row, or where its aligned pass is on the full-width list;
+// every other row <- the empty crop's.  A thread looks at one of the block's 256 consecutive V3 rows, then the block copies the rows that are
+// not computed; nothing to copy where the listed conv3 reads the image itself
+static constexpr int SKIPX_FB = 256;
+__global__ __launch_bounds__(SKIPX_FB) void k_v3_fillx(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const uint32_t* __restrict__ words,
+                                                       const uint4* __restrict__ v3e, uint4* __restrict__ v3, const int direct) {
+    using G = SkipGeom;
+    constexpr int ROWQ = V3_ROWB / 16;
+    __shared__ unsigned long long s_fill[SKIPX_FB / 64];
+    if (direct && words[SK3_USE]) return;
+    const bool all = words[SK_EMPTY_RANGE] != 0;
+    const int total_pairs = n * G::V3_ROWS, tid = threadIdx.x, gp0 = blockIdx.x * SKIPX_FB;
+    {
+        const int gp = gp0 + tid;
+        bool fill = false;
+        if (gp < total_pairs && !all) {
+            const int crop = gp / G::V3_ROWS, r = gp - crop * G::V3_ROWS;
+            const SkipXWinOf win{bands, cols, all};
+            bool computed = false;
+            if (win(crop) >= 0) { const int2 b = bands[crop]; const SkipRows need = skip_rows({b.x, b.y}); computed = r >= need.lo && r <= need.hi; }
+            fill = !computed && !skipx_full_needed(gp / G::RPP, total_pairs, SkipBandsOf{bands}, win);
+        }
+        const unsigned long long m = __ballot(fill);
+        if ((tid & 63) == 0) s_fill[tid >> 6] = m;
+    }
+    __syncthreads();
+    for (int w = 0; w < SKIPX_FB / 64; ++w) {
+        unsigned long long m = s_fill[w];
+        while (m) {
+            const int gp = gp0 + w * 64 + __ffsll((long long)m) - 1;
+            m &= m - 1;
+            for (int q = tid; q < ROWQ; q += SKIPX_FB) v3[(size_t)gp * ROWQ + q] = v3e[(gp % G::V3_ROWS) * ROWQ + q];
         }
     }
 }

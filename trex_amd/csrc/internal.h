@@ -172,7 +172,7 @@ struct trexhip_ctx {
     int cnn_mode = TREXHIP_CNN_FP16X3;  // TREXHIP_CNN_*: fp32-class arithmetic on the fp16 matrix cores, range-guarded
 
     bool profiling = false;
-    int tune_conv_geom = 0;             // dev only: which identity-network chain runs (TREXHIP_CONV_GEOM, bits 0-11 and 24-30)
+    int tune_conv_geom = 0;             // dev only: which identity-network chain runs (TREXHIP_CONV_GEOM, bits 0-11 and 23-30)
     // hipFuncSetAttribute is per device: one process may drive several devices through several contexts
     bool attr_cnn = false, attr_ccl = false, attr_split = false, attr_prefilter = false;
     bool ctr_dirty = false;             // a detect pass was queued but not to its end: the per-frame overflow counters may be non-zero (launch_segment zeroes them first)
