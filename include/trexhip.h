@@ -586,7 +586,8 @@ int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* li
  * conv2's output takes windowed passes of the fused conv1+conv2 kernel: 8 tiles of up to 4 output row pairs of that crop alone, the rest taken
  * from images of an all-zero crop made when the weights are loaded; the other crops (and every crop of a network whose background leaves the
  * fp16 range) take the full-width passes as before.  The crops' bytes decide, on the device, in every call; the results are the bits of the
- * full-width kernel.  Bit 23 of TREXHIP_CONV_GEOM (value 8388608) switches this off.
+ * full-width kernel.  Bit 23 of TREXHIP_CONV_GEOM (value 8388608) switches this off: no crop gets a window, the same preparation kernels
+ * make the one list of full-width passes.
  * What the last such call did (waits for the context's stream): *crops_windowed that took windowed passes, *windowed_passes of them, and the
  * aligned *full_passes the other crops took; zeros where the windowed form did not run.  trexhip_identify_skip_stats keeps counting by the row
  * rule alone.  No reference counterpart; any pointer may be NULL.  (ABI 22) */

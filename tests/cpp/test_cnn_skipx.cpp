@@ -7,6 +7,10 @@
 //   packs crop t0                "lo hi crop r0 rows t0" per pass, for every run 0 <= lo <= hi < 20
 //   full y0:y1:x0:x1 ...         one crop per argument: a line of 0 / 1 per aligned pass of the batch (the full-width list), then the windowed
 //                                passes of the batch "crop r0 rows t0", in list order
+//   nowin y0:y1 ...              one crop per argument, none of them with a window (win(crop) == -1): two lines of 0 / 1 per aligned pass of the batch,
+//                                skip_pass_needed and skipx_full_needed -- the list kernels with no column bands rest on their being equal
+//   nowin                        the same for every band (none: 80:-1, and every 0 <= y0 <= y1 < 80) at crops 2, 3 and 4 of a batch of 7 (its rows at
+//                                every alignment of a 3-row pass), an empty crop in front of it, a full one behind it: "at y0 y1 bits bits"
 //   stages                       "w|f first|next a b new chunks stages": windowed (a = first row r0, b = rows; next: behind a pass of 4 rows of the same
 //                                run) and full width (a = pass of a 2-crop batch, b = 0; next: behind pass a - 1)
 //   plan geom n                  "chain=<0 for role split> skip=<0|1> skipx=<0|1>" of the 80 x 80 one-channel FP16X3 plan on 256 CUs
@@ -15,12 +19,25 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 using namespace trexhip;
 
 static_assert(skipx_tiles(SKIP_BAND_NONE).lo > skipx_tiles(SKIP_BAND_NONE).hi, "usable in constant expressions");
 static_assert(rs_round_stages(0, 8) == 3 && rs_round_stages(8, 8) == 3 && rs_round_stages(9, 8) == 6, "a round has its three stages even with nothing to produce");
+
+// the aligned passes a batch without windows needs, by the row rule alone and by the rule of the two lists
+static void nowin_bits(const std::vector<SkipBand>& bands, std::string& rows, std::string& lists) {
+    const int total_pairs = (int)bands.size() * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
+    const auto band = [&](const int crop) { return bands.at((size_t)crop); };
+    rows.clear();
+    lists.clear();
+    for (int p = 0; p < n_pass; ++p) {
+        rows += skip_pass_needed(p, total_pairs, band) ? '1' : '0';
+        lists += skipx_full_needed(p, total_pairs, band, [](int) { return -1; }) ? '1' : '0';
+    }
+}
 
 static void stage_line(const char* inst, const char* kind, const int a, const int b, const SkipXV2 nw, const int chunk) {
     std::printf("%s %s %d %d %d %d %d\n", inst, kind, a, b, nw.nrows, rs_round_chunks(nw.nrows, chunk), rs_round_stages(nw.nrows, chunk));
@@ -89,6 +106,30 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (argc >= 2 && !std::strcmp(argv[1], "nowin")) {
+        std::string rows, lists;
+        if (argc > 2) {
+            std::vector<SkipBand> bands;
+            for (int i = 2; i < argc; ++i) {
+                SkipBand b;
+                if (std::sscanf(argv[i], "%d:%d", &b.y0, &b.y1) != 2) { std::fprintf(stderr, "bad crop: %s\n", argv[i]); return 2; }
+                bands.push_back(b);
+            }
+            nowin_bits(bands, rows, lists);
+            std::printf("%s\n%s\n", rows.c_str(), lists.c_str());
+            return 0;
+        }
+        for (int at = 2; at <= 4; ++at)
+            for (int y0 = -1; y0 < 80; ++y0)
+                for (int y1 = y0; y1 < (y0 < 0 ? 0 : 80); ++y1) {
+                    std::vector<SkipBand> bands(7, SKIP_BAND_NONE);
+                    bands[(size_t)at] = y0 < 0 ? SKIP_BAND_NONE : SkipBand{y0, y1};
+                    bands[(size_t)at + 1] = {0, SkipGeom::CROP_ROWS - 1};
+                    nowin_bits(bands, rows, lists);
+                    std::printf("%d %d %d %s %s\n", at, bands[(size_t)at].y0, bands[(size_t)at].y1, rows.c_str(), lists.c_str());
+                }
+        return 0;
+    }
     if (argc == 2 && !std::strcmp(argv[1], "stages")) {
         constexpr int V3 = SkipGeom::V3_ROWS;
         // windowed: crop 1 of a batch, so that a mistake in the crop's edges would reach the neighbours' rows
@@ -118,6 +159,6 @@ int main(int argc, char** argv) {
         std::printf("chain=%d skip=%d skipx=%d\n", (int)p.chain, (int)p.skip, (int)p.skipx);
         return 0;
     }
-    std::fprintf(stderr, "usage: tiles | window x0 x1 range | windows | pack crop lo hi t0 | packs crop t0 | full y0:y1:x0:x1 ... | stages | plan geom n\n");
+    std::fprintf(stderr, "usage: tiles | window x0 x1 range | windows | pack crop lo hi t0 | packs crop t0 | full y0:y1:x0:x1 ... | nowin [y0:y1 ...] | stages | plan geom n\n");
     return 2;
 }

@@ -6,7 +6,7 @@
 //   plan geom n                  "fc1_listed=<0|1> fc1=<0 exact, 1 split1, 2 split4> head=<0 small, 1 big> fill=<k_act3_fill's grid>" on 256 CUs
 // all: 1 = the empty crop left the fp16 range (the word SK_EMPTY_RANGE is set), 0 = it did not
 #include "../../trex_amd/csrc/cnn_plan.h"
-#include "../../trex_amd/csrc/cnn_skip3.h"
+#include "../../trex_amd/csrc/cnn_skip_words.h"
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>

@@ -5,46 +5,13 @@ import os
 import numpy as np
 import pytest
 import torch
-from trex_amd import capi, weights
+from trex_amd import weights
+from cnn_skip_driver import blob, forward, same, state  # noqa: F401  (state: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 RS, DENSE3, TWO = 1 << 29, 1 << 29 | 1 << 26, 1 << 28
 PAIRB = 10 * 128 * 4          # bytes of one row pair of act3
-
-
-@pytest.fixture(scope="module")
-def state():
-    return weights.synthetic_state(100, 31)
-
-
-def forward(monkeypatch, st, geom, crops, classes=100, calls=1, then=None):
-    """-> (probabilities, logits) of every call, guard_stats, skip3_stats of every call; the same device buffers in every call.  `then`: crops
-    written into the same device buffer in front of one more call"""
-    monkeypatch.setenv("TREXHIP_CONV_GEOM", str(geom))
-    seg = capi.Segmenter(capi.default_params(64, 64, max_batch=1))
-    seg.load_weights(weights.pack_blob(st, classes))
-    seg.set_identity_precision(capi.CNN_FP16X3)
-    n = len(crops)
-    d = torch.from_numpy(np.ascontiguousarray(crops.reshape(n, -1))).cuda()
-    probs = torch.empty((n, classes), dtype=torch.float32, device="cuda")
-    logits = torch.empty_like(probs)
-    outs, skips = [], []
-    for call in range(calls + (then is not None)):
-        if call == calls:
-            d.copy_(torch.from_numpy(np.ascontiguousarray(then.reshape(n, -1))).cuda())
-        probs.fill_(-1.0); logits.fill_(-1.0)
-        seg.identify_device(d.data_ptr(), n, probs.data_ptr(), logits.data_ptr())
-        seg.synchronize()
-        outs.append((probs.cpu().numpy().copy(), logits.cpu().numpy().copy()))
-        skips.append(seg.skip3_stats())
-    guard = seg.guard_stats()
-    seg.close()
-    return outs, guard, skips[-1] if then is None else skips
-
-
-def same(a, b):
-    return a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
 
 
 def pairs_of(crop):
@@ -54,9 +21,10 @@ def pairs_of(crop):
 
 
 def check(monkeypatch, st, crops):
-    on, g_on, s_on = forward(monkeypatch, st, RS, crops)
-    off, g_off, s_off = forward(monkeypatch, st, DENSE3, crops)
+    on, g_on, stats = forward(monkeypatch, st, RS, crops)
+    off, g_off, stats_off = forward(monkeypatch, st, DENSE3, crops)
     two, g_two, _ = forward(monkeypatch, st, TWO, crops)
+    s_on, s_off = stats[-1].skip3, stats_off[-1].skip3
     assert g_on == g_off == g_two == (0, False)              # background activations in range: nothing is re-run
     assert np.all(np.isfinite(on[0][0])) and np.allclose(on[0][0].sum(1), 1.0, atol=1e-5)
     assert same(on[0], off[0]), float(np.abs(on[0][1] - off[0][1]).max())
@@ -71,10 +39,6 @@ def check(monkeypatch, st, crops):
     else:
         assert filled == (0 if listed else pairs * PAIRB)
     return s_on
-
-
-def blob(crops, i, rows, cols, rng):
-    crops[i, rows, cols, 0] = rng.integers(40, 200, crops[i, rows, cols, 0].shape)
 
 
 def test_one_empty_crop_is_all_fill(monkeypatch, state):
@@ -145,8 +109,9 @@ def test_empty_crop_out_of_range_lists_every_pair(monkeypatch, state):
     st["bn2.running_var"] = np.full(64, 1e8, np.float32)      # bring the scale back down behind conv2
     crops = weights.synthetic_crops(9, 99).copy()
     crops[4] = 0
-    on, g_on, s_on = forward(monkeypatch, st, RS, crops)
+    on, g_on, stats = forward(monkeypatch, st, RS, crops)
     off, g_off, _ = forward(monkeypatch, st, DENSE3, crops)
+    s_on = stats[-1].skip3
     assert g_on == g_off and (g_on[1] or g_on[0] > 0), (g_on, g_off)
     assert np.all(np.isfinite(on[0][0]))
     assert same(on[0], off[0])
@@ -162,7 +127,8 @@ def test_through_the_captured_graph(monkeypatch, state):
     crops[5] = 0
     other = np.zeros_like(crops)
     other[:, 30:50] = weights.synthetic_crops(n, 778)[:, 30:50]      # every blob cut down to rows 30 .. 49: fewer pairs than before
-    on, g_on, s_on = forward(monkeypatch, state, RS, crops, calls=5, then=other)
+    on, g_on, stats = forward(monkeypatch, state, RS, crops, calls=5, then=other)
+    s_on = [s.skip3 for s in stats]
     off, g_off, _ = forward(monkeypatch, state, DENSE3, crops)
     off2, g_off2, _ = forward(monkeypatch, state, DENSE3, other)
     assert g_on == g_off == g_off2 == (0, False)

@@ -152,6 +152,26 @@ def test_two_lists_no_pass_holds_two_crops(exe):
         assert rows == sorted(v3_rows(4 * k, 4 * k + 30)) and all(0 <= r < 20 for r in rows)
 
 
+def test_without_windows_the_full_width_list_is_the_row_rules(exe):
+    """the identity the one count / list / fill trio rests on: where no crop has a window (win(crop) == -1), skipx_full_needed is
+    skip_pass_needed, pass by pass.  Every band at crops 2, 3 and 4 of a batch of 7 -- its 20 V3 rows begin at the second, the first and the third
+    row of a 3-row pass -- between an empty crop and a full one"""
+    lines = [line.split() for line in run(exe, "nowin")]
+    assert len(lines) == 3 * (1 + 80 * 81 // 2)
+    seen = set()
+    for at, y0, y1, rows, lists in lines:
+        at, y0, y1 = int(at), int(y0), int(y1)
+        seen.add((at, y0, y1))
+        assert rows == lists, (at, y0, y1)
+        # ... and both are the brute-force propagation's: the batch's V3 rows that read a non-zero crop row, three to a pass (47 passes, the last of 2)
+        need = {20 * at + r for r in (v3_rows(y0, y1) if y0 <= y1 else ())} | set(range(20 * (at + 1), 20 * (at + 2)))
+        assert rows == "".join("1" if any(gp in need for gp in range(3 * p, 3 * p + 3)) else "0" for p in range(47)), (at, y0, y1)
+    assert seen == {(at, *b) for at in (2, 3, 4) for b in [NONE] + [(a, b) for a in range(80) for b in range(a, 80)]}
+    assert {(20 * at) % 3 for at in (2, 3, 4)} == {0, 1, 2}
+    # a batch given on the command line: rows 78, 79 reach V3 rows 18, 19 -- passes 6 (with row 0 of the empty crop behind) and nothing else
+    assert run(exe, "nowin", "78:79", "80:-1") == ["0" * 6 + "1" + "0" * 7] * 2
+
+
 def v2_rows(r0, rows):
     """the V2 rows (of the crop, 0 .. 39) that the V3 rows r0 .. r0 + rows - 1 read: conv2's rows 2 r .. 2 r + 1, each two rows up and down"""
     return {y + k for r in range(r0, r0 + rows) for y in (2 * r, 2 * r + 1) for k in (-2, -1, 0, 1, 2) if 0 <= y + k < 40}

@@ -6,49 +6,27 @@ import os
 import numpy as np
 import pytest
 import torch
-from trex_amd import capi, weights
+from trex_amd import weights
+from cnn_skip_driver import blob, forward, same, state  # noqa: F401  (state: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 RS, NOX, NOSKIP, TWO = 1 << 29, 1 << 29 | 1 << 23, 1 << 29 | 1 << 27, 1 << 28
 
 
-@pytest.fixture(scope="module")
-def state():
-    return weights.synthetic_state(100, 31)
+def listed_passes(crops):
+    """the aligned passes the row rule lists, from the crops' bytes alone: V3 row gp of a crop reads its rows 4 gp - 6 .. 4 gp + 9, a pass is 3
+    consecutive V3 rows of the batch"""
+    need = np.zeros(20 * len(crops), bool)
+    for i, c in enumerate(crops):
+        rows = np.flatnonzero(c.reshape(80, -1).any(1))
+        if len(rows):
+            need[20 * i:20 * i + 20] = [4 * gp + 9 >= rows[0] and 4 * gp - 6 <= rows[-1] for gp in range(20)]
+    return sum(bool(need[p:p + 3].any()) for p in range(0, len(need), 3))
 
 
-def forward(monkeypatch, st, geom, crops, classes=100, calls=1, then=None):
-    """-> (probabilities, logits) of every call, guard_stats, (skip_stats, skipx_stats) of every call; the same device buffers in every call.
-    `then`: crops written into the same device buffer in front of one more call"""
-    monkeypatch.setenv("TREXHIP_CONV_GEOM", str(geom))
-    seg = capi.Segmenter(capi.default_params(64, 64, max_batch=1))
-    seg.load_weights(weights.pack_blob(st, classes))
-    seg.set_identity_precision(capi.CNN_FP16X3)
-    n = len(crops)
-    d = torch.from_numpy(np.ascontiguousarray(crops.reshape(n, -1))).cuda()
-    probs = torch.empty((n, classes), dtype=torch.float32, device="cuda")
-    logits = torch.empty_like(probs)
-    outs, stats = [], []
-    for call in range(calls + (then is not None)):
-        if call == calls:
-            d.copy_(torch.from_numpy(np.ascontiguousarray(then.reshape(n, -1))).cuda())
-        probs.fill_(-1.0); logits.fill_(-1.0)
-        seg.identify_device(d.data_ptr(), n, probs.data_ptr(), logits.data_ptr())
-        seg.synchronize()
-        outs.append((probs.cpu().numpy().copy(), logits.cpu().numpy().copy()))
-        stats.append((seg.skip_stats(), seg.skipx_stats()))
-    guard = seg.guard_stats()
-    seg.close()
-    return outs, guard, stats
-
-
-def same(a, b):
-    return a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
-
-
-def check(monkeypatch, st, crops):
-    """-> skipx_stats of the windowed run; its skip_stats are those of the run without the windowed form"""
+def check(monkeypatch, st, crops, both=False):
+    """-> skipx_stats of the windowed run; its skip_stats are those of the run without the windowed form (both: -> those two as well)"""
     on, g_on, s_on = forward(monkeypatch, st, RS, crops)
     nox, g_nox, s_nox = forward(monkeypatch, st, NOX, crops)
     off, g_off, _ = forward(monkeypatch, st, NOSKIP, crops)
@@ -59,11 +37,7 @@ def check(monkeypatch, st, crops):
         assert same(on[0], other[0]), (name, float(np.abs(on[0][1] - other[0][1]).max()), np.flatnonzero(np.any(on[0][1] != other[0][1], axis=1))[:10])
     assert s_on[0][0] == s_nox[0][0]                          # SK_LEN, SK_NPASS, SK_FILLED keep their meaning
     assert s_nox[0][1] == (0, 0, 0)                           # switched off: the new words are not written
-    return s_on[0][1]
-
-
-def blob(crops, i, rows, cols, rng):
-    crops[i, rows, cols, 0] = rng.integers(40, 200, crops[i, rows, cols, 0].shape)
+    return (s_on[0][1], s_on[0][0], s_nox[0][0]) if both else s_on[0][1]
 
 
 def test_one_pixel_in_row_r_column_c(monkeypatch, state):
@@ -115,7 +89,11 @@ def test_tickets_of_two_slots(monkeypatch, state):
     crops = weights.synthetic_crops(n, 4321).copy()
     crops[17] = 0
     crops[200, :, :, 0] = np.random.default_rng(1).integers(1, 256, (80, 80))
-    windowed, wpasses, full = check(monkeypatch, state, crops)
+    (windowed, wpasses, full), skip_on, skip_nox = check(monkeypatch, state, crops, both=True)
+    # (at 256 CUs: 2134 passes, three blocks of the count / list kernels, the last one partial -- the prefix across blocks is in it)
+    want = listed_passes(crops)
+    print("row rule: %d of %d passes listed, numpy says %d" % (skip_on[1], skip_on[0], want))
+    assert skip_on[1] == want and skip_nox[1] == want
     print("%d synthetic crops: %d windowed in %d passes, %d full-width passes" % (n, windowed, wpasses, full))
     assert windowed <= n - 2 and windowed <= wpasses <= 5 * windowed and full >= 7       # the noise crop alone is 7 or 8 aligned passes
     assert windowed >= n // 2                                  # an ellipse of 18 x 5 px is at most 36 columns: 5 + 2 tiles
@@ -132,13 +110,15 @@ def test_empty_crop_out_of_range_goes_full_width(monkeypatch, state):
     on, g_on, s_on = forward(monkeypatch, st, RS, crops)
     assert np.all(np.isfinite(on[0][0]))
     for name, geom in (("bit 23", NOX), ("bit 27", NOSKIP), ("bit 28", TWO)):
-        other, g_other, _ = forward(monkeypatch, st, geom, crops)
+        other, g_other, s_other = forward(monkeypatch, st, geom, crops)
+        if geom == NOX:
+            assert s_other[0][:2] == ((60, 60, 0), (0, 0, 0))
         # the background itself is out of range: every crop is re-run, whichever kernel raised the flag and however it names the crops
         assert (g_on[1] or g_on[0] > 0) and (g_other[1] or g_other[0] > 0), (name, g_on, g_other)
         if geom != TWO:
             assert g_on == g_other, (name, g_on, g_other)
         assert same(on[0], other[0]), (name, float(np.abs(on[0][1] - other[0][1]).max()))
-    assert s_on[0] == ((60, 60, 0), (0, 0, 60))
+    assert s_on[0][:2] == ((60, 60, 0), (0, 0, 60))
 
 
 def test_through_the_captured_graph(monkeypatch, state):

@@ -6,8 +6,9 @@ batches."""
 import os
 import numpy as np
 import pytest
-import torch
-from trex_amd import capi, weights
+from trex_amd import weights
+from cnn_skip_driver import blob, same, state  # noqa: F401  (state: the module's fixture)
+import cnn_skip_driver
 
 pytestmark = pytest.mark.gpu
 
@@ -15,38 +16,11 @@ RS, COPY, DENSE3, TWO = 1 << 29, 1 << 29 | 1 << 25, 1 << 29 | 1 << 26, 1 << 28
 V3_ROWB = 10240
 
 
-@pytest.fixture(scope="module")
-def state():
-    return weights.synthetic_state(100, 31)
-
-
-def forward(monkeypatch, st, geom, crops, classes=100, calls=1, then=None):
-    """-> (probabilities, logits) of every call, skip_stats and skip3_stats of the last call; the same device buffers in every call.  `then`: crops
-    written into the same device buffer in front of one more call"""
-    monkeypatch.setenv("TREXHIP_CONV_GEOM", str(geom))
-    seg = capi.Segmenter(capi.default_params(64, 64, max_batch=1))
-    seg.load_weights(weights.pack_blob(st, classes))
-    seg.set_identity_precision(capi.CNN_FP16X3)
-    n = len(crops)
-    d = torch.from_numpy(np.ascontiguousarray(crops.reshape(n, -1))).cuda()
-    probs = torch.empty((n, classes), dtype=torch.float32, device="cuda")
-    logits = torch.empty_like(probs)
-    outs = []
-    for call in range(calls + (then is not None)):
-        if call == calls:
-            d.copy_(torch.from_numpy(np.ascontiguousarray(then.reshape(n, -1))).cuda())
-        probs.fill_(-1.0); logits.fill_(-1.0)
-        seg.identify_device(d.data_ptr(), n, probs.data_ptr(), logits.data_ptr())
-        seg.synchronize()
-        outs.append((probs.cpu().numpy().copy(), logits.cpu().numpy().copy()))
-    skip, skip3, guard = seg.skip_stats(), seg.skip3_stats(), seg.guard_stats()
-    seg.close()
+def forward(monkeypatch, st, geom, crops, **kw):
+    """-> (probabilities, logits) of every call, skip_stats and skip3_stats of the last call"""
+    outs, guard, stats = cnn_skip_driver.forward(monkeypatch, st, geom, crops, **kw)
     assert guard == (0, False)                               # background activations in range: nothing is re-run
-    return outs, skip, skip3
-
-
-def same(a, b):
-    return a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+    return outs, stats[-1].skip, stats[-1].skip3
 
 
 def check(monkeypatch, st, crops):
@@ -62,10 +36,6 @@ def check(monkeypatch, st, crops):
     print("%d crops: skip %s, skip3 %s" % (len(crops), s_on, s3_on))
     assert s_on == s_cp == s_off and s3_on == s3_cp          # the counters do not know who supplies the rows
     return s_on, s3_on
-
-
-def blob(crops, i, rows, cols, rng):
-    crops[i, rows, cols, 0] = rng.integers(40, 200, crops[i, rows, cols, 0].shape)
 
 
 def noise(n, seed):

@@ -1,5 +1,6 @@
 // capi.hip -- C ABI of libtrexhip (include/trexhip.h): context, memory, background, segment, fetch.
 #include "internal.h"
+#include "cnn_plan.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -208,10 +209,9 @@ int trexhip_create(const trexhip_params* p, trexhip_ctx** out) {
     fill_cfg(ctx);
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess && cus > 0) ctx->n_cus = cus; }
     // the two test hooks (INTEGRATION.md "Environment variables"): each chooses between schedules that give identical results.
-    // TREXHIP_CONV_GEOM: any of bits 0-11 selects the fp32-activation chain of the identity network; bit 28 keeps conv1 and conv2 apart,
-    // bit 29 forces the role-split conv1+conv2 kernel, bit 30 the two-workgroups-per-CU one; bit 27 makes the role-split kernel compute every pass, those of
-    // background rows too.  The other bits mean nothing.
-    if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e) & (0xfff | (255 << 23));
+    // TREXHIP_CONV_GEOM: which chain of the identity network runs and which of its preparations (the bits: GEOM_* in cnn_plan.h).  The other
+    // bits mean nothing.
+    if (const char* e = std::getenv("TREXHIP_CONV_GEOM")) ctx->tune_conv_geom = std::atoi(e) & GEOM_MASK;
     if (const char* e = std::getenv("TREXHIP_CCL_BANDS")) ctx->tune_ccl_bands = std::atoi(e);     // same tables whatever the bands
     const size_t B = p->max_batch, H = p->height, W = p->width, R = p->max_runs, NB = p->max_blobs, P = p->max_pixels;
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete ctx; return TREXHIP_E_DEVICE; }

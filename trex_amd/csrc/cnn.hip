@@ -1447,10 +1447,9 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     if (net->v3e) {                            // the pass list of the role-split kernel
         const size_t n_pass = (N * SkipGeom::V3_ROWS + SkipGeom::RPP - 1) / SkipGeom::RPP;
         TRY(B.device_bytes(&net->skip_bands, N * sizeof(int2), who));
-        TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4, who));
+        TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4 * 4, who));
         TRY(B.device_bytes(&net->skip_list, (n_pass + SKIP_PAD) * 4, who));
         TRY(B.device_bytes(&net->skipx_cols, N * sizeof(int2), who));
-        TRY(B.device_bytes(&net->skipx_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4 * 4, who));
         TRY(B.device_bytes(&net->skipx_list, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         const size_t blocks3 = (N + Skip3Geom::BLOCK - 1) / Skip3Geom::BLOCK;
         TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint2), who));
@@ -1480,14 +1479,11 @@ static const ByChannels K_CONV1_MFMA{Kern(k_conv1_mfma, 256), Kern(k_conv1_mfma3
 static const ByChannels K_CONV1_WPRE{Kern(k_conv1_wpre<1>, 256), Kern(k_conv1_wpre<3>, 256)};
 static const Kern K_CONV12_RS(k_conv12_rs<W12RGeom>, 512, W12RGeom::LDS_BYTES);
 static const Kern K_CONV12_RSX(k_conv12_rs<W12XGeom>, 512, W12XGeom::LDS_BYTES);
-static const Kern K_PASSX_COUNT(k_passx_count, SKIP_LB);
-static const Kern K_PASSX_LIST(k_passx_list, SKIP_LB);
-static const Kern K_V3_FILLX(k_v3_fillx, 256);
 static const Kern K_CONV12_WPRE(k_conv12_wpre, 256, W12Geom::LDS_BYTES);
 static const Kern K_CROP_BANDS(k_crop_bands, 256);
 static const Kern K_PASS_COUNT(k_pass_count, SKIP_LB);
 static const Kern K_PASS_LIST(k_pass_list, SKIP_LB);
-static const Kern K_V3_FILL(k_v3_fill, 256);
+static const Kern K_V3_FILL(k_v3_fill, SKIP_FILL_TB);
 static const Kern K_CONV2_WPRE2(k_conv2_wpre2, 256, W2bGeom::LDS_BYTES);
 static const Kern K_CONV2_STREAM(k_conv5_stream<16, 64, 40, 8, 4>, 256, ConvGeomS<16, 64, 40, 8, 4>::LDS_BYTES);
 using GW3 = WinoGeom<64, 128, 20, 2>;
@@ -1588,7 +1584,7 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->act2e, (size_t)SkipGeom::V3_ROWS * 20 * 64 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&zero, SkipGeom::CROP_ROWS * 80, who);
     if (rc != TREXHIP_OK) return rc;
-    const CnnPlan p = cnn_plan(80, 80, 1, TREXHIP_CNN_FP16X3, true, (1 << 29) | (1 << 27), 1, ctx->n_cus);
+    const CnnPlan p = cnn_plan(80, 80, 1, TREXHIP_CNN_FP16X3, true, GEOM_ROLE_SPLIT | GEOM_NO_SKIP, 1, ctx->n_cus);
     TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV12_RS.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV12_RS.lds));
     TH_CHECK_HIP(hipMemsetAsync(net->d_skip, 0, SK_WORDS * 4, ctx->stream));
     TH_CHECK_HIP(hipMemsetAsync(zero, 0, SkipGeom::CROP_ROWS * 80, ctx->stream));
@@ -1612,6 +1608,27 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
         TH_CHECK_HIP(hipMemcpy(net->d_skip + SK_EMPTY_RANGE, &one, 4, hipMemcpyHostToDevice));
     }
     return TREXHIP_OK;
+}
+
+// The role-split chain's preparation (cnn_skip_kernels.h), in front of conv1+conv2: which passes, row pairs and fc1 rows the crops need, and the
+// V3 rows of the others; every decision stays on the device.  `direct`: the listed conv3 reads background rows from the image, the fill copies
+// only where the dense form runs
+static void launch_skip_prep(const Pass& f, const bool direct) {
+    const Net& net = f.net;
+    const CnnPlan& p = f.p;
+    const int n = f.n, lb = ceil_div(p.conv2.items, SKIP_LB);
+    int2* cols = p.skipx ? net.skipx_cols : nullptr;      // null: no crop gets a window, one list
+    K_CROP_BANDS(f.s, ceil_div(n, 4), f.crops, n, net.skip_bands, cols);
+    K_PASS_COUNT(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts);
+    K_PASS_LIST(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts, net.skip_list, net.skipx_list);
+    if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
+        K_PAIR_COUNT(f.s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
+        K_PAIR_LIST(f.s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
+        // the crops each plane of the listed fc1 computes: from the bands alone, so here and not between conv3 and fc1
+        if (p.fc1_listed) K_FC1_LIST(f.s, Skip3Geom::PAIRS, net.skip_bands, n, net.d_skip, net.fc1_list, net.max_crops);
+    }
+    K_V3_FILL(f.s, ceil_div(n * SkipGeom::V3_ROWS, SKIP_FILL_TB), net.skip_bands, cols, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e),
+              reinterpret_cast<uint4*>(net.v3), (int)direct);
 }
 
 static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
@@ -1638,29 +1655,7 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         stage_begin(ctx, TREXHIP_STAGE_CONV2);
         switch (p.chain) {
         case Chain::ROLE_SPLIT:
-            if (p.skip) {      // which passes the crops need, and the rows of the others (cnn_skip_kernels.h); the decisions stay on the device
-                const int lb = ceil_div(p.conv2.items, SKIP_LB);
-                K_CROP_BANDS(s, ceil_div(n, 4), d_crops, n, net.skip_bands, p.skipx ? net.skipx_cols : nullptr);
-                if (p.skipx) {     // two lists: the windowed passes of the crops that have a window, the full-width passes the others need
-                    K_PASSX_COUNT(s, lb, net.skip_bands, net.skipx_cols, n, net.d_skip, net.skipx_counts);
-                    K_PASSX_LIST(s, lb, net.skip_bands, net.skipx_cols, n, net.d_skip, net.skipx_counts, net.skip_list, net.skipx_list);
-                } else {
-                    K_PASS_COUNT(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts);
-                    K_PASS_LIST(s, lb, net.skip_bands, n, net.d_skip, net.skip_counts, net.skip_list);
-                }
-                if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
-                    K_PAIR_COUNT(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
-                    K_PAIR_LIST(s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
-                    // the crops each plane of the listed fc1 computes: from the bands alone, so here and not between conv3 and fc1
-                    if (p.fc1_listed) K_FC1_LIST(s, Skip3Geom::PAIRS, net.skip_bands, n, net.d_skip, net.fc1_list, net.max_crops);
-                }
-                if (p.skipx)
-                    K_V3_FILLX(s, ceil_div(n * SkipGeom::V3_ROWS, SKIPX_FB), net.skip_bands, net.skipx_cols, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e),
-                               reinterpret_cast<uint4*>(net.v3), (int)direct);
-                else
-                    K_V3_FILL(s, ceil_div(p.conv2.items, SKIP_FB), net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.v3e), reinterpret_cast<uint4*>(net.v3),
-                              (int)direct);
-            }
+            if (p.skip) launch_skip_prep(f, direct);
             // (an instance whose list is empty returns at once)
             if (p.skipx)
                 K_CONV12_RSX(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.d_skip + SKX_CTR,
@@ -1841,12 +1836,19 @@ int trexhip_identify_guard_stats(trexhip_ctx* ctx, uint32_t* rerun_crops, uint32
     return TREXHIP_OK;
 }
 
-int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* listed, uint64_t* bytes_filled) {
-    if (!ctx || !ctx->net) { set_error("trexhip_identify_skip_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
-    Net* net = static_cast<Net*>(ctx->net);
-    uint32_t w[SK_WORDS] = {};
+// the words of Net::d_skip as the queued work leaves them (zeros: a network without them)
+static int read_skip_words(trexhip_ctx* ctx, const char* who, uint32_t (&w)[SK_WORDS]) {
+    if (!ctx || !ctx->net) { set_error(std::string(who) + ": no context / weights not loaded"); return TREXHIP_E_INVALID; }
+    const Net* net = static_cast<Net*>(ctx->net);
+    std::fill(w, w + SK_WORDS, 0u);
     TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     if (net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* listed, uint64_t* bytes_filled) {
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_skip_stats", w)) return rc;
     if (passes) *passes = w[SK_NPASS];
     if (listed) *listed = w[SK_LEN];
     if (bytes_filled) *bytes_filled = (uint64_t)w[SK_FILLED] * V3_ROWB;
@@ -1854,11 +1856,8 @@ int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* li
 }
 
 int trexhip_identify_skipx_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes) {
-    if (!ctx || !ctx->net) { set_error("trexhip_identify_skipx_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
-    Net* net = static_cast<Net*>(ctx->net);
-    uint32_t w[SK_WORDS] = {};
-    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_skipx_stats", w)) return rc;
     if (crops_windowed) *crops_windowed = w[SKX_CROPS];
     if (windowed_passes) *windowed_passes = w[SKX_PASSES];
     if (full_passes) *full_passes = w[SKX_FULL];
@@ -1866,11 +1865,8 @@ int trexhip_identify_skipx_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uin
 }
 
 int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled) {
-    if (!ctx || !ctx->net) { set_error("trexhip_identify_skip3_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
-    Net* net = static_cast<Net*>(ctx->net);
-    uint32_t w[SK_WORDS] = {};
-    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_skip3_stats", w)) return rc;
     if (pairs) *pairs = w[SK3_PAIRS];
     if (listed) *listed = w[SK3_LISTED];
     if (passes) *passes = w[SK3_USE] ? w[SK3_PASSES] : 0u;
@@ -1879,13 +1875,11 @@ int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* li
 }
 
 int trexhip_identify_fc1_stats(trexhip_ctx* ctx, uint32_t* rows, uint32_t* listed) {
-    if (!ctx || !ctx->net) { set_error("trexhip_identify_fc1_stats: no context / weights not loaded"); return TREXHIP_E_INVALID; }
-    Net* net = static_cast<Net*>(ctx->net);
-    uint32_t w[SK_WORDS] = {};
-    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (net->last_fc1_n && net->d_skip) TH_CHECK_HIP(hipMemcpy(w, net->d_skip, sizeof w, hipMemcpyDeviceToHost));
-    uint32_t sum = 0;
-    for (int q = 0; q < Skip3Geom::PAIRS; ++q) sum += w[SK3_FC1_LEN + q];
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_fc1_stats", w)) return rc;
+    const Net* net = static_cast<Net*>(ctx->net);
+    uint32_t sum = 0;      // (the lengths are those of the last call that listed: they count only where that was the last call)
+    for (int q = 0; q < Skip3Geom::PAIRS && net->last_fc1_n; ++q) sum += w[SK3_FC1_LEN + q];
     if (rows) *rows = (uint32_t)net->last_fc1_n * Skip3Geom::PAIRS;
     if (listed) *listed = sum;
     return TREXHIP_OK;

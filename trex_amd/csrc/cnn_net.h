@@ -3,7 +3,7 @@
 #include "internal.h"
 #include "cnn_plan.h"
 #include "cnn_skip.h"
-#include "cnn_skip3.h"
+#include "cnn_skip_words.h"
 #include "cnn_skipx.h"
 #include <tuple>
 
@@ -32,17 +32,16 @@ struct Net {
     uint8_t *v2 = nullptr, *v3 = nullptr;      // Winograd-domain operand images of conv2 / conv3 (fp16 pieces), written by the producing layer (cnn_wpre.h)
                                                // (v3: a copy of v3e lies in front of it and behind its max_crops * 20 rows, where v3e exists)
     uint8_t* crops = nullptr;
-    // skipping the passes of k_conv12_rs whose crop rows are all background (cnn_skip.h, cnn_skip_kernels.h)
+    // skipping the passes of k_conv12_rs whose crop rows are all background (cnn_skip.h, cnn_skip_kernels.h; the words of d_skip: cnn_skip_words.h)
     uint8_t* v3e = nullptr;                    // the V3 image of an all-zero crop [20][V3_ROWB], made when the weights are loaded (1 channel, 80 x 80)
     uint32_t* d_skip = nullptr;                // SK_WORDS words: the empty crop's range flag, the last call's list length and counters
     int2* skip_bands = nullptr;                // [max_crops] first / last non-zero row
-    uint32_t* skip_counts = nullptr;           // needed passes per SKIP_LB passes
-    int* skip_list = nullptr;                  // the passes to compute, in order, + the SKIP_PAD entry behind them
+    uint32_t* skip_counts = nullptr;           // per SKIP_LB passes / crops: full-width passes, aligned needed passes, windowed passes, windowed crops
+    int* skip_list = nullptr;                  // the full-width passes to compute, in order, + the SKIP_PAD entry behind them
     // the windowed conv1+conv2 (cnn_skipx.h)
     float* act2e = nullptr;                    // the pooled conv2 activations of an all-zero crop [20][20][64], made by the run that makes v3e
     int2* skipx_cols = nullptr;                // [max_crops] first / last non-zero column
     int* skipx_list = nullptr;                 // the windowed passes (skipx_pack), in order, + the SKIP_PAD entry behind them
-    uint32_t* skipx_counts = nullptr;          // per SKIP_LB passes / crops: full-width passes, aligned needed passes, windowed passes, windowed crops
     // computing only the row pairs of conv3 whose V3 rows hold more than background (cnn_skip3.h, cnn_skip_kernels.h)
     float* act3e = nullptr;                    // the act3 of an all-zero crop [10][10][128], made when the weights are loaded, behind v3e
     uint2* skip3_counts = nullptr;             // listed passes and pairs per workgroup of k_pair_count

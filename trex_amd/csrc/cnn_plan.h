@@ -4,25 +4,43 @@
 #include <algorithm>
 #include "../../include/trexhip.h"
 #include "cnn_geom.h"
-#include "cnn_skip3.h"
+#include "cnn_skip_words.h"
 #include "cnn_skipx.h"
 
 namespace trexhip {
 
+// the bits of TREXHIP_CONV_GEOM (a test hook; include/trexhip.h documents the values)
+enum : int {
+    GEOM_FP32_ACT = 0xfff,            // bits 0-11, any of them: the fp32-activation chain
+    GEOM_NO_SKIPX = 1 << 23,          // no crop gets a window
+    GEOM_DENSE_FC1 = 1 << 24,         // the dense fc1
+    GEOM_V3_COPY = 1 << 25,           // the listed conv3 reads every row from V3
+    GEOM_DENSE_CONV3 = 1 << 26,       // the dense conv3 alone
+    GEOM_NO_SKIP = 1 << 27,           // conv1+conv2 computes every pass
+    GEOM_TWO_KERNEL = 1 << 28,        // conv1 and conv2 as two kernels
+    GEOM_ROLE_SPLIT = 1 << 29,        // the role-split conv1+conv2 at any batch size
+    GEOM_FUSED_2WG = 1 << 30,         // the two-workgroup conv1+conv2 at any batch size
+    GEOM_MASK = GEOM_FP32_ACT | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
+};
+
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
 //   ROLE_SPLIT  k_conv12_rs (conv1 inside conv2, one workgroup per CU)   -> k_conv5_wpair       1 channel, aligned crops, >= 3200 crops
-//               (in front of it, unless bit 27 is set: k_crop_bands, k_pass_count, k_pass_list, k_v3_fill -- passes of background rows are skipped;
-//                unless bit 26 is set as well: k_pair_count and k_pair_list in front of k_v3_fill, k_act3_fill and BOTH forms of k_conv5_wpair, the
-//                dense one and the one that walks the listed row pairs, behind conv2 -- the word k_pair_list writes names the one that runs, the
-//                other returns at once.  The listed form reads the background rows from the empty crop's image itself and k_v3_fill returns at
-//                once where that form runs; bit 25 keeps the copy -- the fill always runs and the listed form reads every row from V3.
-//                Above 1024 crops, unless bit 24 is set: k_fc1_list beside k_pair_list, and fc1 computes only the (crop, split-K plane) rows whose
-//                row pair is listed -- the listed k_fc1_split<4>; k_head takes the other planes from the empty crop's, k_act3_fill copies no pair.
-//                Bit 24 keeps the dense fc1 and the fill's copy: the chain as it was before fc1 was listed, launch for launch.
-//                Unless bit 23 is set: k_crop_bands writes the column bands as well, k_passx_count / k_passx_list stand in for k_pass_count /
-//                k_pass_list and make TWO lists -- the windowed passes (8 tiles x up to 4 row pairs of one crop) of the crops whose blob fits 8
-//                tiles, the aligned full-width passes the other crops need -- k_v3_fillx stands in for k_v3_fill, and k_conv12_rs<W12XGeom> runs on
-//                the first list in front of k_conv12_rs<W12RGeom> on the second.  Bit 23 keeps the chain as it was, launch for launch)
+//               In front of it, the preparation that lets the chain skip background (launch_skip_prep, cnn_skip_kernels.h), every part with its
+//               switch in TREXHIP_CONV_GEOM:
+//                 skip        k_crop_bands, k_pass_count, k_pass_list, k_v3_fill: conv1+conv2 walks a list of the passes that hold a blob's rows, the
+//                             V3 rows of the others are the empty crop's.  Off (GEOM_NO_SKIP, bit 27): none of this chain's preparation runs
+//                 skipx       k_crop_bands writes the column bands as well and k_pass_list makes TWO lists -- the windowed passes (8 tiles x up to 4
+//                             row pairs of one crop) of the crops whose blob fits 8 tiles, the aligned full-width passes the other crops need;
+//                             k_conv12_rs<W12XGeom> runs on the first in front of k_conv12_rs<W12RGeom> on the second.  Off (GEOM_NO_SKIPX, bit
+//                             23): no crop gets a window -- the same three kernels, one list, the full-width instance alone
+//                 skip3       k_pair_count and k_pair_list in front of k_v3_fill; k_act3_fill and BOTH forms of k_conv5_wpair, the dense one and
+//                             the one that walks the listed row pairs, behind conv2 -- the word k_pair_list writes names the one that runs, the
+//                             other returns at once.  Off (GEOM_DENSE_CONV3, bit 26): the dense conv3 alone
+//                 v3_direct   the listed conv3 reads the background rows from the empty crop's image itself and k_v3_fill returns at once where
+//                             that form runs.  Off (GEOM_V3_COPY, bit 25): the fill always copies, the listed form reads every row from V3
+//                 fc1_listed  above 1024 crops: k_fc1_list beside k_pair_list, fc1 computes only the (crop, split-K plane) rows whose row pair is
+//                             listed -- the listed k_fc1_split<4>; k_head takes the other planes from the empty crop's, k_act3_fill copies no
+//                             pair.  Off (GEOM_DENSE_FC1, bit 24): the dense fc1, and the fill copies
 //   FUSED_2WG   k_conv12_wpre (the same, two workgroups per CU)          -> k_conv5_wpair       1 channel, aligned crops, fewer
 //   TWO_KERNEL  k_conv1_wpre -> k_conv2_wpre2                            -> k_conv5_wpair       3 channels, or TREXHIP_CONV_GEOM bit 28
 //   FP32_ACT    conv1 -> act1 -> k_conv5_stream -> act2 -> k_conv5_wino                         unaligned crops, or any of bits 0-11
@@ -111,24 +129,24 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
     // the matrix-core conv1 kernels read the crops with 16-byte loads: unaligned crop buffers take the VALU kernel (and the fp32-activation chain)
     // default chain (cnn_wpre.h): the Winograd-domain fp16 operand images V2 / V3 are written by the producing layer.  Any of bits 0-11 of
     // TREXHIP_CONV_GEOM selects the fp32-activation chain of rounds 1-2 instead.
-    const bool pre = h16 && aligned && (geom & 0xfff) == 0;
+    const bool pre = h16 && aligned && (geom & GEOM_FP32_ACT) == 0;
     // one input channel: conv1 runs INSIDE conv2 (cnn_fused12.h: the V2 image stays in LDS); TREXHIP_CONV_GEOM bit 28 keeps the two kernels
-    const bool fused12 = pre && CH == 1 && !(geom & (1 << 28));
+    const bool fused12 = pre && CH == 1 && !(geom & GEOM_TWO_KERNEL);
     // the role-split form (cnn_fused12rs.h): one workgroup of 8 waves per CU, consumer waves (tap loop, output transform) beside producer waves (V3
     // transform of the previous pass, V2 rows of the next), the first 15 taps' weight fragments resident in LDS.  Bit-identical to the
     // two-workgroups-per-CU kernel and 6 % faster at 25600 crops (3.81 against 4.05 ms on one box); batches that do not give every CU a few
     // passes keep the older kernel (1000 crops: 0.207 against 0.196 ms).  TREXHIP_CONV_GEOM bit 29 forces the role-split kernel, bit 30 the older one
-    const bool role_split = fused12 && !(geom & (1 << 30)) && ((geom & (1 << 29)) || n >= 3200);
+    const bool role_split = fused12 && !(geom & GEOM_FUSED_2WG) && ((geom & GEOM_ROLE_SPLIT) || n >= 3200);
     p.chain = role_split ? Chain::ROLE_SPLIT : fused12 ? Chain::FUSED_2WG : pre ? Chain::TWO_KERNEL : h16 ? Chain::FP32_ACT : Chain::EXACT;
     p.conv1 = fused12 ? Conv1::FUSED : pre ? Conv1::WPRE : aligned ? Conv1::MFMA : Conv1::VALU;
     p.conv1_grid = n;
-    p.skip = role_split && !(geom & (1 << 27));
-    p.skip3 = p.skip && !(geom & (1 << 26));
-    p.skipx = p.skip && !(geom & (1 << 23)) && n < SKIPX_MAX_CROPS;
+    p.skip = role_split && !(geom & GEOM_NO_SKIP);
+    p.skip3 = p.skip && !(geom & GEOM_DENSE_CONV3);
+    p.skipx = p.skip && !(geom & GEOM_NO_SKIPX) && n < SKIPX_MAX_CROPS;
     if (p.skip3) {
         p.skip3_grid = ceil_div(ceil_div(n, 32 /* Skip3Geom::BLOCK crops per thread */), 256);
         p.act3_fill = {ceil_div(n, 16), n};
-        p.v3_direct = !(geom & (1 << 25)) && skip3_direct_fits((long long)n * SkipGeom::V3_ROWS);
+        p.v3_direct = !(geom & GEOM_V3_COPY) && skip3_direct_fits((long long)n * SkipGeom::V3_ROWS);
     }
 
     const int n_pass2 = ceil_div(n * 20, W2bGeom::RPP), n_pass3 = ceil_div(n * GW::TPC, GW::MB);
@@ -163,7 +181,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
         if (!small) p.fc1_grid = ceil_div(n, 128);
     }
     if (small) { p.head = Head::SMALL; p.head_grid = ceil_div(n, 4); }
-    p.fc1_listed = p.skip3 && p.fc1 == Fc1::SPLIT4 && p.head == Head::BIG && !(geom & (1 << 24));
+    p.fc1_listed = p.skip3 && p.fc1 == Fc1::SPLIT4 && p.head == Head::BIG && !(geom & GEOM_DENSE_FC1);
     p.head_plans = h16 && small;
     p.rerun_conv1 = pre;
     p.r_conv2 = guarded(n * ConvGeomB<16, 64, 40, 10, SPLIT_NP>::BPC, n_cus);

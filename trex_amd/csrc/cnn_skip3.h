@@ -170,18 +170,7 @@ TREXHIP_HD constexpr void skip3_row_words(const Skip3Pass& p, const SkipRows own
     }
 }
 
-// the words of Net::d_skip that belong to the listed conv3 (the others: cnn_skip_kernels.h)
-enum : int {
-    SK3_PAIRS = 8,           // row pairs of the last call's batch
-    SK3_LISTED = 9,          // row pairs listed
-    SK3_PASSES = 10,         // listed passes
-    SK3_FILLED = 11,         // act3 row pairs filled from the empty crop's
-    SK3_USE = 12,            // non-zero: the listed form of k_conv5_wpair runs, zero: the dense one
-    SK3_EMPTY_CTR = 13,      // the pass counter of the run that made the empty crop's act3
-    SK3_FC1E_RANGE = 14,     // the fp16 range flag of the run that made the empty crop's fc1 planes (Net::fc1e): non-zero -> SK_EMPTY_RANGE is raised
-    SK3_FC1_LEN = 16,        // .. + PAIRS - 1: crops listed for plane q of the listed fc1 by the last call that listed (skip3_fc1_listed)
-    SK3_LAST = SK3_FC1_LEN + Skip3Geom::PAIRS - 1
-};
+// (the words of Net::d_skip that the kernels of the listed conv3 and fc1 write and read: cnn_skip_words.h)
 
 // fc1's split-K plane s is row pair q = s of every crop (FC1_KSPLIT planes of 10 x 128 inputs), and a crop's row of an MFMA tile depends on
 // that crop's activations and the weights alone: the partial sum of a pair that holds the empty crop's bits is, bit for bit, plane q of fc1 run on

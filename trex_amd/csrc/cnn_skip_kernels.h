@@ -1,43 +1,30 @@
-// cnn_skip_kernels.h -- the per-call preparation that lets k_conv12_rs skip passes whose crop rows are all background (the rule: cnn_skip.h).
-// Included by cnn.hip inside namespace trexhip.  Four small kernels on the forward pass's stream, no host read between them:
-//   k_crop_bands   first / last non-zero row of every crop (it looks at the bytes, not at how the crop was made)
-//   k_pass_count   needed passes per block of SKIP_LB consecutive passes
-//   k_pass_list    order-preserving compaction of the needed passes into the list k_conv12_rs walks, its length, the entry behind its end
-//   k_v3_fill      the V3 rows of every pass that is NOT listed, copied from the V3 image of an all-zero crop (Net::v3e, made at load) -- for
-//                  the dense conv3 only: where the listed form runs and takes those rows from the image itself (`direct`), it returns at once
-// and three more for the listed form of k_conv5_wpair (the rule and the packing: cnn_skip3.h), from the same bands:
-//   k_pair_count   listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK consecutive crops
+// cnn_skip_kernels.h -- the per-call preparation that lets the role-split chain leave out what is background: the passes of k_conv12_rs whose
+// crop rows are all zero (the rule: cnn_skip.h), the tile columns a crop's blob does not reach (cnn_skipx.h), the row pairs of conv3 and the
+// (crop, plane) rows of fc1 that read no blob (cnn_skip3.h).  Included by cnn.hip inside namespace trexhip.  Small kernels on the forward pass's
+// stream, no host read between them; the words they leave in Net::d_skip: cnn_skip_words.h.  In the order they run (launch_skip_prep):
+//   k_crop_bands   first / last non-zero row of every crop (it looks at the bytes, not at how the crop was made), and, where crops can have
+//                  windows (`cols` not null), the first / last non-zero column
+//   k_pass_count   thread i: pass i and crop i.  Per SKIP_LB of them: full-width passes, passes the row rule lists, windowed passes, windowed crops
+//   k_pass_list    order-preserving compaction into the lists k_conv12_rs walks: the aligned full-width passes that a crop WITHOUT a window needs,
+//                  and the windowed passes of the crops that have one; their lengths, the entry behind the end of each, the windowed instance's
+//                  ticket counter zeroed, and SK_LEN / SK_NPASS / SK_FILLED by the row rule alone.  `cols` null: no crop has a window -- the
+//                  full-width list is the row rule's, and neither the windowed list nor the SKX_* words are touched
+//   k_pair_count   (listed conv3) listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK
+//                  consecutive crops
 //   k_pair_list    the passes in order, each as its two runs, the counters, and the word that names the form of conv3 that runs (SK3_USE)
-//                  (both run in front of k_v3_fill, which reads that word)
-//   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place) and the sources of its rows; then a wave per crop: the act3 row pairs
-//                  that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load) -- counted only, where the listed fc1
-//                  runs: it never reads them
-// and one for the listed form of k_fc1_split (the rule: skip3_fc1_listed, cnn_skip3.h), beside the two above:
-//   k_fc1_list     a workgroup per split-K plane: the crops whose pair the plane has to compute, in order, and how many they are
-// and, where the windowed conv1+conv2 runs (the rule in x, the windows and the packing: cnn_skipx.h), in the place of k_pass_count, k_pass_list
-// and k_v3_fill:
-//   k_crop_bands   writes the first / last non-zero COLUMN of every crop as well
-//   k_passx_count  per SKIP_LB passes and crops: full-width passes, passes the row rule lists, windowed passes, windowed crops
-//   k_passx_list   TWO lists in order: the windowed passes of the crops that have a window, the aligned full-width passes the other crops need;
-//                  their lengths, the entries behind their ends, the windowed instance's ticket counter zeroed, and the words of k_pass_list
-//                  with the values k_pass_list gives them
-//   k_v3_fillx     k_v3_fill row by row: a row is computed where its crop has a window and needs it, or where its aligned pass is on the
-//                  full-width list
+//   k_fc1_list     (listed fc1) a workgroup per split-K plane: the crops whose pair the plane has to compute, in order, and how many they are
+//   k_v3_fill      row by row: a V3 row that nobody computes -- its crop has no window over it and its aligned pass is not on the full-width
+//                  list -- copied from the V3 image of an all-zero crop (Net::v3e, made at load).  For the dense conv3 only: where the listed
+//                  form runs and takes those rows from the image itself (`direct`), it reads SK3_USE and returns at once
+// and behind conv1+conv2:
+//   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place) and the sources of its rows; then a wave per
+//                  crop: the act3 row pairs that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load) -- counted
+//                  only, where the listed fc1 runs: it never reads them
 #pragma once
 
-// the words of Net::d_skip
-enum : int {
-    SK_EMPTY_RANGE = 0,      // the fp16 range flag of the run that made the empty crop's V3 image: non-zero -> every pass is listed
-    SK_EMPTY_CTR = 1,        // that run's pass counter
-    SK_LEN = 2,              // passes listed by the last call
-    SK_NPASS = 3,            // passes of the last call's batch
-    SK_FILLED = 4,           // V3 rows the last call took from the empty crop's image instead of computing them (copied by k_v3_fill or read in place)
-    SK_WORDS = 32            // (8 ..: the words of the listed conv3 and the listed fc1, SK3_* in cnn_skip3.h)
-};
-static_assert(SK3_LAST < SK_WORDS, "the words of the listed conv3 lie behind these");
-static constexpr int SKIP_LB = 1024;      // passes per block of the count / list kernels (one per thread)
+static constexpr int SKIP_LB = 1024;      // passes / crops per block of the count / list kernels (one per thread)
 static constexpr int SKIP_PAD = 1;        // one entry behind the last one: k_conv12_rs clamps every read behind the list's end to it (RS_LIST)
-static constexpr int SKIP_FB = 64;        // passes per block of the fill kernel
+static constexpr int SKIP_FILL_TB = 256;  // V3 rows per block of the fill kernel (one per thread)
 
 // one wave per crop: 400 x 16 bytes, unit i lies in row i / 5
 // cols (may be null): the first / last non-zero COLUMN as well (cnn_skipx.h), from the same registers
@@ -101,87 +88,36 @@ struct SkipBandsOf {
 __device__ __forceinline__ bool skip_needed(const int p, const int total_pairs, const int2* __restrict__ bands, const bool all) {
     return all || skip_pass_needed(p, total_pairs, SkipBandsOf{bands});
 }
-
-__global__ __launch_bounds__(SKIP_LB) void k_pass_count(const int2* __restrict__ bands, const int n, const uint32_t* __restrict__ words,
-                                                        uint32_t* __restrict__ counts) {
-    __shared__ uint32_t s_cnt;
-    const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
-    const int p = blockIdx.x * SKIP_LB + threadIdx.x;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    const bool need = p < n_pass && skip_needed(p, total_pairs, bands, words[SK_EMPTY_RANGE] != 0);
-    const unsigned long long m = __ballot(need);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_cnt, (uint32_t)__popcll(m));
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_cnt;
-}
-
-__global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
-                                                       const uint32_t* __restrict__ counts, int* __restrict__ list) {
-    __shared__ uint32_t s_base, s_wave[SKIP_LB / 64];
-    const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p = blockIdx.x * SKIP_LB + tid;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    // the needed passes in front of this block
-    uint32_t part = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += SKIP_LB) part += counts[b];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    if (lane == 0 && part) atomicAdd(&s_base, part);
-    const bool need = p < n_pass && skip_needed(p, total_pairs, bands, words[SK_EMPTY_RANGE] != 0);
-    const unsigned long long m = __ballot(need);
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = s_base, total = s_base;
-    for (int w = 0; w < SKIP_LB / 64; ++w) { const uint32_t c = s_wave[w]; if (w < wave) off += c; total += c; }
-    if (need) list[off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = p;
-    if (blockIdx.x == gridDim.x - 1) {                                   // the last block knows the length
-        if (tid < SKIP_PAD) list[total + tid] = n_pass;
-        // the rows of the passes that are not listed (the batch's last pass may be short): counted here, whoever supplies them
-        if (p == n_pass - 1) {
-            const uint32_t listed_rows = total * SkipGeom::RPP - (need ? (uint32_t)(n_pass * SkipGeom::RPP - total_pairs) : 0u);
-            words[SK_LEN] = total; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = (uint32_t)total_pairs - listed_rows;
-        }
-    }
-}
-
-// ---- the windowed conv1+conv2 (cnn_skipx.h): two lists from one pair of kernels ----
-// the words of Net::d_skip that belong to it
-enum : int {
-    SKX_CROPS = 26,          // crops of the last call that took windowed passes
-    SKX_PASSES = 27,         // windowed passes listed by the last call: the length of the windowed instance's list
-    SKX_FULL = 28,           // full-width passes listed by the last call (for the crops without a window): the length of the full-width instance's list
-    SKX_CTR = 29             // the windowed instance's ticket counter (zeroed by k_passx_list)
-};
-static_assert(SKX_CROPS > SK3_LAST && SKX_CTR < SK_WORDS, "behind the words of the listed conv3 and fc1");
-
+// a crop's window (cnn_skipx.h); a crop without a blob has a window and no pass.  cols null: no crop has one
 struct SkipXWinOf {
-    const int2* bands; const int2* cols; bool all;
-    // a crop without a blob has a window and no pass
-    __host__ __device__ int operator()(const int crop) const { const int2 c = cols[crop]; return skipx_window({c.x, c.y}, all); }
+    const int2* cols; bool all;
+    __host__ __device__ int operator()(const int crop) const {
+        if (!cols) return -1;
+        const int2 c = cols[crop];
+        return skipx_window({c.x, c.y}, all);
+    }
 };
 // thread i of the grid: pass i of the batch (full width: is it needed by a crop without a window; and by the row rule alone, for the counters)
 // and crop i (its windowed passes).  counts[4 b ..]: full-width passes, aligned needed passes, windowed passes, windowed crops of block b
 struct SkipXItem { bool full, need; int wpasses, t0; SkipRows rows; };
 __device__ __forceinline__ SkipXItem skipx_item(const int i, const int n, const int2* __restrict__ bands, const int2* __restrict__ cols, const bool all) {
     const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
+    const bool none = all || !cols;      // no crop has a window: a pass is on the full-width list where the row rule lists it (uniform across the grid)
     SkipXItem it{false, false, 0, -1, {1, 0}};
     if (i < n_pass) {
         it.need = skip_needed(i, total_pairs, bands, all);
-        it.full = all || (it.need && skipx_full_needed(i, total_pairs, SkipBandsOf{bands}, SkipXWinOf{bands, cols, all}));
+        it.full = it.need && (none || skipx_full_needed(i, total_pairs, SkipBandsOf{bands}, SkipXWinOf{cols, all}));
     }
     if (i < n) {
-        it.t0 = SkipXWinOf{bands, cols, all}(i);
+        it.t0 = SkipXWinOf{cols, all}(i);
         const int2 b = bands[i];
         it.rows = skip_rows({b.x, b.y});
         it.wpasses = it.t0 >= 0 ? skipx_passes(it.rows) : 0;
     }
     return it;
 }
-__global__ __launch_bounds__(SKIP_LB) void k_passx_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
-                                                         const uint32_t* __restrict__ words, uint32_t* __restrict__ counts) {
+__global__ __launch_bounds__(SKIP_LB) void k_pass_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
+                                                        const uint32_t* __restrict__ words, uint32_t* __restrict__ counts) {
     __shared__ uint32_t s_cnt[4];
     if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -196,9 +132,9 @@ __global__ __launch_bounds__(SKIP_LB) void k_passx_count(const int2* __restrict_
     __syncthreads();
     if (threadIdx.x < 4) counts[blockIdx.x * 4 + threadIdx.x] = s_cnt[threadIdx.x];
 }
-__global__ __launch_bounds__(SKIP_LB) void k_passx_list(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
-                                                        uint32_t* __restrict__ words, const uint32_t* __restrict__ counts, int* __restrict__ list,
-                                                        int* __restrict__ wlist) {
+__global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
+                                                       uint32_t* __restrict__ words, const uint32_t* __restrict__ counts, int* __restrict__ list,
+                                                       int* __restrict__ wlist) {
     __shared__ uint32_t s_base[4], s_wave[2][SKIP_LB / 64];
     const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -242,78 +178,53 @@ __global__ __launch_bounds__(SKIP_LB) void k_passx_list(const int2* __restrict__
         const uint32_t full = s_base[0] + sc[0], wp = s_base[2] + sc[1];
         uint32_t need = s_base[1], wc = s_base[3];
         for (int k = 0; k < 2; ++k) { const uint32_t c = counts[blockIdx.x * 4 + 1 + 2 * k]; if (k) wc += c; else need += c; }
-        for (int k = 0; k < SKIP_PAD; ++k) { list[full + k] = n_pass; wlist[wp + k] = 0; }
-        // SK_LEN, SK_NPASS, SK_FILLED keep their meaning: the aligned passes the row rule lists and the rows outside them
+        for (int k = 0; k < SKIP_PAD; ++k) list[full + k] = n_pass;
+        // SK_LEN, SK_NPASS, SK_FILLED: the aligned passes the row rule lists and the rows outside them (the batch's last pass may be short), whoever
+        // supplies those rows
         const bool last_need = skip_needed(n_pass - 1, total_pairs, bands, words[SK_EMPTY_RANGE] != 0);
         const uint32_t listed_rows = need * SkipGeom::RPP - (last_need ? (uint32_t)(n_pass * SkipGeom::RPP - total_pairs) : 0u);
         words[SK_LEN] = need; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = (uint32_t)total_pairs - listed_rows;
-        words[SKX_CROPS] = wc; words[SKX_PASSES] = wp; words[SKX_FULL] = full; words[SKX_CTR] = 0;
+        if (cols) {                                                        // (null: nobody reads the windowed list or its words)
+            for (int k = 0; k < SKIP_PAD; ++k) wlist[wp + k] = 0;
+            words[SKX_CROPS] = wc; words[SKX_PASSES] = wp; words[SKX_FULL] = full; words[SKX_CTR] = 0;
+        }
     }
 }
-// with both lists: V3 row r of crop c is computed where c has a window and needs the row, or where its aligned pass is on the full-width list;
-// every other row <- the empty crop's.  A thread looks at one of the block's 256 consecutive V3 rows, then the block copies the rows that are
-// not computed; nothing to copy where the listed conv3 reads the image itself
-static constexpr int SKIPX_FB = 256;
-__global__ __launch_bounds__(SKIPX_FB) void k_v3_fillx(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const uint32_t* __restrict__ words,
-                                                       const uint4* __restrict__ v3e, uint4* __restrict__ v3, const int direct) {
+// V3 row r of crop c is computed where c has a window and needs the row, or where its aligned pass is on the full-width list; every other row
+// <- the empty crop's.  (No crop with a window: the rows of the passes the row rule does not list.)  A thread looks at one of the block's
+// SKIP_FILL_TB consecutive V3 rows, then the block copies the rows that are not computed; nothing to copy where the listed conv3 reads the
+// image itself
+__global__ __launch_bounds__(SKIP_FILL_TB) void k_v3_fill(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const uint32_t* __restrict__ words,
+                                                          const uint4* __restrict__ v3e, uint4* __restrict__ v3, const int direct) {
     using G = SkipGeom;
     constexpr int ROWQ = V3_ROWB / 16;
-    __shared__ unsigned long long s_fill[SKIPX_FB / 64];
+    __shared__ unsigned long long s_fill[SKIP_FILL_TB / 64];
     if (direct && words[SK3_USE]) return;
     const bool all = words[SK_EMPTY_RANGE] != 0;
-    const int total_pairs = n * G::V3_ROWS, tid = threadIdx.x, gp0 = blockIdx.x * SKIPX_FB;
+    const int total_pairs = n * G::V3_ROWS, tid = threadIdx.x, gp0 = blockIdx.x * SKIP_FILL_TB;
     {
         const int gp = gp0 + tid;
         bool fill = false;
         if (gp < total_pairs && !all) {
             const int crop = gp / G::V3_ROWS, r = gp - crop * G::V3_ROWS;
-            const SkipXWinOf win{bands, cols, all};
-            bool computed = false;
-            if (win(crop) >= 0) { const int2 b = bands[crop]; const SkipRows need = skip_rows({b.x, b.y}); computed = r >= need.lo && r <= need.hi; }
-            fill = !computed && !skipx_full_needed(gp / G::RPP, total_pairs, SkipBandsOf{bands}, win);
+            if (!cols) fill = !skip_pass_needed(gp / G::RPP, total_pairs, SkipBandsOf{bands});      // (uniform across the grid)
+            else {
+                const SkipXWinOf win{cols, all};
+                bool computed = false;
+                if (win(crop) >= 0) { const int2 b = bands[crop]; const SkipRows need = skip_rows({b.x, b.y}); computed = r >= need.lo && r <= need.hi; }
+                fill = !computed && !skipx_full_needed(gp / G::RPP, total_pairs, SkipBandsOf{bands}, win);
+            }
         }
         const unsigned long long m = __ballot(fill);
         if ((tid & 63) == 0) s_fill[tid >> 6] = m;
     }
     __syncthreads();
-    for (int w = 0; w < SKIPX_FB / 64; ++w) {
+    for (int w = 0; w < SKIP_FILL_TB / 64; ++w) {
         unsigned long long m = s_fill[w];
         while (m) {
             const int gp = gp0 + w * 64 + __ffsll((long long)m) - 1;
             m &= m - 1;
-            for (int q = tid; q < ROWQ; q += SKIPX_FB) v3[(size_t)gp * ROWQ + q] = v3e[(gp % G::V3_ROWS) * ROWQ + q];
-        }
-    }
-}
-
-// V3 rows of the passes that are not listed <- the empty crop's rows.  A block looks at SKIP_FB consecutive passes
-__global__ __launch_bounds__(256) void k_v3_fill(const int2* __restrict__ bands, const int n, const uint32_t* __restrict__ words,
-                                                 const uint4* __restrict__ v3e /*[20][V3_ROWB]*/, uint4* __restrict__ v3,
-                                                 const int direct /* the listed conv3 reads the image itself: nothing to copy where it runs */) {
-    using G = SkipGeom;
-    static_assert(SKIP_FB == 64, "one ballot");
-    __shared__ unsigned long long s_skip;
-    constexpr int ROWQ = V3_ROWB / 16;
-    const int total_pairs = n * G::V3_ROWS, n_pass = (total_pairs + G::RPP - 1) / G::RPP;
-    const int tid = threadIdx.x, p0 = blockIdx.x * SKIP_FB;
-    if (direct && words[SK3_USE]) return;
-    if (tid < 64) {
-        const int p = p0 + tid;
-        const bool skip = p < n_pass && !skip_needed(p, total_pairs, bands, words[SK_EMPTY_RANGE] != 0);
-        const unsigned long long m = __ballot(skip);
-        if (tid == 0) s_skip = m;
-    }
-    __syncthreads();
-    unsigned long long m = s_skip;
-    while (m) {
-        const int b = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int gp0 = (p0 + b) * G::RPP;
-        const int nr = total_pairs - gp0 < G::RPP ? total_pairs - gp0 : G::RPP;
-        for (int i = tid; i < nr * ROWQ; i += 256) {
-            const int r = i / ROWQ, q = i - r * ROWQ;
-            const int gp = gp0 + r;
-            v3[(size_t)gp * ROWQ + q] = v3e[(gp % G::V3_ROWS) * ROWQ + q];
+            for (int q = tid; q < ROWQ; q += SKIP_FILL_TB) v3[(size_t)gp * ROWQ + q] = v3e[(gp % G::V3_ROWS) * ROWQ + q];
         }
     }
 }
