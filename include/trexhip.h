@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 22
+#define TREXHIP_ABI_VERSION 23
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -592,6 +592,15 @@ int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* li
  * aligned *full_passes the other crops took; zeros where the windowed form did not run.  trexhip_identify_skip_stats keeps counting by the row
  * rule alone.  No reference counterpart; any pointer may be NULL.  (ABI 22) */
 int trexhip_identify_skipx_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes);
+
+/* A windowed pass reads 12 rows of conv1's pooled output (40 per crop); those with no non-zero crop row under them -- the rows above and below
+ * the blob -- hold one constant per channel, the same in every crop.  The windowed kernel does not make them: it reads them from a row made
+ * once, when the weights are loaded, and makes only the others.  The results are the bits of the kernel that makes every row.  Bit 22 of TREXHIP_CONV_GEOM
+ * (value 4194304) switches this off.
+ * What the last call with windowed passes did (waits for the context's stream): *rows_read = the rows of conv1's pooled output its windowed
+ * passes read, the passes of a crop counted as one run, *rows_made of them made; both 0 where every row is made (bit 22, bit 23).  No
+ * reference counterpart; either pointer may be NULL.  (ABI 23) */
+int trexhip_identify_bgrow_stats(trexhip_ctx* ctx, uint32_t* rows_read, uint32_t* rows_made);
 
 /* Where conv3 lists row pairs and the batch has more than 1024 crops, fc1 -- ten split-K planes, plane q = row pair q of every crop -- computes
  * only the (crop, plane) rows whose row pair is listed; the head takes every other plane from the fc1 planes of an all-zero crop, made when the

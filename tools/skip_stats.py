@@ -6,7 +6,8 @@ itself -- the count is the same) -- and the crops' own row statistics, on the ho
 form walked (0: the dense kernel ran) against the dense kernel's, bytes of act3 filled from the empty crop's -- and those of the listed fc1
 (trexhip_identify_fc1_stats): crop-plane rows of the batch and the rows it computed -- and those of the windowed conv1+conv2
 (trexhip_identify_skipx_stats): crops that took windowed passes, those passes, the full-width passes the other crops took (the first counters
-keep counting by the row rule alone).  Nothing here is timed.  One JSON line.
+keep counting by the row rule alone) -- and (trexhip_identify_bgrow_stats) the rows of conv1's pooled output those passes read against the rows
+the kernel made of them, the others being background rows.  Nothing here is timed.  One JSON line.
    python tools/skip_stats.py"""
 import json
 import os
@@ -29,6 +30,7 @@ passes, listed, filled = lane.seg.skip_stats()
 pairs3, listed3, passes3, filled3 = lane.seg.skip3_stats()
 fc1_rows, fc1_listed = lane.seg.fc1_stats()          # crop-plane rows of the listed fc1 and the rows it computed (0, 0: the dense fc1 ran)
 x_crops, x_passes, x_full = lane.seg.skipx_stats()
+v2_read, v2_made = lane.seg.bgrow_stats()            # rows of conv1's pooled output the windowed passes read, and those of them made (0, 0: all are)
 crops = lane.crops[:passes * 3 // 20]
 rows = (crops != 0).any(dim=2)                       # [n][80]: the row holds a non-zero byte
 print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passes": passes, "passes_listed": listed,
@@ -40,5 +42,6 @@ print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passe
                   "conv3_pass_ratio": round(passes3 / max((pairs3 * 10 + 63) // 64, 1), 4), "act3_bytes_filled": filled3,
                   "fc1_rows": fc1_rows, "fc1_rows_listed": fc1_listed, "fc1_fraction_listed": round(fc1_listed / max(fc1_rows, 1), 4),
                   "crops_windowed": x_crops, "windowed_passes": x_passes, "full_width_passes": x_full,
-                  "windowed_passes_per_crop": round(x_passes / max(x_crops, 1), 3)}))
+                  "windowed_passes_per_crop": round(x_passes / max(x_crops, 1), 3),
+                  "v2_rows_read": v2_read, "v2_rows_made": v2_made, "v2_fraction_made": round(v2_made / max(v2_read, 1), 4)}))
 pipe.close()

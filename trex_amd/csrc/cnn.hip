@@ -1447,10 +1447,11 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     if (net->v3e) {                            // the pass list of the role-split kernel
         const size_t n_pass = (N * SkipGeom::V3_ROWS + SkipGeom::RPP - 1) / SkipGeom::RPP;
         TRY(B.device_bytes(&net->skip_bands, N * sizeof(int2), who));
-        TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * 4 * 4, who));
+        TRY(B.device_bytes(&net->skip_counts, ((n_pass + SKIP_LB - 1) / SKIP_LB) * SKIP_NCNT * 4, who));
         TRY(B.device_bytes(&net->skip_list, (n_pass + SKIP_PAD) * 4, who));
         TRY(B.device_bytes(&net->skipx_cols, N * sizeof(int2), who));
         TRY(B.device_bytes(&net->skipx_list, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
+        TRY(B.device_bytes(&net->skipx_rows, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         const size_t blocks3 = (N + Skip3Geom::BLOCK - 1) / Skip3Geom::BLOCK;
         TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint2), who));
         TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 4, who));
@@ -1582,6 +1583,7 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->fc1e, (size_t)FC1_KSPLIT * 128 * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->d_skip, SK_WORDS * 4, who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->act2e, (size_t)SkipGeom::V3_ROWS * 20 * 64 * 4, who);
+    if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&net->bgtab, (size_t)W2xGeom::NBG * W2xGeom::BG_UNITS * sizeof(uint4), who);
     if (rc == TREXHIP_OK) rc = net->weights.device_bytes(&zero, SkipGeom::CROP_ROWS * 80, who);
     if (rc != TREXHIP_OK) return rc;
     const CnnPlan p = cnn_plan(80, 80, 1, TREXHIP_CNN_FP16X3, true, GEOM_ROLE_SPLIT | GEOM_NO_SKIP, 1, ctx->n_cus);
@@ -1589,7 +1591,12 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
     TH_CHECK_HIP(hipMemsetAsync(net->d_skip, 0, SK_WORDS * 4, ctx->stream));
     TH_CHECK_HIP(hipMemsetAsync(zero, 0, SkipGeom::CROP_ROWS * 80, ctx->stream));
     K_CONV12_RS(ctx->stream, p.conv2.grid, zero, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3e, net->inv2w, net->d_skip + SK_EMPTY_RANGE, 1,
-                net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr, net->act2e);
+                net->d_skip + SK_EMPTY_CTR, p.pk2, nullptr, nullptr, nullptr, net->act2e, nullptr, nullptr);
+    TH_CHECK_HIP(hipGetLastError());
+    // the background row of the windowed instance, as each first tile sees it: that instance itself without a list, one workgroup (cnn_fused12rs.h)
+    TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV12_RSX.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV12_RSX.lds));
+    K_CONV12_RSX(ctx->stream, 1, zero, net->w1h, net->b1, net->inv1h, net->w2w, net->b2, net->v3e, net->inv2w, net->d_skip + SK_EMPTY_RANGE, 1,
+                 net->d_skip + SKX_CTR, 1, nullptr, nullptr, nullptr, net->act2e, nullptr, net->bgtab);
     TH_CHECK_HIP(hipGetLastError());
     TH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(K_CONV3_WPAIR.fn), hipFuncAttributeMaxDynamicSharedMemorySize, K_CONV3_WPAIR.lds));
     K_CONV3_WPAIR(ctx->stream, p.conv3.grid, net->v3e, net->w3w, net->b3, net->act3e, net->inv3w, 1, net->d_skip + SK3_EMPTY_CTR, p.n_big3, nullptr, nullptr, nullptr);
@@ -1619,8 +1626,8 @@ static void launch_skip_prep(const Pass& f, const bool direct) {
     const int n = f.n, lb = ceil_div(p.conv2.items, SKIP_LB);
     int2* cols = p.skipx ? net.skipx_cols : nullptr;      // null: no crop gets a window, one list
     K_CROP_BANDS(f.s, ceil_div(n, 4), f.crops, n, net.skip_bands, cols);
-    K_PASS_COUNT(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts);
-    K_PASS_LIST(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts, net.skip_list, net.skipx_list);
+    K_PASS_COUNT(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts, (int)p.bgrows);
+    K_PASS_LIST(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts, net.skip_list, net.skipx_list, net.skipx_rows, (int)p.bgrows);
     if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
         K_PAIR_COUNT(f.s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
         K_PAIR_LIST(f.s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
@@ -1659,9 +1666,9 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
             // (an instance whose list is empty returns at once)
             if (p.skipx)
                 K_CONV12_RSX(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.d_skip + SKX_CTR,
-                             p.pk2, net.d_ovfc, net.skipx_list, net.d_skip + SKX_PASSES, net.act2e);
+                             p.pk2, net.d_ovfc, net.skipx_list, net.d_skip + SKX_PASSES, net.act2e, net.skipx_rows, net.bgtab);
             K_CONV12_RS(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
-                        p.pk2, net.d_ovfc, p.skip ? net.skip_list : nullptr, p.skip ? net.d_skip + (p.skipx ? SKX_FULL : SK_LEN) : nullptr, nullptr);
+                        p.pk2, net.d_ovfc, p.skip ? net.skip_list : nullptr, p.skip ? net.d_skip + (p.skipx ? SKX_FULL : SK_LEN) : nullptr, nullptr, nullptr, nullptr);
             break;
         case Chain::FUSED_2WG:
             K_CONV12_WPRE(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.ovf(OVF_PASS2),
@@ -1861,6 +1868,14 @@ int trexhip_identify_skipx_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uin
     if (crops_windowed) *crops_windowed = w[SKX_CROPS];
     if (windowed_passes) *windowed_passes = w[SKX_PASSES];
     if (full_passes) *full_passes = w[SKX_FULL];
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_bgrow_stats(trexhip_ctx* ctx, uint32_t* rows_read, uint32_t* rows_made) {
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_bgrow_stats", w)) return rc;
+    if (rows_read) *rows_read = w[SKX_V2_READ];
+    if (rows_made) *rows_made = w[SKX_V2_MADE];
     return TREXHIP_OK;
 }
 

@@ -31,7 +31,23 @@
 //
 // The geometry is a template parameter (W12RGeomT): the full-width instance is the kernel described above; the windowed instance (cnn_skipx.h)
 // computes 8 of a row's 10 tiles for up to 4 row pairs of one crop per pass -- 64 of 64 M-slots, a ring of 12 rows x 8 tiles, chunks of 8 rows,
-// 108 KB of LDS and 12 resident taps -- and is told at the kernel.
+// 112 KB of LDS and 11 resident taps -- and is told at the kernel.
+//
+// The windowed instance does not make BACKGROUND rows (cnn_skipx.h, skipx_v2_rows): a V2 row with no non-zero crop row under it -- the rows a
+// pass reads above and below the blob, 0.37 of them on the benchmark's crops -- is relu(bias) in every pixel, the same in every crop.  Beside each
+// list entry k_pass_list writes the V2 rows of its crop that are not background (Net::skipx_rows, a scalar both roles read one round ahead,
+// like the entry: a second table and not the bands, whose address would wait for the entry).  rs_round gives both roles the rows of a round
+// that are made and its chunks by THAT count: P0, P1, P2 and the range guard run over them alone, no ring slot of a background row is written,
+// and the consumers read a row of the crop outside the crop's range from the background slot (NR + 1), as they read an out-of-crop row from the
+// zero row.  The slot (4 KB behind the ring: 11 resident taps instead of 12) holds the row as the pass's first tile t0 sees it -- conv2's zero
+// padding at tiles 0 and 9 is all that tells the three forms apart: the producers fill it in front of the first pass and rewrite it in stage 3,
+// where nobody reads the planes, when the next pass has another t0 (one uint4 per producer thread, requested in stage 1).  The forms come from a
+// 12 KB table (Net::bgtab) that THIS instance writes once per loaded network, in a run without a list: its own P1 and P2 on the crop-row
+// buffer while that is still all zero, once per t0 -- what P2 writes for an interior row of an all-zero crop, bit for bit, by construction.
+// (Three slots, made by every workgroup for itself, cost 12 KB and three more taps out of LDS: measured, profiles/conv12_bg_rows.txt.)  The
+// range guard needs nothing new: the instance runs only where the empty crop's activations were in range.  A first pass whose crop does not
+// start in its first rows then fits one chunk (8 rows of the 12 it reads), and a round that makes 5 rows or fewer runs conv1 in one step.
+// Off: TREXHIP_CONV_GEOM bit 22 -- the table beside the list says every row.
 
 // max of three / two floats as ONE instruction each (the compiler's fmaxf puts a canonicalising v_max v, v, v in front of operands it does not
 // know to be canonical); exact, so results do not change.  ONLY for operands written by ordinary VALU instructions: an MFMA result read by
@@ -58,10 +74,13 @@ struct W2xGeom {
     static constexpr int CO = 64, S = 40, TPP = 2 * SkipXGeom::WT, RPP = SkipXGeom::RPP, NR = SkipXGeom::NR;
     static constexpr int KH = 5, POOL = 2;
     static constexpr int ROWL = 4 * SkipXGeom::WT * 32;                 // one (row, piece, group): 4 positions x WT tiles x 32 B
-    static constexpr int PLANE = (NR + 1) * ROWL, BUF = 2 * PLANE;
+    // behind the zero row and the ring: the background row (cnn_skipx.h, skipx_v2_rows) as the pass's first tile t0 sees it, slot NR + 1; its
+    // NBG forms (t0 = 0, 1, 2) lie in a table in memory (Net::bgtab), BG_UNITS x 16 B each: the slot's part of the four planes
+    static constexpr int NBG = SkipXGeom::TILES - SkipXGeom::WT + 1, BG_SLOT = NR + 1, BG_UNITS = 4 * ROWL / 16;
+    static constexpr int PLANE = (NR + 2) * ROWL, BUF = 2 * PLANE;
     static constexpr int PBUF_OFF = 2 * BUF;
     static constexpr int BV = 2 * 2 * CO;
-    static_assert(RPP * TPP == 64 && NR == POOL * RPP + KH - 1, "64 M-slots, the V2 rows a pass reads");
+    static_assert(RPP * TPP == 64 && NR == POOL * RPP + KH - 1 && NBG == 3 && BG_UNITS == 256, "64 M-slots, the V2 rows a pass reads, the background slot: a unit per producer thread");
 };
 
 // GG: the V2 geometry; CHUNK_: V2 rows the producers make per three stages; TPR_: tiles per ring row; NW1_: conv1 windows (4 outputs = 2 pooled
@@ -126,7 +145,9 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                                                    const int n_crops, uint32_t* __restrict__ pass_ctr, const int PK /* consecutive passes per ticket */,
                                                    uint8_t* __restrict__ crop_flags /* per-crop range flags (may be null) */,
                                                    const int* __restrict__ list /* the passes to compute, in order (cnn_skip_kernels.h); null: every pass */,
-                                                   const uint32_t* __restrict__ list_len, float* __restrict__ act2e) {
+                                                   const uint32_t* __restrict__ list_len, float* __restrict__ act2e,
+                                                   const int* __restrict__ vrows /* windowed: beside every list entry, the V2 rows of its crop that are made (skipx_v2_pack) */,
+                                                   uint4* __restrict__ bgtab /* windowed: the background row's three forms [NBG][BG_UNITS]; WRITTEN by the run without a list */) {
     using G = typename F::G;
     constexpr int CO = 64, S = 40;
     extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
@@ -143,6 +164,9 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
 #define RS_LIST(i_) list[(i_) < n_pass ? (i_) : n_pass]
     int pass = list ? RS_LIST(slot) : slot;
     int ahead = list ? RS_LIST(slot + 1) : 0;                             // list[slot + 1], read one round before it is needed
+    // windowed: the V2 rows of the pass's crop that are made at all (the others are background rows), read with the entry and as far ahead
+    auto rs_vrows = [&](const int i) { if constexpr (F::WIN) return vrows ? vrows[i < n_pass ? i : n_pass] : 0; else return 0; };
+    int vr = rs_vrows(slot), vr_ahead = rs_vrows(slot + 1);
     // the next ticket's first pass: written by thread 0, read by every wave behind a barrier (a plain LDS word: through a volatile pointer into
     // the dynamic array it became a FLAT load with a vmcnt(0) behind it, and everything computed from it vector arithmetic)
     int* s_next = reinterpret_cast<int*>(ldsb + F::CTL_OFF);
@@ -184,39 +208,38 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         else { const int gp = e * G::RPP + rp; return gp < total_pairs ? gp : total_pairs - 1; }
     };
     auto rs_t0 = [&](const int e) { if constexpr (F::WIN) return skipx_unpack(e).t0; else return 0; };
-#define RS_ROWS(pass_, qmin_, nrows_)                                                                                            \
-    do {                                                                                                                         \
-        const int gp0_ = rs_gp0(pass_);                                                                                          \
-        const SkipXV2 v_ = rs_v2_rows(gp0_, gp0_ + rs_nrw(pass_) - 1);                                                           \
-        qmin_ = v_.qmin;                                                                                                         \
-        nrows_ = v_.nrows;                                                                                                       \
-    } while (0)
-    // the rows the NEXT pass needs that are not in the ring yet: [lo, hi); the next pass itself (the last pass of a ticket moves on to the
-    // ticket drawn one round earlier).  Computed identically by every wave.
-#define RS_NEXT(pass_, res_hi_, nslot_, next_, have_, lo_, hi_, extra_)                                                                \
+    // the round (rs_round, cnn_skipx.h): the rows the NEXT pass needs that are not in the ring yet, those of them the producers make, its chunks;
+    // the next pass itself (the last pass of a ticket moves on to the ticket drawn one round earlier).  Computed identically by every wave.
+#define RS_NEXT(pass_, res_hi_, nslot_, next_, nvr_, have_, rd_)                                                                 \
     do {                                                                                                                         \
         const bool draw_ = tleft == 1;                                                                                           \
         nslot_ = draw_ ? __builtin_amdgcn_readfirstlane(*s_next) : slot + 1;                                                     \
         have_ = nslot_ < n_pass;                                                                                                 \
         next_ = nslot_;                                                                                                          \
+        nvr_ = 0;                                                                                                                \
         if (list) {                                                                                                              \
             next_ = draw_ ? RS_LIST(nslot_) : ahead;                                                                             \
             ahead = RS_LIST(nslot_ + 1);                                                                                         \
+            nvr_ = draw_ ? rs_vrows(nslot_) : vr_ahead;                                                                          \
+            vr_ahead = rs_vrows(nslot_ + 1);                                                                                     \
         }                                                                                                                        \
-        lo_ = hi_ = 0;                                                                                                           \
+        rd_ = RS_ROUND_NONE;                                                                                                     \
         if (have_) {                                                                                                             \
             const int gn_ = rs_gp0(next_);                                                                                       \
             const bool follows_ = F::WIN ? gn_ == rs_gp0(pass_) + rs_nrw(pass_) : next_ == (pass_) + 1;                          \
-            const SkipXV2 nw_ = rs_new_rows(follows_, res_hi_, gn_, gn_ + rs_nrw(next_) - 1);                                    \
-            lo_ = nw_.qmin;                                                                                                      \
-            hi_ = lo_ + nw_.nrows;                                                                                               \
+            rd_ = rs_round(follows_, res_hi_, gn_, gn_ + rs_nrw(next_) - 1, F::WIN, skipx_v2_unpack(nvr_), F::CHUNK);            \
         }                                                                                                                        \
-        extra_ = rs_round_chunks(hi_ - lo_, F::CHUNK) - 1;                                                                       \
     } while (0)
     __syncthreads();
 
-    int qmin, nrows;
-    RS_ROWS(pass, qmin, nrows);
+    // the first pass: every row it reads is new
+    const RsRound first = rs_round(false, 0, rs_gp0(pass), rs_gp0(pass) + rs_nrw(pass) - 1, F::WIN, skipx_v2_unpack(vr), F::CHUNK);
+    // windowed, without a list (once per loaded network, one workgroup): the run that MAKES the table of the background row -- this kernel's own
+    // P1 and P2 on the crop-row buffer while it is still all zero, once per t0, into the background slot and from there into the table: bit for
+    // bit what P2 writes for an interior row of an all-zero crop.  Two barriers per form, executed by both roles; nothing else runs
+    const bool make_bg = F::WIN && !list;
+    // the background slot's unit of this producer thread: plane rt / 64, unit rt % 64 of the slot's row
+    auto bg_unit = [&]() { if constexpr (F::WIN) return reinterpret_cast<uint4*>(ldsb + (rt >> 6) * G::PLANE + G::BG_SLOT * G::ROWL) + (rt & 63); else return (uint4*)nullptr; };
     if (producer) {
         // ------------------------------------------------------------------------------------------------------------------------
         // PRODUCER: V3 transform of the previous pass, V2 rows of the next one
@@ -332,11 +355,12 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             }
         };
         // P2: (V2 row v, conv2 tile tx, channel quad): 8 pooled pixels x 4 channels -> B^T d -> pieces -> the ring slots (q % NR + 1) of the planes
-        auto p2 = [&](const int c0, const int nr, const int tw) {
+        // (bgslot >= 0: row 0 of the chunk into that slot -- the background row)
+        auto p2 = [&](const int c0, const int nr, const int tw, const int bgslot = -1) {
             if (rt < nr * (4 * F::TPR)) {
                 const int v = rt / (4 * F::TPR), rem = rt - v * (4 * F::TPR), tx = rem >> 2, quad = rem & 3;
                 const int q = c0 + v;
-                const int slot = q % G::NR + 1, rot = w2b_rot(slot);
+                const int slot = bgslot >= 0 ? bgslot : q % G::NR + 1, rot = w2b_rot(slot);
                 float4 d[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -424,30 +448,52 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                 *reinterpret_cast<float4*>(pbe + (rp * F::PEP + 2 + px) * 64 + c4 * 4) = bg;
             }
         };
-        // prologue: every row of the first pass, chunk by chunk (three barriers each; the consumers wait at them)
-        for (int c = 0, c0 = qmin; c < rs_round_chunks(nrows, F::CHUNK); ++c, c0 += F::CHUNK) {
-            const int nr = qmin + nrows - c0 < F::CHUNK ? qmin + nrows - c0 : F::CHUNK;
+        if constexpr (F::WIN) {
+            if (make_bg) {
+                for (int t = 0; t < G::NBG; ++t) {
+                    p1(1, t);
+                    RS_BAR();
+                    p2(0, 1, t, G::BG_SLOT);
+                    RS_BAR();
+                    bgtab[t * G::BG_UNITS + rt] = *bg_unit();              // (the next form's P2 writes the slot behind the next barrier)
+                }
+                return;
+            }
+            *bg_unit() = bgtab[rs_t0(pass) * G::BG_UNITS + rt];            // the first pass's form; the consumers read it behind the prologue's barriers
+        }
+        // prologue: every row of the first pass that is made, chunk by chunk (three barriers each; the consumers wait at them)
+        for (int c = 0, c0 = first.clo; c < first.chunks; ++c, c0 += F::CHUNK) {
+            const int nr = first.chi - c0 < F::CHUNK ? first.chi - c0 : F::CHUNK;
             uint4 px;
             p0_load(c0, nr, px);
             p0_store(nr, px);
             RS_BAR();
             p1(nr, rs_t0(pass));
-            flag_crops(c0, c0 + nr - 1, S);
+            if (nr > 0) flag_crops(c0, c0 + nr - 1, S);
             RS_BAR();
             p2(c0, nr, rs_t0(pass));
             RS_BAR();
         }
-        int res_hi = qmin + nrows;
+        int res_hi = first.hi;
         int prev = -1;
         for (;;) {
-            int next_slot, next_pass, lo, hi, extra;
+            int next_slot, next_pass, next_vr;
             bool have_next;
-            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi, extra);
+            RsRound rd;
+            RS_NEXT(pass, res_hi, next_slot, next_pass, next_vr, have_next, rd);
+            const int lo = rd.clo, hi = rd.chi, extra = rd.chunks - 1;      // the rows to make
             const int tn = have_next ? rs_t0(next_pass) : 0;
             // S1 (beside taps 0-19): the crop rows of the first chunk are requested, the V3 transform of the previous pass runs under their flight
             const int nr0 = hi - lo < F::CHUNK ? hi - lo : F::CHUNK;
             uint4 px;
             p0_load(lo, nr0, px);
+            // windowed: the next pass has another first tile: its form of the background row, requested here, stored in S3
+            bool bg_swap = false;
+            uint4 bgv = make_uint4(0, 0, 0, 0);
+            if constexpr (F::WIN) {
+                bg_swap = have_next && tn != rs_t0(pass);
+                if (bg_swap) bgv = bgtab[tn * G::BG_UNITS + rt];
+            }
             if (prev >= 0) e2(prev);
             p0_store(nr0, px);
             RS_BAR();
@@ -460,6 +506,7 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             RS_BAR();
             // S3 (beside the output transform; nobody reads the ring): the rows go to their slots
             p2(lo, nr0, tn);
+            if constexpr (F::WIN) { if (bg_swap) *bg_unit() = bgv; }
             RS_BAR();
             // a ticket's first pass needs more rows than a chunk: the further chunks in three more stages each (the consumers wait)
             for (int c = 0, c0 = lo + F::CHUNK; c < extra; ++c, c0 += F::CHUNK) {
@@ -475,9 +522,10 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             }
             prev = pass;
             if (!have_next) break;
-            res_hi = hi;
+            res_hi = rd.hi;
             tleft = tleft == 1 ? PK : tleft - 1;
             pass = next_pass;
+            vr = next_vr;
             slot = next_slot;
         }
         e2(prev);                                                         // the last pass's activations (behind its third barrier)
@@ -492,8 +540,11 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
         const int boff = (h * CO + n * 32 + j) * 16;
         const int co = n * 32 + j;
         const float bz = bias[co];
-        for (int c = 0; c < rs_round_chunks(nrows, F::CHUNK); ++c) { RS_BAR(); RS_BAR(); RS_BAR(); }      // the producers' prologue
-        int res_hi = qmin + nrows;
+        if constexpr (F::WIN) {
+            if (make_bg) { for (int t = 0; t < G::NBG; ++t) { RS_BAR(); RS_BAR(); } return; }           // the run that makes the background row's table
+        }
+        for (int c = 0; c < first.chunks; ++c) { RS_BAR(); RS_BAR(); RS_BAR(); }                        // the producers' prologue
+        int res_hi = first.hi;
 #define W2_POS(tau_) rs_pos(tau_)
 #define W2_BOFF(tau_) ((rs_ky(tau_) * 8 + W2_POS(tau_)) * G::BV * 16)
         // the weight fragments of taps 0 .. RS_BD - 1 are the same for every pass: the last taps of a pass fetch them for the next one
@@ -525,8 +576,10 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
 #pragma unroll
             for (int pg = 0; pg < 4; ++pg) { const int w_ = pg * (2 * F::TPR) + tx_ * 2 + h; wh[pg] = (w_ & ~15) * 16; wl[pg] = w_ & 15; }
         }
-#define RS_AOFF(ps_)                                                                                                             \
+#define RS_AOFF(ps_, vr_)                                                                                                        \
         do {                                                                                                                     \
+            const SkipV2 v2_ = skipx_v2_unpack(vr_);                                                                             \
+            const int bg_ = G::NR + 1;                                    /* the background slot: it holds the form of this pass's t0 */ \
             int s_ = mg * 32 + j;                                                                                                \
             s_ = s_ < G::RPP * G::TPP ? s_ : G::RPP * G::TPP - 1;                                                                \
             const int rp_ = s_ / G::TPP, r2_ = s_ - rp_ * G::TPP;                                                                \
@@ -534,16 +587,19 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
             const int qo_ = 2 * gp_ + (r2_ & 1), y_ = qo_ % S;                                                                   \
             _Pragma("unroll") for (int ky = 0; ky < G::KH; ++ky) {                                                               \
                 const int iy_ = y_ + ky - G::KH / 2;                                                                             \
-                const int slot_ = (iy_ >= 0 && iy_ < S) ? (qo_ + ky - G::KH / 2) % G::NR + 1 : 0;                                \
+                const bool made_ = !F::WIN || (iy_ >= v2_.lo && iy_ <= v2_.hi);                                                  \
+                const int slot_ = (iy_ >= 0 && iy_ < S) ? (made_ ? (qo_ + ky - G::KH / 2) % G::NR + 1 : bg_) : 0;                \
                 srow[ky] = slot_ * G::ROWL; srot[ky] = w2b_rot(slot_);                                                           \
             }                                                                                                                    \
         } while (0)
 #define RS_AUNIT(tau_) do { if ((tau_) < 20) aoff[rs_ky(tau_)][rs_pg(tau_)] = srow[rs_ky(tau_)] + (wh[rs_pg(tau_)] | (((wl[rs_pg(tau_)] + srot[rs_ky(tau_)]) & 15) << 4)); } while (0)
-        RS_AOFF(pass);
+        RS_AOFF(pass, vr);
         for (;;) {
-            int next_slot, next_pass, lo, hi, extra;
+            int next_slot, next_pass, next_vr;
             bool have_next;
-            RS_NEXT(pass, res_hi, next_slot, next_pass, have_next, lo, hi, extra);
+            RsRound rd;
+            RS_NEXT(pass, res_hi, next_slot, next_pass, next_vr, have_next, rd);
+            const int extra = rd.chunks - 1;
             const bool draw = tleft == 1;
             uint32_t ticket = 0;
             // the ticket after the next one (raw instruction: atomicAdd() waits for the returned value on the spot); stored behind the second barrier
@@ -643,13 +699,14 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
                 }
             }
             { const int g0 = rs_gp0(pass); flag_crops(g0, g0 + rs_nrw(pass) - 1, S / 2); }
-            if (have_next) RS_AOFF(next_pass);
+            if (have_next) RS_AOFF(next_pass, next_vr);
             RS_BAR();                                                     // S3 | the next round
             for (int c = 0; c < extra; ++c) { RS_BAR(); RS_BAR(); RS_BAR(); }    // the further chunks of a ticket's first pass
             if (!have_next) break;
-            res_hi = hi;
+            res_hi = rd.hi;
             tleft = tleft == 1 ? PK : tleft - 1;
             pass = next_pass;
+            vr = next_vr;
             slot = next_slot;
         }
 #undef RS_TAP
@@ -662,7 +719,6 @@ __global__ __launch_bounds__(512) void k_conv12_rs(const uint8_t* __restrict__ c
     }
 #undef RS_NEXT
 #undef RS_LIST
-#undef RS_ROWS
 #undef RS_BAR
     if (__any(!(ovfm < 4368.0f)) && lane == 0) atomicOr(overflow, 3u);      // (nothing is left here behind the last flag_crops; if it ever is, it is unattributed: every crop)
 }

@@ -42,6 +42,8 @@ struct Net {
     float* act2e = nullptr;                    // the pooled conv2 activations of an all-zero crop [20][20][64], made by the run that makes v3e
     int2* skipx_cols = nullptr;                // [max_crops] first / last non-zero column
     int* skipx_list = nullptr;                 // the windowed passes (skipx_pack), in order, + the SKIP_PAD entry behind them
+    uint4* bgtab = nullptr;                    // the background row of the windowed instance as its first tile t0 = 0, 1, 2 sees it: the LDS slot's bytes (cnn_fused12rs.h)
+    int* skipx_rows = nullptr;                 // beside every entry of skipx_list: the V2 rows of its crop that are made (skipx_v2_pack)
     // computing only the row pairs of conv3 whose V3 rows hold more than background (cnn_skip3.h, cnn_skip_kernels.h)
     float* act3e = nullptr;                    // the act3 of an all-zero crop [10][10][128], made when the weights are loaded, behind v3e
     uint2* skip3_counts = nullptr;             // listed passes and pairs per workgroup of k_pair_count

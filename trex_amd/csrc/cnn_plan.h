@@ -12,6 +12,7 @@ namespace trexhip {
 // the bits of TREXHIP_CONV_GEOM (a test hook; include/trexhip.h documents the values)
 enum : int {
     GEOM_FP32_ACT = 0xfff,            // bits 0-11, any of them: the fp32-activation chain
+    GEOM_NO_BGROWS = 1 << 22,         // the windowed conv1+conv2 makes every V2 row, background rows too
     GEOM_NO_SKIPX = 1 << 23,          // no crop gets a window
     GEOM_DENSE_FC1 = 1 << 24,         // the dense fc1
     GEOM_V3_COPY = 1 << 25,           // the listed conv3 reads every row from V3
@@ -20,7 +21,7 @@ enum : int {
     GEOM_TWO_KERNEL = 1 << 28,        // conv1 and conv2 as two kernels
     GEOM_ROLE_SPLIT = 1 << 29,        // the role-split conv1+conv2 at any batch size
     GEOM_FUSED_2WG = 1 << 30,         // the two-workgroup conv1+conv2 at any batch size
-    GEOM_MASK = GEOM_FP32_ACT | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
+    GEOM_MASK = GEOM_FP32_ACT | GEOM_NO_BGROWS | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
 };
 
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
@@ -33,6 +34,10 @@ enum : int {
 //                             row pairs of one crop) of the crops whose blob fits 8 tiles, the aligned full-width passes the other crops need;
 //                             k_conv12_rs<W12XGeom> runs on the first in front of k_conv12_rs<W12RGeom> on the second.  Off (GEOM_NO_SKIPX, bit
 //                             23): no crop gets a window -- the same three kernels, one list, the full-width instance alone
+//                 bgrows      k_pass_list writes, beside every windowed pass, the V2 rows of its crop that have a non-zero crop row under them
+//                             (skipx_v2_rows): the windowed instance's producers make only those, its consumers read the others from a
+//                             background slot, filled from a table that instance wrote when the weights were loaded.  Off (GEOM_NO_BGROWS,
+//                             bit 22): the word says every row, the producers make every new row
 //                 skip3       k_pair_count and k_pair_list in front of k_v3_fill; k_act3_fill and BOTH forms of k_conv5_wpair, the dense one and
 //                             the one that walks the listed row pairs, behind conv2 -- the word k_pair_list writes names the one that runs, the
 //                             other returns at once.  Off (GEOM_DENSE_CONV3, bit 26): the dense conv3 alone
@@ -85,6 +90,7 @@ struct CnnPlan {
     bool skipx;                     // where skip is on: the crops whose blob fits a window of 8 tiles take the windowed instance of the role-split kernel
                                     // (cnn_skipx.h), the others the full-width one, each on its own list, grid conv2.grid and tickets of pk2 slots; off: bit 23,
                                     // or a batch of SKIPX_MAX_CROPS (2^22) crops or more, whose crop index a windowed list entry does not hold
+    bool bgrows;                    // where skipx is on: the windowed instance makes only the V2 rows with a non-zero crop row under them; off: bit 22
 };
 
 inline int ceil_div(const int a, const int b) { return (a + b - 1) / b; }
@@ -143,6 +149,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
     p.skip = role_split && !(geom & GEOM_NO_SKIP);
     p.skip3 = p.skip && !(geom & GEOM_DENSE_CONV3);
     p.skipx = p.skip && !(geom & GEOM_NO_SKIPX) && n < SKIPX_MAX_CROPS;
+    p.bgrows = p.skipx && !(geom & GEOM_NO_BGROWS);
     if (p.skip3) {
         p.skip3_grid = ceil_div(ceil_div(n, 32 /* Skip3Geom::BLOCK crops per thread */), 256);
         p.act3_fill = {ceil_div(n, 16), n};

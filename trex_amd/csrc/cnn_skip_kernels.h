@@ -4,9 +4,11 @@
 // stream, no host read between them; the words they leave in Net::d_skip: cnn_skip_words.h.  In the order they run (launch_skip_prep):
 //   k_crop_bands   first / last non-zero row of every crop (it looks at the bytes, not at how the crop was made), and, where crops can have
 //                  windows (`cols` not null), the first / last non-zero column
-//   k_pass_count   thread i: pass i and crop i.  Per SKIP_LB of them: full-width passes, passes the row rule lists, windowed passes, windowed crops
+//   k_pass_count   thread i: pass i and crop i.  Per SKIP_LB of them: full-width passes, passes the row rule lists, windowed passes, windowed crops,
+//                  and, where the windowed instance leaves out background rows (`bgrows`), the V2 rows those passes read and the rows made of them
 //   k_pass_list    order-preserving compaction into the lists k_conv12_rs walks: the aligned full-width passes that a crop WITHOUT a window needs,
-//                  and the windowed passes of the crops that have one; their lengths, the entry behind the end of each, the windowed instance's
+//                  and the windowed passes of the crops that have one, beside each of these the V2 rows of its crop that are made at all
+//                  (skipx_v2_rows; every row without `bgrows`); their lengths, the entry behind the end of each, the windowed instance's
 //                  ticket counter zeroed, and SK_LEN / SK_NPASS / SK_FILLED by the row rule alone.  `cols` null: no crop has a window -- the
 //                  full-width list is the row rule's, and neither the windowed list nor the SKX_* words are touched
 //   k_pair_count   (listed conv3) listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK
@@ -24,6 +26,7 @@
 
 static constexpr int SKIP_LB = 1024;      // passes / crops per block of the count / list kernels (one per thread)
 static constexpr int SKIP_PAD = 1;        // one entry behind the last one: k_conv12_rs clamps every read behind the list's end to it (RS_LIST)
+static constexpr int SKIP_NCNT = 6;       // words per block that k_pass_count leaves for k_pass_list
 static constexpr int SKIP_FILL_TB = 256;  // V3 rows per block of the fill kernel (one per thread)
 
 // one wave per crop: 400 x 16 bytes, unit i lies in row i / 5
@@ -98,12 +101,15 @@ struct SkipXWinOf {
     }
 };
 // thread i of the grid: pass i of the batch (full width: is it needed by a crop without a window; and by the row rule alone, for the counters)
-// and crop i (its windowed passes).  counts[4 b ..]: full-width passes, aligned needed passes, windowed passes, windowed crops of block b
-struct SkipXItem { bool full, need; int wpasses, t0; SkipRows rows; };
-__device__ __forceinline__ SkipXItem skipx_item(const int i, const int n, const int2* __restrict__ bands, const int2* __restrict__ cols, const bool all) {
+// and crop i (its windowed passes).  counts[SKIP_NCNT b ..]: full-width passes, aligned needed passes, windowed passes, windowed crops of block
+// b; the V2 rows its windowed passes read -- a crop's passes taken as one run, as they are wherever no ticket ends inside the crop: the rows
+// rs_v2_rows gives for its needed V3 rows -- and the rows of those that are made (both 0 without `bgrows`)
+struct SkipXItem { bool full, need; int wpasses, t0; SkipRows rows; SkipV2 v2; int v2_read, v2_made; };
+__device__ __forceinline__ SkipXItem skipx_item(const int i, const int n, const int2* __restrict__ bands, const int2* __restrict__ cols, const bool all,
+                                                const bool bgrows) {
     const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
     const bool none = all || !cols;      // no crop has a window: a pass is on the full-width list where the row rule lists it (uniform across the grid)
-    SkipXItem it{false, false, 0, -1, {1, 0}};
+    SkipXItem it{false, false, 0, -1, {1, 0}, SKIPX_V2_ALL, 0, 0};
     if (i < n_pass) {
         it.need = skip_needed(i, total_pairs, bands, all);
         it.full = it.need && (none || skipx_full_needed(i, total_pairs, SkipBandsOf{bands}, SkipXWinOf{cols, all}));
@@ -113,47 +119,53 @@ __device__ __forceinline__ SkipXItem skipx_item(const int i, const int n, const 
         const int2 b = bands[i];
         it.rows = skip_rows({b.x, b.y});
         it.wpasses = it.t0 >= 0 ? skipx_passes(it.rows) : 0;
+        if (bgrows && it.wpasses) {
+            it.v2 = skipx_v2_rows({b.x, b.y});
+            const RsRound r = rs_round(false, 0, it.rows.lo, it.rows.hi, true, it.v2, SkipXGeom::CHUNK);      // (rows of the crop: crop 0 of a batch)
+            it.v2_read = r.hi - r.lo;
+            it.v2_made = r.chi - r.clo;
+        }
     }
     return it;
 }
 __global__ __launch_bounds__(SKIP_LB) void k_pass_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
-                                                        const uint32_t* __restrict__ words, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t s_cnt[4];
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+                                                        const uint32_t* __restrict__ words, uint32_t* __restrict__ counts, const int bgrows) {
+    __shared__ uint32_t s_cnt[SKIP_NCNT];
+    if (threadIdx.x < SKIP_NCNT) s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    const SkipXItem it = skipx_item(blockIdx.x * SKIP_LB + threadIdx.x, n, bands, cols, words[SK_EMPTY_RANGE] != 0);
-    uint32_t v[4] = {it.full ? 1u : 0u, it.need ? 1u : 0u, (uint32_t)it.wpasses, it.wpasses ? 1u : 0u};
+    const SkipXItem it = skipx_item(blockIdx.x * SKIP_LB + threadIdx.x, n, bands, cols, words[SK_EMPTY_RANGE] != 0, bgrows != 0);
+    uint32_t v[SKIP_NCNT] = {it.full ? 1u : 0u, it.need ? 1u : 0u, (uint32_t)it.wpasses, it.wpasses ? 1u : 0u, (uint32_t)it.v2_read, (uint32_t)it.v2_made};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < SKIP_NCNT; ++k) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
         if ((threadIdx.x & 63) == 0 && v[k]) atomicAdd(&s_cnt[k], v[k]);
     }
     __syncthreads();
-    if (threadIdx.x < 4) counts[blockIdx.x * 4 + threadIdx.x] = s_cnt[threadIdx.x];
+    if (threadIdx.x < SKIP_NCNT) counts[blockIdx.x * SKIP_NCNT + threadIdx.x] = s_cnt[threadIdx.x];
 }
 __global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n,
                                                        uint32_t* __restrict__ words, const uint32_t* __restrict__ counts, int* __restrict__ list,
-                                                       int* __restrict__ wlist) {
-    __shared__ uint32_t s_base[4], s_wave[2][SKIP_LB / 64];
+                                                       int* __restrict__ wlist, int* __restrict__ wrows, const int bgrows) {
+    __shared__ uint32_t s_base[SKIP_NCNT], s_wave[2][SKIP_LB / 64];
     const int total_pairs = n * SkipGeom::V3_ROWS, n_pass = (total_pairs + SkipGeom::RPP - 1) / SkipGeom::RPP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * SKIP_LB + tid;
-    if (tid < 4) s_base[tid] = 0;
+    if (tid < SKIP_NCNT) s_base[tid] = 0;
     __syncthreads();
     // what the blocks in front of this one counted
-    uint32_t part[4] = {0, 0, 0, 0};
+    uint32_t part[SKIP_NCNT] = {0, 0, 0, 0, 0, 0};
     for (int b = tid; b < (int)blockIdx.x; b += SKIP_LB) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) part[k] += counts[b * 4 + k];
+        for (int k = 0; k < SKIP_NCNT; ++k) part[k] += counts[b * SKIP_NCNT + k];
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < SKIP_NCNT; ++k) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) part[k] += __shfl_xor(part[k], d);
         if (lane == 0 && part[k]) atomicAdd(&s_base[k], part[k]);
     }
-    const SkipXItem it = skipx_item(i, n, bands, cols, words[SK_EMPTY_RANGE] != 0);
+    const SkipXItem it = skipx_item(i, n, bands, cols, words[SK_EMPTY_RANGE] != 0, bgrows != 0);
     // inclusive scans over the workgroup: inside the wave by shuffles, the waves' totals through LDS
     uint32_t sc[2] = {it.full ? 1u : 0u, (uint32_t)it.wpasses};
 #pragma unroll
@@ -172,12 +184,12 @@ __global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ 
     if (it.full) list[s_base[0] + sc[0] - 1] = i;
     if (it.wpasses) {
         const uint32_t at = s_base[2] + sc[1] - (uint32_t)it.wpasses;
-        for (int k = 0; k < it.wpasses; ++k) wlist[at + k] = skipx_pack(skipx_pass(i, it.rows, it.t0, k));
+        for (int k = 0; k < it.wpasses; ++k) { wlist[at + k] = skipx_pack(skipx_pass(i, it.rows, it.t0, k)); wrows[at + k] = skipx_v2_pack(it.v2); }
     }
     if (blockIdx.x == gridDim.x - 1 && tid == SKIP_LB - 1) {               // the last block knows the lengths
         const uint32_t full = s_base[0] + sc[0], wp = s_base[2] + sc[1];
         uint32_t need = s_base[1], wc = s_base[3];
-        for (int k = 0; k < 2; ++k) { const uint32_t c = counts[blockIdx.x * 4 + 1 + 2 * k]; if (k) wc += c; else need += c; }
+        for (int k = 0; k < 2; ++k) { const uint32_t c = counts[blockIdx.x * SKIP_NCNT + 1 + 2 * k]; if (k) wc += c; else need += c; }
         for (int k = 0; k < SKIP_PAD; ++k) list[full + k] = n_pass;
         // SK_LEN, SK_NPASS, SK_FILLED: the aligned passes the row rule lists and the rows outside them (the batch's last pass may be short), whoever
         // supplies those rows
@@ -185,8 +197,9 @@ __global__ __launch_bounds__(SKIP_LB) void k_pass_list(const int2* __restrict__ 
         const uint32_t listed_rows = need * SkipGeom::RPP - (last_need ? (uint32_t)(n_pass * SkipGeom::RPP - total_pairs) : 0u);
         words[SK_LEN] = need; words[SK_NPASS] = (uint32_t)n_pass; words[SK_FILLED] = (uint32_t)total_pairs - listed_rows;
         if (cols) {                                                        // (null: nobody reads the windowed list or its words)
-            for (int k = 0; k < SKIP_PAD; ++k) wlist[wp + k] = 0;
+            for (int k = 0; k < SKIP_PAD; ++k) { wlist[wp + k] = 0; wrows[wp + k] = skipx_v2_pack(SKIPX_V2_ALL); }
             words[SKX_CROPS] = wc; words[SKX_PASSES] = wp; words[SKX_FULL] = full; words[SKX_CTR] = 0;
+            words[SKX_V2_READ] = s_base[4] + counts[blockIdx.x * SKIP_NCNT + 4]; words[SKX_V2_MADE] = s_base[5] + counts[blockIdx.x * SKIP_NCNT + 5];
         }
     }
 }

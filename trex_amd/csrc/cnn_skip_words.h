@@ -27,8 +27,10 @@ enum : int {
     SKX_PASSES = 27,         // windowed passes listed by the last call: the length of the windowed instance's list
     SKX_FULL = 28,           // full-width passes listed by the last call (for the crops without a window): the length of the full-width instance's list
     SKX_CTR = 29,            // the windowed instance's ticket counter (zeroed by k_pass_list)
+    SKX_V2_READ = 30,        // V2 rows the last call's windowed passes read as new rows, a crop's passes counted as one run (cnn_skipx.h: skipx_v2_rows)
+    SKX_V2_MADE = 31,        // ... and how many of them the producers made: the others are background rows.  Both 0 where background rows are made
     SK_WORDS = 32
 };
-static_assert(SK_FILLED < SK3_PAIRS && SK3_LAST < SKX_CROPS && SKX_CTR < SK_WORDS, "no word twice, the last one inside the table");
+static_assert(SK_FILLED < SK3_PAIRS && SK3_LAST < SKX_CROPS && SKX_V2_MADE < SK_WORDS, "no word twice, the last one inside the table");
 
 }  // namespace trexhip

@@ -78,10 +78,31 @@ TREXHIP_HD constexpr bool skipx_full_needed(const int p, const int total_pairs, 
     return false;
 }
 
-// The stages (s_barrier) of one round of k_conv12_rs, either instance: three for the taps beside the first chunk of the next pass's new V2 rows,
-// three more per further chunk.  BOTH roles call this with the same count of new rows: they cannot execute different numbers of barriers.
-TREXHIP_HD constexpr int rs_round_chunks(const int new_rows, const int chunk) { return new_rows <= chunk ? 1 : (new_rows + chunk - 1) / chunk; }
-TREXHIP_HD constexpr int rs_round_stages(const int new_rows, const int chunk) { return 3 * rs_round_chunks(new_rows, chunk); }
+// The V2 rows (conv1's pooled rows, 0 .. V2_ROWS - 1) of a crop that have a non-zero crop row under them, from its first and last non-zero
+// ROW: V2 row y reads the crop rows skip_layer_lo(y) .. skip_layer_hi(y) = 2 y - 2 .. 2 y + 3.  None: lo > hi.  Every other V2 row of the crop is
+// the BACKGROUND row: conv1's accumulator is exactly 0 for each of its pixels (background is 0, and so is the padding around the crop), each
+// pixel is relu(0 * inv_scale1 + bias) -- the same in every crop and at every y.  The windowed instance does not make such rows: its consumers
+// read them from a row slot made once per workgroup and first tile t0 (conv2's zero padding at tiles 0 and 9 is all that makes it depend on t0)
+struct SkipV2 { int lo, hi; };
+static constexpr SkipV2 SKIPX_V2_ALL{0, SkipGeom::V2_ROWS - 1};
+TREXHIP_HD constexpr SkipV2 skipx_v2_rows(const SkipBand b) {
+    using G = SkipGeom;
+    if (b.y0 > b.y1) return {1, 0};
+    // skip_layer_hi(y) >= y0  and  skip_layer_lo(y) <= y1
+    constexpr int HI0 = skip_layer_hi(0), LO0 = skip_layer_lo(0);
+    const int lo = b.y0 <= HI0 ? 0 : (b.y0 - HI0 + G::POOL - 1) / G::POOL;
+    const int hi = (b.y1 - LO0) / G::POOL;
+    return {lo, hi < G::V2_ROWS - 1 ? hi : G::V2_ROWS - 1};
+}
+// a crop's range as the word k_pass_list writes beside every windowed list entry (Net::skipx_rows): both roles of the kernel read it as a scalar,
+// one round ahead, like the entry itself
+TREXHIP_HD constexpr int skipx_v2_pack(const SkipV2 v) { return v.lo | v.hi << 8; }
+TREXHIP_HD constexpr SkipV2 skipx_v2_unpack(const int w) { return {w & 0xff, (w >> 8) & 0xff}; }
+
+// The stages (s_barrier) of one round of k_conv12_rs, either instance: three for the taps beside the first chunk of the V2 rows the producers
+// make for the next pass, three more per further chunk.  Called by rs_round alone.
+TREXHIP_HD constexpr int rs_round_chunks(const int made_rows, const int chunk) { return made_rows <= chunk ? 1 : (made_rows + chunk - 1) / chunk; }
+TREXHIP_HD constexpr int rs_round_stages(const int made_rows, const int chunk) { return 3 * rs_round_chunks(made_rows, chunk); }
 
 // the V2 rows [qmin, qmin + nrows) of the batch that the V3 rows gp0 .. gpl (of one crop, or of the aligned pass) read: two halo rows either
 // side where the crop has them
@@ -98,5 +119,26 @@ TREXHIP_HD constexpr SkipXV2 rs_new_rows(const bool follows, const int res_hi, c
     const int lo = (follows && res_hi > v.qmin) ? res_hi : v.qmin;
     return {lo, v.qmin + v.nrows - lo};
 }
+// One round of k_conv12_rs, as BOTH roles take it from this one function on the same data: the new rows [lo, hi) of the next pass (rs_new_rows;
+// the ring counts as holding them from then on), the rows [clo, chi) of them the producers make -- `clip`: those inside the range `v2` of the
+// pass's crop (the windowed instance, whose pass holds one crop: the others are background rows, which nobody makes and the consumers read from
+// the background slot); otherwise all of them -- and the chunks of the round, by the rows MADE: the roles cannot execute different numbers
+// of barriers.  A first pass: follows = false.
+struct RsRound { int lo, hi, clo, chi, chunks; };
+TREXHIP_HD constexpr RsRound rs_round(const bool follows, const int res_hi, const int gp0n, const int gpln, const bool clip, const SkipV2 v2, const int chunk) {
+    constexpr int S = W2bGeom::S;
+    const SkipXV2 nw = rs_new_rows(follows, res_hi, gp0n, gpln);
+    const int lo = nw.qmin, hi = nw.qmin + nw.nrows;
+    int clo = lo, chi = hi;
+    if (clip) {
+        const int base = (gp0n / (S / 2)) * S;                              // the crop's first V2 row of the batch
+        clo = lo > base + v2.lo ? lo : base + v2.lo;
+        chi = hi < base + v2.hi + 1 ? hi : base + v2.hi + 1;
+        if (chi < clo) chi = clo;
+    }
+    return {lo, hi, clo, chi, rs_round_chunks(chi - clo, chunk)};
+}
+// no round: the last pass of a workgroup has no next one
+static constexpr RsRound RS_ROUND_NONE{0, 0, 0, 0, 1};
 
 }  // namespace trexhip
