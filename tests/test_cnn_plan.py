@@ -107,6 +107,8 @@ def test_any_size(exe):
         head="k_head", head_grid=7, rerun=1, head_plans=0, rerun_conv1=0, r_conv2="400/400", r_conv3="100/100", r_fc1_grid="4,8", r_head_grid=7, any="4,4,8,1,8")
     has(plan(exe, 3, W=100, H=60, CH=3), chain="any_size", conv1_grid=24, conv2="21/21", conv3="6/6", fc1_grid="1,7", K=10752, any="8,7,4,2,8")
     has(plan(exe, 5, W=8, H=8), chain="any_size", conv1_grid=5, conv2="5/5", conv3="5/5", fc1_grid="1,1", K=128, any="1,1,8,1,8")
+    # 120x16: conv2 over 4 x 30 windows and conv3 over 2 x 15 both take the 16-wide tile (4 x 16 windows): 1 x 2 tiles and 1 x 1, 8-wide would be 4 and 2
+    has(plan(exe, 33, W=120, H=16), chain="any_size", conv1_grid=132, conv2="66/66", conv3="33/33", K=3840, any="4,2,16,1,16")
     has(plan(exe, 3000, W=64, H=64), r_conv2="1024/12000", r_conv3="1024/3000", head="k_head", head_plans=0)
     has(plan(exe, 100, W=64, H=64, mode=BF16X6), chain="any_size", rerun=0, fc1="k_fc1")
 

@@ -53,6 +53,37 @@ def test_reference_vectors_at_other_sizes(case, mode):
     seg.close()
 
 
+@pytest.fixture(scope="module")
+def wide_case():
+    """120x16, 1 channel, 8 classes, 33 crops: the only V118_3 case on the 16-wide tile (test_cnn_plan.py::test_any_size) -- conv2 over 4 x 30
+    windows, two tiles, ragged in x; conv3 over 2 x 15, one tile, ragged in x and y.  The synthetic ellipse fills 14 % of such a crop, so the
+    later half of the crops gets texture on every zero pixel (as cnn_arch_edge_cases.make): a wrong column at the ragged edge must not see
+    constant background only.  -> (state, crops, the oracle's probabilities), computed once"""
+    w, h, classes, n = 120, 16, 8, 33
+    st = weights.synthetic_state(classes, 41, 1, w, h)
+    crops = weights.synthetic_crops(n, 1041, 1, w, h)
+    late = crops[n // 2:]
+    late[late == 0] = np.random.default_rng(2041).integers(1, 256, late.shape, dtype=np.uint8)[late == 0]
+    assert (crops[:n // 2] == 0).any() and not (late == 0).any()
+    want, _ = cnn_oracle.predict(st, crops, threads=8)
+    return st, crops, want
+
+
+@pytest.mark.parametrize("mode", EXACT_MODES)
+def test_the_16_wide_tile_against_the_oracle(wide_case, mode):
+    st, crops, want = wide_case
+    seg = make_net(st, 8, 1, 120, 16)
+    seg.set_identity_precision(mode)
+    p, _ = run_device(seg, crops, 8)
+    assert p.shape == want.shape and np.all(np.isfinite(p))
+    err = np.abs(p - want).max()
+    print(f"120x16 mode {mode}: max |dp| = {err:.3g}")
+    assert err <= 1e-4, err
+    if mode == capi.CNN_FP16X3:
+        assert seg.guard_stats() == (0, False)
+    seg.close()
+
+
 @pytest.mark.parametrize("n", [300, 2049])
 @pytest.mark.parametrize("size", [(64, 64), (100, 60)])
 def test_large_batches_against_the_oracle(size, n):

@@ -21,6 +21,7 @@
 #include "cnn_net.h"
 #include "cnn_arch.h"
 #include "cnn_split.h"
+#include "conv_tiled.h"
 #include "cnn_weights.h"
 #include <algorithm>
 #include <cmath>
@@ -112,42 +113,8 @@ __global__ __launch_bounds__(256, 2) void k_conv1(const uint8_t* __restrict__ cr
 // ------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ------------------------------------------------------------------------------------------------
-// fp16 range guard, per crop (round 5).  The default chain raises overflow[0] when an activation leaves the range its fp16 pieces can hold and,
-// where it knows the crop, flags[crop].  k_guard_plan turns the flags into a plan for the bf16 re-run:
-//   plan[0] = number of listed crops, plan[1] = mode (0 nothing to do, 1 the listed crops only, 2 every crop), plan[2 ..] = the list.
-// The re-run kernels take the plan as their guard: item i of a launch is crop plan[2 + i] in list mode.  One out-of-range crop in 25600
-// used to cost a second pass over the whole batch (4x the step); now it costs the launches of the re-run chain and its own crop.
-// ------------------------------------------------------------------------------------------------
+// the fp16 range guard's plan: guard_plan (conv_tiled.h), by a launch of its own or by the small head's first workgroup
 __device__ __forceinline__ int fb_count(const uint32_t* __restrict__ plan, const int n) { return (plan && plan[1] == 1u) ? (int)plan[0] : n; }
-// (called by every thread of ONE workgroup of NT threads; `cnt` is that workgroup's shared counter.)  The last reader of the range flag and of the
-// persistent convolutions' pass counters hands all three back zeroed for the next forward pass: no memset in front of a pass (round 6)
-template <int NT>
-__device__ __forceinline__ void guard_plan(uint32_t* __restrict__ overflow, uint8_t* __restrict__ flags, const int n, uint32_t* __restrict__ plan, uint32_t& cnt) {
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    const uint32_t raised = overflow[0];      // bit 0: something left the fp16 range; bit 1: a kernel that cannot name the crop saw it
-    if (raised == 0u) {
-        // (flags of an aborted earlier pass would enlarge a later plan: what is there is cleared even when nothing was raised -- ADVICE r5)
-        for (int i = threadIdx.x; i < n; i += NT) if (flags[i]) flags[i] = 0;
-        if (threadIdx.x == 0) { plan[0] = 0; plan[1] = 0; overflow[1] = 0u; overflow[2] = 0u; }
-        return;
-    }
-    for (int i = threadIdx.x; i < n; i += NT)
-        if (flags[i]) {
-            flags[i] = 0;
-            const uint32_t k = atomicAdd(&cnt, 1u);
-            if (k < (uint32_t)FB_MAX) plan[2 + k] = (uint32_t)i;
-        }
-    __syncthreads();
-    // an unattributed flag re-runs every crop even when other crops ARE listed: a crop that left the range in k_conv1_wpre / k_conv2_wpre2 (the
-    // 3-channel chain) must not keep its fp16 result because fc1 happened to flag another crop of the batch
-    if (threadIdx.x == 0) {
-        const bool whole = (raised & 2u) || cnt == 0u || cnt > (uint32_t)FB_MAX;
-        plan[0] = whole ? 0u : cnt; plan[1] = whole ? 2u : 1u;
-        overflow[0] = 0u; overflow[1] = 0u; overflow[2] = 0u;
-    }
-}
 __global__ __launch_bounds__(1024) void k_guard_plan(uint32_t* __restrict__ overflow, uint8_t* __restrict__ flags, const int n, uint32_t* __restrict__ plan) {
     __shared__ uint32_t cnt;
     guard_plan<1024>(overflow, flags, n, plan, cnt);

@@ -1,11 +1,11 @@
 // cnn_arch.hip -- the identity networks v100, v110, v119 and v200 (visual_identification_network_torch.py:30-382; the layer table: cnn_arch_plan.h)
 // at any individual_image_size of their range, inference only.  NHWC fp32 activations throughout, every pool floors like nn.MaxPool2d.
 //
-//   k_arch_conv1<CH, T>   first layer, u8 crops -> fp32, T x T taps, 16 output channels per workgroup (grid y = CO / 16), exact fp32 on the VALU:
-//                         the model of k_any_conv1 with the tap size, the optional pool and the epilogue below
-//   k_arch_conv<COB, ..>  every further convolution as T * T shifted GEMMs on the matrix cores, the model of k_any_conv (cnn_any.hip): run-time
-//                         CI, taps 3 or 5, fused floor 2x2 max-pool or none, COB = 32 / 64 / 128 output channels per workgroup with the
-//                         channel block on the grid's y, the three arithmetic kinds, the fp16 range flag per crop and the guarded bf16x6 re-run
+//   k_arch_conv1<CH, T>   first layer, u8 crops -> fp32, T x T taps, 16 output channels per workgroup (grid y = CO / 16), exact fp32 on the VALU
+//   k_arch_conv<COB, ..>  every further convolution as T * T shifted GEMMs on the matrix cores: run-time CI, taps 3 or 5, fused floor 2x2 max-pool
+//                         or none, COB = 32 / 64 / 128 output channels per workgroup with the channel block on the grid's y, the three
+//                         arithmetic kinds, the fp16 range flag per crop and the guarded bf16x6 re-run
+//                         -- both are the TiledArgs instances of the bodies in conv_tiled.h, which the any-size V118_3 chain (cnn_any.hip) shares
 //   k_pool3               floor 3x3 max-pool, streaming, one float4 of channels per lane (v200: a 3x3 window does not fit the window-major tile)
 //   k_gap                 global average pool (v200), summed in raster order
 //   k_arch_fc1            fc1 as an exact fp32 GEMM on the matrix cores, K split over the 4 waves of a workgroup and summed in wave order
@@ -15,300 +15,38 @@
 // The category network (trex_learn_category.py:18-44; category_spec, cnn_arch_plan.h) runs the same chain from the context's second slot
 // (ctx->cat): its first layer is the NORM instance of k_arch_conv1, which stages x / 127.5 - 1 instead of x, and k_cat_label follows its head.
 //
-// The epilogue of both convolution kernels: relu((max_window(conv) * out_scale + bias[co]) * s[co] + t[co]) -- the affine BEHIND the pool, which
-// v110 needs (its BatchNorm follows the max-pool and its scale may be negative); v119 / v200 fold their BatchNorm into weights and bias
-// (s = 1, t = 0), v100 has none.
+// The epilogue of both convolution kernels puts the layer's affine (s, t) BEHIND the pool (conv_tiled.h): v110 needs it, v119 / v200 fold their
+// BatchNorm into weights and bias (s = 1, t = 0), v100 has none.
 //
 // A call's crops are walked in chunks of ArchPlan::chunk (a constant of version and size); every kernel computes a crop from that crop alone, in
 // an order that does not depend on the chunk or on n, so a crop's row is the same bits wherever it stands.
 #include "cnn_arch.h"
-#include "cnn_split.h"
+#include "conv_tiled.h"
 #include "cnn_weights.h"
 
 namespace trexhip {
 namespace {
 
-// ------------------------------------------------------------------------------------------------
-// first layer: CH -> 16 channels of one block, T x T 'same', optional floor 2x2 max-pool, exact fp32
-// ------------------------------------------------------------------------------------------------
-// One thread per 2 x 2 window of conv pixels, 16 x 16 windows per workgroup.  LDS: (CH * T * T * 16 + CH * PW * PW) * 4 bytes, PW = 32 + T - 1
-// (3 channels, 5 taps: 4800 + 15552 = 20352 B); 64 accumulators per thread
-// NORM (the category network, trex_learn_category.py:289, :435 "torch.tensor(images, float32) / 127.5 - 1"): a pixel inside the crop is staged as
-//     __fsub_rn(__fdiv_rn((float)byte, 127.5f), 1.0f)      -- a true fp32 division, then an fp32 subtraction, each rounded on its own --
-// which is what torch's CPU and what numpy give for all 256 bytes (a multiply by the rounded reciprocal differs at 111 of them, a fused multiply-
-// subtract at 205: tests/test_category_ref.py); a pixel outside it as 0, because the reference pads the NORMALISED image with zeros.  The offset
-// can therefore not live in the bias.  The identity instances (NORM = false) compile to what they were: the mode is a template parameter.
+// The first layer: conv1_tiled (conv_tiled.h) with CO, the pool and the affine as arguments and the block of 16 output channels on the grid's y.
+// NORM: the category network's, which stages x / 127.5 - 1; the identity instances compile without it.
 template <int CH, int T, bool NORM = false>
 __global__ __launch_bounds__(256) void k_arch_conv1(const uint8_t* __restrict__ crops /*[N][H][W][CH]*/, const float* __restrict__ w /*[CO/16][CH][T*T][16]*/,
                                                     const float* __restrict__ bias, const float* __restrict__ sv, const float* __restrict__ tv,
                                                     float* __restrict__ out /*[N][Ho][Wo][CO]*/, const int CO, const int W, const int H, const int pool,
                                                     const int tx_n, const int tiles) {
-    constexpr int C1 = ARCH_C1T, PW = 2 * C1 + T - 1, PAD = T / 2, T2 = T * T;
-    __shared__ __attribute__((aligned(16))) float wl[CH * T2 * 16];
-    __shared__ float img[CH * PW * PW];
-    const int crop = blockIdx.x / tiles, t = blockIdx.x - crop * tiles;
-    const int ty = t / tx_n, tx = t - ty * tx_n;
-    const int cog = blockIdx.y;
-    const int y0 = 2 * C1 * ty - PAD, x0 = 2 * C1 * tx - PAD;
-    const uint8_t* src = crops + (size_t)crop * H * W * CH;
-    const float* wg = w + (size_t)cog * CH * T2 * 16;
-    for (int i = threadIdx.x; i < CH * T2 * 16; i += 256) wl[i] = wg[i];
-    for (int i = threadIdx.x; i < PW * PW * CH; i += 256) {
-        const int c = i % CH, p = i / CH, py = p / PW, px = p - py * PW;
-        const int iy = y0 + py, ix = x0 + px;
-        const bool inside = iy >= 0 && iy < H && ix >= 0 && ix < W;
-        const size_t at = ((size_t)iy * W + ix) * CH + c;
-        if constexpr (NORM) img[c * PW * PW + p] = inside ? __fsub_rn(__fdiv_rn((float)src[at], 127.5f), 1.0f) : 0.f;      // zero padding of the normalised image
-        else img[c * PW * PW + p] = inside ? (float)src[at] : 0.f;                                                          // predict_numpy: no scaling
-    }
-    __syncthreads();
-    const int wy = threadIdx.x / C1, wx = threadIdx.x % C1;
-    const int py0 = 2 * (C1 * ty + wy), px0 = 2 * (C1 * tx + wx);       // the window's first conv pixel
-    if (py0 >= H || px0 >= W) return;
-    float acc[4][16];
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int co = 0; co < 16; ++co) acc[s4][co] = 0.f;
-    for (int c = 0; c < CH; ++c) {
-        const float* base = img + c * PW * PW + (2 * wy) * PW + 2 * wx;
-#pragma unroll 1
-        for (int ky = 0; ky < T; ++ky) {
-            float r0[T + 1], r1[T + 1];
-#pragma unroll
-            for (int b6 = 0; b6 < T + 1; ++b6) { r0[b6] = base[ky * PW + b6]; r1[b6] = base[(ky + 1) * PW + b6]; }
-#pragma unroll
-            for (int kx = 0; kx < T; ++kx) {
-                const float4* wt = reinterpret_cast<const float4*>(wl + (c * T2 + ky * T + kx) * 16);
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const float4 wv = wt[q4];
-                    const float ww[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int co = q4 * 4 + q;
-                        acc[0][co] = fmaf(r0[kx], ww[q], acc[0][co]);
-                        acc[1][co] = fmaf(r0[kx + 1], ww[q], acc[1][co]);
-                        acc[2][co] = fmaf(r1[kx], ww[q], acc[2][co]);
-                        acc[3][co] = fmaf(r1[kx + 1], ww[q], acc[3][co]);
-                    }
-                }
-            }
-        }
-    }
-    const int cb = cog * 16;
-    if (pool) {
-        const int Ho = H / 2, Wo = W / 2, oy = py0 >> 1, ox = px0 >> 1;
-        if (oy >= Ho || ox >= Wo) return;                                // the odd last row / column is dropped by the floor
-        float* o = out + (((size_t)crop * Ho + oy) * Wo + ox) * CO + cb;
-#pragma unroll
-        for (int co = 0; co < 16; co += 4) {
-            float4 v;
-            float* vv = &v.x;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float m = fmaxf(fmaxf(acc[0][co + q], acc[1][co + q]), fmaxf(acc[2][co + q], acc[3][co + q]));
-                vv[q] = fmaxf((m + bias[cb + co + q]) * sv[cb + co + q] + tv[cb + co + q], 0.f);
-            }
-            *reinterpret_cast<float4*>(o + co) = v;
-        }
-    } else {
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const int py = py0 + (s4 >> 1), px = px0 + (s4 & 1);
-            if (py >= H || px >= W) continue;
-            float* o = out + (((size_t)crop * H + py) * W + px) * CO + cb;
-#pragma unroll
-            for (int co = 0; co < 16; co += 4) {
-                float4 v;
-                float* vv = &v.x;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) vv[q] = fmaxf((acc[s4][co + q] + bias[cb + co + q]) * sv[cb + co + q] + tv[cb + co + q], 0.f);
-                *reinterpret_cast<float4*>(o + co) = v;
-            }
-        }
-    }
+    conv1_tiled<CH, T, NORM>(TiledArgs{CH, CO, T, pool, sv, tv}, crops, w, bias, out, W, H, tx_n, tiles);
 }
 
-// ------------------------------------------------------------------------------------------------
-// every further convolution: T x T 'same' on the matrix cores, 2-D tiles of 64 windows of 2 x 2 conv pixels
-// ------------------------------------------------------------------------------------------------
-constexpr int ARCH_APMAX = 36 * 12;          // patch pixels of the largest tile shape at 5 taps (4 x 16 or 16 x 4 windows); 3 taps: 34 * 10
-
-template <int KIND> struct ArchK;            // 0 = bf16 (3 pieces), 1 = fp16 (2 pieces), 2 = fp32
-template <> struct ArchK<0> { static constexpr int NP = 3; using frag = bf16x8; };
-template <> struct ArchK<1> { static constexpr int NP = 2; using frag = f16x8; };
-template <> struct ArchK<2> { static constexpr int NP = 1; using frag = float; };
-
-// per instance: LDS bytes and accumulator registers.  Input channels are staged 16 at a time in every kind.
-//   COB 128: fp32 29376 + 16384 = 45760 B, bf16 62208 + 24576 = 86784 B, fp16 41472 + 16384 = 57856 B; 4 M-tiles per wave = 64 accumulators
-//   COB  64: fp32 37568, bf16 74496, fp16 49664 B; 32 accumulators          COB 32: fp32 33472, bf16 68352, fp16 45568 B; 16 accumulators
-template <int COB, int KIND>
-struct ArchGeom {
-    static constexpr int CIC = 16;
-    static constexpr int NP = ArchK<KIND>::NP;
-    static constexpr int PSTRIDE = KIND == 2 ? (CIC + 1) * 4 : CIC * 2 + 16;      // bytes per patch pixel (fp32: odd float stride; split: odd multiple of 16)
-    static constexpr int PIECE = ARCH_APMAX * PSTRIDE;                             // bytes per piece of the patch
-    static constexpr int BT = KIND == 2 ? CIC * COB * 4 : NP * (CIC / 8) * COB * 16;   // bytes per weight tile (one tap of one chunk of one block)
-    static constexpr int BV = BT / 16;
-    static constexpr int BPT = (BV + 511) / 512;
-    static constexpr int NT = COB / 32, WM = 8 / NT, TPW = 8 / WM;                // 8 waves: NT along N, WM along M, TPW M-tiles each
-    static constexpr int ACC = TPW * 16;
-    static constexpr int LDS_BYTES = NP * PIECE + 2 * BT;
-    static_assert(COB == 32 || COB == 64 || COB == 128, "channel block");
-    static_assert(LDS_BYTES <= 160 * 1024 && ACC <= 128, "LDS / accumulators");
-};
-
-// wp: [CO/COB][CI/16][T*T] weight tiles: KIND 2 [16][COB] fp32; KIND 0 / 1 [NP][2][COB] x 16 B (pack_arch_bf16x3 / pack_arch_f16x2).
-// Grid (items, CO / COB): one workgroup per (crop, tile) and channel block; with a guard (the plan of k_arch_guard_plan) the x grid strides over
-// the tiles of the listed crops.
+// Every further convolution: conv_tiled (conv_tiled.h) with CI, CO, taps (3 or 5) and pool as arguments, COB = 32 / 64 / 128 output channels
+// per workgroup on the grid's y, input channels staged 16 at a time.  wp: pack_arch_conv / pack_arch_bf16x3 / pack_arch_f16x2.
 template <int COB, int KIND, int NTERMS>
 __global__ __launch_bounds__(512) void k_arch_conv(const float* __restrict__ in /*[N][Hi][Wi][CI]*/, const uint4* __restrict__ wp, const float* __restrict__ bias,
                                                    const float* __restrict__ sv, const float* __restrict__ tv, float* __restrict__ out /*[N][Ho][Wo][CO]*/,
                                                    const int CI, const int CO, const int Hi, const int Wi, const int taps, const int pool, const int TX,
                                                    const int tx_n, const int tiles, const float out_scale, uint32_t* __restrict__ overflow,
                                                    uint8_t* __restrict__ crop_flags, const uint32_t* __restrict__ guard, const int n_blocks) {
-    if (guard && guard[1] == 0u) return;          // re-run pass: only when the fp16 pass flagged something
-    using G = ArchGeom<COB, KIND>;
-    using frag = typename ArchK<KIND>::frag;
-    constexpr int CIC = G::CIC, Q4 = CIC / 4, KO = CIC / 8;
-    extern __shared__ __attribute__((aligned(16))) uint8_t ldsb[];
-    uint8_t* patch = ldsb;
-    uint8_t* Bs = ldsb + G::NP * G::PIECE;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int n = wave % G::NT, mg = wave / G::NT;
-    const int T2 = taps * taps, pad = taps >> 1;
-    const int TY = AW / TX, PW = 2 * TX + taps - 1, PH = 2 * TY + taps - 1;
-    const int Ho = pool ? Hi / 2 : Hi, Wo = pool ? Wi / 2 : Wi;
-    const int cob = blockIdx.y, ncc = CI / CIC;
-    const uint4* wblk = wp + (size_t)cob * ncc * T2 * G::BV;
-    int aoff[G::TPW];
-#pragma unroll
-    for (int m = 0; m < G::TPW; ++m) {
-        const int p = (mg + G::WM * m) * 32 + j;                        // window-major pixel index of the tile, < 256
-        const int wi = p >> 2, sub = p & 3;
-        const int wy = wi / TX, wx = wi - wy * TX;
-        aoff[m] = ((2 * wy + (sub >> 1)) * PW + (2 * wx + (sub & 1))) * G::PSTRIDE + (KIND == 2 ? h * 4 : h * 16);
-    }
-    const int n_eff = (guard && guard[1] == 1u) ? (int)guard[0] * tiles : n_blocks;
-    for (int blk = blockIdx.x; blk < n_eff; blk += gridDim.x) {
-        if (blk != (int)blockIdx.x) __syncthreads();                    // the previous tile's readers are done with the LDS buffers
-        const int crop = plan_crop(guard, blk / tiles), t = blk % tiles;
-        const int ty = t / tx_n, tx = t - ty * tx_n;
-        const int oy0 = ty * TY, ox0 = tx * TX;                         // first window of the tile
-        const int iy0 = 2 * oy0 - pad, ix0 = 2 * ox0 - pad;             // first input pixel of its patch
-        f32x16 acc[G::TPW];
-#pragma unroll
-        for (int m = 0; m < G::TPW; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-        const float* inc = in + (size_t)crop * Hi * Wi * CI;
-        bool ovf = false;
-        for (int cc = 0; cc < ncc; ++cc) {
-            __syncthreads();
-            for (int idx = tid; idx < PH * PW * Q4; idx += 512) {
-                const int q = idx % Q4, px = idx / Q4;
-                const int py = px / PW, pxx = px - py * PW;
-                const int iy = iy0 + py, ix = ix0 + pxx;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);             // zero padding ('same'), and the rows / columns past a ragged edge
-                if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi)
-                    v = *reinterpret_cast<const float4*>(inc + ((size_t)iy * Wi + ix) * CI + cc * CIC + q * 4);
-                if constexpr (KIND == 2) {
-                    float* d = reinterpret_cast<float*>(patch + px * G::PSTRIDE) + q * 4;
-                    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-                } else {
-                    uint32_t a1[4], a2[4], a3[4];
-                    if constexpr (KIND == 0) {
-                        split3(v.x, a1[0], a2[0], a3[0]); split3(v.y, a1[1], a2[1], a3[1]);
-                        split3(v.z, a1[2], a2[2], a3[2]); split3(v.w, a1[3], a2[3], a3[3]);
-                    } else {
-                        split2h(v.x, a1[0], a2[0], ovf); split2h(v.y, a1[1], a2[1], ovf);
-                        split2h(v.z, a1[2], a2[2], ovf); split2h(v.w, a1[3], a2[3], ovf);
-                    }
-                    uint8_t* d = patch + px * G::PSTRIDE + q * 8;
-                    *reinterpret_cast<uint2*>(d) = make_uint2(a1[0] | (a1[1] << 16), a1[2] | (a1[3] << 16));
-                    *reinterpret_cast<uint2*>(d + G::PIECE) = make_uint2(a2[0] | (a2[1] << 16), a2[2] | (a2[3] << 16));
-                    if constexpr (KIND == 0) *reinterpret_cast<uint2*>(d + 2 * G::PIECE) = make_uint2(a3[0] | (a3[1] << 16), a3[2] | (a3[3] << 16));
-                }
-            }
-            const uint4* wsrc = wblk + (size_t)cc * T2 * G::BV;
-            for (int i = tid; i < G::BV; i += 512) reinterpret_cast<uint4*>(Bs)[i] = wsrc[i];
-            __syncthreads();
-            int ky = 0, kx = 0;
-#pragma unroll 1
-            for (int tap = 0; tap < T2; ++tap) {
-                const int buf = tap & 1;
-                uint4 nb[G::BPT];
-                if (tap < T2 - 1) {
-#pragma unroll
-                    for (int u = 0; u < G::BPT; ++u) { const int i = tid + u * 512; if (i < G::BV) nb[u] = wsrc[(size_t)(tap + 1) * G::BV + i]; }
-                }
-                const uint8_t* asrc = patch + (ky * PW + kx) * G::PSTRIDE;
-                if constexpr (KIND == 2) {
-                    const float* bsrc = reinterpret_cast<const float*>(Bs + buf * G::BT) + h * COB + n * 32 + j;
-#pragma unroll
-                    for (int t2 = 0; t2 < CIC / 2; ++t2) {                // input channel 2 t2 + h of the chunk
-                        const float b = bsrc[2 * t2 * COB];
-#pragma unroll
-                        for (int m = 0; m < G::TPW; ++m) {
-                            const float a = *reinterpret_cast<const float*>(asrc + aoff[m] + 8 * t2);
-                            acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[m], 0, 0, 0);
-                        }
-                    }
-                } else {
-                    const uint8_t* bsrc = Bs + buf * G::BT + (h * COB + n * 32 + j) * 16;
-                    const frag b1 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc));
-                    const frag b2 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + KO * COB * 16));
-                    frag b3 = b1;
-                    if constexpr (G::NP == 3) b3 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(bsrc + 2 * KO * COB * 16));
-#pragma unroll
-                    for (int m = 0; m < G::TPW; ++m) {
-                        const frag p1 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(asrc + aoff[m]));
-                        const frag p2 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(asrc + aoff[m] + G::PIECE));
-                        if constexpr (KIND == 0 && NTERMS == 6) {        // smallest products first: a3b1 a2b2 a1b3 a2b1 a1b2 a1b1
-                            const frag p3 = __builtin_bit_cast(frag, *reinterpret_cast<const uint4*>(asrc + aoff[m] + 2 * G::PIECE));
-                            acc[m] = mfma16(p3, b1, acc[m]); acc[m] = mfma16(p2, b2, acc[m]); acc[m] = mfma16(p1, b3, acc[m]);
-                        }
-                        acc[m] = mfma16(p2, b1, acc[m]); acc[m] = mfma16(p1, b2, acc[m]); acc[m] = mfma16(p1, b1, acc[m]);
-                    }
-                }
-                if (tap < T2 - 1) {
-#pragma unroll
-                    for (int u = 0; u < G::BPT; ++u) { const int i = tid + u * 512; if (i < G::BV) reinterpret_cast<uint4*>(Bs + (buf ^ 1) * G::BT)[i] = nb[u]; }
-                }
-                if (++kx == taps) { kx = 0; ++ky; }
-                __syncthreads();
-            }
-        }
-        if (KIND == 1 && __any(ovf) && lane == 0) { crop_flags[crop] = 1; atomicOr(overflow, 1u); }     // the crop is known: the plan lists it
-        // epilogue: lane (j, h) holds for g = 0..3 the four pixels of window mt * 8 + 2 g + h, channel cob * COB + n * 32 + j
-        const int co = cob * COB + n * 32 + j;
-        const float bz = bias[co], sc = sv[co], sh = tv[co];
-        float* oc = out + (size_t)crop * Ho * Wo * CO;
-#pragma unroll
-        for (int m = 0; m < G::TPW; ++m) {
-            const int mt = mg + G::WM * m;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int wi = mt * 8 + 2 * g + h;
-                const int wy = wi / TX, wx = wi - wy * TX;
-                if (pool) {
-                    const int oy = oy0 + wy, ox = ox0 + wx;
-                    if (oy >= Ho || ox >= Wo) continue;                 // ragged edge of the layer
-                    const float v = fmaxf(fmaxf(acc[m][4 * g], acc[m][4 * g + 1]), fmaxf(acc[m][4 * g + 2], acc[m][4 * g + 3]));
-                    oc[((size_t)oy * Wo + ox) * CO + co] = fmaxf((v * out_scale + bz) * sc + sh, 0.f);      // out_scale undoes the weight scaling (fp16 pieces)
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int py = 2 * (oy0 + wy) + (q >> 1), px = 2 * (ox0 + wx) + (q & 1);
-                        if (py >= Hi || px >= Wi) continue;
-                        oc[((size_t)py * Wi + px) * CO + co] = fmaxf((acc[m][4 * g + q] * out_scale + bz) * sc + sh, 0.f);
-                    }
-                }
-            }
-        }
-    }
+    conv_tiled<COB, KIND, NTERMS, 16>(TiledArgs{CI, CO, taps, pool, sv, tv}, in, wp, bias, out, Hi, Wi, TX, tx_n, tiles, out_scale, overflow, crop_flags, guard,
+                                      n_blocks);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -469,38 +207,18 @@ __global__ __launch_bounds__(256) void k_cat_label(const float* __restrict__ log
     if (lane == 0) labels[crop] = at;
 }
 
-// the plan of a chunk's guarded re-run: the protocol of k_guard_plan (cnn.hip) -- lists the flagged crops, clears their flags and the range word --
-// and adds what it planned to the call's two statistics words
+// the plan of a chunk's guarded re-run (guard_plan, conv_tiled.h): lists the flagged crops, clears their flags and the range word, and adds what
+// it planned to the call's two statistics words
 __global__ __launch_bounds__(1024) void k_arch_guard_plan(uint32_t* __restrict__ overflow, uint8_t* __restrict__ flags, const int n, uint32_t* __restrict__ plan,
                                                           uint32_t* __restrict__ stats) {
     __shared__ uint32_t cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    const uint32_t raised = overflow[0];
-    if (raised == 0u) {
-        for (int i = threadIdx.x; i < n; i += 1024) if (flags[i]) flags[i] = 0;
-        if (threadIdx.x == 0) { plan[0] = 0; plan[1] = 0; }
-        return;
-    }
-    for (int i = threadIdx.x; i < n; i += 1024)
-        if (flags[i]) {
-            flags[i] = 0;
-            const uint32_t k = atomicAdd(&cnt, 1u);
-            if (k < (uint32_t)FB_MAX) plan[2 + k] = (uint32_t)i;
-        }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const bool whole = cnt == 0u || cnt > (uint32_t)FB_MAX;
-        plan[0] = whole ? 0u : cnt; plan[1] = whole ? 2u : 1u;
-        if (whole) stats[1] = 1u; else stats[0] += cnt;
-        overflow[0] = 0u;
-    }
+    guard_plan<1024>(overflow, flags, n, plan, cnt, stats);
 }
 
 // ---- the instances, each stated once ----
 using ArchKern = decltype(Kern(k_arch_conv<128, 2, 1>, 512));
 template <int COB, int KIND, int NTERMS>
-ArchKern arch_kern() { return Kern(k_arch_conv<COB, KIND, NTERMS>, 512, ArchGeom<COB, KIND>::LDS_BYTES); }
+ArchKern arch_kern() { return Kern(k_arch_conv<COB, KIND, NTERMS>, 512, TileGeom<COB, KIND, 16>::LDS_BYTES); }
 struct ArchConvSet { ArchKern by_mode[4]; };     // indexed by TREXHIP_CNN_*: FP32, BF16X6, BF16X3, FP16X3
 template <int COB>
 ArchConvSet arch_set() { return {{arch_kern<COB, 2, 1>(), arch_kern<COB, 0, 6>(), arch_kern<COB, 0, 3>(), arch_kern<COB, 1, 3>()}}; }

@@ -56,7 +56,6 @@ inline int arch_cob(const int CO) { return CO >= 128 ? 128 : CO; }
 // -- and with it nothing a crop's row could depend on -- is a pure function of (version, W, H, CH)
 static constexpr size_t ARCH_ACT_BUDGET = (size_t)2 << 30;
 static constexpr int ARCH_CHUNK_MAX = 1 << 16;     // small crops: bounds the grids (chunk * tiles) far below 2^31
-static constexpr int ARCH_C1T = 16;                // first layer: 16 x 16 windows of 2 x 2 conv pixels per workgroup, one window per thread
 
 struct ArchLayerPlan {
     int CI, CO;               // padded channels in / out (layer 0: CI = CH)
@@ -101,7 +100,7 @@ inline ArchPlan arch_plan_of(const ArchSpec* s, const int W, const int H, const 
         const bool p2 = c.pool == 2;
         l.Ho = p2 ? h / 2 : h; l.Wo = p2 ? w / 2 : w;
         const int wy = p2 ? l.Ho : (h + 1) / 2, wx = p2 ? l.Wo : (w + 1) / 2;
-        if (i == 0) { const int tx = (wx + ARCH_C1T - 1) / ARCH_C1T; l.tl = {ARCH_C1T, tx, ((wy + ARCH_C1T - 1) / ARCH_C1T) * tx}; }
+        if (i == 0) { const int tx = (wx + C1T - 1) / C1T; l.tl = {C1T, tx, ((wy + C1T - 1) / C1T) * tx}; }
         else l.tl = any_tiles(wy, wx);
         l.H3 = c.pool == 3 ? l.Ho / 3 : l.Ho; l.W3 = c.pool == 3 ? l.Wo / 3 : l.Wo;
         l.act_floats = (size_t)l.Ho * l.Wo * l.CO;

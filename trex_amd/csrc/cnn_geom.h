@@ -109,10 +109,10 @@ struct W2bGeom {
     static_assert(2 * (LDS_BYTES + 64) <= 160 * 1024, "two workgroups per CU");
 };
 
-// the any-size chain (cnn_any.hip)
-constexpr int C1T = 16;                      // conv1: pooled outputs per tile side, one per thread
-constexpr int AW = 64;                       // conv2 / conv3: pool windows per tile = 8 M-tiles of 32 conv pixels
-// the tile shape (TX windows wide, 64 / TX high) with the fewest tiles over a pooled output of Ho x Wo; 8 x 8 on a tie
+// the tiled convolutions (conv_tiled.h) of the any-size chain (cnn_any.hip) and of the other identity networks (cnn_arch.hip)
+constexpr int C1T = 16;                      // first layer: 16 x 16 windows of 2 x 2 conv pixels per workgroup, one window per thread
+constexpr int AW = 64;                       // every further layer: windows per tile = 8 M-tiles of 32 conv pixels
+// the tile shape (TX windows wide, 64 / TX high) with the fewest tiles over Ho x Wo windows (the pooled output where the layer pools); 8 x 8 on a tie
 struct AnyTiles { int TX, tx_n, tiles; };
 inline AnyTiles any_tiles(const int Ho, const int Wo) {
     AnyTiles best{8, (Wo + 7) / 8, ((Ho + 7) / 8) * ((Wo + 7) / 8)};

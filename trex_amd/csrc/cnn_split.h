@@ -1,5 +1,5 @@
 // cnn_split.h -- the operand splits of the identity network's matrix-core convolutions, shared by the 80x80 chain (cnn.hip and its
-// headers) and the any-size chain (cnn_any.hip): one definition, so the two chains split an operand into the same bits.
+// headers) and the tiled convolutions of every other chain (conv_tiled.h): one definition, so the chains split an operand into the same bits.
 //
 // Every fp32 operand is split into three bf16 pieces x = x1 + x2 + x3 (x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2); 24
 // mantissa bits in total) and a product a*w is formed from the six piece products whose order is >= 2^-16
@@ -42,7 +42,7 @@ __device__ __forceinline__ void split2h(float x, uint32_t& p1, uint32_t& p2, boo
 __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-// the re-run plan of k_guard_plan (cnn.hip): plan[1] == 1 -> item i is crop plan[2 + i]
+// the re-run plan of guard_plan (conv_tiled.h): plan[1] == 1 -> item i is crop plan[2 + i]
 __device__ __forceinline__ int plan_crop(const uint32_t* __restrict__ plan, const int i) { return (plan && plan[1] == 1u) ? (int)plan[2 + i] : i; }
 
 }  // namespace trexhip
