@@ -23,9 +23,12 @@
 // supplies V118_3's chain: begin_step (the fork, the masks), forward, backward.  Each of the three blocks is one `Layer` -- shape, tensor ids,
 // buffers, and the kernel instances of the trainer's precision bound to their LDS sizes -- filled once in v118_trainer_create; the forward
 // pass, block_backward and trainer_attrs walk that table.
-// The kernels of this file are the 80x80 chain.  A blob of any other individual_image_size (8..256 each way) trains on the chain of
-// train_any.hip (exact fp32, geometry in train_geom.h): the same walk, with `Trainer::any` choosing the launch at every size-dependent
-// kernel; the head, Adam, the masks, the target check, the loss and the reductions are shared.
+// The convolutions of this file -- conv1 with its fused column sums, conv2 / conv3 in their three roles, conv1's weight gradient -- are the
+// 80x80 chain's: tilings, a summation order and the fp16 two-piece path of their own.  A blob of any other individual_image_size (8..256 each
+// way) trains on the convolutions of train_any.hip (exact fp32, geometry in train_geom.h): the same walk, with `Trainer::any` choosing the
+// launch where the algorithm differs -- those convolutions, the head's plane count, the partial-buffer sizes.  What merely follows the plane's
+// size -- BN + ReLU + pool + dropout and its way back, fc1 and its two gradients -- is train_any.hip's k_tany_ kernels at every size, 80x80
+// included; the head, Adam, the masks, the target check, the loss and the reductions do not depend on the size.
 // A v100, v110 or category ('TRXC') blob gives a ChainTrainer (train_arch.hip) instead: trexhip_trainer_create (train_host.hip) chooses by the
 // blob, and that chain and the core launch this file's size-independent kernels through the t_* functions declared in train_host.h.
 #include "internal.h"
@@ -199,174 +202,9 @@ __global__ void k_t_bn_from_running(const float* __restrict__ run_mean, const fl
 }
 
 // ------------------------------------------------------------------------------------------------
-// BN (batch statistics) + ReLU + 2x2 max-pool + channel dropout: z [n][S][S][C] -> a [n][S/2][S/2][C]
+// The head.  (BN + ReLU + pool + dropout with its way back, and fc1 with its two gradients, follow the plane's size: they are train_any.hip's
+// k_tany_ kernels at every size, 80x80 included)
 // ------------------------------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ void load_window(const float* __restrict__ z, int S, int crop, int py, int px, int c4, float4 v[4]) {
-    const float* base = z + (((size_t)crop * S + 2 * py) * S + 2 * px) * C + c4 * 4;
-    v[0] = *reinterpret_cast<const float4*>(base);
-    v[1] = *reinterpret_cast<const float4*>(base + C);
-    v[2] = *reinterpret_cast<const float4*>(base + (size_t)S * C);
-    v[3] = *reinterpret_cast<const float4*>(base + (size_t)S * C + C);
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void k_t_bn_pool(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                   const float* __restrict__ g, const float* __restrict__ be, const uint8_t* __restrict__ keep /*[n][C]*/,
-                                                   float scale, float* __restrict__ a, int n, int S) {
-    const int H = S / 2;
-    const size_t total = (size_t)n * H * H * (C / 4);
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int c4 = idx % (C / 4);
-    const size_t pos = idx / (C / 4);
-    const int px = pos % H, py = (pos / H) % H, crop = pos / ((size_t)H * H);
-    float4 v[4];
-    load_window<C>(z, S, crop, py, px, c4, v);
-    float4 out;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = c4 * 4 + k;
-        const float alpha = invstd[c] * g[c], beta = be[c] - mean[c] * alpha;
-        float m = f4get(v[0], k) * alpha + beta;
-#pragma unroll
-        for (int q = 1; q < 4; ++q) m = fmaxf(m, f4get(v[q], k) * alpha + beta);
-        m = fmaxf(m, 0.f);
-        f4set(out, k, keep[(size_t)crop * C + c] ? m * scale : 0.f);
-    }
-    *reinterpret_cast<float4*>(a + pos * C + c4 * 4) = out;
-}
-
-// sums of dy and dy * x-hat over (n, y, x) per channel (BN backward), from the pooled gradient: partial[block][2][C] (FIN_BN_BWD)
-template <int C>
-__global__ __launch_bounds__(256) void k_t_pool_bwd_stats(const float* __restrict__ da, const float* __restrict__ z, const float* __restrict__ mean,
-                                                          const float* __restrict__ invstd, const float* __restrict__ g, const float* __restrict__ be,
-                                                          const uint8_t* __restrict__ keep, float scale, int n, int S, double* __restrict__ partial) {
-    constexpr int LC = C / 4, RL = 256 / LC;
-    __shared__ double sh[RL * C];
-    const int tid = threadIdx.x, cl = tid % LC, rl = tid / LC;
-    const int H = S / 2;
-    const size_t rows = (size_t)n * H * H;
-    float mn[4], iv[4], al[4], bt[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = cl * 4 + k;
-        mn[k] = mean[c]; iv[k] = invstd[c]; al[k] = iv[k] * g[c]; bt[k] = be[c] - mn[k] * al[k];
-    }
-    double a[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    for (size_t r = (size_t)blockIdx.x * RL + rl; r < rows; r += (size_t)gridDim.x * RL) {
-        const int px = r % H, py = (r / H) % H, crop = r / ((size_t)H * H);
-        float4 v[4];
-        load_window<C>(z, S, crop, py, px, cl, v);
-        const float4 d = *reinterpret_cast<const float4*>(da + r * C + cl * 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float zq[4] = {f4get(v[0], k), f4get(v[1], k), f4get(v[2], k), f4get(v[3], k)};
-            int arg; float xh;
-            const float gy = pooled_grad(zq, mn[k], iv[k], al[k], bt[k], f4get(d, k), keep[(size_t)crop * C + cl * 4 + k] != 0, scale, &arg, &xh);
-            a[0][k] += gy; a[1][k] += (double)gy * xh;
-        }
-    }
-    block_columns<C, 2>(a, sh, partial);
-}
-
-// dz = gamma * invstd * (dy - mean(dy) - x-hat * mean(dy x-hat)), written over z (dy is non-zero at the pool's arg-max only); the column sums
-// of what was written are the convolution bias's gradient (rounding noise around 0: the bias feeds a BatchNorm): partial[block][1][C]
-// (FIN_BIAS).  A thread's elements lie a grid-stride apart (a multiple of C / 4: it stays on its four channels)
-template <int C>
-__global__ __launch_bounds__(256) void k_t_bn_bwd(const float* __restrict__ da, float* __restrict__ z, const float* __restrict__ mean,
-                                                  const float* __restrict__ invstd, const float* __restrict__ g, const float* __restrict__ be,
-                                                  const uint8_t* __restrict__ keep, float scale, const float* __restrict__ sums, float inv_count, int n, int S,
-                                                  double* __restrict__ partial) {
-    constexpr int LC = C / 4, RL = 256 / LC;
-    __shared__ double sh[RL * C];
-    const int H = S / 2;
-    const size_t total = (size_t)n * H * H * LC;
-    const int c4 = threadIdx.x % LC;
-    float mn[4], iv[4], al[4], bt[4], m1[4], m2[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = c4 * 4 + k;
-        mn[k] = mean[c]; iv[k] = invstd[c]; al[k] = iv[k] * g[c]; bt[k] = be[c] - mn[k] * al[k];
-        m1[k] = sums[c] * inv_count; m2[k] = sums[C + c] * inv_count;
-    }
-    double a[1][4] = {{0, 0, 0, 0}};
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const size_t pos = idx / LC;
-        const int px = pos % H, py = (pos / H) % H, crop = pos / ((size_t)H * H);
-        float4 v[4];
-        load_window<C>(z, S, crop, py, px, c4, v);
-        const float4 d = *reinterpret_cast<const float4*>(da + pos * C + c4 * 4);
-        float4 o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float zq[4] = {f4get(v[0], k), f4get(v[1], k), f4get(v[2], k), f4get(v[3], k)};
-            int arg; float xh;
-            const float gy = pooled_grad(zq, mn[k], iv[k], al[k], bt[k], f4get(d, k), keep[(size_t)crop * C + c4 * 4 + k] != 0, scale, &arg, &xh);
-            float w = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float xhat = (zq[q] - mn[k]) * iv[k];
-                const float dz = al[k] * ((q == arg ? gy : 0.f) - m1[k] - xhat * m2[k]);
-                f4set(o[q], k, dz);
-                w += dz;
-            }
-            a[0][k] += w;
-        }
-        float* base = z + (((size_t)crop * S + 2 * py) * S + 2 * px) * C + c4 * 4;
-        *reinterpret_cast<float4*>(base) = o[0];
-        *reinterpret_cast<float4*>(base + C) = o[1];
-        *reinterpret_cast<float4*>(base + (size_t)S * C) = o[2];
-        *reinterpret_cast<float4*>(base + (size_t)S * C + C) = o[3];
-    }
-    block_columns<C, 1>(a, sh, partial);
-}
-
-// ------------------------------------------------------------------------------------------------
-// fc1: h[n][100] = a3[n][hw][c] . W1c[hw][c][o], as 100 partial planes (one per hw) summed in fixed order by the head kernel.
-// Block = one position x 64 samples on fp32 MFMA (32x32x2: one step contracts two channels); wave = 32 outputs (the last wave: 4), two sample
-// tiles.  (The VALU form -- 8 x 4 outputs per thread, 12 LDS reads per 32 multiply-adds, one wave per SIMD -- took 30 us.)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_t_fc1(const float* __restrict__ a3 /*[n][100][128]*/, const float* __restrict__ w /*[100][128][100]*/,
-                                               float* __restrict__ hpart /*[100][n][100]*/, int n) {
-    __shared__ float As[64 * 129];                                    // [sample][channel], pitch 129: the 32 rows of a fragment on 32 banks
-    __shared__ __attribute__((aligned(16))) float Ws[128 * 100];      // [channel][output]
-    const int tid = threadIdx.x, hw = blockIdx.x, n0 = blockIdx.y * 64;
-    for (int idx = tid; idx < 64 * 32; idx += 256) {
-        const int i = idx >> 5, q = idx & 31;
-        const float4 v = (n0 + i < n) ? *reinterpret_cast<const float4*>(a3 + ((size_t)(n0 + i) * 100 + hw) * 128 + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float* d = As + i * 129 + q * 4;
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    {
-        const float4* src = reinterpret_cast<const float4*>(w + (size_t)hw * 12800);
-        for (int idx = tid; idx < 3200; idx += 256) reinterpret_cast<float4*>(Ws)[idx] = src[idx];
-    }
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6, j = lane & 31, h = lane >> 5;
-    const int o = wave * 32 + j;
-    const bool ov = o < 100;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-    const float* a0 = As + j * 129 + h;
-    const float* a1 = As + (32 + j) * 129 + h;
-    const float* bp = Ws + h * 100 + (ov ? o : 0);
-#pragma unroll 8
-    for (int t = 0; t < 64; ++t) {
-        const float bv = ov ? bp[2 * t * 100] : 0.f;
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[2 * t], bv, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[2 * t], bv, acc1, 0, 0, 0);
-    }
-    if (!ov) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * h;                 // accumulator r of lane (j, h) is row 8 (r / 4) + 4 h + r % 4
-        if (n0 + i < n) hpart[((size_t)hw * n + n0 + i) * 100 + o] = acc0[r];
-        if (n0 + 32 + i < n) hpart[((size_t)hw * n + n0 + 32 + i) * 100 + o] = acc1[r];
-    }
-}
-
 // block reduction of one float over 128 threads, fixed order
 __device__ __forceinline__ float block_sum128(float v, float* red) {
     const int tid = threadIdx.x;
@@ -553,66 +391,6 @@ __global__ __launch_bounds__(256) void k_t_head_grads(const float* __restrict__ 
         else { HG_SUM(dh[(size_t)s * 100 + j], 1.f) g_b1[j] = acc; }
     }
 #undef HG_SUM
-}
-
-// fc1 weight gradient: dW1c[hw][c][o] = sum_n a3[n][hw][c] * dh[n][o] -- per spatial position a 128 x 100 matrix = A^T D with the batch as
-// the contraction: fp32 MFMA, one 32x32x2 step contracts two samples; block = one position, wave = 32 channels x all outputs (4 tiles,
-// the last one 4 columns wide); samples in order, so the same bits every run
-__global__ __launch_bounds__(256) void k_t_fc1_wgrad(const float* __restrict__ a3, const float* __restrict__ dh, float* __restrict__ gw, int n) {
-    const int tid = threadIdx.x, lane = tid & 63, mt = tid >> 6, j = lane & 31, h = lane >> 5, hw = blockIdx.x;
-    f32x16 acc[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-    const float* ap = a3 + (size_t)hw * 128 + mt * 32 + j;
-    const bool last_ok = 96 + j < 100;
-    for (int s0 = 0; s0 < n; s0 += 2) {
-        const int s = s0 + h;
-        const bool ok = s < n;
-        const float av = ok ? ap[(size_t)s * 12800] : 0.f;
-        float bv[4];
-#pragma unroll
-        for (int nt = 0; nt < 3; ++nt) bv[nt] = ok ? dh[(size_t)s * 100 + nt * 32 + j] : 0.f;
-        bv[3] = (ok && last_ok) ? dh[(size_t)s * 100 + 96 + j] : 0.f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[nt], acc[nt], 0, 0, 0);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int o = nt * 32 + j;
-        if (o >= 100) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = mt * 32 + 8 * (r / 4) + 4 * h + (r % 4);         // accumulator r of lane (j, h) is row 8 (r / 4) + 4 h + r % 4
-            gw[((size_t)hw * 128 + c) * 100 + o] = acc[nt][r];
-        }
-    }
-}
-
-// fc1 data gradient: da3[n][hw][c] = sum_o dh[n][o] * W1c[hw][c][o].  Block = one position x 32 samples on fp32 MFMA (one step contracts two
-// outputs), wave = 32 channels
-__global__ __launch_bounds__(256) void k_t_fc1_dgrad(const float* __restrict__ dh, const float* __restrict__ w, float* __restrict__ da3, int n) {
-    __shared__ float Ws[128 * 101];                                   // [channel][output], pitch 101: a fragment's 32 channels on 32 banks
-    __shared__ float Ds[32 * 101];                                    // [sample][output]
-    const int tid = threadIdx.x, hw = blockIdx.x, n0 = blockIdx.y * 32;
-    for (int idx = tid; idx < 128 * 100; idx += 256) Ws[(idx / 100) * 101 + idx % 100] = w[(size_t)hw * 12800 + idx];
-    for (int idx = tid; idx < 32 * 100; idx += 256) Ds[(idx / 100) * 101 + idx % 100] = (n0 + idx / 100) < n ? dh[(size_t)n0 * 100 + idx] : 0.f;
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6, j = lane & 31, h = lane >> 5;
-    const int c = wave * 32 + j;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const float* ap = Ds + j * 101 + h;
-    const float* bp = Ws + c * 101 + h;
-#pragma unroll 10
-    for (int t = 0; t < 50; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * t], bp[2 * t], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int nn = n0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (nn < n) da3[((size_t)nn * 100 + hw) * 128 + c] = acc[r];
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1385,16 +1163,12 @@ static WgradKernel wgrad_h2(int max_shares) { using G = WgradHGeom<CI, CO, S, CI
 
 // One convolution block [conv5x5 -> BatchNorm2d -> ReLU -> MaxPool2 -> Dropout2d], stated once (trexhip_trainer_create fills the three)
 struct Layer {
-    int C, CI, S;                          // output / input channels, input side: z [n][S][S][C], a and da [n][S/2][S/2][C]
+    int C, CI;                             // output / input channels
+    int ph, pw;                            // its plane: z [n][ph][pw][C], a and da [n][ph/2][pw/2][C] (the level's (h, w) of TrainAnyGeom: 80, 40, 20 at 80x80)
     int w, b, g, be, rm, rv;               // tensor ids: weight, bias, gamma, beta, running mean, running variance
     int dz_event;                          // recorded when its dz is complete
     int slot;                              // its statistics: stat + slot * 512 (mean, invstd, sums[2] x 128), red_bias + slot * BWD_BLOCKS * 128
     int keep_off;                          // its keep masks inside the mask row
-    // the BN kernels at its channel count
-    decltype(&k_t_bn_stats<64>) bn_stats;
-    decltype(&k_t_bn_pool<64>) bn_pool;
-    decltype(&k_t_pool_bwd_stats<64>) pool_bwd_stats;
-    decltype(&k_t_bn_bwd<64>) bn_bwd;
     float *z = nullptr, *a = nullptr, *da = nullptr;
     // blocks 2 and 3: the three roles of its convolution at the trainer's precision, and the weight images they read
     ConvKernel fwd, dgrad;
@@ -1403,7 +1177,6 @@ struct Layer {
     uint4 *wh_f = nullptr, *wh_b = nullptr;   // precision 0: fp16 two-piece operand images (forward, data gradient) and their scale
     float* wh_scale = nullptr;
     float* wb = nullptr;                   // precision 1: flipped + transposed weights of the data gradient
-    int ph = 0, pw = 0;                    // the plane of z as the size-following code reads it: S x S at 80x80, the level's (h, w) of TrainAnyGeom elsewhere
 };
 
 // The streams of a step: main = the context's, w = the side stream (main itself when the step does not fork), es = main as events name it.
@@ -1413,9 +1186,9 @@ struct Layer {
 struct Streams { hipStream_t s, w, es; bool forked; };
 
 struct Trainer : TrainerCore {
-    bool any = false;                    // not 80x80: the chain of train_any.hip on the geometry below (exact fp32 whatever `precision` says)
-    TrainAnyGeom geom{};
-    float* hsum = nullptr;               // any: fc1's partial planes added up (k_tany_fc1_sum), what the head reads as its one plane
+    bool any = false;                    // not 80x80: the convolutions of train_any.hip (exact fp32 whatever `precision` says)
+    TrainAnyGeom geom{};                 // the planes and fc1's positions at every size; the convolutions' tiles and grids where `any`
+    float* hsum = nullptr;               // any: fc1's partial planes added up (k_tany_fc1_sum), what the head reads as its one plane; 80x80: none, the head adds them
     Layer L[3] = {};
     decltype(&k_t_conv1<1>) conv1 = nullptr;      // block 1's convolution and weight gradient (no MFMA) at the trainer's 1 or 3 input channels
     decltype(&k_t_wgrad1<1>) wgrad1 = nullptr;
@@ -1429,7 +1202,7 @@ struct Trainer : TrainerCore {
     hipEvent_t ev[EV_COUNT] = {};
     Streams q{};                         // the streams of the step being queued (begin_step)
     bool masks_on_side = false;          // this step's keep masks are being drawn on `side` (EV_MASKS)
-    double* red_bias = nullptr;          // [3][BWD_BLOCKS][128]: k_t_bn_bwd's column sums, finalized on `side`
+    double* red_bias = nullptr;          // [3][BWD_BLOCKS][128]: k_tany_bn_bwd's column sums, finalized on `side`
 
     ~Trainer() override {
         if (side) (void)hipStreamSynchronize(side);                       // (a step joins its side stream before Adam; this is for a half-queued one)
@@ -1462,19 +1235,16 @@ static void bn_forward(Trainer* t, hipStream_t s, const Layer& L, int n, const u
     float* invstd = mean + 128;
     if (train) {
         const size_t rows = (size_t)n * L.ph * L.pw;                  // every pixel counts in the statistics, the odd last row / column too
-        if (!partials) hipLaunchKernelGGL(L.bn_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.z, rows, t->red);
+        if (!partials) t_bn_stats(s, L.C, L.z, rows, t->red);
         hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_STATS>), dim3(L.C), dim3(256), 0, s, t->red, partials ? partials : RED_BLOCKS, L.C,
                            FinArgs{(double)rows, t->p.bn_momentum, mean, invstd, P + o[L.rm], P + o[L.rv], t->bad_target});
     } else {
         hipLaunchKernelGGL(k_t_bn_from_running, dim3(1), dim3(128), 0, s, P + o[L.rm], P + o[L.rv], L.C, mean, invstd);
     }
-    if (t->any) { tany_bn_pool(s, L.C, L.z, mean, invstd, P + o[L.g], P + o[L.be], keep + (size_t)n * L.keep_off, scale, L.a, n, L.ph, L.pw); return; }
-    const size_t total = (size_t)n * (L.S / 2) * (L.S / 2) * (L.C / 4);
-    hipLaunchKernelGGL(L.bn_pool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L.z, mean, invstd, P + o[L.g], P + o[L.be], keep + (size_t)n * L.keep_off,
-                       scale, L.a, n, L.S);
+    tany_bn_pool(s, L.C, L.z, mean, invstd, P + o[L.g], P + o[L.be], keep + (size_t)n * L.keep_off, scale, L.a, n, L.ph, L.pw);
 }
 
-// da (pooled gradient) -> dz written over z; gradients of gamma and beta.  Returns the grid of k_t_bn_bwd, whose column sums bias_finalize adds
+// da (pooled gradient) -> dz written over z; gradients of gamma and beta.  Returns the grid of k_tany_bn_bwd, whose column sums bias_finalize adds
 static int bn_backward(Trainer* t, hipStream_t s, const Layer& L, int n, const uint8_t* keep, float scale) {
     float* P = t->P;
     const size_t* o = t->tt.off;
@@ -1482,22 +1252,14 @@ static int bn_backward(Trainer* t, hipStream_t s, const Layer& L, int n, const u
     float* invstd = mean + 128;
     float* sums = mean + 256;
     const uint8_t* kp = keep + (size_t)n * L.keep_off;
-    if (t->any) tany_pool_bwd_stats(s, L.C, RED_BLOCKS, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.ph, L.pw, t->red);
-    else hipLaunchKernelGGL(L.pool_bwd_stats, dim3(RED_BLOCKS), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.S, t->red);
+    tany_pool_bwd_stats(s, L.C, RED_BLOCKS, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, n, L.ph, L.pw, t->red);
     hipLaunchKernelGGL((k_t_red_finalize<FIN_BN_BWD>), dim3(L.C), dim3(256), 0, s, t->red, RED_BLOCKS, L.C,
                        FinArgs{0.0, 0.f, sums, t->G + o[L.g], t->G + o[L.be], nullptr, nullptr});
     const float inv_count = (float)(1.0 / ((double)n * L.ph * L.pw));      // the means run over every pixel of the plane
-    if (t->any)
-        return tany_bn_bwd(s, L.C, BWD_BLOCKS, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, sums, inv_count, n, L.ph, L.pw,
-                           t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128);
-    const size_t total = (size_t)n * (L.S / 2) * (L.S / 2) * (L.C / 4);
-    // whole rounds: every workgroup takes the same number of elements, all of them resident at once
-    const unsigned nb0 = (unsigned)((total + 255) / 256), per = (nb0 + BWD_BLOCKS - 1) / BWD_BLOCKS, nb = (nb0 + per - 1) / per;
-    hipLaunchKernelGGL(L.bn_bwd, dim3(nb), dim3(256), 0, s, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, sums, inv_count, n, L.S,
+    return tany_bn_bwd(s, L.C, BWD_BLOCKS, L.da, L.z, mean, invstd, P + o[L.g], P + o[L.be], kp, scale, sums, inv_count, n, L.ph, L.pw,
                        t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128);
-    return (int)nb;
 }
-// the convolution bias's gradient from k_t_bn_bwd's column sums (nothing but Adam waits for it: the caller puts it on the side stream)
+// the convolution bias's gradient from k_tany_bn_bwd's column sums (nothing but Adam waits for it: the caller puts it on the side stream)
 static void bias_finalize(Trainer* t, hipStream_t w, const Layer& L, int nb) {
     hipLaunchKernelGGL((k_t_red_finalize<FIN_BIAS>), dim3(L.C), dim3(256), 0, w, t->red_bias + (size_t)L.slot * BWD_BLOCKS * 128, nb, L.C,
                        FinArgs{0.0, 0.f, t->G + t->tt.off[L.b], nullptr, nullptr, nullptr, nullptr});
@@ -1567,8 +1329,7 @@ void Trainer::forward(hipStream_t s, const float* x, const int32_t* targets, int
         else hipLaunchKernelGGL(k.f32, dim3(n * k.bpc), dim3(512), k.lds, s, L[i - 1].a, P + o[L[i].w], P + o[L[i].b], L[i].z);
         bn_forward(t, s, L[i], n, keep, scale, train, k.h2 ? n * k.bpc : 0);
     }
-    if (t->any) tany_fc1(s, t->geom, n, L[2].a, P + o[T_F1W], t->hpart, t->hsum);
-    else hipLaunchKernelGGL(k_t_fc1, dim3(FC1_POS, (n + 63) / 64), dim3(256), 0, s, L[2].a, P + o[T_F1W], t->hpart, n);
+    tany_fc1(s, t->geom, n, L[2].a, P + o[T_F1W], t->hpart, t->hsum);         // (80x80: no hsum and no launch for it -- the head adds the 100 planes)
     const float* planes = t->any ? t->hsum : t->hpart;
     if (probs) {
         hipLaunchKernelGGL(t->any ? &k_t_head_eval<1> : &k_t_head_eval<FC1_POS>, dim3(n), dim3(128), 0, s, planes, n, P + o[T_F1B], P + o[T_LNG], P + o[T_LNB], P + o[T_F2W], P + o[T_F2B], t->classes, probs);
@@ -1605,11 +1366,9 @@ void Trainer::backward(hipStream_t s, const float* x, int n, const uint8_t* keep
         hipLaunchKernelGGL(k_t_head_grads, dim3((cnt + 255) / 256), dim3(256), 0, w, t->dl, t->hd, t->dy, t->xhat, t->dh, n, t->classes, G + o[T_F2W], G + o[T_F2B],
                            G + o[T_LNG], G + o[T_LNB], G + o[T_F1B]);
     }
-    if (t->any) tany_fc1_wgrad(w, t->geom, n, t->L[2].a, t->dh, G + o[T_F1W]);
-    else hipLaunchKernelGGL(k_t_fc1_wgrad, dim3(FC1_POS), dim3(256), 0, w, t->L[2].a, t->dh, G + o[T_F1W], n);
+    tany_fc1_wgrad(w, t->geom, n, t->L[2].a, t->dh, G + o[T_F1W]);
     hipLaunchKernelGGL(k_t_loss, dim3(1), dim3(64), 0, w, t->loss, t->correct, n, t->out2);
-    if (t->any) tany_fc1_dgrad(s, t->geom, n, t->dh, P + o[T_F1W], t->L[2].da);
-    else hipLaunchKernelGGL(k_t_fc1_dgrad, dim3(FC1_POS, (n + 31) / 32), dim3(256), 0, s, t->dh, P + o[T_F1W], t->L[2].da, n);
+    tany_fc1_dgrad(s, t->geom, n, t->dh, P + o[T_F1W], t->L[2].da);
     for (int i = 2; i >= 0; --i) block_backward(t, q, t->L[i], n, keep, scale);
     if (forked) (void)hipEventRecord(t->ev[EV_SIDE_DONE], w);               // the side stream's last piece of this step
     if (t->any) tany_wgrad1(s, t->geom, n, x, t->L[0].z, t->part1);
@@ -1688,17 +1447,14 @@ int v118_trainer_create(trexhip_ctx* ctx, const void* blob, size_t bytes, const 
     // ---- the three blocks and their kernel instances.  The convolutions' precision is chosen here, once per role
     const bool h2 = p->precision == 0 && !t->any;      // every other size runs the exact-fp32 chain at both precisions
     Layer* L = t->L;
-    // (k_t_bn_stats<16> is never launched by this chain: conv1 always leaves its column sums.  It stays instantiated because the compiler lays out the epilogue
-    // of k_t_pool_bwd_stats<16>, which shares block_columns<16, 2> with it, in another order without it)
-    //      C    CI  S        weight bias   gamma beta   running mean / variance  dz event  slot  masks    BN kernels
-    L[0] = {16,  CH, IMG,     T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, (int)t->tt.keep_off[0], &k_t_bn_stats<16>, &k_t_bn_pool<16>, &k_t_pool_bwd_stats<16>, &k_t_bn_bwd<16>};
-    L[1] = {64,  16, IMG / 2, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, EV_DZ2, 1, (int)t->tt.keep_off[1], &k_t_bn_stats<64>, &k_t_bn_pool<64>, &k_t_pool_bwd_stats<64>, &k_t_bn_bwd<64>};
-    L[2] = {128, 64, IMG / 4, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3, EV_DZ3, 2, (int)t->tt.keep_off[2], &k_t_bn_stats<128>, &k_t_bn_pool<128>, &k_t_pool_bwd_stats<128>, &k_t_bn_bwd<128>};
-    for (int i = 0; i < 3; ++i) { L[i].ph = t->any ? t->geom.L[i].h : L[i].S; L[i].pw = t->any ? t->geom.L[i].w : L[i].S; }
+    const TrainAnyLayer* gl = t->geom.L;
+    //      C    CI  plane           weight bias   gamma beta   running mean / variance  dz event  slot  masks
+    L[0] = {16,  CH, gl[0].h, gl[0].w, T_C1W, T_C1B, T_G1, T_BE1, T_RM1, T_RV1, EV_DZ1, 0, (int)t->tt.keep_off[0]};
+    L[1] = {64,  16, gl[1].h, gl[1].w, T_C2W, T_C2B, T_G2, T_BE2, T_RM2, T_RV2, EV_DZ2, 1, (int)t->tt.keep_off[1]};
+    L[2] = {128, 64, gl[2].h, gl[2].w, T_C3W, T_C3B, T_G3, T_BE3, T_RM3, T_RV3, EV_DZ3, 2, (int)t->tt.keep_off[2]};
     if (t->any) {
-        // the generic chain (train_any.hip): the BN / pool kernels, the convolutions' three roles and fc1 follow t->geom; what the shared kernels
-        // (k_t_wgrad_reduce, k_t_repack_bwd) read of a convolution is its weight image: the parameter layout's chunk, the data gradient's chunk and tile
-        for (int i = 0; i < 3; ++i) L[i].S = 0;
+        // the generic convolutions (train_any.hip) follow t->geom in their three roles; what the shared kernels (k_t_wgrad_reduce, k_t_repack_bwd)
+        // read of a convolution is its weight image: the parameter layout's chunk, the data gradient's chunk and tile
         L[1].fwd.cic = 16; L[1].dgrad.cic = 16; L[1].dgrad.co = 32;        // conv2's data gradient: 16 real channels in a 32-wide tile
         L[2].fwd.cic = 32; L[2].dgrad.cic = 32; L[2].dgrad.co = 64;
     } else {

@@ -1,5 +1,5 @@
-// train_any.h -- the launches of the training chain at any individual_image_size but 80x80 (train_any.hip), as train.hip's walk calls them.
-// Every grid comes from the TrainAnyGeom of the trainer (train_geom.h); everything is queued on the given stream, nothing synchronises.
+// train_any.h -- the launches of the size-following training kernels (train_any.hip), as train.hip's walk calls them: the convolutions at any
+// individual_image_size but 80x80, the BN / pool and fc1 kernels at every size.  Every grid comes from the TrainAnyGeom of the trainer (train_geom.h); everything is queued on the given stream, nothing synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +32,8 @@ void tany_pool_bwd_stats(hipStream_t s, int C, int blocks, const float* da, cons
 int tany_bn_bwd(hipStream_t s, int C, int max_blocks, const float* da, float* z, const float* mean, const float* invstd, const float* g, const float* be,
                 const uint8_t* keep, float scale, const float* sums, float inv_count, int n, int h, int w, double* partial, int creal = 0);
 
-// fc1 at P positions: hpart [P][n][100] partial planes, hsum [n][100] = their sum in position order
+// fc1 at P positions: hpart [P][n][100] partial planes, hsum [n][100] = their sum in position order (null: no sum and no launch for it -- the
+// 80x80 head adds the planes itself)
 void tany_fc1(hipStream_t s, const TrainAnyGeom& g, int n, const float* a3, const float* w, float* hpart, float* hsum);
 void tany_fc1_wgrad(hipStream_t s, const TrainAnyGeom& g, int n, const float* a3, const float* dh, float* gw);
 void tany_fc1_dgrad(hipStream_t s, const TrainAnyGeom& g, int n, const float* dh, const float* w, float* da3);

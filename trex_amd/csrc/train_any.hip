@@ -1,6 +1,7 @@
-// train_any.hip -- the training step of the identity network V118_3 at any individual_image_size but 80x80 (train.hip keeps its own
-// kernels there, as cnn.hip does beside cnn_any.hip).  W, H = 8..256 at run time, square or not, CH = 1 or 3, NHWC fp32 throughout, exact
-// fp32 arithmetic (both values of trexhip_train_params.precision).  Every pool floors like nn.MaxPool2d(2).
+// train_any.hip -- the kernels of the identity network V118_3's training step that follow the individual_image_size: W, H = 8..256 at run
+// time, square or not, CH = 1 or 3, NHWC fp32 throughout, exact fp32 arithmetic.  Every pool floors like nn.MaxPool2d(2).
+// The BN / pool and fc1 kernels run at every size, 80x80 included; the convolutions and weight gradients at every size but 80x80, where
+// train.hip keeps its own (other tilings, another summation order, the fp16 two-piece path), as cnn.hip does beside cnn_any.hip.
 //
 // The tap count of every convolution kernel is a template parameter: 5 (V118_3, v100, v110) or 3 (the category network, train_arch.hip), whose conv1
 // pair also normalises its input and whose block kernels read element-wise dropout masks.
@@ -10,8 +11,9 @@
 //                      k_any_conv (cnn_any.hip) with a raw epilogue
 //   k_tany_wgrad<>     conv2 / conv3 weight gradients on the same instruction, operands straight from L2, partials per share of the batch
 //   k_tany_wgrad1      conv1 weight gradient: k_t_wgrad1's sliding window on bands of 8 rows x strips of 64 columns
-//   k_tany_bn_pool, k_tany_pool_bwd_stats, k_tany_bn_bwd    the expressions of their k_t_ namesakes on planes of h x w pixels
-//   k_tany_fc1, _sum, _wgrad, _dgrad                        fc1 at P = (H/8)(W/8) positions
+//   k_tany_bn_pool, k_tany_pool_bwd_stats, k_tany_bn_bwd    BN + ReLU + pool + dropout and its way back on planes of h x w pixels (every size)
+//   k_tany_fc1, _wgrad, _dgrad                              fc1 at P = (H/8)(W/8) positions (every size)
+//   k_tany_fc1_sum                                          its partial planes added up (not at 80x80: the head adds the 100 itself)
 // k_t_bn_stats, k_t_red_finalize, k_t_wgrad_reduce, k_t_reduce, k_t_repack_bwd, the head, the masks and Adam are train.hip's own: they do
 // not depend on the size.
 //
@@ -326,7 +328,7 @@ __global__ __launch_bounds__(512) void k_tany_wgrad1(const float* __restrict__ x
 
 // ------------------------------------------------------------------------------------------------
 // BN (batch statistics) + ReLU + floor 2x2 max-pool + dropout (per channel, or per element: ELEM) on a plane of H x W pixels: z [n][H][W][C] -> a [n][H/2][W/2][C].
-// k_t_bn_pool's expressions; the odd last row / column is read by no window
+// The odd last row / column is read by no window
 // ------------------------------------------------------------------------------------------------
 template <int C>
 __device__ __forceinline__ void load_window_hw(const float* __restrict__ z, int H, int W, int crop, int py, int px, int c4, float4 v[4]) {
@@ -378,7 +380,7 @@ __global__ __launch_bounds__(256) void k_tany_bn_pool(const float* __restrict__ 
     *reinterpret_cast<float4*>(a + pos * C + c4 * 4) = out;
 }
 
-// sums of dy and dy * x-hat per channel (BN backward) from the pooled gradient, k_t_pool_bwd_stats's expressions: partial[block][2][C].
+// sums of dy and dy * x-hat per channel (BN backward) from the pooled gradient: partial[block][2][C] (FIN_BN_BWD).
 // dy is non-zero at the arg-max of a pool window only, so the pixels outside every window add nothing here -- they do count in the
 // 1 / (n H W) of the means (train.hip: bn_backward)
 template <int C, bool ELEM = false>
@@ -414,8 +416,8 @@ __global__ __launch_bounds__(256) void k_tany_pool_bwd_stats(const float* __rest
     block_columns<C, 2>(acc, sh, partial);
 }
 
-// dz = gamma * invstd * (dy - mean(dy) - x-hat * mean(dy x-hat)) written over z, k_t_bn_bwd's expressions; the column sums of what was written
-// are the convolution bias's gradient: partial[block][1][C].  The walk is over ceil(H/2) x ceil(W/2) windows: a window past the pooled plane
+// dz = gamma * invstd * (dy - mean(dy) - x-hat * mean(dy x-hat)) written over z (dy is non-zero at the pool's arg-max only); the column sums of what
+// was written are the convolution bias's gradient (rounding noise around 0: the bias feeds a BatchNorm): partial[block][1][C] (FIN_BIAS).  The walk is over ceil(H/2) x ceil(W/2) windows: a window past the pooled plane
 // (odd H or W) has no arg-max and no dy, but its pixels inside the image still get dz = gamma invstd (0 - mean(dy) - x-hat mean(dy x-hat)),
 // which the weight gradient, the data gradient and the bias sum below all see.  A thread's elements lie a grid-stride apart (a multiple of
 // C / 4: it stays on its four channels)
@@ -476,9 +478,10 @@ __global__ __launch_bounds__(256) void k_tany_bn_bwd(const float* __restrict__ d
 }
 
 // ------------------------------------------------------------------------------------------------
-// fc1 at P = (H/8)(W/8) positions (run time, 1..1024): k_t_fc1's, k_t_fc1_wgrad's and k_t_fc1_dgrad's MFMA walks with the position count as
-// an argument.  h[n][100] = a3[n][p][c] . W1c[p][c][o]: one partial plane per position, added in position order by k_tany_fc1_sum -- an
-// order that depends on the size and never on n
+// fc1 at P = (H/8)(W/8) positions (run time, 1..1024; 100 at 80x80).  h[n][100] = a3[n][p][c] . W1c[p][c][o]: one partial plane per position,
+// added in position order by k_tany_fc1_sum (at 80x80 by the head kernel) -- an order that depends on the size and never on n.
+// Block = one position x 64 samples on fp32 MFMA (32x32x2: one step contracts two channels); wave = 32 outputs (the last wave: 4), two sample
+// tiles.  (The VALU form -- 8 x 4 outputs per thread, 12 LDS reads per 32 multiply-adds, one wave per SIMD -- took 30 us at 80x80.)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_tany_fc1(const float* __restrict__ a3 /*[n][P][128]*/, const float* __restrict__ w /*[P][128][100]*/,
                                                   float* __restrict__ hpart /*[P][n][100]*/, int n, int P) {
@@ -679,7 +682,7 @@ int tany_bn_bwd(hipStream_t s, int C, int max_blocks, const float* da, float* z,
 
 void tany_fc1(hipStream_t s, const TrainAnyGeom& g, int n, const float* a3, const float* w, float* hpart, float* hsum) {
     hipLaunchKernelGGL(k_tany_fc1, dim3(g.P, (n + 63) / 64), dim3(256), 0, s, a3, w, hpart, n, g.P);
-    hipLaunchKernelGGL(k_tany_fc1_sum, dim3((n * TA_HID + 255) / 256), dim3(256), 0, s, hpart, n * TA_HID, g.P, hsum);
+    if (hsum) hipLaunchKernelGGL(k_tany_fc1_sum, dim3((n * TA_HID + 255) / 256), dim3(256), 0, s, hpart, n * TA_HID, g.P, hsum);
 }
 
 void tany_fc1_wgrad(hipStream_t s, const TrainAnyGeom& g, int n, const float* a3, const float* dh, float* gw) {

@@ -1,5 +1,5 @@
-// train_dev.h -- the device helpers that the 80x80 training kernels (train.hip) and the any-size ones (train_any.hip) share: the pool's
-// backward rule and the fixed-order column sums of a workgroup.  One statement of each, so that both chains use the same expressions.
+// train_dev.h -- the device helpers that the training kernels of train.hip (k_t_bn_stats) and the size-following ones (train_any.hip,
+// train_arch.hip) share: the pool's backward rule and the fixed-order column sums of a workgroup.  One statement of each.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

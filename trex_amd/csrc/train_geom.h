@@ -1,6 +1,6 @@
-// train_geom.h -- the geometry of the training chain at any individual_image_size but 80x80 (train_any.hip): the sizes of every level, the
+// train_geom.h -- the geometry of the training chain at any individual_image_size (train_any.hip): the sizes of every level, the
 // tiles and grids of the three roles of a convolution (forward, data gradient, weight gradient), fc1's positions and the buffer sizes, as one
-// pure function of (W, H, CH).  No device code and no HIP: train.hip sizes its buffers and train_any.hip its launches from it, and
+// pure function of (W, H, CH).  (At 80x80 the planes and fc1's positions are read from it; the convolutions there are train.hip's own.)  No device code and no HIP: train.hip sizes its buffers and train_any.hip its launches from it, and
 // tests/cpp/test_train_geom.cpp holds it to hand-derived numbers.
 #pragma once
 #include <stddef.h>
