@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 23
+#define TREXHIP_ABI_VERSION 24
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -579,8 +579,20 @@ int trexhip_identify_skip_stats(trexhip_ctx* ctx, uint32_t* passes, uint32_t* li
  * (value 33554432) has them copied into conv2's output first, as for the dense kernel.
  * What the last such call did (waits for the context's stream): *pairs of the batch (10 per crop), *listed of them to be computed, *passes the
  * listed form walked (0: the dense kernel ran), *bytes_filled of conv3's output copied instead; zeros before the first such call.  No reference
- * counterpart; any pointer may be NULL.  (ABI 16) */
+ * counterpart; any pointer may be NULL.  (ABI 16; since ABI 24 *passes counts by the row rule alone, six pairs to a pass, whatever windows the
+ * call below gave its crops) */
 int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled);
+
+/* Where the listed form of conv3 reads the all-zero crop's image itself, a crop whose blob reaches at most 3 of the 5 column tiles of conv3's
+ * map has its listed row pairs computed in windowed passes: ten row pairs of 3 tiles to a pass where a full-width pass holds six of 5; the 4
+ * pooled columns of such a pair outside the window are copied from the all-zero crop's output.  The crops' bytes decide, on the device, in
+ * every call (no crop has a window where the network's background leaves the fp16 range); the results are the bits of the dense kernel.  Bit 21
+ * of TREXHIP_CONV_GEOM (value 2097152) switches this off: one list of full-width passes, as before.
+ * What the last such call did (waits for the context's stream): *crops_windowed whose pairs went into windowed passes, *windowed_passes of them,
+ * and the *full_passes of six pairs the other crops took; zeros where the dense kernel ran.  trexhip_identify_skip3_stats keeps counting by the
+ * row rule alone: its *passes are the passes of six pairs that the listed pairs make, which is what ran before there were windows and under bit 21.
+ * No reference counterpart; any pointer may be NULL.  (ABI 24) */
+int trexhip_identify_skip3x_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes);
 
 /* Above 3200 one-channel 80x80 crops in TREXHIP_CNN_FP16X3, where the skipping above is on, a crop whose blob fits 8 of the 10 column tiles of
  * conv2's output takes windowed passes of the fused conv1+conv2 kernel: 8 tiles of up to 4 output row pairs of that crop alone, the rest taken

@@ -201,7 +201,7 @@ SYMBOLS = [
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
-    "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats", "trexhip_identify_skip_stats", "trexhip_identify_skip3_stats", "trexhip_identify_skipx_stats", "trexhip_identify_bgrow_stats", "trexhip_identify_fc1_stats",
+    "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats", "trexhip_identify_skip_stats", "trexhip_identify_skip3_stats", "trexhip_identify_skip3x_stats", "trexhip_identify_skipx_stats", "trexhip_identify_bgrow_stats", "trexhip_identify_fc1_stats",
     "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_trainer_version", "trexhip_trainer_keep_mask_bytes", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
@@ -294,6 +294,7 @@ def lib():
         L.trexhip_identify_skip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.trexhip_identify_skipx_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify_bgrow_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.trexhip_identify_skip3x_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify_skip3_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.trexhip_identify_fc1_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_weight_blob_bytes.argtypes = [C.c_int32, C.c_int32]
@@ -704,10 +705,17 @@ class Segmenter:
 
     def skip3_stats(self):
         """(row pairs of the batch, row pairs conv3 had to compute, passes its listed form walked -- 0: the dense kernel ran --, bytes of act3 filled
-        instead) of the last call that listed"""
+        instead) of the last call that listed; the passes are counted by the row rule alone, six pairs each: skip3x_stats says what ran"""
         a, b, c, d = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
         _check(lib().trexhip_identify_skip3_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return int(a.value), int(b.value), int(c.value), int(d.value)
+
+    def skip3x_stats(self):
+        """(crops whose listed conv3 row pairs went into windowed passes of 3 tiles, those passes, the full-width listed passes the other crops
+        took) of the last call that listed; (0, 0, 0) where the dense kernel ran"""
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().trexhip_identify_skip3x_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def fc1_stats(self):
         """(crop-plane rows of the last identify call -- 10 per crop --, rows its listed fc1 computed); (0, 0) where fc1 was not the listed form"""

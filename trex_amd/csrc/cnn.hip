@@ -1420,10 +1420,12 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->skipx_list, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         TRY(B.device_bytes(&net->skipx_rows, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         const size_t blocks3 = (N + Skip3Geom::BLOCK - 1) / Skip3Geom::BLOCK;
-        TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint2), who));
-        TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 4, who));
+        TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint4), who));
+        TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 2 * sizeof(uint32_t), who));
         TRY(B.device_bytes(&net->skip3_desc, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Geom::DESC * 4, who));
         TRY(B.device_bytes(&net->skip3_rows, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Reach::WORDS * 4, who));
+        TRY(B.device_bytes(&net->skip3x_desc, blocks3 * Skip3XGeom::BLOCK_PASSES * Skip3XGeom::DESC * 4, who));
+        TRY(B.device_bytes(&net->skip3x_rows, blocks3 * Skip3XGeom::BLOCK_PASSES * Skip3Reach::WORDS * 4, who));
         TRY(B.device_bytes(&net->fc1_list, Skip3Geom::PAIRS * N * sizeof(int), who));
     }
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
@@ -1458,8 +1460,10 @@ using GW3 = WinoGeom<64, 128, 20, 2>;
 static const Kern K_CONV3_WINO(k_conv5_wino<64, 128, 20, 2>, GW3::NTHR, GW3::LDS_BYTES);
 static const Kern K_CONV3_WPAIR(k_conv5_wpair<false>, 256, GW3::LDS_BYTES + 1024 /* slack for the last DMA instruction */);
 static const Kern K_CONV3_WPAIR_LIST(k_conv5_wpair<true>, 256, GW3::LDS_BYTES + 1024);
-static const Kern K_PAIR_COUNT(k_pair_count, SKIP3_TB);
-static const Kern K_PAIR_LIST(k_pair_list, SKIP3_TB);
+using GW3X = Wino3Pass<Skip3XGeom::TILES, Skip3XGeom::NR>;
+static const Kern K_CONV3_WPAIR_LISTX(k_conv5_wpair<true, Skip3XGeom>, 256, GW3X::LDS_BYTES + 1024);
+static const Kern K_PAIR_COUNT(k_pair_count, SKIP3_NT);
+static const Kern K_PAIR_LIST(k_pair_list, SKIP3_NT);
 static const Kern K_ACT3_FILL(k_act3_fill, 256);
 template <int CI, int CO, int S, int ROWS, int NTERMS>
 static auto split_kern() { return Kern(k_conv5_split<CI, CO, S, ROWS, NTERMS>, 512, ConvGeomB<CI, CO, S, ROWS, SPLIT_NP>::LDS_BYTES); }
@@ -1587,17 +1591,19 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
 // The role-split chain's preparation (cnn_skip_kernels.h), in front of conv1+conv2: which passes, row pairs and fc1 rows the crops need, and the
 // V3 rows of the others; every decision stays on the device.  `direct`: the listed conv3 reads background rows from the image, the fill copies
 // only where the dense form runs
-static void launch_skip_prep(const Pass& f, const bool direct) {
+static void launch_skip_prep(const Pass& f, const bool direct, const bool x3 /* conv3's listed pairs in two lists, windowed passes and full-width ones */) {
     const Net& net = f.net;
     const CnnPlan& p = f.p;
     const int n = f.n, lb = ceil_div(p.conv2.items, SKIP_LB);
     int2* cols = p.skipx ? net.skipx_cols : nullptr;      // null: no crop gets a window, one list
-    K_CROP_BANDS(f.s, ceil_div(n, 4), f.crops, n, net.skip_bands, cols);
+    K_CROP_BANDS(f.s, ceil_div(n, 4), f.crops, n, net.skip_bands, cols || x3 ? net.skipx_cols : nullptr);
     K_PASS_COUNT(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts, (int)p.bgrows);
     K_PASS_LIST(f.s, lb, net.skip_bands, cols, n, net.d_skip, net.skip_counts, net.skip_list, net.skipx_list, net.skipx_rows, (int)p.bgrows);
     if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
-        K_PAIR_COUNT(f.s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
-        K_PAIR_LIST(f.s, p.skip3_grid, net.skip_bands, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc);
+        // (skip3x: the crops with a window of conv3 tiles go into a list of their own; its column bands are the ones k_crop_bands writes for skipx)
+        const int2* cols3 = x3 ? net.skipx_cols : nullptr;
+        K_PAIR_COUNT(f.s, p.skip3_grid, net.skip_bands, cols3, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
+        K_PAIR_LIST(f.s, p.skip3_grid, net.skip_bands, cols3, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc, net.skip3x_desc);
         // the crops each plane of the listed fc1 computes: from the bands alone, so here and not between conv3 and fc1
         if (p.fc1_listed) K_FC1_LIST(f.s, Skip3Geom::PAIRS, net.skip_bands, n, net.d_skip, net.fc1_list, net.max_crops);
     }
@@ -1617,6 +1623,7 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
     // the back image lies behind the ALLOCATION's rows, whatever this call's n is
     const long long alloc_rows = (long long)net.max_crops * SkipGeom::V3_ROWS;
     const bool direct = p.v3_direct && skip3_direct_fits(alloc_rows);
+    const bool x3 = p.skip3x && direct && skip3x_direct_fits(alloc_rows);
     // (the guard words in front of the plan start at zero: the plan's writer -- the last reader of all three -- hands them back zeroed; net_forward
     // clears them itself behind a pass that was not queued to its end)
     stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
@@ -1629,7 +1636,7 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         stage_begin(ctx, TREXHIP_STAGE_CONV2);
         switch (p.chain) {
         case Chain::ROLE_SPLIT:
-            if (p.skip) launch_skip_prep(f, direct);
+            if (p.skip) launch_skip_prep(f, direct, x3);
             // (an instance whose list is empty returns at once)
             if (p.skipx)
                 K_CONV12_RSX(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.d_skip + SKX_CTR,
@@ -1653,8 +1660,11 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         stage_begin(ctx, TREXHIP_STAGE_CONV3);
         if (pre) {
             if (p.skip3) {     // the listed passes' descriptors and row sources, and the other pairs' act3; which form of the kernel runs is the device's word
-                K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e), reinterpret_cast<uint4*>(net.act3), net.skip3_desc,
-                            net.skip3_rows, alloc_rows, (int)direct, (int)!p.fc1_listed);
+                K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, x3 ? net.skipx_cols : nullptr, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e),
+                            reinterpret_cast<uint4*>(net.act3), net.skip3_desc, net.skip3_rows, net.skip3x_desc, net.skip3x_rows, alloc_rows, (int)direct, (int)!p.fc1_listed);
+                // (an instance whose list is empty returns at once)
+                if (x3)
+                    K_CONV3_WPAIR_LISTX(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.d_skip + SK3X_CTR, 0, net.skip3x_desc, net.skip3x_rows, net.d_skip);
                 K_CONV3_WPAIR_LIST(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.skip3_rows, net.d_skip);
             }
             K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3, nullptr, nullptr, p.skip3 ? net.d_skip : nullptr);
@@ -1846,12 +1856,40 @@ int trexhip_identify_bgrow_stats(trexhip_ctx* ctx, uint32_t* rows_read, uint32_t
     return TREXHIP_OK;
 }
 
+int trexhip_identify_skip3x_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes) {
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_skip3x_stats", w)) return rc;
+    if (crops_windowed) *crops_windowed = w[SK3_USE] ? w[SK3X_CROPS] : 0u;
+    if (windowed_passes) *windowed_passes = w[SK3_USE] ? w[SK3X_PASSES] : 0u;
+    if (full_passes) *full_passes = w[SK3_USE] ? w[SK3_PASSES] : 0u;
+    return TREXHIP_OK;
+}
+
 int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* listed, uint32_t* passes, uint64_t* bytes_filled) {
     uint32_t w[SK_WORDS];
     if (const int rc = read_skip_words(ctx, "trexhip_identify_skip3_stats", w)) return rc;
     if (pairs) *pairs = w[SK3_PAIRS];
     if (listed) *listed = w[SK3_LISTED];
-    if (passes) *passes = w[SK3_USE] ? w[SK3_PASSES] : 0u;
+    // (passes keeps counting by the row rule alone, as skip_stats does: the passes of six pairs the listed pairs make.  Where windowed passes ran
+    // the device has not counted those; the host restates them from the bands the call left, with the function the list kernels pack by)
+    uint32_t by_rows = w[SK3_PASSES];
+    if (passes && w[SK3_USE] && w[SK3X_PASSES]) {
+        const Net* net = static_cast<Net*>(ctx->net);
+        const int n = (int)(w[SK3_PAIRS] / Skip3Geom::PAIRS);
+        std::vector<int2> bands((size_t)n);
+        TH_CHECK_HIP(hipMemcpy(bands.data(), net->skip_bands, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+        int count = 0;
+        for (int c0 = 0; c0 < n; c0 += Skip3Geom::BLOCK) {
+            Skip3Pass p{};
+            for (int c = c0; c < n && c < c0 + Skip3Geom::BLOCK; ++c) {
+                const SkipPairs r = skip3_pairs({bands[(size_t)c].x, bands[(size_t)c].y});      // (windows exist: the empty crop is in range)
+                if (r.lo <= r.hi) skip3_add_run(p, count, c * Skip3Geom::PAIRS + r.lo, r.hi - r.lo + 1, [](int, const Skip3Pass&) {});
+            }
+            skip3_flush(p, count, [](int, const Skip3Pass&) {});
+        }
+        by_rows = (uint32_t)count;
+    }
+    if (passes) *passes = w[SK3_USE] ? by_rows : 0u;
     if (bytes_filled) *bytes_filled = (uint64_t)w[SK3_FILLED] * (10 * 128 * 4);
     return TREXHIP_OK;
 }

@@ -46,7 +46,19 @@
 // dense instance keeps its registers (256 + 210, no scratch, 2 vector spills), the listed one has 256 + 242, no scratch, no vector spills (256 +
 // 230 and 20 spills before).  (The pass's values are plain scalars on purpose: as members of a struct handed to the lambdas they stayed in scratch memory, 104
 // bytes per lane in BOTH instances.)
-template <bool LISTED>
+//
+// The WINDOWED listed form (L = Skip3XGeom; cnn_skip3.h: skip3_window) computes, of every listed pair of a crop whose blob reaches at most WT3 = 3
+// of a row's 5 tiles, only those 3: a pass is TEN pair slots of 6 tiles -- again 60 of the 64 tile slots -- from at most two runs, 28 V3 rows.
+// What differs from the full-width listed form is the LDS image (Wino3Pass, cnn_geom.h) and three constants: an LDS row holds the window's 3 tiles of
+// each of the 8 position groups (768 bytes of the V3 row's 1280), gathered by the staging -- the lane's constant maps its 16 LDS bytes to the head
+// of their 160-byte group of the V3 row and the row's table entry carries t0 * 32 bytes (skip3_row_words), so the staging instructions and the
+// tap loop are the same ones, fewer (12 DMA instructions per wave and unit instead of 14) --; the lane's tile is pair slot t / 6, place t % 6; and the
+// pair's act3 offset carries the window's 2 t0 pooled columns.  Per output element nothing depends on the slot or window it lands in: the bits are the
+// dense kernel's.  The 4 pooled columns outside the window hold the empty crop's bits, written by k_act3_fill.
+// Measured (profiles/conv3_windowed.txt; the benchmark's 25600 crops: 7347 windowed + 19658 full-width passes where the row-only list has 31383):
+// 116.4 ns per windowed pass against 113.7 ns per full-width pass under a kernel trace, 3423 -> 3091 us for both instances.  Registers: 256 + 236,
+// no scratch, no vector spills; the dense and the full-width listed instance keep theirs (256 + 210, 256 + 242).
+template <bool LISTED, class L = Skip3Geom>
 __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__ v3, const uint4* __restrict__ wp /*[4][5][8][2][2][128] x 16 B*/,
                                                      const float* __restrict__ bias, float* __restrict__ out, const float out_scale,
                                                      const int n_crops, uint32_t* __restrict__ pass_ctr,
@@ -66,13 +78,15 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     __shared__ int s_next_pass;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
-    using L = Skip3Geom;
     using LR = Skip3Reach;
+    using P = Wino3Pass<L::TILES, L::NR>;                 // the LDS image of a pass
+    constexpr bool WIN = L::TILES != G::TPR;              // the windowed listed form
+    static_assert(LISTED || !WIN, "only a listed pass has a window");
     static_assert(LR::ROWB == V3_ROWB && SkipGeom::V3_ROWS == S, "the images in front of V3 and behind it are S rows of V3_ROWB bytes");
-    static_assert(L::NR == G::NR && L::SLOTS * G::TPP <= G::MB && L::PAIRS * 2 == S, "a listed pass fits the dense pass's rows and tiles");
+    static_assert((WIN || (P::NR == G::NR && P::RP == G::RP && P::BUF == G::BUF)) && L::SLOTS * P::TPP <= G::MB && L::PAIRS * 2 == S, "a listed pass fits the dense pass's rows and tiles");
     if (words && (words[SK3_USE] != 0) != LISTED) return;
     const int total_tiles = n_crops * G::TPC;
-    const int n_pass = LISTED ? __builtin_amdgcn_readfirstlane((int)words[SK3_PASSES]) : (total_tiles + G::MB - 1) / G::MB;
+    const int n_pass = LISTED ? __builtin_amdgcn_readfirstlane((int)words[WIN ? SK3X_PASSES : SK3_PASSES]) : (total_tiles + G::MB - 1) / G::MB;
     const int n_big = LISTED ? (n_pass >= 16 * (int)gridDim.x ? (int)((long long)n_pass * 7 / 8) / 4 : 0) : n_big_dense;
     const int big_end = n_big * PK;
     auto ticket_first = [&](const int t) { return t < n_big ? t * PK : big_end + (t - n_big); };
@@ -86,22 +100,24 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     // the next buffer's zero row, or in the kilobyte of slack behind the second buffer) -- is given an offset outside the resource and comes
     // back as ZEROS, which is what a zero row holds.  No clamps, no lane masks, no branches: per instruction one scalar add (M0), the lane's
     // precomputed offset, the load.  Wave w issues the instructions w, w + 4, ...: NDW per wave and unit, one per tap.
-    constexpr int RNG = (2 * G::NR + 1) * G::RP, NI = (RNG + 1023) / 1024, NDW = (NI + 3) / 4;
+    constexpr int RNG = (2 * P::NR + 1) * P::RP, NI = (RNG + 1023) / 1024, NDW = (NI + 3) / 4;
     static_assert(DT0 + NDW <= 40 - BD, "the DMA instructions are older than the last 2 BD weight loads of a unit");
     static_assert(NI * 1024 - RNG <= 1024, "slack behind the second buffer");
     uint32_t dvo[NDW];
 #pragma unroll
     for (int k = 0; k < NDW; ++k) {
         const int o = (wave + 4 * k) * 1024 + lane * 16;
-        const int pc = o >= (G::NR + 1) * G::RP ? 1 : 0, q = o - pc * (G::NR + 1) * G::RP;
-        const int row = q / G::RP, w = q - row * G::RP;
-        const bool real = q < G::NR * G::RP && o < RNG;
-        const uint32_t inrow = (uint32_t)(pc * 1280 + (w < G::RP0 ? w : G::RP0 - 16));
+        const int pc = o >= (P::NR + 1) * P::RP ? 1 : 0, q = o - pc * (P::NR + 1) * P::RP;
+        const int row = q / P::RP, w = q - row * P::RP;
+        const bool real = q < P::NR * P::RP && o < RNG;
+        // (WIN: the LDS row's position group w / PS lies G::PS bytes apart in the V3 row; the window's first tile comes with the row's source)
+        const int wv = WIN ? (w / P::PS) * G::PS + w % P::PS : w;
+        const uint32_t inrow = (uint32_t)(pc * 1280 + (w < P::RP0 ? wv : G::RP0 - 16 - (WIN ? 2 * LR::TILEB : 0)));
         // LISTED: the row slot and the byte in the row; the slot's source is the pass's (its table's entry NR: none)
-        dvo[k] = LISTED ? (real ? (uint32_t)row << LR::ROW_SHIFT | inrow : (uint32_t)G::NR << LR::ROW_SHIFT)
+        dvo[k] = LISTED ? (real ? (uint32_t)row << LR::ROW_SHIFT | inrow : (uint32_t)P::NR << LR::ROW_SHIFT)
                         : real ? (uint32_t)(row * V3_ROWB) + inrow : 0x80000000u;
     }
-    const uint32_t mbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + G::RP + wave * 1024));
+    const uint32_t mbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + P::RP + wave * 1024));
     // (LISTED: qmin_ is the row of V3's allocation the pass's resource starts at -- the empty crop's image lies in front of V3 and behind it,
     // cnn_skip3.h --, and the resource has one size: the table's offsets are in range, what it calls none is not)
     auto stage_rsrc = [&](const int g, const int qmin_, const int nrows_) {
@@ -119,12 +135,12 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         if ((k_) < NDW - 1 || wave + 4 * (NDW - 1) < NI) {                                                                       \
             const uint32_t vo_ = LISTED ? dvo[k_] + (src_) : dvo[k_];                                                            \
             asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds"                          \
-                         :: "s"(mbase), "n"((buf_) * G::BUF + (k_) * 4096), "v"(vo_), "s"(srs_) : "memory", "scc");               \
+                         :: "s"(mbase), "n"((buf_) * P::BUF + (k_) * 4096), "v"(vo_), "s"(srs_) : "memory", "scc");               \
         }                                                                                                                        \
     } while (0)
-    for (int i = tid; i < 4 * (G::RP / 16); i += G::NTHR) {          // row slot 0 of the four planes = the zero row
-        const int pl = i / (G::RP / 16), o = i - pl * (G::RP / 16);
-        *reinterpret_cast<uint4*>(ldsb + pl * G::PLANE + o * 16) = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < 4 * (P::RP / 16); i += G::NTHR) {          // row slot 0 of the four planes = the zero row
+        const int pl = i / (P::RP / 16), o = i - pl * (P::RP / 16);
+        *reinterpret_cast<uint4*>(ldsb + pl * P::PLANE + o * 16) = make_uint4(0, 0, 0, 0);
     }
     const __amdgpu_buffer_rsrc_t wrs = make_rsrc(wp, (uint32_t)(G::NCH * 40 * G::BV * 16));
     const int boff = (h * CO + wave * 32 + j) * 16;
@@ -136,8 +152,8 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
 #pragma unroll
     for (int m = 0; m < TPW; ++m) {
         const int t = m * 32 + j;
-        lps[m] = t / G::TPP < L::SLOTS ? t / G::TPP : L::SLOTS - 1;
-        lr2[m] = t % G::TPP;
+        lps[m] = t / P::TPP < L::SLOTS ? t / P::TPP : L::SLOTS - 1;
+        lr2[m] = t % P::TPP;
     }
     // what a pass is: the dense form's rows qmin .. qmin + nrows - 1; LISTED: the descriptor's scalars (rows of run A, gap, the pairs' act3 offsets
     // relative to the pass's first pair) and the lane's two pair entries
@@ -158,8 +174,10 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         span_ = __builtin_amdgcn_readlane(w, S3_SPAN);
 #pragma unroll
         for (int s2 = 0; s2 < L::SLOTS; ++s2) {
-            const uint32_t rp = (uint32_t)__builtin_amdgcn_readlane(w, S3_SLOT + s2) >> 16;
-            rel_[s2] = rp == (uint32_t)S3_IDLE ? 0x80000000u : rp * (uint32_t)(G::TPP * CO * 4);
+            const uint32_t e = (uint32_t)__builtin_amdgcn_readlane(w, S3_SLOT + s2), rp = e >> 16;
+            // (WIN: the window's first pooled column, 2 t0, goes into the pair's offset: slot and place stay compile-time per accumulator row)
+            rel_[s2] = rp == (uint32_t)S3_IDLE ? 0x80000000u
+                     : rp * (uint32_t)(G::TPP * CO * 4) + (WIN ? ((e >> S3_T0_SHIFT) & S3_T0_MASK) * (uint32_t)(2 * CO * 4) : 0u);
         }
     };
     int qmin = 0, nrows = 0, gp0 = 0, span = 0;
@@ -187,7 +205,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     auto a_base = [&](const int pass_, const int qmin_, const int m, int& inr, int& zr, int& yy) {
         if (LISTED) {             // (the entries fetched last: this pass's in front of the loop, the next one's under the last unit)
             const int r2 = lr2[m], par = r2 & 1, e = ent[m];
-            yy = 2 * ((e >> 8) & 0xff) + par; zr = (r2 >> 1) * 32 + h * 16; inr = ((e & 0xff) + par) * G::RP + zr;
+            yy = 2 * ((e >> 8) & (WIN ? S3_Q_MASK : 0xff)) + par; zr = (r2 >> 1) * 32 + h * 16; inr = ((e & 0xff) + par) * P::RP + zr;
             return;
         }
         int T = pass_ * G::MB + m * 32 + j;
@@ -198,7 +216,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     };
     auto a_offset = [&](const int inr, const int zr, const int yy, const int ky) {
         const int iy = yy + ky - 2;
-        return (iy >= 0 && iy < S) ? inr + (ky - 2) * G::RP : zr;
+        return (iy >= 0 && iy < S) ? inr + (ky - 2) * P::RP : zr;
     };
     int aoff[TPW][5];
 #pragma unroll
@@ -245,8 +263,8 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             // tiles t0 = m * 32 + i (h = 0) and t0 + 4 (h = 1): pair slot and place in the pair are compile-time, the pair's offset is the pass's
             // (all of it in the lane's offset: that is what the resource's range check looks at)
             const int t0 = m * 32 + i, t1 = t0 + 4;
-            const uint32_t o0 = rel_prev[t0 / G::TPP] + (uint32_t)((t0 % G::TPP) * CO * 4);
-            const uint32_t o1 = t1 / G::TPP < L::SLOTS ? rel_prev[t1 / G::TPP < L::SLOTS ? t1 / G::TPP : 0] + (uint32_t)((t1 % G::TPP) * CO * 4) : 0x80000000u;
+            const uint32_t o0 = rel_prev[t0 / P::TPP] + (uint32_t)((t0 % P::TPP) * CO * 4);
+            const uint32_t o1 = t1 / P::TPP < L::SLOTS ? rel_prev[t1 / P::TPP < L::SLOTS ? t1 / P::TPP : 0] + (uint32_t)((t1 % P::TPP) * CO * 4) : 0x80000000u;
             const int vo = co * 4 + (int)(h ? o1 : o0);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v0 * out_scale + bz, 0.f)), rs, vo, 0, 2 /* nt */);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v1 * out_scale + bz, 0.f)), rs, vo + CO * 4, 0, 2);
@@ -289,7 +307,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             }
             // (without a next pass the descriptor fetched is this pass's own: the next = this one once more)
             if (LISTED && last_u) pass_decode(qmin_n, gp0_n, span_n, rel_n);
-            const uint8_t* pbase = ldsb + (g & 1) * G::BUF;
+            const uint8_t* pbase = ldsb + (g & 1) * P::BUF;
             // staged under this unit: the next unit of this pass, or unit 0 of the next pass (without one: this pass's once more, into the buffer
             // nobody reads again)
             const int sg = last_u ? 0 : g + 1;
@@ -302,8 +320,8 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             for (int a = 0; a < AD; ++a)
 #pragma unroll
                 for (int m = 0; m < TPW; ++m) {
-                    af[a][m][0] = *reinterpret_cast<const uint4*>(pbase + (a & 1) * G::PS + aoff[m][a / 2]);
-                    af[a][m][1] = *reinterpret_cast<const uint4*>(pbase + (a & 1) * G::PS + aoff[m][a / 2] + G::PLANE);
+                    af[a][m][0] = *reinterpret_cast<const uint4*>(pbase + (a & 1) * P::PS + aoff[m][a / 2]);
+                    af[a][m][1] = *reinterpret_cast<const uint4*>(pbase + (a & 1) * P::PS + aoff[m][a / 2] + P::PLANE);
                 }
 #pragma clang loop unroll(full)
             for (int tt = 0; tt < 40; ++tt) {
@@ -313,11 +331,11 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                 const uint32_t src_cur = src_next;
                 if (LISTED && tt + 1 >= DT0 && tt + 1 < DT0 + NDW) src_next = P3_SRC(tt + 1 - DT0, tab);
                 if (tt + AD < 40) {
-                    const uint8_t* an = pbase + (((tt + AD) / 10) * 2 + ((tt + AD) & 1)) * G::PS;
+                    const uint8_t* an = pbase + (((tt + AD) / 10) * 2 + ((tt + AD) & 1)) * P::PS;
 #pragma unroll
                     for (int m = 0; m < TPW; ++m) {
                         af[nxt][m][0] = *reinterpret_cast<const uint4*>(an + aoff[m][((tt + AD) % 10) / 2]);
-                        af[nxt][m][1] = *reinterpret_cast<const uint4*>(an + aoff[m][((tt + AD) % 10) / 2] + G::PLANE);
+                        af[nxt][m][1] = *reinterpret_cast<const uint4*>(an + aoff[m][((tt + AD) % 10) / 2] + P::PLANE);
                     }
                 }
                 const int wt = tt + BD < 40 ? w_off(g, tt + BD) : w_off(sg, tt + BD - 40);

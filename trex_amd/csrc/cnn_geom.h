@@ -94,6 +94,29 @@ struct WinoGeom {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
+// k_conv5_wpair's LDS image of a pass (cnn_conv3p.h): NR row slots (and the zero row) of TPR tiles per piece, two pieces, two buffers.  The
+// dense form and the full-width listed form hold whole rows (TPR 5: WinoGeom's numbers); the windowed listed form holds the WT3 = 3 tiles of a
+// crop's window (cnn_skip3.h), gathered from the V3 row by the staging.
+// Row pitch: a ds_read_b128 is served in lane groups of 16 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of each half wave), and a group is free of
+// conflicts when its lanes fall into 16 different 16-byte slots of the 256-byte bank row.  Lane j of a half reads tile j (or 32 + j) = pair slot
+// j / (2 TPR), row j & 1 of the pair, tile (j % (2 TPR)) >> 1 of the row, at (row slot * RP + 32 tile) bytes.  Counted over the four groups of both
+// of a wave's tiles, for consecutive pairs and for two runs a halo apart, every pitch leaves at least one group with two lanes on one slot; the
+// pitches == 5 (mod 8) slots at TPR 5 and == 3 (mod 8) slots at TPR 3 leave exactly one such group, every other pitch 2 to 7 times as many
+// conflicts.  (TPR 5: the pitch WinoGeom::RP derived from contiguous lane groups -- the same number.)
+template <int TPR_, int NR_>
+struct Wino3Pass {
+    static_assert(TPR_ == 5 || TPR_ == 3, "pitches counted for 5 and 3 tiles per row");
+    static constexpr int TPR = TPR_, TPP = 2 * TPR, NR = NR_;
+    static constexpr int PS = TPR * 32, RP0 = 8 * PS;                   // bytes per position of a row; bytes of a row
+    static constexpr int PITCH_MOD8 = TPR == 5 ? 5 : 3;
+    static constexpr int RP = RP0 + (((PITCH_MOD8 - (RP0 / 16) % 8) + 8) % 8) * 16;
+    static constexpr int PLANE = (NR + 1) * RP, BUF = 2 * PLANE, LDS_BYTES = 2 * BUF;
+    static_assert(LDS_BYTES + 1024 <= 160 * 1024, "LDS");
+};
+static_assert(Wino3Pass<5, 20>::RP == WinoGeom<64, 128, 20, 2>::RP && Wino3Pass<5, 20>::LDS_BYTES == WinoGeom<64, 128, 20, 2>::LDS_BYTES &&
+              Wino3Pass<5, 20>::PS == WinoGeom<64, 128, 20, 2>::PS, "the full-width pass is WinoGeom's");
+static_assert(Wino3Pass<3, 28>::RP == 816, "768 bytes of tiles + 3 slots");
+
 // k_conv2_wpre2 (cnn_wpre.h) and the fused conv1+conv2 kernels on top of it: a pass = RPP row pairs of conv2's output
 struct W2bGeom {
     static constexpr int CO = 64, S = 40, TPP = 20, RPP = 3, NR = 2 * RPP + 4;

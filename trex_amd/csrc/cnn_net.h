@@ -46,10 +46,12 @@ struct Net {
     int* skipx_rows = nullptr;                 // beside every entry of skipx_list: the V2 rows of its crop that are made (skipx_v2_pack)
     // computing only the row pairs of conv3 whose V3 rows hold more than background (cnn_skip3.h, cnn_skip_kernels.h)
     float* act3e = nullptr;                    // the act3 of an all-zero crop [10][10][128], made when the weights are loaded, behind v3e
-    uint2* skip3_counts = nullptr;             // listed passes and pairs per workgroup of k_pair_count
-    uint32_t* skip3_tcounts = nullptr;         // listed passes per thread of it (Skip3Geom::BLOCK crops)
+    uint4* skip3_counts = nullptr;             // per workgroup of k_pair_count: full-width listed passes, pairs, windowed passes, windowed crops
+    uint32_t* skip3_tcounts = nullptr;         // full-width and windowed listed passes per block of Skip3Geom::BLOCK crops
     int* skip3_desc = nullptr;                 // Skip3Geom::DESC words per listed pass
     uint32_t* skip3_rows = nullptr;            // Skip3Reach::WORDS words per listed pass: where the rows it stages come from
+    int* skip3x_desc = nullptr;                // Skip3XGeom::DESC words per windowed listed pass (skip3_window)
+    uint32_t* skip3x_rows = nullptr;           // Skip3Reach::WORDS words per windowed listed pass
     // fc1 computing only the listed (crop, plane) rows (skip3_fc1_listed, cnn_skip3.h)
     float* fc1e = nullptr;                     // the fc1 planes of an all-zero crop [FC1_KSPLIT][128] (plane 0 with the bias), made behind act3e
     int* fc1_list = nullptr;                   // [Skip3Geom::PAIRS][max_crops]: per plane the crops it computes, in order (lengths: d_skip + SK3_FC1_LEN)

@@ -12,6 +12,7 @@ namespace trexhip {
 // the bits of TREXHIP_CONV_GEOM (a test hook; include/trexhip.h documents the values)
 enum : int {
     GEOM_FP32_ACT = 0xfff,            // bits 0-11, any of them: the fp32-activation chain
+    GEOM_NO_SKIP3X = 1 << 21,         // no crop gets a window of conv3 tiles
     GEOM_NO_BGROWS = 1 << 22,         // the windowed conv1+conv2 makes every V2 row, background rows too
     GEOM_NO_SKIPX = 1 << 23,          // no crop gets a window
     GEOM_DENSE_FC1 = 1 << 24,         // the dense fc1
@@ -21,7 +22,7 @@ enum : int {
     GEOM_TWO_KERNEL = 1 << 28,        // conv1 and conv2 as two kernels
     GEOM_ROLE_SPLIT = 1 << 29,        // the role-split conv1+conv2 at any batch size
     GEOM_FUSED_2WG = 1 << 30,         // the two-workgroup conv1+conv2 at any batch size
-    GEOM_MASK = GEOM_FP32_ACT | GEOM_NO_BGROWS | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
+    GEOM_MASK = GEOM_FP32_ACT | GEOM_NO_SKIP3X | GEOM_NO_BGROWS | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
 };
 
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
@@ -43,6 +44,11 @@ enum : int {
 //                             other returns at once.  Off (GEOM_DENSE_CONV3, bit 26): the dense conv3 alone
 //                 v3_direct   the listed conv3 reads the background rows from the empty crop's image itself and k_v3_fill returns at once where
 //                             that form runs.  Off (GEOM_V3_COPY, bit 25): the fill always copies, the listed form reads every row from V3
+//                 skip3x      where v3_direct is on: k_pair_count / k_pair_list read the column bands too and make TWO lists of conv3 passes -- windowed
+//                             passes (10 row pairs x 3 tiles, skip3_window) of the crops whose blob reaches at most 3 of conv3's 5 tiles, full-width
+//                             passes (6 row pairs) of the others; k_act3_fill describes both and copies the pooled columns outside the windows;
+//                             k_conv5_wpair<true, Skip3XGeom> runs on the first list in front of the full-width listed instance on the second.  Off
+//                             (GEOM_NO_SKIP3X, bit 21): no crop gets a window -- the same kernels, one list, the full-width listed instance alone
 //                 fc1_listed  above 1024 crops: k_fc1_list beside k_pair_list, fc1 computes only the (crop, split-K plane) rows whose row pair is
 //                             listed -- the listed k_fc1_split<4>; k_head takes the other planes from the empty crop's, k_act3_fill copies no
 //                             pair.  Off (GEOM_DENSE_FC1, bit 24): the dense fc1, and the fill copies
@@ -85,6 +91,9 @@ struct CnnPlan {
     Launch act3_fill;               // k_act3_fill: 16 crops (SKIP3_FC) per workgroup
     bool v3_direct;                 // where skip3 is on: the listed conv3 reads background rows from the empty crop's image, k_v3_fill copies only for the
                                     // dense form; off: bit 25, or a batch whose V3 is longer than both images' reach (skip3_direct_fits)
+    bool skip3x;                    // where skip3 and v3_direct are on: the listed pairs of the crops whose blob fits a window of 3 conv3 tiles (skip3_window) go
+                                    // into windowed passes -- k_pair_count / k_pair_list make two lists, k_act3_fill describes both and copies the pooled columns
+                                    // outside the windows, and k_conv5_wpair<true, Skip3XGeom> runs in front of the full-width listed instance; off: bit 21
     bool fc1_listed;                // where skip3 is on, fc1 is SPLIT4 and the head BIG: k_fc1_list in front of conv1+conv2, the listed k_fc1_split<4>
                                     // computes only the listed (crop, plane) rows, k_head takes the others from Net::fc1e, k_act3_fill copies nothing; off: bit 24
     bool skipx;                     // where skip is on: the crops whose blob fits a window of 8 tiles take the windowed instance of the role-split kernel
@@ -154,6 +163,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
         p.skip3_grid = ceil_div(ceil_div(n, 32 /* Skip3Geom::BLOCK crops per thread */), 256);
         p.act3_fill = {ceil_div(n, 16), n};
         p.v3_direct = !(geom & GEOM_V3_COPY) && skip3_direct_fits((long long)n * SkipGeom::V3_ROWS);
+        p.skip3x = p.v3_direct && !(geom & GEOM_NO_SKIP3X) && skip3x_direct_fits((long long)n * SkipGeom::V3_ROWS);
     }
 
     const int n_pass2 = ceil_div(n * 20, W2bGeom::RPP), n_pass3 = ceil_div(n * GW::TPC, GW::MB);

@@ -12,6 +12,7 @@
 
 namespace trexhip {
 
+constexpr bool S3X_DESC_OK(const int desc, const int slots) { return 8 + slots <= desc && (desc & (desc - 1)) == 0; }
 struct Skip3Geom {
     static constexpr int PAIRS = SkipGeom::V3_ROWS / SkipGeom::POOL;        // row pairs per crop (10)
     static constexpr int SLOTS = 6;                                         // row pairs per listed pass: 60 of the kernel's 64 tiles
@@ -22,9 +23,56 @@ struct Skip3Geom {
     static constexpr int BLOCK = 32;                                        // crops packed by one thread; a pass never holds pairs of two blocks
     static constexpr int BLOCK_PASSES = (BLOCK * PAIRS + SLOTS - 1) / SLOTS + BLOCK + 1;   // full passes + passes closed by a third run + the last
     static constexpr int DESC = 16;                                         // words of a pass's descriptor
+    static constexpr int TILES = SkipGeom::V3_ROWS / 4;                     // F(4,5) tiles of a row that a pass computes: all 5
     static_assert(PAIRS == 10 && HALO == 2 && NR == 20, "pair q reads V3 rows 2q - 2 .. 2q + 3");
     static_assert((long long)(SPAN + SLOTS) * SkipGeom::POOL * 10240 < (1ll << 31), "V3 byte distance inside a pass");
 };
+
+// ---- the rule in x ----
+// conv3 tile t (F(4,5): TILE output columns of the 20-wide map) reads the V3 columns TILE t - KH / 2 .. TILE t + TILE - 1 + KH / 2, V3 column c
+// conv2's columns under its pool window, those V2's columns skip_layer_lo .. skip_layer_hi, and a V2 column the crop's columns likewise: two
+// layers of cnn_skip.h under the tile's window.  A tile whose whole band of crop columns is background -- in every row its pair reads -- holds
+// the empty crop's bits, for the reason cnn_skip.h gives for rows.
+struct Skip3XGeom {
+    static constexpr int PAIRS = Skip3Geom::PAIRS, RUNS = Skip3Geom::RUNS, HALO = Skip3Geom::HALO, SPAN = Skip3Geom::SPAN, BLOCK = Skip3Geom::BLOCK;
+    static constexpr int TILE = 4;                                          // conv3 output columns per tile
+    static constexpr int ROW_TILES = SkipGeom::V3_ROWS / TILE;              // 5 per row
+    static constexpr int WT3 = 3;                                           // the window: tiles of a row that a windowed pass computes
+    static constexpr int TILES = WT3;
+    static constexpr int SLOTS = 10;                                        // row pairs per windowed pass: 60 of the kernel's 64 tiles, as in the full-width form
+    // V3 rows a windowed pass can stage: two runs of any lengths (a narrow row is 0.6 of a full one, so 29 row slots are 93 KB of LDS where the
+    // full-width form's 21 are 112 KB).  Packing the benchmark's crops (800 of them, blocks of 32 crops) on the CPU: 20 or 24 rows give 897
+    // passes for the narrow and the wide list together, 28 rows 855, against 985 full-width passes; 40 rows (two whole crops) need a 64-word row
+    // table and were not tried
+    static constexpr int NR = SkipGeom::POOL * SLOTS + 2 * HALO * RUNS;
+    static constexpr int BLOCK_PASSES = (BLOCK * PAIRS + SLOTS - 1) / SLOTS + BLOCK + 1;
+    static constexpr int DESC = 32;                                         // 8 + SLOTS words, a power of two
+    static constexpr int V3_LO0 = -(SKIP_KH / 2), V3_HI0 = TILE - 1 + SKIP_KH / 2;
+    static constexpr int STEP = TILE * SkipGeom::POOL * SkipGeom::POOL, LO0 = skip_layer_lo(skip_layer_lo(V3_LO0)), HI0 = skip_layer_hi(skip_layer_hi(V3_HI0));
+    static_assert(STEP == 16 && LO0 == -14 && HI0 == 29, "tile t reads crop columns 16 t - 14 .. 16 t + 29");
+    static_assert(SLOTS * 2 * WT3 <= 64 && NR == 28 && S3X_DESC_OK(DESC, SLOTS), "60 of 64 tile slots; the descriptor holds the slots");
+    static_assert((long long)(SPAN + SLOTS) * SkipGeom::POOL * 10240 < (1ll << 31), "V3 byte distance inside a pass");
+};
+
+// the conv3 tiles of a crop that can differ from the empty crop's, from its first and last non-zero COLUMN (SkipBand's y0, y1 read as x0, x1); none: lo > hi
+struct Skip3Tiles { int lo, hi; };
+TREXHIP_HD constexpr Skip3Tiles skip3_tiles(const SkipBand b) {
+    using X = Skip3XGeom;
+    if (b.y0 > b.y1) return {1, 0};
+    // STEP t + HI0 >= x0  and  STEP t + LO0 <= x1
+    const int lo = b.y0 <= X::HI0 ? 0 : (b.y0 - X::HI0 + X::STEP - 1) / X::STEP;
+    const int hi = (b.y1 - X::LO0) / X::STEP;
+    return {lo, hi < X::ROW_TILES - 1 ? hi : X::ROW_TILES - 1};
+}
+// the window [t0, t0 + WT3) of a crop; -1: it has none -- it needs more than WT3 tiles, it has no column band (and no pair to compute), or the
+// empty crop's image is not to be used
+TREXHIP_HD constexpr int skip3_window(const SkipBand cols, const bool empty_out_of_range) {
+    using X = Skip3XGeom;
+    if (empty_out_of_range) return -1;
+    const Skip3Tiles t = skip3_tiles(cols);
+    if (t.lo > t.hi || t.hi - t.lo + 1 > X::WT3) return -1;
+    return t.lo < X::ROW_TILES - X::WT3 ? t.lo : X::ROW_TILES - X::WT3;
+}
 
 // the row pairs of a crop that must be computed; none: lo > hi
 struct SkipPairs { int lo, hi; };
@@ -45,9 +93,9 @@ struct Skip3Pass { int n, runs, gp0[Skip3Geom::RUNS], len[Skip3Geom::RUNS]; };
 
 // the pairs gp .. gp + len - 1 of one crop go into the pass being filled and the passes behind it; emit(index, pass) takes every pass that closes.
 // A pass closes when it is full, when a third run would begin, or when the next run lies more than SPAN pairs behind its first one
-template <class E>
+// (G: Skip3Geom, the full-width passes, or Skip3XGeom, the windowed ones -- the same rule with their slots)
+template <class G = Skip3Geom, class E>
 TREXHIP_HD constexpr void skip3_add_run(Skip3Pass& p, int& passes, int gp, int len, E&& emit) {
-    using G = Skip3Geom;
     while (len > 0) {
         if (p.n == G::SLOTS || p.runs == G::RUNS || (p.runs && gp - p.gp0[0] > G::SPAN)) { emit(passes, p); ++passes; p = Skip3Pass{}; }
         const int take = len < G::SLOTS - p.n ? len : G::SLOTS - p.n;
@@ -74,12 +122,13 @@ TREXHIP_HD constexpr Skip3Rows skip3_run_rows(const int gp0, const int len) {
 // What the kernel reads of a pass, DESC words:
 //   0  first staged V3 row of run A        1  rows of run A          2  V3 rows between the end of run A's rows and run B's first (>= 0)
 //   3  rows of both runs (<= NR)           4  first pair of the pass 5  pairs from the first to the last of the pass (the act3 range it stores to)
-//   8 + s, s < SLOTS: pair slot s = (pair - first pair) << 16 | q << 8 | LDS row slot of the pair's even conv row (1 ..); idle: 0xffff << 16 | 1
-enum : int { S3_ROW0 = 0, S3_NA = 1, S3_GAP = 2, S3_ROWS = 3, S3_GP0 = 4, S3_SPAN = 5, S3_SLOT = 8 };
+//   8 + s, s < SLOTS: pair slot s = (pair - first pair) << 16 | t0 << 12 | q << 8 | LDS row slot of the pair's even conv row (1 ..); idle: 0xffff << 16 | 1
+//   (t0: the first tile of the window of the run's crop, windowed passes only: 0 in a full-width pass)
+enum : int { S3_ROW0 = 0, S3_NA = 1, S3_GAP = 2, S3_ROWS = 3, S3_GP0 = 4, S3_SPAN = 5, S3_SLOT = 8, S3_T0_SHIFT = 12, S3_Q_MASK = 0xf, S3_T0_MASK = 0x3 };
 static constexpr int S3_IDLE = 0xffff;
 // (every index into d is a constant once the loops are unrolled: on the device the words stay in registers)
-TREXHIP_HD constexpr void skip3_describe(const Skip3Pass& p, int (&d)[Skip3Geom::DESC]) {
-    using G = Skip3Geom;
+template <class G = Skip3Geom>
+TREXHIP_HD constexpr void skip3_describe(const Skip3Pass& p, int (&d)[G::DESC], const int t0a = 0, const int t0b = 0) {
     const bool two = p.runs > 1;
     const int la = p.len[0], lb = two ? p.len[1] : 0, ga = p.gp0[0], gb = two ? p.gp0[1] : ga + la;
     const Skip3Rows a = skip3_run_rows(ga, la);
@@ -91,7 +140,7 @@ TREXHIP_HD constexpr void skip3_describe(const Skip3Pass& p, int (&d)[Skip3Geom:
         const bool in_a = s < la, in_b = !in_a && s - la < lb;
         const int gp = in_a ? ga + s : gb + (s - la);
         const int slot = 1 + (in_a ? 0 : a.n) + SkipGeom::POOL * gp - (in_a ? a.row0 : b.row0);
-        d[S3_SLOT + s] = in_a || in_b ? (gp - ga) << 16 | (gp % G::PAIRS) << 8 | slot : S3_IDLE << 16 | 1;
+        d[S3_SLOT + s] = in_a || in_b ? (gp - ga) << 16 | (in_a ? t0a : t0b) << S3_T0_SHIFT | (gp % G::PAIRS) << 8 | slot : S3_IDLE << 16 | 1;
     }
 }
 
@@ -105,8 +154,8 @@ TREXHIP_HD constexpr void skip3_describe(const Skip3Pass& p, int (&d)[Skip3Geom:
 //     S3_SRC_NONE               behind the pass's rows: reads zeros
 // own_a / own_b: skip_rows of the bands of run A's and run B's crop ({0, V3_ROWS - 1}: every row from V3 -- where k_v3_fill has copied the image)
 enum : int { S3_SRC_NONE = -1, S3_SRC_IMAGE = 1 << 30 };
-TREXHIP_HD constexpr void skip3_row_sources(const Skip3Pass& p, const SkipRows own_a, const SkipRows own_b, int (&src)[Skip3Geom::NR]) {
-    using G = Skip3Geom;
+template <class G = Skip3Geom>
+TREXHIP_HD constexpr void skip3_row_sources(const Skip3Pass& p, const SkipRows own_a, const SkipRows own_b, int (&src)[G::NR]) {
     const bool two = p.runs > 1;
     const Skip3Rows a = skip3_run_rows(p.gp0[0], p.len[0]);
     const Skip3Rows b = two ? skip3_run_rows(p.gp0[1], p.len[1]) : Skip3Rows{a.row0 + a.n, 0};
@@ -137,7 +186,10 @@ struct Skip3Reach {
     static constexpr unsigned OFF_NONE = 0xFFFF0000u;                       // + a byte in the row: still below 2^32, never below NUM_RECORDS
     static constexpr long long REACH_ROWS = REACH / ROWB;
     static constexpr int PASS_ROWS = (Skip3Geom::SPAN + Skip3Geom::SLOTS) * SkipGeom::POOL + 2 * Skip3Geom::HALO;   // first to last row of a pass, at most
+    static constexpr int PASS_ROWS_X = (Skip3XGeom::SPAN + Skip3XGeom::SLOTS) * SkipGeom::POOL + 2 * Skip3XGeom::HALO;   // ... of a windowed pass
+    static constexpr int TILEB = 32;                                        // bytes of a tile in each of a row's position groups: a window starts t0 * TILEB into them
     static_assert(ROWB * 4 <= (1 << ROW_SHIFT) && Skip3Geom::NR < WORDS - 1 && (Skip3Geom::NR << ROW_SHIFT) > 0, "the packed constant");
+    static_assert(Skip3XGeom::NR < WORDS - 1 && (Skip3XGeom::NR << ROW_SHIFT) > 0, "the packed constant, windowed passes");
     static_assert(NUM_RECORDS - 4 * 2560 >= REACH && OFF_NONE >= NUM_RECORDS, "none is out of range in every unit's resource");
 };
 // can every pass of a batch of `total` V3 rows reach an image?  (a pass out of the front image's reach starts behind row
@@ -146,13 +198,20 @@ TREXHIP_HD constexpr bool skip3_direct_fits(const long long total) {
     using R = Skip3Reach;
     return total <= 2 * R::REACH_ROWS - 2 * SkipGeom::V3_ROWS - R::PASS_ROWS - 1;
 }
+// ... and every windowed pass (10 pair slots: its rows reach further)
+TREXHIP_HD constexpr bool skip3x_direct_fits(const long long total) {
+    using R = Skip3Reach;
+    return total <= 2 * R::REACH_ROWS - 2 * SkipGeom::V3_ROWS - R::PASS_ROWS_X - 1;
+}
+// (t0a, t0b: windowed passes -- the first tile of the window of run A's and run B's crop: a row's source starts t0 * TILEB bytes into the row, so
+// that the lane's constant, which places the window's tiles at the head of each position group, lands on tile t0's)
+template <class G = Skip3Geom>
 TREXHIP_HD constexpr void skip3_row_words(const Skip3Pass& p, const SkipRows own_a, const SkipRows own_b, const long long total,
-                                          unsigned (&w)[Skip3Reach::WORDS]) {
-    using G = Skip3Geom;
+                                          unsigned (&w)[Skip3Reach::WORDS], const int t0a = 0, const int t0b = 0) {
     using R = Skip3Reach;
     constexpr int IMG = SkipGeom::V3_ROWS;
     int src[G::NR] = {};
-    skip3_row_sources(p, own_a, own_b, src);
+    skip3_row_sources<G>(p, own_a, own_b, src);
     const bool two = p.runs > 1;
     const Skip3Rows a = skip3_run_rows(p.gp0[0], p.len[0]);
     const Skip3Rows b = two ? skip3_run_rows(p.gp0[1], p.len[1]) : Skip3Rows{a.row0 + a.n, 0};
@@ -165,7 +224,7 @@ TREXHIP_HD constexpr void skip3_row_words(const Skip3Pass& p, const SkipRows own
         const int s = i < G::NR ? src[i < G::NR ? i : 0] : S3_SRC_NONE;
         const bool none = s == S3_SRC_NONE, img = !none && (s & S3_SRC_IMAGE);
         const long long row = img ? (front ? 0 : back) + (s & ~S3_SRC_IMAGE) : IMG + s;
-        const unsigned off = none ? R::OFF_NONE : (unsigned)((row - base) * R::ROWB);
+        const unsigned off = none ? R::OFF_NONE : (unsigned)((row - base) * R::ROWB) + (unsigned)((i < a.n ? t0a : t0b) * R::TILEB);
         w[i] = i == R::BASE ? (unsigned)base : off - ((unsigned)i << R::ROW_SHIFT);
     }
 }

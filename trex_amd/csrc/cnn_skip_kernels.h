@@ -12,16 +12,19 @@
 //                  ticket counter zeroed, and SK_LEN / SK_NPASS / SK_FILLED by the row rule alone.  `cols` null: no crop has a window -- the
 //                  full-width list is the row rule's, and neither the windowed list nor the SKX_* words are touched
 //   k_pair_count   (listed conv3) listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK
-//                  consecutive crops
-//   k_pair_list    the passes in order, each as its two runs, the counters, and the word that names the form of conv3 that runs (SK3_USE)
+//                  consecutive crops -- where crops can have windows of conv3 tiles (`cols` not null; skip3_window), those of the crops with one
+//                  into windowed passes (Skip3XGeom: 10 pairs), the others' into full-width passes (6 pairs), in one walk
+//   k_pair_list    the passes of both lists in order, each as its two runs, the counters, the windowed instance's ticket counter zeroed, and the
+//                  word that names the form of conv3 that runs (SK3_USE: the passes of both lists together against the dense kernel's)
 //   k_fc1_list     (listed fc1) a workgroup per split-K plane: the crops whose pair the plane has to compute, in order, and how many they are
 //   k_v3_fill      row by row: a V3 row that nobody computes -- its crop has no window over it and its aligned pass is not on the full-width
 //                  list -- copied from the V3 image of an all-zero crop (Net::v3e, made at load).  For the dense conv3 only: where the listed
 //                  form runs and takes those rows from the image itself (`direct`), it reads SK3_USE and returns at once
 // and behind conv1+conv2:
-//   k_act3_fill    a thread per pass: the runs made into the descriptor the kernel reads (in place) and the sources of its rows; then a wave per
-//                  crop: the act3 row pairs that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load) -- counted
-//                  only, where the listed fc1 runs: it never reads them
+//   k_act3_fill    a thread per pass of either list: the runs made into the descriptor the kernel reads (in place) and the sources of its rows; then
+//                  a wave per crop: the act3 row pairs that are NOT listed, copied from the act3 of an all-zero crop (Net::act3e, made at load) --
+//                  counted only, where the listed fc1 runs: it never reads them --, and of the LISTED pairs of a crop with a window the 4 pooled
+//                  columns outside it, copied always
 #pragma once
 
 static constexpr int SKIP_LB = 1024;      // passes / crops per block of the count / list kernels (one per thread)
@@ -248,93 +251,121 @@ static constexpr int SKIP3_TB = 256;      // threads per workgroup of the count 
 // the listed pairs of the workgroup's SKIP3_TB * BLOCK crops into LDS, one byte each for the first pair and the count, crop k of thread t at
 // [k][t]: read with coalesced loads here, walked by one thread per BLOCK crops from LDS in a loop that stays small (a walk unrolled over
 // registers is 30 KB of code that every thread runs once, from a cold instruction cache: 35 us for what is 800 threads' work)
-__device__ __forceinline__ void skip3_stage_runs(const int2* __restrict__ bands, const int n, const bool all, uint16_t* s_run) {
+// (cols not null: the crops whose blob fits a window of WT3 conv3 tiles carry t0 + 1 in bits 12 ..: their runs go into the windowed list)
+// The count / list kernels run SKIP3_NT = 2 SKIP3_TB threads: the first SKIP3_TB walk the full-width list of their BLOCK crops, the others -- whole
+// waves -- the windowed list of the same crops at the same time (one thread walking both lists, in one loop or in two, was 1.6 times the time of
+// these kernels, which is that loop's latency)
+static constexpr int SKIP3_NT = 2 * SKIP3_TB;
+__device__ __forceinline__ void skip3_stage_runs(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const bool all, uint16_t* s_run) {
     using G = Skip3Geom;
     const int c0 = blockIdx.x * SKIP3_TB * G::BLOCK;
     constexpr int U = 8;              // loads in flight per thread: one after the other they are BLOCK round trips to memory
-    static_assert(G::BLOCK % U == 0, "whole groups of loads");
-    for (int i0 = threadIdx.x; i0 < SKIP3_TB * G::BLOCK; i0 += U * SKIP3_TB) {
-        int2 b[U];
+    static_assert(G::BLOCK % U == 0 && (SKIP3_TB * G::BLOCK) % (U * SKIP3_NT) == 0, "whole groups of loads");
+    for (int i0 = threadIdx.x; i0 < SKIP3_TB * G::BLOCK; i0 += U * SKIP3_NT) {
+        int2 b[U], c[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * SKIP3_TB;
+            const int i = i0 + u * SKIP3_NT;
             b[u] = c0 + i < n ? bands[c0 + i] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
+            c[u] = cols && c0 + i < n ? cols[c0 + i] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * SKIP3_TB;
+            const int i = i0 + u * SKIP3_NT;
             const SkipPairs r = all && c0 + i < n ? SkipPairs{0, G::PAIRS - 1} : skip3_pairs({b[u].x, b[u].y});
-            s_run[(i % G::BLOCK) * SKIP3_TB + i / G::BLOCK] = (uint16_t)(r.lo <= r.hi ? r.lo | (r.hi - r.lo + 1) << 8 : 0);
+            const int t0 = skip3_window({c[u].x, c[u].y}, all);
+            s_run[(i % G::BLOCK) * SKIP3_TB + i / G::BLOCK] = (uint16_t)(r.lo <= r.hi ? r.lo | (r.hi - r.lo + 1) << 8 | (t0 + 1) << 12 : 0);
         }
     }
     __syncthreads();
 }
-// the row pairs of the crops of block `blk` (this thread's) packed into passes (numbered from `passes` on); emit(index, pass) takes each; -> pairs listed
-template <class E>
-__device__ __forceinline__ int skip3_walk(const uint16_t* s_run, const int blk, int& passes, E&& emit) {
-    using G = Skip3Geom;
+// the row pairs of the crops of block `blk` (column t of s_run) that belong to list G -- Skip3XGeom: the crops with a window, Skip3Geom: the others --
+// packed into passes (numbered from `passes` on); emit(index, pass) takes each; crops: how many took part; -> pairs listed
+template <class G, class E>
+__device__ __forceinline__ int skip3_walk(const uint16_t* s_run, const int t, const int blk, int& passes, int& crops, E&& emit) {
+    constexpr bool WIN = G::TILES != Skip3Geom::TILES;
     Skip3Pass p{};
     int listed = 0;
 #pragma unroll 1
     for (int k = 0; k < G::BLOCK; ++k) {
-        const int r = s_run[k * SKIP3_TB + threadIdx.x], len = r >> 8;
-        if (len) {
+        const int r = s_run[k * SKIP3_TB + t], len = (r >> 8) & 0xf;
+        if (len && ((r >> 12) != 0) == WIN) {
             listed += len;
-            skip3_add_run(p, passes, (blk * G::BLOCK + k) * G::PAIRS + (r & 0xff), len, emit);
+            ++crops;
+            skip3_add_run<G>(p, passes, (blk * G::BLOCK + k) * G::PAIRS + (r & 0xff), len, emit);
         }
     }
     skip3_flush(p, passes, emit);
     return listed;
 }
 
-__global__ __launch_bounds__(SKIP3_TB) void k_pair_count(const int2* __restrict__ bands, const int n, const uint32_t* __restrict__ words,
-                                                         uint2* __restrict__ counts /* per workgroup: passes, pairs */,
-                                                         uint32_t* __restrict__ tcounts /* per thread: passes */) {
-    __shared__ uint32_t s_pass, s_pair;
+// (cols null: no crop has a window, one list, as before there were windows; the second half of the workgroup has nothing to walk)
+__global__ __launch_bounds__(SKIP3_NT) void k_pair_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const uint32_t* __restrict__ words,
+                                                         uint4* __restrict__ counts /* per workgroup: full-width passes, pairs, windowed passes, windowed crops */,
+                                                         uint32_t* __restrict__ tcounts /* per block of crops: full-width passes, windowed passes */) {
+    __shared__ uint32_t s_pass, s_pair, s_wpass, s_wcrop;
     __shared__ uint16_t s_run[SKIP3_TB * Skip3Geom::BLOCK];
-    if (threadIdx.x == 0) { s_pass = 0; s_pair = 0; }
-    skip3_stage_runs(bands, n, words[SK_EMPTY_RANGE] != 0, s_run);
-    const int blk = blockIdx.x * SKIP3_TB + threadIdx.x;
+    if (threadIdx.x == 0) { s_pass = 0; s_pair = 0; s_wpass = 0; s_wcrop = 0; }
+    skip3_stage_runs(bands, cols, n, words[SK_EMPTY_RANGE] != 0, s_run);
+    const bool win = threadIdx.x >= SKIP3_TB;                 // (whole waves)
+    const int t = threadIdx.x & (SKIP3_TB - 1), blk = blockIdx.x * SKIP3_TB + t;
     if (blk * Skip3Geom::BLOCK < n) {
-        int passes = 0;
-        const int listed = skip3_walk(s_run, blk, passes, [](int, const Skip3Pass&) {});
-        tcounts[blk] = (uint32_t)passes;
-        if (passes) { atomicAdd(&s_pass, (uint32_t)passes); atomicAdd(&s_pair, (uint32_t)listed); }
+        int passes = 0, crops = 0, listed = 0;
+        if (!win) listed = skip3_walk<Skip3Geom>(s_run, t, blk, passes, crops, [](int, const Skip3Pass&) {});
+        else if (cols) listed = skip3_walk<Skip3XGeom>(s_run, t, blk, passes, crops, [](int, const Skip3Pass&) {});
+        tcounts[2 * blk + (win ? 1 : 0)] = (uint32_t)passes;
+        if (passes) atomicAdd(win ? &s_wpass : &s_pass, (uint32_t)passes);
+        if (listed) atomicAdd(&s_pair, (uint32_t)listed);
+        if (win && crops) atomicAdd(&s_wcrop, (uint32_t)crops);
     }
     __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = make_uint2(s_pass, s_pair);
+    if (threadIdx.x == 0) counts[blockIdx.x] = make_uint4(s_pass, s_pair, s_wpass, s_wcrop);
 }
 
-__global__ __launch_bounds__(SKIP3_TB) void k_pair_list(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
-                                                        const uint2* __restrict__ counts, const uint32_t* __restrict__ tcounts, int* __restrict__ desc) {
+__global__ __launch_bounds__(SKIP3_NT) void k_pair_list(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, uint32_t* __restrict__ words,
+                                                        const uint4* __restrict__ counts, const uint32_t* __restrict__ tcounts, int* __restrict__ desc,
+                                                        int* __restrict__ xdesc /* the windowed passes, Skip3XGeom::DESC words each */) {
     using G = Skip3Geom;
-    __shared__ uint32_t s_scan[SKIP3_TB];
+    using X = Skip3XGeom;
+    __shared__ uint2 s_scan[SKIP3_TB];
     __shared__ uint16_t s_run[SKIP3_TB * G::BLOCK];
-    const int tid = threadIdx.x, blk = blockIdx.x * SKIP3_TB + tid;
+    const int tid = threadIdx.x, t = tid & (SKIP3_TB - 1), blk = blockIdx.x * SKIP3_TB + t;
+    const bool win = tid >= SKIP3_TB;                         // (whole waves)
     const bool mine = blk * G::BLOCK < n;
-    skip3_stage_runs(bands, n, words[SK_EMPTY_RANGE] != 0, s_run);
+    skip3_stage_runs(bands, cols, n, words[SK_EMPTY_RANGE] != 0, s_run);
     // the passes in front of this workgroup (all of them, and the pairs: the last workgroup writes the counters)
-    uint32_t before = 0, pairs = 0;
-    for (int b = 0; b <= (int)blockIdx.x; ++b) { const uint2 c = counts[b]; if (b < (int)blockIdx.x) before += c.x; pairs += c.y; }
-    const int cnt = mine ? (int)tcounts[blk] : 0;
-    s_scan[tid] = (uint32_t)cnt;
+    uint32_t before = 0, wbefore = 0, pairs = 0, wcrops = 0;
+    for (int b = 0; b <= (int)blockIdx.x; ++b) {
+        const uint4 c = counts[b];
+        if (b < (int)blockIdx.x) { before += c.x; wbefore += c.z; }
+        pairs += c.y; wcrops += c.w;
+    }
+    const uint2 cnt = mine ? make_uint2(tcounts[2 * blk], tcounts[2 * blk + 1]) : make_uint2(0, 0);
+    if (!win) s_scan[t] = cnt;
     __syncthreads();
-    for (int d = 1; d < SKIP3_TB; d <<= 1) {          // inclusive scan
-        const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
+    for (int d = 1; d < SKIP3_TB; d <<= 1) {          // inclusive scan, by the first half
+        const uint2 v = !win && t >= d ? s_scan[t - d] : make_uint2(0, 0);
         __syncthreads();
-        s_scan[tid] += v;
+        if (!win) { s_scan[t].x += v.x; s_scan[t].y += v.y; }
         __syncthreads();
     }
-    int at = (int)(before + s_scan[tid]) - cnt;
-    if (mine)         // (the pass as its runs, in the first words of its descriptor: k_act3_fill makes the descriptor of it, a thread per pass)
-        skip3_walk(s_run, blk, at, [&](const int idx, const Skip3Pass& p) {
+    int at = win ? (int)(wbefore + s_scan[t].y - cnt.y) : (int)(before + s_scan[t].x - cnt.x), crops = 0;
+    // (the pass as its runs, in the first words of its descriptor: k_act3_fill makes the descriptor of it, a thread per pass)
+    if (mine && !win)
+        skip3_walk<G>(s_run, t, blk, at, crops, [&](const int idx, const Skip3Pass& p) {
             *reinterpret_cast<int4*>(desc + (size_t)idx * G::DESC) = make_int4(p.gp0[0], p.len[0], p.gp0[1], p.runs > 1 ? p.len[1] : 0);
         });
+    if (mine && win && cols)
+        skip3_walk<X>(s_run, t, blk, at, crops, [&](const int idx, const Skip3Pass& p) {
+            *reinterpret_cast<int4*>(xdesc + (size_t)idx * X::DESC) = make_int4(p.gp0[0], p.len[0], p.gp0[1], p.runs > 1 ? p.len[1] : 0);
+        });
     if (blockIdx.x == gridDim.x - 1 && tid == SKIP3_TB - 1) {
-        const uint32_t listed = before + s_scan[tid];
+        const uint32_t listed = before + s_scan[t].x, wlisted = wbefore + s_scan[t].y;
         const long long dense = ((long long)n * (G::PAIRS * 10) + 63) / 64;      // the dense form's passes: 64 of the crop's 100 tiles each
         words[SK3_PAIRS] = (uint32_t)(n * G::PAIRS); words[SK3_LISTED] = pairs; words[SK3_PASSES] = listed; words[SK3_FILLED] = 0;
-        words[SK3_USE] = skip3_use_list(listed, dense) ? 1u : 0u;
+        words[SK3X_PASSES] = wlisted; words[SK3X_CROPS] = wcrops; words[SK3X_CTR] = 0;
+        // (a windowed pass is counted as a full-width one: 117.6 against 116.2 ns under a kernel trace, profiles/conv3_windowed.txt)
+        words[SK3_USE] = skip3_use_list((long long)listed + wlisted, dense) ? 1u : 0u;
     }
 }
 
@@ -394,14 +425,20 @@ __global__ __launch_bounds__(FC1L_TB) void k_fc1_list(const int2* __restrict__ b
 // <- the empty crop's (a pair is 10 x 128 floats).  Nothing to do when the dense form runs.  (n * 16 threads, fewer than 3 n passes.)  One add to
 // the counter per workgroup: an add per crop is 25600 of them on one word, and they took longer than the copy
 static constexpr int SKIP3_FC = 16;
-__global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ bands, const int n, uint32_t* __restrict__ words,
+// cols (null: no crop has a window): the windowed passes' descriptors and row sources as well (xdesc, xrows), and of every LISTED pair of a crop
+// with a window the pooled columns outside it <- the empty crop's: the windowed kernel does not write them, and fc1 -- listed or not -- reads
+// whole pairs.  These are not counted: SK3_FILLED is the row rule's
+__global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, uint32_t* __restrict__ words,
                                                    const uint4* __restrict__ act3e, uint4* __restrict__ act3, int* __restrict__ desc,
                                                    uint32_t* __restrict__ rows /* Skip3Reach::WORDS per pass */,
+                                                   int* __restrict__ xdesc, uint32_t* __restrict__ xrows,
                                                    const long long alloc_rows /* V3 rows in front of the back image */, const int direct,
                                                    const int copy /* 0: the listed fc1 runs and reads no unlisted pair -- they are counted, not copied */) {
     using G = Skip3Geom;
     constexpr int PQ = 10 * 128 * 4 / 16;             // 16-byte units per pair
-    static_assert(Skip3Geom::BLOCK_PASSES * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass: 256 threads per SKIP3_FC crops");
+    using X = Skip3XGeom;
+    constexpr int CQ = 128 * 4 / 16;                  // 16-byte units per pooled column of a pair
+    static_assert((Skip3Geom::BLOCK_PASSES + X::BLOCK_PASSES) * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass of either list: 256 threads per SKIP3_FC crops");
     __shared__ uint32_t s_filled;
     const int lane = threadIdx.x & 63;
     if (!words[SK3_USE]) return;
@@ -409,7 +446,30 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
     __syncthreads();
     const bool all = words[SK_EMPTY_RANGE] != 0;
     const int gid = blockIdx.x * 256 + threadIdx.x;
-    if (gid < (int)words[SK3_PASSES]) {
+    const int n_full = (int)words[SK3_PASSES], n_win = cols ? (int)words[SK3X_PASSES] : 0;
+    const SkipRows every{0, SkipGeom::V3_ROWS - 1};
+    const bool from_v3 = all || !direct;
+    if (gid >= n_full && gid - n_full < n_win) {          // a windowed pass: the same, with its crops' windows
+        int4* dst = reinterpret_cast<int4*>(xdesc + (size_t)(gid - n_full) * X::DESC);
+        const int4 r = dst[0];
+        Skip3Pass p{};
+        p.runs = r.w ? 2 : 1; p.n = r.y + r.w;
+        p.gp0[0] = r.x; p.len[0] = r.y; p.gp0[1] = r.z; p.len[1] = r.w;
+        const int ca = r.x / X::PAIRS, cb = (r.w ? r.z : r.x) / X::PAIRS;
+        const int2 xa = cols[ca], xb = cols[cb];
+        const int t0a = skip3_window({xa.x, xa.y}, all), t0b = skip3_window({xb.x, xb.y}, all);
+        int d[X::DESC];
+        skip3_describe<X>(p, d, t0a, t0b);
+#pragma unroll
+        for (int k = 0; k < X::DESC / 4; ++k) dst[k] = make_int4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+        const int2 ba = bands[ca], bb = bands[cb];
+        unsigned w[Skip3Reach::WORDS];
+        skip3_row_words<X>(p, from_v3 ? every : skip_rows({ba.x, ba.y}), from_v3 ? every : skip_rows({bb.x, bb.y}), alloc_rows, w, t0a, t0b);
+        uint4* wd = reinterpret_cast<uint4*>(xrows + (size_t)(gid - n_full) * Skip3Reach::WORDS);
+#pragma unroll
+        for (int k = 0; k < Skip3Reach::WORDS / 4; ++k) wd[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    }
+    if (gid < n_full) {
         int4* dst = reinterpret_cast<int4*>(desc + (size_t)gid * G::DESC);
         const int4 r = dst[0];
         Skip3Pass p{};
@@ -420,8 +480,6 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
 #pragma unroll
         for (int k = 0; k < G::DESC / 4; ++k) dst[k] = make_int4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
         // where its rows come from: the own rows of its crops from V3, the others from the image -- or all of them from V3, where the copy is kept
-        const SkipRows every{0, SkipGeom::V3_ROWS - 1};
-        const bool from_v3 = all || !direct;
         const int2 ba = bands[r.x / G::PAIRS], bb = bands[(r.w ? r.z : r.x) / G::PAIRS];
         unsigned w[Skip3Reach::WORDS];
         skip3_row_words(p, from_v3 ? every : skip_rows({ba.x, ba.y}), from_v3 ? every : skip_rows({bb.x, bb.y}), alloc_rows, w);
@@ -435,8 +493,19 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
         if (crop >= n) break;
         const int2 b = bands[crop];
         const SkipPairs r = all ? SkipPairs{0, G::PAIRS - 1} : skip3_pairs({b.x, b.y});
+        const int2 c = cols ? cols[crop] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
+        const int t0 = skip3_window({c.x, c.y}, all);
         for (int q = 0; q < G::PAIRS; ++q) {
-            if (q >= r.lo && q <= r.hi) continue;
+            if (q >= r.lo && q <= r.hi) {
+                if (t0 >= 0) {        // the pooled columns in front of the window's 2 WT3 and behind them
+                    constexpr int OUT = (10 - 2 * X::WT3) * CQ;
+                    for (int i = lane; i < OUT; i += 64) {
+                        const int u = i < 2 * t0 * CQ ? i : i + 2 * X::WT3 * CQ;
+                        act3[((size_t)crop * G::PAIRS + q) * PQ + u] = act3e[q * PQ + u];
+                    }
+                }
+                continue;
+            }
             ++filled;
             if (!copy) continue;
 #pragma unroll

@@ -12,10 +12,14 @@ enum : int {
     SK_LEN = 2,              // aligned passes the row rule lists for the last call: the full-width list's length where no crop has a window
     SK_NPASS = 3,            // passes of the last call's batch
     SK_FILLED = 4,           // V3 rows outside those passes: taken from the empty crop's image instead of being computed (copied by k_v3_fill or read in place)
+    // the windowed listed conv3 (cnn_skip3.h: skip3_window); all zero where no crop can have a window of conv3 tiles
+    SK3X_CROPS = 5,          // crops of the last call whose listed pairs went into windowed passes
+    SK3X_PASSES = 6,         // windowed listed passes of the last call: the length of the windowed instance's list
+    SK3X_CTR = 7,            // the windowed instance's ticket counter (zeroed by k_pair_list)
     // the listed conv3 and the listed fc1 (cnn_skip3.h)
     SK3_PAIRS = 8,           // row pairs of the last call's batch
     SK3_LISTED = 9,          // row pairs listed
-    SK3_PASSES = 10,         // listed passes
+    SK3_PASSES = 10,         // listed full-width passes (all listed passes, where no crop can have a window)
     SK3_FILLED = 11,         // act3 row pairs filled from the empty crop's
     SK3_USE = 12,            // non-zero: the listed form of k_conv5_wpair runs, zero: the dense one
     SK3_EMPTY_CTR = 13,      // the pass counter of the run that made the empty crop's act3
@@ -31,6 +35,6 @@ enum : int {
     SKX_V2_MADE = 31,        // ... and how many of them the producers made: the others are background rows.  Both 0 where background rows are made
     SK_WORDS = 32
 };
-static_assert(SK_FILLED < SK3_PAIRS && SK3_LAST < SKX_CROPS && SKX_V2_MADE < SK_WORDS, "no word twice, the last one inside the table");
+static_assert(SK_FILLED < SK3X_CROPS && SK3X_CTR < SK3_PAIRS && SK3_LAST < SKX_CROPS && SKX_V2_MADE < SK_WORDS, "no word twice, the last one inside the table");
 
 }  // namespace trexhip
