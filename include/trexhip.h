@@ -373,7 +373,12 @@ int trexhip_prefilter_device(trexhip_ctx* ctx, const trexhip_prefilter_params* p
  *                           of SplitBlob::split's result (:204-221); the rest is returned sorted by (num_pixels, blob_id) descending
  *                           and shifted by -bounds().pos() (:166-172), which the caller does on the fetched table.
  * Needs a fetched batch (n_blobs = total_blobs).  Three size classes by LDS need (2048 / 16384 / 61440 pixels per blob); blobs with
- * more than 61440 pixels or 2048 lines (or 4096 lines after thresholding) report status 2 and no threshold. */
+ * more than 61440 pixels or 2048 lines (or, at a threshold the search reaches, more lines after thresholding than their class holds:
+ * 1024 / 2048 / 4096) report status 2 and no threshold.
+ * cm_per_pixel: the sizes compared here are (float)n_pixels * sqcm with sqcm = (float)(cm_per_pixel * cm_per_pixel) of the context's
+ * double.  The reference holds cm_per_pixel as a float and squares it in float; for values such as 0.37, 0.1 or 0.0173 the two differ
+ * by one ulp unless the double handed to the context is itself a widened float ((double)(float)cm), and then a blob whose size lies on
+ * the edge of a size range is decided differently.  Pass a widened float where the reference's decisions have to be met exactly. */
 typedef struct trexhip_split_params {
     int32_t track_threshold;                 /* core/default_config.cpp track_threshold            */
     int32_t track_posture_threshold;

@@ -37,9 +37,10 @@ def size_class(n_pixels, ranges, cm_per_pixel=1.0):
     return 1 if v < min(a for a, _ in ranges) else 2
 
 
-def assert_per_blob_equal(det, sub, bg, thr, method, ranges=()):
+def assert_per_blob_equal(det, sub, bg, thr, method, ranges=(), cm_per_pixel=1.0, connectivity=8):
     """det, sub: one frame's detect and pass-2 FrameResult after rethreshold_per_blob; thr: the frame's share of the thresholds.  Every detect blob's
-    sub-blobs are oracle.threshold_blob's of its own lines and pixels: matched by bid, then lines, pixels and every field that describes the blob"""
+    sub-blobs are oracle.threshold_blob's of its own lines and pixels: matched by bid, then lines, pixels and every field that describes the blob.
+    cm_per_pixel, connectivity: the context's detect settings, which the pass takes over"""
     assert sub.info["flags"] == 0 and det.info["flags"] == 0
     seen = 0
     for k, b in enumerate(det.blobs):
@@ -50,7 +51,7 @@ def assert_per_blob_equal(det, sub, bg, thr, method, ranges=()):
             continue
         rs = det.runs[b["run_begin"]:b["run_begin"] + b["n_runs"]]
         px = det.pixels[b["pix_begin"]:b["pix_begin"] + b["n_pixels"]]
-        ob, orr, opx = oracle.threshold_blob(rs, px, bg, method, int(thr[k]))
+        ob, orr, opx = oracle.threshold_blob(rs, px, bg, method, int(thr[k]), connectivity)
         assert sorted(mine["n_pixels"].tolist()) == sorted(ob["n_pixels"].tolist())
         assert sorted(mine["bid"].tolist()) == sorted(ob["bid"].tolist())
         assert len(set(ob["bid"].tolist())) == len(ob), "two sub-blobs of one parent share a bid: the scene cannot match them"
@@ -62,5 +63,5 @@ def assert_per_blob_equal(det, sub, bg, thr, method, ranges=()):
             for name in ob.dtype.names:
                 if name not in OWN_FIELDS:
                     assert m[name] == o[name], (k, name)
-            assert m["flags"] == size_class(int(m["n_pixels"]), ranges), (k, int(m["n_pixels"]))
+            assert m["flags"] == size_class(int(m["n_pixels"]), ranges, cm_per_pixel), (k, int(m["n_pixels"]))
     assert seen == len(sub.blobs)                                       # no sub-blob without a parent of this frame

@@ -3,37 +3,12 @@ SplitBlob::split (tracking/SplitBlob.cpp:419-800): same threshold per merged blo
 trexhip_rethreshold_per_blob_device at those thresholds = pixel::threshold_blob at them."""
 import numpy as np
 import pytest
-import torch
 from oracle import oracle
 from trex_amd import capi
 from split_cases import merged_scene
+from split_device import device_search
 
 pytestmark = pytest.mark.gpu
-
-
-def device_search(frames, bg, presumed_of, method=1, ranges=(), detect_threshold=15, detect_kw=None, **kw):
-    n, H, W = frames.shape
-    dkw = dict(threshold=detect_threshold)
-    dkw.update(detect_kw or {})
-    seg = capi.Segmenter(capi.default_params(W, H, max_batch=n, max_blobs=4096, **dkw))
-    seg.set_background(bg)
-    d = torch.from_numpy(frames).cuda()
-    seg.segment_device(d.data_ptr(), n)
-    det = seg.fetch()
-    nb = sum(len(r.blobs) for r in det)
-    presumed = np.zeros(nb, np.int32)                        # pooled order: frame f's blobs start at info["blob_begin"]
-    for r in det:
-        presumed[r.info["blob_begin"]:r.info["blob_begin"] + len(r.blobs)] = presumed_of(r)
-    d_pres = torch.from_numpy(presumed).cuda()
-    d_thr = torch.full((max(nb, 1),), -7, dtype=torch.int32, device="cuda")
-    d_info = torch.zeros(max(nb, 1) * capi.SPLIT_INFO_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-    seg.split_search_device(d_pres.data_ptr(), nb, d_thr.data_ptr(), d_info.data_ptr(), method=method, size_ranges=ranges, **kw)
-    seg.rethreshold_per_blob(d_thr.data_ptr(), method, ranges)
-    sub = seg.fetch(rethreshold=True)
-    thr = d_thr.cpu().numpy()[:nb]
-    info = d_info.cpu().numpy().view(capi.SPLIT_INFO_DTYPE)[:nb]
-    seg.close()
-    return det, presumed, thr, info, sub
 
 
 @pytest.mark.parametrize("algorithm", [1, 2])
