@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 24
+#define TREXHIP_ABI_VERSION 25
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -1023,6 +1023,25 @@ int trexhip_categorize(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, int32_
  * TREXHIP_OK and writes nothing but *skipped = 0.  Needs no category weights.  Ordered on the context's stream; the call synchronises. */
 int trexhip_tracklet_labels_device(trexhip_ctx* ctx, const int32_t* d_labels, const int32_t* d_tracklet, int32_t n, int32_t n_tracklets, int32_t categories,
                                    uint32_t* d_counts, uint32_t* d_rows, int32_t* d_label, float* d_share /* or NULL */, uint32_t* skipped /* host, or NULL */);
+/* Every tracklet's crops reduced to its median image: the last step of the output_tracklet_images export, hist_utils::init / addImage
+ * (Application/src/tracker/ui/Export.cpp:78-154) driven by the loop over a tracklet's fixed-size images (Export.cpp:1287-1364), for every
+ * tracklet in one call and on the crop pool the three crop calls write.
+ *   d_crops [n][height][width][channels]   uint8.  1 channel is taken as it is, 3 channels (B, G, R) go through cv::COLOR_BGR2GRAY (:1320-1327):
+ *                                (B*1868 + G*9617 + R*4899 + 8192) >> 14
+ *   d_tracklet[n]                a row's tracklet, 0..n_tracklets-1, or -1 = the row belongs to none.  Rows may stand in any order and
+ *                                tracklets may interleave
+ *   d_median[T][height][width]   gray: per pixel the value addImage leaves after the tracklet's last image (:104-110) -- the smallest i whose
+ *                                cumulative count exceeds rows / 2 = sorted[rows / 2], the upper median at an even count.  A tracklet without
+ *                                rows gets the all-zero image init leaves (:145-153); one row gives that image (its gray) back
+ *   d_rows[T]                    uint32: rows of each tracklet.  The reference stores a median only where this is > 1 (:1355): the caller's rule
+ * Integer arithmetic only: two calls, or any permutation of the rows, give the same bytes.  A checked pass runs before any result is written:
+ * an id outside [-1, n_tracklets) is TREXHIP_E_INVALID; a tracklet with more than 32767 rows is TREXHIP_E_UNSUPPORTED (the reference's bins
+ * are `short`, :85-89; more is undefined there) and trexhip_last_error() names the tracklet and its count; nothing is written in either case.
+ * 8 <= width, height <= 256 and channels 1 or 3, TREXHIP_E_UNSUPPORTED otherwise; 1 <= n_tracklets <= 2^24, 0 <= n <= 2^24.  n = 0 returns
+ * TREXHIP_OK with d_rows and d_median zeroed.  d_crops and d_median need no alignment (dword loads and stores where both bases and the crop
+ * size allow, bytes otherwise; same result).  Ordered on the context's stream; synchronises only to read the checked pass's flag. */
+int trexhip_tracklet_medians_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n, int32_t width, int32_t height, int32_t channels,
+                                    const int32_t* d_tracklet, int32_t n_tracklets, uint8_t* d_median, uint32_t* d_rows);
 
 #ifdef __cplusplus
 }

@@ -210,7 +210,7 @@ SYMBOLS = [
     "trexhip_default_prefilter_params", "trexhip_prefilter_device",
     "trexhip_default_vf_params", "trexhip_visual_field_device",
     "trexhip_categorize_load_weights", "trexhip_categorize_info", "trexhip_categorize_blob_bytes", "trexhip_categorize_device", "trexhip_categorize",
-    "trexhip_tracklet_labels_device",
+    "trexhip_tracklet_labels_device", "trexhip_tracklet_medians_device",
 ]
 
 
@@ -342,6 +342,7 @@ def lib():
         L.trexhip_categorize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.trexhip_tracklet_labels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.POINTER(C.c_uint32)]
+        L.trexhip_tracklet_medians_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -852,6 +853,29 @@ class Segmenter:
                                       np.zeros((T, Cn), np.float32) if share else None, 0)
             return TrackletLabels(self.copy_to_host(ptrs[2], (T, Cn), np.uint32), self.copy_to_host(ptrs[3], (T,), np.uint32),
                                   self.copy_to_host(ptrs[4], (T,), np.int32), self.copy_to_host(ptrs[5], (T, Cn), np.float32) if share else None, skipped)
+        finally:
+            for d in ptrs:
+                self.device_free(d)
+
+    def tracklet_medians_device(self, d_crops_ptr, n, width, height, channels, d_tracklet_ptr, n_tracklets, d_median_ptr, d_rows_ptr):
+        """hist_utils::addImage's final image for every tracklet of a crop pool in HBM (trexhip_tracklet_medians_device): uint8 medians
+        [n_tracklets][height][width] at d_median_ptr, uint32 row counts [n_tracklets] at d_rows_ptr; synchronises only for the checked pass"""
+        _check(lib().trexhip_tracklet_medians_device(self._h, C.c_void_p(d_crops_ptr or 0), n, width, height, channels, C.c_void_p(d_tracklet_ptr or 0),
+                                                     n_tracklets, C.c_void_p(d_median_ptr or 0), C.c_void_p(d_rows_ptr or 0)))
+
+    def tracklet_medians(self, d_crops_ptr, n, width, height, channels, d_tracklet_ptr, n_tracklets):
+        """the same with the results fetched: crops uint8 [n][height][width][channels] and int32 tracklet ids [n] (-1 = none) on the device ->
+        (medians uint8 (n_tracklets, height, width), rows uint32 (n_tracklets,)) on the host.  The reference keeps a median where rows > 1."""
+        T = int(n_tracklets)
+        if not 1 <= T <= 1 << 24 or not (8 <= width <= 256 and 8 <= height <= 256):
+            self.tracklet_medians_device(d_crops_ptr, n, width, height, channels, d_tracklet_ptr, T, 0, 0)      # the library says what is wrong
+            raise ValueError("trexhip_tracklet_medians_device accepted arguments outside its ranges")
+        ptrs = []
+        try:
+            for b in (T * width * height, T * 4):
+                ptrs.append(self.device_alloc(b))
+            self.tracklet_medians_device(d_crops_ptr, n, width, height, channels, d_tracklet_ptr, T, ptrs[0], ptrs[1])
+            return self.copy_to_host(ptrs[0], (T, height, width), np.uint8), self.copy_to_host(ptrs[1], (T,), np.uint32)
         finally:
             for d in ptrs:
                 self.device_free(d)

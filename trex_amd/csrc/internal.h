@@ -168,6 +168,7 @@ struct trexhip_ctx {
     void* net = nullptr;                // trexhip::Net (cnn.hip)
     void* cat = nullptr;                // trexhip::Net of the category network (cnn_arch.hip), beside the identity network: neither load touches the other
     trexhip::Scratch vote;              // flag, skipped count of trexhip_tracklet_labels_device (categorize.hip)
+    trexhip::Scratch med;               // flags, counts, offsets and row list of trexhip_tracklet_medians_device (tracklet_median.hip)
     trexhip::Pass2 pass2;
     int cnn_mode = TREXHIP_CNN_FP16X3;  // TREXHIP_CNN_*: fp32-class arithmetic on the fp16 matrix cores, range-guarded
 
