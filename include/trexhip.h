@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 25
+#define TREXHIP_ABI_VERSION 26
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -211,6 +211,23 @@ int trexhip_copy_to_device(trexhip_ctx* ctx, void* device_dst, const void* host_
  * core/default_config.cpp:1113) leave the device as ONE kernel that writes the filled parts of all five tables into the pinned mirrors + one
  * stream synchronize; larger batches as two rounds of DMA copies (frame table and totals, then the tables at their exact sizes). */
 int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out);
+/* trexhip_fetch in two halves, for a caller that needs the COUNTS on the host to go on (crops, posture and the identity table read the device
+ * tables) and the blob / run / pixel tables only later (ABI 26).
+ *   trexhip_fetch_begin  does what trexhip_fetch does until the frame table and the totals are on the host (the same checks, return codes and
+ *                        messages), queues the copies of the three pooled tables on the context's stream, records an event behind them and
+ *                        returns without waiting: `out` holds the counts and the pointers, out->frames is valid, the memory behind
+ *                        out->blobs / runs / pixels is NOT until trexhip_fetch_wait has returned.  A batch of up to 16 frames and an empty batch
+ *                        are served as by trexhip_fetch: nothing is pending afterwards.
+ *   trexhip_fetch_wait   blocks until those copies have arrived; returns at once with nothing pending, so it may be called twice.
+ * Every call that overwrites the device tables or the pinned mirrors (the segment calls, trexhip_load_frames_v6_device, trexhip_fetch[_begin],
+ * trexhip_destroy) or reads the mirrors on the host (trexhip_posture_device, trexhip_posture_auto_device, trexhip_split_search_device) waits
+ * first itself: a caller that forgets trexhip_fetch_wait gets the data of a plain fetch, never a race inside the library -- only its own reads of
+ * out->blobs / runs / pixels are its own business.  trexhip_set_stream does not wait for pending copies: they stay on the stream they were
+ * queued on (fetch_begin synchronised that stream in front of them), and work queued on the new stream is not ordered behind them.
+ * (Two segment calls on the same frames give the same blobs but not the same pooled ORDER: a frame reserves its share of the pools when its
+ * labelling ends.  The frame table's *_begin words are those of the segment call, whichever fetch reads them.) */
+int trexhip_fetch_begin(trexhip_ctx* ctx, trexhip_batch_result* out);
+int trexhip_fetch_wait(trexhip_ctx* ctx);
 int trexhip_device_view_get(trexhip_ctx* ctx, trexhip_device_view* out);
 int trexhip_synchronize(trexhip_ctx* ctx);
 
@@ -553,6 +570,31 @@ int trexhip_set_identity_precision(trexhip_ctx* ctx, int32_t mode);
  * (visual_recognition_torch.py:290-352): crops are uint8 NHWC [n][H][W][C] of the loaded network (trexhip_network_image_size,
  * trexhip_network_channels; values 0..255, no scaling), probs is [n][classes] float32 softmax rows.  d_logits may be NULL. */
 int trexhip_identify_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n, float* d_probs, float* d_logits);
+/* The part of the next trexhip_identify_device(ctx, d_crops, n, ...) that needs nothing but the crops' bytes and the loaded network, queued
+ * now on the context's stream: which passes, row pairs and fc1 rows the crops' blobs reach, and the background rows of the others (k_crop_bands
+ * ... k_v3_fill and k_act3_fill).  For a caller that drives two contexts and lets only one network run at a time: issue this BEFORE
+ * waiting for the other context's network, so that these small latency-bound kernels run beside its tail and not behind it.  No reference
+ * counterpart (predict_numpy is one call).
+ *   - The next trexhip_identify_device on the context takes the record this call leaves, whatever its arguments: it skips those launches if
+ *     crops pointer, n, precision mode, stream and the loaded weights / batch buffers are the ones prepared for, and runs the whole chain as ever
+ *     otherwise.  Its results are bit-identical either way.  The crops' bytes must not change between the two calls.
+ *   - trexhip_load_weights, trexhip_set_identity_precision, a larger batch than the buffers hold, and trexhip_destroy drop the record; a second
+ *     prepare call replaces it.
+ *   - TREXHIP_OK without launching anything where the identify call's chain has no such part: another precision mode than TREXHIP_CNN_FP16X3,
+ *     another size than 80 x 80 or another version than V118_3, a batch that takes another convolution chain (fewer than 3200 crops, 3 channels,
+ *     unaligned crops), and a batch small enough for the captured-graph path (a captured chain is replayed whole).
+ *   - With the stage timers on, the prepared launches are bracketed as TREXHIP_STAGE_PREPARE and are no longer inside the CONV2 / CONV3 brackets
+ *     of the identify call that uses them.
+ *   - Like an identify call it sizes the batch buffers for n: a prepare with a larger n than any call before reallocates them (and drops the
+ *     captured chains that point into them).
+ *   - The prepared kernels write the words the skip statistics read (trexhip_identify_skip_stats, _skipx_, _skip3_, _skip3x_, _fc1_ and
+ *     _bgrow_stats): from the prepare call on these report the PREPARED batch, not the last identify call's.  Read a call's statistics
+ *     before preparing the next one.
+ * trexhip_identify_prepare_stats: records made by prepare calls on this context so far, and how many of them an identify call found and used
+ * (a caller checks with it that its two calls do match: a mismatch costs the overlap in silence, never a bit).  Either pointer may be NULL.
+ * (ABI 26) */
+int trexhip_identify_prepare_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n);
+int trexhip_identify_prepare_stats(trexhip_ctx* ctx, uint32_t* records, uint32_t* hits);
 int trexhip_identify(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, float* probs);
 /* What the fp16 range guard of the LAST identify call on this context did (waits for the context's stream): *rerun_crops = crops
  * whose layer stack was re-run by the BF16X6 kernels (0 = none; the whole batch when the flag came from a kernel that does not
@@ -673,7 +715,9 @@ enum { TREXHIP_STAGE_ROWS = 0, TREXHIP_STAGE_SEGMENT_ALL = 1, TREXHIP_STAGE_CONV
        TREXHIP_STAGE_CNN_ALL = 4, TREXHIP_STAGE_CROPS = 5, TREXHIP_STAGE_POSTURE = 6,
        /* host-pointer entry points (trexhip_segment, trexhip_segment_color): per FRAME, always collected -- host milliseconds spent copying
         * pageable tiles into the pinned ring, and DMA milliseconds (HIP events on the copy stream).  The two legs overlap each other. */
-       TREXHIP_STAGE_UPLOAD_COPY = 8, TREXHIP_STAGE_UPLOAD_DMA = 9, TREXHIP_STAGE_COUNT = 10 };
+       TREXHIP_STAGE_UPLOAD_COPY = 8, TREXHIP_STAGE_UPLOAD_DMA = 9,
+       /* the launches of trexhip_identify_prepare_device (ABI 26); an unprepared identify call keeps them inside CONV2 / CONV3 */
+       TREXHIP_STAGE_PREPARE = 10, TREXHIP_STAGE_COUNT = 11 };
 int trexhip_profile_enable(trexhip_ctx* ctx, int32_t on);
 int trexhip_profile_read(trexhip_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
 int trexhip_profile_reset(trexhip_ctx* ctx);

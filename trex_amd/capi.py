@@ -30,6 +30,7 @@ assert BLOB_DTYPE.itemsize == 104 and RUN_DTYPE.itemsize == 8 and INFO_DTYPE.ite
 CNN_FP32, CNN_BF16X6, CNN_BF16X3, CNN_FP16X3 = 0, 1, 2, 3
 STAGE_ROWS, STAGE_SEGMENT_ALL, STAGE_CONV2, STAGE_CONV3, STAGE_CNN_ALL, STAGE_CROPS, STAGE_POSTURE = 0, 1, 2, 3, 4, 5, 6
 STAGE_UPLOAD_COPY, STAGE_UPLOAD_DMA = 8, 9       # host-input legs (per frame): pageable -> pinned copy (host ms), DMA (event ms)
+STAGE_PREPARE = 10                               # the launches of identify_prepare_device (outside CONV2 / CONV3 where a call was prepared)
 
 
 class Params(C.Structure):
@@ -211,6 +212,7 @@ SYMBOLS = [
     "trexhip_default_vf_params", "trexhip_visual_field_device",
     "trexhip_categorize_load_weights", "trexhip_categorize_info", "trexhip_categorize_blob_bytes", "trexhip_categorize_device", "trexhip_categorize",
     "trexhip_tracklet_labels_device", "trexhip_tracklet_medians_device",
+    "trexhip_identify_prepare_device", "trexhip_fetch_begin", "trexhip_fetch_wait", "trexhip_identify_prepare_stats",
 ]
 
 
@@ -243,6 +245,8 @@ def lib():
         L.trexhip_rethreshold_per_blob_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.trexhip_fetch_rethreshold.argtypes = [C.c_void_p, C.POINTER(BatchResult)]
         L.trexhip_fetch.argtypes = [C.c_void_p, C.POINTER(BatchResult)]
+        L.trexhip_fetch_begin.argtypes = [C.c_void_p, C.POINTER(BatchResult)]
+        L.trexhip_fetch_wait.argtypes = [C.c_void_p]
         L.trexhip_device_view_get.argtypes = [C.c_void_p, C.POINTER(DeviceView)]
         L.trexhip_synchronize.argtypes = [C.c_void_p]
         L.trexhip_profile_enable.argtypes = [C.c_void_p, C.c_int32]
@@ -289,6 +293,8 @@ def lib():
         L.trexhip_comm_count_ranks.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.trexhip_set_identity_precision.argtypes = [C.c_void_p, C.c_int32]
         L.trexhip_identify_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.trexhip_identify_prepare_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.trexhip_identify_prepare_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.trexhip_identify_guard_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify_skip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -522,6 +528,20 @@ class Segmenter:
             self.last_capacity_error = lib().trexhip_last_error().decode()
         return r
 
+    def fetch_begin_raw(self):
+        """trexhip_fetch_begin: the BatchResult with the counts and the frame table; the blob / run / pixel tables behind its pointers are on
+        their way and valid once fetch_wait() has returned.  The return code (0, or -3 for a batch over capacity) is kept in last_fetch_rc."""
+        r = BatchResult()
+        rc = self.last_fetch_rc = lib().trexhip_fetch_begin(self._h, C.byref(r))
+        if rc != 0 and rc != -3:
+            _check(rc)
+        if rc == -3:
+            self.last_capacity_error = lib().trexhip_last_error().decode()
+        return r
+
+    def fetch_wait(self):
+        _check(lib().trexhip_fetch_wait(self._h))
+
     def fetch(self, copy=True, rethreshold=False):
         r = BatchResult()
         rc = (lib().trexhip_fetch_rethreshold if rethreshold else lib().trexhip_fetch)(self._h, C.byref(r))
@@ -727,6 +747,17 @@ class Segmenter:
     def identify_device(self, d_crops_ptr, n, d_probs_ptr, d_logits_ptr=None):
         _check(lib().trexhip_identify_device(self._h, C.c_void_p(d_crops_ptr), n, C.c_void_p(d_probs_ptr),
                                              C.c_void_p(d_logits_ptr) if d_logits_ptr else None))
+
+    def identify_prepare_device(self, d_crops_ptr, n):
+        """queues the part of the next identify_device(d_crops_ptr, n, ...) that reads only the crops and the loaded network (the role-split
+        chain's lists and background fills); that call skips it if its arguments match, and runs everything otherwise.  Same bits either way."""
+        _check(lib().trexhip_identify_prepare_device(self._h, C.c_void_p(d_crops_ptr), n))
+
+    def prepare_stats(self):
+        """(records prepare calls made on this context, records an identify call found and used)"""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        _check(lib().trexhip_identify_prepare_stats(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     # ---- the training loader on the device ----
     def device_alloc(self, nbytes):

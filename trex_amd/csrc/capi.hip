@@ -91,8 +91,15 @@ static int fetch_info(trexhip_ctx* ctx, BlobTables& t) {
 }
 
 // the rest of a fetch, once h_info and h_totals are in: clamp the totals to the pools (frames that overflowed the pool reserved nothing valid),
-// copy the filled parts of the three tables unless a kernel has already exported them, wait, and fill the caller's result
-static int fetch_tables(trexhip_ctx* ctx, BlobTables& t, bool copy, trexhip_batch_result* out) {
+// copy the filled parts of the three tables unless a kernel has already exported them, wait -- or (begin) record the context's event behind the
+// copies and leave the wait to fetch_wait --, and fill the caller's result
+int fetch_wait(trexhip_ctx* ctx) {
+    if (!ctx->fetch_pending) return TREXHIP_OK;
+    ctx->fetch_pending = false;
+    TH_CHECK_HIP(hipEventSynchronize(ctx->fetch_ev));
+    return TREXHIP_OK;
+}
+static int fetch_tables(trexhip_ctx* ctx, BlobTables& t, bool copy, trexhip_batch_result* out, bool begin = false) {
     std::memset(out, 0, sizeof(*out));
     out->n_frames = t.valid_n;
     out->frames = t.h_info; out->blobs = t.h_blobs; out->runs = t.h_runs; out->pixels = t.h_pixels;
@@ -104,7 +111,13 @@ static int fetch_tables(trexhip_ctx* ctx, BlobTables& t, bool copy, trexhip_batc
         if (tb) TH_CHECK_HIP(hipMemcpyAsync(t.h_blobs, t.d_blobs, sizeof(trexhip_blob) * tb, hipMemcpyDeviceToHost, s));
         if (tr) TH_CHECK_HIP(hipMemcpyAsync(t.h_runs, t.d_runs, sizeof(trexhip_run) * tr, hipMemcpyDeviceToHost, s));
         if (tp) TH_CHECK_HIP(hipMemcpyAsync(t.h_pixels, t.d_pixels, (size_t)tp * ctx->pix_ch, hipMemcpyDeviceToHost, s));
-        TH_CHECK_HIP(hipStreamSynchronize(s));
+        if (begin) {
+            if (!ctx->fetch_ev) TH_CHECK_HIP(hipEventCreateWithFlags(&ctx->fetch_ev, hipEventDisableTiming));
+            TH_CHECK_HIP(hipEventRecord(ctx->fetch_ev, s));
+            ctx->fetch_stream = s;
+            ctx->fetch_pending = true;
+        }
+        else TH_CHECK_HIP(hipStreamSynchronize(s));
     }
     out->total_blobs = tb; out->total_runs = tr; out->total_pixels = tp;
     t.fetched = true;
@@ -245,7 +258,9 @@ int trexhip_create(const trexhip_params* p, trexhip_ctx** out) {
 void trexhip_destroy(trexhip_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->p.device);
+    (void)fetch_wait(ctx);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
+    if (ctx->fetch_ev) hipEventDestroy(ctx->fetch_ev);
     net_free(ctx);
     ctx->pass2.mem.free_all();
     upload_free(ctx);
@@ -320,7 +335,9 @@ int trexhip_update_params(trexhip_ctx* ctx, const trexhip_live_params* lp) {
 
 int trexhip_set_stream(trexhip_ctx* ctx, void* hip_stream) {
     if (!ctx) { set_error("null ctx"); return TREXHIP_E_INVALID; }
-    TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    // (with the table copies of trexhip_fetch_begin pending on the stream that is left -- fetch_begin synchronised it in front of them --, they
+    // stay there behind their event: trexhip_fetch_wait waits for them, not this call)
+    if (!(ctx->fetch_pending && ctx->fetch_stream == ctx->stream)) TH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     ctx->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->own_stream;
     return TREXHIP_OK;
 }
@@ -430,9 +447,11 @@ static int export_or_fetch_info(trexhip_ctx* ctx, bool by_kernel) {
 }  // namespace trexhip
 extern "C" {
 
-int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out) {
-    if (!ctx || !out) { set_error("trexhip_fetch: null argument"); return TREXHIP_E_INVALID; }
+// trexhip_fetch, or (begin) everything of it but the wait for the three table copies of a batch that k_export does not serve
+static int fetch_batch(trexhip_ctx* ctx, trexhip_batch_result* out, const char* who, const bool begin) {
+    if (!ctx || !out) { set_error(std::string(who) + ": null argument"); return TREXHIP_E_INVALID; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    if (const int rc = fetch_wait(ctx)) return rc;      // (copies still on their way write the mirrors this call fills)
     BlobTables& t = ctx->tables;
     const int n = t.valid_n;
     const bool by_kernel = n <= EXPORT_MAX_FRAMES;      // a few frames: one launch + one synchronize (k_export)
@@ -447,7 +466,7 @@ int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out) {
             if (rc1) return rc1;
         }
     }
-    int rc = fetch_tables(ctx, t, !by_kernel, out);
+    int rc = fetch_tables(ctx, t, !by_kernel, out, begin);
     if (rc || n == 0) return rc;
     for (int i = 0; i < n; ++i)
         if (t.h_info[i].flags & TREXHIP_FRAME_MALFORMED) {       // a loaded frame (trexhip_load_frames_v6_device) that broke a rule of pv_read.h
@@ -465,6 +484,13 @@ int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out) {
             rc = TREXHIP_E_CAPACITY;
         }
     return rc;
+}
+
+int trexhip_fetch(trexhip_ctx* ctx, trexhip_batch_result* out) { return fetch_batch(ctx, out, "trexhip_fetch", false); }
+int trexhip_fetch_begin(trexhip_ctx* ctx, trexhip_batch_result* out) { return fetch_batch(ctx, out, "trexhip_fetch_begin", true); }
+int trexhip_fetch_wait(trexhip_ctx* ctx) {
+    if (!ctx) { set_error("trexhip_fetch_wait: null ctx"); return TREXHIP_E_INVALID; }
+    return fetch_wait(ctx);
 }
 
 static int pass2_alloc(trexhip_ctx* ctx, const char* who) {

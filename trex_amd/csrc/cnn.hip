@@ -1333,6 +1333,7 @@ static int upload(Net* net, T** dst, float* inv, const ScaledImage& im) { *inv =
 static int make_empty_v3(trexhip_ctx* ctx, Net* net);
 // parse -> pack (cnn_weights.hip) -> upload
 int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
+    ctx->prepared.weights_loaded();      // whatever was prepared was prepared for the network that goes
     const int arch = blob_arch_id(blob, bytes);
     if (arch >= TREXHIP_NET_V100 && arch <= TREXHIP_NET_V200) return arch_load(ctx, blob, bytes);      // the other architectures: cnn_arch.hip
     WeightBlob wb;
@@ -1385,6 +1386,7 @@ int net_load(trexhip_ctx* ctx, const void* blob, size_t bytes) {
 static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
     if (n <= net->max_crops) return TREXHIP_OK;
     drop_graphs(net);                                      // the captured chains point into the buffers that are replaced here
+    ctx->prepared.batch_reallocated();                     // ... and so do the lists of a prepared call
     net->batch.free_all();
     net->h_probs = nullptr;
     net->max_crops = 0;
@@ -1591,7 +1593,14 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
 // The role-split chain's preparation (cnn_skip_kernels.h), in front of conv1+conv2: which passes, row pairs and fc1 rows the crops need, and the
 // V3 rows of the others; every decision stays on the device.  `direct`: the listed conv3 reads background rows from the image, the fill copies
 // only where the dense form runs
-static void launch_skip_prep(const Pass& f, const bool direct, const bool x3 /* conv3's listed pairs in two lists, windowed passes and full-width ones */) {
+struct PrepArgs { long long alloc_rows; bool direct, x3 /* conv3's listed pairs in two lists, windowed passes and full-width ones */; };
+static PrepArgs prep_args(const Net& net, const CnnPlan& p) {
+    // the back image lies behind the ALLOCATION's rows, whatever this call's n is
+    const long long alloc_rows = (long long)net.max_crops * SkipGeom::V3_ROWS;
+    const bool direct = p.v3_direct && skip3_direct_fits(alloc_rows);
+    return {alloc_rows, direct, p.skip3x && direct && skip3x_direct_fits(alloc_rows)};
+}
+static void launch_skip_prep(const Pass& f, const bool direct, const bool x3) {
     const Net& net = f.net;
     const CnnPlan& p = f.p;
     const int n = f.n, lb = ceil_div(p.conv2.items, SKIP_LB);
@@ -1611,19 +1620,41 @@ static void launch_skip_prep(const Pass& f, const bool direct, const bool x3 /* 
               reinterpret_cast<uint4*>(net.v3), (int)direct);
 }
 
-static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
-    const Net& net = *static_cast<Net*>(ctx->net);
+// The launches of a role-split pass that read nothing but the crops and the loaded network, stated once: PREP_LISTS in front of conv1+conv2,
+// PREP_ACT3 -- the listed passes' descriptors and row sources, and the other pairs' act3 -- in front of conv3, or both at once ahead of the pass
+// (trexhip_identify_prepare_device): k_act3_fill reads what the list kernels wrote and nothing of conv1+conv2's.  Which form of conv3 runs is the
+// device's word
+// (PREP_ACT3 alone is only ever launched behind the PREP_LISTS of the same pass: k_act3_fill turns the runs k_pair_list left in the descriptors
+// into descriptors IN PLACE, so a second fill without a list pass in between would read descriptors as runs)
+enum : int { PREP_LISTS = 1, PREP_ACT3 = 2 };
+static bool plan_prepares(const CnnPlan& p) { return p.chain == Chain::ROLE_SPLIT && p.skip; }
+static void launch_prep(const Pass& f, const int parts) {
+    const Net& net = f.net;
+    const CnnPlan& p = f.p;
+    if (!plan_prepares(p)) return;
+    const PrepArgs a = prep_args(net, p);
+    if (parts & PREP_LISTS) launch_skip_prep(f, a.direct, a.x3);
+    if ((parts & PREP_ACT3) && p.skip3)
+        K_ACT3_FILL(f.s, p.act3_fill.grid, net.skip_bands, a.x3 ? net.skipx_cols : nullptr, f.n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e),
+                    reinterpret_cast<uint4*>(net.act3), net.skip3_desc, net.skip3_rows, net.skip3x_desc, net.skip3x_rows, a.alloc_rows, (int)a.direct, (int)!p.fc1_listed);
+}
+
+static int set_cnn_attrs(trexhip_ctx* ctx) {
     if (!ctx->attr_cnn) {
         for (const LdsAttr& a : lds_attrs()) TH_CHECK_HIP(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes));
         ctx->attr_cnn = true;
     }
+    return TREXHIP_OK;
+}
+
+// prepared: launch_prep(f, PREP_LISTS | PREP_ACT3) for this very pass is queued on the stream already (cnn_prepared.h)
+static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits, const bool prepared = false) {
+    const Net& net = *static_cast<Net*>(ctx->net);
+    if (const int rc = set_cnn_attrs(ctx)) return rc;
     const CnnPlan p = cnn_plan(net.W, net.H, net.CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0, ctx->tune_conv_geom, n, ctx->n_cus);
     const Pass f{net, p, ctx->stream, ctx->cnn_mode, d_crops, n, d_probs, d_logits};
     hipStream_t s = f.s;
-    // the back image lies behind the ALLOCATION's rows, whatever this call's n is
-    const long long alloc_rows = (long long)net.max_crops * SkipGeom::V3_ROWS;
-    const bool direct = p.v3_direct && skip3_direct_fits(alloc_rows);
-    const bool x3 = p.skip3x && direct && skip3x_direct_fits(alloc_rows);
+    const bool x3 = prep_args(net, p).x3;
     // (the guard words in front of the plan start at zero: the plan's writer -- the last reader of all three -- hands them back zeroed; net_forward
     // clears them itself behind a pass that was not queued to its end)
     stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
@@ -1636,7 +1667,7 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         stage_begin(ctx, TREXHIP_STAGE_CONV2);
         switch (p.chain) {
         case Chain::ROLE_SPLIT:
-            if (p.skip) launch_skip_prep(f, direct, x3);
+            if (!prepared) launch_prep(f, PREP_LISTS);
             // (an instance whose list is empty returns at once)
             if (p.skipx)
                 K_CONV12_RSX(s, p.conv2.grid, d_crops, net.w1h, net.b1, net.inv1h, net.w2w, net.b2, net.v3, net.inv2w, net.ovf(OVF_RANGE), n, net.d_skip + SKX_CTR,
@@ -1659,9 +1690,8 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
         stage_end(ctx, TREXHIP_STAGE_CONV2);
         stage_begin(ctx, TREXHIP_STAGE_CONV3);
         if (pre) {
-            if (p.skip3) {     // the listed passes' descriptors and row sources, and the other pairs' act3; which form of the kernel runs is the device's word
-                K_ACT3_FILL(s, p.act3_fill.grid, net.skip_bands, x3 ? net.skipx_cols : nullptr, n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e),
-                            reinterpret_cast<uint4*>(net.act3), net.skip3_desc, net.skip3_rows, net.skip3x_desc, net.skip3x_rows, alloc_rows, (int)direct, (int)!p.fc1_listed);
+            if (p.skip3) {
+                if (!prepared) launch_prep(f, PREP_ACT3);
                 // (an instance whose list is empty returns at once)
                 if (x3)
                     K_CONV3_WPAIR_LISTX(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.d_skip + SK3X_CTR, 0, net.skip3x_desc, net.skip3x_rows, net.d_skip);
@@ -1685,16 +1715,25 @@ static constexpr int GRAPH_MAX_CROPS = 6400;      // above this the kernels them
 static constexpr size_t GRAPH_CACHE = 8;
 static constexpr int GRAPH_MIN_SEEN = 3;          // calls with the same key before its chain is captured
 
-static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits);
+// a call's chain is counted, captured or replayed (net_forward_inner) -- not launched as it stands
+static bool graph_path(const trexhip_ctx* ctx, const Net* net, const int n) {
+    static const bool enabled = [] { const char* e = std::getenv("TREXHIP_GRAPHS"); return !(e && std::atoi(e) == 0); }();
+    // not while profiling (the stage events are host-side bookkeeping), not before the first plain call (function attributes are set there)
+    return enabled && net->graphs_ok && n <= GRAPH_MAX_CROPS && !ctx->profiling && ctx->attr_cnn;
+}
+
+static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits, bool prepared);
 int net_forward(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
     Net* net = static_cast<Net*>(ctx->net);
+    // every forward pass takes the record of a prepare call; only the pass it was made for finds its launches done (cnn_prepared.h)
+    const bool prepared = ctx->prepared.consume(ctx->prepared.make(d_crops, n, ctx->cnn_mode, ctx->tune_conv_geom, ctx->stream));
     if (ctx->cnn_mode == TREXHIP_CNN_FP16X3) {
         // the range flag and the pass counters: zero by construction (the plan kernel of the previous pass), cleared here only behind a pass that
         // failed half-way (outside any capture: a replayed chain never holds this memset)
         if (!net->ovf_clean) TH_CHECK_HIP(hipMemsetAsync(net->d_ovf, 0, OVF_PLAN * 4, ctx->stream));
         net->ovf_clean = false;
     }
-    const int rc = net_forward_inner(ctx, d_crops, n, d_probs, d_logits);
+    const int rc = net_forward_inner(ctx, d_crops, n, d_probs, d_logits, prepared);
     if (rc == TREXHIP_OK) { net->last_mode = ctx->cnn_mode; if (ctx->cnn_mode == TREXHIP_CNN_FP16X3) net->ovf_clean = true; }
     // (the plan is a pure function of these: the same one the launch, or the capture that is replayed, was made from)
     net->last_fc1_n = rc == TREXHIP_OK && !net->arch && cnn_plan(net->W, net->H, net->CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0,
@@ -1725,12 +1764,11 @@ static bool capture_chain(trexhip_ctx* ctx, Net* net, Net::GraphEntry* cand, con
     return true;
 }
 
-static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits) {
+static int net_forward_inner(trexhip_ctx* ctx, const uint8_t* d_crops, int n, float* d_probs, float* d_logits, const bool prepared) {
     Net* net = static_cast<Net*>(ctx->net);
     if (net->arch) return arch_forward(ctx, *net, d_crops, n, d_probs, d_logits);      // chunked, never captured
-    static const bool enabled = [] { const char* e = std::getenv("TREXHIP_GRAPHS"); return !(e && std::atoi(e) == 0); }();
-    // not while profiling (the stage events are host-side bookkeeping), not before the first plain call (function attributes are set there)
-    if (!enabled || !net->graphs_ok || n > GRAPH_MAX_CROPS || ctx->profiling || !ctx->attr_cnn) return net_forward_launch(ctx, d_crops, n, d_probs, d_logits);
+    // (a prepared call that ends up on the graph path -- the timers were switched off in between -- runs its whole chain)
+    if (!graph_path(ctx, net, n)) return net_forward_launch(ctx, d_crops, n, d_probs, d_logits, prepared);
     hipStream_t s = ctx->stream;
     const Net::GraphKey key{d_crops, n, d_probs, d_logits, ctx->cnn_mode, ctx->tune_conv_geom, s};
     ++net->tick;
@@ -1785,6 +1823,30 @@ int trexhip_identify_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n,
     const int rc = identify_prepare(ctx, ctx && d_crops && d_probs, "trexhip_identify_device", n, &net);
     if (rc || !net) return rc;
     return net_forward(ctx, d_crops, n, d_probs, d_logits);
+}
+
+int trexhip_identify_prepare_device(trexhip_ctx* ctx, const uint8_t* d_crops, int32_t n) {
+    Net* net;
+    const int rc = identify_prepare(ctx, ctx && d_crops, "trexhip_identify_prepare_device", n, &net);
+    if (rc || !net) return rc;
+    ctx->prepared.drop();
+    if (net->arch || ctx->cnn_mode != TREXHIP_CNN_FP16X3 || graph_path(ctx, net, n)) return TREXHIP_OK;
+    const CnnPlan p = cnn_plan(net->W, net->H, net->CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0, ctx->tune_conv_geom, n, ctx->n_cus);
+    if (!plan_prepares(p)) return TREXHIP_OK;
+    const Pass f{*net, p, ctx->stream, ctx->cnn_mode, d_crops, n, nullptr, nullptr};
+    stage_begin(ctx, TREXHIP_STAGE_PREPARE);
+    launch_prep(f, PREP_LISTS | PREP_ACT3);
+    stage_end(ctx, TREXHIP_STAGE_PREPARE);
+    TH_CHECK_HIP(hipGetLastError());
+    ctx->prepared.set(ctx->prepared.make(d_crops, n, ctx->cnn_mode, ctx->tune_conv_geom, ctx->stream));
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_prepare_stats(trexhip_ctx* ctx, uint32_t* records, uint32_t* hits) {
+    if (!ctx) { set_error("trexhip_identify_prepare_stats: null ctx"); return TREXHIP_E_INVALID; }
+    if (records) *records = ctx->prepared.records;
+    if (hits) *hits = ctx->prepared.hits;
+    return TREXHIP_OK;
 }
 
 int trexhip_identify(trexhip_ctx* ctx, const uint8_t* crops, int32_t n, float* probs) {
@@ -1908,6 +1970,7 @@ int trexhip_identify_fc1_stats(trexhip_ctx* ctx, uint32_t* rows, uint32_t* liste
 int trexhip_set_identity_precision(trexhip_ctx* ctx, int32_t mode) {
     if (!ctx || mode < 0 || mode > 3) { set_error("trexhip_set_identity_precision: mode must be one of TREXHIP_CNN_*"); return TREXHIP_E_INVALID; }
     ctx->cnn_mode = mode;
+    ctx->prepared.precision_changed();
     return TREXHIP_OK;
 }
 
@@ -1950,6 +2013,7 @@ int trexhip_network_image_size(trexhip_ctx* ctx, int32_t* width, int32_t* height
 
 namespace trexhip {
 void net_free(trexhip_ctx* ctx) {
+    ctx->prepared.closed();
     free_net(static_cast<Net*>(ctx->net)); ctx->net = nullptr;
     free_net(static_cast<Net*>(ctx->cat)); ctx->cat = nullptr;
 }

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "../../include/trexhip.h"
+#include "cnn_prepared.h"
 
 #define TREXHIP_ROW_SLOT 16
 #define TREXHIP_CTR_STRIDE 32
@@ -143,6 +144,11 @@ struct trexhip_ctx {
     // device memory (layout: DESIGN.md "Data layout in HBM")
     trexhip::Mem mem;                   // owns every buffer below
     trexhip::BlobTables tables;         // pass 1: valid_n frames of the last segmented / loaded batch
+    // trexhip_fetch_begin: the copies of the three pooled tables into the pinned mirrors are queued, fetch_ev is recorded behind them on
+    // fetch_stream, and nobody has waited for it yet (trexhip::fetch_wait)
+    hipEvent_t fetch_ev = nullptr;      // created on first use, hipEventDisableTiming
+    hipStream_t fetch_stream = nullptr;
+    bool fetch_pending = false;
     trexhip::LabelState label;
     uint8_t* d_bg = nullptr;
     uint8_t* d_staging = nullptr;       // frames uploaded by the host-pointer API
@@ -171,6 +177,7 @@ struct trexhip_ctx {
     trexhip::Scratch med;               // flags, counts, offsets and row list of trexhip_tracklet_medians_device (tracklet_median.hip)
     trexhip::Pass2 pass2;
     int cnn_mode = TREXHIP_CNN_FP16X3;  // TREXHIP_CNN_*: fp32-class arithmetic on the fp16 matrix cores, range-guarded
+    trexhip::PreparedState prepared;    // what trexhip_identify_prepare_device queued for the next identify call (cnn_prepared.h)
 
     bool profiling = false;
     int tune_conv_geom = 0;             // dev only: which identity-network chain runs (TREXHIP_CONV_GEOM, bits 0-11 and 23-30)
@@ -195,6 +202,9 @@ int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n);
 void stage_begin(trexhip_ctx* ctx, int stage);
 void stage_end(trexhip_ctx* ctx, int stage);
 void net_free(trexhip_ctx* ctx);
+// blocks until the table copies of a trexhip_fetch_begin have arrived; at once with nothing pending.  Called by every entry point that overwrites
+// the device tables or the pinned mirrors, or reads the mirrors on the host (capi.hip)
+int fetch_wait(trexhip_ctx* ctx);
 int launch_pending(trexhip_ctx* ctx);
 int launch_morphology(trexhip_ctx* ctx, const uint8_t* d_frames, int n, const uint32_t** result);
 int launch_rethreshold(trexhip_ctx* ctx, int thr, int method, const double* ranges, int n_ranges, const int32_t* d_blob_thr);

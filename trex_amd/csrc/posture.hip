@@ -916,6 +916,7 @@ extern "C" int trexhip_posture_device(trexhip_ctx* ctx, int32_t table, const tre
     } else if (table != 0) { set_error("trexhip_posture_device: table must be 0 (detect) or 1 (re-threshold)"); return TREXHIP_E_INVALID; }
     const BlobTables& t = table == 0 ? ctx->tables : ctx->pass2.tables;
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    if (const int rc = fetch_wait(ctx)) return rc;      // the plan reads the fetched blob table on the host
     const PosturePlan plan(pp, t, n_blobs, false);
     if (int rc = launch_posture(ctx, plan, t, n_blobs, PostureOut{reinterpret_cast<float2*>(d_outline), reinterpret_cast<float4*>(d_segments), d_info}, nullptr, nullptr)) return rc;
     TH_CHECK_HIP(hipGetLastError());
@@ -1037,6 +1038,7 @@ extern "C" int trexhip_posture_auto_device(trexhip_ctx* ctx, const trexhip_postu
     hipStream_t s = ctx->stream;
     const dim3 g256((unsigned)((n + 255) / 256));
     hipLaunchKernelGGL(k_auto_init, g256, dim3(256), 0, s, n, (int)track_posture_threshold, a, d_info);
+    if (const int rc = fetch_wait(ctx)) return rc;
     PosturePlan plan(pp, ctx->tables, n, true);
     for (int round = 0; round < 51; ++round) {                        // thresholds t, t+2, ..., below t+100
         int rc = trexhip_rethreshold_per_blob_device(ctx, 0, a.thr, method, nullptr, 0);     // negative entries (finished blobs) are skipped

@@ -1669,6 +1669,7 @@ static void launch_rows(int nch, dim3 grid, hipStream_t s, const uint8_t* frames
 // could not hold] -> [k_gather].  Every choice below is made from what the call can see (frame size and count, alignment, settings, CUs, the two
 // hint words); none changes a result.
 int launch_segment(trexhip_ctx* ctx, const uint8_t* d_frames, int n) {
+    if (const int rc = fetch_wait(ctx)) return rc;      // the tables this pass overwrites may still be on their way to the host
     SegCfg c = ctx->cfg;
     c.B = n;
     ctx->batch_invert = c.invert; ctx->batch_zero_bg = c.zero_bg;      // the batch's own copy: downstream calls on this batch use it

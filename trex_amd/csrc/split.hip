@@ -325,6 +325,7 @@ int launch_split_search(trexhip_ctx* ctx, const trexhip_split_params* sp, int me
                        ctx->d_bg, ctx->tables.d_info, ctx->tables.d_blob_frame, ctx->tables.d_blobs, ctx->tables.d_runs, d_presumed, n_blobs, d_thr, d_info);
     // the third size class (134 KB of LDS: one blob per CU) only when the fetched tables hold a blob of that size
     bool huge = false;
+    if (const int rc = fetch_wait(ctx)) return rc;
     for (int i = 0; i < n_blobs && !huge; ++i) huge = ctx->tables.h_blobs[i].n_pixels > (uint32_t)S_PX || ctx->tables.h_blobs[i].n_runs > (uint32_t)S_RUNS;
     if (huge) {
         const int bytes = split_lds_bytes(S_PX_HUGE, S_RUNS_HUGE, S_SUB_HUGE);

@@ -336,6 +336,7 @@ extern "C" int trexhip_load_frames_v6_device(trexhip_ctx* ctx, const uint8_t* d_
     if (ctx->p.width > 32768) { set_error("trexhip_load_frames_v6_device: LegacyShortHorizontalLine holds x1 < 32768 (pv.h:36)"); return TREXHIP_E_UNSUPPORTED; }
     if (ctx->p.max_blobs > 65535) { set_error("trexhip_load_frames_v6_device: a frame holds at most 65535 objects (u16 n, pv.cpp:686)"); return TREXHIP_E_UNSUPPORTED; }
     TH_CHECK_HIP(hipSetDevice(ctx->p.device));
+    if (int rc = fetch_wait(ctx)) return rc;             // the tables this call overwrites may still be on their way to the host
     const size_t B = (size_t)ctx->p.max_batch, W = (size_t)ctx->p.width, H = (size_t)ctx->p.height, NB = (size_t)ctx->p.max_blobs;
     if (int rc = ensure_staging(ctx, "trexhip_load_frames_v6_device")) return rc;
     if (int rc = ctx->load.reserve(ctx, B * NB * sizeof(LoadBlob) + B * sizeof(LoadFrame), "trexhip_load_frames_v6_device")) return rc;

@@ -80,7 +80,10 @@ class Lane:
     def identify(self, step_idx):
         pl, seg = self.pl, self.seg
         o = pl.opt
-        res = self.res = seg.fetch_raw()        # waits for detect; blob/run/pixel tables now on this rank's host (pinned)
+        # waits for detect and the counts; the blob / run / pixel tables travel to this rank's host (pinned) while everything below is queued:
+        # nothing below reads them there, and drain() waits for them
+        # (with posture the plain fetch: the posture plan reads the blob table on the host, so the wait would only move into that call)
+        res = self.res = seg.fetch_raw() if pl.with_posture else seg.fetch_begin_raw()
         n = self.n = int(res.total_blobs)
         assert n <= pl.rows, "identity table too small"
         if self.hi is not None:
@@ -94,6 +97,9 @@ class Lane:
                     seg.crops_posture_device(self.crops.data_ptr(), n, self.p_minfo.data_ptr())
                 else:
                     seg.crops_device(self.crops.data_ptr(), n, normalization=1 if o["normalize"] == "moments" else 0)
+                # what the network needs from the crops alone (bands, lists, background fills) goes out in front of the wait below: beside the
+                # other lane's fc1 / head, not in series behind them (a no-op where the chain has no such part)
+                seg.identify_prepare_device(self.crops.data_ptr(), n)
                 # one identity network on the matrix cores at a time; posture / crops above and the table hand-off below overlap the other
                 # lane's network.  Not for batches of a few frames (TRex's default is ONE frame per call): their network is a chain of small
                 # launches that leaves most of the chip idle, and two lanes' chains side by side are what keeps it busy
@@ -126,6 +132,7 @@ class Lane:
             self.done.record(self.stream)
 
     def drain(self):
+        self.seg.fetch_wait()
         self.stream.synchronize()
         if self.copy_stream is not None:
             self.copy_stream.synchronize()
