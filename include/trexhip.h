@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define TREXHIP_ABI_VERSION 26
+#define TREXHIP_ABI_VERSION 27
 
 /* A failed allocation is reported the same way by every entry point: when the device (or the pinned host pool) is out of memory the call
    returns TREXHIP_E_NOMEM and trexhip_last_error() names the entry point; any other HIP failure is TREXHIP_E_DEVICE.  (Up to and including
@@ -638,8 +638,19 @@ int trexhip_identify_skip3_stats(trexhip_ctx* ctx, uint32_t* pairs, uint32_t* li
  * What the last such call did (waits for the context's stream): *crops_windowed whose pairs went into windowed passes, *windowed_passes of them,
  * and the *full_passes of six pairs the other crops took; zeros where the dense kernel ran.  trexhip_identify_skip3_stats keeps counting by the
  * row rule alone: its *passes are the passes of six pairs that the listed pairs make, which is what ran before there were windows and under bit 21.
- * No reference counterpart; any pointer may be NULL.  (ABI 24) */
+ * No reference counterpart; any pointer may be NULL.  (ABI 24; since ABI 27 *windowed_passes and *full_passes count passes of WHOLE pairs, ten and
+ * six to a pass, whether the kernel walked those or the passes of the call below -- as *passes of trexhip_identify_skip3_stats does.  The choice
+ * between the listed and the dense form is made on these counts.) */
 int trexhip_identify_skip3x_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, uint32_t* windowed_passes, uint32_t* full_passes);
+
+/* A pass of the listed conv3 kernel has 64 tile slots, and whole pairs fill 60 of them (6 pairs of 10 tiles, 10 pairs of a window's 6).  Since
+ * ABI 27 a listed pass, full-width or windowed, is up to 64 CONSECUTIVE tiles of its list's pair sequence instead: it may begin and end at any
+ * even tile of a pair, and a pair cut between two passes is computed in part by each.  The results are the bits of the passes of whole pairs,
+ * which bit 20 of TREXHIP_CONV_GEOM (value 1048576) brings back.
+ * What the last such call did (waits for the context's stream): the *windowed_passes and *full_passes that the two listed instances walked --
+ * under bit 20 the numbers of trexhip_identify_skip3x_stats --; zeros where the dense kernel ran.  No reference counterpart; either pointer may
+ * be NULL.  (ABI 27) */
+int trexhip_identify_skip3_ran(trexhip_ctx* ctx, uint32_t* windowed_passes, uint32_t* full_passes);
 
 /* Above 3200 one-channel 80x80 crops in TREXHIP_CNN_FP16X3, where the skipping above is on, a crop whose blob fits 8 of the 10 column tiles of
  * conv2's output takes windowed passes of the fused conv1+conv2 kernel: 8 tiles of up to 4 output row pairs of that crop alone, the rest taken

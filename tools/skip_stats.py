@@ -9,7 +9,9 @@ form walked (0: the dense kernel ran) against the dense kernel's, bytes of act3 
 keep counting by the row rule alone) -- and (trexhip_identify_bgrow_stats) the rows of conv1's pooled output those passes read against the rows
 the kernel made of them, the others being background rows -- and those of the windowed listed conv3 (trexhip_identify_skip3x_stats): crops whose
 listed pairs went into windowed passes of 3 tiles, those passes, the full-width listed passes of the other crops (conv3_listed_passes keeps
-counting by the row rule alone; conv3_passes_run is what ran).  Nothing here is timed.  One JSON line.
+counting by the row rule alone; conv3_passes_run counts passes of whole pairs, six full-width or ten windowed) -- and the passes the two listed
+instances walked (trexhip_identify_skip3_ran: conv3_windowed_passes_ran, conv3_full_width_passes_ran -- the full-width ones are passes of up
+to 64 consecutive tiles unless TREXHIP_CONV_GEOM bit 20 is set).  Nothing here is timed.  One JSON line.
    python tools/skip_stats.py"""
 import json
 import os
@@ -33,6 +35,7 @@ pairs3, listed3, passes3, filled3 = lane.seg.skip3_stats()
 fc1_rows, fc1_listed = lane.seg.fc1_stats()          # crop-plane rows of the listed fc1 and the rows it computed (0, 0: the dense fc1 ran)
 x_crops, x_passes, x_full = lane.seg.skipx_stats()
 x3_crops, x3_passes, x3_full = lane.seg.skip3x_stats()
+ran_windowed, ran_full = lane.seg.skip3_ran()
 v2_read, v2_made = lane.seg.bgrow_stats()            # rows of conv1's pooled output the windowed passes read, and those of them made (0, 0: all are)
 crops = lane.crops[:passes * 3 // 20]
 rows = (crops != 0).any(dim=2)                       # [n][80]: the row holds a non-zero byte
@@ -45,6 +48,8 @@ print(json.dumps({"blobs_per_step": int(n), "crops": int(crops.shape[0]), "passe
                   "conv3_pass_ratio": round(passes3 / max((pairs3 * 10 + 63) // 64, 1), 4), "act3_bytes_filled": filled3,
                   "conv3_passes_run": x3_passes + x3_full, "conv3_run_ratio": round((x3_passes + x3_full) / max((pairs3 * 10 + 63) // 64, 1), 4),
                   "conv3_crops_windowed": x3_crops, "conv3_windowed_passes": x3_passes, "conv3_full_width_passes": x3_full,
+                  "conv3_windowed_passes_ran": ran_windowed, "conv3_full_width_passes_ran": ran_full,
+                  "conv3_ran_ratio": round((ran_windowed + ran_full) / max(x3_passes + x3_full, 1), 4),
                   "fc1_rows": fc1_rows, "fc1_rows_listed": fc1_listed, "fc1_fraction_listed": round(fc1_listed / max(fc1_rows, 1), 4),
                   "crops_windowed": x_crops, "windowed_passes": x_passes, "full_width_passes": x_full,
                   "windowed_passes_per_crop": round(x_passes / max(x_crops, 1), 3),

@@ -202,7 +202,7 @@ SYMBOLS = [
     "trexhip_set_stream", "trexhip_get_live_params", "trexhip_update_params", "trexhip_set_background", "trexhip_set_background_device", "trexhip_set_background_color", "trexhip_set_background_color_device", "trexhip_generate_average_device", "trexhip_get_background", "trexhip_segment_device",
     "trexhip_segment", "trexhip_segment_color", "trexhip_segment_color_device", "trexhip_rethreshold_device", "trexhip_rethreshold_per_blob_device", "trexhip_fetch_rethreshold", "trexhip_fetch", "trexhip_device_view_get", "trexhip_synchronize",
     "trexhip_profile_enable", "trexhip_profile_read", "trexhip_profile_reset",
-    "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats", "trexhip_identify_skip_stats", "trexhip_identify_skip3_stats", "trexhip_identify_skip3x_stats", "trexhip_identify_skipx_stats", "trexhip_identify_bgrow_stats", "trexhip_identify_fc1_stats",
+    "trexhip_default_posture_params", "trexhip_posture_device", "trexhip_posture_auto_device", "trexhip_pack_frames_v6_device", "trexhip_crops_device", "trexhip_pixel_channels", "trexhip_device_alloc", "trexhip_device_free", "trexhip_copy_to_host", "trexhip_copy_to_device", "trexhip_crops_transformed_device", "trexhip_crops_posture_device", "trexhip_default_midline_params", "trexhip_midline_device", "trexhip_midline_movement_device", "trexhip_default_split_params", "trexhip_split_search_device", "trexhip_export_id_table_device", "trexhip_export_id_table_ex_device", "trexhip_load_weights", "trexhip_set_identity_precision", "trexhip_num_classes", "trexhip_identify_device", "trexhip_identify", "trexhip_identify_guard_stats", "trexhip_identify_skip_stats", "trexhip_identify_skip3_stats", "trexhip_identify_skip3x_stats", "trexhip_identify_skip3_ran", "trexhip_identify_skipx_stats", "trexhip_identify_bgrow_stats", "trexhip_identify_fc1_stats",
     "trexhip_weight_blob_bytes", "trexhip_trainer_create", "trexhip_trainer_destroy", "trexhip_trainer_set_lr", "trexhip_trainer_steps", "trexhip_trainer_image_size", "trexhip_trainer_version", "trexhip_trainer_keep_mask_bytes", "trexhip_train_step_device", "trexhip_train_step", "trexhip_train_eval_device", "trexhip_train_eval", "trexhip_trainer_read", "trexhip_trainer_export",
     "trexhip_default_augment_params", "trexhip_augment_device",
     "trexhip_train_predict_device", "trexhip_validation_metrics_device", "trexhip_class_averages_device",
@@ -301,6 +301,7 @@ def lib():
         L.trexhip_identify_skipx_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify_bgrow_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify_skip3x_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.trexhip_identify_skip3_ran.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_identify_skip3_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.trexhip_identify_fc1_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.trexhip_weight_blob_bytes.argtypes = [C.c_int32, C.c_int32]
@@ -737,6 +738,14 @@ class Segmenter:
         a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         _check(lib().trexhip_identify_skip3x_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    def skip3_ran(self):
+        """(windowed passes, full-width passes) that the listed instances of conv3 walked in the last call that listed: passes of up to 64
+        consecutive tiles, or -- TREXHIP_CONV_GEOM bit 20 -- the passes of whole pairs that skip3x_stats counts either way; (0, 0): the dense
+        kernel ran"""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        _check(lib().trexhip_identify_skip3_ran(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def fc1_stats(self):
         """(crop-plane rows of the last identify call -- 10 per crop --, rows its listed fc1 computed); (0, 0) where fc1 was not the listed form"""

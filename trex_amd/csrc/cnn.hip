@@ -1422,12 +1422,15 @@ static int ensure_act(trexhip_ctx* ctx, Net* net, int n) {
         TRY(B.device_bytes(&net->skipx_list, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         TRY(B.device_bytes(&net->skipx_rows, (N * skipx_passes({0, SkipGeom::V3_ROWS - 1}) + SKIP_PAD) * 4, who));
         const size_t blocks3 = (N + Skip3Geom::BLOCK - 1) / Skip3Geom::BLOCK;
-        TRY(B.device_bytes(&net->skip3_counts, ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint4), who));
+        // (the lists of either form of a listed pass, pair slots or tile slots: the longer one)
+        constexpr size_t BP3 = std::max(Skip3Geom::BLOCK_PASSES, Skip3TGeom::BLOCK_PASSES), BP3X = std::max(Skip3XGeom::BLOCK_PASSES, Skip3TXGeom::BLOCK_PASSES);
+        static_assert(Skip3Geom::DESC == Skip3TGeom::DESC && Skip3XGeom::DESC == Skip3TXGeom::DESC, "one descriptor size per list");
+        TRY(B.device_bytes(&net->skip3_counts, 2 * ((blocks3 + SKIP3_TB - 1) / SKIP3_TB) * sizeof(uint4), who));
         TRY(B.device_bytes(&net->skip3_tcounts, blocks3 * 2 * sizeof(uint32_t), who));
-        TRY(B.device_bytes(&net->skip3_desc, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Geom::DESC * 4, who));
-        TRY(B.device_bytes(&net->skip3_rows, blocks3 * Skip3Geom::BLOCK_PASSES * Skip3Reach::WORDS * 4, who));
-        TRY(B.device_bytes(&net->skip3x_desc, blocks3 * Skip3XGeom::BLOCK_PASSES * Skip3XGeom::DESC * 4, who));
-        TRY(B.device_bytes(&net->skip3x_rows, blocks3 * Skip3XGeom::BLOCK_PASSES * Skip3Reach::WORDS * 4, who));
+        TRY(B.device_bytes(&net->skip3_desc, blocks3 * BP3 * Skip3Geom::DESC * 4, who));
+        TRY(B.device_bytes(&net->skip3_rows, blocks3 * BP3 * Skip3Reach::WORDS * 4, who));
+        TRY(B.device_bytes(&net->skip3x_desc, blocks3 * BP3X * Skip3XGeom::DESC * 4, who));
+        TRY(B.device_bytes(&net->skip3x_rows, blocks3 * BP3X * std::max(Skip3Reach::WORDS, Skip3TXGeom::ROW_WORDS) * 4, who));
         TRY(B.device_bytes(&net->fc1_list, Skip3Geom::PAIRS * N * sizeof(int), who));
     }
     TRY(B.device_bytes(&net->crops, N * net->W * net->H * net->CH, who));
@@ -1464,9 +1467,14 @@ static const Kern K_CONV3_WPAIR(k_conv5_wpair<false>, 256, GW3::LDS_BYTES + 1024
 static const Kern K_CONV3_WPAIR_LIST(k_conv5_wpair<true>, 256, GW3::LDS_BYTES + 1024);
 using GW3X = Wino3Pass<Skip3XGeom::TILES, Skip3XGeom::NR>;
 static const Kern K_CONV3_WPAIR_LISTX(k_conv5_wpair<true, Skip3XGeom>, 256, GW3X::LDS_BYTES + 1024);
-static const Kern K_PAIR_COUNT(k_pair_count, SKIP3_NT);
-static const Kern K_PAIR_LIST(k_pair_list, SKIP3_NT);
-static const Kern K_ACT3_FILL(k_act3_fill, 256);
+// (the listed instances on passes of tile slots, cnn_skip3.h, and the list kernels that make those)
+using GW3T = Wino3Pass<Skip3TGeom::TILES, Skip3TGeom::NR>;
+using GW3TX = Wino3Pass<Skip3TXGeom::TILES, Skip3TXGeom::NR>;
+static const Kern K_CONV3_WPAIR_TLIST(k_conv5_wpair<true, Skip3TGeom>, 256, GW3T::LDS_BYTES + 1024);
+static const Kern K_CONV3_WPAIR_TLISTX(k_conv5_wpair<true, Skip3TXGeom>, 256, GW3TX::LDS_BYTES + 1024);
+static const Kern K_PAIR_COUNT(k_pair_count<false>, SKIP3_NT), K_PAIR_COUNT_T(k_pair_count<true>, SKIP3_NT_TILED);
+static const Kern K_PAIR_LIST(k_pair_list<false>, SKIP3_NT), K_PAIR_LIST_T(k_pair_list<true>, SKIP3_NT);
+static const Kern K_ACT3_FILL(k_act3_fill<false>, 256), K_ACT3_FILL_T(k_act3_fill<true>, 256);
 template <int CI, int CO, int S, int ROWS, int NTERMS>
 static auto split_kern() { return Kern(k_conv5_split<CI, CO, S, ROWS, NTERMS>, 512, ConvGeomB<CI, CO, S, ROWS, SPLIT_NP>::LDS_BYTES); }
 // conv2 / conv3 on fp32 activations in the exact modes; x6_plan is the bf16x6 instance of every chain's guarded re-run
@@ -1593,14 +1601,14 @@ static int make_empty_v3(trexhip_ctx* ctx, Net* net) {
 // The role-split chain's preparation (cnn_skip_kernels.h), in front of conv1+conv2: which passes, row pairs and fc1 rows the crops need, and the
 // V3 rows of the others; every decision stays on the device.  `direct`: the listed conv3 reads background rows from the image, the fill copies
 // only where the dense form runs
-struct PrepArgs { long long alloc_rows; bool direct, x3 /* conv3's listed pairs in two lists, windowed passes and full-width ones */; };
+struct PrepArgs { long long alloc_rows; bool direct, x3 /* conv3's listed pairs in two lists, windowed passes and full-width ones */, tiled /* passes of tile slots */; };
 static PrepArgs prep_args(const Net& net, const CnnPlan& p) {
     // the back image lies behind the ALLOCATION's rows, whatever this call's n is
     const long long alloc_rows = (long long)net.max_crops * SkipGeom::V3_ROWS;
     const bool direct = p.v3_direct && skip3_direct_fits(alloc_rows);
-    return {alloc_rows, direct, p.skip3x && direct && skip3x_direct_fits(alloc_rows)};
+    return {alloc_rows, direct, p.skip3x && direct && skip3x_direct_fits(alloc_rows), p.skip3t && skip3t_direct_fits(alloc_rows)};
 }
-static void launch_skip_prep(const Pass& f, const bool direct, const bool x3) {
+static void launch_skip_prep(const Pass& f, const bool direct, const bool x3, const bool tiled) {
     const Net& net = f.net;
     const CnnPlan& p = f.p;
     const int n = f.n, lb = ceil_div(p.conv2.items, SKIP_LB);
@@ -1611,8 +1619,8 @@ static void launch_skip_prep(const Pass& f, const bool direct, const bool x3) {
     if (p.skip3) {     // the row pairs conv3 computes, packed into passes: the word that names its form tells the fill whether to copy
         // (skip3x: the crops with a window of conv3 tiles go into a list of their own; its column bands are the ones k_crop_bands writes for skipx)
         const int2* cols3 = x3 ? net.skipx_cols : nullptr;
-        K_PAIR_COUNT(f.s, p.skip3_grid, net.skip_bands, cols3, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
-        K_PAIR_LIST(f.s, p.skip3_grid, net.skip_bands, cols3, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc, net.skip3x_desc);
+        (tiled ? K_PAIR_COUNT_T : K_PAIR_COUNT)(f.s, p.skip3_grid, net.skip_bands, cols3, n, net.d_skip, net.skip3_counts, net.skip3_tcounts);
+        (tiled ? K_PAIR_LIST_T : K_PAIR_LIST)(f.s, p.skip3_grid, net.skip_bands, cols3, n, net.d_skip, net.skip3_counts, net.skip3_tcounts, net.skip3_desc, net.skip3x_desc);
         // the crops each plane of the listed fc1 computes: from the bands alone, so here and not between conv3 and fc1
         if (p.fc1_listed) K_FC1_LIST(f.s, Skip3Geom::PAIRS, net.skip_bands, n, net.d_skip, net.fc1_list, net.max_crops);
     }
@@ -1633,9 +1641,9 @@ static void launch_prep(const Pass& f, const int parts) {
     const CnnPlan& p = f.p;
     if (!plan_prepares(p)) return;
     const PrepArgs a = prep_args(net, p);
-    if (parts & PREP_LISTS) launch_skip_prep(f, a.direct, a.x3);
+    if (parts & PREP_LISTS) launch_skip_prep(f, a.direct, a.x3, a.tiled);
     if ((parts & PREP_ACT3) && p.skip3)
-        K_ACT3_FILL(f.s, p.act3_fill.grid, net.skip_bands, a.x3 ? net.skipx_cols : nullptr, f.n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e),
+        (a.tiled ? K_ACT3_FILL_T : K_ACT3_FILL)(f.s, p.act3_fill.grid, net.skip_bands, a.x3 ? net.skipx_cols : nullptr, f.n, net.d_skip, reinterpret_cast<const uint4*>(net.act3e),
                     reinterpret_cast<uint4*>(net.act3), net.skip3_desc, net.skip3_rows, net.skip3x_desc, net.skip3x_rows, a.alloc_rows, (int)a.direct, (int)!p.fc1_listed);
 }
 
@@ -1654,7 +1662,7 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
     const CnnPlan p = cnn_plan(net.W, net.H, net.CH, ctx->cnn_mode, (reinterpret_cast<uintptr_t>(d_crops) & 15) == 0, ctx->tune_conv_geom, n, ctx->n_cus);
     const Pass f{net, p, ctx->stream, ctx->cnn_mode, d_crops, n, d_probs, d_logits};
     hipStream_t s = f.s;
-    const bool x3 = prep_args(net, p).x3;
+    const bool x3 = prep_args(net, p).x3, tiled = prep_args(net, p).tiled;
     // (the guard words in front of the plan start at zero: the plan's writer -- the last reader of all three -- hands them back zeroed; net_forward
     // clears them itself behind a pass that was not queued to its end)
     stage_begin(ctx, TREXHIP_STAGE_CNN_ALL);
@@ -1694,8 +1702,8 @@ static int net_forward_launch(trexhip_ctx* ctx, const uint8_t* d_crops, int n, f
                 if (!prepared) launch_prep(f, PREP_ACT3);
                 // (an instance whose list is empty returns at once)
                 if (x3)
-                    K_CONV3_WPAIR_LISTX(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.d_skip + SK3X_CTR, 0, net.skip3x_desc, net.skip3x_rows, net.d_skip);
-                K_CONV3_WPAIR_LIST(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.skip3_rows, net.d_skip);
+                    (tiled ? K_CONV3_WPAIR_TLISTX : K_CONV3_WPAIR_LISTX)(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.d_skip + SK3X_CTR, 0, net.skip3x_desc, net.skip3x_rows, net.d_skip);
+                (tiled ? K_CONV3_WPAIR_TLIST : K_CONV3_WPAIR_LIST)(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), 0, net.skip3_desc, net.skip3_rows, net.d_skip);
             }
             K_CONV3_WPAIR(s, p.conv3.grid, net.v3, net.w3w, net.b3, net.act3, net.inv3w, n, net.ovf(OVF_PASS3), p.n_big3, nullptr, nullptr, p.skip3 ? net.d_skip : nullptr);
         }
@@ -1924,6 +1932,14 @@ int trexhip_identify_skip3x_stats(trexhip_ctx* ctx, uint32_t* crops_windowed, ui
     if (crops_windowed) *crops_windowed = w[SK3_USE] ? w[SK3X_CROPS] : 0u;
     if (windowed_passes) *windowed_passes = w[SK3_USE] ? w[SK3X_PASSES] : 0u;
     if (full_passes) *full_passes = w[SK3_USE] ? w[SK3_PASSES] : 0u;
+    return TREXHIP_OK;
+}
+
+int trexhip_identify_skip3_ran(trexhip_ctx* ctx, uint32_t* windowed_passes, uint32_t* full_passes) {
+    uint32_t w[SK_WORDS];
+    if (const int rc = read_skip_words(ctx, "trexhip_identify_skip3_ran", w)) return rc;
+    if (windowed_passes) *windowed_passes = w[SK3_USE] ? w[SK3X_RAN] : 0u;
+    if (full_passes) *full_passes = w[SK3_USE] ? w[SK3_RAN] : 0u;
     return TREXHIP_OK;
 }
 

@@ -58,6 +58,20 @@
 // Measured (profiles/conv3_windowed.txt; the benchmark's 25600 crops: 7347 windowed + 19658 full-width passes where the row-only list has 31383):
 // 116.4 ns per windowed pass against 113.7 ns per full-width pass under a kernel trace, 3423 -> 3091 us for both instances.  Registers: 256 + 236,
 // no scratch, no vector spills; the dense and the full-width listed instance keep theirs (256 + 210, 256 + 242).
+//
+// Passes of TILE SLOTS (L = Skip3TGeom, Skip3TXGeom; cnn_skip3.h): whole pairs leave 4 of the 64 tile slots idle, and both MFMA M-blocks run whole
+// either way.  A listed pass is now up to 64 CONSECUTIVE tiles of its list's pair sequence: tile slot t = m * 32 + j is tile o + t of it, o the
+// (even) tiles the pass begins into its first pair -- pair slot (o + t) / TPP and place (o + t) % TPP are the pass's, not the lane's for good.  They
+// are made where the next pass's A offsets are, under the last unit (a_base): the pair's entry comes out of the descriptor words the wave holds in
+// its lanes (raw_w) by one ds_bpermute_b32, and the tile's act3 offset -- its pair's, its place's, the window's, out of the resource's range for
+// a slot past the pass's tile count -- is made there once per pass and kept by the lane whose number is the slot; the tail reads the two offsets
+// of an accumulator row pair from lanes t0 and t0 + 4, compile-time lane numbers, where it added compile-time places to two of the pass's
+// scalars.  The tap loop has the instructions it had.  A full-width pass touches up to 8 pairs: 24 V3 rows, 25 row slots of 1360 bytes per piece
+// (133 KB of LDS), 17 staging instructions per wave and unit instead of 14; a windowed one up to 12 pairs: 32 rows, 33 slots of 816 bytes (105 KB),
+// 13 instead of 12, and a row table of 64 words, one per lane, where the others have 32 (RW).  One workgroup per CU as before.  Registers: 256 +
+// 242 and 256 + 234, no scratch, no vector spills; the dense and the pair-slot instances are unchanged (256 + 210 and 2 spills, 256 + 242, 256 +
+// 236).  TREXHIP_CONV_GEOM bit 20 runs the pair-slot instances.
+// Measured: profiles/conv3_tile_slots.txt.
 template <bool LISTED, class L = Skip3Geom>
 __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__ v3, const uint4* __restrict__ wp /*[4][5][8][2][2][128] x 16 B*/,
                                                      const float* __restrict__ bias, float* __restrict__ out, const float out_scale,
@@ -81,12 +95,15 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     using LR = Skip3Reach;
     using P = Wino3Pass<L::TILES, L::NR>;                 // the LDS image of a pass
     constexpr bool WIN = L::TILES != G::TPR;              // the windowed listed form
-    static_assert(LISTED || !WIN, "only a listed pass has a window");
+    constexpr bool TS = Skip3Tiled<L>::value;             // a listed pass of tile slots
+    constexpr int RW = Skip3Tiled<L>::ROW_WORDS;          // words of a pass's row table: its base in the last one
+    static_assert(LISTED || (!WIN && !TS), "only a listed pass has a window or tile slots");
     static_assert(LR::ROWB == V3_ROWB && SkipGeom::V3_ROWS == S, "the images in front of V3 and behind it are S rows of V3_ROWB bytes");
-    static_assert((WIN || (P::NR == G::NR && P::RP == G::RP && P::BUF == G::BUF)) && L::SLOTS * P::TPP <= G::MB && L::PAIRS * 2 == S, "a listed pass fits the dense pass's rows and tiles");
+    static_assert((WIN || TS || (P::NR == G::NR && P::RP == G::RP && P::BUF == G::BUF)) && (TS || L::SLOTS * P::TPP <= G::MB) && L::PAIRS * 2 == S, "a listed pass fits the dense pass's rows and tiles");
+    static_assert(!TS || (P::TPP - 2 + G::MB - 1) / P::TPP < L::SLOTS, "tile slots: every lane's pair slot is one of the descriptor's");
     if (words && (words[SK3_USE] != 0) != LISTED) return;
     const int total_tiles = n_crops * G::TPC;
-    const int n_pass = LISTED ? __builtin_amdgcn_readfirstlane((int)words[WIN ? SK3X_PASSES : SK3_PASSES]) : (total_tiles + G::MB - 1) / G::MB;
+    const int n_pass = LISTED ? __builtin_amdgcn_readfirstlane((int)words[WIN ? SK3X_RAN : SK3_RAN]) : (total_tiles + G::MB - 1) / G::MB;
     const int n_big = LISTED ? (n_pass >= 16 * (int)gridDim.x ? (int)((long long)n_pass * 7 / 8) / 4 : 0) : n_big_dense;
     const int big_end = n_big * PK;
     auto ticket_first = [&](const int t) { return t < n_big ? t * PK : big_end + (t - n_big); };
@@ -163,15 +180,17 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     auto pass_fetch = [&](const int pass_) {
         const int* d = desc + (size_t)pass_ * L::DESC;
         raw_w = d[lane & (L::DESC - 1)];
-        tab = rowsrc[(size_t)pass_ * LR::WORDS + (lane & (LR::WORDS - 1))];
+        tab = rowsrc[(size_t)pass_ * RW + (lane & (RW - 1))];
+        if (TS) return;           // (tile slots: the pair entries come out of raw_w, a_base)
 #pragma unroll
         for (int m = 0; m < TPW; ++m) ent[m] = d[S3_SLOT + lps[m]];
     };
-    auto pass_decode = [&](int& qmin_, int& gp0_, int& span_, uint32_t (&rel_)[L::SLOTS]) {
+    auto pass_decode = [&](int& qmin_, int& gp0_, int& span_, uint32_t (&rel_)[L::SLOTS], int& tiles_) {
         const int w = raw_w;
-        qmin_ = __builtin_amdgcn_readlane((int)tab, LR::BASE);
+        qmin_ = __builtin_amdgcn_readlane((int)tab, RW - 1);
         gp0_ = __builtin_amdgcn_readlane(w, S3_GP0);
         span_ = __builtin_amdgcn_readlane(w, S3_SPAN);
+        if (TS) { tiles_ = __builtin_amdgcn_readlane(w, S3_TILES); return; }      // (the act3 offsets are the lanes': a_base)
 #pragma unroll
         for (int s2 = 0; s2 < L::SLOTS; ++s2) {
             const uint32_t e = (uint32_t)__builtin_amdgcn_readlane(w, S3_SLOT + s2), rp = e >> 16;
@@ -180,9 +199,9 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                      : rp * (uint32_t)(G::TPP * CO * 4) + (WIN ? ((e >> S3_T0_SHIFT) & S3_T0_MASK) * (uint32_t)(2 * CO * 4) : 0u);
         }
     };
-    int qmin = 0, nrows = 0, gp0 = 0, span = 0;
+    int qmin = 0, nrows = 0, gp0 = 0, span = 0, tiles = 0;
     uint32_t rel[L::SLOTS] = {};
-    if (LISTED) { pass_fetch(pass); pass_decode(qmin, gp0, span, rel); }
+    if (LISTED) { pass_fetch(pass); pass_decode(qmin, gp0, span, rel, tiles); }
     else wino_pass_rows<G, S>(pass, total_tiles, qmin, nrows);
     const __amdgpu_buffer_rsrc_t srs0 = stage_rsrc(0, qmin, nrows);
 #pragma unroll
@@ -202,7 +221,25 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
     }
     // A-operand byte offsets of this lane's two tiles, per kernel row: the row slot (out-of-crop rows -> the zero row) + the tile's 32 bytes
     // (per tile: the offset of its own input row and of the zero row, and its y; per kernel row a compare and a select)
-    auto a_base = [&](const int pass_, const int qmin_, const int m, int& inr, int& zr, int& yy) {
+    // TS: tile slot t = m * 32 + j of a pass is tile o + t of its pair sequence: pair slot (o + t) / TPP, whose entry the wave holds in lane
+    // S3_SLOT + slot of raw_w, and place (o + t) % TPP -- per pass, where the pair-slot form has them per lane for good.  The act3 offset of the
+    // tile -- its pair's, its place's and the window's; past the pass's tile count, out of the resource's range -- is made here as well, once
+    // per pass: toff[m], of which lane l keeps that of tile slot l (otab_n) for the tail to read by lane number
+    uint32_t toff[TPW] = {};
+    auto a_base = [&](const int pass_, const int qmin_, const int tiles_, const int m, int& inr, int& zr, int& yy) {
+        if (TS) {
+            constexpr int MUL = P::TPP == 10 ? 205 : 171, SH = P::TPP == 10 ? 11 : 10;      // x / TPP for x < 72
+            static_assert(P::TPP == 10 || P::TPP == 6, "the division by multiplication");
+            const int o = tiles_ & S3_O_MASK, cnt = tiles_ >> S3_COUNT_SHIFT, t = m * 32 + j;
+            const int x = o + t, slot = (x * MUL) >> SH, r2 = x - slot * P::TPP, par = r2 & 1;
+            const int e = __builtin_amdgcn_ds_bpermute((S3_SLOT + slot) * 4, raw_w);
+            yy = 2 * ((e >> 8) & S3_Q_MASK) + par; zr = (r2 >> 1) * 32 + h * 16; inr = ((e & 0xff) + par) * P::RP + zr;
+            const uint32_t rp = (uint32_t)e >> 16;
+            toff[m] = t < cnt && rp != (uint32_t)S3_IDLE
+                    ? rp * (uint32_t)(G::TPP * CO * 4) + (uint32_t)(r2 * CO * 4) + (WIN ? ((e >> S3_T0_SHIFT) & S3_T0_MASK) * (uint32_t)(2 * CO * 4) : 0u)
+                    : 0x80000000u;
+            return;
+        }
         if (LISTED) {             // (the entries fetched last: this pass's in front of the loop, the next one's under the last unit)
             const int r2 = lr2[m], par = r2 & 1, e = ent[m];
             yy = 2 * ((e >> 8) & (WIN ? S3_Q_MASK : 0xff)) + par; zr = (r2 >> 1) * 32 + h * 16; inr = ((e & 0xff) + par) * P::RP + zr;
@@ -222,11 +259,13 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
 #pragma unroll
     for (int m = 0; m < TPW; ++m) {
         int inr, zr, yy;
-        a_base(pass, qmin, m, inr, zr, yy);
+        a_base(pass, qmin, tiles, m, inr, zr, yy);
 #pragma unroll
         for (int ky = 0; ky < 5; ++ky) aoff[m][ky] = a_offset(inr, zr, yy, ky);
     }
     int an_in[TPW] = {}, an_z[TPW] = {}, an_y[TPW] = {};
+    // TS: the act3 offset of tile slot l in lane l, of this pass and of the pass whose tail is still to run
+    uint32_t otab = h ? toff[1] : toff[0], otab_prev = 0x80000000u;
     // two accumulator banks x two tiles x the two positions of a pair; the partial outputs y0..y3 of both tiles.  All of it lives across
     // passes (the tail of a pass runs inside the next one); the first pass's "previous pass" stores into an empty buffer resource (dropped)
     // one accumulator register read where it is written (the compiler's own copies move a whole 16-register tuple to vector registers at
@@ -259,6 +298,15 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         const float d0 = y[m][3][r] + P3_ACC(acc[1][m][1][r]), d1 = y[m][3][r + 1] + P3_ACC(acc[1][m][1][r + 1]);
         const float v0 = fmaxf(fmaxf(a0, y[m][1][r]), fmaxf(a1, y[m][1][r + 1]));
         const float v1 = fmaxf(fmaxf(y[m][2][r], d0), fmaxf(y[m][2][r + 1], d1));
+        if (TS) {
+            // tile slots t0 = m * 32 + i (h = 0) and t0 + 4 (h = 1): their offsets are those lanes' of the pass's table
+            const int t0 = m * 32 + i;
+            const uint32_t o0 = (uint32_t)__builtin_amdgcn_readlane((int)otab_prev, t0), o1 = (uint32_t)__builtin_amdgcn_readlane((int)otab_prev, t0 + 4);
+            const int vo = co * 4 + (int)(h ? o1 : o0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v0 * out_scale + bz, 0.f)), rs, vo, 0, 2 /* nt */);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(v1 * out_scale + bz, 0.f)), rs, vo + CO * 4, 0, 2);
+            return;
+        }
         if (LISTED) {
             // tiles t0 = m * 32 + i (h = 0) and t0 + 4 (h = 1): pair slot and place in the pair are compile-time, the pair's offset is the pass's
             // (all of it in the lane's offset: that is what the resource's range check looks at)
@@ -293,7 +341,8 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
         const bool draw = pass >= big_end || pass % PK == PK - 1;          // the last pass of a ticket draws the next one
         if (draw && tid == 0) s_next_pass = ticket_first((int)atomicAdd(pass_ctr, 1u) + (int)gridDim.x);   // read by everyone after the first unit's barrier
         bool have_next = false;
-        int qmin_n = qmin, nrows_n = nrows, gp0_n = gp0, span_n = span;
+        int qmin_n = qmin, nrows_n = nrows, gp0_n = gp0, span_n = span, tiles_n = tiles;
+        uint32_t otab_n = otab;
         uint32_t rel_n[L::SLOTS];
 #pragma unroll
         for (int s2 = 0; s2 < L::SLOTS; ++s2) rel_n[s2] = rel[s2];
@@ -306,7 +355,7 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                 if (have_next) wino_pass_rows<G, S>(next_pass, total_tiles, qmin_n, nrows_n);
             }
             // (without a next pass the descriptor fetched is this pass's own: the next = this one once more)
-            if (LISTED && last_u) pass_decode(qmin_n, gp0_n, span_n, rel_n);
+            if (LISTED && last_u) pass_decode(qmin_n, gp0_n, span_n, rel_n, tiles_n);
             const uint8_t* pbase = ldsb + (g & 1) * P::BUF;
             // staged under this unit: the next unit of this pass, or unit 0 of the next pass (without one: this pass's once more, into the buffer
             // nobody reads again)
@@ -368,7 +417,8 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
                     fold(g - 1, (tt - 2) / 16, (tt - 2) % 16);
                 }
                 // the next pass's A offsets, in place: kernel row ky was last read for tap 31 + 2 ky of this unit, one tap ahead
-                if (last_u && have_next && (tt == 28 || tt == 30)) a_base(next_pass, qmin_n, (tt - 28) / 2, an_in[(tt - 28) / 2], an_z[(tt - 28) / 2], an_y[(tt - 28) / 2]);
+                if (last_u && have_next && (tt == 28 || tt == 30)) a_base(next_pass, qmin_n, tiles_n, (tt - 28) / 2, an_in[(tt - 28) / 2], an_z[(tt - 28) / 2], an_y[(tt - 28) / 2]);
+                if (TS && last_u && have_next && tt == 31) otab_n = h ? toff[1] : toff[0];
                 if (last_u && have_next && (tt == 39 || (tt >= 32 && tt < 39 && !(tt & 1)))) {
                     const int ky = tt == 39 ? 4 : (tt - 32) / 2;
 #pragma unroll
@@ -389,10 +439,11 @@ __global__ __launch_bounds__(256) void k_conv5_wpair(const uint8_t* __restrict__
             __syncthreads();
         }
         ors_prev = ors;
+        otab_prev = otab; otab = otab_n;
 #pragma unroll
         for (int s2 = 0; s2 < L::SLOTS; ++s2) { rel_prev[s2] = rel[s2]; rel[s2] = rel_n[s2]; }
         if (!have_next) break;
-        pass = next_pass; qmin = qmin_n; nrows = nrows_n; gp0 = gp0_n; span = span_n;
+        pass = next_pass; qmin = qmin_n; nrows = nrows_n; gp0 = gp0_n; span = span_n; tiles = tiles_n;
     }
     // the last pass's tail has no next pass to run under (fold of unit 2 ran under unit 3; unit 3's pair is positions 0 and 7, taken by the tail itself)
 #pragma unroll

@@ -12,6 +12,7 @@ namespace trexhip {
 // the bits of TREXHIP_CONV_GEOM (a test hook; include/trexhip.h documents the values)
 enum : int {
     GEOM_FP32_ACT = 0xfff,            // bits 0-11, any of them: the fp32-activation chain
+    GEOM_PAIR_SLOTS = 1 << 20,        // the listed conv3 walks passes of pair slots (6 or 10 whole pairs), not of tile slots
     GEOM_NO_SKIP3X = 1 << 21,         // no crop gets a window of conv3 tiles
     GEOM_NO_BGROWS = 1 << 22,         // the windowed conv1+conv2 makes every V2 row, background rows too
     GEOM_NO_SKIPX = 1 << 23,          // no crop gets a window
@@ -22,7 +23,7 @@ enum : int {
     GEOM_TWO_KERNEL = 1 << 28,        // conv1 and conv2 as two kernels
     GEOM_ROLE_SPLIT = 1 << 29,        // the role-split conv1+conv2 at any batch size
     GEOM_FUSED_2WG = 1 << 30,         // the two-workgroup conv1+conv2 at any batch size
-    GEOM_MASK = GEOM_FP32_ACT | GEOM_NO_SKIP3X | GEOM_NO_BGROWS | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
+    GEOM_MASK = GEOM_FP32_ACT | GEOM_PAIR_SLOTS | GEOM_NO_SKIP3X | GEOM_NO_BGROWS | GEOM_NO_SKIPX | GEOM_DENSE_FC1 | GEOM_V3_COPY | GEOM_DENSE_CONV3 | GEOM_NO_SKIP | GEOM_TWO_KERNEL | GEOM_ROLE_SPLIT | GEOM_FUSED_2WG
 };
 
 // 80 x 80, TREXHIP_CNN_FP16X3 (the operand images V2 / V3 are written by the producing layer, cnn_wpre.h):
@@ -49,6 +50,11 @@ enum : int {
 //                             passes (6 row pairs) of the others; k_act3_fill describes both and copies the pooled columns outside the windows;
 //                             k_conv5_wpair<true, Skip3XGeom> runs on the first list in front of the full-width listed instance on the second.  Off
 //                             (GEOM_NO_SKIP3X, bit 21): no crop gets a window -- the same kernels, one list, the full-width listed instance alone
+//                 skip3t      a listed pass of either list is up to 64 CONSECUTIVE TILES of the list's pair sequence (cnn_skip3.h: Skip3TGeom,
+//                             Skip3TXGeom), begun and ended at any even tile of a pair: k_pair_count<true> / k_pair_list<true> / k_act3_fill<true>
+//                             make those lists (and still count the passes of pair slots, which the counters and the choice of the form keep
+//                             to), the instances k_conv5_wpair<true, Skip3TGeom> and <true, Skip3TXGeom> walk them.  Off (GEOM_PAIR_SLOTS, bit 20):
+//                             passes of 6 (10) whole pairs, 60 of the kernel's 64 tiles
 //                 fc1_listed  above 1024 crops: k_fc1_list beside k_pair_list, fc1 computes only the (crop, split-K plane) rows whose row pair is
 //                             listed -- the listed k_fc1_split<4>; k_head takes the other planes from the empty crop's, k_act3_fill copies no
 //                             pair.  Off (GEOM_DENSE_FC1, bit 24): the dense fc1, and the fill copies
@@ -94,6 +100,7 @@ struct CnnPlan {
     bool skip3x;                    // where skip3 and v3_direct are on: the listed pairs of the crops whose blob fits a window of 3 conv3 tiles (skip3_window) go
                                     // into windowed passes -- k_pair_count / k_pair_list make two lists, k_act3_fill describes both and copies the pooled columns
                                     // outside the windows, and k_conv5_wpair<true, Skip3XGeom> runs in front of the full-width listed instance; off: bit 21
+    bool skip3t;                    // where skip3 is on: the listed passes are 64 consecutive tiles of the list's pairs, not whole pairs; off: bit 20
     bool fc1_listed;                // where skip3 is on, fc1 is SPLIT4 and the head BIG: k_fc1_list in front of conv1+conv2, the listed k_fc1_split<4>
                                     // computes only the listed (crop, plane) rows, k_head takes the others from Net::fc1e, k_act3_fill copies nothing; off: bit 24
     bool skipx;                     // where skip is on: the crops whose blob fits a window of 8 tiles take the windowed instance of the role-split kernel
@@ -164,6 +171,7 @@ inline CnnPlan cnn_plan(const int W, const int H, const int CH, const int mode, 
         p.act3_fill = {ceil_div(n, 16), n};
         p.v3_direct = !(geom & GEOM_V3_COPY) && skip3_direct_fits((long long)n * SkipGeom::V3_ROWS);
         p.skip3x = p.v3_direct && !(geom & GEOM_NO_SKIP3X) && skip3x_direct_fits((long long)n * SkipGeom::V3_ROWS);
+        p.skip3t = !(geom & GEOM_PAIR_SLOTS) && skip3t_direct_fits((long long)n * SkipGeom::V3_ROWS);
     }
 
     const int n_pass2 = ceil_div(n * 20, W2bGeom::RPP), n_pass3 = ceil_div(n * GW::TPC, GW::MB);

@@ -229,6 +229,133 @@ TREXHIP_HD constexpr void skip3_row_words(const Skip3Pass& p, const SkipRows own
     }
 }
 
+// ---- passes of TILE slots ----
+// A pass of pair slots (above) fills 60 of the kernel's 64 tiles, and the matrix cores compute the other 4 anyway.  A pass of tile slots is up to
+// 64 CONSECUTIVE TILES of its list's pair sequence instead: it begins `o` tiles into its first pair (o even: a conv row pair's two rows alternate
+// along the tile numbering, and the kernel pools tiles 2k and 2k + 1) and may end inside its last one; a pair cut between two passes is staged by
+// both, each computes its own tiles of it.  The runs, the block and the SPAN rule are the pair-slot passes'; after an early close (a third run, SPAN)
+// the next pass begins at a pair boundary, because runs do.  Both lists are packed this way.
+//   full width (Skip3TGeom):  o = 0 .. 8, o + 64 tiles touch at most 8 pairs: 2 * 8 + 4 * 2 = 24 V3 rows (25 row slots of 5440 bytes: 133 KB of LDS)
+//   windowed (Skip3TXGeom):   o = 0 .. 4, o + 64 tiles touch 11 pairs and at o = 4 twelve: 2 * 12 + 4 * 2 = 32 V3 rows, two more than the 32-word
+//                             row table of the pair-slot passes has room for (Skip3Reach: NR < WORDS - 1), so these passes have a row
+//                             table of ROW_WORDS = 64 words, one per lane (skip3t_row_words).  33 row slots of 3264 bytes: 105 KB of LDS.
+//                             Holding a pass to the 11 pairs a 32-word table allows was counted first: the pass that begins at o = 4 then
+//                             closes at 62 tiles, and the benchmark's windowed crops -- all of 8 pairs, 48 tiles -- need four passes for five
+//                             crops, as with pair slots (8 + 2, 6 + 4, 4 + 6, 2 + 8), where 48 + 16 | 32 + 32 | 16 + 48 are three for four:
+//                             7349 windowed passes instead of 6901 on 25600 crops (profiles/conv3_tile_slots.txt).
+// The descriptor is skip3_describe's of the pairs the pass TOUCHES (SLOTS pair slots), its row words skip3_row_words' (full width) or
+// skip3t_row_words' (windowed) of them, and word S3_TILES carries o and the tile count.
+struct Skip3TGeom {
+    static constexpr int PAIRS = Skip3Geom::PAIRS, RUNS = Skip3Geom::RUNS, HALO = Skip3Geom::HALO, SPAN = Skip3Geom::SPAN, BLOCK = Skip3Geom::BLOCK;
+    static constexpr int TILES = Skip3Geom::TILES, TPP = 2 * TILES;         // tiles of a row that a pass computes (all 5); tiles per pair
+    static constexpr int MB = 64;                                           // tile slots of a pass
+    static constexpr int MAXP = (TPP - 2 + MB + TPP - 1) / TPP;             // pairs a pass can touch (8)
+    static constexpr int SLOTS = MAXP;                                      // pair slots of the descriptor
+    static constexpr int NR = SkipGeom::POOL * MAXP + 2 * HALO * RUNS;      // V3 rows a pass can stage (24)
+    static constexpr int BLOCK_PASSES = (BLOCK * PAIRS * TPP + MB - 1) / MB + BLOCK + 1;   // full passes + passes closed by a third run + the last
+    static constexpr int DESC = 16;
+    static constexpr int ROW_WORDS = 32;                                    // words of a pass's row table: Skip3Reach's
+    static_assert(MAXP == 8 && NR == 24 && S3X_DESC_OK(DESC, SLOTS), "2 + 60 + 2 tiles: 8 pairs, and the descriptor holds their slots");
+    static_assert((long long)(SPAN + SLOTS) * SkipGeom::POOL * 10240 < (1ll << 31), "V3 byte distance inside a pass");
+};
+struct Skip3TXGeom {
+    static constexpr int PAIRS = Skip3Geom::PAIRS, RUNS = Skip3Geom::RUNS, HALO = Skip3Geom::HALO, SPAN = Skip3Geom::SPAN, BLOCK = Skip3Geom::BLOCK;
+    static constexpr int WT3 = Skip3XGeom::WT3, TILES = WT3, TPP = 2 * TILES;
+    static constexpr int MB = 64;
+    static constexpr int MAXP = (TPP - 2 + MB + TPP - 1) / TPP;             // pairs a pass can touch (12: 2 + 60 + 2 tiles)
+    static constexpr int SLOTS = MAXP;
+    static constexpr int NR = SkipGeom::POOL * MAXP + 2 * HALO * RUNS;      // V3 rows a pass can stage (32)
+    static constexpr int ROW_WORDS = 64;                                    // words of a pass's row table
+    static constexpr int BLOCK_PASSES = (BLOCK * PAIRS * TPP + MB - 1) / MB + BLOCK + 1;
+    static constexpr int DESC = 32;
+    static_assert(MAXP == 12 && NR == 32 && NR < ROW_WORDS - 1, "12 pairs, and the row table holds their rows and `none`");
+    static_assert(S3X_DESC_OK(DESC, SLOTS), "the descriptor holds the slots");
+    static_assert((long long)(SPAN + SLOTS) * SkipGeom::POOL * 10240 < (1ll << 31), "V3 byte distance inside a pass");
+};
+template <class G> struct Skip3Tiled { static constexpr bool value = false; static constexpr int ROW_WORDS = 32 /* Skip3Reach::WORDS */; };
+template <> struct Skip3Tiled<Skip3TGeom> { static constexpr bool value = true; static constexpr int ROW_WORDS = Skip3TGeom::ROW_WORDS; };
+template <> struct Skip3Tiled<Skip3TXGeom> { static constexpr bool value = true; static constexpr int ROW_WORDS = Skip3TXGeom::ROW_WORDS; };
+
+// a pass of tile slots while it is filled: n tiles from `runs` runs, the first one entered o tiles into the pair gp0[0]; run r touches the pairs
+// gp0[r] .. gp0[r] + len[r] - 1 (the first of run A from tile o on, the last of the pass's last run maybe not to its end)
+struct Skip3TPass { int n, runs, o, gp0[Skip3Geom::RUNS], len[Skip3Geom::RUNS]; };
+
+// the tiles a pass that begins o tiles into a pair and has touched `pairs` pairs of earlier runs can still take of a run it enters at tile `off`
+template <class T>
+TREXHIP_HD constexpr int skip3t_room(const Skip3TPass& p, const int off) {
+    const int touched = p.runs ? p.len[0] : 0;                              // (a second run is the last: only run A is in front of the one entered)
+    const int by_pairs = (T::MAXP - touched) * T::TPP - off, by_tiles = T::MB - p.n;
+    return by_pairs < by_tiles ? by_pairs : by_tiles;
+}
+// the pairs gp .. gp + len - 1 of one crop, from tile `off` of the first on (off != 0: only into an empty pass), go into the pass being filled and
+// the passes behind it; emit(index, pass) takes every pass that closes.  A pass closes when it has no room (64 tiles, or MAXP pairs), when a
+// third run would begin, or when the next run lies more than SPAN pairs behind its first pair
+template <class T, class E>
+TREXHIP_HD constexpr void skip3t_add_run(Skip3TPass& p, int& passes, int gp, const int len, E&& emit) {
+    int left = len * T::TPP, off = 0;
+    while (left > 0) {
+        if (p.runs && (skip3t_room<T>(p, off) <= 0 || p.runs == T::RUNS || gp - p.gp0[0] > T::SPAN)) { emit(passes, p); ++passes; p = Skip3TPass{}; }
+        const int room = skip3t_room<T>(p, off), take = left < room ? left : room;
+        const int touch = (off + take + T::TPP - 1) / T::TPP;
+        if (p.runs == 0) { p.o = off; p.gp0[0] = gp; p.len[0] = touch; }    // (no index that is a variable: the pass stays in registers on the device)
+        else { p.gp0[1] = gp; p.len[1] = touch; }
+        ++p.runs; p.n += take; left -= take;
+        off += take; gp += off / T::TPP; off %= T::TPP;
+        // a run that goes on behind this pass does so in an empty one
+        if (left > 0) { emit(passes, p); ++passes; p = Skip3TPass{}; }
+    }
+}
+template <class E>
+TREXHIP_HD constexpr void skip3t_flush(Skip3TPass& p, int& passes, E&& emit) {
+    if (p.n) { emit(passes, p); ++passes; p = Skip3TPass{}; }
+}
+// the pairs a pass of tile slots touches, as a pass of pair slots: what skip3_describe and skip3_row_words take
+TREXHIP_HD constexpr Skip3Pass skip3t_pairs(const Skip3TPass& p) {
+    Skip3Pass r{};
+    r.runs = p.runs; r.gp0[0] = p.gp0[0]; r.len[0] = p.len[0];
+    r.gp0[1] = p.runs > 1 ? p.gp0[1] : 0; r.len[1] = p.runs > 1 ? p.len[1] : 0;
+    r.n = r.len[0] + r.len[1];
+    return r;
+}
+// descriptor word S3_TILES of a pass of tile slots: o | tiles << 8.  Tile slot t of the pass is tile (o + t) % TPP of pair slot (o + t) / TPP
+enum : int { S3_TILES = 6, S3_O_MASK = 0xff, S3_COUNT_SHIFT = 8 };
+template <class T>
+TREXHIP_HD constexpr void skip3t_describe(const Skip3TPass& p, int (&d)[T::DESC], const int t0a = 0, const int t0b = 0) {
+    skip3_describe<T>(skip3t_pairs(p), d, t0a, t0b);
+    d[S3_TILES] = p.o | p.n << S3_COUNT_SHIFT;
+}
+// The row words of a pass of tile slots: skip3_row_words' of the pairs it touches, in a table of T::ROW_WORDS words -- entry i < NR the source of
+// row slot 1 + i, the entries behind them none, the last one the row of the allocation the resource starts at
+template <class T>
+TREXHIP_HD constexpr void skip3t_row_words(const Skip3Pass& p /* skip3t_pairs of the pass */, const SkipRows own_a, const SkipRows own_b, const long long total,
+                                           unsigned (&w)[T::ROW_WORDS], const int t0a = 0, const int t0b = 0) {
+    using R = Skip3Reach;
+    constexpr int IMG = SkipGeom::V3_ROWS, BASE = T::ROW_WORDS - 1;
+    int src[T::NR] = {};
+    skip3_row_sources<T>(p, own_a, own_b, src);
+    const bool two = p.runs > 1;
+    const Skip3Rows a = skip3_run_rows(p.gp0[0], p.len[0]);
+    const Skip3Rows b = two ? skip3_run_rows(p.gp0[1], p.len[1]) : Skip3Rows{a.row0 + a.n, 0};
+    const long long last = b.row0 + b.n - 1;
+    bool image = false;
+    for (int i = 0; i < T::NR; ++i) image = image || (src[i] != S3_SRC_NONE && (src[i] & S3_SRC_IMAGE));
+    const bool front = image && IMG + last + 1 <= R::REACH_ROWS;
+    const long long base = front ? 0 : IMG + a.row0, back = IMG + total;
+    for (int i = 0; i < T::ROW_WORDS; ++i) {
+        const int s = i < T::NR ? src[i < T::NR ? i : 0] : S3_SRC_NONE;
+        const bool none = s == S3_SRC_NONE, img = !none && (s & S3_SRC_IMAGE);
+        const long long row = img ? (front ? 0 : back) + (s & ~S3_SRC_IMAGE) : IMG + s;
+        const unsigned off = none ? R::OFF_NONE : (unsigned)((row - base) * R::ROWB) + (unsigned)((i < a.n ? t0a : t0b) * R::TILEB);
+        w[i] = i == BASE ? (unsigned)base : off - ((unsigned)i << R::ROW_SHIFT);
+    }
+}
+// every pass of tile slots of a batch of `total` V3 rows reaches an image (skip3_direct_fits, with the pairs these passes touch)
+TREXHIP_HD constexpr bool skip3t_direct_fits(const long long total) {
+    using R = Skip3Reach;
+    return total <= 2 * R::REACH_ROWS - 2 * SkipGeom::V3_ROWS - ((Skip3TXGeom::SPAN + Skip3TXGeom::SLOTS) * SkipGeom::POOL + 2 * Skip3TXGeom::HALO) - 1;
+}
+static_assert(Skip3TGeom::NR < Skip3TGeom::ROW_WORDS - 1 && Skip3TGeom::ROW_WORDS == Skip3Reach::WORDS, "the row table holds a pass's rows and `none`");
+
 // (the words of Net::d_skip that the kernels of the listed conv3 and fc1 write and read: cnn_skip_words.h)
 
 // fc1's split-K plane s is row pair q = s of every crop (FC1_KSPLIT planes of 10 x 128 inputs), and a crop's row of an MFMA tile depends on

@@ -13,7 +13,9 @@
 //                  full-width list is the row rule's, and neither the windowed list nor the SKX_* words are touched
 //   k_pair_count   (listed conv3) listed passes per thread and passes and pairs per workgroup; a thread packs the row pairs of Skip3Geom::BLOCK
 //                  consecutive crops -- where crops can have windows of conv3 tiles (`cols` not null; skip3_window), those of the crops with one
-//                  into windowed passes (Skip3XGeom: 10 pairs), the others' into full-width passes (6 pairs), in one walk
+//                  into windowed passes (Skip3XGeom: 10 pairs), the others' into full-width passes (6 pairs), in one walk.  TILED: the lists the
+//                  kernel walks are passes of tile slots (Skip3TXGeom, Skip3TGeom: up to 64 consecutive tiles); the passes of pair slots are still
+//                  counted, by two more groups of threads, for the counters and for the choice of the form
 //   k_pair_list    the passes of both lists in order, each as its two runs, the counters, the windowed instance's ticket counter zeroed, and the
 //                  word that names the form of conv3 that runs (SK3_USE: the passes of both lists together against the dense kernel's)
 //   k_fc1_list     (listed fc1) a workgroup per split-K plane: the crops whose pair the plane has to compute, in order, and how many they are
@@ -255,23 +257,25 @@ static constexpr int SKIP3_TB = 256;      // threads per workgroup of the count 
 // The count / list kernels run SKIP3_NT = 2 SKIP3_TB threads: the first SKIP3_TB walk the full-width list of their BLOCK crops, the others -- whole
 // waves -- the windowed list of the same crops at the same time (one thread walking both lists, in one loop or in two, was 1.6 times the time of
 // these kernels, which is that loop's latency)
-static constexpr int SKIP3_NT = 2 * SKIP3_TB;
+// (TILED: four groups -- the lists of tile slots that the kernel walks, and behind them the two lists of pair slots, which are only counted)
+static constexpr int SKIP3_NT = 2 * SKIP3_TB, SKIP3_NT_TILED = 4 * SKIP3_TB;
+template <int NT>
 __device__ __forceinline__ void skip3_stage_runs(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const bool all, uint16_t* s_run) {
     using G = Skip3Geom;
     const int c0 = blockIdx.x * SKIP3_TB * G::BLOCK;
     constexpr int U = 8;              // loads in flight per thread: one after the other they are BLOCK round trips to memory
-    static_assert(G::BLOCK % U == 0 && (SKIP3_TB * G::BLOCK) % (U * SKIP3_NT) == 0, "whole groups of loads");
-    for (int i0 = threadIdx.x; i0 < SKIP3_TB * G::BLOCK; i0 += U * SKIP3_NT) {
+    static_assert(G::BLOCK % U == 0 && (SKIP3_TB * G::BLOCK) % (U * NT) == 0, "whole groups of loads");
+    for (int i0 = threadIdx.x; i0 < SKIP3_TB * G::BLOCK; i0 += U * NT) {
         int2 b[U], c[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * SKIP3_NT;
+            const int i = i0 + u * NT;
             b[u] = c0 + i < n ? bands[c0 + i] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
             c[u] = cols && c0 + i < n ? cols[c0 + i] : make_int2(SKIP_BAND_NONE.y0, SKIP_BAND_NONE.y1);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * SKIP3_NT;
+            const int i = i0 + u * NT;
             const SkipPairs r = all && c0 + i < n ? SkipPairs{0, G::PAIRS - 1} : skip3_pairs({b[u].x, b[u].y});
             const int t0 = skip3_window({c[u].x, c[u].y}, all);
             s_run[(i % G::BLOCK) * SKIP3_TB + i / G::BLOCK] = (uint16_t)(r.lo <= r.hi ? r.lo | (r.hi - r.lo + 1) << 8 | (t0 + 1) << 12 : 0);
@@ -283,8 +287,8 @@ __device__ __forceinline__ void skip3_stage_runs(const int2* __restrict__ bands,
 // packed into passes (numbered from `passes` on); emit(index, pass) takes each; crops: how many took part; -> pairs listed
 template <class G, class E>
 __device__ __forceinline__ int skip3_walk(const uint16_t* s_run, const int t, const int blk, int& passes, int& crops, E&& emit) {
-    constexpr bool WIN = G::TILES != Skip3Geom::TILES;
-    Skip3Pass p{};
+    constexpr bool WIN = G::TILES != Skip3Geom::TILES, TILED = Skip3Tiled<G>::value;
+    std::conditional_t<TILED, Skip3TPass, Skip3Pass> p{};
     int listed = 0;
 #pragma unroll 1
     for (int k = 0; k < G::BLOCK; ++k) {
@@ -292,53 +296,71 @@ __device__ __forceinline__ int skip3_walk(const uint16_t* s_run, const int t, co
         if (len && ((r >> 12) != 0) == WIN) {
             listed += len;
             ++crops;
-            skip3_add_run<G>(p, passes, (blk * G::BLOCK + k) * G::PAIRS + (r & 0xff), len, emit);
+            const int gp = (blk * G::BLOCK + k) * G::PAIRS + (r & 0xff);
+            if constexpr (TILED) skip3t_add_run<G>(p, passes, gp, len, emit);
+            else skip3_add_run<G>(p, passes, gp, len, emit);
         }
     }
-    skip3_flush(p, passes, emit);
+    if constexpr (TILED) skip3t_flush(p, passes, emit);
+    else skip3_flush(p, passes, emit);
     return listed;
 }
 
 // (cols null: no crop has a window, one list, as before there were windows; the second half of the workgroup has nothing to walk)
-__global__ __launch_bounds__(SKIP3_NT) void k_pair_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const uint32_t* __restrict__ words,
+// (counts: [0 .. grid) of the lists the kernel walks; [grid .. 2 grid) the passes of pair slots, full-width and windowed -- the same numbers
+// where the kernel walks those)
+template <bool TILED>
+__global__ __launch_bounds__(TILED ? SKIP3_NT_TILED : SKIP3_NT) void k_pair_count(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, const uint32_t* __restrict__ words,
                                                          uint4* __restrict__ counts /* per workgroup: full-width passes, pairs, windowed passes, windowed crops */,
                                                          uint32_t* __restrict__ tcounts /* per block of crops: full-width passes, windowed passes */) {
-    __shared__ uint32_t s_pass, s_pair, s_wpass, s_wcrop;
+    __shared__ uint32_t s_pass, s_pair, s_wpass, s_wcrop, s_ppass, s_pwpass;
     __shared__ uint16_t s_run[SKIP3_TB * Skip3Geom::BLOCK];
-    if (threadIdx.x == 0) { s_pass = 0; s_pair = 0; s_wpass = 0; s_wcrop = 0; }
-    skip3_stage_runs(bands, cols, n, words[SK_EMPTY_RANGE] != 0, s_run);
-    const bool win = threadIdx.x >= SKIP3_TB;                 // (whole waves)
+    if (threadIdx.x == 0) { s_pass = 0; s_pair = 0; s_wpass = 0; s_wcrop = 0; s_ppass = 0; s_pwpass = 0; }
+    skip3_stage_runs<TILED ? SKIP3_NT_TILED : SKIP3_NT>(bands, cols, n, words[SK_EMPTY_RANGE] != 0, s_run);
+    const int grp = threadIdx.x / SKIP3_TB;                   // (whole waves)
+    const bool win = grp & 1;
     const int t = threadIdx.x & (SKIP3_TB - 1), blk = blockIdx.x * SKIP3_TB + t;
     if (blk * Skip3Geom::BLOCK < n) {
         int passes = 0, crops = 0, listed = 0;
-        if (!win) listed = skip3_walk<Skip3Geom>(s_run, t, blk, passes, crops, [](int, const Skip3Pass&) {});
-        else if (cols) listed = skip3_walk<Skip3XGeom>(s_run, t, blk, passes, crops, [](int, const Skip3Pass&) {});
-        tcounts[2 * blk + (win ? 1 : 0)] = (uint32_t)passes;
-        if (passes) atomicAdd(win ? &s_wpass : &s_pass, (uint32_t)passes);
-        if (listed) atomicAdd(&s_pair, (uint32_t)listed);
-        if (win && crops) atomicAdd(&s_wcrop, (uint32_t)crops);
+        const auto none = [](int, const auto&) {};
+        if (grp >= 2) {                                       // TILED only: the passes of pair slots, counted
+            if (!win) skip3_walk<Skip3Geom>(s_run, t, blk, passes, crops, none);
+            else if (cols) skip3_walk<Skip3XGeom>(s_run, t, blk, passes, crops, none);
+            if (passes) atomicAdd(win ? &s_pwpass : &s_ppass, (uint32_t)passes);
+        } else {
+            if (!win) listed = skip3_walk<std::conditional_t<TILED, Skip3TGeom, Skip3Geom>>(s_run, t, blk, passes, crops, none);
+            else if (cols) listed = skip3_walk<std::conditional_t<TILED, Skip3TXGeom, Skip3XGeom>>(s_run, t, blk, passes, crops, none);
+            tcounts[2 * blk + (win ? 1 : 0)] = (uint32_t)passes;
+            if (passes) atomicAdd(win ? &s_wpass : &s_pass, (uint32_t)passes);
+            if (listed) atomicAdd(&s_pair, (uint32_t)listed);
+            if (win && crops) atomicAdd(&s_wcrop, (uint32_t)crops);
+        }
     }
     __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = make_uint4(s_pass, s_pair, s_wpass, s_wcrop);
+    if (threadIdx.x == 0) {
+        counts[blockIdx.x] = make_uint4(s_pass, s_pair, s_wpass, s_wcrop);
+        counts[gridDim.x + blockIdx.x] = TILED ? make_uint4(s_ppass, s_pwpass, 0, 0) : make_uint4(s_pass, s_wpass, 0, 0);
+    }
 }
 
+template <bool TILED>
 __global__ __launch_bounds__(SKIP3_NT) void k_pair_list(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, uint32_t* __restrict__ words,
                                                         const uint4* __restrict__ counts, const uint32_t* __restrict__ tcounts, int* __restrict__ desc,
-                                                        int* __restrict__ xdesc /* the windowed passes, Skip3XGeom::DESC words each */) {
-    using G = Skip3Geom;
-    using X = Skip3XGeom;
+                                                        int* __restrict__ xdesc /* the windowed passes, Skip3XGeom::DESC words each, either form */) {
+    using G = std::conditional_t<TILED, Skip3TGeom, Skip3Geom>;
+    using X = std::conditional_t<TILED, Skip3TXGeom, Skip3XGeom>;
     __shared__ uint2 s_scan[SKIP3_TB];
     __shared__ uint16_t s_run[SKIP3_TB * G::BLOCK];
     const int tid = threadIdx.x, t = tid & (SKIP3_TB - 1), blk = blockIdx.x * SKIP3_TB + t;
     const bool win = tid >= SKIP3_TB;                         // (whole waves)
     const bool mine = blk * G::BLOCK < n;
-    skip3_stage_runs(bands, cols, n, words[SK_EMPTY_RANGE] != 0, s_run);
+    skip3_stage_runs<SKIP3_NT>(bands, cols, n, words[SK_EMPTY_RANGE] != 0, s_run);
     // the passes in front of this workgroup (all of them, and the pairs: the last workgroup writes the counters)
-    uint32_t before = 0, wbefore = 0, pairs = 0, wcrops = 0;
+    uint32_t before = 0, wbefore = 0, pairs = 0, wcrops = 0, ppasses = 0, pwpasses = 0;
     for (int b = 0; b <= (int)blockIdx.x; ++b) {
-        const uint4 c = counts[b];
+        const uint4 c = counts[b], pc = counts[gridDim.x + b];
         if (b < (int)blockIdx.x) { before += c.x; wbefore += c.z; }
-        pairs += c.y; wcrops += c.w;
+        pairs += c.y; wcrops += c.w; ppasses += pc.x; pwpasses += pc.y;
     }
     const uint2 cnt = mine ? make_uint2(tcounts[2 * blk], tcounts[2 * blk + 1]) : make_uint2(0, 0);
     if (!win) s_scan[t] = cnt;
@@ -350,22 +372,26 @@ __global__ __launch_bounds__(SKIP3_NT) void k_pair_list(const int2* __restrict__
         __syncthreads();
     }
     int at = win ? (int)(wbefore + s_scan[t].y - cnt.y) : (int)(before + s_scan[t].x - cnt.x), crops = 0;
-    // (the pass as its runs, in the first words of its descriptor: k_act3_fill makes the descriptor of it, a thread per pass)
+    // (the pass as its runs, in the first words of its descriptor: k_act3_fill makes the descriptor of it, a thread per pass; TILED: o and the
+    // tile count beside run A's pairs, as in word S3_TILES, 8 bits further up)
+    const auto runs_of = [](const auto& p) {
+        int la = p.len[0];
+        if constexpr (std::is_same_v<std::decay_t<decltype(p)>, Skip3TPass>) la |= (p.o | p.n << S3_COUNT_SHIFT) << 8;
+        return make_int4(p.gp0[0], la, p.gp0[1], p.runs > 1 ? p.len[1] : 0);
+    };
     if (mine && !win)
-        skip3_walk<G>(s_run, t, blk, at, crops, [&](const int idx, const Skip3Pass& p) {
-            *reinterpret_cast<int4*>(desc + (size_t)idx * G::DESC) = make_int4(p.gp0[0], p.len[0], p.gp0[1], p.runs > 1 ? p.len[1] : 0);
-        });
+        skip3_walk<G>(s_run, t, blk, at, crops, [&](const int idx, const auto& p) { *reinterpret_cast<int4*>(desc + (size_t)idx * G::DESC) = runs_of(p); });
     if (mine && win && cols)
-        skip3_walk<X>(s_run, t, blk, at, crops, [&](const int idx, const Skip3Pass& p) {
-            *reinterpret_cast<int4*>(xdesc + (size_t)idx * X::DESC) = make_int4(p.gp0[0], p.len[0], p.gp0[1], p.runs > 1 ? p.len[1] : 0);
-        });
+        skip3_walk<X>(s_run, t, blk, at, crops, [&](const int idx, const auto& p) { *reinterpret_cast<int4*>(xdesc + (size_t)idx * X::DESC) = runs_of(p); });
     if (blockIdx.x == gridDim.x - 1 && tid == SKIP3_TB - 1) {
         const uint32_t listed = before + s_scan[t].x, wlisted = wbefore + s_scan[t].y;
         const long long dense = ((long long)n * (G::PAIRS * 10) + 63) / 64;      // the dense form's passes: 64 of the crop's 100 tiles each
-        words[SK3_PAIRS] = (uint32_t)(n * G::PAIRS); words[SK3_LISTED] = pairs; words[SK3_PASSES] = listed; words[SK3_FILLED] = 0;
-        words[SK3X_PASSES] = wlisted; words[SK3X_CROPS] = wcrops; words[SK3X_CTR] = 0;
+        // (the counters and the choice stay those of the passes of pair slots, whichever lists the kernel walks: SK3_RAN, SK3X_RAN)
+        words[SK3_PAIRS] = (uint32_t)(n * G::PAIRS); words[SK3_LISTED] = pairs; words[SK3_PASSES] = ppasses; words[SK3_FILLED] = 0;
+        words[SK3X_PASSES] = pwpasses; words[SK3X_CROPS] = wcrops; words[SK3X_CTR] = 0;
+        words[SK3_RAN] = listed; words[SK3X_RAN] = wlisted;
         // (a windowed pass is counted as a full-width one: 117.6 against 116.2 ns under a kernel trace, profiles/conv3_windowed.txt)
-        words[SK3_USE] = skip3_use_list((long long)listed + wlisted, dense) ? 1u : 0u;
+        words[SK3_USE] = skip3_use_list((long long)ppasses + pwpasses, dense) ? 1u : 0u;
     }
 }
 
@@ -428,17 +454,27 @@ static constexpr int SKIP3_FC = 16;
 // cols (null: no crop has a window): the windowed passes' descriptors and row sources as well (xdesc, xrows), and of every LISTED pair of a crop
 // with a window the pooled columns outside it <- the empty crop's: the windowed kernel does not write them, and fc1 -- listed or not -- reads
 // whole pairs.  These are not counted: SK3_FILLED is the row rule's
+template <bool TILED>
 __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ bands, const int2* __restrict__ cols, const int n, uint32_t* __restrict__ words,
                                                    const uint4* __restrict__ act3e, uint4* __restrict__ act3, int* __restrict__ desc,
                                                    uint32_t* __restrict__ rows /* Skip3Reach::WORDS per pass */,
-                                                   int* __restrict__ xdesc, uint32_t* __restrict__ xrows,
+                                                   int* __restrict__ xdesc, uint32_t* __restrict__ xrows /* TILED: Skip3TXGeom::ROW_WORDS per pass */,
                                                    const long long alloc_rows /* V3 rows in front of the back image */, const int direct,
                                                    const int copy /* 0: the listed fc1 runs and reads no unlisted pair -- they are counted, not copied */) {
-    using G = Skip3Geom;
+    using G = std::conditional_t<TILED, Skip3TGeom, Skip3Geom>;
     constexpr int PQ = 10 * 128 * 4 / 16;             // 16-byte units per pair
-    using X = Skip3XGeom;
+    using X = std::conditional_t<TILED, Skip3TXGeom, Skip3XGeom>;
     constexpr int CQ = 128 * 4 / 16;                  // 16-byte units per pooled column of a pair
-    static_assert((Skip3Geom::BLOCK_PASSES + X::BLOCK_PASSES) * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass of either list: 256 threads per SKIP3_FC crops");
+    static_assert((G::BLOCK_PASSES + X::BLOCK_PASSES) * SKIP3_FC <= Skip3Geom::BLOCK * 256 && SKIP3_FC % 4 == 0, "a thread per pass of either list: 256 threads per SKIP3_FC crops");
+    // the runs k_pair_list left -> the pass as its pairs, and o | tiles << 8 (TILED)
+    const auto pass_of = [](const int4 r, int& tiles) {
+        Skip3Pass p{};
+        const int la = TILED ? r.y & 0xff : r.y;
+        tiles = TILED ? r.y >> 8 : 0;
+        p.runs = r.w ? 2 : 1; p.n = la + r.w;
+        p.gp0[0] = r.x; p.len[0] = la; p.gp0[1] = r.z; p.len[1] = r.w;
+        return p;
+    };
     __shared__ uint32_t s_filled;
     const int lane = threadIdx.x & 63;
     if (!words[SK3_USE]) return;
@@ -446,43 +482,47 @@ __global__ __launch_bounds__(256) void k_act3_fill(const int2* __restrict__ band
     __syncthreads();
     const bool all = words[SK_EMPTY_RANGE] != 0;
     const int gid = blockIdx.x * 256 + threadIdx.x;
-    const int n_full = (int)words[SK3_PASSES], n_win = cols ? (int)words[SK3X_PASSES] : 0;
+    const int n_full = (int)words[SK3_RAN], n_win = cols ? (int)words[SK3X_RAN] : 0;
     const SkipRows every{0, SkipGeom::V3_ROWS - 1};
     const bool from_v3 = all || !direct;
     if (gid >= n_full && gid - n_full < n_win) {          // a windowed pass: the same, with its crops' windows
         int4* dst = reinterpret_cast<int4*>(xdesc + (size_t)(gid - n_full) * X::DESC);
         const int4 r = dst[0];
-        Skip3Pass p{};
-        p.runs = r.w ? 2 : 1; p.n = r.y + r.w;
-        p.gp0[0] = r.x; p.len[0] = r.y; p.gp0[1] = r.z; p.len[1] = r.w;
+        int tiles;
+        const Skip3Pass p = pass_of(r, tiles);
         const int ca = r.x / X::PAIRS, cb = (r.w ? r.z : r.x) / X::PAIRS;
         const int2 xa = cols[ca], xb = cols[cb];
         const int t0a = skip3_window({xa.x, xa.y}, all), t0b = skip3_window({xb.x, xb.y}, all);
         int d[X::DESC];
         skip3_describe<X>(p, d, t0a, t0b);
+        if (TILED) d[S3_TILES] = tiles;
 #pragma unroll
         for (int k = 0; k < X::DESC / 4; ++k) dst[k] = make_int4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
         const int2 ba = bands[ca], bb = bands[cb];
-        unsigned w[Skip3Reach::WORDS];
-        skip3_row_words<X>(p, from_v3 ? every : skip_rows({ba.x, ba.y}), from_v3 ? every : skip_rows({bb.x, bb.y}), alloc_rows, w, t0a, t0b);
-        uint4* wd = reinterpret_cast<uint4*>(xrows + (size_t)(gid - n_full) * Skip3Reach::WORDS);
+        // (TILED: a windowed pass can stage 32 rows, and its row table is one of 64 words)
+        constexpr int XW = TILED ? Skip3TXGeom::ROW_WORDS : Skip3Reach::WORDS;
+        unsigned w[XW];
+        const SkipRows oa = from_v3 ? every : skip_rows({ba.x, ba.y}), ob = from_v3 ? every : skip_rows({bb.x, bb.y});
+        if constexpr (TILED) skip3t_row_words<X>(p, oa, ob, alloc_rows, w, t0a, t0b);
+        else skip3_row_words<X>(p, oa, ob, alloc_rows, w, t0a, t0b);
+        uint4* wd = reinterpret_cast<uint4*>(xrows + (size_t)(gid - n_full) * XW);
 #pragma unroll
-        for (int k = 0; k < Skip3Reach::WORDS / 4; ++k) wd[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+        for (int k = 0; k < XW / 4; ++k) wd[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
     }
     if (gid < n_full) {
         int4* dst = reinterpret_cast<int4*>(desc + (size_t)gid * G::DESC);
         const int4 r = dst[0];
-        Skip3Pass p{};
-        p.runs = r.w ? 2 : 1; p.n = r.y + r.w;
-        p.gp0[0] = r.x; p.len[0] = r.y; p.gp0[1] = r.z; p.len[1] = r.w;
+        int tiles;
+        const Skip3Pass p = pass_of(r, tiles);
         int d[G::DESC];
-        skip3_describe(p, d);
+        skip3_describe<G>(p, d);
+        if (TILED) d[S3_TILES] = tiles;
 #pragma unroll
         for (int k = 0; k < G::DESC / 4; ++k) dst[k] = make_int4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
         // where its rows come from: the own rows of its crops from V3, the others from the image -- or all of them from V3, where the copy is kept
         const int2 ba = bands[r.x / G::PAIRS], bb = bands[(r.w ? r.z : r.x) / G::PAIRS];
         unsigned w[Skip3Reach::WORDS];
-        skip3_row_words(p, from_v3 ? every : skip_rows({ba.x, ba.y}), from_v3 ? every : skip_rows({bb.x, bb.y}), alloc_rows, w);
+        skip3_row_words<G>(p, from_v3 ? every : skip_rows({ba.x, ba.y}), from_v3 ? every : skip_rows({bb.x, bb.y}), alloc_rows, w);
         uint4* wd = reinterpret_cast<uint4*>(rows + (size_t)gid * Skip3Reach::WORDS);
 #pragma unroll
         for (int k = 0; k < Skip3Reach::WORDS / 4; ++k) wd[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);

@@ -33,8 +33,12 @@ enum : int {
     SKX_CTR = 29,            // the windowed instance's ticket counter (zeroed by k_pass_list)
     SKX_V2_READ = 30,        // V2 rows the last call's windowed passes read as new rows, a crop's passes counted as one run (cnn_skipx.h: skipx_v2_rows)
     SKX_V2_MADE = 31,        // ... and how many of them the producers made: the others are background rows.  Both 0 where background rows are made
-    SK_WORDS = 32
+    // what the listed instances of k_conv5_wpair walk (cnn_skip3.h): passes of tile slots, or -- TREXHIP_CONV_GEOM bit 20 -- the passes of pair slots
+    // that SK3_PASSES and SK3X_PASSES count either way (the counters of the stats calls, and what the choice of SK3_USE is made on)
+    SK3_RAN = 32,            // the length of the full-width listed instance's list
+    SK3X_RAN = 33,           // the length of the windowed listed instance's list
+    SK_WORDS = 34
 };
-static_assert(SK_FILLED < SK3X_CROPS && SK3X_CTR < SK3_PAIRS && SK3_LAST < SKX_CROPS && SKX_V2_MADE < SK_WORDS, "no word twice, the last one inside the table");
+static_assert(SK_FILLED < SK3X_CROPS && SK3X_CTR < SK3_PAIRS && SK3_LAST < SKX_CROPS && SKX_V2_MADE < SK3_RAN && SK3X_RAN < SK_WORDS, "no word twice, the last one inside the table");
 
 }  // namespace trexhip
